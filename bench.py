@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ORB kfeatures/sec, extract + match (BASELINE.json metric), on 1..N MI355X of one node.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload euroc|kitti|tumvi]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload euroc|kitti|tumvi] [--dump-outputs DIR]
 
 A "step" = one pass of the hot path over one batch of synthetic frames of ONE camera sequence per GPU:
   euroc (default, the metric's configuration): 256 frames 752x480, nFeatures=1000 -- extract (pyramid, FAST, quad-tree,
@@ -574,6 +574,49 @@ def base_line(R, metric, value, dt_max, extra_cfg):
             "dtype": "u8", "data": "synthetic", "config": extra_cfg, "process_group": R.group, "per_rank": getattr(R, "per_rank", None)}
 
 
+# ---------------------------------------------------------------------------------------------------------
+# --dump-outputs DIR: what the last step of a timed region delivered to the host, as float32 / float64 .npy files, so that two builds can
+# be compared output for output (the inputs of a workload are the same from run to run for the same arguments)
+# ---------------------------------------------------------------------------------------------------------
+DUMP_LIMIT = 64 << 20   # bytes in all; above it a fixed, seeded sample of the step's frames is written
+
+
+def dump_frames(n_frames, bound_per_frame, limit=DUMP_LIMIT):
+    """Frames of the step to dump, ascending: all of them, or -- when n_frames x bound_per_frame (the most a frame can take, from the
+    extractor's output capacity) exceeds the limit -- a sample drawn with a fixed seed, so that it depends on the arguments alone."""
+    if n_frames * bound_per_frame <= limit:
+        return np.arange(n_frames)
+    m = max(1, limit // bound_per_frame)
+    return np.sort(np.random.default_rng(0).permutation(n_frames)[:m])
+
+
+def kp_table(raw):
+    """(n, 28) uint8 keypoint records (orbx_keypoint) -> (n, 7) float32 columns x, y, size, angle, response, octave, class_id (exact)."""
+    from orb_slam3_amd import KP_DTYPE
+    k = np.ascontiguousarray(raw).view(KP_DTYPE).reshape(-1)
+    return np.stack([k[c].astype(np.float32) for c in KP_DTYPE.names], axis=1)
+
+
+def save_dump(out_dir, arrays):
+    """Writes DIR/<name>.npy for every array (float32 or float64 only); returns the block the JSON line reports."""
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {"dir": os.path.abspath(out_dir), "files": sorted(arrays), "bytes": int(total), "frames": int(len(arrays["frame_index"]))}
+
+
+def feature_arrays(keep, kps, desc, cnt, mono, suffix=""):
+    """keypoints / descriptors (float32 rows, the frames' features in frame order) and per-frame counts / monoIndex of the frames in keep."""
+    n = [int(cnt[f]) for f in keep]
+    return {"keypoints" + suffix: np.concatenate([kp_table(kps[f, :c].numpy()) for f, c in zip(keep, n)]),
+            "descriptors" + suffix: np.concatenate([desc[f, :c].numpy().astype(np.float32) for f, c in zip(keep, n)]),
+            "keypoint_count" + suffix: np.array(n, np.float64),
+            "mono_index" + suffix: np.array([int(mono[f]) for f in keep], np.float64)}
+
+
 STAMPS = []          # host time at which every step's results had arrived (appended by the run loops, cut per region by region_gaps)
 
 
@@ -794,7 +837,10 @@ def bench_euroc(R):
     host_enqueue = [0.0]   # seconds the host thread spent issuing work (HIP API calls through the C ABI), per timed region
 
     def timed(from_host):
-        t0 = R.timed_begin([ex], warm=lambda: run(max(a.warmup, 1), from_host))
+        def warm():
+            step_no[0] = 0   # the rotation starts at set 0 with the warm-up however many settle steps ran: the region's inputs follow from W and K alone
+            run(max(a.warmup, 1), from_host)
+        t0 = R.timed_begin([ex], warm=warm)
         STAMPS.clear()
         host_enqueue[0] = 0.0
         feats = run(a.steps, from_host)
@@ -830,6 +876,16 @@ def bench_euroc(R):
     parity_all = R.gather_objects(parity)
     for pr, pc in zip(per_rank, parity_all):
         pr["parity_checked"] = pc
+    # ---- --dump-outputs: rank 0's delivered step, copied before the later regions reuse the host buffers ----
+    dump = None
+    if a.dump_outputs and R.rank == 0:
+        keep = dump_frames(B, cap * (28 + 32 * 4 + 4) + 64)
+        arrays = dict(frame_index=keep.astype(np.float64), **feature_arrays(keep, last.kps, last.desc, last.cnt, last.mono))
+        mk = keep[keep >= 1]   # the matcher's frame f >= 1 against frame f-1 of the batch; frame 0 has no match vector
+        arrays["match_frame_index"] = mk.astype(np.float64)
+        arrays["matches"] = np.concatenate([last.match[f, :int(last.cnt[f])].numpy().astype(np.float32) for f in mk] or [np.zeros(0, np.float32)])
+        arrays["match_count"] = np.array([int(last.nm[f]) for f in mk], np.float64)
+        dump = dict(save_dump(a.dump_outputs, arrays), input_set=last_set[0], of_frames=B)
 
     # ---- the K timed steps again, `repeat` regions in all (each between its own barriers): spread of the number above ----
     regions = [(dt_max, feats_all)]
@@ -928,7 +984,7 @@ def bench_euroc(R):
         out["metric"] = "DIAGNOSTIC, NOT A RESULT (parts of the step left out: " + ",".join(sorted(ablate)) + "): " + out["metric"]
     out.update({"roofline": roofline, "cpu_baseline": cpu, "pcie_inclusive": pcie, "parity_checked": parity, "kernels": kernels,
                 "host_enqueue_ms_per_step": round(enqueue_ms, 3), "settle_ms_per_step": round(settle_ms, 3),
-                "repeats": repeats, "latency": latency, "other_workloads": others, "input_sets": NS, "single_input_set": single,
+                "repeats": repeats, "latency": latency, "other_workloads": others, "input_sets": NS, "single_input_set": single, "dump_outputs": dump,
                 "value_device_resident": round(feats_all / dt_max / 1e3, 2), "value_pcie_inclusive": pcie["value"],
                 "metric_definition_note": "TWO clocks, both in this line.  `value` (= value_device_resident) = features delivered to pinned host memory "
                                           "per second with the input frames already resident in HBM when the timed region starts: the bench contract "
@@ -1366,6 +1422,15 @@ def bench_kitti(R):
     last = sets[(a.steps - 1) % 2]
     host, h_ur, h_depth, h_nm = last.cam, last.ur, last.depth, last.nm   # the last step's results: what the parity check reads
     R.per_rank = per_rank
+    dump = None
+    if a.dump_outputs and R.rank == 0:   # every region processes the same pairs: the last region's final step is the first region's
+        keep = dump_frames(B, cap * (2 * (28 + 32 * 4) + 2 * 4) + 64)
+        arrays = dict(frame_index=keep.astype(np.float64), **feature_arrays(keep, *host["l"], suffix="_left"), **feature_arrays(keep, *host["r"], suffix="_right"))
+        nl = [int(host["l"][2][f]) for f in keep]   # mvuRight / mvDepth: one value per left keypoint
+        arrays["u_right"] = np.concatenate([h_ur[f, :c].numpy() for f, c in zip(keep, nl)])
+        arrays["depth"] = np.concatenate([h_depth[f, :c].numpy() for f, c in zip(keep, nl)])
+        arrays["stereo_match_count"] = np.array([int(h_nm[f]) for f in keep], np.float64)
+        dump = dict(save_dump(a.dump_outputs, arrays), of_frames=B)
 
     parity = None
     if R.rank == 0 and a.verify > 0:
@@ -1427,7 +1492,8 @@ def bench_kitti(R):
                      "pairs_per_step_per_gpu": B, "sequences": R.world, "features_per_pair": round(feats / a.steps / B, 1),
                      "stereo_matches_per_pair": round(float(h_nm.sum()) / B, 1)})
     out["data"] = data
-    out.update({"roofline": roofline, "cpu_baseline": cpu, "parity_checked": parity, "kernels": kernels, "repeats": repeats_block(regions, a.steps, gaps)})
+    out.update({"roofline": roofline, "cpu_baseline": cpu, "parity_checked": parity, "kernels": kernels, "repeats": repeats_block(regions, a.steps, gaps),
+                "dump_outputs": dump})
     R.finish(out)
 
 
@@ -1527,6 +1593,13 @@ def bench_tumvi(R):
     R.per_rank = per_rank
     host_enqueue[0] = enq
     last = hs[(a.steps - 1) % 2]
+    dump = None
+    if a.dump_outputs and R.rank == 0:
+        keep = dump_frames(B, cap * (28 + 32 * 4 + 4) + 64)
+        arrays = dict(frame_index=keep.astype(np.float64), **feature_arrays(keep, last["kps"], last["desc"], last["cnt"], last["mono"]))
+        arrays["matches"] = np.concatenate([last["match"][f, :int(last["cnt"][f])].numpy().astype(np.float32) for f in keep])   # map-point index or -1
+        arrays["match_count"] = np.array([int(last["nm"][f]) for f in keep], np.float64)
+        dump = dict(save_dump(a.dump_outputs, arrays), of_frames=B)
 
     parity = None
     if R.rank == 0 and a.verify > 0:
@@ -1582,7 +1655,7 @@ def bench_tumvi(R):
                      "map_point_matches_per_frame": round(float(last["nm"].sum()) / B, 1)})
     out["data"] = data
     out.update({"roofline": roofline, "cpu_baseline": cpu, "parity_checked": parity, "kernels": kernels,
-                "host_enqueue_ms_per_step": round(host_enqueue[0] / a.steps * 1e3, 3), "repeats": repeats_block(regions, a.steps, gaps)})
+                "host_enqueue_ms_per_step": round(host_enqueue[0] / a.steps * 1e3, 3), "repeats": repeats_block(regions, a.steps, gaps), "dump_outputs": dump})
     R.finish(out)
 
 
@@ -1696,6 +1769,9 @@ def main():
     ap.add_argument("--threads", action="store_true",
                     help="SURVEY.md 8(e) as ONE process: --gpus N host worker threads (thread s on GPU s mod the visible GPUs), each with its own extractor "
                          "and pinned ring, instead of N rank processes; euroc workload, device-resident clock, parity of every thread's last step")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="write what the last step of a timed region delivered (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB "
+                         "(a fixed, seeded sample of the step's frames above that); `dump_outputs` in the line lists the files")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.other_workloads is None:
@@ -1703,6 +1779,8 @@ def main():
     if args.pmc_child:
         return pmc_child(args)
     if args.threads:
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs is not supported with --threads")
         return bench_threads(args)
 
     if "WORLD_SIZE" not in os.environ:
