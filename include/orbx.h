@@ -312,6 +312,39 @@ int orbx_search_by_projection_window(orbx_matcher *m, const orbx_frame_desc *fra
                                      const int32_t *q_max_level, const float *q_angle, const uint8_t *q_desc,
                                      const uint8_t *q_has_obs, float max_dist, int check_orientation, int32_t *match);
 
+/* ---- device-resident frame handle ----
+ * In the reference one Frame is built once (ExtractORB -> UndistortKeyPoints -> AssignFeaturesToGrid, Frame.cc:311-367) and then searched by three
+ * to five matcher calls (Tracking.cc:2886,2894,3377,3413).  An orbx_frame keeps such a frame on the device across calls: undistorted keypoints,
+ * descriptors, optional mvuRight, the count, the scale factors and the 64x48 grid, in buffers of its own for `cap` features.
+ * It belongs to the matcher that created it (its device, its stream): every load and every use is ordered on that stream, and a handle passed to
+ * another matcher is refused with ORBX_E_BAD_ARG.  Destroy the handles of a matcher before the matcher.
+ *   orbx_frame_create: cap <= ORBX_MAX_FRAME_FEATURES (ORBX_E_TOO_LARGE otherwise).  A new handle holds an empty frame.
+ *   orbx_frame_load_host: uploads the frame once (desc->n <= cap) and builds the grid.  Returns without waiting for the upload.
+ *   orbx_frame_load_batch: frame `frame` of the extractor's last batch (orbx_batch_view: d_keypoints_un, d_descriptors, d_count); bounds4 =
+ *     {mnMinX, mnMaxX, mnMinY, mnMaxY} (NULL: the extractor's camera / image rectangle), scale_factors[nlevels] (NULL: the extractor's).
+ *     Asynchronous: the matcher's stream waits for the extraction, no host synchronisation, nothing passes through host memory.  The handle
+ *     holds a COPY: the extractor's next batch waits for it, and later extract calls do not change what the handle holds.  ORBX_E_BAD_ARG when
+ *     the frame index is not one of the batch, `ex` is on another device, or the batch's per-frame capacity exceeds `cap`.  No mvuRight.
+ *   orbx_frame_count: N, synchronising the matcher's stream once if the count is still on the device (cached until the next load).
+ * Checks that fail return before anything is enqueued. */
+typedef struct orbx_frame orbx_frame;
+int orbx_frame_create(orbx_matcher *m, int cap, orbx_frame **out);
+void orbx_frame_destroy(orbx_frame *f);
+int orbx_frame_load_host(orbx_frame *f, const orbx_frame_desc *desc);
+int orbx_frame_load_batch(orbx_frame *f, orbx_extractor *ex, int frame, const float *bounds4, const float *scale_factors, int nlevels);
+int orbx_frame_count(orbx_frame *f, int *n);
+/* Handle forms of the two projection matchers: arguments, outputs and results of orbx_search_by_projection_mappoints /
+ * orbx_search_by_projection_frame with the resident frame in place of the orbx_frame_desc; frame_match / cur_match hold N entries.
+ * The occupancy mask (N entries, may be NULL) comes from the host on every call.  Results equal the host-pointer forms' bit for bit. */
+int orbx_frame_search_by_projection_mappoints(orbx_matcher *m, orbx_frame *frame, const uint8_t *frame_occupied, int n_mp, const float *proj_x,
+                                              const float *proj_y, const float *proj_xr, const int32_t *pred_level, const float *view_cos,
+                                              const uint8_t *mp_desc, const uint8_t *mp_in_view, const uint8_t *mp_has_obs, float th, float nnratio,
+                                              int32_t *frame_match);
+int orbx_frame_search_by_projection_frame(orbx_matcher *m, orbx_frame *cur, const uint8_t *cur_occupied, int n_q, const float *q_u, const float *q_v,
+                                          const float *q_ur, const int32_t *q_octave, const float *q_angle, const uint8_t *q_desc,
+                                          const uint8_t *q_has_obs, float th, int level_mode, int check_orientation, int32_t *cur_match);
+/* orbx_frame_search_local_points: below, after orbx_camera / orbx_frame_pose. */
+
 /* ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (ORBmatcher.cc:648-763).
  * prev_matched: n1 (x, y) pairs, updated in place (:757-760).  matches12[i1] = index in F2 or -1. */
 int orbx_search_for_initialization(orbx_matcher *m, const orbx_keypoint *kps1_un, const uint8_t *desc1, int n1,
@@ -476,6 +509,18 @@ int orbx_is_in_frustum(orbx_matcher *m, const orbx_camera *cam, const orbx_frame
                        int nlevels, float viewing_cos_limit, int n_mp, const float *pos, const float *normal, const float *min_dist,
                        const float *max_dist, uint8_t *in_view, float *proj_x, float *proj_y, float *proj_xr, float *depth, int32_t *level,
                        float *view_cos);
+/* Tracking::SearchLocalPoints (Tracking.cc:3339-3413) on a resident frame in one call with one synchronisation: Frame::isInFrustum (Frame.cc:512-575,
+ * mono or rectified stereo, as orbx_is_in_frustum with the frame's bounds and levels) of every map point, then SearchByProjection(F, vpMapPoints, th,
+ * bFarPoints, thFarPoints) (ORBmatcher.cc:43-213, Nleft == -1).  Map points flat: pos / normal (3 floats each), min_dist / max_dist, 32-byte
+ * descriptors, eligible[j] = !isBad() && mnLastFrameSeen != F.mnId (NULL = all), has_obs[j] = Observations() > 0 (NULL = all).  A map point is
+ * searched iff eligible, in view, its predicted level one of the frame's and not (far_points && depth > th_far_points).  Outputs: in_view[n_mp]
+ * (mbTrackInView of the eligible points: the caller's IncreaseVisible), frame_match[N] as orbx_search_by_projection_mappoints.  The projection
+ * records never leave the device.  Returns nmatches. */
+int orbx_frame_search_local_points(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_camera *cam, const orbx_frame_pose *pose,
+                                   float log_scale_factor, float viewing_cos_limit, int n_mp, const float *pos, const float *normal,
+                                   const float *min_dist, const float *max_dist, const uint8_t *mp_desc, const uint8_t *eligible,
+                                   const uint8_t *has_obs, float th, float nnratio, int far_points, float th_far_points, uint8_t *in_view,
+                                   int32_t *frame_match);
 /* One camera of a fisheye rig as Frame::isInFrustumChecks (Frame.cc:1168-1240) sees it.  The caller evaluates the reference's expressions (:1172-1186):
  * left camera R = mRcw, t = mtcw, twc = mOw; right camera (bRight) R = Rrl * mRcw, t = Rrl * mtcw + trl, twc = mRwc * mTlr.translation() + mOw.
  * params = KannalaBrandt8::mvParameters (fx, fy, cx, cy, k0 .. k3). */

@@ -112,6 +112,8 @@ SYMBOLS = [
     "orbx_search_for_initialization", "orbx_search_by_bow_frame", "orbx_search_by_bow_keyframes",
     "orbx_search_for_triangulation", "orbx_search_for_triangulation_pinhole", "orbx_search_for_triangulation_kb8", "orbx_debug_kb8_epipolar", "orbx_stereo_batch_device", "orbx_stereo_batch_download", "orbx_stereo_batch_download_all", "orbx_stereo_batch_download_async", "orbx_stereo_download_wait", "orbx_search_mappoints_batch_device", "orbx_vocabulary_create",
     "orbx_vocabulary_destroy", "orbx_bow_transform", "orbx_distinctive_descriptors", "orbx_fuse_search",
+    "orbx_frame_create", "orbx_frame_destroy", "orbx_frame_load_host", "orbx_frame_load_batch", "orbx_frame_count",
+    "orbx_frame_search_by_projection_mappoints", "orbx_frame_search_by_projection_frame", "orbx_frame_search_local_points",
 ]
 
 
@@ -204,6 +206,16 @@ def lib() -> C.CDLL:
     L.orbx_search_for_triangulation_pinhole.argtypes = [vp, vp, vp, i32, fvp, vp, vp, i32, fvp, i32, C.POINTER(PinholeGate), vp]
     L.orbx_search_for_triangulation_kb8.argtypes = [vp, vp, vp, i32, fvp, vp, vp, i32, fvp, i32, C.POINTER(Kb8GateStruct), vp]
     L.orbx_debug_kb8_epipolar.argtypes = [vp, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.orbx_frame_create.argtypes = [vp, i32, C.POINTER(vp)]
+    L.orbx_frame_destroy.argtypes = [vp]
+    L.orbx_frame_destroy.restype = None
+    L.orbx_frame_load_host.argtypes = [vp, C.POINTER(FrameDesc)]
+    L.orbx_frame_load_batch.argtypes = [vp, vp, i32, vp, vp, i32]
+    L.orbx_frame_count.argtypes = [vp, C.POINTER(i32)]
+    L.orbx_frame_search_by_projection_mappoints.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp]
+    L.orbx_frame_search_by_projection_frame.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, i32, i32, vp]
+    L.orbx_frame_search_local_points.argtypes = [vp, vp, vp, C.POINTER(Camera), C.POINTER(FramePose), f32, f32, i32, vp, vp, vp, vp, vp, vp, vp,
+                                                 f32, f32, i32, f32, vp, vp]
     _lib = L
     return L
 

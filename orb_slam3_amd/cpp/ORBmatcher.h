@@ -44,6 +44,39 @@ struct MapPointBatch {
     int size() const { return (int)mTrackProjX.size(); }
 };
 
+class ORBmatcher;
+
+// A Frame resident on the device across matcher calls (orbx_frame, include/orbx.h): built once per Frame -- load() after UndistortKeyPoints, or
+// loadBatch() from an extractor's resident batch -- and passed to the SearchByProjection / SearchLocalPoints overloads below in place of a
+// FrameView.  It belongs to the ORBmatcher it was created with and must not outlive it.
+class DeviceFrame {
+public:
+    DeviceFrame(ORBmatcher &matcher, int cap);
+    ~DeviceFrame() { orbx_frame_destroy(f_); }
+    DeviceFrame(const DeviceFrame &) = delete;
+    DeviceFrame &operator=(const DeviceFrame &) = delete;
+    void load(const FrameView &F) {
+        orbx_frame_desc fd = F.c();
+        check(orbx_frame_load_host(f_, &fd), "orbx_frame_load_host");
+    }
+    // frame `frame` of the extractor's last batch; bounds4 / scaleFactors NULL = the extractor's
+    void loadBatch(orbx_extractor *ex, int frame, const float *bounds4 = nullptr, const float *scaleFactors = nullptr, int nlevels = 0) {
+        check(orbx_frame_load_batch(f_, ex, frame, bounds4, scaleFactors, nlevels), "orbx_frame_load_batch");
+    }
+    int count() {
+        int n = 0;
+        check(orbx_frame_count(f_, &n), "orbx_frame_count");
+        return n;
+    }
+    orbx_frame *handle() const { return f_; }
+
+private:
+    static void check(int st, const char *what) {
+        if (st < 0) throw std::runtime_error(std::string(what) + ": " + orbx_status_string(st) + " " + orbx_last_error());
+    }
+    orbx_frame *f_ = nullptr;
+};
+
 class ORBmatcher {
 public:
     static const int TH_LOW = ORBX_TH_LOW;
@@ -103,6 +136,52 @@ public:
             q.hasObservations.empty() ? nullptr : q.hasObservations.data(), th, mode, mbCheckOrientation ? 1 : 0, vpMatch.data());
         if (r < 0) throw std::runtime_error(std::string("orbx_search_by_projection_frame: ") + orbx_status_string(r));
         return r;   // vpMatch[i]: query index, -1 = untouched, -2 = assigned then cleared by the rotation check (slot becomes NULL)
+    }
+
+    // The same two matchers on a resident frame (DeviceFrame): nothing of the frame travels, its grid is built already
+    int SearchByProjection(DeviceFrame &F, const std::vector<uint8_t> &occupied, const MapPointBatch &mps, float th, std::vector<int32_t> &vpMatch) {
+        vpMatch.assign(F.count(), -1);
+        const int r = orbx_frame_search_by_projection_mappoints(
+            m_, F.handle(), occupied.empty() ? nullptr : occupied.data(), mps.size(), mps.mTrackProjX.data(), mps.mTrackProjY.data(),
+            mps.mTrackProjXR.empty() ? nullptr : mps.mTrackProjXR.data(), mps.mnTrackScaleLevel.data(), mps.mTrackViewCos.data(),
+            mps.descriptors.data(), mps.inView.empty() ? nullptr : mps.inView.data(),
+            mps.hasObservations.empty() ? nullptr : mps.hasObservations.data(), th, mfNNratio, vpMatch.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_by_projection_mappoints: ") + orbx_status_string(r));
+        return r;
+    }
+    int SearchByProjection(DeviceFrame &Cur, const std::vector<uint8_t> &occupied, const ProjectedQueries &q, float th, bool bForward, bool bBackward,
+                           std::vector<int32_t> &vpMatch) {
+        vpMatch.assign(Cur.count(), -1);
+        const int mode = bForward ? 1 : (bBackward ? 2 : 0);
+        const int r = orbx_frame_search_by_projection_frame(
+            m_, Cur.handle(), occupied.empty() ? nullptr : occupied.data(), (int)q.u.size(), q.u.data(), q.v.data(),
+            q.ur.empty() ? nullptr : q.ur.data(), q.octave.data(), q.angle.data(), q.descriptors.data(),
+            q.hasObservations.empty() ? nullptr : q.hasObservations.data(), th, mode, mbCheckOrientation ? 1 : 0, vpMatch.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_by_projection_frame: ") + orbx_status_string(r));
+        return r;
+    }
+
+    // Tracking::SearchLocalPoints (Tracking.cc:3339-3413) on a resident frame: isInFrustum of every local map point and
+    // SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) in one call.  eligible[j] = !isBad() && mnLastFrameSeen != F.mnId,
+    // hasObservations[j] = Observations() > 0 (empty = all).  inView[j] = mbTrackInView (for IncreaseVisible); vpMatch[i] = map point of feature i or -1.
+    struct LocalMapPoints {
+        std::vector<float> pos, normal;             // 3 floats each: GetWorldPos(), GetNormal()
+        std::vector<float> minDistance, maxDistance; // GetMinDistanceInvariance / GetMaxDistanceInvariance inputs (mfMinDistance, mfMaxDistance)
+        std::vector<uint8_t> descriptors;            // n x 32
+        std::vector<uint8_t> eligible, hasObservations;
+        int size() const { return (int)minDistance.size(); }
+    };
+    int SearchLocalPoints(DeviceFrame &F, const std::vector<uint8_t> &occupied, const orbx_camera &cam, const orbx_frame_pose &pose, float logScaleFactor,
+                          float viewingCosLimit, const LocalMapPoints &mps, float th, bool bFarPoints, float thFarPoints, std::vector<uint8_t> &inView,
+                          std::vector<int32_t> &vpMatch) {
+        inView.assign(mps.size(), 0);
+        vpMatch.assign(F.count(), -1);
+        const int r = orbx_frame_search_local_points(
+            m_, F.handle(), occupied.empty() ? nullptr : occupied.data(), &cam, &pose, logScaleFactor, viewingCosLimit, mps.size(), mps.pos.data(),
+            mps.normal.data(), mps.minDistance.data(), mps.maxDistance.data(), mps.descriptors.data(), mps.eligible.empty() ? nullptr : mps.eligible.data(),
+            mps.hasObservations.empty() ? nullptr : mps.hasObservations.data(), th, mfNNratio, bFarPoints ? 1 : 0, thFarPoints, inView.data(), vpMatch.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_local_points: ") + orbx_status_string(r));
+        return r;
     }
 
     // SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, const set<MapPoint*> &sAlreadyFound, th, ORBdist)
@@ -334,6 +413,10 @@ protected:
 // TemplatedVocabulary::transform(features, BowVector&, FeatureVector&, levelsup) (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1151-1193)
 // as called from Frame::ComputeBoW (Frame.cc:462-470) / KeyFrame::ComputeBoW: per feature the word id and the node id `levelsup`
 // levels above the leaf; the caller folds them into BowVector (addWeight) and FeatureVector (addFeature) in feature order.
+inline DeviceFrame::DeviceFrame(ORBmatcher &matcher, int cap) {
+    check(orbx_frame_create(matcher.handle(), cap, &f_), "orbx_frame_create");
+}
+
 class ORBVocabularyDevice {
 public:
     ORBVocabularyDevice(int L, const std::vector<int32_t> &childPtr, const std::vector<int32_t> &childIdx, const std::vector<uint8_t> &nodeDesc,

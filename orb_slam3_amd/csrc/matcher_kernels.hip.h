@@ -811,13 +811,10 @@ constexpr int kGridCells = 64 * 48;
 // round trip per 64 features and pass, a 64-step shuffle loop per chunk for the rank inside a cell) took 51 us per 256 frames, this one
 // 25 us (round 3, profiles/r03_a_chain_grid2_dpp_kernel_stats.csv).
 // grid (n_problems), block 64
-__global__ __launch_bounds__(64) void k_grid_build(const WindowProblem *__restrict__ probs, GridParams g) {
-    __shared__ uint16_t cnt[kGridCells];
-    __shared__ uint16_t start[kGridCells];
-    __shared__ uint32_t claim[kGridCells];
-    const WindowProblem P = probs[blockIdx.x];
+// The body is shared with k_frame_prepare (the resident frame of orbx_frame): one wave, LDS cnt / start / claim [kGridCells] from the caller.
+__device__ __forceinline__ void grid_build_wave(const orbx_keypoint *kps, int n, uint16_t *gstart, uint16_t *gorder, const GridParams &g,
+                                                uint16_t *cnt, uint16_t *start, uint32_t *claim) {
     const int lane = threadIdx.x;
-    const int n = gld(P.n_ptr);   // (gld / gst: the record's pointers are device memory, see above)
     for (int i = lane; i < kGridCells; i += 64) { cnt[i] = 0; claim[i] = 0xffffffffu; }
     __syncthreads();
     auto cell_of = [&](float x, float y) -> int {   // PosInGrid (Frame.cc:725-735); -1 = outside the grid
@@ -832,7 +829,7 @@ __global__ __launch_bounds__(64) void k_grid_build(const WindowProblem *__restri
         for (int k = 0; k < 8; k++) {
             const int i = i0 + 64 * k + lane;
             xy[k] = float2{-1e8f, -1e8f};   // (outside every grid; small enough that the float -> int conversion of its cell is defined)
-            if (i < n) { xy[k].x = gld(&P.kps[i].x); xy[k].y = gld(&P.kps[i].y); }
+            if (i < n) { xy[k].x = gld(&kps[i].x); xy[k].y = gld(&kps[i].y); }
         }
 #pragma unroll
         for (int k = 0; k < 8; k++) {
@@ -854,10 +851,10 @@ __global__ __launch_bounds__(64) void k_grid_build(const WindowProblem *__restri
     for (int k = 0; k < kGridCells / 64; k++) {
         const int c = lane * (kGridCells / 64) + k;
         start[c] = (uint16_t)run;
-        gst(P.gstart + c, (uint16_t)run);
+        gst(gstart + c, (uint16_t)run);
         run += cnt[c];
     }
-    if (lane == 63) gst(P.gstart + kGridCells, (uint16_t)run);
+    if (lane == 63) gst(gstart + kGridCells, (uint16_t)run);
     __syncthreads();
     // pass 2: stable fill, 64 features at a time in index order (eight chunks loaded per round trip)
     for (int i0 = 0; i0 < n; i0 += 8 * 64) {
@@ -866,7 +863,7 @@ __global__ __launch_bounds__(64) void k_grid_build(const WindowProblem *__restri
         for (int k = 0; k < 8; k++) {
             const int i = i0 + 64 * k + lane;
             xy[k] = float2{-1e8f, -1e8f};   // (outside every grid; small enough that the float -> int conversion of its cell is defined)
-            if (i < n) { xy[k].x = gld(&P.kps[i].x); xy[k].y = gld(&P.kps[i].y); }
+            if (i < n) { xy[k].x = gld(&kps[i].x); xy[k].y = gld(&kps[i].y); }
         }
 #pragma unroll
         for (int k = 0; k < 8; k++) {
@@ -879,7 +876,7 @@ __global__ __launch_bounds__(64) void k_grid_build(const WindowProblem *__restri
                 const bool won = todo && claim[c] == (uint32_t)lane;
                 one_wave_sync();
                 if (won) {
-                    gst(P.gorder + start[c], (uint16_t)i);
+                    gst(gorder + start[c], (uint16_t)i);
                     start[c] = (uint16_t)(start[c] + 1);
                     claim[c] = 0xffffffffu;
                     todo = false;
@@ -888,6 +885,56 @@ __global__ __launch_bounds__(64) void k_grid_build(const WindowProblem *__restri
             }
         }
     }
+}
+
+__global__ __launch_bounds__(64) void k_grid_build(const WindowProblem *__restrict__ probs, GridParams g) {
+    __shared__ uint16_t cnt[kGridCells];
+    __shared__ uint16_t start[kGridCells];
+    __shared__ uint32_t claim[kGridCells];
+    const WindowProblem P = probs[blockIdx.x];
+    grid_build_wave(P.kps, gld(P.n_ptr), P.gstart, P.gorder, g, cnt, start, claim);   // (gld / gst: the record's pointers are device memory, see above)
+}
+
+// The resident frame of an orbx_frame handle (Frame::ExtractORB -> UndistortKeyPoints -> AssignFeaturesToGrid, Frame.cc:311-367, done ONCE per
+// frame and read by every projection matcher of it): the rows of one frame are copied into the handle's own buffers and its 64x48 grid is built
+// with the count read from device memory -- the host never needs N to enqueue.  src_kps == NULL: the rows are in place already (orbx_frame_load_host
+// uploaded them), only the grid is built.  The grid is grid_build_wave's, i.e. k_grid_build's order (cell x, cell y, index): the window kernels'
+// candidate order, and with it every tie, is the host-pointer forms'.
+constexpr int kFrameMaxLevels = 32;
+struct FramePrepare {
+    const orbx_keypoint *src_kps;   // rows to copy (NULL: in place)
+    const uint8_t *src_desc;
+    const int32_t *src_count;       // device count of the source rows (NULL: n_host)
+    int n_host;
+    orbx_keypoint *kps;             // the handle's buffers [cap]
+    uint8_t *desc;
+    int32_t *count;
+    float *scale;                   // [nlevels] <- scale_host (mvScaleFactors, read by the window setup of orbx_frame_search_local_points)
+    uint16_t *gstart, *gorder;
+    int cap, nlevels;
+    float scale_host[kFrameMaxLevels];
+};
+// grid (1 + ceil(copied rows / 256)), block 64: block 0 writes the count and the scale factors and builds the grid from the SOURCE rows (it does not
+// wait for the copy), block b >= 1 copies rows [256 (b-1), 256 b)
+__global__ __launch_bounds__(64) void k_frame_prepare(const FramePrepare F, GridParams g) {
+    __shared__ uint16_t cnt[kGridCells];
+    __shared__ uint16_t start[kGridCells];
+    __shared__ uint32_t claim[kGridCells];
+    const int n = max(0, min(F.src_count ? gld(F.src_count) : F.n_host, F.cap));
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0) gst(F.count, (int32_t)n);
+        if (threadIdx.x < F.nlevels) gst(F.scale + threadIdx.x, F.scale_host[threadIdx.x]);
+        grid_build_wave(F.src_kps ? F.src_kps : F.kps, n, F.gstart, F.gorder, g, cnt, start, claim);
+        return;
+    }
+    const int i0 = (blockIdx.x - 1) * 256, i1 = min(i0 + 256, n);
+    if (!F.src_kps || i0 >= i1) return;
+    const uint32_t *sk = reinterpret_cast<const uint32_t *>(F.src_kps);   // 28-byte rows: 7 dwords each
+    uint32_t *dk = reinterpret_cast<uint32_t *>(F.kps);
+    for (int w = i0 * 7 + (int)threadIdx.x; w < i1 * 7; w += 64) dk[w] = sk[w];
+    const uint4 *sd = reinterpret_cast<const uint4 *>(F.src_desc);       // 32-byte rows: 2 x 16 bytes
+    uint4 *dd = reinterpret_cast<uint4 *>(F.desc);
+    for (int w = i0 * 2 + (int)threadIdx.x; w < i1 * 2; w += 64) dd[w] = sd[w];
 }
 
 // Search windows of SearchByProjection(Frame, MapPoints) (ORBmatcher.cc:53-72) for every (frame, map point) of a batch:
@@ -909,6 +956,30 @@ __global__ __launch_bounds__(256) void k_mappoint_windows(int n_mp, const int32_
     qmin[k] = lvl - 1;
     qmax[k] = lvl;
     qvalid[k] = ok ? 1 : 0;
+}
+
+// Search windows of Tracking::SearchLocalPoints (Tracking.cc:3339-3413) on one resident frame, straight from k_in_frustum's outputs: the map point
+// is searched iff the caller flags it eligible (!isBad() && mnLastFrameSeen != F.mnId), isInFrustum put it in view, its predicted level is one of
+// the frame's and it is not a far point (bFarPoints && mTrackDepth > thFarPoints, ORBmatcher.cc:48-52); r = RadiusByViewingCos(viewCos) [* th if th
+// != 1] * mvScaleFactors[nPredictedLevel], levels [level-1, level] (:53-72).  Rounds as the host loop of orbx_search_by_projection_mappoints does.
+// in_view_out = mbTrackInView as the caller's IncreaseVisible reads it (isInFrustum's flag of the eligible points).  grid ceil(n_mp/256), block 256
+__global__ __launch_bounds__(256) void k_local_windows(int n_mp, const uint8_t *__restrict__ in_view, const uint8_t *__restrict__ eligible,
+                                                       const int32_t *__restrict__ level, const float *__restrict__ view_cos,
+                                                       const float *__restrict__ depth, const float *__restrict__ scale, int nlevels, float th,
+                                                       int far_points, float th_far_points, float *__restrict__ qr, int32_t *__restrict__ qmin,
+                                                       int32_t *__restrict__ qmax, uint8_t *__restrict__ qvalid, uint8_t *__restrict__ in_view_out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_mp) return;
+    const bool iv = in_view[i] && (!eligible || eligible[i]);
+    const int lvl = iv ? level[i] : -1;   // (level, view_cos and depth are written for points in view only)
+    const bool ok = iv && lvl >= 0 && lvl < nlevels && !(far_points && depth[i] > th_far_points);
+    float r = (ok && (double)view_cos[i] > 0.998) ? 2.5f : 4.0f;   // :146 RadiusByViewingCos: float against the double literal
+    if (th != 1.0f) r = __fmul_rn(r, th);
+    qr[i] = ok ? __fmul_rn(r, scale[lvl]) : 0.f;
+    qmin[i] = lvl - 1;
+    qmax[i] = lvl;
+    qvalid[i] = ok ? 1 : 0;
+    in_view_out[i] = iv ? 1 : 0;
 }
 
 // candidate key of the grid scan: dist << 32 | seq << 16 | idx, seq = position in the reference's candidate enumeration

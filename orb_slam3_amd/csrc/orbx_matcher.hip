@@ -539,6 +539,59 @@ int orbx_compute_stereo_matches(orbx_matcher *m, const orbx_keypoint *kl, const 
 
 }  // extern "C"
 
+// A frame resident on the device across matcher calls (include/orbx.h, orbx_frame): keypoints, descriptors, optional mvuRight, the count, the
+// scale factors and the 64x48 grid in buffers of its own -- not in the matcher's per-call arena, which begin() hands out again on every call.
+// Every load and every use is enqueued on the owner's stream, so a load is ordered behind the calls that read the previous contents.
+struct orbx_frame {
+    orbx_matcher *owner = nullptr;
+    int cap = 0;
+    uint8_t *dev = nullptr;           // one allocation, carved below
+    orbx_keypoint *kps = nullptr;
+    uint8_t *desc = nullptr;
+    float *u_right = nullptr, *scale = nullptr;
+    int32_t *count = nullptr;
+    uint16_t *gstart = nullptr, *gorder = nullptr;
+    uint8_t *stage = nullptr;         // pinned (device-visible) staging of orbx_frame_load_host: the rows at the device layout's offsets
+    size_t stage_bytes = 0;
+    int32_t *h_count = nullptr;       // pinned: orbx_frame_count's download
+    hipEvent_t ev_src = nullptr;      // load_batch: the extractor's stream up to the batch
+    hipEvent_t ev_done = nullptr;     // load_batch: the copy has run (the extractor's next batch waits for it); load_host: the staging is free again
+    bool stage_busy = false;
+    bool loaded = false, has_ur = false, n_known = false;
+    int n = 0, nlevels = 0;
+    std::vector<float> scale_h;       // mvScaleFactors on the host (the projection matchers' host-side window setup)
+    float bounds[4] = {0, 0, 0, 0};
+    std::vector<int32_t> h_match;     // [cap]: results of a call made while N was still on the device
+    size_t off_kps = 0, off_desc = 0, off_ur = 0, off_count = 0, off_scale = 0, off_gstart = 0, off_gorder = 0;
+};
+
+namespace {
+
+inline GridParams grid_of(const float *b) {
+    GridParams g;
+    g.minx = b[0]; g.miny = b[2];
+    g.inv_w = 64.0f / (b[1] - b[0]);  // Frame.cc:342-343
+    g.inv_h = 48.0f / (b[3] - b[2]);
+    return g;
+}
+
+// N of a handle: cached, else one download of the device count (and a synchronisation of the owner's stream)
+int frame_count(orbx_frame *f, int *n) {
+    if (!f->n_known) {
+        orbx_matcher *m = f->owner;
+        ORBX_HIP(hipSetDevice(m->device));
+        ORBX_HIP(hipMemcpyAsync(f->h_count, f->count, 4, hipMemcpyDeviceToHost, m->stream));
+        ORBX_HIP(hipStreamSynchronize(m->stream));
+        m->dirty = false;
+        f->n = *f->h_count;
+        f->n_known = true;
+    }
+    *n = f->n;
+    return ORBX_OK;
+}
+
+}  // namespace
+
 namespace {
 
 // shared driver of the two projection matchers (host-pointer form)
@@ -557,16 +610,21 @@ struct ProjArgs {
     float max_dist;
 };
 
-int run_projection(orbx_matcher *m, const ProjArgs &a) {
+// fh != NULL: the handle form -- the frame's rows and grid are resident (a.frame is not read); while its N is still on the device (a load_batch
+// nobody has counted yet) every per-feature buffer is sized by the handle's capacity and the count comes back with the results
+int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr) {
     const orbx_frame_desc *F = a.frame;
-    const int n = F->n, nq = a.nq;
+    const int nq = a.nq;
+    int n = fh ? -1 : F->n;
+    if (fh && (fh->n_known || a.occupied || nq == 0)) { const int rc = frame_count(fh, &n); if (rc != ORBX_OK) return rc; }   // the mask holds N entries
     for (int i = 0; i < n; i++) a.match_out[i] = -1;
     if (n == 0 || nq == 0) return 0;
-    if (n > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;  // before anything is enqueued: the resolve pass keeps 10 B per feature in LDS
+    const int nc = n >= 0 ? n : fh->cap;   // features the device buffers are sized for
+    if (nc > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;  // before anything is enqueued: the resolve pass keeps 10 B per feature in LDS
     ORBX_HIP(hipSetDevice(m->device));
-    size_t need = Arena::pad(28 * (size_t)n) + Arena::pad(32 * (size_t)n) + 3 * Arena::pad((size_t)n) + Arena::pad(4 * (size_t)n) * 2 +
+    size_t need = Arena::pad(28 * (size_t)nc) + Arena::pad(32 * (size_t)nc) + 3 * Arena::pad((size_t)nc) + Arena::pad(4 * (size_t)nc) * 2 +
                   Arena::pad(4 * (size_t)nq) * 7 + Arena::pad(32 * (size_t)nq) + Arena::pad((size_t)nq) * 2 + Arena::pad(8 * (size_t)nq) * 5 +
-                  Arena::pad(sizeof(WindowProblem)) + Arena::pad(sizeof(ResolveProblem)) + Arena::pad(2 * (kGridCells + 1)) + Arena::pad(2 * (size_t)n) +
+                  Arena::pad(sizeof(WindowProblem)) + Arena::pad(sizeof(ResolveProblem)) + Arena::pad(2 * (kGridCells + 1)) + Arena::pad(2 * (size_t)nc) +
                   16 * 256 + 4096;
     int r = m->reserve_all(need);
     if (r != ORBX_OK) return r;
@@ -576,15 +634,21 @@ int run_projection(orbx_matcher *m, const ProjArgs &a) {
     memset(&P, 0, sizeof(P));
     ResolveProblem R;
     memset(&R, 0, sizeof(R));
-    orbx_keypoint *dk = A.take<orbx_keypoint>(n);
-    uint8_t *dd = A.take<uint8_t>(32 * (size_t)n);
-    H2D(dk, F->keypoints_un, 28 * (size_t)n); H2D(dd, F->descriptors, 32 * (size_t)n);
-    P.kps = dk; P.desc = dd;
+    if (fh) {   // resident rows: nothing of the frame travels
+        P.kps = fh->kps; P.desc = fh->desc;
+    } else {
+        orbx_keypoint *dk = A.take<orbx_keypoint>(n);
+        uint8_t *dd = A.take<uint8_t>(32 * (size_t)n);
+        H2D(dk, F->keypoints_un, 28 * (size_t)n); H2D(dd, F->descriptors, 32 * (size_t)n);
+        P.kps = dk; P.desc = dd;
+    }
     int32_t *dcnt = A.take<int32_t>(4);
     const int32_t cnts[2] = {n, nq};
     H2D(dcnt, cnts, 8);
-    P.n_ptr = dcnt; P.nq_ptr = dcnt + 1;
-    if (F->u_right) { float *p = A.take<float>(n); H2D(p, F->u_right, 4 * (size_t)n); P.u_right = p; }
+    P.n_ptr = fh ? fh->count : dcnt; P.nq_ptr = dcnt + 1;
+    const bool has_ur = fh ? fh->has_ur : F->u_right != nullptr;
+    if (fh && has_ur) P.u_right = fh->u_right;
+    else if (has_ur) { float *p = A.take<float>(n); H2D(p, F->u_right, 4 * (size_t)n); P.u_right = p; }
     if (a.occupied) { uint8_t *p = A.take<uint8_t>(n); H2D(p, a.occupied, (size_t)n); P.occupied0 = p; }
     float *f3[3]; const float *h3[3] = {a.qx, a.qy, a.qr};
     for (int k = 0; k < 3; k++) { f3[k] = A.take<float>(nq); H2D(f3[k], h3[k], 4 * (size_t)nq); }
@@ -592,7 +656,7 @@ int run_projection(orbx_matcher *m, const ProjArgs &a) {
     int32_t *i2[2]; const int32_t *hi2[2] = {a.qmin, a.qmax};
     for (int k = 0; k < 2; k++) { i2[k] = A.take<int32_t>(nq); H2D(i2[k], hi2[k], 4 * (size_t)nq); }
     P.qmin = i2[0]; P.qmax = i2[1];
-    if (a.qxr && F->u_right) { float *p = A.take<float>(nq); H2D(p, a.qxr, 4 * (size_t)nq); P.qxr = p; }
+    if (a.qxr && has_ur) { float *p = A.take<float>(nq); H2D(p, a.qxr, 4 * (size_t)nq); P.qxr = p; }
     { uint8_t *p = A.take<uint8_t>(32 * (size_t)nq); H2D(p, a.qdesc, 32 * (size_t)nq); P.qdesc = p; }
     if (a.qvalid) { uint8_t *p = A.take<uint8_t>(nq); H2D(p, a.qvalid, (size_t)nq); P.qvalid = p; }
     R.mode = a.mode; R.nnratio = a.nnratio; R.check_orientation = a.check_orientation; R.max_dist = a.max_dist;
@@ -604,29 +668,39 @@ int run_projection(orbx_matcher *m, const ProjArgs &a) {
     WindowProblem *dP = A.take<WindowProblem>(1);
     ResolveProblem *dR = A.take<ResolveProblem>(1);
     P.keys = A.take<u64>((size_t)nq * kTopK); P.meta = A.take<int32_t>(nq);
-    P.gstart = A.take<uint16_t>(kGridCells + 1); P.gorder = A.take<uint16_t>(n);
+    if (fh) { P.gstart = fh->gstart; P.gorder = fh->gorder; }
+    else { P.gstart = A.take<uint16_t>(kGridCells + 1); P.gorder = A.take<uint16_t>(n); }
     R.entries = A.take<int32_t>(nq);
-    R.match = A.take<int32_t>(n);
+    R.match = A.take<int32_t>(nc);
     R.nmatches = A.take<int32_t>(1);
-    // a small problem skips the grid: k_window_brute walks all features per query (no k_grid_build launch, whose counting sort this one call would use once)
-    const bool brute = m->brute_windows && (size_t)nq * (size_t)n <= kBruteMaxPairs;
+    // a small problem skips the grid: k_window_brute walks all features per query (no k_grid_build launch, whose counting sort this one call would use once);
+    // a handle's grid is built already
+    const bool brute = !fh && m->brute_windows && (size_t)nq * (size_t)n <= kBruteMaxPairs;
     if (brute) { P.gstart = nullptr; P.gorder = nullptr; }
     H2D(dP, &P, sizeof(P)); H2D(dR, &R, sizeof(R));
-    GridParams g;
-    g.minx = F->min_x; g.miny = F->min_y;
-    g.inv_w = 64.0f / (F->max_x - F->min_x);  // Frame.cc:342-343
-    g.inv_h = 48.0f / (F->max_y - F->min_y);
+    const float fb[4] = {fh ? fh->bounds[0] : F->min_x, fh ? fh->bounds[1] : F->max_x, fh ? fh->bounds[2] : F->min_y, fh ? fh->bounds[3] : F->max_y};
+    const GridParams g = grid_of(fb);
     if (brute) {
         hipLaunchKernelGGL(k_window_brute, dim3((nq + 3) / 4), dim3(256), 0, m->exec(), dP, g);
     } else {
-        ORBX_LAUNCH_GRID_BUILD( dim3(1), dim3(64), 0, m->exec(), dP, g);
+        if (!fh) ORBX_LAUNCH_GRID_BUILD( dim3(1), dim3(64), 0, m->exec(), dP, g);
         ORBX_LAUNCH_WINDOW_BEST2(nq, 1, m->exec(), dP, g);
     }
-    { const int rr = brute ? launch_resolve<true>(1, m->exec(), dP, dR, g, n, nq, 4) : launch_resolve<false>(1, m->exec(), dP, dR, g, n, nq, 4); if (rr != ORBX_OK) return rr; }
+    { const int rr = brute ? launch_resolve<true>(1, m->exec(), dP, dR, g, nc, nq, 4) : launch_resolve<false>(1, m->exec(), dP, dR, g, nc, nq, 4); if (rr != ORBX_OK) return rr; }
     int32_t nm = 0;
-    D2H(a.match_out, R.match, 4 * (size_t)n);
+    if (n >= 0) {
+        D2H(a.match_out, R.match, 4 * (size_t)n);
+    } else {   // N comes back with the results (one small copy of the handle's count)
+        fh->h_match.resize((size_t)fh->cap);
+        D2H(fh->h_match.data(), R.match, 4 * (size_t)nc);
+        D2H(&fh->n, fh->count, 4);
+    }
     D2H(&nm, R.nmatches, 4);
     SYNC_AND_DELIVER();
+    if (n < 0) {
+        fh->n_known = true;
+        memcpy(a.match_out, fh->h_match.data(), 4 * (size_t)std::max(fh->n, 0));
+    }
     return nm;
 }
 
@@ -634,11 +708,10 @@ int run_projection(orbx_matcher *m, const ProjArgs &a) {
 
 extern "C" {
 
-int orbx_search_by_projection_mappoints(orbx_matcher *m, const orbx_frame_desc *frame, const uint8_t *frame_occupied, int n_mp,
-                                        const float *proj_x, const float *proj_y, const float *proj_xr,
-                                        const int32_t *pred_level, const float *view_cos, const uint8_t *mp_desc,
-                                        const uint8_t *mp_in_view, const uint8_t *mp_has_obs, float th, float nnratio,
-                                        int32_t *frame_match) {
+static int search_mappoints_impl(orbx_matcher *m, const orbx_frame_desc *frame, orbx_frame *fh, const uint8_t *frame_occupied, int n_mp,
+                                 const float *proj_x, const float *proj_y, const float *proj_xr, const int32_t *pred_level, const float *view_cos,
+                                 const uint8_t *mp_desc, const uint8_t *mp_in_view, const uint8_t *mp_has_obs, float th, float nnratio,
+                                 int32_t *frame_match) {
     if (!m || !frame || frame->n < 0 || (!frame_match && frame->n > 0) || n_mp < 0) return ORBX_E_BAD_ARG;   // empty frames / query sets are legal
     if (n_mp > 0 && (!proj_x || !proj_y || !pred_level || !view_cos || !mp_desc)) return ORBX_E_BAD_ARG;
     // per-query window: r = RadiusByViewingCos(viewCos) [* th] * scale[level], levels [lvl-1, lvl]  (ORBmatcher.cc:63-72)
@@ -656,13 +729,21 @@ int orbx_search_by_projection_mappoints(orbx_matcher *m, const orbx_frame_desc *
     }
     ProjArgs a = {frame, frame_occupied, n_mp, proj_x, proj_y, qr.data(), proj_xr, qmin.data(), qmax.data(), mp_desc, valid.data(),
                   mp_has_obs, nullptr, 1, nnratio, 0, frame_match, (float)ORBX_TH_HIGH};
-    return run_projection(m, a);
+    return run_projection(m, a, fh);
 }
 
-int orbx_search_by_projection_frame(orbx_matcher *m, const orbx_frame_desc *cur, const uint8_t *cur_occupied, int n_q,
-                                    const float *q_u, const float *q_v, const float *q_ur, const int32_t *q_octave,
-                                    const float *q_angle, const uint8_t *q_desc, const uint8_t *q_has_obs, float th, int level_mode,
-                                    int check_orientation, int32_t *cur_match) {
+int orbx_search_by_projection_mappoints(orbx_matcher *m, const orbx_frame_desc *frame, const uint8_t *frame_occupied, int n_mp,
+                                        const float *proj_x, const float *proj_y, const float *proj_xr,
+                                        const int32_t *pred_level, const float *view_cos, const uint8_t *mp_desc,
+                                        const uint8_t *mp_in_view, const uint8_t *mp_has_obs, float th, float nnratio,
+                                        int32_t *frame_match) {
+    return search_mappoints_impl(m, frame, nullptr, frame_occupied, n_mp, proj_x, proj_y, proj_xr, pred_level, view_cos, mp_desc, mp_in_view,
+                                 mp_has_obs, th, nnratio, frame_match);
+}
+
+static int search_frame_impl(orbx_matcher *m, const orbx_frame_desc *cur, orbx_frame *fh, const uint8_t *cur_occupied, int n_q, const float *q_u,
+                             const float *q_v, const float *q_ur, const int32_t *q_octave, const float *q_angle, const uint8_t *q_desc,
+                             const uint8_t *q_has_obs, float th, int level_mode, int check_orientation, int32_t *cur_match) {
     if (!m || !cur || cur->n < 0 || (!cur_match && cur->n > 0) || n_q < 0) return ORBX_E_BAD_ARG;
     if (n_q > 0 && (!q_u || !q_v || !q_octave || !q_desc || (check_orientation && !q_angle))) return ORBX_E_BAD_ARG;
     std::vector<float> qr(n_q);
@@ -678,7 +759,175 @@ int orbx_search_by_projection_frame(orbx_matcher *m, const orbx_frame_desc *cur,
     }
     ProjArgs a = {cur, cur_occupied, n_q, q_u, q_v, qr.data(), q_ur, qmin.data(), qmax.data(), q_desc, valid.data(), q_has_obs,
                   q_angle, 2, 0.f, check_orientation, cur_match, (float)ORBX_TH_HIGH};
-    return run_projection(m, a);
+    return run_projection(m, a, fh);
+}
+
+int orbx_search_by_projection_frame(orbx_matcher *m, const orbx_frame_desc *cur, const uint8_t *cur_occupied, int n_q,
+                                    const float *q_u, const float *q_v, const float *q_ur, const int32_t *q_octave,
+                                    const float *q_angle, const uint8_t *q_desc, const uint8_t *q_has_obs, float th, int level_mode,
+                                    int check_orientation, int32_t *cur_match) {
+    return search_frame_impl(m, cur, nullptr, cur_occupied, n_q, q_u, q_v, q_ur, q_octave, q_angle, q_desc, q_has_obs, th, level_mode,
+                             check_orientation, cur_match);
+}
+// ---------------------------------------------------------------------------------------------------------
+// Device-resident frame handle (orbx_frame): ExtractORB -> UndistortKeyPoints -> AssignFeaturesToGrid once per frame, then every projection
+// matcher of that frame reads the resident rows and grid.
+// ---------------------------------------------------------------------------------------------------------
+void orbx_frame_destroy(orbx_frame *f) {
+    if (!f) return;
+    (void)hipSetDevice(f->owner->device);
+    (void)hipStreamSynchronize(f->owner->stream);   // nothing of the owner's may still read or write the buffers
+    if (f->dev) (void)hipFree(f->dev);
+    if (f->stage) (void)hipHostFree(f->stage);
+    if (f->h_count) (void)hipHostFree(f->h_count);
+    if (f->ev_src) (void)hipEventDestroy(f->ev_src);
+    if (f->ev_done) (void)hipEventDestroy(f->ev_done);
+    delete f;
+}
+
+int orbx_frame_create(orbx_matcher *m, int cap, orbx_frame **out) {
+    if (!m || !out || cap < 1) return ORBX_E_BAD_ARG;
+    *out = nullptr;
+    if (cap > ORBX_MAX_FRAME_FEATURES) return ORBX_E_TOO_LARGE;
+    ORBX_HIP(hipSetDevice(m->device));
+    orbx_frame *f = new orbx_frame();
+    f->owner = m;
+    f->cap = cap;
+    size_t o = 0;
+    auto carve = [&o](size_t bytes) { const size_t r = o; o += Arena::pad(bytes); return r; };
+    f->off_kps = carve(28 * (size_t)cap); f->off_desc = carve(32 * (size_t)cap); f->off_ur = carve(4 * (size_t)cap);
+    f->off_count = carve(4); f->off_scale = carve(4 * (size_t)kFrameMaxLevels);
+    f->off_gstart = carve(2 * ((size_t)kGridCells + 1)); f->off_gorder = carve(2 * (size_t)cap);
+    f->stage_bytes = f->off_count;   // the rows: keypoints, descriptors, mvuRight at the device layout's offsets
+    hipError_t e = hipMalloc((void **)&f->dev, o);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&f->stage, f->stage_bytes, hipHostMallocCoherent);   // read by k_xfer's lanes
+    if (e == hipSuccess) e = hipHostMalloc((void **)&f->h_count, 64, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_src, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_done, hipEventDisableTiming);
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_frame_destroy(f); return ORBX_E_HIP; }
+    f->kps = (orbx_keypoint *)(f->dev + f->off_kps); f->desc = f->dev + f->off_desc; f->u_right = (float *)(f->dev + f->off_ur);
+    f->count = (int32_t *)(f->dev + f->off_count); f->scale = (float *)(f->dev + f->off_scale);
+    f->gstart = (uint16_t *)(f->dev + f->off_gstart); f->gorder = (uint16_t *)(f->dev + f->off_gorder);
+    f->n_known = true;   // an empty frame until the first load
+    *out = f;
+    return ORBX_OK;
+}
+
+static void frame_prepare_common(orbx_frame *f, FramePrepare &P, const float *scale_factors, int nlevels, const float *bounds4) {
+    memset(&P, 0, sizeof(P));
+    P.kps = f->kps; P.desc = f->desc; P.count = f->count; P.scale = f->scale; P.gstart = f->gstart; P.gorder = f->gorder;
+    P.cap = f->cap; P.nlevels = nlevels;
+    memcpy(P.scale_host, scale_factors, sizeof(float) * (size_t)nlevels);
+    f->scale_h.assign(scale_factors, scale_factors + nlevels);
+    f->nlevels = nlevels;
+    memcpy(f->bounds, bounds4, sizeof(f->bounds));
+}
+
+int orbx_frame_load_host(orbx_frame *f, const orbx_frame_desc *d) {
+    if (!f || !d || d->n < 0 || (d->n > 0 && (!d->keypoints_un || !d->descriptors)) || !d->scale_factors || d->nlevels < 1 ||
+        d->nlevels > kFrameMaxLevels)
+        return ORBX_E_BAD_ARG;
+    if (d->n > f->cap) return ORBX_E_TOO_LARGE;
+    orbx_matcher *m = f->owner;
+    ORBX_HIP(hipSetDevice(m->device));
+    if (f->stage_busy) { ORBX_HIP(hipEventSynchronize(f->ev_done)); f->stage_busy = false; }   // the previous load still reads the staging
+    m->begin();   // (transfer statistics of this load: orbx_matcher_debug_transfers)
+    const int n = d->n;
+    const size_t b_kps = 28 * (size_t)n, b_desc = 32 * (size_t)n, b_ur = d->u_right ? 4 * (size_t)n : 0;
+    memcpy(f->stage + f->off_kps, d->keypoints_un, b_kps);
+    memcpy(f->stage + f->off_desc, d->descriptors, b_desc);
+    if (b_ur) memcpy(f->stage + f->off_ur, d->u_right, b_ur);
+    // the rows in ONE k_xfer launch in the owner's queue (ORBX_MATCHER_DMA=1: by the DMA engine); count and scale factors travel as k_frame_prepare's arguments
+    XferOps X;
+    X.n = 0;
+    uint32_t max_units = 0;
+    const size_t offs[3] = {f->off_kps, f->off_desc, f->off_ur}, bytes[3] = {b_kps, b_desc, b_ur};
+    for (int k = 0; k < 3; k++) {
+        if (!bytes[k]) continue;
+        if (m->kernel_xfer) {
+            const uint32_t units = (uint32_t)((bytes[k] + 15) / 16);   // (rounded up to 16 bytes: inside the region's 256-byte padding)
+            X.op[X.n++] = XferOp{f->dev + offs[k], f->stage + offs[k], units, 0};
+            max_units = std::max(max_units, units);
+        } else {
+            ORBX_HIP(hipMemcpyAsync(f->dev + offs[k], f->stage + offs[k], bytes[k], hipMemcpyHostToDevice, m->stream));
+            m->xfers[4]++;
+        }
+        m->xfers[0]++; m->xfers[2] += (int64_t)bytes[k];
+    }
+    if (X.n) m->launch_xfer(X, max_units);
+    if (m->xfer_err != hipSuccess) { set_error(hipGetErrorString(m->xfer_err)); return ORBX_E_HIP; }
+    FramePrepare P;
+    const float b[4] = {d->min_x, d->max_x, d->min_y, d->max_y};
+    frame_prepare_common(f, P, d->scale_factors, d->nlevels, b);
+    P.n_host = n;
+    hipLaunchKernelGGL(k_frame_prepare, dim3(1), dim3(64), 0, m->stream, P, grid_of(f->bounds));
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
+    f->stage_busy = true;
+    f->n = n; f->n_known = true; f->has_ur = d->u_right != nullptr; f->loaded = true;
+    return ORBX_OK;
+}
+
+int orbx_frame_load_batch(orbx_frame *f, orbx_extractor *ex, int frame, const float *bounds4, const float *scale_factors, int nlevels) {
+    if (!f || !ex) return ORBX_E_BAD_ARG;
+    orbx_matcher *m = f->owner;
+    if (frame < 0 || frame >= ex->last_batch || ex->device != m->device || ex->cap > f->cap) return ORBX_E_BAD_ARG;
+    const float *sf = scale_factors ? scale_factors : ex->scale.data();
+    const int nl = scale_factors ? nlevels : ex->prm.nlevels;
+    if (nl < 1 || nl > kFrameMaxLevels || (!bounds4 && ex->width <= 0)) return ORBX_E_BAD_ARG;
+    const float *b = bounds4 ? bounds4 : ex->bounds;   // mnMinX.. of the extractor's camera (orbx_set_camera) or the image rectangle
+    ORBX_HIP(hipSetDevice(m->device));
+    FramePrepare P;
+    frame_prepare_common(f, P, sf, nl, b);
+    const size_t cap = (size_t)ex->cap;
+    P.src_kps = (const orbx_keypoint *)ex->match_kps() + (size_t)frame * cap;   // mvKeysUn
+    P.src_desc = (const uint8_t *)ex->d_desc.p + (size_t)frame * cap * 32;
+    P.src_count = (const int32_t *)ex->d_count.p + frame;
+    // the owner's stream waits for the extraction, the extractor's stream for the copy: no host synchronisation, and the next batch on `ex`
+    // overwrites its outputs only after this frame holds its own copy
+    ORBX_HIP(hipEventRecord(f->ev_src, ex->stream));
+    ORBX_HIP(hipStreamWaitEvent(m->stream, f->ev_src, 0));
+    hipLaunchKernelGGL(k_frame_prepare, dim3(1 + (unsigned)((cap + 255) / 256)), dim3(64), 0, m->stream, P, grid_of(f->bounds));
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
+    ORBX_HIP(hipStreamWaitEvent(ex->stream, f->ev_done, 0));
+    f->n_known = false; f->has_ur = false; f->loaded = true;
+    return ORBX_OK;
+}
+
+int orbx_frame_count(orbx_frame *f, int *n) {
+    if (!f || !n) return ORBX_E_BAD_ARG;
+    return frame_count(f, n);
+}
+
+// the orbx_frame_desc the host-side window setup reads (scale factors, levels, bounds); rows are never read from it
+static orbx_frame_desc frame_desc_of(const orbx_frame *f) {
+    orbx_frame_desc d;
+    memset(&d, 0, sizeof(d));
+    d.n = f->n_known ? f->n : f->cap;
+    d.min_x = f->bounds[0]; d.max_x = f->bounds[1]; d.min_y = f->bounds[2]; d.max_y = f->bounds[3];
+    d.scale_factors = f->scale_h.data(); d.nlevels = f->nlevels;
+    d.u_right = f->has_ur ? f->u_right : nullptr;
+    return d;
+}
+
+int orbx_frame_search_by_projection_mappoints(orbx_matcher *m, orbx_frame *frame, const uint8_t *frame_occupied, int n_mp, const float *proj_x,
+                                              const float *proj_y, const float *proj_xr, const int32_t *pred_level, const float *view_cos,
+                                              const uint8_t *mp_desc, const uint8_t *mp_in_view, const uint8_t *mp_has_obs, float th, float nnratio,
+                                              int32_t *frame_match) {
+    if (!m || !frame || frame->owner != m || !frame_match) return ORBX_E_BAD_ARG;
+    const orbx_frame_desc d = frame_desc_of(frame);
+    return search_mappoints_impl(m, &d, frame, frame_occupied, n_mp, proj_x, proj_y, proj_xr, pred_level, view_cos, mp_desc, mp_in_view, mp_has_obs,
+                                 th, nnratio, frame_match);
+}
+
+int orbx_frame_search_by_projection_frame(orbx_matcher *m, orbx_frame *cur, const uint8_t *cur_occupied, int n_q, const float *q_u, const float *q_v,
+                                          const float *q_ur, const int32_t *q_octave, const float *q_angle, const uint8_t *q_desc,
+                                          const uint8_t *q_has_obs, float th, int level_mode, int check_orientation, int32_t *cur_match) {
+    if (!m || !cur || cur->owner != m || !cur_match) return ORBX_E_BAD_ARG;
+    const orbx_frame_desc d = frame_desc_of(cur);
+    return search_frame_impl(m, &d, cur, cur_occupied, n_q, q_u, q_v, q_ur, q_octave, q_angle, q_desc, q_has_obs, th, level_mode, check_orientation,
+                             cur_match);
 }
 
 }  // extern "C"
@@ -1946,4 +2195,105 @@ extern "C" int orbx_fuse_search(orbx_matcher *m, const orbx_frame_desc *kf, cons
         if (k != kNoKey) { best_idx[i] = (int32_t)(k & 0xffff); best_dist[i] = (int32_t)(k >> 32); }
     }
     return ORBX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Tracking::SearchLocalPoints on a resident frame (Tracking.cc:3339-3413): Frame::isInFrustum (Frame.cc:512-575) of every local map point, the
+// window setup and SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) (ORBmatcher.cc:43-213, Nleft == -1) in one call: the projection
+// records stay in the call's arena, one transfer up, one down, one synchronisation.
+// ---------------------------------------------------------------------------------------------------------
+extern "C" int orbx_frame_search_local_points(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_camera *cam,
+                                              const orbx_frame_pose *pose, float log_scale_factor, float viewing_cos_limit, int n_mp, const float *pos,
+                                              const float *normal, const float *min_dist, const float *max_dist, const uint8_t *mp_desc,
+                                              const uint8_t *eligible, const uint8_t *has_obs, float th, float nnratio, int far_points,
+                                              float th_far_points, uint8_t *in_view, int32_t *frame_match) {
+    if (!m || !f || f->owner != m || !cam || !pose || n_mp < 0 || !frame_match) return ORBX_E_BAD_ARG;
+    if (n_mp > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !in_view)) return ORBX_E_BAD_ARG;
+    int n = -1;
+    if (f->n_known || frame_occupied || n_mp == 0) { const int rc = frame_count(f, &n); if (rc != ORBX_OK) return rc; }   // the mask holds N entries
+    for (int i = 0; i < n; i++) frame_match[i] = -1;
+    if (n_mp == 0) return 0;
+    const int nc = n >= 0 ? n : f->cap;
+    if (nc > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;
+    ORBX_HIP(hipSetDevice(m->device));
+    const size_t q = (size_t)n_mp;
+    const size_t need = 2 * Arena::pad(12 * q) + 2 * Arena::pad(4 * q) + Arena::pad(32 * q) + 2 * Arena::pad(q) + Arena::pad(sizeof(FrustumFrame)) +
+                        Arena::pad((size_t)nc) + Arena::pad(q) + 6 * Arena::pad(4 * q) + 3 * Arena::pad(4 * q) + 2 * Arena::pad(q) +
+                        Arena::pad(8 * kTopK * q) + 2 * Arena::pad(4 * q) + Arena::pad(4 * (size_t)nc) + Arena::pad(sizeof(WindowProblem)) +
+                        Arena::pad(sizeof(ResolveProblem)) + 16 * 256 + 4096;
+    int r = m->reserve_all(need);
+    if (r != ORBX_OK) return r;
+    Arena &A = m->arena;
+    m->begin();
+    // inputs (one run of the arena)
+    float *dp = A.take<float>(3 * q), *dn = A.take<float>(3 * q), *dmn = A.take<float>(q), *dmx = A.take<float>(q);
+    uint8_t *ddesc = A.take<uint8_t>(32 * q);
+    H2D(dp, pos, 12 * q); H2D(dn, normal, 12 * q); H2D(dmn, min_dist, 4 * q); H2D(dmx, max_dist, 4 * q); H2D(ddesc, mp_desc, 32 * q);
+    uint8_t *delig = nullptr, *dho = nullptr, *docc = nullptr;
+    if (eligible) { delig = A.take<uint8_t>(q); H2D(delig, eligible, q); }
+    if (has_obs) { dho = A.take<uint8_t>(q); H2D(dho, has_obs, q); }
+    if (frame_occupied && n > 0) { docc = A.take<uint8_t>((size_t)n); H2D(docc, frame_occupied, (size_t)n); }
+    FrustumFrame *dF = A.take<FrustumFrame>(1);
+    const FrustumFrame FF = frustum_frame(cam, pose, f->bounds, log_scale_factor, f->nlevels, viewing_cos_limit);
+    H2D(dF, &FF, sizeof(FF));
+    int32_t *dcnt = A.take<int32_t>(4);
+    const int32_t cnts[2] = {n, n_mp};
+    H2D(dcnt, cnts, 8);
+    WindowProblem *dP = A.take<WindowProblem>(1);
+    ResolveProblem *dR = A.take<ResolveProblem>(1);
+    // the projection records and the windows: device only
+    uint8_t *div = A.take<uint8_t>(q);
+    float *dx = A.take<float>(q), *dy = A.take<float>(q), *dxr = A.take<float>(q), *dd = A.take<float>(q), *dvc = A.take<float>(q);
+    int32_t *dl = A.take<int32_t>(q);
+    float *dqr = A.take<float>(q);
+    int32_t *dqmin = A.take<int32_t>(q), *dqmax = A.take<int32_t>(q);
+    uint8_t *dvalid = A.take<uint8_t>(q);
+    WindowProblem P;
+    memset(&P, 0, sizeof(P));
+    ResolveProblem R;
+    memset(&R, 0, sizeof(R));
+    P.kps = f->kps; P.desc = f->desc; P.n_ptr = f->count; P.nq_ptr = dcnt + 1;
+    if (f->has_ur) { P.u_right = f->u_right; P.qxr = dxr; }   // mTrackProjXR against mvuRight (ORBmatcher.cc:92-97)
+    P.occupied0 = docc;
+    P.qx = dx; P.qy = dy; P.qr = dqr; P.qmin = dqmin; P.qmax = dqmax; P.qdesc = ddesc; P.qvalid = dvalid;
+    P.gstart = f->gstart; P.gorder = f->gorder;
+    P.keys = A.take<u64>(q * kTopK); P.meta = A.take<int32_t>(q);
+    R.mode = 1; R.nnratio = nnratio; R.max_dist = (float)ORBX_TH_HIGH; R.cleared_value = -2; R.q_has_obs = dho;
+    R.entries = A.take<int32_t>(q);
+    // the downloads side by side: mbTrackInView, the matches, nmatches
+    uint8_t *div_out = A.take<uint8_t>(q);
+    R.match = A.take<int32_t>(nc);
+    R.nmatches = A.take<int32_t>(1);
+    H2D(dP, &P, sizeof(P)); H2D(dR, &R, sizeof(R));
+    hipLaunchKernelGGL(k_in_frustum, dim3((n_mp + 255) / 256, 1), dim3(256), 0, m->exec(), (const FrustumFrame *)dF, n_mp, (const float *)dp,
+                       (const float *)dn, (const float *)dmn, (const float *)dmx, div, dx, dy, dxr, dd, dl, dvc);
+    hipLaunchKernelGGL(k_local_windows, dim3((n_mp + 255) / 256), dim3(256), 0, m->exec(), n_mp, (const uint8_t *)div, (const uint8_t *)delig,
+                       (const int32_t *)dl, (const float *)dvc, (const float *)dd, (const float *)f->scale, f->nlevels, th, far_points ? 1 : 0,
+                       th_far_points, dqr, dqmin, dqmax, dvalid, div_out);
+    const bool match = n != 0;   // (an empty frame: isInFrustum only)
+    if (match) {
+        const GridParams g = grid_of(f->bounds);
+        ORBX_LAUNCH_WINDOW_BEST2(n_mp, 1, m->exec(), dP, g);
+        const int rr = launch_resolve<false>(1, m->exec(), dP, dR, g, nc, n_mp, 4);
+        if (rr != ORBX_OK) return rr;
+    }
+    ORBX_HIP(hipGetLastError());
+    int32_t nm = 0;
+    D2H(in_view, div_out, q);
+    if (match) {
+        if (n >= 0) {
+            D2H(frame_match, R.match, 4 * (size_t)n);
+        } else {   // N comes back with the results
+            f->h_match.resize((size_t)f->cap);
+            D2H(f->h_match.data(), R.match, 4 * (size_t)nc);
+            D2H(&f->n, f->count, 4);
+        }
+        D2H(&nm, R.nmatches, 4);
+    }
+    SYNC_AND_DELIVER();
+    if (n < 0) {
+        f->n_known = true;
+        memcpy(frame_match, f->h_match.data(), 4 * (size_t)std::max(f->n, 0));
+    }
+    return nm;
 }

@@ -58,6 +58,43 @@ class FeatureVector:
         return cls(self.node_id.ctypes.data, self.node_ptr.ctypes.data, self.index.ctypes.data, len(self.node_id))
 
 
+class DeviceFrame:
+    """A frame resident on the device across matcher calls (orbx_frame, include/orbx.h): what Frame::ExtractORB / UndistortKeyPoints /
+    AssignFeaturesToGrid build once per frame -- keypoints, descriptors, optional mvuRight, the count, the scale factors and the 64x48 grid.
+    It belongs to the matcher it was created with; ORBmatcher.SearchByProjection / SearchByProjectionFrame / SearchLocalPoints take it in
+    place of a FrameView."""
+
+    def __init__(self, matcher: "ORBmatcher", cap: int):
+        self._L = _lib.lib()
+        self.matcher = matcher        # (the owner outlives the handle)
+        self.cap = int(cap)
+        self._h = C.c_void_p()
+        check(self._L.orbx_frame_create(matcher._h, self.cap, C.byref(self._h)), "orbx_frame_create")
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_frame_destroy(self._h)
+            self._h = None
+
+    def load(self, F: "FrameView"):
+        """Upload a host frame once and build its grid (orbx_frame_load_host)."""
+        fd = F.c_struct()
+        check(self._L.orbx_frame_load_host(self._h, C.byref(fd)), "orbx_frame_load_host")   # (the rows are staged before it returns)
+        return self
+
+    def load_batch(self, extractor, f: int, bounds=None, scale_factors=None):
+        """Frame f of the extractor's last batch, copied on the device (orbx_frame_load_batch): asynchronous, no host synchronisation.
+        bounds = (minX, maxX, minY, maxY) or None (the extractor's camera / image rectangle); scale_factors None = the extractor's."""
+        b, sf = _f32(bounds), _f32(scale_factors)
+        check(self._L.orbx_frame_load_batch(self._h, extractor._h, int(f), ptr(b), ptr(sf), 0 if sf is None else len(sf)), "orbx_frame_load_batch")
+        return self
+
+    def count(self) -> int:
+        n = C.c_int(0)
+        check(self._L.orbx_frame_count(self._h, C.byref(n)), "orbx_frame_count")
+        return n.value
+
+
 def _f32(a):
     return None if a is None else np.ascontiguousarray(a, np.float32)
 
@@ -201,34 +238,67 @@ class ORBmatcher:
 
     # ---- SearchByProjection(Frame&, vector<MapPoint*>&, th, ...) (ORBmatcher.cc:43-213) ----
     def SearchByProjection(self, F: FrameView, mp: dict, th: float = 3.0, frame_occupied=None):
-        """mp: proj_x, proj_y, proj_xr, level, view_cos, desc, in_view, has_obs.  Returns (nmatches, frame_match)."""
-        fd = F.c_struct()
+        """mp: proj_x, proj_y, proj_xr, level, view_cos, desc, in_view, has_obs.  F: FrameView or DeviceFrame.  Returns (nmatches, frame_match)."""
         n_mp = len(mp["proj_x"])
-        fm = np.full(fd.n, -1, np.int32)
         a = dict(px=_f32(mp["proj_x"]), py=_f32(mp["proj_y"]), pxr=_f32(mp.get("proj_xr")), lv=_i32(mp["level"]),
                  vc=_f32(mp["view_cos"]), d=_u8(mp["desc"]), iv=_u8(mp.get("in_view")), ho=_u8(mp.get("has_obs")))
         occ = _u8(frame_occupied)
-        n = check(self._L.orbx_search_by_projection_mappoints(
-            self._h, C.byref(fd), ptr(occ), n_mp, ptr(a["px"]), ptr(a["py"]), ptr(a["pxr"]), ptr(a["lv"]),
-            ptr(a["vc"]), ptr(a["d"]), ptr(a["iv"]), ptr(a["ho"]), th, self.mfNNratio, ptr(fm)),
-            "orbx_search_by_projection_mappoints")
+        args = (ptr(occ), n_mp, ptr(a["px"]), ptr(a["py"]), ptr(a["pxr"]), ptr(a["lv"]), ptr(a["vc"]), ptr(a["d"]), ptr(a["iv"]), ptr(a["ho"]),
+                th, self.mfNNratio)
+        if isinstance(F, DeviceFrame):
+            fm = np.full(self._frame_rows(F, occ), -1, np.int32)
+            n = check(self._L.orbx_frame_search_by_projection_mappoints(self._h, F._h, *args, ptr(fm)), "orbx_frame_search_by_projection_mappoints")
+            return n, fm[:F.count()]
+        fd = F.c_struct()
+        fm = np.full(fd.n, -1, np.int32)
+        n = check(self._L.orbx_search_by_projection_mappoints(self._h, C.byref(fd), *args, ptr(fm)), "orbx_search_by_projection_mappoints")
         return n, fm
+
+    @staticmethod
+    def _frame_rows(F: "DeviceFrame", occ) -> int:
+        """Rows of a result array for a handle: N when it is known (or must be: an occupancy mask holds N entries), else the capacity."""
+        return len(occ) if occ is not None else F.cap
 
     # ---- SearchByProjection(Frame& Cur, const Frame& Last, th, bMono) (ORBmatcher.cc:1676-1887) ----
     def SearchByProjectionFrame(self, Cur: FrameView, q: dict, th: float, level_mode: int = 0, cur_occupied=None, raw=False):
         """q: u, v, ur, octave, angle, desc, has_obs (last-frame map points already projected into Cur).
         raw=True keeps the C ABI's -2 for "assigned, then cleared by the rotation check" (the slot becomes NULL in the reference)."""
-        fd = Cur.c_struct()
         nq = len(q["u"])
-        cm = np.full(fd.n, -1, np.int32)
         a = dict(u=_f32(q["u"]), v=_f32(q["v"]), ur=_f32(q.get("ur")), o=_i32(q["octave"]), ang=_f32(q["angle"]),
                  d=_u8(q["desc"]), ho=_u8(q.get("has_obs")))
         occ = _u8(cur_occupied)
-        n = check(self._L.orbx_search_by_projection_frame(
-            self._h, C.byref(fd), ptr(occ), nq, ptr(a["u"]), ptr(a["v"]), ptr(a["ur"]), ptr(a["o"]), ptr(a["ang"]),
-            ptr(a["d"]), ptr(a["ho"]), th, level_mode, int(self.mbCheckOrientation), ptr(cm)),
-            "orbx_search_by_projection_frame")
+        args = (ptr(occ), nq, ptr(a["u"]), ptr(a["v"]), ptr(a["ur"]), ptr(a["o"]), ptr(a["ang"]), ptr(a["d"]), ptr(a["ho"]), th, level_mode,
+                int(self.mbCheckOrientation))
+        if isinstance(Cur, DeviceFrame):
+            cm = np.full(self._frame_rows(Cur, occ), -1, np.int32)
+            n = check(self._L.orbx_frame_search_by_projection_frame(self._h, Cur._h, *args, ptr(cm)), "orbx_frame_search_by_projection_frame")
+            cm = cm[:Cur.count()]
+        else:
+            fd = Cur.c_struct()
+            cm = np.full(fd.n, -1, np.int32)
+            n = check(self._L.orbx_search_by_projection_frame(self._h, C.byref(fd), *args, ptr(cm)), "orbx_search_by_projection_frame")
         return n, (cm if raw else np.maximum(cm, -1))
+
+    # ---- Tracking::SearchLocalPoints (Tracking.cc:3339-3413): isInFrustum + SearchByProjection(F, MPs, th, bFarPoints, thFarPoints) ----
+    def SearchLocalPoints(self, F, cam, pose, log_scale_factor, cos_limit, pos, normal, min_dist, max_dist, desc, eligible=None, has_obs=None,
+                          th: float = 1.0, far_points: bool = False, th_far_points: float = 0.0, frame_occupied=None):
+        """One call, one synchronisation (orbx_frame_search_local_points).  F: DeviceFrame (or a FrameView, loaded into a handle for the call).
+        cam = orbx_camera fields (fx, fy, cx, cy, k1, k2, p1, p2, k3, bf); pose = (Rcw, tcw, Ow).  eligible[j] = !isBad() && mnLastFrameSeen != F.mnId,
+        has_obs[j] = Observations() > 0.  Returns (nmatches, frame_match[N], in_view[n_mp])."""
+        from ._lib import Camera, FramePose
+        if not isinstance(F, DeviceFrame):
+            F = DeviceFrame(self, max(1, len(F.keypoints_un))).load(F)
+        P, Nn = _f32(np.asarray(pos).reshape(-1, 3)), _f32(np.asarray(normal).reshape(-1, 3))
+        mn, mx, d, el, ho, occ = _f32(min_dist), _f32(max_dist), _u8(desc), _u8(eligible), _u8(has_obs), _u8(frame_occupied)
+        n_mp = len(P)
+        iv = np.zeros(n_mp, np.uint8)
+        fm = np.full(self._frame_rows(F, occ), -1, np.int32)
+        c, p = Camera(*[float(x) for x in cam]), FramePose.make(*pose)
+        n = check(self._L.orbx_frame_search_local_points(self._h, F._h, ptr(occ), C.byref(c), C.byref(p), float(log_scale_factor), float(cos_limit),
+                                                         n_mp, ptr(P), ptr(Nn), ptr(mn), ptr(mx), ptr(d), ptr(el), ptr(ho), float(th), self.mfNNratio,
+                                                         int(bool(far_points)), float(th_far_points), ptr(iv), ptr(fm)),
+                  "orbx_frame_search_local_points")
+        return n, fm[:F.count()], iv
 
     # ---- candidate generation: Frame::UndistortKeyPoints / ComputeImageBounds / isInFrustum ----
     def UndistortKeyPoints(self, cam, kps):
