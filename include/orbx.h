@@ -431,6 +431,37 @@ int orbx_search_for_triangulation_kb8(orbx_matcher *m, const uint8_t *desc1, con
 int orbx_debug_kb8_epipolar(orbx_matcher *m, const float *cam1_2x8, const float *cam2_2x8, const float *R12_4x9, const float *t12_4x3, int n, const float *xy1,
                             const float *xy2, const float *sigma1, const float *sigma2, const uint8_t *sel, uint8_t *ok);
 
+/* ---- Frame::ComputeStereoFishEyeMatches (src/Frame.cc:1126-1166) on the device: the rig's two KannalaBrandt8 cameras, no callback ----
+ * kNN-2 of the two lapping-area tails (BFmatcher.knnMatch, :1144: ties to the lower train index), Lowe's ratio as :1151 writes it ((float)d0 < (float)d1 * 0.7,
+ * float against double; a missing second neighbour fails), then KannalaBrandt8::TriangulateMatches (src/CameraModels/KannalaBrandt8.cpp:305-368) of mvKeys[iL]
+ * (cam1 = mpCamera) and mvKeysRight[iR] (cam2 = mpCamera2) with R12 = mRlr, t12 = mtlr and both level variances from the frame's mvLevelSigma2 (:1155).
+ * depth > 0.0001f accepts (:1157): mvLeftToRightMatch[iL] = iR, mvRightToLeftMatch[iR] = iL (of two accepted queries on one iR the larger iL, the
+ * reference's later one), mvDepth[iL], mvStereo3Dpoints[iL] = x3D.  Every output is initialised over the whole frame as :1134-1138 (l2r / r2l / depth = -1,
+ * p3d = 0); mvuRight stays -1 (the caller's).  The same device function as orbx_search_for_triangulation_kb8's gate: atan2f / tanf restated from glibc bit
+ * for bit, cos / sin in double, Eigen's JacobiSVD restated from its published source -- that step's parity is UNPINNED (Eigen is not vendored by the
+ * reference: DESIGN.md section 5). */
+typedef struct orbx_kb8_rig {   /* Frame::mpCamera / mpCamera2 mvParameters (fx, fy, cx, cy, k0..k3), mRlr (row-major), mtlr */
+    float cam_left[8], cam_right[8], R_lr[9], t_lr[3];
+} orbx_kb8_rig;
+/* on host arrays: returns nMatches; l2r / depth [n_left], p3d [n_left][3], r2l [n_right]; *desc_matches = the pairs that passed the ratio test (may be NULL).
+ * ORBX_E_BAD_ARG before any device work for mono_left outside [0, n_left], mono_right outside [0, n_right], a NULL array that is needed, or an octave outside
+ * [0, nlevels).  One launch chain and one synchronisation in the matcher's queue. */
+int orbx_compute_stereo_fisheye_matches(orbx_matcher *m, const orbx_kb8_rig *rig, const orbx_keypoint *kps_left, const uint8_t *desc_left, int n_left,
+                                        int mono_left, const orbx_keypoint *kps_right, const uint8_t *desc_right, int n_right, int mono_right,
+                                        const float *level_sigma2, int nlevels, int32_t *l2r, int32_t *r2l, float *depth, float *p3d, int *desc_matches);
+/* the same for every frame pair of two resident batches (left / right extractor: same n_frames, same nlevels, same device): the extractors' raw keypoints
+ * (mvKeys), counts and mono indices, the LEFT extractor's mvLevelSigma2.  Runs on the left extractor's match stream behind both extractions; the next pair
+ * of batches may be extracted meanwhile (both extractors' next k_finalize waits for this stage).  Reads no pyramid level.  Results stay valid until the next
+ * call of this function on `left`. */
+int orbx_stereo_fisheye_batch_device(orbx_extractor *left, orbx_extractor *right, const orbx_kb8_rig *rig);
+/* one frame: l2r / depth [n_left], p3d [n_left][3], r2l [n_right], the counts (any pointer may be NULL); synchronous */
+int orbx_stereo_fisheye_batch_download(orbx_extractor *left, int frame, int32_t *l2r, int32_t *r2l, float *depth, float *p3d, int *n_left, int *n_right,
+                                       int *n_matches, int *desc_matches);
+/* all frames: l2r / depth [n_frames][cap_left], p3d [n_frames][cap_left][3], r2l [n_frames][cap_right] (caps = orbx_batch_view_get's cap of each extractor;
+ * entries beyond a frame's counts unspecified), n_matches / desc_matches [n_frames]; synchronous */
+int orbx_stereo_fisheye_batch_download_all(orbx_extractor *left, int32_t *l2r, int32_t *r2l, float *depth, float *p3d, int32_t *n_matches,
+                                           int32_t *desc_matches);
+
 /* ---- fisheye-stereo forms (F.Nleft != -1: KannalaBrandt8 stereo rigs, both cameras' features in one Frame) ----
  * Feature indices follow the reference: [0, n_left) = left camera (F.mvKeys), [n_left, n_left + n_right) = right camera
  * (F.mvKeysRight); `left` describes the left camera (keypoints_un = mvKeys, n = n_left, image bounds, scale factors) and its

@@ -88,6 +88,24 @@ class Kb8GateStruct(C.Structure):
                 ("t12", C.c_float * 12), ("coarse", C.c_int)]
 
 
+class Kb8Rig(C.Structure):
+    """orbx_kb8_rig (include/orbx.h): Frame::mpCamera / mpCamera2 mvParameters, mRlr (row-major), mtlr."""
+    _fields_ = [("cam_left", C.c_float * 8), ("cam_right", C.c_float * 8), ("R_lr", C.c_float * 9), ("t_lr", C.c_float * 3)]
+
+    @classmethod
+    def make(cls, rig):
+        """rig: an object with the four fields as attributes, or a dict with those keys"""
+        import numpy as np
+        get = (lambda k: rig[k]) if isinstance(rig, dict) else (lambda k: getattr(rig, k))
+        r = cls()
+        for k, n in (("cam_left", 8), ("cam_right", 8), ("R_lr", 9), ("t_lr", 3)):
+            v = np.asarray(get(k), np.float32).ravel()
+            if len(v) != n:
+                raise ValueError(f"{k}: {n} values expected, got {len(v)}")
+            getattr(r, k)[:] = [float(x) for x in v]
+        return r
+
+
 class FeatVec(C.Structure):
     """DBoW2::FeatureVector flattened: node ids ascending + CSR of feature indices."""
     _fields_ = [("node_id", C.c_void_p), ("node_ptr", C.c_void_p), ("index", C.c_void_p), ("n_nodes", C.c_int32)]
@@ -114,6 +132,8 @@ SYMBOLS = [
     "orbx_vocabulary_destroy", "orbx_bow_transform", "orbx_distinctive_descriptors", "orbx_fuse_search",
     "orbx_frame_create", "orbx_frame_destroy", "orbx_frame_load_host", "orbx_frame_load_batch", "orbx_frame_count",
     "orbx_frame_search_by_projection_mappoints", "orbx_frame_search_by_projection_frame", "orbx_frame_search_local_points",
+    "orbx_compute_stereo_fisheye_matches", "orbx_stereo_fisheye_batch_device", "orbx_stereo_fisheye_batch_download",
+    "orbx_stereo_fisheye_batch_download_all",
 ]
 
 
@@ -216,6 +236,10 @@ def lib() -> C.CDLL:
     L.orbx_frame_search_by_projection_frame.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, i32, i32, vp]
     L.orbx_frame_search_local_points.argtypes = [vp, vp, vp, C.POINTER(Camera), C.POINTER(FramePose), f32, f32, i32, vp, vp, vp, vp, vp, vp, vp,
                                                  f32, f32, i32, f32, vp, vp]
+    L.orbx_compute_stereo_fisheye_matches.argtypes = [vp, C.POINTER(Kb8Rig), vp, vp, i32, i32, vp, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp]
+    L.orbx_stereo_fisheye_batch_device.argtypes = [vp, vp, C.POINTER(Kb8Rig)]
+    L.orbx_stereo_fisheye_batch_download.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbx_stereo_fisheye_batch_download_all.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

@@ -381,6 +381,33 @@ public:
         return nMatches;
     }
 
+    // The same member whole on the device, no callback: the rig's two KannalaBrandt8 cameras (mpCamera / mpCamera2 mvParameters, mRlr, mtlr) in `rig`,
+    // KannalaBrandt8::TriangulateMatches (KannalaBrandt8.cpp:305-368) evaluated by the kernel (orbx_compute_stereo_fisheye_matches).  Same outputs;
+    // mvuRight stays -1.  The callback form above remains the route for other camera models.
+    int ComputeStereoFishEyeMatches(const orbx_keypoint *mvKeys, const uint8_t *mDescriptors, int Nleft, int monoLeft,
+                                    const orbx_keypoint *mvKeysRight, const uint8_t *mDescriptorsRight, int Nright, int monoRight,
+                                    const float *mvLevelSigma2, int nlevels, const orbx_kb8_rig &rig, std::vector<int> &mvLeftToRightMatch,
+                                    std::vector<int> &mvRightToLeftMatch, std::vector<float> &mvDepth, std::vector<float> &mvuRight,
+                                    std::vector<std::array<float, 3>> &mvStereo3Dpoints, int *descMatches = nullptr) {
+        const int nl = Nleft > 0 ? Nleft : 0, nr = Nright > 0 ? Nright : 0;
+        mvLeftToRightMatch.assign(nl, -1);
+        mvRightToLeftMatch.assign(nr, -1);
+        mvDepth.assign(nl, -1.0f);
+        mvuRight.assign(nl, -1.0f);
+        mvStereo3Dpoints.assign(nl, std::array<float, 3>{0.f, 0.f, 0.f});
+        static_assert(sizeof(std::array<float, 3>) == 3 * sizeof(float), "mvStereo3Dpoints rows are three packed floats");
+        std::vector<int32_t> l2r(nl), r2l(nr);
+        int nDesc = 0;
+        const int r = orbx_compute_stereo_fisheye_matches(m_, &rig, mvKeys, mDescriptors, Nleft, monoLeft, mvKeysRight, mDescriptorsRight, Nright, monoRight,
+                                                          mvLevelSigma2, nlevels, l2r.data(), r2l.data(), mvDepth.data(),
+                                                          reinterpret_cast<float *>(mvStereo3Dpoints.data()), &nDesc);
+        if (r < 0) throw std::runtime_error(std::string("orbx_compute_stereo_fisheye_matches: ") + orbx_status_string(r));
+        for (int i = 0; i < nl; i++) mvLeftToRightMatch[i] = l2r[i];
+        for (int i = 0; i < nr; i++) mvRightToLeftMatch[i] = r2l[i];
+        if (descMatches) *descMatches = nDesc;
+        return r;
+    }
+
     // Frame::ComputeStereoMatches (Frame.cc:811-981) on host vectors: mvuRight / mvDepth out.  pyrLeft/pyrRight[l] are the level ROI
     // origins of the two extractors' mvImagePyramid (host copies, e.g. ORBextractor::GetPyramidLevel).  For the device-resident
     // batched form (no pyramid transfer) use orbx_stereo_batch_device / orbx_stereo_batch_download on the two extractors.

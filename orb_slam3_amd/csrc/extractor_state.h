@@ -196,6 +196,11 @@ struct orbx_extractor {
     bool copy_pending = false;                         // a download was issued since the last (re)configuration
     int32_t *h_err = nullptr;  // pinned, 2 slots
     DevBuf d_st_bidx, d_st_bdist, d_st_ur, d_st_depth, d_st_sad, d_st_nm, d_st_scales, d_st_rowptr, d_st_rowidx;  // device stereo matcher (left extractor)
+    // fisheye stereo stage (orbx_stereo_fisheye_batch_device, left extractor): its own result buffers -- kNN-2 rows [B][capL][2], l2r / depth [B][capL],
+    // p3d [B][capL][3], r2l [B][capR], counts [B][4] (nMatches, descMatches, n_left, n_right) -- and the shape they were written with (a later extraction
+    // may change last_batch / the counts before the download)
+    DevBuf d_sf_idx, d_sf_dist, d_sf_l2r, d_sf_r2l, d_sf_depth, d_sf_p3d, d_sf_cnt, d_sf_sigma, d_sf_rig;
+    int sf_batch = 0, sf_capL = 0, sf_capR = 0;
     DevBuf d_match, d_nmatch;  // internal match outputs [B][cap], [B] (one matcher per batch: orbx.h)
     int internal_match_owner = 0;   // which batched matcher wrote them for the current batch: 0 none, 1 frame-to-frame, 2 map points
     // cached problem descriptors of orbx_match_consecutive_device

@@ -320,10 +320,12 @@ __host__ __device__ inline void eigen_jacobi_svd4_v3(const float (*A)[4], float 
     }
 }
 
-// KannalaBrandt8::epipolarConstrain = TriangulateMatches(...) > 0.0001f (KannalaBrandt8.cpp:216-221, 305-368, Triangulate :387-400) for keypoint kp1 of camera
-// cam1 and kp2 of cam2, R12 / t12 the relative pose (row-major), sigmaLevel / unc the two level variances
-__host__ __device__ inline bool kb8_epipolar_constrain(const float *cam1, const float *cam2, float x1, float y1, float x2, float y2, const float *R12,
-                                                       const float *t12, float sigmaLevel, float unc) {
+// KannalaBrandt8::TriangulateMatches (KannalaBrandt8.cpp:305-368, Triangulate :387-400) for keypoint kp1 of camera cam1 and kp2 of cam2, R12 / t12 the
+// relative pose (row-major), sigmaLevel / unc the two level variances.  Returns the value and x3D by value (no scratch frame): value = -1 .. -5 at the
+// early exits (x3D = 0), z1 on success with x3D (the reference sets p3D = x3D on success only)
+struct Kb8Triangulation { float value, x, y, z; };
+__host__ __device__ inline Kb8Triangulation kb8_triangulate_matches(const float *cam1, const float *cam2, float x1, float y1, float x2, float y2, const float *R12,
+                                                          const float *t12, float sigmaLevel, float unc) {
     float r1[3], r2[3];
     kb8_unproject(cam1, x1, y1, 1e-6f, &r1[0], &r1[1]); r1[2] = 1.f;
     kb8_unproject(cam2, x2, y2, 1e-6f, &r2[0], &r2[1]); r2[2] = 1.f;
@@ -332,7 +334,7 @@ __host__ __device__ inline bool kb8_epipolar_constrain(const float *cam1, const 
     const float dot = ((0.f + r1[0] * r21[0]) + r1[1] * r21[1]) + r1[2] * r21[2];
     const float n1 = sqrtf(((0.f + r1[0] * r1[0]) + r1[1] * r1[1]) + r1[2] * r1[2]), n21 = sqrtf(((0.f + r21[0] * r21[0]) + r21[1] * r21[1]) + r21[2] * r21[2]);
     const float cosParallaxRays = dot / (n1 * n21);
-    if ((double)cosParallaxRays > 0.9998) return false;
+    if ((double)cosParallaxRays > 0.9998) return Kb8Triangulation{-1.f, 0.f, 0.f, 0.f};
     float R21[3][3], T2[3][4];
     for (int i = 0; i < 3; i++)
         for (int j = 0; j < 3; j++) R21[i][j] = R12[3 * j + i];
@@ -352,19 +354,25 @@ __host__ __device__ inline bool kb8_epipolar_constrain(const float *cam1, const 
     eigen_jacobi_svd4_v3(A, xh);
     const float X[3] = {xh[0] / xh[3], xh[1] / xh[3], xh[2] / xh[3]};
     const float z1 = X[2];
-    if (z1 <= 0) return false;
+    if (z1 <= 0) return Kb8Triangulation{-2.f, 0.f, 0.f, 0.f};
     const float z2 = (((0.f + R21[2][0] * X[0]) + R21[2][1] * X[1]) + R21[2][2] * X[2]) + T2[2][3];
-    if (z2 <= 0) return false;
+    if (z2 <= 0) return Kb8Triangulation{-3.f, 0.f, 0.f, 0.f};
     float u, v;
     kb8_project(cam1, X[0], X[1], X[2], &u, &v);
     const float errX1 = u - x1, errY1 = v - y1;
-    if ((double)(errX1 * errX1 + errY1 * errY1) > 5.991 * (double)sigmaLevel) return false;
+    if ((double)(errX1 * errX1 + errY1 * errY1) > 5.991 * (double)sigmaLevel) return Kb8Triangulation{-4.f, 0.f, 0.f, 0.f};
     float X2[3];
     for (int i = 0; i < 3; i++) X2[i] = (((0.f + R21[i][0] * X[0]) + R21[i][1] * X[1]) + R21[i][2] * X[2]) + T2[i][3];
     kb8_project(cam2, X2[0], X2[1], X2[2], &u, &v);
     const float errX2 = u - x2, errY2 = v - y2;
-    if ((double)(errX2 * errX2 + errY2 * errY2) > 5.991 * (double)unc) return false;
-    return z1 > 0.0001f;
+    if ((double)(errX2 * errX2 + errY2 * errY2) > 5.991 * (double)unc) return Kb8Triangulation{-5.f, 0.f, 0.f, 0.f};
+    return Kb8Triangulation{z1, X[0], X[1], X[2]};
+}
+
+// KannalaBrandt8::epipolarConstrain (KannalaBrandt8.cpp:216-221) = TriangulateMatches(...) > 0.0001f
+__host__ __device__ inline bool kb8_epipolar_constrain(const float *cam1, const float *cam2, float x1, float y1, float x2, float y2, const float *R12,
+                                                       const float *t12, float sigmaLevel, float unc) {
+    return kb8_triangulate_matches(cam1, cam2, x1, y1, x2, y2, R12, t12, sigmaLevel, unc).value > 0.0001f;
 }
 
 // grid (ceil(n_mp / 256), n_views), block 256.  Outputs [n_views][n_mp]: the MapPoint fields the function writes when every test passes

@@ -165,13 +165,29 @@ __global__ __launch_bounds__(256) void k_hamming_best2_csr(const uint8_t *__rest
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// brute-force kNN-2: one wave per query, train rows staged through LDS in tiles of kKnnTile rows
+// brute-force kNN-2: one wave per query, train rows staged through LDS in tiles of kKnnTile rows.
+// Per-frame form (F.q_count != nullptr, the batched fisheye stereo stage): frame f = blockIdx.y matches its query rows [q_mono[f], q_count[f]) of
+// row block f * q_cap against its train rows [t_mono[f], t_count[f]) of block f * t_cap (the extractor's lapping-area tails); idx / dist rows at
+// (f * q_cap + query) * 2, train indices relative to the train tail -- as the single form run on the two tails.
 // ---------------------------------------------------------------------------------------------------------
 constexpr int kKnnTile = 1024;  // 32 KiB
 
+struct KnnFrames { const int32_t *q_count, *q_mono, *t_count, *t_mono; int q_cap, t_cap; };
+
 __global__ __launch_bounds__(256) void k_knn2(const uint8_t *__restrict__ q, int nq, const uint8_t *__restrict__ t, int nt,
-                                              int32_t *__restrict__ idx, int32_t *__restrict__ dist) {
+                                              int32_t *__restrict__ idx, int32_t *__restrict__ dist, const KnnFrames F) {
     __shared__ ulonglong2 tile[kKnnTile * 2];
+    if (F.q_count) {
+        const int f = blockIdx.y;
+        const int qc = F.q_count[f], tc = F.t_count[f];
+        const int qm = min(max(F.q_mono[f], 0), qc), tm = min(max(F.t_mono[f], 0), tc);
+        nq = qc - qm; nt = tc - tm;
+        q += ((size_t)f * F.q_cap + qm) * 32;
+        t += ((size_t)f * F.t_cap + tm) * 32;
+        idx += (size_t)f * F.q_cap * 2;
+        dist += (size_t)f * F.q_cap * 2;
+    }
+    if ((int)blockIdx.x * 4 >= nq) return;   // block-uniform: no query of this block (the batch grid covers the capacity)
     const int qi = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     Desc dq;
     if (qi < nq) dq = load_desc(q + (size_t)qi * 32);
@@ -2709,6 +2725,91 @@ __global__ __launch_bounds__(64) void k_replay_bow_finish(BowProblem P) {
         nmatches -= dropped;
     }
     if (lane == 0) *P.nmatches = nmatches;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_tri_kb8_stereo: the per-query loop of Frame::ComputeStereoFishEyeMatches (Frame.cc:1147-1163) behind k_knn2, a LANE per left feature (the
+// gate is ~10^4 instructions per pair: a wave per query would leave 63 lanes idle).  Lane iL of frame f = blockIdx.y writes the frame's left outputs
+// over the WHOLE frame (:1134-1138: l2r = -1, depth = -1, p3d = 0 unless accepted); a lapping query (iL >= mono_left) with two neighbours passes Lowe's
+// ratio as :1151 writes it ((float)d0 < (float)d1 * 0.7: float against double), then KannalaBrandt8::TriangulateMatches (KannalaBrandt8.cpp:305-368)
+// of mvKeys[iL] (cam1 = left) and mvKeysRight[iR] (cam2 = right) with R12 = mRlr, t12 = mtlr and BOTH variances from the left table (:1155).  Accepted
+// (depth > 0.0001f, :1157): l2r, depth, p3d, and r2l[iR] = the LARGEST accepted iL (atomicMax: the reference's queries run in increasing iL, the later
+// one overwrites).  r2l is filled with -1 and counts[f][0..1] (nMatches, descMatches) are zeroed before the launch; counts[f][2..3] = the frame's
+// feature counts.  grid (ceil(capL / 256), n_frames), block 256.
+// ---------------------------------------------------------------------------------------------------------
+struct FisheyeStereo {
+    const orbx_kb8_rig *rig;
+    const orbx_keypoint *kl, *kr;            // [B][capL] mvKeys, [B][capR] mvKeysRight (raw, distorted: a KB8 frame triangulates them)
+    const int32_t *nl, *ml, *nr, *mr;        // [B] feature counts and mono indices (monoLeft / monoRight)
+    int capL, capR;
+    const float *sigma2;                     // mvLevelSigma2 of the frame (the left extractor's)
+    const int32_t *knn_idx, *knn_dist;       // [B][capL][2], row = iL - monoLeft, train index relative to the right tail
+    int32_t *l2r, *r2l;                      // [B][capL], [B][capR]
+    float *depth, *p3d;                      // [B][capL], [B][capL][3]
+    int32_t *counts;                         // [B][4]
+};
+__global__ __launch_bounds__(256) void k_tri_kb8_stereo(const FisheyeStereo S) {
+    const int f = blockIdx.y, iL = (int)(blockIdx.x * 256 + threadIdx.x);
+    const int nl = S.nl[f], nr = S.nr[f];
+    if (blockIdx.x == 0 && threadIdx.x == 0) { S.counts[4 * f + 2] = nl; S.counts[4 * f + 3] = nr; }
+    if (iL >= nl) return;   // (lane 0 holds the wave's lowest iL: a wave whose lane 0 left has no active lane)
+    const int ml = min(max(S.ml[f], 0), nl), mr = min(max(S.mr[f], 0), nr);
+    const size_t o = (size_t)f * S.capL + iL;
+    int match = -1;
+    bool desc_ok = false;
+    Kb8Triangulation T{-1.f, 0.f, 0.f, 0.f};
+    if (iL >= ml) {
+        const size_t k = ((size_t)f * S.capL + (iL - ml)) * 2;
+        const int i0 = S.knn_idx[k], i1 = S.knn_idx[k + 1];
+        const int d0 = S.knn_dist[k], d1 = S.knn_dist[k + 1];
+        if (i1 >= 0 && (double)(float)d0 < (double)(float)d1 * 0.7) {
+            desc_ok = true;
+            const int iR = i0 + mr;
+            const orbx_keypoint a = S.kl[o], b = S.kr[(size_t)f * S.capR + iR];
+            const orbx_kb8_rig *g = S.rig;
+            const Kb8Triangulation t = kb8_triangulate_matches(g->cam_left, g->cam_right, a.x, a.y, b.x, b.y, g->R_lr, g->t_lr, S.sigma2[a.octave],
+                                                               S.sigma2[b.octave]);
+            if (t.value > 0.0001f) {
+                T = t;
+                match = iR;
+                atomicMax(&S.r2l[(size_t)f * S.capR + iR], iL);
+            }
+        }
+    }
+    S.l2r[o] = match;
+    S.depth[o] = match >= 0 ? T.value : -1.f;
+    S.p3d[3 * o] = T.x; S.p3d[3 * o + 1] = T.y; S.p3d[3 * o + 2] = T.z;
+    const u64 bm = __ballot(match >= 0), bd = __ballot(desc_ok);
+    if ((threadIdx.x & 63) == 0) {
+        if (bm) atomicAdd(&S.counts[4 * f], __popcll(bm));
+        if (bd) atomicAdd(&S.counts[4 * f + 1], __popcll(bd));
+    }
+}
+
+// the batched stage's set-up (one launch, in the stage's stream): the rig and the level variances from the kernel argument into the stage's buffers,
+// r2l = -1 over [B][capR], counts = 0.  grid ceil(n_r2l / 256), block 256
+struct FisheyeStereoInit {
+    orbx_kb8_rig rig;
+    float sigma2[kMaxLevels];
+    int nlevels;
+    orbx_kb8_rig *d_rig;
+    float *d_sigma2;
+    int32_t *r2l, *counts;
+    int n_r2l, n_counts;
+};
+__global__ __launch_bounds__(256) void k_tri_kb8_stereo_init(const FisheyeStereoInit P) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (i < P.n_r2l) P.r2l[i] = -1;
+    if (i < P.n_counts) P.counts[i] = 0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        const float *src = &P.rig.cam_left[0];
+        float *dst = &P.d_rig->cam_left[0];
+#pragma unroll
+        for (int k = 0; k < (int)(sizeof(orbx_kb8_rig) / sizeof(float)); k++) dst[k] = src[k];
+#pragma unroll
+        for (int k = 0; k < kMaxLevels; k++)
+            if (k < P.nlevels) P.d_sigma2[k] = P.sigma2[k];
+    }
 }
 
 }  // namespace orbx

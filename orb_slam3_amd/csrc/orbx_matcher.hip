@@ -429,7 +429,7 @@ int orbx_knn2(orbx_matcher *m, const uint8_t *q, int nq, const uint8_t *t, int n
     int32_t *di = m->arena.take<int32_t>(2 * (size_t)nq), *dd = m->arena.take<int32_t>(2 * (size_t)nq);
     H2D(dq, q, (size_t)nq * 32);
     if (nt > 0) H2D(dt, t, (size_t)nt * 32);
-    hipLaunchKernelGGL(k_knn2, dim3((nq + 3) / 4), dim3(256), 0, m->exec(), dq, nq, dt, nt, di, dd);
+    hipLaunchKernelGGL(k_knn2, dim3((nq + 3) / 4), dim3(256), 0, m->exec(), dq, nq, dt, nt, di, dd, KnnFrames{});
     D2H(idx, di, 8 * (size_t)nq); D2H(dist, dd, 8 * (size_t)nq);
     SYNC_AND_DELIVER();
     return ORBX_OK;
@@ -1512,6 +1512,67 @@ int orbx_search_for_triangulation_kb8(orbx_matcher *m, const uint8_t *desc1, con
     return run_bow_replay(m, 2, desc1, a1.data(), skip1, n1, fv1, desc2, a2.data(), skip2, n2, fv2, 0.f, check_orientation, matches12, n1, nullptr, 0, gate);
 }
 
+// Frame::ComputeStereoFishEyeMatches (Frame.cc:1126-1166) whole, on host arrays: k_knn2 over the lapping-area tails, k_tri_kb8_stereo (ratio test,
+// KannalaBrandt8::TriangulateMatches, the four output vectors); one launch chain and one synchronisation in the matcher's queue
+int orbx_compute_stereo_fisheye_matches(orbx_matcher *m, const orbx_kb8_rig *rig, const orbx_keypoint *kps_left, const uint8_t *desc_left, int n_left,
+                                        int mono_left, const orbx_keypoint *kps_right, const uint8_t *desc_right, int n_right, int mono_right,
+                                        const float *level_sigma2, int nlevels, int32_t *l2r, int32_t *r2l, float *depth, float *p3d, int *desc_matches) {
+    if (!m || !rig || n_left < 0 || n_right < 0 || mono_left < 0 || mono_left > n_left || mono_right < 0 || mono_right > n_right) return ORBX_E_BAD_ARG;
+    if (!level_sigma2 || nlevels <= 0 || nlevels > 64) return ORBX_E_BAD_ARG;
+    if (n_left > 0 && (!kps_left || !desc_left || !l2r || !depth || !p3d)) return ORBX_E_BAD_ARG;
+    if (n_right > 0 && (!kps_right || !desc_right || !r2l)) return ORBX_E_BAD_ARG;
+    for (int i = 0; i < n_left; i++) if (kps_left[i].octave < 0 || kps_left[i].octave >= nlevels) return ORBX_E_BAD_ARG;
+    for (int i = 0; i < n_right; i++) if (kps_right[i].octave < 0 || kps_right[i].octave >= nlevels) return ORBX_E_BAD_ARG;
+    if (n_left == 0) {   // nothing to match; r2l = -1 (:1134-1138)
+        for (int i = 0; i < n_right; i++) r2l[i] = -1;
+        if (desc_matches) *desc_matches = 0;
+        return 0;
+    }
+    ORBX_HIP(hipSetDevice(m->device));
+    const size_t NL = (size_t)n_left, NR = (size_t)n_right, nq = NL - (size_t)mono_left, nt = NR - (size_t)mono_right;
+    int r = m->reserve_all(Arena::pad(sizeof(orbx_kb8_rig)) + Arena::pad(64) + Arena::pad(4 * (size_t)nlevels) + Arena::pad(28 * NL) + Arena::pad(28 * NR + 28) +
+                           Arena::pad(32 * nq + 32) + Arena::pad(32 * nt + 32) + 2 * Arena::pad(8 * nq + 8) + 2 * Arena::pad(4 * NL) + Arena::pad(12 * NL) +
+                           Arena::pad(4 * NR + 4) + Arena::pad(16) + 4096);
+    if (r != ORBX_OK) return r;
+    Arena &A = m->arena;
+    m->begin();
+    orbx_kb8_rig *drig = A.take<orbx_kb8_rig>(1);
+    int32_t *dn = A.take<int32_t>(16);   // n_left, mono_left, n_right, mono_right
+    float *ds = A.take<float>(nlevels);
+    orbx_keypoint *dkl = A.take<orbx_keypoint>(NL), *dkr = A.take<orbx_keypoint>(NR + 1);
+    uint8_t *ddl = A.take<uint8_t>(32 * nq + 32), *ddr = A.take<uint8_t>(32 * nt + 32);
+    int32_t *di = A.take<int32_t>(2 * nq + 2), *dd = A.take<int32_t>(2 * nq + 2);
+    int32_t *dl2r = A.take<int32_t>(NL);
+    float *ddep = A.take<float>(NL), *dp = A.take<float>(3 * NL);
+    int32_t *dr2l = A.take<int32_t>(NR + 1), *dcnt = A.take<int32_t>(4);
+    const int32_t hn[4] = {n_left, mono_left, n_right, mono_right};
+    H2D(drig, rig, sizeof(orbx_kb8_rig));
+    H2D(dn, hn, sizeof(hn));
+    H2D(ds, level_sigma2, 4 * (size_t)nlevels);
+    H2D(dkl, kps_left, 28 * NL);
+    H2D(dkr, kps_right, 28 * NR);
+    H2D(ddl, desc_left + 32 * (size_t)mono_left, 32 * nq);     // the lapping-area tails (:1128-1132)
+    H2D(ddr, desc_right + 32 * (size_t)mono_right, 32 * nt);
+    ORBX_HIP(m->fill(dr2l, 0xff, 4 * NR));
+    ORBX_HIP(m->fill(dcnt, 0, 16));
+    if (nq > 0)
+        hipLaunchKernelGGL(k_knn2, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, m->exec(), (const uint8_t *)ddl, (int)nq, (const uint8_t *)ddr, (int)nt, di, dd,
+                           KnnFrames{});
+    FisheyeStereo S;
+    S.rig = drig; S.kl = dkl; S.kr = dkr;
+    S.nl = dn; S.ml = dn + 1; S.nr = dn + 2; S.mr = dn + 3;
+    S.capL = n_left; S.capR = n_right;
+    S.sigma2 = ds; S.knn_idx = di; S.knn_dist = dd;
+    S.l2r = dl2r; S.r2l = dr2l; S.depth = ddep; S.p3d = dp; S.counts = dcnt;
+    hipLaunchKernelGGL(k_tri_kb8_stereo, dim3((unsigned)((NL + 255) / 256), 1), dim3(256), 0, m->exec(), S);
+    ORBX_HIP(hipGetLastError());
+    int32_t cnt[4] = {0, 0, 0, 0};
+    D2H(l2r, dl2r, 4 * NL); D2H(depth, ddep, 4 * NL); D2H(p3d, dp, 12 * NL); D2H(r2l, dr2l, 4 * NR); D2H(cnt, dcnt, 16);
+    SYNC_AND_DELIVER();
+    if (desc_matches) *desc_matches = cnt[1];
+    return cnt[0];
+}
+
 // test hook: KannalaBrandt8::epipolarConstrain of n independent pairs on the device (k_debug_kb8_gate); sel[i] = 2 * right1 + right2 picks cam1[right1],
 // cam2[right2] and R12 / t12 [sel] as the search does per candidate
 int orbx_debug_kb8_epipolar(orbx_matcher *m, const float *cam1_2x8, const float *cam2_2x8, const float *R12_4x9, const float *t12_4x3, int n, const float *xy1,
@@ -2049,6 +2110,131 @@ extern "C" int orbx_stereo_download_wait(orbx_extractor *L) {
     ORBX_HIP(hipSetDevice(L->device));
     ORBX_HIP(hipEventSynchronize(L->ev_stereo_copy[L->stereo_copy_waited & 1]));   // the OLDEST one in flight
     L->stereo_copy_waited++;
+    return ORBX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Frame::ComputeStereoFishEyeMatches (Frame.cc:1126-1166) for every frame pair of two resident batches (left / right extractor of a KannalaBrandt8 rig):
+// k_knn2 per frame over the two lapping-area tails (the extractors' counts and mono indices on the device), then k_tri_kb8_stereo.  Ordered as
+// orbx_stereo_batch_device minus the pyramid part: no pyramid level is read, so level 0 is not materialised and the extractors keep their single slab.
+// Raw keypoints (mvKeys: a KB8 frame triangulates the distorted points), the left extractor's mvLevelSigma2, result buffers of its own.
+// ---------------------------------------------------------------------------------------------------------
+extern "C" int orbx_stereo_fisheye_batch_device(orbx_extractor *L, orbx_extractor *R, const orbx_kb8_rig *rig) {
+    RoctxRange rr("orbx:stereo_fisheye");
+    if (!L || !R || !rig) return ORBX_E_BAD_ARG;
+    if (L->last_batch <= 0 || L->last_batch != R->last_batch || L->prm.nlevels != R->prm.nlevels || L->device != R->device) return ORBX_E_BAD_ARG;
+    ORBX_HIP(hipSetDevice(L->device));
+    const int n = L->last_batch, capL = L->cap, capR = R->cap, nl = L->prm.nlevels;
+    const size_t NL = (size_t)n * capL, NR = (size_t)n * capR;
+    if (NR + 4 * (size_t)n > (size_t)INT_MAX || nl > kMaxLevels || (int)L->sigma2.size() < nl) return ORBX_E_BAD_ARG;
+    int r;
+#define ENS(buf, bytes) if ((r = (buf).ensure(bytes)) != ORBX_OK) return r
+    ENS(L->d_sf_idx, 8 * NL);
+    ENS(L->d_sf_dist, 8 * NL);
+    ENS(L->d_sf_l2r, 4 * NL);
+    ENS(L->d_sf_depth, 4 * NL);
+    ENS(L->d_sf_p3d, 12 * NL);
+    ENS(L->d_sf_r2l, 4 * NR);
+    ENS(L->d_sf_cnt, 16 * (size_t)n);
+    ENS(L->d_sf_sigma, sizeof(float) * kMaxLevels);
+    ENS(L->d_sf_rig, sizeof(orbx_kb8_rig));
+#undef ENS
+    const bool side = !L->profile && L->side_streams;
+    hipStream_t st = side ? L->match_stream : L->stream;
+    ORBX_HIP(hipStreamWaitEvent(st, L->ev_describe, 0));  // the two extractions of this batch (the downloads of these results are synchronous: none in flight)
+    ORBX_HIP(hipStreamWaitEvent(st, R->ev_describe, 0));
+    FisheyeStereoInit I;
+    memset(&I, 0, sizeof(I));
+    I.rig = *rig;
+    for (int k = 0; k < nl; k++) I.sigma2[k] = L->sigma2[k];   // mvLevelSigma2: the frame's (left) table for both cameras (:1155)
+    I.nlevels = nl;
+    I.d_rig = (orbx_kb8_rig *)L->d_sf_rig.p; I.d_sigma2 = (float *)L->d_sf_sigma.p;
+    I.r2l = (int32_t *)L->d_sf_r2l.p; I.counts = (int32_t *)L->d_sf_cnt.p;
+    I.n_r2l = (int)NR; I.n_counts = 4 * n;
+    const size_t n_init = std::max(NR, (size_t)4 * n);
+    hipLaunchKernelGGL(k_tri_kb8_stereo_init, dim3((unsigned)((n_init + 255) / 256)), dim3(256), 0, st, I);
+    const KnnFrames F{(const int32_t *)L->d_count.p, (const int32_t *)L->d_mono.p, (const int32_t *)R->d_count.p, (const int32_t *)R->d_mono.p, capL, capR};
+    hipLaunchKernelGGL(k_knn2, dim3((unsigned)((capL + 3) / 4), (unsigned)n), dim3(256), 0, st, (const uint8_t *)L->d_desc.p, 0, (const uint8_t *)R->d_desc.p, 0,
+                       (int32_t *)L->d_sf_idx.p, (int32_t *)L->d_sf_dist.p, F);
+    FisheyeStereo S;
+    S.rig = (const orbx_kb8_rig *)L->d_sf_rig.p;
+    S.kl = (const orbx_keypoint *)L->d_kps.p; S.kr = (const orbx_keypoint *)R->d_kps.p;
+    S.nl = (const int32_t *)L->d_count.p; S.ml = (const int32_t *)L->d_mono.p;
+    S.nr = (const int32_t *)R->d_count.p; S.mr = (const int32_t *)R->d_mono.p;
+    S.capL = capL; S.capR = capR;
+    S.sigma2 = (const float *)L->d_sf_sigma.p;
+    S.knn_idx = (const int32_t *)L->d_sf_idx.p; S.knn_dist = (const int32_t *)L->d_sf_dist.p;
+    S.l2r = (int32_t *)L->d_sf_l2r.p; S.r2l = (int32_t *)L->d_sf_r2l.p;
+    S.depth = (float *)L->d_sf_depth.p; S.p3d = (float *)L->d_sf_p3d.p; S.counts = (int32_t *)L->d_sf_cnt.p;
+    hipLaunchKernelGGL(k_tri_kb8_stereo, dim3((unsigned)((capL + 255) / 256), (unsigned)n), dim3(256), 0, st, S);
+    ORBX_HIP(hipGetLastError());
+    L->sf_batch = n; L->sf_capL = capL; L->sf_capR = capR;
+    // the extractors must not overwrite their keypoints / descriptors / counts before these kernels are done
+    ORBX_HIP(hipEventRecord(L->ev_match, st));
+    L->match_pending = true; L->copy_covers_match = false;
+    ORBX_HIP(hipEventRecord(R->ev_match, st));   // the right extractor's next k_finalize waits for it as for a matcher of its own
+    R->match_pending = true; R->copy_covers_match = false;
+    return ORBX_OK;
+}
+
+// one frame of the last fisheye stereo stage: l2r / depth [n_left], p3d [n_left][3], r2l [n_right] (any output may be NULL); synchronous
+extern "C" int orbx_stereo_fisheye_batch_download(orbx_extractor *L, int frame, int32_t *l2r, int32_t *r2l, float *depth, float *p3d, int *n_left,
+                                                  int *n_right, int *n_matches, int *desc_matches) {
+    if (!L || frame < 0 || frame >= L->sf_batch || !L->d_sf_l2r.p) return ORBX_E_BAD_ARG;
+    ORBX_HIP(hipSetDevice(L->device));
+    ORBX_HIP(hipStreamWaitEvent(L->stream, L->ev_match, 0));   // the stage runs on the match stream
+    const size_t cl = (size_t)L->sf_capL, cr = (size_t)L->sf_capR, f = (size_t)frame;
+    auto al = [](size_t b) { return (b + 63) & ~(size_t)63; };
+    const size_t o_l = 64, o_d = o_l + al(4 * cl), o_p = o_d + al(4 * cl), o_r = o_p + al(12 * cl);
+    int r = L->d2h_staged_begin(o_r + al(4 * cr));
+    if (r != ORBX_OK) return r;
+    if ((r = L->d2h_staged(0, (int32_t *)L->d_sf_cnt.p + 4 * f, 16)) != ORBX_OK) return r;
+    if (l2r && (r = L->d2h_staged(o_l, (int32_t *)L->d_sf_l2r.p + f * cl, 4 * cl)) != ORBX_OK) return r;
+    if (depth && (r = L->d2h_staged(o_d, (float *)L->d_sf_depth.p + f * cl, 4 * cl)) != ORBX_OK) return r;
+    if (p3d && (r = L->d2h_staged(o_p, (float *)L->d_sf_p3d.p + 3 * f * cl, 12 * cl)) != ORBX_OK) return r;
+    if (r2l && (r = L->d2h_staged(o_r, (int32_t *)L->d_sf_r2l.p + f * cr, 4 * cr)) != ORBX_OK) return r;
+    ORBX_HIP(hipStreamSynchronize(L->stream));
+    int32_t h[4];
+    memcpy(h, L->staged(0), 16);
+    const size_t nlv = (size_t)std::min(std::max(h[2], 0), L->sf_capL), nrv = (size_t)std::min(std::max(h[3], 0), L->sf_capR);
+    if (n_matches) *n_matches = h[0];
+    if (desc_matches) *desc_matches = h[1];
+    if (n_left) *n_left = (int)nlv;
+    if (n_right) *n_right = (int)nrv;
+    if (l2r) memcpy(l2r, L->staged(o_l), 4 * nlv);
+    if (depth) memcpy(depth, L->staged(o_d), 4 * nlv);
+    if (p3d) memcpy(p3d, L->staged(o_p), 12 * nlv);
+    if (r2l) memcpy(r2l, L->staged(o_r), 4 * nrv);
+    return ORBX_OK;
+}
+
+// all frames of the last fisheye stereo stage: l2r / depth [n_frames][cap_left], p3d [n_frames][cap_left][3], r2l [n_frames][cap_right] (entries beyond a
+// frame's feature counts unspecified), n_matches / desc_matches [n_frames]; any output may be NULL; synchronous on the left extractor's stream
+extern "C" int orbx_stereo_fisheye_batch_download_all(orbx_extractor *L, int32_t *l2r, int32_t *r2l, float *depth, float *p3d, int32_t *n_matches,
+                                                      int32_t *desc_matches) {
+    if (!L || L->sf_batch <= 0 || !L->d_sf_l2r.p) return ORBX_E_BAD_ARG;
+    ORBX_HIP(hipSetDevice(L->device));
+    ORBX_HIP(hipStreamWaitEvent(L->stream, L->ev_match, 0));
+    const size_t n = (size_t)L->sf_batch, bl = 4 * n * L->sf_capL, br = 4 * n * L->sf_capR;
+    auto al = [](size_t b) { return (b + 63) & ~(size_t)63; };
+    const size_t o_d = al(16 * n), o_l = o_d + al(bl), o_p = o_l + al(bl), o_r = o_p + al(3 * bl);
+    int r = L->d2h_staged_begin(o_r + al(br));
+    if (r != ORBX_OK) return r;
+    if ((n_matches || desc_matches) && (r = L->d2h_staged(0, L->d_sf_cnt.p, 16 * n)) != ORBX_OK) return r;
+    if (depth && (r = L->d2h_staged(o_d, L->d_sf_depth.p, bl)) != ORBX_OK) return r;
+    if (l2r && (r = L->d2h_staged(o_l, L->d_sf_l2r.p, bl)) != ORBX_OK) return r;
+    if (p3d && (r = L->d2h_staged(o_p, L->d_sf_p3d.p, 3 * bl)) != ORBX_OK) return r;
+    if (r2l && (r = L->d2h_staged(o_r, L->d_sf_r2l.p, br)) != ORBX_OK) return r;
+    ORBX_HIP(hipStreamSynchronize(L->stream));
+    const int32_t *c = (const int32_t *)L->staged(0);
+    for (size_t f = 0; f < n; f++) {
+        if (n_matches) n_matches[f] = c[4 * f];
+        if (desc_matches) desc_matches[f] = c[4 * f + 1];
+    }
+    if (depth) memcpy(depth, L->staged(o_d), bl);
+    if (l2r) memcpy(l2r, L->staged(o_l), bl);
+    if (p3d) memcpy(p3d, L->staged(o_p), 3 * bl);
+    if (r2l) memcpy(r2l, L->staged(o_r), br);
     return ORBX_OK;
 }
 

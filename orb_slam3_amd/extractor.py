@@ -26,6 +26,7 @@ class ORBextractor:
         self.nfeatures, self.nlevels, self.device = nfeatures, nlevels, device
         self._last_shape = None
         self._cap_of = {}   # (width, height) -> output capacity
+        self._sf_shape = None   # (n_frames, cap_left, cap_right) of the last stereo_fisheye_batch_device
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -183,6 +184,46 @@ class ORBextractor:
         check(self._L.orbx_stereo_batch_download(self._h, frame, ptr(ur), ptr(depth), C.byref(nl), C.byref(nm)),
               "orbx_stereo_batch_download")
         return nm.value, ur[:nl.value].copy(), depth[:nl.value].copy()
+
+    # ---- Frame::ComputeStereoFishEyeMatches on two resident batches of a KannalaBrandt8 rig (self = left extractor) ----
+    def stereo_fisheye_batch_device(self, right: "ORBextractor", rig):
+        """rig: Kb8Rig or a dataclass / dict with cam_left, cam_right, R_lr, t_lr.  Runs behind both extractions on this extractor's match stream."""
+        c = rig if isinstance(rig, _lib.Kb8Rig) else _lib.Kb8Rig.make(rig)
+        check(self._L.orbx_stereo_fisheye_batch_device(self._h, right._h, C.byref(c)), "orbx_stereo_fisheye_batch_device")
+        self._sf_shape = (self.batch_view().n_frames, self.batch_view().cap, right.batch_view().cap)
+
+    def stereo_fisheye_download(self, frame: int):
+        """Returns (nMatches, descMatches, l2r[n_left], r2l[n_right], depth[n_left], p3d[n_left, 3]) of `frame` of the last fisheye stage."""
+        if self._sf_shape is None:
+            raise RuntimeError("stereo_fisheye_download: no stereo_fisheye_batch_device on this extractor yet")
+        _, capl, capr = self._sf_shape
+        l2r, r2l = np.zeros(capl, np.int32), np.zeros(capr, np.int32)
+        depth, p3d = np.zeros(capl, np.float32), np.zeros((capl, 3), np.float32)
+        nl, nr, nm, nd = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        check(self._L.orbx_stereo_fisheye_batch_download(self._h, frame, ptr(l2r), ptr(r2l), ptr(depth), ptr(p3d), C.byref(nl), C.byref(nr), C.byref(nm),
+                                                         C.byref(nd)), "orbx_stereo_fisheye_batch_download")
+        a, b = nl.value, nr.value
+        return nm.value, nd.value, l2r[:a].copy(), r2l[:b].copy(), depth[:a].copy(), p3d[:a].copy()
+
+    def stereo_fisheye_download_all(self, l2r=None, r2l=None, depth=None, p3d=None, n_matches=None, desc_matches=None):
+        """All frames of the last fisheye stage: l2r / depth [n_frames, cap_left], r2l [n_frames, cap_right], p3d [n_frames, cap_left, 3], the two
+        counts [n_frames] (entries beyond a frame's feature counts unspecified).  Arrays may be passed in (contiguous, of those shapes)."""
+        if self._sf_shape is None:
+            raise RuntimeError("stereo_fisheye_download_all: no stereo_fisheye_batch_device on this extractor yet")
+        n, capl, capr = self._sf_shape
+        l2r = np.zeros((n, capl), np.int32) if l2r is None else l2r
+        r2l = np.zeros((n, capr), np.int32) if r2l is None else r2l
+        depth = np.zeros((n, capl), np.float32) if depth is None else depth
+        p3d = np.zeros((n, capl, 3), np.float32) if p3d is None else p3d
+        n_matches = np.zeros(n, np.int32) if n_matches is None else n_matches
+        desc_matches = np.zeros(n, np.int32) if desc_matches is None else desc_matches
+        for a, shape, dt in ((l2r, (n, capl), np.int32), (r2l, (n, capr), np.int32), (depth, (n, capl), np.float32), (p3d, (n, capl, 3), np.float32),
+                             (n_matches, (n,), np.int32), (desc_matches, (n,), np.int32)):
+            if a.shape != shape or a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError(f"expected a contiguous {np.dtype(dt).name} array of shape {shape}, got {a.dtype} {a.shape}")
+        check(self._L.orbx_stereo_fisheye_batch_download_all(self._h, ptr(l2r), ptr(r2l), ptr(depth), ptr(p3d), ptr(n_matches), ptr(desc_matches)),
+              "orbx_stereo_fisheye_batch_download_all")
+        return n_matches, desc_matches, l2r, r2l, depth, p3d
 
     # ---- accessors (ORBextractor.h:62-83) ----
     def GetLevels(self) -> int:

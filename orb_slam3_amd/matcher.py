@@ -37,6 +37,15 @@ class FrameView:
                          len(self.scale_factors), None if self.u_right is None else self.u_right.ctypes.data)
 
 
+@dataclass
+class FisheyeRig:
+    """What Frame::ComputeStereoFishEyeMatches reads of a KannalaBrandt8 stereo rig (orbx_kb8_rig)."""
+    cam_left: np.ndarray              # float32 [8] mpCamera->mvParameters (fx, fy, cx, cy, k0..k3)
+    cam_right: np.ndarray             # float32 [8] mpCamera2->mvParameters
+    R_lr: np.ndarray                  # float32 [3, 3] Frame::mRlr
+    t_lr: np.ndarray                  # float32 [3] Frame::mtlr
+
+
 class FeatureVector:
     """DBoW2::FeatureVector as arrays: `nodes` ascending node ids, `lists[k]` = feature indices of node k."""
 
@@ -204,6 +213,22 @@ class ORBmatcher:
                     l2r[il], r2l[ir], depth[il], p3d[il] = ir, il, d, np.asarray(p, np.float32)
                     n_matches += 1
         return n_matches, n_desc, l2r, r2l, depth, ur, p3d
+
+    def ComputeStereoFishEyeMatches(self, kl, dl, mono_left, kr, dr, mono_right, level_sigma2, rig):
+        """Frame::ComputeStereoFishEyeMatches (Frame.cc:1126-1166) whole on the device: kNN-2 of the lapping-area tails, Lowe's ratio and
+        KannalaBrandt8::TriangulateMatches (KannalaBrandt8.cpp:305-368) of the rig's two cameras.  rig: Kb8Rig, or a dataclass / dict with cam_left,
+        cam_right (mvParameters), R_lr (mRlr) and t_lr (mtlr).  Returns (nMatches, descMatches, l2r, r2l, depth, u_right (all -1), p3d[n_left, 3])."""
+        kl, kr = np.ascontiguousarray(kl, KP_DTYPE), np.ascontiguousarray(kr, KP_DTYPE)
+        dl, dr, s2 = _u8(dl), _u8(dr), _f32(level_sigma2)
+        n_left, n_right = len(kl), len(kr)
+        c = rig if isinstance(rig, _lib.Kb8Rig) else _lib.Kb8Rig.make(rig)
+        l2r, r2l = np.full(n_left, -1, np.int32), np.full(n_right, -1, np.int32)
+        depth, ur, p3d = np.full(n_left, -1.0, np.float32), np.full(n_left, -1.0, np.float32), np.zeros((n_left, 3), np.float32)
+        nd = C.c_int(0)
+        n = check(self._L.orbx_compute_stereo_fisheye_matches(self._h, C.byref(c), ptr(kl), ptr(dl), n_left, int(mono_left), ptr(kr), ptr(dr), n_right,
+                                                              int(mono_right), ptr(s2), len(s2), ptr(l2r), ptr(r2l), ptr(depth), ptr(p3d),
+                                                              C.cast(C.byref(nd), C.c_void_p)), "orbx_compute_stereo_fisheye_matches")
+        return n, nd.value, l2r, r2l, depth, ur, p3d
 
     def stereo_rowband(self, kl, dl, kr, dr, scale_factors, n_rows, min_d, max_d):
         kl = np.ascontiguousarray(kl, KP_DTYPE)

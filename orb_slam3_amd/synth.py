@@ -209,3 +209,49 @@ def make_fisheye_keyframes(rng, n_pts: int = 420, with_poses: bool = False):
         f = lambda T: (T[:3, :3].astype(np.float32), T[:3, 3].astype(np.float32))
         out += (dict(pose1=f(np.eye(4)), pose2=f(T2w), trl=f(Trl)),)
     return out
+
+
+def make_fisheye_stereo_frame(rng, n_pts: int = 1500, n_left: int | None = None, n_right: int | None = None, mono_left: int = 0, mono_right: int = 0,
+                              flip: float = 0.04):
+    """One frame of a TUM-VI-like fisheye rig (make_fisheye_keyframes' first key frame): mvKeys / mvKeysRight with their descriptors, arranged as
+    ORBextractor leaves them -- the features outside the lapping area first, the lapping-area tail last (monoLeft / monoRight).  The left tail holds points
+    seen by both cameras; the right tail holds as many of those same points as fit (in another order), then others.  Descriptors: one random descriptor
+    per 3-D point, each feature's a copy with `flip` of its bits flipped (flip = 0: true correspondents have EQUAL descriptors, unrelated ones distinct).
+    n_left / n_right default to the features there are; n_pts must be large enough for the sizes asked (ValueError otherwise).
+    Returns (kl, dl, kr, dr, mono_left, mono_right, rig, id_left, id_right); rig = dict(cam_left, cam_right, R_lr, t_lr) (mRlr, mtlr: x_left = R_lr x_right + t_lr)."""
+    k1, nl1, _, id1, _, _, _, _, _, _, cams, poses = make_fisheye_keyframes(rng, n_pts, with_poses=True)
+    Rrl, trl = [np.asarray(x, np.float64) for x in poses["trl"]]
+    R_lr = Rrl.T
+    t_lr = -Rrl.T @ trl
+    left, right = np.arange(nl1), np.arange(nl1, len(k1))
+    n_left = len(left) if n_left is None else n_left
+    n_right = len(right) if n_right is None else n_right
+    if not (0 <= mono_left <= n_left and 0 <= mono_right <= n_right):
+        raise ValueError("mono index outside [0, n]")
+    nq, nt = n_left - mono_left, n_right - mono_right
+    pos_r = {int(id1[j]): j for j in right}
+    common = rng.permutation([i for i in left if int(id1[i]) in pos_r])
+    only_l = rng.permutation([i for i in left if int(id1[i]) not in pos_r])
+    tail_l = list(common[:nq]) + list(only_l[:max(0, nq - len(common))])
+    used_l = set(tail_l)
+    head_l = [i for i in rng.permutation(left) if i not in used_l][:mono_left]
+    shared = [pos_r[int(id1[i])] for i in tail_l if int(id1[i]) in pos_r][:nt]
+    used_r = set(shared)
+    rest_r = [j for j in rng.permutation(right) if j not in used_r]
+    tail_r = list(rng.permutation(shared + rest_r[:nt - len(shared)])) if nt else []
+    used_r |= set(tail_r)
+    head_r = [j for j in rest_r if j not in used_r][:mono_right]
+    if len(tail_l) != nq or len(head_l) != mono_left or len(tail_r) != nt or len(head_r) != mono_right:
+        raise ValueError(f"n_pts = {n_pts} too small for ({n_left}, {n_right}, {mono_left}, {mono_right})")
+    il = np.array(head_l + list(rng.permutation(tail_l)), np.int64)
+    ir = np.array(head_r + tail_r, np.int64)
+    pdesc = rng.integers(0, 256, (int(id1.max()) + 1, 32), dtype=np.uint8)
+
+    def desc(ids):
+        d = pdesc[ids]
+        if flip > 0:
+            d = d ^ np.packbits(rng.random((len(ids), 256)) < flip, axis=1, bitorder="little")
+        return np.ascontiguousarray(d)
+    kl, kr = k1[il].copy(), k1[ir].copy()
+    rig = dict(cam_left=cams[0].copy(), cam_right=cams[1].copy(), R_lr=R_lr.astype(np.float32), t_lr=t_lr.astype(np.float32))
+    return kl, desc(id1[il]), kr, desc(id1[ir]), mono_left, mono_right, rig, id1[il].copy(), id1[ir].copy()
