@@ -615,6 +615,46 @@ void orbx_vocabulary_destroy(orbx_vocabulary *voc);
  * its own vocabulary copy, tf-idf + L1 in double) and FeatureVector from these ids. */
 int orbx_bow_transform(orbx_matcher *m, const orbx_vocabulary *voc, const uint8_t *descriptors, int n, int levelsup,
                        int32_t *word_id, int32_t *node_id);
+/* The stop words of TemplatedVocabulary::transform(features, BowVector&, FeatureVector&, levelsup) (TemplatedVocabulary.h:1151-1193): a
+ * feature enters the FeatureVector only `if (w > 0)`.  weight[id] = m_words[id]->weight for every word id 0 .. n_words - 1 (n_words above the
+ * largest word id of the tree, ORBX_E_BAD_ARG otherwise); only the sign is kept on the device.  A vocabulary without weights stops no word.
+ * Takes effect at the next orbx_frame_compute_bow. */
+int orbx_vocabulary_set_word_weights(orbx_vocabulary *voc, const double *weight, int n_words);
+
+/* ---- BoW on the device-resident frame: Tracking::TrackReferenceKeyFrame and Tracking::Relocalization ----
+ * orbx_frame_compute_bow replaces Frame::ComputeBoW's transform (Frame.cc:738-745: mpORBvocabulary->transform(vCurrentDesc, mBowVec, mFeatVec, 4))
+ * on the handle's descriptors: nothing of the frame is uploaded.  The frame's FeatureVector (ascending node ids, each with its feature indices in
+ * ascending order, stopped features left out: the std::map order of FeatureVector::addFeature) stays in the handle.  Node ids are
+ * orbx_bow_transform's (node 0 for a leaf above level L - levelsup).  word_id / node_id (optional, N entries each; N may be unknown to the caller
+ * after orbx_frame_load_batch: buffers of the handle's capacity always suffice) return the per-feature ids -- the adapter still folds the word ids
+ * into mBowVec (tf-idf, L1) for the KeyFrameDatabase.  Both NULL: asynchronous, nothing waits.  The handle keeps the result, the vocabulary and
+ * levelsup until its next load.  ORBX_E_BAD_ARG for a handle of another matcher or a vocabulary on another device, before anything is enqueued. */
+int orbx_frame_compute_bow(orbx_matcher *m, orbx_frame *f, const orbx_vocabulary *voc, int levelsup, int32_t *word_id, int32_t *node_id);
+/* One key frame of a SearchByBoW batch: mDescriptors (n x 32), mvKeysUn[i].angle, valid[i] = GetMapPointMatches()[i] present and !isBad()
+ * (NULL: all), its mFeatVec flattened (node ids strictly ascending, indices < n).  n <= 65535. */
+typedef struct orbx_bow_keyframe {
+    const uint8_t *descriptors;
+    const float *angle;
+    const uint8_t *valid;
+    int32_t n;
+    orbx_featvec fv;
+} orbx_bow_keyframe;
+#define ORBX_MAX_BOW_KEYFRAMES 1024
+/* ORBmatcher(nnratio, check_orientation).SearchByBoW(kfs[k], F, vvpMapPointMatches[k]) (ORBmatcher.cc:223-425) for k = 0 .. n_kf - 1 against the
+ * handle's frame (its descriptors, mvKeysUn angles and orbx_frame_compute_bow's FeatureVector): match[k * match_stride + iF] = KF feature index or
+ * -1 for iF < N, nmatches[k] = the member's return value.  Row k equals orbx_search_by_bow_frame for key frame k bit for bit.  Relocalization's
+ * candidates in one call: one upload run, one launch chain whose length does not depend on n_kf, one download run, one synchronisation.
+ * match_stride >= N; while N is still on the device (orbx_frame_load_batch) a stride below the handle's capacity costs one orbx_frame_count first.
+ * Monocular / rectified frames only (fisheye-stereo frames: orbx_search_by_bow_frame_fisheye).  n_kf <= ORBX_MAX_BOW_KEYFRAMES (ORBX_E_TOO_LARGE).
+ * Returns ORBX_OK; ORBX_E_BAD_ARG, before anything is enqueued, for a handle of another matcher, a frame without orbx_frame_compute_bow since its
+ * last load, or a malformed key frame. */
+int orbx_frame_search_by_bow(orbx_matcher *m, orbx_frame *f, int n_kf, const orbx_bow_keyframe *kfs, float nnratio, int check_orientation,
+                             int32_t *match, int match_stride, int32_t *nmatches);
+/* orbx_search_by_projection_window on the resident frame (ORBmatcher.cc:1889-2010: Relocalization's SearchByProjection(F, pKF, sFound, 10, 100)
+ * and (.., 3, 64)); match holds N entries.  Results equal the host-pointer form's bit for bit. */
+int orbx_frame_search_by_projection_window(orbx_matcher *m, orbx_frame *f, const uint8_t *occupied, int n_q, const float *q_x, const float *q_y,
+                                           const float *q_r, const int32_t *q_min_level, const int32_t *q_max_level, const float *q_angle,
+                                           const uint8_t *q_desc, const uint8_t *q_has_obs, float max_dist, int check_orientation, int32_t *match);
 
 /* Frame::ComputeStereoMatches (Frame.cc:811-981) for every frame of two resident batches: `left` and `right` must have
  * extracted batches of the same size and image shape (rectified stereo, lapping {0,0}).  Row-band Hamming match, 11x11

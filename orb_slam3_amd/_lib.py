@@ -111,6 +111,13 @@ class FeatVec(C.Structure):
     _fields_ = [("node_id", C.c_void_p), ("node_ptr", C.c_void_p), ("index", C.c_void_p), ("n_nodes", C.c_int32)]
 
 
+class BowKeyFrame(C.Structure):
+    """orbx_bow_keyframe: one key frame of a batched SearchByBoW (descriptors, angles, valid mask, count, feature vector)."""
+    _fields_ = [("descriptors", C.c_void_p), ("angle", C.c_void_p), ("valid", C.c_void_p), ("n", C.c_int32), ("fv", FeatVec)]
+
+
+MAX_BOW_KEYFRAMES = 1024   # ORBX_MAX_BOW_KEYFRAMES
+
 PAIR_PREDICATE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
 _lib = None
@@ -134,6 +141,7 @@ SYMBOLS = [
     "orbx_frame_search_by_projection_mappoints", "orbx_frame_search_by_projection_frame", "orbx_frame_search_local_points",
     "orbx_compute_stereo_fisheye_matches", "orbx_stereo_fisheye_batch_device", "orbx_stereo_fisheye_batch_download",
     "orbx_stereo_fisheye_batch_download_all",
+    "orbx_vocabulary_set_word_weights", "orbx_frame_compute_bow", "orbx_frame_search_by_bow", "orbx_frame_search_by_projection_window",
 ]
 
 
@@ -240,6 +248,10 @@ def lib() -> C.CDLL:
     L.orbx_stereo_fisheye_batch_device.argtypes = [vp, vp, C.POINTER(Kb8Rig)]
     L.orbx_stereo_fisheye_batch_download.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbx_stereo_fisheye_batch_download_all.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.orbx_vocabulary_set_word_weights.argtypes = [vp, vp, i32]
+    L.orbx_frame_compute_bow.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.orbx_frame_search_by_bow.argtypes = [vp, vp, i32, C.POINTER(BowKeyFrame), f32, i32, vp, i32, vp]
+    L.orbx_frame_search_by_projection_window.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, i32, vp]
     _lib = L
     return L
 

@@ -8,6 +8,7 @@
 #ifndef ORBX_ADAPTER_ORBMATCHER_H
 #define ORBX_ADAPTER_ORBMATCHER_H
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <set>
@@ -45,6 +46,7 @@ struct MapPointBatch {
 };
 
 class ORBmatcher;
+class ORBVocabularyDevice;
 
 // A Frame resident on the device across matcher calls (orbx_frame, include/orbx.h): built once per Frame -- load() after UndistortKeyPoints, or
 // loadBatch() from an extractor's resident batch -- and passed to the SearchByProjection / SearchLocalPoints overloads below in place of a
@@ -68,6 +70,10 @@ public:
         check(orbx_frame_count(f_, &n), "orbx_frame_count");
         return n;
     }
+    // Frame::ComputeBoW's transform on the resident descriptors (orbx_frame_compute_bow): the FeatureVector stays here for the SearchByBoW
+    // overloads on a DeviceFrame.  wordId / nodeId (optional) receive N ids each -- mBowVec is folded from the word ids on the host.
+    inline void ComputeBoW(ORBmatcher &matcher, const ORBVocabularyDevice &voc, int levelsup = 4, std::vector<int32_t> *wordId = nullptr,
+                           std::vector<int32_t> *nodeId = nullptr);
     orbx_frame *handle() const { return f_; }
 
 private:
@@ -75,6 +81,7 @@ private:
         if (st < 0) throw std::runtime_error(std::string(what) + ": " + orbx_status_string(st) + " " + orbx_last_error());
     }
     orbx_frame *f_ = nullptr;
+    int cap_ = 0;
 };
 
 class ORBmatcher {
@@ -204,6 +211,18 @@ public:
         return r;
     }
 
+    // the same on a resident frame (Relocalization's second stage): vpMatch holds N entries
+    int SearchByProjectionWindow(DeviceFrame &F, const std::vector<uint8_t> &occupied, const WindowQueries &q, float maxDist, bool checkOrientation,
+                                 std::vector<int32_t> &vpMatch) {
+        vpMatch.assign(F.count(), -1);
+        const int r = orbx_frame_search_by_projection_window(m_, F.handle(), occupied.empty() ? nullptr : occupied.data(), (int)q.x.size(), q.x.data(),
+                                                             q.y.data(), q.r.data(), q.minLevel.data(), q.maxLevel.data(),
+                                                             q.angle.empty() ? nullptr : q.angle.data(), q.descriptors.data(), nullptr, maxDist,
+                                                             checkOrientation ? 1 : 0, vpMatch.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_by_projection_window: ") + orbx_status_string(r));
+        return r;
+    }
+
     // SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (ORBmatcher.cc:648-763)
     int SearchForInitialization(const orbx_keypoint *mvKeysUn1, const uint8_t *mDescriptors1, int N1, const FrameView &F2,
                                 std::vector<float> &vbPrevMatchedXY, std::vector<int> &vnMatches12, int windowSize = 10) {
@@ -240,6 +259,23 @@ public:
                                                mbCheckOrientation ? 1 : 0, vpMatch.data());
         if (r < 0) throw std::runtime_error(std::string("orbx_search_by_bow_frame: ") + orbx_status_string(r));
         return r;
+    }
+    // SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) against every key frame of kfs at once on a resident frame after DeviceFrame::ComputeBoW
+    // (orbx_frame_search_by_bow): vpMatch[k][iF] = KF feature index or -1, nmatches[k] = the member's return value.  Returns the sum.
+    int SearchByBoW(DeviceFrame &F, const std::vector<orbx_bow_keyframe> &kfs, std::vector<int32_t> &nmatches, std::vector<std::vector<int32_t>> &vpMatch) {
+        const int nkf = (int)kfs.size();
+        const int N = F.count(), stride = std::max(N, 1);
+        std::vector<int32_t> rows((size_t)std::max(nkf, 1) * stride, -1);
+        nmatches.assign(nkf, 0);
+        const int r = orbx_frame_search_by_bow(m_, F.handle(), nkf, kfs.data(), mfNNratio, mbCheckOrientation ? 1 : 0, rows.data(), stride, nmatches.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_by_bow: ") + orbx_status_string(r) + " " + orbx_last_error());
+        vpMatch.assign(nkf, std::vector<int32_t>());
+        int total = 0;
+        for (int k = 0; k < nkf; k++) {
+            vpMatch[k].assign(rows.begin() + (size_t)k * stride, rows.begin() + (size_t)k * stride + N);
+            total += nmatches[k];
+        }
+        return total;
     }
     // SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (ORBmatcher.cc:765-905): vpMatches12[i1] = i2 or -1
     int SearchByBoW(const uint8_t *desc1, const float *angle1, const uint8_t *valid1, int n1, const FeatVec &fv1, const uint8_t *desc2,
@@ -440,7 +476,7 @@ protected:
 // TemplatedVocabulary::transform(features, BowVector&, FeatureVector&, levelsup) (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1151-1193)
 // as called from Frame::ComputeBoW (Frame.cc:462-470) / KeyFrame::ComputeBoW: per feature the word id and the node id `levelsup`
 // levels above the leaf; the caller folds them into BowVector (addWeight) and FeatureVector (addFeature) in feature order.
-inline DeviceFrame::DeviceFrame(ORBmatcher &matcher, int cap) {
+inline DeviceFrame::DeviceFrame(ORBmatcher &matcher, int cap) : cap_(cap) {
     check(orbx_frame_create(matcher.handle(), cap, &f_), "orbx_frame_create");
 }
 
@@ -460,10 +496,29 @@ public:
         const int r = orbx_bow_transform(m.handle(), v_, descriptors, n, levelsup, wordId.data(), nodeId.data());
         if (r < 0) throw std::runtime_error(std::string("orbx_bow_transform: ") + orbx_status_string(r));
     }
+    // m_words[id]->weight for every word id: words with weight <= 0 are stop words of DeviceFrame::ComputeBoW's FeatureVector
+    void setWordWeights(const std::vector<double> &weights) {
+        const int r = orbx_vocabulary_set_word_weights(v_, weights.data(), (int)weights.size());
+        if (r < 0) throw std::runtime_error(std::string("orbx_vocabulary_set_word_weights: ") + orbx_status_string(r));
+    }
+    const orbx_vocabulary *handle() const { return v_; }
 
 private:
     orbx_vocabulary *v_ = nullptr;
 };
+
+inline void DeviceFrame::ComputeBoW(ORBmatcher &matcher, const ORBVocabularyDevice &voc, int levelsup, std::vector<int32_t> *wordId,
+                                    std::vector<int32_t> *nodeId) {
+    if (!wordId && !nodeId) {
+        check(orbx_frame_compute_bow(matcher.handle(), f_, voc.handle(), levelsup, nullptr, nullptr), "orbx_frame_compute_bow");
+        return;
+    }
+    std::vector<int32_t> w(cap_), nd(cap_);
+    check(orbx_frame_compute_bow(matcher.handle(), f_, voc.handle(), levelsup, w.data(), nd.data()), "orbx_frame_compute_bow");
+    const int n = count();   // known after the call
+    if (wordId) wordId->assign(w.begin(), w.begin() + n);
+    if (nodeId) nodeId->assign(nd.begin(), nd.begin() + n);
+}
 
 }  // namespace ORB_SLAM3
 

@@ -236,6 +236,55 @@ public:
         return nmatches;
     }
 
+    // The same member against a frame resident on the device (DeviceFrame, after DeviceFrame::ComputeBoW): the frame's descriptors, angles and
+    // FeatureVector are not uploaded again.  Monocular / rectified frames only (F.Nleft == -1; a fisheye-stereo frame takes the overload above).
+    // Like everything in this file it compiles only inside a tree with the reference's Frame / KeyFrame / MapPoint.
+    int SearchByBoW(KeyFrame *pKF, Frame &F, DeviceFrame &DF, std::vector<MapPoint *> &vpMapPointMatches) {
+        std::vector<KeyFrame *> kfs(1, pKF);
+        std::vector<std::vector<MapPoint *>> matches;
+        std::vector<int> nmatches;
+        SearchByBoW(kfs, F, DF, matches, nmatches);
+        vpMapPointMatches = matches[0];
+        return nmatches[0];
+    }
+    // Tracking::Relocalization (Tracking.cc:3670-3700): SearchByBoW(vpCandidateKFs[i], mCurrentFrame, vvpMapPointMatches[i]) for every candidate in ONE
+    // device call (orbx_frame_search_by_bow: one upload, one launch chain, one synchronisation).  Candidates are independent -- each writes its own
+    // vvpMapPointMatches[i] and histogram -- so nmatches[i] and vvpMapPointMatches[i] equal what the per-candidate calls return.
+    void SearchByBoW(const std::vector<KeyFrame *> &vpKFs, Frame &F, DeviceFrame &DF, std::vector<std::vector<MapPoint *>> &vvpMapPointMatches,
+                     std::vector<int> &nmatches) {
+        if (F.Nleft != -1) throw std::runtime_error("SearchByBoW(DeviceFrame): a fisheye-stereo frame takes SearchByBoW(KeyFrame*, Frame&, ...)");
+        const size_t nkf = vpKFs.size();
+        std::vector<std::vector<MapPoint *>> vpMPs(nkf);
+        std::vector<std::vector<uint8_t>> valid(nkf);
+        std::vector<std::vector<float>> ang(nkf);
+        std::vector<FeatVec> fvs(nkf);
+        std::vector<orbx_bow_keyframe> kfs(nkf);
+        for (size_t k = 0; k < nkf; k++) {
+            KeyFrame *pKF = vpKFs[k];
+            vpMPs[k] = pKF->GetMapPointMatches();
+            const int nKF = (int)vpMPs[k].size();
+            valid[k].resize(nKF);
+            ang[k].resize(nKF);
+            for (int i = 0; i < nKF; i++) {
+                MapPoint *pMP = vpMPs[k][i];
+                valid[k][i] = (pMP && !pMP->isBad()) ? 1 : 0;                          // :252-256
+                ang[k][i] = pKF->mvKeysUn[i].angle;                                    // :335
+            }
+            fvs[k] = FeatVec::from(pKF->mFeatVec);
+            kfs[k] = orbx_bow_keyframe{pKF->mDescriptors.data, ang[k].data(), valid[k].data(), nKF, fvs[k].c()};
+        }
+        std::vector<int32_t> nm;
+        std::vector<std::vector<int32_t>> match;
+        SearchByBoW(DF, kfs, nm, match);
+        vvpMapPointMatches.assign(nkf, std::vector<MapPoint *>(F.N, static_cast<MapPoint *>(NULL)));
+        nmatches.assign(nkf, 0);
+        for (size_t k = 0; k < nkf; k++) {
+            nmatches[k] = nm[k];
+            for (int i = 0; i < F.N && i < (int)match[k].size(); i++)
+                if (match[k][i] >= 0) vvpMapPointMatches[k][i] = vpMPs[k][match[k][i]];   // :329
+        }
+    }
+
     // ORBmatcher.cc:765-905 (LoopClosing / place recognition)
     int SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint *> &vpMatches12) {
         const std::vector<MapPoint *> vpMapPoints1 = pKF1->GetMapPointMatches();

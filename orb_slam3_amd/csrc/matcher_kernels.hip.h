@@ -311,10 +311,10 @@ __global__ __launch_bounds__(256) void k_distinctive(const uint8_t *__restrict__
 // node, the packed key (dist << 16 | child position) is min-reduced inside the 16-lane group.
 // grid (ceil(n/16)), block 256
 // ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_bow_transform(const int32_t *__restrict__ child_ptr, const int32_t *__restrict__ child_idx,
-                                                       const uint8_t *__restrict__ node_desc, const int32_t *__restrict__ word_id, int L,
-                                                       int levelsup, const uint8_t *__restrict__ desc, int n,
-                                                       int32_t *__restrict__ word_out, int32_t *__restrict__ node_out) {
+__device__ __forceinline__ void bow_transform_body(const int32_t *__restrict__ child_ptr, const int32_t *__restrict__ child_idx,
+                                                   const uint8_t *__restrict__ node_desc, const int32_t *__restrict__ word_id, int L,
+                                                   int levelsup, const uint8_t *__restrict__ desc, int n,
+                                                   int32_t *__restrict__ word_out, int32_t *__restrict__ node_out) {
     const int i = blockIdx.x * 16 + (threadIdx.x >> 4), sl = threadIdx.x & 15;
     const bool valid = i < n;
     Desc dq;
@@ -347,6 +347,21 @@ __global__ __launch_bounds__(256) void k_bow_transform(const int32_t *__restrict
         }
     }
     if (valid && sl == 0) { word_out[i] = word_id[node]; node_out[i] = (nid_level <= 0) ? 0 : nid; }
+}
+__global__ __launch_bounds__(256) void k_bow_transform(const int32_t *__restrict__ child_ptr, const int32_t *__restrict__ child_idx,
+                                                       const uint8_t *__restrict__ node_desc, const int32_t *__restrict__ word_id, int L,
+                                                       int levelsup, const uint8_t *__restrict__ desc, int n,
+                                                       int32_t *__restrict__ word_out, int32_t *__restrict__ node_out) {
+    bow_transform_body(child_ptr, child_idx, node_desc, word_id, L, levelsup, desc, n, word_out, node_out);
+}
+// the same on a resident frame (orbx_frame_compute_bow): n_host >= 0, or the frame's count read on the device (a batch-loaded frame nobody has
+// counted yet; the grid then covers the handle's capacity).  grid (ceil(n or cap / 16)), block 256
+__global__ __launch_bounds__(256) void k_frame_bow_transform(const int32_t *__restrict__ child_ptr, const int32_t *__restrict__ child_idx,
+                                                             const uint8_t *__restrict__ node_desc, const int32_t *__restrict__ word_id, int L,
+                                                             int levelsup, const uint8_t *__restrict__ desc, const int32_t *__restrict__ count,
+                                                             int n_host, int cap, int32_t *__restrict__ word_out, int32_t *__restrict__ node_out) {
+    const int n = n_host >= 0 ? n_host : min(max(*count, 0), cap);
+    bow_transform_body(child_ptr, child_idx, node_desc, word_id, L, levelsup, desc, n, word_out, node_out);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2587,7 +2602,7 @@ __device__ __forceinline__ void replay_bow_node64(const BowProblem &P, const int
     if (lane == 0 && nmatches) atomicAdd(&P.counters[1], nmatches);
 }
 
-__global__ __launch_bounds__(256) void k_replay_bow(BowProblem P) {
+__device__ __forceinline__ void replay_bow_wave(const BowProblem &P) {
     const int lane = threadIdx.x & 63;
     const int ia = (int)(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (ia >= P.fa.n_nodes) return;
@@ -2598,6 +2613,7 @@ __global__ __launch_bounds__(256) void k_replay_bow(BowProblem P) {
     if (b1 - b0 <= 64) replay_bow_node64(P, a0, a1, b0, b1 - b0, lane);
     else replay_bow_big_node(P, ia, ib, lane);
 }
+__global__ __launch_bounds__(256) void k_replay_bow(BowProblem P) { replay_bow_wave(P); }
 
 // debug kernel (orbx_debug_kb8_epipolar): KannalaBrandt8::epipolarConstrain for n independent keypoint pairs, a lane per pair -- the device function k_tri_kb8 calls,
 // on its own, so that a test can compare EVERY verdict with the oracle on the hardware (through the search only the winning candidate of a query shows)
@@ -2705,7 +2721,7 @@ __global__ __launch_bounds__(256) void k_tri_kb8(BowProblem P) {
 }
 
 // the rotation-consistency filter over the matches of all nodes (:401-416, :882-897, :1120-1137) and the match count
-__global__ __launch_bounds__(64) void k_replay_bow_finish(BowProblem P) {
+__device__ __forceinline__ void replay_bow_finish(const BowProblem &P) {
     __shared__ int hist[ORBX_HISTO_LENGTH];
     const int lane = threadIdx.x;
     int nmatches = P.counters[1];
@@ -2726,6 +2742,115 @@ __global__ __launch_bounds__(64) void k_replay_bow_finish(BowProblem P) {
     }
     if (lane == 0) *P.nmatches = nmatches;
 }
+__global__ __launch_bounds__(64) void k_replay_bow_finish(BowProblem P) { replay_bow_finish(P); }
+
+// ---------------------------------------------------------------------------------------------------------
+// Frame::ComputeBoW on a resident frame (orbx_frame_compute_bow) and SearchByBoW(KeyFrame*, Frame&) against many key frames at once
+// (orbx_frame_search_by_bow).
+//
+// k_frame_featvec: the frame's DBoW2::FeatureVector from k_frame_bow_transform's word / node ids, in the handle.  TemplatedVocabulary::transform
+// (TemplatedVocabulary.h:1151-1193) adds feature i to node nid only `if (w > 0)` (not stopped) and in increasing i, so the std::map holds the
+// ascending node ids, each with its features in ascending order.  ONE workgroup sorts the keys node << 16 | i of the kept features (a stopped
+// feature: the all-ones key, sorted behind them) by a bitonic network in LDS, then marks where a node starts and numbers those starts by a
+// workgroup scan: node_id[k] / node_ptr[k] / index[p] are pure functions of the input -- no atomics, nothing depends on scheduling.  Also copies
+// mvKeysUn[i].angle into angle[] for the replay's rotation histogram.  grid 1, block 1024, dynamic LDS 8 * sort_cap (a power of two >= the
+// features the call may see: N, or the capacity while N is on the device).
+// ---------------------------------------------------------------------------------------------------------
+struct FrameBow {
+    const int32_t *count; int n_host, cap;
+    const orbx_keypoint *kps;
+    const int32_t *word, *node;      // k_frame_bow_transform's outputs [cap]
+    const uint8_t *word_pos;         // [n_words] weight > 0 per word id (orbx_vocabulary_set_word_weights); NULL: no word is stopped
+    int n_words;
+    float *angle;                    // out [cap]
+    uint32_t *fv_node;               // out [cap]: ascending node ids
+    int32_t *fv_ptr;                 // out [cap + 1]: CSR into fv_index
+    int32_t *fv_index;               // out [cap]
+    int32_t *fv_meta;                // out [2]: node count, features kept
+};
+__global__ __launch_bounds__(1024) void k_frame_featvec(const FrameBow B, int sort_cap) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    u64 *keys = reinterpret_cast<u64 *>(lds);
+    __shared__ int32_t sums[1024];
+    __shared__ int32_t kept_s;
+    const int t = threadIdx.x;
+    const int n = B.n_host >= 0 ? B.n_host : min(max(*B.count, 0), B.cap);
+    int p2 = 1;
+    while (p2 < n) p2 <<= 1;
+    p2 = min(p2, sort_cap);
+    if (t == 0) kept_s = 0;
+    for (int p = t; p < p2; p += 1024) {
+        u64 key = kNoKey;
+        if (p < n) {
+            const int w = B.word[p];
+            const bool stopped = B.word_pos && (w < 0 || w >= B.n_words || !B.word_pos[w]);
+            if (!stopped) key = ((u64)(uint32_t)B.node[p] << 16) | (u64)p;
+            B.angle[p] = B.kps[p].angle;
+        }
+        keys[p] = key;
+    }
+    __syncthreads();
+    for (int k = 2; k <= p2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int p = t; p < p2; p += 1024) {
+                const int q = p ^ j;
+                if (q > p) {
+                    const u64 a = keys[p], b = keys[q];
+                    if ((a > b) == ((p & k) == 0)) { keys[p] = b; keys[q] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // kept features = the keys before the first all-ones one (the keys of kept features are distinct)
+    for (int p = t; p < p2; p += 1024)
+        if (keys[p] != kNoKey && (p + 1 == p2 || keys[p + 1] == kNoKey)) kept_s = p + 1;
+    __syncthreads();
+    const int kept = kept_s;
+    const int chunk = (p2 + 1023) / 1024, c0 = min(t * chunk, kept), c1 = min(c0 + chunk, kept);
+    auto starts = [&](int p) { return p == 0 || (keys[p] >> 16) != (keys[p - 1] >> 16); };
+    int c = 0;
+    for (int p = c0; p < c1; p++) c += starts(p) ? 1 : 0;
+    sums[t] = c;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {   // inclusive scan of the per-thread node starts
+        const int v = t >= off ? sums[t - off] : 0;
+        __syncthreads();
+        sums[t] += v;
+        __syncthreads();
+    }
+    int slot = sums[t] - c;
+    for (int p = c0; p < c1; p++) {
+        if (starts(p)) { B.fv_node[slot] = (uint32_t)(keys[p] >> 16); B.fv_ptr[slot] = p; slot++; }
+        B.fv_index[p] = (int32_t)(keys[p] & 0xffffu);
+    }
+    if (t == 1023) { B.fv_ptr[sums[1023]] = kept; B.fv_meta[0] = sums[1023]; B.fv_meta[1] = kept; }
+}
+
+// k_bow_pair_nodes: the node pairing of SearchByBoW (:246-250, the merge-join of the two sorted maps) for every node of every key frame of a batch,
+// a lane per (key frame, node): pair[t] = the position of kf_node[t] in the frame's ascending node list (binary search), or -1.  Equal to the
+// merge-join for strictly ascending lists.  The replay reads pair[] as BowProblem::pair_b, no search inside it.  grid ceil(total / 256), block 256
+__global__ __launch_bounds__(256) void k_bow_pair_nodes(const uint32_t *__restrict__ kf_node, int total, const uint32_t *__restrict__ f_node,
+                                                        const int32_t *__restrict__ f_meta, int32_t *__restrict__ pair) {
+    const int t = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (t >= total) return;
+    const int nn = f_meta[0];
+    const uint32_t id = kf_node[t];
+    int lo = 0, hi = nn;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (f_node[mid] < id) lo = mid + 1;
+        else hi = mid;
+    }
+    pair[t] = (lo < nn && f_node[lo] == id) ? lo : -1;
+}
+
+// The batched forms of k_replay_bow / k_replay_bow_finish (mode 0: SearchByBoW(KeyFrame*, Frame&) per key frame): one BowProblem per key frame in
+// device memory -- its own feature vector, descriptors, angles, pair_b, match row, histogram, counters and entries; the frame's side (fb, desc_b,
+// angle_b) is the resident handle's for all of them.  Key frames share nothing they write, so each row is what the single call computes.
+// k_replay_bow_batch: grid (ceil(max fa.n_nodes / 4), n_kf), block 256.  k_replay_bow_finish_batch: grid n_kf, block 64.
+__global__ __launch_bounds__(256) void k_replay_bow_batch(const BowProblem *__restrict__ probs) { replay_bow_wave(probs[blockIdx.y]); }
+__global__ __launch_bounds__(64) void k_replay_bow_finish_batch(const BowProblem *__restrict__ probs) { replay_bow_finish(probs[blockIdx.x]); }
 
 // ---------------------------------------------------------------------------------------------------------
 // k_tri_kb8_stereo: the per-query loop of Frame::ComputeStereoFishEyeMatches (Frame.cc:1147-1163) behind k_knn2, a LANE per left feature (the

@@ -284,6 +284,9 @@ struct orbx_vocabulary {
     int device = 0, k = 0, L = 0, n_nodes = 0;
     int32_t *child_ptr = nullptr, *child_idx = nullptr, *word_id = nullptr;
     uint8_t *node_desc = nullptr;
+    int max_word = -1;                 // the largest word id of the tree
+    uint8_t *word_pos = nullptr;       // [n_words] m_words[id]->weight > 0 (orbx_vocabulary_set_word_weights); NULL: no word is stopped
+    int n_words = 0;
 };
 
 extern "C" {
@@ -563,6 +566,15 @@ struct orbx_frame {
     float bounds[4] = {0, 0, 0, 0};
     std::vector<int32_t> h_match;     // [cap]: results of a call made while N was still on the device
     size_t off_kps = 0, off_desc = 0, off_ur = 0, off_count = 0, off_scale = 0, off_gstart = 0, off_gorder = 0;
+    // Frame::ComputeBoW (orbx_frame_compute_bow): word / node id per feature, the FeatureVector (ascending node ids, CSR, feature indices) with its
+    // node count on the device, and mvKeysUn[i].angle.  Valid until the next load.
+    int32_t *bow_word = nullptr, *bow_node = nullptr, *fv_ptr = nullptr, *fv_index = nullptr, *fv_meta = nullptr;
+    uint32_t *fv_node = nullptr;
+    float *angle = nullptr;
+    bool bow_valid = false;
+    std::vector<int32_t> h_bow;       // [2 cap]: word / node ids downloaded while N was still on the device
+    const orbx_vocabulary *bow_voc = nullptr;
+    int bow_levelsup = 0;
 };
 
 namespace {
@@ -798,6 +810,8 @@ int orbx_frame_create(orbx_matcher *m, int cap, orbx_frame **out) {
     f->off_kps = carve(28 * (size_t)cap); f->off_desc = carve(32 * (size_t)cap); f->off_ur = carve(4 * (size_t)cap);
     f->off_count = carve(4); f->off_scale = carve(4 * (size_t)kFrameMaxLevels);
     f->off_gstart = carve(2 * ((size_t)kGridCells + 1)); f->off_gorder = carve(2 * (size_t)cap);
+    const size_t off_bw = carve(4 * (size_t)cap), off_bn = carve(4 * (size_t)cap), off_fn = carve(4 * (size_t)cap), off_fp = carve(4 * ((size_t)cap + 1)),
+                 off_fi = carve(4 * (size_t)cap), off_fm = carve(16), off_an = carve(4 * (size_t)cap);
     f->stage_bytes = f->off_count;   // the rows: keypoints, descriptors, mvuRight at the device layout's offsets
     hipError_t e = hipMalloc((void **)&f->dev, o);
     if (e == hipSuccess) e = hipHostMalloc((void **)&f->stage, f->stage_bytes, hipHostMallocCoherent);   // read by k_xfer's lanes
@@ -808,6 +822,9 @@ int orbx_frame_create(orbx_matcher *m, int cap, orbx_frame **out) {
     f->kps = (orbx_keypoint *)(f->dev + f->off_kps); f->desc = f->dev + f->off_desc; f->u_right = (float *)(f->dev + f->off_ur);
     f->count = (int32_t *)(f->dev + f->off_count); f->scale = (float *)(f->dev + f->off_scale);
     f->gstart = (uint16_t *)(f->dev + f->off_gstart); f->gorder = (uint16_t *)(f->dev + f->off_gorder);
+    f->bow_word = (int32_t *)(f->dev + off_bw); f->bow_node = (int32_t *)(f->dev + off_bn); f->fv_node = (uint32_t *)(f->dev + off_fn);
+    f->fv_ptr = (int32_t *)(f->dev + off_fp); f->fv_index = (int32_t *)(f->dev + off_fi); f->fv_meta = (int32_t *)(f->dev + off_fm);
+    f->angle = (float *)(f->dev + off_an);
     f->n_known = true;   // an empty frame until the first load
     *out = f;
     return ORBX_OK;
@@ -864,7 +881,7 @@ int orbx_frame_load_host(orbx_frame *f, const orbx_frame_desc *d) {
     ORBX_HIP(hipGetLastError());
     ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
     f->stage_busy = true;
-    f->n = n; f->n_known = true; f->has_ur = d->u_right != nullptr; f->loaded = true;
+    f->n = n; f->n_known = true; f->has_ur = d->u_right != nullptr; f->loaded = true; f->bow_valid = false;
     return ORBX_OK;
 }
 
@@ -891,7 +908,7 @@ int orbx_frame_load_batch(orbx_frame *f, orbx_extractor *ex, int frame, const fl
     ORBX_HIP(hipGetLastError());
     ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
     ORBX_HIP(hipStreamWaitEvent(ex->stream, f->ev_done, 0));
-    f->n_known = false; f->has_ur = false; f->loaded = true;
+    f->n_known = false; f->has_ur = false; f->loaded = true; f->bow_valid = false;
     return ORBX_OK;
 }
 
@@ -1092,6 +1109,19 @@ extern "C" int orbx_search_by_projection_window(orbx_matcher *m, const orbx_fram
     ProjArgs a = {frame, occupied, n_q, q_x, q_y, q_r, nullptr, q_min_level, q_max_level, q_desc, nullptr, q_has_obs,
                   q_angle, 2, 0.f, check_orientation, match, max_dist};
     return run_projection(m, a);
+}
+
+// the same on a resident frame (Tracking::Relocalization's second stage, Tracking.cc:3726,3740): the frame's rows and grid are the handle's
+extern "C" int orbx_frame_search_by_projection_window(orbx_matcher *m, orbx_frame *f, const uint8_t *occupied, int n_q, const float *q_x,
+                                                      const float *q_y, const float *q_r, const int32_t *q_min_level, const int32_t *q_max_level,
+                                                      const float *q_angle, const uint8_t *q_desc, const uint8_t *q_has_obs, float max_dist,
+                                                      int check_orientation, int32_t *match) {
+    if (!m || !f || f->owner != m || !match || n_q < 0) return ORBX_E_BAD_ARG;
+    if (n_q > 0 && (!q_x || !q_y || !q_r || !q_min_level || !q_max_level || !q_desc || (check_orientation && !q_angle))) return ORBX_E_BAD_ARG;
+    const orbx_frame_desc d = frame_desc_of(f);
+    ProjArgs a = {&d, occupied, n_q, q_x, q_y, q_r, nullptr, q_min_level, q_max_level, q_desc, nullptr, q_has_obs,
+                  q_angle, 2, 0.f, check_orientation, match, max_dist};
+    return run_projection(m, a, f);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2264,6 +2294,7 @@ extern "C" int orbx_vocabulary_create(int device, int L, int n_nodes, const int3
     ORBX_HIP(hipMemcpy(v->child_idx, child_idx, 4 * (size_t)nchild, hipMemcpyHostToDevice));
     ORBX_HIP(hipMemcpy(v->word_id, word_id, 4 * (size_t)n_nodes, hipMemcpyHostToDevice));
     ORBX_HIP(hipMemcpy(v->node_desc, node_desc, 32 * (size_t)n_nodes, hipMemcpyHostToDevice));
+    for (int i = 0; i < n_nodes; i++) v->max_word = std::max(v->max_word, (int)word_id[i]);
     *out = v;
     return ORBX_OK;
 }
@@ -2272,7 +2303,23 @@ extern "C" void orbx_vocabulary_destroy(orbx_vocabulary *v) {
     if (!v) return;
     (void)hipSetDevice(v->device);
     (void)hipFree(v->child_ptr); (void)hipFree(v->child_idx); (void)hipFree(v->word_id); (void)hipFree(v->node_desc);
+    if (v->word_pos) (void)hipFree(v->word_pos);
     delete v;
+}
+
+// the stop-word test of TemplatedVocabulary::transform (`if (w > 0)`, TemplatedVocabulary.h:1170): only the sign of each word's weight is kept
+extern "C" int orbx_vocabulary_set_word_weights(orbx_vocabulary *v, const double *weight, int n_words) {
+    if (!v || !weight || n_words <= v->max_word || n_words <= 0) return ORBX_E_BAD_ARG;   // every word id of the tree needs a weight
+    std::vector<uint8_t> pos((size_t)n_words);
+    for (int i = 0; i < n_words; i++) pos[i] = weight[i] > 0 ? 1 : 0;
+    ORBX_HIP(hipSetDevice(v->device));
+    uint8_t *d = nullptr;
+    ORBX_HIP(hipMalloc((void **)&d, (size_t)n_words));
+    hipError_t e = hipMemcpy(d, pos.data(), (size_t)n_words, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); set_error(hipGetErrorString(e)); return ORBX_E_HIP; }
+    if (v->word_pos) (void)hipFree(v->word_pos);
+    v->word_pos = d; v->n_words = n_words;
+    return ORBX_OK;
 }
 
 extern "C" int orbx_bow_transform(orbx_matcher *m, const orbx_vocabulary *v, const uint8_t *desc, int n, int levelsup, int32_t *word_id,
@@ -2290,6 +2337,182 @@ extern "C" int orbx_bow_transform(orbx_matcher *m, const orbx_vocabulary *v, con
                        v->L, levelsup, dd, n, dw, dn);
     D2H(word_id, dw, 4 * (size_t)n); D2H(node_id, dn, 4 * (size_t)n);
     SYNC_AND_DELIVER();
+    return ORBX_OK;
+}
+
+// Frame::ComputeBoW (Frame.cc:738-745) on a resident frame: k_frame_bow_transform over the handle's descriptors, then k_frame_featvec builds the
+// FeatureVector in the handle.  Nothing of the frame is uploaded; without downloads nothing waits (the launches are ordered on the owner's stream).
+extern "C" int orbx_frame_compute_bow(orbx_matcher *m, orbx_frame *f, const orbx_vocabulary *v, int levelsup, int32_t *word_id, int32_t *node_id) {
+    if (!m || !f || !v || f->owner != m || v->device != m->device) return ORBX_E_BAD_ARG;
+    ORBX_HIP(hipSetDevice(m->device));
+    const bool down = word_id || node_id;
+    const int n_host = f->n_known ? f->n : -1;
+    const int nc = f->n_known ? f->n : f->cap;   // features the kernels may see
+    int sort_cap = 1;
+    while (sort_cap < nc) sort_cap <<= 1;
+    const size_t lds = 8 * (size_t)sort_cap;
+    int r = m->reserve_all(Arena::pad(8 * (size_t)nc) + 4096);   // (the staging of the downloads)
+    if (r != ORBX_OK) return r;
+    m->begin();
+    f->bow_valid = false;
+    if (nc > 0)
+        hipLaunchKernelGGL(k_frame_bow_transform, dim3((nc + 15) / 16), dim3(256), 0, m->stream, v->child_ptr, v->child_idx, v->node_desc, v->word_id,
+                           v->L, levelsup, f->desc, f->count, n_host, f->cap, f->bow_word, f->bow_node);
+    FrameBow B;
+    memset(&B, 0, sizeof(B));
+    B.count = f->count; B.n_host = n_host; B.cap = f->cap; B.kps = f->kps; B.word = f->bow_word; B.node = f->bow_node;
+    B.word_pos = v->word_pos; B.n_words = v->n_words;
+    B.angle = f->angle; B.fv_node = f->fv_node; B.fv_ptr = f->fv_ptr; B.fv_index = f->fv_index; B.fv_meta = f->fv_meta;
+    if (lds > 64 * 1024) ORBX_HIP(hipFuncSetAttribute((const void *)k_frame_featvec, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_frame_featvec, dim3(1), dim3(1024), lds, m->stream, B, sort_cap);
+    ORBX_HIP(hipGetLastError());
+    f->bow_valid = true; f->bow_voc = v; f->bow_levelsup = levelsup;
+    if (!down || nc == 0) return ORBX_OK;
+    if (n_host >= 0) {
+        if (word_id) D2H(word_id, f->bow_word, 4 * (size_t)nc);
+        if (node_id) D2H(node_id, f->bow_node, 4 * (size_t)nc);
+        SYNC_AND_DELIVER();
+        return ORBX_OK;
+    }
+    f->h_bow.resize(2 * (size_t)f->cap);   // N comes back with the ids
+    D2H(f->h_bow.data(), f->bow_word, 4 * (size_t)nc);
+    D2H(f->h_bow.data() + f->cap, f->bow_node, 4 * (size_t)nc);
+    D2H(&f->n, f->count, 4);
+    SYNC_AND_DELIVER();
+    f->n = std::min(std::max(f->n, 0), f->cap);
+    f->n_known = true;
+    if (word_id) memcpy(word_id, f->h_bow.data(), 4 * (size_t)f->n);
+    if (node_id) memcpy(node_id, f->h_bow.data() + f->cap, 4 * (size_t)f->n);
+    return ORBX_OK;
+}
+
+// ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (ORBmatcher.cc:223-425) of the resident frame against n_kf key frames at once
+// (Tracking::Relocalization, Tracking.cc:3670-3700; n_kf = 1: TrackReferenceKeyFrame): one upload run (the key frames and one BowProblem each),
+// k_bow_pair_nodes, k_replay_bow_batch and k_replay_bow_finish_batch, one download run, one synchronisation -- whatever n_kf is.
+extern "C" int orbx_frame_search_by_bow(orbx_matcher *m, orbx_frame *f, int n_kf, const orbx_bow_keyframe *kfs, float nnratio, int check_orientation,
+                                        int32_t *match, int match_stride, int32_t *nmatches) {
+    if (!m || !f || f->owner != m || !f->bow_valid || n_kf < 0) return ORBX_E_BAD_ARG;
+    if (n_kf > ORBX_MAX_BOW_KEYFRAMES) return ORBX_E_TOO_LARGE;
+    if (n_kf == 0) return ORBX_OK;
+    if (!kfs || !match || !nmatches || match_stride < 0) return ORBX_E_BAD_ARG;
+    size_t tot_nodes = 0;
+    int max_nodes = 0;
+    for (int k = 0; k < n_kf; k++) {   // every key frame is checked before anything is enqueued
+        const orbx_bow_keyframe &K = kfs[k];
+        const orbx_featvec &F = K.fv;
+        if (K.n > 65535) return ORBX_E_TOO_LARGE;
+        if (K.n < 0 || F.n_nodes < 0 || !F.node_ptr || (F.n_nodes > 0 && !F.node_id) || F.node_ptr[0] != 0) return ORBX_E_BAD_ARG;
+        if (K.n > 0 && (!K.descriptors || (check_orientation && !K.angle))) return ORBX_E_BAD_ARG;
+        for (int j = 0; j < F.n_nodes; j++)   // a CSR, node ids strictly ascending (std::map order: the pairing is a binary search)
+            if (F.node_ptr[j + 1] < F.node_ptr[j] || (j > 0 && F.node_id[j] <= F.node_id[j - 1])) return ORBX_E_BAD_ARG;
+        const int ni = F.node_ptr[F.n_nodes];
+        if (ni > 0 && !F.index) return ORBX_E_BAD_ARG;
+        for (int a = 0; a < ni; a++)
+            if (F.index[a] < 0 || F.index[a] >= K.n) return ORBX_E_BAD_ARG;
+        tot_nodes += (size_t)F.n_nodes;
+        max_nodes = std::max(max_nodes, F.n_nodes);
+    }
+    int n = f->n_known ? f->n : -1;
+    if (n < 0 && match_stride < f->cap) { const int rc = frame_count(f, &n); if (rc != ORBX_OK) return rc; }   // the rows must fit the stride
+    if (n >= 0 && match_stride < n) return ORBX_E_BAD_ARG;
+    const int nc = n >= 0 ? n : f->cap;   // features the device rows are sized for
+    for (int k = 0; k < n_kf; k++) {
+        nmatches[k] = 0;
+        for (int i = 0; i < std::max(n, 0); i++) match[(size_t)k * match_stride + i] = -1;
+    }
+    if (n == 0) return ORBX_OK;
+    ORBX_HIP(hipSetDevice(m->device));
+    const int ne = std::max(nc, 1);
+    size_t need = Arena::pad(4 * (tot_nodes + 1)) * 2 + Arena::pad(sizeof(BowProblem) * (size_t)n_kf) + Arena::pad(4 * (size_t)n_kf * nc) +
+                  Arena::pad(4 * (size_t)n_kf) + Arena::pad(4 * (size_t)n_kf * (ORBX_HISTO_LENGTH + 2)) + Arena::pad(4 * (size_t)n_kf * ne) + 4096;
+    for (int k = 0; k < n_kf; k++) {
+        const size_t nk = (size_t)kfs[k].n, nn = (size_t)kfs[k].fv.n_nodes, ni = (size_t)kfs[k].fv.node_ptr[nn];
+        need += Arena::pad(32 * nk) + Arena::pad(4 * nk) + Arena::pad(nk) + Arena::pad(4 * (nn + 1)) + Arena::pad(4 * (ni + 1));
+    }
+    int r = m->reserve_all(need);
+    if (r != ORBX_OK) return r;
+    Arena &A = m->arena;
+    m->begin();
+    std::vector<BowProblem> probs((size_t)n_kf);
+    std::vector<uint8_t> skip;
+    // the uploads, side by side: per key frame its rows and feature vector, then every node id of the batch, then the problem records
+    for (int k = 0; k < n_kf; k++) {
+        const orbx_bow_keyframe &K = kfs[k];
+        const int nn = K.fv.n_nodes, ni = K.fv.node_ptr[nn];
+        BowProblem &P = probs[k];
+        memset(&P, 0, sizeof(P));
+        uint8_t *dd = A.take<uint8_t>(32 * (size_t)K.n);
+        H2D(dd, K.descriptors, 32 * (size_t)K.n);
+        P.desc_a = dd;
+        if (K.angle && check_orientation) { float *da = A.take<float>(K.n); H2D(da, K.angle, 4 * (size_t)K.n); P.angle_a = da; }
+        if (K.valid) {
+            skip.resize((size_t)K.n);
+            for (int i = 0; i < K.n; i++) skip[i] = K.valid[i] ? 0 : 1;
+            uint8_t *ds = A.take<uint8_t>(K.n);
+            H2D(ds, skip.data(), (size_t)K.n);
+            P.skip_a = ds;
+        }
+        int32_t *dp = A.take<int32_t>(nn + 1), *di = A.take<int32_t>(ni + 1);
+        H2D(dp, K.fv.node_ptr, 4 * ((size_t)nn + 1));
+        H2D(di, K.fv.index, 4 * (size_t)ni);
+        P.fa.node_ptr = dp; P.fa.index = di; P.fa.n_nodes = nn;
+        P.na = K.n;
+    }
+    uint32_t *dkn = A.take<uint32_t>(tot_nodes + 1);
+    {
+        size_t o = 0;
+        for (int k = 0; k < n_kf; k++) {
+            const int nn = kfs[k].fv.n_nodes;
+            H2D(dkn + o, kfs[k].fv.node_id, 4 * (size_t)nn);
+            probs[k].fa.node_id = dkn + o;
+            o += (size_t)nn;
+        }
+    }
+    BowProblem *dP = A.take<BowProblem>(n_kf);
+    // device-only: the pairing, the rows (filled with -1) and match counts side by side (one download run), histograms + counters (zeroed), entries
+    int32_t *dpair = A.take<int32_t>(tot_nodes + 1);
+    int32_t *dmatch = A.take<int32_t>((size_t)n_kf * nc), *dnm = A.take<int32_t>(n_kf);
+    int32_t *dhist = A.take<int32_t>((size_t)n_kf * (ORBX_HISTO_LENGTH + 2));
+    int32_t *dent = A.take<int32_t>((size_t)n_kf * ne);
+    {
+        size_t o = 0;
+        for (int k = 0; k < n_kf; k++) {
+            BowProblem &P = probs[k];
+            P.mode = 0;
+            P.fb.node_id = f->fv_node; P.fb.node_ptr = f->fv_ptr; P.fb.index = f->fv_index; P.fb.n_nodes = 0;   // (the frame's node count stays on the device)
+            P.desc_b = f->desc; P.angle_b = f->angle; P.nb = nc;
+            P.nnratio = nnratio; P.check_orientation = check_orientation ? 1 : 0;
+            P.match = dmatch + (size_t)k * nc; P.nmatches = dnm + k;
+            P.hist = dhist + (size_t)k * (ORBX_HISTO_LENGTH + 2); P.counters = P.hist + ORBX_HISTO_LENGTH;
+            P.entries = dent + (size_t)k * ne;
+            P.pair_b = dpair + o;
+            o += (size_t)P.fa.n_nodes;
+        }
+    }
+    H2D(dP, probs.data(), sizeof(BowProblem) * (size_t)n_kf);
+    ORBX_HIP(m->fill(dmatch, 0xff, 4 * (size_t)n_kf * nc));
+    ORBX_HIP(m->fill(dhist, 0, 4 * (size_t)n_kf * (ORBX_HISTO_LENGTH + 2)));
+    if (tot_nodes > 0) {
+        hipLaunchKernelGGL(k_bow_pair_nodes, dim3((unsigned)((tot_nodes + 255) / 256)), dim3(256), 0, m->exec(), dkn, (int)tot_nodes, f->fv_node,
+                           f->fv_meta, dpair);
+        hipLaunchKernelGGL(k_replay_bow_batch, dim3((unsigned)((max_nodes + 3) / 4), (unsigned)n_kf), dim3(256), 0, m->exec(), (const BowProblem *)dP);
+    }
+    hipLaunchKernelGGL(k_replay_bow_finish_batch, dim3((unsigned)n_kf), dim3(64), 0, m->exec(), (const BowProblem *)dP);
+    ORBX_HIP(hipGetLastError());
+    if (n >= 0) {
+        for (int k = 0; k < n_kf; k++) D2H(match + (size_t)k * match_stride, dmatch + (size_t)k * nc, 4 * (size_t)n);
+    } else {   // N comes back with the results
+        f->h_match.resize((size_t)n_kf * nc);
+        D2H(f->h_match.data(), dmatch, 4 * (size_t)n_kf * nc);
+        D2H(&f->n, f->count, 4);
+    }
+    D2H(nmatches, dnm, 4 * (size_t)n_kf);
+    SYNC_AND_DELIVER();
+    if (n < 0) {
+        f->n = std::min(std::max(f->n, 0), f->cap);
+        f->n_known = true;
+        for (int k = 0; k < n_kf; k++) memcpy(match + (size_t)k * match_stride, f->h_match.data() + (size_t)k * nc, 4 * (size_t)f->n);
+    }
     return ORBX_OK;
 }
 

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import KP_DTYPE, FeatVec, FrameDesc, PAIR_PREDICATE, PinholeGate, check, ptr
+from ._lib import KP_DTYPE, BowKeyFrame, FeatVec, FrameDesc, PAIR_PREDICATE, PinholeGate, check, ptr
 
 
 @dataclass
@@ -103,6 +103,18 @@ class DeviceFrame:
         check(self._L.orbx_frame_count(self._h, C.byref(n)), "orbx_frame_count")
         return n.value
 
+    def compute_bow(self, voc: "ORBVocabulary", levelsup: int = 4, download: bool = True):
+        """Frame::ComputeBoW's transform on the resident descriptors (orbx_frame_compute_bow); the FeatureVector stays in the handle for
+        ORBmatcher.SearchByBoWDevice.  download=True returns (word_id[N], node_id[N]); download=False returns None and does not wait."""
+        if not download:
+            check(self._L.orbx_frame_compute_bow(self.matcher._h, self._h, voc._h, int(levelsup), None, None), "orbx_frame_compute_bow")
+            return None
+        w = np.zeros(self.cap, np.int32)
+        nd = np.zeros(self.cap, np.int32)
+        check(self._L.orbx_frame_compute_bow(self.matcher._h, self._h, voc._h, int(levelsup), ptr(w), ptr(nd)), "orbx_frame_compute_bow")
+        n = self.count()   # (known after the call: no further synchronisation)
+        return w[:n], nd[:n]
+
 
 def _f32(a):
     return None if a is None else np.ascontiguousarray(a, np.float32)
@@ -132,6 +144,13 @@ class ORBVocabulary:
         if getattr(self, "_h", None):
             self._L_.orbx_vocabulary_destroy(self._h)
             self._h = None
+
+    def set_word_weights(self, weights):
+        """m_words[id]->weight for every word id (orbx_vocabulary_set_word_weights): words with weight <= 0 are stop words for
+        DeviceFrame.compute_bow's FeatureVector."""
+        w = np.ascontiguousarray(weights, np.float64)
+        check(self._L_.orbx_vocabulary_set_word_weights(self._h, ptr(w), len(w)), "orbx_vocabulary_set_word_weights")
+        return self
 
 
 class ORBmatcher:
@@ -413,17 +432,21 @@ class ORBmatcher:
     # ---- general window form: M3 = SearchByProjection(Frame&, KeyFrame*, ...) (ORBmatcher.cc:1889-2010) and
     #      M4 = SearchByProjection(KeyFrame*, Sim3f&, ...) (ORBmatcher.cc:427-646) ----
     def SearchByProjectionWindow(self, F: FrameView, q: dict, max_dist: float, check_orientation: bool, occupied=None, raw=False):
-        """q: x, y, r, min_level, max_level, angle, desc[, has_obs].  raw: see SearchByProjectionFrame."""
-        fd = F.c_struct()
+        """q: x, y, r, min_level, max_level, angle, desc[, has_obs].  F: FrameView or DeviceFrame.  raw: see SearchByProjectionFrame."""
         nq = len(q["x"])
-        match = np.full(fd.n, -1, np.int32)
         a = dict(x=_f32(q["x"]), y=_f32(q["y"]), r=_f32(q["r"]), lo=_i32(q["min_level"]), hi=_i32(q["max_level"]),
                  ang=_f32(q.get("angle")), d=_u8(q["desc"]), ho=_u8(q.get("has_obs")))
         occ = _u8(occupied)
-        n = check(self._L.orbx_search_by_projection_window(
-            self._h, C.byref(fd), ptr(occ), nq, ptr(a["x"]), ptr(a["y"]), ptr(a["r"]), ptr(a["lo"]), ptr(a["hi"]),
-            ptr(a["ang"]), ptr(a["d"]), ptr(a["ho"]), max_dist, int(check_orientation), ptr(match)),
-            "orbx_search_by_projection_window")
+        args = (ptr(occ), nq, ptr(a["x"]), ptr(a["y"]), ptr(a["r"]), ptr(a["lo"]), ptr(a["hi"]), ptr(a["ang"]), ptr(a["d"]), ptr(a["ho"]),
+                max_dist, int(check_orientation))
+        if isinstance(F, DeviceFrame):
+            match = np.full(self._frame_rows(F, occ), -1, np.int32)
+            n = check(self._L.orbx_frame_search_by_projection_window(self._h, F._h, *args, ptr(match)), "orbx_frame_search_by_projection_window")
+            match = match[:F.count()]
+        else:
+            fd = F.c_struct()
+            match = np.full(fd.n, -1, np.int32)
+            n = check(self._L.orbx_search_by_projection_window(self._h, C.byref(fd), *args, ptr(match)), "orbx_search_by_projection_window")
         return n, (match if raw else np.maximum(match, -1))
 
     # ---- SearchForInitialization (ORBmatcher.cc:648-763) ----
@@ -448,6 +471,24 @@ class ORBmatcher:
                                                    len(fdsc), C.byref(b), self.mfNNratio, int(self.mbCheckOrientation),
                                                    ptr(fm)), "orbx_search_by_bow_frame")
         return n, fm
+
+    def SearchByBoWDevice(self, F: DeviceFrame, kfs):
+        """SearchByBoW(KeyFrame*, Frame&) of the resident frame against every key frame of `kfs` in one call (orbx_frame_search_by_bow; the frame
+        needs DeviceFrame.compute_bow first).  kfs: sequence of (desc, angle, valid, FeatureVector) -- valid may be None.
+        Returns (nmatches[n_kf], match[n_kf, N]): row k = SearchByBoWFrame for key frame k."""
+        n_kf = len(kfs)
+        keep, arr = [], (BowKeyFrame * max(n_kf, 1))()
+        for k, (d, a, v, fv) in enumerate(kfs):
+            d, a, v = _u8(d).reshape(-1, 32), _f32(a), _u8(v)
+            keep.append((d, a, v, fv))
+            arr[k] = BowKeyFrame(d.ctypes.data, None if a is None else a.ctypes.data, None if v is None else v.ctypes.data, len(d), fv.c_struct())
+        stride = F.cap
+        match = np.full((max(n_kf, 1), stride), -1, np.int32)
+        nm = np.zeros(max(n_kf, 1), np.int32)
+        check(self._L.orbx_frame_search_by_bow(self._h, F._h, n_kf, arr, self.mfNNratio, int(self.mbCheckOrientation), ptr(match), stride, ptr(nm)),
+              "orbx_frame_search_by_bow")
+        del keep
+        return nm[:n_kf], match[:n_kf, :F.count()]
 
     def SearchByBoWKeyFrames(self, desc1, angle1, valid1, fv1: FeatureVector, desc2, angle2, valid2, fv2: FeatureVector):
         d1, a1, v1, d2, a2, v2 = _u8(desc1), _f32(angle1), _u8(valid1), _u8(desc2), _f32(angle2), _u8(valid2)
