@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- ORB kfeatures/sec, extract + match (BASELINE.json metric), on 1..N MI355X of one node.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload euroc|kitti|tumvi] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload euroc|kitti|tumvi] [--dump-outputs DIR] [--full]
 
 A "step" = one pass of the hot path over one batch of synthetic frames of ONE camera sequence per GPU:
   euroc (default, the metric's configuration): 256 frames 752x480, nFeatures=1000 -- extract (pyramid, FAST, quad-tree,
@@ -11,17 +11,21 @@ A "step" = one pass of the hot path over one batch of synthetic frames of ONE ca
         Frame::ComputeStereoMatches (row-band Hamming, SAD sub-pixel, median rejection) on the device + D2H;
   tumvi (BASELINE config 4): 128 frames 1024x1024, nFeatures=1500 -- extract + SearchByProjection(Frame, MapPoints) against
         10,000 map-point descriptors per frame (Tracking.cc:3390-3413) + D2H.
-`value` follows the bench contract: inputs are resident in HBM when the timed region starts.  The same run also measures the
-host-input rate (`pcie_inclusive`: frames start in pinned host memory, orbx_extract_batch_host uploads batch i+1 while batch
-i computes) -- SURVEY.md 8d's "wall clock covering H2D ... D2H".
+`value` follows the bench contract: inputs are resident in HBM when the timed region starts.
+
+A plain run does only what that figure needs: set-up (frames, extractor, settle steps), the W warm-up steps, the K timed steps, the
+--dump-outputs arrays and the JSON line.  Everything else the bench measures or checks runs with --full (each part still has its own
+option, which sets or skips it with or without --full): the host-input rate (`pcie_inclusive`: frames start in pinned host memory,
+orbx_extract_batch_host uploads batch i+1 while batch i computes -- SURVEY.md 8d's "wall clock covering H2D ... D2H"), the parity check,
+the repeated regions, the per-kernel profile and PMC passes, the CPU baseline, the latencies and the other two workloads.
 
 Processes: with WORLD_SIZE unset this file is a LAUNCHER: it starts one rank process per GPU itself (RANK / LOCAL_RANK /
 WORLD_SIZE / MASTER_ADDR=127.0.0.1 / MASTER_PORT in the environment) and relays rank 0's JSON line; under
 torch.distributed.run it is a rank directly (and --gpus must equal WORLD_SIZE).  Ranks shard independent camera sequences
 (seed = 10 + rank), no data-path collective; torch.distributed over GLOO (host tensors) carries only the timing
 barrier and the gather of every rank's (seconds, features) -- no RCCL communicator is created on the GPUs (north_star: "RCCL not
-required").  After the timed loop rank 0 checks EVERY frame and EVERY match vector of the last timed step (keypoints, descriptors, match
-indices) against the CPU oracle: "parity_checked" in the JSON line; a mismatch is a failed run.  The K timed steps are then repeated
+required").  With --full, after the timed loop rank 0 checks EVERY frame and EVERY match vector of the last timed step (keypoints, descriptors,
+match indices) against the CPU oracle: "parity_checked" in the JSON line; a mismatch is a failed run.  The K timed steps are then repeated
 (`repeats`: median / min / max over the regions), the drop-in call is timed one frame at a time (`latency`), and at --gpus 1 the other two
 BASELINE configurations (KITTI stereo, TUM-VI map-point search) run as child processes of the same file (`other_workloads`).
 """
@@ -655,11 +659,20 @@ def pinned(torch, shape, dtype):
     return torch.empty(shape, dtype=dtype).pin_memory()
 
 
+def synth_frames(make, n):
+    """[make(t) for t in range(n)] on a few host threads.  A synthetic frame draws its noise from a generator seeded by its own index
+    (synth.frame_from_canvas), so the frames do not depend on the order they are made in; numpy releases the GIL in the draws.  In one
+    thread the 768 frames of the euroc workload are several seconds of a plain run."""
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, min(8, len(os.sched_getaffinity(0))))) as pool:
+        return list(pool.map(make, range(n)))
+
+
 def bench_threads(args):
     """`--threads`: SURVEY.md 8(e) as ONE process -- N host worker threads, thread s on GPU s mod G, each with its own extractor (its own HIP streams),
     its own resident frames and its own pinned result ring; no process group, no collective.  The same extract + match + download loop as the
     euroc workload's `value`; value = features of all threads / the slowest thread's time between a common start and its own last result.
-    Parity of every thread's last step against the oracle.  (tests/cpp/multi_gpu_demo.cpp is the same shape in C++.)"""
+    With --full (or --verify), parity of every thread's last step against the oracle.  (tests/cpp/multi_gpu_demo.cpp is the same shape in C++.)"""
     import threading
     import torch
     import orb_slam3_amd as osa
@@ -777,12 +790,12 @@ def bench_euroc(R):
         canvas = synth.make_scene_canvas(a.scene, seed)
         if a.scene != "quads":
             data = f"synthetic, STRESS scene {a.scene} (synth.make_texture_canvas: 1/f noise + dense high-contrast texture; blend:<a> mixes it into the quad scene); not the metric's scene"
-        allf = np.stack([synth.frame_from_canvas(canvas, t, W, H, 1000 * seed + t) for t in range(NS * B)])
+        allf = np.stack(synth_frames(lambda t: synth.frame_from_canvas(canvas, t, W, H, 1000 * seed + t), NS * B))
     sets = [np.ascontiguousarray(allf[k * B:(k + 1) * B]) for k in range(NS)]
     frames = sets[0]
-    h_sets = [torch.from_numpy(f).pin_memory() for f in sets]   # the camera thread's buffers (pcie_inclusive leg)
     d_sets = [torch.from_numpy(f).cuda() for f in sets]         # resident inputs of the contract's `value`
     torch.cuda.synchronize()
+    h_sets = []         # the camera thread's buffers: pinned copies of the sets, made for the pcie_inclusive leg (--full)
     rotate = [True]
     step_no = [0]       # steps enqueued so far: step i reads set i mod NS
     last_set = [0]
@@ -899,7 +912,7 @@ def bench_euroc(R):
     repeats = repeats_block(regions, a.steps, gaps)
     # ---- one more region over ONE resident set (what rounds 1-4 timed): does the Infinity Cache serve the frame reads then? ----
     single = None
-    if NS > 1:
+    if a.full and NS > 1:
         rotate[0] = False
         t0 = R.timed_begin([ex], warm=lambda: run(max(a.warmup, 1), False))
         STAMPS.clear()
@@ -911,23 +924,26 @@ def bench_euroc(R):
     R.per_rank = per_rank
 
     # ---- the same loop with the frames starting in pinned host memory (upload inside the timed region) ----
-    dt_h, feats_h = timed(True)
-    dt_h_max, feats_h_all = R.reduce(dt_h, feats_h)
-    per_rank_host = R.per_rank
-    R.per_rank = per_rank     # `per_rank` of the line belongs to `value` (resident inputs); the host-input leg carries its own list
-    pcie_parity = None
-    if a.verify > 0:
-        pcie_parity = verify_euroc(sets[last_set[0]], host[(a.steps - 1) % 2], a.verify, W, H, NF, ex)   # the host-input path delivers the same results
-    for pr, pc in zip(per_rank_host, R.gather_objects(pcie_parity)):
-        pr["parity_checked"] = pc
-    pcie = {"value": round(feats_h_all / dt_h_max / 1e3, 2), "unit": "kfeatures/s", "ms_per_step": round(dt_h_max / a.steps * 1e3, 3),
-            "h2d_bytes_per_step": int(B * W * H), "h2d_GBs": round(B * W * H / (dt_h_max / a.steps) / 1e9, 1), "host_affinity": R.numa,
-            "parity_checked": pcie_parity, "per_rank": per_rank_host,
-            "note": "frames in pinned host memory; orbx_extract_batch_host uploads batch i+1 on its own stream while batch i computes"}
+    pcie = None
+    if a.full:
+        h_sets.extend(torch.from_numpy(f).pin_memory() for f in sets)
+        dt_h, feats_h = timed(True)
+        dt_h_max, feats_h_all = R.reduce(dt_h, feats_h)
+        per_rank_host = R.per_rank
+        R.per_rank = per_rank     # `per_rank` of the line belongs to `value` (resident inputs); the host-input leg carries its own list
+        pcie_parity = None
+        if a.verify > 0:
+            pcie_parity = verify_euroc(sets[last_set[0]], host[(a.steps - 1) % 2], a.verify, W, H, NF, ex)   # the host-input path delivers the same results
+        for pr, pc in zip(per_rank_host, R.gather_objects(pcie_parity)):
+            pr["parity_checked"] = pc
+        pcie = {"value": round(feats_h_all / dt_h_max / 1e3, 2), "unit": "kfeatures/s", "ms_per_step": round(dt_h_max / a.steps * 1e3, 3),
+                "h2d_bytes_per_step": int(B * W * H), "h2d_GBs": round(B * W * H / (dt_h_max / a.steps) / 1e9, 1), "host_affinity": R.numa,
+                "parity_checked": pcie_parity, "per_rank": per_rank_host,
+                "note": "frames in pinned host memory; orbx_extract_batch_host uploads batch i+1 on its own stream while batch i computes"}
 
     # ---- per-kernel timing with HIP events on the extractor's stream (separate, untimed, serialized passes) ----
     roofline, kernels = None, {}
-    if R.rank == 0 and not a.no_profile:
+    if R.rank == 0 and a.profile:
         passes = 3
         ex.profile_enable(True)
         for _ in range(passes):
@@ -985,8 +1001,8 @@ def bench_euroc(R):
     out.update({"roofline": roofline, "cpu_baseline": cpu, "pcie_inclusive": pcie, "parity_checked": parity, "kernels": kernels,
                 "host_enqueue_ms_per_step": round(enqueue_ms, 3), "settle_ms_per_step": round(settle_ms, 3),
                 "repeats": repeats, "latency": latency, "other_workloads": others, "input_sets": NS, "single_input_set": single, "dump_outputs": dump,
-                "value_device_resident": round(feats_all / dt_max / 1e3, 2), "value_pcie_inclusive": pcie["value"],
-                "metric_definition_note": "TWO clocks, both in this line.  `value` (= value_device_resident) = features delivered to pinned host memory "
+                "value_device_resident": round(feats_all / dt_max / 1e3, 2), "value_pcie_inclusive": pcie["value"] if pcie else None,
+                "metric_definition_note": "TWO clocks, both in the --full line.  `value` (= value_device_resident) = features delivered to pinned host memory "
                                           "per second with the input frames already resident in HBM when the timed region starts: the bench contract "
                                           "of this build ('inputs already resident in HBM ... the PCIe-inclusive rate is never value').  SURVEY.md "
                                           "8(d)'s wall clock covering H2D of the images, all kernels, D2H of the results is `value_pcie_inclusive` "
@@ -1284,9 +1300,9 @@ def latency_calls(osa, device, n_calls, n_cpu=5, small=False):
 
 
 def other_workload_child(wl, a):
-    """`python bench.py --workload wl` (same K / W, parity check on, no CPU baseline, no PMC pass) as a child process; the fields a reader of
+    """`python bench.py --workload wl --full` (same K / W, parity check on, no CPU baseline, no PMC pass) as a child process; the fields a reader of
     the euroc line needs."""
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--workload", wl, "--steps", str(a.steps), "--warmup", str(a.warmup), "--cpu-frames", "0",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--workload", wl, "--steps", str(a.steps), "--warmup", str(a.warmup), "--full", "--cpu-frames", "0",
            "--no-pmc", "--gpus", "1"]
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "ORBX_BENCH_RANK_PROCESS"):
@@ -1363,7 +1379,7 @@ def bench_kitti(R):
         data = f"dataset: {dataset.dataset_dir('kitti')} (first {B} pairs)"
     else:
         canvas = synth.make_canvas(30 + R.rank, size=2600, n_shapes=4000)
-        pairs = [synth.make_stereo_pair(30 + R.rank, t, W, H, canvas) for t in range(B)]
+        pairs = synth_frames(lambda t: synth.make_stereo_pair(30 + R.rank, t, W, H, canvas), B)
     dl = torch.from_numpy(np.stack([p[0] for p in pairs])).cuda()
     dr = torch.from_numpy(np.stack([p[1] for p in pairs])).cuda()
     torch.cuda.synchronize()
@@ -1437,7 +1453,7 @@ def bench_kitti(R):
         from oracle import oracle_binding as ob
         from concurrent.futures import ThreadPoolExecutor
         tb = ob.OracleExtractor(NF, 1.2, NLEVELS, 20, 7, flags=ob.FLAG_DESC_FMA).tables()
-        # a.verify >= 4 (the default): EVERY pair of the delivered step, pair-parallel on the host cores (ctypes releases the GIL)
+        # a.verify >= 4 (the --full default): EVERY pair of the delivered step, pair-parallel on the host cores (ctypes releases the GIL)
         fset = list(range(B)) if a.verify >= 4 else sorted(set(int(x) for x in np.linspace(0, B - 1, a.verify)))
         nthreads = max(1, min(os.cpu_count() or 1, 64, len(fset)))
 
@@ -1467,7 +1483,7 @@ def bench_kitti(R):
         parity = {"pairs": len(fset), "of_pairs": B, "oracle_threads": nthreads}
 
     roofline, kernels = None, {}
-    if R.rank == 0 and not a.no_profile:
+    if R.rank == 0 and a.profile:
         passes = 3
         exl.profile_enable(True)
         for _ in range(passes):
@@ -1531,8 +1547,8 @@ def bench_tumvi(R):
         frames = dataset.load_mono("tumvi", B, W, H, start=R.rank * B)
         data = f"dataset: {dataset.dataset_dir('tumvi')} (first {B} frames per rank)"
     else:
-        frames = np.stack([np.clip(np.rint(synth.frame_from_canvas(canvas, t, W, H, 1000 * seed + t).astype(np.float32) * vign), 0, 255).astype(np.uint8)
-                           for t in range(B)])
+        frames = np.stack(synth_frames(lambda t: np.clip(np.rint(synth.frame_from_canvas(canvas, t, W, H, 1000 * seed + t).astype(np.float32) * vign),
+                                                         0, 255).astype(np.uint8), B))
     d_frames = torch.from_numpy(frames).cuda()
     torch.cuda.synchronize()
     ex = osa.ORBextractor(NF, 1.2, NLEVELS, 20, 7, device=R.device)
@@ -1606,7 +1622,7 @@ def bench_tumvi(R):
         from oracle import oracle_binding as ob
         from concurrent.futures import ThreadPoolExecutor
         sf = ob.OracleExtractor(NF, 1.2, NLEVELS, 20, 7, flags=ob.FLAG_DESC_FMA).tables()["scale"]
-        # a.verify >= 4 (the default): EVERY frame of the delivered step, frame-parallel on the host cores
+        # a.verify >= 4 (the --full default): EVERY frame of the delivered step, frame-parallel on the host cores
         fset = list(range(B)) if a.verify >= 4 else sorted(set(int(x) for x in np.linspace(0, B - 1, a.verify)))
         nthreads = max(1, min(os.cpu_count() or 1, 64, len(fset)))
 
@@ -1630,7 +1646,7 @@ def bench_tumvi(R):
         parity = {"frames": len(fset), "of_frames": B, "oracle_threads": nthreads}
 
     roofline, kernels = None, {}
-    if R.rank == 0 and not a.no_profile:
+    if R.rank == 0 and a.profile:
         passes = 3
         ex.profile_enable(True)
         for _ in range(passes):
@@ -1727,9 +1743,13 @@ def launcher(args, argv):
             return 1
 
 
-def main():
-    if len(sys.argv) == 4 and sys.argv[1] == "--reference-build-child":
-        return reference_build_child(sys.argv[2], int(sys.argv[3]))
+# The parts of a run beyond its headline figure, as the defaults of the options that set or skip them: with --full (which also adds the euroc
+# workload's region over one input set and its host-input leg) and in a plain run.  An option given on the command line holds in both.
+FULL_DEFAULTS = {"cpu_frames": 384, "verify": 4, "repeat": 5, "latency": 200, "profile": True, "pmc": True}
+PLAIN_DEFAULTS = {"cpu_frames": 0, "verify": 0, "repeat": 1, "latency": 0, "profile": False, "pmc": False}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -1741,19 +1761,28 @@ def main():
                          "(TUM-VI workload, warm-up 3: 1.29-1.31 ms per step; warm-up 10: 1.07)")
     ap.add_argument("--settle-seconds", dest="settle_seconds", type=float, default=0.25, help="... and at least this long (see settle())")
     ap.add_argument("--batch", type=int, default=0, help="frames (stereo pairs) per step per GPU; 0 = the workload's default (256 / 128 / 128, SURVEY.md 8d)")
-    ap.add_argument("--cpu-frames", type=int, default=384, help="frames in the CPU baseline sample (0 = skip); 384 = about 13 s of one core for euroc")
-    ap.add_argument("--verify", type=int, default=4, help="parity of the last timed step against the CPU oracle on rank 0: >= 4 = every frame and every "
-                                                          "match vector of the step (euroc), 1-3 = that many sampled pairs, 0 = skip")
-    ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--repeat", type=int, default=5, help="timed regions of K steps each (the line's value is the first; `repeats` reports median / min / max)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything the bench measures or checks beyond the headline figure: parity against the CPU oracle, repeated regions, "
+                         "the euroc workload's single-input-set region and host-input leg, per-kernel profile and PMC passes, CPU baseline, "
+                         "latencies, the other two workloads (the defaults marked --full below; a plain run skips them all)")
+    ap.add_argument("--cpu-frames", type=int, default=None, help="frames in the CPU baseline sample (0 = skip; --full: 384 = about 13 s of one core for euroc)")
+    ap.add_argument("--verify", type=int, default=None, help="parity of the last timed step against the CPU oracle on rank 0: >= 4 = every frame and every "
+                                                             "match vector of the step (euroc; the --full default), 1-3 = that many sampled pairs, 0 = skip")
+    ap.add_argument("--profile", dest="profile", action="store_true", default=None,
+                    help="per-kernel times (HIP events, serialized passes after the timed loop) and the roofline (the --full default)")
+    ap.add_argument("--no-profile", dest="profile", action="store_false")
+    ap.add_argument("--repeat", type=int, default=None, help="timed regions of K steps each (the line's value is the first; `repeats` reports median / min / max; "
+                                                             "--full: 5)")
     ap.add_argument("--input-sets", dest="input_sets", type=int, default=3,
                     help="euroc workload: resident input sets of `batch` frames used in rotation by the timed loop (3 x 92 MB > the 256 MB Infinity Cache)")
-    ap.add_argument("--latency", type=int, default=200, help="single-frame orbx_extract calls timed for the `latency` block (0 = skip)")
+    ap.add_argument("--latency", type=int, default=None, help="single-frame orbx_extract calls timed for the `latency` block (0 = skip; --full: 200)")
     ap.add_argument("--other-workloads", dest="other_workloads", action="store_true", default=None,
-                    help="also run the kitti and tumvi workloads as child processes and embed their results (default for the euroc workload at --gpus 1)")
+                    help="also run the kitti and tumvi workloads as child processes and embed their results (--full default for the euroc workload at "
+                         "--gpus 1)")
     ap.add_argument("--no-other-workloads", dest="other_workloads", action="store_false")
-    ap.add_argument("--pmc", dest="pmc", action="store_true", default=True,
-                    help="measure roofline.traffic in this run: two extra rocprofv3 --pmc child passes of a few steps, about 40 s (default at --gpus 1)")
+    ap.add_argument("--pmc", dest="pmc", action="store_true", default=None,
+                    help="with the profile, measure roofline.traffic in this run: two extra rocprofv3 --pmc child passes of a few steps, about 40 s "
+                         "(--full default at --gpus 1)")
     ap.add_argument("--no-pmc", dest="pmc", action="store_false", help="skip the rocprofv3 --pmc child passes (roofline.traffic = null)")
     ap.add_argument("--retries", type=int, default=1, help="launcher: re-run the whole job this many times if a rank process dies (reported in the JSON)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="euroc",
@@ -1765,17 +1794,27 @@ def main():
     ap.add_argument("--scene", default="quads",
                     help="euroc workload, synthetic frames: quads = SURVEY.md 8(d)'s scene (the metric); texture = the stress scene with natural-image "
                          "statistics and 13 x the FAST candidates; blend:<a> (0..1) = (1 - a) quads + a texture, densities in between "
-                         "(whole-step parity as usual; stage_stats_last_step says which paths it took; tools/density_sweep.sh)")
+                         "(whole-step parity with --full; stage_stats_last_step says which paths it took; tools/density_sweep.sh)")
     ap.add_argument("--threads", action="store_true",
                     help="SURVEY.md 8(e) as ONE process: --gpus N host worker threads (thread s on GPU s mod the visible GPUs), each with its own extractor "
-                         "and pinned ring, instead of N rank processes; euroc workload, device-resident clock, parity of every thread's last step")
+                         "and pinned ring, instead of N rank processes; euroc workload, device-resident clock, with --full parity of every thread's last step")
     ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
                     help="write what the last step of a timed region delivered (rank 0) as DIR/<name>.npy, float32 / float64, at most 64 MB "
                          "(a fixed, seeded sample of the step's frames above that); `dump_outputs` in the line lists the files")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    for k, v in (FULL_DEFAULTS if args.full else PLAIN_DEFAULTS).items():
+        if getattr(args, k) is None:
+            setattr(args, k, v)
     if args.other_workloads is None:
-        args.other_workloads = args.workload == "euroc" and args.cpu_frames > 0 and not args.no_profile   # the full default run only
+        args.other_workloads = args.full and args.workload == "euroc" and args.cpu_frames > 0 and args.profile   # the full default run only
+    return args
+
+
+def main():
+    if len(sys.argv) == 4 and sys.argv[1] == "--reference-build-child":
+        return reference_build_child(sys.argv[2], int(sys.argv[3]))
+    args = parse_args()
     if args.pmc_child:
         return pmc_child(args)
     if args.threads:

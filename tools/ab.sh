@@ -14,7 +14,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 O=gpurun_out/$TAG; mkdir -p $O
 run() { wl=$1; shift
-  env "$@" timeout 300 python3 bench.py --workload $wl --cpu-frames 0 --no-pmc --no-other-workloads --latency 0 --no-profile --verify $VERIFY 2>$O/err.txt | tail -1 | \
+  env "$@" timeout 300 python3 bench.py --full --workload $wl --cpu-frames 0 --no-pmc --no-other-workloads --latency 0 --no-profile --verify $VERIFY 2>$O/err.txt | tail -1 | \
     python3 -c "import sys,json
 try:
     d=json.loads(sys.stdin.read()); r=d['repeats']['ms_per_step']; p=d.get('pcie_inclusive') or {}

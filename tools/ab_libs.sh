@@ -2,7 +2,7 @@
 # A/B of two builds of the library (orb_slam3_amd/liborbx_base.so, liborbx_new.so) on the timed loop + serialized kernel stats
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
-run() { python3 bench.py --cpu-frames 0 --no-pmc --no-other-workloads --latency 0 --no-profile --verify 4 --workload $1 2>/dev/null | tail -1 | python3 -c "
+run() { python3 bench.py --full --cpu-frames 0 --no-pmc --no-other-workloads --latency 0 --no-profile --verify 4 --workload $1 2>/dev/null | tail -1 | python3 -c "
 import sys,json; d=json.loads(sys.stdin.read()); r=d['repeats']['ms_per_step']; print('$1 $2', d['value'], 'ms', d['ms_per_step'], 'median', r['median'], 'min', r['min'], 'max', r['max'], bool(d['parity_checked']))"; }
 for rep in 1 2; do for v in base new; do cp orb_slam3_amd/liborbx_$v.so orb_slam3_amd/liborbx.so; for wl in ${WLS:-euroc}; do run $wl $v; done; done; done
 for v in base new; do cp orb_slam3_amd/liborbx_$v.so orb_slam3_amd/liborbx.so

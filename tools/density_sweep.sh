@@ -9,7 +9,7 @@ TAG=${1:-a}
 O=gpurun_out/density_$TAG; rm -rf $O; mkdir -p $O
 for sc in quads blend:0.1 blend:0.2 blend:0.35 blend:0.5 blend:0.75 texture; do
   f=$O/bench_$(echo $sc | tr ':.' '__').json
-  timeout 400 python3 bench.py --scene $sc --cpu-frames 0 --no-pmc --no-other-workloads --latency 0 --repeat 2 --verify 8 2> $O/err.txt | tail -1 > $f
+  timeout 400 python3 bench.py --full --scene $sc --cpu-frames 0 --no-pmc --no-other-workloads --latency 0 --repeat 2 --verify 8 2> $O/err.txt | tail -1 > $f
   python3 - "$sc" "$f" <<'PY'
 import json, sys
 sc, f = sys.argv[1:3]

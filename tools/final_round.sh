@@ -15,14 +15,14 @@ biggest_db() { find "$1" -name "*.db" -printf "%s %p\n" | sort -n | tail -1 | cu
 CHILD="python bench.py --pmc-child --workload euroc"
 timeout 600 python3 -m pytest tests -m gpu -q > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -3 $O/pytest.log; tail -3 $O/pytest.log > $O/profiles_copy/${TAG}_gpu_suite.log
 lap suite
-( time timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 2> $O/bench.err | tail -1 > $O/profiles_copy/${TAG}_bench_euroc.json ) 2>&1 | grep real
+( time timeout 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 2> $O/bench.err | tail -1 > $O/profiles_copy/${TAG}_bench_euroc.json ) 2>&1 | grep real
 cut -c1-300 $O/profiles_copy/${TAG}_bench_euroc.json; echo
 lap bench
 timeout 60 rocprofv3 --kernel-trace --stats -d $O/se -o se -- $CHILD --steps 12 --warmup 3 > /dev/null 2>&1
 python tools/rocprof_summary.py $(biggest_db $O/se) $O/profiles_copy/${TAG}_serialized_kernel_stats.csv
 python3 tools/rocprof_dispatches.py $(biggest_db $O/se) | grep -i "pyr\|strip\|describe" > $O/profiles_copy/${TAG}_dispatches.txt
 lap serialized
-WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 timeout 60 rocprofv3 --kernel-trace --stats -d $O/ov -o ov -- python bench.py --steps 12 --warmup 3 --cpu-frames 0 --no-profile --verify 0 --no-pmc --repeat 1 --latency 0 > /dev/null 2>&1
+WORLD_SIZE=1 RANK=0 LOCAL_RANK=0 timeout 60 rocprofv3 --kernel-trace --stats -d $O/ov -o ov -- python bench.py --full --steps 12 --warmup 3 --cpu-frames 0 --no-profile --verify 0 --no-pmc --repeat 1 --latency 0 > /dev/null 2>&1
 python tools/rocprof_summary.py $(biggest_db $O/ov) $O/profiles_copy/${TAG}_overlapped_kernel_stats.csv > /dev/null
 bash tools/timeline.sh > $O/profiles_copy/${TAG}_timeline.txt 2>&1
 lap overlapped+timeline
@@ -34,7 +34,7 @@ timeout 60 rocprofv3 --pmc WRITE_SIZE -d $O/pw -o pw -- $CHILD --steps 3 --warmu
 python tools/pmc_summary.py $(biggest_db $O/pf) $(biggest_db $O/pw) $TAG && cp profiles/${TAG}_pmc_traffic.csv $O/profiles_copy/
 lap counters
 for wl in tumvi kitti; do
-  timeout 200 python bench.py --workload $wl --cpu-frames 48 2> $O/bench_$wl.err | tail -1 > $O/profiles_copy/${TAG}_bench_$wl.json
+  timeout 200 python bench.py --full --workload $wl --cpu-frames 48 2> $O/bench_$wl.err | tail -1 > $O/profiles_copy/${TAG}_bench_$wl.json
   cut -c1-200 $O/profiles_copy/${TAG}_bench_$wl.json; echo
 done
 lap workloads
@@ -53,14 +53,14 @@ lap calls
 bash tools/density_sweep.sh $TAG > /dev/null 2>&1; cp gpurun_out/density_$TAG/density_sweep.txt $O/profiles_copy/${TAG}_density_sweep.txt; cp gpurun_out/density_$TAG/density_sweep.json $O/profiles_copy/${TAG}_density_sweep.json
 tail -7 $O/profiles_copy/${TAG}_density_sweep.txt | cut -c1-120
 lap density
-timeout 300 python bench.py --gpus 2 --share-gpus --steps 20 --warmup 5 --cpu-frames 0 --no-pmc --no-other-workloads --latency 0 --no-profile 2> $O/two_ranks.err | tail -1 > $O/profiles_copy/${TAG}_two_ranks_one_gpu.json
+timeout 300 python bench.py --full --gpus 2 --share-gpus --steps 20 --warmup 5 --cpu-frames 0 --no-pmc --no-other-workloads --latency 0 --no-profile 2> $O/two_ranks.err | tail -1 > $O/profiles_copy/${TAG}_two_ranks_one_gpu.json
 python3 -c "
 import json
 d = json.load(open('$O/profiles_copy/${TAG}_two_ranks_one_gpu.json')); print('2 ranks on one GPU: n_gpus', d['n_gpus'], 'value', d['value'], 'per_rank', [(r.get('rank'), r.get('parity_checked') is not None) for r in d.get('per_rank', [])], 'pcie', d['pcie_inclusive']['value'])"
 lap two-ranks
 # steady state: one region of K = 4000 pipelined steps (the contract's K = 20 regions pay the pipeline's fill and drain); SOAK=0 skips it
 if [ "${SOAK:-1}" != "0" ]; then
-  timeout 150 python bench.py --gpus 1 --steps 4000 --warmup 5 --cpu-frames 0 --no-pmc --no-other-workloads --latency 0 --no-profile --repeat 2 2> /dev/null | tail -1 > $O/profiles_copy/${TAG}_soak_4000_step_regions.json
+  timeout 150 python bench.py --full --gpus 1 --steps 4000 --warmup 5 --cpu-frames 0 --no-pmc --no-other-workloads --latency 0 --no-profile --repeat 2 2> /dev/null | tail -1 > $O/profiles_copy/${TAG}_soak_4000_step_regions.json
   python3 -c "
 import sys, json
 d = json.load(open('$O/profiles_copy/${TAG}_soak_4000_step_regions.json')); print('K = 4000: ms_per_step', d['ms_per_step'], d['repeats']['ms_per_step_in_order'], 'value', d['value'], 'parity', d['parity_checked'], 'pcie-inclusive', d['pcie_inclusive']['ms_per_step'])"

@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 O=gpurun_out/$TAG; mkdir -p $O
 if [ -n "$PYT" ]; then timeout 900 python3 -m pytest $PYT -m gpu -x -q > $O/pytest.log 2>&1; echo "pytest rc=$?"; tail -4 $O/pytest.log; fi
-run() { env "$@" timeout 200 python3 bench.py --cpu-frames 0 --no-pmc --no-other-workloads --latency 0 --no-profile --verify ${VERIFY:-4} --repeat 3 2>$O/err.txt | tail -1 | \
+run() { env "$@" timeout 200 python3 bench.py --full --cpu-frames 0 --no-pmc --no-other-workloads --latency 0 --no-profile --verify ${VERIFY:-4} --repeat 3 2>$O/err.txt | tail -1 | \
     python3 -c "import sys,json
 try:
     d=json.loads(sys.stdin.read()); r=d['repeats']['ms_per_step']; p=d.get('pcie_inclusive') or {}
