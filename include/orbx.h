@@ -326,6 +326,8 @@ int orbx_search_by_projection_window(orbx_matcher *m, const orbx_frame_desc *fra
  *     holds a COPY: the extractor's next batch waits for it, and later extract calls do not change what the handle holds.  ORBX_E_BAD_ARG when
  *     the frame index is not one of the batch, `ex` is on another device, or the batch's per-frame capacity exceeds `cap`.  No mvuRight.
  *   orbx_frame_count: N, synchronising the matcher's stream once if the count is still on the device (cached until the next load).
+ * A handle holds a monocular / rectified frame (these loads) or a fisheye-stereo frame (orbx_frame_load_host_fisheye,
+ * orbx_frame_load_stereo_fisheye_batch, below); each kind's entry points refuse the other kind with ORBX_E_BAD_ARG.
  * Checks that fail return before anything is enqueued. */
 typedef struct orbx_frame orbx_frame;
 int orbx_frame_create(orbx_matcher *m, int cap, orbx_frame **out);
@@ -344,6 +346,39 @@ int orbx_frame_search_by_projection_frame(orbx_matcher *m, orbx_frame *cur, cons
                                           const float *q_ur, const int32_t *q_octave, const float *q_angle, const uint8_t *q_desc,
                                           const uint8_t *q_has_obs, float th, int level_mode, int check_orientation, int32_t *cur_match);
 /* orbx_frame_search_local_points: below, after orbx_camera / orbx_frame_pose. */
+
+/* ---- fisheye-stereo frames on the handle (Frame::Nleft != -1: KannalaBrandt8 stereo rigs) ----
+ * Numbering as the host-pointer fisheye forms (below): features [0, N_left) = left camera, [N_left, N) = right camera; occupancy masks and match
+ * arrays hold N entries.  cap covers both cameras.
+ *   orbx_frame_load_host_fisheye: left->keypoints_un = mvKeys, left->n = N_left, left->descriptors = ALL N rows; kps_right = mvKeysRight [n_right];
+ *     l2r [N_left] = mvLeftToRightMatch, r2l [n_right] = mvRightToLeftMatch (-1 = none).  ORBX_E_BAD_ARG when l2r[i] is not in [-1, n_right) or
+ *     r2l[j] not in [-1, N_left); ORBX_E_TOO_LARGE when N > cap.  Returns without waiting for the upload.
+ *   orbx_frame_load_stereo_fisheye_batch: frame `frame` of the last orbx_stereo_fisheye_batch_device(left, right, ...): both extractors' RAW
+ *     keypoints (mvKeys / mvKeysRight: what the stage triangulated), descriptors and counts, and the stage's l2r / r2l rows -- copied on the device.
+ *     bounds4 / scale_factors as orbx_frame_load_batch (NULL: the left extractor's).  Asynchronous, no host synchronisation: the matcher's stream
+ *     waits for the stage; both extractors' next batches and the left extractor's next fisheye stage wait for the copy.  The counts stay on the
+ *     device until a search returns them (or orbx_frame_counts).  ORBX_E_BAD_ARG when the stage's results are not those of the extractors'
+ *     current batches (an extraction since the stage, another right extractor), the frame is not one of the batch, an extractor is on another
+ *     device, or cap_left + cap_right > cap.
+ *   orbx_frame_counts: N_left and N_right (n_right = -1 for a monocular / rectified frame, as Frame::Nleft == -1); synchronises like orbx_frame_count. */
+int orbx_frame_load_host_fisheye(orbx_frame *f, const orbx_frame_desc *left, const orbx_keypoint *kps_right, int n_right, const int32_t *l2r,
+                                 const int32_t *r2l);
+int orbx_frame_load_stereo_fisheye_batch(orbx_frame *f, orbx_extractor *left, orbx_extractor *right, int frame, const float *bounds4,
+                                         const float *scale_factors, int nlevels);
+int orbx_frame_counts(orbx_frame *f, int *n_left, int *n_right);
+/* Handle forms of orbx_search_by_projection_mappoints_fisheye (M1, ORBmatcher.cc:43-213 whole) and orbx_search_by_projection_frame_fisheye
+ * (M2, :1676-1887 with :1794-1863): the same arguments and results with the frame, kps_right, l2r and r2l taken from the handle; frame_match /
+ * cur_match hold N entries (the handle's capacity while the counts are still on the device: N comes back with the results).  Bit for bit the
+ * host-pointer forms' results. */
+int orbx_frame_search_by_projection_mappoints_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, int n_mp, const uint8_t *in_view,
+                                                      const float *proj_x, const float *proj_y, const int32_t *pred_level, const float *view_cos,
+                                                      const uint8_t *in_view_r, const float *proj_xr, const float *proj_yr, const int32_t *pred_level_r,
+                                                      const float *view_cos_r, const uint8_t *mp_desc, const uint8_t *mp_has_obs, float th, float nnratio,
+                                                      int32_t *frame_match);
+int orbx_frame_search_by_projection_frame_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *cur_occupied, int n_q, const float *q_u, const float *q_v,
+                                                  const float *q_ur, const float *q_vr, const int32_t *q_octave, const float *q_angle, const uint8_t *q_desc,
+                                                  const uint8_t *q_has_obs, float th, int level_mode, int check_orientation, int32_t *cur_match);
+/* orbx_frame_search_local_points_fisheye: below, after orbx_fisheye_view. */
 
 /* ORBmatcher::SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (ORBmatcher.cc:648-763).
  * prev_matched: n1 (x, y) pairs, updated in place (:757-760).  matches12[i1] = index in F2 or -1. */
@@ -568,6 +603,21 @@ typedef struct orbx_fisheye_view {
 int orbx_is_in_frustum_checks(orbx_matcher *m, const orbx_fisheye_view *views, int n_views, const float *bounds4, float log_scale_factor, int nlevels,
                               float viewing_cos_limit, int n_mp, const float *pos, const float *normal, const float *min_dist, const float *max_dist,
                               uint8_t *in_view, float *proj_x, float *proj_y, float *depth, int32_t *level, float *view_cos);
+/* Tracking::SearchLocalPoints (Tracking.cc:3339-3413) on a resident FISHEYE-STEREO frame in one call, one synchronisation: Frame::isInFrustum of
+ * every map point (isInFrustumChecks of views[0] = left and views[1] = right, with the frame's bounds and levels), the window setup and
+ * SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) (ORBmatcher.cc:43-213 whole); the projection records stay on the device.
+ * The contract is orbx_frame_search_local_points', per camera: a map point is searched iff eligible[j] (!isBad() && mnLastFrameSeen != F.mnId;
+ * NULL = all), in view of either camera, and not (far_points && mTrackDepth > th_far_points).  The left sub-query's radius is
+ * RadiusByViewingCos * th (th != 1) * scale, the right one's has no th factor; a level outside the frame's levels drops that camera's sub-query.
+ * mTrackDepth: isInFrustumChecks writes it only when the LEFT camera sees the point (Frame.cc:1168-1240).  For a point only the right camera sees,
+ * the reference's far-point test reads the MapPoint's PREVIOUS mTrackDepth: pass it in track_depth[n_mp] (read for those points only); NULL means
+ * such a point is never far.  Outputs: in_view [2][n_mp] = mbTrackInView / mbTrackInViewR of the eligible points (the caller calls IncreaseVisible
+ * when either is set), frame_match [N].  Returns nmatches. */
+int orbx_frame_search_local_points_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_fisheye_view *views,
+                                           float log_scale_factor, float viewing_cos_limit, int n_mp, const float *pos, const float *normal,
+                                           const float *min_dist, const float *max_dist, const uint8_t *mp_desc, const uint8_t *eligible,
+                                           const uint8_t *has_obs, const float *track_depth, float th, float nnratio, int far_points,
+                                           float th_far_points, uint8_t *in_view, int32_t *frame_match);
 /* The same for n_frames poses at once on device-resident map-point data (shared by all frames); outputs [n_frames][n_mp] in device
  * memory -- exactly the arrays orbx_search_mappoints_batch_device consumes (Tracking::SearchLocalPoints, Tracking.cc:3339-3413: frustum
  * test, then SearchByProjection).  bounds4 = NULL uses the extractor's camera (orbx_set_camera) or the plain image rectangle.
@@ -645,7 +695,8 @@ typedef struct orbx_bow_keyframe {
  * -1 for iF < N, nmatches[k] = the member's return value.  Row k equals orbx_search_by_bow_frame for key frame k bit for bit.  Relocalization's
  * candidates in one call: one upload run, one launch chain whose length does not depend on n_kf, one download run, one synchronisation.
  * match_stride >= N; while N is still on the device (orbx_frame_load_batch) a stride below the handle's capacity costs one orbx_frame_count first.
- * Monocular / rectified frames only (fisheye-stereo frames: orbx_search_by_bow_frame_fisheye).  n_kf <= ORBX_MAX_BOW_KEYFRAMES (ORBX_E_TOO_LARGE).
+ * Monocular / rectified frames only: a fisheye-stereo handle is refused (ORBX_E_BAD_ARG) by this call and orbx_frame_compute_bow (fisheye-stereo
+ * frames: orbx_search_by_bow_frame_fisheye).  n_kf <= ORBX_MAX_BOW_KEYFRAMES (ORBX_E_TOO_LARGE).
  * Returns ORBX_OK; ORBX_E_BAD_ARG, before anything is enqueued, for a handle of another matcher, a frame without orbx_frame_compute_bow since its
  * last load, or a malformed key frame. */
 int orbx_frame_search_by_bow(orbx_matcher *m, orbx_frame *f, int n_kf, const orbx_bow_keyframe *kfs, float nnratio, int check_orientation,

@@ -142,6 +142,8 @@ SYMBOLS = [
     "orbx_compute_stereo_fisheye_matches", "orbx_stereo_fisheye_batch_device", "orbx_stereo_fisheye_batch_download",
     "orbx_stereo_fisheye_batch_download_all",
     "orbx_vocabulary_set_word_weights", "orbx_frame_compute_bow", "orbx_frame_search_by_bow", "orbx_frame_search_by_projection_window",
+    "orbx_frame_load_host_fisheye", "orbx_frame_load_stereo_fisheye_batch", "orbx_frame_counts", "orbx_frame_search_by_projection_mappoints_fisheye",
+    "orbx_frame_search_by_projection_frame_fisheye", "orbx_frame_search_local_points_fisheye",
 ]
 
 
@@ -252,6 +254,12 @@ def lib() -> C.CDLL:
     L.orbx_frame_compute_bow.argtypes = [vp, vp, vp, i32, vp, vp]
     L.orbx_frame_search_by_bow.argtypes = [vp, vp, i32, C.POINTER(BowKeyFrame), f32, i32, vp, i32, vp]
     L.orbx_frame_search_by_projection_window.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, i32, vp]
+    L.orbx_frame_load_host_fisheye.argtypes = [vp, C.POINTER(FrameDesc), vp, i32, vp, vp]
+    L.orbx_frame_load_stereo_fisheye_batch.argtypes = [vp, vp, vp, i32, vp, vp, i32]
+    L.orbx_frame_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.orbx_frame_search_by_projection_mappoints_fisheye.argtypes = [vp, vp, vp, i32] + [vp] * 12 + [f32, f32, vp]
+    L.orbx_frame_search_by_projection_frame_fisheye.argtypes = [vp, vp, vp, i32] + [vp] * 8 + [f32, i32, i32, vp]
+    L.orbx_frame_search_local_points_fisheye.argtypes = [vp, vp, vp, vp, f32, f32, i32] + [vp] * 8 + [f32, f32, i32, f32, vp, vp]
     _lib = L
     return L
 

@@ -70,6 +70,19 @@ public:
         check(orbx_frame_count(f_, &n), "orbx_frame_count");
         return n;
     }
+    // a fisheye-stereo frame (Frame::Nleft != -1): left.mvKeysUn = mvKeys, left.N = Nleft, left.mDescriptors = ALL N rows; keysRight = mvKeysRight,
+    // l2r / r2l = mvLeftToRightMatch / mvRightToLeftMatch
+    void loadFisheye(const FrameView &left, const std::vector<orbx_keypoint> &keysRight, const std::vector<int32_t> &l2r, const std::vector<int32_t> &r2l) {
+        orbx_frame_desc fd = left.c();
+        check(orbx_frame_load_host_fisheye(f_, &fd, keysRight.data(), (int)keysRight.size(), l2r.data(), r2l.data()), "orbx_frame_load_host_fisheye");
+    }
+    // frame `frame` of the last fisheye stereo stage on (left, right) (orbx_stereo_fisheye_batch_device); asynchronous
+    void loadStereoFisheyeBatch(orbx_extractor *left, orbx_extractor *right, int frame, const float *bounds4 = nullptr, const float *scaleFactors = nullptr,
+                                int nlevels = 0) {
+        check(orbx_frame_load_stereo_fisheye_batch(f_, left, right, frame, bounds4, scaleFactors, nlevels), "orbx_frame_load_stereo_fisheye_batch");
+    }
+    // Nleft and N - Nleft (-1 for a monocular / rectified frame)
+    void counts(int &nLeft, int &nRight) { check(orbx_frame_counts(f_, &nLeft, &nRight), "orbx_frame_counts"); }
     // Frame::ComputeBoW's transform on the resident descriptors (orbx_frame_compute_bow): the FeatureVector stays here for the SearchByBoW
     // overloads on a DeviceFrame.  wordId / nodeId (optional) receive N ids each -- mBowVec is folded from the word ids on the host.
     inline void ComputeBoW(ORBmatcher &matcher, const ORBVocabularyDevice &voc, int levelsup = 4, std::vector<int32_t> *wordId = nullptr,
@@ -188,6 +201,53 @@ public:
             mps.normal.data(), mps.minDistance.data(), mps.maxDistance.data(), mps.descriptors.data(), mps.eligible.empty() ? nullptr : mps.eligible.data(),
             mps.hasObservations.empty() ? nullptr : mps.hasObservations.data(), th, mfNNratio, bFarPoints ? 1 : 0, thFarPoints, inView.data(), vpMatch.data());
         if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_local_points: ") + orbx_status_string(r));
+        return r;
+    }
+
+    // The fisheye-stereo twins on a resident rig frame (DeviceFrame::loadFisheye / loadStereoFisheyeBatch): features [0, Nleft) left, [Nleft, N) right.
+    // SearchByProjection(Frame&, vector<MapPoint*>&, th, ...) whole (ORBmatcher.cc:43-213); the *R fields are the right camera's mTrack*R.
+    struct FisheyeMapPoints {
+        std::vector<uint8_t> inView, inViewR, descriptors, hasObservations;
+        std::vector<float> projX, projY, viewCos, projXR, projYR, viewCosR;
+        std::vector<int32_t> level, levelR;
+        int size() const { return (int)projX.size(); }
+    };
+    int SearchByProjectionFisheye(DeviceFrame &F, const std::vector<uint8_t> &occupied, const FisheyeMapPoints &mp, float th, std::vector<int32_t> &vpMatch) {
+        vpMatch.assign(F.count(), -1);
+        const int r = orbx_frame_search_by_projection_mappoints_fisheye(
+            m_, F.handle(), occupied.empty() ? nullptr : occupied.data(), mp.size(), mp.inView.data(), mp.projX.data(), mp.projY.data(), mp.level.data(),
+            mp.viewCos.data(), mp.inViewR.data(), mp.projXR.data(), mp.projYR.data(), mp.levelR.data(), mp.viewCosR.data(), mp.descriptors.data(),
+            mp.hasObservations.empty() ? nullptr : mp.hasObservations.data(), th, mfNNratio, vpMatch.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_by_projection_mappoints_fisheye: ") + orbx_status_string(r));
+        return r;
+    }
+    // SearchByProjection(Frame &Cur, const Frame &Last, th, bMono) with the twin (:1676-1887, :1794-1863); vr = v of the right-camera projection
+    // (q.ur holds its u)
+    int SearchByProjectionFisheye(DeviceFrame &Cur, const std::vector<uint8_t> &occupied, const ProjectedQueries &q, const std::vector<float> &vr, float th,
+                                  bool bForward, bool bBackward, std::vector<int32_t> &vpMatch) {
+        vpMatch.assign(Cur.count(), -1);
+        const int mode = bForward ? 1 : (bBackward ? 2 : 0);
+        const int r = orbx_frame_search_by_projection_frame_fisheye(
+            m_, Cur.handle(), occupied.empty() ? nullptr : occupied.data(), (int)q.u.size(), q.u.data(), q.v.data(), q.ur.data(), vr.data(),
+            q.octave.data(), q.angle.data(), q.descriptors.data(), q.hasObservations.empty() ? nullptr : q.hasObservations.data(), th, mode,
+            mbCheckOrientation ? 1 : 0, vpMatch.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_by_projection_frame_fisheye: ") + orbx_status_string(r));
+        return r;
+    }
+    // Tracking::SearchLocalPoints on a rig frame in one call: views[0] / views[1] = left / right camera (isInFrustumChecks), trackDepth = the map
+    // points' previous mTrackDepth (read for points only the right camera sees; empty: such a point is never far).  inView [2][n] =
+    // mbTrackInView / mbTrackInViewR.
+    int SearchLocalPointsFisheye(DeviceFrame &F, const std::vector<uint8_t> &occupied, const orbx_fisheye_view views[2], float logScaleFactor,
+                                 float viewingCosLimit, const LocalMapPoints &mps, const std::vector<float> &trackDepth, float th, bool bFarPoints,
+                                 float thFarPoints, std::vector<uint8_t> &inView, std::vector<int32_t> &vpMatch) {
+        inView.assign(2 * (size_t)mps.size(), 0);
+        vpMatch.assign(F.count(), -1);
+        const int r = orbx_frame_search_local_points_fisheye(
+            m_, F.handle(), occupied.empty() ? nullptr : occupied.data(), views, logScaleFactor, viewingCosLimit, mps.size(), mps.pos.data(),
+            mps.normal.data(), mps.minDistance.data(), mps.maxDistance.data(), mps.descriptors.data(), mps.eligible.empty() ? nullptr : mps.eligible.data(),
+            mps.hasObservations.empty() ? nullptr : mps.hasObservations.data(), trackDepth.empty() ? nullptr : trackDepth.data(), th, mfNNratio,
+            bFarPoints ? 1 : 0, thFarPoints, inView.data(), vpMatch.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_local_points_fisheye: ") + orbx_status_string(r));
         return r;
     }
 

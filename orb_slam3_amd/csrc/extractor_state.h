@@ -201,6 +201,10 @@ struct orbx_extractor {
     // may change last_batch / the counts before the download)
     DevBuf d_sf_idx, d_sf_dist, d_sf_l2r, d_sf_r2l, d_sf_depth, d_sf_p3d, d_sf_cnt, d_sf_sigma, d_sf_rig;
     int sf_batch = 0, sf_capL = 0, sf_capR = 0;
+    // which batches the stage read (batch_seq of both extractors) and its end on the device: orbx_frame_load_stereo_fisheye_batch copies from it
+    uint64_t batch_seq = 0, sf_seq_l = 0, sf_seq_r = 0;
+    const orbx_extractor *sf_right = nullptr;
+    hipEvent_t ev_sf = nullptr;
     DevBuf d_match, d_nmatch;  // internal match outputs [B][cap], [B] (one matcher per batch: orbx.h)
     int internal_match_owner = 0;   // which batched matcher wrote them for the current batch: 0 none, 1 frame-to-frame, 2 map points
     // cached problem descriptors of orbx_match_consecutive_device

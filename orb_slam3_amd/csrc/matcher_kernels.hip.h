@@ -968,6 +968,91 @@ __global__ __launch_bounds__(64) void k_frame_prepare(const FramePrepare F, Grid
     for (int w = i0 * 2 + (int)threadIdx.x; w < i1 * 2; w += 64) dd[w] = sd[w];
 }
 
+// The same for a fisheye-stereo frame: both cameras' rows (right rows at the fixed row offset roff), both counts, mvLeftToRightMatch /
+// mvRightToLeftMatch and TWO grids -- block s < 2 writes count[s] and builds camera s's grid from its source rows with side-local indices
+// (the grids run_projection_twin's k_grid_build launch of grid 2 builds, so every tie is the host-pointer forms'); block 0 also writes the
+// scale factors.  Blocks b >= 2 copy rows [256 (b-2), 256 (b-1)) of each camera and its partner entries.  src_kps[s] == NULL: in place.
+struct FisheyePrepare {
+    const orbx_keypoint *src_kps[2];
+    const uint8_t *src_desc[2];
+    const int32_t *src_count[2];    // device counts (NULL: n_host)
+    const int32_t *src_l2r, *src_r2l;
+    int n_host[2], cap_side[2];     // counts are clamped to [0, cap_side]
+    orbx_keypoint *kps;             // [cap]: left rows at 0, right rows at roff
+    uint8_t *desc;
+    int32_t *count;                 // [2]
+    int32_t *l2r, *r2l;
+    float *scale;
+    uint16_t *gstart[2], *gorder[2];
+    int roff, nlevels;
+    float scale_host[kFrameMaxLevels];
+};
+__global__ __launch_bounds__(64) void k_frame_prepare_fisheye(const FisheyePrepare F, GridParams g) {
+    __shared__ uint16_t cnt[kGridCells];
+    __shared__ uint16_t start[kGridCells];
+    __shared__ uint32_t claim[kGridCells];
+    int n[2];
+#pragma unroll
+    for (int s = 0; s < 2; s++) n[s] = max(0, min(F.src_count[s] ? gld(F.src_count[s]) : F.n_host[s], F.cap_side[s]));
+    if (blockIdx.x < 2) {
+        const int s = blockIdx.x;
+        if (threadIdx.x == 0) gst(F.count + s, (int32_t)n[s]);
+        if (s == 0 && threadIdx.x < F.nlevels) gst(F.scale + threadIdx.x, F.scale_host[threadIdx.x]);
+        grid_build_wave(F.src_kps[s] ? F.src_kps[s] : F.kps + (s ? F.roff : 0), n[s], F.gstart[s], F.gorder[s], g, cnt, start, claim);
+        return;
+    }
+    const int i0 = (blockIdx.x - 2) * 256;
+#pragma unroll 1
+    for (int s = 0; s < 2; s++) {
+        const int i1 = min(i0 + 256, n[s]);
+        if (!F.src_kps[s] || i0 >= i1) continue;
+        const size_t o = s ? (size_t)F.roff : 0;
+        const uint32_t *sk = reinterpret_cast<const uint32_t *>(F.src_kps[s]);   // 28-byte rows: 7 dwords each
+        uint32_t *dk = reinterpret_cast<uint32_t *>(F.kps + o);
+        for (int w = i0 * 7 + (int)threadIdx.x; w < i1 * 7; w += 64) dk[w] = sk[w];
+        const uint4 *sd = reinterpret_cast<const uint4 *>(F.src_desc[s]);       // 32-byte rows: 2 x 16 bytes
+        uint4 *dd = reinterpret_cast<uint4 *>(F.desc + o * 32);
+        for (int w = i0 * 2 + (int)threadIdx.x; w < i1 * 2; w += 64) dd[w] = sd[w];
+        const int32_t *sp = s ? F.src_r2l : F.src_l2r;
+        int32_t *dp = s ? F.r2l : F.l2r;
+        for (int i = i0 + (int)threadIdx.x; i < i1; i += 64) dp[i] = sp[i];
+    }
+}
+
+// The search windows of Tracking::SearchLocalPoints on a fisheye-stereo frame, from k_in_frustum_checks' outputs ([2][n_mp]: left, right): a map
+// point is searched iff it is eligible, in view of either camera (mbTrackInView || mbTrackInViewR) and not a far point (bFarPoints && mTrackDepth >
+// thFarPoints, ORBmatcher.cc:48-52).  isInFrustumChecks writes mTrackDepth only when the LEFT camera sees the point (Frame.cc:1168-1240); for a point
+// only the right camera sees, the test reads the MapPoint's previous mTrackDepth: track_depth[i] (NULL: not far).  Left sub-query: RadiusByViewingCos
+// [* th if th != 1] * scale, levels [l-1, l] (:60-72); right sub-query (:144-152): no th factor.  A level outside the frame's levels invalidates that
+// camera's sub-query.  in_view_out [2][n_mp] = mbTrackInView / mbTrackInViewR of the eligible points.  grid ceil(n_mp/256), block 256
+__global__ __launch_bounds__(256) void k_local_windows_fisheye(int n_mp, const uint8_t *__restrict__ in_view, const uint8_t *__restrict__ eligible,
+                                                               const int32_t *__restrict__ level, const float *__restrict__ view_cos,
+                                                               const float *__restrict__ depth, const float *__restrict__ track_depth,
+                                                               const float *__restrict__ scale, int nlevels, float th, int far_points, float th_far_points,
+                                                               float *__restrict__ qr, int32_t *__restrict__ qmin, int32_t *__restrict__ qmax,
+                                                               uint8_t *__restrict__ qvalid, uint8_t *__restrict__ in_view_out) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_mp) return;
+    const bool el = !eligible || eligible[i];
+    const bool ivL = el && in_view[i], ivR = el && in_view[n_mp + i];
+    const float dep = ivL ? depth[i] : (track_depth ? track_depth[i] : 0.f);
+    const bool far = far_points && (ivL || track_depth) && dep > th_far_points;
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        const size_t k = (size_t)s * n_mp + i;
+        const bool iv = s ? ivR : ivL;
+        const int lvl = iv ? level[k] : -1;
+        const bool ok = iv && !far && lvl >= 0 && lvl < nlevels;
+        float r = (ok && (double)view_cos[k] > 0.998) ? 2.5f : 4.0f;   // :146 RadiusByViewingCos: float against the double literal
+        if (s == 0 && th != 1.0f) r = __fmul_rn(r, th);
+        qr[k] = ok ? __fmul_rn(r, scale[lvl]) : 0.f;
+        qmin[k] = lvl - 1;
+        qmax[k] = lvl;
+        qvalid[k] = ok ? 1 : 0;
+        in_view_out[k] = iv ? 1 : 0;
+    }
+}
+
 // Search windows of SearchByProjection(Frame, MapPoints) (ORBmatcher.cc:53-72) for every (frame, map point) of a batch:
 // r = RadiusByViewingCos(viewCos) [* th if th != 1] * mvScaleFactors[nPredictedLevel], levels [level-1, level]; a map point
 // that is not in view (mbTrackInView false) or whose predicted level is out of range is skipped.
@@ -1795,14 +1880,13 @@ __device__ __forceinline__ void dev_three_maxima(const int *hist, int &ind1, int
 //   mode 2  SearchByProjection(Frame, Frame) :1676-1887 with the twin :1794-1863: best free candidate <= TH_HIGH on either side,
 //           rotation-histogram entries for both; an EMPTY left window `continue`s past the twin (:1738-1739)
 // probs[0] / probs[1] = left / right WindowProblem (own grid, own key lists from k_window_best2, occupied0 = NULL: the lists are
-// occupancy-free, occupancy lives here).  ONE wave replays the query loop in the reference's order; the (at most kTopK) listed
-// candidates of the current sub-query are examined by lanes 0..kTopK-1, a list that runs dry before the answer is known makes
-// the whole wave re-scan the window against the current occupancy -- exactly what the sequential loop sees at that point.
-// grid (1), block 64, dynamic LDS: occ[n_left + n_right] bytes
+// occupancy-free, occupancy lives here).  The feature counts are read from the problems' n_ptr (device: a resident frame loaded from an
+// extractor batch has them on the device only); the right camera's keys are side-local, its slots [n_left, n_left + n_right).
+// grid (1), block kTwinBlock, dynamic LDS: occ[n_alloc] bytes (n_alloc >= n_left + n_right) + the staged chunk (twin_lds_bytes)
 // ---------------------------------------------------------------------------------------------------------
 struct TwinProblem {
     int mode;
-    int n_left, n_right, nq;
+    int nq;
     float nnratio, max_dist;
     int check_orientation, cleared_value;
     const int32_t *l2r, *r2l;      // mode 1: stereo partners (-1 = none)
@@ -1814,93 +1898,176 @@ struct TwinProblem {
     int32_t *entries;              // scratch [2 * nq]: rotation histogram pushes bin << 16 | slot
 };
 
-__global__ __launch_bounds__(64) void k_replay_twin(const WindowProblem *__restrict__ probs, TwinProblem T, GridParams g) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t occ[];
+// k_replay_twin: the serial replay of the twin query loop.  Its decisions are made by ONE wave, sub-query after sub-query (left, then right),
+// exactly as the reference's loop makes them; what each decision reads is staged beforehand.  Per chunk of kTwinChunk queries every lane of the
+// block stages ONE query -- validity, meta, its kTopK listed candidates as (distance, index) plus each candidate's octave, rotation bin and
+// stereo partner -- with two dependent global round trips for the whole chunk (records, then the candidates' keypoints and partners); the
+// serial pass then reads LDS only, and walks only the chunk's queries that have a valid side (a ballot mask).  The one exception is the
+// re-scan of a list that ran dry (not exhaustive), which reads the window from global memory as before -- rare, and exact.
+constexpr int kTwinChunk = 256;
+constexpr int kTwinBlock = 256;   // = kTwinChunk: one staging lane per query
+constexpr uint32_t kTwinNone = 0xffffffffu;
+struct TwinStage {                     // LDS image of one chunk
+    uint32_t key[2][kTwinChunk][kTopK];   // dist << 16 | side-local feature, kTwinNone past the list
+    uint32_t aux[2][kTwinChunk][kTopK];   // octave | rotation bin << 8 | (global partner slot + 1) << 16
+    uint16_t meta[2][kTwinChunk];         // valid_len | exhaustive << 8 | empty << 9 | qvalid << 10 | live << 11
+    uint8_t obs[kTwinChunk];
+    uint8_t act[kTwinChunk];
+};
+inline size_t twin_lds_bytes(int n_alloc) { return (((size_t)n_alloc + 15) & ~(size_t)15) + sizeof(TwinStage); }
+
+// octave, rotation bin and partner of side-local candidate t of query iq, as one aux word
+__device__ __forceinline__ uint32_t twin_aux(const WindowProblem &P, const TwinProblem &T, int side, int t, int iq, int nL, bool ori) {
+    const orbx_keypoint kp = gld_kp(P.kps + t);
+    int partner = -1;
+    if (T.mode == 1) {
+        const int32_t *pp = side ? T.r2l : T.l2r;
+        const int p = pp ? gld(pp + t) : -1;
+        if (p != -1) partner = side ? p : nL + p;
+    }
+    const int b = ori ? dev_rot_bin(gld(T.q_angle + iq), kp.angle) : 0;
+    return (uint32_t)(kp.octave & 0xff) | ((uint32_t)(b & 0xff) << 8) | ((uint32_t)(partner + 1) << 16);
+}
+
+__global__ __launch_bounds__(kTwinBlock) void k_replay_twin(const WindowProblem *__restrict__ probs, TwinProblem T, GridParams g, int n_alloc) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds_twin[];
     __shared__ int hist[ORBX_HISTO_LENGTH + 2];
-    const int lane = threadIdx.x;
+    uint8_t *occ = lds_twin;
+    TwinStage &S = *reinterpret_cast<TwinStage *>(lds_twin + (((size_t)n_alloc + 15) & ~(size_t)15));
+    const int tid = threadIdx.x, lane = tid & 63;
+    const bool w0 = tid < 64;
     const WindowProblem PL = probs[0], PR = probs[1];
-    const int N = T.n_left + T.n_right;
-    for (int i = lane; i < N; i += 64) {
+    const int nL = max(0, gld(PL.n_ptr)), nR = max(0, gld(PR.n_ptr));
+    const int N = min(nL + nR, n_alloc);
+    for (int i = tid; i < N; i += kTwinBlock) {
         occ[i] = T.occupied0 ? T.occupied0[i] : 0;
         T.match[i] = -1;
     }
-    if (lane < ORBX_HISTO_LENGTH) hist[lane] = 0;
+    if (tid < ORBX_HISTO_LENGTH) hist[tid] = 0;
     __syncthreads();
     int nmatches = 0, n_entries = 0;
     const bool two = (T.mode == 1), ori = (T.mode == 2 && T.check_orientation);
-    for (int iq = 0; iq < T.nq; iq++) {
-        const uint8_t obs = T.q_has_obs ? T.q_has_obs[iq] : (uint8_t)1;
-        bool skip_right = false;
+    for (int c0 = 0; c0 < T.nq; c0 += kTwinChunk) {
+        // ---- stage the chunk: one lane per query ----
+        {
+            const int j = tid, iq = c0 + j;
+            const bool in = iq < T.nq;
+            bool live[2], emptyL = false;
 #pragma unroll 1
-        for (int side = 0; side < 2; side++) {
-            if (side == 1 && skip_right) break;
-            const WindowProblem &P = side ? PR : PL;
-            const int off = side ? T.n_left : 0, nside = side ? T.n_right : T.n_left;
-            if (P.qvalid && !P.qvalid[iq]) continue;
-            const int meta = P.meta[iq];
-            if (meta & 512) {                                   // vIndices.empty()
-                if (T.mode == 2 && side == 0) skip_right = true;
-                continue;
-            }
-            const int valid_len = meta & 0xff;
-            const bool exhaustive = (meta & 256) != 0;
-            u64 k = kNoKey;
-            if (lane < valid_len) k = P.keys[(size_t)iq * kTopK + lane];
-            const bool is_free = (k != kNoKey) && !occ[off + (int)(k & 0xffff)];
-            const u64 fb = __ballot(is_free);
-            u64 c1 = kNoKey, c2 = kNoKey;
-            if (fb) {
-                c1 = __shfl(k, __ffsll((long long)fb) - 1);
-                const u64 rest = fb & (fb - 1ull);
-                if (rest) c2 = __shfl(k, __ffsll((long long)rest) - 1);
-            }
-            const bool need_slow = !exhaustive && (c1 == kNoKey || (two && c2 == kNoKey && (float)(int)(c1 >> 32) <= T.max_dist));
-            if (need_slow) {   // the list ran dry: scan the window against the occupancy of this very moment
-                QueryWin w;
-                Desc dq;
-                u64 r1 = kNoKey, r2 = kNoKey;
-                if (load_query(P, iq, &w, g, &dq)) {
-                    scan_window(P, g, w, dq, nside, occ + off, lane, r1, r2);
-                    wave_min2(r1, r2);
+            for (int side = 0; side < 2; side++) {
+                const WindowProblem &P = side ? PR : PL;
+                const int nside = side ? nR : nL;
+                const bool qv = in && (!P.qvalid || gld(P.qvalid + iq));
+                const int meta = in ? gld(P.meta + iq) : 0;
+                u64 k[kTopK];
+#pragma unroll
+                for (int r = 0; r < kTopK; r++) k[r] = in ? gld(P.keys + (size_t)iq * kTopK + r) : kNoKey;
+                const int vl = meta & 0xff;
+#pragma unroll
+                for (int r = 0; r < kTopK; r++) {
+                    const int t = (int)(k[r] & 0xffff);
+                    const bool ok = qv && !(meta & 512) && r < vl && k[r] != kNoKey && t < nside;
+                    S.key[side][j][r] = ok ? ((uint32_t)(k[r] >> 32) << 16) | (uint32_t)t : kTwinNone;
+                    S.aux[side][j][r] = ok ? twin_aux(P, T, side, t, iq, nL, ori) : 0u;
                 }
-                c1 = r1; c2 = r2;
+                // a LIVE sub-query can change the loop's state: its window holds a candidate within max_dist (the list's first key is the smallest
+                // of all candidates, free or not) or its list was cut before any key.  Any other sub-query ends in a `continue` that changes nothing.
+                live[side] = qv && !(meta & 512) && (vl == 0 || (float)(int)(k[0] >> 32) <= T.max_dist);
+                if (side == 0) emptyL = qv && (meta & 512);
+                S.meta[side][j] = (uint16_t)(qv ? ((meta & 0x3ff) | 1024 | (live[side] ? 2048 : 0)) : 0);
             }
-            if (c1 == kNoKey) continue;
-            const int bestDist = (int)(c1 >> 32);
-            if ((float)bestDist > T.max_dist) continue;
-            const int t = (int)(c1 & 0xffff);
-            if (two) {
-                const int bestDist2 = (c2 == kNoKey) ? 256 : (int)(c2 >> 32);
-                const int bestLevel = P.kps[t].octave;
-                const int bestLevel2 = (c2 == kNoKey) ? -1 : P.kps[(int)(c2 & 0xffff)].octave;
-                if (bestLevel == bestLevel2 && (float)bestDist > T.nnratio * (float)bestDist2) {
-                    if (side == 0) skip_right = true;           // :125-126: `continue` leaves the whole iteration
-                    continue;
-                }
-            }
-            int np = 1;
-            int partner = -1;
-            if (two) {
-                const int p = side ? T.r2l[t] : T.l2r[t];
-                if (p != -1) { partner = side ? p : T.n_left + p; np = 2; }
-            }
-            if (lane == 0) {
-                T.match[off + t] = iq;
-                occ[off + t] = obs;
-                if (partner >= 0) { T.match[partner] = iq; occ[partner] = obs; }
-                if (ori) {
-                    const int b = dev_rot_bin(T.q_angle[iq], P.kps[t].angle);
-                    T.entries[n_entries] = (b << 16) | (off + t);
-                    hist[b]++;
-                }
-            }
-            nmatches += np;
-            if (ori) n_entries++;
-            one_wave_sync();   // single wave: orders lane 0's LDS writes (occ, hist) before the next sub-query's reads; match / entries are read after the loop's __syncthreads()
+            S.obs[j] = (in && T.q_has_obs) ? T.q_has_obs[iq] : (uint8_t)1;
+            // the serial pass visits a query iff a sub-query of it is live (mode 2: an empty left window skips the right one, :1738-1739)
+            S.act[j] = (live[0] || (live[1] && !(T.mode == 2 && emptyL))) ? 1 : 0;
         }
+        __syncthreads();
+        // ---- the serial pass of the chunk: wave 0, LDS only ----
+        if (w0) {
+#pragma unroll 1
+            for (int g0 = 0; g0 < kTwinChunk; g0 += 64) {
+                u64 todo = __ballot(S.act[g0 + lane] != 0);
+                while (todo) {
+                    const int j = g0 + __ffsll((long long)todo) - 1;
+                    todo &= todo - 1ull;
+                    const int iq = c0 + j;
+                    const uint8_t obs = S.obs[j];
+                    bool skip_right = false;
+#pragma unroll 1
+                    for (int side = 0; side < 2; side++) {
+                        if (side == 1 && skip_right) break;
+                        const WindowProblem &P = side ? PR : PL;
+                        const int off = side ? nL : 0, nside = side ? nR : nL;
+                        const int meta = S.meta[side][j];
+                        if (!(meta & 1024)) continue;                   // qvalid
+                        if (meta & 512) {                               // vIndices.empty()
+                            if (T.mode == 2 && side == 0) skip_right = true;
+                            continue;
+                        }
+                        if (!(meta & 2048)) continue;                   // no candidate within max_dist: nothing changes
+                        const bool exhaustive = (meta & 256) != 0;
+                        uint32_t k = kTwinNone, ax = 0;
+                        if (lane < kTopK) { k = S.key[side][j][lane]; ax = S.aux[side][j][lane]; }
+                        const bool is_free = (k != kTwinNone) && !occ[off + (int)(k & 0xffff)];
+                        const u64 fb = __ballot(is_free);
+                        int d1 = -1, t1 = 0, d2 = -1;
+                        uint32_t a1 = 0, a2 = 0;
+                        if (fb) {
+                            const int l1 = __ffsll((long long)fb) - 1;
+                            const uint32_t k1 = __shfl(k, l1);
+                            a1 = __shfl(ax, l1);
+                            d1 = (int)(k1 >> 16); t1 = (int)(k1 & 0xffff);
+                            const u64 rest = fb & (fb - 1ull);
+                            if (rest) {
+                                const int l2 = __ffsll((long long)rest) - 1;
+                                d2 = (int)(__shfl(k, l2) >> 16);
+                                a2 = __shfl(ax, l2);
+                            }
+                        }
+                        const bool need_slow = !exhaustive && (d1 < 0 || (two && d2 < 0 && (float)d1 <= T.max_dist));
+                        if (need_slow) {   // the list ran dry: scan the window against the occupancy of this very moment
+                            QueryWin w;
+                            Desc dq;
+                            u64 r1 = kNoKey, r2 = kNoKey;
+                            if (load_query(P, iq, &w, g, &dq)) {
+                                scan_window(P, g, w, dq, nside, occ + off, lane, r1, r2);
+                                wave_min2(r1, r2);
+                            }
+                            d1 = d2 = -1;
+                            if (r1 != kNoKey) { d1 = (int)(r1 >> 32); t1 = (int)(r1 & 0xffff); a1 = twin_aux(P, T, side, t1, iq, nL, ori); }
+                            if (r2 != kNoKey) { d2 = (int)(r2 >> 32); a2 = twin_aux(P, T, side, (int)(r2 & 0xffff), iq, nL, ori); }
+                        }
+                        if (d1 < 0) continue;
+                        if ((float)d1 > T.max_dist) continue;
+                        if (two) {
+                            const int bestDist2 = d2 < 0 ? 256 : d2;
+                            const int bestLevel = (int)(a1 & 0xff);
+                            const int bestLevel2 = d2 < 0 ? -1 : (int)(a2 & 0xff);
+                            if (bestLevel == bestLevel2 && (float)d1 > T.nnratio * (float)bestDist2) {
+                                if (side == 0) skip_right = true;       // :125-126: `continue` leaves the whole iteration
+                                continue;
+                            }
+                        }
+                        const int partner = two ? (int)(a1 >> 16) - 1 : -1;
+                        if (lane == 0) {
+                            T.match[off + t1] = iq;
+                            occ[off + t1] = obs;
+                            if (partner >= 0) { T.match[partner] = iq; occ[partner] = obs; }
+                            if (ori) {
+                                const int b = (int)((a1 >> 8) & 0xff);
+                                T.entries[n_entries] = (b << 16) | (off + t1);
+                                hist[b]++;
+                            }
+                        }
+                        nmatches += partner >= 0 ? 2 : 1;
+                        if (ori) n_entries++;
+                        one_wave_sync();   // single wave: orders lane 0's LDS writes (occ, hist) before the next sub-query's reads
+                    }
+                }
+            }
+        }
+        __syncthreads();   // the next chunk is staged over this one
     }
-    __syncthreads();
-    if (ori) {
+    if (w0 && ori) {
         int ind1, ind2, ind3;
         dev_three_maxima(hist, ind1, ind2, ind3);
         int dropped = 0;
@@ -1912,7 +2079,7 @@ __global__ __launch_bounds__(64) void k_replay_twin(const WindowProblem *__restr
         for (int s = 32; s > 0; s >>= 1) dropped += __shfl_xor(dropped, s);
         nmatches -= dropped;
     }
-    if (lane == 0) *T.nmatches = nmatches;
+    if (tid == 0) *T.nmatches = nmatches;
 }
 
 struct InitProblem {  // ORBmatcher::SearchForInitialization (ORBmatcher.cc:648-763)

@@ -625,6 +625,7 @@ static int configure(orbx_extractor *ex, int width, int height, int batch) {
       ex->oct_single_wave = v && v[0] == 'w'; }   // ORBX_OCTREE=w1: the global-memory form on ONE wave (round 5's; the whole workgroup since round 6)
     ex->n_fast_tiles = (int)fast_tiles.size(); ex->n_blur_items = (int)blur_items.size();
     ex->last_batch = 0;
+    ex->batch_seq++;
     ex->lvl0_inplace = false;
     if (ex->has_camera) {
         CameraModel c = {ex->cam_params[0], ex->cam_params[1], ex->cam_params[2], ex->cam_params[3], ex->cam_params[4], ex->cam_params[5],
@@ -903,6 +904,7 @@ static int enqueue_extract(orbx_extractor *ex, const uint8_t *d_images, int n, s
     ORBX_HIP(hipEventRecord(ex->ev_describe, st));
     ORBX_HIP(hipGetLastError());
     ex->last_batch = n;
+    ex->batch_seq++;
     return ORBX_OK;
 }
 
@@ -1067,6 +1069,7 @@ void orbx_destroy(orbx_extractor *ex) {
     for (hipEvent_t ev : {ex->ev_in_free[0], ex->ev_in_free[1], ex->ev_in_ready[0], ex->ev_in_ready[1]}) if (ev) (void)hipEventDestroy(ev);
     ex->d_in[0].release(); ex->d_in[1].release();
     for (hipEvent_t ev : {ex->ev_pyr, ex->ev_blur, ex->ev_describe, ex->ev_match}) if (ev) (void)hipEventDestroy(ev);
+    if (ex->ev_sf) (void)hipEventDestroy(ex->ev_sf);
     for (hipEvent_t ev : ex->ev_stereo_copy) if (ev) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : ex->ev_copy_done) if (ev) (void)hipEventDestroy(ev);
     if (ex->h_err) (void)hipHostFree(ex->h_err);

@@ -575,6 +575,15 @@ struct orbx_frame {
     std::vector<int32_t> h_bow;       // [2 cap]: word / node ids downloaded while N was still on the device
     const orbx_vocabulary *bow_voc = nullptr;
     int bow_levelsup = 0;
+    // A fisheye-stereo frame (Frame::Nleft != -1, orbx_frame_load_host_fisheye / orbx_frame_load_stereo_fisheye_batch): features [0, N_left) are the
+    // left camera's (rows [0, N_left)), [N_left, N) the right camera's, stored at rows [roff, roff + N_right) -- roff is known on the host before
+    // the counts are (a batch load puts them at the left extractor's capacity).  count[0] / count[1] = N_left / N_right on the device; the right
+    // camera has a grid of its own; l2r [N_left] / r2l [N_right] = mvLeftToRightMatch / mvRightToLeftMatch.
+    bool fisheye = false;
+    int roff = 0, n_left = 0, n_right = -1;   // (cached with n_known)
+    int32_t *l2r = nullptr, *r2l = nullptr;
+    uint16_t *gstart_r = nullptr, *gorder_r = nullptr;
+    size_t off_l2r = 0, off_r2l = 0;
 };
 
 namespace {
@@ -587,15 +596,16 @@ inline GridParams grid_of(const float *b) {
     return g;
 }
 
-// N of a handle: cached, else one download of the device count (and a synchronisation of the owner's stream)
+// N of a handle: cached, else one download of the device count(s) (and a synchronisation of the owner's stream)
 int frame_count(orbx_frame *f, int *n) {
     if (!f->n_known) {
         orbx_matcher *m = f->owner;
         ORBX_HIP(hipSetDevice(m->device));
-        ORBX_HIP(hipMemcpyAsync(f->h_count, f->count, 4, hipMemcpyDeviceToHost, m->stream));
+        ORBX_HIP(hipMemcpyAsync(f->h_count, f->count, f->fisheye ? 8 : 4, hipMemcpyDeviceToHost, m->stream));
         ORBX_HIP(hipStreamSynchronize(m->stream));
         m->dirty = false;
-        f->n = *f->h_count;
+        if (f->fisheye) { f->n_left = f->h_count[0]; f->n_right = f->h_count[1]; f->n = f->n_left + f->n_right; }
+        else f->n = *f->h_count;
         f->n_known = true;
     }
     *n = f->n;
@@ -808,11 +818,13 @@ int orbx_frame_create(orbx_matcher *m, int cap, orbx_frame **out) {
     size_t o = 0;
     auto carve = [&o](size_t bytes) { const size_t r = o; o += Arena::pad(bytes); return r; };
     f->off_kps = carve(28 * (size_t)cap); f->off_desc = carve(32 * (size_t)cap); f->off_ur = carve(4 * (size_t)cap);
-    f->off_count = carve(4); f->off_scale = carve(4 * (size_t)kFrameMaxLevels);
+    f->off_count = carve(8); f->off_scale = carve(4 * (size_t)kFrameMaxLevels);
     f->off_gstart = carve(2 * ((size_t)kGridCells + 1)); f->off_gorder = carve(2 * (size_t)cap);
+    const size_t off_gsr = carve(2 * ((size_t)kGridCells + 1)), off_gor = carve(2 * (size_t)cap);
+    f->off_l2r = carve(4 * (size_t)cap); f->off_r2l = carve(4 * (size_t)cap);
     const size_t off_bw = carve(4 * (size_t)cap), off_bn = carve(4 * (size_t)cap), off_fn = carve(4 * (size_t)cap), off_fp = carve(4 * ((size_t)cap + 1)),
                  off_fi = carve(4 * (size_t)cap), off_fm = carve(16), off_an = carve(4 * (size_t)cap);
-    f->stage_bytes = f->off_count;   // the rows: keypoints, descriptors, mvuRight at the device layout's offsets
+    f->stage_bytes = o;   // the rows (keypoints, descriptors, mvuRight; a fisheye frame's partners) at the device layout's offsets
     hipError_t e = hipMalloc((void **)&f->dev, o);
     if (e == hipSuccess) e = hipHostMalloc((void **)&f->stage, f->stage_bytes, hipHostMallocCoherent);   // read by k_xfer's lanes
     if (e == hipSuccess) e = hipHostMalloc((void **)&f->h_count, 64, hipHostMallocDefault);
@@ -825,6 +837,8 @@ int orbx_frame_create(orbx_matcher *m, int cap, orbx_frame **out) {
     f->bow_word = (int32_t *)(f->dev + off_bw); f->bow_node = (int32_t *)(f->dev + off_bn); f->fv_node = (uint32_t *)(f->dev + off_fn);
     f->fv_ptr = (int32_t *)(f->dev + off_fp); f->fv_index = (int32_t *)(f->dev + off_fi); f->fv_meta = (int32_t *)(f->dev + off_fm);
     f->angle = (float *)(f->dev + off_an);
+    f->gstart_r = (uint16_t *)(f->dev + off_gsr); f->gorder_r = (uint16_t *)(f->dev + off_gor);
+    f->l2r = (int32_t *)(f->dev + f->off_l2r); f->r2l = (int32_t *)(f->dev + f->off_r2l);
     f->n_known = true;   // an empty frame until the first load
     *out = f;
     return ORBX_OK;
@@ -882,6 +896,7 @@ int orbx_frame_load_host(orbx_frame *f, const orbx_frame_desc *d) {
     ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
     f->stage_busy = true;
     f->n = n; f->n_known = true; f->has_ur = d->u_right != nullptr; f->loaded = true; f->bow_valid = false;
+    f->fisheye = false; f->n_right = -1;
     return ORBX_OK;
 }
 
@@ -909,6 +924,7 @@ int orbx_frame_load_batch(orbx_frame *f, orbx_extractor *ex, int frame, const fl
     ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
     ORBX_HIP(hipStreamWaitEvent(ex->stream, f->ev_done, 0));
     f->n_known = false; f->has_ur = false; f->loaded = true; f->bow_valid = false;
+    f->fisheye = false; f->n_right = -1;
     return ORBX_OK;
 }
 
@@ -932,7 +948,7 @@ int orbx_frame_search_by_projection_mappoints(orbx_matcher *m, orbx_frame *frame
                                               const float *proj_y, const float *proj_xr, const int32_t *pred_level, const float *view_cos,
                                               const uint8_t *mp_desc, const uint8_t *mp_in_view, const uint8_t *mp_has_obs, float th, float nnratio,
                                               int32_t *frame_match) {
-    if (!m || !frame || frame->owner != m || !frame_match) return ORBX_E_BAD_ARG;
+    if (!m || !frame || frame->owner != m || frame->fisheye || !frame_match) return ORBX_E_BAD_ARG;   // (a fisheye frame: the _fisheye forms)
     const orbx_frame_desc d = frame_desc_of(frame);
     return search_mappoints_impl(m, &d, frame, frame_occupied, n_mp, proj_x, proj_y, proj_xr, pred_level, view_cos, mp_desc, mp_in_view, mp_has_obs,
                                  th, nnratio, frame_match);
@@ -941,7 +957,7 @@ int orbx_frame_search_by_projection_mappoints(orbx_matcher *m, orbx_frame *frame
 int orbx_frame_search_by_projection_frame(orbx_matcher *m, orbx_frame *cur, const uint8_t *cur_occupied, int n_q, const float *q_u, const float *q_v,
                                           const float *q_ur, const int32_t *q_octave, const float *q_angle, const uint8_t *q_desc,
                                           const uint8_t *q_has_obs, float th, int level_mode, int check_orientation, int32_t *cur_match) {
-    if (!m || !cur || cur->owner != m || !cur_match) return ORBX_E_BAD_ARG;
+    if (!m || !cur || cur->owner != m || cur->fisheye || !cur_match) return ORBX_E_BAD_ARG;
     const orbx_frame_desc d = frame_desc_of(cur);
     return search_frame_impl(m, &d, cur, cur_occupied, n_q, q_u, q_v, q_ur, q_octave, q_angle, q_desc, q_has_obs, th, level_mode, check_orientation,
                              cur_match);
@@ -967,16 +983,35 @@ struct TwinArgs {
     int32_t *match_out;
 };
 
-int run_projection_twin(orbx_matcher *m, const TwinArgs &a) {
+// the twin window search of both cameras and the replay; dP = the two problems (uploaded or to be uploaded by the caller), n_alloc >= N
+int launch_twin(orbx_matcher *m, const WindowProblem *dP, const TwinProblem &T, const GridParams &g, int n_alloc, int nq) {
+    ORBX_LAUNCH_WINDOW_BEST2(nq, 2, m->exec(), dP, g);
+    const size_t lds = twin_lds_bytes(n_alloc);
+    if (lds > 64 * 1024) ORBX_HIP(hipFuncSetAttribute((const void *)k_replay_twin, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_replay_twin, dim3(1), dim3(kTwinBlock), lds, m->exec(), dP, T, g, n_alloc);
+    ORBX_HIP(hipGetLastError());
+    return ORBX_OK;
+}
+
+// fh != NULL: the handle form -- rows, grids, counts and stereo partners are resident (a.left supplies the bounds and scale factors only); while the
+// counts are still on the device every per-feature buffer is sized by the handle's capacity and N comes back with the results
+int run_projection_twin(orbx_matcher *m, const TwinArgs &a, orbx_frame *fh = nullptr) {
     const orbx_frame_desc *F = a.left;
-    const int nl = F->n, nr = a.n_right, N = nl + nr, nq = a.nq;
+    const int nq = a.nq;
+    int nl = fh ? -1 : F->n, nr = fh ? -1 : a.n_right, N = fh ? -1 : nl + nr;
+    if (fh && (fh->n_known || a.occupied || nq == 0)) {   // the mask holds N entries
+        const int rc = frame_count(fh, &N);
+        if (rc != ORBX_OK) return rc;
+        nl = fh->n_left; nr = fh->n_right;
+    }
     for (int i = 0; i < N; i++) a.match_out[i] = -1;
     if (N == 0 || nq == 0) return 0;
-    if (N > 60000) return ORBX_E_TOO_LARGE;   // 16-bit feature indices in the candidate keys; occupancy bytes in LDS
+    const int nc = N >= 0 ? N : fh->cap;   // features the device buffers are sized for
+    if (nc > 60000) return ORBX_E_TOO_LARGE;   // 16-bit feature indices in the candidate keys; occupancy bytes in LDS
     ORBX_HIP(hipSetDevice(m->device));
-    const size_t need = Arena::pad(28 * (size_t)N) + Arena::pad(32 * (size_t)N) + Arena::pad((size_t)N) + 2 * Arena::pad(4 * (size_t)N) +
+    const size_t need = Arena::pad(28 * (size_t)nc) + Arena::pad(32 * (size_t)nc) + Arena::pad((size_t)nc) + 2 * Arena::pad(4 * (size_t)nc) +
                         2 * (5 * Arena::pad(4 * (size_t)nq) + Arena::pad((size_t)nq) + Arena::pad(8 * (size_t)kTopK * nq) + Arena::pad(4 * (size_t)nq) +
-                             Arena::pad(2 * (kGridCells + 1)) + Arena::pad(2 * (size_t)N)) +
+                             Arena::pad(2 * (kGridCells + 1)) + Arena::pad(2 * (size_t)nc)) +
                         Arena::pad(32 * (size_t)nq) + Arena::pad((size_t)nq) + Arena::pad(4 * (size_t)nq) + Arena::pad(8 * (size_t)nq) +
                         Arena::pad(2 * sizeof(WindowProblem)) + 64 * 256 + 4096;
     int r = m->reserve_all(need);
@@ -985,19 +1020,29 @@ int run_projection_twin(orbx_matcher *m, const TwinArgs &a) {
     m->begin();
     WindowProblem P[2];
     memset(P, 0, sizeof(P));
-    orbx_keypoint *dk = A.take<orbx_keypoint>(N);
-    uint8_t *dd = A.take<uint8_t>(32 * (size_t)N);
-    if (nl) H2D(dk, F->keypoints_un, 28 * (size_t)nl);
-    if (nr) H2D(dk + nl, a.kps_right, 28 * (size_t)nr);
-    H2D(dd, F->descriptors, 32 * (size_t)N);
     int32_t *dcnt = A.take<int32_t>(4);
     const int32_t cnts[3] = {nl, nr, nq};
     H2D(dcnt, cnts, 12);
+    if (fh) {   // resident rows and grids: nothing of the frame travels
+        P[0].kps = fh->kps; P[0].desc = fh->desc; P[0].n_ptr = fh->count; P[0].gstart = fh->gstart; P[0].gorder = fh->gorder;
+        P[1].kps = fh->kps + fh->roff; P[1].desc = fh->desc + (size_t)fh->roff * 32; P[1].n_ptr = fh->count + 1;
+        P[1].gstart = fh->gstart_r; P[1].gorder = fh->gorder_r;
+    } else {
+        orbx_keypoint *dk = A.take<orbx_keypoint>(N);
+        uint8_t *dd = A.take<uint8_t>(32 * (size_t)N);
+        if (nl) H2D(dk, F->keypoints_un, 28 * (size_t)nl);
+        if (nr) H2D(dk + nl, a.kps_right, 28 * (size_t)nr);
+        H2D(dd, F->descriptors, 32 * (size_t)N);
+        for (int s = 0; s < 2; s++) {
+            P[s].kps = dk + (s ? nl : 0); P[s].desc = dd + (s ? (size_t)nl * 32 : 0); P[s].n_ptr = dcnt + s;
+            P[s].gstart = A.take<uint16_t>(kGridCells + 1); P[s].gorder = A.take<uint16_t>(std::max(s ? nr : nl, 1));
+        }
+    }
     uint8_t *dqd = A.take<uint8_t>(32 * (size_t)nq);
     H2D(dqd, a.qdesc, 32 * (size_t)nq);
     for (int s = 0; s < 2; s++) {
         WindowProblem &w = P[s];
-        w.kps = dk + (s ? nl : 0); w.desc = dd + (s ? (size_t)nl * 32 : 0); w.n_ptr = dcnt + s; w.nq_ptr = dcnt + 2;
+        w.nq_ptr = dcnt + 2;
         float *f3[3]; const float *h3[3] = {a.qx[s], a.qy[s], a.qr[s]};
         for (int k = 0; k < 3; k++) { f3[k] = A.take<float>(nq); H2D(f3[k], h3[k], 4 * (size_t)nq); }
         w.qx = f3[0]; w.qy = f3[1]; w.qr = f3[2];
@@ -1007,47 +1052,57 @@ int run_projection_twin(orbx_matcher *m, const TwinArgs &a) {
         { uint8_t *p = A.take<uint8_t>(nq); H2D(p, a.qvalid[s], (size_t)nq); w.qvalid = p; }
         w.qdesc = dqd;
         w.keys = A.take<u64>((size_t)nq * kTopK); w.meta = A.take<int32_t>(nq);
-        w.gstart = A.take<uint16_t>(kGridCells + 1); w.gorder = A.take<uint16_t>(std::max(s ? nr : nl, 1));
     }
     TwinProblem T;
     memset(&T, 0, sizeof(T));
-    T.mode = a.mode; T.n_left = nl; T.n_right = nr; T.nq = nq; T.nnratio = a.nnratio; T.max_dist = (float)ORBX_TH_HIGH;
+    T.mode = a.mode; T.nq = nq; T.nnratio = a.nnratio; T.max_dist = (float)ORBX_TH_HIGH;
     T.check_orientation = a.check_orientation; T.cleared_value = -2;
-    if (a.l2r && nl) { int32_t *p = A.take<int32_t>(nl); H2D(p, a.l2r, 4 * (size_t)nl); T.l2r = p; }
-    if (a.r2l && nr) { int32_t *p = A.take<int32_t>(nr); H2D(p, a.r2l, 4 * (size_t)nr); T.r2l = p; }
+    if (fh) { T.l2r = fh->l2r; T.r2l = fh->r2l; }
+    else {
+        if (a.l2r && nl) { int32_t *p = A.take<int32_t>(nl); H2D(p, a.l2r, 4 * (size_t)nl); T.l2r = p; }
+        if (a.r2l && nr) { int32_t *p = A.take<int32_t>(nr); H2D(p, a.r2l, 4 * (size_t)nr); T.r2l = p; }
+    }
     if (a.occupied) { uint8_t *p = A.take<uint8_t>(N); H2D(p, a.occupied, (size_t)N); T.occupied0 = p; }
     if (a.q_has_obs) { uint8_t *p = A.take<uint8_t>(nq); H2D(p, a.q_has_obs, (size_t)nq); T.q_has_obs = p; }
     if (a.q_angle) { float *p = A.take<float>(nq); H2D(p, a.q_angle, 4 * (size_t)nq); T.q_angle = p; }
-    T.match = A.take<int32_t>(N); T.nmatches = A.take<int32_t>(1); T.entries = A.take<int32_t>(2 * (size_t)nq);
+    T.match = A.take<int32_t>(nc); T.nmatches = A.take<int32_t>(1); T.entries = A.take<int32_t>(2 * (size_t)nq);
     WindowProblem *dP = A.take<WindowProblem>(2);
     H2D(dP, P, sizeof(P));
-    GridParams g;
-    g.minx = F->min_x; g.miny = F->min_y;
-    g.inv_w = 64.0f / (F->max_x - F->min_x);
-    g.inv_h = 48.0f / (F->max_y - F->min_y);
-    ORBX_LAUNCH_GRID_BUILD( dim3(2), dim3(64), 0, m->exec(), dP, g);
-    ORBX_LAUNCH_WINDOW_BEST2(nq, 2, m->exec(), dP, g);
-    const size_t lds = ((size_t)N + 63) & ~(size_t)63;
-    hipLaunchKernelGGL(k_replay_twin, dim3(1), dim3(64), lds, m->exec(), dP, T, g);
+    const float fb[4] = {F->min_x, F->max_x, F->min_y, F->max_y};
+    const GridParams g = grid_of(fb);
+    if (!fh) ORBX_LAUNCH_GRID_BUILD( dim3(2), dim3(64), 0, m->exec(), dP, g);
+    r = launch_twin(m, dP, T, g, nc, nq);
+    if (r != ORBX_OK) return r;
     int32_t nm = 0;
-    D2H(a.match_out, T.match, 4 * (size_t)N);
+    if (N >= 0) {
+        D2H(a.match_out, T.match, 4 * (size_t)N);
+    } else {   // the counts come back with the results
+        fh->h_match.resize((size_t)fh->cap);
+        D2H(fh->h_match.data(), T.match, 4 * (size_t)nc);
+        D2H(fh->h_count, fh->count, 8);
+    }
     D2H(&nm, T.nmatches, 4);
     SYNC_AND_DELIVER();
+    if (N < 0) {
+        fh->n_left = fh->h_count[0]; fh->n_right = fh->h_count[1]; fh->n = fh->n_left + fh->n_right; fh->n_known = true;
+        memcpy(a.match_out, fh->h_match.data(), 4 * (size_t)std::max(fh->n, 0));
+    }
     return nm;
 }
 
 }  // namespace
 
 // SearchByProjection(Frame&, const vector<MapPoint*>&, th, ...) for a fisheye-stereo frame (F.Nleft != -1), ORBmatcher.cc:43-213 whole
-extern "C" int orbx_search_by_projection_mappoints_fisheye(orbx_matcher *m, const orbx_frame_desc *left, const orbx_keypoint *kps_right, int n_right,
-                                                           const int32_t *left_to_right, const int32_t *right_to_left, const uint8_t *frame_occupied,
-                                                           int n_mp, const uint8_t *in_view, const float *proj_x, const float *proj_y,
-                                                           const int32_t *pred_level, const float *view_cos, const uint8_t *in_view_r,
-                                                           const float *proj_xr, const float *proj_yr, const int32_t *pred_level_r,
-                                                           const float *view_cos_r, const uint8_t *mp_desc, const uint8_t *mp_has_obs, float th,
-                                                           float nnratio, int32_t *frame_match) {
+// fh != NULL: the handle form (left / kps_right / l2r / r2l: the resident frame's; left supplies the scale factors and levels only)
+static int search_mappoints_fisheye_impl(orbx_matcher *m, const orbx_frame_desc *left, orbx_frame *fh, const orbx_keypoint *kps_right, int n_right,
+                                         const int32_t *left_to_right, const int32_t *right_to_left, const uint8_t *frame_occupied,
+                                         int n_mp, const uint8_t *in_view, const float *proj_x, const float *proj_y,
+                                         const int32_t *pred_level, const float *view_cos, const uint8_t *in_view_r,
+                                         const float *proj_xr, const float *proj_yr, const int32_t *pred_level_r,
+                                         const float *view_cos_r, const uint8_t *mp_desc, const uint8_t *mp_has_obs, float th,
+                                         float nnratio, int32_t *frame_match) {
     if (!m || !left || left->n < 0 || n_right < 0 || n_mp < 0 || (!frame_match && left->n + n_right > 0)) return ORBX_E_BAD_ARG;
-    if ((left->n > 0 && !left_to_right) || (n_right > 0 && (!right_to_left || !kps_right))) return ORBX_E_BAD_ARG;
+    if (!fh && ((left->n > 0 && !left_to_right) || (n_right > 0 && (!right_to_left || !kps_right)))) return ORBX_E_BAD_ARG;
     if (n_mp > 0 && (!in_view || !proj_x || !proj_y || !pred_level || !view_cos || !in_view_r || !proj_xr || !proj_yr || !pred_level_r || !view_cos_r || !mp_desc))
         return ORBX_E_BAD_ARG;
     std::vector<float> qr[2];
@@ -1073,15 +1128,27 @@ extern "C" int orbx_search_by_projection_mappoints_fisheye(orbx_matcher *m, cons
     TwinArgs a = {left, kps_right, n_right, left_to_right, right_to_left, frame_occupied, n_mp, {proj_x, proj_xr}, {proj_y, proj_yr},
                   {qr[0].data(), qr[1].data()}, {qmin[0].data(), qmin[1].data()}, {qmax[0].data(), qmax[1].data()}, {valid[0].data(), valid[1].data()},
                   mp_desc, mp_has_obs, nullptr, 1, nnratio, 0, frame_match};
-    return run_projection_twin(m, a);
+    return run_projection_twin(m, a, fh);
+}
+
+extern "C" int orbx_search_by_projection_mappoints_fisheye(orbx_matcher *m, const orbx_frame_desc *left, const orbx_keypoint *kps_right, int n_right,
+                                                           const int32_t *left_to_right, const int32_t *right_to_left, const uint8_t *frame_occupied,
+                                                           int n_mp, const uint8_t *in_view, const float *proj_x, const float *proj_y,
+                                                           const int32_t *pred_level, const float *view_cos, const uint8_t *in_view_r,
+                                                           const float *proj_xr, const float *proj_yr, const int32_t *pred_level_r,
+                                                           const float *view_cos_r, const uint8_t *mp_desc, const uint8_t *mp_has_obs, float th,
+                                                           float nnratio, int32_t *frame_match) {
+    return search_mappoints_fisheye_impl(m, left, nullptr, kps_right, n_right, left_to_right, right_to_left, frame_occupied, n_mp, in_view, proj_x, proj_y,
+                                         pred_level, view_cos, in_view_r, proj_xr, proj_yr, pred_level_r, view_cos_r, mp_desc, mp_has_obs, th, nnratio,
+                                         frame_match);
 }
 
 // SearchByProjection(Frame& Cur, const Frame& Last, th, bMono) for a fisheye-stereo current frame, ORBmatcher.cc:1676-1887 with :1794-1863
-extern "C" int orbx_search_by_projection_frame_fisheye(orbx_matcher *m, const orbx_frame_desc *left, const orbx_keypoint *kps_right, int n_right,
-                                                       const uint8_t *cur_occupied, int n_q, const float *q_u, const float *q_v, const float *q_ur,
-                                                       const float *q_vr, const int32_t *q_octave, const float *q_angle, const uint8_t *q_desc,
-                                                       const uint8_t *q_has_obs, float th, int level_mode, int check_orientation, int32_t *cur_match) {
-    if (!m || !left || left->n < 0 || n_right < 0 || n_q < 0 || (!cur_match && left->n + n_right > 0) || (n_right > 0 && !kps_right)) return ORBX_E_BAD_ARG;
+static int search_frame_fisheye_impl(orbx_matcher *m, const orbx_frame_desc *left, orbx_frame *fh, const orbx_keypoint *kps_right, int n_right,
+                                     const uint8_t *cur_occupied, int n_q, const float *q_u, const float *q_v, const float *q_ur,
+                                     const float *q_vr, const int32_t *q_octave, const float *q_angle, const uint8_t *q_desc,
+                                     const uint8_t *q_has_obs, float th, int level_mode, int check_orientation, int32_t *cur_match) {
+    if (!m || !left || left->n < 0 || n_right < 0 || n_q < 0 || (!cur_match && left->n + n_right > 0) || (!fh && n_right > 0 && !kps_right)) return ORBX_E_BAD_ARG;
     if (n_q > 0 && (!q_u || !q_v || !q_ur || !q_vr || !q_octave || !q_desc || (check_orientation && !q_angle))) return ORBX_E_BAD_ARG;
     std::vector<float> qr(n_q);
     std::vector<int32_t> qmin(n_q), qmax(n_q);
@@ -1097,7 +1164,15 @@ extern "C" int orbx_search_by_projection_frame_fisheye(orbx_matcher *m, const or
     TwinArgs a = {left, kps_right, n_right, nullptr, nullptr, cur_occupied, n_q, {q_u, q_ur}, {q_v, q_vr}, {qr.data(), qr.data()},
                   {qmin.data(), qmin.data()}, {qmax.data(), qmax.data()}, {valid.data(), valid.data()}, q_desc, q_has_obs, q_angle, 2, 0.f,
                   check_orientation, cur_match};
-    return run_projection_twin(m, a);
+    return run_projection_twin(m, a, fh);
+}
+
+extern "C" int orbx_search_by_projection_frame_fisheye(orbx_matcher *m, const orbx_frame_desc *left, const orbx_keypoint *kps_right, int n_right,
+                                                       const uint8_t *cur_occupied, int n_q, const float *q_u, const float *q_v, const float *q_ur,
+                                                       const float *q_vr, const int32_t *q_octave, const float *q_angle, const uint8_t *q_desc,
+                                                       const uint8_t *q_has_obs, float th, int level_mode, int check_orientation, int32_t *cur_match) {
+    return search_frame_fisheye_impl(m, left, nullptr, kps_right, n_right, cur_occupied, n_q, q_u, q_v, q_ur, q_vr, q_octave, q_angle, q_desc, q_has_obs, th,
+                                     level_mode, check_orientation, cur_match);
 }
 
 extern "C" int orbx_search_by_projection_window(orbx_matcher *m, const orbx_frame_desc *frame, const uint8_t *occupied, int n_q,
@@ -1116,7 +1191,7 @@ extern "C" int orbx_frame_search_by_projection_window(orbx_matcher *m, orbx_fram
                                                       const float *q_y, const float *q_r, const int32_t *q_min_level, const int32_t *q_max_level,
                                                       const float *q_angle, const uint8_t *q_desc, const uint8_t *q_has_obs, float max_dist,
                                                       int check_orientation, int32_t *match) {
-    if (!m || !f || f->owner != m || !match || n_q < 0) return ORBX_E_BAD_ARG;
+    if (!m || !f || f->owner != m || f->fisheye || !match || n_q < 0) return ORBX_E_BAD_ARG;
     if (n_q > 0 && (!q_x || !q_y || !q_r || !q_min_level || !q_max_level || !q_desc || (check_orientation && !q_angle))) return ORBX_E_BAD_ARG;
     const orbx_frame_desc d = frame_desc_of(f);
     ProjArgs a = {&d, occupied, n_q, q_x, q_y, q_r, nullptr, q_min_level, q_max_level, q_desc, nullptr, q_has_obs,
@@ -2199,6 +2274,9 @@ extern "C" int orbx_stereo_fisheye_batch_device(orbx_extractor *L, orbx_extracto
     hipLaunchKernelGGL(k_tri_kb8_stereo, dim3((unsigned)((capL + 255) / 256), (unsigned)n), dim3(256), 0, st, S);
     ORBX_HIP(hipGetLastError());
     L->sf_batch = n; L->sf_capL = capL; L->sf_capR = capR;
+    L->sf_seq_l = L->batch_seq; L->sf_seq_r = R->batch_seq; L->sf_right = R;
+    if (!L->ev_sf) ORBX_HIP(hipEventCreateWithFlags(&L->ev_sf, hipEventDisableTiming));
+    ORBX_HIP(hipEventRecord(L->ev_sf, st));   // (orbx_frame_load_stereo_fisheye_batch waits for it)
     // the extractors must not overwrite their keypoints / descriptors / counts before these kernels are done
     ORBX_HIP(hipEventRecord(L->ev_match, st));
     L->match_pending = true; L->copy_covers_match = false;
@@ -2343,7 +2421,7 @@ extern "C" int orbx_bow_transform(orbx_matcher *m, const orbx_vocabulary *v, con
 // Frame::ComputeBoW (Frame.cc:738-745) on a resident frame: k_frame_bow_transform over the handle's descriptors, then k_frame_featvec builds the
 // FeatureVector in the handle.  Nothing of the frame is uploaded; without downloads nothing waits (the launches are ordered on the owner's stream).
 extern "C" int orbx_frame_compute_bow(orbx_matcher *m, orbx_frame *f, const orbx_vocabulary *v, int levelsup, int32_t *word_id, int32_t *node_id) {
-    if (!m || !f || !v || f->owner != m || v->device != m->device) return ORBX_E_BAD_ARG;
+    if (!m || !f || !v || f->owner != m || f->fisheye || v->device != m->device) return ORBX_E_BAD_ARG;   // (BoW on a fisheye frame: not yet)
     ORBX_HIP(hipSetDevice(m->device));
     const bool down = word_id || node_id;
     const int n_host = f->n_known ? f->n : -1;
@@ -2391,7 +2469,7 @@ extern "C" int orbx_frame_compute_bow(orbx_matcher *m, orbx_frame *f, const orbx
 // k_bow_pair_nodes, k_replay_bow_batch and k_replay_bow_finish_batch, one download run, one synchronisation -- whatever n_kf is.
 extern "C" int orbx_frame_search_by_bow(orbx_matcher *m, orbx_frame *f, int n_kf, const orbx_bow_keyframe *kfs, float nnratio, int check_orientation,
                                         int32_t *match, int match_stride, int32_t *nmatches) {
-    if (!m || !f || f->owner != m || !f->bow_valid || n_kf < 0) return ORBX_E_BAD_ARG;
+    if (!m || !f || f->owner != m || f->fisheye || !f->bow_valid || n_kf < 0) return ORBX_E_BAD_ARG;
     if (n_kf > ORBX_MAX_BOW_KEYFRAMES) return ORBX_E_TOO_LARGE;
     if (n_kf == 0) return ORBX_OK;
     if (!kfs || !match || !nmatches || match_stride < 0) return ORBX_E_BAD_ARG;
@@ -2616,7 +2694,7 @@ extern "C" int orbx_frame_search_local_points(orbx_matcher *m, orbx_frame *f, co
                                               const float *normal, const float *min_dist, const float *max_dist, const uint8_t *mp_desc,
                                               const uint8_t *eligible, const uint8_t *has_obs, float th, float nnratio, int far_points,
                                               float th_far_points, uint8_t *in_view, int32_t *frame_match) {
-    if (!m || !f || f->owner != m || !cam || !pose || n_mp < 0 || !frame_match) return ORBX_E_BAD_ARG;
+    if (!m || !f || f->owner != m || f->fisheye || !cam || !pose || n_mp < 0 || !frame_match) return ORBX_E_BAD_ARG;
     if (n_mp > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !in_view)) return ORBX_E_BAD_ARG;
     int n = -1;
     if (f->n_known || frame_occupied || n_mp == 0) { const int rc = frame_count(f, &n); if (rc != ORBX_OK) return rc; }   // the mask holds N entries
@@ -2702,6 +2780,248 @@ extern "C" int orbx_frame_search_local_points(orbx_matcher *m, orbx_frame *f, co
     SYNC_AND_DELIVER();
     if (n < 0) {
         f->n_known = true;
+        memcpy(frame_match, f->h_match.data(), 4 * (size_t)std::max(f->n, 0));
+    }
+    return nm;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Fisheye-stereo frames on the handle (Frame::Nleft != -1: KannalaBrandt8 rigs).  Features [0, N_left) are the left camera's, [N_left, N) the right
+// camera's; the occupancy masks and match arrays of every entry point use that numbering.
+// ---------------------------------------------------------------------------------------------------------
+extern "C" int orbx_frame_load_host_fisheye(orbx_frame *f, const orbx_frame_desc *left, const orbx_keypoint *kps_right, int n_right, const int32_t *l2r,
+                                            const int32_t *r2l) {
+    if (!f || !left || left->n < 0 || n_right < 0 || (left->n > 0 && (!left->keypoints_un || !l2r)) || (n_right > 0 && (!kps_right || !r2l)) ||
+        (left->n + n_right > 0 && !left->descriptors) || !left->scale_factors || left->nlevels < 1 || left->nlevels > kFrameMaxLevels)
+        return ORBX_E_BAD_ARG;
+    const int nl = left->n, nr = n_right, N = nl + nr;
+    // the partners index device memory: checked before anything is enqueued
+    for (int i = 0; i < nl; i++) if (l2r[i] < -1 || l2r[i] >= nr) return ORBX_E_BAD_ARG;
+    for (int j = 0; j < nr; j++) if (r2l[j] < -1 || r2l[j] >= nl) return ORBX_E_BAD_ARG;
+    if (N > f->cap) return ORBX_E_TOO_LARGE;
+    orbx_matcher *m = f->owner;
+    ORBX_HIP(hipSetDevice(m->device));
+    if (f->stage_busy) { ORBX_HIP(hipEventSynchronize(f->ev_done)); f->stage_busy = false; }   // the previous load still reads the staging
+    m->begin();
+    // rows in place: left at 0, right at roff = N_left, so the descriptors of all N features are one run
+    const size_t b_kl = 28 * (size_t)nl, b_kr = 28 * (size_t)nr, b_desc = 32 * (size_t)N, b_l2r = 4 * (size_t)nl, b_r2l = 4 * (size_t)nr;
+    memcpy(f->stage + f->off_kps, left->keypoints_un, b_kl);
+    memcpy(f->stage + f->off_kps + b_kl, kps_right, b_kr);
+    memcpy(f->stage + f->off_desc, left->descriptors, b_desc);
+    memcpy(f->stage + f->off_l2r, l2r, b_l2r);
+    memcpy(f->stage + f->off_r2l, r2l, b_r2l);
+    XferOps X;
+    X.n = 0;
+    uint32_t max_units = 0;
+    const size_t offs[4] = {f->off_kps, f->off_desc, f->off_l2r, f->off_r2l}, bytes[4] = {b_kl + b_kr, b_desc, b_l2r, b_r2l};
+    for (int k = 0; k < 4; k++) {
+        if (!bytes[k]) continue;
+        if (m->kernel_xfer) {
+            const uint32_t units = (uint32_t)((bytes[k] + 15) / 16);   // (rounded up to 16 bytes: inside the region's 256-byte padding)
+            X.op[X.n++] = XferOp{f->dev + offs[k], f->stage + offs[k], units, 0};
+            max_units = std::max(max_units, units);
+        } else {
+            ORBX_HIP(hipMemcpyAsync(f->dev + offs[k], f->stage + offs[k], bytes[k], hipMemcpyHostToDevice, m->stream));
+            m->xfers[4]++;
+        }
+        m->xfers[0]++; m->xfers[2] += (int64_t)bytes[k];
+    }
+    if (X.n) m->launch_xfer(X, max_units);
+    if (m->xfer_err != hipSuccess) { set_error(hipGetErrorString(m->xfer_err)); return ORBX_E_HIP; }
+    FramePrepare P0;
+    const float b[4] = {left->min_x, left->max_x, left->min_y, left->max_y};
+    frame_prepare_common(f, P0, left->scale_factors, left->nlevels, b);
+    FisheyePrepare P;
+    memset(&P, 0, sizeof(P));
+    P.n_host[0] = nl; P.n_host[1] = nr; P.cap_side[0] = nl; P.cap_side[1] = nr;
+    P.kps = f->kps; P.desc = f->desc; P.count = f->count; P.l2r = f->l2r; P.r2l = f->r2l; P.scale = f->scale;
+    P.gstart[0] = f->gstart; P.gorder[0] = f->gorder; P.gstart[1] = f->gstart_r; P.gorder[1] = f->gorder_r;
+    P.roff = nl; P.nlevels = left->nlevels;
+    memcpy(P.scale_host, left->scale_factors, sizeof(float) * (size_t)left->nlevels);
+    hipLaunchKernelGGL(k_frame_prepare_fisheye, dim3(2), dim3(64), 0, m->stream, P, grid_of(f->bounds));
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
+    f->stage_busy = true;
+    f->fisheye = true; f->roff = nl; f->n_left = nl; f->n_right = nr; f->n = N; f->n_known = true;
+    f->has_ur = false; f->loaded = true; f->bow_valid = false;
+    return ORBX_OK;
+}
+
+extern "C" int orbx_frame_load_stereo_fisheye_batch(orbx_frame *f, orbx_extractor *L, orbx_extractor *R, int frame, const float *bounds4,
+                                                    const float *scale_factors, int nlevels) {
+    if (!f || !L || !R) return ORBX_E_BAD_ARG;
+    orbx_matcher *m = f->owner;
+    // the stage's results must be those of the extractors' current batches
+    if (L->sf_batch <= 0 || !L->ev_sf || L->sf_right != R || L->sf_seq_l != L->batch_seq || L->sf_seq_r != R->batch_seq) return ORBX_E_BAD_ARG;
+    if (frame < 0 || frame >= L->sf_batch || frame >= L->last_batch || L->device != m->device || R->device != m->device) return ORBX_E_BAD_ARG;
+    const int capL = L->sf_capL, capR = L->sf_capR;
+    if (capL != L->cap || capR != R->cap || (size_t)capL + (size_t)capR > (size_t)f->cap) return ORBX_E_BAD_ARG;
+    const float *sf = scale_factors ? scale_factors : L->scale.data();
+    const int nl = scale_factors ? nlevels : L->prm.nlevels;
+    if (nl < 1 || nl > kFrameMaxLevels || (!bounds4 && L->width <= 0)) return ORBX_E_BAD_ARG;
+    const float *b = bounds4 ? bounds4 : L->bounds;
+    ORBX_HIP(hipSetDevice(m->device));
+    FramePrepare P0;
+    frame_prepare_common(f, P0, sf, nl, b);
+    FisheyePrepare P;
+    memset(&P, 0, sizeof(P));
+    const size_t fr = (size_t)frame;
+    P.src_kps[0] = (const orbx_keypoint *)L->d_kps.p + fr * capL;   // mvKeys: the raw keypoints k_tri_kb8_stereo read
+    P.src_kps[1] = (const orbx_keypoint *)R->d_kps.p + fr * capR;
+    P.src_desc[0] = (const uint8_t *)L->d_desc.p + fr * capL * 32;
+    P.src_desc[1] = (const uint8_t *)R->d_desc.p + fr * capR * 32;
+    P.src_count[0] = (const int32_t *)L->d_count.p + fr;
+    P.src_count[1] = (const int32_t *)R->d_count.p + fr;
+    P.src_l2r = (const int32_t *)L->d_sf_l2r.p + fr * capL;
+    P.src_r2l = (const int32_t *)L->d_sf_r2l.p + fr * capR;
+    P.cap_side[0] = capL; P.cap_side[1] = capR;
+    P.kps = f->kps; P.desc = f->desc; P.count = f->count; P.l2r = f->l2r; P.r2l = f->r2l; P.scale = f->scale;
+    P.gstart[0] = f->gstart; P.gorder[0] = f->gorder; P.gstart[1] = f->gstart_r; P.gorder[1] = f->gorder_r;
+    P.roff = capL; P.nlevels = nl;
+    memcpy(P.scale_host, sf, sizeof(float) * (size_t)nl);
+    // the owner's stream waits for the stage (which waited for both extractions); both extractors' next batches and the left extractor's next
+    // stage wait for the copy: no host synchronisation
+    ORBX_HIP(hipStreamWaitEvent(m->stream, L->ev_sf, 0));
+    hipLaunchKernelGGL(k_frame_prepare_fisheye, dim3(2 + (unsigned)((std::max(capL, capR) + 255) / 256)), dim3(64), 0, m->stream, P, grid_of(f->bounds));
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
+    ORBX_HIP(hipStreamWaitEvent(L->stream, f->ev_done, 0));
+    ORBX_HIP(hipStreamWaitEvent(R->stream, f->ev_done, 0));
+    if (L->match_stream) ORBX_HIP(hipStreamWaitEvent(L->match_stream, f->ev_done, 0));
+    f->fisheye = true; f->roff = capL; f->n_known = false; f->has_ur = false; f->loaded = true; f->bow_valid = false;
+    return ORBX_OK;
+}
+
+extern "C" int orbx_frame_counts(orbx_frame *f, int *n_left, int *n_right) {
+    if (!f) return ORBX_E_BAD_ARG;
+    int n = 0;
+    const int rc = frame_count(f, &n);
+    if (rc != ORBX_OK) return rc;
+    if (n_left) *n_left = f->fisheye ? f->n_left : n;
+    if (n_right) *n_right = f->fisheye ? f->n_right : -1;
+    return ORBX_OK;
+}
+
+extern "C" int orbx_frame_search_by_projection_mappoints_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, int n_mp,
+                                                                 const uint8_t *in_view, const float *proj_x, const float *proj_y, const int32_t *pred_level,
+                                                                 const float *view_cos, const uint8_t *in_view_r, const float *proj_xr, const float *proj_yr,
+                                                                 const int32_t *pred_level_r, const float *view_cos_r, const uint8_t *mp_desc,
+                                                                 const uint8_t *mp_has_obs, float th, float nnratio, int32_t *frame_match) {
+    if (!m || !f || f->owner != m || !f->fisheye || !frame_match) return ORBX_E_BAD_ARG;
+    const orbx_frame_desc d = frame_desc_of(f);
+    return search_mappoints_fisheye_impl(m, &d, f, nullptr, 0, nullptr, nullptr, frame_occupied, n_mp, in_view, proj_x, proj_y, pred_level, view_cos,
+                                         in_view_r, proj_xr, proj_yr, pred_level_r, view_cos_r, mp_desc, mp_has_obs, th, nnratio, frame_match);
+}
+
+extern "C" int orbx_frame_search_by_projection_frame_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *cur_occupied, int n_q, const float *q_u,
+                                                             const float *q_v, const float *q_ur, const float *q_vr, const int32_t *q_octave,
+                                                             const float *q_angle, const uint8_t *q_desc, const uint8_t *q_has_obs, float th, int level_mode,
+                                                             int check_orientation, int32_t *cur_match) {
+    if (!m || !f || f->owner != m || !f->fisheye || !cur_match) return ORBX_E_BAD_ARG;
+    const orbx_frame_desc d = frame_desc_of(f);
+    return search_frame_fisheye_impl(m, &d, f, nullptr, 0, cur_occupied, n_q, q_u, q_v, q_ur, q_vr, q_octave, q_angle, q_desc, q_has_obs, th, level_mode,
+                                     check_orientation, cur_match);
+}
+
+// Tracking::SearchLocalPoints on a resident fisheye-stereo frame: isInFrustumChecks of both cameras (k_in_frustum_checks), the windows
+// (k_local_windows_fisheye), the twin window search and the replay (k_replay_twin) -- the projection records never leave the device.
+extern "C" int orbx_frame_search_local_points_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_fisheye_view *views,
+                                                      float log_scale_factor, float viewing_cos_limit, int n_mp, const float *pos, const float *normal,
+                                                      const float *min_dist, const float *max_dist, const uint8_t *mp_desc, const uint8_t *eligible,
+                                                      const uint8_t *has_obs, const float *track_depth, float th, float nnratio, int far_points,
+                                                      float th_far_points, uint8_t *in_view, int32_t *frame_match) {
+    if (!m || !f || f->owner != m || !f->fisheye || !views || n_mp < 0 || !frame_match) return ORBX_E_BAD_ARG;
+    if (n_mp > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !in_view)) return ORBX_E_BAD_ARG;
+    int N = -1;
+    if (f->n_known || frame_occupied || n_mp == 0) { const int rc = frame_count(f, &N); if (rc != ORBX_OK) return rc; }   // the mask holds N entries
+    for (int i = 0; i < N; i++) frame_match[i] = -1;
+    if (n_mp == 0) return 0;
+    const int nc = N >= 0 ? N : f->cap;
+    ORBX_HIP(hipSetDevice(m->device));
+    const size_t q = (size_t)n_mp, q2 = 2 * q;
+    const size_t need = 2 * Arena::pad(12 * q) + 2 * Arena::pad(4 * q) + Arena::pad(32 * q) + 3 * Arena::pad(q) + Arena::pad(4 * q) + Arena::pad(sizeof(FrustumChecks)) +
+                        Arena::pad((size_t)nc) + Arena::pad(16) + Arena::pad(2 * sizeof(WindowProblem)) + Arena::pad(q2) + 5 * Arena::pad(4 * q2) +
+                        3 * Arena::pad(4 * q2) + Arena::pad(q2) + 2 * Arena::pad(8 * kTopK * q) + 2 * Arena::pad(4 * q) + Arena::pad(4 * q2) + Arena::pad(q2) +
+                        Arena::pad(4 * (size_t)nc) + 16 * 256 + 4096;
+    int r = m->reserve_all(need);
+    if (r != ORBX_OK) return r;
+    Arena &A = m->arena;
+    m->begin();
+    // inputs (one run of the arena)
+    float *dp = A.take<float>(3 * q), *dn = A.take<float>(3 * q), *dmn = A.take<float>(q), *dmx = A.take<float>(q);
+    uint8_t *ddesc = A.take<uint8_t>(32 * q);
+    H2D(dp, pos, 12 * q); H2D(dn, normal, 12 * q); H2D(dmn, min_dist, 4 * q); H2D(dmx, max_dist, 4 * q); H2D(ddesc, mp_desc, 32 * q);
+    uint8_t *delig = nullptr, *dho = nullptr, *docc = nullptr;
+    float *dtd = nullptr;
+    if (eligible) { delig = A.take<uint8_t>(q); H2D(delig, eligible, q); }
+    if (has_obs) { dho = A.take<uint8_t>(q); H2D(dho, has_obs, q); }
+    if (track_depth) { dtd = A.take<float>(q); H2D(dtd, track_depth, 4 * q); }
+    if (frame_occupied && N > 0) { docc = A.take<uint8_t>((size_t)N); H2D(docc, frame_occupied, (size_t)N); }
+    FrustumChecks FC;
+    memset(&FC, 0, sizeof(FC));
+    static_assert(sizeof(FisheyeView) == sizeof(orbx_fisheye_view), "orbx_fisheye_view layout");
+    memcpy(FC.view, views, sizeof(FisheyeView) * 2);
+    FC.minx = f->bounds[0]; FC.maxx = f->bounds[1]; FC.miny = f->bounds[2]; FC.maxy = f->bounds[3];
+    FC.log_scale_factor = log_scale_factor; FC.nlevels = f->nlevels; FC.cos_limit = viewing_cos_limit;
+    FrustumChecks *dF = A.take<FrustumChecks>(1);
+    H2D(dF, &FC, sizeof(FC));
+    int32_t *dcnt = A.take<int32_t>(4);
+    const int32_t cnts[4] = {n_mp, 0, 0, 0};
+    H2D(dcnt, cnts, 16);
+    WindowProblem *dP = A.take<WindowProblem>(2);
+    // the projection records and the windows: device only, [2][n_mp] (left, right)
+    uint8_t *div = A.take<uint8_t>(q2);
+    float *dx = A.take<float>(q2), *dy = A.take<float>(q2), *dd = A.take<float>(q2), *dvc = A.take<float>(q2);
+    int32_t *dl = A.take<int32_t>(q2);
+    float *dqr = A.take<float>(q2);
+    int32_t *dqmin = A.take<int32_t>(q2), *dqmax = A.take<int32_t>(q2);
+    uint8_t *dvalid = A.take<uint8_t>(q2);
+    WindowProblem P[2];
+    memset(P, 0, sizeof(P));
+    P[0].kps = f->kps; P[0].desc = f->desc; P[0].n_ptr = f->count; P[0].gstart = f->gstart; P[0].gorder = f->gorder;
+    P[1].kps = f->kps + f->roff; P[1].desc = f->desc + (size_t)f->roff * 32; P[1].n_ptr = f->count + 1; P[1].gstart = f->gstart_r; P[1].gorder = f->gorder_r;
+    for (int s = 0; s < 2; s++) {
+        const size_t o = (size_t)s * q;
+        P[s].nq_ptr = dcnt;
+        P[s].qx = dx + o; P[s].qy = dy + o; P[s].qr = dqr + o; P[s].qmin = dqmin + o; P[s].qmax = dqmax + o; P[s].qvalid = dvalid + o; P[s].qdesc = ddesc;
+        P[s].keys = A.take<u64>(q * kTopK); P[s].meta = A.take<int32_t>(q);
+    }
+    TwinProblem T;
+    memset(&T, 0, sizeof(T));
+    T.mode = 1; T.nq = n_mp; T.nnratio = nnratio; T.max_dist = (float)ORBX_TH_HIGH; T.cleared_value = -2;
+    T.l2r = f->l2r; T.r2l = f->r2l; T.occupied0 = docc; T.q_has_obs = dho;
+    T.entries = A.take<int32_t>(q2);
+    // the downloads side by side: mbTrackInView / mbTrackInViewR, the matches, nmatches
+    uint8_t *div_out = A.take<uint8_t>(q2);
+    T.match = A.take<int32_t>(nc);
+    T.nmatches = A.take<int32_t>(1);
+    H2D(dP, P, sizeof(P));
+    hipLaunchKernelGGL(k_in_frustum_checks, dim3((n_mp + 255) / 256, 2), dim3(256), 0, m->exec(), (const FrustumChecks *)dF, n_mp, (const float *)dp,
+                       (const float *)dn, (const float *)dmn, (const float *)dmx, div, dx, dy, dd, dl, dvc);
+    hipLaunchKernelGGL(k_local_windows_fisheye, dim3((n_mp + 255) / 256), dim3(256), 0, m->exec(), n_mp, (const uint8_t *)div, (const uint8_t *)delig,
+                       (const int32_t *)dl, (const float *)dvc, (const float *)dd, (const float *)dtd, (const float *)f->scale, f->nlevels, th,
+                       far_points ? 1 : 0, th_far_points, dqr, dqmin, dqmax, dvalid, div_out);
+    const bool match = N != 0;   // (an empty frame: isInFrustumChecks only)
+    if (match) {
+        r = launch_twin(m, dP, T, grid_of(f->bounds), nc, n_mp);
+        if (r != ORBX_OK) return r;
+    }
+    ORBX_HIP(hipGetLastError());
+    int32_t nm = 0;
+    D2H(in_view, div_out, q2);
+    if (match) {
+        if (N >= 0) {
+            D2H(frame_match, T.match, 4 * (size_t)N);
+        } else {   // the counts come back with the results
+            f->h_match.resize((size_t)f->cap);
+            D2H(f->h_match.data(), T.match, 4 * (size_t)nc);
+            D2H(f->h_count, f->count, 8);
+        }
+        D2H(&nm, T.nmatches, 4);
+    }
+    SYNC_AND_DELIVER();
+    if (N < 0) {
+        f->n_left = f->h_count[0]; f->n_right = f->h_count[1]; f->n = f->n_left + f->n_right; f->n_known = true;
         memcpy(frame_match, f->h_match.data(), 4 * (size_t)std::max(f->n, 0));
     }
     return nm;

@@ -103,6 +103,30 @@ class DeviceFrame:
         check(self._L.orbx_frame_count(self._h, C.byref(n)), "orbx_frame_count")
         return n.value
 
+    def load_fisheye(self, left: "FrameView", kps_right, l2r, r2l):
+        """Upload a fisheye-stereo frame (orbx_frame_load_host_fisheye): left.keypoints_un = mvKeys, left.descriptors = ALL N rows,
+        kps_right = mvKeysRight, l2r / r2l = mvLeftToRightMatch / mvRightToLeftMatch."""
+        self._kr = np.ascontiguousarray(kps_right, KP_DTYPE)
+        self._l2r, self._r2l = _i32(l2r), _i32(r2l)
+        fd = left.c_struct()
+        check(self._L.orbx_frame_load_host_fisheye(self._h, C.byref(fd), ptr(self._kr), len(self._kr), ptr(self._l2r), ptr(self._r2l)),
+              "orbx_frame_load_host_fisheye")
+        return self
+
+    def load_stereo_fisheye_batch(self, left_ex, right_ex, f: int, bounds=None, scale_factors=None):
+        """Frame f of the last ORBextractor.stereo_fisheye_device stage, copied on the device (orbx_frame_load_stereo_fisheye_batch): asynchronous;
+        the counts stay on the device until the first search.  bounds / scale_factors as load_batch."""
+        b, sf = _f32(bounds), _f32(scale_factors)
+        check(self._L.orbx_frame_load_stereo_fisheye_batch(self._h, left_ex._h, right_ex._h, int(f), ptr(b), ptr(sf), 0 if sf is None else len(sf)),
+              "orbx_frame_load_stereo_fisheye_batch")
+        return self
+
+    def counts(self):
+        """(N_left, N_right); N_right = -1 for a monocular / rectified frame (Frame::Nleft == -1)."""
+        nl, nr = C.c_int(0), C.c_int(0)
+        check(self._L.orbx_frame_counts(self._h, C.byref(nl), C.byref(nr)), "orbx_frame_counts")
+        return nl.value, nr.value
+
     def compute_bow(self, voc: "ORBVocabulary", levelsup: int = 4, download: bool = True):
         """Frame::ComputeBoW's transform on the resident descriptors (orbx_frame_compute_bow); the FeatureVector stays in the handle for
         ORBmatcher.SearchByBoWDevice.  download=True returns (word_id[N], node_id[N]); download=False returns None and does not wait."""
@@ -393,7 +417,17 @@ class ORBmatcher:
     # ---- fisheye-stereo twins (F.Nleft != -1): features [0, n_left) left camera, [n_left, N) right camera ----
     def SearchByProjectionFisheye(self, left: FrameView, kps_right, l2r, r2l, mp: dict, th: float = 3.0, frame_occupied=None):
         """ORBmatcher.cc:43-213 whole.  left.descriptors holds ALL n_left + n_right rows; mp: in_view, proj_x, proj_y, level,
-        view_cos, in_view_r, proj_xr, proj_yr, level_r, view_cos_r, desc, has_obs."""
+        view_cos, in_view_r, proj_xr, proj_yr, level_r, view_cos_r, desc, has_obs.  left may be a fisheye DeviceFrame (kps_right, l2r and
+        r2l are then the handle's: pass None)."""
+        if isinstance(left, DeviceFrame):
+            a = [_u8(mp["in_view"]), _f32(mp["proj_x"]), _f32(mp["proj_y"]), _i32(mp["level"]), _f32(mp["view_cos"]), _u8(mp["in_view_r"]),
+                 _f32(mp["proj_xr"]), _f32(mp["proj_yr"]), _i32(mp["level_r"]), _f32(mp["view_cos_r"]), _u8(mp["desc"]), _u8(mp.get("has_obs"))]
+            occ = _u8(frame_occupied)
+            fm = np.full(self._frame_rows(left, occ), -1, np.int32)
+            n = check(self._L.orbx_frame_search_by_projection_mappoints_fisheye(self._h, left._h, ptr(occ), len(a[0]), *[ptr(x) for x in a], th,
+                                                                                self.mfNNratio, ptr(fm)),
+                      "orbx_frame_search_by_projection_mappoints_fisheye")
+            return n, fm[:left.count()]
         kr = np.ascontiguousarray(kps_right, KP_DTYPE)
         left.keypoints_un = np.ascontiguousarray(left.keypoints_un, KP_DTYPE)
         fd = left.c_struct()
@@ -408,7 +442,17 @@ class ORBmatcher:
         return n, fm
 
     def SearchByProjectionFrameFisheye(self, left: FrameView, kps_right, q: dict, th: float, level_mode: int = 0, cur_occupied=None, raw=False):
-        """ORBmatcher.cc:1676-1887 with the twin :1794-1863.  q: u, v, xr, yr, octave, angle, desc, has_obs."""
+        """ORBmatcher.cc:1676-1887 with the twin :1794-1863.  q: u, v, xr, yr, octave, angle, desc, has_obs.  left may be a fisheye
+        DeviceFrame (kps_right: None)."""
+        if isinstance(left, DeviceFrame):
+            a = [_f32(q["u"]), _f32(q["v"]), _f32(q["xr"]), _f32(q["yr"]), _i32(q["octave"]), _f32(q["angle"]), _u8(q["desc"]), _u8(q.get("has_obs"))]
+            occ = _u8(cur_occupied)
+            cm = np.full(self._frame_rows(left, occ), -1, np.int32)
+            n = check(self._L.orbx_frame_search_by_projection_frame_fisheye(self._h, left._h, ptr(occ), len(a[0]), *[ptr(x) for x in a], th, level_mode,
+                                                                            int(self.mbCheckOrientation), ptr(cm)),
+                      "orbx_frame_search_by_projection_frame_fisheye")
+            cm = cm[:left.count()]
+            return n, (cm if raw else np.maximum(cm, -1))
         kr = np.ascontiguousarray(kps_right, KP_DTYPE)
         fd = left.c_struct()
         cm = np.full(fd.n + len(kr), -1, np.int32)
@@ -418,6 +462,25 @@ class ORBmatcher:
                                                                   th, level_mode, int(self.mbCheckOrientation), ptr(cm)),
                   "orbx_search_by_projection_frame_fisheye")
         return n, (cm if raw else np.maximum(cm, -1))
+
+    def SearchLocalPointsFisheye(self, F: DeviceFrame, views, log_scale_factor, cos_limit, pos, normal, min_dist, max_dist, desc, eligible=None,
+                                 has_obs=None, track_depth=None, th: float = 1.0, far_points: bool = False, th_far_points: float = 0.0,
+                                 frame_occupied=None):
+        """Tracking::SearchLocalPoints on a fisheye-stereo DeviceFrame in one call (orbx_frame_search_local_points_fisheye).  views = [left, right],
+        each (R, t, twc, params8) as isInFrustumChecks.  track_depth = the map points' previous mTrackDepth (read for right-only points; None: such
+        a point is never far).  Returns (nmatches, frame_match[N], in_view[2, n_mp])."""
+        P, Nn = _f32(np.asarray(pos).reshape(-1, 3)), _f32(np.asarray(normal).reshape(-1, 3))
+        mn, mx, d, el, ho, td, occ = _f32(min_dist), _f32(max_dist), _u8(desc), _u8(eligible), _u8(has_obs), _f32(track_depth), _u8(frame_occupied)
+        n_mp = len(P)
+        V = np.ascontiguousarray(np.concatenate([np.concatenate([np.asarray(x, np.float32).ravel() for x in v]) for v in views]), np.float32)
+        assert V.size == 46, "views: left and right camera"
+        iv = np.zeros((2, n_mp), np.uint8)
+        fm = np.full(self._frame_rows(F, occ), -1, np.int32)
+        n = check(self._L.orbx_frame_search_local_points_fisheye(self._h, F._h, ptr(occ), ptr(V), float(log_scale_factor), float(cos_limit), n_mp,
+                                                                 ptr(P), ptr(Nn), ptr(mn), ptr(mx), ptr(d), ptr(el), ptr(ho), ptr(td), float(th),
+                                                                 self.mfNNratio, int(bool(far_points)), float(th_far_points), ptr(iv), ptr(fm)),
+                  "orbx_frame_search_local_points_fisheye")
+        return n, fm[:F.count()], iv
 
     def SearchByBoWFrameFisheye(self, kf_desc, kf_angle, kf_valid, kf_fv: "FeatureVector", f_desc, f_angle, n_f_left: int, f_fv: "FeatureVector"):
         """ORBmatcher.cc:283-392 (frame features >= n_f_left are the right camera's; `|| true` on the right ratio test)."""
