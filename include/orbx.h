@@ -327,7 +327,8 @@ int orbx_search_by_projection_window(orbx_matcher *m, const orbx_frame_desc *fra
  *     the frame index is not one of the batch, `ex` is on another device, or the batch's per-frame capacity exceeds `cap`.  No mvuRight.
  *   orbx_frame_count: N, synchronising the matcher's stream once if the count is still on the device (cached until the next load).
  * A handle holds a monocular / rectified frame (these loads) or a fisheye-stereo frame (orbx_frame_load_host_fisheye,
- * orbx_frame_load_stereo_fisheye_batch, below); each kind's entry points refuse the other kind with ORBX_E_BAD_ARG.
+ * orbx_frame_load_stereo_fisheye_batch, below); each kind's entry points refuse the other kind with ORBX_E_BAD_ARG (the `_fisheye` forms of
+ * ComputeBoW, SearchByBoW and the window search: after orbx_frame_search_by_projection_window).
  * Checks that fail return before anything is enqueued. */
 typedef struct orbx_frame orbx_frame;
 int orbx_frame_create(orbx_matcher *m, int cap, orbx_frame **out);
@@ -696,16 +697,41 @@ typedef struct orbx_bow_keyframe {
  * candidates in one call: one upload run, one launch chain whose length does not depend on n_kf, one download run, one synchronisation.
  * match_stride >= N; while N is still on the device (orbx_frame_load_batch) a stride below the handle's capacity costs one orbx_frame_count first.
  * Monocular / rectified frames only: a fisheye-stereo handle is refused (ORBX_E_BAD_ARG) by this call and orbx_frame_compute_bow (fisheye-stereo
- * frames: orbx_search_by_bow_frame_fisheye).  n_kf <= ORBX_MAX_BOW_KEYFRAMES (ORBX_E_TOO_LARGE).
+ * handles: orbx_frame_compute_bow_fisheye / orbx_frame_search_by_bow_fisheye, below).  n_kf <= ORBX_MAX_BOW_KEYFRAMES (ORBX_E_TOO_LARGE).
  * Returns ORBX_OK; ORBX_E_BAD_ARG, before anything is enqueued, for a handle of another matcher, a frame without orbx_frame_compute_bow since its
  * last load, or a malformed key frame. */
 int orbx_frame_search_by_bow(orbx_matcher *m, orbx_frame *f, int n_kf, const orbx_bow_keyframe *kfs, float nnratio, int check_orientation,
                              int32_t *match, int match_stride, int32_t *nmatches);
 /* orbx_search_by_projection_window on the resident frame (ORBmatcher.cc:1889-2010: Relocalization's SearchByProjection(F, pKF, sFound, 10, 100)
- * and (.., 3, 64)); match holds N entries.  Results equal the host-pointer form's bit for bit. */
+ * and (.., 3, 64)); match holds N entries.  Results equal the host-pointer form's bit for bit.  Monocular / rectified frames only (fisheye-stereo
+ * handles: orbx_frame_search_by_projection_window_fisheye). */
 int orbx_frame_search_by_projection_window(orbx_matcher *m, orbx_frame *f, const uint8_t *occupied, int n_q, const float *q_x, const float *q_y,
                                            const float *q_r, const int32_t *q_min_level, const int32_t *q_max_level, const float *q_angle,
                                            const uint8_t *q_desc, const uint8_t *q_has_obs, float max_dist, int check_orientation, int32_t *match);
+
+/* ---- BoW and the relocalization window search on a fisheye-stereo handle (Frame::Nleft != -1): TrackReferenceKeyFrame and Relocalization of a rig.
+ * These refuse a monocular / rectified handle with ORBX_E_BAD_ARG, as the forms above refuse a fisheye-stereo one.  Numbering as everywhere for a
+ * rig: features [0, N_left) = left camera, [N_left, N) = right camera.
+ * orbx_frame_compute_bow_fisheye: Frame::ComputeBoW of a rig frame (Frame.cc:738-745; mDescriptors holds all N = N_left + N_right rows) on the
+ *   handle's rows, after orbx_frame_load_host_fisheye or orbx_frame_load_stereo_fisheye_batch.  The FeatureVector stays in the handle (equal to
+ *   TemplatedVocabulary::transform's over the N rows: ascending node ids, ascending feature indices within a node, stopped words dropped).
+ *   word_id / node_id: as orbx_frame_compute_bow (optional, N entries each; buffers of the handle's capacity always suffice).  Both NULL:
+ *   asynchronous, nothing waits and the counts are not read on the host. */
+int orbx_frame_compute_bow_fisheye(orbx_matcher *m, orbx_frame *f, const orbx_vocabulary *voc, int levelsup, int32_t *word_id, int32_t *node_id);
+/* orbx_frame_search_by_bow_fisheye: SearchByBoW(kfs[k], F, vvpMapPointMatches[k]) for a rig frame (ORBmatcher.cc:283-392) for k < n_kf; row k
+ *   equals orbx_search_by_bow_frame_fisheye for key frame k bit for bit (N entries; a right-camera match sits at N_left + j).  kfs[k].angle: the
+ *   key frame's keypoint angles (mvKeysUn, or mvKeys / mvKeysRight of a fisheye key frame).  Arguments, limits, cost shape and errors as
+ *   orbx_frame_search_by_bow; the frame needs orbx_frame_compute_bow_fisheye since its last load. */
+int orbx_frame_search_by_bow_fisheye(orbx_matcher *m, orbx_frame *f, int n_kf, const orbx_bow_keyframe *kfs, float nnratio, int check_orientation,
+                                     int32_t *match, int match_stride, int32_t *nmatches);
+/* orbx_frame_search_by_projection_window_fisheye: Relocalization's SearchByProjection(F, pKF, sFound, th, ORBdist) (ORBmatcher.cc:1889-2010) on a
+ *   rig frame.  GetFeaturesInArea runs with its default bRight = false, so only the LEFT camera is searched (raw mvKeys, the left grid; N_left is
+ *   read on the device).  occupied and match hold all N entries: occupancy is read for [0, N_left) only, the right camera's entries of match
+ *   stay -1.  Otherwise as orbx_frame_search_by_projection_window. */
+int orbx_frame_search_by_projection_window_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *occupied, int n_q, const float *q_x,
+                                                   const float *q_y, const float *q_r, const int32_t *q_min_level, const int32_t *q_max_level,
+                                                   const float *q_angle, const uint8_t *q_desc, const uint8_t *q_has_obs, float max_dist,
+                                                   int check_orientation, int32_t *match);
 
 /* Frame::ComputeStereoMatches (Frame.cc:811-981) for every frame of two resident batches: `left` and `right` must have
  * extracted batches of the same size and image shape (rectified stereo, lapping {0,0}).  Row-band Hamming match, 11x11

@@ -144,6 +144,7 @@ SYMBOLS = [
     "orbx_vocabulary_set_word_weights", "orbx_frame_compute_bow", "orbx_frame_search_by_bow", "orbx_frame_search_by_projection_window",
     "orbx_frame_load_host_fisheye", "orbx_frame_load_stereo_fisheye_batch", "orbx_frame_counts", "orbx_frame_search_by_projection_mappoints_fisheye",
     "orbx_frame_search_by_projection_frame_fisheye", "orbx_frame_search_local_points_fisheye",
+    "orbx_frame_compute_bow_fisheye", "orbx_frame_search_by_bow_fisheye", "orbx_frame_search_by_projection_window_fisheye",
 ]
 
 
@@ -260,6 +261,9 @@ def lib() -> C.CDLL:
     L.orbx_frame_search_by_projection_mappoints_fisheye.argtypes = [vp, vp, vp, i32] + [vp] * 12 + [f32, f32, vp]
     L.orbx_frame_search_by_projection_frame_fisheye.argtypes = [vp, vp, vp, i32] + [vp] * 8 + [f32, i32, i32, vp]
     L.orbx_frame_search_local_points_fisheye.argtypes = [vp, vp, vp, vp, f32, f32, i32] + [vp] * 8 + [f32, f32, i32, f32, vp, vp]
+    L.orbx_frame_compute_bow_fisheye.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.orbx_frame_search_by_bow_fisheye.argtypes = [vp, vp, i32, C.POINTER(BowKeyFrame), f32, i32, vp, i32, vp]
+    L.orbx_frame_search_by_projection_window_fisheye.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, i32, vp]
     _lib = L
     return L
 

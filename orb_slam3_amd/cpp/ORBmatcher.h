@@ -87,6 +87,10 @@ public:
     // overloads on a DeviceFrame.  wordId / nodeId (optional) receive N ids each -- mBowVec is folded from the word ids on the host.
     inline void ComputeBoW(ORBmatcher &matcher, const ORBVocabularyDevice &voc, int levelsup = 4, std::vector<int32_t> *wordId = nullptr,
                            std::vector<int32_t> *nodeId = nullptr);
+    // the same for a fisheye-stereo frame (orbx_frame_compute_bow_fisheye): all N = Nleft + N_right rows, ids in the rig's numbering (features
+    // >= Nleft are the right camera's); the FeatureVector stays here for ORBmatcher::SearchByBoWFisheye
+    inline void ComputeBoWFisheye(ORBmatcher &matcher, const ORBVocabularyDevice &voc, int levelsup = 4, std::vector<int32_t> *wordId = nullptr,
+                                  std::vector<int32_t> *nodeId = nullptr);
     orbx_frame *handle() const { return f_; }
 
 private:
@@ -282,6 +286,18 @@ public:
         if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_by_projection_window: ") + orbx_status_string(r));
         return r;
     }
+    // the same on a resident fisheye-stereo frame (orbx_frame_search_by_projection_window_fisheye): the LEFT camera only (GetFeaturesInArea's
+    // default bRight = false); occupied and vpMatch hold N entries, the right camera's entries of vpMatch stay -1
+    int SearchByProjectionWindowFisheye(DeviceFrame &F, const std::vector<uint8_t> &occupied, const WindowQueries &q, float maxDist, bool checkOrientation,
+                                        std::vector<int32_t> &vpMatch) {
+        vpMatch.assign(F.count(), -1);
+        const int r = orbx_frame_search_by_projection_window_fisheye(m_, F.handle(), occupied.empty() ? nullptr : occupied.data(), (int)q.x.size(),
+                                                                     q.x.data(), q.y.data(), q.r.data(), q.minLevel.data(), q.maxLevel.data(),
+                                                                     q.angle.empty() ? nullptr : q.angle.data(), q.descriptors.data(), nullptr, maxDist,
+                                                                     checkOrientation ? 1 : 0, vpMatch.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_by_projection_window_fisheye: ") + orbx_status_string(r));
+        return r;
+    }
 
     // SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) (ORBmatcher.cc:648-763)
     int SearchForInitialization(const orbx_keypoint *mvKeysUn1, const uint8_t *mDescriptors1, int N1, const FrameView &F2,
@@ -323,12 +339,22 @@ public:
     // SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) against every key frame of kfs at once on a resident frame after DeviceFrame::ComputeBoW
     // (orbx_frame_search_by_bow): vpMatch[k][iF] = KF feature index or -1, nmatches[k] = the member's return value.  Returns the sum.
     int SearchByBoW(DeviceFrame &F, const std::vector<orbx_bow_keyframe> &kfs, std::vector<int32_t> &nmatches, std::vector<std::vector<int32_t>> &vpMatch) {
+        return searchByBoWDevice(F, kfs, nmatches, vpMatch, orbx_frame_search_by_bow, "orbx_frame_search_by_bow");
+    }
+    // the same for a fisheye-stereo frame after DeviceFrame::ComputeBoWFisheye (orbx_frame_search_by_bow_fisheye, ORBmatcher.cc:283-392):
+    // vpMatch[k] holds N entries, a right-camera match at Nleft + j.  kfs[k].angle: mvKeysUn, or mvKeys / mvKeysRight of a fisheye key frame.
+    int SearchByBoWFisheye(DeviceFrame &F, const std::vector<orbx_bow_keyframe> &kfs, std::vector<int32_t> &nmatches,
+                           std::vector<std::vector<int32_t>> &vpMatch) {
+        return searchByBoWDevice(F, kfs, nmatches, vpMatch, orbx_frame_search_by_bow_fisheye, "orbx_frame_search_by_bow_fisheye");
+    }
+    int searchByBoWDevice(DeviceFrame &F, const std::vector<orbx_bow_keyframe> &kfs, std::vector<int32_t> &nmatches, std::vector<std::vector<int32_t>> &vpMatch,
+                          int (*fn)(orbx_matcher *, orbx_frame *, int, const orbx_bow_keyframe *, float, int, int32_t *, int, int32_t *), const char *what) {
         const int nkf = (int)kfs.size();
         const int N = F.count(), stride = std::max(N, 1);
         std::vector<int32_t> rows((size_t)std::max(nkf, 1) * stride, -1);
         nmatches.assign(nkf, 0);
-        const int r = orbx_frame_search_by_bow(m_, F.handle(), nkf, kfs.data(), mfNNratio, mbCheckOrientation ? 1 : 0, rows.data(), stride, nmatches.data());
-        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_by_bow: ") + orbx_status_string(r) + " " + orbx_last_error());
+        const int r = fn(m_, F.handle(), nkf, kfs.data(), mfNNratio, mbCheckOrientation ? 1 : 0, rows.data(), stride, nmatches.data());
+        if (r < 0) throw std::runtime_error(std::string(what) + ": " + orbx_status_string(r) + " " + orbx_last_error());
         vpMatch.assign(nkf, std::vector<int32_t>());
         int total = 0;
         for (int k = 0; k < nkf; k++) {
@@ -575,6 +601,19 @@ inline void DeviceFrame::ComputeBoW(ORBmatcher &matcher, const ORBVocabularyDevi
     }
     std::vector<int32_t> w(cap_), nd(cap_);
     check(orbx_frame_compute_bow(matcher.handle(), f_, voc.handle(), levelsup, w.data(), nd.data()), "orbx_frame_compute_bow");
+    const int n = count();   // known after the call
+    if (wordId) wordId->assign(w.begin(), w.begin() + n);
+    if (nodeId) nodeId->assign(nd.begin(), nd.begin() + n);
+}
+
+inline void DeviceFrame::ComputeBoWFisheye(ORBmatcher &matcher, const ORBVocabularyDevice &voc, int levelsup, std::vector<int32_t> *wordId,
+                                           std::vector<int32_t> *nodeId) {
+    if (!wordId && !nodeId) {
+        check(orbx_frame_compute_bow_fisheye(matcher.handle(), f_, voc.handle(), levelsup, nullptr, nullptr), "orbx_frame_compute_bow_fisheye");
+        return;
+    }
+    std::vector<int32_t> w(cap_), nd(cap_);
+    check(orbx_frame_compute_bow_fisheye(matcher.handle(), f_, voc.handle(), levelsup, w.data(), nd.data()), "orbx_frame_compute_bow_fisheye");
     const int n = count();   // known after the call
     if (wordId) wordId->assign(w.begin(), w.begin() + n);
     if (nodeId) nodeId->assign(nd.begin(), nd.begin() + n);

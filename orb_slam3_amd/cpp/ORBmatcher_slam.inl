@@ -150,11 +150,48 @@ public:
         // bRight = false, mvKeysUn == mvKeys there (Frame.cc:751); the right camera's features are neither candidates nor written
         const bool fisheye = CurrentFrame.Nleft != -1;
         const int NL = fisheye ? CurrentFrame.Nleft : CurrentFrame.N;
+        WindowQueries q;
+        std::vector<MapPoint *> live;
+        relocalizationQueries(CurrentFrame, pKF, sAlreadyFound, th, q, live);
+        std::vector<uint8_t> occupied(NL);
+        for (int i = 0; i < NL; i++) occupied[i] = CurrentFrame.mvpMapPoints[i] ? 1 : 0;   // :1955: any map point blocks the slot
+        std::vector<int32_t> match;
+        FrameView fv = view_of(CurrentFrame, fisheye ? CurrentFrame.mvKeys : CurrentFrame.mvKeysUn, false);
+        fv.N = NL;
+        const int nmatches = SearchByProjectionWindow(fv, occupied, q, (float)ORBdist, mbCheckOrientation, match);
+        for (int i = 0; i < NL; i++) {
+            if (match[i] >= 0) CurrentFrame.mvpMapPoints[i] = live[match[i]];
+            else if (match[i] == -2) CurrentFrame.mvpMapPoints[i] = NULL;           // :2001
+        }
+        return nmatches;
+    }
+
+    // The same member for a fisheye-stereo frame resident on the device (DeviceFrame after loadFisheye / loadStereoFisheyeBatch): the left camera's
+    // rows and grid are the handle's (orbx_frame_search_by_projection_window_fisheye); nothing of the frame is uploaded again.
+    int SearchByProjectionFisheye(Frame &CurrentFrame, DeviceFrame &DF, KeyFrame *pKF, const std::set<MapPoint *> &sAlreadyFound, const float th,
+                                  const int ORBdist) {
+        if (CurrentFrame.Nleft == -1) throw std::runtime_error("SearchByProjectionFisheye(DeviceFrame): a monocular / rectified frame takes SearchByProjection");
+        const int N = CurrentFrame.N, NL = CurrentFrame.Nleft;
+        WindowQueries q;
+        std::vector<MapPoint *> live;
+        relocalizationQueries(CurrentFrame, pKF, sAlreadyFound, th, q, live);
+        std::vector<uint8_t> occupied(N);
+        for (int i = 0; i < N; i++) occupied[i] = CurrentFrame.mvpMapPoints[i] ? 1 : 0;     // :1955 (read for [0, Nleft) only)
+        std::vector<int32_t> match;
+        const int nmatches = SearchByProjectionWindowFisheye(DF, occupied, q, (float)ORBdist, mbCheckOrientation, match);
+        for (int i = 0; i < NL; i++) {
+            if (match[i] >= 0) CurrentFrame.mvpMapPoints[i] = live[match[i]];
+            else if (match[i] == -2) CurrentFrame.mvpMapPoints[i] = NULL;           // :2001
+        }
+        return nmatches;
+    }
+
+    // the queries of SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) (ORBmatcher.cc:1906-1948): live[k] = the map point of query k
+    void relocalizationQueries(Frame &CurrentFrame, KeyFrame *pKF, const std::set<MapPoint *> &sAlreadyFound, const float th, WindowQueries &q,
+                               std::vector<MapPoint *> &live) {
         const Sophus::SE3f Tcw = CurrentFrame.GetPose();
         Eigen::Vector3f Ow = Tcw.inverse().translation();
         const std::vector<MapPoint *> vpMPs = pKF->GetMapPointMatches();
-        WindowQueries q;
-        std::vector<MapPoint *> live;
         for (size_t i = 0, iend = vpMPs.size(); i < iend; i++) {
             MapPoint *pMP = vpMPs[i];
             if (!pMP || pMP->isBad() || sAlreadyFound.count(pMP)) continue;
@@ -176,17 +213,6 @@ public:
             push_desc(q.descriptors, pMP->GetDescriptor());
             live.push_back(pMP);
         }
-        std::vector<uint8_t> occupied(NL);
-        for (int i = 0; i < NL; i++) occupied[i] = CurrentFrame.mvpMapPoints[i] ? 1 : 0;   // :1955: any map point blocks the slot
-        std::vector<int32_t> match;
-        FrameView fv = view_of(CurrentFrame, fisheye ? CurrentFrame.mvKeys : CurrentFrame.mvKeysUn, false);
-        fv.N = NL;
-        const int nmatches = SearchByProjectionWindow(fv, occupied, q, (float)ORBdist, mbCheckOrientation, match);
-        for (int i = 0; i < NL; i++) {
-            if (match[i] >= 0) CurrentFrame.mvpMapPoints[i] = live[match[i]];
-            else if (match[i] == -2) CurrentFrame.mvpMapPoints[i] = NULL;           // :2001
-        }
-        return nmatches;
     }
 
     // ORBmatcher.cc:648-763 (Tracking::MonocularInitialization)
@@ -282,6 +308,53 @@ public:
             nmatches[k] = nm[k];
             for (int i = 0; i < F.N && i < (int)match[k].size(); i++)
                 if (match[k][i] >= 0) vvpMapPointMatches[k][i] = vpMPs[k][match[k][i]];   // :329
+        }
+    }
+
+    // The rig's forms on a fisheye-stereo frame resident on the device (F.Nleft != -1, DeviceFrame after DeviceFrame::ComputeBoWFisheye):
+    // SearchByBoW(KeyFrame*, Frame&, ...) of ORBmatcher.cc:283-392 against one key frame (Tracking::TrackReferenceKeyFrame) or every Relocalization
+    // candidate in ONE device call (orbx_frame_search_by_bow_fisheye).  Each result equals the overload without a DeviceFrame above.
+    int SearchByBoWFisheye(KeyFrame *pKF, Frame &F, DeviceFrame &DF, std::vector<MapPoint *> &vpMapPointMatches) {
+        std::vector<KeyFrame *> kfs(1, pKF);
+        std::vector<std::vector<MapPoint *>> matches;
+        std::vector<int> nmatches;
+        SearchByBoWFisheye(kfs, F, DF, matches, nmatches);
+        vpMapPointMatches = matches[0];
+        return nmatches[0];
+    }
+    void SearchByBoWFisheye(const std::vector<KeyFrame *> &vpKFs, Frame &F, DeviceFrame &DF, std::vector<std::vector<MapPoint *>> &vvpMapPointMatches,
+                            std::vector<int> &nmatches) {
+        if (F.Nleft == -1) throw std::runtime_error("SearchByBoWFisheye(DeviceFrame): a monocular / rectified frame takes SearchByBoW(DeviceFrame)");
+        const size_t nkf = vpKFs.size();
+        std::vector<std::vector<MapPoint *>> vpMPs(nkf);
+        std::vector<std::vector<uint8_t>> valid(nkf);
+        std::vector<std::vector<float>> ang(nkf);
+        std::vector<FeatVec> fvs(nkf);
+        std::vector<orbx_bow_keyframe> kfs(nkf);
+        for (size_t k = 0; k < nkf; k++) {
+            KeyFrame *pKF = vpKFs[k];
+            vpMPs[k] = pKF->GetMapPointMatches();
+            const int nKF = (int)vpMPs[k].size();
+            valid[k].resize(nKF);
+            ang[k].resize(nKF);
+            for (int i = 0; i < nKF; i++) {
+                MapPoint *pMP = vpMPs[k][i];
+                valid[k][i] = (pMP && !pMP->isBad()) ? 1 : 0;                          // :252-256
+                ang[k][i] = (!pKF->mpCamera2) ? pKF->mvKeysUn[i].angle                 // :331-343
+                                              : (i >= pKF->NLeft ? pKF->mvKeysRight[i - pKF->NLeft].angle : pKF->mvKeys[i].angle);
+            }
+            fvs[k] = FeatVec::from(pKF->mFeatVec);
+            kfs[k] = orbx_bow_keyframe{pKF->mDescriptors.data, ang[k].data(), valid[k].data(), nKF, fvs[k].c()};
+        }
+        std::vector<int32_t> nm;
+        std::vector<std::vector<int32_t>> match;
+        SearchByBoWFisheye(DF, kfs, nm, match);
+        vvpMapPointMatches.assign(nkf, std::vector<MapPoint *>(F.N, static_cast<MapPoint *>(NULL)));
+        nmatches.assign(nkf, 0);
+        for (size_t k = 0; k < nkf; k++) {
+            nmatches[k] = nm[k];
+            for (int i = 0; i < F.N && i < (int)match[k].size(); i++)
+                if (match[k][i] >= 0) vvpMapPointMatches[k][i] = vpMPs[k][match[k][i]];   // :329, :359
         }
     }
 

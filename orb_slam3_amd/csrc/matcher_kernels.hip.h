@@ -363,6 +363,20 @@ __global__ __launch_bounds__(256) void k_frame_bow_transform(const int32_t *__re
     const int n = n_host >= 0 ? n_host : min(max(*count, 0), cap);
     bow_transform_body(child_ptr, child_idx, node_desc, word_id, L, levelsup, desc, n, word_out, node_out);
 }
+// the same on a resident fisheye-stereo frame (orbx_frame_compute_bow_fisheye): blockIdx.y = camera, the right camera's rows start at roff (the gap
+// rows between N_left and roff are never read).  n_host[c] >= 0, or count[c] read on the device, clamped to cap_side[c].  Ids land at the rows.
+// grid (ceil(max side / 16), 2), block 256
+__global__ __launch_bounds__(256) void k_frame_bow_transform_fisheye(const int32_t *__restrict__ child_ptr, const int32_t *__restrict__ child_idx,
+                                                                     const uint8_t *__restrict__ node_desc, const int32_t *__restrict__ word_id, int L,
+                                                                     int levelsup, const uint8_t *__restrict__ desc, const int32_t *__restrict__ count,
+                                                                     int nl_host, int nr_host, int cap_l, int cap_r, int roff,
+                                                                     int32_t *__restrict__ word_out, int32_t *__restrict__ node_out) {
+    const int c = blockIdx.y;
+    const int nh = c ? nr_host : nl_host;
+    const int n = nh >= 0 ? nh : min(max(count[c], 0), c ? cap_r : cap_l);
+    const size_t o = c ? (size_t)roff : 0;
+    bow_transform_body(child_ptr, child_idx, node_desc, word_id, L, levelsup, desc + o * 32, n, word_out + o, node_out + o);
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // Frame::ComputeStereoMatches fully on the device for a batch of rectified stereo frames whose left / right
@@ -2992,6 +3006,84 @@ __global__ __launch_bounds__(1024) void k_frame_featvec(const FrameBow B, int so
         B.fv_index[p] = (int32_t)(keys[p] & 0xffffu);
     }
     if (t == 1023) { B.fv_ptr[sums[1023]] = kept; B.fv_meta[0] = sums[1023]; B.fv_meta[1] = kept; }
+}
+// k_frame_featvec for a fisheye-stereo frame (orbx_frame_compute_bow_fisheye), in ROW space: feature p < N_left is row p, feature p >= N_left is
+// row roff + p - N_left (the gap rows of a batch load are never read).  Keys, fv_index and angle[] are rows; rows ascend with the features
+// (roff >= N_left), so every node's list is in the reference's order.  N_left / N_right: nl_host / nr_host, or count[0] / count[1] read on the
+// device (clamped to roff / cap - roff).  grid 1, block 1024, dynamic LDS 8 * sort_cap (a power of two >= the features the call may see)
+__global__ __launch_bounds__(1024) void k_frame_featvec_fisheye(const FrameBow B, int sort_cap, int nl_host, int nr_host, int roff) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+    u64 *keys = reinterpret_cast<u64 *>(lds);
+    __shared__ int32_t sums[1024];
+    __shared__ int32_t kept_s;
+    const int t = threadIdx.x;
+    const int nl = nl_host >= 0 ? nl_host : min(max(B.count[0], 0), roff);
+    const int nr = nr_host >= 0 ? nr_host : min(max(B.count[1], 0), B.cap - roff);
+    const int n = nl + nr;
+    int p2 = 1;
+    while (p2 < n) p2 <<= 1;
+    p2 = min(p2, sort_cap);
+    if (t == 0) kept_s = 0;
+    for (int p = t; p < p2; p += 1024) {
+        u64 key = kNoKey;
+        if (p < n) {
+            const int r = p < nl ? p : roff + p - nl;   // feature p's row
+            const int w = B.word[r];
+            const bool stopped = B.word_pos && (w < 0 || w >= B.n_words || !B.word_pos[w]);
+            if (!stopped) key = ((u64)(uint32_t)B.node[r] << 16) | (u64)r;
+            B.angle[r] = B.kps[r].angle;
+        }
+        keys[p] = key;
+    }
+    __syncthreads();
+    for (int k = 2; k <= p2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int p = t; p < p2; p += 1024) {
+                const int q = p ^ j;
+                if (q > p) {
+                    const u64 a = keys[p], b = keys[q];
+                    if ((a > b) == ((p & k) == 0)) { keys[p] = b; keys[q] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    // kept features = the keys before the first all-ones one (the keys of kept features are distinct)
+    for (int p = t; p < p2; p += 1024)
+        if (keys[p] != kNoKey && (p + 1 == p2 || keys[p + 1] == kNoKey)) kept_s = p + 1;
+    __syncthreads();
+    const int kept = kept_s;
+    const int chunk = (p2 + 1023) / 1024, c0 = min(t * chunk, kept), c1 = min(c0 + chunk, kept);
+    auto starts = [&](int p) { return p == 0 || (keys[p] >> 16) != (keys[p - 1] >> 16); };
+    int c = 0;
+    for (int p = c0; p < c1; p++) c += starts(p) ? 1 : 0;
+    sums[t] = c;
+    __syncthreads();
+    for (int off = 1; off < 1024; off <<= 1) {   // inclusive scan of the per-thread node starts
+        const int v = t >= off ? sums[t - off] : 0;
+        __syncthreads();
+        sums[t] += v;
+        __syncthreads();
+    }
+    int slot = sums[t] - c;
+    for (int p = c0; p < c1; p++) {
+        if (starts(p)) { B.fv_node[slot] = (uint32_t)(keys[p] >> 16); B.fv_ptr[slot] = p; slot++; }
+        B.fv_index[p] = (int32_t)(keys[p] & 0xffffu);
+    }
+    if (t == 1023) { B.fv_ptr[sums[1023]] = kept; B.fv_meta[0] = sums[1023]; B.fv_meta[1] = kept; }
+}
+
+// k_frame_rows_to_features: a fisheye-stereo handle's row space back to the reference numbering, for n_rows arrays side by side:
+// out[k * out_stride + i] = in[k * in_stride + (i < N_left ? i : roff + i - N_left)] for i < N = N_left + N_right.  The counts are nl_host /
+// nr_host, or count[0] / count[1] read on the device (clamped as above): no host synchronisation.  grid (ceil(out_stride / 256), n_rows), block 256
+__global__ __launch_bounds__(256) void k_frame_rows_to_features(const int32_t *__restrict__ in, int in_stride, int32_t *__restrict__ out, int out_stride,
+                                                                const int32_t *__restrict__ count, int nl_host, int nr_host, int cap, int roff) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    const int nl = nl_host >= 0 ? nl_host : min(max(count[0], 0), roff);
+    const int nr = nr_host >= 0 ? nr_host : min(max(count[1], 0), cap - roff);
+    if (i >= nl + nr || i >= out_stride) return;
+    const size_t k = blockIdx.y;
+    out[k * out_stride + i] = in[k * in_stride + (i < nl ? i : roff + i - nl)];
 }
 
 // k_bow_pair_nodes: the node pairing of SearchByBoW (:246-250, the merge-join of the two sorted maps) for every node of every key frame of a batch,

@@ -633,15 +633,22 @@ struct ProjArgs {
 };
 
 // fh != NULL: the handle form -- the frame's rows and grid are resident (a.frame is not read); while its N is still on the device (a load_batch
-// nobody has counted yet) every per-feature buffer is sized by the handle's capacity and the count comes back with the results
-int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr) {
+// nobody has counted yet) every per-feature buffer is sized by the handle's capacity and the count comes back with the results.
+// left_only: a fisheye-stereo handle searched through its left camera only (rows [0, N_left), the left grid, count[0]); match_out and the
+// occupancy mask keep the frame's N entries, the right camera's stay -1.
+int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr, bool left_only = false) {
     const orbx_frame_desc *F = a.frame;
     const int nq = a.nq;
-    int n = fh ? -1 : F->n;
-    if (fh && (fh->n_known || a.occupied || nq == 0)) { const int rc = frame_count(fh, &n); if (rc != ORBX_OK) return rc; }   // the mask holds N entries
-    for (int i = 0; i < n; i++) a.match_out[i] = -1;
+    int n = fh ? -1 : F->n, n_out = n;   // n: the features searched, n_out: the entries of match_out
+    if (fh && (fh->n_known || a.occupied || nq == 0)) {   // the mask holds N entries
+        const int rc = frame_count(fh, &n);
+        if (rc != ORBX_OK) return rc;
+        n_out = n;
+        if (left_only) n = fh->n_left;
+    }
+    for (int i = 0; i < n_out; i++) a.match_out[i] = -1;
     if (n == 0 || nq == 0) return 0;
-    const int nc = n >= 0 ? n : fh->cap;   // features the device buffers are sized for
+    const int nc = n >= 0 ? n : left_only ? fh->roff : fh->cap;   // features the device buffers are sized for
     if (nc > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;  // before anything is enqueued: the resolve pass keeps 10 B per feature in LDS
     ORBX_HIP(hipSetDevice(m->device));
     size_t need = Arena::pad(28 * (size_t)nc) + Arena::pad(32 * (size_t)nc) + 3 * Arena::pad((size_t)nc) + Arena::pad(4 * (size_t)nc) * 2 +
@@ -715,11 +722,18 @@ int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr)
     } else {   // N comes back with the results (one small copy of the handle's count)
         fh->h_match.resize((size_t)fh->cap);
         D2H(fh->h_match.data(), R.match, 4 * (size_t)nc);
-        D2H(&fh->n, fh->count, 4);
+        if (left_only) D2H(fh->h_count, fh->count, 8);
+        else D2H(&fh->n, fh->count, 4);
     }
     D2H(&nm, R.nmatches, 4);
     SYNC_AND_DELIVER();
-    if (n < 0) {
+    if (n < 0 && left_only) {
+        fh->n_left = std::min(std::max(fh->h_count[0], 0), fh->roff);
+        fh->n_right = std::min(std::max(fh->h_count[1], 0), fh->cap - fh->roff);
+        fh->n = fh->n_left + fh->n_right; fh->n_known = true;
+        memcpy(a.match_out, fh->h_match.data(), 4 * (size_t)fh->n_left);
+        for (int i = fh->n_left; i < fh->n; i++) a.match_out[i] = -1;
+    } else if (n < 0) {
         fh->n_known = true;
         memcpy(a.match_out, fh->h_match.data(), 4 * (size_t)std::max(fh->n, 0));
     }
@@ -1197,6 +1211,21 @@ extern "C" int orbx_frame_search_by_projection_window(orbx_matcher *m, orbx_fram
     ProjArgs a = {&d, occupied, n_q, q_x, q_y, q_r, nullptr, q_min_level, q_max_level, q_desc, nullptr, q_has_obs,
                   q_angle, 2, 0.f, check_orientation, match, max_dist};
     return run_projection(m, a, f);
+}
+
+// the same on a resident fisheye-stereo frame: Relocalization's SearchByProjection(F, pKF, sFound, th, ORBdist) calls GetFeaturesInArea with the
+// default bRight = false, so only the LEFT camera is searched (raw mvKeys, the left grid, N_left = count[0] on the device); occupied / match cover
+// all N features and the right camera's entries of match stay -1
+extern "C" int orbx_frame_search_by_projection_window_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *occupied, int n_q, const float *q_x,
+                                                              const float *q_y, const float *q_r, const int32_t *q_min_level,
+                                                              const int32_t *q_max_level, const float *q_angle, const uint8_t *q_desc,
+                                                              const uint8_t *q_has_obs, float max_dist, int check_orientation, int32_t *match) {
+    if (!m || !f || f->owner != m || !f->fisheye || !match || n_q < 0) return ORBX_E_BAD_ARG;
+    if (n_q > 0 && (!q_x || !q_y || !q_r || !q_min_level || !q_max_level || !q_desc || (check_orientation && !q_angle))) return ORBX_E_BAD_ARG;
+    const orbx_frame_desc d = frame_desc_of(f);
+    ProjArgs a = {&d, occupied, n_q, q_x, q_y, q_r, nullptr, q_min_level, q_max_level, q_desc, nullptr, q_has_obs,
+                  q_angle, 2, 0.f, check_orientation, match, max_dist};
+    return run_projection(m, a, f, true);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2464,12 +2493,75 @@ extern "C" int orbx_frame_compute_bow(orbx_matcher *m, orbx_frame *f, const orbx
     return ORBX_OK;
 }
 
+// Frame::ComputeBoW of a resident fisheye-stereo frame (Frame.cc:738-745 over all N = N_left + N_right rows of mDescriptors): the handle's rows
+// are transformed in place (k_frame_bow_transform_fisheye, the gap rows of a batch load skipped) and k_frame_featvec_fisheye builds the
+// FeatureVector in row space.  The downloaded ids are renumbered into features [0, N) on the device (k_frame_rows_to_features): with N_left
+// still on the device nothing waits for it.  Without downloads nothing waits at all.
+extern "C" int orbx_frame_compute_bow_fisheye(orbx_matcher *m, orbx_frame *f, const orbx_vocabulary *v, int levelsup, int32_t *word_id,
+                                              int32_t *node_id) {
+    if (!m || !f || !v || f->owner != m || !f->fisheye || v->device != m->device) return ORBX_E_BAD_ARG;
+    ORBX_HIP(hipSetDevice(m->device));
+    const bool down = word_id || node_id;
+    const int nl_host = f->n_known ? f->n_left : -1, nr_host = f->n_known ? f->n_right : -1;
+    const int cap_l = f->roff, cap_r = f->cap - f->roff;   // the rows each camera may occupy
+    const int nc = f->n_known ? f->n : f->cap;             // features the kernels may see
+    const int side = f->n_known ? std::max(nl_host, nr_host) : std::max(cap_l, cap_r);
+    int sort_cap = 1;
+    while (sort_cap < nc) sort_cap <<= 1;
+    const size_t lds = 8 * (size_t)sort_cap;
+    int r = m->reserve_all(Arena::pad(8 * (size_t)nc) + 4096);   // (the renumbered ids)
+    if (r != ORBX_OK) return r;
+    m->begin();
+    f->bow_valid = false;
+    if (side > 0)
+        hipLaunchKernelGGL(k_frame_bow_transform_fisheye, dim3((unsigned)((side + 15) / 16), 2), dim3(256), 0, m->stream, v->child_ptr, v->child_idx,
+                           v->node_desc, v->word_id, v->L, levelsup, f->desc, f->count, nl_host, nr_host, cap_l, cap_r, f->roff, f->bow_word,
+                           f->bow_node);
+    FrameBow B;
+    memset(&B, 0, sizeof(B));
+    B.count = f->count; B.n_host = f->n_known ? f->n : -1; B.cap = f->cap; B.kps = f->kps; B.word = f->bow_word; B.node = f->bow_node;
+    B.word_pos = v->word_pos; B.n_words = v->n_words;
+    B.angle = f->angle; B.fv_node = f->fv_node; B.fv_ptr = f->fv_ptr; B.fv_index = f->fv_index; B.fv_meta = f->fv_meta;
+    if (lds > 64 * 1024)
+        ORBX_HIP(hipFuncSetAttribute((const void *)k_frame_featvec_fisheye, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_frame_featvec_fisheye, dim3(1), dim3(1024), lds, m->stream, B, sort_cap, nl_host, nr_host, f->roff);
+    ORBX_HIP(hipGetLastError());
+    f->bow_valid = true; f->bow_voc = v; f->bow_levelsup = levelsup;
+    if (!down || nc == 0) return ORBX_OK;
+    int32_t *dids = m->arena.take<int32_t>(2 * (size_t)nc);   // word ids, then node ids, in features [0, N)
+    const int32_t *src[2] = {f->bow_word, f->bow_node};
+    for (int k = 0; k < 2; k++)
+        hipLaunchKernelGGL(k_frame_rows_to_features, dim3((unsigned)((nc + 255) / 256), 1), dim3(256), 0, m->stream, src[k], 0, dids + (size_t)k * nc, nc,
+                           f->count, nl_host, nr_host, f->cap, f->roff);
+    ORBX_HIP(hipGetLastError());
+    if (f->n_known) {
+        if (word_id) D2H(word_id, dids, 4 * (size_t)nc);
+        if (node_id) D2H(node_id, dids + nc, 4 * (size_t)nc);
+        SYNC_AND_DELIVER();
+        return ORBX_OK;
+    }
+    f->h_bow.resize(2 * (size_t)f->cap);   // the counts come back with the ids
+    D2H(f->h_bow.data(), dids, 8 * (size_t)nc);
+    D2H(f->h_count, f->count, 8);
+    SYNC_AND_DELIVER();
+    f->n_left = std::min(std::max(f->h_count[0], 0), f->roff);
+    f->n_right = std::min(std::max(f->h_count[1], 0), f->cap - f->roff);
+    f->n = f->n_left + f->n_right;
+    f->n_known = true;
+    if (word_id) memcpy(word_id, f->h_bow.data(), 4 * (size_t)f->n);
+    if (node_id) memcpy(node_id, f->h_bow.data() + f->cap, 4 * (size_t)f->n);
+    return ORBX_OK;
+}
+
 // ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (ORBmatcher.cc:223-425) of the resident frame against n_kf key frames at once
 // (Tracking::Relocalization, Tracking.cc:3670-3700; n_kf = 1: TrackReferenceKeyFrame): one upload run (the key frames and one BowProblem each),
 // k_bow_pair_nodes, k_replay_bow_batch and k_replay_bow_finish_batch, one download run, one synchronisation -- whatever n_kf is.
-extern "C" int orbx_frame_search_by_bow(orbx_matcher *m, orbx_frame *f, int n_kf, const orbx_bow_keyframe *kfs, float nnratio, int check_orientation,
-                                        int32_t *match, int match_stride, int32_t *nmatches) {
-    if (!m || !f || f->owner != m || f->fisheye || !f->bow_valid || n_kf < 0) return ORBX_E_BAD_ARG;
+// fisheye (orbx_frame_search_by_bow_fisheye): the frame side is the handle's ROW space -- k_replay_bow mode 3 with nb_left = roff (a row >= roff is
+// the right camera's; rows ascend with the reference's feature indices, so every tie is the reference's), then k_frame_rows_to_features renumbers
+// the rows into features [0, N) on the device.
+static int frame_search_by_bow_impl(orbx_matcher *m, orbx_frame *f, int n_kf, const orbx_bow_keyframe *kfs, float nnratio, int check_orientation,
+                                    int32_t *match, int match_stride, int32_t *nmatches, bool fisheye) {
+    if (!m || !f || f->owner != m || f->fisheye != fisheye || !f->bow_valid || n_kf < 0) return ORBX_E_BAD_ARG;
     if (n_kf > ORBX_MAX_BOW_KEYFRAMES) return ORBX_E_TOO_LARGE;
     if (n_kf == 0) return ORBX_OK;
     if (!kfs || !match || !nmatches || match_stride < 0) return ORBX_E_BAD_ARG;
@@ -2494,6 +2586,7 @@ extern "C" int orbx_frame_search_by_bow(orbx_matcher *m, orbx_frame *f, int n_kf
     if (n < 0 && match_stride < f->cap) { const int rc = frame_count(f, &n); if (rc != ORBX_OK) return rc; }   // the rows must fit the stride
     if (n >= 0 && match_stride < n) return ORBX_E_BAD_ARG;
     const int nc = n >= 0 ? n : f->cap;   // features the device rows are sized for
+    const int nrows = !fisheye ? nc : n >= 0 ? f->roff + f->n_right : f->cap;   // the replay's rows (fisheye: left, gap, right)
     for (int k = 0; k < n_kf; k++) {
         nmatches[k] = 0;
         for (int i = 0; i < std::max(n, 0); i++) match[(size_t)k * match_stride + i] = -1;
@@ -2501,8 +2594,14 @@ extern "C" int orbx_frame_search_by_bow(orbx_matcher *m, orbx_frame *f, int n_kf
     if (n == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
     const int ne = std::max(nc, 1);
-    size_t need = Arena::pad(4 * (tot_nodes + 1)) * 2 + Arena::pad(sizeof(BowProblem) * (size_t)n_kf) + Arena::pad(4 * (size_t)n_kf * nc) +
-                  Arena::pad(4 * (size_t)n_kf) + Arena::pad(4 * (size_t)n_kf * (ORBX_HISTO_LENGTH + 2)) + Arena::pad(4 * (size_t)n_kf * ne) + 4096;
+    size_t n_ent = (size_t)n_kf * ne;
+    if (fisheye) {   // mode 3: 2 max(na, nb) entries per key frame (BowProblem::entries)
+        n_ent = 0;
+        for (int k = 0; k < n_kf; k++) n_ent += 2 * (size_t)std::max(std::max(kfs[k].n, nrows), 1);
+    }
+    size_t need = Arena::pad(4 * (tot_nodes + 1)) * 2 + Arena::pad(sizeof(BowProblem) * (size_t)n_kf) + Arena::pad(4 * (size_t)n_kf * nrows) +
+                  Arena::pad(4 * (size_t)n_kf) + Arena::pad(4 * (size_t)n_kf * (ORBX_HISTO_LENGTH + 2)) + Arena::pad(4 * n_ent) + 4096 +
+                  (fisheye ? Arena::pad(4 * (size_t)n_kf * nc) : 0);
     for (int k = 0; k < n_kf; k++) {
         const size_t nk = (size_t)kfs[k].n, nn = (size_t)kfs[k].fv.n_nodes, ni = (size_t)kfs[k].fv.node_ptr[nn];
         need += Arena::pad(32 * nk) + Arena::pad(4 * nk) + Arena::pad(nk) + Arena::pad(4 * (nn + 1)) + Arena::pad(4 * (ni + 1));
@@ -2549,26 +2648,29 @@ extern "C" int orbx_frame_search_by_bow(orbx_matcher *m, orbx_frame *f, int n_kf
     BowProblem *dP = A.take<BowProblem>(n_kf);
     // device-only: the pairing, the rows (filled with -1) and match counts side by side (one download run), histograms + counters (zeroed), entries
     int32_t *dpair = A.take<int32_t>(tot_nodes + 1);
-    int32_t *dmatch = A.take<int32_t>((size_t)n_kf * nc), *dnm = A.take<int32_t>(n_kf);
+    int32_t *dmatch = A.take<int32_t>((size_t)n_kf * nrows);
+    int32_t *dout = fisheye ? A.take<int32_t>((size_t)n_kf * nc) : dmatch;   // fisheye: the rows renumbered into features, next to the counts
+    int32_t *dnm = A.take<int32_t>(n_kf);
     int32_t *dhist = A.take<int32_t>((size_t)n_kf * (ORBX_HISTO_LENGTH + 2));
-    int32_t *dent = A.take<int32_t>((size_t)n_kf * ne);
+    int32_t *dent = A.take<int32_t>(n_ent);
     {
-        size_t o = 0;
+        size_t o = 0, oe = 0;
         for (int k = 0; k < n_kf; k++) {
             BowProblem &P = probs[k];
-            P.mode = 0;
+            P.mode = fisheye ? 3 : 0; P.nb_left = fisheye ? f->roff : 0;
             P.fb.node_id = f->fv_node; P.fb.node_ptr = f->fv_ptr; P.fb.index = f->fv_index; P.fb.n_nodes = 0;   // (the frame's node count stays on the device)
-            P.desc_b = f->desc; P.angle_b = f->angle; P.nb = nc;
+            P.desc_b = f->desc; P.angle_b = f->angle; P.nb = nrows;
             P.nnratio = nnratio; P.check_orientation = check_orientation ? 1 : 0;
-            P.match = dmatch + (size_t)k * nc; P.nmatches = dnm + k;
+            P.match = dmatch + (size_t)k * nrows; P.nmatches = dnm + k;
             P.hist = dhist + (size_t)k * (ORBX_HISTO_LENGTH + 2); P.counters = P.hist + ORBX_HISTO_LENGTH;
-            P.entries = dent + (size_t)k * ne;
+            P.entries = dent + oe;
+            oe += fisheye ? 2 * (size_t)std::max(std::max(kfs[k].n, nrows), 1) : (size_t)ne;
             P.pair_b = dpair + o;
             o += (size_t)P.fa.n_nodes;
         }
     }
     H2D(dP, probs.data(), sizeof(BowProblem) * (size_t)n_kf);
-    ORBX_HIP(m->fill(dmatch, 0xff, 4 * (size_t)n_kf * nc));
+    ORBX_HIP(m->fill(dmatch, 0xff, 4 * (size_t)n_kf * nrows));
     ORBX_HIP(m->fill(dhist, 0, 4 * (size_t)n_kf * (ORBX_HISTO_LENGTH + 2)));
     if (tot_nodes > 0) {
         hipLaunchKernelGGL(k_bow_pair_nodes, dim3((unsigned)((tot_nodes + 255) / 256)), dim3(256), 0, m->exec(), dkn, (int)tot_nodes, f->fv_node,
@@ -2576,22 +2678,43 @@ extern "C" int orbx_frame_search_by_bow(orbx_matcher *m, orbx_frame *f, int n_kf
         hipLaunchKernelGGL(k_replay_bow_batch, dim3((unsigned)((max_nodes + 3) / 4), (unsigned)n_kf), dim3(256), 0, m->exec(), (const BowProblem *)dP);
     }
     hipLaunchKernelGGL(k_replay_bow_finish_batch, dim3((unsigned)n_kf), dim3(64), 0, m->exec(), (const BowProblem *)dP);
+    if (fisheye)
+        hipLaunchKernelGGL(k_frame_rows_to_features, dim3((unsigned)((nc + 255) / 256), (unsigned)n_kf), dim3(256), 0, m->exec(), dmatch, nrows, dout, nc,
+                           f->count, n >= 0 ? f->n_left : -1, n >= 0 ? f->n_right : -1, f->cap, f->roff);
     ORBX_HIP(hipGetLastError());
     if (n >= 0) {
-        for (int k = 0; k < n_kf; k++) D2H(match + (size_t)k * match_stride, dmatch + (size_t)k * nc, 4 * (size_t)n);
+        for (int k = 0; k < n_kf; k++) D2H(match + (size_t)k * match_stride, dout + (size_t)k * nc, 4 * (size_t)n);
     } else {   // N comes back with the results
         f->h_match.resize((size_t)n_kf * nc);
-        D2H(f->h_match.data(), dmatch, 4 * (size_t)n_kf * nc);
-        D2H(&f->n, f->count, 4);
+        D2H(f->h_match.data(), dout, 4 * (size_t)n_kf * nc);
+        if (fisheye) D2H(f->h_count, f->count, 8);
+        else D2H(&f->n, f->count, 4);
     }
     D2H(nmatches, dnm, 4 * (size_t)n_kf);
     SYNC_AND_DELIVER();
     if (n < 0) {
+        if (fisheye) {
+            f->n_left = std::min(std::max(f->h_count[0], 0), f->roff);
+            f->n_right = std::min(std::max(f->h_count[1], 0), f->cap - f->roff);
+            f->n = f->n_left + f->n_right;
+        }
         f->n = std::min(std::max(f->n, 0), f->cap);
         f->n_known = true;
         for (int k = 0; k < n_kf; k++) memcpy(match + (size_t)k * match_stride, f->h_match.data() + (size_t)k * nc, 4 * (size_t)f->n);
     }
     return ORBX_OK;
+}
+
+extern "C" int orbx_frame_search_by_bow(orbx_matcher *m, orbx_frame *f, int n_kf, const orbx_bow_keyframe *kfs, float nnratio, int check_orientation,
+                                        int32_t *match, int match_stride, int32_t *nmatches) {
+    return frame_search_by_bow_impl(m, f, n_kf, kfs, nnratio, check_orientation, match, match_stride, nmatches, false);
+}
+
+// SearchByBoW(KeyFrame*, Frame&) of a resident fisheye-stereo frame (F.Nleft != -1, ORBmatcher.cc:283-392) against n_kf key frames: row k equals
+// orbx_search_by_bow_frame_fisheye for key frame k.  The same cost shape as orbx_frame_search_by_bow (one more launch: the renumbering).
+extern "C" int orbx_frame_search_by_bow_fisheye(orbx_matcher *m, orbx_frame *f, int n_kf, const orbx_bow_keyframe *kfs, float nnratio,
+                                                int check_orientation, int32_t *match, int match_stride, int32_t *nmatches) {
+    return frame_search_by_bow_impl(m, f, n_kf, kfs, nnratio, check_orientation, match, match_stride, nmatches, true);
 }
 
 // MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403) for a batch of map points

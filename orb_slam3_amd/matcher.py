@@ -139,6 +139,19 @@ class DeviceFrame:
         n = self.count()   # (known after the call: no further synchronisation)
         return w[:n], nd[:n]
 
+    def compute_bow_fisheye(self, voc: "ORBVocabulary", levelsup: int = 4, download: bool = True):
+        """compute_bow for a fisheye-stereo handle (orbx_frame_compute_bow_fisheye): all N = N_left + N_right rows are transformed; the
+        FeatureVector stays in the handle for ORBmatcher.SearchByBoWDeviceFisheye.  download=True returns (word_id[N], node_id[N]) in the rig's
+        numbering (features >= N_left are the right camera's); download=False returns None and does not wait."""
+        if not download:
+            check(self._L.orbx_frame_compute_bow_fisheye(self.matcher._h, self._h, voc._h, int(levelsup), None, None), "orbx_frame_compute_bow_fisheye")
+            return None
+        w = np.zeros(self.cap, np.int32)
+        nd = np.zeros(self.cap, np.int32)
+        check(self._L.orbx_frame_compute_bow_fisheye(self.matcher._h, self._h, voc._h, int(levelsup), ptr(w), ptr(nd)), "orbx_frame_compute_bow_fisheye")
+        n = self.count()   # (known after the call: no further synchronisation)
+        return w[:n], nd[:n]
+
 
 def _f32(a):
     return None if a is None else np.ascontiguousarray(a, np.float32)
@@ -494,14 +507,17 @@ class ORBmatcher:
 
     # ---- general window form: M3 = SearchByProjection(Frame&, KeyFrame*, ...) (ORBmatcher.cc:1889-2010) and
     #      M4 = SearchByProjection(KeyFrame*, Sim3f&, ...) (ORBmatcher.cc:427-646) ----
-    def SearchByProjectionWindow(self, F: FrameView, q: dict, max_dist: float, check_orientation: bool, occupied=None, raw=False):
-        """q: x, y, r, min_level, max_level, angle, desc[, has_obs].  F: FrameView or DeviceFrame.  raw: see SearchByProjectionFrame."""
-        nq = len(q["x"])
+    @staticmethod
+    def _window_args(q: dict, max_dist: float, check_orientation: bool, occ):
         a = dict(x=_f32(q["x"]), y=_f32(q["y"]), r=_f32(q["r"]), lo=_i32(q["min_level"]), hi=_i32(q["max_level"]),
                  ang=_f32(q.get("angle")), d=_u8(q["desc"]), ho=_u8(q.get("has_obs")))
+        return a, (ptr(occ), len(q["x"]), ptr(a["x"]), ptr(a["y"]), ptr(a["r"]), ptr(a["lo"]), ptr(a["hi"]), ptr(a["ang"]), ptr(a["d"]),
+                   ptr(a["ho"]), max_dist, int(check_orientation))
+
+    def SearchByProjectionWindow(self, F: FrameView, q: dict, max_dist: float, check_orientation: bool, occupied=None, raw=False):
+        """q: x, y, r, min_level, max_level, angle, desc[, has_obs].  F: FrameView or DeviceFrame.  raw: see SearchByProjectionFrame."""
         occ = _u8(occupied)
-        args = (ptr(occ), nq, ptr(a["x"]), ptr(a["y"]), ptr(a["r"]), ptr(a["lo"]), ptr(a["hi"]), ptr(a["ang"]), ptr(a["d"]), ptr(a["ho"]),
-                max_dist, int(check_orientation))
+        _keep, args = self._window_args(q, max_dist, check_orientation, occ)
         if isinstance(F, DeviceFrame):
             match = np.full(self._frame_rows(F, occ), -1, np.int32)
             n = check(self._L.orbx_frame_search_by_projection_window(self._h, F._h, *args, ptr(match)), "orbx_frame_search_by_projection_window")
@@ -510,6 +526,18 @@ class ORBmatcher:
             fd = F.c_struct()
             match = np.full(fd.n, -1, np.int32)
             n = check(self._L.orbx_search_by_projection_window(self._h, C.byref(fd), *args, ptr(match)), "orbx_search_by_projection_window")
+        return n, (match if raw else np.maximum(match, -1))
+
+    def SearchByProjectionWindowFisheye(self, F: DeviceFrame, q: dict, max_dist: float, check_orientation: bool, occupied=None, raw=False):
+        """Relocalization's window search on a fisheye-stereo handle (orbx_frame_search_by_projection_window_fisheye): only the left camera is
+        searched (GetFeaturesInArea's default bRight = false).  occupied: N entries or None.  Returns (nmatches, match[N]); the right camera's
+        entries are -1.  raw: see SearchByProjectionFrame."""
+        occ = _u8(occupied)
+        _keep, args = self._window_args(q, max_dist, check_orientation, occ)
+        match = np.full(self._frame_rows(F, occ), -1, np.int32)
+        n = check(self._L.orbx_frame_search_by_projection_window_fisheye(self._h, F._h, *args, ptr(match)),
+                  "orbx_frame_search_by_projection_window_fisheye")
+        match = match[:F.count()]
         return n, (match if raw else np.maximum(match, -1))
 
     # ---- SearchForInitialization (ORBmatcher.cc:648-763) ----
@@ -539,6 +567,14 @@ class ORBmatcher:
         """SearchByBoW(KeyFrame*, Frame&) of the resident frame against every key frame of `kfs` in one call (orbx_frame_search_by_bow; the frame
         needs DeviceFrame.compute_bow first).  kfs: sequence of (desc, angle, valid, FeatureVector) -- valid may be None.
         Returns (nmatches[n_kf], match[n_kf, N]): row k = SearchByBoWFrame for key frame k."""
+        return self._search_by_bow_device(F, kfs, "orbx_frame_search_by_bow")
+
+    def SearchByBoWDeviceFisheye(self, F: DeviceFrame, kfs):
+        """SearchByBoWDevice for a fisheye-stereo handle (orbx_frame_search_by_bow_fisheye; the frame needs DeviceFrame.compute_bow_fisheye first).
+        Returns (nmatches[n_kf], match[n_kf, N]): row k = SearchByBoWFrameFisheye for key frame k (right-camera matches at N_left + j)."""
+        return self._search_by_bow_device(F, kfs, "orbx_frame_search_by_bow_fisheye")
+
+    def _search_by_bow_device(self, F: DeviceFrame, kfs, fn: str):
         n_kf = len(kfs)
         keep, arr = [], (BowKeyFrame * max(n_kf, 1))()
         for k, (d, a, v, fv) in enumerate(kfs):
@@ -548,8 +584,7 @@ class ORBmatcher:
         stride = F.cap
         match = np.full((max(n_kf, 1), stride), -1, np.int32)
         nm = np.zeros(max(n_kf, 1), np.int32)
-        check(self._L.orbx_frame_search_by_bow(self._h, F._h, n_kf, arr, self.mfNNratio, int(self.mbCheckOrientation), ptr(match), stride, ptr(nm)),
-              "orbx_frame_search_by_bow")
+        check(getattr(self._L, fn)(self._h, F._h, n_kf, arr, self.mfNNratio, int(self.mbCheckOrientation), ptr(match), stride, ptr(nm)), fn)
         del keep
         return nm[:n_kf], match[:n_kf, :F.count()]
 
