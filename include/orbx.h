@@ -645,6 +645,70 @@ int orbx_fuse_search(orbx_matcher *m, const orbx_frame_desc *kf, const float *in
                      const float *q_v, const float *q_ur, const float *q_r, const int32_t *q_level, const uint8_t *q_desc,
                      int strict_fp, int32_t *best_idx, int32_t *best_dist);
 
+/* ---- device-resident key frames ----
+ * KeyFrame::KeyFrame(Frame &F, Map*, KeyFrameDatabase*) (KeyFrame.cc:36-82) copies the frame's mvKeysUn, mDescriptors, mvuRight, mvScaleFactors,
+ * mvInvLevelSigma2, the image bounds and mGrid; none of them changes afterwards, and LocalMapping / LoopClosing search the same 10 - 30 covisible key
+ * frames again for every new key frame.  An orbx_keyframe is that copy on the device: ONE allocation sized by N (about 66 bytes per feature + 6 KB of
+ * grid; sized by the frame handle's capacity only when N of a batch-loaded frame is still on the device), immutable once made.  Monocular / rectified
+ * key frames (NLeft == -1, Pinhole) only.
+ *   orbx_keyframe_from_frame: a device-to-device copy of a loaded monocular / rectified orbx_frame owned by `m` -- rows, count, scale factors and the grid
+ *     AS BUILT (no rebuild) -- plus inv_level_sigma2 [the frame's nlevels] (mvInvLevelSigma2; NULL = none: only the gate-less searches accept the key
+ *     frame).  Enqueued on m's stream, no host synchronisation, also while N is still on the device; the frame may be reloaded as soon as the call
+ *     returns (stream order protects the copy).  A fisheye handle, a handle that was never loaded or one of another matcher: ORBX_E_BAD_ARG before anything
+ *     is enqueued.
+ *   orbx_keyframe_create_host: the same object from host arrays (a loaded atlas, tests): one upload, the grid built as orbx_fuse_search builds it, so the
+ *     candidate order and every tie are that entry point's.  desc->n <= 65535 (ORBX_E_TOO_LARGE otherwise).  Returns without waiting for the upload.
+ *   orbx_keyframe_count: N (one download behind the copy if the key frame was made while N was still on the device; cached).
+ * SHARING.  A key frame belongs to no matcher: it records an event when its copy / upload is enqueued, and ANY matcher context of the same device may
+ * search it -- the context's stream waits for that event until a call that did so has returned.  (A context of another device: ORBX_E_BAD_ARG.)  The
+ * key frame is read-only afterwards, so contexts on different threads may search the same key frames at the same time without a lock.
+ * orbx_keyframe_destroy waits for the copy / upload, then frees the allocation and the event; call it only when no call that was handed the key frame
+ * is running (both searches below synchronise before they return, so "running" means: has not returned yet).  A key frame may outlive the matcher and the
+ * frame handle it was made from. */
+typedef struct orbx_keyframe orbx_keyframe;
+int orbx_keyframe_from_frame(orbx_matcher *m, orbx_frame *frame, const float *inv_level_sigma2, orbx_keyframe **out);
+int orbx_keyframe_create_host(orbx_matcher *m, const orbx_frame_desc *desc, const float *inv_level_sigma2, orbx_keyframe **out);
+int orbx_keyframe_count(orbx_keyframe *kf, int *n);
+void orbx_keyframe_destroy(orbx_keyframe *kf);
+
+/* The most key frames one orbx_keyframe_fuse_search / orbx_keyframe_fuse_map_points call takes (ORBX_E_TOO_LARGE beyond). */
+#define ORBX_MAX_FUSE_KEYFRAMES 256
+/* One query set of orbx_keyframe_fuse_search: the q_* arguments of orbx_fuse_search (ur may be NULL; everything may be NULL when n == 0). */
+typedef struct orbx_fuse_queries {
+    int32_t n;
+    const float *u, *v, *ur, *r;
+    const int32_t *level;
+    const uint8_t *desc;
+} orbx_fuse_queries;
+/* orbx_fuse_search (the candidate loops of ORBmatcher::Fuse, ORBmatcher.cc:1246-1306 and :1405-1433; SearchBySim3's two searches, :1457-1674) for n_kf
+ * resident key frames in one call, key frame k with its own query set queries[k].  use_chi2 != 0: the reprojection gate with the key frame's
+ * mvInvLevelSigma2 (first overload; ORBX_E_BAD_ARG if a key frame has none); 0: the gate-less form (Fuse(pKF, Scw, ...), SearchBySim3).  The gate-less form
+ * never reads the key frame's mvuRight, as the reference's (:1405-1433) and the adapter's call of orbx_fuse_search for it (a frame description without
+ * u_right) do not.
+ * best_idx[k] / best_dist[k] (queries[k].n entries each; may be NULL when that is 0) equal orbx_fuse_search on key frame k's host arrays bit for bit.
+ * Key frames of one call may have different image bounds.  One upload run, one launch, one download run, one synchronisation whatever n_kf is;
+ * n_kf = 0 and empty query sets are fine.  Argument errors (a NULL row included) are reported before anything is enqueued. */
+int orbx_keyframe_fuse_search(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fuse_queries *queries, int use_chi2, int strict_fp,
+                              int32_t *const *best_idx, int32_t *const *best_dist);
+/* The Fuse loop of LocalMapping::SearchInNeighbors (LocalMapping.cc: one ORBmatcher::Fuse(pKFi, vpMapPointMatches) per target key frame) in one call,
+ * projection included: ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th, bRight = false) (ORBmatcher.cc:1148-1337) up to and including the
+ * candidate loop, for n_kf target key frames and n_mp map points given once.  cams[k] / poses[k]: the key frame's Pinhole intrinsics and mbf,
+ * GetPose() (Rcw row-major, tcw) and GetCameraCenter(); map points flat as orbx_frame_search_local_points takes them (world position and normal, 3 floats
+ * each; mfMinDistance / mfMaxDistance; GetDescriptor(), 32 bytes); skip [n_kf][n_mp] (may be NULL) = !pMP || isBad() || IsInKeyFrame(pKF_k) (:1193-1201).
+ * Per pair, in the reference's order and rounding (:1186-1244): p3Dc.z < 0 rejects; Pinhole::project and KeyFrame::IsInImage -- x >= mnMinX && x < mnMaxX
+ * && y >= mnMinY && y < mnMaxY, strict on the max side, unlike Frame::isInFrustum; ur = u - bf / z; dist3D outside [0.8 mfMinDistance, 1.2 mfMaxDistance]
+ * rejects; PO.dot(Pn) < 0.5 * dist3D rejects (compared in double, no division); PredictScale(dist3D, pKF) (MapPoint.cc:531-546) with the key frame's
+ * levels and log_scale_factor; radius = th * mvScaleFactors[level]; candidates with octave in [level - 1, level] and chi2 <= 5.99 / 7.8 as
+ * orbx_fuse_search (every key frame needs inv_level_sigma2: ORBX_E_BAD_ARG otherwise).
+ * Outputs [n_kf][n_mp]: best_idx / best_dist (-1 / 256 when the pair was skipped, failed a gate or found no candidate), projected (may be NULL; 1 = the
+ * pair passed every gate above).  The caller accepts best_dist <= ORBX_TH_LOW and runs the reference's tail (:1308-1330) per key frame, re-checking
+ * isBad() / IsInKeyFrame on the live graph: the searches of the loop are independent, an earlier Fuse changes only those two for a later one.
+ * The map points are uploaded once, the query records never leave the device; the transfers and the launch chain do not grow with n_kf. */
+int orbx_keyframe_fuse_map_points(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams, const orbx_frame_pose *poses, float th,
+                                  float log_scale_factor, int strict_fp, int n_mp, const float *pos, const float *normal, const float *min_dist,
+                                  const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
+                                  uint8_t *projected);
+
 /* MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403), batched over map points: set s = the descriptors of the
  * observations of map point s, descriptors[set_ptr[s] .. set_ptr[s+1]) (gathered by the adapter from
  * pKF->mDescriptors.row(leftIndex/rightIndex) in std::map order).  best_idx[s] = index inside the set of the descriptor

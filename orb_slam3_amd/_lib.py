@@ -118,6 +118,15 @@ class BowKeyFrame(C.Structure):
 
 MAX_BOW_KEYFRAMES = 1024   # ORBX_MAX_BOW_KEYFRAMES
 
+
+class FuseQueries(C.Structure):
+    """orbx_fuse_queries: one query set of orbx_keyframe_fuse_search (the q_* arguments of orbx_fuse_search)."""
+    _fields_ = [("n", C.c_int32), ("u", C.c_void_p), ("v", C.c_void_p), ("ur", C.c_void_p), ("r", C.c_void_p), ("level", C.c_void_p),
+                ("desc", C.c_void_p)]
+
+
+MAX_FUSE_KEYFRAMES = 256   # ORBX_MAX_FUSE_KEYFRAMES
+
 PAIR_PREDICATE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
 _lib = None
@@ -145,6 +154,8 @@ SYMBOLS = [
     "orbx_frame_load_host_fisheye", "orbx_frame_load_stereo_fisheye_batch", "orbx_frame_counts", "orbx_frame_search_by_projection_mappoints_fisheye",
     "orbx_frame_search_by_projection_frame_fisheye", "orbx_frame_search_local_points_fisheye",
     "orbx_frame_compute_bow_fisheye", "orbx_frame_search_by_bow_fisheye", "orbx_frame_search_by_projection_window_fisheye",
+    "orbx_keyframe_from_frame", "orbx_keyframe_create_host", "orbx_keyframe_count", "orbx_keyframe_destroy", "orbx_keyframe_fuse_search",
+    "orbx_keyframe_fuse_map_points",
 ]
 
 
@@ -258,6 +269,14 @@ def lib() -> C.CDLL:
     L.orbx_frame_load_host_fisheye.argtypes = [vp, C.POINTER(FrameDesc), vp, i32, vp, vp]
     L.orbx_frame_load_stereo_fisheye_batch.argtypes = [vp, vp, vp, i32, vp, vp, i32]
     L.orbx_frame_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.orbx_keyframe_from_frame.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    L.orbx_keyframe_create_host.argtypes = [vp, C.POINTER(FrameDesc), vp, C.POINTER(vp)]
+    L.orbx_keyframe_count.argtypes = [vp, C.POINTER(i32)]
+    L.orbx_keyframe_destroy.argtypes = [vp]
+    L.orbx_keyframe_destroy.restype = None
+    L.orbx_keyframe_fuse_search.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(FuseQueries), i32, i32, C.POINTER(vp), C.POINTER(vp)]
+    L.orbx_keyframe_fuse_map_points.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(Camera), C.POINTER(FramePose), f32, f32, i32, i32, vp, vp, vp, vp, vp,
+                                                vp, vp, vp, vp]
     L.orbx_frame_search_by_projection_mappoints_fisheye.argtypes = [vp, vp, vp, i32] + [vp] * 12 + [f32, f32, vp]
     L.orbx_frame_search_by_projection_frame_fisheye.argtypes = [vp, vp, vp, i32] + [vp] * 8 + [f32, i32, i32, vp]
     L.orbx_frame_search_local_points_fisheye.argtypes = [vp, vp, vp, vp, f32, f32, i32] + [vp] * 8 + [f32, f32, i32, f32, vp, vp]

@@ -101,6 +101,30 @@ private:
     int cap_ = 0;
 };
 
+// An immutable key frame resident on the device (orbx_keyframe): what KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-82) copies of the frame.  It belongs
+// to no matcher -- every ORBmatcher of the same device may search it, from any thread (ORBmatcher::FuseSearchKeyFrames / FuseMapPoints); destroy it
+// only when no call that was handed it is running.
+class DeviceKeyFrame {
+public:
+    // a device-to-device copy of a loaded monocular / rectified DeviceFrame of `matcher` (asynchronous; the frame may be reloaded right away)
+    inline DeviceKeyFrame(ORBmatcher &matcher, DeviceFrame &frame, const float *mvInvLevelSigma2);
+    // the same object from host arrays (a loaded atlas): one upload
+    inline DeviceKeyFrame(ORBmatcher &matcher, const FrameView &KF, const float *mvInvLevelSigma2);
+    ~DeviceKeyFrame() { orbx_keyframe_destroy(kf_); }
+    DeviceKeyFrame(const DeviceKeyFrame &) = delete;
+    DeviceKeyFrame &operator=(const DeviceKeyFrame &) = delete;
+    int count() {
+        int n = 0;
+        const int st = orbx_keyframe_count(kf_, &n);
+        if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_count: ") + orbx_status_string(st));
+        return n;
+    }
+    orbx_keyframe *handle() const { return kf_; }
+
+private:
+    orbx_keyframe *kf_ = nullptr;
+};
+
 class ORBmatcher {
 public:
     static const int TH_LOW = ORBX_TH_LOW;
@@ -428,6 +452,56 @@ public:
         if (r < 0) throw std::runtime_error(std::string("orbx_fuse_search: ") + orbx_status_string(r));
     }
 
+    // FuseSearch for K resident key frames in ONE call (orbx_keyframe_fuse_search): key frame k with its own query set q[k]; useChi2 = the first
+    // overload's reprojection gate with the key frames' mvInvLevelSigma2, false = the gate-less form (Fuse with a Sim3, SearchBySim3).
+    // bestIdx[k] / bestDist[k] equal FuseSearch on key frame k's host arrays.
+    void FuseSearchKeyFrames(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<FuseQueries> &q, bool useChi2,
+                             std::vector<std::vector<int32_t>> &bestIdx, std::vector<std::vector<int32_t>> &bestDist, bool strictFloat = false) {
+        const size_t K = vpKFs.size();
+        if (q.size() != K) throw std::invalid_argument("FuseSearchKeyFrames: one query set per key frame");
+        std::vector<orbx_keyframe *> h(K);
+        std::vector<orbx_fuse_queries> c(K);
+        std::vector<int32_t *> pi(K), pd(K);
+        bestIdx.assign(K, {}); bestDist.assign(K, {});
+        for (size_t k = 0; k < K; k++) {
+            const int nq = (int)q[k].u.size();
+            h[k] = vpKFs[k]->handle();
+            c[k] = orbx_fuse_queries{nq, q[k].u.data(), q[k].v.data(), q[k].ur.empty() ? nullptr : q[k].ur.data(), q[k].radius.data(),
+                                     q[k].nPredictedLevel.data(), q[k].descriptors.data()};
+            bestIdx[k].assign(nq, -1); bestDist[k].assign(nq, 256);
+            pi[k] = bestIdx[k].data(); pd[k] = bestDist[k].data();
+        }
+        const int r = orbx_keyframe_fuse_search(m_, (int)K, h.data(), c.data(), useChi2 ? 1 : 0, strictFloat ? 1 : 0, pi.data(), pd.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_fuse_search: ") + orbx_status_string(r));
+    }
+
+    // The Fuse loop of LocalMapping::SearchInNeighbors in ONE call, projection included (orbx_keyframe_fuse_map_points): Fuse(pKF, vpMapPoints, th)
+    // (ORBmatcher.cc:1148-1337) up to and including the candidate loop for every target key frame.  cams[k] / poses[k] = pKF_k's intrinsics + mbf and
+    // GetPose() / GetCameraCenter(); the map points flat and given once (mfMinDistance / mfMaxDistance UNSCALED: the device applies 0.8f / 1.2f);
+    // skip [K][n] (empty = none) = !pMP || isBad() || IsInKeyFrame(pKF_k).  bestIdx / bestDist / projected: [K][n], row-major.
+    struct FuseMapPointSet {
+        std::vector<float> pos, normal;              // 3 floats each: GetWorldPos(), GetNormal()
+        std::vector<float> minDistance, maxDistance; // mfMinDistance, mfMaxDistance
+        std::vector<uint8_t> descriptors;            // n x 32
+        int size() const { return (int)minDistance.size(); }
+    };
+    void FuseMapPoints(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<orbx_camera> &cams, const std::vector<orbx_frame_pose> &poses,
+                       const FuseMapPointSet &mps, const std::vector<uint8_t> &skip, float th, float logScaleFactor, std::vector<int32_t> &bestIdx,
+                       std::vector<int32_t> &bestDist, std::vector<uint8_t> *projected = nullptr, bool strictFloat = false) {
+        const size_t K = vpKFs.size(), n = (size_t)mps.size();
+        if (cams.size() != K || poses.size() != K || (!skip.empty() && skip.size() != K * n))
+            throw std::invalid_argument("FuseMapPoints: one camera and pose per key frame, K x n skip flags");
+        std::vector<orbx_keyframe *> h(K);
+        for (size_t k = 0; k < K; k++) h[k] = vpKFs[k]->handle();
+        bestIdx.assign(K * n, -1); bestDist.assign(K * n, 256);
+        if (projected) projected->assign(K * n, 0);
+        const int r = orbx_keyframe_fuse_map_points(m_, (int)K, h.data(), cams.data(), poses.data(), th, logScaleFactor, strictFloat ? 1 : 0, (int)n,
+                                                    mps.pos.data(), mps.normal.data(), mps.minDistance.data(), mps.maxDistance.data(),
+                                                    mps.descriptors.data(), skip.empty() ? nullptr : skip.data(), bestIdx.data(), bestDist.data(),
+                                                    projected ? projected->data() : nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_fuse_map_points: ") + orbx_status_string(r));
+    }
+
     // SearchBySim3(pKF1, pKF2, vpMatches12, S12, th) (ORBmatcher.cc:1457-1674): the two projection searches are gate-less fuse searches
     // (KeyFrame::GetFeaturesInArea, octave gate [l-1,l], first minimum wins, accept bestDist <= TH_HIGH :1569/:1656), followed by the
     // mutual-agreement pass (:1662-1675).  q1 = KF1's map points transformed by S21 and projected into KF2 (one entry per KF1 feature,
@@ -564,6 +638,16 @@ protected:
 // levels above the leaf; the caller folds them into BowVector (addWeight) and FeatureVector (addFeature) in feature order.
 inline DeviceFrame::DeviceFrame(ORBmatcher &matcher, int cap) : cap_(cap) {
     check(orbx_frame_create(matcher.handle(), cap, &f_), "orbx_frame_create");
+}
+
+inline DeviceKeyFrame::DeviceKeyFrame(ORBmatcher &matcher, DeviceFrame &frame, const float *mvInvLevelSigma2) {
+    const int st = orbx_keyframe_from_frame(matcher.handle(), frame.handle(), mvInvLevelSigma2, &kf_);
+    if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_from_frame: ") + orbx_status_string(st) + " " + orbx_last_error());
+}
+inline DeviceKeyFrame::DeviceKeyFrame(ORBmatcher &matcher, const FrameView &KF, const float *mvInvLevelSigma2) {
+    orbx_frame_desc fd = KF.c();
+    const int st = orbx_keyframe_create_host(matcher.handle(), &fd, mvInvLevelSigma2, &kf_);
+    if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_create_host: ") + orbx_status_string(st) + " " + orbx_last_error());
 }
 
 class ORBVocabularyDevice {

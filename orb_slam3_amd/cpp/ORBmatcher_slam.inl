@@ -661,6 +661,76 @@ public:
         return nFused;
     }
 
+    // The Fuse loop of LocalMapping::SearchInNeighbors (LocalMapping.cc: `matcher.Fuse(pKFi, vpMapPointMatches)` per target key frame) as ONE device call:
+    // the candidate searches of that loop are independent -- what an earlier Fuse changes for a later one is only pMP->isBad() and
+    // pMP->IsInKeyFrame(pKF), which the tail below re-checks per query on the live graph.  Monocular / rectified key frames (NLeft == -1).
+    // The gates (:1186-1244) run here, once per (key frame, map point), with the reference's own accessors (MapPoint publishes only the SCALED distance
+    // bounds: GetMinDistanceInvariance / GetMaxDistanceInvariance); the survivors of all key frames go to orbx_keyframe_fuse_search together.  A tree
+    // that can read mfMinDistance / mfMaxDistance hands the flat map points to FuseMapPoints instead and drops this loop.
+    // vpDeviceKFs[k] is the resident copy of vpTargetKFs[k] (KeyFrame::mpDevice in an integrated tree).  Returns the fused points per key frame.
+    std::vector<int> Fuse(const std::vector<KeyFrame *> &vpTargetKFs, const std::vector<DeviceKeyFrame *> &vpDeviceKFs,
+                          const std::vector<MapPoint *> &vpMapPoints, const float th = 3.0) {
+        const size_t K = vpTargetKFs.size();
+        if (vpDeviceKFs.size() != K) throw std::invalid_argument("Fuse: one DeviceKeyFrame per target key frame");
+        std::vector<FuseQueries> q(K);
+        std::vector<std::vector<int>> live(K);
+        const int nMPs = (int)vpMapPoints.size();
+        for (size_t k = 0; k < K; k++) {
+            KeyFrame *pKF = vpTargetKFs[k];
+            if (pKF->NLeft != -1) throw std::invalid_argument("Fuse: resident key frames are monocular / rectified");
+            Sophus::SE3f Tcw = pKF->GetPose();
+            Eigen::Vector3f Ow = pKF->GetCameraCenter();
+            const float &bf = pKF->mbf;
+            for (int i = 0; i < nMPs; i++) {
+                MapPoint *pMP = vpMapPoints[i];
+                if (!pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
+                Eigen::Vector3f p3Dw = pMP->GetWorldPos();
+                Eigen::Vector3f p3Dc = Tcw * p3Dw;
+                if (p3Dc(2) < 0.0f) continue;
+                const float invz = 1 / p3Dc(2);
+                const Eigen::Vector2f uv = pKF->mpCamera->project(p3Dc);
+                if (!pKF->IsInImage(uv(0), uv(1))) continue;
+                const float ur = uv(0) - bf * invz;
+                const float maxDistance = pMP->GetMaxDistanceInvariance();
+                const float minDistance = pMP->GetMinDistanceInvariance();
+                Eigen::Vector3f PO = p3Dw - Ow;
+                const float dist3D = PO.norm();
+                if (dist3D < minDistance || dist3D > maxDistance) continue;
+                Eigen::Vector3f Pn = pMP->GetNormal();
+                if (PO.dot(Pn) < 0.5 * dist3D) continue;
+                int nPredictedLevel = pMP->PredictScale(dist3D, pKF);
+                q[k].u.push_back(uv(0)); q[k].v.push_back(uv(1)); q[k].ur.push_back(ur);
+                q[k].radius.push_back(th * pKF->mvScaleFactors[nPredictedLevel]);
+                q[k].nPredictedLevel.push_back(nPredictedLevel);
+                push_desc(q[k].descriptors, pMP->GetDescriptor());
+                live[k].push_back(i);
+            }
+        }
+        std::vector<std::vector<int32_t>> bestIdx, bestDist;
+        FuseSearchKeyFrames(vpDeviceKFs, q, true, bestIdx, bestDist);
+        std::vector<int> nFused(K, 0);
+        for (size_t k = 0; k < K; k++) {   // the reference's order: key frame by key frame, each with its tail on the live graph (:1309-1330)
+            KeyFrame *pKF = vpTargetKFs[k];
+            for (size_t j = 0; j < live[k].size(); j++) {
+                MapPoint *pMP = vpMapPoints[live[k][j]];
+                if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;   // an earlier Replace / AddObservation (this key frame's or an earlier one's) retired the query
+                if (bestIdx[k][j] < 0 || bestDist[k][j] > TH_LOW) continue;
+                MapPoint *pMPinKF = pKF->GetMapPoint(bestIdx[k][j]);
+                if (pMPinKF) {
+                    if (!pMPinKF->isBad()) {
+                        if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
+                        else pMPinKF->Replace(pMP);
+                    }
+                } else {
+                    pMP->AddObservation(pKF, bestIdx[k][j]);
+                    pKF->AddMapPoint(pMP, bestIdx[k][j]);
+                }
+                nFused[k]++;
+            }
+        }
+        return nFused;
+    }
+
     // ORBmatcher.cc:1339-1455 (LoopClosing::SearchAndFuse)
     int Fuse(KeyFrame *pKF, Sophus::Sim3f &Scw, const std::vector<MapPoint *> &vpPoints, float th, std::vector<MapPoint *> &vpReplacePoint) {
         Sophus::SE3f Tcw = Sophus::SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale());

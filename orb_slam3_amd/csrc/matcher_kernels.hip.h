@@ -1240,6 +1240,203 @@ __global__ __launch_bounds__(256) void k_window_best2_t(const WindowProblem *__r
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Resident key frames (orbx_keyframe): ORBmatcher::Fuse(KeyFrame*, vpMapPoints, th) (ORBmatcher.cc:1148-1337) for K target key frames in one call.
+// ---------------------------------------------------------------------------------------------------------
+// One (key frame, query set) of orbx_keyframe_fuse_search / orbx_keyframe_fuse_map_points: the window problem, the key frame's OWN grid parameters
+// (key frames of one call may have different image bounds) and what KeyFrame::IsInImage / PredictScale read of the key frame.  256 bytes.
+struct KfProblem {
+    WindowProblem P;
+    GridParams g;            // mnMinX, mnMinY, mfGridElementWidthInv, mfGridElementHeightInv
+    float maxx, maxy;        // mnMaxX, mnMaxY
+    int nlevels;             // mnScaleLevels
+    int pad_[3];
+};
+static_assert(sizeof(KfProblem) == 256, "KfProblem: one arena unit");
+
+// k_window_best2_t<8>'s scan specialised for Fuse on resident key frames: the grid parameters are those of each problem's OWN key frame (k_window_best2_t
+// takes one GridParams per launch), and as Fuse's queries do not interact only the smallest candidate key of a query is kept -- P.keys holds ONE entry per
+// query (kNoKey = none), no meta word, no extraction rounds.  Candidate enumeration, tests, gates and key (seq_key: the reference's enumeration order breaks
+// ties) are k_window_best2_t's, statement for statement.  grid as k_window_best2_t (ORBX_LAUNCH_WINDOW_BEST2's shape), block 256
+__global__ __launch_bounds__(256) void k_window_best1_kf(const KfProblem *__restrict__ recs, int n_problems) {
+    constexpr int LQ = 8;
+    const int prob = (int)(blockIdx.z * gridDim.x + blockIdx.x);
+    if (prob >= n_problems) return;
+    const WindowProblem P = recs[prob].P;
+    const GridParams g = recs[prob].g;
+    const int sub = threadIdx.x / LQ, sl = threadIdx.x & (LQ - 1);
+    const int qi = blockIdx.y * (256 / LQ) + sub;
+    const int nq = gld(P.nq_ptr);
+    const bool qvalid = qi < nq;
+    QueryWin w;
+    Desc dq;
+    u64 k1 = kNoKey;
+    bool go = false;
+    if (qvalid) go = load_query(P, qi, &w, g, &dq);
+    if (go) {
+        int seq0 = 0;
+        for (int cx = w.cx0; cx <= w.cx1; cx += 8) {
+            int cs[8], ce[8];
+#pragma unroll
+            for (int c = 0; c < 8; c++) {
+                const int ix = min(cx + c, w.cx1);
+                cs[c] = gld(P.gstart + ix * 48 + w.cy0);
+                ce[c] = gld(P.gstart + ix * 48 + w.cy1 + 1);
+            }
+            int pre[9];
+            pre[0] = 0;
+#pragma unroll
+            for (int c = 0; c < 8; c++) pre[c + 1] = pre[c] + ((cx + c <= w.cx1) ? ce[c] - cs[c] : 0);
+            const int tot = pre[8];
+            for (int t = sl; t < tot; t += LQ) {
+                int j = cs[0] + t;  // column of the t-th candidate: the last c with pre[c] <= t
+#pragma unroll
+                for (int c = 1; c < 8; c++) j = (t >= pre[c]) ? cs[c] + (t - pre[c]) : j;
+                const int i = gld(P.gorder + j);
+                const orbx_keypoint kp = gld_kp(P.kps + i);
+                if (w.check_levels) {
+                    if (kp.octave < w.minL) continue;
+                    if (w.maxL >= 0 && kp.octave > w.maxL) continue;
+                }
+                const float dx = kp.x - w.x, dy = kp.y - w.y;
+                if (!(fabsf(dx) < w.r && fabsf(dy) < w.r)) continue;
+                if (P.inv_sigma2) {  // Fuse: chi2 gate on the reprojection error
+                    const float ex = __fsub_rn(w.x, kp.x), ey = __fsub_rn(w.y, kp.y);
+                    if (P.u_right && gld(P.u_right + i) >= 0) {
+                        const float er = __fsub_rn(w.xr, gld(P.u_right + i));
+                        const float e2 = P.chi2_fma ? __fmaf_rn(er, er, __fmaf_rn(ex, ex, __fmul_rn(ey, ey)))
+                                                    : __fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(er, er));
+                        if ((double)__fmul_rn(e2, gld(P.inv_sigma2 + kp.octave)) > 7.8) continue;
+                    } else {
+                        const float e2 = P.chi2_fma ? __fmaf_rn(ex, ex, __fmul_rn(ey, ey)) : __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+                        if ((double)__fmul_rn(e2, gld(P.inv_sigma2 + kp.octave)) > 5.99) continue;
+                    }
+                } else if (P.u_right && gld(P.u_right + i) > 0) {  // ORBmatcher.cc:92-97 / 1751-1757
+                    const float er = fabsf(w.xr - gld(P.u_right + i));
+                    if (er > w.r) continue;
+                }
+                const int d = hamming(dq, gld_desc(P.desc + (size_t)i * 32));
+                const u64 key = seq_key(d, seq0 + t, i);
+                k1 = key < k1 ? key : k1;
+            }
+            seq0 += tot;
+        }
+    }
+    u64 m = k1;   // the minimum inside the LQ-lane group (xor masks LQ/2 .. 1 stay inside the group)
+#pragma unroll
+    for (int s = LQ / 2; s > 0; s >>= 1) {
+        const u64 o = __shfl_xor(m, s);
+        m = o < m ? o : m;
+    }
+    if (qvalid && sl == 0) gst(P.keys + qi, m);
+}
+
+// k_fuse_project: the projection half of ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint*> &vpMapPoints, th) (ORBmatcher.cc:1186-1244) for every
+// (key frame, map point) of LocalMapping::SearchInNeighbors' Fuse loop -- a lane per pair writes the query record of problem k straight into the arrays
+// k_window_best1_kf reads (qvalid switches a rejected pair off; the descriptors are the one shared array).  The gates in the reference's order, every float
+// operation rounded separately and summed in the order k_in_frustum fixes for the same expressions:
+//   p3Dc = Rcw p + tcw; reject p3Dc.z < 0.0f; invz = 1 / z
+//   Pinhole::project; KeyFrame::IsInImage: x >= mnMinX && x < mnMaxX && y >= mnMinY && y < mnMaxY  (strict on the max side)
+//   ur = u - bf invz
+//   dist3D = |p - Ow|; reject outside [0.8f mfMinDistance, 1.2f mfMaxDistance]
+//   reject PO . Pn < 0.5 * dist3D, compared in double and WITHOUT isInFrustum's division
+//   PredictScale(dist3D, pKF); radius = th * mvScaleFactors[level]; levels [level - 1, level]
+// skip [n_kf][n_mp] (may be NULL) = !pMP || isBad() || IsInKeyFrame(pKF_k).  Streaming work: no LDS, no scratch.
+// grid (ceil(n_mp / 256), n_kf), block 256
+__global__ __launch_bounds__(256) void k_fuse_project(const KfProblem *__restrict__ recs, const orbx_camera *__restrict__ cams,
+                                                      const orbx_frame_pose *__restrict__ poses, float th, float log_scale_factor, int n_mp,
+                                                      const float *__restrict__ pos, const float *__restrict__ normal, const float *__restrict__ min_dist,
+                                                      const float *__restrict__ max_dist, const uint8_t *__restrict__ skip, float *__restrict__ qx,
+                                                      float *__restrict__ qy, float *__restrict__ qxr, float *__restrict__ qr, int32_t *__restrict__ qmin,
+                                                      int32_t *__restrict__ qmax, uint8_t *__restrict__ qvalid) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_mp) return;
+    const int k = blockIdx.y;
+    const size_t o = (size_t)k * n_mp + i;
+    const orbx_frame_pose T = poses[k];
+    const float fx = cams[k].fx, fy = cams[k].fy, cx = cams[k].cx, cy = cams[k].cy, bf = cams[k].bf;
+    const float minx = recs[k].g.minx, miny = recs[k].g.miny, maxx = recs[k].maxx, maxy = recs[k].maxy;
+    const int nlevels = recs[k].nlevels;
+    const float *scale = recs[k].P.scale;
+    // every input of the pair requested at once (the gates read them conditionally: each would be a dependent round trip)
+    const uint8_t sk = skip ? skip[o] : (uint8_t)0;
+    const float P0 = pos[3 * i], P1 = pos[3 * i + 1], P2 = pos[3 * i + 2];
+    const float mn_in = min_dist[i], mx = max_dist[i], N0 = normal[3 * i], N1 = normal[3 * i + 1], N2 = normal[3 * i + 2];
+    float Pc[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+        Pc[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T.Rcw[3 * r], P0), __fmul_rn(T.Rcw[3 * r + 1], P1)), __fmul_rn(T.Rcw[3 * r + 2], P2)), T.tcw[r]);
+    bool ok = !sk && !(Pc[2] < 0.0f);
+    const float invz = __fdiv_rn(1.0f, Pc[2]);
+    const float u = __fadd_rn(__fdiv_rn(__fmul_rn(fx, Pc[0]), Pc[2]), cx), v = __fadd_rn(__fdiv_rn(__fmul_rn(fy, Pc[1]), Pc[2]), cy);
+    ok = ok && (u >= minx && u < maxx && v >= miny && v < maxy);
+    const float ur = __fsub_rn(u, __fmul_rn(bf, invz));
+    const float PO0 = __fsub_rn(P0, T.Ow[0]), PO1 = __fsub_rn(P1, T.Ow[1]), PO2 = __fsub_rn(P2, T.Ow[2]);
+    const float dist = sqrtf(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, PO0)), __fmul_rn(PO1, PO1)), __fmul_rn(PO2, PO2)));
+    const float maxDistance = __fmul_rn(1.2f, mx), minDistance = __fmul_rn(0.8f, mn_in);
+    ok = ok && !(dist < minDistance || dist > maxDistance);
+    const float dot = __fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, N0)), __fmul_rn(PO1, N1)), __fmul_rn(PO2, N2));
+    ok = ok && !((double)dot < 0.5 * (double)dist);
+    int lvl = 0;
+    float radius = 0.f;
+    if (ok) {   // MapPoint::PredictScale(dist3D, pKF) (MapPoint.cc:531-546), as k_in_frustum evaluates the same expressions
+        const float ratio = __fdiv_rn(mx, dist);
+        lvl = (int)ceilf(__fdiv_rn((float)log((double)ratio), log_scale_factor));
+        if (lvl < 0) lvl = 0;
+        else if (lvl >= nlevels) lvl = nlevels - 1;
+        radius = __fmul_rn(th, gld(scale + lvl));
+    }
+    qx[o] = u; qy[o] = v; qxr[o] = ur; qr[o] = radius;
+    qmin[o] = lvl - 1; qmax[o] = lvl;   // kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel
+    qvalid[o] = ok ? 1 : 0;
+}
+
+// A loaded monocular / rectified orbx_frame copied into a key frame's own allocation -- what KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-82) does with
+// mvKeysUn, mDescriptors, mvuRight, mvScaleFactors, mvInvLevelSigma2 and mGrid: rows, count, scale factors and the grid AS BUILT (no rebuild).  The count is
+// read on the device (a batch-loaded frame's N may not have reached the host yet).
+struct KeyFrameCopy {
+    const orbx_keypoint *src_kps;
+    const uint8_t *src_desc;
+    const float *src_ur;            // NULL: the frame has no mvuRight
+    const int32_t *src_count;
+    const float *src_scale;
+    const uint16_t *src_gstart, *src_gorder;
+    orbx_keypoint *kps;
+    uint8_t *desc;
+    float *ur;
+    int32_t *count;
+    float *scale, *inv_sigma2;      // inv_sigma2 NULL: none given
+    uint16_t *gstart, *gorder;
+    int cap, nlevels;
+    float inv_sigma2_host[kFrameMaxLevels];
+};
+// grid (1 + ceil(cap / 256)), block 64: block 0 copies the count, the per-level arrays and the grid's cell offsets, block b >= 1 rows [256 (b-1), 256 b)
+__global__ __launch_bounds__(64) void k_keyframe_copy(const KeyFrameCopy F) {
+    const int n = max(0, min(gld(F.src_count), F.cap));
+    const int lane = threadIdx.x;
+    if (blockIdx.x == 0) {
+        if (lane == 0) gst(F.count, (int32_t)n);
+        if (lane < F.nlevels) {
+            gst(F.scale + lane, gld(F.src_scale + lane));
+            if (F.inv_sigma2) gst(F.inv_sigma2 + lane, F.inv_sigma2_host[lane]);
+        }
+        for (int c = lane; c <= kGridCells; c += 64) gst(F.gstart + c, gld(F.src_gstart + c));
+        return;
+    }
+    const int i0 = (blockIdx.x - 1) * 256, i1 = min(i0 + 256, n);
+    if (i0 >= i1) return;
+    const uint32_t *sk = reinterpret_cast<const uint32_t *>(F.src_kps);   // 28-byte rows: 7 dwords each
+    uint32_t *dk = reinterpret_cast<uint32_t *>(F.kps);
+    for (int w = i0 * 7 + lane; w < i1 * 7; w += 64) dk[w] = sk[w];
+    const uint4 *sd = reinterpret_cast<const uint4 *>(F.src_desc);       // 32-byte rows: 2 x 16 bytes
+    uint4 *dd = reinterpret_cast<uint4 *>(F.desc);
+    for (int w = i0 * 2 + lane; w < i1 * 2; w += 64) dd[w] = sd[w];
+    for (int i = i0 + lane; i < i1; i += 64) {
+        if (F.src_ur) F.ur[i] = F.src_ur[i];
+        F.gorder[i] = F.src_gorder[i];   // (the grid holds at most n entries: features outside it have none)
+    }
+}
+
 // k_window_brute (round 6): the same lists as k_window_best2_t WITHOUT the frame's grid, for ONE small problem (a single host-pointer call with a
 // thousand queries into a thousand features): a wave per query walks every feature of the frame, applies PosInGrid + GetFeaturesInArea's tests itself
 // (in_window: the candidate's grid cell comes out of that, so the key orders candidates exactly as the grid enumeration does: cell x, cell y, index) and

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
@@ -2806,6 +2807,326 @@ extern "C" int orbx_fuse_search(orbx_matcher *m, const orbx_frame_desc *kf, cons
     }
     return ORBX_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// Device-resident key frames (include/orbx.h, orbx_keyframe): what KeyFrame::KeyFrame(Frame&) copies of the frame -- immutable from then on, in ONE
+// allocation of its own, readable by every matcher context of its device -- and ORBmatcher::Fuse for K of them in one call.
+// ---------------------------------------------------------------------------------------------------------
+struct orbx_keyframe {
+    int device = 0;
+    uint8_t *dev = nullptr;            // one allocation, carved below
+    orbx_keypoint *kps = nullptr;
+    uint8_t *desc = nullptr;
+    float *u_right = nullptr;          // NULL: no mvuRight
+    float *inv_sigma2 = nullptr;       // NULL: no mvInvLevelSigma2 given
+    float *scale = nullptr;
+    int32_t *count = nullptr;
+    uint16_t *gstart = nullptr, *gorder = nullptr;
+    hipEvent_t ready = nullptr;        // recorded behind the copy / upload + grid build on the creating context's stream
+    std::atomic<bool> done{false};     // a call that waited for `ready` has synchronised since: nobody needs to wait again
+    std::atomic<int> n{-1};            // N; -1 while it is known on the device only (made from a batch-loaded frame)
+    int cap = 0, nlevels = 0;
+    float bounds[4] = {0, 0, 0, 0};
+};
+
+namespace {
+
+// one allocation per key frame: rows for `cap` features (28 + 32 [+ 4] + 2 bytes each), the per-level arrays, the count and the grid's 3073 cell offsets
+int keyframe_alloc(int device, int cap, bool has_ur, bool has_sigma, int nlevels, const float *bounds4, orbx_keyframe **out) {
+    orbx_keyframe *kf = new orbx_keyframe();
+    kf->device = device; kf->cap = cap; kf->nlevels = nlevels;
+    memcpy(kf->bounds, bounds4, sizeof(kf->bounds));
+    const size_t c = (size_t)std::max(cap, 1);
+    size_t o = 0;
+    auto carve = [&o](size_t bytes) { const size_t r = o; o += Arena::pad(bytes); return r; };
+    // (rows and inv_sigma2 first: orbx_keyframe_create_host uploads them as one run)
+    const size_t off_kps = carve(28 * c), off_desc = carve(32 * c), off_ur = has_ur ? carve(4 * c) : 0, off_sg = has_sigma ? carve(4 * (size_t)kFrameMaxLevels) : 0;
+    const size_t off_scale = carve(4 * (size_t)kFrameMaxLevels), off_count = carve(8), off_gs = carve(2 * ((size_t)kGridCells + 1)), off_go = carve(2 * c);
+    hipError_t e = hipMalloc((void **)&kf->dev, o);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&kf->ready, hipEventDisableTiming);
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
+    kf->kps = (orbx_keypoint *)(kf->dev + off_kps); kf->desc = kf->dev + off_desc;
+    kf->u_right = has_ur ? (float *)(kf->dev + off_ur) : nullptr;
+    kf->inv_sigma2 = has_sigma ? (float *)(kf->dev + off_sg) : nullptr;
+    kf->scale = (float *)(kf->dev + off_scale); kf->count = (int32_t *)(kf->dev + off_count);
+    kf->gstart = (uint16_t *)(kf->dev + off_gs); kf->gorder = (uint16_t *)(kf->dev + off_go);
+    *out = kf;
+    return ORBX_OK;
+}
+
+// the calling context's stream is ordered behind the key frame's creation (until a call that did so has synchronised)
+inline int keyframe_acquire(orbx_matcher *m, orbx_keyframe *const *kfs, int n_kf) {
+    for (int k = 0; k < n_kf; k++)
+        if (!kfs[k]->done.load(std::memory_order_acquire)) ORBX_HIP(hipStreamWaitEvent(m->stream, kfs[k]->ready, 0));
+    return ORBX_OK;
+}
+inline void keyframe_release(orbx_keyframe *const *kfs, int n_kf) {   // after the call's synchronisation
+    for (int k = 0; k < n_kf; k++) kfs[k]->done.store(true, std::memory_order_release);
+}
+
+// the key-frame side of problem k
+inline void keyframe_problem(const orbx_keyframe *kf, bool chi2, int strict_fp, KfProblem *R) {
+    memset(R, 0, sizeof(*R));
+    R->P.kps = kf->kps; R->P.desc = kf->desc; R->P.n_ptr = kf->count;
+    R->P.u_right = chi2 ? kf->u_right : nullptr;   // the gate-less form (Fuse with a Sim3, SearchBySim3) never reads mvuRight (ORBmatcher.cc:1405-1433)
+    R->P.scale = kf->scale;
+    R->P.inv_sigma2 = chi2 ? kf->inv_sigma2 : nullptr;
+    R->P.chi2_fma = strict_fp ? 0 : 1;
+    R->P.gstart = kf->gstart; R->P.gorder = kf->gorder;
+    R->g = grid_of(kf->bounds);
+    R->maxx = kf->bounds[1]; R->maxy = kf->bounds[3];
+    R->nlevels = kf->nlevels;
+}
+
+inline void launch_window_best1_kf(hipStream_t st, const KfProblem *dR, int nq_max, int np) {   // ORBX_LAUNCH_WINDOW_BEST2's shape: a problem's blocks on one XCD
+    const int nb = (nq_max + 31) / 32;
+    const dim3 grid = np >= 8 ? dim3(8, (unsigned)nb, (unsigned)((np + 7) / 8)) : dim3(1, (unsigned)nb, (unsigned)np);
+    hipLaunchKernelGGL(k_window_best1_kf, grid, dim3(256), 0, st, dR, np);
+}
+
+}  // namespace
+
+extern "C" {
+
+void orbx_keyframe_destroy(orbx_keyframe *kf) {
+    if (!kf) return;
+    (void)hipSetDevice(kf->device);
+    if (kf->ready) { (void)hipEventSynchronize(kf->ready); (void)hipEventDestroy(kf->ready); }   // the copy / upload has run; no search is running (the caller's contract)
+    if (kf->dev) (void)hipFree(kf->dev);
+    delete kf;
+}
+
+int orbx_keyframe_create_host(orbx_matcher *m, const orbx_frame_desc *d, const float *inv_level_sigma2, orbx_keyframe **out) {
+    if (out) *out = nullptr;
+    if (!m || !out || !d || d->n < 0 || (d->n > 0 && (!d->keypoints_un || !d->descriptors)) || !d->scale_factors || d->nlevels < 1 ||
+        d->nlevels > kFrameMaxLevels)
+        return ORBX_E_BAD_ARG;
+    if (d->n > 65535) return ORBX_E_TOO_LARGE;   // 16-bit grid entries, as orbx_fuse_search
+    ORBX_HIP(hipSetDevice(m->device));
+    const int n = d->n, nl = d->nlevels;
+    const float b[4] = {d->min_x, d->max_x, d->min_y, d->max_y};
+    orbx_keyframe *kf = nullptr;
+    int r = keyframe_alloc(m->device, n, d->u_right != nullptr, inv_level_sigma2 != nullptr, nl, b, &kf);
+    if (r != ORBX_OK) return r;
+    // ONE upload: the rows and inv_sigma2 staged at the allocation's own offsets (pinned; the context's next call waits before it stages over them)
+    const size_t up_end = (size_t)((inv_level_sigma2 ? (uint8_t *)(kf->inv_sigma2 + nl) : d->u_right ? (uint8_t *)(kf->u_right + n) : kf->desc + 32 * (size_t)n) - kf->dev);
+    r = m->reserve_all(up_end + 4096);
+    if (r != ORBX_OK) { orbx_keyframe_destroy(kf); return r; }
+    m->begin();
+    if (n > 0 || inv_level_sigma2) {
+        uint8_t *st = static_cast<uint8_t *>(m->stage.take(up_end + 16));
+        if (!st) { set_error("staging arena exhausted"); orbx_keyframe_destroy(kf); return ORBX_E_INTERNAL; }
+        memset(st, 0, up_end + 16);
+        memcpy(st + ((uint8_t *)kf->kps - kf->dev), d->keypoints_un, 28 * (size_t)n);
+        memcpy(st + (kf->desc - kf->dev), d->descriptors, 32 * (size_t)n);
+        if (d->u_right) memcpy(st + ((uint8_t *)kf->u_right - kf->dev), d->u_right, 4 * (size_t)n);
+        if (inv_level_sigma2) memcpy(st + ((uint8_t *)kf->inv_sigma2 - kf->dev), inv_level_sigma2, 4 * (size_t)nl);
+        m->dirty = true;
+        if (m->kernel_xfer && up_end <= orbx_matcher::kKernelXferMax) {
+            XferOps X;
+            X.n = 1;
+            X.op[0] = XferOp{kf->dev, st, (uint32_t)((up_end + 15) / 16), 0};   // (rounded up to 16 bytes: inside the region's 256-byte padding)
+            m->launch_xfer(X, X.op[0].units);
+        } else {
+            m->note(hipMemcpyAsync(kf->dev, st, up_end, hipMemcpyHostToDevice, m->stream));
+            m->xfers[4]++;
+        }
+        m->xfers[0]++; m->xfers[2] += (int64_t)up_end;
+        if (m->xfer_err != hipSuccess) { set_error(hipGetErrorString(m->xfer_err)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
+    }
+    FramePrepare P;   // k_frame_prepare's in-place form (as orbx_frame_load_host): count, scale factors, grid_build_wave over the uploaded rows
+    memset(&P, 0, sizeof(P));
+    P.kps = kf->kps; P.desc = kf->desc; P.count = kf->count; P.scale = kf->scale; P.gstart = kf->gstart; P.gorder = kf->gorder;
+    P.n_host = n; P.cap = n; P.nlevels = nl;
+    memcpy(P.scale_host, d->scale_factors, sizeof(float) * (size_t)nl);
+    m->dirty = true;
+    hipLaunchKernelGGL(k_frame_prepare, dim3(1), dim3(64), 0, m->stream, P, grid_of(kf->bounds));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(kf->ready, m->stream);
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
+    kf->n.store(n);
+    *out = kf;
+    return ORBX_OK;
+}
+
+int orbx_keyframe_from_frame(orbx_matcher *m, orbx_frame *f, const float *inv_level_sigma2, orbx_keyframe **out) {
+    if (out) *out = nullptr;
+    if (!m || !out || !f || f->owner != m || !f->loaded || f->fisheye) return ORBX_E_BAD_ARG;
+    ORBX_HIP(hipSetDevice(m->device));
+    const int cap = f->n_known ? f->n : f->cap;   // sized by N where the host knows it
+    orbx_keyframe *kf = nullptr;
+    int r = keyframe_alloc(m->device, cap, f->has_ur, inv_level_sigma2 != nullptr, f->nlevels, f->bounds, &kf);
+    if (r != ORBX_OK) return r;
+    KeyFrameCopy C;
+    memset(&C, 0, sizeof(C));
+    C.src_kps = f->kps; C.src_desc = f->desc; C.src_ur = f->has_ur ? f->u_right : nullptr; C.src_count = f->count; C.src_scale = f->scale;
+    C.src_gstart = f->gstart; C.src_gorder = f->gorder;
+    C.kps = kf->kps; C.desc = kf->desc; C.ur = kf->u_right; C.count = kf->count; C.scale = kf->scale; C.inv_sigma2 = kf->inv_sigma2;
+    C.gstart = kf->gstart; C.gorder = kf->gorder; C.cap = cap; C.nlevels = f->nlevels;
+    if (inv_level_sigma2) memcpy(C.inv_sigma2_host, inv_level_sigma2, sizeof(float) * (size_t)f->nlevels);
+    // on the owner's stream: behind the frame's load, ahead of its next one -- no host synchronisation
+    m->dirty = true;
+    hipLaunchKernelGGL(k_keyframe_copy, dim3(1 + (unsigned)((cap + 255) / 256)), dim3(64), 0, m->stream, C);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(kf->ready, m->stream);
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
+    kf->n.store(f->n_known ? f->n : -1);
+    *out = kf;
+    return ORBX_OK;
+}
+
+int orbx_keyframe_count(orbx_keyframe *kf, int *n) {
+    if (!kf || !n) return ORBX_E_BAD_ARG;
+    int v = kf->n.load();
+    if (v < 0) {   // made from a batch-loaded frame: one download behind the copy
+        ORBX_HIP(hipSetDevice(kf->device));
+        ORBX_HIP(hipEventSynchronize(kf->ready));
+        int32_t c = 0;
+        ORBX_HIP(hipMemcpy(&c, kf->count, 4, hipMemcpyDeviceToHost));
+        v = c;
+        kf->n.store(v);
+        kf->done.store(true, std::memory_order_release);
+    }
+    *n = v;
+    return ORBX_OK;
+}
+
+// orbx_fuse_search for n_kf resident key frames, each with its own query set, in one call: one upload run, k_window_best1_kf over all problems, one
+// download run, one synchronisation.
+int orbx_keyframe_fuse_search(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fuse_queries *queries, int use_chi2, int strict_fp,
+                              int32_t *const *best_idx, int32_t *const *best_dist) {
+    if (!m || n_kf < 0 || (n_kf > 0 && (!kfs || !queries || !best_idx || !best_dist))) return ORBX_E_BAD_ARG;
+    if (n_kf > ORBX_MAX_FUSE_KEYFRAMES) return ORBX_E_TOO_LARGE;
+    size_t total = 0, need = 0;
+    int nq_max = 0;
+    for (int k = 0; k < n_kf; k++) {
+        const orbx_fuse_queries &q = queries[k];
+        if (!kfs[k] || kfs[k]->device != m->device || q.n < 0 || (use_chi2 && !kfs[k]->inv_sigma2)) return ORBX_E_BAD_ARG;
+        if (q.n > 0 && (!q.u || !q.v || !q.r || !q.level || !q.desc || !best_idx[k] || !best_dist[k])) return ORBX_E_BAD_ARG;
+        total += (size_t)q.n;
+        nq_max = std::max(nq_max, q.n);
+        need += 6 * Arena::pad(4 * (size_t)q.n) + Arena::pad(32 * (size_t)q.n);
+    }
+    for (int k = 0; k < n_kf; k++)
+        for (int i = 0; i < queries[k].n; i++) { best_idx[k][i] = -1; best_dist[k][i] = 256; }
+    if (total == 0) return ORBX_OK;
+    ORBX_HIP(hipSetDevice(m->device));
+    need += Arena::pad(4 * (size_t)n_kf) + Arena::pad(sizeof(KfProblem) * (size_t)n_kf) + Arena::pad(8 * total) + 16 * 256 + 4096;
+    int r = m->reserve_all(need);
+    if (r != ORBX_OK) return r;
+    Arena &A = m->arena;
+    m->begin();
+    std::vector<KfProblem> R((size_t)n_kf);
+    std::vector<int32_t> cnts((size_t)n_kf), lv;
+    std::vector<size_t> off((size_t)n_kf);
+    size_t o = 0;
+    for (int k = 0; k < n_kf; k++) {   // the inputs of every problem, adjacent in the arena: one upload run
+        const orbx_fuse_queries &q = queries[k];
+        const size_t nq = (size_t)q.n;
+        keyframe_problem(kfs[k], use_chi2 != 0, strict_fp, &R[k]);
+        cnts[k] = q.n; off[k] = o; o += nq;
+        if (nq == 0) continue;
+        WindowProblem &P = R[k].P;
+        float *f3[3]; const float *h3[3] = {q.u, q.v, q.r};
+        for (int c = 0; c < 3; c++) { f3[c] = A.take<float>(nq); H2D(f3[c], h3[c], 4 * nq); }
+        P.qx = f3[0]; P.qy = f3[1]; P.qr = f3[2];
+        int32_t *dmin = A.take<int32_t>(nq), *dmax = A.take<int32_t>(nq);
+        lv.resize(nq);
+        for (size_t i = 0; i < nq; i++) lv[i] = q.level[i] - 1;   // kpLevel<nPredictedLevel-1 || kpLevel>nPredictedLevel
+        H2D(dmin, lv.data(), 4 * nq); H2D(dmax, q.level, 4 * nq);
+        P.qmin = dmin; P.qmax = dmax;
+        if (q.ur && P.u_right) { float *p = A.take<float>(nq); H2D(p, q.ur, 4 * nq); P.qxr = p; }
+        { uint8_t *p = A.take<uint8_t>(32 * nq); H2D(p, q.desc, 32 * nq); P.qdesc = p; }
+    }
+    int32_t *dcnt = A.take<int32_t>(n_kf);
+    KfProblem *dR = A.take<KfProblem>(n_kf);
+    u64 *dkeys = A.take<u64>(total);
+    for (int k = 0; k < n_kf; k++) { R[k].P.nq_ptr = dcnt + k; R[k].P.keys = dkeys + off[k]; }
+    H2D(dcnt, cnts.data(), 4 * (size_t)n_kf);
+    H2D(dR, R.data(), sizeof(KfProblem) * (size_t)n_kf);
+    r = keyframe_acquire(m, kfs, n_kf);
+    if (r != ORBX_OK) return r;
+    launch_window_best1_kf(m->exec(), dR, nq_max, n_kf);
+    std::vector<u64> keys(total);
+    D2H(keys.data(), dkeys, 8 * total);
+    SYNC_AND_DELIVER();
+    keyframe_release(kfs, n_kf);
+    for (int k = 0; k < n_kf; k++)
+        for (int i = 0; i < queries[k].n; i++) {
+            const u64 key = keys[off[k] + (size_t)i];
+            if (key != kNoKey) { best_idx[k][i] = (int32_t)(key & 0xffff); best_dist[k][i] = (int32_t)(key >> 32); }
+        }
+    return ORBX_OK;
+}
+
+// LocalMapping::SearchInNeighbors' Fuse loop in one call: k_fuse_project writes the query records of every (key frame, map point) into the arena,
+// k_window_best1_kf searches them -- the records never visit the host, the map points go up once.
+int orbx_keyframe_fuse_map_points(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams, const orbx_frame_pose *poses, float th,
+                                  float log_scale_factor, int strict_fp, int n_mp, const float *pos, const float *normal, const float *min_dist,
+                                  const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
+                                  uint8_t *projected) {
+    if (!m || n_kf < 0 || n_mp < 0 || (n_kf > 0 && (!kfs || !cams || !poses))) return ORBX_E_BAD_ARG;
+    if (n_kf > ORBX_MAX_FUSE_KEYFRAMES) return ORBX_E_TOO_LARGE;
+    const size_t np = (size_t)n_mp, total = (size_t)n_kf * np;
+    if (total > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !best_idx || !best_dist)) return ORBX_E_BAD_ARG;
+    for (int k = 0; k < n_kf; k++)
+        if (!kfs[k] || kfs[k]->device != m->device || !kfs[k]->inv_sigma2) return ORBX_E_BAD_ARG;
+    if (total == 0) return ORBX_OK;
+    ORBX_HIP(hipSetDevice(m->device));
+    const size_t need = 2 * Arena::pad(12 * np) + 2 * Arena::pad(4 * np) + Arena::pad(32 * np) + Arena::pad(sizeof(orbx_camera) * (size_t)n_kf) +
+                        Arena::pad(sizeof(orbx_frame_pose) * (size_t)n_kf) + Arena::pad(sizeof(KfProblem) * (size_t)n_kf) + 2 * Arena::pad(total) +
+                        6 * Arena::pad(4 * total) + Arena::pad(8 * total) + 16 * 256 + 4096;
+    int r = m->reserve_all(need);
+    if (r != ORBX_OK) return r;
+    Arena &A = m->arena;
+    m->begin();
+    // uploads, adjacent in the arena (one run): the map points ONCE, then what grows with n_kf -- cameras, poses, problem records, skip flags
+    float *dp = A.take<float>(3 * np), *dn = A.take<float>(3 * np), *dmn = A.take<float>(np), *dmx = A.take<float>(np);
+    uint8_t *dd = A.take<uint8_t>(32 * np);
+    int32_t *dcnt = A.take<int32_t>(4);
+    orbx_camera *dcam = A.take<orbx_camera>(n_kf);
+    orbx_frame_pose *dpose = A.take<orbx_frame_pose>(n_kf);
+    KfProblem *dR = A.take<KfProblem>(n_kf);
+    uint8_t *dskip = skip ? A.take<uint8_t>(total) : nullptr;
+    // written by k_fuse_project, read by k_window_best1_kf
+    float *qx = A.take<float>(total), *qy = A.take<float>(total), *qxr = A.take<float>(total), *qr = A.take<float>(total);
+    int32_t *qmin = A.take<int32_t>(total), *qmax = A.take<int32_t>(total);
+    uint8_t *qvalid = A.take<uint8_t>(total);
+    u64 *dkeys = A.take<u64>(total);
+    std::vector<KfProblem> R((size_t)n_kf);
+    for (int k = 0; k < n_kf; k++) {
+        keyframe_problem(kfs[k], true, strict_fp, &R[k]);
+        WindowProblem &P = R[k].P;
+        const size_t o = (size_t)k * np;
+        P.qx = qx + o; P.qy = qy + o; P.qr = qr + o; P.qxr = qxr + o; P.qmin = qmin + o; P.qmax = qmax + o; P.qvalid = qvalid + o;
+        P.qdesc = dd; P.nq_ptr = dcnt; P.keys = dkeys + o;
+    }
+    const int32_t cnt4[4] = {n_mp, 0, 0, 0};
+    H2D(dp, pos, 12 * np); H2D(dn, normal, 12 * np); H2D(dmn, min_dist, 4 * np); H2D(dmx, max_dist, 4 * np); H2D(dd, mp_desc, 32 * np);
+    H2D(dcnt, cnt4, 16);
+    H2D(dcam, cams, sizeof(orbx_camera) * (size_t)n_kf); H2D(dpose, poses, sizeof(orbx_frame_pose) * (size_t)n_kf);
+    H2D(dR, R.data(), sizeof(KfProblem) * (size_t)n_kf);
+    if (skip) H2D(dskip, skip, total);
+    r = keyframe_acquire(m, kfs, n_kf);
+    if (r != ORBX_OK) return r;
+    hipLaunchKernelGGL(k_fuse_project, dim3((unsigned)((n_mp + 255) / 256), (unsigned)n_kf), dim3(256), 0, m->exec(), (const KfProblem *)dR,
+                       (const orbx_camera *)dcam, (const orbx_frame_pose *)dpose, th, log_scale_factor, n_mp, (const float *)dp, (const float *)dn,
+                       (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx, qy, qxr, qr, qmin, qmax, qvalid);
+    launch_window_best1_kf(m->exec(), dR, n_mp, n_kf);
+    std::vector<u64> keys(total);
+    if (projected) D2H(projected, qvalid, total);   // (adjacent to the keys: one download run)
+    D2H(keys.data(), dkeys, 8 * total);
+    SYNC_AND_DELIVER();
+    keyframe_release(kfs, n_kf);
+    for (size_t i = 0; i < total; i++) {
+        const u64 key = keys[i];
+        best_idx[i] = key == kNoKey ? -1 : (int32_t)(key & 0xffff);
+        best_dist[i] = key == kNoKey ? 256 : (int32_t)(key >> 32);
+    }
+    return ORBX_OK;
+}
+
+}  // extern "C"
 
 // ---------------------------------------------------------------------------------------------------------
 // Tracking::SearchLocalPoints on a resident frame (Tracking.cc:3339-3413): Frame::isInFrustum (Frame.cc:512-575) of every local map point, the

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import KP_DTYPE, BowKeyFrame, FeatVec, FrameDesc, PAIR_PREDICATE, PinholeGate, check, ptr
+from ._lib import KP_DTYPE, BowKeyFrame, FeatVec, FrameDesc, FuseQueries, PAIR_PREDICATE, PinholeGate, check, ptr
 
 
 @dataclass
@@ -151,6 +151,47 @@ class DeviceFrame:
         check(self._L.orbx_frame_compute_bow_fisheye(self.matcher._h, self._h, voc._h, int(levelsup), ptr(w), ptr(nd)), "orbx_frame_compute_bow_fisheye")
         n = self.count()   # (known after the call: no further synchronisation)
         return w[:n], nd[:n]
+
+
+class DeviceKeyFrame:
+    """An immutable key frame resident on the device (orbx_keyframe, include/orbx.h): what KeyFrame::KeyFrame(Frame&) copies of the frame --
+    mvKeysUn, descriptors, optional mvuRight, scale factors, mvInvLevelSigma2, the bounds and the 64x48 grid.  It belongs to no matcher: every
+    ORBmatcher of the same device may search it (FuseSearchKeyFrames / FuseMapPoints), from any thread.  close() (or garbage collection) frees it;
+    no call that was handed the key frame may be running then."""
+
+    def __init__(self, handle):
+        self._L = _lib.lib()
+        self._h = handle
+
+    @classmethod
+    def from_frame(cls, matcher: "ORBmatcher", frame: "DeviceFrame", inv_level_sigma2=None) -> "DeviceKeyFrame":
+        """Device-to-device copy of a loaded monocular / rectified DeviceFrame of `matcher` (orbx_keyframe_from_frame): asynchronous, the
+        frame may be reloaded right away."""
+        isg = _f32(inv_level_sigma2)
+        h = C.c_void_p()
+        check(_lib.lib().orbx_keyframe_from_frame(matcher._h, frame._h, ptr(isg), C.byref(h)), "orbx_keyframe_from_frame")
+        return cls(h)
+
+    @classmethod
+    def from_host(cls, matcher: "ORBmatcher", F: "FrameView", inv_level_sigma2=None) -> "DeviceKeyFrame":
+        """The same object from host arrays (orbx_keyframe_create_host): one upload, the grid built as FuseSearch builds it."""
+        isg = _f32(inv_level_sigma2)
+        fd = F.c_struct()
+        h = C.c_void_p()
+        check(_lib.lib().orbx_keyframe_create_host(matcher._h, C.byref(fd), ptr(isg), C.byref(h)), "orbx_keyframe_create_host")   # (staged before it returns)
+        return cls(h)
+
+    def count(self) -> int:
+        n = C.c_int(0)
+        check(self._L.orbx_keyframe_count(self._h, C.byref(n)), "orbx_keyframe_count")
+        return n.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_keyframe_destroy(self._h)
+            self._h = None
+
+    __del__ = close
 
 
 def _f32(a):
@@ -686,6 +727,53 @@ class ORBmatcher:
         check(self._L.orbx_fuse_search(self._h, C.byref(fd), ptr(isg), nq, ptr(a["u"]), ptr(a["v"]), ptr(a["ur"]), ptr(a["r"]),
                                        ptr(a["lv"]), ptr(a["d"]), int(strict_fp), ptr(bi), ptr(bd)), "orbx_fuse_search")
         return bi, bd
+
+    # ---- Fuse on resident key frames: K targets in one call (LocalMapping::SearchInNeighbors) ----
+    def FuseSearchKeyFrames(self, kfs, queries, use_chi2: bool = True, strict_fp: bool = False):
+        """FuseSearch for K DeviceKeyFrames in one call (orbx_keyframe_fuse_search).  queries[k]: dict(u, v, ur, r, level, desc) of key frame k
+        (ur may be None).  use_chi2: the reprojection gate with the key frames' inv_level_sigma2; False = the gate-less form (Fuse with a Sim3,
+        SearchBySim3).  Returns [(best_idx, best_dist)] per key frame, each equal to FuseSearch on that key frame's host arrays."""
+        K = len(kfs)
+        assert len(queries) == K
+        keep, qs = [], (FuseQueries * max(K, 1))()
+        bi, bd = [], []
+        for k, q in enumerate(queries):
+            nq = len(q["u"])
+            a = [_f32(q["u"]), _f32(q["v"]), _f32(q.get("ur")), _f32(q["r"]), _i32(q["level"]), _u8(q["desc"])]
+            keep.append(a)
+            qs[k] = FuseQueries(nq, *[None if (x is None or nq == 0) else x.ctypes.data for x in a])
+            bi.append(np.zeros(nq, np.int32))
+            bd.append(np.zeros(nq, np.int32))
+        vp = C.c_void_p
+        hs = (vp * max(K, 1))(*[kf._h.value if isinstance(kf._h, vp) else kf._h for kf in kfs])
+        pi = (vp * max(K, 1))(*[ptr(x) for x in bi])
+        pd = (vp * max(K, 1))(*[ptr(x) for x in bd])
+        check(self._L.orbx_keyframe_fuse_search(self._h, K, hs, qs, int(bool(use_chi2)), int(bool(strict_fp)), pi, pd), "orbx_keyframe_fuse_search")
+        return list(zip(bi, bd))
+
+    def FuseMapPoints(self, kfs, cams, poses, map_points: dict, th: float = 3.0, log_scale_factor: float = 0.0, skip=None,
+                      strict_fp: bool = False, want_projected: bool = True):
+        """The Fuse loop of LocalMapping::SearchInNeighbors in one call, projection included (orbx_keyframe_fuse_map_points).  cams[k] = orbx_camera
+        fields (fx, fy, cx, cy, k1, k2, p1, p2, k3, bf), poses[k] = (Rcw, tcw, Ow) of key frame k; map_points: dict(pos [n, 3], normal [n, 3],
+        min_dist, max_dist, desc [n, 32]); skip [K, n] = !pMP || isBad() || IsInKeyFrame(pKF_k) or None.
+        Returns (best_idx [K, n], best_dist [K, n], projected [K, n] or None)."""
+        from ._lib import Camera, FramePose
+        K = len(kfs)
+        assert len(cams) == K and len(poses) == K
+        P, Nn = _f32(np.asarray(map_points["pos"]).reshape(-1, 3)), _f32(np.asarray(map_points["normal"]).reshape(-1, 3))
+        mn, mx, d = _f32(map_points["min_dist"]), _f32(map_points["max_dist"]), _u8(map_points["desc"])
+        n = len(P)
+        sk = None if skip is None else _u8(np.asarray(skip).reshape(K, n))
+        cs = (Camera * max(K, 1))(*[Camera(*[float(x) for x in c]) for c in cams])
+        ps = (FramePose * max(K, 1))(*[FramePose.make(*p) for p in poses])
+        vp = C.c_void_p
+        hs = (vp * max(K, 1))(*[kf._h.value if isinstance(kf._h, vp) else kf._h for kf in kfs])
+        bi, bd = np.full((K, n), -1, np.int32), np.full((K, n), 256, np.int32)
+        pr = np.zeros((K, n), np.uint8) if want_projected else None
+        check(self._L.orbx_keyframe_fuse_map_points(self._h, K, hs, cs, ps, float(th), float(log_scale_factor), int(bool(strict_fp)), n, ptr(P),
+                                                    ptr(Nn), ptr(mn), ptr(mx), ptr(d), ptr(sk), ptr(bi), ptr(bd), ptr(pr)),
+              "orbx_keyframe_fuse_map_points")
+        return bi, bd, pr
 
     # ---- SearchBySim3 (ORBmatcher.cc:1457-1674): two gate-less fuse searches + mutual agreement ----
     def SearchBySim3(self, KF1: FrameView, KF2: FrameView, side1: dict, side2: dict, th: float, already_matched1=None,

@@ -255,3 +255,90 @@ def make_fisheye_stereo_frame(rng, n_pts: int = 1500, n_left: int | None = None,
     kl, kr = k1[il].copy(), k1[ir].copy()
     rig = dict(cam_left=cams[0].copy(), cam_right=cams[1].copy(), R_lr=R_lr.astype(np.float32), t_lr=t_lr.astype(np.float32))
     return kl, desc(id1[il]), kr, desc(id1[ir]), mono_left, mono_right, rig, id1[il].copy(), id1[ir].copy()
+
+
+def make_fuse_scene(rng, n_kf: int = 20, n_mp: int = 1000, outliers: bool = True, n_clutter: int = 300, bounds=(0.0, 752.0, 0.0, 480.0),
+                    nlevels: int = 8, scale_factor: float = 1.2):
+    """A LocalMapping::SearchInNeighbors scene: n_mp map points seen from n_kf covisible key frames (EuRoC intrinsics, poses within about 0.5 m /
+    0.06 rad of each other; key frame 0 has the identity pose).  Each key frame's features sit at 70 % of the map points' projections into it (0.8 px
+    noise, 2 - 25 % flipped descriptor bits, octave = the level the distance predicts) plus n_clutter random ones; half of the features have u_right.
+    outliers: 8 % of the points mirrored behind the cameras, 8 % with x * 2.5 (outside the image), 4 % with mfMaxDistance * 0.3, 4 % with mfMinDistance
+    = 2 mfMaxDistance, 10 % with random normals -- one population per gate of ORBmatcher::Fuse.  bounds: one (minX, maxX, minY, maxY) for all key
+    frames or one per key frame.  Feature placement uses a plain float64 projection: the exact gates are the caller's (or the library's) business.
+    Returns dict(cams [n_kf] orbx_camera tuples, poses [n_kf] (Rcw, tcw, Ow) float32, bounds [n_kf, 4], scale_factors, inv_level_sigma2,
+    log_scale_factor, map_points dict(pos, normal, min_dist, max_dist, desc), key_frames [n_kf] dict(kps KP_DTYPE, desc, u_right))."""
+    from ._lib import KP_DTYPE
+    f32 = np.float32
+    fx, fy, cx, cy, bf = 458.654, 457.296, 367.215, 248.375, 47.9
+    sf = (f32(scale_factor) ** np.arange(nlevels)).astype(f32)
+    log_sf = float(np.log(f32(scale_factor)))
+    b = np.broadcast_to(np.asarray(bounds, f32).reshape(-1, 4), (n_kf, 4)).copy()
+    # map points in front of key frame 0, spread over its image
+    z = rng.uniform(2.0, 12.0, n_mp)
+    u0, v0 = rng.uniform(30, 720, n_mp), rng.uniform(30, 450, n_mp)
+    pos = np.stack([(u0 - cx) / fx * z, (v0 - cy) / fy * z, z], axis=1)
+    ref_dist = np.linalg.norm(pos, axis=1)
+    ref_level = rng.integers(0, nlevels - 1, n_mp)
+    max_d = ref_dist * sf[ref_level].astype(np.float64) * rng.uniform(0.95, 1.05, n_mp)
+    min_d = max_d / float(sf[-1])
+    normal = pos / ref_dist[:, None] + rng.normal(0, 0.15, pos.shape)   # MapPoint::mNormalVector: the mean viewing direction (camera -> point)
+    normal = normal / np.linalg.norm(normal, axis=1, keepdims=True)
+    if outliers:
+        kind = rng.choice(6, n_mp, p=[0.66, 0.08, 0.08, 0.04, 0.04, 0.10])
+        pos[kind == 1] *= -1.0
+        pos[kind == 2, 0] *= 2.5
+        max_d[kind == 3] *= 0.3
+        min_d[kind == 3] = max_d[kind == 3] / float(sf[-1])
+        min_d[kind == 4] = 2.0 * max_d[kind == 4]
+        rn = rng.normal(0, 1, (int((kind == 5).sum()), 3))
+        normal[kind == 5] = rn / np.linalg.norm(rn, axis=1, keepdims=True)
+    mp_desc = rng.integers(0, 256, (n_mp, 32), dtype=np.uint8)
+    pos, normal, min_d, max_d = pos.astype(f32), normal.astype(f32), min_d.astype(f32), max_d.astype(f32)
+    cams, poses, kfs = [], [], []
+    for k in range(n_kf):
+        if k == 0:
+            R, t = np.eye(3), np.zeros(3)
+        else:
+            w = rng.normal(0, 0.035, 3)
+            th = np.linalg.norm(w)
+            K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]]) / max(th, 1e-12)
+            R = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
+            t = rng.normal(0, 0.3, 3)
+        Rcw, tcw = R.astype(f32), t.astype(f32)
+        Ow = (-Rcw.astype(np.float64).T @ tcw.astype(np.float64)).astype(f32)
+        cams.append((fx, fy, cx, cy, 0.0, 0.0, 0.0, 0.0, 0.0, bf))
+        poses.append((Rcw, tcw, Ow))
+        # plain projection for the feature placement
+        pc = pos.astype(np.float64) @ Rcw.astype(np.float64).T + tcw
+        with np.errstate(divide="ignore", invalid="ignore"):
+            uu, vv = fx * pc[:, 0] / pc[:, 2] + cx, fy * pc[:, 1] / pc[:, 2] + cy
+        d3 = np.linalg.norm(pos.astype(np.float64) - Ow, axis=1)
+        vis = (pc[:, 2] > 0) & (uu > b[k, 0] + 2) & (uu < b[k, 1] - 2) & (vv > b[k, 2] + 2) & (vv < b[k, 3] - 2)
+        sel = np.nonzero(vis & (rng.random(n_mp) < 0.7))[0]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            lvl = np.clip(np.ceil(np.log(max_d[sel].astype(np.float64) / d3[sel]) / log_sf), 0, nlevels - 1).astype(np.int32)
+        lvl = np.where(rng.random(len(sel)) < 0.25, np.maximum(lvl - 1, 0), lvl)
+        n = len(sel) + n_clutter
+        kp = np.zeros(n, KP_DTYPE)
+        kp["x"][:len(sel)] = uu[sel] + rng.normal(0, 0.8, len(sel))
+        kp["y"][:len(sel)] = vv[sel] + rng.normal(0, 0.8, len(sel))
+        kp["octave"][:len(sel)] = lvl
+        kp["x"][len(sel):] = rng.uniform(b[k, 0] + 1, b[k, 1] - 1, n_clutter)
+        kp["y"][len(sel):] = rng.uniform(b[k, 2] + 1, b[k, 3] - 1, n_clutter)
+        kp["octave"][len(sel):] = rng.integers(0, nlevels, n_clutter)
+        kp["size"] = 31.0 * sf[kp["octave"]]
+        kp["angle"] = rng.uniform(0, 360, n)
+        kp["response"] = rng.integers(7, 200, n)
+        kp["class_id"] = -1
+        flip = rng.uniform(0.02, 0.25, len(sel))[:, None]
+        d = np.concatenate([mp_desc[sel] ^ np.packbits(rng.random((len(sel), 256)) < flip, axis=1, bitorder="little"),
+                            rng.integers(0, 256, (n_clutter, 32), dtype=np.uint8)])
+        ur = np.full(n, -1.0, f32)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ur[:len(sel)] = (kp["x"][:len(sel)] - bf / pc[sel, 2] + rng.normal(0, 0.5, len(sel))).astype(f32)
+        ur[len(sel):] = kp["x"][len(sel):] - rng.uniform(2, 40, n_clutter).astype(f32)
+        ur[rng.random(n) < 0.5] = -1.0
+        perm = rng.permutation(n)
+        kfs.append(dict(kps=np.ascontiguousarray(kp[perm]), desc=np.ascontiguousarray(d[perm]), u_right=np.ascontiguousarray(ur[perm])))
+    return dict(cams=cams, poses=poses, bounds=b, scale_factors=sf, inv_level_sigma2=(f32(1.0) / (sf * sf)).astype(f32), log_scale_factor=log_sf,
+                map_points=dict(pos=pos, normal=normal, min_dist=min_d, max_dist=max_d, desc=mp_desc), key_frames=kfs)
