@@ -662,6 +662,8 @@ int orbx_fuse_search(orbx_matcher *m, const orbx_frame_desc *kf, const float *in
  * SHARING.  A key frame belongs to no matcher: it records an event when its copy / upload is enqueued, and ANY matcher context of the same device may
  * search it -- the context's stream waits for that event until a call that did so has returned.  (A context of another device: ORBX_E_BAD_ARG.)  The
  * key frame is read-only afterwards, so contexts on different threads may search the same key frames at the same time without a lock.
+ * (The one later write is attaching the BoW state, orbx_keyframe_compute_bow / orbx_keyframe_bow_from_frame below: the caller orders that call before any
+ * BoW search is handed the key frame -- "SHARING, continued" there.)
  * orbx_keyframe_destroy waits for the copy / upload, then frees the allocation and the event; call it only when no call that was handed the key frame
  * is running (both searches below synchronise before they return, so "running" means: has not returned yet).  A key frame may outlive the matcher and the
  * frame handle it was made from. */
@@ -796,6 +798,65 @@ int orbx_frame_search_by_projection_window_fisheye(orbx_matcher *m, orbx_frame *
                                                    const float *q_y, const float *q_r, const int32_t *q_min_level, const int32_t *q_max_level,
                                                    const float *q_angle, const uint8_t *q_desc, const uint8_t *q_has_obs, float max_dist,
                                                    int check_orientation, int32_t *match);
+
+/* ---- BoW on device-resident key frames: KeyFrame::ComputeBoW and the BoW-guided matchers with BOTH sides resident ----
+ * A key frame's BoW state is a second allocation, made when BoW is first attached (key frames without it keep their ~66 bytes per feature): per-feature
+ * word and node ids, mvKeysUn[i].angle, and mFeatVec as orbx_frame_compute_bow keeps it (ascending node ids, each with its feature indices in
+ * ascending order, stopped words left out: the std::map order of FeatureVector::addFeature), with the vocabulary and levelsup it was made with.
+ * It is set ONCE and immutable afterwards.  Key frames of at most 16384 features (ORBX_E_TOO_LARGE beyond: the FeatureVector is sorted in LDS).
+ *   orbx_keyframe_compute_bow: KeyFrame::ComputeBoW (KeyFrame.cc: `if (mBowVec.empty() || mFeatVec.empty())` ... transform(vCurrentDesc, mBowVec,
+ *     mFeatVec, 4), the transform of Frame.cc:738-745) on the key frame's own descriptors: nothing is uploaded, N is read on the device when the key
+ *     frame came from a batch-loaded frame.  word_id / node_id: optional, N entries each (a buffer of the key frame's capacity -- the frame handle's,
+ *     if N was unknown when it was made -- always suffices); both NULL: nothing waits.  A second call with the same vocabulary and levelsup does not
+ *     compute again, as the reference's guard: it only returns the ids that were kept.  With another vocabulary or levelsup: ORBX_E_BAD_ARG.
+ *   orbx_keyframe_bow_from_frame: the mBowVec(F.mBowVec), mFeatVec(F.mFeatVec) part of KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-82): a
+ *     device-to-device copy of the frame handle's BoW state on the owner's stream, no host synchronisation.  `frame` must be the handle `kf` was
+ *     made from by orbx_keyframe_from_frame (ORBX_E_BAD_ARG otherwise), still holding that load (ORBX_E_STALE if it has been loaded since), with an
+ *     orbx_frame_compute_bow since that load (ORBX_E_BAD_ARG otherwise).  A key frame that already has BoW: ORBX_E_BAD_ARG.
+ * SHARING, continued.  The BoW state is guarded as the rows are: an event behind its creation, every context's stream waits for it until a call that
+ * did so has returned.  ORDER: attaching BoW is the one write a key frame sees after its creation, and it takes no lock.  The caller orders the
+ * attaching call before any BoW search is handed the key frame (and before a second attaching call), as LocalMapping::ProcessNewKeyFrame computes
+ * the BoW before the key frame enters the map; searches that do not read the BoW state (the Fuse forms) may run meanwhile. */
+int orbx_keyframe_compute_bow(orbx_matcher *m, orbx_keyframe *kf, const orbx_vocabulary *voc, int levelsup, int32_t *word_id, int32_t *node_id);
+int orbx_keyframe_bow_from_frame(orbx_matcher *m, orbx_keyframe *kf, orbx_frame *frame);
+/* The three searches below share one driver: flags and one problem record per problem go up in one run, a pairing kernel reads both sides' node counts
+ * on the device, then the batched replay and its finish pass, one download run, one synchronisation; the launch chain does not grow with n_kf and
+ * nothing waits before the launches.  Refused with ORBX_E_BAD_ARG before anything is enqueued: a key frame without BoW, key frames / a frame whose
+ * vocabulary or levelsup differ, a key frame of another device, a NULL key frame or row, a fisheye-stereo handle.  n_kf > ORBX_MAX_BOW_KEYFRAMES:
+ * ORBX_E_TOO_LARGE.  Flags are given for all N features of their key frame; if N of that key frame is still on the device only, flags other than
+ * NULL cost one orbx_keyframe_count first.
+ *
+ * orbx_frame_search_by_bow_resident: ORBmatcher(nnratio, check_orientation).SearchByBoW(kfs[k], F, vvpMapPointMatches[k]) (ORBmatcher.cc:223-425)
+ *   for k < n_kf -- Tracking::Relocalization's candidates, TrackReferenceKeyFrame with n_kf = 1 -- against the handle's frame (after
+ *   orbx_frame_compute_bow).  valid[k][i] != 0 <=> feature i of key frame k has a good map point (valid or valid[k] NULL: all).  match / match_stride
+ *   / nmatches as orbx_frame_search_by_bow; row k equals that call's, and orbx_search_by_bow_frame's, for the same key frame given as host arrays,
+ *   bit for bit.  Uploaded per key frame: its flags and its record. */
+int orbx_frame_search_by_bow_resident(orbx_matcher *m, orbx_frame *f, int n_kf, orbx_keyframe *const *kfs, const uint8_t *const *valid, float nnratio,
+                                      int check_orientation, int32_t *match, int match_stride, int32_t *nmatches);
+/* orbx_keyframe_search_by_bow: SearchByBoW(pKF1, kfs2[k], vpMatches12) (ORBmatcher.cc:765-905; LoopClosing::DetectCommonRegionsFromBoW runs it for
+ *   the current key frame against every candidate's covisible key frames) for k < n_kf.  match12[k * match_stride + i1] = feature of kfs2[k] or -1 for
+ *   i1 < N1, nmatches[k] = the member's return value; row k equals orbx_search_by_bow_keyframes(kf1, kfs2[k]) bit for bit.  vbMatched2, the row, the
+ *   rotation histogram and the counters are per problem: the same key frame may appear several times in kfs2, and kf1 among them.
+ *   match_stride >= N1 (below kf1's capacity while N1 is on the device only: one orbx_keyframe_count first). */
+int orbx_keyframe_search_by_bow(orbx_matcher *m, orbx_keyframe *kf1, const uint8_t *valid1, int n_kf, orbx_keyframe *const *kfs2,
+                                const uint8_t *const *valid2, float nnratio, int check_orientation, int32_t *match12, int match_stride, int32_t *nmatches);
+/* orbx_keyframe_search_for_triangulation: SearchForTriangulation (ORBmatcher.cc:907-1146) between two resident PINHOLE key frames with both gates on
+ *   the device: orbx_search_for_triangulation_pinhole with everything the key frames already hold taken from them (mvKeysUn, mvuRight, descriptors,
+ *   mFeatVec, pKF2->mvScaleFactors).  The gate carries what is left: F12, the epipole, coarse, strict_fp and pKF2->mvLevelSigma2 [nlevels = the key
+ *   frame's] -- the key frame keeps mvInvLevelSigma2 and the reference reads mvLevelSigma2 (Pinhole.cpp:107-129), so the table is sent, not derived by
+ *   a division.  skip1 / skip2 (N1 / N2 entries, NULL: none) and matches12 (N1 entries) as orbx_search_for_triangulation_pinhole; returns the number
+ *   of matches (>= 0) or an error.  LocalMapping::CreateNewMapPoints calls it once per neighbour: its calls depend on each other through skip1, so
+ *   there is no batched form.  Uploads: the two flag rows, the level table and the record. */
+typedef struct orbx_keyframe_gate {
+    float F12[9];
+    float ep_x, ep_y;
+    int coarse;
+    int strict_fp;
+    int nlevels;
+    const float *level_sigma2_2;   /* pKF2->mvLevelSigma2 [nlevels] */
+} orbx_keyframe_gate;
+int orbx_keyframe_search_for_triangulation(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                           int check_orientation, const orbx_keyframe_gate *gate, int32_t *matches12);
 
 /* Frame::ComputeStereoMatches (Frame.cc:811-981) for every frame of two resident batches: `left` and `right` must have
  * extracted batches of the same size and image shape (rectified stereo, lapping {0,0}).  Row-band Hamming match, 11x11

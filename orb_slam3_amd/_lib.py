@@ -127,6 +127,13 @@ class FuseQueries(C.Structure):
 
 MAX_FUSE_KEYFRAMES = 256   # ORBX_MAX_FUSE_KEYFRAMES
 
+
+class KeyFrameGate(C.Structure):
+    """orbx_keyframe_gate: what orbx_keyframe_search_for_triangulation needs beyond the two resident key frames."""
+    _fields_ = [("F12", C.c_float * 9), ("ep_x", C.c_float), ("ep_y", C.c_float), ("coarse", C.c_int), ("strict_fp", C.c_int), ("nlevels", C.c_int),
+                ("level_sigma2_2", C.c_void_p)]
+
+
 PAIR_PREDICATE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
 _lib = None
@@ -156,6 +163,8 @@ SYMBOLS = [
     "orbx_frame_compute_bow_fisheye", "orbx_frame_search_by_bow_fisheye", "orbx_frame_search_by_projection_window_fisheye",
     "orbx_keyframe_from_frame", "orbx_keyframe_create_host", "orbx_keyframe_count", "orbx_keyframe_destroy", "orbx_keyframe_fuse_search",
     "orbx_keyframe_fuse_map_points",
+    "orbx_keyframe_compute_bow", "orbx_keyframe_bow_from_frame", "orbx_frame_search_by_bow_resident", "orbx_keyframe_search_by_bow",
+    "orbx_keyframe_search_for_triangulation",
 ]
 
 
@@ -277,6 +286,11 @@ def lib() -> C.CDLL:
     L.orbx_keyframe_fuse_search.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(FuseQueries), i32, i32, C.POINTER(vp), C.POINTER(vp)]
     L.orbx_keyframe_fuse_map_points.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(Camera), C.POINTER(FramePose), f32, f32, i32, i32, vp, vp, vp, vp, vp,
                                                 vp, vp, vp, vp]
+    L.orbx_keyframe_compute_bow.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.orbx_keyframe_bow_from_frame.argtypes = [vp, vp, vp]
+    L.orbx_frame_search_by_bow_resident.argtypes = [vp, vp, i32, C.POINTER(vp), C.POINTER(vp), f32, i32, vp, i32, vp]
+    L.orbx_keyframe_search_by_bow.argtypes = [vp, vp, vp, i32, C.POINTER(vp), C.POINTER(vp), f32, i32, vp, i32, vp]
+    L.orbx_keyframe_search_for_triangulation.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(KeyFrameGate), vp]
     L.orbx_frame_search_by_projection_mappoints_fisheye.argtypes = [vp, vp, vp, i32] + [vp] * 12 + [f32, f32, vp]
     L.orbx_frame_search_by_projection_frame_fisheye.argtypes = [vp, vp, vp, i32] + [vp] * 8 + [f32, i32, i32, vp]
     L.orbx_frame_search_local_points_fisheye.argtypes = [vp, vp, vp, vp, f32, f32, i32] + [vp] * 8 + [f32, f32, i32, f32, vp, vp]

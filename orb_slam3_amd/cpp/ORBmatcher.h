@@ -119,6 +119,15 @@ public:
         if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_count: ") + orbx_status_string(st));
         return n;
     }
+    // KeyFrame::ComputeBoW on the resident descriptors (orbx_keyframe_compute_bow): the key frame keeps mFeatVec for the resident SearchByBoW /
+    // SearchForTriangulation overloads of ORBmatcher.  Set once; a second call with the same vocabulary and levelsup only returns the ids.  wordId /
+    // nodeId (optional) receive N ids each -- mBowVec is folded from the word ids on the host.  Order this call before any BoW search is handed the
+    // key frame (include/orbx.h, SHARING).
+    inline void ComputeBoW(ORBmatcher &matcher, const ORBVocabularyDevice &voc, int levelsup = 4, std::vector<int32_t> *wordId = nullptr,
+                           std::vector<int32_t> *nodeId = nullptr);
+    // the mBowVec(F.mBowVec), mFeatVec(F.mFeatVec) part of KeyFrame::KeyFrame(Frame&) (orbx_keyframe_bow_from_frame): a device-to-device copy from the
+    // DeviceFrame this key frame was made from, after its ComputeBoW and before its next load; asynchronous
+    inline void BowFromFrame(ORBmatcher &matcher, DeviceFrame &frame);
     orbx_keyframe *handle() const { return kf_; }
 
 private:
@@ -383,6 +392,70 @@ public:
         int total = 0;
         for (int k = 0; k < nkf; k++) {
             vpMatch[k].assign(rows.begin() + (size_t)k * stride, rows.begin() + (size_t)k * stride + N);
+            total += nmatches[k];
+        }
+        return total;
+    }
+    // SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (ORBmatcher.cc:223-425) against resident key frames that carry BoW
+    // (orbx_frame_search_by_bow_resident): only valid[k] (GetMapPointMatches()[i] present and !isBad(); an empty vector = all) and one record per
+    // key frame are uploaded.  vpMatch[k][iF] = feature of key frame k or -1, nmatches[k] = the member's return value.  Returns the sum.
+    int SearchByBoW(DeviceFrame &F, const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<std::vector<uint8_t>> &valid, std::vector<int32_t> &nmatches,
+                    std::vector<std::vector<int32_t>> &vpMatch) {
+        const size_t K = vpKFs.size();
+        if (!valid.empty() && valid.size() != K) throw std::invalid_argument("SearchByBoW: one valid mask per key frame (or none at all)");
+        std::vector<orbx_keyframe *> h(K);
+        std::vector<const uint8_t *> fl(K, nullptr);
+        for (size_t k = 0; k < K; k++) {
+            h[k] = vpKFs[k]->handle();
+            if (!valid.empty() && !valid[k].empty()) fl[k] = valid[k].data();
+        }
+        const int N = F.count(), stride = std::max(N, 1);
+        std::vector<int32_t> rows(std::max<size_t>(K, 1) * stride, -1);
+        nmatches.assign(K, 0);
+        const int r = orbx_frame_search_by_bow_resident(m_, F.handle(), (int)K, h.data(), fl.data(), mfNNratio, mbCheckOrientation ? 1 : 0, rows.data(), stride,
+                                                        nmatches.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_by_bow_resident: ") + orbx_status_string(r) + " " + orbx_last_error());
+        return splitRows(rows, stride, N, nmatches, vpMatch);
+    }
+    // SearchByBoW(pKF1, pKF2, vpMatches12) (ORBmatcher.cc:765-905) for KF1 against every key frame of vpKFs2 in one call (orbx_keyframe_search_by_bow;
+    // LoopClosing::DetectCommonRegionsFromBoW's loop over a candidate's covisible key frames): vpMatches12[k][i1] = feature of vpKFs2[k] or -1.
+    int SearchByBoW(DeviceKeyFrame &KF1, const std::vector<uint8_t> &valid1, const std::vector<DeviceKeyFrame *> &vpKFs2,
+                    const std::vector<std::vector<uint8_t>> &valid2, std::vector<int32_t> &nmatches, std::vector<std::vector<int32_t>> &vpMatches12) {
+        const size_t K = vpKFs2.size();
+        if (!valid2.empty() && valid2.size() != K) throw std::invalid_argument("SearchByBoW: one valid mask per key frame (or none at all)");
+        std::vector<orbx_keyframe *> h(K);
+        std::vector<const uint8_t *> fl(K, nullptr);
+        for (size_t k = 0; k < K; k++) {
+            h[k] = vpKFs2[k]->handle();
+            if (!valid2.empty() && !valid2[k].empty()) fl[k] = valid2[k].data();
+        }
+        const int N1 = KF1.count(), stride = std::max(N1, 1);
+        std::vector<int32_t> rows(std::max<size_t>(K, 1) * stride, -1);
+        nmatches.assign(K, 0);
+        const int r = orbx_keyframe_search_by_bow(m_, KF1.handle(), valid1.empty() ? nullptr : valid1.data(), (int)K, h.data(), fl.data(), mfNNratio,
+                                                  mbCheckOrientation ? 1 : 0, rows.data(), stride, nmatches.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_search_by_bow: ") + orbx_status_string(r) + " " + orbx_last_error());
+        return splitRows(rows, stride, N1, nmatches, vpMatches12);
+    }
+    // SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse) (ORBmatcher.cc:907-1146) between two resident pinhole key frames with both
+    // gates on the device (orbx_keyframe_search_for_triangulation): skip1 / skip2 (empty = none) as the host-pointer overloads take them, `gate` = F12,
+    // the epipole, bCoarse and pKF2->mvLevelSigma2; everything else is the key frames' own.  One call per neighbour, as CreateNewMapPoints makes them.
+    int SearchForTriangulation(DeviceKeyFrame &KF1, DeviceKeyFrame &KF2, const std::vector<uint8_t> &skip1, const std::vector<uint8_t> &skip2,
+                               const orbx_keyframe_gate &gate, std::vector<std::pair<size_t, size_t>> &vMatchedPairs) {
+        const int n1 = KF1.count();
+        std::vector<int32_t> m12((size_t)std::max(n1, 1), -1);
+        const int r = orbx_keyframe_search_for_triangulation(m_, KF1.handle(), KF2.handle(), skip1.empty() ? nullptr : skip1.data(),
+                                                             skip2.empty() ? nullptr : skip2.data(), mbCheckOrientation ? 1 : 0, &gate, m12.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_search_for_triangulation: ") + orbx_status_string(r) + " " + orbx_last_error());
+        vMatchedPairs.clear();
+        for (int i = 0; i < n1; i++) if (m12[i] >= 0) vMatchedPairs.emplace_back((size_t)i, (size_t)m12[i]);  // :1138-1143
+        return r;
+    }
+    static int splitRows(const std::vector<int32_t> &rows, int stride, int n, const std::vector<int32_t> &nmatches, std::vector<std::vector<int32_t>> &out) {
+        out.assign(nmatches.size(), std::vector<int32_t>());
+        int total = 0;
+        for (size_t k = 0; k < nmatches.size(); k++) {
+            out[k].assign(rows.begin() + k * (size_t)stride, rows.begin() + k * (size_t)stride + n);
             total += nmatches[k];
         }
         return total;
@@ -701,6 +774,25 @@ inline void DeviceFrame::ComputeBoWFisheye(ORBmatcher &matcher, const ORBVocabul
     const int n = count();   // known after the call
     if (wordId) wordId->assign(w.begin(), w.begin() + n);
     if (nodeId) nodeId->assign(nd.begin(), nd.begin() + n);
+}
+
+inline void DeviceKeyFrame::ComputeBoW(ORBmatcher &matcher, const ORBVocabularyDevice &voc, int levelsup, std::vector<int32_t> *wordId,
+                                       std::vector<int32_t> *nodeId) {
+    auto check = [](int st) { if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_compute_bow: ") + orbx_status_string(st) + " " + orbx_last_error()); };
+    if (!wordId && !nodeId) {
+        check(orbx_keyframe_compute_bow(matcher.handle(), kf_, voc.handle(), levelsup, nullptr, nullptr));
+        return;
+    }
+    const int n = count();   // (the id buffers hold N entries)
+    std::vector<int32_t> w((size_t)std::max(n, 1)), nd((size_t)std::max(n, 1));
+    check(orbx_keyframe_compute_bow(matcher.handle(), kf_, voc.handle(), levelsup, w.data(), nd.data()));
+    if (wordId) wordId->assign(w.begin(), w.begin() + n);
+    if (nodeId) nodeId->assign(nd.begin(), nd.begin() + n);
+}
+
+inline void DeviceKeyFrame::BowFromFrame(ORBmatcher &matcher, DeviceFrame &frame) {
+    const int st = orbx_keyframe_bow_from_frame(matcher.handle(), kf_, frame.handle());
+    if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_bow_from_frame: ") + orbx_status_string(st) + " " + orbx_last_error());
 }
 
 }  // namespace ORB_SLAM3

@@ -379,6 +379,115 @@ public:
         return nmatches;
     }
 
+    // ---- the BoW-guided members on RESIDENT key frames (DeviceKeyFrame after ComputeBoW / BowFromFrame; KeyFrame::mpDevice in an integrated tree) ----
+    // Each takes the DeviceKeyFrame beside its KeyFrame*, gathers the valid / skip flags with the reference's accessors as the overloads above do, and
+    // uploads nothing else of the key frames.  Monocular / rectified key frames only (NLeft == -1).  Like the Fuse overload on DeviceKeyFrames below,
+    // these compile against the mock types of the test tree but have NOT been run against the compiled reference.
+
+    // Tracking::Relocalization / TrackReferenceKeyFrame: SearchByBoW(vpKFs[k], F, vvpMapPointMatches[k]) (ORBmatcher.cc:223-425) for every candidate in
+    // ONE device call (orbx_frame_search_by_bow_resident); DF after DeviceFrame::ComputeBoW with the key frames' vocabulary and levelsup.
+    void SearchByBoW(const std::vector<KeyFrame *> &vpKFs, const std::vector<DeviceKeyFrame *> &vpDeviceKFs, Frame &F, DeviceFrame &DF,
+                     std::vector<std::vector<MapPoint *>> &vvpMapPointMatches, std::vector<int> &nmatches) {
+        if (F.Nleft != -1) throw std::runtime_error("SearchByBoW(DeviceKeyFrame): monocular / rectified frames only");
+        const size_t nkf = vpKFs.size();
+        if (vpDeviceKFs.size() != nkf) throw std::invalid_argument("SearchByBoW: one DeviceKeyFrame per key frame");
+        std::vector<std::vector<MapPoint *>> vpMPs(nkf);
+        std::vector<std::vector<uint8_t>> valid(nkf);
+        for (size_t k = 0; k < nkf; k++) {
+            if (vpKFs[k]->NLeft != -1) throw std::invalid_argument("SearchByBoW: resident key frames are monocular / rectified");
+            vpMPs[k] = vpKFs[k]->GetMapPointMatches();
+            valid[k].resize(vpMPs[k].size());
+            for (size_t i = 0; i < vpMPs[k].size(); i++) {
+                MapPoint *pMP = vpMPs[k][i];
+                valid[k][i] = (pMP && !pMP->isBad()) ? 1 : 0;                              // :252-256
+            }
+        }
+        std::vector<int32_t> nm;
+        std::vector<std::vector<int32_t>> match;
+        SearchByBoW(DF, vpDeviceKFs, valid, nm, match);
+        vvpMapPointMatches.assign(nkf, std::vector<MapPoint *>(F.N, static_cast<MapPoint *>(NULL)));
+        nmatches.assign(nkf, 0);
+        for (size_t k = 0; k < nkf; k++) {
+            nmatches[k] = nm[k];
+            for (int i = 0; i < F.N && i < (int)match[k].size(); i++)
+                if (match[k][i] >= 0) vvpMapPointMatches[k][i] = vpMPs[k][match[k][i]];   // :329
+        }
+    }
+    int SearchByBoW(KeyFrame *pKF, DeviceKeyFrame *pDeviceKF, Frame &F, DeviceFrame &DF, std::vector<MapPoint *> &vpMapPointMatches) {
+        std::vector<std::vector<MapPoint *>> matches;
+        std::vector<int> nmatches;
+        SearchByBoW(std::vector<KeyFrame *>(1, pKF), std::vector<DeviceKeyFrame *>(1, pDeviceKF), F, DF, matches, nmatches);
+        vpMapPointMatches = matches[0];
+        return nmatches[0];
+    }
+
+    // LoopClosing::DetectCommonRegionsFromBoW: SearchByBoW(pKF1, vpKFs2[k], vvpMatches12[k]) (ORBmatcher.cc:765-905) for the current key frame against
+    // every covisible key frame of a candidate in ONE device call (orbx_keyframe_search_by_bow)
+    void SearchByBoW(KeyFrame *pKF1, DeviceKeyFrame *pDeviceKF1, const std::vector<KeyFrame *> &vpKFs2, const std::vector<DeviceKeyFrame *> &vpDeviceKFs2,
+                     std::vector<std::vector<MapPoint *>> &vvpMatches12, std::vector<int> &nmatches) {
+        const size_t nkf = vpKFs2.size();
+        if (vpDeviceKFs2.size() != nkf) throw std::invalid_argument("SearchByBoW: one DeviceKeyFrame per key frame");
+        if (pKF1->NLeft != -1) throw std::invalid_argument("SearchByBoW: resident key frames are monocular / rectified");
+        const std::vector<MapPoint *> vpMapPoints1 = pKF1->GetMapPointMatches();
+        const int n1 = (int)vpMapPoints1.size();
+        std::vector<uint8_t> v1(n1);
+        for (int i = 0; i < n1; i++) { MapPoint *p = vpMapPoints1[i]; v1[i] = (p && !p->isBad()) ? 1 : 0; }          // :810-815
+        std::vector<std::vector<MapPoint *>> vpMPs2(nkf);
+        std::vector<std::vector<uint8_t>> v2(nkf);
+        for (size_t k = 0; k < nkf; k++) {
+            if (vpKFs2[k]->NLeft != -1) throw std::invalid_argument("SearchByBoW: resident key frames are monocular / rectified");
+            vpMPs2[k] = vpKFs2[k]->GetMapPointMatches();
+            v2[k].resize(vpMPs2[k].size());
+            for (size_t i = 0; i < vpMPs2[k].size(); i++) { MapPoint *p = vpMPs2[k][i]; v2[k][i] = (p && !p->isBad()) ? 1 : 0; }   // :829-834
+        }
+        std::vector<int32_t> nm;
+        std::vector<std::vector<int32_t>> m12;
+        SearchByBoW(*pDeviceKF1, v1, vpDeviceKFs2, v2, nm, m12);
+        vvpMatches12.assign(nkf, std::vector<MapPoint *>(n1, static_cast<MapPoint *>(NULL)));
+        nmatches.assign(nkf, 0);
+        for (size_t k = 0; k < nkf; k++) {
+            nmatches[k] = nm[k];
+            for (int i = 0; i < n1 && i < (int)m12[k].size(); i++)
+                if (m12[k][i] >= 0) vvpMatches12[k][i] = vpMPs2[k][m12[k][i]];            // :861
+        }
+    }
+
+    // LocalMapping::CreateNewMapPoints: SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse) (ORBmatcher.cc:907-1146) between two
+    // resident PINHOLE key frames (orbx_keyframe_search_for_triangulation): the skip flags, F12 (the Eigen expression of Pinhole.cpp:109-112, as the
+    // overload above builds it), the epipole and pKF2->mvLevelSigma2 are all that goes up.  One call per neighbour, as the reference's loop makes them.
+    int SearchForTriangulation(KeyFrame *pKF1, DeviceKeyFrame *pDeviceKF1, KeyFrame *pKF2, DeviceKeyFrame *pDeviceKF2,
+                               std::vector<std::pair<size_t, size_t>> &vMatchedPairs, const bool bOnlyStereo, const bool bCoarse = false) {
+        GeometricCamera *pCamera1 = pKF1->mpCamera, *pCamera2 = pKF2->mpCamera;
+        if (pKF1->mpCamera2 || pKF2->mpCamera2 || pCamera1->GetType() != GeometricCamera::CAM_PINHOLE || pCamera2->GetType() != GeometricCamera::CAM_PINHOLE)
+            throw std::invalid_argument("SearchForTriangulation(DeviceKeyFrame): pinhole key frames only");
+        Sophus::SE3f T1w = pKF1->GetPose();
+        Sophus::SE3f T2w = pKF2->GetPose();
+        Sophus::SE3f Tw2 = pKF2->GetPoseInverse();
+        Eigen::Vector3f Cw = pKF1->GetCameraCenter();
+        Eigen::Vector3f C2 = T2w * Cw;
+        Eigen::Vector2f ep = pKF2->mpCamera->project(C2);                                // :919-921
+        Sophus::SE3f T12 = T1w * Tw2;
+        Eigen::Matrix3f R12 = T12.rotationMatrix();
+        Eigen::Vector3f t12 = T12.translation();
+        const int n1 = pKF1->N, n2 = pKF2->N;
+        std::vector<uint8_t> skip1(n1), skip2(n2);
+        for (int i = 0; i < n1; i++) skip1[i] = (pKF1->GetMapPoint(i) || (bOnlyStereo && !(pKF1->mvuRight[i] >= 0))) ? 1 : 0;   // :971-983
+        for (int i = 0; i < n2; i++) skip2[i] = (pKF2->GetMapPoint(i) || (bOnlyStereo && !(pKF2->mvuRight[i] >= 0))) ? 1 : 0;   // :1002-1012
+        Eigen::Matrix3f t12x = Sophus::SO3f::hat(t12);                                   // Pinhole.cpp:109
+        Eigen::Matrix3f K1 = pCamera1->toK_();                                           // :110
+        Eigen::Matrix3f K2 = pCamera2->toK_();                                           // :111
+        Eigen::Matrix3f F12 = K1.transpose().inverse() * t12x * R12 * K2.inverse();      // :112
+        orbx_keyframe_gate g;
+        std::memset(&g, 0, sizeof(g));
+        for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) g.F12[3 * r + c] = F12(r, c);
+        g.ep_x = ep(0); g.ep_y = ep(1);
+        g.coarse = bCoarse ? 1 : 0;
+        g.strict_fp = 0;
+        g.nlevels = (int)pKF2->mvLevelSigma2.size();
+        g.level_sigma2_2 = pKF2->mvLevelSigma2.data();                                   // `unc` of :1072
+        return SearchForTriangulation(*pDeviceKF1, *pDeviceKF2, skip1, skip2, g, vMatchedPairs);
+    }
+
     // ORBmatcher.cc:2058-2074 on the reference's argument type
     static int DescriptorDistance(const cv::Mat &a, const cv::Mat &b) { return DescriptorDistance((const uint8_t *)a.data, (const uint8_t *)b.data); }
 

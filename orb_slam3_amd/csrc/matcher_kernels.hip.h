@@ -3309,6 +3309,71 @@ __global__ __launch_bounds__(256) void k_replay_bow_batch(const BowProblem *__re
 __global__ __launch_bounds__(64) void k_replay_bow_finish_batch(const BowProblem *__restrict__ probs) { replay_bow_finish(probs[blockIdx.x]); }
 
 // ---------------------------------------------------------------------------------------------------------
+// BoW searches whose BOTH sides are resident (orbx_frame_search_by_bow_resident, orbx_keyframe_search_by_bow,
+// orbx_keyframe_search_for_triangulation): a key frame that carries its FeatureVector against the frame handle or against other such key frames.
+//
+// k_bow_pair_resident: k_bow_pair_nodes with blockIdx.y = problem.  Neither node count has to be on the host: the A side's comes from its
+// FeatureVector's meta (a key frame made from a batch-loaded frame nobody counted), the B side differs per problem (key frame against key frames).
+// Lane t of problem k pairs node t of A with B's ascending node list by binary search (= the merge-join of :246-250, :800-805, :961-965 for strictly
+// ascending lists) and writes pair[t]; lane 0 also PATCHES the problem record -- fa.n_nodes / fb.n_nodes, which the host left 0 -- and copies the
+// two feature counts next to the match counts, so that a count still on the device comes back in the call's one download run.  The replay is
+// launched behind this kernel and reads the patched record; its waves beyond the real node count exit (replay_bow_wave).
+// grid (ceil(max bound_a / 256), n_problems), block 256; bound_a = the host's bound on A's node count (pair[] holds that many entries)
+// ---------------------------------------------------------------------------------------------------------
+struct BowPairSrc {
+    const uint32_t *node_a, *node_b;     // ascending node ids of the two FeatureVectors
+    const int32_t *meta_a, *meta_b;      // [0] = node count (k_frame_featvec's fv_meta)
+    const int32_t *count_a, *count_b;    // the sides' feature counts on the device
+    int32_t *pair;                       // out [bound_a] = the problem's BowProblem::pair_b
+    int32_t *counts_out;                 // out [2]
+    int bound_a, cap_a, cap_b;
+};
+__global__ __launch_bounds__(256) void k_bow_pair_resident(BowProblem *__restrict__ probs, const BowPairSrc *__restrict__ srcs) {
+    const BowPairSrc &S = srcs[blockIdx.y];
+    const int t = (int)(blockIdx.x * 256 + threadIdx.x);
+    const int na = min(max(S.meta_a[0], 0), S.bound_a), nb = max(S.meta_b[0], 0);
+    if (t == 0) {
+        probs[blockIdx.y].fa.n_nodes = na;
+        probs[blockIdx.y].fb.n_nodes = nb;
+        S.counts_out[0] = min(max(S.count_a[0], 0), S.cap_a);
+        S.counts_out[1] = min(max(S.count_b[0], 0), S.cap_b);
+    }
+    if (t >= na) return;
+    const uint32_t id = S.node_a[t];
+    int lo = 0, hi = nb;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (S.node_b[mid] < id) lo = mid + 1;
+        else hi = mid;
+    }
+    S.pair[t] = (lo < nb && S.node_b[lo] == id) ? lo : -1;
+}
+
+// k_keyframe_bow_copy: the mBowVec(F.mBowVec), mFeatVec(F.mFeatVec) part of KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-82) on the device
+// (orbx_keyframe_bow_from_frame): the frame handle's per-feature ids, angles and FeatureVector into the key frame's BoW allocation.  N is n_host or
+// the frame's count read on the device; only what k_frame_featvec wrote is read (node_count nodes, `kept` indices).
+// grid ceil((cap + 1) / 256), block 256
+struct KeyFrameBowCopy {
+    const int32_t *src_count; int n_host, cap;
+    const int32_t *src_word, *src_node, *src_ptr, *src_index, *src_meta;
+    const uint32_t *src_fv_node;
+    const float *src_angle;
+    int32_t *word, *node, *ptr, *index, *meta;
+    uint32_t *fv_node;
+    float *angle;
+};
+__global__ __launch_bounds__(256) void k_keyframe_bow_copy(const KeyFrameBowCopy C) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    const int n = C.n_host >= 0 ? min(C.n_host, C.cap) : min(max(C.src_count[0], 0), C.cap);
+    const int nn = min(max(C.src_meta[0], 0), n), kept = min(max(C.src_meta[1], 0), n);
+    if (i == 0) { C.meta[0] = nn; C.meta[1] = kept; }
+    if (i < n) { C.word[i] = C.src_word[i]; C.node[i] = C.src_node[i]; C.angle[i] = C.src_angle[i]; }
+    if (i < nn) C.fv_node[i] = C.src_fv_node[i];
+    if (i <= nn) C.ptr[i] = C.src_ptr[i];
+    if (i < kept) C.index[i] = C.src_index[i];
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // k_tri_kb8_stereo: the per-query loop of Frame::ComputeStereoFishEyeMatches (Frame.cc:1147-1163) behind k_knn2, a LANE per left feature (the
 // gate is ~10^4 instructions per pair: a wave per query would leave 63 lanes idle).  Lane iL of frame f = blockIdx.y writes the frame's left outputs
 // over the WHOLE frame (:1134-1138: l2r = -1, depth = -1, p3d = 0 unless accepted); a lapping query (iL >= mono_left) with two neighbours passes Lowe's

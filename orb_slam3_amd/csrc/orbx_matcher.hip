@@ -288,6 +288,11 @@ struct orbx_vocabulary {
     int max_word = -1;                 // the largest word id of the tree
     uint8_t *word_pos = nullptr;       // [n_words] m_words[id]->weight > 0 (orbx_vocabulary_set_word_weights); NULL: no word is stopped
     int n_words = 0;
+    std::vector<int> depth_nodes;      // nodes at depth d of the tree (root: depth 0), counted once at creation: the host's bound on a FeatureVector's node count
+    int node_bound(int levelsup) const {   // node ids of TemplatedVocabulary::transform at level L - levelsup: the nodes of that depth, or node 0 (a leaf above it / a level <= 0)
+        const int d = L - levelsup;
+        return 1 + ((d > 0 && d < (int)depth_nodes.size()) ? depth_nodes[(size_t)d] : 0);
+    }
 };
 
 extern "C" {
@@ -573,6 +578,7 @@ struct orbx_frame {
     uint32_t *fv_node = nullptr;
     float *angle = nullptr;
     bool bow_valid = false;
+    uint64_t load_seq = 0;            // loads so far: orbx_keyframe_from_frame remembers (handle, load_seq) for orbx_keyframe_bow_from_frame
     std::vector<int32_t> h_bow;       // [2 cap]: word / node ids downloaded while N was still on the device
     const orbx_vocabulary *bow_voc = nullptr;
     int bow_levelsup = 0;
@@ -910,7 +916,7 @@ int orbx_frame_load_host(orbx_frame *f, const orbx_frame_desc *d) {
     ORBX_HIP(hipGetLastError());
     ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
     f->stage_busy = true;
-    f->n = n; f->n_known = true; f->has_ur = d->u_right != nullptr; f->loaded = true; f->bow_valid = false;
+    f->n = n; f->n_known = true; f->has_ur = d->u_right != nullptr; f->loaded = true; f->bow_valid = false; f->load_seq++;
     f->fisheye = false; f->n_right = -1;
     return ORBX_OK;
 }
@@ -938,7 +944,7 @@ int orbx_frame_load_batch(orbx_frame *f, orbx_extractor *ex, int frame, const fl
     ORBX_HIP(hipGetLastError());
     ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
     ORBX_HIP(hipStreamWaitEvent(ex->stream, f->ev_done, 0));
-    f->n_known = false; f->has_ur = false; f->loaded = true; f->bow_valid = false;
+    f->n_known = false; f->has_ur = false; f->loaded = true; f->bow_valid = false; f->load_seq++;
     f->fisheye = false; f->n_right = -1;
     return ORBX_OK;
 }
@@ -2403,6 +2409,19 @@ extern "C" int orbx_vocabulary_create(int device, int L, int n_nodes, const int3
     ORBX_HIP(hipMemcpy(v->word_id, word_id, 4 * (size_t)n_nodes, hipMemcpyHostToDevice));
     ORBX_HIP(hipMemcpy(v->node_desc, node_desc, 32 * (size_t)n_nodes, hipMemcpyHostToDevice));
     for (int i = 0; i < n_nodes; i++) v->max_word = std::max(v->max_word, (int)word_id[i]);
+    {   // nodes per depth, breadth first from the root (a malformed tree's cycles end at n_nodes visits)
+        std::vector<int> cur{0}, next;
+        size_t seen = 0;
+        while (!cur.empty() && seen <= (size_t)n_nodes) {
+            v->depth_nodes.push_back((int)cur.size());
+            seen += cur.size();
+            next.clear();
+            for (int nd : cur)
+                if (nd >= 0 && nd < n_nodes)
+                    for (int c = child_ptr[nd]; c < child_ptr[nd + 1] && next.size() <= (size_t)n_nodes; c++) next.push_back(child_idx[c]);
+            cur.swap(next);
+        }
+    }
     *out = v;
     return ORBX_OK;
 }
@@ -2812,6 +2831,21 @@ extern "C" int orbx_fuse_search(orbx_matcher *m, const orbx_frame_desc *kf, cons
 // Device-resident key frames (include/orbx.h, orbx_keyframe): what KeyFrame::KeyFrame(Frame&) copies of the frame -- immutable from then on, in ONE
 // allocation of its own, readable by every matcher context of its device -- and ORBmatcher::Fuse for K of them in one call.
 // ---------------------------------------------------------------------------------------------------------
+// The BoW state of a key frame (orbx_keyframe_compute_bow / orbx_keyframe_bow_from_frame): a SECOND allocation, made when BoW is first attached -- key
+// frames without it keep their size.  Set once, immutable afterwards; guarded as the rows are (an event behind its creation, a done flag).
+struct KeyFrameBow {
+    uint8_t *dev = nullptr;            // one allocation, carved below
+    int32_t *word = nullptr, *node = nullptr;          // per-feature WordId / NodeId
+    float *angle = nullptr;                            // mvKeysUn[i].angle
+    uint32_t *fv_node = nullptr;                       // the FeatureVector as k_frame_featvec writes it: ascending node ids,
+    int32_t *fv_ptr = nullptr, *fv_index = nullptr;    //   the CSR and the indices in std::map / addFeature order (stopped words dropped),
+    int32_t *fv_meta = nullptr;                        //   {node count, features kept}
+    const orbx_vocabulary *voc = nullptr;
+    int levelsup = 0;
+    hipEvent_t ready = nullptr;
+    std::atomic<bool> done{false};
+};
+
 struct orbx_keyframe {
     int device = 0;
     uint8_t *dev = nullptr;            // one allocation, carved below
@@ -2827,9 +2861,19 @@ struct orbx_keyframe {
     std::atomic<int> n{-1};            // N; -1 while it is known on the device only (made from a batch-loaded frame)
     int cap = 0, nlevels = 0;
     float bounds[4] = {0, 0, 0, 0};
+    std::atomic<KeyFrameBow *> bow{nullptr};   // NULL: no BoW attached (yet)
+    const orbx_frame *src_frame = nullptr;     // orbx_keyframe_from_frame: the handle and its load counter at the copy
+    uint64_t src_seq = 0;
 };
 
 namespace {
+
+void keyframe_bow_free(KeyFrameBow *b) {
+    if (!b) return;
+    if (b->ready) { (void)hipEventSynchronize(b->ready); (void)hipEventDestroy(b->ready); }
+    if (b->dev) (void)hipFree(b->dev);
+    delete b;
+}
 
 // one allocation per key frame: rows for `cap` features (28 + 32 [+ 4] + 2 bytes each), the per-level arrays, the count and the grid's 3073 cell offsets
 int keyframe_alloc(int device, int cap, bool has_ur, bool has_sigma, int nlevels, const float *bounds4, orbx_keyframe **out) {
@@ -2892,6 +2936,7 @@ void orbx_keyframe_destroy(orbx_keyframe *kf) {
     if (!kf) return;
     (void)hipSetDevice(kf->device);
     if (kf->ready) { (void)hipEventSynchronize(kf->ready); (void)hipEventDestroy(kf->ready); }   // the copy / upload has run; no search is running (the caller's contract)
+    keyframe_bow_free(kf->bow.load());
     if (kf->dev) (void)hipFree(kf->dev);
     delete kf;
 }
@@ -2971,6 +3016,7 @@ int orbx_keyframe_from_frame(orbx_matcher *m, orbx_frame *f, const float *inv_le
     if (e == hipSuccess) e = hipEventRecord(kf->ready, m->stream);
     if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
     kf->n.store(f->n_known ? f->n : -1);
+    kf->src_frame = f; kf->src_seq = f->load_seq;
     *out = kf;
     return ORBX_OK;
 }
@@ -3124,6 +3170,414 @@ int orbx_keyframe_fuse_map_points(orbx_matcher *m, int n_kf, orbx_keyframe *cons
         best_dist[i] = key == kNoKey ? 256 : (int32_t)(key >> 32);
     }
     return ORBX_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// BoW on resident key frames: KeyFrame::ComputeBoW / the mBowVec, mFeatVec part of KeyFrame::KeyFrame(Frame&), and the three BoW-guided matchers with
+// BOTH sides resident -- SearchByBoW(KeyFrame*, Frame&), SearchByBoW(KeyFrame*, KeyFrame*) and SearchForTriangulation (pinhole gates) -- through one
+// driver (run_bow_resident): only flags and problem records go up.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+
+static_assert(sizeof(BowProblem) + sizeof(BowPairSrc) <= 512, "the per-problem upload of a resident BoW search (tests/test_gpu_keyframe_bow.py bounds it)");
+constexpr int kKeyFrameBowMax = 16384;   // k_frame_featvec sorts 8-byte keys in LDS: 128 KB at most
+
+int keyframe_bow_alloc(int cap, KeyFrameBow **out) {
+    KeyFrameBow *b = new KeyFrameBow();
+    const size_t c = (size_t)std::max(cap, 1);
+    size_t o = 0;
+    auto carve = [&o](size_t bytes) { const size_t r = o; o += Arena::pad(bytes); return r; };
+    const size_t off_w = carve(4 * c), off_n = carve(4 * c), off_a = carve(4 * c), off_fn = carve(4 * c), off_fp = carve(4 * (c + 1)), off_fi = carve(4 * c),
+                 off_m = carve(8);
+    hipError_t e = hipMalloc((void **)&b->dev, o);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&b->ready, hipEventDisableTiming);
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); keyframe_bow_free(b); return ORBX_E_HIP; }
+    b->word = (int32_t *)(b->dev + off_w); b->node = (int32_t *)(b->dev + off_n); b->angle = (float *)(b->dev + off_a);
+    b->fv_node = (uint32_t *)(b->dev + off_fn); b->fv_ptr = (int32_t *)(b->dev + off_fp); b->fv_index = (int32_t *)(b->dev + off_fi);
+    b->fv_meta = (int32_t *)(b->dev + off_m);
+    *out = b;
+    return ORBX_OK;
+}
+
+// the calling context's stream behind the key frame's rows AND its BoW state (each until a call that waited has synchronised)
+inline int keyframe_bow_acquire(orbx_matcher *m, orbx_keyframe *kf) {
+    if (!kf->done.load(std::memory_order_acquire)) ORBX_HIP(hipStreamWaitEvent(m->stream, kf->ready, 0));
+    KeyFrameBow *b = kf->bow.load(std::memory_order_acquire);
+    if (b && !b->done.load(std::memory_order_acquire)) ORBX_HIP(hipStreamWaitEvent(m->stream, b->ready, 0));
+    return ORBX_OK;
+}
+inline void keyframe_bow_release(orbx_keyframe *kf) {   // after the call's synchronisation
+    kf->done.store(true, std::memory_order_release);
+    if (KeyFrameBow *b = kf->bow.load(std::memory_order_acquire)) b->done.store(true, std::memory_order_release);
+}
+
+// One side of a resident BoW problem: a key frame with BoW, or the frame handle.
+struct BowSide {
+    const uint8_t *desc; const float *angle;
+    const uint32_t *fv_node; const int32_t *fv_ptr, *fv_index, *fv_meta, *count;
+    int n;       // N, or -1 while it is on the device only
+    int cap;     // rows the side's arrays hold
+    int bound;   // the host's bound on the FeatureVector's node count
+    int rows() const { return n >= 0 ? n : cap; }
+};
+inline BowSide bow_side(const orbx_keyframe *kf) {
+    const KeyFrameBow *b = kf->bow.load(std::memory_order_acquire);
+    BowSide S;
+    S.desc = kf->desc; S.angle = b->angle; S.fv_node = b->fv_node; S.fv_ptr = b->fv_ptr; S.fv_index = b->fv_index; S.fv_meta = b->fv_meta;
+    S.count = kf->count; S.n = kf->n.load(); S.cap = kf->cap;
+    S.bound = std::min(S.rows(), b->voc->node_bound(b->levelsup));
+    return S;
+}
+inline BowSide bow_side(const orbx_frame *f) {
+    BowSide S;
+    S.desc = f->desc; S.angle = f->angle; S.fv_node = f->fv_node; S.fv_ptr = f->fv_ptr; S.fv_index = f->fv_index; S.fv_meta = f->fv_meta;
+    S.count = f->count; S.n = f->n_known ? f->n : -1; S.cap = f->cap;
+    S.bound = std::min(S.rows(), f->bow_voc->node_bound(f->bow_levelsup));
+    return S;
+}
+
+// The driver of the three resident BoW searches.  Problem k: A[k] against B[k] in `mode` (BowProblem::mode: 0 rows indexed by B's features, 1 / 2 by
+// A's); flags_a[k] / flags_b[k] (arrays may be NULL, entries may be NULL = no feature is switched off) are `valid` flags when invert, else `skip`
+// flags, of A[k].n / B[k].n entries (the callers resolve N before they hand over flags).  The side the rows are indexed by is the same object in
+// every problem.  One upload run (flags, the level table of the gate, the records), k_bow_pair_resident, k_replay_bow_batch,
+// k_replay_bow_finish_batch, one download run (rows, match counts, the sides' counts), one synchronisation -- whatever np is, and with no host
+// synchronisation before the launches.  counts[2 k], counts[2 k + 1] = N of A[k], B[k] as read on the device.
+int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const BowSide *B, const uint8_t *const *flags_a, const uint8_t *const *flags_b,
+                     bool invert, float nnratio, int check_orientation, const TriGate *gate, const float *sigma2_2, int nlevels, int32_t *match,
+                     int match_stride, int32_t *nmatches, std::vector<int32_t> &counts) {
+    const BowSide &O = mode == 0 ? B[0] : A[0];
+    const int nrows = O.rows();
+    size_t need = 16384 + Arena::pad(sizeof(BowProblem) * (size_t)np) + Arena::pad(sizeof(BowPairSrc) * (size_t)np) + Arena::pad(4 * (size_t)np * nrows) +
+                  Arena::pad(4 * (size_t)np) + Arena::pad(8 * (size_t)np) + Arena::pad(4 * (size_t)np * (ORBX_HISTO_LENGTH + 2)) + Arena::pad(4 * 64);
+    size_t tot_bound = 0, tot_nb = 0, n_ent = 0;
+    int max_bound = 1;
+    for (int k = 0; k < np; k++) {
+        const size_t na = (size_t)A[k].rows(), nb = (size_t)B[k].rows();
+        need += Arena::pad(na) + Arena::pad(nb);
+        tot_bound += (size_t)A[k].bound; tot_nb += nb; n_ent += std::max<size_t>(std::max(na, nb), 1);
+        max_bound = std::max(max_bound, A[k].bound);
+    }
+    need += Arena::pad(4 * (tot_bound + 1)) + Arena::pad(tot_nb + 1) + Arena::pad(4 * n_ent);
+    int r = m->reserve_all(need);
+    if (r != ORBX_OK) return r;
+    Arena &Ar = m->arena;
+    m->begin();
+    std::vector<BowProblem> probs((size_t)np);
+    std::vector<BowPairSrc> srcs((size_t)np);
+    std::vector<uint8_t> skip;
+    auto up_flags = [&](const uint8_t *fl, int n, const uint8_t **out) -> int {   // (H2D returns from the enclosing function on failure)
+        *out = nullptr;
+        if (!fl || n <= 0) return ORBX_OK;
+        uint8_t *d = Ar.take<uint8_t>((size_t)n);
+        const uint8_t *src = fl;
+        if (invert) {
+            skip.resize((size_t)n);
+            for (int i = 0; i < n; i++) skip[i] = fl[i] ? 0 : 1;
+            src = skip.data();
+        }
+        H2D(d, src, (size_t)n);
+        *out = d;
+        return ORBX_OK;
+    };
+    // the uploads, side by side: the flags, the gate's level table, the records
+    for (int k = 0; k < np; k++) {
+        BowProblem &P = probs[k];
+        memset(&P, 0, sizeof(P));
+        if ((r = up_flags(flags_a ? flags_a[k] : nullptr, A[k].n, &P.skip_a)) != ORBX_OK) return r;
+        if ((r = up_flags(flags_b ? flags_b[k] : nullptr, B[k].n, &P.skip_b)) != ORBX_OK) return r;
+    }
+    const float *dsig = nullptr;
+    if (gate) {
+        float *p = Ar.take<float>((size_t)nlevels);
+        H2D(p, sigma2_2, 4 * (size_t)nlevels);
+        dsig = p;
+    }
+    BowProblem *dP = Ar.take<BowProblem>(np);
+    BowPairSrc *dS = Ar.take<BowPairSrc>(np);
+    // device-only: the pairing; rows (filled with -1), match counts and the sides' counts side by side (one download run); vbMatched2, histograms +
+    // counters (zeroed by one fill); entries
+    int32_t *dpair = Ar.take<int32_t>(tot_bound + 1);
+    int32_t *dmatch = Ar.take<int32_t>((size_t)np * nrows);
+    int32_t *dnm = Ar.take<int32_t>(np);
+    int32_t *dcnt = Ar.take<int32_t>(2 * (size_t)np);
+    uint8_t *dtaken = Ar.take<uint8_t>(tot_nb + 1);
+    int32_t *dhist = Ar.take<int32_t>((size_t)np * (ORBX_HISTO_LENGTH + 2));
+    int32_t *dent = Ar.take<int32_t>(n_ent);
+    {
+        size_t op = 0, ot = 0, oe = 0;
+        for (int k = 0; k < np; k++) {
+            BowProblem &P = probs[k];
+            const BowSide &a = A[k], &b = B[k];
+            P.mode = mode;
+            if (gate) { P.gate = *gate; P.gate.sigma2_2 = dsig; }
+            P.fa.node_id = a.fv_node; P.fa.node_ptr = a.fv_ptr; P.fa.index = a.fv_index; P.fa.n_nodes = 0;   // (both node counts: k_bow_pair_resident)
+            P.fb.node_id = b.fv_node; P.fb.node_ptr = b.fv_ptr; P.fb.index = b.fv_index; P.fb.n_nodes = 0;
+            P.desc_a = a.desc; P.angle_a = a.angle; P.na = a.rows();
+            P.desc_b = b.desc; P.angle_b = b.angle; P.nb = b.rows();
+            P.nnratio = nnratio; P.check_orientation = check_orientation ? 1 : 0;
+            P.match = dmatch + (size_t)k * nrows; P.nmatches = dnm + k;
+            P.taken_b = dtaken + ot;
+            P.hist = dhist + (size_t)k * (ORBX_HISTO_LENGTH + 2); P.counters = P.hist + ORBX_HISTO_LENGTH;
+            P.entries = dent + oe;
+            P.pair_b = dpair + op;
+            BowPairSrc &S = srcs[k];
+            memset(&S, 0, sizeof(S));
+            S.node_a = a.fv_node; S.node_b = b.fv_node; S.meta_a = a.fv_meta; S.meta_b = b.fv_meta; S.count_a = a.count; S.count_b = b.count;
+            S.pair = dpair + op; S.counts_out = dcnt + 2 * (size_t)k; S.bound_a = a.bound; S.cap_a = a.cap; S.cap_b = b.cap;
+            op += (size_t)a.bound; ot += (size_t)b.rows(); oe += std::max<size_t>(std::max((size_t)a.rows(), (size_t)b.rows()), 1);
+        }
+    }
+    H2D(dP, probs.data(), sizeof(BowProblem) * (size_t)np);
+    H2D(dS, srcs.data(), sizeof(BowPairSrc) * (size_t)np);
+    ORBX_HIP(m->fill(dmatch, 0xff, 4 * (size_t)np * nrows));
+    ORBX_HIP(m->fill(dtaken, 0, (size_t)((const uint8_t *)(dhist + (size_t)np * (ORBX_HISTO_LENGTH + 2)) - dtaken)));   // vbMatched2, (padding,) histograms + counters
+    hipLaunchKernelGGL(k_bow_pair_resident, dim3((unsigned)((max_bound + 255) / 256), (unsigned)np), dim3(256), 0, m->exec(), dP, (const BowPairSrc *)dS);
+    hipLaunchKernelGGL(k_replay_bow_batch, dim3((unsigned)((max_bound + 3) / 4), (unsigned)np), dim3(256), 0, m->exec(), (const BowProblem *)dP);
+    hipLaunchKernelGGL(k_replay_bow_finish_batch, dim3((unsigned)np), dim3(64), 0, m->exec(), (const BowProblem *)dP);
+    ORBX_HIP(hipGetLastError());
+    std::vector<int32_t> rows;
+    if (O.n >= 0) {
+        for (int k = 0; k < np; k++) D2H(match + (size_t)k * match_stride, dmatch + (size_t)k * nrows, 4 * (size_t)O.n);
+    } else if (nrows > 0) {   // N comes back with the results
+        rows.resize((size_t)np * nrows);
+        D2H(rows.data(), dmatch, 4 * (size_t)np * nrows);
+    }
+    counts.assign(2 * (size_t)np, 0);
+    D2H(nmatches, dnm, 4 * (size_t)np);
+    D2H(counts.data(), dcnt, 8 * (size_t)np);
+    SYNC_AND_DELIVER();
+    if (O.n < 0) {
+        const int n = std::min(std::max(counts[mode == 0 ? 1 : 0], 0), O.cap);
+        for (int k = 0; k < np; k++)
+            if (n > 0) memcpy(match + (size_t)k * match_stride, rows.data() + (size_t)k * nrows, 4 * (size_t)n);
+    }
+    return ORBX_OK;
+}
+
+// a key frame a BoW search may take: on this device, with BoW; the vocabulary and levelsup it was made with come back for the cross-check
+inline bool keyframe_bow_ok(const orbx_matcher *m, const orbx_keyframe *kf, const orbx_vocabulary **voc, int *levelsup) {
+    if (!kf || kf->device != m->device) return false;
+    const KeyFrameBow *b = kf->bow.load(std::memory_order_acquire);
+    if (!b) return false;
+    if (*voc && (*voc != b->voc || *levelsup != b->levelsup)) return false;
+    *voc = b->voc; *levelsup = b->levelsup;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+// KeyFrame::ComputeBoW (KeyFrame.cc; the transform of Frame.cc:738-745) on the key frame's own descriptors.  The kernels are the FRAME's
+// (k_frame_bow_transform, k_frame_featvec): they take every array as an argument, so they run on the key frame's rows as they are -- no new code object,
+// no existing kernel's ISA touched.
+int orbx_keyframe_compute_bow(orbx_matcher *m, orbx_keyframe *kf, const orbx_vocabulary *v, int levelsup, int32_t *word_id, int32_t *node_id) {
+    if (!m || !kf || !v || kf->device != m->device || v->device != m->device) return ORBX_E_BAD_ARG;
+    KeyFrameBow *b = kf->bow.load(std::memory_order_acquire);
+    const bool down = word_id || node_id;
+    if (b) {   // `if (mBowVec.empty() || mFeatVec.empty())`: not computed again
+        if (b->voc != v || b->levelsup != levelsup) return ORBX_E_BAD_ARG;
+        if (!down) return ORBX_OK;
+    }
+    const int n_host = kf->n.load();
+    const int nc = n_host >= 0 ? n_host : kf->cap;   // features the kernels may see
+    if (nc > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;
+    ORBX_HIP(hipSetDevice(m->device));
+    int r = m->reserve_all(Arena::pad(8 * (size_t)nc) + 4096);
+    if (r != ORBX_OK) return r;
+    m->begin();
+    if (!b) {
+        if ((r = keyframe_bow_alloc(kf->cap, &b)) != ORBX_OK) return r;
+        b->voc = v; b->levelsup = levelsup;
+        int sort_cap = 1;
+        while (sort_cap < nc) sort_cap <<= 1;
+        const size_t lds = 8 * (size_t)sort_cap;
+        hipError_t e = hipSuccess;
+        if (!kf->done.load(std::memory_order_acquire)) e = hipStreamWaitEvent(m->stream, kf->ready, 0);
+        if (e == hipSuccess && lds > 64 * 1024) e = hipFuncSetAttribute((const void *)k_frame_featvec, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e == hipSuccess) {
+            m->dirty = true;
+            if (nc > 0)
+                hipLaunchKernelGGL(k_frame_bow_transform, dim3((nc + 15) / 16), dim3(256), 0, m->stream, v->child_ptr, v->child_idx, v->node_desc, v->word_id,
+                                   v->L, levelsup, kf->desc, kf->count, n_host, kf->cap, b->word, b->node);
+            FrameBow B;
+            memset(&B, 0, sizeof(B));
+            B.count = kf->count; B.n_host = n_host; B.cap = kf->cap; B.kps = kf->kps; B.word = b->word; B.node = b->node;
+            B.word_pos = v->word_pos; B.n_words = v->n_words;
+            B.angle = b->angle; B.fv_node = b->fv_node; B.fv_ptr = b->fv_ptr; B.fv_index = b->fv_index; B.fv_meta = b->fv_meta;
+            hipLaunchKernelGGL(k_frame_featvec, dim3(1), dim3(1024), lds, m->stream, B, sort_cap);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipEventRecord(b->ready, m->stream);
+        if (e != hipSuccess) { set_error(hipGetErrorString(e)); (void)hipStreamSynchronize(m->stream); m->dirty = false; keyframe_bow_free(b); return ORBX_E_HIP; }
+        kf->bow.store(b, std::memory_order_release);
+    } else {
+        r = keyframe_bow_acquire(m, kf);
+        if (r != ORBX_OK) return r;
+    }
+    if (!down || nc == 0) return ORBX_OK;
+    std::vector<int32_t> h;
+    int32_t cnt = n_host;
+    if (n_host >= 0) {
+        if (word_id) D2H(word_id, b->word, 4 * (size_t)nc);
+        if (node_id) D2H(node_id, b->node, 4 * (size_t)nc);
+    } else {   // N comes back with the ids
+        h.resize(2 * (size_t)nc);
+        D2H(h.data(), b->word, 4 * (size_t)nc);
+        D2H(h.data() + nc, b->node, 4 * (size_t)nc);
+        D2H(&cnt, kf->count, 4);
+    }
+    SYNC_AND_DELIVER();
+    keyframe_bow_release(kf);
+    if (n_host < 0) {
+        cnt = std::min(std::max(cnt, 0), kf->cap);
+        kf->n.store(cnt);
+        if (word_id) memcpy(word_id, h.data(), 4 * (size_t)cnt);
+        if (node_id) memcpy(node_id, h.data() + nc, 4 * (size_t)cnt);
+    }
+    return ORBX_OK;
+}
+
+// mBowVec(F.mBowVec), mFeatVec(F.mFeatVec) of KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-82): k_keyframe_bow_copy on the owner's stream, behind the
+// frame's orbx_frame_compute_bow and ahead of its next load; no host synchronisation.
+int orbx_keyframe_bow_from_frame(orbx_matcher *m, orbx_keyframe *kf, orbx_frame *f) {
+    if (!m || !kf || !f || f->owner != m || f->fisheye || kf->device != m->device || kf->src_frame != f) return ORBX_E_BAD_ARG;
+    if (kf->bow.load(std::memory_order_acquire)) return ORBX_E_BAD_ARG;   // set once
+    if (f->load_seq != kf->src_seq) return ORBX_E_STALE;                  // the handle holds another frame by now
+    if (!f->bow_valid) return ORBX_E_BAD_ARG;
+    if ((f->n_known ? f->n : f->cap) > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;
+    ORBX_HIP(hipSetDevice(m->device));
+    KeyFrameBow *b = nullptr;
+    int r = keyframe_bow_alloc(kf->cap, &b);
+    if (r != ORBX_OK) return r;
+    b->voc = f->bow_voc; b->levelsup = f->bow_levelsup;
+    KeyFrameBowCopy Cp;
+    memset(&Cp, 0, sizeof(Cp));
+    Cp.src_count = f->count; Cp.n_host = f->n_known ? f->n : -1; Cp.cap = kf->cap;
+    Cp.src_word = f->bow_word; Cp.src_node = f->bow_node; Cp.src_ptr = f->fv_ptr; Cp.src_index = f->fv_index; Cp.src_meta = f->fv_meta;
+    Cp.src_fv_node = f->fv_node; Cp.src_angle = f->angle;
+    Cp.word = b->word; Cp.node = b->node; Cp.ptr = b->fv_ptr; Cp.index = b->fv_index; Cp.meta = b->fv_meta; Cp.fv_node = b->fv_node; Cp.angle = b->angle;
+    m->dirty = true;
+    hipLaunchKernelGGL(k_keyframe_bow_copy, dim3((unsigned)((kf->cap + 256) / 256)), dim3(256), 0, m->stream, Cp);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(b->ready, m->stream);
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); (void)hipStreamSynchronize(m->stream); m->dirty = false; keyframe_bow_free(b); return ORBX_E_HIP; }
+    kf->bow.store(b, std::memory_order_release);
+    return ORBX_OK;
+}
+
+// SearchByBoW(kfs[k], F, ...) (ORBmatcher.cc:223-425) with both sides resident: mode 0, A = key frame k, B = the frame handle
+int orbx_frame_search_by_bow_resident(orbx_matcher *m, orbx_frame *f, int n_kf, orbx_keyframe *const *kfs, const uint8_t *const *valid, float nnratio,
+                                      int check_orientation, int32_t *match, int match_stride, int32_t *nmatches) {
+    if (!m || !f || f->owner != m || f->fisheye || !f->bow_valid || n_kf < 0) return ORBX_E_BAD_ARG;
+    if (n_kf > ORBX_MAX_BOW_KEYFRAMES) return ORBX_E_TOO_LARGE;
+    if (n_kf == 0) return ORBX_OK;
+    if (!kfs || !match || !nmatches || match_stride < 0) return ORBX_E_BAD_ARG;
+    const orbx_vocabulary *voc = f->bow_voc;
+    int levelsup = f->bow_levelsup;
+    for (int k = 0; k < n_kf; k++)   // every key frame is checked before anything is enqueued
+        if (!keyframe_bow_ok(m, kfs[k], &voc, &levelsup)) return ORBX_E_BAD_ARG;
+    int n = f->n_known ? f->n : -1;
+    if (n < 0 && match_stride < f->cap) { const int rc = frame_count(f, &n); if (rc != ORBX_OK) return rc; }   // the rows must fit the stride
+    if (n >= 0 && match_stride < n) return ORBX_E_BAD_ARG;
+    for (int k = 0; k < n_kf; k++) {
+        if (valid && valid[k] && kfs[k]->n.load() < 0) { int nk; const int rc = orbx_keyframe_count(kfs[k], &nk); if (rc != ORBX_OK) return rc; }   // flags: N entries
+        nmatches[k] = 0;
+        for (int i = 0; i < std::max(n, 0); i++) match[(size_t)k * match_stride + i] = -1;
+    }
+    if (n == 0) return ORBX_OK;
+    ORBX_HIP(hipSetDevice(m->device));
+    std::vector<BowSide> A((size_t)n_kf), B((size_t)n_kf, bow_side(f));
+    for (int k = 0; k < n_kf; k++) A[k] = bow_side(kfs[k]);
+    for (int k = 0; k < n_kf; k++) { const int rc = keyframe_bow_acquire(m, kfs[k]); if (rc != ORBX_OK) return rc; }
+    std::vector<int32_t> counts;
+    const int r = run_bow_resident(m, 0, n_kf, A.data(), B.data(), valid, nullptr, true, nnratio, check_orientation, nullptr, nullptr, 0, match, match_stride,
+                                   nmatches, counts);
+    if (r != ORBX_OK) return r;
+    for (int k = 0; k < n_kf; k++) {
+        keyframe_bow_release(kfs[k]);
+        if (kfs[k]->n.load() < 0) kfs[k]->n.store(std::min(std::max(counts[2 * (size_t)k], 0), kfs[k]->cap));
+    }
+    if (!f->n_known) { f->n = std::min(std::max(counts[1], 0), f->cap); f->n_known = true; }
+    return ORBX_OK;
+}
+
+// SearchByBoW(pKF1, kfs2[k], ...) (ORBmatcher.cc:765-905) with both sides resident: mode 1, A = kf1 for every problem, B = kfs2[k]
+int orbx_keyframe_search_by_bow(orbx_matcher *m, orbx_keyframe *kf1, const uint8_t *valid1, int n_kf, orbx_keyframe *const *kfs2,
+                                const uint8_t *const *valid2, float nnratio, int check_orientation, int32_t *match12, int match_stride, int32_t *nmatches) {
+    if (!m || n_kf < 0) return ORBX_E_BAD_ARG;
+    const orbx_vocabulary *voc = nullptr;
+    int levelsup = 0;
+    if (!keyframe_bow_ok(m, kf1, &voc, &levelsup)) return ORBX_E_BAD_ARG;
+    if (n_kf > ORBX_MAX_BOW_KEYFRAMES) return ORBX_E_TOO_LARGE;
+    if (n_kf == 0) return ORBX_OK;
+    if (!kfs2 || !match12 || !nmatches || match_stride < 0) return ORBX_E_BAD_ARG;
+    for (int k = 0; k < n_kf; k++)
+        if (!keyframe_bow_ok(m, kfs2[k], &voc, &levelsup)) return ORBX_E_BAD_ARG;
+    int n1 = kf1->n.load();
+    if (n1 < 0 && (match_stride < kf1->cap || valid1)) { const int rc = orbx_keyframe_count(kf1, &n1); if (rc != ORBX_OK) return rc; }
+    if (n1 >= 0 && match_stride < n1) return ORBX_E_BAD_ARG;
+    for (int k = 0; k < n_kf; k++) {
+        if (valid2 && valid2[k] && kfs2[k]->n.load() < 0) { int nk; const int rc = orbx_keyframe_count(kfs2[k], &nk); if (rc != ORBX_OK) return rc; }
+        nmatches[k] = 0;
+        for (int i = 0; i < std::max(n1, 0); i++) match12[(size_t)k * match_stride + i] = -1;
+    }
+    if (n1 == 0) return ORBX_OK;
+    ORBX_HIP(hipSetDevice(m->device));
+    std::vector<BowSide> A((size_t)n_kf, bow_side(kf1)), B((size_t)n_kf);
+    std::vector<const uint8_t *> fa((size_t)n_kf, valid1);
+    for (int k = 0; k < n_kf; k++) B[k] = bow_side(kfs2[k]);
+    int rc = keyframe_bow_acquire(m, kf1);
+    for (int k = 0; k < n_kf && rc == ORBX_OK; k++) rc = keyframe_bow_acquire(m, kfs2[k]);
+    if (rc != ORBX_OK) return rc;
+    std::vector<int32_t> counts;
+    const int r = run_bow_resident(m, 1, n_kf, A.data(), B.data(), fa.data(), valid2, true, nnratio, check_orientation, nullptr, nullptr, 0, match12,
+                                   match_stride, nmatches, counts);
+    if (r != ORBX_OK) return r;
+    keyframe_bow_release(kf1);
+    if (kf1->n.load() < 0) kf1->n.store(std::min(std::max(counts[0], 0), kf1->cap));
+    for (int k = 0; k < n_kf; k++) {
+        keyframe_bow_release(kfs2[k]);
+        if (kfs2[k]->n.load() < 0) kfs2[k]->n.store(std::min(std::max(counts[2 * (size_t)k + 1], 0), kfs2[k]->cap));
+    }
+    return ORBX_OK;
+}
+
+// SearchForTriangulation (ORBmatcher.cc:907-1146) between two resident pinhole key frames: mode 2 with the gates of orbx_search_for_triangulation_pinhole;
+// keypoints, mvuRight and pKF2->mvScaleFactors are the key frames' own rows, pKF2->mvLevelSigma2 rides up beside the record
+int orbx_keyframe_search_for_triangulation(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                           int check_orientation, const orbx_keyframe_gate *gate, int32_t *matches12) {
+    if (!m || !gate || !gate->level_sigma2_2) return ORBX_E_BAD_ARG;
+    const orbx_vocabulary *voc = nullptr;
+    int levelsup = 0;
+    if (!keyframe_bow_ok(m, kf1, &voc, &levelsup) || !keyframe_bow_ok(m, kf2, &voc, &levelsup)) return ORBX_E_BAD_ARG;
+    if (gate->nlevels != kf2->nlevels) return ORBX_E_BAD_ARG;
+    int n1 = 0, n2 = kf2->n.load();
+    int rc = orbx_keyframe_count(kf1, &n1);   // matches12 holds N1 entries: N1 has to be known here
+    if (rc == ORBX_OK && skip2 && n2 < 0) rc = orbx_keyframe_count(kf2, &n2);
+    if (rc != ORBX_OK) return rc;
+    if (n1 > 0 && !matches12) return ORBX_E_BAD_ARG;
+    for (int i = 0; i < n1; i++) matches12[i] = -1;
+    if (n1 == 0 || n2 == 0) return 0;
+    ORBX_HIP(hipSetDevice(m->device));
+    TriGate G;
+    memset(&G, 0, sizeof(G));
+    G.enabled = 1; G.coarse = gate->coarse ? 1 : 0; G.strict = gate->strict_fp ? 1 : 0;
+    G.k1 = kf1->kps; G.k2 = kf2->kps; G.ur1 = kf1->u_right; G.ur2 = kf2->u_right; G.scale2 = kf2->scale;
+    for (int i = 0; i < 9; i++) G.F[i] = gate->F12[i];
+    G.ex = gate->ep_x; G.ey = gate->ep_y;
+    const BowSide A = bow_side(kf1), B = bow_side(kf2);
+    if ((rc = keyframe_bow_acquire(m, kf1)) != ORBX_OK || (rc = keyframe_bow_acquire(m, kf2)) != ORBX_OK) return rc;
+    std::vector<int32_t> counts;
+    int32_t nm = 0;
+    const int r = run_bow_resident(m, 2, 1, &A, &B, &skip1, &skip2, false, 0.f, check_orientation, &G, gate->level_sigma2_2, gate->nlevels, matches12, n1, &nm,
+                                   counts);
+    if (r != ORBX_OK) return r;
+    keyframe_bow_release(kf1); keyframe_bow_release(kf2);
+    if (kf2->n.load() < 0) kf2->n.store(std::min(std::max(counts[1], 0), kf2->cap));
+    return nm;
 }
 
 }  // extern "C"
@@ -3287,7 +3741,7 @@ extern "C" int orbx_frame_load_host_fisheye(orbx_frame *f, const orbx_frame_desc
     ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
     f->stage_busy = true;
     f->fisheye = true; f->roff = nl; f->n_left = nl; f->n_right = nr; f->n = N; f->n_known = true;
-    f->has_ur = false; f->loaded = true; f->bow_valid = false;
+    f->has_ur = false; f->loaded = true; f->bow_valid = false; f->load_seq++;
     return ORBX_OK;
 }
 
@@ -3332,7 +3786,7 @@ extern "C" int orbx_frame_load_stereo_fisheye_batch(orbx_frame *f, orbx_extracto
     ORBX_HIP(hipStreamWaitEvent(L->stream, f->ev_done, 0));
     ORBX_HIP(hipStreamWaitEvent(R->stream, f->ev_done, 0));
     if (L->match_stream) ORBX_HIP(hipStreamWaitEvent(L->match_stream, f->ev_done, 0));
-    f->fisheye = true; f->roff = capL; f->n_known = false; f->has_ur = false; f->loaded = true; f->bow_valid = false;
+    f->fisheye = true; f->roff = capL; f->n_known = false; f->has_ur = false; f->loaded = true; f->bow_valid = false; f->load_seq++;
     return ORBX_OK;
 }
 

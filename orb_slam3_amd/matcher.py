@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import KP_DTYPE, BowKeyFrame, FeatVec, FrameDesc, FuseQueries, PAIR_PREDICATE, PinholeGate, check, ptr
+from ._lib import KP_DTYPE, BowKeyFrame, FeatVec, FrameDesc, FuseQueries, KeyFrameGate, PAIR_PREDICATE, PinholeGate, check, ptr
 
 
 @dataclass
@@ -185,6 +185,28 @@ class DeviceKeyFrame:
         n = C.c_int(0)
         check(self._L.orbx_keyframe_count(self._h, C.byref(n)), "orbx_keyframe_count")
         return n.value
+
+    def compute_bow(self, matcher: "ORBmatcher", voc: "ORBVocabulary", levelsup: int = 4, download: bool = True, cap: int | None = None):
+        """KeyFrame::ComputeBoW on the resident descriptors (orbx_keyframe_compute_bow): the key frame keeps its FeatureVector for
+        ORBmatcher.SearchByBoWResident / SearchByBoWKeyFramesResident / SearchForTriangulationResident.  Set once: a second call with the same
+        vocabulary and levelsup only returns the ids.  download=True returns (word_id[N], node_id[N]); download=False returns None and does not
+        wait.  cap: the size of the id buffers while N is on the device only (the capacity of the frame handle the key frame was made from);
+        None = count first."""
+        self._voc = voc   # (the vocabulary outlives the key frame's BoW state)
+        if not download:
+            check(self._L.orbx_keyframe_compute_bow(matcher._h, self._h, voc._h, int(levelsup), None, None), "orbx_keyframe_compute_bow")
+            return None
+        size = self.count() if cap is None else int(cap)
+        w, nd = np.zeros(max(size, 1), np.int32), np.zeros(max(size, 1), np.int32)
+        check(self._L.orbx_keyframe_compute_bow(matcher._h, self._h, voc._h, int(levelsup), ptr(w), ptr(nd)), "orbx_keyframe_compute_bow")
+        n = self.count()   # (known after the call: no further synchronisation)
+        return w[:n], nd[:n]
+
+    def bow_from_frame(self, matcher: "ORBmatcher", frame: "DeviceFrame"):
+        """The mBowVec / mFeatVec part of KeyFrame::KeyFrame(Frame&) (orbx_keyframe_bow_from_frame): a device-to-device copy of the BoW state of the
+        DeviceFrame this key frame was made from (after its compute_bow, before its next load); asynchronous."""
+        check(self._L.orbx_keyframe_bow_from_frame(matcher._h, self._h, frame._h), "orbx_keyframe_bow_from_frame")
+        return self
 
     def close(self):
         if getattr(self, "_h", None):
@@ -638,6 +660,58 @@ class ORBmatcher:
                                                        int(self.mbCheckOrientation), ptr(m12)),
                   "orbx_search_by_bow_keyframes")
         return n, m12
+
+    # ---- the BoW-guided matchers with both sides resident (DeviceKeyFrames with BoW) ----
+    @staticmethod
+    def _kf_handles(kfs):
+        vp = C.c_void_p
+        return (vp * max(len(kfs), 1))(*[kf._h.value if isinstance(kf._h, vp) else kf._h for kf in kfs])
+
+    @staticmethod
+    def _flag_rows(flags, K):
+        keep = [None] * K if flags is None else [_u8(v) for v in flags]
+        assert len(keep) == K
+        return keep, (C.c_void_p * max(K, 1))(*[None if v is None else v.ctypes.data for v in keep])
+
+    def SearchByBoWResident(self, F: DeviceFrame, kfs, valid=None):
+        """SearchByBoW(KeyFrame*, Frame&) of the resident frame against DeviceKeyFrames that carry BoW, in one call (orbx_frame_search_by_bow_resident).
+        valid: per key frame a uint8[N_k] mask or None (all), or None for all key frames.  Returns (nmatches[K], match[K, N]): row k =
+        SearchByBoWFrame for key frame k's host arrays.  Only the masks and one record per key frame are uploaded."""
+        K = len(kfs)
+        keep, rows = self._flag_rows(valid, K)
+        stride = F.cap
+        match = np.full((max(K, 1), stride), -1, np.int32)
+        nm = np.zeros(max(K, 1), np.int32)
+        check(self._L.orbx_frame_search_by_bow_resident(self._h, F._h, K, self._kf_handles(kfs), rows, self.mfNNratio, int(self.mbCheckOrientation),
+                                                        ptr(match), stride, ptr(nm)), "orbx_frame_search_by_bow_resident")
+        del keep
+        return nm[:K], match[:K, :F.count()]
+
+    def SearchByBoWKeyFramesResident(self, kf1: DeviceKeyFrame, kfs2, valid1=None, valid2=None):
+        """SearchByBoW(pKF1, pKF2) for kf1 against every key frame of kfs2 in one call (orbx_keyframe_search_by_bow).  Returns (nmatches[K],
+        match12[K, N1]): row k = SearchByBoWKeyFrames(kf1, kfs2[k]) on host arrays."""
+        K = len(kfs2)
+        v1 = _u8(valid1)
+        keep, rows = self._flag_rows(valid2, K)
+        n1 = kf1.count()
+        match = np.full((max(K, 1), max(n1, 1)), -1, np.int32)
+        nm = np.zeros(max(K, 1), np.int32)
+        check(self._L.orbx_keyframe_search_by_bow(self._h, kf1._h, ptr(v1), K, self._kf_handles(kfs2), rows, self.mfNNratio, int(self.mbCheckOrientation),
+                                                  ptr(match), max(n1, 1), ptr(nm)), "orbx_keyframe_search_by_bow")
+        del keep
+        return nm[:K], match[:K, :n1]
+
+    def SearchForTriangulationResident(self, kf1: DeviceKeyFrame, kf2: DeviceKeyFrame, skip1, skip2, level_sigma2_2, F12, epipole, coarse=False,
+                                       strict_fp=False):
+        """SearchForTriangulationPinhole between two resident key frames (orbx_keyframe_search_for_triangulation): keypoints, mvuRight, descriptors,
+        FeatureVectors and scale factors are the key frames' own; level_sigma2_2 = pKF2->mvLevelSigma2.  Returns (nmatches, matches12[N1])."""
+        s1, s2, sg = _u8(skip1), _u8(skip2), _f32(level_sigma2_2)
+        g = KeyFrameGate((C.c_float * 9)(*[float(x) for x in np.asarray(F12, np.float32).ravel()]), float(epipole[0]), float(epipole[1]), int(coarse),
+                         int(strict_fp), len(sg), sg.ctypes.data)
+        m12 = np.full(max(kf1.count(), 1), -1, np.int32)
+        n = check(self._L.orbx_keyframe_search_for_triangulation(self._h, kf1._h, kf2._h, ptr(s1), ptr(s2), int(self.mbCheckOrientation), C.byref(g),
+                                                                 ptr(m12)), "orbx_keyframe_search_for_triangulation")
+        return n, m12[:kf1.count()]
 
     # ---- SearchForTriangulation (ORBmatcher.cc:907-1146) ----
     def SearchForTriangulation(self, desc1, angle1, skip1, fv1: FeatureVector, desc2, angle2, skip2, fv2: FeatureVector,
