@@ -135,7 +135,7 @@ struct orbx_extractor {
     DevBuf d_lv, d_xtab, d_ytab, d_xgtab, d_fast_tiles, d_strips, d_blur_items, d_dc;
     // k_pyr_stream (levels 1 .. n-1 in one launch): per-geometry tables; ps_ok false = the geometry does not fit, the per-level launches run
     // one plan per band count (1, 2, 4, 8 bands per frame): the launch takes the one that puts about two workgroups on every CU for the batch at hand
-    struct PyrPlanDev { DevBuf cols, steps, tasks, band0; orbx::PyrStreamGeom geom; int bands = 0; size_t lds = 0; bool ok = false; };
+    struct PyrPlanDev { DevBuf cols, steps, tasks, lists; orbx::PyrStreamGeom geom; int bands = 0; size_t lds = 0; bool ok = false; };
     PyrPlanDev ps_plan[4];
     bool ps_ok = false;         // at least one plan exists
     int ps_wg_target = 512;     // workgroups a launch should have (2 per CU): 256 frames -> 2 bands, 128 -> 4 (KITTI 150 -> 104 us, TUM-VI 328 -> 222 us against 2 bands)

@@ -89,8 +89,8 @@ struct PyrStreamPlan {
     std::vector<PyrStreamLevel> levels;   // [nlevels], entry 0 unused
     std::vector<PyrColumn> cols;
     std::vector<PyrStep> steps;      // [bands][steps_per_band]
-    std::vector<PyrTask> tasks;      // all bands
-    std::vector<uint32_t> band_task0;
+    std::vector<PyrTask> tasks;      // all bands: [band][worker wave][step][k], one unused descriptor after each wave's
+    std::vector<PyrWaveList> lists;  // [bands][workers]
     int bands = 0;
     size_t lds_bytes = 0;
 };
@@ -191,85 +191,116 @@ static bool build_pyr_stream(const std::vector<LevelInfo> &lv, const std::vector
         lds += (size_t)ring[l] * ring_pitch[l];
     }
     lds += 16;
-    if (lds > lds_budget || lds / 16 >= 0xffff) return false;
+    if (lds > lds_budget) return false;
     G.ring0_off = ring_off[0]; G.ring0_pitch = ring_pitch[0]; G.ring0_rows = (uint32_t)ring[0];
     G.steps_per_band = (uint32_t)max_steps;
     // ---- steps and tasks ----
-    P.steps.assign((size_t)bands * max_steps, PyrStep{0u, 0u, 0u, 0u});
+    // A step's tasks, the costliest first, go to the worker waves in turn (wave w: tasks w, w + W, ... of the step: the step's last round holds
+    // the cheap ones); each wave's tasks of all steps then form one list with the schedule's barriers counted inside it.
+    struct HostTask { PyrTask t; uint32_t col; int cost; };
+    const uint32_t W = G.workers;
+    if (xg_bytes > 0xffffu) return false;   // PyrTask::next_col holds the table offset in 16 bits
+    P.steps.assign((size_t)bands * max_steps, PyrStep{0u, 0u});
+    P.lists.assign((size_t)bands * W, PyrWaveList{0u, 0u, 0u, 0u});
     for (int k = 0; k < bands; k++) {
         const Band &b = B[k];
-        P.band_task0.push_back((uint32_t)P.tasks.size());
-        const size_t t0 = P.tasks.size();
-        auto slot_off = [&](int l, int row) { return (uint16_t)((ring_off[l] + (uint32_t)((row - b.comp[l].first) % ring[l]) * ring_pitch[l]) / 16u); };
+        auto slot_off = [&](int l, int row) { return ring_off[l] + (uint32_t)((row - b.comp[l].first) % ring[l]) * ring_pitch[l]; };
+        std::vector<std::vector<HostTask>> wave(W);
+        std::vector<uint32_t> idle(W, 0u);   // steps since the wave's last task
+        size_t band_tasks = 0;
         for (size_t s = 0; s < max_steps; s++) {
             PyrStep &d = P.steps[(size_t)k * max_steps + s];
-            d.task_begin = d.task_end = (uint32_t)(P.tasks.size() - t0);
-            if (s >= b.steps.size()) continue;
-            const auto &st = b.steps[s];
-            const int y0 = st[0].first, ny = st[0].second - st[0].first;
-            if (y0 > 0xffff || ny > 0xffff) return false;
-            d.y0_rows = (uint32_t)y0 | ((uint32_t)ny << 16);
-            d.slot0 = (uint32_t)((y0 - b.comp[0].first) % ring[0]);
-            for (int l = 1; l < nl; l++) {
-                int r = st[l].first;
-                const int re = st[l].second;
-                while (r < re) {
-                    PyrTask T;
-                    memset(&T, 0, sizeof(T));
-                    const int a0 = src0(l, r), a1 = src1(l, r);
-                    int rows = 1, nsrc = 2;
-                    if (r + 1 < re && a1 == a0 + 1) {   // a pair: rows r, r + 1 from three (shared middle) or four consecutive source rows
-                        const int c0 = src0(l, r + 1), c1 = src1(l, r + 1);
-                        if (c0 == a1 && c1 == a1 + 1) { rows = 2; nsrc = 3; }
-                        else if (c0 == a1 + 1 && c1 == a1 + 2) { rows = 2; nsrc = 4; }
-                    }
-                    const uint32_t s0 = slot_off(l - 1, a0), s1 = slot_off(l - 1, a1);
-                    const uint32_t s2 = nsrc >= 3 ? slot_off(l - 1, a0 + 2) : s1, s3 = nsrc >= 4 ? slot_off(l - 1, a0 + 3) : s2;
-                    T.src01 = s0 | (s1 << 16);
-                    T.src23 = s2 | (s3 << 16);
-                    const PyrStreamLevel &S = P.levels[l];
-                    const int h = lv[l].h;
-                    if (h < 2 * kEdge + 2) return false;   // a row with a copy in both rings: not handled (levels are at least 67 rows high)
-                    for (int c = 0; c < nchunk[l]; c++) {
-                        const uint32_t dcol0 = S.col0 + 64u * (uint32_t)c;                               // dword column of lane 0 inside the padded row
-                        const int nlive = std::min(64, (int)S.ncol - 64 * c);
-                        const int roi_first = std::max(0, kRoiX / 4 - (int)dcol0);                        // first lane whose dword lies in the ROI
-                        const int roi_n = std::max(0, std::min(nlive, kRoiX / 4 + (int)S.roi_dw - (int)dcol0) - roi_first);
-                        T.hdr = (uint32_t)(rows - 1) | ((uint32_t)nsrc << 1) | ((uint32_t)nlive << 4) | ((uint32_t)roi_first << 11) | ((uint32_t)roi_n << 18);
-                        T.xg = S.xg_lds + 64u * (uint32_t)c * (uint32_t)sizeof(PyrColumn);
-                        for (int q = 0; q < 2; q++) {
-                            const int rr = r + (q < rows ? q : 0);
-                            const ResizeTap &ty = ytab[lv[l].ytab_off + rr];
-                            T.b[q] = (uint32_t)(uint16_t)ty.c0 | ((uint32_t)(uint16_t)ty.c1 << 16);
-                            T.goff[q] = T.moff[q] = 0xffffffffu;
-                            if (q == 0) T.dlds = 0xffffffffu;
-                            if (q >= rows) continue;
-                            if (l + 1 < nl && roi_n > 0)
-                                T.dlds = (T.dlds & ~(0xffffu << (16 * q))) |
-                                         ((((uint32_t)slot_off(l, rr) * 16u + 4u * (dcol0 + (uint32_t)roi_first - (uint32_t)(kRoiX / 4))) / 4u) << (16 * q));
-                            if (rr >= b.own[l].first && rr < b.own[l].second) {
-                                const uint64_t row0 = lv[l].off + 4ull * dcol0;
-                                T.goff[q] = (uint32_t)(row0 + (uint64_t)(kEdge + rr) * lv[l].pitch);
-                                if (rr >= 1 && rr <= kEdge) T.moff[q] = (uint32_t)(row0 + (uint64_t)(kEdge - rr) * lv[l].pitch);
-                                if (rr <= h - 2 && rr >= h - 1 - kEdge) T.moff[q] = (uint32_t)(row0 + (uint64_t)(kEdge + 2 * (h - 1) - rr) * lv[l].pitch);
-                            }
+            std::vector<HostTask> step;
+            if (s < b.steps.size()) {
+                const auto &st = b.steps[s];
+                const int y0 = st[0].first, ny = st[0].second - st[0].first;
+                if (y0 > 0xffff || ny > 0xffff) return false;
+                d.y0_rows = (uint32_t)y0 | ((uint32_t)ny << 16);
+                d.slot0 = (uint32_t)((y0 - b.comp[0].first) % ring[0]);
+                for (int l = 1; l < nl; l++) {
+                    int r = st[l].first;
+                    const int re = st[l].second;
+                    while (r < re) {
+                        HostTask T;
+                        memset(&T, 0, sizeof(T));
+                        const int a0 = src0(l, r), a1 = src1(l, r);
+                        int rows = 1, nsrc = 2;
+                        if (r + 1 < re && a1 == a0 + 1) {   // a pair: rows r, r + 1 from three (shared middle) or four consecutive source rows
+                            const int c0 = src0(l, r + 1), c1 = src1(l, r + 1);
+                            if (c0 == a1 && c1 == a1 + 1) { rows = 2; nsrc = 3; }
+                            else if (c0 == a1 + 1 && c1 == a1 + 2) { rows = 2; nsrc = 4; }
                         }
-                        P.tasks.push_back(T);
+                        T.t.src[0] = slot_off(l - 1, a0); T.t.src[1] = slot_off(l - 1, a1);
+                        T.t.src[2] = nsrc >= 3 ? slot_off(l - 1, a0 + 2) : T.t.src[1];
+                        T.t.src[3] = nsrc >= 4 ? slot_off(l - 1, a0 + 3) : T.t.src[2];
+                        T.cost = (rows - 1) * 2 + nsrc;
+                        const PyrStreamLevel &S = P.levels[l];
+                        const int h = lv[l].h;
+                        if (h < 2 * kEdge + 2) return false;   // a row with a copy in both rings: not handled (levels are at least 67 rows high)
+                        for (int c = 0; c < nchunk[l]; c++) {
+                            const uint32_t dcol0 = S.col0 + 64u * (uint32_t)c;                               // dword column of lane 0 inside the padded row
+                            const int nlive = std::min(64, (int)S.ncol - 64 * c);
+                            const int roi_first = std::max(0, kRoiX / 4 - (int)dcol0);                        // first lane whose dword lies in the ROI
+                            const int roi_n = std::max(0, std::min(nlive, kRoiX / 4 + (int)S.roi_dw - (int)dcol0) - roi_first);
+                            const bool keep = l + 1 < nl && roi_n > 0;   // the next level reads these rows from the LDS ring
+                            T.col = (S.xg_lds + 64u * (uint32_t)c * (uint32_t)sizeof(PyrColumn)) | ((uint32_t)(nlive - 1) << 16);
+                            T.t.flags = (rows == 2 ? kPyrTwoRows : 0u) | (nsrc == 4 ? kPyrFourSrc : 0u) | ((uint32_t)(nlive - 1) << 8);
+                            T.t.roi_lo = (uint32_t)roi_first; T.t.roi_n = keep ? (uint32_t)roi_n : 0u;
+                            for (int q = 0; q < 2; q++) {
+                                const int rr = r + (q < rows ? q : 0);
+                                const ResizeTap &ty = ytab[lv[l].ytab_off + rr];
+                                T.t.b[q] = (uint32_t)(uint16_t)ty.c0 | ((uint32_t)(uint16_t)ty.c1 << 16);
+                                T.t.goff[q] = T.t.moff[q] = T.t.dlds[q] = 0u;
+                                if (q >= rows) continue;
+                                // lane i's dword: dlds + 4 i (lane roi_first holds the row's first ROI dword; the sum is taken modulo 2^32)
+                                if (keep) T.t.dlds[q] = slot_off(l, rr) + 4u * (dcol0 - (uint32_t)(kRoiX / 4));
+                                if (rr >= b.own[l].first && rr < b.own[l].second) {
+                                    const uint64_t row0 = lv[l].off + 4ull * dcol0;
+                                    uint64_t g = row0 + (uint64_t)(kEdge + rr) * lv[l].pitch, m = 0;
+                                    if (rr >= 1 && rr <= kEdge) m = row0 + (uint64_t)(kEdge - rr) * lv[l].pitch;
+                                    if (rr <= h - 2 && rr >= h - 1 - kEdge) m = row0 + (uint64_t)(kEdge + 2 * (h - 1) - rr) * lv[l].pitch;
+                                    if (g + 256u > 0xffffffffull || m + 256u > 0xffffffffull) return false;   // offset + 4 x lane is a 32-bit sum
+                                    T.t.goff[q] = (uint32_t)g; T.t.flags |= kPyrStoreRow << q;
+                                    if (m) { T.t.moff[q] = (uint32_t)m; T.t.flags |= kPyrStoreCopy << q; }
+                                }
+                            }
+                            step.push_back(T);
+                        }
+                        r += rows;
                     }
-                    r += rows;
                 }
             }
-            d.task_end = (uint32_t)(P.tasks.size() - t0);
-            // the costliest tasks first: with the waves taking tasks w, w + W, ... the step's last round holds the cheap ones
-            std::stable_sort(P.tasks.begin() + (ptrdiff_t)(t0 + d.task_begin), P.tasks.end(), [](const PyrTask &a, const PyrTask &b) {
-                auto cost = [](const PyrTask &t) { return (int)((t.hdr & 1u) * 2u + ((t.hdr >> 1) & 7u)); };
-                return cost(a) > cost(b);
-            });
+            std::stable_sort(step.begin(), step.end(), [](const HostTask &x, const HostTask &y) { return x.cost > y.cost; });
+            band_tasks += step.size();
+            for (uint32_t w = 0; w < W; w++) {
+                bool any = false;
+                for (size_t j = w; j < step.size(); j += W) {
+                    if (!any) {   // the steps the wave sat out: barriers after its previous task, or before its first
+                        if (wave[w].empty()) P.lists[(size_t)k * W + w].lead = idle[w];
+                        else wave[w].back().t.flags += idle[w] << 16;
+                        idle[w] = 0u; any = true;
+                    }
+                    wave[w].push_back(step[j]);
+                }
+                if (any) wave[w].back().t.flags += 1u << 16;   // this step's barrier
+                else idle[w]++;
+            }
+        }
+        if (band_tasks == 0) return false;   // a band without a task: not a geometry this form takes
+        for (uint32_t w = 0; w < W; w++) {
+            PyrWaveList &L = P.lists[(size_t)k * W + w];
+            L.first = (uint32_t)P.tasks.size(); L.n = (uint32_t)wave[w].size();
+            if (wave[w].empty()) L.lead = idle[w];
+            else { wave[w].back().t.flags += idle[w] << 16; L.col0 = wave[w][0].col; }
+            for (size_t j = 0; j < wave[w].size(); j++) {
+                wave[w][j].t.next_col = j + 1 < wave[w].size() ? wave[w][j + 1].col : 0u;
+                P.tasks.push_back(wave[w][j].t);
+            }
+            PyrTask pad;
+            memset(&pad, 0, sizeof(pad));
+            P.tasks.push_back(pad);   // fetched ahead by the wave's last task, never used
         }
     }
-    if (P.tasks.empty()) return false;
-    P.band_task0.push_back((uint32_t)P.tasks.size());   // sentinel: band b's tasks are [band_task0[b], band_task0[b + 1])
-    for (int k = 0; k < bands; k++) if (P.band_task0[k + 1] == P.band_task0[k]) return false;   // a band without a task: not a geometry this form takes
     P.bands = bands;
     P.lds_bytes = lds;
     out = std::move(P);
@@ -465,7 +496,7 @@ static int configure(orbx_extractor *ex, int width, int height, int batch) {
             ENS(ex->ps_plan[k].cols, plans[k].cols.size() * sizeof(PyrColumn));
             ENS(ex->ps_plan[k].steps, plans[k].steps.size() * sizeof(PyrStep));
             ENS(ex->ps_plan[k].tasks, plans[k].tasks.size() * sizeof(PyrTask));
-            ENS(ex->ps_plan[k].band0, plans[k].band_task0.size() * sizeof(uint32_t));
+            ENS(ex->ps_plan[k].lists, plans[k].lists.size() * sizeof(PyrWaveList));
         }
     ENS(ex->d_pyr, pyr_off * B);
     if (ex->pyr_double) ENS(ex->d_pyr2, pyr_off * B);
@@ -513,7 +544,7 @@ static int configure(orbx_extractor *ex, int width, int height, int batch) {
         ORBX_HIP(hipMemcpy(ex->ps_plan[k].cols.p, pl.cols.data(), pl.cols.size() * sizeof(PyrColumn), hipMemcpyHostToDevice));
         ORBX_HIP(hipMemcpy(ex->ps_plan[k].steps.p, pl.steps.data(), pl.steps.size() * sizeof(PyrStep), hipMemcpyHostToDevice));
         ORBX_HIP(hipMemcpy(ex->ps_plan[k].tasks.p, pl.tasks.data(), pl.tasks.size() * sizeof(PyrTask), hipMemcpyHostToDevice));
-        ORBX_HIP(hipMemcpy(ex->ps_plan[k].band0.p, pl.band_task0.data(), pl.band_task0.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        ORBX_HIP(hipMemcpy(ex->ps_plan[k].lists.p, pl.lists.data(), pl.lists.size() * sizeof(PyrWaveList), hipMemcpyHostToDevice));
         if (pl.lds_bytes > 64 * 1024) ORBX_HIP(hipFuncSetAttribute((const void *)k_pyr_stream, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024)));
     }
     ORBX_HIP(hipMemset(ex->d_err.p, 0, sizeof(int32_t)));
@@ -530,7 +561,7 @@ static int configure(orbx_extractor *ex, int width, int height, int batch) {
             ex->ps_plan[k].geom = plans[k].geom; ex->ps_plan[k].bands = plans[k].bands; ex->ps_plan[k].lds = plans[k].lds_bytes; ex->ps_plan[k].ok = true;
             if (getenv("ORBX_DEBUG_ALLOC"))
                 fprintf(stderr, "[orbx pyr] k_pyr_stream plan: %d bands, %u steps, %zu tasks, LDS %zu B (tables %u B)\n", plans[k].bands, plans[k].geom.steps_per_band,
-                        plans[k].tasks.size(), plans[k].lds_bytes, plans[k].geom.xg_bytes);
+                        plans[k].tasks.size() - plans[k].lists.size(), plans[k].lds_bytes, plans[k].geom.xg_bytes);
         }
     if (const char *v = getenv("ORBX_PYR_STREAM_MIN")) {   // test hook "<frames>[,<workgroups>]": the smallest batch that takes k_pyr_stream, the launch size the band plan aims at
         ex->ps_min_frames = std::max(1, atoi(v));
@@ -760,7 +791,7 @@ static int enqueue_extract(orbx_extractor *ex, const uint8_t *d_images, int n, s
     if (stream) {   // levels 1 .. nl-1 in one launch, straight from the caller's frames
         ProfScope ps(ex, K_PYR_RESIZE);
         hipLaunchKernelGGL(k_pyr_stream, xcd_grid(pp->bands, n, pyr_local), dim3(64 * (pp->geom.workers + 1)), pp->lds, pst, pp->geom, (const uint4 *)pp->cols.p,
-                           (const PyrStep *)pp->steps.p, (const PyrTask *)pp->tasks.p, (const uint32_t *)pp->band0.p, d_images, row_stride,
+                           (const PyrStep *)pp->steps.p, (const PyrTask *)pp->tasks.p, (const PyrWaveList *)pp->lists.p, d_images, row_stride,
                            frame_stride, pyr, ex->pyr_frame, inplace0 ? (int32_t *)ex->d_fast_ovf.p : (int32_t *)nullptr, n);
         if (ev_input_consumed && !inplace0) ORBX_HIP(hipEventRecord(ev_input_consumed, pst));   // k_pyr_base and k_pyr_stream have read the frames
     }
@@ -1083,9 +1114,9 @@ void orbx_destroy(orbx_extractor *ex) {
                       &ex->d_mkey1, &ex->d_mkey2, &ex->d_mocc, &ex->d_mentries, &ex->d_mprobs, &ex->d_mres, &ex->d_mscale, &ex->d_mgrid, &ex->d_xgtab,
                       &ex->d_mp_qr, &ex->d_mp_qmin, &ex->d_mp_qmax, &ex->d_mp_valid, &ex->d_mp_keys, &ex->d_mp_meta, &ex->d_mp_grid, &ex->d_mp_probs,
                       &ex->d_mp_res, &ex->d_mp_misc, &ex->d_mp_entries, &ex->d_kps_un, &ex->d_frustum_frames, &ex->d_strips,
-                      &ex->ps_plan[0].cols, &ex->ps_plan[0].steps, &ex->ps_plan[0].tasks, &ex->ps_plan[0].band0, &ex->ps_plan[1].cols, &ex->ps_plan[1].steps,
-                      &ex->ps_plan[1].tasks, &ex->ps_plan[1].band0, &ex->ps_plan[2].cols, &ex->ps_plan[2].steps, &ex->ps_plan[2].tasks, &ex->ps_plan[2].band0,
-                      &ex->ps_plan[3].cols, &ex->ps_plan[3].steps, &ex->ps_plan[3].tasks, &ex->ps_plan[3].band0};
+                      &ex->ps_plan[0].cols, &ex->ps_plan[0].steps, &ex->ps_plan[0].tasks, &ex->ps_plan[0].lists, &ex->ps_plan[1].cols, &ex->ps_plan[1].steps,
+                      &ex->ps_plan[1].tasks, &ex->ps_plan[1].lists, &ex->ps_plan[2].cols, &ex->ps_plan[2].steps, &ex->ps_plan[2].tasks, &ex->ps_plan[2].lists,
+                      &ex->ps_plan[3].cols, &ex->ps_plan[3].steps, &ex->ps_plan[3].tasks, &ex->ps_plan[3].lists};
     for (DevBuf *b : bufs) b->release();
     if (ex->h_stage) (void)hipHostFree(ex->h_stage);
     if (ex->ev0) (void)hipEventDestroy(ex->ev0);

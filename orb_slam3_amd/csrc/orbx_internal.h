@@ -93,24 +93,33 @@ struct PyrStreamGeom {    // kernel argument (scalar loads)
     int32_t w0;
 };
 
-struct PyrStep {          // 16 bytes, one scalar load
-    uint32_t task_begin, task_end;   // indices into the band's task list
+struct PyrStep {          // 8 bytes, one scalar load of the loader wave
     uint32_t y0_rows;         // first frame row to stage | number of rows << 16
     uint32_t slot0;           // ring slot of that row (the following rows take the following slots, wrapping at ring0_rows)
 };
 
-struct PyrTask {          // 48 bytes, scalar loads; everything a wave needs to know about its 64 dword columns of one or two output rows
-    uint32_t hdr;         // (rows - 1) | source rows << 1 | live lanes (1 .. 64) << 4 | first lane with an ROI dword << 11 | lanes with an ROI dword << 18
-    uint32_t src01, src23;   // LDS byte offsets / 16 of the source rows (ROI byte 0), consecutive rows of the level before: row 0 | row 1 << 16, row 2 | row 3 << 16
-                          // (every field a whole dword: a 16-bit field would be fetched with a VECTOR load, whose wait also waits for the stores before it)
+// One wave x 64 dword columns x one or two output rows of one level, decoded on the host: 64 bytes = ONE s_load_dwordx16, every LDS address
+// ready to add.  A worker wave's tasks of all steps lie one after the other ([band][wave][step][k], PyrWaveList): the next descriptor is the
+// next 64 bytes, and the barriers of the schedule are counts inside the descriptors.
+struct PyrTask {
+    uint32_t src[4];      // LDS byte address of the four source rows (ROI byte 0), consecutive rows of the level before; unused ones repeat the last
     uint32_t b[2];        // vertical tap pair c0 | c1 << 16 of each output row
-    uint32_t goff[2];     // byte offset inside a frame's pyramid slab of lane 0's dword of each output row; 0xffffffff: another band stores this row
-    uint32_t moff[2];     // ... of its REFLECT_101 copy in the 19-row ring above / below the level; 0xffffffff: none
-    uint32_t dlds;        // LDS byte offset / 4 of the first ROI dword of each output row in this level's ring (row 0 | row 1 << 16); 0xffff: the last level keeps none
-    uint32_t xg;          // LDS byte offset of lane 0's PyrColumn
-    uint32_t pad;
+    uint32_t goff[2];     // byte offset inside a frame's pyramid slab of lane 0's dword of each output row (kPyrStoreRow flags)
+    uint32_t moff[2];     // ... of its REFLECT_101 copy in the 19-row ring above / below the level (kPyrStoreCopy flags)
+    uint32_t dlds[2];     // LDS byte address of lane 0's dword of each output row in this level's ring (lanes outside [roi_lo, roi_lo + roi_n) store none)
+    uint32_t next_col;    // the column block of the wave's NEXT task: LDS byte offset of lane 0's PyrColumn | (live lanes - 1) << 16
+    uint32_t flags;       // kPyrTwoRows | kPyrFourSrc | kPyrStoreRow << row | kPyrStoreCopy << row | (live lanes - 1) << 8 | barriers after this task << 16
+    uint32_t roi_lo, roi_n;   // first lane with an ROI dword the next level reads, number of such lanes (0: the last level keeps no ring)
 };
-static_assert(sizeof(PyrTask) == 48 && sizeof(PyrStep) == 16, "task table layout");
+constexpr uint32_t kPyrTwoRows = 1u, kPyrFourSrc = 2u, kPyrStoreRow = 4u, kPyrStoreCopy = 16u;   // StoreRow / StoreCopy: bit + output row
+
+struct PyrWaveList {      // [band][worker wave], 16 bytes
+    uint32_t first;       // index of the wave's first descriptor; its list ends with one unused descriptor (the last task's fetch ahead)
+    uint32_t n;           // tasks of the wave over all steps
+    uint32_t lead;        // steps before the wave's first task (all steps when it has none): barriers to pass first
+    uint32_t col0;        // the column block of the first task, as PyrTask::next_col
+};
+static_assert(sizeof(PyrTask) == 64 && sizeof(PyrStep) == 8 && sizeof(PyrWaveList) == 16, "task table layout");
 
 struct TileRef {  // blockIdx.x -> (level, tile) mapping for multi-level launches
     int16_t level;

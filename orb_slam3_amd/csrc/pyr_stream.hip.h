@@ -12,7 +12,8 @@
 //     the LDS ring the next level reads; nothing is read back from HBM.
 // The row schedule is a per-geometry table built on the host (build_pyr_stream, orbx_extractor.hip): the kernel holds no index arithmetic beyond
 // "task -> LDS offsets".  A task = one wave x 64 dword columns x one or two output rows of one level (two rows share the horizontal pass of
-// their common source row).  Bands of one frame overlap by the few rows the cascade needs (9 of 480 rows for two bands of a 752x480 frame);
+// their common source row); every worker wave has its own list of them over all steps (PyrWaveList, PyrTask: orbx_internal.h), with the steps'
+// barriers counted inside the list, so that the next task's descriptor and column entries can be fetched while this one is computed.  Bands of one frame overlap by the few rows the cascade needs (9 of 480 rows for two bands of a 752x480 frame);
 // rows in the overlap are computed by both bands and stored by the one that owns them.
 // Arithmetic = k_pyr_resize_march's ([OCV] resize INTER_LINEAR 8U: Q11 taps, horizontal sums >> 4, (b * H) >> 16 per source row, + 2 >> 2), bit for bit.
 // grid xcd_grid(bands per frame, B), block 64 x (worker waves + 1: the loader wave), dynamic LDS = PyrStreamGeom::lds_bytes
@@ -23,10 +24,8 @@ namespace orbx {
 // horizontal pass of one source row for the four pixels of a dword column: sums >> 4 ([OCV] the vertical pass multiplies (sum >> 4)).
 // The column's 8 source bytes start at any byte of the row: three ALIGNED dwords + two v_alignbyte (measured: an 8-byte LDS read at an odd address
 // costs the kernel 66 of 228 us -- the LDS serves it in pieces).
-__device__ __forceinline__ void pyr_hpass(const uint8_t *row4, const uint32_t osh, const uint32_t sel, const uint32_t selr, const uint32_t (&cc)[4], uint32_t (&H)[4]) {
-    const uint32_t *p = reinterpret_cast<const uint32_t *>(row4);
-    const uint32_t d0 = p[0], d1 = p[1], d2 = p[2];
-    const uint32_t vx = __builtin_amdgcn_alignbyte(d1, d0, osh), vy = __builtin_amdgcn_alignbyte(d2, d1, osh);
+__device__ __forceinline__ void pyr_hpass(const uint32_t (&d)[3], const uint32_t osh, const uint32_t sel, const uint32_t selr, const uint32_t (&cc)[4], uint32_t (&H)[4]) {
+    const uint32_t vx = __builtin_amdgcn_alignbyte(d[1], d[0], osh), vy = __builtin_amdgcn_alignbyte(d[2], d[1], osh);
     constexpr uint32_t kPair[4] = {0x0c040c00u, 0x0c050c01u, 0x0c060c02u, 0x0c070c03u};  // (left tap k, right tap k) as two u16
     const uint32_t l = __builtin_amdgcn_perm(vy, vx, sel), q = __builtin_amdgcn_perm(vy, vx, selr);
 #pragma unroll
@@ -43,9 +42,83 @@ __device__ __forceinline__ uint32_t pyr_vpass(const uint32_t (&A)[4], const uint
     }
     return ((uint32_t)(uint16_t)__builtin_amdgcn_ashr_pk_u8_i32(t[0], t[1], 2)) | ((uint32_t)(uint16_t)__builtin_amdgcn_ashr_pk_u8_i32(t[2], t[3], 2) << 16);
 }
+// the three aligned dwords of a source row that hold a column's 8 source bytes
+__device__ __forceinline__ void pyr_row_read(const uint8_t *row4, uint32_t (&d)[3]) {
+    const uint32_t *p = reinterpret_cast<const uint32_t *>(row4);
+    d[0] = p[0]; d[1] = p[1]; d[2] = p[2];
+}
+// a lane's PyrColumn of a column block (col = PyrTask::next_col: LDS offset of lane 0's entry | (live lanes - 1) << 16)
+__device__ __forceinline__ void pyr_col_read(const uint8_t *smem, const uint32_t col, const int lane, uint2 &e0, uint32_t (&cc)[4]) {
+    const uint8_t *e = smem + (col & 0xffffu) + (uint32_t)min(lane, (int)(col >> 16)) * 24u;
+    e0 = *reinterpret_cast<const uint2 *>(e);
+    const uint2 a = *reinterpret_cast<const uint2 *>(e + 8), b = *reinterpret_cast<const uint2 *>(e + 16);
+    cc[0] = a.x; cc[1] = a.y; cc[2] = b.x; cc[3] = b.y;
+}
+
+// ---- a worker wave's descriptor fetch ----
+// The 64 bytes of the NEXT task are requested by hand, at the one place of a task where the request costs nothing: after the task's LDS reads
+// have returned and before its arithmetic.  LDS and scalar memory share one counter (lgkmcnt) and scalar loads return out of order, so a wait for
+// LDS data with a descriptor in flight is a wait for the descriptor too (a round trip to L2: a band's lists are larger than the scalar cache);
+// left to the compiler, the request sinks below the task's last store and its wait stands a dozen instructions later (round 6: 159 us per launch
+// against 96 us of VALU issue).  The row dwords pass through the statement, which makes the compiler retire the LDS reads in front of it and keeps
+// the arithmetic behind it; pyr_desc_wait() is the only place the descriptor's registers are touched again (tests/test_isa_pyr_stream.py walks
+// the emitted code for both properties).
+typedef uint32_t PyrDesc __attribute__((ext_vector_type(16)));
+static_assert(sizeof(PyrDesc) == sizeof(PyrTask), "one descriptor = one s_load_dwordx16");
+#if defined(__AMDGCN__)
+#define PYR_ROW(d) "+v"(d[2])
+#define PYR_DESC_FETCH(N, p, ra, rb, rc, rd) asm volatile("s_load_dwordx16 %[n], %[a], 0x0" : [n] "=s"(N), PYR_ROW(ra), PYR_ROW(rb), PYR_ROW(rc), PYR_ROW(rd) : [a] "s"(p) : "memory")
+__device__ __forceinline__ void pyr_desc_wait(PyrDesc &N) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(N) : : "memory"); }
+#else   // the CPU emulation build: a plain load
+#define PYR_DESC_FETCH(N, p, ra, rb, rc, rd) N = *(p)
+__device__ __forceinline__ void pyr_desc_wait(PyrDesc &) {}
+#endif
+enum { kPtSrc = 0, kPtB = 4, kPtGoff = 6, kPtMoff = 8, kPtDlds = 10, kPtNextCol = 12, kPtFlags = 13, kPtRoiLo = 14, kPtRoiN = 15 };   // dwords of PyrTask
+
+// One task: C = its descriptor, (e0, cc) = its lanes' PyrColumn entries, both fetched during the wave's task before.  Requests the next task's
+// column entries (ne0, ncc: a read-only table, so this may cross a step's barrier) and descriptor (N).
+__device__ __forceinline__ void pyr_task(const PyrDesc &C, PyrDesc &N, const PyrDesc *next, const uint2 e0, const uint32_t (&cc)[4], uint2 &ne0, uint32_t (&ncc)[4],
+                                         uint8_t *smem, uint8_t *slab, const int lane) {
+    const uint32_t f = C[kPtFlags];
+    const uint32_t base = e0.x & 0xfffcu, osh = e0.x & 3u, valid = e0.x >> 30, sel = e0.y, selr = e0.y + 0x01010101u;
+    // every LDS operand of the task in ONE round trip: its source rows (a one-row task reads its second row three times: no branch in front of the
+    // reads) and the next task's column entries
+    uint32_t r0[3], r1[3], r2[3], r3[3], H0[4], H1[4], H2[4], H3[4];
+    pyr_row_read(smem + C[kPtSrc + 0] + base, r0);
+    pyr_row_read(smem + C[kPtSrc + 1] + base, r1);
+    pyr_row_read(smem + C[kPtSrc + 2] + base, r2);
+    pyr_row_read(smem + C[kPtSrc + 3] + base, r3);
+    pyr_col_read(smem, C[kPtNextCol], lane, ne0, ncc);
+    PYR_DESC_FETCH(N, next, r0, r1, r2, r3);
+    pyr_hpass(r0, osh, sel, selr, cc, H0);
+    pyr_hpass(r1, osh, sel, selr, cc, H1);
+    uint32_t o0 = pyr_vpass(H0, H1, C[kPtB + 0]), o1 = 0u;
+    if (f & kPyrTwoRows) {   // wave-uniform: three source rows (the middle one shared) or four (two independent pairs)
+        pyr_hpass(r2, osh, sel, selr, cc, H2);
+        if (f & kPyrFourSrc) {
+            pyr_hpass(r3, osh, sel, selr, cc, H3);
+            o1 = pyr_vpass(H2, H3, C[kPtB + 1]);
+        } else {
+            o1 = pyr_vpass(H1, H2, C[kPtB + 1]);
+        }
+    }
+    if (valid != 1u) { o0 = 0u; o1 = 0u; }   // a dword past the ring's last pixel
+    const bool live = (uint32_t)lane <= ((f >> 8) & 63u);
+    const bool in_roi = (uint32_t)lane - C[kPtRoiLo] < C[kPtRoiN];   // this lane's dword belongs to the ROI row the next level reads
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+        if (k == 1 && !(f & kPyrTwoRows)) break;
+        const uint32_t o = k ? o1 : o0;
+        if (live) {   // slab + (32-bit offset): the store takes the slab as its scalar base
+            if (f & (kPyrStoreRow << k)) *reinterpret_cast<uint32_t *>(slab + (size_t)(C[kPtGoff + k] + 4u * (uint32_t)lane)) = o;   // wave-uniform conditions
+            if (f & (kPyrStoreCopy << k)) *reinterpret_cast<uint32_t *>(slab + (size_t)(C[kPtMoff + k] + 4u * (uint32_t)lane)) = o;
+        }
+        if (in_roi) *reinterpret_cast<uint32_t *>(smem + (uint32_t)(C[kPtDlds + k] + 4u * (uint32_t)lane)) = o;
+    }
+}
 
 __global__ __launch_bounds__(1024) void k_pyr_stream(const PyrStreamGeom G, const uint4 *__restrict__ xg24, const PyrStep *__restrict__ steps,
-                                                                   const PyrTask *__restrict__ tasks, const uint32_t *__restrict__ band_task0,
+                                                                   const PyrTask *__restrict__ tasks, const PyrWaveList *__restrict__ lists,
                                                                    const uint8_t *__restrict__ img, size_t row_stride, size_t frame_stride,
                                                                    uint8_t *__restrict__ pyr, size_t pyr_frame_stride, int32_t *__restrict__ zero_word, int n_frames) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -92,60 +165,26 @@ __global__ __launch_bounds__(1024) void k_pyr_stream(const PyrStreamGeom G, cons
         }
         return;
     }
-    // ---- the worker waves: the step's tasks, wave w takes tasks w, w + NW, ... ----
+    // ---- the worker waves: each works through its own list of tasks (PyrWaveList), two descriptor sets and two sets of column entries in turn:
+    // while task t is computed, the descriptor of t + 1 is on its way and the column entries of t + 1 sit in registers ----
     uint8_t *slab = pyr + (size_t)f * pyr_frame_stride;
-    const PyrTask *tk = tasks + band_task0[band];
-    PyrStep d = st[0];
-    const uint32_t last_task = band_task0[band + 1] - band_task0[band] - 1u;   // a step without tasks points one past its predecessor's: never fetch beyond the band's list
-    PyrTask T = tk[min(min(d.task_begin + (uint32_t)wave, d.task_end - (d.task_end > d.task_begin ? 1u : 0u)), last_task)];
-    for (uint32_t s = 0; s < G.steps_per_band; s++) {
-        // the next step's descriptor and this wave's first task of it are requested now and waited for after the barrier: a step does not start
-        // with two dependent scalar-memory round trips
-        const PyrStep dn = st[min(s + 1u, G.steps_per_band - 1u)];
-        for (uint32_t t = d.task_begin + (uint32_t)wave; t < d.task_end; t += NW) {
-            const PyrTask C = T;
-            // the next task's descriptor is on its way while this one is computed (after the step's last one: the first of the next step)
-            T = tk[t + NW < d.task_end ? t + NW : min(min(dn.task_begin + (uint32_t)wave, dn.task_end - (dn.task_end > dn.task_begin ? 1u : 0u)), last_task)];
-            const uint32_t two = C.hdr & 1u, nsrc = (C.hdr >> 1) & 7u, nlive = (C.hdr >> 4) & 127u, roi_lo = (C.hdr >> 11) & 127u, roi_n = (C.hdr >> 18) & 127u;
-            const bool live = (uint32_t)lane < nlive;
-            const uint8_t *e = smem + C.xg + (uint32_t)min(lane, (int)nlive - 1) * 24u;
-            const uint2 e0 = *reinterpret_cast<const uint2 *>(e);
-            uint32_t cc[4];
-            { uint2 a, b; a = *reinterpret_cast<const uint2 *>(e + 8); b = *reinterpret_cast<const uint2 *>(e + 16); cc[0] = a.x; cc[1] = a.y; cc[2] = b.x; cc[3] = b.y; }
-            const uint32_t base = e0.x & 0xfffcu, osh = e0.x & 3u, valid = e0.x >> 30, sel = e0.y, selr = e0.y + 0x01010101u;
-            uint32_t H0[4], H1[4], H2[4], H3[4];
-            pyr_hpass(smem + (C.src01 & 0xffffu) * 16u + base, osh, sel, selr, cc, H0);
-            pyr_hpass(smem + (C.src01 >> 16) * 16u + base, osh, sel, selr, cc, H1);
-            uint32_t o0 = pyr_vpass(H0, H1, C.b[0]), o1 = 0u;
-            if (two) {   // wave-uniform: three source rows (the middle one shared) or four (two independent pairs)
-                pyr_hpass(smem + (C.src23 & 0xffffu) * 16u + base, osh, sel, selr, cc, H2);
-                if (nsrc == 4u) {
-                    pyr_hpass(smem + (C.src23 >> 16) * 16u + base, osh, sel, selr, cc, H3);
-                    o1 = pyr_vpass(H2, H3, C.b[1]);
-                } else {
-                    o1 = pyr_vpass(H1, H2, C.b[1]);
-                }
-            }
-            if (valid != 1u) { o0 = 0u; o1 = 0u; }   // a dword past the ring's last pixel
-            uint8_t *gl = slab + 4u * (uint32_t)lane;
-            const bool in_roi = (uint32_t)lane - roi_lo < roi_n;   // this lane's dword belongs to the ROI row the next level reads
-            uint8_t *ll = smem + 4u * ((uint32_t)lane - roi_lo);
-#pragma unroll
-            for (int k = 0; k < 2; k++) {
-                if (k == 1 && !two) break;
-                const uint32_t o = k ? o1 : o0;
-                if (live) {
-                    if (C.goff[k] != 0xffffffffu) *reinterpret_cast<uint32_t *>(gl + C.goff[k]) = o;   // wave-uniform conditions
-                    if (C.moff[k] != 0xffffffffu) *reinterpret_cast<uint32_t *>(gl + C.moff[k]) = o;
-                }
-                const uint32_t dl = k ? C.dlds >> 16 : C.dlds & 0xffffu;
-                if (in_roi && dl != 0xffffu) *reinterpret_cast<uint32_t *>(ll + dl * 4u) = o;
-            }
-        }
-        if (d.task_begin + (uint32_t)wave >= d.task_end)   // no task of this step for this wave: nothing has fetched the next step's first one
-            T = tk[min(min(dn.task_begin + (uint32_t)wave, dn.task_end - (dn.task_end > dn.task_begin ? 1u : 0u)), last_task)];
-        d = dn;
-        __syncthreads();
+    const PyrWaveList wl = lists[(size_t)band * G.workers + (uint32_t)wave];
+    for (uint32_t b = wl.lead; b; b--) __syncthreads();
+    if (wl.n == 0u) return;
+    const PyrDesc *p = reinterpret_cast<const PyrDesc *>(tasks) + wl.first;
+    PyrDesc A = *p, B;
+    uint2 ea, eb;
+    uint32_t ca[4], cb[4];
+    pyr_col_read(smem, wl.col0, lane, ea, ca);
+    for (uint32_t n = wl.n;;) {
+        pyr_task(A, B, ++p, ea, ca, eb, cb, smem, slab, lane);
+        for (uint32_t b = A[kPtFlags] >> 16; b; b--) __syncthreads();
+        pyr_desc_wait(B);
+        if (--n == 0u) break;
+        pyr_task(B, A, ++p, eb, cb, ea, ca, smem, slab, lane);
+        for (uint32_t b = B[kPtFlags] >> 16; b; b--) __syncthreads();
+        pyr_desc_wait(A);
+        if (--n == 0u) break;
     }
 }
 
