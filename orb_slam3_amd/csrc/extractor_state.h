@@ -23,6 +23,12 @@ void set_error(const std::string &s);
             return ORBX_E_HIP;                                                                         \
         }                                                                                              \
     } while (0)
+// a step that returns an ORBX_* code itself
+#define ORBX_TRY(expr)                                                                                 \
+    do {                                                                                               \
+        const int _r = (expr);                                                                         \
+        if (_r != ORBX_OK) return _r;                                                                  \
+    } while (0)
 
 // Device buffer.  Normal mode: hipMalloc + zero fill (every buffer has defined contents from its first use).
 // Guard mode (ORBX_GUARD=1|2, debugging aid, see tools/repro_fault.sh): the buffer is placed through the HIP virtual-memory

@@ -16,6 +16,9 @@
 #include "matcher_kernels.hip.h"
 #include "geometry_kernels.hip.h"
 #include "extractor_state.h"
+#include "matcher_context.h"
+
+static_assert(sizeof(orbx_keypoint) == 28, "the rows every matcher uploads and the kernels index");
 
 using namespace orbx;
 
@@ -56,229 +59,9 @@ inline int launch_resolve(int np, hipStream_t st, const WindowProblem *dP, const
         const dim3 grid_ = np_ >= 8 ? dim3(8, (unsigned)nb_, (unsigned)((np_ + 7) / 8)) : dim3(1, (unsigned)nb_, (unsigned)np_);               \
         hipLaunchKernelGGL(k_window_best2_t<8>, grid_, dim3(256), 0, stream, __VA_ARGS__, np_);                                                \
     } while (0)
-struct Arena {  // bump allocator over one device buffer, reset per call
-    uint8_t *base = nullptr;
-    size_t cap = 0, used = 0;
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return ORBX_OK;
-        if (base) (void)hipFree(base);
-        base = nullptr; cap = 0;
-        bytes = (bytes * 3 / 2 + 4095) & ~(size_t)4095;
-        ORBX_HIP(hipMalloc((void **)&base, bytes));
-        cap = bytes;
-        return ORBX_OK;
-    }
-    void reset() { used = 0; }
-    template <typename T> T *take(size_t n) {
-        used = (used + 255) & ~(size_t)255;
-        T *p = reinterpret_cast<T *>(base + used);
-        used += n * sizeof(T);
-        return p;
-    }
-    static size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-};
 
 }  // namespace
 
-// Pinned host staging of a matcher context.  No entry point ever hands a CALLER'S (pageable) pointer to the HIP runtime: uploads are
-// memcpy'd into this arena first, downloads land here and are memcpy'd out after the stream synchronisation.  (The runtime's
-// alternative for pageable memory is to pin the caller's pages on the fly for the duration of the DMA; keeping that machinery out of
-// the hot path removes a whole class of lifetime hazards -- stack temporaries, vectors freed right after the call -- and is faster
-// for the small transfers these entry points make.)
-struct PinnedArena {
-    uint8_t *base = nullptr;
-    size_t cap = 0, used = 0;
-    int reserve(size_t bytes) {
-        if (bytes <= cap) return ORBX_OK;
-        if (base) (void)hipHostFree(base);
-        base = nullptr; cap = 0;
-        bytes = (bytes * 3 / 2 + 4095) & ~(size_t)4095;
-        // coherent (fine-grained) whatever HIP_HOST_COHERENT says: k_xfer's lanes read the staged inputs from and write the results into this block
-        // themselves, and the host reads them right after the stream synchronisation (as the extractor's h_stage, extractor_state.h)
-        ORBX_HIP(hipHostMalloc((void **)&base, bytes, hipHostMallocCoherent));
-        cap = bytes;
-        return ORBX_OK;
-    }
-    void reset() { used = 0; }
-    void *take(size_t bytes) {
-        used = (used + 63) & ~(size_t)63;
-        if (used + bytes > cap) return nullptr;
-        void *p = base + used;
-        used += bytes;
-        return p;
-    }
-};
-
-struct orbx_matcher {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    Arena arena;
-    PinnedArena stage;
-    // Transfers of ONE call are coalesced (round 5) and issued as KERNEL work (round 6).  `mirror` is a pinned, device-visible image of the device arena: an
-    // upload to arena offset o is staged at mirror offset o and only RECORDED; exec() -- the stream as every launch, fill and download of a call obtains it --
-    // first issues the recorded uploads and fills: every run of arena-adjacent buffers (adjacent = nothing but take()'s alignment padding between them, which
-    // no buffer owns) is one op of a k_xfer launch whose lanes read the mirror themselves (runs above kKernelXferMax: one hipMemcpyAsync).  Downloads from the
-    // arena are recorded the same way and issued as runs by deliver(): a k_xfer launch that writes the mirror.  Round 4: 14 uploads and 2 downloads of
-    // 4 B .. 32 KB per projection-matcher call, each a DMA submission (~5 us); round 5: 1 + 1 DMA submissions; now none -- the call's work is one in-order
-    // chain of launches in the compute queue, no hand-over to a DMA engine and back.  Transfers whose device side is not in the arena take the direct path.
-    PinnedArena mirror;
-    struct Span { size_t off, bytes; };
-    std::vector<Span> uploads;      // recorded, not yet issued (ascending offsets: the arena is a bump allocator)
-    std::vector<Span> issued;       // mirror ranges a transfer issued since the last synchronisation may still read: not staged over (such an upload goes direct)
-    struct Fill { size_t off, bytes; uint32_t value; };
-    std::vector<Fill> fills;        // recorded fills of arena ranges, issued with the uploads
-    struct Pending { void *dst; const void *src; size_t bytes; };
-    std::vector<Pending> pending;   // downloads waiting in pinned memory for the stream synchronisation
-    struct Down { void *dst; size_t off, bytes; };
-    std::vector<Down> downloads;    // recorded downloads from the arena (issued by deliver())
-    std::vector<Down> direct;       // results a kernel wrote straight into the mirror (host_view): handed out after the synchronisation, no transfer
-    hipError_t xfer_err = hipSuccess;
-    int64_t xfers[6] = {0, 0, 0, 0, 0, 0};   // transfer submissions (runs) up / down and their bytes since begin(); [4] of them by a DMA engine, [5] k_xfer launches
-    bool kernel_xfer = true;                 // ORBX_MATCHER_DMA=1: every run by hipMemcpyAsync, fills by hipMemsetAsync (round 5's transport, for A/B)
-    bool brute_windows = true;               // ORBX_MATCHER_BRUTE=0: small single calls build the grid as large ones do (A/B)
-    bool dirty = false;                      // something was enqueued since the last synchronisation
-    int32_t replay_stats[3] = {0, 0, 0};     // k_replay_init_lists of the last orbx_search_for_initialization: rounds, whole-wave re-scans, queries
-    static constexpr size_t kPadGap = 255;   // Arena::take aligns to 256
-    static constexpr size_t kKernelXferMax = (size_t)1 << 20;
-    // device scratch for one call + staging for everything that call can move in either direction
-    int reserve_all(size_t device_bytes) {
-        if (dirty) { (void)hipStreamSynchronize(stream); dirty = false; }   // a call that failed between exec() and deliver(): nothing of it may still read what is re-allocated here
-        int r = arena.reserve(device_bytes);
-        if (r != ORBX_OK) return r;
-        r = mirror.reserve(arena.cap);
-        if (r != ORBX_OK) return r;
-        return stage.reserve(2 * device_bytes + 65536);
-    }
-    // begin() follows a synchronisation of the previous call: every entry point ends in deliver(); one that returned between exec() and deliver() (a failed
-    // launch, an exhausted staging arena) left `dirty` set and is waited for here, before its mirror ranges are staged over
-    void begin() {
-        if (dirty) { (void)hipStreamSynchronize(stream); dirty = false; }
-        arena.reset(); stage.reset(); pending.clear(); uploads.clear(); downloads.clear(); direct.clear(); issued.clear(); fills.clear(); xfer_err = hipSuccess;
-        for (int64_t &x : xfers) x = 0;
-    }
-    bool in_arena(const void *p, size_t bytes) const {
-        const uint8_t *q = static_cast<const uint8_t *>(p);
-        return arena.base && q >= arena.base && q + bytes <= arena.base + arena.cap && arena.cap <= mirror.cap;
-    }
-    bool stageable(const void *p, size_t bytes) const {   // an upload that may be staged in the mirror
-        if (!in_arena(p, bytes)) return false;
-        const size_t o = (size_t)(static_cast<const uint8_t *>(p) - arena.base);
-        for (const Span &q : issued)
-            if (o < q.off + q.bytes && q.off < o + bytes) return false;
-        return true;
-    }
-    void note(hipError_t e) { if (e != hipSuccess && xfer_err == hipSuccess) xfer_err = e; }
-    // DIRECT access (round 6): a purely streaming kernel (every input read once, every output written once: k_in_frustum) is handed the MIRROR's addresses
-    // of its arena buffers -- its lanes read the staged inputs over the host link and write the results into host memory themselves: one launch per call
-    // instead of three (k_xfer, kernel, k_xfer).  host_view(p) = the mirror address of arena buffer p; stage_direct copies an input there without recording an
-    // upload; result_direct registers an output for deliver().
-    template <class T> T *host_view(T *p) const { return reinterpret_cast<T *>(mirror.base + (reinterpret_cast<const uint8_t *>(p) - arena.base)); }
-    bool direct_ok(size_t total_bytes) const { return kernel_xfer && total_bytes <= kKernelXferMax * 2; }
-    void stage_direct(void *arena_dst, const void *src, size_t bytes) { memcpy(host_view(static_cast<uint8_t *>(arena_dst)), src, bytes); }
-    void result_direct(void *dst, const void *arena_src, size_t bytes) {
-        direct.push_back(Down{dst, (size_t)(static_cast<const uint8_t *>(arena_src) - arena.base), bytes});
-    }
-    void record_upload(size_t o, size_t bytes) {   // staged in the mirror at offset o by the caller
-        for (const Fill &f : fills)
-            if (o < f.off + f.bytes + 16 && f.off < o + bytes + 16) { flush_uploads(); break; }   // never reorder an upload and a fill of one range
-        uploads.push_back(Span{o, bytes});
-    }
-    void launch_xfer(const XferOps &X, uint32_t max_units) {
-        const uint32_t grid = std::min<uint32_t>(1024u, (max_units + 255u) / 256u);
-        hipLaunchKernelGGL(k_xfer, dim3(grid ? grid : 1), dim3(256), 0, stream, X);
-        note(hipGetLastError());
-        xfers[5]++;
-    }
-    // a fill of an arena range, issued with the call's uploads (the device side of the range must not be the target of a recorded upload)
-    hipError_t fill(void *dst, int value, size_t bytes) {
-        if (bytes == 0) return hipSuccess;
-        const size_t o = (size_t)(static_cast<const uint8_t *>(dst) - arena.base);
-        if (kernel_xfer && in_arena(dst, bytes) && (o & 15) == 0) {
-            for (const Span &u : uploads)
-                if (o < u.off + u.bytes + 16 && u.off < o + bytes + 16) { flush_uploads(); break; }   // never reorder a fill and an upload of one range
-            fills.push_back(Fill{o, bytes, (uint32_t)(value & 0xff)});
-            return hipSuccess;
-        }
-        dirty = true;
-        return hipMemsetAsync(dst, value, bytes, exec());
-    }
-    void flush_uploads() {
-        std::sort(uploads.begin(), uploads.end(), [](const Span &a, const Span &b) { return a.off < b.off; });   // (a record uploaded after its buffers were taken lies between them)
-        XferOps X;
-        X.n = 0;
-        uint32_t max_units = 0;
-        auto add = [&](uint8_t *dst, const uint8_t *src, size_t bytes, uint32_t value) {
-            if (X.n == kMaxXferOps) { launch_xfer(X, max_units); X.n = 0; max_units = 0; }
-            const uint32_t units = (uint32_t)((bytes + 15) / 16);
-            X.op[X.n++] = XferOp{dst, src, units, value};
-            max_units = std::max(max_units, units);
-        };
-        size_t i = 0;
-        while (i < uploads.size()) {
-            const size_t b = uploads[i].off;
-            size_t e = b + uploads[i].bytes, j = i + 1;
-            while (j < uploads.size() && uploads[j].off <= e + kPadGap) { e = std::max(e, uploads[j].off + uploads[j].bytes); j++; }
-            if (kernel_xfer && e - b <= kKernelXferMax && (b & 15) == 0) {
-                add(arena.base + b, mirror.base + b, e - b, 0);   // (rounded up to 16 bytes: alignment padding at most, the next buffer starts on a multiple of 256)
-            } else {
-                note(hipMemcpyAsync(arena.base + b, mirror.base + b, e - b, hipMemcpyHostToDevice, stream));
-                xfers[4]++;
-            }
-            xfers[0]++; xfers[2] += (int64_t)(e - b);
-            issued.push_back(Span{b, e - b});
-            i = j;
-        }
-        uploads.clear();
-        for (const Fill &f : fills) add(arena.base + f.off, nullptr, f.bytes, f.value);
-        fills.clear();
-        if (X.n) launch_xfer(X, max_units);
-        dirty = true;
-    }
-    // the stream for anything that consumes the call's uploads (kernel launches, memsets, downloads, the synchronisation)
-    hipStream_t exec() {
-        if (!uploads.empty() || !fills.empty()) flush_uploads();
-        dirty = true;
-        return stream;
-    }
-    // issue the recorded downloads (runs of arena-adjacent buffers), wait for the stream, hand the bytes to the caller's buffers
-    hipError_t deliver() {
-        (void)exec();
-        std::sort(downloads.begin(), downloads.end(), [](const Down &a, const Down &b) { return a.off < b.off; });
-        XferOps X;
-        X.n = 0;
-        uint32_t max_units = 0;
-        size_t i = 0;
-        while (i < downloads.size()) {
-            const size_t b = downloads[i].off;
-            size_t e = b + downloads[i].bytes, j = i + 1;
-            while (j < downloads.size() && downloads[j].off <= e + kPadGap) { e = std::max(e, downloads[j].off + downloads[j].bytes); j++; }
-            if (kernel_xfer && e - b <= kKernelXferMax && (b & 15) == 0) {
-                if (X.n == kMaxXferOps) { launch_xfer(X, max_units); X.n = 0; max_units = 0; }
-                const uint32_t units = (uint32_t)((e - b + 15) / 16);
-                X.op[X.n++] = XferOp{mirror.base + b, arena.base + b, units, 0};
-                max_units = std::max(max_units, units);
-            } else {
-                note(hipMemcpyAsync(mirror.base + b, arena.base + b, e - b, hipMemcpyDeviceToHost, stream));
-                xfers[4]++;
-            }
-            xfers[1]++; xfers[3] += (int64_t)(e - b);
-            i = j;
-        }
-        if (X.n) launch_xfer(X, max_units);
-        note(hipStreamSynchronize(stream));
-        dirty = false;
-        if (xfer_err == hipSuccess) {
-            for (const Down &d : downloads) memcpy(d.dst, mirror.base + d.off, d.bytes);
-            for (const Down &d : direct) memcpy(d.dst, mirror.base + d.off, d.bytes);
-            for (const Pending &q : pending) memcpy(q.dst, q.src, q.bytes);
-        }
-        downloads.clear();
-        direct.clear();
-        pending.clear();
-        issued.clear();
-        return xfer_err;
-    }
-};
 
 // ORBVocabulary (DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>) resident on the device
 struct orbx_vocabulary {
@@ -341,43 +124,6 @@ void orbx_matcher_destroy(orbx_matcher *m) {
     delete m;
 }
 
-#define H2D(dst, src, bytes)                                                                                      \
-    do {                                                                                                          \
-        const size_t _b = (bytes);                                                                                \
-        if (_b > 0) {                                                                                             \
-            if (m->stageable((dst), _b)) {  /* recorded; issued with its arena neighbours by exec() */             \
-                const size_t _o = (size_t)((const uint8_t *)(dst) - m->arena.base);                               \
-                memcpy(m->mirror.base + _o, (src), _b);                                                           \
-                m->record_upload(_o, _b);                                                                         \
-            } else {                                                                                              \
-                void *_s = m->stage.take(_b);                                                                     \
-                if (!_s) { set_error("staging arena exhausted"); return ORBX_E_INTERNAL; }                        \
-                memcpy(_s, (src), _b);                                                                            \
-                m->dirty = true;                                                                                  \
-                ORBX_HIP(hipMemcpyAsync((dst), _s, _b, hipMemcpyHostToDevice, m->stream));                        \
-                m->xfers[0]++; m->xfers[2] += (int64_t)_b; m->xfers[4]++;                                         \
-            }                                                                                                     \
-        }                                                                                                         \
-    } while (0)
-#define D2H(dst, src, bytes)                                                                                      \
-    do {                                                                                                          \
-        const size_t _b = (bytes);                                                                                \
-        if (_b > 0) {                                                                                             \
-            if (m->in_arena((src), _b)) {   /* recorded; issued with its arena neighbours by deliver() */          \
-                m->downloads.push_back(orbx_matcher::Down{(void *)(dst), (size_t)((const uint8_t *)(src) - m->arena.base), _b}); \
-            } else {                                                                                              \
-                void *_s = m->stage.take(_b);                                                                     \
-                if (!_s) { set_error("staging arena exhausted"); return ORBX_E_INTERNAL; }                        \
-                ORBX_HIP(hipMemcpyAsync(_s, (src), _b, hipMemcpyDeviceToHost, m->exec()));                        \
-                m->xfers[1]++; m->xfers[3] += (int64_t)_b; m->xfers[4]++;                                         \
-                m->pending.push_back(orbx_matcher::Pending{(void *)(dst), _s, _b});                               \
-            }                                                                                                     \
-        }                                                                                                         \
-    } while (0)
-#define SYNC_AND_DELIVER()                                                                                        \
-    do {                                                                                                          \
-        ORBX_HIP(m->deliver());                                                                                   \
-    } while (0)
 
 int orbx_hamming_csr(orbx_matcher *m, const uint8_t *q, int nq, const uint8_t *t, int nt, const int32_t *row_ptr,
                      const int32_t *cand, uint16_t *dist_out) {
@@ -387,17 +133,17 @@ int orbx_hamming_csr(orbx_matcher *m, const uint8_t *q, int nq, const uint8_t *t
     if (nnz <= 0) return ORBX_OK;
     if (!t || !cand || !dist_out) return ORBX_E_BAD_ARG;
     ORBX_HIP(hipSetDevice(m->device));
-    int r = m->reserve_all(Arena::pad((size_t)nq * 32) + Arena::pad((size_t)nt * 32) + Arena::pad(4 * (size_t)(nq + 1)) +
-                             Arena::pad(4 * (size_t)nnz) + Arena::pad(2 * (size_t)nnz) + 4096);
-    if (r != ORBX_OK) return r;
-    m->begin();
-    uint8_t *dq = m->arena.take<uint8_t>((size_t)nq * 32), *dt = m->arena.take<uint8_t>((size_t)nt * 32);
-    int32_t *drp = m->arena.take<int32_t>(nq + 1), *dc = m->arena.take<int32_t>(nnz);
-    uint16_t *dd = m->arena.take<uint16_t>(nnz);
-    H2D(dq, q, (size_t)nq * 32); H2D(dt, t, (size_t)nt * 32); H2D(drp, row_ptr, 4 * (size_t)(nq + 1)); H2D(dc, cand, 4 * (size_t)nnz);
+    uint8_t *dq, *dt;
+    int32_t *drp, *dc;
+    uint16_t *dd;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        dq = A.up(q, (size_t)nq * 32); dt = A.up(t, (size_t)nt * 32);
+        drp = A.up(row_ptr, (size_t)nq + 1); dc = A.up(cand, (size_t)nnz);
+        dd = A.take<uint16_t>(nnz);
+    }));
     hipLaunchKernelGGL(k_hamming_csr, dim3((nq + 3) / 4), dim3(256), 0, m->exec(), dq, nq, dt, drp, dc, dd);
-    D2H(dist_out, dd, 2 * (size_t)nnz);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(dist_out, dd, 2 * (size_t)nnz));
+    ORBX_TRY(m->sync_and_deliver());
     return ORBX_OK;
 }
 
@@ -408,22 +154,17 @@ int orbx_hamming_best2_csr(orbx_matcher *m, const uint8_t *q, int nq, const uint
     if (nq == 0) return ORBX_OK;
     const int nnz = row_ptr[nq];
     ORBX_HIP(hipSetDevice(m->device));
-    int r = m->reserve_all(Arena::pad((size_t)nq * 32) + Arena::pad((size_t)nt * 32 + 32) + Arena::pad(4 * (size_t)(nq + 1)) +
-                             Arena::pad(4 * (size_t)nnz + 4) + 4 * Arena::pad(4 * (size_t)nq) + 4096);
-    if (r != ORBX_OK) return r;
-    m->begin();
-    uint8_t *dq = m->arena.take<uint8_t>((size_t)nq * 32), *dt = m->arena.take<uint8_t>((size_t)nt * 32 + 32);
-    int32_t *drp = m->arena.take<int32_t>(nq + 1), *dc = m->arena.take<int32_t>(nnz + 1);
-    int32_t *o[4];
-    for (int k = 0; k < 4; k++) o[k] = m->arena.take<int32_t>(nq);
-    H2D(dq, q, (size_t)nq * 32);
-    if (nt > 0) H2D(dt, t, (size_t)nt * 32);
-    H2D(drp, row_ptr, 4 * (size_t)(nq + 1));
-    if (nnz > 0) H2D(dc, cand, 4 * (size_t)nnz);
+    uint8_t *dq, *dt;
+    int32_t *drp, *dc, *o[4];
+    ORBX_TRY(m->carve([&](Carve &A) {
+        dq = A.up(q, (size_t)nq * 32); dt = A.up(t, (size_t)nt * 32, 32);
+        drp = A.up(row_ptr, (size_t)nq + 1); dc = A.up(cand, (size_t)nnz, 1);
+        for (int k = 0; k < 4; k++) o[k] = A.take<int32_t>(nq);
+    }));
     hipLaunchKernelGGL(k_hamming_best2_csr, dim3((nq + 3) / 4), dim3(256), 0, m->exec(), dq, nq, dt, drp, dc, o[0], o[1], o[2], o[3]);
     int32_t *host[4] = {best_pos, best_dist, second_pos, second_dist};
-    for (int k = 0; k < 4; k++) if (host[k]) D2H(host[k], o[k], 4 * (size_t)nq);
-    SYNC_AND_DELIVER();
+    for (int k = 0; k < 4; k++) if (host[k]) ORBX_TRY(m->d2h(host[k], o[k], 4 * (size_t)nq));
+    ORBX_TRY(m->sync_and_deliver());
     return ORBX_OK;
 }
 
@@ -431,16 +172,15 @@ int orbx_knn2(orbx_matcher *m, const uint8_t *q, int nq, const uint8_t *t, int n
     if (!m || nq < 0 || nt < 0 || (nq > 0 && (!q || !idx || !dist))) return ORBX_E_BAD_ARG;
     if (nq == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
-    int r = m->reserve_all(Arena::pad((size_t)nq * 32) + Arena::pad((size_t)nt * 32 + 32) + 2 * Arena::pad(8 * (size_t)nq) + 4096);
-    if (r != ORBX_OK) return r;
-    m->begin();
-    uint8_t *dq = m->arena.take<uint8_t>((size_t)nq * 32), *dt = m->arena.take<uint8_t>((size_t)nt * 32 + 32);
-    int32_t *di = m->arena.take<int32_t>(2 * (size_t)nq), *dd = m->arena.take<int32_t>(2 * (size_t)nq);
-    H2D(dq, q, (size_t)nq * 32);
-    if (nt > 0) H2D(dt, t, (size_t)nt * 32);
+    uint8_t *dq, *dt;
+    int32_t *di, *dd;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        dq = A.up(q, (size_t)nq * 32); dt = A.up(t, (size_t)nt * 32, 32);
+        di = A.take<int32_t>(2 * (size_t)nq); dd = A.take<int32_t>(2 * (size_t)nq);
+    }));
     hipLaunchKernelGGL(k_knn2, dim3((nq + 3) / 4), dim3(256), 0, m->exec(), dq, nq, dt, nt, di, dd, KnnFrames{});
-    D2H(idx, di, 8 * (size_t)nq); D2H(dist, dd, 8 * (size_t)nq);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(idx, di, 8 * (size_t)nq)); ORBX_TRY(m->d2h(dist, dd, 8 * (size_t)nq));
+    ORBX_TRY(m->sync_and_deliver());
     return ORBX_OK;
 }
 
@@ -451,21 +191,20 @@ int orbx_stereo_rowband(orbx_matcher *m, const orbx_keypoint *kl, const uint8_t 
     if (nl == 0) return ORBX_OK;
     if (!kl || !dl || !best_idx_r || !best_dist) return ORBX_E_BAD_ARG;
     ORBX_HIP(hipSetDevice(m->device));
-    int r = m->reserve_all(Arena::pad(28 * (size_t)nl) + Arena::pad(32 * (size_t)nl) + Arena::pad(28 * (size_t)nr + 32) +
-                             Arena::pad(32 * (size_t)nr + 32) + Arena::pad(4 * (size_t)nlevels) + 2 * Arena::pad(4 * (size_t)nl) + 4096);
-    if (r != ORBX_OK) return r;
-    m->begin();
-    orbx_keypoint *dkl = m->arena.take<orbx_keypoint>(nl), *dkr = m->arena.take<orbx_keypoint>(nr + 1);
-    uint8_t *ddl = m->arena.take<uint8_t>(32 * (size_t)nl), *ddr = m->arena.take<uint8_t>(32 * (size_t)nr + 32);
-    float *dsc = m->arena.take<float>(nlevels);
-    int32_t *dbi = m->arena.take<int32_t>(nl), *dbd = m->arena.take<int32_t>(nl);
-    H2D(dkl, kl, 28 * (size_t)nl); H2D(ddl, dl, 32 * (size_t)nl);
-    if (nr > 0) { H2D(dkr, kr, 28 * (size_t)nr); H2D(ddr, dr, 32 * (size_t)nr); }
-    H2D(dsc, scale, 4 * (size_t)nlevels);
+    orbx_keypoint *dkl, *dkr;
+    uint8_t *ddl, *ddr;
+    float *dsc;
+    int32_t *dbi, *dbd;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        dkl = A.up(kl, (size_t)nl); dkr = A.up(kr, (size_t)nr, 1);
+        ddl = A.up(dl, 32 * (size_t)nl); ddr = A.up(dr, 32 * (size_t)nr, 32);
+        dsc = A.up(scale, (size_t)nlevels);
+        dbi = A.take<int32_t>(nl); dbd = A.take<int32_t>(nl);
+    }));
     hipLaunchKernelGGL(k_stereo_rowband, dim3((nl + 3) / 4), dim3(256), 0, m->exec(), dkl, ddl, nl, dkr, ddr, nr, dsc, n_rows, min_d,
                        max_d, dbi, dbd);
-    D2H(best_idx_r, dbi, 4 * (size_t)nl); D2H(best_dist, dbd, 4 * (size_t)nl);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(best_idx_r, dbi, 4 * (size_t)nl)); ORBX_TRY(m->d2h(best_dist, dbd, 4 * (size_t)nl));
+    ORBX_TRY(m->sync_and_deliver());
     return ORBX_OK;
 }
 
@@ -501,39 +240,35 @@ int orbx_compute_stereo_matches(orbx_matcher *m, const orbx_keypoint *kl, const 
         lv[l].off = slab - (size_t)kEdge * pyr_stride[l] - kRoiX;   // so that the kernels' (kEdge + y) * pitch + kRoiX + x lands on (x, y)
         slab += (pyr_stride[l] * (size_t)pyr_h[l] + 255) & ~(size_t)255;
     }
-    const size_t need = 2 * Arena::pad(slab) + Arena::pad(28 * (size_t)N) + Arena::pad(28 * (size_t)Nr) + Arena::pad(32 * (size_t)N) +
-                        Arena::pad(32 * (size_t)Nr) + 5 * Arena::pad(4 * (size_t)N) + Arena::pad(sizeof(LevelInfo) * nlevels) +
-                        Arena::pad(8 * (size_t)nlevels) + Arena::pad(4 * ((size_t)kStereoIndexMaxBuckets + 1)) + Arena::pad(16 * (size_t)Nr) + 8192;
-    int r = m->reserve_all(need);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
-    uint8_t *dL = A.take<uint8_t>(slab), *dR = A.take<uint8_t>(slab);
-    for (int l = 0; l < nlevels; l++) {
-        const size_t o = lv[l].off + (size_t)kEdge * pyr_stride[l] + kRoiX, bytes = pyr_stride[l] * (size_t)(pyr_h[l] - 1) + pyr_w[l];
-        H2D(dL + o, pyr_left[l], bytes);
-        H2D(dR + o, pyr_right[l], bytes);
-    }
     StereoBatch S;
     memset(&S, 0, sizeof(S));
-    orbx_keypoint *dkl = A.take<orbx_keypoint>(N), *dkr = A.take<orbx_keypoint>(Nr);
-    uint8_t *ddl = A.take<uint8_t>(32 * (size_t)N), *ddr = A.take<uint8_t>(32 * (size_t)Nr);
-    H2D(dkl, kl, 28 * (size_t)N); H2D(dkr, kr, 28 * (size_t)Nr); H2D(ddl, dl, 32 * (size_t)N); H2D(ddr, dr, 32 * (size_t)Nr);
-    LevelInfo *dlv = A.take<LevelInfo>(nlevels);
-    H2D(dlv, lv.data(), sizeof(LevelInfo) * nlevels);
-    float *dsc = A.take<float>(2 * (size_t)nlevels);
-    H2D(dsc, scale_factors, 4 * (size_t)nlevels); H2D(dsc + nlevels, inv_scale_factors, 4 * (size_t)nlevels);
-    int32_t *dcnt = A.take<int32_t>(4);
-    const int32_t cnts[2] = {N, Nr};
-    H2D(dcnt, cnts, 8);
-    S.kl = dkl; S.kr = dkr; S.dl = ddl; S.dr = ddr; S.nl = dcnt; S.nr = dcnt + 1; S.capL = N; S.capR = Nr;
-    S.pyrL = dL; S.pyrR = dR; S.pyr_frame_L = 0; S.pyr_frame_R = 0; S.lvL = dlv; S.lvR = dlv;
-    S.scale = dsc; S.inv_scale = dsc + nlevels; S.n_rows = pyr_h[0]; S.bf = bf; S.b = b;
-    S.best_idx = A.take<int32_t>(N); S.best_dist = A.take<int32_t>(N);
-    S.u_right = A.take<float>(N); S.depth = A.take<float>(N); S.nmatches = A.take<int32_t>(4); S.sad = A.take<int32_t>(N);   // the three downloads side by side: one DMA
     stereo_index_params(S, pyr_h[0], scale_factors, nlevels);
-    int32_t *drp = A.take<int32_t>((size_t)S.n_buckets + 1);
-    uint4 *den = A.take<uint4>(Nr);
+    const int32_t cnts[2] = {N, Nr};
+    uint8_t *dL, *dR;
+    float *dsc;
+    int32_t *dcnt, *drp;
+    uint4 *den;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        dL = A.take<uint8_t>(slab); dR = A.take<uint8_t>(slab);
+        S.kl = A.up(kl, (size_t)N); S.kr = A.up(kr, (size_t)Nr);
+        S.dl = A.up(dl, 32 * (size_t)N); S.dr = A.up(dr, 32 * (size_t)Nr);
+        S.lvL = S.lvR = A.up(lv.data(), (size_t)nlevels);
+        dsc = A.take<float>(2 * (size_t)nlevels);
+        dcnt = A.up(cnts, 2, 2);
+        S.best_idx = A.take<int32_t>(N); S.best_dist = A.take<int32_t>(N);
+        S.u_right = A.take<float>(N); S.depth = A.take<float>(N); S.nmatches = A.take<int32_t>(4); S.sad = A.take<int32_t>(N);   // the three downloads side by side: one DMA
+        drp = A.take<int32_t>((size_t)S.n_buckets + 1);
+        den = A.take<uint4>(Nr);
+    }));
+    for (int l = 0; l < nlevels; l++) {
+        const size_t o = lv[l].off + (size_t)kEdge * pyr_stride[l] + kRoiX, bytes = pyr_stride[l] * (size_t)(pyr_h[l] - 1) + pyr_w[l];
+        ORBX_TRY(m->h2d(dL + o, pyr_left[l], bytes));
+        ORBX_TRY(m->h2d(dR + o, pyr_right[l], bytes));
+    }
+    ORBX_TRY(m->h2d(dsc, scale_factors, 4 * (size_t)nlevels)); ORBX_TRY(m->h2d(dsc + nlevels, inv_scale_factors, 4 * (size_t)nlevels));
+    S.nl = dcnt; S.nr = dcnt + 1; S.capL = N; S.capR = Nr;
+    S.pyrL = dL; S.pyrR = dR; S.pyr_frame_L = 0; S.pyr_frame_R = 0;
+    S.scale = dsc; S.inv_scale = dsc + nlevels; S.n_rows = pyr_h[0]; S.bf = bf; S.b = b;
     S.row_ptr = drp; S.row_ent = den;
     hipLaunchKernelGGL(k_stereo_row_index, dim3(1), dim3(256), 4 * ((size_t)S.n_buckets + 1) + 1024, m->exec(), S, drp, den);
     hipLaunchKernelGGL(k_stereo_rowband_batch, dim3((N + 15) / 16, 1), dim3(256), 0, m->exec(), S);
@@ -541,8 +276,8 @@ int orbx_compute_stereo_matches(orbx_matcher *m, const orbx_keypoint *kl, const 
     hipLaunchKernelGGL(k_stereo_reject, dim3(1), dim3(256), 0, m->exec(), S);
     ORBX_HIP(hipGetLastError());
     int32_t nm = 0;
-    D2H(u_right, S.u_right, 4 * (size_t)N); D2H(depth, S.depth, 4 * (size_t)N); D2H(&nm, S.nmatches, 4);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(u_right, S.u_right, 4 * (size_t)N)); ORBX_TRY(m->d2h(depth, S.depth, 4 * (size_t)N)); ORBX_TRY(m->d2h(&nm, S.nmatches, 4));
+    ORBX_TRY(m->sync_and_deliver());
     return nm;
 }
 
@@ -658,62 +393,51 @@ int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr,
     const int nc = n >= 0 ? n : left_only ? fh->roff : fh->cap;   // features the device buffers are sized for
     if (nc > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;  // before anything is enqueued: the resolve pass keeps 10 B per feature in LDS
     ORBX_HIP(hipSetDevice(m->device));
-    size_t need = Arena::pad(28 * (size_t)nc) + Arena::pad(32 * (size_t)nc) + 3 * Arena::pad((size_t)nc) + Arena::pad(4 * (size_t)nc) * 2 +
-                  Arena::pad(4 * (size_t)nq) * 7 + Arena::pad(32 * (size_t)nq) + Arena::pad((size_t)nq) * 2 + Arena::pad(8 * (size_t)nq) * 5 +
-                  Arena::pad(sizeof(WindowProblem)) + Arena::pad(sizeof(ResolveProblem)) + Arena::pad(2 * (kGridCells + 1)) + Arena::pad(2 * (size_t)nc) +
-                  16 * 256 + 4096;
-    int r = m->reserve_all(need);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
     WindowProblem P;
     memset(&P, 0, sizeof(P));
     ResolveProblem R;
     memset(&R, 0, sizeof(R));
-    if (fh) {   // resident rows: nothing of the frame travels
-        P.kps = fh->kps; P.desc = fh->desc;
-    } else {
-        orbx_keypoint *dk = A.take<orbx_keypoint>(n);
-        uint8_t *dd = A.take<uint8_t>(32 * (size_t)n);
-        H2D(dk, F->keypoints_un, 28 * (size_t)n); H2D(dd, F->descriptors, 32 * (size_t)n);
-        P.kps = dk; P.desc = dd;
-    }
-    int32_t *dcnt = A.take<int32_t>(4);
-    const int32_t cnts[2] = {n, nq};
-    H2D(dcnt, cnts, 8);
-    P.n_ptr = fh ? fh->count : dcnt; P.nq_ptr = dcnt + 1;
-    const bool has_ur = fh ? fh->has_ur : F->u_right != nullptr;
-    if (fh && has_ur) P.u_right = fh->u_right;
-    else if (has_ur) { float *p = A.take<float>(n); H2D(p, F->u_right, 4 * (size_t)n); P.u_right = p; }
-    if (a.occupied) { uint8_t *p = A.take<uint8_t>(n); H2D(p, a.occupied, (size_t)n); P.occupied0 = p; }
-    float *f3[3]; const float *h3[3] = {a.qx, a.qy, a.qr};
-    for (int k = 0; k < 3; k++) { f3[k] = A.take<float>(nq); H2D(f3[k], h3[k], 4 * (size_t)nq); }
-    P.qx = f3[0]; P.qy = f3[1]; P.qr = f3[2];
-    int32_t *i2[2]; const int32_t *hi2[2] = {a.qmin, a.qmax};
-    for (int k = 0; k < 2; k++) { i2[k] = A.take<int32_t>(nq); H2D(i2[k], hi2[k], 4 * (size_t)nq); }
-    P.qmin = i2[0]; P.qmax = i2[1];
-    if (a.qxr && has_ur) { float *p = A.take<float>(nq); H2D(p, a.qxr, 4 * (size_t)nq); P.qxr = p; }
-    { uint8_t *p = A.take<uint8_t>(32 * (size_t)nq); H2D(p, a.qdesc, 32 * (size_t)nq); P.qdesc = p; }
-    if (a.qvalid) { uint8_t *p = A.take<uint8_t>(nq); H2D(p, a.qvalid, (size_t)nq); P.qvalid = p; }
     R.mode = a.mode; R.nnratio = a.nnratio; R.check_orientation = a.check_orientation; R.max_dist = a.max_dist;
     R.cleared_value = -2;
-    if (a.q_angle) { float *p = A.take<float>(nq); H2D(p, a.q_angle, 4 * (size_t)nq); R.q_angle = p; }
-    if (a.q_has_obs) { uint8_t *p = A.take<uint8_t>(nq); H2D(p, a.q_has_obs, (size_t)nq); R.q_has_obs = p; }
-    // everything the call uploads lies in ONE run of the arena (one DMA, orbx_matcher::exec): the two problem records directly behind the inputs,
-    // the buffers only the device writes behind them; the downloads (match, nmatches) side by side as well
-    WindowProblem *dP = A.take<WindowProblem>(1);
-    ResolveProblem *dR = A.take<ResolveProblem>(1);
-    P.keys = A.take<u64>((size_t)nq * kTopK); P.meta = A.take<int32_t>(nq);
-    if (fh) { P.gstart = fh->gstart; P.gorder = fh->gorder; }
-    else { P.gstart = A.take<uint16_t>(kGridCells + 1); P.gorder = A.take<uint16_t>(n); }
-    R.entries = A.take<int32_t>(nq);
-    R.match = A.take<int32_t>(nc);
-    R.nmatches = A.take<int32_t>(1);
+    const bool has_ur = fh ? fh->has_ur : F->u_right != nullptr;
     // a small problem skips the grid: k_window_brute walks all features per query (no k_grid_build launch, whose counting sort this one call would use once);
     // a handle's grid is built already
     const bool brute = !fh && m->brute_windows && (size_t)nq * (size_t)n <= kBruteMaxPairs;
+    const int32_t cnts[2] = {n, nq};
+    int32_t *dcnt;
+    WindowProblem *dP;
+    ResolveProblem *dR;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        if (fh) {   // resident rows: nothing of the frame travels
+            P.kps = fh->kps; P.desc = fh->desc;
+        } else {
+            P.kps = A.up(F->keypoints_un, (size_t)n); P.desc = A.up(F->descriptors, 32 * (size_t)n);
+        }
+        dcnt = A.up(cnts, 2, 2);
+        if (fh && has_ur) P.u_right = fh->u_right;
+        else if (has_ur) P.u_right = A.up(F->u_right, (size_t)n);
+        P.occupied0 = A.up_opt(a.occupied, (size_t)n);
+        P.qx = A.up(a.qx, (size_t)nq); P.qy = A.up(a.qy, (size_t)nq); P.qr = A.up(a.qr, (size_t)nq);
+        P.qmin = A.up(a.qmin, (size_t)nq); P.qmax = A.up(a.qmax, (size_t)nq);
+        if (has_ur) P.qxr = A.up_opt(a.qxr, (size_t)nq);
+        P.qdesc = A.up(a.qdesc, 32 * (size_t)nq);
+        P.qvalid = A.up_opt(a.qvalid, (size_t)nq);
+        R.q_angle = A.up_opt(a.q_angle, (size_t)nq);
+        R.q_has_obs = A.up_opt(a.q_has_obs, (size_t)nq);
+        // everything the call uploads lies in ONE run of the arena (one DMA, orbx_matcher::exec): the two problem records directly behind the inputs,
+        // the buffers only the device writes behind them; the downloads (match, nmatches) side by side as well
+        dP = A.take<WindowProblem>(1);
+        dR = A.take<ResolveProblem>(1);
+        P.keys = A.take<u64>((size_t)nq * kTopK); P.meta = A.take<int32_t>(nq);
+        if (fh) { P.gstart = fh->gstart; P.gorder = fh->gorder; }
+        else { P.gstart = A.take<uint16_t>(kGridCells + 1); P.gorder = A.take<uint16_t>(n); }
+        R.entries = A.take<int32_t>(nq);
+        R.match = A.take<int32_t>(nc);
+        R.nmatches = A.take<int32_t>(1);
+    }));
+    P.n_ptr = fh ? fh->count : dcnt; P.nq_ptr = dcnt + 1;
     if (brute) { P.gstart = nullptr; P.gorder = nullptr; }
-    H2D(dP, &P, sizeof(P)); H2D(dR, &R, sizeof(R));
+    ORBX_TRY(m->h2d(dP, &P, sizeof(P))); ORBX_TRY(m->h2d(dR, &R, sizeof(R)));
     const float fb[4] = {fh ? fh->bounds[0] : F->min_x, fh ? fh->bounds[1] : F->max_x, fh ? fh->bounds[2] : F->min_y, fh ? fh->bounds[3] : F->max_y};
     const GridParams g = grid_of(fb);
     if (brute) {
@@ -725,15 +449,15 @@ int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr,
     { const int rr = brute ? launch_resolve<true>(1, m->exec(), dP, dR, g, nc, nq, 4) : launch_resolve<false>(1, m->exec(), dP, dR, g, nc, nq, 4); if (rr != ORBX_OK) return rr; }
     int32_t nm = 0;
     if (n >= 0) {
-        D2H(a.match_out, R.match, 4 * (size_t)n);
+        ORBX_TRY(m->d2h(a.match_out, R.match, 4 * (size_t)n));
     } else {   // N comes back with the results (one small copy of the handle's count)
         fh->h_match.resize((size_t)fh->cap);
-        D2H(fh->h_match.data(), R.match, 4 * (size_t)nc);
-        if (left_only) D2H(fh->h_count, fh->count, 8);
-        else D2H(&fh->n, fh->count, 4);
+        ORBX_TRY(m->d2h(fh->h_match.data(), R.match, 4 * (size_t)nc));
+        if (left_only) ORBX_TRY(m->d2h(fh->h_count, fh->count, 8));
+        else ORBX_TRY(m->d2h(&fh->n, fh->count, 4));
     }
-    D2H(&nm, R.nmatches, 4);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(&nm, R.nmatches, 4));
+    ORBX_TRY(m->sync_and_deliver());
     if (n < 0 && left_only) {
         fh->n_left = std::min(std::max(fh->h_count[0], 0), fh->roff);
         fh->n_right = std::min(std::max(fh->h_count[1], 0), fh->cap - fh->roff);
@@ -836,17 +560,16 @@ int orbx_frame_create(orbx_matcher *m, int cap, orbx_frame **out) {
     orbx_frame *f = new orbx_frame();
     f->owner = m;
     f->cap = cap;
-    size_t o = 0;
-    auto carve = [&o](size_t bytes) { const size_t r = o; o += Arena::pad(bytes); return r; };
-    f->off_kps = carve(28 * (size_t)cap); f->off_desc = carve(32 * (size_t)cap); f->off_ur = carve(4 * (size_t)cap);
-    f->off_count = carve(8); f->off_scale = carve(4 * (size_t)kFrameMaxLevels);
-    f->off_gstart = carve(2 * ((size_t)kGridCells + 1)); f->off_gorder = carve(2 * (size_t)cap);
-    const size_t off_gsr = carve(2 * ((size_t)kGridCells + 1)), off_gor = carve(2 * (size_t)cap);
-    f->off_l2r = carve(4 * (size_t)cap); f->off_r2l = carve(4 * (size_t)cap);
-    const size_t off_bw = carve(4 * (size_t)cap), off_bn = carve(4 * (size_t)cap), off_fn = carve(4 * (size_t)cap), off_fp = carve(4 * ((size_t)cap + 1)),
-                 off_fi = carve(4 * (size_t)cap), off_fm = carve(16), off_an = carve(4 * (size_t)cap);
-    f->stage_bytes = o;   // the rows (keypoints, descriptors, mvuRight; a fisheye frame's partners) at the device layout's offsets
-    hipError_t e = hipMalloc((void **)&f->dev, o);
+    Layout L;
+    f->off_kps = L.add(28 * (size_t)cap); f->off_desc = L.add(32 * (size_t)cap); f->off_ur = L.add(4 * (size_t)cap);
+    f->off_count = L.add(8); f->off_scale = L.add(4 * (size_t)kFrameMaxLevels);
+    f->off_gstart = L.add(2 * ((size_t)kGridCells + 1)); f->off_gorder = L.add(2 * (size_t)cap);
+    const size_t off_gsr = L.add(2 * ((size_t)kGridCells + 1)), off_gor = L.add(2 * (size_t)cap);
+    f->off_l2r = L.add(4 * (size_t)cap); f->off_r2l = L.add(4 * (size_t)cap);
+    const size_t off_bw = L.add(4 * (size_t)cap), off_bn = L.add(4 * (size_t)cap), off_fn = L.add(4 * (size_t)cap), off_fp = L.add(4 * ((size_t)cap + 1)),
+                 off_fi = L.add(4 * (size_t)cap), off_fm = L.add(16), off_an = L.add(4 * (size_t)cap);
+    f->stage_bytes = L.used;   // the rows (keypoints, descriptors, mvuRight; a fisheye frame's partners) at the device layout's offsets
+    hipError_t e = hipMalloc((void **)&f->dev, L.used);
     if (e == hipSuccess) e = hipHostMalloc((void **)&f->stage, f->stage_bytes, hipHostMallocCoherent);   // read by k_xfer's lanes
     if (e == hipSuccess) e = hipHostMalloc((void **)&f->h_count, 64, hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_src, hipEventDisableTiming);
@@ -890,24 +613,8 @@ int orbx_frame_load_host(orbx_frame *f, const orbx_frame_desc *d) {
     memcpy(f->stage + f->off_desc, d->descriptors, b_desc);
     if (b_ur) memcpy(f->stage + f->off_ur, d->u_right, b_ur);
     // the rows in ONE k_xfer launch in the owner's queue (ORBX_MATCHER_DMA=1: by the DMA engine); count and scale factors travel as k_frame_prepare's arguments
-    XferOps X;
-    X.n = 0;
-    uint32_t max_units = 0;
-    const size_t offs[3] = {f->off_kps, f->off_desc, f->off_ur}, bytes[3] = {b_kps, b_desc, b_ur};
-    for (int k = 0; k < 3; k++) {
-        if (!bytes[k]) continue;
-        if (m->kernel_xfer) {
-            const uint32_t units = (uint32_t)((bytes[k] + 15) / 16);   // (rounded up to 16 bytes: inside the region's 256-byte padding)
-            X.op[X.n++] = XferOp{f->dev + offs[k], f->stage + offs[k], units, 0};
-            max_units = std::max(max_units, units);
-        } else {
-            ORBX_HIP(hipMemcpyAsync(f->dev + offs[k], f->stage + offs[k], bytes[k], hipMemcpyHostToDevice, m->stream));
-            m->xfers[4]++;
-        }
-        m->xfers[0]++; m->xfers[2] += (int64_t)bytes[k];
-    }
-    if (X.n) m->launch_xfer(X, max_units);
-    if (m->xfer_err != hipSuccess) { set_error(hipGetErrorString(m->xfer_err)); return ORBX_E_HIP; }
+    const orbx_matcher::Span rows[3] = {{f->off_kps, b_kps}, {f->off_desc, b_desc}, {f->off_ur, b_ur}};
+    ORBX_TRY(m->upload_ranges(f->dev, f->stage, rows, 3));
     FramePrepare P;
     const float b[4] = {d->min_x, d->max_x, d->min_y, d->max_y};
     frame_prepare_common(f, P, d->scale_factors, d->nlevels, b);
@@ -1030,80 +737,69 @@ int run_projection_twin(orbx_matcher *m, const TwinArgs &a, orbx_frame *fh = nul
     const int nc = N >= 0 ? N : fh->cap;   // features the device buffers are sized for
     if (nc > 60000) return ORBX_E_TOO_LARGE;   // 16-bit feature indices in the candidate keys; occupancy bytes in LDS
     ORBX_HIP(hipSetDevice(m->device));
-    const size_t need = Arena::pad(28 * (size_t)nc) + Arena::pad(32 * (size_t)nc) + Arena::pad((size_t)nc) + 2 * Arena::pad(4 * (size_t)nc) +
-                        2 * (5 * Arena::pad(4 * (size_t)nq) + Arena::pad((size_t)nq) + Arena::pad(8 * (size_t)kTopK * nq) + Arena::pad(4 * (size_t)nq) +
-                             Arena::pad(2 * (kGridCells + 1)) + Arena::pad(2 * (size_t)nc)) +
-                        Arena::pad(32 * (size_t)nq) + Arena::pad((size_t)nq) + Arena::pad(4 * (size_t)nq) + Arena::pad(8 * (size_t)nq) +
-                        Arena::pad(2 * sizeof(WindowProblem)) + 64 * 256 + 4096;
-    int r = m->reserve_all(need);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
     WindowProblem P[2];
     memset(P, 0, sizeof(P));
-    int32_t *dcnt = A.take<int32_t>(4);
-    const int32_t cnts[3] = {nl, nr, nq};
-    H2D(dcnt, cnts, 12);
-    if (fh) {   // resident rows and grids: nothing of the frame travels
-        P[0].kps = fh->kps; P[0].desc = fh->desc; P[0].n_ptr = fh->count; P[0].gstart = fh->gstart; P[0].gorder = fh->gorder;
-        P[1].kps = fh->kps + fh->roff; P[1].desc = fh->desc + (size_t)fh->roff * 32; P[1].n_ptr = fh->count + 1;
-        P[1].gstart = fh->gstart_r; P[1].gorder = fh->gorder_r;
-    } else {
-        orbx_keypoint *dk = A.take<orbx_keypoint>(N);
-        uint8_t *dd = A.take<uint8_t>(32 * (size_t)N);
-        if (nl) H2D(dk, F->keypoints_un, 28 * (size_t)nl);
-        if (nr) H2D(dk + nl, a.kps_right, 28 * (size_t)nr);
-        H2D(dd, F->descriptors, 32 * (size_t)N);
-        for (int s = 0; s < 2; s++) {
-            P[s].kps = dk + (s ? nl : 0); P[s].desc = dd + (s ? (size_t)nl * 32 : 0); P[s].n_ptr = dcnt + s;
-            P[s].gstart = A.take<uint16_t>(kGridCells + 1); P[s].gorder = A.take<uint16_t>(std::max(s ? nr : nl, 1));
-        }
-    }
-    uint8_t *dqd = A.take<uint8_t>(32 * (size_t)nq);
-    H2D(dqd, a.qdesc, 32 * (size_t)nq);
-    for (int s = 0; s < 2; s++) {
-        WindowProblem &w = P[s];
-        w.nq_ptr = dcnt + 2;
-        float *f3[3]; const float *h3[3] = {a.qx[s], a.qy[s], a.qr[s]};
-        for (int k = 0; k < 3; k++) { f3[k] = A.take<float>(nq); H2D(f3[k], h3[k], 4 * (size_t)nq); }
-        w.qx = f3[0]; w.qy = f3[1]; w.qr = f3[2];
-        int32_t *i2[2]; const int32_t *hi2[2] = {a.qmin[s], a.qmax[s]};
-        for (int k = 0; k < 2; k++) { i2[k] = A.take<int32_t>(nq); H2D(i2[k], hi2[k], 4 * (size_t)nq); }
-        w.qmin = i2[0]; w.qmax = i2[1];
-        { uint8_t *p = A.take<uint8_t>(nq); H2D(p, a.qvalid[s], (size_t)nq); w.qvalid = p; }
-        w.qdesc = dqd;
-        w.keys = A.take<u64>((size_t)nq * kTopK); w.meta = A.take<int32_t>(nq);
-    }
     TwinProblem T;
     memset(&T, 0, sizeof(T));
     T.mode = a.mode; T.nq = nq; T.nnratio = a.nnratio; T.max_dist = (float)ORBX_TH_HIGH;
     T.check_orientation = a.check_orientation; T.cleared_value = -2;
-    if (fh) { T.l2r = fh->l2r; T.r2l = fh->r2l; }
-    else {
-        if (a.l2r && nl) { int32_t *p = A.take<int32_t>(nl); H2D(p, a.l2r, 4 * (size_t)nl); T.l2r = p; }
-        if (a.r2l && nr) { int32_t *p = A.take<int32_t>(nr); H2D(p, a.r2l, 4 * (size_t)nr); T.r2l = p; }
+    const int32_t cnts[3] = {nl, nr, nq};
+    int32_t *dcnt;
+    orbx_keypoint *dk = nullptr;
+    uint8_t *dd = nullptr;
+    WindowProblem *dP;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        dcnt = A.up(cnts, 3, 1);
+        if (!fh) {   // (resident rows and grids: nothing of the frame travels)
+            dk = A.take<orbx_keypoint>(N);
+            dd = A.up(F->descriptors, 32 * (size_t)N);
+            for (int s = 0; s < 2; s++) { P[s].gstart = A.take<uint16_t>(kGridCells + 1); P[s].gorder = A.take<uint16_t>(std::max(s ? nr : nl, 1)); }
+        }
+        const uint8_t *dqd = A.up(a.qdesc, 32 * (size_t)nq);
+        for (int s = 0; s < 2; s++) {
+            WindowProblem &w = P[s];
+            w.qx = A.up(a.qx[s], (size_t)nq); w.qy = A.up(a.qy[s], (size_t)nq); w.qr = A.up(a.qr[s], (size_t)nq);
+            w.qmin = A.up(a.qmin[s], (size_t)nq); w.qmax = A.up(a.qmax[s], (size_t)nq);
+            w.qvalid = A.up(a.qvalid[s], (size_t)nq);
+            w.qdesc = dqd;
+            w.keys = A.take<u64>((size_t)nq * kTopK); w.meta = A.take<int32_t>(nq);
+        }
+        if (fh) { T.l2r = fh->l2r; T.r2l = fh->r2l; }
+        else {
+            if (nl) T.l2r = A.up_opt(a.l2r, (size_t)nl);
+            if (nr) T.r2l = A.up_opt(a.r2l, (size_t)nr);
+        }
+        T.occupied0 = A.up_opt(a.occupied, (size_t)N);
+        T.q_has_obs = A.up_opt(a.q_has_obs, (size_t)nq);
+        T.q_angle = A.up_opt(a.q_angle, (size_t)nq);
+        T.match = A.take<int32_t>(nc); T.nmatches = A.take<int32_t>(1); T.entries = A.take<int32_t>(2 * (size_t)nq);
+        dP = A.take<WindowProblem>(2);
+    }));
+    if (fh) {
+        P[0].kps = fh->kps; P[0].desc = fh->desc; P[0].n_ptr = fh->count; P[0].gstart = fh->gstart; P[0].gorder = fh->gorder;
+        P[1].kps = fh->kps + fh->roff; P[1].desc = fh->desc + (size_t)fh->roff * 32; P[1].n_ptr = fh->count + 1;
+        P[1].gstart = fh->gstart_r; P[1].gorder = fh->gorder_r;
+    } else {
+        if (nl) ORBX_TRY(m->h2d(dk, F->keypoints_un, 28 * (size_t)nl));
+        if (nr) ORBX_TRY(m->h2d(dk + nl, a.kps_right, 28 * (size_t)nr));
+        for (int s = 0; s < 2; s++) { P[s].kps = dk + (s ? nl : 0); P[s].desc = dd + (s ? (size_t)nl * 32 : 0); P[s].n_ptr = dcnt + s; }
     }
-    if (a.occupied) { uint8_t *p = A.take<uint8_t>(N); H2D(p, a.occupied, (size_t)N); T.occupied0 = p; }
-    if (a.q_has_obs) { uint8_t *p = A.take<uint8_t>(nq); H2D(p, a.q_has_obs, (size_t)nq); T.q_has_obs = p; }
-    if (a.q_angle) { float *p = A.take<float>(nq); H2D(p, a.q_angle, 4 * (size_t)nq); T.q_angle = p; }
-    T.match = A.take<int32_t>(nc); T.nmatches = A.take<int32_t>(1); T.entries = A.take<int32_t>(2 * (size_t)nq);
-    WindowProblem *dP = A.take<WindowProblem>(2);
-    H2D(dP, P, sizeof(P));
+    P[0].nq_ptr = P[1].nq_ptr = dcnt + 2;
+    ORBX_TRY(m->h2d(dP, P, sizeof(P)));
     const float fb[4] = {F->min_x, F->max_x, F->min_y, F->max_y};
     const GridParams g = grid_of(fb);
     if (!fh) ORBX_LAUNCH_GRID_BUILD( dim3(2), dim3(64), 0, m->exec(), dP, g);
-    r = launch_twin(m, dP, T, g, nc, nq);
-    if (r != ORBX_OK) return r;
+    ORBX_TRY(launch_twin(m, dP, T, g, nc, nq));
     int32_t nm = 0;
     if (N >= 0) {
-        D2H(a.match_out, T.match, 4 * (size_t)N);
+        ORBX_TRY(m->d2h(a.match_out, T.match, 4 * (size_t)N));
     } else {   // the counts come back with the results
         fh->h_match.resize((size_t)fh->cap);
-        D2H(fh->h_match.data(), T.match, 4 * (size_t)nc);
-        D2H(fh->h_count, fh->count, 8);
+        ORBX_TRY(m->d2h(fh->h_match.data(), T.match, 4 * (size_t)nc));
+        ORBX_TRY(m->d2h(fh->h_count, fh->count, 8));
     }
-    D2H(&nm, T.nmatches, 4);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(&nm, T.nmatches, 4));
+    ORBX_TRY(m->sync_and_deliver());
     if (N < 0) {
         fh->n_left = fh->h_count[0]; fh->n_right = fh->h_count[1]; fh->n = fh->n_left + fh->n_right; fh->n_known = true;
         memcpy(a.match_out, fh->h_match.data(), 4 * (size_t)std::max(fh->n, 0));
@@ -1325,36 +1021,27 @@ int orbx_search_for_initialization(orbx_matcher *m, const orbx_keypoint *kps1_un
     if (n1 == 0 || n2 == 0) return 0;
     if (n1 > 65535 || n2 > 65535) return ORBX_E_TOO_LARGE;
     ORBX_HIP(hipSetDevice(m->device));
-    GridParams g;
-    g.minx = F2->min_x; g.miny = F2->min_y;
-    g.inv_w = 64.0f / (F2->max_x - F2->min_x);
-    g.inv_h = 48.0f / (F2->max_y - F2->min_y);
+    const float fb[4] = {F2->min_x, F2->max_x, F2->min_y, F2->max_y};
+    const GridParams g = grid_of(fb);
     if (n1 > kMaxResolveFeatures || n2 > kMaxResolveFeatures) {
-        const size_t need = Arena::pad(28 * (size_t)n1) + Arena::pad(32 * (size_t)n1) + Arena::pad(28 * (size_t)n2) + Arena::pad(32 * (size_t)n2) +
-                            Arena::pad(8 * (size_t)n1) + 2 * Arena::pad(4 * (size_t)n1) + 2 * Arena::pad(4 * (size_t)n2) + 4096;
-        int r = m->reserve_all(need);
-        if (r != ORBX_OK) return r;
-        Arena &A = m->arena;
-        m->begin();
         InitProblem P;
         memset(&P, 0, sizeof(P));
-        orbx_keypoint *dk1 = A.take<orbx_keypoint>(n1), *dk2 = A.take<orbx_keypoint>(n2);
-        uint8_t *dd1 = A.take<uint8_t>(32 * (size_t)n1), *dd2 = A.take<uint8_t>(32 * (size_t)n2);
-        float *dprev = A.take<float>(2 * (size_t)n1);
-        H2D(dk1, kps1_un, 28 * (size_t)n1); H2D(dd1, desc1, 32 * (size_t)n1);
-        H2D(dk2, F2->keypoints_un, 28 * (size_t)n2); H2D(dd2, F2->descriptors, 32 * (size_t)n2);
-        H2D(dprev, prev_matched, 8 * (size_t)n1);
-        P.kps1 = dk1; P.desc1 = dd1; P.n1 = n1; P.kps2 = dk2; P.desc2 = dd2; P.n2 = n2; P.prev_matched = dprev;
-        P.window = (float)window_size; P.nnratio = nnratio; P.check_orientation = check_orientation ? 1 : 0;
-        P.matches12 = A.take<int32_t>(n1); P.entries = A.take<int32_t>(n1);
-        P.matches21 = A.take<int32_t>(n2); P.matched_dist = A.take<int32_t>(n2);
-        P.nmatches = A.take<int32_t>(4);
+        P.n1 = n1; P.n2 = n2; P.window = (float)window_size; P.nnratio = nnratio; P.check_orientation = check_orientation ? 1 : 0;
+        float *dprev;
+        ORBX_TRY(m->carve([&](Carve &A) {
+            P.kps1 = A.up(kps1_un, (size_t)n1); P.kps2 = A.up(F2->keypoints_un, (size_t)n2);
+            P.desc1 = A.up(desc1, 32 * (size_t)n1); P.desc2 = A.up(F2->descriptors, 32 * (size_t)n2);
+            P.prev_matched = dprev = A.up(prev_matched, 2 * (size_t)n1);
+            P.matches12 = A.take<int32_t>(n1); P.entries = A.take<int32_t>(n1);
+            P.matches21 = A.take<int32_t>(n2); P.matched_dist = A.take<int32_t>(n2);
+            P.nmatches = A.take<int32_t>(4);
+        }));
         hipLaunchKernelGGL(k_replay_init, dim3(1), dim3(64), 0, m->exec(), P, g);
         int32_t nm = 0;
-        D2H(matches12, P.matches12, 4 * (size_t)n1);
-        D2H(prev_matched, dprev, 8 * (size_t)n1);
-        D2H(&nm, P.nmatches, 4);
-        SYNC_AND_DELIVER();
+        ORBX_TRY(m->d2h(matches12, P.matches12, 4 * (size_t)n1));
+        ORBX_TRY(m->d2h(prev_matched, dprev, 8 * (size_t)n1));
+        ORBX_TRY(m->d2h(&nm, P.nmatches, 4));
+        ORBX_TRY(m->sync_and_deliver());
         return nm;
     }
     // the queries: keypoints of F1 on level 0, in index order (:661-666); window = vbPrevMatched[i1] +- windowSize on level [level1, level1] (:668)
@@ -1375,54 +1062,44 @@ int orbx_search_for_initialization(orbx_matcher *m, const orbx_keypoint *kps1_un
     const size_t lds = 4 * (size_t)n2 + 2 * (size_t)n2 * 2 + 2 * (size_t)n1 + 64;
     // every candidate key of every query for the replay's re-evaluations (WindowProblem::all_keys): up to 512 per query within 8 MB
     const int all_cap = (int)std::min<size_t>(512, std::max<size_t>(64, ((size_t)8 << 20) / (8 * (size_t)nq)));
-    const size_t need = Arena::pad(28 * (size_t)n1) + Arena::pad(28 * (size_t)n2) + Arena::pad(32 * (size_t)n2) + Arena::pad(8 * (size_t)n1) +
-                        Arena::pad(4 * (size_t)nq) * 6 + Arena::pad(32 * (size_t)nq) + Arena::pad(8 * (size_t)nq * kTopK) + Arena::pad(4 * (size_t)nq) * 2 +
-                        Arena::pad(sizeof(WindowProblem)) + Arena::pad(2 * (kGridCells + 1)) + Arena::pad(2 * (size_t)n2) + Arena::pad(4 * (size_t)n1) + 16 * 256 + 4096 +
-                        Arena::pad(4 * (size_t)nq) + Arena::pad(8 * (size_t)nq * all_cap);
-    int r = m->reserve_all(need);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
     WindowProblem P;
     memset(&P, 0, sizeof(P));
     InitReplay R;
     memset(&R, 0, sizeof(R));
-    // every upload in one run of the arena, the problem record directly behind the inputs; device-only buffers behind it; the three downloads side by side
-    orbx_keypoint *dk1 = A.take<orbx_keypoint>(n1), *dk2 = A.take<orbx_keypoint>(n2);
-    uint8_t *dd2 = A.take<uint8_t>(32 * (size_t)n2);
-    H2D(dk1, kps1_un, 28 * (size_t)n1); H2D(dk2, F2->keypoints_un, 28 * (size_t)n2); H2D(dd2, F2->descriptors, 32 * (size_t)n2);
-    P.kps = dk2; P.desc = dd2;
-    int32_t *dcnt = A.take<int32_t>(4);
+    P.all_cap = all_cap;
+    R.n1 = n1; R.n2 = n2; R.nq = nq; R.nnratio = nnratio; R.check_orientation = check_orientation ? 1 : 0;
     const int32_t cnts[2] = {n2, nq};
-    H2D(dcnt, cnts, 8);
+    int32_t *dcnt;
+    WindowProblem *dP;
+    // every upload in one run of the arena, the problem record directly behind the inputs; device-only buffers behind it; the three downloads side by side
+    ORBX_TRY(m->carve([&](Carve &A) {
+        R.kps1 = A.up(kps1_un, (size_t)n1); P.kps = A.up(F2->keypoints_un, (size_t)n2);
+        P.desc = A.up(F2->descriptors, 32 * (size_t)n2);
+        dcnt = A.up(cnts, 2, 2);
+        P.qx = A.up(qx.data(), (size_t)nq); P.qy = A.up(qy.data(), (size_t)nq); P.qr = A.up(qr.data(), (size_t)nq);
+        P.qmin = P.qmax = A.up(qlv.data(), (size_t)nq); R.q_index = A.up(qidx.data(), (size_t)nq);
+        P.qdesc = A.up(qd.data(), 32 * (size_t)nq);
+        dP = A.take<WindowProblem>(1);
+        P.keys = A.take<u64>((size_t)nq * kTopK); P.meta = A.take<int32_t>(nq);
+        P.gstart = A.take<uint16_t>(kGridCells + 1); P.gorder = A.take<uint16_t>(n2);
+        P.all_cnt = A.take<int32_t>(nq); P.all_keys = A.take<u64>((size_t)nq * all_cap);
+        R.entries = A.take<int32_t>(nq);
+        R.matches12 = A.take<int32_t>(n1);
+        R.prev_matched = A.up(prev_matched, 2 * (size_t)n1);
+        R.nmatches = A.take<int32_t>(4);
+    }));
     P.n_ptr = dcnt; P.nq_ptr = dcnt + 1;
-    float *dqx = A.take<float>(nq), *dqy = A.take<float>(nq), *dqr = A.take<float>(nq);
-    int32_t *dql = A.take<int32_t>(nq), *dqi = A.take<int32_t>(nq);
-    uint8_t *dqd = A.take<uint8_t>(32 * (size_t)nq);
-    H2D(dqx, qx.data(), 4 * (size_t)nq); H2D(dqy, qy.data(), 4 * (size_t)nq); H2D(dqr, qr.data(), 4 * (size_t)nq);
-    H2D(dql, qlv.data(), 4 * (size_t)nq); H2D(dqi, qidx.data(), 4 * (size_t)nq); H2D(dqd, qd.data(), 32 * (size_t)nq);
-    P.qx = dqx; P.qy = dqy; P.qr = dqr; P.qmin = dql; P.qmax = dql; P.qdesc = dqd;
-    WindowProblem *dP = A.take<WindowProblem>(1);
-    P.keys = A.take<u64>((size_t)nq * kTopK); P.meta = A.take<int32_t>(nq);
-    P.gstart = A.take<uint16_t>(kGridCells + 1); P.gorder = A.take<uint16_t>(n2);
-    P.all_cap = all_cap; P.all_cnt = A.take<int32_t>(nq); P.all_keys = A.take<u64>((size_t)nq * all_cap);
-    R.q_index = dqi; R.kps1 = dk1; R.n1 = n1; R.n2 = n2; R.nq = nq; R.nnratio = nnratio; R.check_orientation = check_orientation ? 1 : 0;
-    R.entries = A.take<int32_t>(nq);
-    R.matches12 = A.take<int32_t>(n1);
-    R.prev_matched = A.take<float>(2 * (size_t)n1);
-    R.nmatches = A.take<int32_t>(4);
-    H2D(R.prev_matched, prev_matched, 8 * (size_t)n1);
-    H2D(dP, &P, sizeof(P));
+    ORBX_TRY(m->h2d(dP, &P, sizeof(P)));
     ORBX_LAUNCH_GRID_BUILD(dim3(1), dim3(64), 0, m->exec(), dP, g);
     hipLaunchKernelGGL(k_window_best2_t<64>, dim3(1, (unsigned)((nq + 3) / 4), 1), dim3(256), 0, m->exec(), dP, g, 1);   // a wave per query (100-px windows: hundreds of candidates)
     if (lds > 64 * 1024) ORBX_HIP(hipFuncSetAttribute((const void *)k_replay_init_lists, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_replay_init_lists, dim3(1), dim3(64), lds, m->exec(), dP, R, g);
     ORBX_HIP(hipGetLastError());
     int32_t nm[4] = {0, 0, 0, 0};
-    D2H(matches12, R.matches12, 4 * (size_t)n1);
-    D2H(prev_matched, R.prev_matched, 8 * (size_t)n1);
-    D2H(nm, R.nmatches, 16);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(matches12, R.matches12, 4 * (size_t)n1));
+    ORBX_TRY(m->d2h(prev_matched, R.prev_matched, 8 * (size_t)n1));
+    ORBX_TRY(m->d2h(nm, R.nmatches, 16));
+    ORBX_TRY(m->sync_and_deliver());
     for (int k = 0; k < 3; k++) m->replay_stats[k] = nm[k + 1];
     return nm[0];
 }
@@ -1438,92 +1115,60 @@ int run_bow_replay(orbx_matcher *m, int mode, const uint8_t *desc_a, const float
     if (na > 65535 || nb > 65535) return ORBX_E_TOO_LARGE;
     ORBX_HIP(hipSetDevice(m->device));
     const size_t ia = (size_t)fa->node_ptr[fa->n_nodes], ib = (size_t)fb->node_ptr[fb->n_nodes];
-    const size_t need = Arena::pad(33 * (size_t)na) + Arena::pad(33 * (size_t)nb) + 3 * Arena::pad(4 * (size_t)std::max(na, nb)) * 2 +
-                        Arena::pad(8 * (size_t)fa->n_nodes + 8) + Arena::pad(8 * (size_t)fb->n_nodes + 8) + Arena::pad(4 * ia) + Arena::pad(4 * ib) +
-                        Arena::pad(4 * (size_t)fa->n_nodes + 4) + 1024 +
-                        Arena::pad(4 * (size_t)na) + Arena::pad(4 * (size_t)nb) + 8192 +
-                        (gate ? Arena::pad(sizeof(orbx_keypoint) * (size_t)na) + Arena::pad(sizeof(orbx_keypoint) * (size_t)nb) +
-                                    Arena::pad(4 * (size_t)na) + Arena::pad(4 * (size_t)nb) + 4 * Arena::pad(4 * 64) : 0) +
-                        (kgate ? Arena::pad(sizeof(orbx_keypoint) * (size_t)na) + Arena::pad(sizeof(orbx_keypoint) * (size_t)nb) + 2 * Arena::pad(4 * 64) +
-                                     Arena::pad(sizeof(Kb8Gate)) : 0);
-    int r = m->reserve_all(need);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
+    if (!desc_a || !desc_b || (check_orientation && (!angle_a || !angle_b))) return ORBX_E_BAD_ARG;
+    if (gate && (!gate->kps1_un || !gate->kps2_un || !gate->scale_factors2 || !gate->level_sigma2_2)) return ORBX_E_BAD_ARG;
+    const bool kb8_kernel = kgate && !kgate->coarse;   // bCoarse: no gate at all for such key frames (no epipole test either, :1026) = k_replay_bow without a gate
+    if (kb8_kernel && (!kgate->kps1 || !kgate->kps2 || !kgate->level_sigma2_1 || !kgate->level_sigma2_2)) return ORBX_E_BAD_ARG;
     BowProblem P;
     memset(&P, 0, sizeof(P));
-    auto up_fv = [&](const orbx_featvec *f, FeatVecDev &d, size_t nidx) -> int {
-        uint32_t *id = A.take<uint32_t>(f->n_nodes + 1);
-        int32_t *ptr = A.take<int32_t>(f->n_nodes + 1), *idx = A.take<int32_t>(nidx + 1);
-        if (f->n_nodes > 0) H2D(id, f->node_id, 4 * (size_t)f->n_nodes);
-        H2D(ptr, f->node_ptr, 4 * (size_t)(f->n_nodes + 1));
-        if (nidx > 0) H2D(idx, f->index, 4 * nidx);
-        d.node_id = id; d.node_ptr = ptr; d.index = idx; d.n_nodes = f->n_nodes;
-        return ORBX_OK;
-    };
-    if ((r = up_fv(fa, P.fa, ia)) != ORBX_OK || (r = up_fv(fb, P.fb, ib)) != ORBX_OK) return r;
-    {   // the merge-join of the two sorted node-id lists (:246-250, :800-805, :961-965) on the host: node ia of A pairs with node pair_b[ia] of B
-        std::vector<int32_t> pair((size_t)fa->n_nodes + 1, -1);
-        for_common_nodes(fa, fb, [&](int a_, int b_) { pair[a_] = b_; });
-        int32_t *dpair = A.take<int32_t>(fa->n_nodes + 1);
-        H2D(dpair, pair.data(), 4 * ((size_t)fa->n_nodes + 1));
-        P.pair_b = dpair;
-    }
-    auto up = [&](const void *src, size_t bytes) -> const uint8_t * {
-        if (!src) return nullptr;
-        uint8_t *d = A.take<uint8_t>(bytes);
-        if (bytes > 0) {   // recorded like H2D(): issued with its arena neighbours by exec()
-            if (!m->stageable(d, bytes)) return nullptr;
-            const size_t o = (size_t)(d - m->arena.base);
-            memcpy(m->mirror.base + o, src, bytes);
-            m->record_upload(o, bytes);
-        }
-        return d;
-    };
     P.mode = mode; P.nb_left = nb_left;
     { const char *dbg = getenv("ORBX_BOW_DEBUG"); P.debug_stop = dbg ? atoi(dbg) : 0; }
-    P.desc_a = up(desc_a, 32 * (size_t)na); P.desc_b = up(desc_b, 32 * (size_t)nb);
-    P.angle_a = (const float *)up(angle_a, 4 * (size_t)na); P.angle_b = (const float *)up(angle_b, 4 * (size_t)nb);
-    P.skip_a = up(skip_a, na); P.skip_b = up(skip_b, nb);
-    if (!P.desc_a || !P.desc_b || (check_orientation && (!P.angle_a || !P.angle_b))) return ORBX_E_BAD_ARG;
     P.na = na; P.nb = nb; P.nnratio = nnratio; P.check_orientation = check_orientation ? 1 : 0;
+    P.fa.n_nodes = fa->n_nodes; P.fb.n_nodes = fb->n_nodes;
+    // the merge-join of the two sorted node-id lists (:246-250, :800-805, :961-965) on the host: node ia of A pairs with node pair_b[ia] of B
+    std::vector<int32_t> pair((size_t)fa->n_nodes + 1, -1);
+    for_common_nodes(fa, fb, [&](int a_, int b_) { pair[a_] = b_; });
+    Kb8Gate K;
+    memset(&K, 0, sizeof(K));
+    TriGate &G = P.gate;
     if (gate) {  // the pinhole gates of SearchForTriangulation run inside the kernel (mode 2)
-        TriGate &G = P.gate;
         G.enabled = 1; G.coarse = gate->coarse ? 1 : 0; G.strict = gate->strict_fp ? 1 : 0;
-        G.k1 = (const orbx_keypoint *)up(gate->kps1_un, sizeof(orbx_keypoint) * (size_t)na);
-        G.k2 = (const orbx_keypoint *)up(gate->kps2_un, sizeof(orbx_keypoint) * (size_t)nb);
-        G.ur1 = (const float *)up(gate->u_right1, 4 * (size_t)na);
-        G.ur2 = (const float *)up(gate->u_right2, 4 * (size_t)nb);
-        G.scale2 = (const float *)up(gate->scale_factors2, 4 * (size_t)gate->nlevels);
-        G.sigma2_2 = (const float *)up(gate->level_sigma2_2, 4 * (size_t)gate->nlevels);
-        if (!G.k1 || !G.k2 || !G.scale2 || !G.sigma2_2) return ORBX_E_BAD_ARG;
         for (int i = 0; i < 9; i++) G.F[i] = gate->F12[i];
         G.ex = gate->ep_x; G.ey = gate->ep_y;
     }
-    const bool kb8_kernel = kgate && !kgate->coarse;   // bCoarse: no gate at all for such key frames (no epipole test either, :1026) = k_replay_bow without a gate
     if (kb8_kernel) {  // fisheye key frames: KannalaBrandt8::epipolarConstrain on the device (k_tri_kb8)
-        TriGate &G = P.gate;
         G.enabled = 1; G.coarse = 0; G.strict = 1;
-        G.k1 = (const orbx_keypoint *)up(kgate->kps1, sizeof(orbx_keypoint) * (size_t)na);
-        G.k2 = (const orbx_keypoint *)up(kgate->kps2, sizeof(orbx_keypoint) * (size_t)nb);
-        G.sigma2_2 = (const float *)up(kgate->level_sigma2_2, 4 * (size_t)kgate->nlevels);
-        Kb8Gate K;
-        memset(&K, 0, sizeof(K));
         K.n_left1 = kgate->n_left1; K.n_left2 = kgate->n_left2;
-        K.sigma2_1 = (const float *)up(kgate->level_sigma2_1, 4 * (size_t)kgate->nlevels);
         memcpy(K.cam[0], kgate->cam1, sizeof(float) * 16);
         memcpy(K.cam[2], kgate->cam2, sizeof(float) * 16);
         memcpy(K.R12, kgate->R12, sizeof(K.R12));
         memcpy(K.t12, kgate->t12, sizeof(K.t12));
-        if (!G.k1 || !G.k2 || !G.sigma2_2 || !K.sigma2_1) return ORBX_E_BAD_ARG;
-        G.kb8 = (const Kb8Gate *)up(&K, sizeof(K));
-        if (!G.kb8) return ORBX_E_BAD_ARG;
     }
-    // the two downloads side by side (one DMA), the two zero-filled buffers side by side (one fill)
-    P.match = A.take<int32_t>(n_out); P.nmatches = A.take<int32_t>(4);
-    P.taken_b = A.take<uint8_t>(nb);
-    P.hist = A.take<int32_t>(ORBX_HISTO_LENGTH + 2); P.counters = P.hist + ORBX_HISTO_LENGTH;
-    P.entries = A.take<int32_t>(2 * (size_t)std::max(na, nb));
+    ORBX_TRY(m->carve([&](Carve &A) {
+        P.fa.node_id = A.up(fa->node_id, (size_t)fa->n_nodes, 1); P.fa.node_ptr = A.up(fa->node_ptr, (size_t)fa->n_nodes + 1); P.fa.index = A.up(fa->index, ia, 1);
+        P.fb.node_id = A.up(fb->node_id, (size_t)fb->n_nodes, 1); P.fb.node_ptr = A.up(fb->node_ptr, (size_t)fb->n_nodes + 1); P.fb.index = A.up(fb->index, ib, 1);
+        P.pair_b = A.up(pair.data(), pair.size());
+        P.desc_a = A.up(desc_a, 32 * (size_t)na); P.desc_b = A.up(desc_b, 32 * (size_t)nb);
+        P.angle_a = A.up_opt(angle_a, (size_t)na); P.angle_b = A.up_opt(angle_b, (size_t)nb);
+        P.skip_a = A.up_opt(skip_a, (size_t)na); P.skip_b = A.up_opt(skip_b, (size_t)nb);
+        if (gate) {
+            G.k1 = A.up(gate->kps1_un, (size_t)na); G.k2 = A.up(gate->kps2_un, (size_t)nb);
+            G.ur1 = A.up_opt(gate->u_right1, (size_t)na); G.ur2 = A.up_opt(gate->u_right2, (size_t)nb);
+            G.scale2 = A.up(gate->scale_factors2, (size_t)gate->nlevels); G.sigma2_2 = A.up(gate->level_sigma2_2, (size_t)gate->nlevels);
+        }
+        if (kb8_kernel) {
+            G.k1 = A.up(kgate->kps1, (size_t)na); G.k2 = A.up(kgate->kps2, (size_t)nb);
+            G.sigma2_2 = A.up(kgate->level_sigma2_2, (size_t)kgate->nlevels);
+            K.sigma2_1 = A.up(kgate->level_sigma2_1, (size_t)kgate->nlevels);
+            G.kb8 = A.up(&K, 1);   // (behind the level table it points to)
+        }
+        // the two downloads side by side (one DMA), the two zero-filled buffers side by side (one fill)
+        P.match = A.take<int32_t>(n_out); P.nmatches = A.take<int32_t>(4);
+        P.taken_b = A.take<uint8_t>(nb);
+        P.hist = A.take<int32_t>(ORBX_HISTO_LENGTH + 2);
+        P.entries = A.take<int32_t>(2 * (size_t)std::max(na, nb));
+    }));
+    P.counters = P.hist + ORBX_HISTO_LENGTH;
     ORBX_HIP(m->fill(P.match, 0xff, 4 * (size_t)n_out));     // -1: no match.  Both fills ride in the launch that brings the inputs (orbx_matcher::fill)
     ORBX_HIP(m->fill(P.taken_b, 0, (size_t)((const uint8_t *)(P.hist + ORBX_HISTO_LENGTH + 2) - P.taken_b)));   // taken_b, (padding,) hist + counters
     if (fa->n_nodes > 0) {   // a wave per vocabulary node
@@ -1532,9 +1177,9 @@ int run_bow_replay(orbx_matcher *m, int mode, const uint8_t *desc_a, const float
     }
     hipLaunchKernelGGL(k_replay_bow_finish, dim3(1), dim3(64), 0, m->exec(), P);
     int32_t nm = 0;
-    D2H(match_out, P.match, 4 * (size_t)n_out);
-    D2H(&nm, P.nmatches, 4);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(match_out, P.match, 4 * (size_t)n_out));
+    ORBX_TRY(m->d2h(&nm, P.nmatches, 4));
+    ORBX_TRY(m->sync_and_deliver());
     return nm;
 }
 }  // namespace
@@ -1671,29 +1316,24 @@ int orbx_compute_stereo_fisheye_matches(orbx_matcher *m, const orbx_kb8_rig *rig
     }
     ORBX_HIP(hipSetDevice(m->device));
     const size_t NL = (size_t)n_left, NR = (size_t)n_right, nq = NL - (size_t)mono_left, nt = NR - (size_t)mono_right;
-    int r = m->reserve_all(Arena::pad(sizeof(orbx_kb8_rig)) + Arena::pad(64) + Arena::pad(4 * (size_t)nlevels) + Arena::pad(28 * NL) + Arena::pad(28 * NR + 28) +
-                           Arena::pad(32 * nq + 32) + Arena::pad(32 * nt + 32) + 2 * Arena::pad(8 * nq + 8) + 2 * Arena::pad(4 * NL) + Arena::pad(12 * NL) +
-                           Arena::pad(4 * NR + 4) + Arena::pad(16) + 4096);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
-    orbx_kb8_rig *drig = A.take<orbx_kb8_rig>(1);
-    int32_t *dn = A.take<int32_t>(16);   // n_left, mono_left, n_right, mono_right
-    float *ds = A.take<float>(nlevels);
-    orbx_keypoint *dkl = A.take<orbx_keypoint>(NL), *dkr = A.take<orbx_keypoint>(NR + 1);
-    uint8_t *ddl = A.take<uint8_t>(32 * nq + 32), *ddr = A.take<uint8_t>(32 * nt + 32);
-    int32_t *di = A.take<int32_t>(2 * nq + 2), *dd = A.take<int32_t>(2 * nq + 2);
-    int32_t *dl2r = A.take<int32_t>(NL);
-    float *ddep = A.take<float>(NL), *dp = A.take<float>(3 * NL);
-    int32_t *dr2l = A.take<int32_t>(NR + 1), *dcnt = A.take<int32_t>(4);
     const int32_t hn[4] = {n_left, mono_left, n_right, mono_right};
-    H2D(drig, rig, sizeof(orbx_kb8_rig));
-    H2D(dn, hn, sizeof(hn));
-    H2D(ds, level_sigma2, 4 * (size_t)nlevels);
-    H2D(dkl, kps_left, 28 * NL);
-    H2D(dkr, kps_right, 28 * NR);
-    H2D(ddl, desc_left + 32 * (size_t)mono_left, 32 * nq);     // the lapping-area tails (:1128-1132)
-    H2D(ddr, desc_right + 32 * (size_t)mono_right, 32 * nt);
+    orbx_kb8_rig *drig;
+    int32_t *dn, *di, *dd, *dl2r, *dr2l, *dcnt;
+    float *ds, *ddep, *dp;
+    orbx_keypoint *dkl, *dkr;
+    uint8_t *ddl, *ddr;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        drig = A.up(rig, 1);
+        dn = A.up(hn, 4, 12);
+        ds = A.up(level_sigma2, (size_t)nlevels);
+        dkl = A.up(kps_left, NL); dkr = A.up(kps_right, NR, 1);
+        ddl = A.up(desc_left + 32 * (size_t)mono_left, 32 * nq, 32);     // the lapping-area tails (:1128-1132)
+        ddr = A.up(desc_right + 32 * (size_t)mono_right, 32 * nt, 32);
+        di = A.take<int32_t>(2 * nq + 2); dd = A.take<int32_t>(2 * nq + 2);
+        dl2r = A.take<int32_t>(NL);
+        ddep = A.take<float>(NL); dp = A.take<float>(3 * NL);
+        dr2l = A.take<int32_t>(NR + 1); dcnt = A.take<int32_t>(4);
+    }));
     ORBX_HIP(m->fill(dr2l, 0xff, 4 * NR));
     ORBX_HIP(m->fill(dcnt, 0, 16));
     if (nq > 0)
@@ -1708,8 +1348,8 @@ int orbx_compute_stereo_fisheye_matches(orbx_matcher *m, const orbx_kb8_rig *rig
     hipLaunchKernelGGL(k_tri_kb8_stereo, dim3((unsigned)((NL + 255) / 256), 1), dim3(256), 0, m->exec(), S);
     ORBX_HIP(hipGetLastError());
     int32_t cnt[4] = {0, 0, 0, 0};
-    D2H(l2r, dl2r, 4 * NL); D2H(depth, ddep, 4 * NL); D2H(p3d, dp, 12 * NL); D2H(r2l, dr2l, 4 * NR); D2H(cnt, dcnt, 16);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(l2r, dl2r, 4 * NL)); ORBX_TRY(m->d2h(depth, ddep, 4 * NL)); ORBX_TRY(m->d2h(p3d, dp, 12 * NL)); ORBX_TRY(m->d2h(r2l, dr2l, 4 * NR)); ORBX_TRY(m->d2h(cnt, dcnt, 16));
+    ORBX_TRY(m->sync_and_deliver());
     if (desc_matches) *desc_matches = cnt[1];
     return cnt[0];
 }
@@ -1723,26 +1363,25 @@ int orbx_debug_kb8_epipolar(orbx_matcher *m, const float *cam1_2x8, const float 
     for (int i = 0; i < n; i++) if (sel[i] > 3) return ORBX_E_BAD_ARG;
     ORBX_HIP(hipSetDevice(m->device));
     const size_t N = (size_t)n;
-    int r = m->reserve_all(2 * Arena::pad(8 * N) + 2 * Arena::pad(4 * N) + 2 * Arena::pad(N) + Arena::pad(sizeof(Kb8Gate)) + 4096);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
-    float *d1 = A.take<float>(2 * N), *d2 = A.take<float>(2 * N), *s1 = A.take<float>(N), *s2 = A.take<float>(N);
-    uint8_t *dsel = A.take<uint8_t>(N), *dok = A.take<uint8_t>(N);
-    Kb8Gate *dg = A.take<Kb8Gate>(1);
     Kb8Gate K;
     memset(&K, 0, sizeof(K));
     memcpy(K.cam[0], cam1_2x8, sizeof(float) * 16);
     memcpy(K.cam[2], cam2_2x8, sizeof(float) * 16);
     memcpy(K.R12, R12_4x9, sizeof(K.R12));
     memcpy(K.t12, t12_4x3, sizeof(K.t12));
-    H2D(dg, &K, sizeof(K));
-    H2D(d1, xy1, 8 * N); H2D(d2, xy2, 8 * N); H2D(s1, sigma1, 4 * N); H2D(s2, sigma2, 4 * N); H2D(dsel, sel, N);
+    float *d1, *d2, *s1, *s2;
+    uint8_t *dsel, *dok;
+    Kb8Gate *dg;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        d1 = A.up(xy1, 2 * N); d2 = A.up(xy2, 2 * N); s1 = A.up(sigma1, N); s2 = A.up(sigma2, N);
+        dsel = A.up(sel, N); dok = A.take<uint8_t>(N);
+        dg = A.up(&K, 1);
+    }));
     hipLaunchKernelGGL(k_debug_kb8_gate, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->exec(), (const Kb8Gate *)dg, n, (const float *)d1, (const float *)d2,
                        (const float *)s1, (const float *)s2, (const uint8_t *)dsel, dok);
     ORBX_HIP(hipGetLastError());
-    D2H(ok, dok, N);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(ok, dok, N));
+    ORBX_TRY(m->sync_and_deliver());
     return ORBX_OK;
 }
 
@@ -1819,10 +1458,7 @@ extern "C" int orbx_match_consecutive_device(orbx_extractor *ex, float th, float
         ORBX_HIP(hipStreamSynchronize(ex->stream));  // P/R are host temporaries
         ex->mkey = key;
     }
-    GridParams g;
-    g.minx = ex->bounds[0]; g.miny = ex->bounds[2];  // mnMinX.. of the extractor's camera (image rectangle without one, Frame.cc:804-807)
-    g.inv_w = 64.0f / (ex->bounds[1] - ex->bounds[0]);   // Frame.cc:342-343
-    g.inv_h = 48.0f / (ex->bounds[3] - ex->bounds[2]);
+    const GridParams g = grid_of(ex->bounds);  // mnMinX.. of the extractor's camera (image rectangle without one, Frame.cc:804-807)
     // the matcher of batch i runs on its own stream beside the pyramid / FAST / quad-tree of batch i+1
     const bool side = !ex->profile && ex->side_streams;
     hipStream_t ms = side ? ex->match_stream : ex->stream;
@@ -1931,10 +1567,7 @@ extern "C" int orbx_search_mappoints_batch_device(orbx_extractor *ex, int n_mp, 
         ORBX_HIP(hipStreamSynchronize(ex->stream));  // P/R are host temporaries
         ex->mpkey = key;
     }
-    GridParams g;
-    g.minx = ex->bounds[0]; g.miny = ex->bounds[2];  // mnMinX.. of the extractor's camera (image rectangle without one, Frame.cc:804-807)
-    g.inv_w = 64.0f / (ex->bounds[1] - ex->bounds[0]);   // Frame.cc:342-343
-    g.inv_h = 48.0f / (ex->bounds[3] - ex->bounds[2]);
+    const GridParams g = grid_of(ex->bounds);  // mnMinX.. of the extractor's camera (image rectangle without one, Frame.cc:804-807)
     const bool side = !ex->profile && ex->side_streams;
     hipStream_t ms = side ? ex->match_stream : ex->stream;
     if (side) ORBX_HIP(hipStreamWaitEvent(ms, ex->ev_describe, 0));
@@ -1977,15 +1610,11 @@ extern "C" int orbx_undistort_keypoints(orbx_matcher *m, const orbx_camera *cam,
     if (!m || !cam || n < 0 || (n > 0 && (!kps || !kps_un))) return ORBX_E_BAD_ARG;
     if (n == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
-    int r = m->reserve_all(2 * Arena::pad(sizeof(orbx_keypoint) * (size_t)n) + 4096);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
-    orbx_keypoint *di = A.take<orbx_keypoint>(n), *dou = A.take<orbx_keypoint>(n);
-    H2D(di, kps, sizeof(orbx_keypoint) * (size_t)n);
+    orbx_keypoint *di, *dou;
+    ORBX_TRY(m->carve([&](Carve &A) { di = A.up(kps, (size_t)n); dou = A.take<orbx_keypoint>(n); }));
     hipLaunchKernelGGL(k_undistort, dim3((n + 255) / 256, 1), dim3(256), 0, m->exec(), model_of(cam), (const orbx_keypoint *)di, (const int32_t *)nullptr, n, dou);
-    D2H(kps_un, dou, sizeof(orbx_keypoint) * (size_t)n);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(kps_un, dou, sizeof(orbx_keypoint) * (size_t)n));
+    ORBX_TRY(m->sync_and_deliver());
     return ORBX_OK;
 }
 
@@ -1998,15 +1627,17 @@ extern "C" int orbx_is_in_frustum(orbx_matcher *m, const orbx_camera *cam, const
     if (n_mp == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
     const size_t n = (size_t)n_mp;
-    int r = m->reserve_all(2 * Arena::pad(12 * n) + 8 * Arena::pad(4 * n) + Arena::pad(n) + Arena::pad(sizeof(FrustumFrame)) + 8192);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
-    float *dp = A.take<float>(3 * n), *dn = A.take<float>(3 * n), *dmn = A.take<float>(n), *dmx = A.take<float>(n);
-    uint8_t *div = A.take<uint8_t>(n);
-    float *dx = A.take<float>(n), *dy = A.take<float>(n), *dxr = A.take<float>(n), *dd = A.take<float>(n), *dvc = A.take<float>(n);
-    int32_t *dl = A.take<int32_t>(n);
-    FrustumFrame *dF = A.take<FrustumFrame>(1);
+    float *dp, *dn, *dmn, *dmx, *dx, *dy, *dxr, *dd, *dvc;
+    uint8_t *div;
+    int32_t *dl;
+    FrustumFrame *dF;
+    ORBX_TRY(m->carve([&](Carve &A) {   // (the inputs are staged below: by the kernel itself where it reads the mirror)
+        dp = A.take<float>(3 * n); dn = A.take<float>(3 * n); dmn = A.take<float>(n); dmx = A.take<float>(n);
+        div = A.take<uint8_t>(n);
+        dx = A.take<float>(n); dy = A.take<float>(n); dxr = A.take<float>(n); dd = A.take<float>(n); dvc = A.take<float>(n);
+        dl = A.take<int32_t>(n);
+        dF = A.take<FrustumFrame>(1);
+    }));
     const FrustumFrame F = frustum_frame(cam, pose, bounds4, log_scale_factor, nlevels, viewing_cos_limit);
     if (m->direct_ok(57 * n)) {   // streaming kernel, small call: its lanes read the staged inputs from and write the results into the pinned mirror (one launch)
         m->stage_direct(dF, &F, sizeof(F));
@@ -2016,16 +1647,16 @@ extern "C" int orbx_is_in_frustum(orbx_matcher *m, const orbx_camera *cam, const
                            m->host_view(div), m->host_view(dx), m->host_view(dy), m->host_view(dxr), m->host_view(dd), m->host_view(dl), m->host_view(dvc));
         m->result_direct(in_view, div, n); m->result_direct(proj_x, dx, 4 * n); m->result_direct(proj_y, dy, 4 * n); m->result_direct(proj_xr, dxr, 4 * n);
         m->result_direct(depth, dd, 4 * n); m->result_direct(level, dl, 4 * n); m->result_direct(view_cos, dvc, 4 * n);
-        SYNC_AND_DELIVER();
+        ORBX_TRY(m->sync_and_deliver());
         return ORBX_OK;
     }
-    H2D(dF, &F, sizeof(F));
-    H2D(dp, pos, 12 * n); H2D(dn, normal, 12 * n); H2D(dmn, min_dist, 4 * n); H2D(dmx, max_dist, 4 * n);
+    ORBX_TRY(m->h2d(dF, &F, sizeof(F)));
+    ORBX_TRY(m->h2d(dp, pos, 12 * n)); ORBX_TRY(m->h2d(dn, normal, 12 * n)); ORBX_TRY(m->h2d(dmn, min_dist, 4 * n)); ORBX_TRY(m->h2d(dmx, max_dist, 4 * n));
     hipLaunchKernelGGL(k_in_frustum, dim3((n_mp + 255) / 256, 1), dim3(256), 0, m->exec(), (const FrustumFrame *)dF, n_mp, (const float *)dp,
                        (const float *)dn, (const float *)dmn, (const float *)dmx, div, dx, dy, dxr, dd, dl, dvc);
-    D2H(in_view, div, n); D2H(proj_x, dx, 4 * n); D2H(proj_y, dy, 4 * n); D2H(proj_xr, dxr, 4 * n); D2H(depth, dd, 4 * n);
-    D2H(level, dl, 4 * n); D2H(view_cos, dvc, 4 * n);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(in_view, div, n)); ORBX_TRY(m->d2h(proj_x, dx, 4 * n)); ORBX_TRY(m->d2h(proj_y, dy, 4 * n)); ORBX_TRY(m->d2h(proj_xr, dxr, 4 * n)); ORBX_TRY(m->d2h(depth, dd, 4 * n));
+    ORBX_TRY(m->d2h(level, dl, 4 * n)); ORBX_TRY(m->d2h(view_cos, dvc, 4 * n));
+    ORBX_TRY(m->sync_and_deliver());
     return ORBX_OK;
 }
 
@@ -2038,27 +1669,27 @@ extern "C" int orbx_is_in_frustum_checks(orbx_matcher *m, const orbx_fisheye_vie
     if (n_mp == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
     const size_t n = (size_t)n_mp, no = n * (size_t)n_views;
-    int r = m->reserve_all(2 * Arena::pad(12 * n) + 2 * Arena::pad(4 * n) + 5 * Arena::pad(4 * no) + Arena::pad(no) + Arena::pad(sizeof(FrustumChecks)) + 8192);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
-    float *dp = A.take<float>(3 * n), *dn = A.take<float>(3 * n), *dmn = A.take<float>(n), *dmx = A.take<float>(n);
-    uint8_t *div = A.take<uint8_t>(no);
-    float *dx = A.take<float>(no), *dy = A.take<float>(no), *dd = A.take<float>(no), *dvc = A.take<float>(no);
-    int32_t *dl = A.take<int32_t>(no);
-    FrustumChecks *dF = A.take<FrustumChecks>(1);
     FrustumChecks F;
     memset(&F, 0, sizeof(F));
     static_assert(sizeof(FisheyeView) == sizeof(orbx_fisheye_view), "orbx_fisheye_view layout");
     memcpy(F.view, views, sizeof(FisheyeView) * (size_t)n_views);
     F.minx = bounds4[0]; F.maxx = bounds4[1]; F.miny = bounds4[2]; F.maxy = bounds4[3];
     F.log_scale_factor = log_scale_factor; F.nlevels = nlevels; F.cos_limit = viewing_cos_limit;
-    H2D(dF, &F, sizeof(F));
-    H2D(dp, pos, 12 * n); H2D(dn, normal, 12 * n); H2D(dmn, min_dist, 4 * n); H2D(dmx, max_dist, 4 * n);
+    float *dp, *dn, *dmn, *dmx, *dx, *dy, *dd, *dvc;
+    uint8_t *div;
+    int32_t *dl;
+    FrustumChecks *dF;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        dp = A.up(pos, 3 * n); dn = A.up(normal, 3 * n); dmn = A.up(min_dist, n); dmx = A.up(max_dist, n);
+        div = A.take<uint8_t>(no);
+        dx = A.take<float>(no); dy = A.take<float>(no); dd = A.take<float>(no); dvc = A.take<float>(no);
+        dl = A.take<int32_t>(no);
+        dF = A.up(&F, 1);
+    }));
     hipLaunchKernelGGL(k_in_frustum_checks, dim3((n_mp + 255) / 256, n_views), dim3(256), 0, m->exec(), (const FrustumChecks *)dF, n_mp, (const float *)dp,
                        (const float *)dn, (const float *)dmn, (const float *)dmx, div, dx, dy, dd, dl, dvc);
-    D2H(in_view, div, no); D2H(proj_x, dx, 4 * no); D2H(proj_y, dy, 4 * no); D2H(depth, dd, 4 * no); D2H(level, dl, 4 * no); D2H(view_cos, dvc, 4 * no);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(in_view, div, no)); ORBX_TRY(m->d2h(proj_x, dx, 4 * no)); ORBX_TRY(m->d2h(proj_y, dy, 4 * no)); ORBX_TRY(m->d2h(depth, dd, 4 * no)); ORBX_TRY(m->d2h(level, dl, 4 * no)); ORBX_TRY(m->d2h(view_cos, dvc, 4 * no));
+    ORBX_TRY(m->sync_and_deliver());
     return ORBX_OK;
 }
 
@@ -2454,16 +2085,13 @@ extern "C" int orbx_bow_transform(orbx_matcher *m, const orbx_vocabulary *v, con
     if (!m || !v || n < 0 || (n > 0 && (!desc || !word_id || !node_id)) || m->device != v->device) return ORBX_E_BAD_ARG;
     if (n == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
-    int r = m->reserve_all(Arena::pad(32 * (size_t)n) + 2 * Arena::pad(4 * (size_t)n) + 4096);
-    if (r != ORBX_OK) return r;
-    m->begin();
-    uint8_t *dd = m->arena.take<uint8_t>(32 * (size_t)n);
-    int32_t *dw = m->arena.take<int32_t>(n), *dn = m->arena.take<int32_t>(n);
-    H2D(dd, desc, 32 * (size_t)n);
+    uint8_t *dd;
+    int32_t *dw, *dn;
+    ORBX_TRY(m->carve([&](Carve &A) { dd = A.up(desc, 32 * (size_t)n); dw = A.take<int32_t>(n); dn = A.take<int32_t>(n); }));
     hipLaunchKernelGGL(k_bow_transform, dim3((n + 15) / 16), dim3(256), 0, m->exec(), v->child_ptr, v->child_idx, v->node_desc, v->word_id,
                        v->L, levelsup, dd, n, dw, dn);
-    D2H(word_id, dw, 4 * (size_t)n); D2H(node_id, dn, 4 * (size_t)n);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(word_id, dw, 4 * (size_t)n)); ORBX_TRY(m->d2h(node_id, dn, 4 * (size_t)n));
+    ORBX_TRY(m->sync_and_deliver());
     return ORBX_OK;
 }
 
@@ -2478,9 +2106,7 @@ extern "C" int orbx_frame_compute_bow(orbx_matcher *m, orbx_frame *f, const orbx
     int sort_cap = 1;
     while (sort_cap < nc) sort_cap <<= 1;
     const size_t lds = 8 * (size_t)sort_cap;
-    int r = m->reserve_all(Arena::pad(8 * (size_t)nc) + 4096);   // (the staging of the downloads)
-    if (r != ORBX_OK) return r;
-    m->begin();
+    ORBX_TRY(m->reserve_staging(8 * (size_t)nc));   // the ids come down through it
     f->bow_valid = false;
     if (nc > 0)
         hipLaunchKernelGGL(k_frame_bow_transform, dim3((nc + 15) / 16), dim3(256), 0, m->stream, v->child_ptr, v->child_idx, v->node_desc, v->word_id,
@@ -2496,16 +2122,16 @@ extern "C" int orbx_frame_compute_bow(orbx_matcher *m, orbx_frame *f, const orbx
     f->bow_valid = true; f->bow_voc = v; f->bow_levelsup = levelsup;
     if (!down || nc == 0) return ORBX_OK;
     if (n_host >= 0) {
-        if (word_id) D2H(word_id, f->bow_word, 4 * (size_t)nc);
-        if (node_id) D2H(node_id, f->bow_node, 4 * (size_t)nc);
-        SYNC_AND_DELIVER();
+        if (word_id) ORBX_TRY(m->d2h(word_id, f->bow_word, 4 * (size_t)nc));
+        if (node_id) ORBX_TRY(m->d2h(node_id, f->bow_node, 4 * (size_t)nc));
+        ORBX_TRY(m->sync_and_deliver());
         return ORBX_OK;
     }
     f->h_bow.resize(2 * (size_t)f->cap);   // N comes back with the ids
-    D2H(f->h_bow.data(), f->bow_word, 4 * (size_t)nc);
-    D2H(f->h_bow.data() + f->cap, f->bow_node, 4 * (size_t)nc);
-    D2H(&f->n, f->count, 4);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(f->h_bow.data(), f->bow_word, 4 * (size_t)nc));
+    ORBX_TRY(m->d2h(f->h_bow.data() + f->cap, f->bow_node, 4 * (size_t)nc));
+    ORBX_TRY(m->d2h(&f->n, f->count, 4));
+    ORBX_TRY(m->sync_and_deliver());
     f->n = std::min(std::max(f->n, 0), f->cap);
     f->n_known = true;
     if (word_id) memcpy(word_id, f->h_bow.data(), 4 * (size_t)f->n);
@@ -2529,9 +2155,8 @@ extern "C" int orbx_frame_compute_bow_fisheye(orbx_matcher *m, orbx_frame *f, co
     int sort_cap = 1;
     while (sort_cap < nc) sort_cap <<= 1;
     const size_t lds = 8 * (size_t)sort_cap;
-    int r = m->reserve_all(Arena::pad(8 * (size_t)nc) + 4096);   // (the renumbered ids)
-    if (r != ORBX_OK) return r;
-    m->begin();
+    int32_t *dids;   // word ids, then node ids, in features [0, N)
+    ORBX_TRY(m->carve([&](Carve &A) { dids = A.take<int32_t>(2 * (size_t)nc); }));
     f->bow_valid = false;
     if (side > 0)
         hipLaunchKernelGGL(k_frame_bow_transform_fisheye, dim3((unsigned)((side + 15) / 16), 2), dim3(256), 0, m->stream, v->child_ptr, v->child_idx,
@@ -2548,22 +2173,21 @@ extern "C" int orbx_frame_compute_bow_fisheye(orbx_matcher *m, orbx_frame *f, co
     ORBX_HIP(hipGetLastError());
     f->bow_valid = true; f->bow_voc = v; f->bow_levelsup = levelsup;
     if (!down || nc == 0) return ORBX_OK;
-    int32_t *dids = m->arena.take<int32_t>(2 * (size_t)nc);   // word ids, then node ids, in features [0, N)
     const int32_t *src[2] = {f->bow_word, f->bow_node};
     for (int k = 0; k < 2; k++)
         hipLaunchKernelGGL(k_frame_rows_to_features, dim3((unsigned)((nc + 255) / 256), 1), dim3(256), 0, m->stream, src[k], 0, dids + (size_t)k * nc, nc,
                            f->count, nl_host, nr_host, f->cap, f->roff);
     ORBX_HIP(hipGetLastError());
     if (f->n_known) {
-        if (word_id) D2H(word_id, dids, 4 * (size_t)nc);
-        if (node_id) D2H(node_id, dids + nc, 4 * (size_t)nc);
-        SYNC_AND_DELIVER();
+        if (word_id) ORBX_TRY(m->d2h(word_id, dids, 4 * (size_t)nc));
+        if (node_id) ORBX_TRY(m->d2h(node_id, dids + nc, 4 * (size_t)nc));
+        ORBX_TRY(m->sync_and_deliver());
         return ORBX_OK;
     }
     f->h_bow.resize(2 * (size_t)f->cap);   // the counts come back with the ids
-    D2H(f->h_bow.data(), dids, 8 * (size_t)nc);
-    D2H(f->h_count, f->count, 8);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(f->h_bow.data(), dids, 8 * (size_t)nc));
+    ORBX_TRY(m->d2h(f->h_count, f->count, 8));
+    ORBX_TRY(m->sync_and_deliver());
     f->n_left = std::min(std::max(f->h_count[0], 0), f->roff);
     f->n_right = std::min(std::max(f->h_count[1], 0), f->cap - f->roff);
     f->n = f->n_left + f->n_right;
@@ -2619,60 +2243,49 @@ static int frame_search_by_bow_impl(orbx_matcher *m, orbx_frame *f, int n_kf, co
         n_ent = 0;
         for (int k = 0; k < n_kf; k++) n_ent += 2 * (size_t)std::max(std::max(kfs[k].n, nrows), 1);
     }
-    size_t need = Arena::pad(4 * (tot_nodes + 1)) * 2 + Arena::pad(sizeof(BowProblem) * (size_t)n_kf) + Arena::pad(4 * (size_t)n_kf * nrows) +
-                  Arena::pad(4 * (size_t)n_kf) + Arena::pad(4 * (size_t)n_kf * (ORBX_HISTO_LENGTH + 2)) + Arena::pad(4 * n_ent) + 4096 +
-                  (fisheye ? Arena::pad(4 * (size_t)n_kf * nc) : 0);
-    for (int k = 0; k < n_kf; k++) {
-        const size_t nk = (size_t)kfs[k].n, nn = (size_t)kfs[k].fv.n_nodes, ni = (size_t)kfs[k].fv.node_ptr[nn];
-        need += Arena::pad(32 * nk) + Arena::pad(4 * nk) + Arena::pad(nk) + Arena::pad(4 * (nn + 1)) + Arena::pad(4 * (ni + 1));
-    }
-    int r = m->reserve_all(need);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
     std::vector<BowProblem> probs((size_t)n_kf);
-    std::vector<uint8_t> skip;
-    // the uploads, side by side: per key frame its rows and feature vector, then every node id of the batch, then the problem records
-    for (int k = 0; k < n_kf; k++) {
-        const orbx_bow_keyframe &K = kfs[k];
-        const int nn = K.fv.n_nodes, ni = K.fv.node_ptr[nn];
-        BowProblem &P = probs[k];
-        memset(&P, 0, sizeof(P));
-        uint8_t *dd = A.take<uint8_t>(32 * (size_t)K.n);
-        H2D(dd, K.descriptors, 32 * (size_t)K.n);
-        P.desc_a = dd;
-        if (K.angle && check_orientation) { float *da = A.take<float>(K.n); H2D(da, K.angle, 4 * (size_t)K.n); P.angle_a = da; }
-        if (K.valid) {
-            skip.resize((size_t)K.n);
-            for (int i = 0; i < K.n; i++) skip[i] = K.valid[i] ? 0 : 1;
-            uint8_t *ds = A.take<uint8_t>(K.n);
-            H2D(ds, skip.data(), (size_t)K.n);
-            P.skip_a = ds;
+    memset(probs.data(), 0, sizeof(BowProblem) * (size_t)n_kf);
+    uint32_t *dkn;
+    BowProblem *dP;
+    int32_t *dpair, *dmatch, *dout, *dnm, *dhist, *dent;
+    std::vector<uint8_t *> dskip((size_t)n_kf, nullptr);
+    ORBX_TRY(m->carve([&](Carve &A) {
+        // the uploads, side by side: per key frame its rows and feature vector, then every node id of the batch, then the problem records
+        for (int k = 0; k < n_kf; k++) {
+            const orbx_bow_keyframe &K = kfs[k];
+            const int nn = K.fv.n_nodes, ni = K.fv.node_ptr[nn];
+            BowProblem &P = probs[k];
+            P.desc_a = A.up(K.descriptors, 32 * (size_t)K.n);
+            if (K.angle && check_orientation) P.angle_a = A.up(K.angle, (size_t)K.n);
+            if (K.valid) P.skip_a = dskip[k] = A.take<uint8_t>(K.n);   // (uploaded below, inverted)
+            P.fa.node_ptr = A.up(K.fv.node_ptr, (size_t)nn + 1); P.fa.index = A.up(K.fv.index, (size_t)ni, 1); P.fa.n_nodes = nn;
+            P.na = K.n;
         }
-        int32_t *dp = A.take<int32_t>(nn + 1), *di = A.take<int32_t>(ni + 1);
-        H2D(dp, K.fv.node_ptr, 4 * ((size_t)nn + 1));
-        H2D(di, K.fv.index, 4 * (size_t)ni);
-        P.fa.node_ptr = dp; P.fa.index = di; P.fa.n_nodes = nn;
-        P.na = K.n;
-    }
-    uint32_t *dkn = A.take<uint32_t>(tot_nodes + 1);
+        dkn = A.take<uint32_t>(tot_nodes + 1);
+        dP = A.take<BowProblem>(n_kf);
+        // device-only: the pairing, the rows (filled with -1) and match counts side by side (one download run), histograms + counters (zeroed), entries
+        dpair = A.take<int32_t>(tot_nodes + 1);
+        dmatch = A.take<int32_t>((size_t)n_kf * nrows);
+        dout = fisheye ? A.take<int32_t>((size_t)n_kf * nc) : dmatch;   // fisheye: the rows renumbered into features, next to the counts
+        dnm = A.take<int32_t>(n_kf);
+        dhist = A.take<int32_t>((size_t)n_kf * (ORBX_HISTO_LENGTH + 2));
+        dent = A.take<int32_t>(n_ent);
+    }));
     {
+        std::vector<uint8_t> skip;
         size_t o = 0;
         for (int k = 0; k < n_kf; k++) {
-            const int nn = kfs[k].fv.n_nodes;
-            H2D(dkn + o, kfs[k].fv.node_id, 4 * (size_t)nn);
+            const orbx_bow_keyframe &K = kfs[k];
+            if (K.valid) {
+                skip.resize((size_t)K.n);
+                for (int i = 0; i < K.n; i++) skip[i] = K.valid[i] ? 0 : 1;
+                ORBX_TRY(m->h2d(dskip[k], skip.data(), (size_t)K.n));
+            }
+            ORBX_TRY(m->h2d(dkn + o, K.fv.node_id, 4 * (size_t)K.fv.n_nodes));
             probs[k].fa.node_id = dkn + o;
-            o += (size_t)nn;
+            o += (size_t)K.fv.n_nodes;
         }
     }
-    BowProblem *dP = A.take<BowProblem>(n_kf);
-    // device-only: the pairing, the rows (filled with -1) and match counts side by side (one download run), histograms + counters (zeroed), entries
-    int32_t *dpair = A.take<int32_t>(tot_nodes + 1);
-    int32_t *dmatch = A.take<int32_t>((size_t)n_kf * nrows);
-    int32_t *dout = fisheye ? A.take<int32_t>((size_t)n_kf * nc) : dmatch;   // fisheye: the rows renumbered into features, next to the counts
-    int32_t *dnm = A.take<int32_t>(n_kf);
-    int32_t *dhist = A.take<int32_t>((size_t)n_kf * (ORBX_HISTO_LENGTH + 2));
-    int32_t *dent = A.take<int32_t>(n_ent);
     {
         size_t o = 0, oe = 0;
         for (int k = 0; k < n_kf; k++) {
@@ -2689,7 +2302,7 @@ static int frame_search_by_bow_impl(orbx_matcher *m, orbx_frame *f, int n_kf, co
             o += (size_t)P.fa.n_nodes;
         }
     }
-    H2D(dP, probs.data(), sizeof(BowProblem) * (size_t)n_kf);
+    ORBX_TRY(m->h2d(dP, probs.data(), sizeof(BowProblem) * (size_t)n_kf));
     ORBX_HIP(m->fill(dmatch, 0xff, 4 * (size_t)n_kf * nrows));
     ORBX_HIP(m->fill(dhist, 0, 4 * (size_t)n_kf * (ORBX_HISTO_LENGTH + 2)));
     if (tot_nodes > 0) {
@@ -2703,15 +2316,15 @@ static int frame_search_by_bow_impl(orbx_matcher *m, orbx_frame *f, int n_kf, co
                            f->count, n >= 0 ? f->n_left : -1, n >= 0 ? f->n_right : -1, f->cap, f->roff);
     ORBX_HIP(hipGetLastError());
     if (n >= 0) {
-        for (int k = 0; k < n_kf; k++) D2H(match + (size_t)k * match_stride, dout + (size_t)k * nc, 4 * (size_t)n);
+        for (int k = 0; k < n_kf; k++) ORBX_TRY(m->d2h(match + (size_t)k * match_stride, dout + (size_t)k * nc, 4 * (size_t)n));
     } else {   // N comes back with the results
         f->h_match.resize((size_t)n_kf * nc);
-        D2H(f->h_match.data(), dout, 4 * (size_t)n_kf * nc);
-        if (fisheye) D2H(f->h_count, f->count, 8);
-        else D2H(&f->n, f->count, 4);
+        ORBX_TRY(m->d2h(f->h_match.data(), dout, 4 * (size_t)n_kf * nc));
+        if (fisheye) ORBX_TRY(m->d2h(f->h_count, f->count, 8));
+        else ORBX_TRY(m->d2h(&f->n, f->count, 4));
     }
-    D2H(nmatches, dnm, 4 * (size_t)n_kf);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(nmatches, dnm, 4 * (size_t)n_kf));
+    ORBX_TRY(m->sync_and_deliver());
     if (n < 0) {
         if (fisheye) {
             f->n_left = std::min(std::max(f->h_count[0], 0), f->roff);
@@ -2744,16 +2357,12 @@ extern "C" int orbx_distinctive_descriptors(orbx_matcher *m, const uint8_t *desc
     const int total = set_ptr[n_sets];
     if (total > 0 && !desc) return ORBX_E_BAD_ARG;
     ORBX_HIP(hipSetDevice(m->device));
-    int r = m->reserve_all(Arena::pad(32 * (size_t)total + 32) + Arena::pad(4 * (size_t)(n_sets + 1)) + Arena::pad(4 * (size_t)n_sets) + 4096);
-    if (r != ORBX_OK) return r;
-    m->begin();
-    uint8_t *dd = m->arena.take<uint8_t>(32 * (size_t)total + 32);
-    int32_t *dp = m->arena.take<int32_t>(n_sets + 1), *db = m->arena.take<int32_t>(n_sets);
-    if (total > 0) H2D(dd, desc, 32 * (size_t)total);
-    H2D(dp, set_ptr, 4 * (size_t)(n_sets + 1));
+    uint8_t *dd;
+    int32_t *dp, *db;
+    ORBX_TRY(m->carve([&](Carve &A) { dd = A.up(desc, 32 * (size_t)total, 32); dp = A.up(set_ptr, (size_t)n_sets + 1); db = A.take<int32_t>(n_sets); }));
     hipLaunchKernelGGL(k_distinctive, dim3((n_sets + 3) / 4), dim3(256), 0, m->exec(), dd, dp, n_sets, db);
-    D2H(best_idx, db, 4 * (size_t)n_sets);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(best_idx, db, 4 * (size_t)n_sets));
+    ORBX_TRY(m->sync_and_deliver());
     return ORBX_OK;
 }
 
@@ -2771,46 +2380,33 @@ extern "C" int orbx_fuse_search(orbx_matcher *m, const orbx_frame_desc *kf, cons
     if (n > 65535) return ORBX_E_TOO_LARGE;
     ORBX_HIP(hipSetDevice(m->device));
     const int nl = kf->nlevels;
-    size_t need = Arena::pad(28 * (size_t)n) + Arena::pad(32 * (size_t)n) + Arena::pad(4 * (size_t)n) + Arena::pad(4 * (size_t)nl) +
-                  Arena::pad(4 * (size_t)n_q) * 6 + Arena::pad(32 * (size_t)n_q) + Arena::pad(8 * (size_t)n_q * kTopK) + Arena::pad(4 * (size_t)n_q) +
-                  Arena::pad(sizeof(WindowProblem)) + Arena::pad(2 * (kGridCells + 1)) + Arena::pad(2 * (size_t)n) + 16 * 256 + 4096;
-    int r = m->reserve_all(need);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
     WindowProblem P;
     memset(&P, 0, sizeof(P));
-    orbx_keypoint *dk = A.take<orbx_keypoint>(n);
-    uint8_t *dd = A.take<uint8_t>(32 * (size_t)n);
-    H2D(dk, kf->keypoints_un, 28 * (size_t)n); H2D(dd, kf->descriptors, 32 * (size_t)n);
-    P.kps = dk; P.desc = dd;
-    int32_t *dcnt = A.take<int32_t>(4);
-    const int32_t cnts[2] = {n, n_q};
-    H2D(dcnt, cnts, 8);
-    P.n_ptr = dcnt; P.nq_ptr = dcnt + 1;
-    if (kf->u_right) { float *p = A.take<float>(n); H2D(p, kf->u_right, 4 * (size_t)n); P.u_right = p; }
-    if (inv_level_sigma2) { float *p = A.take<float>(nl); H2D(p, inv_level_sigma2, 4 * (size_t)nl); P.inv_sigma2 = p; }
     P.chi2_fma = strict_fp ? 0 : 1;
-    float *f3[3]; const float *h3[3] = {q_u, q_v, q_r};
-    for (int k = 0; k < 3; k++) { f3[k] = A.take<float>(n_q); H2D(f3[k], h3[k], 4 * (size_t)n_q); }
-    P.qx = f3[0]; P.qy = f3[1]; P.qr = f3[2];
     std::vector<int32_t> qmin(n_q), qmax(n_q);
     for (int i = 0; i < n_q; i++) { qmin[i] = q_level[i] - 1; qmax[i] = q_level[i]; }  // kpLevel<nPredictedLevel-1 || kpLevel>nPredictedLevel
-    int32_t *dmin = A.take<int32_t>(n_q), *dmax = A.take<int32_t>(n_q);
-    H2D(dmin, qmin.data(), 4 * (size_t)n_q); H2D(dmax, qmax.data(), 4 * (size_t)n_q);
-    P.qmin = dmin; P.qmax = dmax;
-    if (q_ur && kf->u_right) { float *p = A.take<float>(n_q); H2D(p, q_ur, 4 * (size_t)n_q); P.qxr = p; }
-    { uint8_t *p = A.take<uint8_t>(32 * (size_t)n_q); H2D(p, q_desc, 32 * (size_t)n_q); P.qdesc = p; }
-    WindowProblem *dP = A.take<WindowProblem>(1);   // directly behind the inputs: the call's uploads are one run of the arena (one DMA)
-    P.keys = A.take<u64>((size_t)n_q * kTopK); P.meta = A.take<int32_t>(n_q);
-    P.gstart = A.take<uint16_t>(kGridCells + 1); P.gorder = A.take<uint16_t>(n);
+    const int32_t cnts[2] = {n, n_q};
+    int32_t *dcnt;
+    WindowProblem *dP;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        P.kps = A.up(kf->keypoints_un, (size_t)n); P.desc = A.up(kf->descriptors, 32 * (size_t)n);
+        dcnt = A.up(cnts, 2, 2);
+        P.u_right = A.up_opt(kf->u_right, (size_t)n);
+        P.inv_sigma2 = A.up_opt(inv_level_sigma2, (size_t)nl);
+        P.qx = A.up(q_u, (size_t)n_q); P.qy = A.up(q_v, (size_t)n_q); P.qr = A.up(q_r, (size_t)n_q);
+        P.qmin = A.up(qmin.data(), (size_t)n_q); P.qmax = A.up(qmax.data(), (size_t)n_q);
+        if (kf->u_right) P.qxr = A.up_opt(q_ur, (size_t)n_q);
+        P.qdesc = A.up(q_desc, 32 * (size_t)n_q);
+        dP = A.take<WindowProblem>(1);   // directly behind the inputs: the call's uploads are one run of the arena (one DMA)
+        P.keys = A.take<u64>((size_t)n_q * kTopK); P.meta = A.take<int32_t>(n_q);
+        P.gstart = A.take<uint16_t>(kGridCells + 1); P.gorder = A.take<uint16_t>(n);
+    }));
+    P.n_ptr = dcnt; P.nq_ptr = dcnt + 1;
     const bool brute = m->brute_windows && (size_t)n_q * (size_t)n <= kBruteMaxPairs;
     if (brute) { P.gstart = nullptr; P.gorder = nullptr; }
-    H2D(dP, &P, sizeof(P));
-    GridParams g;
-    g.minx = kf->min_x; g.miny = kf->min_y;
-    g.inv_w = 64.0f / (kf->max_x - kf->min_x);
-    g.inv_h = 48.0f / (kf->max_y - kf->min_y);
+    ORBX_TRY(m->h2d(dP, &P, sizeof(P)));
+    const float fb[4] = {kf->min_x, kf->max_x, kf->min_y, kf->max_y};
+    const GridParams g = grid_of(fb);
     if (brute) {
         hipLaunchKernelGGL(k_window_brute, dim3((n_q + 3) / 4), dim3(256), 0, m->exec(), dP, g);
     } else {
@@ -2818,8 +2414,8 @@ extern "C" int orbx_fuse_search(orbx_matcher *m, const orbx_frame_desc *kf, cons
         ORBX_LAUNCH_WINDOW_BEST2(n_q, 1, m->exec(), dP, g);
     }
     std::vector<u64> keys((size_t)n_q * kTopK);
-    D2H(keys.data(), P.keys, 8 * (size_t)n_q * kTopK);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(keys.data(), P.keys, 8 * (size_t)n_q * kTopK));
+    ORBX_TRY(m->sync_and_deliver());
     for (int i = 0; i < n_q; i++) {
         const u64 k = keys[(size_t)i * kTopK];
         if (k != kNoKey) { best_idx[i] = (int32_t)(k & 0xffff); best_dist[i] = (int32_t)(k >> 32); }
@@ -2881,12 +2477,11 @@ int keyframe_alloc(int device, int cap, bool has_ur, bool has_sigma, int nlevels
     kf->device = device; kf->cap = cap; kf->nlevels = nlevels;
     memcpy(kf->bounds, bounds4, sizeof(kf->bounds));
     const size_t c = (size_t)std::max(cap, 1);
-    size_t o = 0;
-    auto carve = [&o](size_t bytes) { const size_t r = o; o += Arena::pad(bytes); return r; };
+    Layout L;
     // (rows and inv_sigma2 first: orbx_keyframe_create_host uploads them as one run)
-    const size_t off_kps = carve(28 * c), off_desc = carve(32 * c), off_ur = has_ur ? carve(4 * c) : 0, off_sg = has_sigma ? carve(4 * (size_t)kFrameMaxLevels) : 0;
-    const size_t off_scale = carve(4 * (size_t)kFrameMaxLevels), off_count = carve(8), off_gs = carve(2 * ((size_t)kGridCells + 1)), off_go = carve(2 * c);
-    hipError_t e = hipMalloc((void **)&kf->dev, o);
+    const size_t off_kps = L.add(28 * c), off_desc = L.add(32 * c), off_ur = has_ur ? L.add(4 * c) : 0, off_sg = has_sigma ? L.add(4 * (size_t)kFrameMaxLevels) : 0;
+    const size_t off_scale = L.add(4 * (size_t)kFrameMaxLevels), off_count = L.add(8), off_gs = L.add(2 * ((size_t)kGridCells + 1)), off_go = L.add(2 * c);
+    hipError_t e = hipMalloc((void **)&kf->dev, L.used);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&kf->ready, hipEventDisableTiming);
     if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
     kf->kps = (orbx_keypoint *)(kf->dev + off_kps); kf->desc = kf->dev + off_desc;
@@ -2955,9 +2550,8 @@ int orbx_keyframe_create_host(orbx_matcher *m, const orbx_frame_desc *d, const f
     if (r != ORBX_OK) return r;
     // ONE upload: the rows and inv_sigma2 staged at the allocation's own offsets (pinned; the context's next call waits before it stages over them)
     const size_t up_end = (size_t)((inv_level_sigma2 ? (uint8_t *)(kf->inv_sigma2 + nl) : d->u_right ? (uint8_t *)(kf->u_right + n) : kf->desc + 32 * (size_t)n) - kf->dev);
-    r = m->reserve_all(up_end + 4096);
+    r = m->reserve_staging(up_end);   // the rows go up through it
     if (r != ORBX_OK) { orbx_keyframe_destroy(kf); return r; }
-    m->begin();
     if (n > 0 || inv_level_sigma2) {
         uint8_t *st = static_cast<uint8_t *>(m->stage.take(up_end + 16));
         if (!st) { set_error("staging arena exhausted"); orbx_keyframe_destroy(kf); return ORBX_E_INTERNAL; }
@@ -2967,17 +2561,8 @@ int orbx_keyframe_create_host(orbx_matcher *m, const orbx_frame_desc *d, const f
         if (d->u_right) memcpy(st + ((uint8_t *)kf->u_right - kf->dev), d->u_right, 4 * (size_t)n);
         if (inv_level_sigma2) memcpy(st + ((uint8_t *)kf->inv_sigma2 - kf->dev), inv_level_sigma2, 4 * (size_t)nl);
         m->dirty = true;
-        if (m->kernel_xfer && up_end <= orbx_matcher::kKernelXferMax) {
-            XferOps X;
-            X.n = 1;
-            X.op[0] = XferOp{kf->dev, st, (uint32_t)((up_end + 15) / 16), 0};   // (rounded up to 16 bytes: inside the region's 256-byte padding)
-            m->launch_xfer(X, X.op[0].units);
-        } else {
-            m->note(hipMemcpyAsync(kf->dev, st, up_end, hipMemcpyHostToDevice, m->stream));
-            m->xfers[4]++;
-        }
-        m->xfers[0]++; m->xfers[2] += (int64_t)up_end;
-        if (m->xfer_err != hipSuccess) { set_error(hipGetErrorString(m->xfer_err)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
+        const orbx_matcher::Span run = {0, up_end};
+        if ((r = m->upload_ranges(kf->dev, st, &run, 1)) != ORBX_OK) { orbx_keyframe_destroy(kf); return r; }
     }
     FramePrepare P;   // k_frame_prepare's in-place form (as orbx_frame_load_host): count, scale factors, grid_build_wave over the uploaded rows
     memset(&P, 0, sizeof(P));
@@ -3043,7 +2628,7 @@ int orbx_keyframe_fuse_search(orbx_matcher *m, int n_kf, orbx_keyframe *const *k
                               int32_t *const *best_idx, int32_t *const *best_dist) {
     if (!m || n_kf < 0 || (n_kf > 0 && (!kfs || !queries || !best_idx || !best_dist))) return ORBX_E_BAD_ARG;
     if (n_kf > ORBX_MAX_FUSE_KEYFRAMES) return ORBX_E_TOO_LARGE;
-    size_t total = 0, need = 0;
+    size_t total = 0;
     int nq_max = 0;
     for (int k = 0; k < n_kf; k++) {
         const orbx_fuse_queries &q = queries[k];
@@ -3051,51 +2636,47 @@ int orbx_keyframe_fuse_search(orbx_matcher *m, int n_kf, orbx_keyframe *const *k
         if (q.n > 0 && (!q.u || !q.v || !q.r || !q.level || !q.desc || !best_idx[k] || !best_dist[k])) return ORBX_E_BAD_ARG;
         total += (size_t)q.n;
         nq_max = std::max(nq_max, q.n);
-        need += 6 * Arena::pad(4 * (size_t)q.n) + Arena::pad(32 * (size_t)q.n);
     }
     for (int k = 0; k < n_kf; k++)
         for (int i = 0; i < queries[k].n; i++) { best_idx[k][i] = -1; best_dist[k][i] = 256; }
     if (total == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
-    need += Arena::pad(4 * (size_t)n_kf) + Arena::pad(sizeof(KfProblem) * (size_t)n_kf) + Arena::pad(8 * total) + 16 * 256 + 4096;
-    int r = m->reserve_all(need);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
     std::vector<KfProblem> R((size_t)n_kf);
-    std::vector<int32_t> cnts((size_t)n_kf), lv;
+    std::vector<int32_t> cnts((size_t)n_kf), lv(total);
     std::vector<size_t> off((size_t)n_kf);
     size_t o = 0;
-    for (int k = 0; k < n_kf; k++) {   // the inputs of every problem, adjacent in the arena: one upload run
+    for (int k = 0; k < n_kf; k++) {
         const orbx_fuse_queries &q = queries[k];
-        const size_t nq = (size_t)q.n;
         keyframe_problem(kfs[k], use_chi2 != 0, strict_fp, &R[k]);
-        cnts[k] = q.n; off[k] = o; o += nq;
-        if (nq == 0) continue;
-        WindowProblem &P = R[k].P;
-        float *f3[3]; const float *h3[3] = {q.u, q.v, q.r};
-        for (int c = 0; c < 3; c++) { f3[c] = A.take<float>(nq); H2D(f3[c], h3[c], 4 * nq); }
-        P.qx = f3[0]; P.qy = f3[1]; P.qr = f3[2];
-        int32_t *dmin = A.take<int32_t>(nq), *dmax = A.take<int32_t>(nq);
-        lv.resize(nq);
-        for (size_t i = 0; i < nq; i++) lv[i] = q.level[i] - 1;   // kpLevel<nPredictedLevel-1 || kpLevel>nPredictedLevel
-        H2D(dmin, lv.data(), 4 * nq); H2D(dmax, q.level, 4 * nq);
-        P.qmin = dmin; P.qmax = dmax;
-        if (q.ur && P.u_right) { float *p = A.take<float>(nq); H2D(p, q.ur, 4 * nq); P.qxr = p; }
-        { uint8_t *p = A.take<uint8_t>(32 * nq); H2D(p, q.desc, 32 * nq); P.qdesc = p; }
+        cnts[k] = q.n; off[k] = o;
+        for (int i = 0; i < q.n; i++) lv[o + (size_t)i] = q.level[i] - 1;   // kpLevel<nPredictedLevel-1 || kpLevel>nPredictedLevel
+        o += (size_t)q.n;
     }
-    int32_t *dcnt = A.take<int32_t>(n_kf);
-    KfProblem *dR = A.take<KfProblem>(n_kf);
-    u64 *dkeys = A.take<u64>(total);
+    int32_t *dcnt;
+    KfProblem *dR;
+    u64 *dkeys;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        for (int k = 0; k < n_kf; k++) {   // the inputs of every problem, adjacent in the arena: one upload run
+            const orbx_fuse_queries &q = queries[k];
+            const size_t nq = (size_t)q.n;
+            if (nq == 0) continue;
+            WindowProblem &P = R[k].P;
+            P.qx = A.up(q.u, nq); P.qy = A.up(q.v, nq); P.qr = A.up(q.r, nq);
+            P.qmin = A.up(lv.data() + off[k], nq); P.qmax = A.up(q.level, nq);
+            if (P.u_right) P.qxr = A.up_opt(q.ur, nq);
+            P.qdesc = A.up(q.desc, 32 * nq);
+        }
+        dcnt = A.up(cnts.data(), (size_t)n_kf);
+        dR = A.take<KfProblem>(n_kf);
+        dkeys = A.take<u64>(total);
+    }));
     for (int k = 0; k < n_kf; k++) { R[k].P.nq_ptr = dcnt + k; R[k].P.keys = dkeys + off[k]; }
-    H2D(dcnt, cnts.data(), 4 * (size_t)n_kf);
-    H2D(dR, R.data(), sizeof(KfProblem) * (size_t)n_kf);
-    r = keyframe_acquire(m, kfs, n_kf);
-    if (r != ORBX_OK) return r;
+    ORBX_TRY(m->h2d(dR, R.data(), sizeof(KfProblem) * (size_t)n_kf));
+    ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
     launch_window_best1_kf(m->exec(), dR, nq_max, n_kf);
     std::vector<u64> keys(total);
-    D2H(keys.data(), dkeys, 8 * total);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(keys.data(), dkeys, 8 * total));
+    ORBX_TRY(m->sync_and_deliver());
     keyframe_release(kfs, n_kf);
     for (int k = 0; k < n_kf; k++)
         for (int i = 0; i < queries[k].n; i++) {
@@ -3119,26 +2700,29 @@ int orbx_keyframe_fuse_map_points(orbx_matcher *m, int n_kf, orbx_keyframe *cons
         if (!kfs[k] || kfs[k]->device != m->device || !kfs[k]->inv_sigma2) return ORBX_E_BAD_ARG;
     if (total == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
-    const size_t need = 2 * Arena::pad(12 * np) + 2 * Arena::pad(4 * np) + Arena::pad(32 * np) + Arena::pad(sizeof(orbx_camera) * (size_t)n_kf) +
-                        Arena::pad(sizeof(orbx_frame_pose) * (size_t)n_kf) + Arena::pad(sizeof(KfProblem) * (size_t)n_kf) + 2 * Arena::pad(total) +
-                        6 * Arena::pad(4 * total) + Arena::pad(8 * total) + 16 * 256 + 4096;
-    int r = m->reserve_all(need);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
-    // uploads, adjacent in the arena (one run): the map points ONCE, then what grows with n_kf -- cameras, poses, problem records, skip flags
-    float *dp = A.take<float>(3 * np), *dn = A.take<float>(3 * np), *dmn = A.take<float>(np), *dmx = A.take<float>(np);
-    uint8_t *dd = A.take<uint8_t>(32 * np);
-    int32_t *dcnt = A.take<int32_t>(4);
-    orbx_camera *dcam = A.take<orbx_camera>(n_kf);
-    orbx_frame_pose *dpose = A.take<orbx_frame_pose>(n_kf);
-    KfProblem *dR = A.take<KfProblem>(n_kf);
-    uint8_t *dskip = skip ? A.take<uint8_t>(total) : nullptr;
-    // written by k_fuse_project, read by k_window_best1_kf
-    float *qx = A.take<float>(total), *qy = A.take<float>(total), *qxr = A.take<float>(total), *qr = A.take<float>(total);
-    int32_t *qmin = A.take<int32_t>(total), *qmax = A.take<int32_t>(total);
-    uint8_t *qvalid = A.take<uint8_t>(total);
-    u64 *dkeys = A.take<u64>(total);
+    const int32_t cnt4[4] = {n_mp, 0, 0, 0};
+    float *dp, *dn, *dmn, *dmx, *qx, *qy, *qxr, *qr;
+    uint8_t *dd, *dskip, *qvalid;
+    int32_t *dcnt, *qmin, *qmax;
+    orbx_camera *dcam;
+    orbx_frame_pose *dpose;
+    KfProblem *dR;
+    u64 *dkeys;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        // uploads, adjacent in the arena (one run): the map points ONCE, then what grows with n_kf -- cameras, poses, problem records, skip flags
+        dp = A.up(pos, 3 * np); dn = A.up(normal, 3 * np); dmn = A.up(min_dist, np); dmx = A.up(max_dist, np);
+        dd = A.up(mp_desc, 32 * np);
+        dcnt = A.up(cnt4, 4);
+        dcam = A.up(cams, (size_t)n_kf);
+        dpose = A.up(poses, (size_t)n_kf);
+        dR = A.take<KfProblem>(n_kf);
+        dskip = A.up_opt(skip, total);
+        // written by k_fuse_project, read by k_window_best1_kf
+        qx = A.take<float>(total); qy = A.take<float>(total); qxr = A.take<float>(total); qr = A.take<float>(total);
+        qmin = A.take<int32_t>(total); qmax = A.take<int32_t>(total);
+        qvalid = A.take<uint8_t>(total);
+        dkeys = A.take<u64>(total);
+    }));
     std::vector<KfProblem> R((size_t)n_kf);
     for (int k = 0; k < n_kf; k++) {
         keyframe_problem(kfs[k], true, strict_fp, &R[k]);
@@ -3147,22 +2731,16 @@ int orbx_keyframe_fuse_map_points(orbx_matcher *m, int n_kf, orbx_keyframe *cons
         P.qx = qx + o; P.qy = qy + o; P.qr = qr + o; P.qxr = qxr + o; P.qmin = qmin + o; P.qmax = qmax + o; P.qvalid = qvalid + o;
         P.qdesc = dd; P.nq_ptr = dcnt; P.keys = dkeys + o;
     }
-    const int32_t cnt4[4] = {n_mp, 0, 0, 0};
-    H2D(dp, pos, 12 * np); H2D(dn, normal, 12 * np); H2D(dmn, min_dist, 4 * np); H2D(dmx, max_dist, 4 * np); H2D(dd, mp_desc, 32 * np);
-    H2D(dcnt, cnt4, 16);
-    H2D(dcam, cams, sizeof(orbx_camera) * (size_t)n_kf); H2D(dpose, poses, sizeof(orbx_frame_pose) * (size_t)n_kf);
-    H2D(dR, R.data(), sizeof(KfProblem) * (size_t)n_kf);
-    if (skip) H2D(dskip, skip, total);
-    r = keyframe_acquire(m, kfs, n_kf);
-    if (r != ORBX_OK) return r;
+    ORBX_TRY(m->h2d(dR, R.data(), sizeof(KfProblem) * (size_t)n_kf));
+    ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
     hipLaunchKernelGGL(k_fuse_project, dim3((unsigned)((n_mp + 255) / 256), (unsigned)n_kf), dim3(256), 0, m->exec(), (const KfProblem *)dR,
                        (const orbx_camera *)dcam, (const orbx_frame_pose *)dpose, th, log_scale_factor, n_mp, (const float *)dp, (const float *)dn,
                        (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx, qy, qxr, qr, qmin, qmax, qvalid);
     launch_window_best1_kf(m->exec(), dR, n_mp, n_kf);
     std::vector<u64> keys(total);
-    if (projected) D2H(projected, qvalid, total);   // (adjacent to the keys: one download run)
-    D2H(keys.data(), dkeys, 8 * total);
-    SYNC_AND_DELIVER();
+    if (projected) ORBX_TRY(m->d2h(projected, qvalid, total));   // (adjacent to the keys: one download run)
+    ORBX_TRY(m->d2h(keys.data(), dkeys, 8 * total));
+    ORBX_TRY(m->sync_and_deliver());
     keyframe_release(kfs, n_kf);
     for (size_t i = 0; i < total; i++) {
         const u64 key = keys[i];
@@ -3187,11 +2765,10 @@ constexpr int kKeyFrameBowMax = 16384;   // k_frame_featvec sorts 8-byte keys in
 int keyframe_bow_alloc(int cap, KeyFrameBow **out) {
     KeyFrameBow *b = new KeyFrameBow();
     const size_t c = (size_t)std::max(cap, 1);
-    size_t o = 0;
-    auto carve = [&o](size_t bytes) { const size_t r = o; o += Arena::pad(bytes); return r; };
-    const size_t off_w = carve(4 * c), off_n = carve(4 * c), off_a = carve(4 * c), off_fn = carve(4 * c), off_fp = carve(4 * (c + 1)), off_fi = carve(4 * c),
-                 off_m = carve(8);
-    hipError_t e = hipMalloc((void **)&b->dev, o);
+    Layout L;
+    const size_t off_w = L.add(4 * c), off_n = L.add(4 * c), off_a = L.add(4 * c), off_fn = L.add(4 * c), off_fp = L.add(4 * (c + 1)), off_fi = L.add(4 * c),
+                 off_m = L.add(8);
+    hipError_t e = hipMalloc((void **)&b->dev, L.used);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&b->ready, hipEventDisableTiming);
     if (e != hipSuccess) { set_error(hipGetErrorString(e)); keyframe_bow_free(b); return ORBX_E_HIP; }
     b->word = (int32_t *)(b->dev + off_w); b->node = (int32_t *)(b->dev + off_n); b->angle = (float *)(b->dev + off_a);
@@ -3249,62 +2826,58 @@ int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const 
                      int match_stride, int32_t *nmatches, std::vector<int32_t> &counts) {
     const BowSide &O = mode == 0 ? B[0] : A[0];
     const int nrows = O.rows();
-    size_t need = 16384 + Arena::pad(sizeof(BowProblem) * (size_t)np) + Arena::pad(sizeof(BowPairSrc) * (size_t)np) + Arena::pad(4 * (size_t)np * nrows) +
-                  Arena::pad(4 * (size_t)np) + Arena::pad(8 * (size_t)np) + Arena::pad(4 * (size_t)np * (ORBX_HISTO_LENGTH + 2)) + Arena::pad(4 * 64);
     size_t tot_bound = 0, tot_nb = 0, n_ent = 0;
     int max_bound = 1;
     for (int k = 0; k < np; k++) {
         const size_t na = (size_t)A[k].rows(), nb = (size_t)B[k].rows();
-        need += Arena::pad(na) + Arena::pad(nb);
         tot_bound += (size_t)A[k].bound; tot_nb += nb; n_ent += std::max<size_t>(std::max(na, nb), 1);
         max_bound = std::max(max_bound, A[k].bound);
     }
-    need += Arena::pad(4 * (tot_bound + 1)) + Arena::pad(tot_nb + 1) + Arena::pad(4 * n_ent);
-    int r = m->reserve_all(need);
-    if (r != ORBX_OK) return r;
-    Arena &Ar = m->arena;
-    m->begin();
     std::vector<BowProblem> probs((size_t)np);
+    memset(probs.data(), 0, sizeof(BowProblem) * (size_t)np);
     std::vector<BowPairSrc> srcs((size_t)np);
+    // the flags of side A and B of problem k at [2 k], [2 k + 1] (NULL / no feature: none): `skip` flags as they are, `valid` flags inverted in `skip` first
+    std::vector<const uint8_t *> flags(2 * (size_t)np, nullptr);
     std::vector<uint8_t> skip;
-    auto up_flags = [&](const uint8_t *fl, int n, const uint8_t **out) -> int {   // (H2D returns from the enclosing function on failure)
-        *out = nullptr;
-        if (!fl || n <= 0) return ORBX_OK;
-        uint8_t *d = Ar.take<uint8_t>((size_t)n);
-        const uint8_t *src = fl;
-        if (invert) {
-            skip.resize((size_t)n);
-            for (int i = 0; i < n; i++) skip[i] = fl[i] ? 0 : 1;
-            src = skip.data();
-        }
-        H2D(d, src, (size_t)n);
-        *out = d;
-        return ORBX_OK;
-    };
-    // the uploads, side by side: the flags, the gate's level table, the records
     for (int k = 0; k < np; k++) {
-        BowProblem &P = probs[k];
-        memset(&P, 0, sizeof(P));
-        if ((r = up_flags(flags_a ? flags_a[k] : nullptr, A[k].n, &P.skip_a)) != ORBX_OK) return r;
-        if ((r = up_flags(flags_b ? flags_b[k] : nullptr, B[k].n, &P.skip_b)) != ORBX_OK) return r;
+        if (flags_a && A[k].n > 0) flags[2 * (size_t)k] = flags_a[k];
+        if (flags_b && B[k].n > 0) flags[2 * (size_t)k + 1] = flags_b[k];
+    }
+    if (invert) {
+        std::vector<size_t> at(flags.size(), 0);
+        for (size_t s = 0; s < flags.size(); s++) {
+            if (!flags[s]) continue;
+            const size_t n = (size_t)(s & 1 ? B[s / 2].n : A[s / 2].n);
+            at[s] = skip.size();
+            for (size_t i = 0; i < n; i++) skip.push_back(flags[s][i] ? 0 : 1);
+        }
+        for (size_t s = 0; s < flags.size(); s++)
+            if (flags[s]) flags[s] = skip.data() + at[s];
     }
     const float *dsig = nullptr;
-    if (gate) {
-        float *p = Ar.take<float>((size_t)nlevels);
-        H2D(p, sigma2_2, 4 * (size_t)nlevels);
-        dsig = p;
-    }
-    BowProblem *dP = Ar.take<BowProblem>(np);
-    BowPairSrc *dS = Ar.take<BowPairSrc>(np);
-    // device-only: the pairing; rows (filled with -1), match counts and the sides' counts side by side (one download run); vbMatched2, histograms +
-    // counters (zeroed by one fill); entries
-    int32_t *dpair = Ar.take<int32_t>(tot_bound + 1);
-    int32_t *dmatch = Ar.take<int32_t>((size_t)np * nrows);
-    int32_t *dnm = Ar.take<int32_t>(np);
-    int32_t *dcnt = Ar.take<int32_t>(2 * (size_t)np);
-    uint8_t *dtaken = Ar.take<uint8_t>(tot_nb + 1);
-    int32_t *dhist = Ar.take<int32_t>((size_t)np * (ORBX_HISTO_LENGTH + 2));
-    int32_t *dent = Ar.take<int32_t>(n_ent);
+    BowProblem *dP;
+    BowPairSrc *dS;
+    int32_t *dpair, *dmatch, *dnm, *dcnt, *dhist, *dent;
+    uint8_t *dtaken;
+    ORBX_TRY(m->carve([&](Carve &C) {
+        // the uploads, side by side: the flags, the gate's level table, the records
+        for (int k = 0; k < np; k++) {
+            probs[k].skip_a = C.up_opt(flags[2 * (size_t)k], (size_t)A[k].n);
+            probs[k].skip_b = C.up_opt(flags[2 * (size_t)k + 1], (size_t)B[k].n);
+        }
+        if (gate) dsig = C.up(sigma2_2, (size_t)nlevels);
+        dP = C.take<BowProblem>(np);
+        dS = C.take<BowPairSrc>(np);
+        // device-only: the pairing; rows (filled with -1), match counts and the sides' counts side by side (one download run); vbMatched2, histograms +
+        // counters (zeroed by one fill); entries
+        dpair = C.take<int32_t>(tot_bound + 1);
+        dmatch = C.take<int32_t>((size_t)np * nrows);
+        dnm = C.take<int32_t>(np);
+        dcnt = C.take<int32_t>(2 * (size_t)np);
+        dtaken = C.take<uint8_t>(tot_nb + 1);
+        dhist = C.take<int32_t>((size_t)np * (ORBX_HISTO_LENGTH + 2));
+        dent = C.take<int32_t>(n_ent);
+    }));
     {
         size_t op = 0, ot = 0, oe = 0;
         for (int k = 0; k < np; k++) {
@@ -3329,8 +2902,8 @@ int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const 
             op += (size_t)a.bound; ot += (size_t)b.rows(); oe += std::max<size_t>(std::max((size_t)a.rows(), (size_t)b.rows()), 1);
         }
     }
-    H2D(dP, probs.data(), sizeof(BowProblem) * (size_t)np);
-    H2D(dS, srcs.data(), sizeof(BowPairSrc) * (size_t)np);
+    ORBX_TRY(m->h2d(dP, probs.data(), sizeof(BowProblem) * (size_t)np));
+    ORBX_TRY(m->h2d(dS, srcs.data(), sizeof(BowPairSrc) * (size_t)np));
     ORBX_HIP(m->fill(dmatch, 0xff, 4 * (size_t)np * nrows));
     ORBX_HIP(m->fill(dtaken, 0, (size_t)((const uint8_t *)(dhist + (size_t)np * (ORBX_HISTO_LENGTH + 2)) - dtaken)));   // vbMatched2, (padding,) histograms + counters
     hipLaunchKernelGGL(k_bow_pair_resident, dim3((unsigned)((max_bound + 255) / 256), (unsigned)np), dim3(256), 0, m->exec(), dP, (const BowPairSrc *)dS);
@@ -3339,15 +2912,15 @@ int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const 
     ORBX_HIP(hipGetLastError());
     std::vector<int32_t> rows;
     if (O.n >= 0) {
-        for (int k = 0; k < np; k++) D2H(match + (size_t)k * match_stride, dmatch + (size_t)k * nrows, 4 * (size_t)O.n);
+        for (int k = 0; k < np; k++) ORBX_TRY(m->d2h(match + (size_t)k * match_stride, dmatch + (size_t)k * nrows, 4 * (size_t)O.n));
     } else if (nrows > 0) {   // N comes back with the results
         rows.resize((size_t)np * nrows);
-        D2H(rows.data(), dmatch, 4 * (size_t)np * nrows);
+        ORBX_TRY(m->d2h(rows.data(), dmatch, 4 * (size_t)np * nrows));
     }
     counts.assign(2 * (size_t)np, 0);
-    D2H(nmatches, dnm, 4 * (size_t)np);
-    D2H(counts.data(), dcnt, 8 * (size_t)np);
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->d2h(nmatches, dnm, 4 * (size_t)np));
+    ORBX_TRY(m->d2h(counts.data(), dcnt, 8 * (size_t)np));
+    ORBX_TRY(m->sync_and_deliver());
     if (O.n < 0) {
         const int n = std::min(std::max(counts[mode == 0 ? 1 : 0], 0), O.cap);
         for (int k = 0; k < np; k++)
@@ -3385,11 +2958,9 @@ int orbx_keyframe_compute_bow(orbx_matcher *m, orbx_keyframe *kf, const orbx_voc
     const int nc = n_host >= 0 ? n_host : kf->cap;   // features the kernels may see
     if (nc > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;
     ORBX_HIP(hipSetDevice(m->device));
-    int r = m->reserve_all(Arena::pad(8 * (size_t)nc) + 4096);
-    if (r != ORBX_OK) return r;
-    m->begin();
+    ORBX_TRY(m->reserve_staging(8 * (size_t)nc));   // the ids come down through it
     if (!b) {
-        if ((r = keyframe_bow_alloc(kf->cap, &b)) != ORBX_OK) return r;
+        ORBX_TRY(keyframe_bow_alloc(kf->cap, &b));
         b->voc = v; b->levelsup = levelsup;
         int sort_cap = 1;
         while (sort_cap < nc) sort_cap <<= 1;
@@ -3414,22 +2985,21 @@ int orbx_keyframe_compute_bow(orbx_matcher *m, orbx_keyframe *kf, const orbx_voc
         if (e != hipSuccess) { set_error(hipGetErrorString(e)); (void)hipStreamSynchronize(m->stream); m->dirty = false; keyframe_bow_free(b); return ORBX_E_HIP; }
         kf->bow.store(b, std::memory_order_release);
     } else {
-        r = keyframe_bow_acquire(m, kf);
-        if (r != ORBX_OK) return r;
+        ORBX_TRY(keyframe_bow_acquire(m, kf));
     }
     if (!down || nc == 0) return ORBX_OK;
     std::vector<int32_t> h;
     int32_t cnt = n_host;
     if (n_host >= 0) {
-        if (word_id) D2H(word_id, b->word, 4 * (size_t)nc);
-        if (node_id) D2H(node_id, b->node, 4 * (size_t)nc);
+        if (word_id) ORBX_TRY(m->d2h(word_id, b->word, 4 * (size_t)nc));
+        if (node_id) ORBX_TRY(m->d2h(node_id, b->node, 4 * (size_t)nc));
     } else {   // N comes back with the ids
         h.resize(2 * (size_t)nc);
-        D2H(h.data(), b->word, 4 * (size_t)nc);
-        D2H(h.data() + nc, b->node, 4 * (size_t)nc);
-        D2H(&cnt, kf->count, 4);
+        ORBX_TRY(m->d2h(h.data(), b->word, 4 * (size_t)nc));
+        ORBX_TRY(m->d2h(h.data() + nc, b->node, 4 * (size_t)nc));
+        ORBX_TRY(m->d2h(&cnt, kf->count, 4));
     }
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->sync_and_deliver());
     keyframe_bow_release(kf);
     if (n_host < 0) {
         cnt = std::min(std::max(cnt, 0), kf->cap);
@@ -3602,54 +3172,49 @@ extern "C" int orbx_frame_search_local_points(orbx_matcher *m, orbx_frame *f, co
     if (nc > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;
     ORBX_HIP(hipSetDevice(m->device));
     const size_t q = (size_t)n_mp;
-    const size_t need = 2 * Arena::pad(12 * q) + 2 * Arena::pad(4 * q) + Arena::pad(32 * q) + 2 * Arena::pad(q) + Arena::pad(sizeof(FrustumFrame)) +
-                        Arena::pad((size_t)nc) + Arena::pad(q) + 6 * Arena::pad(4 * q) + 3 * Arena::pad(4 * q) + 2 * Arena::pad(q) +
-                        Arena::pad(8 * kTopK * q) + 2 * Arena::pad(4 * q) + Arena::pad(4 * (size_t)nc) + Arena::pad(sizeof(WindowProblem)) +
-                        Arena::pad(sizeof(ResolveProblem)) + 16 * 256 + 4096;
-    int r = m->reserve_all(need);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
-    // inputs (one run of the arena)
-    float *dp = A.take<float>(3 * q), *dn = A.take<float>(3 * q), *dmn = A.take<float>(q), *dmx = A.take<float>(q);
-    uint8_t *ddesc = A.take<uint8_t>(32 * q);
-    H2D(dp, pos, 12 * q); H2D(dn, normal, 12 * q); H2D(dmn, min_dist, 4 * q); H2D(dmx, max_dist, 4 * q); H2D(ddesc, mp_desc, 32 * q);
-    uint8_t *delig = nullptr, *dho = nullptr, *docc = nullptr;
-    if (eligible) { delig = A.take<uint8_t>(q); H2D(delig, eligible, q); }
-    if (has_obs) { dho = A.take<uint8_t>(q); H2D(dho, has_obs, q); }
-    if (frame_occupied && n > 0) { docc = A.take<uint8_t>((size_t)n); H2D(docc, frame_occupied, (size_t)n); }
-    FrustumFrame *dF = A.take<FrustumFrame>(1);
     const FrustumFrame FF = frustum_frame(cam, pose, f->bounds, log_scale_factor, f->nlevels, viewing_cos_limit);
-    H2D(dF, &FF, sizeof(FF));
-    int32_t *dcnt = A.take<int32_t>(4);
     const int32_t cnts[2] = {n, n_mp};
-    H2D(dcnt, cnts, 8);
-    WindowProblem *dP = A.take<WindowProblem>(1);
-    ResolveProblem *dR = A.take<ResolveProblem>(1);
-    // the projection records and the windows: device only
-    uint8_t *div = A.take<uint8_t>(q);
-    float *dx = A.take<float>(q), *dy = A.take<float>(q), *dxr = A.take<float>(q), *dd = A.take<float>(q), *dvc = A.take<float>(q);
-    int32_t *dl = A.take<int32_t>(q);
-    float *dqr = A.take<float>(q);
-    int32_t *dqmin = A.take<int32_t>(q), *dqmax = A.take<int32_t>(q);
-    uint8_t *dvalid = A.take<uint8_t>(q);
     WindowProblem P;
     memset(&P, 0, sizeof(P));
     ResolveProblem R;
     memset(&R, 0, sizeof(R));
+    float *dp, *dn, *dmn, *dmx, *dx, *dy, *dxr, *dd, *dvc, *dqr;
+    uint8_t *ddesc, *delig, *div, *dvalid, *div_out;
+    int32_t *dcnt, *dl, *dqmin, *dqmax;
+    FrustumFrame *dF;
+    WindowProblem *dP;
+    ResolveProblem *dR;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        // inputs (one run of the arena)
+        dp = A.up(pos, 3 * q); dn = A.up(normal, 3 * q); dmn = A.up(min_dist, q); dmx = A.up(max_dist, q);
+        ddesc = A.up(mp_desc, 32 * q);
+        delig = A.up_opt(eligible, q);
+        R.q_has_obs = A.up_opt(has_obs, q);
+        if (n > 0) P.occupied0 = A.up_opt(frame_occupied, (size_t)n);
+        dF = A.up(&FF, 1);
+        dcnt = A.up(cnts, 2, 2);
+        dP = A.take<WindowProblem>(1);
+        dR = A.take<ResolveProblem>(1);
+        // the projection records and the windows: device only
+        div = A.take<uint8_t>(q);
+        dx = A.take<float>(q); dy = A.take<float>(q); dxr = A.take<float>(q); dd = A.take<float>(q); dvc = A.take<float>(q);
+        dl = A.take<int32_t>(q);
+        dqr = A.take<float>(q);
+        dqmin = A.take<int32_t>(q); dqmax = A.take<int32_t>(q);
+        dvalid = A.take<uint8_t>(q);
+        P.keys = A.take<u64>(q * kTopK); P.meta = A.take<int32_t>(q);
+        R.entries = A.take<int32_t>(q);
+        // the downloads side by side: mbTrackInView, the matches, nmatches
+        div_out = A.take<uint8_t>(q);
+        R.match = A.take<int32_t>(nc);
+        R.nmatches = A.take<int32_t>(1);
+    }));
     P.kps = f->kps; P.desc = f->desc; P.n_ptr = f->count; P.nq_ptr = dcnt + 1;
     if (f->has_ur) { P.u_right = f->u_right; P.qxr = dxr; }   // mTrackProjXR against mvuRight (ORBmatcher.cc:92-97)
-    P.occupied0 = docc;
     P.qx = dx; P.qy = dy; P.qr = dqr; P.qmin = dqmin; P.qmax = dqmax; P.qdesc = ddesc; P.qvalid = dvalid;
     P.gstart = f->gstart; P.gorder = f->gorder;
-    P.keys = A.take<u64>(q * kTopK); P.meta = A.take<int32_t>(q);
-    R.mode = 1; R.nnratio = nnratio; R.max_dist = (float)ORBX_TH_HIGH; R.cleared_value = -2; R.q_has_obs = dho;
-    R.entries = A.take<int32_t>(q);
-    // the downloads side by side: mbTrackInView, the matches, nmatches
-    uint8_t *div_out = A.take<uint8_t>(q);
-    R.match = A.take<int32_t>(nc);
-    R.nmatches = A.take<int32_t>(1);
-    H2D(dP, &P, sizeof(P)); H2D(dR, &R, sizeof(R));
+    R.mode = 1; R.nnratio = nnratio; R.max_dist = (float)ORBX_TH_HIGH; R.cleared_value = -2;
+    ORBX_TRY(m->h2d(dP, &P, sizeof(P))); ORBX_TRY(m->h2d(dR, &R, sizeof(R)));
     hipLaunchKernelGGL(k_in_frustum, dim3((n_mp + 255) / 256, 1), dim3(256), 0, m->exec(), (const FrustumFrame *)dF, n_mp, (const float *)dp,
                        (const float *)dn, (const float *)dmn, (const float *)dmx, div, dx, dy, dxr, dd, dl, dvc);
     hipLaunchKernelGGL(k_local_windows, dim3((n_mp + 255) / 256), dim3(256), 0, m->exec(), n_mp, (const uint8_t *)div, (const uint8_t *)delig,
@@ -3664,18 +3229,18 @@ extern "C" int orbx_frame_search_local_points(orbx_matcher *m, orbx_frame *f, co
     }
     ORBX_HIP(hipGetLastError());
     int32_t nm = 0;
-    D2H(in_view, div_out, q);
+    ORBX_TRY(m->d2h(in_view, div_out, q));
     if (match) {
         if (n >= 0) {
-            D2H(frame_match, R.match, 4 * (size_t)n);
+            ORBX_TRY(m->d2h(frame_match, R.match, 4 * (size_t)n));
         } else {   // N comes back with the results
             f->h_match.resize((size_t)f->cap);
-            D2H(f->h_match.data(), R.match, 4 * (size_t)nc);
-            D2H(&f->n, f->count, 4);
+            ORBX_TRY(m->d2h(f->h_match.data(), R.match, 4 * (size_t)nc));
+            ORBX_TRY(m->d2h(&f->n, f->count, 4));
         }
-        D2H(&nm, R.nmatches, 4);
+        ORBX_TRY(m->d2h(&nm, R.nmatches, 4));
     }
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->sync_and_deliver());
     if (n < 0) {
         f->n_known = true;
         memcpy(frame_match, f->h_match.data(), 4 * (size_t)std::max(f->n, 0));
@@ -3708,24 +3273,8 @@ extern "C" int orbx_frame_load_host_fisheye(orbx_frame *f, const orbx_frame_desc
     memcpy(f->stage + f->off_desc, left->descriptors, b_desc);
     memcpy(f->stage + f->off_l2r, l2r, b_l2r);
     memcpy(f->stage + f->off_r2l, r2l, b_r2l);
-    XferOps X;
-    X.n = 0;
-    uint32_t max_units = 0;
-    const size_t offs[4] = {f->off_kps, f->off_desc, f->off_l2r, f->off_r2l}, bytes[4] = {b_kl + b_kr, b_desc, b_l2r, b_r2l};
-    for (int k = 0; k < 4; k++) {
-        if (!bytes[k]) continue;
-        if (m->kernel_xfer) {
-            const uint32_t units = (uint32_t)((bytes[k] + 15) / 16);   // (rounded up to 16 bytes: inside the region's 256-byte padding)
-            X.op[X.n++] = XferOp{f->dev + offs[k], f->stage + offs[k], units, 0};
-            max_units = std::max(max_units, units);
-        } else {
-            ORBX_HIP(hipMemcpyAsync(f->dev + offs[k], f->stage + offs[k], bytes[k], hipMemcpyHostToDevice, m->stream));
-            m->xfers[4]++;
-        }
-        m->xfers[0]++; m->xfers[2] += (int64_t)bytes[k];
-    }
-    if (X.n) m->launch_xfer(X, max_units);
-    if (m->xfer_err != hipSuccess) { set_error(hipGetErrorString(m->xfer_err)); return ORBX_E_HIP; }
+    const orbx_matcher::Span rows[4] = {{f->off_kps, b_kl + b_kr}, {f->off_desc, b_desc}, {f->off_l2r, b_l2r}, {f->off_r2l, b_r2l}};
+    ORBX_TRY(m->upload_ranges(f->dev, f->stage, rows, 4));
     FramePrepare P0;
     const float b[4] = {left->min_x, left->max_x, left->min_y, left->max_y};
     frame_prepare_common(f, P0, left->scale_factors, left->nlevels, b);
@@ -3837,63 +3386,57 @@ extern "C" int orbx_frame_search_local_points_fisheye(orbx_matcher *m, orbx_fram
     const int nc = N >= 0 ? N : f->cap;
     ORBX_HIP(hipSetDevice(m->device));
     const size_t q = (size_t)n_mp, q2 = 2 * q;
-    const size_t need = 2 * Arena::pad(12 * q) + 2 * Arena::pad(4 * q) + Arena::pad(32 * q) + 3 * Arena::pad(q) + Arena::pad(4 * q) + Arena::pad(sizeof(FrustumChecks)) +
-                        Arena::pad((size_t)nc) + Arena::pad(16) + Arena::pad(2 * sizeof(WindowProblem)) + Arena::pad(q2) + 5 * Arena::pad(4 * q2) +
-                        3 * Arena::pad(4 * q2) + Arena::pad(q2) + 2 * Arena::pad(8 * kTopK * q) + 2 * Arena::pad(4 * q) + Arena::pad(4 * q2) + Arena::pad(q2) +
-                        Arena::pad(4 * (size_t)nc) + 16 * 256 + 4096;
-    int r = m->reserve_all(need);
-    if (r != ORBX_OK) return r;
-    Arena &A = m->arena;
-    m->begin();
-    // inputs (one run of the arena)
-    float *dp = A.take<float>(3 * q), *dn = A.take<float>(3 * q), *dmn = A.take<float>(q), *dmx = A.take<float>(q);
-    uint8_t *ddesc = A.take<uint8_t>(32 * q);
-    H2D(dp, pos, 12 * q); H2D(dn, normal, 12 * q); H2D(dmn, min_dist, 4 * q); H2D(dmx, max_dist, 4 * q); H2D(ddesc, mp_desc, 32 * q);
-    uint8_t *delig = nullptr, *dho = nullptr, *docc = nullptr;
-    float *dtd = nullptr;
-    if (eligible) { delig = A.take<uint8_t>(q); H2D(delig, eligible, q); }
-    if (has_obs) { dho = A.take<uint8_t>(q); H2D(dho, has_obs, q); }
-    if (track_depth) { dtd = A.take<float>(q); H2D(dtd, track_depth, 4 * q); }
-    if (frame_occupied && N > 0) { docc = A.take<uint8_t>((size_t)N); H2D(docc, frame_occupied, (size_t)N); }
     FrustumChecks FC;
     memset(&FC, 0, sizeof(FC));
     static_assert(sizeof(FisheyeView) == sizeof(orbx_fisheye_view), "orbx_fisheye_view layout");
     memcpy(FC.view, views, sizeof(FisheyeView) * 2);
     FC.minx = f->bounds[0]; FC.maxx = f->bounds[1]; FC.miny = f->bounds[2]; FC.maxy = f->bounds[3];
     FC.log_scale_factor = log_scale_factor; FC.nlevels = f->nlevels; FC.cos_limit = viewing_cos_limit;
-    FrustumChecks *dF = A.take<FrustumChecks>(1);
-    H2D(dF, &FC, sizeof(FC));
-    int32_t *dcnt = A.take<int32_t>(4);
     const int32_t cnts[4] = {n_mp, 0, 0, 0};
-    H2D(dcnt, cnts, 16);
-    WindowProblem *dP = A.take<WindowProblem>(2);
-    // the projection records and the windows: device only, [2][n_mp] (left, right)
-    uint8_t *div = A.take<uint8_t>(q2);
-    float *dx = A.take<float>(q2), *dy = A.take<float>(q2), *dd = A.take<float>(q2), *dvc = A.take<float>(q2);
-    int32_t *dl = A.take<int32_t>(q2);
-    float *dqr = A.take<float>(q2);
-    int32_t *dqmin = A.take<int32_t>(q2), *dqmax = A.take<int32_t>(q2);
-    uint8_t *dvalid = A.take<uint8_t>(q2);
     WindowProblem P[2];
     memset(P, 0, sizeof(P));
+    TwinProblem T;
+    memset(&T, 0, sizeof(T));
+    float *dp, *dn, *dmn, *dmx, *dtd, *dx, *dy, *dd, *dvc, *dqr;
+    uint8_t *ddesc, *delig, *div, *dvalid, *div_out;
+    int32_t *dcnt, *dl, *dqmin, *dqmax;
+    FrustumChecks *dF;
+    WindowProblem *dP;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        // inputs (one run of the arena)
+        dp = A.up(pos, 3 * q); dn = A.up(normal, 3 * q); dmn = A.up(min_dist, q); dmx = A.up(max_dist, q);
+        ddesc = A.up(mp_desc, 32 * q);
+        delig = A.up_opt(eligible, q);
+        T.q_has_obs = A.up_opt(has_obs, q);
+        dtd = A.up_opt(track_depth, q);
+        if (N > 0) T.occupied0 = A.up_opt(frame_occupied, (size_t)N);
+        dF = A.up(&FC, 1);
+        dcnt = A.up(cnts, 4);
+        dP = A.take<WindowProblem>(2);
+        // the projection records and the windows: device only, [2][n_mp] (left, right)
+        div = A.take<uint8_t>(q2);
+        dx = A.take<float>(q2); dy = A.take<float>(q2); dd = A.take<float>(q2); dvc = A.take<float>(q2);
+        dl = A.take<int32_t>(q2);
+        dqr = A.take<float>(q2);
+        dqmin = A.take<int32_t>(q2); dqmax = A.take<int32_t>(q2);
+        dvalid = A.take<uint8_t>(q2);
+        for (int s = 0; s < 2; s++) { P[s].keys = A.take<u64>(q * kTopK); P[s].meta = A.take<int32_t>(q); }
+        T.entries = A.take<int32_t>(q2);
+        // the downloads side by side: mbTrackInView / mbTrackInViewR, the matches, nmatches
+        div_out = A.take<uint8_t>(q2);
+        T.match = A.take<int32_t>(nc);
+        T.nmatches = A.take<int32_t>(1);
+    }));
     P[0].kps = f->kps; P[0].desc = f->desc; P[0].n_ptr = f->count; P[0].gstart = f->gstart; P[0].gorder = f->gorder;
     P[1].kps = f->kps + f->roff; P[1].desc = f->desc + (size_t)f->roff * 32; P[1].n_ptr = f->count + 1; P[1].gstart = f->gstart_r; P[1].gorder = f->gorder_r;
     for (int s = 0; s < 2; s++) {
         const size_t o = (size_t)s * q;
         P[s].nq_ptr = dcnt;
         P[s].qx = dx + o; P[s].qy = dy + o; P[s].qr = dqr + o; P[s].qmin = dqmin + o; P[s].qmax = dqmax + o; P[s].qvalid = dvalid + o; P[s].qdesc = ddesc;
-        P[s].keys = A.take<u64>(q * kTopK); P[s].meta = A.take<int32_t>(q);
     }
-    TwinProblem T;
-    memset(&T, 0, sizeof(T));
     T.mode = 1; T.nq = n_mp; T.nnratio = nnratio; T.max_dist = (float)ORBX_TH_HIGH; T.cleared_value = -2;
-    T.l2r = f->l2r; T.r2l = f->r2l; T.occupied0 = docc; T.q_has_obs = dho;
-    T.entries = A.take<int32_t>(q2);
-    // the downloads side by side: mbTrackInView / mbTrackInViewR, the matches, nmatches
-    uint8_t *div_out = A.take<uint8_t>(q2);
-    T.match = A.take<int32_t>(nc);
-    T.nmatches = A.take<int32_t>(1);
-    H2D(dP, P, sizeof(P));
+    T.l2r = f->l2r; T.r2l = f->r2l;
+    ORBX_TRY(m->h2d(dP, P, sizeof(P)));
     hipLaunchKernelGGL(k_in_frustum_checks, dim3((n_mp + 255) / 256, 2), dim3(256), 0, m->exec(), (const FrustumChecks *)dF, n_mp, (const float *)dp,
                        (const float *)dn, (const float *)dmn, (const float *)dmx, div, dx, dy, dd, dl, dvc);
     hipLaunchKernelGGL(k_local_windows_fisheye, dim3((n_mp + 255) / 256), dim3(256), 0, m->exec(), n_mp, (const uint8_t *)div, (const uint8_t *)delig,
@@ -3901,23 +3444,22 @@ extern "C" int orbx_frame_search_local_points_fisheye(orbx_matcher *m, orbx_fram
                        far_points ? 1 : 0, th_far_points, dqr, dqmin, dqmax, dvalid, div_out);
     const bool match = N != 0;   // (an empty frame: isInFrustumChecks only)
     if (match) {
-        r = launch_twin(m, dP, T, grid_of(f->bounds), nc, n_mp);
-        if (r != ORBX_OK) return r;
+        ORBX_TRY(launch_twin(m, dP, T, grid_of(f->bounds), nc, n_mp));
     }
     ORBX_HIP(hipGetLastError());
     int32_t nm = 0;
-    D2H(in_view, div_out, q2);
+    ORBX_TRY(m->d2h(in_view, div_out, q2));
     if (match) {
         if (N >= 0) {
-            D2H(frame_match, T.match, 4 * (size_t)N);
+            ORBX_TRY(m->d2h(frame_match, T.match, 4 * (size_t)N));
         } else {   // the counts come back with the results
             f->h_match.resize((size_t)f->cap);
-            D2H(f->h_match.data(), T.match, 4 * (size_t)nc);
-            D2H(f->h_count, f->count, 8);
+            ORBX_TRY(m->d2h(f->h_match.data(), T.match, 4 * (size_t)nc));
+            ORBX_TRY(m->d2h(f->h_count, f->count, 8));
         }
-        D2H(&nm, T.nmatches, 4);
+        ORBX_TRY(m->d2h(&nm, T.nmatches, 4));
     }
-    SYNC_AND_DELIVER();
+    ORBX_TRY(m->sync_and_deliver());
     if (N < 0) {
         f->n_left = f->h_count[0]; f->n_right = f->h_count[1]; f->n = f->n_left + f->n_right; f->n_known = true;
         memcpy(frame_match, f->h_match.data(), 4 * (size_t)std::max(f->n, 0));

@@ -50,16 +50,19 @@ def main():
     if "asm(" in "".join((BUILD / f).read_text() for f in ("extractor_kernels.hip.h", "matcher_kernels.hip.h")):
         print("warning: inline assembly left in the copies", file=sys.stderr)
     asan = "--asan" in sys.argv[1:]   # AddressSanitizer build: device-side out-of-bounds accesses to "device" (heap) buffers are reported
+    # --asan --static-rt: the library leaves the sanitizer's symbols to the EXECUTABLE that links it (a stand-alone program linked with -fsanitize=address
+    # carries the runtime itself, so nothing about the process's library order matters); not loadable into python
+    static_rt = asan and "--static-rt" in sys.argv[1:]
     units = [a for a in sys.argv[1:] if not a.startswith("--")] or ["orbx_extractor.cc", "orbx_matcher.cc"]
     # UBSan build: conversions of out-of-range floats to integers (x86 and gfx950 give DIFFERENT results for those), shifts by >= the
     # width, signed overflow, out-of-bounds indices of fixed-size arrays; unaligned accesses are intended (the kernels rely on them)
     ubsan = "--ubsan" in sys.argv[1:]
-    out = BUILD / ("liborbx_emul_asan.so" if asan else "liborbx_emul_ubsan.so" if ubsan else "liborbx_emul.so")
+    out = BUILD / ("liborbx_emul_asan_static.so" if static_rt else "liborbx_emul_asan.so" if asan else "liborbx_emul_ubsan.so" if ubsan else "liborbx_emul.so")
     cmd = [CLANG, "-std=c++17", "-O1", "-g", "-fPIC", "-shared", "-ffp-contract=off", "-fno-strict-aliasing", "-Wno-unused-value",
            "-Wno-ignored-attributes", "-Wno-unknown-attributes", f"-I{HERE}", f"-I{BUILD}", "-o", str(out),
            str(HERE / "launch.cc")] + [str(BUILD / u) for u in units] + ["-ldl"]
     if asan:
-        cmd[1:1] = ["-fsanitize=address", "-fno-omit-frame-pointer", "-shared-libasan"]
+        cmd[1:1] = ["-fsanitize=address", "-fno-omit-frame-pointer"] + ([] if static_rt else ["-shared-libasan"])
     if ubsan:
         rt = subprocess.run([CLANG, "-print-file-name=libclang_rt.ubsan_standalone-x86_64.so"], capture_output=True, text=True).stdout.strip()
         cmd[1:1] = ["-fsanitize=float-cast-overflow,shift,signed-integer-overflow,bounds,integer-divide-by-zero,float-divide-by-zero",

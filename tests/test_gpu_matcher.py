@@ -250,6 +250,44 @@ def test_projection_matchers_at_the_largest_frame(oracle):
         m.SearchByProjectionFrame(_frame_view(k1, d1, sf, W, H), q, 15.0, 0, None)
 
 
+def test_one_context_growing_calls_that_fit_the_old_arena(oracle):
+    """One ORBmatcher, calls of growing size that still fit the arena an earlier call left behind (it grows by 3/2): M2 with 2000 queries, then 3060
+    (u_right, occupancy mask, angles, has_obs: every optional buffer), M1 with 3110 map points, knn2 -- each == oracle.  A call's arena size is the
+    sum of the buffers it carves; nothing is re-allocated between these calls, so a size that missed a buffer would show here."""
+    import orb_slam3_amd as osa
+    rng = np.random.default_rng(33)
+    W, H, N = 640, 480, 200
+    kf, df = _synthetic_frame(rng, N, W, H)
+    sf = np.array([1.2 ** i for i in range(8)], np.float32)
+    ur = np.where(rng.random(N) < 0.7, kf["x"] - rng.uniform(1, 30, N), -1.0).astype(np.float32)
+    view = osa.FrameView(kf, df, 0.0, float(W), 0.0, float(H), sf, ur)
+    occ = (rng.random(N) < 0.1).astype(np.uint8)
+    grid = oracle.OracleGrid(kf, 0.0, float(W), 0.0, float(H))
+    m = osa.ORBmatcher(0.8, True)
+
+    def queries(n):
+        src = rng.integers(0, N, n)
+        return src, dict(u=kf["x"][src] + rng.normal(0, 1.5, n).astype(np.float32), v=kf["y"][src] + rng.normal(0, 1.5, n).astype(np.float32),
+                         ur=np.where(ur[src] >= 0, ur[src] + 0.5, -1.0).astype(np.float32), octave=kf["octave"][src], angle=kf["angle"][src],
+                         desc=_noisy_copy(rng, df[src], 0.05), has_obs=(rng.random(n) < 0.9).astype(np.uint8))
+
+    for n_q in (2000, 3060):
+        _, q = queries(n_q)
+        on, ocm = oracle.search_by_projection_frame(grid, df, sf, q, 15.0, 0, True, ur, occ)
+        n, cm = m.SearchByProjectionFrame(view, q, 15.0, 0, occ)
+        assert n == on and np.array_equal(cm, ocm) and n > 50, (n_q, n, on)
+    n_mp = 3110
+    src, q = queries(n_mp)
+    mp = dict(proj_x=q["u"], proj_y=q["v"], proj_xr=q["ur"], level=kf["octave"][src], view_cos=rng.uniform(0.9, 1.0, n_mp).astype(np.float32),
+              desc=q["desc"], in_view=(rng.random(n_mp) < 0.95).astype(np.uint8), has_obs=q["has_obs"])
+    on, ofm = oracle.search_by_projection_mappoints(grid, df, sf, mp, 3.0, 0.8, ur, occ)
+    n, fm = m.SearchByProjection(view, mp, 3.0, occ)
+    assert n == on and np.array_equal(fm, ofm) and n > 50, (n, on)
+    idx, dist = m.knn2(q["desc"], df)
+    oi, od = oracle.knn2(q["desc"], df)
+    assert np.array_equal(idx, oi) and np.array_equal(dist, od)
+
+
 @pytest.mark.parametrize("seed", [1, 2, 3])
 def test_projection_matchers_under_heavy_contention(oracle, seed):
     """The replay of the sequential query loop (k_resolve_wide_t) where it is hardest: thousands of queries compete for a few hundred features packed into a

@@ -285,3 +285,25 @@ def test_device_atan2f_equals_libm_and_kb8_projection_equals_oracle(emul_lib, tm
     assert r.returncode == 0, r.stderr[-3000:]
     r = subprocess.run([str(exe), "7"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0 and "bad 0" in r.stdout, r.stdout[-2000:]
+
+
+def test_one_context_calls_of_changing_size_stand_alone_under_sanitizers(tmp_path):
+    """tests/cpp/arena_reuse_check.cpp: on ONE matcher context per entry point a big call, one about 1.5 times as big that still fits the arena the first
+    left behind, and a small one -- SearchByProjection (frame with u_right, mask, angles, has_obs; map points; window), Fuse's search, knn2,
+    SearchForInitialization, ComputeDistinctiveDescriptors; every result equals the same call on a fresh context.  A stand-alone program compiled with
+    -fsanitize=address,undefined, the sanitizer's runtime linked INTO it, and the AddressSanitizer build of the emulated library resolving against that
+    runtime: an upload staged past the pinned mirror or a kernel writing past the arena ends the run.  (The stand-in HIP runtime never frees its
+    streams: leak detection is off.)"""
+    import fcntl
+    (SIMT / "build").mkdir(exist_ok=True)
+    with open(SIMT / "build" / ".lock", "w") as lock:   # the copied sources in tests/simt/build are shared with the other tests' builds
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        r = subprocess.run([sys.executable, str(SIMT / "build.py"), "--asan", "--static-rt"], capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    exe = tmp_path / "arena_reuse_check"
+    r = subprocess.run([str(CLANG), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
+                        str(ROOT / "tests/cpp/arena_reuse_check.cpp"), "-o", str(exe), str(SIMT / "build" / "liborbx_emul_asan_static.so"),
+                        f"-Wl,-rpath,{SIMT / 'build'}"], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=1500, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    assert r.returncode == 0 and "arena reuse ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
