@@ -297,7 +297,7 @@ struct orbx_frame {
     uint16_t *gstart = nullptr, *gorder = nullptr;
     uint8_t *stage = nullptr;         // pinned (device-visible) staging of orbx_frame_load_host: the rows at the device layout's offsets
     size_t stage_bytes = 0;
-    int32_t *h_count = nullptr;       // pinned: orbx_frame_count's download
+    int32_t *h_count = nullptr;       // pinned: where the device count(s) land (fetch_count, frame_count) until adopt_count() reads them
     hipEvent_t ev_src = nullptr;      // load_batch: the extractor's stream up to the batch
     hipEvent_t ev_done = nullptr;     // load_batch: the copy has run (the extractor's next batch waits for it); load_host: the staging is free again
     bool stage_busy = false;
@@ -305,7 +305,7 @@ struct orbx_frame {
     int n = 0, nlevels = 0;
     std::vector<float> scale_h;       // mvScaleFactors on the host (the projection matchers' host-side window setup)
     float bounds[4] = {0, 0, 0, 0};
-    std::vector<int32_t> h_match;     // [cap]: results of a call made while N was still on the device
+    std::vector<int32_t> h_match;     // result rows of a call made while N was still on the device (fetch_rows / take_rows)
     size_t off_kps = 0, off_desc = 0, off_ur = 0, off_count = 0, off_scale = 0, off_gstart = 0, off_gorder = 0;
     // Frame::ComputeBoW (orbx_frame_compute_bow): word / node id per feature, the FeatureVector (ascending node ids, CSR, feature indices) with its
     // node count on the device, and mvKeysUn[i].angle.  Valid until the next load.
@@ -314,7 +314,6 @@ struct orbx_frame {
     float *angle = nullptr;
     bool bow_valid = false;
     uint64_t load_seq = 0;            // loads so far: orbx_keyframe_from_frame remembers (handle, load_seq) for orbx_keyframe_bow_from_frame
-    std::vector<int32_t> h_bow;       // [2 cap]: word / node ids downloaded while N was still on the device
     const orbx_vocabulary *bow_voc = nullptr;
     int bow_levelsup = 0;
     // A fisheye-stereo frame (Frame::Nleft != -1, orbx_frame_load_host_fisheye / orbx_frame_load_stereo_fisheye_batch): features [0, N_left) are the
@@ -326,6 +325,49 @@ struct orbx_frame {
     int32_t *l2r = nullptr, *r2l = nullptr;
     uint16_t *gstart_r = nullptr, *gorder_r = nullptr;
     size_t off_l2r = 0, off_r2l = 0;
+
+    // N as the host sees it.  A batch load leaves the count(s) on the device (n_known == false) until a call needs them: host_*() = the count, or -1
+    // for "not yet"; rows_*() = the count, or meanwhile the capacity that a call's per-feature buffers are sized by.
+    int host_n() const { return n_known ? n : -1; }
+    int host_left() const { return n_known ? n_left : -1; }
+    int host_right() const { return n_known ? n_right : -1; }
+    int rows_n() const { return n_known ? n : cap; }
+    int rows_left() const { return n_known ? n_left : roff; }
+    int rows_right() const { return n_known ? n_right : cap - roff; }
+    // A call that meets the handle with N pending brings N home with its results: fetch_count() among its downloads, adopt_count() behind its
+    // synchronisation.  Apart from the loaders, adopt() is the one place that learns N.
+    int fetch_count() { return owner->d2h(h_count, count, fisheye ? 8 : 4); }
+    void adopt(int c0, int c1 = 0) {
+        if (fisheye) { n_left = std::min(std::max(c0, 0), roff); n_right = std::min(std::max(c1, 0), cap - roff); }
+        n = fisheye ? n_left + n_right : std::min(std::max(c0, 0), cap);
+        n_known = true;
+    }
+    void adopt_count() { adopt(h_count[0], fisheye ? h_count[1] : 0); }
+    // Result rows on their way to the caller.  A block: row k = nc int32 at src + k * nc on the device, bound for dst + k * stride (dst NULL: not
+    // wanted).  N known (nc = the entries the caller gets): each row goes straight to the caller.  N pending (nc = the capacity the rows are
+    // sized by): each block comes down whole into h_match, one block behind the other, and take_rows() hands the first `count` entries of every
+    // row out once N is adopted.  A call names all its blocks at once: h_match must not move while a download into it is on its way.
+    struct Rows { const int32_t *src; int k_rows, nc; int32_t *dst; size_t stride; };
+    int fetch_rows(const Rows *blocks, int n_blocks = 1) {
+        size_t total = 0, at = 0;
+        for (int b = 0; b < n_blocks; b++) total += (size_t)blocks[b].k_rows * blocks[b].nc;
+        if (!n_known && h_match.size() < total) h_match.resize(total);
+        for (int b = 0; b < n_blocks; b++) {
+            const Rows &r = blocks[b];
+            if (!n_known) ORBX_TRY(owner->d2h(h_match.data() + at, r.src, 4 * (size_t)r.k_rows * r.nc));
+            for (int k = 0; n_known && r.dst && k < r.k_rows; k++) ORBX_TRY(owner->d2h(r.dst + k * r.stride, r.src + (size_t)k * r.nc, 4 * (size_t)r.nc));
+            at += (size_t)r.k_rows * r.nc;
+        }
+        return ORBX_OK;
+    }
+    void take_rows(const Rows *blocks, int n_blocks, int count) const {
+        size_t at = 0;
+        for (int b = 0; b < n_blocks; b++) {
+            const Rows &r = blocks[b];
+            for (int k = 0; r.dst && k < r.k_rows; k++) memcpy(r.dst + k * r.stride, h_match.data() + at + (size_t)k * r.nc, 4 * (size_t)count);
+            at += (size_t)r.k_rows * r.nc;
+        }
+    }
 };
 
 namespace {
@@ -346,9 +388,7 @@ int frame_count(orbx_frame *f, int *n) {
         ORBX_HIP(hipMemcpyAsync(f->h_count, f->count, f->fisheye ? 8 : 4, hipMemcpyDeviceToHost, m->stream));
         ORBX_HIP(hipStreamSynchronize(m->stream));
         m->dirty = false;
-        if (f->fisheye) { f->n_left = f->h_count[0]; f->n_right = f->h_count[1]; f->n = f->n_left + f->n_right; }
-        else f->n = *f->h_count;
-        f->n_known = true;
+        f->adopt_count();
     }
     *n = f->n;
     return ORBX_OK;
@@ -390,7 +430,7 @@ int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr,
     }
     for (int i = 0; i < n_out; i++) a.match_out[i] = -1;
     if (n == 0 || nq == 0) return 0;
-    const int nc = n >= 0 ? n : left_only ? fh->roff : fh->cap;   // features the device buffers are sized for
+    const int nc = !fh ? n : left_only ? fh->rows_left() : fh->rows_n();   // features the device buffers are sized for
     if (nc > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;  // before anything is enqueued: the resolve pass keeps 10 B per feature in LDS
     ORBX_HIP(hipSetDevice(m->device));
     WindowProblem P;
@@ -448,25 +488,16 @@ int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr,
     }
     { const int rr = brute ? launch_resolve<true>(1, m->exec(), dP, dR, g, nc, nq, 4) : launch_resolve<false>(1, m->exec(), dP, dR, g, nc, nq, 4); if (rr != ORBX_OK) return rr; }
     int32_t nm = 0;
-    if (n >= 0) {
-        ORBX_TRY(m->d2h(a.match_out, R.match, 4 * (size_t)n));
-    } else {   // N comes back with the results (one small copy of the handle's count)
-        fh->h_match.resize((size_t)fh->cap);
-        ORBX_TRY(m->d2h(fh->h_match.data(), R.match, 4 * (size_t)nc));
-        if (left_only) ORBX_TRY(m->d2h(fh->h_count, fh->count, 8));
-        else ORBX_TRY(m->d2h(&fh->n, fh->count, 4));
-    }
+    const orbx_frame::Rows rows = {R.match, 1, nc, a.match_out, 0};
+    if (!fh) ORBX_TRY(m->d2h(a.match_out, R.match, 4 * (size_t)n));
+    else ORBX_TRY(fh->fetch_rows(&rows));
+    if (n < 0) ORBX_TRY(fh->fetch_count());   // N comes back with the results (one small copy of the handle's count)
     ORBX_TRY(m->d2h(&nm, R.nmatches, 4));
     ORBX_TRY(m->sync_and_deliver());
-    if (n < 0 && left_only) {
-        fh->n_left = std::min(std::max(fh->h_count[0], 0), fh->roff);
-        fh->n_right = std::min(std::max(fh->h_count[1], 0), fh->cap - fh->roff);
-        fh->n = fh->n_left + fh->n_right; fh->n_known = true;
-        memcpy(a.match_out, fh->h_match.data(), 4 * (size_t)fh->n_left);
-        for (int i = fh->n_left; i < fh->n; i++) a.match_out[i] = -1;
-    } else if (n < 0) {
-        fh->n_known = true;
-        memcpy(a.match_out, fh->h_match.data(), 4 * (size_t)std::max(fh->n, 0));
+    if (n < 0) {
+        fh->adopt_count();
+        fh->take_rows(&rows, 1, left_only ? fh->n_left : fh->n);
+        if (left_only) for (int i = fh->n_left; i < fh->n; i++) a.match_out[i] = -1;
     }
     return nm;
 }
@@ -665,7 +696,7 @@ int orbx_frame_count(orbx_frame *f, int *n) {
 static orbx_frame_desc frame_desc_of(const orbx_frame *f) {
     orbx_frame_desc d;
     memset(&d, 0, sizeof(d));
-    d.n = f->n_known ? f->n : f->cap;
+    d.n = f->rows_n();
     d.min_x = f->bounds[0]; d.max_x = f->bounds[1]; d.min_y = f->bounds[2]; d.max_y = f->bounds[3];
     d.scale_factors = f->scale_h.data(); d.nlevels = f->nlevels;
     d.u_right = f->has_ur ? f->u_right : nullptr;
@@ -734,7 +765,7 @@ int run_projection_twin(orbx_matcher *m, const TwinArgs &a, orbx_frame *fh = nul
     }
     for (int i = 0; i < N; i++) a.match_out[i] = -1;
     if (N == 0 || nq == 0) return 0;
-    const int nc = N >= 0 ? N : fh->cap;   // features the device buffers are sized for
+    const int nc = fh ? fh->rows_n() : N;   // features the device buffers are sized for
     if (nc > 60000) return ORBX_E_TOO_LARGE;   // 16-bit feature indices in the candidate keys; occupancy bytes in LDS
     ORBX_HIP(hipSetDevice(m->device));
     WindowProblem P[2];
@@ -791,19 +822,13 @@ int run_projection_twin(orbx_matcher *m, const TwinArgs &a, orbx_frame *fh = nul
     if (!fh) ORBX_LAUNCH_GRID_BUILD( dim3(2), dim3(64), 0, m->exec(), dP, g);
     ORBX_TRY(launch_twin(m, dP, T, g, nc, nq));
     int32_t nm = 0;
-    if (N >= 0) {
-        ORBX_TRY(m->d2h(a.match_out, T.match, 4 * (size_t)N));
-    } else {   // the counts come back with the results
-        fh->h_match.resize((size_t)fh->cap);
-        ORBX_TRY(m->d2h(fh->h_match.data(), T.match, 4 * (size_t)nc));
-        ORBX_TRY(m->d2h(fh->h_count, fh->count, 8));
-    }
+    const orbx_frame::Rows rows = {T.match, 1, nc, a.match_out, 0};
+    if (!fh) ORBX_TRY(m->d2h(a.match_out, T.match, 4 * (size_t)N));
+    else ORBX_TRY(fh->fetch_rows(&rows));
+    if (N < 0) ORBX_TRY(fh->fetch_count());   // the counts come back with the results
     ORBX_TRY(m->d2h(&nm, T.nmatches, 4));
     ORBX_TRY(m->sync_and_deliver());
-    if (N < 0) {
-        fh->n_left = fh->h_count[0]; fh->n_right = fh->h_count[1]; fh->n = fh->n_left + fh->n_right; fh->n_known = true;
-        memcpy(a.match_out, fh->h_match.data(), 4 * (size_t)std::max(fh->n, 0));
-    }
+    if (N < 0) { fh->adopt_count(); fh->take_rows(&rows, 1, fh->n); }
     return nm;
 }
 
@@ -2095,48 +2120,85 @@ extern "C" int orbx_bow_transform(orbx_matcher *m, const orbx_vocabulary *v, con
     return ORBX_OK;
 }
 
-// Frame::ComputeBoW (Frame.cc:738-745) on a resident frame: k_frame_bow_transform over the handle's descriptors, then k_frame_featvec builds the
-// FeatureVector in the handle.  Nothing of the frame is uploaded; without downloads nothing waits (the launches are ordered on the owner's stream).
-extern "C" int orbx_frame_compute_bow(orbx_matcher *m, orbx_frame *f, const orbx_vocabulary *v, int levelsup, int32_t *word_id, int32_t *node_id) {
-    if (!m || !f || !v || f->owner != m || f->fisheye || v->device != m->device) return ORBX_E_BAD_ARG;   // (BoW on a fisheye frame: not yet)
-    ORBX_HIP(hipSetDevice(m->device));
-    const bool down = word_id || node_id;
-    const int n_host = f->n_known ? f->n : -1;
-    const int nc = f->n_known ? f->n : f->cap;   // features the kernels may see
+namespace {
+
+// What ComputeBoW reads and writes: the rows of a frame handle or of a key frame, and the seven arrays that take the result.
+struct BowTarget {
+    const uint8_t *desc; const orbx_keypoint *kps; const int32_t *count;
+    int n_host, cap;                  // N, or -1 while it is on the device only; the rows the arrays hold
+    int32_t *word, *node; float *angle; uint32_t *fv_node; int32_t *fv_ptr, *fv_index, *fv_meta;
+    bool fisheye;                     // a fisheye-stereo handle: the row-space kernel pair; the right camera's rows from roff on, N per camera (or -1)
+    int roff, n_host_side[2];
+    int rows() const { return n_host >= 0 ? n_host : cap; }   // features the kernels may see
+};
+inline BowTarget bow_target(const orbx_frame *f) {
+    return BowTarget{f->desc, f->kps, f->count, f->host_n(), f->cap, f->bow_word, f->bow_node, f->angle, f->fv_node, f->fv_ptr, f->fv_index, f->fv_meta,
+                     f->fisheye, f->roff, {f->host_left(), f->host_right()}};
+}
+
+// The driver of every ComputeBoW: the transform of the target's descriptors (k_frame_bow_transform[_fisheye]) and the FeatureVector
+// (k_frame_featvec[_fisheye]) on m->stream.  Returns the first HIP error; nothing is synchronised.
+hipError_t launch_compute_bow(orbx_matcher *m, const orbx_vocabulary *v, int levelsup, const BowTarget &t) {
+    const int nc = t.rows();
     int sort_cap = 1;
     while (sort_cap < nc) sort_cap <<= 1;
     const size_t lds = 8 * (size_t)sort_cap;
-    ORBX_TRY(m->reserve_staging(8 * (size_t)nc));   // the ids come down through it
-    f->bow_valid = false;
-    if (nc > 0)
-        hipLaunchKernelGGL(k_frame_bow_transform, dim3((nc + 15) / 16), dim3(256), 0, m->stream, v->child_ptr, v->child_idx, v->node_desc, v->word_id,
-                           v->L, levelsup, f->desc, f->count, n_host, f->cap, f->bow_word, f->bow_node);
+    if (lds > 64 * 1024) {
+        const void *featvec = t.fisheye ? (const void *)k_frame_featvec_fisheye : (const void *)k_frame_featvec;
+        const hipError_t e = hipFuncSetAttribute(featvec, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
     FrameBow B;
     memset(&B, 0, sizeof(B));
-    B.count = f->count; B.n_host = n_host; B.cap = f->cap; B.kps = f->kps; B.word = f->bow_word; B.node = f->bow_node;
+    B.count = t.count; B.n_host = t.n_host; B.cap = t.cap; B.kps = t.kps; B.word = t.word; B.node = t.node;
     B.word_pos = v->word_pos; B.n_words = v->n_words;
-    B.angle = f->angle; B.fv_node = f->fv_node; B.fv_ptr = f->fv_ptr; B.fv_index = f->fv_index; B.fv_meta = f->fv_meta;
-    if (lds > 64 * 1024) ORBX_HIP(hipFuncSetAttribute((const void *)k_frame_featvec, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_frame_featvec, dim3(1), dim3(1024), lds, m->stream, B, sort_cap);
-    ORBX_HIP(hipGetLastError());
-    f->bow_valid = true; f->bow_voc = v; f->bow_levelsup = levelsup;
-    if (!down || nc == 0) return ORBX_OK;
-    if (n_host >= 0) {
-        if (word_id) ORBX_TRY(m->d2h(word_id, f->bow_word, 4 * (size_t)nc));
-        if (node_id) ORBX_TRY(m->d2h(node_id, f->bow_node, 4 * (size_t)nc));
-        ORBX_TRY(m->sync_and_deliver());
-        return ORBX_OK;
+    B.angle = t.angle; B.fv_node = t.fv_node; B.fv_ptr = t.fv_ptr; B.fv_index = t.fv_index; B.fv_meta = t.fv_meta;
+    if (t.fisheye) {
+        const int nl = t.n_host_side[0], nr = t.n_host_side[1], cap_l = t.roff, cap_r = t.cap - t.roff;   // the rows each camera may occupy
+        const int side = t.n_host >= 0 ? std::max(nl, nr) : std::max(cap_l, cap_r);
+        if (side > 0)
+            hipLaunchKernelGGL(k_frame_bow_transform_fisheye, dim3((unsigned)((side + 15) / 16), 2), dim3(256), 0, m->stream, v->child_ptr, v->child_idx,
+                               v->node_desc, v->word_id, v->L, levelsup, t.desc, t.count, nl, nr, cap_l, cap_r, t.roff, t.word, t.node);
+        hipLaunchKernelGGL(k_frame_featvec_fisheye, dim3(1), dim3(1024), lds, m->stream, B, sort_cap, nl, nr, t.roff);
+    } else {
+        if (nc > 0)
+            hipLaunchKernelGGL(k_frame_bow_transform, dim3((nc + 15) / 16), dim3(256), 0, m->stream, v->child_ptr, v->child_idx, v->node_desc, v->word_id,
+                               v->L, levelsup, t.desc, t.count, t.n_host, t.cap, t.word, t.node);
+        hipLaunchKernelGGL(k_frame_featvec, dim3(1), dim3(1024), lds, m->stream, B, sort_cap);
     }
-    f->h_bow.resize(2 * (size_t)f->cap);   // N comes back with the ids
-    ORBX_TRY(m->d2h(f->h_bow.data(), f->bow_word, 4 * (size_t)nc));
-    ORBX_TRY(m->d2h(f->h_bow.data() + f->cap, f->bow_node, 4 * (size_t)nc));
-    ORBX_TRY(m->d2h(&f->n, f->count, 4));
-    ORBX_TRY(m->sync_and_deliver());
-    f->n = std::min(std::max(f->n, 0), f->cap);
-    f->n_known = true;
-    if (word_id) memcpy(word_id, f->h_bow.data(), 4 * (size_t)f->n);
-    if (node_id) memcpy(node_id, f->h_bow.data() + f->cap, 4 * (size_t)f->n);
+    return hipGetLastError();
+}
+
+// ComputeBoW of a frame handle (either kind), and the tail of both forms: the ids of the features the kernels saw come down from src_word /
+// src_node, with N while it is pending.
+int frame_compute_bow(orbx_matcher *m, orbx_frame *f, const orbx_vocabulary *v, int levelsup) {
+    f->bow_valid = false;
+    ORBX_HIP(launch_compute_bow(m, v, levelsup, bow_target(f)));
+    f->bow_valid = true; f->bow_voc = v; f->bow_levelsup = levelsup;
     return ORBX_OK;
+}
+int frame_bow_ids_down(orbx_frame *f, const int32_t *src_word, const int32_t *src_node, int32_t *word_id, int32_t *node_id) {
+    const bool pending = !f->n_known;
+    const orbx_frame::Rows ids[2] = {{src_word, 1, f->rows_n(), word_id, 0}, {src_node, 1, f->rows_n(), node_id, 0}};
+    ORBX_TRY(f->fetch_rows(ids, 2));
+    if (pending) ORBX_TRY(f->fetch_count());   // N comes back with the ids
+    ORBX_TRY(f->owner->sync_and_deliver());
+    if (pending) { f->adopt_count(); f->take_rows(ids, 2, f->n); }
+    return ORBX_OK;
+}
+
+}  // namespace
+
+// Frame::ComputeBoW (Frame.cc:738-745) on a resident frame: k_frame_bow_transform over the handle's descriptors, then k_frame_featvec builds the
+// FeatureVector in the handle.  Nothing of the frame is uploaded; without downloads nothing waits (the launches are ordered on the owner's stream).
+extern "C" int orbx_frame_compute_bow(orbx_matcher *m, orbx_frame *f, const orbx_vocabulary *v, int levelsup, int32_t *word_id, int32_t *node_id) {
+    if (!m || !f || !v || f->owner != m || f->fisheye || v->device != m->device) return ORBX_E_BAD_ARG;   // (a fisheye frame: the _fisheye form)
+    ORBX_HIP(hipSetDevice(m->device));
+    const int nc = f->rows_n();   // features the kernels may see
+    ORBX_TRY(m->reserve_staging(8 * (size_t)nc));   // the ids come down through it
+    ORBX_TRY(frame_compute_bow(m, f, v, levelsup));
+    if ((!word_id && !node_id) || nc == 0) return ORBX_OK;
+    return frame_bow_ids_down(f, f->bow_word, f->bow_node, word_id, node_id);
 }
 
 // Frame::ComputeBoW of a resident fisheye-stereo frame (Frame.cc:738-745 over all N = N_left + N_right rows of mDescriptors): the handle's rows
@@ -2147,54 +2209,17 @@ extern "C" int orbx_frame_compute_bow_fisheye(orbx_matcher *m, orbx_frame *f, co
                                               int32_t *node_id) {
     if (!m || !f || !v || f->owner != m || !f->fisheye || v->device != m->device) return ORBX_E_BAD_ARG;
     ORBX_HIP(hipSetDevice(m->device));
-    const bool down = word_id || node_id;
-    const int nl_host = f->n_known ? f->n_left : -1, nr_host = f->n_known ? f->n_right : -1;
-    const int cap_l = f->roff, cap_r = f->cap - f->roff;   // the rows each camera may occupy
-    const int nc = f->n_known ? f->n : f->cap;             // features the kernels may see
-    const int side = f->n_known ? std::max(nl_host, nr_host) : std::max(cap_l, cap_r);
-    int sort_cap = 1;
-    while (sort_cap < nc) sort_cap <<= 1;
-    const size_t lds = 8 * (size_t)sort_cap;
+    const int nc = f->rows_n();   // features the kernels may see
     int32_t *dids;   // word ids, then node ids, in features [0, N)
     ORBX_TRY(m->carve([&](Carve &A) { dids = A.take<int32_t>(2 * (size_t)nc); }));
-    f->bow_valid = false;
-    if (side > 0)
-        hipLaunchKernelGGL(k_frame_bow_transform_fisheye, dim3((unsigned)((side + 15) / 16), 2), dim3(256), 0, m->stream, v->child_ptr, v->child_idx,
-                           v->node_desc, v->word_id, v->L, levelsup, f->desc, f->count, nl_host, nr_host, cap_l, cap_r, f->roff, f->bow_word,
-                           f->bow_node);
-    FrameBow B;
-    memset(&B, 0, sizeof(B));
-    B.count = f->count; B.n_host = f->n_known ? f->n : -1; B.cap = f->cap; B.kps = f->kps; B.word = f->bow_word; B.node = f->bow_node;
-    B.word_pos = v->word_pos; B.n_words = v->n_words;
-    B.angle = f->angle; B.fv_node = f->fv_node; B.fv_ptr = f->fv_ptr; B.fv_index = f->fv_index; B.fv_meta = f->fv_meta;
-    if (lds > 64 * 1024)
-        ORBX_HIP(hipFuncSetAttribute((const void *)k_frame_featvec_fisheye, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_frame_featvec_fisheye, dim3(1), dim3(1024), lds, m->stream, B, sort_cap, nl_host, nr_host, f->roff);
-    ORBX_HIP(hipGetLastError());
-    f->bow_valid = true; f->bow_voc = v; f->bow_levelsup = levelsup;
-    if (!down || nc == 0) return ORBX_OK;
+    ORBX_TRY(frame_compute_bow(m, f, v, levelsup));
+    if ((!word_id && !node_id) || nc == 0) return ORBX_OK;
     const int32_t *src[2] = {f->bow_word, f->bow_node};
     for (int k = 0; k < 2; k++)
         hipLaunchKernelGGL(k_frame_rows_to_features, dim3((unsigned)((nc + 255) / 256), 1), dim3(256), 0, m->stream, src[k], 0, dids + (size_t)k * nc, nc,
-                           f->count, nl_host, nr_host, f->cap, f->roff);
+                           f->count, f->host_left(), f->host_right(), f->cap, f->roff);
     ORBX_HIP(hipGetLastError());
-    if (f->n_known) {
-        if (word_id) ORBX_TRY(m->d2h(word_id, dids, 4 * (size_t)nc));
-        if (node_id) ORBX_TRY(m->d2h(node_id, dids + nc, 4 * (size_t)nc));
-        ORBX_TRY(m->sync_and_deliver());
-        return ORBX_OK;
-    }
-    f->h_bow.resize(2 * (size_t)f->cap);   // the counts come back with the ids
-    ORBX_TRY(m->d2h(f->h_bow.data(), dids, 8 * (size_t)nc));
-    ORBX_TRY(m->d2h(f->h_count, f->count, 8));
-    ORBX_TRY(m->sync_and_deliver());
-    f->n_left = std::min(std::max(f->h_count[0], 0), f->roff);
-    f->n_right = std::min(std::max(f->h_count[1], 0), f->cap - f->roff);
-    f->n = f->n_left + f->n_right;
-    f->n_known = true;
-    if (word_id) memcpy(word_id, f->h_bow.data(), 4 * (size_t)f->n);
-    if (node_id) memcpy(node_id, f->h_bow.data() + f->cap, 4 * (size_t)f->n);
-    return ORBX_OK;
+    return frame_bow_ids_down(f, dids, dids + nc, word_id, node_id);
 }
 
 // ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) (ORBmatcher.cc:223-425) of the resident frame against n_kf key frames at once
@@ -2226,11 +2251,11 @@ static int frame_search_by_bow_impl(orbx_matcher *m, orbx_frame *f, int n_kf, co
         tot_nodes += (size_t)F.n_nodes;
         max_nodes = std::max(max_nodes, F.n_nodes);
     }
-    int n = f->n_known ? f->n : -1;
+    int n = f->host_n();
     if (n < 0 && match_stride < f->cap) { const int rc = frame_count(f, &n); if (rc != ORBX_OK) return rc; }   // the rows must fit the stride
     if (n >= 0 && match_stride < n) return ORBX_E_BAD_ARG;
-    const int nc = n >= 0 ? n : f->cap;   // features the device rows are sized for
-    const int nrows = !fisheye ? nc : n >= 0 ? f->roff + f->n_right : f->cap;   // the replay's rows (fisheye: left, gap, right)
+    const int nc = f->rows_n();   // features the device rows are sized for
+    const int nrows = !fisheye ? nc : f->roff + f->rows_right();   // the replay's rows (fisheye: left, gap, right)
     for (int k = 0; k < n_kf; k++) {
         nmatches[k] = 0;
         for (int i = 0; i < std::max(n, 0); i++) match[(size_t)k * match_stride + i] = -1;
@@ -2313,28 +2338,14 @@ static int frame_search_by_bow_impl(orbx_matcher *m, orbx_frame *f, int n_kf, co
     hipLaunchKernelGGL(k_replay_bow_finish_batch, dim3((unsigned)n_kf), dim3(64), 0, m->exec(), (const BowProblem *)dP);
     if (fisheye)
         hipLaunchKernelGGL(k_frame_rows_to_features, dim3((unsigned)((nc + 255) / 256), (unsigned)n_kf), dim3(256), 0, m->exec(), dmatch, nrows, dout, nc,
-                           f->count, n >= 0 ? f->n_left : -1, n >= 0 ? f->n_right : -1, f->cap, f->roff);
+                           f->count, f->host_left(), f->host_right(), f->cap, f->roff);
     ORBX_HIP(hipGetLastError());
-    if (n >= 0) {
-        for (int k = 0; k < n_kf; k++) ORBX_TRY(m->d2h(match + (size_t)k * match_stride, dout + (size_t)k * nc, 4 * (size_t)n));
-    } else {   // N comes back with the results
-        f->h_match.resize((size_t)n_kf * nc);
-        ORBX_TRY(m->d2h(f->h_match.data(), dout, 4 * (size_t)n_kf * nc));
-        if (fisheye) ORBX_TRY(m->d2h(f->h_count, f->count, 8));
-        else ORBX_TRY(m->d2h(&f->n, f->count, 4));
-    }
+    const orbx_frame::Rows rows = {dout, n_kf, nc, match, (size_t)match_stride};
+    ORBX_TRY(f->fetch_rows(&rows));
+    if (n < 0) ORBX_TRY(f->fetch_count());   // N comes back with the results
     ORBX_TRY(m->d2h(nmatches, dnm, 4 * (size_t)n_kf));
     ORBX_TRY(m->sync_and_deliver());
-    if (n < 0) {
-        if (fisheye) {
-            f->n_left = std::min(std::max(f->h_count[0], 0), f->roff);
-            f->n_right = std::min(std::max(f->h_count[1], 0), f->cap - f->roff);
-            f->n = f->n_left + f->n_right;
-        }
-        f->n = std::min(std::max(f->n, 0), f->cap);
-        f->n_known = true;
-        for (int k = 0; k < n_kf; k++) memcpy(match + (size_t)k * match_stride, f->h_match.data() + (size_t)k * nc, 4 * (size_t)f->n);
-    }
+    if (n < 0) { f->adopt_count(); f->take_rows(&rows, 1, f->n); }
     return ORBX_OK;
 }
 
@@ -2583,7 +2594,7 @@ int orbx_keyframe_from_frame(orbx_matcher *m, orbx_frame *f, const float *inv_le
     if (out) *out = nullptr;
     if (!m || !out || !f || f->owner != m || !f->loaded || f->fisheye) return ORBX_E_BAD_ARG;
     ORBX_HIP(hipSetDevice(m->device));
-    const int cap = f->n_known ? f->n : f->cap;   // sized by N where the host knows it
+    const int cap = f->rows_n();   // sized by N where the host knows it
     orbx_keyframe *kf = nullptr;
     int r = keyframe_alloc(m->device, cap, f->has_ur, inv_level_sigma2 != nullptr, f->nlevels, f->bounds, &kf);
     if (r != ORBX_OK) return r;
@@ -2600,7 +2611,7 @@ int orbx_keyframe_from_frame(orbx_matcher *m, orbx_frame *f, const float *inv_le
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipEventRecord(kf->ready, m->stream);
     if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
-    kf->n.store(f->n_known ? f->n : -1);
+    kf->n.store(f->host_n());
     kf->src_frame = f; kf->src_seq = f->load_seq;
     *out = kf;
     return ORBX_OK;
@@ -2810,7 +2821,7 @@ inline BowSide bow_side(const orbx_keyframe *kf) {
 inline BowSide bow_side(const orbx_frame *f) {
     BowSide S;
     S.desc = f->desc; S.angle = f->angle; S.fv_node = f->fv_node; S.fv_ptr = f->fv_ptr; S.fv_index = f->fv_index; S.fv_meta = f->fv_meta;
-    S.count = f->count; S.n = f->n_known ? f->n : -1; S.cap = f->cap;
+    S.count = f->count; S.n = f->host_n(); S.cap = f->cap;
     S.bound = std::min(S.rows(), f->bow_voc->node_bound(f->bow_levelsup));
     return S;
 }
@@ -2962,24 +2973,12 @@ int orbx_keyframe_compute_bow(orbx_matcher *m, orbx_keyframe *kf, const orbx_voc
     if (!b) {
         ORBX_TRY(keyframe_bow_alloc(kf->cap, &b));
         b->voc = v; b->levelsup = levelsup;
-        int sort_cap = 1;
-        while (sort_cap < nc) sort_cap <<= 1;
-        const size_t lds = 8 * (size_t)sort_cap;
         hipError_t e = hipSuccess;
         if (!kf->done.load(std::memory_order_acquire)) e = hipStreamWaitEvent(m->stream, kf->ready, 0);
-        if (e == hipSuccess && lds > 64 * 1024) e = hipFuncSetAttribute((const void *)k_frame_featvec, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e == hipSuccess) {
             m->dirty = true;
-            if (nc > 0)
-                hipLaunchKernelGGL(k_frame_bow_transform, dim3((nc + 15) / 16), dim3(256), 0, m->stream, v->child_ptr, v->child_idx, v->node_desc, v->word_id,
-                                   v->L, levelsup, kf->desc, kf->count, n_host, kf->cap, b->word, b->node);
-            FrameBow B;
-            memset(&B, 0, sizeof(B));
-            B.count = kf->count; B.n_host = n_host; B.cap = kf->cap; B.kps = kf->kps; B.word = b->word; B.node = b->node;
-            B.word_pos = v->word_pos; B.n_words = v->n_words;
-            B.angle = b->angle; B.fv_node = b->fv_node; B.fv_ptr = b->fv_ptr; B.fv_index = b->fv_index; B.fv_meta = b->fv_meta;
-            hipLaunchKernelGGL(k_frame_featvec, dim3(1), dim3(1024), lds, m->stream, B, sort_cap);
-            e = hipGetLastError();
+            e = launch_compute_bow(m, v, levelsup, BowTarget{kf->desc, kf->kps, kf->count, n_host, kf->cap, b->word, b->node, b->angle, b->fv_node, b->fv_ptr,
+                                                             b->fv_index, b->fv_meta, false, 0, {-1, -1}});
         }
         if (e == hipSuccess) e = hipEventRecord(b->ready, m->stream);
         if (e != hipSuccess) { set_error(hipGetErrorString(e)); (void)hipStreamSynchronize(m->stream); m->dirty = false; keyframe_bow_free(b); return ORBX_E_HIP; }
@@ -3017,7 +3016,7 @@ int orbx_keyframe_bow_from_frame(orbx_matcher *m, orbx_keyframe *kf, orbx_frame 
     if (kf->bow.load(std::memory_order_acquire)) return ORBX_E_BAD_ARG;   // set once
     if (f->load_seq != kf->src_seq) return ORBX_E_STALE;                  // the handle holds another frame by now
     if (!f->bow_valid) return ORBX_E_BAD_ARG;
-    if ((f->n_known ? f->n : f->cap) > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;
+    if (f->rows_n() > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;
     ORBX_HIP(hipSetDevice(m->device));
     KeyFrameBow *b = nullptr;
     int r = keyframe_bow_alloc(kf->cap, &b);
@@ -3025,7 +3024,7 @@ int orbx_keyframe_bow_from_frame(orbx_matcher *m, orbx_keyframe *kf, orbx_frame 
     b->voc = f->bow_voc; b->levelsup = f->bow_levelsup;
     KeyFrameBowCopy Cp;
     memset(&Cp, 0, sizeof(Cp));
-    Cp.src_count = f->count; Cp.n_host = f->n_known ? f->n : -1; Cp.cap = kf->cap;
+    Cp.src_count = f->count; Cp.n_host = f->host_n(); Cp.cap = kf->cap;
     Cp.src_word = f->bow_word; Cp.src_node = f->bow_node; Cp.src_ptr = f->fv_ptr; Cp.src_index = f->fv_index; Cp.src_meta = f->fv_meta;
     Cp.src_fv_node = f->fv_node; Cp.src_angle = f->angle;
     Cp.word = b->word; Cp.node = b->node; Cp.ptr = b->fv_ptr; Cp.index = b->fv_index; Cp.meta = b->fv_meta; Cp.fv_node = b->fv_node; Cp.angle = b->angle;
@@ -3049,7 +3048,7 @@ int orbx_frame_search_by_bow_resident(orbx_matcher *m, orbx_frame *f, int n_kf, 
     int levelsup = f->bow_levelsup;
     for (int k = 0; k < n_kf; k++)   // every key frame is checked before anything is enqueued
         if (!keyframe_bow_ok(m, kfs[k], &voc, &levelsup)) return ORBX_E_BAD_ARG;
-    int n = f->n_known ? f->n : -1;
+    int n = f->host_n();
     if (n < 0 && match_stride < f->cap) { const int rc = frame_count(f, &n); if (rc != ORBX_OK) return rc; }   // the rows must fit the stride
     if (n >= 0 && match_stride < n) return ORBX_E_BAD_ARG;
     for (int k = 0; k < n_kf; k++) {
@@ -3070,7 +3069,7 @@ int orbx_frame_search_by_bow_resident(orbx_matcher *m, orbx_frame *f, int n_kf, 
         keyframe_bow_release(kfs[k]);
         if (kfs[k]->n.load() < 0) kfs[k]->n.store(std::min(std::max(counts[2 * (size_t)k], 0), kfs[k]->cap));
     }
-    if (!f->n_known) { f->n = std::min(std::max(counts[1], 0), f->cap); f->n_known = true; }
+    if (!f->n_known) f->adopt(counts[1]);
     return ORBX_OK;
 }
 
@@ -3168,7 +3167,7 @@ extern "C" int orbx_frame_search_local_points(orbx_matcher *m, orbx_frame *f, co
     if (f->n_known || frame_occupied || n_mp == 0) { const int rc = frame_count(f, &n); if (rc != ORBX_OK) return rc; }   // the mask holds N entries
     for (int i = 0; i < n; i++) frame_match[i] = -1;
     if (n_mp == 0) return 0;
-    const int nc = n >= 0 ? n : f->cap;
+    const int nc = f->rows_n();
     if (nc > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;
     ORBX_HIP(hipSetDevice(m->device));
     const size_t q = (size_t)n_mp;
@@ -3230,21 +3229,14 @@ extern "C" int orbx_frame_search_local_points(orbx_matcher *m, orbx_frame *f, co
     ORBX_HIP(hipGetLastError());
     int32_t nm = 0;
     ORBX_TRY(m->d2h(in_view, div_out, q));
+    const orbx_frame::Rows rows = {R.match, 1, nc, frame_match, 0};
     if (match) {
-        if (n >= 0) {
-            ORBX_TRY(m->d2h(frame_match, R.match, 4 * (size_t)n));
-        } else {   // N comes back with the results
-            f->h_match.resize((size_t)f->cap);
-            ORBX_TRY(m->d2h(f->h_match.data(), R.match, 4 * (size_t)nc));
-            ORBX_TRY(m->d2h(&f->n, f->count, 4));
-        }
+        ORBX_TRY(f->fetch_rows(&rows));
+        if (n < 0) ORBX_TRY(f->fetch_count());   // N comes back with the results
         ORBX_TRY(m->d2h(&nm, R.nmatches, 4));
     }
     ORBX_TRY(m->sync_and_deliver());
-    if (n < 0) {
-        f->n_known = true;
-        memcpy(frame_match, f->h_match.data(), 4 * (size_t)std::max(f->n, 0));
-    }
+    if (n < 0) { f->adopt_count(); f->take_rows(&rows, 1, f->n); }
     return nm;
 }
 
@@ -3383,7 +3375,7 @@ extern "C" int orbx_frame_search_local_points_fisheye(orbx_matcher *m, orbx_fram
     if (f->n_known || frame_occupied || n_mp == 0) { const int rc = frame_count(f, &N); if (rc != ORBX_OK) return rc; }   // the mask holds N entries
     for (int i = 0; i < N; i++) frame_match[i] = -1;
     if (n_mp == 0) return 0;
-    const int nc = N >= 0 ? N : f->cap;
+    const int nc = f->rows_n();
     ORBX_HIP(hipSetDevice(m->device));
     const size_t q = (size_t)n_mp, q2 = 2 * q;
     FrustumChecks FC;
@@ -3449,20 +3441,13 @@ extern "C" int orbx_frame_search_local_points_fisheye(orbx_matcher *m, orbx_fram
     ORBX_HIP(hipGetLastError());
     int32_t nm = 0;
     ORBX_TRY(m->d2h(in_view, div_out, q2));
+    const orbx_frame::Rows rows = {T.match, 1, nc, frame_match, 0};
     if (match) {
-        if (N >= 0) {
-            ORBX_TRY(m->d2h(frame_match, T.match, 4 * (size_t)N));
-        } else {   // the counts come back with the results
-            f->h_match.resize((size_t)f->cap);
-            ORBX_TRY(m->d2h(f->h_match.data(), T.match, 4 * (size_t)nc));
-            ORBX_TRY(m->d2h(f->h_count, f->count, 8));
-        }
+        ORBX_TRY(f->fetch_rows(&rows));
+        if (N < 0) ORBX_TRY(f->fetch_count());   // the counts come back with the results
         ORBX_TRY(m->d2h(&nm, T.nmatches, 4));
     }
     ORBX_TRY(m->sync_and_deliver());
-    if (N < 0) {
-        f->n_left = f->h_count[0]; f->n_right = f->h_count[1]; f->n = f->n_left + f->n_right; f->n_known = true;
-        memcpy(frame_match, f->h_match.data(), 4 * (size_t)std::max(f->n, 0));
-    }
+    if (N < 0) { f->adopt_count(); f->take_rows(&rows, 1, f->n); }
     return nm;
 }

@@ -347,6 +347,102 @@ def test_load_stereo_fisheye_batch_equals_host_load(oracle):
         osa.DeviceFrame(m, capl + capr).load_stereo_fisheye_batch(exl, exl, 0)
 
 
+def _whole(a):
+    """The array a wrapper handed to the library, of which the returned `a` is the leading N entries of every row."""
+    return a if a.base is None else a.base
+
+
+# entry points that can be the first to touch a batch-loaded fisheye handle, and the value their wrappers fill the result arrays with
+PENDING = {"mappoints": -1, "frame": -1, "window_left_only": -1, "local_points": -1, "compute_bow": 0, "search_by_bow": -1}
+
+
+@pytest.mark.parametrize("entry", sorted(PENDING))
+def test_counts_pending_equal_counted_first(entry):
+    """Two handles loaded from the same frame of a fisheye stereo stage with a capacity above N: A is counted first, B meets the call with its
+    counts still on the device.  The same return value, the same entries [0, N), nothing written beyond N (the wrappers' arrays have the handle's
+    capacity and keep their fill there), and B knows A's counts afterwards."""
+    import orb_slam3_amd as osa
+    from test_gpu_matcher import _random_vocabulary
+    from test_gpu_stereo_fisheye import _rig_for_shifted_images
+    w = h = 512
+    nb, nf, f = 8, 1000, 3
+    left, right = _extract_pairs(w, h, nb, nf)
+    exl, exr = osa.ORBextractor(nf, 1.2, 8, 20, 7), osa.ORBextractor(nf, 1.2, 8, 20, 7)
+    exl.extract_batch_device(left.data_ptr(), nb, w, h, w, w * h, (0, 0))
+    exr.extract_batch_device(right.data_ptr(), nb, w, h, w, w * h, (0, 0))
+    exl.stereo_fisheye_batch_device(exr, _rig_for_shifted_images())
+    sf = exl.GetScaleFactors().astype(np.float32)
+    bounds = (0.0, float(w), 0.0, float(h))
+    (_, kl, dl), (_, kr, dr), (_, kl2, dl2) = exl.download(f), exr.download(f), exl.download(f - 1)
+    desc = np.concatenate([dl, dr]).reshape(-1, 32)
+    nl, nr = len(kl), len(kr)
+    N, cap = nl + nr, exl.batch_view().cap + exr.batch_view().cap + 37
+    assert nl > 0 and nr > 0 and N < cap
+    rng = np.random.default_rng(83)
+    m = osa.ORBmatcher(0.8, True)
+    if entry == "mappoints":
+        mp = _mp(rng, kl, kr, desc, 1500)
+
+        def call(D):
+            n, fm = m.SearchByProjectionFisheye(D, None, None, None, mp, 3.0)
+            return [n], [fm]
+    elif entry == "frame":
+        q = _q(rng, kl, kr, desc, 800)
+
+        def call(D):
+            n, cm = m.SearchByProjectionFrameFisheye(D, None, q, 5.0, 0, raw=True)
+            return [n], [cm]
+    elif entry == "window_left_only":
+        q = _q(rng, kl, kr, desc, 800)
+        o = np.minimum(q["octave"], 7)
+        qw = dict(x=q["u"], y=q["v"], r=(7.0 * sf[o]).astype(np.float32), min_level=o - 1, max_level=o + 1, angle=q["angle"], desc=q["desc"],
+                  has_obs=q["has_obs"])
+
+        def call(D):
+            n, match = m.SearchByProjectionWindowFisheye(D, qw, 64.0, True, raw=True)
+            assert (match[nl:] == -1).all()   # the right camera is not searched
+            return [n], [match]
+    elif entry == "local_points":
+        from test_oracle_geometry import fisheye_case, fisheye_views
+        c = fisheye_case(1, n=3000)
+        views = fisheye_views(fisheye_case(1), "fisheye/1")
+        mp_desc = _noisy(rng, desc[rng.integers(0, N, 3000)], 0.05)
+
+        def call(D):
+            n, fm, iv = m.SearchLocalPointsFisheye(D, views, c["lsf"], c["cosl"], c["pos"], c["normal"], c["mn"], c["mx"], mp_desc, th=30.0)   # (wide windows: the points are not the features')
+            return [n, iv], [fm]
+    else:
+        cp, ci, nd, wi = _random_vocabulary(rng, 4, 2, ragged=False)
+        voc = osa.ORBVocabulary(2, cp, ci, _noisy(rng, desc[rng.integers(0, N, len(nd))], 0.03), wi)
+        if entry == "compute_bow":
+            def call(D):
+                return [], list(D.compute_bow_fisheye(voc, 1))
+        else:
+            _, node = m.BowTransform(voc, dl2, 1)
+            nodes = np.unique(node)
+            kfs = [(dl2, kl2["angle"], None, osa.FeatureVector(nodes, [np.nonzero(node == x)[0] for x in nodes]))]
+
+            def call(D):
+                D.compute_bow_fisheye(voc, 1, download=False)
+                nm, match = m.SearchByBoWDeviceFisheye(D, kfs)
+                return [nm], [match]
+
+    def load():
+        return osa.DeviceFrame(m, cap).load_stereo_fisheye_batch(exl, exr, f, bounds=bounds, scale_factors=sf)
+    A, B = load(), load()
+    assert A.counts() == (nl, nr)
+    (ra, a), (rb, b) = call(A), call(B)
+    assert len(ra) == len(rb) and all(np.array_equal(x, y) for x, y in zip(ra, rb)), (ra, rb)
+    assert len(a) == len(b) > 0
+    for x, y in zip(a, b):
+        assert x.shape == y.shape and x.shape[-1] == N and np.array_equal(x, y)
+        for whole in (_whole(x), _whole(y)):
+            assert whole.shape[-1] == cap and (whole[..., N:] == PENDING[entry]).all()
+    if entry not in ("compute_bow", "local_points"):
+        assert (a[0] >= 0).sum() > 20   # the call did match
+    assert B.counts() == (nl, nr) and B.count() == N
+
+
 # ---- refusals ----
 def test_refusals(oracle):
     import orb_slam3_amd as osa

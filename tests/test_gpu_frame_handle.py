@@ -291,3 +291,94 @@ def test_errors_before_anything_is_enqueued(canvas1):
     ex.sync()
     big.load_batch(ex, 3)
     assert big.count() == len(ex.download(3)[1])
+
+
+def _whole(a):
+    """The array a wrapper handed to the library, of which the returned `a` is the leading N entries of every row."""
+    return a if a.base is None else a.base
+
+
+# entry points that can be the first to touch a batch-loaded handle, and the value their wrappers fill the result arrays with
+PENDING = {"mappoints": -1, "frame": -1, "window": -1, "local_points": -1, "compute_bow": 0, "search_by_bow": -1, "search_by_bow_resident": -1}
+
+
+@pytest.mark.parametrize("entry", sorted(PENDING))
+def test_count_pending_equals_counted_first(canvas1, entry):
+    """Two handles loaded from the same batch frame with a capacity above N: A is counted first, B meets the call with its count still on the
+    device.  The same return value, the same entries [0, N), nothing written beyond N (the wrappers' arrays have the handle's capacity and keep
+    their fill there), and B knows A's count afterwards."""
+    import orb_slam3_amd as osa
+    from test_gpu_matcher import _random_vocabulary
+    ex = osa.ORBextractor(1000, 1.2, 8, 20, 7)
+    d_frames = _batch(canvas1, 0)
+    ex.extract_batch_device(d_frames.data_ptr(), 8, W, H, W, W * H, (0, 1000))
+    sf = ex.GetScaleFactors().astype(np.float32)
+    (_, k2, d2), (_, k, d) = ex.download(2), ex.download(3)
+    N, cap = len(k), ex.batch_view().cap + 37
+    assert 0 < N < cap
+    rng = np.random.default_rng(17)
+    m = osa.ORBmatcher(0.8, True)
+    mp, src = _mp(rng, k, d, 700, 2.0)
+    q = _queries(rng, k, d, src)
+    if entry == "mappoints":
+        def call(D):
+            n, fm = m.SearchByProjection(D, mp, 3.0)
+            return [n], [fm]
+    elif entry == "frame":
+        def call(D):
+            n, cm = m.SearchByProjectionFrame(D, q, 15.0, 0, raw=True)
+            return [n], [cm]
+    elif entry == "window":
+        o = q["octave"]
+        qw = dict(x=q["u"], y=q["v"], r=(7.0 * sf[o]).astype(np.float32), min_level=o - 1, max_level=o + 1, angle=q["angle"], desc=q["desc"],
+                  has_obs=q["has_obs"])
+
+        def call(D):
+            n, match = m.SearchByProjectionWindow(D, qw, 64.0, True, raw=True)
+            return [n], [match]
+    elif entry == "local_points":
+        src, pos, normal, min_d, max_d = _local_map(rng, k, 3000, False)
+        desc = _noisy(rng, d[src], 0.05)
+        pose = (np.eye(3, dtype=np.float32), np.zeros(3, np.float32), np.zeros(3, np.float32))
+
+        def call(D):
+            n, fm, iv = m.SearchLocalPoints(D, EUROC4 + (0, 0, 0, 0, 0, 0.0), pose, np.float32(np.log(np.float32(1.2))), 0.5, pos, normal, min_d,
+                                            max_d, desc, th=3.0)
+            return [n, iv], [fm]
+    else:
+        cp, ci, nd, wi = _random_vocabulary(rng, 4, 2, ragged=False)
+        voc = osa.ORBVocabulary(2, cp, ci, _noisy(rng, d[rng.integers(0, N, len(nd))], 0.03), wi)
+        if entry == "compute_bow":
+            def call(D):
+                return [], list(D.compute_bow(voc, 1))
+        elif entry == "search_by_bow":
+            kfs = []
+            for kk, dd in ((k2, d2), (k, d)):
+                _, node = m.BowTransform(voc, dd, 1)
+                nodes = np.unique(node)
+                kfs.append((dd, kk["angle"], None, osa.FeatureVector(nodes, [np.nonzero(node == x)[0] for x in nodes])))
+
+            def call(D):
+                D.compute_bow(voc, 1, download=False)
+                nm, match = m.SearchByBoWDevice(D, kfs)
+                return [nm], [match]
+        else:
+            kf = osa.DeviceKeyFrame.from_host(m, osa.FrameView(k2, d2, 0.0, float(W), 0.0, float(H), sf))
+            kf.compute_bow(m, voc, 1, download=False)
+
+            def call(D):
+                D.compute_bow(voc, 1, download=False)
+                nm, match = m.SearchByBoWResident(D, [kf])
+                return [nm], [match]
+    A, B = osa.DeviceFrame(m, cap).load_batch(ex, 3), osa.DeviceFrame(m, cap).load_batch(ex, 3)
+    assert A.count() == N
+    (ra, a), (rb, b) = call(A), call(B)
+    assert len(ra) == len(rb) and all(np.array_equal(x, y) for x, y in zip(ra, rb)), (ra, rb)
+    assert len(a) == len(b) > 0
+    for x, y in zip(a, b):
+        assert x.shape == y.shape and x.shape[-1] == N and np.array_equal(x, y)
+        for whole in (_whole(x), _whole(y)):
+            assert whole.shape[-1] == cap and (whole[..., N:] == PENDING[entry]).all()
+    if entry != "compute_bow":
+        assert (a[0] >= 0).sum() > 50   # the call did match
+    assert B.count() == N

@@ -287,23 +287,40 @@ def test_device_atan2f_equals_libm_and_kb8_projection_equals_oracle(emul_lib, tm
     assert r.returncode == 0 and "bad 0" in r.stdout, r.stdout[-2000:]
 
 
-def test_one_context_calls_of_changing_size_stand_alone_under_sanitizers(tmp_path):
-    """tests/cpp/arena_reuse_check.cpp: on ONE matcher context per entry point a big call, one about 1.5 times as big that still fits the arena the first
-    left behind, and a small one -- SearchByProjection (frame with u_right, mask, angles, has_obs; map points; window), Fuse's search, knn2,
-    SearchForInitialization, ComputeDistinctiveDescriptors; every result equals the same call on a fresh context.  A stand-alone program compiled with
-    -fsanitize=address,undefined, the sanitizer's runtime linked INTO it, and the AddressSanitizer build of the emulated library resolving against that
-    runtime: an upload staged past the pinned mirror or a kernel writing past the arena ends the run.  (The stand-in HIP runtime never frees its
-    streams: leak detection is off.)"""
+def _stand_alone_under_sanitizers(tmp_path, name):
+    """tests/cpp/<name>.cpp compiled with -fsanitize=address,undefined, the sanitizer's runtime linked INTO the program, and the AddressSanitizer
+    build of the emulated library resolving against that runtime; returns the finished run.  (The stand-in HIP runtime never frees its streams:
+    leak detection is off.)"""
     import fcntl
     (SIMT / "build").mkdir(exist_ok=True)
     with open(SIMT / "build" / ".lock", "w") as lock:   # the copied sources in tests/simt/build are shared with the other tests' builds
         fcntl.flock(lock, fcntl.LOCK_EX)
         r = subprocess.run([sys.executable, str(SIMT / "build.py"), "--asan", "--static-rt"], capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    exe = tmp_path / "arena_reuse_check"
+    exe = tmp_path / name
     r = subprocess.run([str(CLANG), "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer",
-                        str(ROOT / "tests/cpp/arena_reuse_check.cpp"), "-o", str(exe), str(SIMT / "build" / "liborbx_emul_asan_static.so"),
+                        str(ROOT / "tests" / "cpp" / f"{name}.cpp"), "-o", str(exe), str(SIMT / "build" / "liborbx_emul_asan_static.so"),
                         f"-Wl,-rpath,{SIMT / 'build'}"], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
-    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=1500, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+    return subprocess.run([str(exe)], capture_output=True, text=True, timeout=1500, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=0"))
+
+
+def test_one_context_calls_of_changing_size_stand_alone_under_sanitizers(tmp_path):
+    """tests/cpp/arena_reuse_check.cpp: on ONE matcher context per entry point a big call, one about 1.5 times as big that still fits the arena the first
+    left behind, and a small one -- SearchByProjection (frame with u_right, mask, angles, has_obs; map points; window), Fuse's search, knn2,
+    SearchForInitialization, ComputeDistinctiveDescriptors; every result equals the same call on a fresh context.  A stand-alone program under
+    AddressSanitizer and UBSan (_stand_alone_under_sanitizers): an upload staged past the pinned mirror or a kernel writing past the arena ends the
+    run."""
+    r = _stand_alone_under_sanitizers(tmp_path, "arena_reuse_check")
     assert r.returncode == 0 and "arena reuse ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+def test_frame_handle_adopts_its_pending_count_stand_alone_under_sanitizers(tmp_path):
+    """tests/cpp/frame_pending_count_check.cpp: two extracted batches of two 320 x 240 frames (one extractor; a left / right pair with the fisheye
+    stereo stage), and per entry point that can be the first to touch a batch-loaded handle -- the three SearchByProjection forms, SearchLocalPoints,
+    ComputeBoW with downloads, SearchByBoW against host and resident key frames, and their fisheye twins with the left-only window search -- two
+    handles of a capacity above N, one counted first, one not: the same return value, the same entries [0, N), the caller's arrays (heap blocks of
+    exactly the capacity, filled with a sentinel) untouched beyond N, the same counts afterwards.  Under the same sanitizers as the program above:
+    a copy that runs past the caller's array ends the run."""
+    r = _stand_alone_under_sanitizers(tmp_path, "frame_pending_count_check")
+    assert r.returncode == 0 and "frame pending count ok" in r.stdout and "FAILED" not in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
