@@ -649,8 +649,8 @@ int orbx_fuse_search(orbx_matcher *m, const orbx_frame_desc *kf, const float *in
  * KeyFrame::KeyFrame(Frame &F, Map*, KeyFrameDatabase*) (KeyFrame.cc:36-82) copies the frame's mvKeysUn, mDescriptors, mvuRight, mvScaleFactors,
  * mvInvLevelSigma2, the image bounds and mGrid; none of them changes afterwards, and LocalMapping / LoopClosing search the same 10 - 30 covisible key
  * frames again for every new key frame.  An orbx_keyframe is that copy on the device: ONE allocation sized by N (about 66 bytes per feature + 6 KB of
- * grid; sized by the frame handle's capacity only when N of a batch-loaded frame is still on the device), immutable once made.  Monocular / rectified
- * key frames (NLeft == -1, Pinhole) only.
+ * grid; sized by the frame handle's capacity only when N of a batch-loaded frame is still on the device), immutable once made.  These entry points take monocular / rectified
+ * key frames (NLeft == -1, Pinhole); fisheye-stereo key frames have the `_fisheye` forms further down, and each kind's calls refuse the other kind.
  *   orbx_keyframe_from_frame: a device-to-device copy of a loaded monocular / rectified orbx_frame owned by `m` -- rows, count, scale factors and the grid
  *     AS BUILT (no rebuild) -- plus inv_level_sigma2 [the frame's nlevels] (mvInvLevelSigma2; NULL = none: only the gate-less searches accept the key
  *     frame).  Enqueued on m's stream, no host synchronisation, also while N is still on the device; the frame may be reloaded as soon as the call
@@ -710,6 +710,54 @@ int orbx_keyframe_fuse_map_points(orbx_matcher *m, int n_kf, orbx_keyframe *cons
                                   float log_scale_factor, int strict_fp, int n_mp, const float *pos, const float *normal, const float *min_dist,
                                   const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
                                   uint8_t *projected);
+
+/* ---- fisheye-stereo key frames (KeyFrame::NLeft != -1: KannalaBrandt8 rigs) ----
+ * What KeyFrame::KeyFrame(Frame&) copies of a rig frame and Fuse reads: mvKeys (rows [0, N_left)), mvKeysRight (stored at a row offset the host knows
+ * before the counts are, as the frame handle's), all N = N_left + N_right descriptor rows, the two counts, mvScaleFactors, mvInvLevelSigma2, the bounds,
+ * mGrid and mGridRight (side-local indices).  One allocation, immutable, owned by no matcher; the `ready` event, orbx_keyframe_destroy and SHARING are
+ * those of every orbx_keyframe.  NOT kept: mvLeftToRightMatch / mvRightToLeftMatch (Fuse does not read them) and mvuRight (a rig key frame has none that
+ * Fuse could use: every candidate of either camera meets the monocular gate, 5.99, as through the adapter's single-target Fuse).
+ * Numbering as every fisheye entry point: features [0, N_left) = left camera, [N_left, N) = right camera.
+ *   orbx_keyframe_from_frame_fisheye: a device-to-device copy of a loaded fisheye-stereo orbx_frame owned by `m` (orbx_frame_load_host_fisheye or
+ *     orbx_frame_load_stereo_fisheye_batch): rows, both counts, scale factors and both grids AS BUILT, plus inv_level_sigma2 (NULL = none).  On m's
+ *     stream, no host synchronisation, also while the counts are still on the device (the key frame is searchable without one, too: the counts come
+ *     home with the first search's results); the frame may be reloaded as soon as the call returns.  A monocular handle, a handle that was never
+ *     loaded or one of another matcher: ORBX_E_BAD_ARG before anything is enqueued.
+ *   orbx_keyframe_create_host_fisheye: the same object from host arrays; arguments as orbx_frame_load_host_fisheye without l2r / r2l (left->keypoints_un
+ *     = mvKeys, left->n = N_left, left->descriptors = ALL N rows, kps_right = mvKeysRight [n_right]).  One upload; both grids in k_grid_build's order,
+ *     so candidate order and ties are orbx_fuse_search's on that camera's arrays.  N <= 65535 (ORBX_E_TOO_LARGE).
+ *   orbx_keyframe_counts: N_left and N_right (n_right = -1 for a monocular key frame, as orbx_frame_counts); at most one synchronisation, then cached.
+ *     orbx_keyframe_count of a fisheye key frame returns N.
+ * Every other key-frame call above and below (orbx_keyframe_fuse_search, orbx_keyframe_fuse_map_points, the BoW calls and searches) refuses a fisheye
+ * key frame with ORBX_E_BAD_ARG before anything is enqueued, and the two searches here refuse a monocular one.  Not covered: BoW on fisheye key frames
+ * and the KannalaBrandt8 triangulation gate on resident key frames. */
+int orbx_keyframe_from_frame_fisheye(orbx_matcher *m, orbx_frame *frame, const float *inv_level_sigma2, orbx_keyframe **out);
+int orbx_keyframe_create_host_fisheye(orbx_matcher *m, const orbx_frame_desc *left, const orbx_keypoint *kps_right, int n_right,
+                                      const float *inv_level_sigma2, orbx_keyframe **out);
+int orbx_keyframe_counts(orbx_keyframe *kf, int *n_left, int *n_right);
+/* orbx_keyframe_fuse_search for rig key frames: queries / best_idx / best_dist hold [n_kf][2] entries, index 2 k = key frame k's left-camera query set,
+ * 2 k + 1 its right-camera set.  A left-camera problem searches mvKeys with the left grid and descriptor rows [0, N_left), a right-camera problem
+ * mvKeysRight with the right grid and rows [N_left, N); a right-camera best_idx comes back in the rig's numbering, N_left + j (ORBmatcher.cc:1296; -1
+ * stays -1).  queries[.].ur is ignored and may be NULL: use_chi2 applies the monocular gate (5.99) to every candidate.  Each row equals
+ * orbx_fuse_search on that camera's host arrays (right indices + N_left) bit for bit.  Cost shape, limits and errors as orbx_keyframe_fuse_search: one
+ * upload run, one launch over 2 n_kf problems, one download run, one synchronisation; n_kf <= ORBX_MAX_FUSE_KEYFRAMES. */
+int orbx_keyframe_fuse_search_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fuse_queries *queries, int use_chi2, int strict_fp,
+                                      int32_t *const *best_idx, int32_t *const *best_dist);
+/* BOTH Fuse calls of LocalMapping::SearchInNeighbors' loop on a rig -- matcher.Fuse(pKFi, vpMapPointMatches) and matcher.Fuse(pKFi, vpMapPointMatches,
+ * true) -- for n_kf target key frames in one call, projection included (ORBmatcher.cc:1148-1337 with :1150-1163 choosing the camera).
+ * views [n_kf][2]: the left camera's R, t = GetPose(), twc = GetCameraCenter(), params = mpCamera's; the right camera's GetRightPose(),
+ * GetRightCameraCenter(), mpCamera2's -- evaluated by the caller, as for orbx_is_in_frustum_checks.  Map points flat as orbx_keyframe_fuse_map_points
+ * takes them; skip [n_kf][n_mp] (may be NULL): one row per key frame, read by both cameras (the caller's tail re-checks isBad() / IsInKeyFrame per
+ * camera).  Per (key frame, camera, map point), in the reference's order (:1186-1244): p3Dc = R p + t; p3Dc.z < 0 rejects; KannalaBrandt8::project
+ * (the restatement orbx_is_in_frustum_checks uses, same one-ulp caveat); KeyFrame::IsInImage, strict on the max side; dist3D outside [0.8 mfMinDistance,
+ * 1.2 mfMaxDistance] rejects; PO.dot(Pn) < 0.5 * dist3D rejects (in double, no division); PredictScale; radius = th * mvScaleFactors[level]; candidates
+ * with octave in [level - 1, level] and chi2 <= 5.99.  Every key frame needs inv_level_sigma2.
+ * Outputs [n_kf][2][n_mp]: best_idx (rig numbering) / best_dist, projected (may be NULL).  Four launches whatever n_kf is (upload, projection, search,
+ * download), one synchronisation; the map points go up once and the query records never visit the host. */
+int orbx_keyframe_fuse_map_points_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views, float th,
+                                          float log_scale_factor, int strict_fp, int n_mp, const float *pos, const float *normal, const float *min_dist,
+                                          const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
+                                          uint8_t *projected);
 
 /* MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403), batched over map points: set s = the descriptors of the
  * observations of map point s, descriptors[set_ptr[s] .. set_ptr[s+1]) (gathered by the adapter from

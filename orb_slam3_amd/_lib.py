@@ -165,6 +165,8 @@ SYMBOLS = [
     "orbx_keyframe_fuse_map_points",
     "orbx_keyframe_compute_bow", "orbx_keyframe_bow_from_frame", "orbx_frame_search_by_bow_resident", "orbx_keyframe_search_by_bow",
     "orbx_keyframe_search_for_triangulation",
+    "orbx_keyframe_from_frame_fisheye", "orbx_keyframe_create_host_fisheye", "orbx_keyframe_counts", "orbx_keyframe_fuse_search_fisheye",
+    "orbx_keyframe_fuse_map_points_fisheye",
 ]
 
 
@@ -291,6 +293,11 @@ def lib() -> C.CDLL:
     L.orbx_frame_search_by_bow_resident.argtypes = [vp, vp, i32, C.POINTER(vp), C.POINTER(vp), f32, i32, vp, i32, vp]
     L.orbx_keyframe_search_by_bow.argtypes = [vp, vp, vp, i32, C.POINTER(vp), C.POINTER(vp), f32, i32, vp, i32, vp]
     L.orbx_keyframe_search_for_triangulation.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(KeyFrameGate), vp]
+    L.orbx_keyframe_from_frame_fisheye.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    L.orbx_keyframe_create_host_fisheye.argtypes = [vp, C.POINTER(FrameDesc), vp, i32, vp, C.POINTER(vp)]
+    L.orbx_keyframe_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+    L.orbx_keyframe_fuse_search_fisheye.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(FuseQueries), i32, i32, C.POINTER(vp), C.POINTER(vp)]
+    L.orbx_keyframe_fuse_map_points_fisheye.argtypes = [vp, i32, C.POINTER(vp), vp, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbx_frame_search_by_projection_mappoints_fisheye.argtypes = [vp, vp, vp, i32] + [vp] * 12 + [f32, f32, vp]
     L.orbx_frame_search_by_projection_frame_fisheye.argtypes = [vp, vp, vp, i32] + [vp] * 8 + [f32, i32, i32, vp]
     L.orbx_frame_search_local_points_fisheye.argtypes = [vp, vp, vp, vp, f32, f32, i32] + [vp] * 8 + [f32, f32, i32, f32, vp, vp]

@@ -110,6 +110,14 @@ public:
     inline DeviceKeyFrame(ORBmatcher &matcher, DeviceFrame &frame, const float *mvInvLevelSigma2);
     // the same object from host arrays (a loaded atlas): one upload
     inline DeviceKeyFrame(ORBmatcher &matcher, const FrameView &KF, const float *mvInvLevelSigma2);
+    // a fisheye-stereo key frame (KeyFrame::NLeft != -1) -- mvKeys, mvKeysRight, all N descriptor rows, both counts and both grids: a device-to-device
+    // copy of a loaded fisheye-stereo DeviceFrame of `matcher` (orbx_keyframe_from_frame_fisheye; asynchronous, also while the counts are still on the
+    // device) ...
+    struct Fisheye {};
+    inline DeviceKeyFrame(Fisheye, ORBmatcher &matcher, DeviceFrame &frame, const float *mvInvLevelSigma2);
+    // ... or the same object from host arrays (orbx_keyframe_create_host_fisheye): left.mvKeysUn = mvKeys, left.N = NLeft, left.mDescriptors = ALL N
+    // rows, keysRight = mvKeysRight.  mvLeftToRightMatch / mvRightToLeftMatch are not kept: Fuse does not read them.
+    inline DeviceKeyFrame(ORBmatcher &matcher, const FrameView &left, const std::vector<orbx_keypoint> &keysRight, const float *mvInvLevelSigma2);
     ~DeviceKeyFrame() { orbx_keyframe_destroy(kf_); }
     DeviceKeyFrame(const DeviceKeyFrame &) = delete;
     DeviceKeyFrame &operator=(const DeviceKeyFrame &) = delete;
@@ -118,6 +126,11 @@ public:
         const int st = orbx_keyframe_count(kf_, &n);
         if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_count: ") + orbx_status_string(st));
         return n;
+    }
+    // NLeft and N - NLeft (-1 for a monocular / rectified key frame)
+    void counts(int &nLeft, int &nRight) {
+        const int st = orbx_keyframe_counts(kf_, &nLeft, &nRight);
+        if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_counts: ") + orbx_status_string(st));
     }
     // KeyFrame::ComputeBoW on the resident descriptors (orbx_keyframe_compute_bow): the key frame keeps mFeatVec for the resident SearchByBoW /
     // SearchForTriangulation overloads of ORBmatcher.  Set once; a second call with the same vocabulary and levelsup only returns the ids.  wordId /
@@ -575,6 +588,48 @@ public:
         if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_fuse_map_points: ") + orbx_status_string(r));
     }
 
+    // FuseSearchKeyFrames for K fisheye-stereo key frames (orbx_keyframe_fuse_search_fisheye): q / bestIdx / bestDist hold 2 K entries, 2 k = key frame
+    // k's left-camera set, 2 k + 1 its right-camera set (ur is not read).  A right-camera index is NLeft + j (ORBmatcher.cc:1296).
+    void FuseSearchKeyFramesFisheye(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<FuseQueries> &q, bool useChi2,
+                                    std::vector<std::vector<int32_t>> &bestIdx, std::vector<std::vector<int32_t>> &bestDist, bool strictFloat = false) {
+        const size_t K = vpKFs.size();
+        if (q.size() != 2 * K) throw std::invalid_argument("FuseSearchKeyFramesFisheye: a left and a right query set per key frame");
+        std::vector<orbx_keyframe *> h(K);
+        std::vector<orbx_fuse_queries> c(2 * K);
+        std::vector<int32_t *> pi(2 * K), pd(2 * K);
+        bestIdx.assign(2 * K, {}); bestDist.assign(2 * K, {});
+        for (size_t k = 0; k < K; k++) h[k] = vpKFs[k]->handle();
+        for (size_t p = 0; p < 2 * K; p++) {
+            const int nq = (int)q[p].u.size();
+            c[p] = orbx_fuse_queries{nq, q[p].u.data(), q[p].v.data(), nullptr, q[p].radius.data(), q[p].nPredictedLevel.data(), q[p].descriptors.data()};
+            bestIdx[p].assign(nq, -1); bestDist[p].assign(nq, 256);
+            pi[p] = bestIdx[p].data(); pd[p] = bestDist[p].data();
+        }
+        const int r = orbx_keyframe_fuse_search_fisheye(m_, (int)K, h.data(), c.data(), useChi2 ? 1 : 0, strictFloat ? 1 : 0, pi.data(), pd.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_fuse_search_fisheye: ") + orbx_status_string(r));
+    }
+
+    // BOTH Fuse calls of LocalMapping::SearchInNeighbors' loop on a rig -- Fuse(pKFi, vpMapPointMatches) and Fuse(pKFi, vpMapPointMatches, true) -- for
+    // every target in ONE call, projection included (orbx_keyframe_fuse_map_points_fisheye).  views [K][2]: GetPose() / GetCameraCenter() / mpCamera's
+    // parameters, then GetRightPose() / GetRightCameraCenter() / mpCamera2's; skip [K][n] (empty = none), one row per key frame for both cameras.
+    // bestIdx (the rig's numbering) / bestDist / projected: [K][2][n], row-major.
+    void FuseMapPointsFisheye(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<orbx_fisheye_view> &views, const FuseMapPointSet &mps,
+                              const std::vector<uint8_t> &skip, float th, float logScaleFactor, std::vector<int32_t> &bestIdx,
+                              std::vector<int32_t> &bestDist, std::vector<uint8_t> *projected = nullptr, bool strictFloat = false) {
+        const size_t K = vpKFs.size(), n = (size_t)mps.size();
+        if (views.size() != 2 * K || (!skip.empty() && skip.size() != K * n))
+            throw std::invalid_argument("FuseMapPointsFisheye: two views per key frame, K x n skip flags");
+        std::vector<orbx_keyframe *> h(K);
+        for (size_t k = 0; k < K; k++) h[k] = vpKFs[k]->handle();
+        bestIdx.assign(2 * K * n, -1); bestDist.assign(2 * K * n, 256);
+        if (projected) projected->assign(2 * K * n, 0);
+        const int r = orbx_keyframe_fuse_map_points_fisheye(m_, (int)K, h.data(), views.data(), th, logScaleFactor, strictFloat ? 1 : 0, (int)n,
+                                                            mps.pos.data(), mps.normal.data(), mps.minDistance.data(), mps.maxDistance.data(),
+                                                            mps.descriptors.data(), skip.empty() ? nullptr : skip.data(), bestIdx.data(),
+                                                            bestDist.data(), projected ? projected->data() : nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_fuse_map_points_fisheye: ") + orbx_status_string(r));
+    }
+
     // SearchBySim3(pKF1, pKF2, vpMatches12, S12, th) (ORBmatcher.cc:1457-1674): the two projection searches are gate-less fuse searches
     // (KeyFrame::GetFeaturesInArea, octave gate [l-1,l], first minimum wins, accept bestDist <= TH_HIGH :1569/:1656), followed by the
     // mutual-agreement pass (:1662-1675).  q1 = KF1's map points transformed by S21 and projected into KF2 (one entry per KF1 feature,
@@ -721,6 +776,17 @@ inline DeviceKeyFrame::DeviceKeyFrame(ORBmatcher &matcher, const FrameView &KF, 
     orbx_frame_desc fd = KF.c();
     const int st = orbx_keyframe_create_host(matcher.handle(), &fd, mvInvLevelSigma2, &kf_);
     if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_create_host: ") + orbx_status_string(st) + " " + orbx_last_error());
+}
+
+inline DeviceKeyFrame::DeviceKeyFrame(Fisheye, ORBmatcher &matcher, DeviceFrame &frame, const float *mvInvLevelSigma2) {
+    const int st = orbx_keyframe_from_frame_fisheye(matcher.handle(), frame.handle(), mvInvLevelSigma2, &kf_);
+    if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_from_frame_fisheye: ") + orbx_status_string(st) + " " + orbx_last_error());
+}
+inline DeviceKeyFrame::DeviceKeyFrame(ORBmatcher &matcher, const FrameView &left, const std::vector<orbx_keypoint> &keysRight,
+                                      const float *mvInvLevelSigma2) {
+    orbx_frame_desc fd = left.c();
+    const int st = orbx_keyframe_create_host_fisheye(matcher.handle(), &fd, keysRight.data(), (int)keysRight.size(), mvInvLevelSigma2, &kf_);
+    if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_create_host_fisheye: ") + orbx_status_string(st) + " " + orbx_last_error());
 }
 
 class ORBVocabularyDevice {

@@ -772,23 +772,32 @@ public:
 
     // The Fuse loop of LocalMapping::SearchInNeighbors (LocalMapping.cc: `matcher.Fuse(pKFi, vpMapPointMatches)` per target key frame) as ONE device call:
     // the candidate searches of that loop are independent -- what an earlier Fuse changes for a later one is only pMP->isBad() and
-    // pMP->IsInKeyFrame(pKF), which the tail below re-checks per query on the live graph.  Monocular / rectified key frames (NLeft == -1).
-    // The gates (:1186-1244) run here, once per (key frame, map point), with the reference's own accessors (MapPoint publishes only the SCALED distance
-    // bounds: GetMinDistanceInvariance / GetMaxDistanceInvariance); the survivors of all key frames go to orbx_keyframe_fuse_search together.  A tree
-    // that can read mfMinDistance / mfMaxDistance hands the flat map points to FuseMapPoints instead and drops this loop.
-    // vpDeviceKFs[k] is the resident copy of vpTargetKFs[k] (KeyFrame::mpDevice in an integrated tree).  Returns the fused points per key frame.
+    // pMP->IsInKeyFrame(pKF), which the tail below re-checks per query on the live graph.  The targets are all monocular / rectified (NLeft == -1) or
+    // all fisheye-stereo (a mixed list throws); for a rig the loop's second call, `matcher.Fuse(pKFi, vpMapPointMatches, true)`, is part of the same
+    // device call: every target contributes a left-camera and a right-camera problem (:1150-1163 choose pose, centre and camera).
+    // The gates (:1186-1244) run here, once per (key frame, camera, map point), with the reference's own accessors (MapPoint publishes only the SCALED
+    // distance bounds: GetMinDistanceInvariance / GetMaxDistanceInvariance); the survivors of all key frames go to orbx_keyframe_fuse_search (or
+    // orbx_keyframe_fuse_search_fisheye) together.  A tree that can read mfMinDistance / mfMaxDistance hands the flat map points to FuseMapPoints /
+    // FuseMapPointsFisheye instead and drops this loop.
+    // vpDeviceKFs[k] is the resident copy of vpTargetKFs[k] (KeyFrame::mpDevice in an integrated tree).  Returns the fused points per key frame (a
+    // rig's two calls added up).
     std::vector<int> Fuse(const std::vector<KeyFrame *> &vpTargetKFs, const std::vector<DeviceKeyFrame *> &vpDeviceKFs,
                           const std::vector<MapPoint *> &vpMapPoints, const float th = 3.0) {
         const size_t K = vpTargetKFs.size();
         if (vpDeviceKFs.size() != K) throw std::invalid_argument("Fuse: one DeviceKeyFrame per target key frame");
-        std::vector<FuseQueries> q(K);
-        std::vector<std::vector<int>> live(K);
+        const bool bFisheye = K > 0 && vpTargetKFs[0]->NLeft != -1;
+        for (size_t k = 0; k < K; k++)
+            if ((vpTargetKFs[k]->NLeft != -1) != bFisheye) throw std::invalid_argument("Fuse: monocular / rectified and fisheye-stereo targets in one list");
+        const size_t S = bFisheye ? 2 : 1;   // problems per key frame: problem k * S + bRight
+        std::vector<FuseQueries> q(K * S);
+        std::vector<std::vector<int>> live(K * S);
         const int nMPs = (int)vpMapPoints.size();
-        for (size_t k = 0; k < K; k++) {
-            KeyFrame *pKF = vpTargetKFs[k];
-            if (pKF->NLeft != -1) throw std::invalid_argument("Fuse: resident key frames are monocular / rectified");
-            Sophus::SE3f Tcw = pKF->GetPose();
-            Eigen::Vector3f Ow = pKF->GetCameraCenter();
+        for (size_t p = 0; p < K * S; p++) {
+            KeyFrame *pKF = vpTargetKFs[p / S];
+            const bool bRight = p % S == 1;
+            Sophus::SE3f Tcw = bRight ? pKF->GetRightPose() : pKF->GetPose();
+            Eigen::Vector3f Ow = bRight ? pKF->GetRightCameraCenter() : pKF->GetCameraCenter();
+            GeometricCamera *pCamera = bRight ? pKF->mpCamera2 : pKF->mpCamera;
             const float &bf = pKF->mbf;
             for (int i = 0; i < nMPs; i++) {
                 MapPoint *pMP = vpMapPoints[i];
@@ -797,7 +806,7 @@ public:
                 Eigen::Vector3f p3Dc = Tcw * p3Dw;
                 if (p3Dc(2) < 0.0f) continue;
                 const float invz = 1 / p3Dc(2);
-                const Eigen::Vector2f uv = pKF->mpCamera->project(p3Dc);
+                const Eigen::Vector2f uv = pCamera->project(p3Dc);
                 if (!pKF->IsInImage(uv(0), uv(1))) continue;
                 const float ur = uv(0) - bf * invz;
                 const float maxDistance = pMP->GetMaxDistanceInvariance();
@@ -808,33 +817,34 @@ public:
                 Eigen::Vector3f Pn = pMP->GetNormal();
                 if (PO.dot(Pn) < 0.5 * dist3D) continue;
                 int nPredictedLevel = pMP->PredictScale(dist3D, pKF);
-                q[k].u.push_back(uv(0)); q[k].v.push_back(uv(1)); q[k].ur.push_back(ur);
-                q[k].radius.push_back(th * pKF->mvScaleFactors[nPredictedLevel]);
-                q[k].nPredictedLevel.push_back(nPredictedLevel);
-                push_desc(q[k].descriptors, pMP->GetDescriptor());
-                live[k].push_back(i);
+                q[p].u.push_back(uv(0)); q[p].v.push_back(uv(1)); q[p].ur.push_back(ur);
+                q[p].radius.push_back(th * pKF->mvScaleFactors[nPredictedLevel]);
+                q[p].nPredictedLevel.push_back(nPredictedLevel);
+                push_desc(q[p].descriptors, pMP->GetDescriptor());
+                live[p].push_back(i);
             }
         }
         std::vector<std::vector<int32_t>> bestIdx, bestDist;
-        FuseSearchKeyFrames(vpDeviceKFs, q, true, bestIdx, bestDist);
+        if (bFisheye) FuseSearchKeyFramesFisheye(vpDeviceKFs, q, true, bestIdx, bestDist);   // (right-camera indices come back as idx + NLeft, :1296)
+        else FuseSearchKeyFrames(vpDeviceKFs, q, true, bestIdx, bestDist);
         std::vector<int> nFused(K, 0);
-        for (size_t k = 0; k < K; k++) {   // the reference's order: key frame by key frame, each with its tail on the live graph (:1309-1330)
-            KeyFrame *pKF = vpTargetKFs[k];
-            for (size_t j = 0; j < live[k].size(); j++) {
-                MapPoint *pMP = vpMapPoints[live[k][j]];
+        for (size_t p = 0; p < K * S; p++) {   // the reference's order: key frame by key frame, left then right, each with its tail on the live graph (:1309-1330)
+            KeyFrame *pKF = vpTargetKFs[p / S];
+            for (size_t j = 0; j < live[p].size(); j++) {
+                MapPoint *pMP = vpMapPoints[live[p][j]];
                 if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;   // an earlier Replace / AddObservation (this key frame's or an earlier one's) retired the query
-                if (bestIdx[k][j] < 0 || bestDist[k][j] > TH_LOW) continue;
-                MapPoint *pMPinKF = pKF->GetMapPoint(bestIdx[k][j]);
+                if (bestIdx[p][j] < 0 || bestDist[p][j] > TH_LOW) continue;
+                MapPoint *pMPinKF = pKF->GetMapPoint(bestIdx[p][j]);
                 if (pMPinKF) {
                     if (!pMPinKF->isBad()) {
                         if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
                         else pMPinKF->Replace(pMP);
                     }
                 } else {
-                    pMP->AddObservation(pKF, bestIdx[k][j]);
-                    pKF->AddMapPoint(pMP, bestIdx[k][j]);
+                    pMP->AddObservation(pKF, bestIdx[p][j]);
+                    pKF->AddMapPoint(pMP, bestIdx[p][j]);
                 }
-                nFused[k]++;
+                nFused[p / S]++;
             }
         }
         return nFused;

@@ -1437,6 +1437,123 @@ __global__ __launch_bounds__(64) void k_keyframe_copy(const KeyFrameCopy F) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Fisheye-stereo key frames (KeyFrame::NLeft != -1: KannalaBrandt8 rigs): both cameras' rows in one key frame, the right camera's at the row offset
+// roff the host knows, a grid per camera with side-local indices (as the fisheye frame handle).  A key frame is TWO problems of k_window_best1_kf:
+// (mvKeys, left grid, rows [0, N_left)) and (mvKeysRight, right grid, rows [N_left, N)).
+// ---------------------------------------------------------------------------------------------------------
+// k_fuse_project_kb8: k_fuse_project with the rig's camera -- the projection half of Fuse(pKF, vpMapPoints, th, bRight) (ORBmatcher.cc:1186-1244) for
+// every (key frame, camera, map point); problem p = 2 k + camera has its own view (GetPose() / GetRightPose(), the camera centre, mpCamera / mpCamera2's
+// parameters).  The gates in the reference's order, sums in k_fuse_project's order:
+//   p3Dc = R p + t; reject p3Dc.z < 0.0f
+//   KannalaBrandt8::project (kb8_project, as k_in_frustum_checks calls it); KeyFrame::IsInImage, strict on the max side
+//   dist3D = |p - twc|; reject outside [0.8f mfMinDistance, 1.2f mfMaxDistance]
+//   reject PO . Pn < 0.5 * dist3D, compared in double and without a division
+//   PredictScale(dist3D, pKF); radius = th * mvScaleFactors[level]; levels [level - 1, level]
+// There is no mvuRight on a rig key frame: no right-coordinate prediction is written.  skip [n_kf][n_mp] (may be NULL): one row per key frame, read by
+// both cameras.  Outputs [n_kf][2][n_mp].  Streaming work: no LDS.
+// grid (ceil(n_mp / 256), 2 n_kf), block 256
+__global__ __launch_bounds__(256) void k_fuse_project_kb8(const KfProblem *__restrict__ recs, const FisheyeView *__restrict__ views, float th,
+                                                          float log_scale_factor, int n_mp, const float *__restrict__ pos,
+                                                          const float *__restrict__ normal, const float *__restrict__ min_dist,
+                                                          const float *__restrict__ max_dist, const uint8_t *__restrict__ skip, float *__restrict__ qx,
+                                                          float *__restrict__ qy, float *__restrict__ qr, int32_t *__restrict__ qmin,
+                                                          int32_t *__restrict__ qmax, uint8_t *__restrict__ qvalid) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_mp) return;
+    const int p = blockIdx.y;
+    const size_t o = (size_t)p * n_mp + i;
+    const FisheyeView &V = views[p];
+    const float minx = recs[p].g.minx, miny = recs[p].g.miny, maxx = recs[p].maxx, maxy = recs[p].maxy;
+    const int nlevels = recs[p].nlevels;
+    const float *scale = recs[p].P.scale;
+    // every input of the pair requested at once (the gates read them conditionally: each would be a dependent round trip)
+    const uint8_t sk = skip ? skip[(size_t)(p >> 1) * n_mp + i] : (uint8_t)0;
+    const float P0 = pos[3 * i], P1 = pos[3 * i + 1], P2 = pos[3 * i + 2];
+    const float mn_in = min_dist[i], mx = max_dist[i], N0 = normal[3 * i], N1 = normal[3 * i + 1], N2 = normal[3 * i + 2];
+    float Pc[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+        Pc[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(V.R[3 * r], P0), __fmul_rn(V.R[3 * r + 1], P1)), __fmul_rn(V.R[3 * r + 2], P2)), V.t[r]);
+    float u = 0.f, v = 0.f, radius = 0.f;
+    int lvl = 0;
+    bool ok = false;
+    if (!sk && !(Pc[2] < 0.0f)) {
+        kb8_project(V.p, Pc[0], Pc[1], Pc[2], &u, &v);
+        if (u >= minx && u < maxx && v >= miny && v < maxy) {
+            const float PO0 = __fsub_rn(P0, V.twc[0]), PO1 = __fsub_rn(P1, V.twc[1]), PO2 = __fsub_rn(P2, V.twc[2]);
+            const float dist = sqrtf(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, PO0)), __fmul_rn(PO1, PO1)), __fmul_rn(PO2, PO2)));
+            const float maxDistance = __fmul_rn(1.2f, mx), minDistance = __fmul_rn(0.8f, mn_in);
+            const float dot = __fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, N0)), __fmul_rn(PO1, N1)), __fmul_rn(PO2, N2));
+            if (!(dist < minDistance || dist > maxDistance) && !((double)dot < 0.5 * (double)dist)) {
+                // MapPoint::PredictScale(dist3D, pKF) (MapPoint.cc:531-546), as k_fuse_project evaluates it
+                const float ratio = __fdiv_rn(mx, dist);
+                lvl = (int)ceilf(__fdiv_rn((float)log((double)ratio), log_scale_factor));
+                if (lvl < 0) lvl = 0;
+                else if (lvl >= nlevels) lvl = nlevels - 1;
+                radius = __fmul_rn(th, gld(scale + lvl));
+                ok = true;
+            }
+        }
+    }
+    qx[o] = u; qy[o] = v; qr[o] = radius;
+    qmin[o] = lvl - 1; qmax[o] = lvl;   // kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel
+    qvalid[o] = ok ? 1 : 0;
+}
+
+// A loaded fisheye-stereo orbx_frame copied into a key frame's own allocation -- what KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-82) does with mvKeys,
+// mvKeysRight, mDescriptors, mvScaleFactors, mvInvLevelSigma2, mGrid and mGridRight: both cameras' rows, both counts, the scale factors and both grids AS
+// BUILT.  The counts are read on the device.  The right rows move from the frame's row offset src_roff to the key frame's roff (the frame keeps them at
+// the left extractor's capacity while its counts are pending; the key frame is sized by the counts where the host knows them).
+struct KeyFrameCopyFisheye {
+    const orbx_keypoint *src_kps;
+    const uint8_t *src_desc;
+    const int32_t *src_count;       // [2]
+    const float *src_scale;
+    const uint16_t *src_gstart_l, *src_gorder_l, *src_gstart_r, *src_gorder_r;
+    orbx_keypoint *kps;
+    uint8_t *desc;
+    int32_t *count;                 // [2]
+    float *scale, *inv_sigma2;      // inv_sigma2 NULL: none given
+    uint16_t *gstart_l, *gorder_l, *gstart_r, *gorder_r;
+    int src_roff, roff, cap_l, cap_r, nlevels;
+    float inv_sigma2_host[kFrameMaxLevels];
+};
+// grid (2 + ceil(max(cap_l, cap_r) / 256)), block 64: block s < 2 copies count[s] and camera s's cell offsets, block 0 also the per-level arrays; block
+// b >= 2 copies rows [256 (b-2), 256 (b-1)) of each camera
+__global__ __launch_bounds__(64) void k_keyframe_copy_fisheye(const KeyFrameCopyFisheye F) {
+    const int nl = max(0, min(gld(F.src_count), F.cap_l)), nr = max(0, min(gld(F.src_count + 1), F.cap_r));
+    const int lane = threadIdx.x;
+    if (blockIdx.x < 2) {
+        const bool right = blockIdx.x == 1;
+        if (lane == 0) gst(F.count + (right ? 1 : 0), (int32_t)(right ? nr : nl));
+        if (!right && lane < F.nlevels) {
+            gst(F.scale + lane, gld(F.src_scale + lane));
+            if (F.inv_sigma2) gst(F.inv_sigma2 + lane, F.inv_sigma2_host[lane]);
+        }
+        const uint16_t *sg = right ? F.src_gstart_r : F.src_gstart_l;
+        uint16_t *dg = right ? F.gstart_r : F.gstart_l;
+        for (int c = lane; c <= kGridCells; c += 64) gst(dg + c, gld(sg + c));
+        return;
+    }
+    const int i0 = (blockIdx.x - 2) * 256;
+#pragma unroll 1
+    for (int s = 0; s < 2; s++) {
+        const int i1 = min(i0 + 256, s ? nr : nl);
+        if (i0 >= i1) continue;
+        const size_t so = s ? (size_t)F.src_roff : 0, dof = s ? (size_t)F.roff : 0;
+        const uint32_t *sk = reinterpret_cast<const uint32_t *>(F.src_kps + so);   // 28-byte rows: 7 dwords each
+        uint32_t *dk = reinterpret_cast<uint32_t *>(F.kps + dof);
+        for (int w = i0 * 7 + lane; w < i1 * 7; w += 64) dk[w] = sk[w];
+        const uint4 *sd = reinterpret_cast<const uint4 *>(F.src_desc + so * 32);   // 32-byte rows: 2 x 16 bytes
+        uint4 *dd = reinterpret_cast<uint4 *>(F.desc + dof * 32);
+        for (int w = i0 * 2 + lane; w < i1 * 2; w += 64) dd[w] = sd[w];
+        const uint16_t *sgo = s ? F.src_gorder_r : F.src_gorder_l;
+        uint16_t *dgo = s ? F.gorder_r : F.gorder_l;
+        for (int i = i0 + lane; i < i1; i += 64) dgo[i] = sgo[i];   // (a grid holds at most n entries: features outside it have none)
+    }
+}
+
 // k_window_brute (round 6): the same lists as k_window_best2_t WITHOUT the frame's grid, for ONE small problem (a single host-pointer call with a
 // thousand queries into a thousand features): a wave per query walks every feature of the frame, applies PosInGrid + GetFeaturesInArea's tests itself
 // (in_window: the candidate's grid cell comes out of that, so the key orders candidates exactly as the grid enumeration does: cell x, cell y, index) and

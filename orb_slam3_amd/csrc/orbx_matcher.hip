@@ -2471,6 +2471,14 @@ struct orbx_keyframe {
     std::atomic<KeyFrameBow *> bow{nullptr};   // NULL: no BoW attached (yet)
     const orbx_frame *src_frame = nullptr;     // orbx_keyframe_from_frame: the handle and its load counter at the copy
     uint64_t src_seq = 0;
+    // A fisheye-stereo key frame (KeyFrame::NLeft != -1; orbx_keyframe_from_frame_fisheye / orbx_keyframe_create_host_fisheye): kps = mvKeys at rows
+    // [0, N_left) and mvKeysRight at rows [roff, roff + N_right) -- roff is known on the host before the counts are; desc = mDescriptors with the
+    // right camera's rows at roff as well; count[0] / count[1] = N_left / N_right; a grid per camera with side-local indices (gorder_r = gorder + roff).
+    // n = N_left + N_right.  No mvuRight; mvLeftToRightMatch / mvRightToLeftMatch are not kept (Fuse does not read them).
+    bool fisheye = false;
+    int roff = 0;
+    uint16_t *gstart_r = nullptr, *gorder_r = nullptr;
+    std::atomic<int> n_left{-1}, n_right{-1};  // -1 while known on the device only (cached with n)
 };
 
 namespace {
@@ -2483,15 +2491,18 @@ void keyframe_bow_free(KeyFrameBow *b) {
 }
 
 // one allocation per key frame: rows for `cap` features (28 + 32 [+ 4] + 2 bytes each), the per-level arrays, the count and the grid's 3073 cell offsets
-int keyframe_alloc(int device, int cap, bool has_ur, bool has_sigma, int nlevels, const float *bounds4, orbx_keyframe **out) {
+// (roff >= 0: a fisheye-stereo key frame -- cap = roff + the right camera's rows, a second set of cell offsets)
+int keyframe_alloc(int device, int cap, bool has_ur, bool has_sigma, int nlevels, const float *bounds4, orbx_keyframe **out, int roff = -1) {
     orbx_keyframe *kf = new orbx_keyframe();
     kf->device = device; kf->cap = cap; kf->nlevels = nlevels;
+    kf->fisheye = roff >= 0; kf->roff = std::max(roff, 0);
     memcpy(kf->bounds, bounds4, sizeof(kf->bounds));
     const size_t c = (size_t)std::max(cap, 1);
     Layout L;
     // (rows and inv_sigma2 first: orbx_keyframe_create_host uploads them as one run)
     const size_t off_kps = L.add(28 * c), off_desc = L.add(32 * c), off_ur = has_ur ? L.add(4 * c) : 0, off_sg = has_sigma ? L.add(4 * (size_t)kFrameMaxLevels) : 0;
     const size_t off_scale = L.add(4 * (size_t)kFrameMaxLevels), off_count = L.add(8), off_gs = L.add(2 * ((size_t)kGridCells + 1)), off_go = L.add(2 * c);
+    const size_t off_gsr = kf->fisheye ? L.add(2 * ((size_t)kGridCells + 1)) : 0;
     hipError_t e = hipMalloc((void **)&kf->dev, L.used);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&kf->ready, hipEventDisableTiming);
     if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
@@ -2500,6 +2511,7 @@ int keyframe_alloc(int device, int cap, bool has_ur, bool has_sigma, int nlevels
     kf->inv_sigma2 = has_sigma ? (float *)(kf->dev + off_sg) : nullptr;
     kf->scale = (float *)(kf->dev + off_scale); kf->count = (int32_t *)(kf->dev + off_count);
     kf->gstart = (uint16_t *)(kf->dev + off_gs); kf->gorder = (uint16_t *)(kf->dev + off_go);
+    if (kf->fisheye) { kf->gstart_r = (uint16_t *)(kf->dev + off_gsr); kf->gorder_r = kf->gorder + kf->roff; }
     *out = kf;
     return ORBX_OK;
 }
@@ -2514,18 +2526,39 @@ inline void keyframe_release(orbx_keyframe *const *kfs, int n_kf) {   // after t
     for (int k = 0; k < n_kf; k++) kfs[k]->done.store(true, std::memory_order_release);
 }
 
-// the key-frame side of problem k
-inline void keyframe_problem(const orbx_keyframe *kf, bool chi2, int strict_fp, KfProblem *R) {
+// a fisheye key frame's counts as a call brought them home (clamped as k_keyframe_copy_fisheye clamps them)
+inline void keyframe_adopt_counts(orbx_keyframe *kf, int c0, int c1) {
+    const int nl = std::min(std::max(c0, 0), kf->roff), nr = std::min(std::max(c1, 0), kf->cap - kf->roff);
+    kf->n_left.store(nl); kf->n_right.store(nr); kf->n.store(nl + nr);
+}
+
+// the key-frame side of a problem; right: the right camera of a fisheye-stereo key frame (mvKeysRight, its grid, descriptor rows [N_left, N))
+inline void keyframe_problem(const orbx_keyframe *kf, bool chi2, int strict_fp, KfProblem *R, bool right = false) {
     memset(R, 0, sizeof(*R));
-    R->P.kps = kf->kps; R->P.desc = kf->desc; R->P.n_ptr = kf->count;
+    const size_t ro = right ? (size_t)kf->roff : 0;
+    R->P.kps = kf->kps + ro; R->P.desc = kf->desc + 32 * ro; R->P.n_ptr = kf->count + (right ? 1 : 0);
     R->P.u_right = chi2 ? kf->u_right : nullptr;   // the gate-less form (Fuse with a Sim3, SearchBySim3) never reads mvuRight (ORBmatcher.cc:1405-1433)
     R->P.scale = kf->scale;
     R->P.inv_sigma2 = chi2 ? kf->inv_sigma2 : nullptr;
     R->P.chi2_fma = strict_fp ? 0 : 1;
-    R->P.gstart = kf->gstart; R->P.gorder = kf->gorder;
+    R->P.gstart = right ? kf->gstart_r : kf->gstart; R->P.gorder = right ? kf->gorder_r : kf->gorder;
     R->g = grid_of(kf->bounds);
     R->maxx = kf->bounds[1]; R->maxy = kf->bounds[3];
     R->nlevels = kf->nlevels;
+}
+
+// Fisheye key frames whose counts are still on the device (made from a batch-loaded handle): a search brings them home among its downloads and adopts
+// them behind its synchronisation -- no synchronisation of their own.  pend: [n_kf][2] landing slots (sized before the first download is recorded).
+inline int keyframe_fetch_counts(orbx_matcher *m, bool fisheye, int n_kf, orbx_keyframe *const *kfs, std::vector<int32_t> *pend) {
+    if (!fisheye) return ORBX_OK;
+    pend->assign(2 * (size_t)n_kf, 0);
+    for (int k = 0; k < n_kf; k++)
+        if (kfs[k]->n.load() < 0) ORBX_TRY(m->d2h(pend->data() + 2 * (size_t)k, kfs[k]->count, 8));
+    return ORBX_OK;
+}
+inline void keyframe_take_counts(bool fisheye, int n_kf, orbx_keyframe *const *kfs, const std::vector<int32_t> &pend) {
+    for (int k = 0; fisheye && k < n_kf; k++)
+        if (kfs[k]->n.load() < 0) keyframe_adopt_counts(kfs[k], pend[2 * (size_t)k], pend[2 * (size_t)k + 1]);
 }
 
 inline void launch_window_best1_kf(hipStream_t st, const KfProblem *dR, int nq_max, int np) {   // ORBX_LAUNCH_WINDOW_BEST2's shape: a problem's blocks on one XCD
@@ -2623,43 +2656,57 @@ int orbx_keyframe_count(orbx_keyframe *kf, int *n) {
     if (v < 0) {   // made from a batch-loaded frame: one download behind the copy
         ORBX_HIP(hipSetDevice(kf->device));
         ORBX_HIP(hipEventSynchronize(kf->ready));
-        int32_t c = 0;
-        ORBX_HIP(hipMemcpy(&c, kf->count, 4, hipMemcpyDeviceToHost));
-        v = c;
-        kf->n.store(v);
+        int32_t c[2] = {0, 0};
+        ORBX_HIP(hipMemcpy(c, kf->count, kf->fisheye ? 8 : 4, hipMemcpyDeviceToHost));
+        if (kf->fisheye) keyframe_adopt_counts(kf, c[0], c[1]);
+        else kf->n.store(c[0]);
+        v = kf->n.load();
         kf->done.store(true, std::memory_order_release);
     }
     *n = v;
     return ORBX_OK;
 }
 
+int orbx_keyframe_counts(orbx_keyframe *kf, int *n_left, int *n_right) {
+    if (!kf) return ORBX_E_BAD_ARG;
+    int n = 0;
+    const int rc = orbx_keyframe_count(kf, &n);   // at most one synchronisation, then cached
+    if (rc != ORBX_OK) return rc;
+    if (n_left) *n_left = kf->fisheye ? kf->n_left.load() : n;
+    if (n_right) *n_right = kf->fisheye ? kf->n_right.load() : -1;
+    return ORBX_OK;
+}
+
 // orbx_fuse_search for n_kf resident key frames, each with its own query set, in one call: one upload run, k_window_best1_kf over all problems, one
-// download run, one synchronisation.
-int orbx_keyframe_fuse_search(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fuse_queries *queries, int use_chi2, int strict_fp,
-                              int32_t *const *best_idx, int32_t *const *best_dist) {
+// download run, one synchronisation.  fisheye: every key frame is two problems (left camera, right camera), queries / rows [n_kf][2]; a right-camera
+// index comes back in the rig's numbering (N_left + j, ORBmatcher.cc:1296) -- where N_left is still on the device it comes home with the results.
+static int keyframe_fuse_search_impl(orbx_matcher *m, bool fisheye, int n_kf, orbx_keyframe *const *kfs, const orbx_fuse_queries *queries, int use_chi2,
+                                     int strict_fp, int32_t *const *best_idx, int32_t *const *best_dist) {
     if (!m || n_kf < 0 || (n_kf > 0 && (!kfs || !queries || !best_idx || !best_dist))) return ORBX_E_BAD_ARG;
     if (n_kf > ORBX_MAX_FUSE_KEYFRAMES) return ORBX_E_TOO_LARGE;
+    const int sides = fisheye ? 2 : 1, np = n_kf * sides;   // problem p: key frame p / sides, camera p % sides
     size_t total = 0;
     int nq_max = 0;
-    for (int k = 0; k < n_kf; k++) {
-        const orbx_fuse_queries &q = queries[k];
-        if (!kfs[k] || kfs[k]->device != m->device || q.n < 0 || (use_chi2 && !kfs[k]->inv_sigma2)) return ORBX_E_BAD_ARG;
-        if (q.n > 0 && (!q.u || !q.v || !q.r || !q.level || !q.desc || !best_idx[k] || !best_dist[k])) return ORBX_E_BAD_ARG;
+    for (int p = 0; p < np; p++) {
+        const orbx_fuse_queries &q = queries[p];
+        const orbx_keyframe *kf = kfs[p / sides];
+        if (!kf || kf->fisheye != fisheye || kf->device != m->device || q.n < 0 || (use_chi2 && !kf->inv_sigma2)) return ORBX_E_BAD_ARG;
+        if (q.n > 0 && (!q.u || !q.v || !q.r || !q.level || !q.desc || !best_idx[p] || !best_dist[p])) return ORBX_E_BAD_ARG;
         total += (size_t)q.n;
         nq_max = std::max(nq_max, q.n);
     }
-    for (int k = 0; k < n_kf; k++)
-        for (int i = 0; i < queries[k].n; i++) { best_idx[k][i] = -1; best_dist[k][i] = 256; }
+    for (int p = 0; p < np; p++)
+        for (int i = 0; i < queries[p].n; i++) { best_idx[p][i] = -1; best_dist[p][i] = 256; }
     if (total == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
-    std::vector<KfProblem> R((size_t)n_kf);
-    std::vector<int32_t> cnts((size_t)n_kf), lv(total);
-    std::vector<size_t> off((size_t)n_kf);
+    std::vector<KfProblem> R((size_t)np);
+    std::vector<int32_t> cnts((size_t)np), lv(total);
+    std::vector<size_t> off((size_t)np);
     size_t o = 0;
-    for (int k = 0; k < n_kf; k++) {
-        const orbx_fuse_queries &q = queries[k];
-        keyframe_problem(kfs[k], use_chi2 != 0, strict_fp, &R[k]);
-        cnts[k] = q.n; off[k] = o;
+    for (int p = 0; p < np; p++) {
+        const orbx_fuse_queries &q = queries[p];
+        keyframe_problem(kfs[p / sides], use_chi2 != 0, strict_fp, &R[p], p % sides == 1);
+        cnts[p] = q.n; off[p] = o;
         for (int i = 0; i < q.n; i++) lv[o + (size_t)i] = q.level[i] - 1;   // kpLevel<nPredictedLevel-1 || kpLevel>nPredictedLevel
         o += (size_t)q.n;
     }
@@ -2667,34 +2714,49 @@ int orbx_keyframe_fuse_search(orbx_matcher *m, int n_kf, orbx_keyframe *const *k
     KfProblem *dR;
     u64 *dkeys;
     ORBX_TRY(m->carve([&](Carve &A) {
-        for (int k = 0; k < n_kf; k++) {   // the inputs of every problem, adjacent in the arena: one upload run
-            const orbx_fuse_queries &q = queries[k];
+        for (int p = 0; p < np; p++) {   // the inputs of every problem, adjacent in the arena: one upload run
+            const orbx_fuse_queries &q = queries[p];
             const size_t nq = (size_t)q.n;
             if (nq == 0) continue;
-            WindowProblem &P = R[k].P;
+            WindowProblem &P = R[p].P;
             P.qx = A.up(q.u, nq); P.qy = A.up(q.v, nq); P.qr = A.up(q.r, nq);
-            P.qmin = A.up(lv.data() + off[k], nq); P.qmax = A.up(q.level, nq);
+            P.qmin = A.up(lv.data() + off[p], nq); P.qmax = A.up(q.level, nq);
             if (P.u_right) P.qxr = A.up_opt(q.ur, nq);
             P.qdesc = A.up(q.desc, 32 * nq);
         }
-        dcnt = A.up(cnts.data(), (size_t)n_kf);
-        dR = A.take<KfProblem>(n_kf);
+        dcnt = A.up(cnts.data(), (size_t)np);
+        dR = A.take<KfProblem>(np);
         dkeys = A.take<u64>(total);
     }));
-    for (int k = 0; k < n_kf; k++) { R[k].P.nq_ptr = dcnt + k; R[k].P.keys = dkeys + off[k]; }
-    ORBX_TRY(m->h2d(dR, R.data(), sizeof(KfProblem) * (size_t)n_kf));
+    for (int p = 0; p < np; p++) { R[p].P.nq_ptr = dcnt + p; R[p].P.keys = dkeys + off[p]; }
+    ORBX_TRY(m->h2d(dR, R.data(), sizeof(KfProblem) * (size_t)np));
     ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
-    launch_window_best1_kf(m->exec(), dR, nq_max, n_kf);
+    launch_window_best1_kf(m->exec(), dR, nq_max, np);
     std::vector<u64> keys(total);
     ORBX_TRY(m->d2h(keys.data(), dkeys, 8 * total));
+    std::vector<int32_t> pend;   // the counts of fisheye key frames that still have them on the device: home with the results
+    ORBX_TRY(keyframe_fetch_counts(m, fisheye, n_kf, kfs, &pend));
     ORBX_TRY(m->sync_and_deliver());
     keyframe_release(kfs, n_kf);
-    for (int k = 0; k < n_kf; k++)
-        for (int i = 0; i < queries[k].n; i++) {
-            const u64 key = keys[off[k] + (size_t)i];
-            if (key != kNoKey) { best_idx[k][i] = (int32_t)(key & 0xffff); best_dist[k][i] = (int32_t)(key >> 32); }
+    keyframe_take_counts(fisheye, n_kf, kfs, pend);
+    for (int p = 0; p < np; p++) {
+        const int base = p % sides == 1 ? kfs[p / sides]->n_left.load() : 0;
+        for (int i = 0; i < queries[p].n; i++) {
+            const u64 key = keys[off[p] + (size_t)i];
+            if (key != kNoKey) { best_idx[p][i] = base + (int32_t)(key & 0xffff); best_dist[p][i] = (int32_t)(key >> 32); }
         }
+    }
     return ORBX_OK;
+}
+
+int orbx_keyframe_fuse_search(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fuse_queries *queries, int use_chi2, int strict_fp,
+                              int32_t *const *best_idx, int32_t *const *best_dist) {
+    return keyframe_fuse_search_impl(m, false, n_kf, kfs, queries, use_chi2, strict_fp, best_idx, best_dist);
+}
+
+int orbx_keyframe_fuse_search_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fuse_queries *queries, int use_chi2, int strict_fp,
+                                      int32_t *const *best_idx, int32_t *const *best_dist) {
+    return keyframe_fuse_search_impl(m, true, n_kf, kfs, queries, use_chi2, strict_fp, best_idx, best_dist);
 }
 
 // LocalMapping::SearchInNeighbors' Fuse loop in one call: k_fuse_project writes the query records of every (key frame, map point) into the arena,
@@ -2708,7 +2770,7 @@ int orbx_keyframe_fuse_map_points(orbx_matcher *m, int n_kf, orbx_keyframe *cons
     const size_t np = (size_t)n_mp, total = (size_t)n_kf * np;
     if (total > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !best_idx || !best_dist)) return ORBX_E_BAD_ARG;
     for (int k = 0; k < n_kf; k++)
-        if (!kfs[k] || kfs[k]->device != m->device || !kfs[k]->inv_sigma2) return ORBX_E_BAD_ARG;
+        if (!kfs[k] || kfs[k]->fisheye || kfs[k]->device != m->device || !kfs[k]->inv_sigma2) return ORBX_E_BAD_ARG;
     if (total == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
     const int32_t cnt4[4] = {n_mp, 0, 0, 0};
@@ -2757,6 +2819,155 @@ int orbx_keyframe_fuse_map_points(orbx_matcher *m, int n_kf, orbx_keyframe *cons
         const u64 key = keys[i];
         best_idx[i] = key == kNoKey ? -1 : (int32_t)(key & 0xffff);
         best_dist[i] = key == kNoKey ? 256 : (int32_t)(key >> 32);
+    }
+    return ORBX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Fisheye-stereo key frames (KeyFrame::NLeft != -1): the object and SearchInNeighbors' two Fuse calls per target -- Fuse(pKFi, vpMapPointMatches) and
+// Fuse(pKFi, vpMapPointMatches, true) -- for every target in one call.
+// ---------------------------------------------------------------------------------------------------------
+int orbx_keyframe_create_host_fisheye(orbx_matcher *m, const orbx_frame_desc *left, const orbx_keypoint *kps_right, int n_right,
+                                      const float *inv_level_sigma2, orbx_keyframe **out) {
+    if (out) *out = nullptr;
+    if (!m || !out || !left || left->n < 0 || n_right < 0 || (left->n > 0 && !left->keypoints_un) || (n_right > 0 && !kps_right) ||
+        (left->n + n_right > 0 && !left->descriptors) || !left->scale_factors || left->nlevels < 1 || left->nlevels > kFrameMaxLevels)
+        return ORBX_E_BAD_ARG;
+    if ((int64_t)left->n + n_right > 65535) return ORBX_E_TOO_LARGE;   // 16-bit grid entries, as orbx_fuse_search
+    ORBX_HIP(hipSetDevice(m->device));
+    const int nl = left->n, nr = n_right, N = nl + nr, nlv = left->nlevels;
+    const float b[4] = {left->min_x, left->max_x, left->min_y, left->max_y};
+    orbx_keyframe *kf = nullptr;
+    int r = keyframe_alloc(m->device, N, false, inv_level_sigma2 != nullptr, nlv, b, &kf, nl);
+    if (r != ORBX_OK) return r;
+    // ONE upload, as orbx_keyframe_create_host: mvKeys and mvKeysRight one behind the other (roff = N_left), all N descriptor rows, inv_sigma2
+    const size_t up_end = (size_t)((inv_level_sigma2 ? (uint8_t *)(kf->inv_sigma2 + nlv) : kf->desc + 32 * (size_t)N) - kf->dev);
+    r = m->reserve_staging(up_end);
+    if (r != ORBX_OK) { orbx_keyframe_destroy(kf); return r; }
+    if (N > 0 || inv_level_sigma2) {
+        uint8_t *st = static_cast<uint8_t *>(m->stage.take(up_end + 16));
+        if (!st) { set_error("staging arena exhausted"); orbx_keyframe_destroy(kf); return ORBX_E_INTERNAL; }
+        memset(st, 0, up_end + 16);
+        const size_t o_kps = (size_t)((uint8_t *)kf->kps - kf->dev);
+        if (nl) memcpy(st + o_kps, left->keypoints_un, 28 * (size_t)nl);
+        if (nr) memcpy(st + o_kps + 28 * (size_t)nl, kps_right, 28 * (size_t)nr);
+        if (N) memcpy(st + (kf->desc - kf->dev), left->descriptors, 32 * (size_t)N);
+        if (inv_level_sigma2) memcpy(st + ((uint8_t *)kf->inv_sigma2 - kf->dev), inv_level_sigma2, 4 * (size_t)nlv);
+        m->dirty = true;
+        const orbx_matcher::Span run = {0, up_end};
+        if ((r = m->upload_ranges(kf->dev, st, &run, 1)) != ORBX_OK) { orbx_keyframe_destroy(kf); return r; }
+    }
+    FisheyePrepare P;   // k_frame_prepare_fisheye's in-place form (as orbx_frame_load_host_fisheye): counts, scale factors, one grid per camera
+    memset(&P, 0, sizeof(P));
+    P.n_host[0] = nl; P.n_host[1] = nr; P.cap_side[0] = nl; P.cap_side[1] = nr;
+    P.kps = kf->kps; P.desc = kf->desc; P.count = kf->count; P.scale = kf->scale;
+    P.gstart[0] = kf->gstart; P.gorder[0] = kf->gorder; P.gstart[1] = kf->gstart_r; P.gorder[1] = kf->gorder_r;
+    P.roff = nl; P.nlevels = nlv;
+    memcpy(P.scale_host, left->scale_factors, sizeof(float) * (size_t)nlv);
+    m->dirty = true;
+    hipLaunchKernelGGL(k_frame_prepare_fisheye, dim3(2), dim3(64), 0, m->stream, P, grid_of(kf->bounds));
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(kf->ready, m->stream);
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
+    kf->n_left.store(nl); kf->n_right.store(nr); kf->n.store(N);
+    *out = kf;
+    return ORBX_OK;
+}
+
+int orbx_keyframe_from_frame_fisheye(orbx_matcher *m, orbx_frame *f, const float *inv_level_sigma2, orbx_keyframe **out) {
+    if (out) *out = nullptr;
+    if (!m || !out || !f || f->owner != m || !f->loaded || !f->fisheye) return ORBX_E_BAD_ARG;
+    ORBX_HIP(hipSetDevice(m->device));
+    const int cap_l = f->rows_left(), cap_r = f->rows_right();   // sized by the counts where the host knows them
+    orbx_keyframe *kf = nullptr;
+    int r = keyframe_alloc(m->device, cap_l + cap_r, false, inv_level_sigma2 != nullptr, f->nlevels, f->bounds, &kf, cap_l);
+    if (r != ORBX_OK) return r;
+    KeyFrameCopyFisheye C;
+    memset(&C, 0, sizeof(C));
+    C.src_kps = f->kps; C.src_desc = f->desc; C.src_count = f->count; C.src_scale = f->scale;
+    C.src_gstart_l = f->gstart; C.src_gorder_l = f->gorder; C.src_gstart_r = f->gstart_r; C.src_gorder_r = f->gorder_r;
+    C.kps = kf->kps; C.desc = kf->desc; C.count = kf->count; C.scale = kf->scale; C.inv_sigma2 = kf->inv_sigma2;
+    C.gstart_l = kf->gstart; C.gorder_l = kf->gorder; C.gstart_r = kf->gstart_r; C.gorder_r = kf->gorder_r;
+    C.src_roff = f->roff; C.roff = cap_l; C.cap_l = cap_l; C.cap_r = cap_r; C.nlevels = f->nlevels;
+    if (inv_level_sigma2) memcpy(C.inv_sigma2_host, inv_level_sigma2, sizeof(float) * (size_t)f->nlevels);
+    // on the owner's stream: behind the frame's load, ahead of its next one -- no host synchronisation
+    m->dirty = true;
+    hipLaunchKernelGGL(k_keyframe_copy_fisheye, dim3(2 + (unsigned)((std::max(cap_l, cap_r) + 255) / 256)), dim3(64), 0, m->stream, C);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(kf->ready, m->stream);
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
+    kf->n_left.store(f->host_left()); kf->n_right.store(f->host_right()); kf->n.store(f->host_n());
+    *out = kf;
+    return ORBX_OK;
+}
+
+// Both Fuse calls of LocalMapping::SearchInNeighbors' loop for every target of a rig in one call: k_fuse_project_kb8 writes the query records of every
+// (key frame, camera, map point) into the arena, k_window_best1_kf searches the 2 n_kf problems -- the records never visit the host, the map points go
+// up once.
+int orbx_keyframe_fuse_map_points_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views, float th,
+                                          float log_scale_factor, int strict_fp, int n_mp, const float *pos, const float *normal, const float *min_dist,
+                                          const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
+                                          uint8_t *projected) {
+    if (!m || n_kf < 0 || n_mp < 0 || (n_kf > 0 && (!kfs || !views))) return ORBX_E_BAD_ARG;
+    if (n_kf > ORBX_MAX_FUSE_KEYFRAMES) return ORBX_E_TOO_LARGE;
+    const int nprob = 2 * n_kf;
+    const size_t np = (size_t)n_mp, total = (size_t)nprob * np;
+    if (total > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !best_idx || !best_dist)) return ORBX_E_BAD_ARG;
+    for (int k = 0; k < n_kf; k++)
+        if (!kfs[k] || !kfs[k]->fisheye || kfs[k]->device != m->device || !kfs[k]->inv_sigma2) return ORBX_E_BAD_ARG;
+    if (total == 0) return ORBX_OK;
+    ORBX_HIP(hipSetDevice(m->device));
+    static_assert(sizeof(FisheyeView) == sizeof(orbx_fisheye_view), "orbx_fisheye_view layout");
+    const int32_t cnt4[4] = {n_mp, 0, 0, 0};
+    float *dp, *dn, *dmn, *dmx, *qx, *qy, *qr;
+    uint8_t *dd, *dskip, *qvalid;
+    int32_t *dcnt, *qmin, *qmax;
+    FisheyeView *dview;
+    KfProblem *dR;
+    u64 *dkeys;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        // uploads, adjacent in the arena (one run): the map points ONCE, then what grows with n_kf -- two views, two problem records, one skip row each
+        dp = A.up(pos, 3 * np); dn = A.up(normal, 3 * np); dmn = A.up(min_dist, np); dmx = A.up(max_dist, np);
+        dd = A.up(mp_desc, 32 * np);
+        dcnt = A.up(cnt4, 4);
+        dview = A.up(reinterpret_cast<const FisheyeView *>(views), (size_t)nprob);
+        dR = A.take<KfProblem>(nprob);
+        dskip = A.up_opt(skip, (size_t)n_kf * np);
+        // written by k_fuse_project_kb8, read by k_window_best1_kf
+        qx = A.take<float>(total); qy = A.take<float>(total); qr = A.take<float>(total);
+        qmin = A.take<int32_t>(total); qmax = A.take<int32_t>(total);
+        qvalid = A.take<uint8_t>(total);
+        dkeys = A.take<u64>(total);
+    }));
+    std::vector<KfProblem> R((size_t)nprob);
+    for (int p = 0; p < nprob; p++) {
+        keyframe_problem(kfs[p >> 1], true, strict_fp, &R[p], (p & 1) != 0);
+        WindowProblem &P = R[p].P;
+        const size_t o = (size_t)p * np;
+        P.qx = qx + o; P.qy = qy + o; P.qr = qr + o; P.qmin = qmin + o; P.qmax = qmax + o; P.qvalid = qvalid + o;
+        P.qdesc = dd; P.nq_ptr = dcnt; P.keys = dkeys + o;
+    }
+    ORBX_TRY(m->h2d(dR, R.data(), sizeof(KfProblem) * (size_t)nprob));
+    ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
+    hipLaunchKernelGGL(k_fuse_project_kb8, dim3((unsigned)((n_mp + 255) / 256), (unsigned)nprob), dim3(256), 0, m->exec(), (const KfProblem *)dR,
+                       (const FisheyeView *)dview, th, log_scale_factor, n_mp, (const float *)dp, (const float *)dn, (const float *)dmn,
+                       (const float *)dmx, (const uint8_t *)dskip, qx, qy, qr, qmin, qmax, qvalid);
+    launch_window_best1_kf(m->exec(), dR, n_mp, nprob);
+    std::vector<u64> keys(total);
+    if (projected) ORBX_TRY(m->d2h(projected, qvalid, total));   // (adjacent to the keys: one download run)
+    ORBX_TRY(m->d2h(keys.data(), dkeys, 8 * total));
+    std::vector<int32_t> pend;
+    ORBX_TRY(keyframe_fetch_counts(m, true, n_kf, kfs, &pend));
+    ORBX_TRY(m->sync_and_deliver());
+    keyframe_release(kfs, n_kf);
+    keyframe_take_counts(true, n_kf, kfs, pend);
+    for (int p = 0; p < nprob; p++) {
+        const int base = (p & 1) ? kfs[p >> 1]->n_left.load() : 0;   // the rig's numbering (ORBmatcher.cc:1296)
+        for (size_t i = (size_t)p * np; i < (size_t)(p + 1) * np; i++) {
+            const u64 key = keys[i];
+            best_idx[i] = key == kNoKey ? -1 : base + (int32_t)(key & 0xffff);
+            best_dist[i] = key == kNoKey ? 256 : (int32_t)(key >> 32);
+        }
     }
     return ORBX_OK;
 }
@@ -2942,7 +3153,7 @@ int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const 
 
 // a key frame a BoW search may take: on this device, with BoW; the vocabulary and levelsup it was made with come back for the cross-check
 inline bool keyframe_bow_ok(const orbx_matcher *m, const orbx_keyframe *kf, const orbx_vocabulary **voc, int *levelsup) {
-    if (!kf || kf->device != m->device) return false;
+    if (!kf || kf->fisheye || kf->device != m->device) return false;
     const KeyFrameBow *b = kf->bow.load(std::memory_order_acquire);
     if (!b) return false;
     if (*voc && (*voc != b->voc || *levelsup != b->levelsup)) return false;
@@ -2958,7 +3169,7 @@ extern "C" {
 // (k_frame_bow_transform, k_frame_featvec): they take every array as an argument, so they run on the key frame's rows as they are -- no new code object,
 // no existing kernel's ISA touched.
 int orbx_keyframe_compute_bow(orbx_matcher *m, orbx_keyframe *kf, const orbx_vocabulary *v, int levelsup, int32_t *word_id, int32_t *node_id) {
-    if (!m || !kf || !v || kf->device != m->device || v->device != m->device) return ORBX_E_BAD_ARG;
+    if (!m || !kf || !v || kf->fisheye || kf->device != m->device || v->device != m->device) return ORBX_E_BAD_ARG;
     KeyFrameBow *b = kf->bow.load(std::memory_order_acquire);
     const bool down = word_id || node_id;
     if (b) {   // `if (mBowVec.empty() || mFeatVec.empty())`: not computed again
@@ -3012,7 +3223,7 @@ int orbx_keyframe_compute_bow(orbx_matcher *m, orbx_keyframe *kf, const orbx_voc
 // mBowVec(F.mBowVec), mFeatVec(F.mFeatVec) of KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-82): k_keyframe_bow_copy on the owner's stream, behind the
 // frame's orbx_frame_compute_bow and ahead of its next load; no host synchronisation.
 int orbx_keyframe_bow_from_frame(orbx_matcher *m, orbx_keyframe *kf, orbx_frame *f) {
-    if (!m || !kf || !f || f->owner != m || f->fisheye || kf->device != m->device || kf->src_frame != f) return ORBX_E_BAD_ARG;
+    if (!m || !kf || !f || f->owner != m || f->fisheye || kf->fisheye || kf->device != m->device || kf->src_frame != f) return ORBX_E_BAD_ARG;
     if (kf->bow.load(std::memory_order_acquire)) return ORBX_E_BAD_ARG;   // set once
     if (f->load_seq != kf->src_seq) return ORBX_E_STALE;                  // the handle holds another frame by now
     if (!f->bow_valid) return ORBX_E_BAD_ARG;

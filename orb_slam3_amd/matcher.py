@@ -157,7 +157,9 @@ class DeviceKeyFrame:
     """An immutable key frame resident on the device (orbx_keyframe, include/orbx.h): what KeyFrame::KeyFrame(Frame&) copies of the frame --
     mvKeysUn, descriptors, optional mvuRight, scale factors, mvInvLevelSigma2, the bounds and the 64x48 grid.  It belongs to no matcher: every
     ORBmatcher of the same device may search it (FuseSearchKeyFrames / FuseMapPoints), from any thread.  close() (or garbage collection) frees it;
-    no call that was handed the key frame may be running then."""
+    no call that was handed the key frame may be running then.
+    A fisheye-stereo key frame (from_frame_fisheye / from_host_fisheye) holds mvKeys, mvKeysRight, all N descriptor rows, both counts and a grid per
+    camera; FuseSearchKeyFramesFisheye / FuseMapPointsFisheye search it, the other key-frame calls refuse it."""
 
     def __init__(self, handle):
         self._L = _lib.lib()
@@ -181,10 +183,37 @@ class DeviceKeyFrame:
         check(_lib.lib().orbx_keyframe_create_host(matcher._h, C.byref(fd), ptr(isg), C.byref(h)), "orbx_keyframe_create_host")   # (staged before it returns)
         return cls(h)
 
+    @classmethod
+    def from_frame_fisheye(cls, matcher: "ORBmatcher", frame: "DeviceFrame", inv_level_sigma2=None) -> "DeviceKeyFrame":
+        """Device-to-device copy of a loaded fisheye-stereo DeviceFrame of `matcher` (orbx_keyframe_from_frame_fisheye): both cameras' rows, both
+        counts and both grids; asynchronous, also while the counts are still on the device; the frame may be reloaded right away."""
+        isg = _f32(inv_level_sigma2)
+        h = C.c_void_p()
+        check(_lib.lib().orbx_keyframe_from_frame_fisheye(matcher._h, frame._h, ptr(isg), C.byref(h)), "orbx_keyframe_from_frame_fisheye")
+        return cls(h)
+
+    @classmethod
+    def from_host_fisheye(cls, matcher: "ORBmatcher", left: "FrameView", kps_right, inv_level_sigma2=None) -> "DeviceKeyFrame":
+        """A fisheye-stereo key frame from host arrays (orbx_keyframe_create_host_fisheye): left.keypoints_un = mvKeys, left.descriptors = ALL
+        N_left + N_right rows, kps_right = mvKeysRight.  One upload, a grid per camera."""
+        isg = _f32(inv_level_sigma2)
+        kr = np.ascontiguousarray(kps_right, KP_DTYPE)
+        fd = left.c_struct()
+        h = C.c_void_p()
+        check(_lib.lib().orbx_keyframe_create_host_fisheye(matcher._h, C.byref(fd), ptr(kr), len(kr), ptr(isg), C.byref(h)),
+              "orbx_keyframe_create_host_fisheye")   # (staged before it returns)
+        return cls(h)
+
     def count(self) -> int:
         n = C.c_int(0)
         check(self._L.orbx_keyframe_count(self._h, C.byref(n)), "orbx_keyframe_count")
         return n.value
+
+    def counts(self):
+        """(N_left, N_right); N_right = -1 for a monocular / rectified key frame (orbx_keyframe_counts)."""
+        nl, nr = C.c_int(0), C.c_int(0)
+        check(self._L.orbx_keyframe_counts(self._h, C.byref(nl), C.byref(nr)), "orbx_keyframe_counts")
+        return nl.value, nr.value
 
     def compute_bow(self, matcher: "ORBmatcher", voc: "ORBVocabulary", levelsup: int = 4, download: bool = True, cap: int | None = None):
         """KeyFrame::ComputeBoW on the resident descriptors (orbx_keyframe_compute_bow): the key frame keeps its FeatureVector for
@@ -824,6 +853,53 @@ class ORBmatcher:
         pd = (vp * max(K, 1))(*[ptr(x) for x in bd])
         check(self._L.orbx_keyframe_fuse_search(self._h, K, hs, qs, int(bool(use_chi2)), int(bool(strict_fp)), pi, pd), "orbx_keyframe_fuse_search")
         return list(zip(bi, bd))
+
+    def FuseSearchKeyFramesFisheye(self, kfs, queries, use_chi2: bool = True, strict_fp: bool = False):
+        """FuseSearchKeyFrames for K fisheye-stereo DeviceKeyFrames (orbx_keyframe_fuse_search_fisheye).  queries[k] = (left set, right set), each a
+        dict(u, v, r, level, desc).  Returns [((best_idx, best_dist) left, (best_idx, best_dist) right)] per key frame; a right-camera index is
+        N_left + j."""
+        K = len(kfs)
+        assert len(queries) == K and all(len(q) == 2 for q in queries)
+        keep, qs = [], (FuseQueries * max(2 * K, 1))()
+        bi, bd = [], []
+        for p, q in enumerate(q for pair in queries for q in pair):
+            nq = len(q["u"])
+            a = [_f32(q["u"]), _f32(q["v"]), None, _f32(q["r"]), _i32(q["level"]), _u8(q["desc"])]
+            keep.append(a)
+            qs[p] = FuseQueries(nq, *[None if (x is None or nq == 0) else x.ctypes.data for x in a])
+            bi.append(np.zeros(nq, np.int32))
+            bd.append(np.zeros(nq, np.int32))
+        vp = C.c_void_p
+        hs = (vp * max(K, 1))(*[kf._h.value if isinstance(kf._h, vp) else kf._h for kf in kfs])
+        pi = (vp * max(2 * K, 1))(*[ptr(x) for x in bi])
+        pd = (vp * max(2 * K, 1))(*[ptr(x) for x in bd])
+        check(self._L.orbx_keyframe_fuse_search_fisheye(self._h, K, hs, qs, int(bool(use_chi2)), int(bool(strict_fp)), pi, pd),
+              "orbx_keyframe_fuse_search_fisheye")
+        return [((bi[2 * k], bd[2 * k]), (bi[2 * k + 1], bd[2 * k + 1])) for k in range(K)]
+
+    def FuseMapPointsFisheye(self, kfs, views, map_points: dict, th: float = 3.0, log_scale_factor: float = 0.0, skip=None,
+                             strict_fp: bool = False, want_projected: bool = True):
+        """Both Fuse calls of LocalMapping::SearchInNeighbors' loop on a rig, for K fisheye-stereo DeviceKeyFrames in one call, projection included
+        (orbx_keyframe_fuse_map_points_fisheye).  views[k] = (left, right), each (R, t, twc, params8) as isInFrustumChecks takes them: GetPose() /
+        GetCameraCenter() / mpCamera and GetRightPose() / GetRightCameraCenter() / mpCamera2.  map_points as FuseMapPoints; skip [K, n] or None.
+        Returns (best_idx [K, 2, n] in the rig's numbering, best_dist [K, 2, n], projected [K, 2, n] or None)."""
+        K = len(kfs)
+        assert len(views) == K
+        P, Nn = _f32(np.asarray(map_points["pos"]).reshape(-1, 3)), _f32(np.asarray(map_points["normal"]).reshape(-1, 3))
+        mn, mx, d = _f32(map_points["min_dist"]), _f32(map_points["max_dist"]), _u8(map_points["desc"])
+        n = len(P)
+        sk = None if skip is None else _u8(np.asarray(skip).reshape(K, n))
+        V = np.zeros(46 * max(K, 1), np.float32)
+        for k, pair in enumerate(views):
+            V[46 * k:46 * (k + 1)] = np.concatenate([np.asarray(x, np.float32).ravel() for cam in pair for x in cam])
+        vp = C.c_void_p
+        hs = (vp * max(K, 1))(*[kf._h.value if isinstance(kf._h, vp) else kf._h for kf in kfs])
+        bi, bd = np.full((K, 2, n), -1, np.int32), np.full((K, 2, n), 256, np.int32)
+        pr = np.zeros((K, 2, n), np.uint8) if want_projected else None
+        check(self._L.orbx_keyframe_fuse_map_points_fisheye(self._h, K, hs, ptr(V), float(th), float(log_scale_factor), int(bool(strict_fp)), n, ptr(P),
+                                                            ptr(Nn), ptr(mn), ptr(mx), ptr(d), ptr(sk), ptr(bi), ptr(bd), ptr(pr)),
+              "orbx_keyframe_fuse_map_points_fisheye")
+        return bi, bd, pr
 
     def FuseMapPoints(self, kfs, cams, poses, map_points: dict, th: float = 3.0, log_scale_factor: float = 0.0, skip=None,
                       strict_fp: bool = False, want_projected: bool = True):

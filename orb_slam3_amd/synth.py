@@ -342,3 +342,97 @@ def make_fuse_scene(rng, n_kf: int = 20, n_mp: int = 1000, outliers: bool = True
         kfs.append(dict(kps=np.ascontiguousarray(kp[perm]), desc=np.ascontiguousarray(d[perm]), u_right=np.ascontiguousarray(ur[perm])))
     return dict(cams=cams, poses=poses, bounds=b, scale_factors=sf, inv_level_sigma2=(f32(1.0) / (sf * sf)).astype(f32), log_scale_factor=log_sf,
                 map_points=dict(pos=pos, normal=normal, min_dist=min_d, max_dist=max_d, desc=mp_desc), key_frames=kfs)
+
+
+def make_fisheye_fuse_scene(rng, n_kf: int = 20, n_mp: int = 1000, outliers: bool = True, n_clutter=300, bounds=(0.0, 512.0, 0.0, 512.0),
+                            nlevels: int = 8, scale_factor: float = 1.2):
+    """make_fuse_scene for a fisheye-stereo rig: n_mp map points seen from n_kf covisible TUM-VI-like rigs (TUMVI_L / TUMVI_R, the baseline of
+    make_fisheye_keyframes; key frame 0's left camera has the identity pose).  Map points: x, y within 4 m, z in 1 .. 8 m of key frame 0, with
+    make_fuse_scene's six populations -- the x-outliers scaled by 6, not 2.5: a 512 x 512 fisheye image sees far more of the half space than a pinhole
+    one.  Each camera's features sit at 70 % of the map points' projections into it (0.8 px noise, 2 - 25 % flipped descriptor bits, octave = the level
+    the distance predicts) plus clutter; n_clutter: one number or (left, right).  bounds: one (minX, maxX, minY, maxY) for all key frames or one per
+    key frame.  Feature placement uses a plain float64 projection: the exact gates are the caller's (or the library's) business.
+    Returns dict(views [n_kf] of (left, right), each (R, t, twc, params8) float32 as orbx_fisheye_view -- GetPose() / GetCameraCenter() / mpCamera and
+    GetRightPose() / GetRightCameraCenter() / mpCamera2 --, bounds [n_kf, 4], scale_factors, inv_level_sigma2, log_scale_factor, map_points
+    dict(pos, normal, min_dist, max_dist, desc), key_frames [n_kf] dict(kps_left, kps_right KP_DTYPE, desc [N_left + N_right, 32]), trl (Rrl, trl))."""
+    from ._lib import KP_DTYPE
+    f32 = np.float32
+    sf = (f32(scale_factor) ** np.arange(nlevels)).astype(f32)
+    log_sf = float(np.log(f32(scale_factor)))
+    b = np.broadcast_to(np.asarray(bounds, f32).reshape(-1, 4), (n_kf, 4)).copy()
+    ncl = (int(n_clutter),) * 2 if np.isscalar(n_clutter) else tuple(int(x) for x in n_clutter)
+
+    def rodrigues(w):
+        th = np.linalg.norm(w)
+        K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]]) / max(th, 1e-12)
+        return np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * K @ K
+    Rrl, trl = rodrigues(rng.uniform(-0.01, 0.01, 3)).astype(f32), np.array([-0.101, 0.002, 0.001], f32)   # right camera from left camera
+    tlr = -Rrl.astype(np.float64).T @ trl.astype(np.float64)                                                # mTlr.translation()
+    pos = np.stack([rng.uniform(-4, 4, n_mp), rng.uniform(-4, 4, n_mp), rng.uniform(1.0, 8.0, n_mp)], axis=1)
+    ref_dist = np.linalg.norm(pos, axis=1)
+    ref_level = rng.integers(0, nlevels - 1, n_mp)
+    max_d = ref_dist * sf[ref_level].astype(np.float64) * rng.uniform(0.95, 1.05, n_mp)
+    min_d = max_d / float(sf[-1])
+    normal = pos / ref_dist[:, None] + rng.normal(0, 0.15, pos.shape)
+    normal = normal / np.linalg.norm(normal, axis=1, keepdims=True)
+    if outliers:
+        kind = rng.choice(6, n_mp, p=[0.66, 0.08, 0.08, 0.04, 0.04, 0.10])
+        pos[kind == 1] *= -1.0
+        pos[kind == 2, 0] *= 6.0
+        max_d[kind == 3] *= 0.3
+        min_d[kind == 3] = max_d[kind == 3] / float(sf[-1])
+        min_d[kind == 4] = 2.0 * max_d[kind == 4]
+        rn = rng.normal(0, 1, (int((kind == 5).sum()), 3))
+        normal[kind == 5] = rn / np.linalg.norm(rn, axis=1, keepdims=True)
+    mp_desc = rng.integers(0, 256, (n_mp, 32), dtype=np.uint8)
+    pos, normal, min_d, max_d = pos.astype(f32), normal.astype(f32), min_d.astype(f32), max_d.astype(f32)
+
+    def proj(prm, X):   # KannalaBrandt8::project in float64
+        th = np.arctan2(np.hypot(X[:, 0], X[:, 1]), X[:, 2]); psi = np.arctan2(X[:, 1], X[:, 0])
+        r = th + prm[4] * th ** 3 + prm[5] * th ** 5 + prm[6] * th ** 7 + prm[7] * th ** 9
+        return prm[0] * r * np.cos(psi) + prm[2], prm[1] * r * np.sin(psi) + prm[3]
+    views, kfs = [], []
+    for k in range(n_kf):
+        if k == 0:
+            R, t = np.eye(3), np.zeros(3)
+        else:
+            R, t = rodrigues(rng.normal(0, 0.035, 3)), rng.normal(0, 0.3, 3)
+        Rcw, tcw = R.astype(f32), t.astype(f32)
+        R64, t64 = Rcw.astype(np.float64), tcw.astype(np.float64)
+        Ow = -R64.T @ t64
+        Rr = (Rrl.astype(np.float64) @ R64).astype(f32)                                   # GetRightPose() = mTrl * mTcw
+        tr = (Rrl.astype(np.float64) @ t64 + trl.astype(np.float64)).astype(f32)
+        Owr = (R64.T @ tlr + Ow).astype(f32)                                              # GetRightCameraCenter() = mRwc * mTlr.translation() + mOw
+        pair = ((Rcw, tcw, Ow.astype(f32), np.array(TUMVI_L, f32)), (Rr, tr, Owr, np.array(TUMVI_R, f32)))
+        views.append(pair)
+        parts, descs = [], []
+        for s, (Rs, ts, Os, prm) in enumerate(pair):
+            pc = pos.astype(np.float64) @ Rs.astype(np.float64).T + ts
+            uu, vv = proj(prm.astype(np.float64), pc)
+            d3 = np.linalg.norm(pos.astype(np.float64) - Os, axis=1)
+            vis = (pc[:, 2] > 0) & (uu > b[k, 0] + 2) & (uu < b[k, 1] - 2) & (vv > b[k, 2] + 2) & (vv < b[k, 3] - 2)
+            sel = np.nonzero(vis & (rng.random(n_mp) < 0.7))[0]
+            with np.errstate(divide="ignore", invalid="ignore"):
+                lvl = np.clip(np.ceil(np.log(max_d[sel].astype(np.float64) / d3[sel]) / log_sf), 0, nlevels - 1).astype(np.int32)
+            lvl = np.where(rng.random(len(sel)) < 0.25, np.maximum(lvl - 1, 0), lvl)
+            n = len(sel) + ncl[s]
+            kp = np.zeros(n, KP_DTYPE)
+            kp["x"][:len(sel)] = uu[sel] + rng.normal(0, 0.8, len(sel))
+            kp["y"][:len(sel)] = vv[sel] + rng.normal(0, 0.8, len(sel))
+            kp["octave"][:len(sel)] = lvl
+            kp["x"][len(sel):] = rng.uniform(b[k, 0] + 1, b[k, 1] - 1, ncl[s])
+            kp["y"][len(sel):] = rng.uniform(b[k, 2] + 1, b[k, 3] - 1, ncl[s])
+            kp["octave"][len(sel):] = rng.integers(0, nlevels, ncl[s])
+            kp["size"] = 31.0 * sf[kp["octave"]]
+            kp["angle"] = rng.uniform(0, 360, n)
+            kp["response"] = rng.integers(7, 200, n)
+            kp["class_id"] = -1
+            flip = rng.uniform(0.02, 0.25, len(sel))[:, None]
+            d = np.concatenate([mp_desc[sel] ^ np.packbits(rng.random((len(sel), 256)) < flip, axis=1, bitorder="little"),
+                                rng.integers(0, 256, (ncl[s], 32), dtype=np.uint8)])
+            perm = rng.permutation(n)
+            parts.append(np.ascontiguousarray(kp[perm]))
+            descs.append(d[perm])
+        kfs.append(dict(kps_left=parts[0], kps_right=parts[1], desc=np.ascontiguousarray(np.concatenate(descs))))
+    return dict(views=views, bounds=b, scale_factors=sf, inv_level_sigma2=(f32(1.0) / (sf * sf)).astype(f32), log_scale_factor=log_sf,
+                map_points=dict(pos=pos, normal=normal, min_dist=min_d, max_dist=max_d, desc=mp_desc), key_frames=kfs, trl=(Rrl, trl))
