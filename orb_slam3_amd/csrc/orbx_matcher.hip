@@ -9,7 +9,9 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -19,6 +21,7 @@
 #include "matcher_context.h"
 
 static_assert(sizeof(orbx_keypoint) == 28, "the rows every matcher uploads and the kernels index");
+static_assert(sizeof(orbx::FisheyeView) == sizeof(orbx_fisheye_view), "the views every fisheye entry point hands to its kernels as they come");
 
 using namespace orbx;
 
@@ -380,6 +383,28 @@ inline GridParams grid_of(const float *b) {
     return g;
 }
 
+// The destination half of a prepare record (FramePrepare / FisheyePrepare), everything else zeroed: the resident buffers of a frame handle or a key frame
+// (both name them alike), the scale factors and the level count.  roff: the right camera's first row (FisheyePrepare only).  The source rows, the
+// counts and the capacities are the caller's to add.
+template <class P, class H> void prepare_dst(P &R, const H *h, int roff, const float *scale_factors, int nlevels) {
+    memset(&R, 0, sizeof(R));
+    R.kps = h->kps; R.desc = h->desc; R.count = h->count; R.scale = h->scale; R.nlevels = nlevels;
+    memcpy(R.scale_host, scale_factors, sizeof(float) * (size_t)nlevels);
+    if constexpr (std::is_same<P, FisheyePrepare>::value) {
+        R.gstart[0] = h->gstart; R.gorder[0] = h->gorder; R.gstart[1] = h->gstart_r; R.gorder[1] = h->gorder_r; R.roff = roff;
+    } else {
+        R.gstart = h->gstart; R.gorder = h->gorder;
+    }
+}
+
+// a load's record, and the handle's bookkeeping: what the host-side window setup reads (scale factors, levels, bounds)
+template <class P> void frame_prepare_common(orbx_frame *f, P &R, int roff, const float *scale_factors, int nlevels, const float *bounds4) {
+    prepare_dst(R, f, roff, scale_factors, nlevels);
+    f->scale_h.assign(scale_factors, scale_factors + nlevels);
+    f->nlevels = nlevels;
+    memcpy(f->bounds, bounds4, sizeof(f->bounds));
+}
+
 // N of a handle: cached, else one download of the device count(s) (and a synchronisation of the owner's stream)
 int frame_count(orbx_frame *f, int *n) {
     if (!f->n_known) {
@@ -619,15 +644,6 @@ int orbx_frame_create(orbx_matcher *m, int cap, orbx_frame **out) {
     return ORBX_OK;
 }
 
-static void frame_prepare_common(orbx_frame *f, FramePrepare &P, const float *scale_factors, int nlevels, const float *bounds4) {
-    memset(&P, 0, sizeof(P));
-    P.kps = f->kps; P.desc = f->desc; P.count = f->count; P.scale = f->scale; P.gstart = f->gstart; P.gorder = f->gorder;
-    P.cap = f->cap; P.nlevels = nlevels;
-    memcpy(P.scale_host, scale_factors, sizeof(float) * (size_t)nlevels);
-    f->scale_h.assign(scale_factors, scale_factors + nlevels);
-    f->nlevels = nlevels;
-    memcpy(f->bounds, bounds4, sizeof(f->bounds));
-}
 
 int orbx_frame_load_host(orbx_frame *f, const orbx_frame_desc *d) {
     if (!f || !d || d->n < 0 || (d->n > 0 && (!d->keypoints_un || !d->descriptors)) || !d->scale_factors || d->nlevels < 1 ||
@@ -648,8 +664,8 @@ int orbx_frame_load_host(orbx_frame *f, const orbx_frame_desc *d) {
     ORBX_TRY(m->upload_ranges(f->dev, f->stage, rows, 3));
     FramePrepare P;
     const float b[4] = {d->min_x, d->max_x, d->min_y, d->max_y};
-    frame_prepare_common(f, P, d->scale_factors, d->nlevels, b);
-    P.n_host = n;
+    frame_prepare_common(f, P, 0, d->scale_factors, d->nlevels, b);
+    P.n_host = n; P.cap = f->cap;
     hipLaunchKernelGGL(k_frame_prepare, dim3(1), dim3(64), 0, m->stream, P, grid_of(f->bounds));
     ORBX_HIP(hipGetLastError());
     ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
@@ -669,7 +685,8 @@ int orbx_frame_load_batch(orbx_frame *f, orbx_extractor *ex, int frame, const fl
     const float *b = bounds4 ? bounds4 : ex->bounds;   // mnMinX.. of the extractor's camera (orbx_set_camera) or the image rectangle
     ORBX_HIP(hipSetDevice(m->device));
     FramePrepare P;
-    frame_prepare_common(f, P, sf, nl, b);
+    frame_prepare_common(f, P, 0, sf, nl, b);
+    P.cap = f->cap;
     const size_t cap = (size_t)ex->cap;
     P.src_kps = (const orbx_keypoint *)ex->match_kps() + (size_t)frame * cap;   // mvKeysUn
     P.src_desc = (const uint8_t *)ex->d_desc.p + (size_t)frame * cap * 32;
@@ -1696,7 +1713,6 @@ extern "C" int orbx_is_in_frustum_checks(orbx_matcher *m, const orbx_fisheye_vie
     const size_t n = (size_t)n_mp, no = n * (size_t)n_views;
     FrustumChecks F;
     memset(&F, 0, sizeof(F));
-    static_assert(sizeof(FisheyeView) == sizeof(orbx_fisheye_view), "orbx_fisheye_view layout");
     memcpy(F.view, views, sizeof(FisheyeView) * (size_t)n_views);
     F.minx = bounds4[0]; F.maxx = bounds4[1]; F.miny = bounds4[2]; F.maxy = bounds4[3];
     F.log_scale_factor = log_scale_factor; F.nlevels = nlevels; F.cos_limit = viewing_cos_limit;
@@ -2436,7 +2452,12 @@ extern "C" int orbx_fuse_search(orbx_matcher *m, const orbx_frame_desc *kf, cons
 
 // ---------------------------------------------------------------------------------------------------------
 // Device-resident key frames (include/orbx.h, orbx_keyframe): what KeyFrame::KeyFrame(Frame&) copies of the frame -- immutable from then on, in ONE
-// allocation of its own, readable by every matcher context of its device -- and ORBmatcher::Fuse for K of them in one call.
+// allocation of its own, readable by every matcher context of its device -- and ORBmatcher::Fuse for K of them in one call.  Two kinds, monocular /
+// rectified and fisheye-stereo (KeyFrame::NLeft != -1), with ONE path each for what they share, the kind being a `bool fisheye` of that path:
+//   construction   keyframe_create_host / keyframe_from_frame (the four public constructors are argument checks), one tail: keyframe_publish
+//   pending counts orbx_keyframe::host_n / rows_n / adopt -- orbx_keyframe_count, both Fuse drivers and the BoW calls learn N through adopt()
+//   Fuse           keyframe_fuse_search_impl (projected queries) and keyframe_fuse_map_points_impl (projection on the device: SearchInNeighbors'
+//                  loop, on a rig both Fuse calls per target), with one decode of the keys: keyframe_fuse_results
 // ---------------------------------------------------------------------------------------------------------
 // The BoW state of a key frame (orbx_keyframe_compute_bow / orbx_keyframe_bow_from_frame): a SECOND allocation, made when BoW is first attached -- key
 // frames without it keep their size.  Set once, immutable afterwards; guarded as the rows are (an event behind its creation, a done flag).
@@ -2479,9 +2500,32 @@ struct orbx_keyframe {
     int roff = 0;
     uint16_t *gstart_r = nullptr, *gorder_r = nullptr;
     std::atomic<int> n_left{-1}, n_right{-1};  // -1 while known on the device only (cached with n)
+
+    // N as the host sees it, as orbx_frame's members of these names.  A key frame made from a batch-loaded handle leaves the count(s) on the device
+    // until a call needs them: host_*() = the count, or -1 for "not yet"; rows_n() = N, or meanwhile the capacity a call's per-feature buffers are
+    // sized by.
+    int host_n() const { return n.load(); }
+    int host_left() const { return n_left.load(); }
+    int host_right() const { return n_right.load(); }
+    int rows_n() const { const int v = n.load(); return v >= 0 ? v : cap; }
+    // The one place that learns the counts: a constructor with what the host knows, or a call that met the key frame with its counts pending and
+    // brought count[0] (, count[1]) home with its results.  Clamped as k_keyframe_copy / k_keyframe_copy_fisheye clamp what they write, so a device
+    // count comes through unchanged.
+    void adopt(int c0, int c1 = 0) {
+        if (fisheye) {
+            const int nl = std::min(std::max(c0, 0), roff), nr = std::min(std::max(c1, 0), cap - roff);
+            n_left.store(nl); n_right.store(nr); n.store(nl + nr);
+        } else {
+            n.store(std::min(std::max(c0, 0), cap));
+        }
+    }
 };
 
 namespace {
+
+// A key frame under construction: destroyed on every way out but the one that releases it to the caller.
+struct KeyFrameDelete { void operator()(orbx_keyframe *kf) const { orbx_keyframe_destroy(kf); } };
+typedef std::unique_ptr<orbx_keyframe, KeyFrameDelete> KeyFramePtr;
 
 void keyframe_bow_free(KeyFrameBow *b) {
     if (!b) return;
@@ -2491,28 +2535,28 @@ void keyframe_bow_free(KeyFrameBow *b) {
 }
 
 // one allocation per key frame: rows for `cap` features (28 + 32 [+ 4] + 2 bytes each), the per-level arrays, the count and the grid's 3073 cell offsets
-// (roff >= 0: a fisheye-stereo key frame -- cap = roff + the right camera's rows, a second set of cell offsets)
-int keyframe_alloc(int device, int cap, bool has_ur, bool has_sigma, int nlevels, const float *bounds4, orbx_keyframe **out, int roff = -1) {
-    orbx_keyframe *kf = new orbx_keyframe();
+// (roff >= 0: a fisheye-stereo key frame -- cap = roff + the right camera's rows, a second set of cell offsets; roff < 0: a monocular one)
+int keyframe_alloc(int device, int cap, int roff, bool has_ur, bool has_sigma, int nlevels, const float *bounds4, KeyFramePtr &out) {
+    out.reset(new orbx_keyframe());
+    orbx_keyframe *kf = out.get();
     kf->device = device; kf->cap = cap; kf->nlevels = nlevels;
     kf->fisheye = roff >= 0; kf->roff = std::max(roff, 0);
     memcpy(kf->bounds, bounds4, sizeof(kf->bounds));
     const size_t c = (size_t)std::max(cap, 1);
     Layout L;
-    // (rows and inv_sigma2 first: orbx_keyframe_create_host uploads them as one run)
+    // (rows and inv_sigma2 first: keyframe_create_host uploads them as one run)
     const size_t off_kps = L.add(28 * c), off_desc = L.add(32 * c), off_ur = has_ur ? L.add(4 * c) : 0, off_sg = has_sigma ? L.add(4 * (size_t)kFrameMaxLevels) : 0;
     const size_t off_scale = L.add(4 * (size_t)kFrameMaxLevels), off_count = L.add(8), off_gs = L.add(2 * ((size_t)kGridCells + 1)), off_go = L.add(2 * c);
     const size_t off_gsr = kf->fisheye ? L.add(2 * ((size_t)kGridCells + 1)) : 0;
     hipError_t e = hipMalloc((void **)&kf->dev, L.used);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&kf->ready, hipEventDisableTiming);
-    if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); return ORBX_E_HIP; }
     kf->kps = (orbx_keypoint *)(kf->dev + off_kps); kf->desc = kf->dev + off_desc;
     kf->u_right = has_ur ? (float *)(kf->dev + off_ur) : nullptr;
     kf->inv_sigma2 = has_sigma ? (float *)(kf->dev + off_sg) : nullptr;
     kf->scale = (float *)(kf->dev + off_scale); kf->count = (int32_t *)(kf->dev + off_count);
     kf->gstart = (uint16_t *)(kf->dev + off_gs); kf->gorder = (uint16_t *)(kf->dev + off_go);
     if (kf->fisheye) { kf->gstart_r = (uint16_t *)(kf->dev + off_gsr); kf->gorder_r = kf->gorder + kf->roff; }
-    *out = kf;
     return ORBX_OK;
 }
 
@@ -2524,12 +2568,6 @@ inline int keyframe_acquire(orbx_matcher *m, orbx_keyframe *const *kfs, int n_kf
 }
 inline void keyframe_release(orbx_keyframe *const *kfs, int n_kf) {   // after the call's synchronisation
     for (int k = 0; k < n_kf; k++) kfs[k]->done.store(true, std::memory_order_release);
-}
-
-// a fisheye key frame's counts as a call brought them home (clamped as k_keyframe_copy_fisheye clamps them)
-inline void keyframe_adopt_counts(orbx_keyframe *kf, int c0, int c1) {
-    const int nl = std::min(std::max(c0, 0), kf->roff), nr = std::min(std::max(c1, 0), kf->cap - kf->roff);
-    kf->n_left.store(nl); kf->n_right.store(nr); kf->n.store(nl + nr);
 }
 
 // the key-frame side of a problem; right: the right camera of a fisheye-stereo key frame (mvKeysRight, its grid, descriptor rows [N_left, N))
@@ -2553,18 +2591,117 @@ inline int keyframe_fetch_counts(orbx_matcher *m, bool fisheye, int n_kf, orbx_k
     if (!fisheye) return ORBX_OK;
     pend->assign(2 * (size_t)n_kf, 0);
     for (int k = 0; k < n_kf; k++)
-        if (kfs[k]->n.load() < 0) ORBX_TRY(m->d2h(pend->data() + 2 * (size_t)k, kfs[k]->count, 8));
+        if (kfs[k]->host_n() < 0) ORBX_TRY(m->d2h(pend->data() + 2 * (size_t)k, kfs[k]->count, 8));
     return ORBX_OK;
 }
 inline void keyframe_take_counts(bool fisheye, int n_kf, orbx_keyframe *const *kfs, const std::vector<int32_t> &pend) {
     for (int k = 0; fisheye && k < n_kf; k++)
-        if (kfs[k]->n.load() < 0) keyframe_adopt_counts(kfs[k], pend[2 * (size_t)k], pend[2 * (size_t)k + 1]);
+        if (kfs[k]->host_n() < 0) kfs[k]->adopt(pend[2 * (size_t)k], pend[2 * (size_t)k + 1]);
 }
 
 inline void launch_window_best1_kf(hipStream_t st, const KfProblem *dR, int nq_max, int np) {   // ORBX_LAUNCH_WINDOW_BEST2's shape: a problem's blocks on one XCD
     const int nb = (nq_max + 31) / 32;
     const dim3 grid = np >= 8 ? dim3(8, (unsigned)nb, (unsigned)((np + 7) / 8)) : dim3(1, (unsigned)nb, (unsigned)np);
     hipLaunchKernelGGL(k_window_best1_kf, grid, dim3(256), 0, st, dR, np);
+}
+
+// The n results of problem p (key frame p / sides, camera p % sides) as the caller gets them: -1 / 256 where nothing qualified; a right-camera index in
+// the rig's numbering, N_left + j (ORBmatcher.cc:1296) -- behind keyframe_take_counts, so N_left is at home.
+inline void keyframe_fuse_results(orbx_keyframe *const *kfs, int sides, int p, const u64 *keys, size_t n, int32_t *best_idx, int32_t *best_dist) {
+    const int base = p % sides == 1 ? kfs[p / sides]->host_left() : 0;
+    for (size_t i = 0; i < n; i++) {
+        best_idx[i] = keys[i] == kNoKey ? -1 : base + (int32_t)(keys[i] & 0xffff);
+        best_dist[i] = keys[i] == kNoKey ? 256 : (int32_t)(keys[i] >> 32);
+    }
+}
+
+// ---- Construction.  Both kinds of key frame are made by the same two functions -- from host arrays, from a frame handle -- with the kind as data;
+// they differ in the kernel launched.  A constructor holds the key frame in a KeyFramePtr, and keyframe_publish() is the one way it reaches the caller.
+
+// The tail behind a constructor's launch: the launch's error, the `ready` event, the counts the host knows (c0 < 0: still on the device only), *out.
+int keyframe_publish(orbx_matcher *m, KeyFramePtr &kf, int c0, int c1, orbx_keyframe **out) {
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(kf->ready, m->stream);
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); return ORBX_E_HIP; }
+    if (c0 >= 0) kf->adopt(c0, c1);
+    *out = kf.release();
+    return ORBX_OK;
+}
+
+// From host arrays (arguments checked by the caller).  d: mvKeysUn / mDescriptors [d->n] and the optional mvuRight of a monocular key frame; of a rig
+// mvKeys [d->n = N_left] and ALL N descriptor rows, with kps_right [n_right] = mvKeysRight (monocular: NULL, 0).
+int keyframe_create_host(orbx_matcher *m, bool fisheye, const orbx_frame_desc *d, const orbx_keypoint *kps_right, int n_right,
+                         const float *inv_level_sigma2, orbx_keyframe **out) {
+    ORBX_HIP(hipSetDevice(m->device));
+    const int nl = d->n, nr = n_right, N = nl + nr, nlv = d->nlevels;
+    const float *ur = fisheye ? nullptr : d->u_right;
+    const float b[4] = {d->min_x, d->max_x, d->min_y, d->max_y};
+    KeyFramePtr kf;
+    ORBX_TRY(keyframe_alloc(m->device, N, fisheye ? nl : -1, ur != nullptr, inv_level_sigma2 != nullptr, nlv, b, kf));
+    // ONE upload: the rows -- a rig's mvKeysRight right behind its mvKeys (roff = N_left) -- mvuRight and inv_sigma2, staged at the allocation's own
+    // offsets (pinned; the context's next call waits before it stages over them)
+    const size_t up_end = (size_t)((inv_level_sigma2 ? (uint8_t *)(kf->inv_sigma2 + nlv) : ur ? (uint8_t *)(kf->u_right + N) : kf->desc + 32 * (size_t)N) - kf->dev);
+    ORBX_TRY(m->reserve_staging(up_end));   // the rows go up through it
+    if (N > 0 || inv_level_sigma2) {
+        uint8_t *st = static_cast<uint8_t *>(m->stage.take(up_end + 16));
+        if (!st) { set_error("staging arena exhausted"); return ORBX_E_INTERNAL; }
+        memset(st, 0, up_end + 16);
+        const size_t o_kps = (size_t)((uint8_t *)kf->kps - kf->dev);
+        if (nl) memcpy(st + o_kps, d->keypoints_un, 28 * (size_t)nl);
+        if (nr) memcpy(st + o_kps + 28 * (size_t)nl, kps_right, 28 * (size_t)nr);
+        if (N) memcpy(st + (kf->desc - kf->dev), d->descriptors, 32 * (size_t)N);
+        if (ur) memcpy(st + ((uint8_t *)kf->u_right - kf->dev), ur, 4 * (size_t)N);
+        if (inv_level_sigma2) memcpy(st + ((uint8_t *)kf->inv_sigma2 - kf->dev), inv_level_sigma2, 4 * (size_t)nlv);
+        m->dirty = true;
+        const orbx_matcher::Span run = {0, up_end};
+        ORBX_TRY(m->upload_ranges(kf->dev, st, &run, 1));
+    }
+    // the in-place form of the frame loaders' kernels: count(s), scale factors, grid_build_wave over the uploaded rows (a grid per camera)
+    m->dirty = true;
+    if (fisheye) {
+        FisheyePrepare P;
+        prepare_dst(P, kf.get(), nl, d->scale_factors, nlv);
+        P.n_host[0] = nl; P.n_host[1] = nr; P.cap_side[0] = nl; P.cap_side[1] = nr;
+        hipLaunchKernelGGL(k_frame_prepare_fisheye, dim3(2), dim3(64), 0, m->stream, P, grid_of(kf->bounds));
+    } else {
+        FramePrepare P;
+        prepare_dst(P, kf.get(), 0, d->scale_factors, nlv);
+        P.n_host = N; P.cap = N;
+        hipLaunchKernelGGL(k_frame_prepare, dim3(1), dim3(64), 0, m->stream, P, grid_of(kf->bounds));
+    }
+    return keyframe_publish(m, kf, nl, nr, out);
+}
+
+// From a loaded frame handle of the same kind, owned by m (checked by the caller): a device-to-device copy on the owner's stream -- behind the frame's
+// load, ahead of its next one, no host synchronisation.  Sized by the counts where the host knows them, else by the handle's capacities.
+int keyframe_from_frame(orbx_matcher *m, bool fisheye, orbx_frame *f, const float *inv_level_sigma2, orbx_keyframe **out) {
+    ORBX_HIP(hipSetDevice(m->device));
+    const int cap_l = fisheye ? f->rows_left() : f->rows_n(), cap_r = fisheye ? f->rows_right() : 0;
+    KeyFramePtr kf;
+    ORBX_TRY(keyframe_alloc(m->device, cap_l + cap_r, fisheye ? cap_l : -1, f->has_ur, inv_level_sigma2 != nullptr, f->nlevels, f->bounds, kf));
+    m->dirty = true;
+    if (fisheye) {
+        KeyFrameCopyFisheye C;
+        memset(&C, 0, sizeof(C));
+        C.src_kps = f->kps; C.src_desc = f->desc; C.src_count = f->count; C.src_scale = f->scale;
+        C.src_gstart_l = f->gstart; C.src_gorder_l = f->gorder; C.src_gstart_r = f->gstart_r; C.src_gorder_r = f->gorder_r;
+        C.kps = kf->kps; C.desc = kf->desc; C.count = kf->count; C.scale = kf->scale; C.inv_sigma2 = kf->inv_sigma2;
+        C.gstart_l = kf->gstart; C.gorder_l = kf->gorder; C.gstart_r = kf->gstart_r; C.gorder_r = kf->gorder_r;
+        C.src_roff = f->roff; C.roff = cap_l; C.cap_l = cap_l; C.cap_r = cap_r; C.nlevels = f->nlevels;
+        if (inv_level_sigma2) memcpy(C.inv_sigma2_host, inv_level_sigma2, sizeof(float) * (size_t)f->nlevels);
+        hipLaunchKernelGGL(k_keyframe_copy_fisheye, dim3(2 + (unsigned)((std::max(cap_l, cap_r) + 255) / 256)), dim3(64), 0, m->stream, C);
+    } else {
+        KeyFrameCopy C;
+        memset(&C, 0, sizeof(C));
+        C.src_kps = f->kps; C.src_desc = f->desc; C.src_ur = f->has_ur ? f->u_right : nullptr; C.src_count = f->count; C.src_scale = f->scale;
+        C.src_gstart = f->gstart; C.src_gorder = f->gorder;
+        C.kps = kf->kps; C.desc = kf->desc; C.ur = kf->u_right; C.count = kf->count; C.scale = kf->scale; C.inv_sigma2 = kf->inv_sigma2;
+        C.gstart = kf->gstart; C.gorder = kf->gorder; C.cap = cap_l; C.nlevels = f->nlevels;
+        if (inv_level_sigma2) memcpy(C.inv_sigma2_host, inv_level_sigma2, sizeof(float) * (size_t)f->nlevels);
+        hipLaunchKernelGGL(k_keyframe_copy, dim3(1 + (unsigned)((cap_l + 255) / 256)), dim3(64), 0, m->stream, C);
+    }
+    kf->src_frame = f; kf->src_seq = f->load_seq;
+    return keyframe_publish(m, kf, fisheye ? f->host_left() : f->host_n(), f->host_right(), out);
 }
 
 }  // namespace
@@ -2586,84 +2723,42 @@ int orbx_keyframe_create_host(orbx_matcher *m, const orbx_frame_desc *d, const f
         d->nlevels > kFrameMaxLevels)
         return ORBX_E_BAD_ARG;
     if (d->n > 65535) return ORBX_E_TOO_LARGE;   // 16-bit grid entries, as orbx_fuse_search
-    ORBX_HIP(hipSetDevice(m->device));
-    const int n = d->n, nl = d->nlevels;
-    const float b[4] = {d->min_x, d->max_x, d->min_y, d->max_y};
-    orbx_keyframe *kf = nullptr;
-    int r = keyframe_alloc(m->device, n, d->u_right != nullptr, inv_level_sigma2 != nullptr, nl, b, &kf);
-    if (r != ORBX_OK) return r;
-    // ONE upload: the rows and inv_sigma2 staged at the allocation's own offsets (pinned; the context's next call waits before it stages over them)
-    const size_t up_end = (size_t)((inv_level_sigma2 ? (uint8_t *)(kf->inv_sigma2 + nl) : d->u_right ? (uint8_t *)(kf->u_right + n) : kf->desc + 32 * (size_t)n) - kf->dev);
-    r = m->reserve_staging(up_end);   // the rows go up through it
-    if (r != ORBX_OK) { orbx_keyframe_destroy(kf); return r; }
-    if (n > 0 || inv_level_sigma2) {
-        uint8_t *st = static_cast<uint8_t *>(m->stage.take(up_end + 16));
-        if (!st) { set_error("staging arena exhausted"); orbx_keyframe_destroy(kf); return ORBX_E_INTERNAL; }
-        memset(st, 0, up_end + 16);
-        memcpy(st + ((uint8_t *)kf->kps - kf->dev), d->keypoints_un, 28 * (size_t)n);
-        memcpy(st + (kf->desc - kf->dev), d->descriptors, 32 * (size_t)n);
-        if (d->u_right) memcpy(st + ((uint8_t *)kf->u_right - kf->dev), d->u_right, 4 * (size_t)n);
-        if (inv_level_sigma2) memcpy(st + ((uint8_t *)kf->inv_sigma2 - kf->dev), inv_level_sigma2, 4 * (size_t)nl);
-        m->dirty = true;
-        const orbx_matcher::Span run = {0, up_end};
-        if ((r = m->upload_ranges(kf->dev, st, &run, 1)) != ORBX_OK) { orbx_keyframe_destroy(kf); return r; }
-    }
-    FramePrepare P;   // k_frame_prepare's in-place form (as orbx_frame_load_host): count, scale factors, grid_build_wave over the uploaded rows
-    memset(&P, 0, sizeof(P));
-    P.kps = kf->kps; P.desc = kf->desc; P.count = kf->count; P.scale = kf->scale; P.gstart = kf->gstart; P.gorder = kf->gorder;
-    P.n_host = n; P.cap = n; P.nlevels = nl;
-    memcpy(P.scale_host, d->scale_factors, sizeof(float) * (size_t)nl);
-    m->dirty = true;
-    hipLaunchKernelGGL(k_frame_prepare, dim3(1), dim3(64), 0, m->stream, P, grid_of(kf->bounds));
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(kf->ready, m->stream);
-    if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
-    kf->n.store(n);
-    *out = kf;
-    return ORBX_OK;
+    return keyframe_create_host(m, false, d, nullptr, 0, inv_level_sigma2, out);
+}
+
+int orbx_keyframe_create_host_fisheye(orbx_matcher *m, const orbx_frame_desc *left, const orbx_keypoint *kps_right, int n_right,
+                                      const float *inv_level_sigma2, orbx_keyframe **out) {
+    if (out) *out = nullptr;
+    if (!m || !out || !left || left->n < 0 || n_right < 0 || (left->n > 0 && !left->keypoints_un) || (n_right > 0 && !kps_right) ||
+        (left->n + n_right > 0 && !left->descriptors) || !left->scale_factors || left->nlevels < 1 || left->nlevels > kFrameMaxLevels)
+        return ORBX_E_BAD_ARG;
+    if ((int64_t)left->n + n_right > 65535) return ORBX_E_TOO_LARGE;   // 16-bit grid entries, as orbx_fuse_search
+    return keyframe_create_host(m, true, left, kps_right, n_right, inv_level_sigma2, out);
 }
 
 int orbx_keyframe_from_frame(orbx_matcher *m, orbx_frame *f, const float *inv_level_sigma2, orbx_keyframe **out) {
     if (out) *out = nullptr;
     if (!m || !out || !f || f->owner != m || !f->loaded || f->fisheye) return ORBX_E_BAD_ARG;
-    ORBX_HIP(hipSetDevice(m->device));
-    const int cap = f->rows_n();   // sized by N where the host knows it
-    orbx_keyframe *kf = nullptr;
-    int r = keyframe_alloc(m->device, cap, f->has_ur, inv_level_sigma2 != nullptr, f->nlevels, f->bounds, &kf);
-    if (r != ORBX_OK) return r;
-    KeyFrameCopy C;
-    memset(&C, 0, sizeof(C));
-    C.src_kps = f->kps; C.src_desc = f->desc; C.src_ur = f->has_ur ? f->u_right : nullptr; C.src_count = f->count; C.src_scale = f->scale;
-    C.src_gstart = f->gstart; C.src_gorder = f->gorder;
-    C.kps = kf->kps; C.desc = kf->desc; C.ur = kf->u_right; C.count = kf->count; C.scale = kf->scale; C.inv_sigma2 = kf->inv_sigma2;
-    C.gstart = kf->gstart; C.gorder = kf->gorder; C.cap = cap; C.nlevels = f->nlevels;
-    if (inv_level_sigma2) memcpy(C.inv_sigma2_host, inv_level_sigma2, sizeof(float) * (size_t)f->nlevels);
-    // on the owner's stream: behind the frame's load, ahead of its next one -- no host synchronisation
-    m->dirty = true;
-    hipLaunchKernelGGL(k_keyframe_copy, dim3(1 + (unsigned)((cap + 255) / 256)), dim3(64), 0, m->stream, C);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(kf->ready, m->stream);
-    if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
-    kf->n.store(f->host_n());
-    kf->src_frame = f; kf->src_seq = f->load_seq;
-    *out = kf;
-    return ORBX_OK;
+    return keyframe_from_frame(m, false, f, inv_level_sigma2, out);
+}
+
+int orbx_keyframe_from_frame_fisheye(orbx_matcher *m, orbx_frame *f, const float *inv_level_sigma2, orbx_keyframe **out) {
+    if (out) *out = nullptr;
+    if (!m || !out || !f || f->owner != m || !f->loaded || !f->fisheye) return ORBX_E_BAD_ARG;
+    return keyframe_from_frame(m, true, f, inv_level_sigma2, out);
 }
 
 int orbx_keyframe_count(orbx_keyframe *kf, int *n) {
     if (!kf || !n) return ORBX_E_BAD_ARG;
-    int v = kf->n.load();
-    if (v < 0) {   // made from a batch-loaded frame: one download behind the copy
+    if (kf->host_n() < 0) {   // made from a batch-loaded frame: one download behind the copy
         ORBX_HIP(hipSetDevice(kf->device));
         ORBX_HIP(hipEventSynchronize(kf->ready));
         int32_t c[2] = {0, 0};
         ORBX_HIP(hipMemcpy(c, kf->count, kf->fisheye ? 8 : 4, hipMemcpyDeviceToHost));
-        if (kf->fisheye) keyframe_adopt_counts(kf, c[0], c[1]);
-        else kf->n.store(c[0]);
-        v = kf->n.load();
+        kf->adopt(c[0], c[1]);
         kf->done.store(true, std::memory_order_release);
     }
-    *n = v;
+    *n = kf->host_n();
     return ORBX_OK;
 }
 
@@ -2672,8 +2767,8 @@ int orbx_keyframe_counts(orbx_keyframe *kf, int *n_left, int *n_right) {
     int n = 0;
     const int rc = orbx_keyframe_count(kf, &n);   // at most one synchronisation, then cached
     if (rc != ORBX_OK) return rc;
-    if (n_left) *n_left = kf->fisheye ? kf->n_left.load() : n;
-    if (n_right) *n_right = kf->fisheye ? kf->n_right.load() : -1;
+    if (n_left) *n_left = kf->fisheye ? kf->host_left() : n;
+    if (n_right) *n_right = kf->fisheye ? kf->host_right() : -1;
     return ORBX_OK;
 }
 
@@ -2739,13 +2834,7 @@ static int keyframe_fuse_search_impl(orbx_matcher *m, bool fisheye, int n_kf, or
     ORBX_TRY(m->sync_and_deliver());
     keyframe_release(kfs, n_kf);
     keyframe_take_counts(fisheye, n_kf, kfs, pend);
-    for (int p = 0; p < np; p++) {
-        const int base = p % sides == 1 ? kfs[p / sides]->n_left.load() : 0;
-        for (int i = 0; i < queries[p].n; i++) {
-            const u64 key = keys[off[p] + (size_t)i];
-            if (key != kNoKey) { best_idx[p][i] = base + (int32_t)(key & 0xffff); best_dist[p][i] = (int32_t)(key >> 32); }
-        }
-    }
+    for (int p = 0; p < np; p++) keyframe_fuse_results(kfs, sides, p, keys.data() + off[p], (size_t)queries[p].n, best_idx[p], best_dist[p]);
     return ORBX_OK;
 }
 
@@ -2759,18 +2848,21 @@ int orbx_keyframe_fuse_search_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *
     return keyframe_fuse_search_impl(m, true, n_kf, kfs, queries, use_chi2, strict_fp, best_idx, best_dist);
 }
 
-// LocalMapping::SearchInNeighbors' Fuse loop in one call: k_fuse_project writes the query records of every (key frame, map point) into the arena,
-// k_window_best1_kf searches them -- the records never visit the host, the map points go up once.
-int orbx_keyframe_fuse_map_points(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams, const orbx_frame_pose *poses, float th,
-                                  float log_scale_factor, int strict_fp, int n_mp, const float *pos, const float *normal, const float *min_dist,
-                                  const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
-                                  uint8_t *projected) {
-    if (!m || n_kf < 0 || n_mp < 0 || (n_kf > 0 && (!kfs || !cams || !poses))) return ORBX_E_BAD_ARG;
+// LocalMapping::SearchInNeighbors' Fuse loop in one call: k_fuse_project (a rig: k_fuse_project_kb8) writes the query records of every (key frame,
+// [camera,] map point) into the arena, k_window_best1_kf searches the sides * n_kf problems -- the records never visit the host, the map points go up
+// once.  Monocular: cams / poses [n_kf], one problem per key frame, Fuse(pKFi, vpMapPointMatches).  fisheye: views [n_kf][2] instead, two problems per
+// key frame -- Fuse(pKFi, vpMapPointMatches) and Fuse(pKFi, vpMapPointMatches, true) -- and counts that are still on the device come home with the results.
+static int keyframe_fuse_map_points_impl(orbx_matcher *m, bool fisheye, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
+                                         const orbx_frame_pose *poses, const orbx_fisheye_view *views, float th, float log_scale_factor, int strict_fp,
+                                         int n_mp, const float *pos, const float *normal, const float *min_dist, const float *max_dist,
+                                         const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist, uint8_t *projected) {
+    if (!m || n_kf < 0 || n_mp < 0 || (n_kf > 0 && (!kfs || (fisheye ? !views : !cams || !poses)))) return ORBX_E_BAD_ARG;
     if (n_kf > ORBX_MAX_FUSE_KEYFRAMES) return ORBX_E_TOO_LARGE;
-    const size_t np = (size_t)n_mp, total = (size_t)n_kf * np;
+    const int sides = fisheye ? 2 : 1, nprob = n_kf * sides;   // problem p: key frame p / sides, camera p % sides
+    const size_t np = (size_t)n_mp, total = (size_t)nprob * np;
     if (total > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !best_idx || !best_dist)) return ORBX_E_BAD_ARG;
     for (int k = 0; k < n_kf; k++)
-        if (!kfs[k] || kfs[k]->fisheye || kfs[k]->device != m->device || !kfs[k]->inv_sigma2) return ORBX_E_BAD_ARG;
+        if (!kfs[k] || kfs[k]->fisheye != fisheye || kfs[k]->device != m->device || !kfs[k]->inv_sigma2) return ORBX_E_BAD_ARG;
     if (total == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
     const int32_t cnt4[4] = {n_mp, 0, 0, 0};
@@ -2779,197 +2871,72 @@ int orbx_keyframe_fuse_map_points(orbx_matcher *m, int n_kf, orbx_keyframe *cons
     int32_t *dcnt, *qmin, *qmax;
     orbx_camera *dcam;
     orbx_frame_pose *dpose;
-    KfProblem *dR;
-    u64 *dkeys;
-    ORBX_TRY(m->carve([&](Carve &A) {
-        // uploads, adjacent in the arena (one run): the map points ONCE, then what grows with n_kf -- cameras, poses, problem records, skip flags
-        dp = A.up(pos, 3 * np); dn = A.up(normal, 3 * np); dmn = A.up(min_dist, np); dmx = A.up(max_dist, np);
-        dd = A.up(mp_desc, 32 * np);
-        dcnt = A.up(cnt4, 4);
-        dcam = A.up(cams, (size_t)n_kf);
-        dpose = A.up(poses, (size_t)n_kf);
-        dR = A.take<KfProblem>(n_kf);
-        dskip = A.up_opt(skip, total);
-        // written by k_fuse_project, read by k_window_best1_kf
-        qx = A.take<float>(total); qy = A.take<float>(total); qxr = A.take<float>(total); qr = A.take<float>(total);
-        qmin = A.take<int32_t>(total); qmax = A.take<int32_t>(total);
-        qvalid = A.take<uint8_t>(total);
-        dkeys = A.take<u64>(total);
-    }));
-    std::vector<KfProblem> R((size_t)n_kf);
-    for (int k = 0; k < n_kf; k++) {
-        keyframe_problem(kfs[k], true, strict_fp, &R[k]);
-        WindowProblem &P = R[k].P;
-        const size_t o = (size_t)k * np;
-        P.qx = qx + o; P.qy = qy + o; P.qr = qr + o; P.qxr = qxr + o; P.qmin = qmin + o; P.qmax = qmax + o; P.qvalid = qvalid + o;
-        P.qdesc = dd; P.nq_ptr = dcnt; P.keys = dkeys + o;
-    }
-    ORBX_TRY(m->h2d(dR, R.data(), sizeof(KfProblem) * (size_t)n_kf));
-    ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
-    hipLaunchKernelGGL(k_fuse_project, dim3((unsigned)((n_mp + 255) / 256), (unsigned)n_kf), dim3(256), 0, m->exec(), (const KfProblem *)dR,
-                       (const orbx_camera *)dcam, (const orbx_frame_pose *)dpose, th, log_scale_factor, n_mp, (const float *)dp, (const float *)dn,
-                       (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx, qy, qxr, qr, qmin, qmax, qvalid);
-    launch_window_best1_kf(m->exec(), dR, n_mp, n_kf);
-    std::vector<u64> keys(total);
-    if (projected) ORBX_TRY(m->d2h(projected, qvalid, total));   // (adjacent to the keys: one download run)
-    ORBX_TRY(m->d2h(keys.data(), dkeys, 8 * total));
-    ORBX_TRY(m->sync_and_deliver());
-    keyframe_release(kfs, n_kf);
-    for (size_t i = 0; i < total; i++) {
-        const u64 key = keys[i];
-        best_idx[i] = key == kNoKey ? -1 : (int32_t)(key & 0xffff);
-        best_dist[i] = key == kNoKey ? 256 : (int32_t)(key >> 32);
-    }
-    return ORBX_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Fisheye-stereo key frames (KeyFrame::NLeft != -1): the object and SearchInNeighbors' two Fuse calls per target -- Fuse(pKFi, vpMapPointMatches) and
-// Fuse(pKFi, vpMapPointMatches, true) -- for every target in one call.
-// ---------------------------------------------------------------------------------------------------------
-int orbx_keyframe_create_host_fisheye(orbx_matcher *m, const orbx_frame_desc *left, const orbx_keypoint *kps_right, int n_right,
-                                      const float *inv_level_sigma2, orbx_keyframe **out) {
-    if (out) *out = nullptr;
-    if (!m || !out || !left || left->n < 0 || n_right < 0 || (left->n > 0 && !left->keypoints_un) || (n_right > 0 && !kps_right) ||
-        (left->n + n_right > 0 && !left->descriptors) || !left->scale_factors || left->nlevels < 1 || left->nlevels > kFrameMaxLevels)
-        return ORBX_E_BAD_ARG;
-    if ((int64_t)left->n + n_right > 65535) return ORBX_E_TOO_LARGE;   // 16-bit grid entries, as orbx_fuse_search
-    ORBX_HIP(hipSetDevice(m->device));
-    const int nl = left->n, nr = n_right, N = nl + nr, nlv = left->nlevels;
-    const float b[4] = {left->min_x, left->max_x, left->min_y, left->max_y};
-    orbx_keyframe *kf = nullptr;
-    int r = keyframe_alloc(m->device, N, false, inv_level_sigma2 != nullptr, nlv, b, &kf, nl);
-    if (r != ORBX_OK) return r;
-    // ONE upload, as orbx_keyframe_create_host: mvKeys and mvKeysRight one behind the other (roff = N_left), all N descriptor rows, inv_sigma2
-    const size_t up_end = (size_t)((inv_level_sigma2 ? (uint8_t *)(kf->inv_sigma2 + nlv) : kf->desc + 32 * (size_t)N) - kf->dev);
-    r = m->reserve_staging(up_end);
-    if (r != ORBX_OK) { orbx_keyframe_destroy(kf); return r; }
-    if (N > 0 || inv_level_sigma2) {
-        uint8_t *st = static_cast<uint8_t *>(m->stage.take(up_end + 16));
-        if (!st) { set_error("staging arena exhausted"); orbx_keyframe_destroy(kf); return ORBX_E_INTERNAL; }
-        memset(st, 0, up_end + 16);
-        const size_t o_kps = (size_t)((uint8_t *)kf->kps - kf->dev);
-        if (nl) memcpy(st + o_kps, left->keypoints_un, 28 * (size_t)nl);
-        if (nr) memcpy(st + o_kps + 28 * (size_t)nl, kps_right, 28 * (size_t)nr);
-        if (N) memcpy(st + (kf->desc - kf->dev), left->descriptors, 32 * (size_t)N);
-        if (inv_level_sigma2) memcpy(st + ((uint8_t *)kf->inv_sigma2 - kf->dev), inv_level_sigma2, 4 * (size_t)nlv);
-        m->dirty = true;
-        const orbx_matcher::Span run = {0, up_end};
-        if ((r = m->upload_ranges(kf->dev, st, &run, 1)) != ORBX_OK) { orbx_keyframe_destroy(kf); return r; }
-    }
-    FisheyePrepare P;   // k_frame_prepare_fisheye's in-place form (as orbx_frame_load_host_fisheye): counts, scale factors, one grid per camera
-    memset(&P, 0, sizeof(P));
-    P.n_host[0] = nl; P.n_host[1] = nr; P.cap_side[0] = nl; P.cap_side[1] = nr;
-    P.kps = kf->kps; P.desc = kf->desc; P.count = kf->count; P.scale = kf->scale;
-    P.gstart[0] = kf->gstart; P.gorder[0] = kf->gorder; P.gstart[1] = kf->gstart_r; P.gorder[1] = kf->gorder_r;
-    P.roff = nl; P.nlevels = nlv;
-    memcpy(P.scale_host, left->scale_factors, sizeof(float) * (size_t)nlv);
-    m->dirty = true;
-    hipLaunchKernelGGL(k_frame_prepare_fisheye, dim3(2), dim3(64), 0, m->stream, P, grid_of(kf->bounds));
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(kf->ready, m->stream);
-    if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
-    kf->n_left.store(nl); kf->n_right.store(nr); kf->n.store(N);
-    *out = kf;
-    return ORBX_OK;
-}
-
-int orbx_keyframe_from_frame_fisheye(orbx_matcher *m, orbx_frame *f, const float *inv_level_sigma2, orbx_keyframe **out) {
-    if (out) *out = nullptr;
-    if (!m || !out || !f || f->owner != m || !f->loaded || !f->fisheye) return ORBX_E_BAD_ARG;
-    ORBX_HIP(hipSetDevice(m->device));
-    const int cap_l = f->rows_left(), cap_r = f->rows_right();   // sized by the counts where the host knows them
-    orbx_keyframe *kf = nullptr;
-    int r = keyframe_alloc(m->device, cap_l + cap_r, false, inv_level_sigma2 != nullptr, f->nlevels, f->bounds, &kf, cap_l);
-    if (r != ORBX_OK) return r;
-    KeyFrameCopyFisheye C;
-    memset(&C, 0, sizeof(C));
-    C.src_kps = f->kps; C.src_desc = f->desc; C.src_count = f->count; C.src_scale = f->scale;
-    C.src_gstart_l = f->gstart; C.src_gorder_l = f->gorder; C.src_gstart_r = f->gstart_r; C.src_gorder_r = f->gorder_r;
-    C.kps = kf->kps; C.desc = kf->desc; C.count = kf->count; C.scale = kf->scale; C.inv_sigma2 = kf->inv_sigma2;
-    C.gstart_l = kf->gstart; C.gorder_l = kf->gorder; C.gstart_r = kf->gstart_r; C.gorder_r = kf->gorder_r;
-    C.src_roff = f->roff; C.roff = cap_l; C.cap_l = cap_l; C.cap_r = cap_r; C.nlevels = f->nlevels;
-    if (inv_level_sigma2) memcpy(C.inv_sigma2_host, inv_level_sigma2, sizeof(float) * (size_t)f->nlevels);
-    // on the owner's stream: behind the frame's load, ahead of its next one -- no host synchronisation
-    m->dirty = true;
-    hipLaunchKernelGGL(k_keyframe_copy_fisheye, dim3(2 + (unsigned)((std::max(cap_l, cap_r) + 255) / 256)), dim3(64), 0, m->stream, C);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(kf->ready, m->stream);
-    if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_keyframe_destroy(kf); return ORBX_E_HIP; }
-    kf->n_left.store(f->host_left()); kf->n_right.store(f->host_right()); kf->n.store(f->host_n());
-    *out = kf;
-    return ORBX_OK;
-}
-
-// Both Fuse calls of LocalMapping::SearchInNeighbors' loop for every target of a rig in one call: k_fuse_project_kb8 writes the query records of every
-// (key frame, camera, map point) into the arena, k_window_best1_kf searches the 2 n_kf problems -- the records never visit the host, the map points go
-// up once.
-int orbx_keyframe_fuse_map_points_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views, float th,
-                                          float log_scale_factor, int strict_fp, int n_mp, const float *pos, const float *normal, const float *min_dist,
-                                          const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
-                                          uint8_t *projected) {
-    if (!m || n_kf < 0 || n_mp < 0 || (n_kf > 0 && (!kfs || !views))) return ORBX_E_BAD_ARG;
-    if (n_kf > ORBX_MAX_FUSE_KEYFRAMES) return ORBX_E_TOO_LARGE;
-    const int nprob = 2 * n_kf;
-    const size_t np = (size_t)n_mp, total = (size_t)nprob * np;
-    if (total > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !best_idx || !best_dist)) return ORBX_E_BAD_ARG;
-    for (int k = 0; k < n_kf; k++)
-        if (!kfs[k] || !kfs[k]->fisheye || kfs[k]->device != m->device || !kfs[k]->inv_sigma2) return ORBX_E_BAD_ARG;
-    if (total == 0) return ORBX_OK;
-    ORBX_HIP(hipSetDevice(m->device));
-    static_assert(sizeof(FisheyeView) == sizeof(orbx_fisheye_view), "orbx_fisheye_view layout");
-    const int32_t cnt4[4] = {n_mp, 0, 0, 0};
-    float *dp, *dn, *dmn, *dmx, *qx, *qy, *qr;
-    uint8_t *dd, *dskip, *qvalid;
-    int32_t *dcnt, *qmin, *qmax;
     FisheyeView *dview;
     KfProblem *dR;
     u64 *dkeys;
     ORBX_TRY(m->carve([&](Carve &A) {
-        // uploads, adjacent in the arena (one run): the map points ONCE, then what grows with n_kf -- two views, two problem records, one skip row each
+        // uploads, adjacent in the arena (one run): the map points ONCE, then what grows with n_kf -- cameras and poses (a rig: two views), problem
+        // records, one skip row per key frame
         dp = A.up(pos, 3 * np); dn = A.up(normal, 3 * np); dmn = A.up(min_dist, np); dmx = A.up(max_dist, np);
         dd = A.up(mp_desc, 32 * np);
         dcnt = A.up(cnt4, 4);
-        dview = A.up(reinterpret_cast<const FisheyeView *>(views), (size_t)nprob);
+        dcam = fisheye ? nullptr : A.up(cams, (size_t)n_kf);
+        dpose = fisheye ? nullptr : A.up(poses, (size_t)n_kf);
+        dview = fisheye ? A.up(reinterpret_cast<const FisheyeView *>(views), (size_t)nprob) : nullptr;
         dR = A.take<KfProblem>(nprob);
         dskip = A.up_opt(skip, (size_t)n_kf * np);
-        // written by k_fuse_project_kb8, read by k_window_best1_kf
-        qx = A.take<float>(total); qy = A.take<float>(total); qr = A.take<float>(total);
+        // written by the projection kernel, read by k_window_best1_kf (no mvuRight on a rig: no qxr)
+        qx = A.take<float>(total); qy = A.take<float>(total); qxr = fisheye ? nullptr : A.take<float>(total); qr = A.take<float>(total);
         qmin = A.take<int32_t>(total); qmax = A.take<int32_t>(total);
         qvalid = A.take<uint8_t>(total);
         dkeys = A.take<u64>(total);
     }));
     std::vector<KfProblem> R((size_t)nprob);
     for (int p = 0; p < nprob; p++) {
-        keyframe_problem(kfs[p >> 1], true, strict_fp, &R[p], (p & 1) != 0);
+        keyframe_problem(kfs[p / sides], true, strict_fp, &R[p], p % sides == 1);
         WindowProblem &P = R[p].P;
         const size_t o = (size_t)p * np;
         P.qx = qx + o; P.qy = qy + o; P.qr = qr + o; P.qmin = qmin + o; P.qmax = qmax + o; P.qvalid = qvalid + o;
+        if (!fisheye) P.qxr = qxr + o;
         P.qdesc = dd; P.nq_ptr = dcnt; P.keys = dkeys + o;
     }
     ORBX_TRY(m->h2d(dR, R.data(), sizeof(KfProblem) * (size_t)nprob));
     ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
-    hipLaunchKernelGGL(k_fuse_project_kb8, dim3((unsigned)((n_mp + 255) / 256), (unsigned)nprob), dim3(256), 0, m->exec(), (const KfProblem *)dR,
-                       (const FisheyeView *)dview, th, log_scale_factor, n_mp, (const float *)dp, (const float *)dn, (const float *)dmn,
-                       (const float *)dmx, (const uint8_t *)dskip, qx, qy, qr, qmin, qmax, qvalid);
+    const dim3 grid((unsigned)((n_mp + 255) / 256), (unsigned)nprob);
+    if (fisheye)
+        hipLaunchKernelGGL(k_fuse_project_kb8, grid, dim3(256), 0, m->exec(), (const KfProblem *)dR, (const FisheyeView *)dview, th, log_scale_factor, n_mp,
+                           (const float *)dp, (const float *)dn, (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx, qy, qr, qmin, qmax, qvalid);
+    else
+        hipLaunchKernelGGL(k_fuse_project, grid, dim3(256), 0, m->exec(), (const KfProblem *)dR, (const orbx_camera *)dcam, (const orbx_frame_pose *)dpose, th,
+                           log_scale_factor, n_mp, (const float *)dp, (const float *)dn, (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx, qy,
+                           qxr, qr, qmin, qmax, qvalid);
     launch_window_best1_kf(m->exec(), dR, n_mp, nprob);
     std::vector<u64> keys(total);
     if (projected) ORBX_TRY(m->d2h(projected, qvalid, total));   // (adjacent to the keys: one download run)
     ORBX_TRY(m->d2h(keys.data(), dkeys, 8 * total));
-    std::vector<int32_t> pend;
-    ORBX_TRY(keyframe_fetch_counts(m, true, n_kf, kfs, &pend));
+    std::vector<int32_t> pend;   // the counts of fisheye key frames that still have them on the device: home with the results
+    ORBX_TRY(keyframe_fetch_counts(m, fisheye, n_kf, kfs, &pend));
     ORBX_TRY(m->sync_and_deliver());
     keyframe_release(kfs, n_kf);
-    keyframe_take_counts(true, n_kf, kfs, pend);
-    for (int p = 0; p < nprob; p++) {
-        const int base = (p & 1) ? kfs[p >> 1]->n_left.load() : 0;   // the rig's numbering (ORBmatcher.cc:1296)
-        for (size_t i = (size_t)p * np; i < (size_t)(p + 1) * np; i++) {
-            const u64 key = keys[i];
-            best_idx[i] = key == kNoKey ? -1 : base + (int32_t)(key & 0xffff);
-            best_dist[i] = key == kNoKey ? 256 : (int32_t)(key >> 32);
-        }
-    }
+    keyframe_take_counts(fisheye, n_kf, kfs, pend);
+    for (int p = 0; p < nprob; p++) keyframe_fuse_results(kfs, sides, p, keys.data() + (size_t)p * np, np, best_idx + (size_t)p * np, best_dist + (size_t)p * np);
     return ORBX_OK;
+}
+
+int orbx_keyframe_fuse_map_points(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams, const orbx_frame_pose *poses, float th,
+                                  float log_scale_factor, int strict_fp, int n_mp, const float *pos, const float *normal, const float *min_dist,
+                                  const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
+                                  uint8_t *projected) {
+    return keyframe_fuse_map_points_impl(m, false, n_kf, kfs, cams, poses, nullptr, th, log_scale_factor, strict_fp, n_mp, pos, normal, min_dist, max_dist,
+                                         mp_desc, skip, best_idx, best_dist, projected);
+}
+
+int orbx_keyframe_fuse_map_points_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views, float th,
+                                          float log_scale_factor, int strict_fp, int n_mp, const float *pos, const float *normal, const float *min_dist,
+                                          const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
+                                          uint8_t *projected) {
+    return keyframe_fuse_map_points_impl(m, true, n_kf, kfs, nullptr, nullptr, views, th, log_scale_factor, strict_fp, n_mp, pos, normal, min_dist,
+                                         max_dist, mp_desc, skip, best_idx, best_dist, projected);
 }
 
 }  // extern "C"
@@ -3025,7 +2992,7 @@ inline BowSide bow_side(const orbx_keyframe *kf) {
     const KeyFrameBow *b = kf->bow.load(std::memory_order_acquire);
     BowSide S;
     S.desc = kf->desc; S.angle = b->angle; S.fv_node = b->fv_node; S.fv_ptr = b->fv_ptr; S.fv_index = b->fv_index; S.fv_meta = b->fv_meta;
-    S.count = kf->count; S.n = kf->n.load(); S.cap = kf->cap;
+    S.count = kf->count; S.n = kf->host_n(); S.cap = kf->cap;
     S.bound = std::min(S.rows(), b->voc->node_bound(b->levelsup));
     return S;
 }
@@ -3176,8 +3143,7 @@ int orbx_keyframe_compute_bow(orbx_matcher *m, orbx_keyframe *kf, const orbx_voc
         if (b->voc != v || b->levelsup != levelsup) return ORBX_E_BAD_ARG;
         if (!down) return ORBX_OK;
     }
-    const int n_host = kf->n.load();
-    const int nc = n_host >= 0 ? n_host : kf->cap;   // features the kernels may see
+    const int n_host = kf->host_n(), nc = kf->rows_n();   // nc: features the kernels may see
     if (nc > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;
     ORBX_HIP(hipSetDevice(m->device));
     ORBX_TRY(m->reserve_staging(8 * (size_t)nc));   // the ids come down through it
@@ -3212,8 +3178,8 @@ int orbx_keyframe_compute_bow(orbx_matcher *m, orbx_keyframe *kf, const orbx_voc
     ORBX_TRY(m->sync_and_deliver());
     keyframe_bow_release(kf);
     if (n_host < 0) {
-        cnt = std::min(std::max(cnt, 0), kf->cap);
-        kf->n.store(cnt);
+        kf->adopt(cnt);
+        cnt = kf->host_n();
         if (word_id) memcpy(word_id, h.data(), 4 * (size_t)cnt);
         if (node_id) memcpy(node_id, h.data() + nc, 4 * (size_t)cnt);
     }
@@ -3263,7 +3229,7 @@ int orbx_frame_search_by_bow_resident(orbx_matcher *m, orbx_frame *f, int n_kf, 
     if (n < 0 && match_stride < f->cap) { const int rc = frame_count(f, &n); if (rc != ORBX_OK) return rc; }   // the rows must fit the stride
     if (n >= 0 && match_stride < n) return ORBX_E_BAD_ARG;
     for (int k = 0; k < n_kf; k++) {
-        if (valid && valid[k] && kfs[k]->n.load() < 0) { int nk; const int rc = orbx_keyframe_count(kfs[k], &nk); if (rc != ORBX_OK) return rc; }   // flags: N entries
+        if (valid && valid[k] && kfs[k]->host_n() < 0) { int nk; const int rc = orbx_keyframe_count(kfs[k], &nk); if (rc != ORBX_OK) return rc; }   // flags: N entries
         nmatches[k] = 0;
         for (int i = 0; i < std::max(n, 0); i++) match[(size_t)k * match_stride + i] = -1;
     }
@@ -3278,7 +3244,7 @@ int orbx_frame_search_by_bow_resident(orbx_matcher *m, orbx_frame *f, int n_kf, 
     if (r != ORBX_OK) return r;
     for (int k = 0; k < n_kf; k++) {
         keyframe_bow_release(kfs[k]);
-        if (kfs[k]->n.load() < 0) kfs[k]->n.store(std::min(std::max(counts[2 * (size_t)k], 0), kfs[k]->cap));
+        if (kfs[k]->host_n() < 0) kfs[k]->adopt(counts[2 * (size_t)k]);
     }
     if (!f->n_known) f->adopt(counts[1]);
     return ORBX_OK;
@@ -3296,11 +3262,11 @@ int orbx_keyframe_search_by_bow(orbx_matcher *m, orbx_keyframe *kf1, const uint8
     if (!kfs2 || !match12 || !nmatches || match_stride < 0) return ORBX_E_BAD_ARG;
     for (int k = 0; k < n_kf; k++)
         if (!keyframe_bow_ok(m, kfs2[k], &voc, &levelsup)) return ORBX_E_BAD_ARG;
-    int n1 = kf1->n.load();
+    int n1 = kf1->host_n();
     if (n1 < 0 && (match_stride < kf1->cap || valid1)) { const int rc = orbx_keyframe_count(kf1, &n1); if (rc != ORBX_OK) return rc; }
     if (n1 >= 0 && match_stride < n1) return ORBX_E_BAD_ARG;
     for (int k = 0; k < n_kf; k++) {
-        if (valid2 && valid2[k] && kfs2[k]->n.load() < 0) { int nk; const int rc = orbx_keyframe_count(kfs2[k], &nk); if (rc != ORBX_OK) return rc; }
+        if (valid2 && valid2[k] && kfs2[k]->host_n() < 0) { int nk; const int rc = orbx_keyframe_count(kfs2[k], &nk); if (rc != ORBX_OK) return rc; }
         nmatches[k] = 0;
         for (int i = 0; i < std::max(n1, 0); i++) match12[(size_t)k * match_stride + i] = -1;
     }
@@ -3317,10 +3283,10 @@ int orbx_keyframe_search_by_bow(orbx_matcher *m, orbx_keyframe *kf1, const uint8
                                    match_stride, nmatches, counts);
     if (r != ORBX_OK) return r;
     keyframe_bow_release(kf1);
-    if (kf1->n.load() < 0) kf1->n.store(std::min(std::max(counts[0], 0), kf1->cap));
+    if (kf1->host_n() < 0) kf1->adopt(counts[0]);
     for (int k = 0; k < n_kf; k++) {
         keyframe_bow_release(kfs2[k]);
-        if (kfs2[k]->n.load() < 0) kfs2[k]->n.store(std::min(std::max(counts[2 * (size_t)k + 1], 0), kfs2[k]->cap));
+        if (kfs2[k]->host_n() < 0) kfs2[k]->adopt(counts[2 * (size_t)k + 1]);
     }
     return ORBX_OK;
 }
@@ -3334,7 +3300,7 @@ int orbx_keyframe_search_for_triangulation(orbx_matcher *m, orbx_keyframe *kf1, 
     int levelsup = 0;
     if (!keyframe_bow_ok(m, kf1, &voc, &levelsup) || !keyframe_bow_ok(m, kf2, &voc, &levelsup)) return ORBX_E_BAD_ARG;
     if (gate->nlevels != kf2->nlevels) return ORBX_E_BAD_ARG;
-    int n1 = 0, n2 = kf2->n.load();
+    int n1 = 0, n2 = kf2->host_n();
     int rc = orbx_keyframe_count(kf1, &n1);   // matches12 holds N1 entries: N1 has to be known here
     if (rc == ORBX_OK && skip2 && n2 < 0) rc = orbx_keyframe_count(kf2, &n2);
     if (rc != ORBX_OK) return rc;
@@ -3356,7 +3322,7 @@ int orbx_keyframe_search_for_triangulation(orbx_matcher *m, orbx_keyframe *kf1, 
                                    counts);
     if (r != ORBX_OK) return r;
     keyframe_bow_release(kf1); keyframe_bow_release(kf2);
-    if (kf2->n.load() < 0) kf2->n.store(std::min(std::max(counts[1], 0), kf2->cap));
+    if (kf2->host_n() < 0) kf2->adopt(counts[1]);
     return nm;
 }
 
@@ -3478,16 +3444,11 @@ extern "C" int orbx_frame_load_host_fisheye(orbx_frame *f, const orbx_frame_desc
     memcpy(f->stage + f->off_r2l, r2l, b_r2l);
     const orbx_matcher::Span rows[4] = {{f->off_kps, b_kl + b_kr}, {f->off_desc, b_desc}, {f->off_l2r, b_l2r}, {f->off_r2l, b_r2l}};
     ORBX_TRY(m->upload_ranges(f->dev, f->stage, rows, 4));
-    FramePrepare P0;
     const float b[4] = {left->min_x, left->max_x, left->min_y, left->max_y};
-    frame_prepare_common(f, P0, left->scale_factors, left->nlevels, b);
     FisheyePrepare P;
-    memset(&P, 0, sizeof(P));
+    frame_prepare_common(f, P, nl, left->scale_factors, left->nlevels, b);
     P.n_host[0] = nl; P.n_host[1] = nr; P.cap_side[0] = nl; P.cap_side[1] = nr;
-    P.kps = f->kps; P.desc = f->desc; P.count = f->count; P.l2r = f->l2r; P.r2l = f->r2l; P.scale = f->scale;
-    P.gstart[0] = f->gstart; P.gorder[0] = f->gorder; P.gstart[1] = f->gstart_r; P.gorder[1] = f->gorder_r;
-    P.roff = nl; P.nlevels = left->nlevels;
-    memcpy(P.scale_host, left->scale_factors, sizeof(float) * (size_t)left->nlevels);
+    P.l2r = f->l2r; P.r2l = f->r2l;
     hipLaunchKernelGGL(k_frame_prepare_fisheye, dim3(2), dim3(64), 0, m->stream, P, grid_of(f->bounds));
     ORBX_HIP(hipGetLastError());
     ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
@@ -3511,10 +3472,8 @@ extern "C" int orbx_frame_load_stereo_fisheye_batch(orbx_frame *f, orbx_extracto
     if (nl < 1 || nl > kFrameMaxLevels || (!bounds4 && L->width <= 0)) return ORBX_E_BAD_ARG;
     const float *b = bounds4 ? bounds4 : L->bounds;
     ORBX_HIP(hipSetDevice(m->device));
-    FramePrepare P0;
-    frame_prepare_common(f, P0, sf, nl, b);
     FisheyePrepare P;
-    memset(&P, 0, sizeof(P));
+    frame_prepare_common(f, P, capL, sf, nl, b);
     const size_t fr = (size_t)frame;
     P.src_kps[0] = (const orbx_keypoint *)L->d_kps.p + fr * capL;   // mvKeys: the raw keypoints k_tri_kb8_stereo read
     P.src_kps[1] = (const orbx_keypoint *)R->d_kps.p + fr * capR;
@@ -3525,10 +3484,7 @@ extern "C" int orbx_frame_load_stereo_fisheye_batch(orbx_frame *f, orbx_extracto
     P.src_l2r = (const int32_t *)L->d_sf_l2r.p + fr * capL;
     P.src_r2l = (const int32_t *)L->d_sf_r2l.p + fr * capR;
     P.cap_side[0] = capL; P.cap_side[1] = capR;
-    P.kps = f->kps; P.desc = f->desc; P.count = f->count; P.l2r = f->l2r; P.r2l = f->r2l; P.scale = f->scale;
-    P.gstart[0] = f->gstart; P.gorder[0] = f->gorder; P.gstart[1] = f->gstart_r; P.gorder[1] = f->gorder_r;
-    P.roff = capL; P.nlevels = nl;
-    memcpy(P.scale_host, sf, sizeof(float) * (size_t)nl);
+    P.l2r = f->l2r; P.r2l = f->r2l;
     // the owner's stream waits for the stage (which waited for both extractions); both extractors' next batches and the left extractor's next
     // stage wait for the copy: no host synchronisation
     ORBX_HIP(hipStreamWaitEvent(m->stream, L->ev_sf, 0));
@@ -3591,7 +3547,6 @@ extern "C" int orbx_frame_search_local_points_fisheye(orbx_matcher *m, orbx_fram
     const size_t q = (size_t)n_mp, q2 = 2 * q;
     FrustumChecks FC;
     memset(&FC, 0, sizeof(FC));
-    static_assert(sizeof(FisheyeView) == sizeof(orbx_fisheye_view), "orbx_fisheye_view layout");
     memcpy(FC.view, views, sizeof(FisheyeView) * 2);
     FC.minx = f->bounds[0]; FC.maxx = f->bounds[1]; FC.miny = f->bounds[2]; FC.maxy = f->bounds[3];
     FC.log_scale_factor = log_scale_factor; FC.nlevels = f->nlevels; FC.cos_limit = viewing_cos_limit;

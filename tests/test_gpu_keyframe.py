@@ -283,6 +283,44 @@ def test_from_frame_of_a_batch_loaded_handle_with_its_count_on_the_device(oracle
     assert kf.count() == len(k1)
 
 
+def test_fuse_map_points_with_the_count_fetched_first_and_with_it_pending(canvas1):
+    """Two key frames from batch-loaded handles (320 x 240, N on the device only) through FuseMapPoints with K = 2 and 200 map points -- the
+    back-projections of 200 features of the first frame through a pinhole camera under an identity pose -- once counted first (counts()), once with
+    their counts pending: the same rows, bit for bit, and the same counts afterwards."""
+    import torch
+    import orb_slam3_amd as osa
+    from orb_slam3_amd import synth
+    w, h, n_mp = 320, 240, 200
+    ex = osa.ORBextractor(500, 1.2, 8, 20, 7)
+    m = osa.ORBmatcher(0.6, True)
+    frames = torch.from_numpy(np.stack([synth.frame_from_canvas(canvas1, t, w, h, 1000 + t) for t in range(2)])).cuda()
+    ex.extract_batch_device(frames.data_ptr(), 2, w, h, w, w * h, (0, 1000))
+    sf = ex.GetScaleFactors()
+    isg = (f32(1.0) / (sf * sf)).astype(f32)
+    handles = [osa.DeviceFrame(m, ex.batch_view().cap).load_batch(ex, t) for t in (0, 1)]   # N stays on the device
+    counted = [osa.DeviceKeyFrame.from_frame(m, D, isg) for D in handles]
+    pending = [osa.DeviceKeyFrame.from_frame(m, D, isg) for D in handles]
+    ns = [kf.counts() for kf in counted]
+    ex.sync()
+    _, k0, d0 = ex.download(0)
+    assert ns[0] == (len(k0), -1) and len(k0) >= n_mp
+    rng = np.random.default_rng(12)
+    idx = rng.choice(len(k0), n_mp, replace=False)
+    ray = np.stack([(k0["x"][idx] - 160.0) / 200.0, (k0["y"][idx] - 120.0) / 200.0, np.ones(n_mp)], axis=1)
+    pos = 5.0 * ray                                                                            # depth 5 in front of a camera at the origin
+    dist = np.linalg.norm(pos, axis=1)
+    md = dist * sf[k0["octave"][idx]].astype(np.float64) * 1.05                               # predicts the feature's octave or the one above
+    mp = dict(pos=pos.astype(f32), normal=(pos / dist[:, None]).astype(f32), min_dist=(md / float(sf[-1])).astype(f32), max_dist=md.astype(f32),
+              desc=np.ascontiguousarray(d0[idx] ^ np.packbits(rng.random((n_mp, 256)) < 0.03, axis=1, bitorder="little")))
+    cams = [(200.0, 200.0, 160.0, 120.0, 0.0, 0.0, 0.0, 0.0, 0.0, 40.0)] * 2
+    poses = [(np.eye(3, dtype=f32), np.zeros(3, f32), np.zeros(3, f32))] * 2
+    ci, cd, cp = m.FuseMapPoints(counted, cams, poses, mp, TH, float(np.log(1.2)))
+    pi, pd, pp = m.FuseMapPoints(pending, cams, poses, mp, TH, float(np.log(1.2)))             # no synchronisation before this search
+    assert np.array_equal(pi, ci) and np.array_equal(pd, cd) and np.array_equal(pp, cp)
+    assert cp[0].sum() > 150 and (cd[0] <= TH_LOW).sum() > 100 and (ci[0][cd[0] <= TH_LOW] == idx[cd[0] <= TH_LOW]).mean() > 0.9
+    assert [kf.counts() for kf in pending] == ns and [kf.count() for kf in pending] == [n for n, _ in ns]
+
+
 # ---- (d) layer 3 against the composed reference ----
 @pytest.mark.parametrize("K", [1, 20])
 @pytest.mark.parametrize("with_skip", [False, True])

@@ -422,6 +422,42 @@ def test_from_frame_of_a_batch_loaded_handle_with_its_counts_on_the_device(oracl
     assert D.counts() == (len(k2), len(r2))
 
 
+def test_fuse_map_points_with_the_counts_fetched_first_and_with_them_pending(oracle):
+    """Two rig key frames from batch-loaded handles (320 x 240, both counts on the device only) through FuseMapPointsFisheye with K = 2 and 200 map
+    points on features of the first one, once counted first (counts()), once with their counts pending -- the search brings them home: the same
+    rows, bit for bit, and the same counts afterwards."""
+    import orb_slam3_amd as osa
+    from orb_slam3_amd import synth
+    from test_gpu_frame_fisheye import _extract_pairs
+    from test_gpu_stereo_fisheye import _rig_for_shifted_images
+    w, h, nf = 320, 240, 500
+    left, right = _extract_pairs(w, h, 2, nf)
+    exl, exr = osa.ORBextractor(nf, 1.2, 8, 20, 7), osa.ORBextractor(nf, 1.2, 8, 20, 7)
+    exl.extract_batch_device(left.data_ptr(), 2, w, h, w, w * h, (0, 0))
+    exr.extract_batch_device(right.data_ptr(), 2, w, h, w, w * h, (0, 0))
+    exl.stereo_fisheye_batch_device(exr, _rig_for_shifted_images())
+    sf = exl.GetScaleFactors().astype(f32)
+    isg = (f32(1.0) / (sf * sf)).astype(f32)
+    bounds = (0.0, float(w), 0.0, float(h))
+    m = osa.ORBmatcher(0.6, True)
+    cap = exl.batch_view().cap + exr.batch_view().cap
+    handles = [osa.DeviceFrame(m, cap).load_stereo_fisheye_batch(exl, exr, t, bounds=bounds, scale_factors=sf) for t in (0, 1)]   # counts on the device
+    counted = [osa.DeviceKeyFrame.from_frame_fisheye(m, D, isg) for D in handles]
+    pending = [osa.DeviceKeyFrame.from_frame_fisheye(m, D, isg) for D in handles]
+    ns = [kf.counts() for kf in counted]
+    _, kl, dl = exl.download(0)
+    _, kr, dr = exr.download(0)
+    assert ns[0] == (len(kl), len(kr)) and min(ns[0]) >= 100
+    sc = synth.make_fisheye_fuse_scene(np.random.default_rng(9), 1, 8, n_clutter=0)   # (the rig: views and the scale pyramid)
+    views = [sc["views"][0]] * 2
+    mp = _points_on_features(np.random.default_rng(13), views[0], (kl, kr), (dl, dr), sf, 100)
+    ci, cd, cp = m.FuseMapPointsFisheye(counted, views, mp, TH, sc["log_scale_factor"])
+    pi, pd, pp = m.FuseMapPointsFisheye(pending, views, mp, TH, sc["log_scale_factor"])      # no synchronisation before this search
+    assert np.array_equal(pi, ci) and np.array_equal(pd, cd) and np.array_equal(pp, cp)
+    assert cp[0].sum() > 100 and (cd[0, 0] <= TH_LOW).sum() > 50 and ((cd[0, 1] <= TH_LOW) & (ci[0, 1] >= len(kl))).sum() > 50
+    assert [kf.counts() for kf in pending] == ns and [kf.count() for kf in pending] == [a + b for a, b in ns]
+
+
 # ---- (5) degenerate shapes ----
 def test_degenerate_shapes(oracle, scene3, ref3):
     import orb_slam3_amd as osa

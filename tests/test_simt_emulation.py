@@ -324,3 +324,14 @@ def test_frame_handle_adopts_its_pending_count_stand_alone_under_sanitizers(tmp_
     a copy that runs past the caller's array ends the run."""
     r = _stand_alone_under_sanitizers(tmp_path, "frame_pending_count_check")
     assert r.returncode == 0 and "frame pending count ok" in r.stdout and "FAILED" not in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+def test_key_frame_paths_of_both_kinds_stand_alone_under_sanitizers(tmp_path):
+    """tests/cpp/keyframe_paths_check.cpp: per kind (monocular, fisheye-stereo) key frames of one 320 x 240 frame made from host arrays, from a
+    host-loaded handle and from a batch-loaded handle of a capacity above N (count pending; a copy of it counted first), through
+    orbx_keyframe_fuse_search[_fisheye] (K = 1, K = 2, one query set empty), orbx_keyframe_fuse_map_points[_fisheye] (K = 2, 300 map points, with and
+    without skip / projected) and orbx_keyframe_compute_bow (with and without id buffers): equal results from all of them, the pending one ends with
+    the counted one's counts, the caller's arrays (heap blocks of exactly the needed size, filled with a sentinel) untouched beyond the rows in use;
+    every entry point refuses the other kind's key frame before it enqueues anything.  Under the same sanitizers as the programs above."""
+    r = _stand_alone_under_sanitizers(tmp_path, "keyframe_paths_check")
+    assert r.returncode == 0 and "keyframe paths ok" in r.stdout and "FAILED" not in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
