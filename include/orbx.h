@@ -153,10 +153,13 @@ int orbx_download_wait(orbx_extractor *ex);
  * dst must hold (h+38) rows of dst_stride >= w+38 bytes; the ROI origin is dst + 19*dst_stride + 19.
  * LEVEL 0 of a batched extraction of ps_min_frames (48) frames or more is not copied into the library's pyramid (its kernels read the caller's
  * frames in place): the first orbx_get_level / orbx_get_level_device of level 0 after such a batch writes the padded level from those frames.
- * That is only possible while the frames are still the library's to read, i.e. BEFORE the orbx_sync / orbx_download_wait that hands them back to
- * the caller: afterwards the request fails with ORBX_E_STALE rather than return a level built from whatever the buffer holds by then.  (The frames
- * of orbx_extract_batch_host live in the library's upload slab, which is kept until the call after the next.)  orbx_get_level_device(0) of such a
- * batch synchronises the extractor's stream before it returns the pointer; for every other level and batch it is a pure getter. */
+ * After orbx_extract_batch_device that is only possible while the frames are still the library's to read, i.e. BEFORE the orbx_sync /
+ * orbx_download_wait that hands them back to the caller (a wait that completes a download issued before the batch does not): afterwards the
+ * request fails with ORBX_E_STALE rather than return a level built from whatever the buffer holds by then, and so do orbx_debug_level_blurred,
+ * orbx_debug_fused_patches and the extractor's first orbx_stereo_batch_device, which need level 0 too.  The frames of orbx_extract_batch_host live
+ * in the library's upload slab, which is kept until the call after the next: level 0 of such a batch can be asked for as long as it is the last
+ * batch, also after orbx_sync / orbx_download_wait.  orbx_get_level_device(0) of an in-place batch synchronises the extractor's stream before it
+ * returns the pointer; for every other level and batch it is a pure getter. */
 int orbx_get_level(orbx_extractor *ex, int frame, int level, uint8_t *dst, size_t dst_stride);
 int orbx_level_size(orbx_extractor *ex, int width, int height, int level, int *w, int *h);
 /* Device pointer to the padded level (for device-resident consumers such as the stereo matcher). */
@@ -178,8 +181,9 @@ int orbx_debug_level_keypoints(orbx_extractor *ex, int frame, int level, orbx_ke
 int orbx_debug_level_blurred(orbx_extractor *ex, int frame, int level, uint8_t *dst, size_t dst_stride);
 /* The blur on demand of k_describe_fused (no blurred pyramid exists then): the 37 x 37 blurred pixels around keypoint k of `frame` of the last batch,
  * dst[k][37][37] for the first min(count, cap_keypoints) keypoints in OUTPUT order, centre = the keypoint's level pixel; pixels outside the level are
- * its BORDER_REFLECT_101 extension.  Re-runs the descriptor kernel of the last batch (its inputs must still be valid).  Returns the number of
- * patches, or < 0 (ORBX_E_BAD_ARG when the extractor uses the blurred slab: orbx_debug_level_blurred). */
+ * its BORDER_REFLECT_101 extension.  Re-runs the descriptor kernel of the last batch, so it is refused with ORBX_E_STALE once level 0 was read in
+ * place from frames that have been released (orbx_get_level).  Returns the number of patches, or < 0 (ORBX_E_BAD_ARG when the extractor uses the
+ * blurred slab: orbx_debug_level_blurred). */
 int orbx_debug_fused_patches(orbx_extractor *ex, int frame, uint8_t *dst, int cap_keypoints);
 /* Which paths the last batch took (bench / stress tests): out[0] = cells that went to the FAST list pass (k_fast_wave_list: corners at iniThFAST
  * that all lost the NMS, or a strip / cell whose candidate queue overflowed), out[1] = cells of the batch, out[2..4] = (frame, level) quad-trees with

@@ -147,13 +147,16 @@ struct orbx_extractor {
     int ps_wg_target = 512;     // workgroups a launch should have (2 per CU): 256 frames -> 2 bands, 128 -> 4 (KITTI 150 -> 104 us, TUM-VI 328 -> 222 us against 2 bands)
     int ps_min_frames = 48;   // batches smaller than ps_min_frames keep the per-level launches (a band is one workgroup: too few to fill the device; measured equal at 16 frames, 3 % slower at 32, 5 % faster at 64, 14 % at 128)
     // Level 0 in place: a batch extracted by k_pyr_stream + k_fast_strip + k_describe_fused reads level 0 from the caller's frames (which orbx.h
-    // keeps untouched until orbx_sync / orbx_download_wait) and leaves the slab's level 0 unwritten; the few readers of the padded level 0
+    // keeps untouched until orbx_sync / orbx_download_wait; the upload slab for orbx_extract_batch_host) and leaves the slab's level 0 unwritten; the few readers of the padded level 0
     // (orbx_get_level, the stereo rig's SAD stage, the blurred-level debug readout) materialise it first: materialize_level0()
     bool lvl0_inplace = false;
-    // level 0 of an in-place batch is written on REQUEST from the caller's frames -- which include/orbx.h lets the caller overwrite after orbx_sync /
-    // orbx_download_wait.  Those two calls therefore mark the frames released; a request for level 0 after that is refused (ORBX_E_STALE) instead of
-    // answered from whatever the buffer holds by then.  in0_copy_seq = downloads issued when the batch was enqueued (a download issued later covers it).
+    // level 0 of an in-place batch is written on REQUEST from the frames it was extracted from.  Frames handed to orbx_extract_batch_device
+    // (in0_callers) are the caller's to overwrite after orbx_sync / orbx_download_wait (include/orbx.h): those two calls mark them released, and level 0
+    // or a re-run of k_describe_fused (orbx_debug_fused_patches) is refused after that (ORBX_E_STALE) instead of answered from whatever the buffer
+    // holds by then.  Frames of orbx_extract_batch_host lie in the library's own upload slab, which nothing overwrites while the batch is the last
+    // one: they are never released.  in0_copy_seq = downloads issued when the batch was enqueued (a download issued later covers it).
     bool in0_released = false;
+    bool in0_callers = false;
     unsigned in0_copy_seq = 0;
     hipEvent_t in0_event = nullptr;   // "input consumed" event of the in-place batch (upload slab of orbx_extract_batch_host): re-recorded behind the materialisation
     const uint8_t *in0_images = nullptr;

@@ -725,6 +725,13 @@ static int launch_pyr_base(orbx_extractor *ex, const uint8_t *d_images, int n, s
     return ORBX_OK;
 }
 
+// an in-place batch whose frames orbx_sync / orbx_download_wait have handed back to the caller: nothing may read level 0 from them any more
+static int level0_stale() {
+    set_error("level 0 of the last batch was read in place from the caller's frames and never copied; orbx_sync / orbx_download_wait have since released "
+              "those frames to the caller -- ask for level 0 (orbx_get_level / orbx_get_level_device) before that call");
+    return ORBX_E_STALE;
+}
+
 }  // namespace orbx
 
 // The padded level 0 of the last batch, if that batch was extracted in place (extractor_state.h): written now, on the extractor's stream, from the
@@ -732,11 +739,7 @@ static int launch_pyr_base(orbx_extractor *ex, const uint8_t *d_images, int n, s
 int orbx_materialize_level0(orbx_extractor *ex) {
     if (!ex) return ORBX_E_BAD_ARG;
     if (!ex->lvl0_inplace) return ORBX_OK;
-    if (ex->in0_released) {
-        set_error("level 0 of the last batch was read in place from the caller's frames and never copied; orbx_sync / orbx_download_wait have since released "
-                  "those frames to the caller -- ask for level 0 (orbx_get_level / orbx_get_level_device) before that call");
-        return ORBX_E_STALE;
-    }
+    if (ex->in0_released) return orbx::level0_stale();
     ORBX_HIP(hipSetDevice(ex->device));
     int r = orbx::launch_pyr_base(ex, ex->in0_images, ex->last_batch, ex->in0_row_stride, ex->in0_frame_stride, ex->pyr_cur(), ex->stream, false);
     if (r != ORBX_OK) return r;
@@ -781,6 +784,7 @@ static int enqueue_extract(orbx_extractor *ex, const uint8_t *d_images, int n, s
     ex->lvl0_inplace = inplace0;
     ex->in0_images = d_images; ex->in0_row_stride = row_stride; ex->in0_frame_stride = frame_stride;
     ex->in0_released = false; ex->in0_copy_seq = ex->copy_issued; ex->in0_event = inplace0 ? ev_input_consumed : nullptr;
+    ex->in0_callers = ev_input_consumed == nullptr;   // orbx_extract_batch_device; the host route's frames lie in the library's own upload slab
     if (!inplace0) {
         int r = launch_pyr_base(ex, d_images, n, row_stride, frame_stride, pyr, pst, true);
         if (r != ORBX_OK) return r;
@@ -1224,7 +1228,7 @@ int orbx_sync(orbx_extractor *ex) {
     ORBX_HIP(hipStreamSynchronize(ex->aux_stream));
     ORBX_HIP(hipStreamSynchronize(ex->match_stream));
     ORBX_HIP(hipStreamSynchronize(ex->in_stream));
-    if (ex->lvl0_inplace) ex->in0_released = true;   // the caller may overwrite the frames from here on (include/orbx.h)
+    if (ex->lvl0_inplace && ex->in0_callers) ex->in0_released = true;   // the caller may overwrite the frames from here on (include/orbx.h)
     return ORBX_OK;
 }
 
@@ -1330,7 +1334,7 @@ int orbx_download_wait(orbx_extractor *ex) {
     const unsigned slot = ex->copy_waited & 1;
     ORBX_HIP(hipEventSynchronize(ex->ev_copy_done[slot]));
     ex->copy_waited++;
-    if (ex->lvl0_inplace && ex->copy_waited > ex->in0_copy_seq) ex->in0_released = true;   // a download issued after the in-place batch has completed: its frames are the caller's again
+    if (ex->lvl0_inplace && ex->in0_callers && ex->copy_waited > ex->in0_copy_seq) ex->in0_released = true;   // a download issued after the in-place batch has completed: its frames are the caller's again
     if (ex->h_err[slot] != 0) {
         set_error("device-side consistency check failed, code " + std::to_string(ex->h_err[slot]));
         ex->h_err[slot] = 0;
@@ -1499,6 +1503,7 @@ int orbx_debug_level_blurred(orbx_extractor *ex, int frame, int level, uint8_t *
 int orbx_debug_fused_patches(orbx_extractor *ex, int frame, uint8_t *dst, int cap_keypoints) {
     if (!ex || !dst || frame < 0 || frame >= ex->last_batch || cap_keypoints <= 0) return ORBX_E_BAD_ARG;
     if (!ex->fused_blur) return ORBX_E_BAD_ARG;   // k_describe reads the blurred slab: orbx_debug_level_blurred
+    if (ex->lvl0_inplace && ex->in0_released) return level0_stale();   // the kernel would read level 0 from frames that are the caller's again
     ORBX_HIP(hipSetDevice(ex->device));
     ORBX_HIP(hipStreamSynchronize(ex->stream));
     DevBuf scratch;

@@ -269,6 +269,14 @@ class ORBextractor:
         check(self._L.orbx_get_level(self._h, frame, level, ptr(out), out.strides[0]), "orbx_get_level")
         return out
 
+    def get_level_device(self, level: int, frame: int = 0):
+        """(device pointer, pitch) of the padded level of `frame` in the library's pyramid: (h + 38) rows of `pitch` bytes, the first w + 38 of each
+        are the level with its ring.  Valid until the next extract call; level 0 of a batch that read its frames in place is written, and complete,
+        when this returns."""
+        p, pitch = C.c_void_p(), C.c_size_t(0)
+        check(self._L.orbx_get_level_device(self._h, frame, level, C.byref(p), C.byref(pitch)), "orbx_get_level_device")
+        return p.value, pitch.value
+
     @property
     def mvImagePyramid(self):
         """ROI views of the last single-frame pyramid (public member of the reference, ORBextractor.h:83)."""
@@ -296,9 +304,7 @@ class ORBextractor:
     def debug_fused_patches(self, frame: int = 0, cap: int = 4096) -> np.ndarray:
         """(n, 37, 37) blurred pixels around the keypoints of `frame` as k_describe_fused computed them in LDS (output order)."""
         out = np.zeros((cap, 37, 37), np.uint8)
-        n = self._L.orbx_debug_fused_patches(self._h, frame, ptr(out), cap)
-        if n < 0:
-            raise RuntimeError(f"orbx_debug_fused_patches: {n}")
+        n = check(self._L.orbx_debug_fused_patches(self._h, frame, ptr(out), cap), "orbx_debug_fused_patches")
         return out[:n]
 
     def stage_stats(self) -> dict:

@@ -96,6 +96,28 @@ def test_emulated_extractor_open_issue_image(emul_lib):
     assert "emulation ok 1008" in out
 
 
+LEVEL0_IN_PLACE = """
+import os, torch
+torch.Tensor.cuda = lambda self, *a, **k: self   # "device" memory is host memory under the emulator
+torch.Tensor.pin_memory = lambda self, *a, **k: self
+os.environ["ORBX_PYR_STREAM_MIN"] = "1,3"   # three frames take k_pyr_stream, one band each, and read level 0 in place
+import test_gpu_level0_in_place as tl
+canvas = synth.make_canvas(1)
+n = tl.check_strided_frames(canvas, 517, 389, 700, 3, True, "random")
+assert tl.check_host_route(canvas, "sync") == n
+print('emulation ok', n)
+"""
+
+
+def test_emulated_level0_in_place_strided_frames_and_host_route_after_sync(emul_lib):
+    """tests/test_gpu_level0_in_place.py on the emulator: three 517 x 389 frames that are an offset, gapped view with an odd row stride of a larger
+    allocation full of random bytes, read in place by k_pyr_stream, k_fast_strip, the FAST list pass and k_describe_fused -- every stage == oracle, and
+    orbx_sync then releases them (ORBX_E_STALE for level 0); three frames through orbx_extract_batch_host: level 0, its blur and the fused patches can
+    still be had after orbx_sync, from the library's upload slab, with the caller's frames overwritten."""
+    out = _child(LEVEL0_IN_PLACE, {"ORBX_TEST_EMULATOR": "1"})
+    assert "emulation ok 2111" in out   # 705 + 704 + 702 keypoints
+
+
 PIPELINE = """
 # the bench's loop shape: two batches in flight (enqueue i, then wait for i - 1), alternating inputs and entry points
 W, H, NF, B, STEPS = 480, 360, 600, 9, 3   # 9 frames: the batch forms of the kernels (up to 8 frames take the short row blocks of the single-frame call)
