@@ -910,6 +910,43 @@ typedef struct orbx_keyframe_gate {
 int orbx_keyframe_search_for_triangulation(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
                                            int check_orientation, const orbx_keyframe_gate *gate, int32_t *matches12);
 
+/* ---- The same five calls for FISHEYE-STEREO key frames (orbx_keyframe_create_host_fisheye / orbx_keyframe_from_frame_fisheye; KeyFrame::NLeft != -1) ----
+ * The calls above refuse such a key frame and these refuse a monocular one (ORBX_E_BAD_ARG before anything is enqueued); a rig frame handle goes with
+ * rig key frames.  Everything said above holds -- set once, the event and done-flag rule, one upload run, one download run and one synchronisation
+ * whatever n_kf is, nothing waiting before the launches unless flags are given for a side whose N is pending.  All indices the caller sees are in the
+ * reference's feature numbering, [0, N_left) the left camera's and [N_left, N) the right camera's; on the device a rig key frame works in ROW space
+ * (the right camera's rows from a fixed offset on) and both renumberings run there, with counts that may still be on the device.  The limit of 16384
+ * is on the key frame's row extent (a key frame made from a batch-loaded handle keeps the handle's left capacity as that offset).
+ *   orbx_keyframe_compute_bow_fisheye: KeyFrame::ComputeBoW over all N = N_left + N_right descriptor rows; word_id / node_id [N], left then right.
+ *   orbx_keyframe_bow_from_frame_fisheye: the mBowVec / mFeatVec copy from the fisheye handle the key frame was made from (after its
+ *     orbx_frame_compute_bow_fisheye); preconditions and ORBX_E_STALE as orbx_keyframe_bow_from_frame; no host synchronisation.
+ *   orbx_frame_search_by_bow_resident_fisheye: SearchByBoW(kfs[k], F, ...) with F.Nleft != -1 (ORBmatcher.cc:283-392) for k < n_kf.  valid[k]: N_k
+ *     entries.  match[k * match_stride + iF] = a feature of key frame k in [0, N_k) or -1 for iF in [0, N): row k equals
+ *     orbx_frame_search_by_bow_fisheye's for the same key frame given as host arrays.
+ *   orbx_keyframe_search_by_bow_fisheye: SearchByBoW(pKF1, kfs2[k], ...) between rig key frames.  The reference skips the right camera's features as
+ *     queries and as candidates (:800-802, :820-822): match12 spans kf1's N features, the right camera's entries are always -1, values are below
+ *     N_left of kfs2[k]; equal to orbx_search_by_bow_keyframes with every right-camera feature marked as having no map point.
+ *   orbx_keyframe_search_for_triangulation_fisheye: SearchForTriangulation between two rig key frames with KannalaBrandt8::epipolarConstrain on the
+ *     device (:1036-1072), as orbx_search_for_triangulation_kb8.  The gate carries what the key frames do not hold (see orbx_kb8_gate for the
+ *     fields); coarse: no gate at all.  matches12[i1] = a feature of kf2 in [0, N2) or -1, i1 < N1; returns the number of matches.  N1 must be
+ *     known (one orbx_keyframe_count otherwise), as in the pinhole form. */
+typedef struct orbx_keyframe_kb8_gate {
+    const float *level_sigma2_1, *level_sigma2_2; /* mvLevelSigma2 of pKF1 / pKF2 [nlevels = the key frames'] */
+    int nlevels;
+    float cam1[2][8], cam2[2][8];
+    float R12[4][9], t12[4][3];
+    int coarse;
+} orbx_keyframe_kb8_gate;
+int orbx_keyframe_compute_bow_fisheye(orbx_matcher *m, orbx_keyframe *kf, const orbx_vocabulary *voc, int levelsup, int32_t *word_id, int32_t *node_id);
+int orbx_keyframe_bow_from_frame_fisheye(orbx_matcher *m, orbx_keyframe *kf, orbx_frame *frame);
+int orbx_frame_search_by_bow_resident_fisheye(orbx_matcher *m, orbx_frame *f, int n_kf, orbx_keyframe *const *kfs, const uint8_t *const *valid,
+                                              float nnratio, int check_orientation, int32_t *match, int match_stride, int32_t *nmatches);
+int orbx_keyframe_search_by_bow_fisheye(orbx_matcher *m, orbx_keyframe *kf1, const uint8_t *valid1, int n_kf, orbx_keyframe *const *kfs2,
+                                        const uint8_t *const *valid2, float nnratio, int check_orientation, int32_t *match12, int match_stride,
+                                        int32_t *nmatches);
+int orbx_keyframe_search_for_triangulation_fisheye(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                                   int check_orientation, const orbx_keyframe_kb8_gate *gate, int32_t *matches12);
+
 /* Frame::ComputeStereoMatches (Frame.cc:811-981) for every frame of two resident batches: `left` and `right` must have
  * extracted batches of the same size and image shape (rectified stereo, lapping {0,0}).  Row-band Hamming match, 11x11
  * SAD sub-pixel refinement on the device-resident pyramids and the median outlier rejection all run on the device, on

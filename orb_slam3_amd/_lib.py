@@ -134,6 +134,12 @@ class KeyFrameGate(C.Structure):
                 ("level_sigma2_2", C.c_void_p)]
 
 
+class KeyFrameKb8Gate(C.Structure):
+    """orbx_keyframe_kb8_gate: what orbx_keyframe_search_for_triangulation_fisheye needs beyond the two resident rig key frames."""
+    _fields_ = [("level_sigma2_1", C.c_void_p), ("level_sigma2_2", C.c_void_p), ("nlevels", C.c_int), ("cam1", C.c_float * 16), ("cam2", C.c_float * 16),
+                ("R12", C.c_float * 36), ("t12", C.c_float * 12), ("coarse", C.c_int)]
+
+
 PAIR_PREDICATE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
 _lib = None
@@ -167,6 +173,8 @@ SYMBOLS = [
     "orbx_keyframe_search_for_triangulation",
     "orbx_keyframe_from_frame_fisheye", "orbx_keyframe_create_host_fisheye", "orbx_keyframe_counts", "orbx_keyframe_fuse_search_fisheye",
     "orbx_keyframe_fuse_map_points_fisheye",
+    "orbx_keyframe_compute_bow_fisheye", "orbx_keyframe_bow_from_frame_fisheye", "orbx_frame_search_by_bow_resident_fisheye",
+    "orbx_keyframe_search_by_bow_fisheye", "orbx_keyframe_search_for_triangulation_fisheye",
 ]
 
 
@@ -293,6 +301,11 @@ def lib() -> C.CDLL:
     L.orbx_frame_search_by_bow_resident.argtypes = [vp, vp, i32, C.POINTER(vp), C.POINTER(vp), f32, i32, vp, i32, vp]
     L.orbx_keyframe_search_by_bow.argtypes = [vp, vp, vp, i32, C.POINTER(vp), C.POINTER(vp), f32, i32, vp, i32, vp]
     L.orbx_keyframe_search_for_triangulation.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(KeyFrameGate), vp]
+    L.orbx_keyframe_compute_bow_fisheye.argtypes = [vp, vp, vp, i32, vp, vp]
+    L.orbx_keyframe_bow_from_frame_fisheye.argtypes = [vp, vp, vp]
+    L.orbx_frame_search_by_bow_resident_fisheye.argtypes = L.orbx_frame_search_by_bow_resident.argtypes
+    L.orbx_keyframe_search_by_bow_fisheye.argtypes = [vp, vp, vp, i32, C.POINTER(vp), C.POINTER(vp), f32, i32, vp, i32, vp]
+    L.orbx_keyframe_search_for_triangulation_fisheye.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(KeyFrameKb8Gate), vp]
     L.orbx_keyframe_from_frame_fisheye.argtypes = [vp, vp, vp, C.POINTER(vp)]
     L.orbx_keyframe_create_host_fisheye.argtypes = [vp, C.POINTER(FrameDesc), vp, i32, vp, C.POINTER(vp)]
     L.orbx_keyframe_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

@@ -132,7 +132,10 @@ public:
         const int st = orbx_keyframe_counts(kf_, &nLeft, &nRight);
         if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_counts: ") + orbx_status_string(st));
     }
-    // KeyFrame::ComputeBoW on the resident descriptors (orbx_keyframe_compute_bow): the key frame keeps mFeatVec for the resident SearchByBoW /
+    // KeyFrame::NLeft != -1: made by one of the two fisheye-stereo constructors.  ComputeBoW / BowFromFrame and the resident BoW searches of ORBmatcher
+    // dispatch on it (orbx_keyframe_*_fisheye); a list that mixes the two kinds throws, as Fuse does.
+    bool fisheye() const { return fisheye_; }
+    // KeyFrame::ComputeBoW on the resident descriptors (orbx_keyframe_compute_bow[_fisheye]): the key frame keeps mFeatVec for the resident SearchByBoW /
     // SearchForTriangulation overloads of ORBmatcher.  Set once; a second call with the same vocabulary and levelsup only returns the ids.  wordId /
     // nodeId (optional) receive N ids each -- mBowVec is folded from the word ids on the host.  Order this call before any BoW search is handed the
     // key frame (include/orbx.h, SHARING).
@@ -145,6 +148,7 @@ public:
 
 private:
     orbx_keyframe *kf_ = nullptr;
+    bool fisheye_ = false;
 };
 
 class ORBmatcher {
@@ -425,8 +429,9 @@ public:
         const int N = F.count(), stride = std::max(N, 1);
         std::vector<int32_t> rows(std::max<size_t>(K, 1) * stride, -1);
         nmatches.assign(K, 0);
-        const int r = orbx_frame_search_by_bow_resident(m_, F.handle(), (int)K, h.data(), fl.data(), mfNNratio, mbCheckOrientation ? 1 : 0, rows.data(), stride,
-                                                        nmatches.data());
+        // fisheye-stereo key frames go with a fisheye-stereo frame (orbx_frame_search_by_bow_resident_fisheye, ORBmatcher.cc:283-392)
+        const auto search = allFisheye(vpKFs, "SearchByBoW") ? orbx_frame_search_by_bow_resident_fisheye : orbx_frame_search_by_bow_resident;
+        const int r = search(m_, F.handle(), (int)K, h.data(), fl.data(), mfNNratio, mbCheckOrientation ? 1 : 0, rows.data(), stride, nmatches.data());
         if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_by_bow_resident: ") + orbx_status_string(r) + " " + orbx_last_error());
         return splitRows(rows, stride, N, nmatches, vpMatch);
     }
@@ -445,8 +450,12 @@ public:
         const int N1 = KF1.count(), stride = std::max(N1, 1);
         std::vector<int32_t> rows(std::max<size_t>(K, 1) * stride, -1);
         nmatches.assign(K, 0);
-        const int r = orbx_keyframe_search_by_bow(m_, KF1.handle(), valid1.empty() ? nullptr : valid1.data(), (int)K, h.data(), fl.data(), mfNNratio,
-                                                  mbCheckOrientation ? 1 : 0, rows.data(), stride, nmatches.data());
+        // between fisheye-stereo key frames the right camera's features are neither queries nor candidates (:800-802, :820-822)
+        std::vector<DeviceKeyFrame *> all(vpKFs2);
+        all.push_back(&KF1);
+        const auto search = allFisheye(all, "SearchByBoW") ? orbx_keyframe_search_by_bow_fisheye : orbx_keyframe_search_by_bow;
+        const int r = search(m_, KF1.handle(), valid1.empty() ? nullptr : valid1.data(), (int)K, h.data(), fl.data(), mfNNratio,
+                             mbCheckOrientation ? 1 : 0, rows.data(), stride, nmatches.data());
         if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_search_by_bow: ") + orbx_status_string(r) + " " + orbx_last_error());
         return splitRows(rows, stride, N1, nmatches, vpMatches12);
     }
@@ -463,6 +472,26 @@ public:
         vMatchedPairs.clear();
         for (int i = 0; i < n1; i++) if (m12[i] >= 0) vMatchedPairs.emplace_back((size_t)i, (size_t)m12[i]);  // :1138-1143
         return r;
+    }
+    // the same member between two resident FISHEYE-STEREO key frames, KannalaBrandt8::epipolarConstrain on the device (:1036-1072;
+    // orbx_keyframe_search_for_triangulation_fisheye): `gate` = the level tables, the four cameras' parameters, the four relative poses and bCoarse
+    int SearchForTriangulation(DeviceKeyFrame &KF1, DeviceKeyFrame &KF2, const std::vector<uint8_t> &skip1, const std::vector<uint8_t> &skip2,
+                               const orbx_keyframe_kb8_gate &gate, std::vector<std::pair<size_t, size_t>> &vMatchedPairs) {
+        const int n1 = KF1.count();
+        std::vector<int32_t> m12((size_t)std::max(n1, 1), -1);
+        const int r = orbx_keyframe_search_for_triangulation_fisheye(m_, KF1.handle(), KF2.handle(), skip1.empty() ? nullptr : skip1.data(),
+                                                                     skip2.empty() ? nullptr : skip2.data(), mbCheckOrientation ? 1 : 0, &gate, m12.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_search_for_triangulation_fisheye: ") + orbx_status_string(r) + " " + orbx_last_error());
+        vMatchedPairs.clear();
+        for (int i = 0; i < n1; i++) if (m12[i] >= 0) vMatchedPairs.emplace_back((size_t)i, (size_t)m12[i]);  // :1138-1143
+        return r;
+    }
+    // the kind of a list of resident key frames: all fisheye-stereo or none (a mixed list throws, as Fuse does)
+    static bool allFisheye(const std::vector<DeviceKeyFrame *> &kfs, const char *who) {
+        size_t n = 0;
+        for (const DeviceKeyFrame *kf : kfs) n += kf && kf->fisheye() ? 1 : 0;
+        if (n != 0 && n != kfs.size()) throw std::invalid_argument(std::string(who) + ": fisheye-stereo and monocular key frames in one call");
+        return n != 0;
     }
     static int splitRows(const std::vector<int32_t> &rows, int stride, int n, const std::vector<int32_t> &nmatches, std::vector<std::vector<int32_t>> &out) {
         out.assign(nmatches.size(), std::vector<int32_t>());
@@ -778,12 +807,12 @@ inline DeviceKeyFrame::DeviceKeyFrame(ORBmatcher &matcher, const FrameView &KF, 
     if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_create_host: ") + orbx_status_string(st) + " " + orbx_last_error());
 }
 
-inline DeviceKeyFrame::DeviceKeyFrame(Fisheye, ORBmatcher &matcher, DeviceFrame &frame, const float *mvInvLevelSigma2) {
+inline DeviceKeyFrame::DeviceKeyFrame(Fisheye, ORBmatcher &matcher, DeviceFrame &frame, const float *mvInvLevelSigma2) : fisheye_(true) {
     const int st = orbx_keyframe_from_frame_fisheye(matcher.handle(), frame.handle(), mvInvLevelSigma2, &kf_);
     if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_from_frame_fisheye: ") + orbx_status_string(st) + " " + orbx_last_error());
 }
 inline DeviceKeyFrame::DeviceKeyFrame(ORBmatcher &matcher, const FrameView &left, const std::vector<orbx_keypoint> &keysRight,
-                                      const float *mvInvLevelSigma2) {
+                                      const float *mvInvLevelSigma2) : fisheye_(true) {
     orbx_frame_desc fd = left.c();
     const int st = orbx_keyframe_create_host_fisheye(matcher.handle(), &fd, keysRight.data(), (int)keysRight.size(), mvInvLevelSigma2, &kf_);
     if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_create_host_fisheye: ") + orbx_status_string(st) + " " + orbx_last_error());
@@ -845,19 +874,20 @@ inline void DeviceFrame::ComputeBoWFisheye(ORBmatcher &matcher, const ORBVocabul
 inline void DeviceKeyFrame::ComputeBoW(ORBmatcher &matcher, const ORBVocabularyDevice &voc, int levelsup, std::vector<int32_t> *wordId,
                                        std::vector<int32_t> *nodeId) {
     auto check = [](int st) { if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_compute_bow: ") + orbx_status_string(st) + " " + orbx_last_error()); };
+    const auto compute = fisheye_ ? orbx_keyframe_compute_bow_fisheye : orbx_keyframe_compute_bow;   // (a rig: all N = NLeft + NRight rows, left then right)
     if (!wordId && !nodeId) {
-        check(orbx_keyframe_compute_bow(matcher.handle(), kf_, voc.handle(), levelsup, nullptr, nullptr));
+        check(compute(matcher.handle(), kf_, voc.handle(), levelsup, nullptr, nullptr));
         return;
     }
     const int n = count();   // (the id buffers hold N entries)
     std::vector<int32_t> w((size_t)std::max(n, 1)), nd((size_t)std::max(n, 1));
-    check(orbx_keyframe_compute_bow(matcher.handle(), kf_, voc.handle(), levelsup, w.data(), nd.data()));
+    check(compute(matcher.handle(), kf_, voc.handle(), levelsup, w.data(), nd.data()));
     if (wordId) wordId->assign(w.begin(), w.begin() + n);
     if (nodeId) nodeId->assign(nd.begin(), nd.begin() + n);
 }
 
 inline void DeviceKeyFrame::BowFromFrame(ORBmatcher &matcher, DeviceFrame &frame) {
-    const int st = orbx_keyframe_bow_from_frame(matcher.handle(), kf_, frame.handle());
+    const int st = (fisheye_ ? orbx_keyframe_bow_from_frame_fisheye : orbx_keyframe_bow_from_frame)(matcher.handle(), kf_, frame.handle());
     if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_bow_from_frame: ") + orbx_status_string(st) + " " + orbx_last_error());
 }
 

@@ -381,20 +381,22 @@ public:
 
     // ---- the BoW-guided members on RESIDENT key frames (DeviceKeyFrame after ComputeBoW / BowFromFrame; KeyFrame::mpDevice in an integrated tree) ----
     // Each takes the DeviceKeyFrame beside its KeyFrame*, gathers the valid / skip flags with the reference's accessors as the overloads above do, and
-    // uploads nothing else of the key frames.  Monocular / rectified key frames only (NLeft == -1).  Like the Fuse overload on DeviceKeyFrames below,
-    // these compile against the mock types of the test tree but have NOT been run against the compiled reference.
+    // uploads nothing else of the key frames.  Key frames of one kind per call: monocular / rectified (NLeft == -1) or all fisheye-stereo (NLeft != -1,
+    // with a fisheye-stereo frame); a mixed list throws, as Fuse does.  Like the Fuse overload on DeviceKeyFrames below, these compile against the mock
+    // types of the test tree but have NOT been run against the compiled reference.
 
     // Tracking::Relocalization / TrackReferenceKeyFrame: SearchByBoW(vpKFs[k], F, vvpMapPointMatches[k]) (ORBmatcher.cc:223-425) for every candidate in
     // ONE device call (orbx_frame_search_by_bow_resident); DF after DeviceFrame::ComputeBoW with the key frames' vocabulary and levelsup.
     void SearchByBoW(const std::vector<KeyFrame *> &vpKFs, const std::vector<DeviceKeyFrame *> &vpDeviceKFs, Frame &F, DeviceFrame &DF,
                      std::vector<std::vector<MapPoint *>> &vvpMapPointMatches, std::vector<int> &nmatches) {
-        if (F.Nleft != -1) throw std::runtime_error("SearchByBoW(DeviceKeyFrame): monocular / rectified frames only");
         const size_t nkf = vpKFs.size();
         if (vpDeviceKFs.size() != nkf) throw std::invalid_argument("SearchByBoW: one DeviceKeyFrame per key frame");
+        const bool rig = F.Nleft != -1;   // (:283-392: the frame's right camera has a best match of its own)
         std::vector<std::vector<MapPoint *>> vpMPs(nkf);
         std::vector<std::vector<uint8_t>> valid(nkf);
         for (size_t k = 0; k < nkf; k++) {
-            if (vpKFs[k]->NLeft != -1) throw std::invalid_argument("SearchByBoW: resident key frames are monocular / rectified");
+            if ((vpKFs[k]->NLeft != -1) != rig || vpDeviceKFs[k]->fisheye() != rig)
+                throw std::invalid_argument("SearchByBoW: the frame and every key frame are of one kind, all fisheye-stereo or none");
             vpMPs[k] = vpKFs[k]->GetMapPointMatches();
             valid[k].resize(vpMPs[k].size());
             for (size_t i = 0; i < vpMPs[k].size(); i++) {
@@ -427,7 +429,8 @@ public:
                      std::vector<std::vector<MapPoint *>> &vvpMatches12, std::vector<int> &nmatches) {
         const size_t nkf = vpKFs2.size();
         if (vpDeviceKFs2.size() != nkf) throw std::invalid_argument("SearchByBoW: one DeviceKeyFrame per key frame");
-        if (pKF1->NLeft != -1) throw std::invalid_argument("SearchByBoW: resident key frames are monocular / rectified");
+        const bool rig = pKF1->NLeft != -1;   // (:800-802, :820-822: the right camera's features are skipped on both sides)
+        if (pDeviceKF1->fisheye() != rig) throw std::invalid_argument("SearchByBoW: the DeviceKeyFrame is not of its key frame's kind");
         const std::vector<MapPoint *> vpMapPoints1 = pKF1->GetMapPointMatches();
         const int n1 = (int)vpMapPoints1.size();
         std::vector<uint8_t> v1(n1);
@@ -435,7 +438,8 @@ public:
         std::vector<std::vector<MapPoint *>> vpMPs2(nkf);
         std::vector<std::vector<uint8_t>> v2(nkf);
         for (size_t k = 0; k < nkf; k++) {
-            if (vpKFs2[k]->NLeft != -1) throw std::invalid_argument("SearchByBoW: resident key frames are monocular / rectified");
+            if ((vpKFs2[k]->NLeft != -1) != rig || vpDeviceKFs2[k]->fisheye() != rig)
+                throw std::invalid_argument("SearchByBoW: key frames of one kind per call, all fisheye-stereo or none");
             vpMPs2[k] = vpKFs2[k]->GetMapPointMatches();
             v2[k].resize(vpMPs2[k].size());
             for (size_t i = 0; i < vpMPs2[k].size(); i++) { MapPoint *p = vpMPs2[k][i]; v2[k][i] = (p && !p->isBad()) ? 1 : 0; }   // :829-834
@@ -455,10 +459,46 @@ public:
     // LocalMapping::CreateNewMapPoints: SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse) (ORBmatcher.cc:907-1146) between two
     // resident PINHOLE key frames (orbx_keyframe_search_for_triangulation): the skip flags, F12 (the Eigen expression of Pinhole.cpp:109-112, as the
     // overload above builds it), the epipole and pKF2->mvLevelSigma2 are all that goes up.  One call per neighbour, as the reference's loop makes them.
+    // Two fisheye-stereo key frames (both carry mpCamera2, KannalaBrandt8 cameras): orbx_keyframe_search_for_triangulation_fisheye, the gate of
+    // SearchForTriangulationFisheye above without its keypoints -- those are the key frames' own rows.
     int SearchForTriangulation(KeyFrame *pKF1, DeviceKeyFrame *pDeviceKF1, KeyFrame *pKF2, DeviceKeyFrame *pDeviceKF2,
                                std::vector<std::pair<size_t, size_t>> &vMatchedPairs, const bool bOnlyStereo, const bool bCoarse = false) {
         GeometricCamera *pCamera1 = pKF1->mpCamera, *pCamera2 = pKF2->mpCamera;
-        if (pKF1->mpCamera2 || pKF2->mpCamera2 || pCamera1->GetType() != GeometricCamera::CAM_PINHOLE || pCamera2->GetType() != GeometricCamera::CAM_PINHOLE)
+        if (pKF1->mpCamera2 || pKF2->mpCamera2) {
+            if (!pKF1->mpCamera2 || !pKF2->mpCamera2 || !pDeviceKF1->fisheye() || !pDeviceKF2->fisheye())
+                throw std::invalid_argument("SearchForTriangulation(DeviceKeyFrame): one key frame is fisheye-stereo and the other is not");
+            GeometricCamera *cam1[2] = {pKF1->mpCamera, pKF1->mpCamera2}, *cam2[2] = {pKF2->mpCamera, pKF2->mpCamera2};
+            for (GeometricCamera *c : {cam1[0], cam1[1], cam2[0], cam2[1]})
+                if (c->GetType() != GeometricCamera::CAM_FISHEYE || c->size() != 8)
+                    throw std::invalid_argument("SearchForTriangulation(DeviceKeyFrame): KannalaBrandt8 cameras only");
+            Sophus::SE3f T1w = pKF1->GetPose();
+            Sophus::SE3f Tw2 = pKF2->GetPoseInverse();
+            Sophus::SE3f Tr1w = pKF1->GetRightPose();
+            Sophus::SE3f Twr2 = pKF2->GetRightPoseInverse();
+            const Sophus::SE3f T[2][2] = {{T1w * Tw2, T1w * Twr2}, {Tr1w * Tw2, Tr1w * Twr2}};   // [right1][right2]: Tll, Tlr, Trl, Trr (:936-939)
+            const int n1 = pKF1->N, n2 = pKF2->N;
+            std::vector<uint8_t> skip1(n1), skip2(n2);   // no feature of a rig is "stereo" (:980, :1008): bOnlyStereo leaves no query
+            for (int i = 0; i < n1; i++) skip1[i] = (pKF1->GetMapPoint(i) || bOnlyStereo) ? 1 : 0;
+            for (int i = 0; i < n2; i++) skip2[i] = (pKF2->GetMapPoint(i) || bOnlyStereo) ? 1 : 0;
+            orbx_keyframe_kb8_gate g;
+            std::memset(&g, 0, sizeof(g));
+            g.level_sigma2_1 = pKF1->mvLevelSigma2.data(); g.level_sigma2_2 = pKF2->mvLevelSigma2.data();
+            g.nlevels = (int)pKF2->mvLevelSigma2.size();
+            for (int c = 0; c < 2; c++)
+                for (int k = 0; k < 8; k++) { g.cam1[c][k] = cam1[c]->getParameter(k); g.cam2[c][k] = cam2[c]->getParameter(k); }
+            for (int a = 0; a < 2; a++)
+                for (int b = 0; b < 2; b++) {
+                    const Eigen::Matrix3f R = T[a][b].rotationMatrix();
+                    const Eigen::Vector3f t = T[a][b].translation();
+                    for (int r = 0; r < 3; r++) {
+                        for (int c = 0; c < 3; c++) g.R12[2 * a + b][3 * r + c] = R(r, c);
+                        g.t12[2 * a + b][r] = t(r);
+                    }
+                }
+            g.coarse = bCoarse ? 1 : 0;
+            return SearchForTriangulation(*pDeviceKF1, *pDeviceKF2, skip1, skip2, g, vMatchedPairs);
+        }
+        if (pCamera1->GetType() != GeometricCamera::CAM_PINHOLE || pCamera2->GetType() != GeometricCamera::CAM_PINHOLE)
             throw std::invalid_argument("SearchForTriangulation(DeviceKeyFrame): pinhole key frames only");
         Sophus::SE3f T1w = pKF1->GetPose();
         Sophus::SE3f T2w = pKF2->GetPose();

@@ -3128,7 +3128,8 @@ __global__ __launch_bounds__(256) void k_debug_kb8_gate(const Kb8Gate *__restric
 // an LDS list), then the gate runs over the list 64 pairs at a time with every lane busy, and a pair that passes lowers its query's key with an LDS atomic
 // (distance << 16 | 0xffff - position: the later of two equal candidates wins, :1017).  grid ceil(fa.n_nodes / 4), block 256; P as for k_replay_bow mode 2.
 constexpr int kTriListCap = 2048;   // pairs per wave between two flushes (8 KB)
-__global__ __launch_bounds__(256) void k_tri_kb8(BowProblem P) {
+// the body of k_tri_kb8 and k_tri_kb8_resident: the node of wave `threadIdx.x >> 6` of block blockIdx.x of problem P
+__device__ __forceinline__ void tri_kb8_wave(const BowProblem &P) {
     __shared__ uint32_t list_s[4][kTriListCap];
     __shared__ uint32_t keymin_s[4][64];
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -3214,6 +3215,11 @@ __global__ __launch_bounds__(256) void k_tri_kb8(BowProblem P) {
     }
     if (lane == 0 && nmatches) atomicAdd(&P.counters[1], nmatches);
 }
+__global__ __launch_bounds__(256) void k_tri_kb8(BowProblem P) { tri_kb8_wave(P); }
+// k_tri_kb8 for problems whose record lies in device memory behind k_bow_pair_resident (orbx_keyframe_search_for_triangulation_fisheye: both key frames
+// resident, their node counts patched into the record on the device), a problem per blockIdx.y.  The sides are in ROW space (the right camera's rows from
+// roff on), so Kb8Gate::n_left1 / n_left2 carry the two key frames' roff.  grid (ceil(max bound_a / 4), n_problems), block 256
+__global__ __launch_bounds__(256) void k_tri_kb8_resident(const BowProblem *__restrict__ probs) { tri_kb8_wave(probs[blockIdx.y]); }
 
 // the rotation-consistency filter over the matches of all nodes (:401-416, :882-897, :1120-1137) and the match count
 __device__ __forceinline__ void replay_bow_finish(const BowProblem &P) {
@@ -3488,6 +3494,63 @@ __global__ __launch_bounds__(256) void k_keyframe_bow_copy(const KeyFrameBowCopy
     if (i < nn) C.fv_node[i] = C.src_fv_node[i];
     if (i <= nn) C.ptr[i] = C.src_ptr[i];
     if (i < kept) C.index[i] = C.src_index[i];
+}
+
+// k_keyframe_bow_copy for a fisheye-stereo key frame (orbx_keyframe_bow_from_frame_fisheye).  Both sides are in ROW space, each with its own roff
+// (the key frame's is the handle's N_left where the host knew it at the copy, else the handle's): the right camera's per-row entries move from
+// src_roff + j to roff + j and the FeatureVector's indices -- rows -- are renumbered the same way.  Both counts are nl_host / nr_host or the
+// frame's count[0] / count[1] read on the device, clamped as k_keyframe_copy_fisheye clamped the key frame's.  grid ceil((cap + 1) / 256), block 256
+struct KeyFrameBowCopyFisheye {
+    KeyFrameBowCopy c;               // (c.n_host unused; c.cap = the key frame's rows)
+    int nl_host, nr_host, src_roff, src_cap, roff;
+};
+__global__ __launch_bounds__(256) void k_keyframe_bow_copy_fisheye(const KeyFrameBowCopyFisheye F) {
+    const KeyFrameBowCopy &C = F.c;
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    const int nl = min(F.nl_host >= 0 ? F.nl_host : min(max(C.src_count[0], 0), F.src_roff), F.roff);
+    const int nr = min(F.nr_host >= 0 ? F.nr_host : min(max(C.src_count[1], 0), F.src_cap - F.src_roff), C.cap - F.roff);
+    const int n = nl + nr;
+    const int nn = min(max(C.src_meta[0], 0), n), kept = min(max(C.src_meta[1], 0), n);
+    if (i == 0) { C.meta[0] = nn; C.meta[1] = kept; }
+    if (i < n) {
+        const int s = i < nl ? i : F.src_roff + i - nl, d = i < nl ? i : F.roff + i - nl;
+        C.word[d] = C.src_word[s]; C.node[d] = C.src_node[s]; C.angle[d] = C.src_angle[s];
+    }
+    if (i < nn) C.fv_node[i] = C.src_fv_node[i];
+    if (i <= nn) C.ptr[i] = C.src_ptr[i];
+    if (i < kept) {
+        const int r = C.src_index[i];
+        C.index[i] = r < F.src_roff ? min(max(r, 0), max(nl - 1, 0)) : F.roff + min(max(r - F.src_roff, 0), max(nr - 1, 0));
+    }
+}
+
+// k_bow_rig_rows: the tail of a resident BoW search between fisheye-stereo sides (run_bow_resident, rig).  The replay works in ROW space; the caller
+// gets the reference's feature numbering.  Problem k = blockIdx.y: out[i] for feature i < N of the side the rows are indexed by = the row's entry, a row
+// of the OTHER side, renumbered into that side's features (row r >= roff is feature N_left + r - roff); -1 stays.  All four counts are the host's or read
+// on the device (clamped as the key frame's / handle's own kernels clamp them), so nothing waits for a pending count; lane 0 writes them next to the
+// match counts: counts_out = N_left, N_right of A, then of B.  grid (ceil(max out_n / 256), n_problems), block 256
+struct BowRigRows {
+    const int32_t *in; int32_t *out; int32_t *counts_out;
+    const int32_t *count[2];               // side A, side B
+    int nl[2], nr[2], cap[2], roff[2];     // the host's counts (-1: on the device only), the rows the side holds, its right camera's first row
+    int out_n, index_side;                 // entries of out; the side the rows are indexed by (0 = A, 1 = B)
+};
+__global__ __launch_bounds__(256) void k_bow_rig_rows(const BowRigRows *__restrict__ recs) {
+    const BowRigRows &R = recs[blockIdx.y];
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    int nl[2], nr[2];
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        nl[s] = R.nl[s] >= 0 ? R.nl[s] : min(max(R.count[s][0], 0), R.roff[s]);
+        nr[s] = R.nr[s] >= 0 ? R.nr[s] : min(max(R.count[s][1], 0), R.cap[s] - R.roff[s]);
+    }
+    if (i == 0) { R.counts_out[0] = nl[0]; R.counts_out[1] = nr[0]; R.counts_out[2] = nl[1]; R.counts_out[3] = nr[1]; }
+    const bool ib = R.index_side != 0;
+    const int nli = ib ? nl[1] : nl[0], nri = ib ? nr[1] : nr[0], roffi = ib ? R.roff[1] : R.roff[0];
+    const int nlv = ib ? nl[0] : nl[1], roffv = ib ? R.roff[0] : R.roff[1];
+    if (i >= nli + nri || i >= R.out_n) return;
+    const int v = R.in[i < nli ? i : roffi + i - nli];
+    R.out[i] = v >= roffv ? v - roffv + nlv : v;
 }
 
 // ---------------------------------------------------------------------------------------------------------

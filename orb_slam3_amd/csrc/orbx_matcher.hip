@@ -2943,12 +2943,14 @@ int orbx_keyframe_fuse_map_points_fisheye(orbx_matcher *m, int n_kf, orbx_keyfra
 
 // ---------------------------------------------------------------------------------------------------------
 // BoW on resident key frames: KeyFrame::ComputeBoW / the mBowVec, mFeatVec part of KeyFrame::KeyFrame(Frame&), and the three BoW-guided matchers with
-// BOTH sides resident -- SearchByBoW(KeyFrame*, Frame&), SearchByBoW(KeyFrame*, KeyFrame*) and SearchForTriangulation (pinhole gates) -- through one
-// driver (run_bow_resident): only flags and problem records go up.
+// BOTH sides resident -- SearchByBoW(KeyFrame*, Frame&), SearchByBoW(KeyFrame*, KeyFrame*) and SearchForTriangulation (pinhole gates; between
+// fisheye-stereo key frames KannalaBrandt8::epipolarConstrain) -- through one driver (run_bow_resident): only flags and problem records go up.
+// Both kinds of key frame share every host path here, the kind being a `bool rig` of that path; the public entry points name the kind.
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 
 static_assert(sizeof(BowProblem) + sizeof(BowPairSrc) <= 512, "the per-problem upload of a resident BoW search (tests/test_gpu_keyframe_bow.py bounds it)");
+static_assert(sizeof(BowProblem) + sizeof(BowPairSrc) + sizeof(BowRigRows) <= 512, "the same between fisheye-stereo sides (tests/test_gpu_keyframe_bow_fisheye.py)");
 constexpr int kKeyFrameBowMax = 16384;   // k_frame_featvec sorts 8-byte keys in LDS: 128 KB at most
 
 int keyframe_bow_alloc(int cap, KeyFrameBow **out) {
@@ -2986,40 +2988,55 @@ struct BowSide {
     int n;       // N, or -1 while it is on the device only
     int cap;     // rows the side's arrays hold
     int bound;   // the host's bound on the FeatureVector's node count
-    int rows() const { return n >= 0 ? n : cap; }
+    // A fisheye-stereo side (roff >= 0) is in ROW space: the right camera's rows from roff on, its counts nl / nr (-1 with n).  A key frame made from a
+    // batch-loaded handle keeps the gap behind its left rows after its counts are adopted: what a call sizes per row (the flags, the match row, vbMatched2,
+    // the entries) goes by the row EXTENT, roff + N_right, not by N.
+    int roff = -1, nl = -1, nr = -1;
+    int feats() const { return n >= 0 ? n : cap; }                                   // features, or their bound
+    int rows() const { return roff < 0 || n < 0 ? feats() : roff + nr; }             // rows the kernels index
+    int flag_n() const { return roff < 0 ? n : rows(); }                             // entries of the side's flags as they go up
 };
 inline BowSide bow_side(const orbx_keyframe *kf) {
     const KeyFrameBow *b = kf->bow.load(std::memory_order_acquire);
     BowSide S;
     S.desc = kf->desc; S.angle = b->angle; S.fv_node = b->fv_node; S.fv_ptr = b->fv_ptr; S.fv_index = b->fv_index; S.fv_meta = b->fv_meta;
     S.count = kf->count; S.n = kf->host_n(); S.cap = kf->cap;
-    S.bound = std::min(S.rows(), b->voc->node_bound(b->levelsup));
+    if (kf->fisheye) { S.roff = kf->roff; S.nl = kf->host_left(); S.nr = kf->host_right(); }
+    S.bound = std::min(S.feats(), b->voc->node_bound(b->levelsup));
     return S;
 }
 inline BowSide bow_side(const orbx_frame *f) {
     BowSide S;
     S.desc = f->desc; S.angle = f->angle; S.fv_node = f->fv_node; S.fv_ptr = f->fv_ptr; S.fv_index = f->fv_index; S.fv_meta = f->fv_meta;
     S.count = f->count; S.n = f->host_n(); S.cap = f->cap;
-    S.bound = std::min(S.rows(), f->bow_voc->node_bound(f->bow_levelsup));
+    if (f->fisheye) { S.roff = f->roff; S.nl = f->host_left(); S.nr = f->host_right(); }
+    S.bound = std::min(S.feats(), f->bow_voc->node_bound(f->bow_levelsup));
     return S;
 }
 
-// The driver of the three resident BoW searches.  Problem k: A[k] against B[k] in `mode` (BowProblem::mode: 0 rows indexed by B's features, 1 / 2 by
-// A's); flags_a[k] / flags_b[k] (arrays may be NULL, entries may be NULL = no feature is switched off) are `valid` flags when invert, else `skip`
+// The driver of the resident BoW searches of both kinds of side.  Problem k: A[k] against B[k] in `mode` (BowProblem::mode: 0 / 3 rows indexed by B's
+// features, 1 / 2 by A's); flags_a[k] / flags_b[k] (arrays may be NULL, entries may be NULL = no feature is switched off) are `valid` flags when invert, else `skip`
 // flags, of A[k].n / B[k].n entries (the callers resolve N before they hand over flags).  The side the rows are indexed by is the same object in
 // every problem.  One upload run (flags, the level table of the gate, the records), k_bow_pair_resident, k_replay_bow_batch,
 // k_replay_bow_finish_batch, one download run (rows, match counts, the sides' counts), one synchronisation -- whatever np is, and with no host
-// synchronisation before the launches.  counts[2 k], counts[2 k + 1] = N of A[k], B[k] as read on the device.
+// synchronisation before the launches.  counts[4 k ..] = the counts of A[k], then of B[k], as read on the device: N and 0, of a rig side N_left and N_right.
+// rig: every side is a fisheye-stereo one, in ROW space.  The flags still come in the reference's feature numbering and are laid out by rows here (mode 1
+// also switches every right-camera row off on both sides, ORBmatcher.cc:800-802, :820-822 -- roff is on the host, so this needs no count), and
+// k_bow_rig_rows hands rows and values back in feature numbering, with both counts of both sides.  kb8 (mode 2, rig): the KannalaBrandt8 gate of
+// k_tri_kb8_resident, which then takes k_replay_bow_batch's place; its level table sigma2_1 and the record ride up beside sigma2_2.
 int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const BowSide *B, const uint8_t *const *flags_a, const uint8_t *const *flags_b,
                      bool invert, float nnratio, int check_orientation, const TriGate *gate, const float *sigma2_2, int nlevels, int32_t *match,
-                     int match_stride, int32_t *nmatches, std::vector<int32_t> &counts) {
-    const BowSide &O = mode == 0 ? B[0] : A[0];
-    const int nrows = O.rows();
+                     int match_stride, int32_t *nmatches, std::vector<int32_t> &counts, bool rig = false, const Kb8Gate *kb8 = nullptr,
+                     const float *sigma2_1 = nullptr) {
+    const bool to_b = mode == 0 || mode == 3;
+    const BowSide &O = to_b ? B[0] : A[0];
+    const int nrows = O.rows(), nfeat = O.feats();
+    // mode 3 appends up to two entries per query (BowProblem::entries)
+    auto entries_of = [&](int k) { return (size_t)(mode == 3 ? 2 : 1) * (size_t)std::max(std::max(A[k].rows(), B[k].rows()), 1); };
     size_t tot_bound = 0, tot_nb = 0, n_ent = 0;
     int max_bound = 1;
     for (int k = 0; k < np; k++) {
-        const size_t na = (size_t)A[k].rows(), nb = (size_t)B[k].rows();
-        tot_bound += (size_t)A[k].bound; tot_nb += nb; n_ent += std::max<size_t>(std::max(na, nb), 1);
+        tot_bound += (size_t)A[k].bound; tot_nb += (size_t)B[k].rows(); n_ent += entries_of(k);
         max_bound = std::max(max_bound, A[k].bound);
     }
     std::vector<BowProblem> probs((size_t)np);
@@ -3032,48 +3049,68 @@ int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const 
         if (flags_a && A[k].n > 0) flags[2 * (size_t)k] = flags_a[k];
         if (flags_b && B[k].n > 0) flags[2 * (size_t)k + 1] = flags_b[k];
     }
-    if (invert) {
-        std::vector<size_t> at(flags.size(), 0);
+    if (invert || rig) {
+        const bool left_only = rig && mode == 1;
+        constexpr size_t kNone = ~(size_t)0;
+        std::vector<size_t> at(flags.size(), kNone);
         for (size_t s = 0; s < flags.size(); s++) {
-            if (!flags[s]) continue;
-            const size_t n = (size_t)(s & 1 ? B[s / 2].n : A[s / 2].n);
+            const BowSide &S = s & 1 ? B[s / 2] : A[s / 2];
+            if (!flags[s] && !(left_only && S.rows() > S.roff)) continue;
             at[s] = skip.size();
-            for (size_t i = 0; i < n; i++) skip.push_back(flags[s][i] ? 0 : 1);
+            auto off = [&](size_t i) { return (uint8_t)((flags[s][i] != 0) == invert ? 0 : 1); };
+            if (!rig) {
+                for (size_t i = 0; i < (size_t)S.n; i++) skip.push_back(off(i));
+                continue;
+            }
+            skip.resize(at[s] + (size_t)S.rows(), 0);
+            uint8_t *row = skip.data() + at[s];
+            for (int i = 0; flags[s] && i < S.nl; i++) row[i] = off((size_t)i);
+            for (int j = 0; flags[s] && j < S.nr; j++) row[S.roff + j] = off((size_t)S.nl + j);
+            for (int r = S.roff; left_only && r < S.rows(); r++) row[r] = 1;
         }
         for (size_t s = 0; s < flags.size(); s++)
-            if (flags[s]) flags[s] = skip.data() + at[s];
+            flags[s] = at[s] == kNone ? nullptr : skip.data() + at[s];
     }
-    const float *dsig = nullptr;
+    const float *dsig = nullptr, *dsig1 = nullptr;
+    Kb8Gate *dK = nullptr;
     BowProblem *dP;
     BowPairSrc *dS;
-    int32_t *dpair, *dmatch, *dnm, *dcnt, *dhist, *dent;
+    BowRigRows *dR = nullptr;
+    int32_t *dpair, *dmatch, *dout, *dpc = nullptr, *dnm, *dcnt, *dhist, *dent;
     uint8_t *dtaken;
+    const size_t cnt_per = rig ? 4 : 2;
     ORBX_TRY(m->carve([&](Carve &C) {
-        // the uploads, side by side: the flags, the gate's level table, the records
+        // the uploads, side by side: the flags, the gate's level table(s) and the rig's gate, the records
         for (int k = 0; k < np; k++) {
-            probs[k].skip_a = C.up_opt(flags[2 * (size_t)k], (size_t)A[k].n);
-            probs[k].skip_b = C.up_opt(flags[2 * (size_t)k + 1], (size_t)B[k].n);
+            probs[k].skip_a = C.up_opt(flags[2 * (size_t)k], (size_t)A[k].flag_n());
+            probs[k].skip_b = C.up_opt(flags[2 * (size_t)k + 1], (size_t)B[k].flag_n());
         }
         if (gate) dsig = C.up(sigma2_2, (size_t)nlevels);
+        if (kb8) { dsig1 = C.up(sigma2_1, (size_t)nlevels); dK = C.take<Kb8Gate>(1); }
         dP = C.take<BowProblem>(np);
         dS = C.take<BowPairSrc>(np);
+        if (rig) dR = C.take<BowRigRows>(np);
         // device-only: the pairing; rows (filled with -1), match counts and the sides' counts side by side (one download run); vbMatched2, histograms +
-        // counters (zeroed by one fill); entries
+        // counters (zeroed by one fill); entries.  rig: the rows the caller gets are k_bow_rig_rows' (k_bow_pair_resident's one count per side is not used)
         dpair = C.take<int32_t>(tot_bound + 1);
         dmatch = C.take<int32_t>((size_t)np * nrows);
+        if (rig) dpc = C.take<int32_t>(2 * (size_t)np);
+        dout = rig ? C.take<int32_t>((size_t)np * nfeat) : dmatch;
         dnm = C.take<int32_t>(np);
-        dcnt = C.take<int32_t>(2 * (size_t)np);
+        dcnt = C.take<int32_t>(cnt_per * (size_t)np);
         dtaken = C.take<uint8_t>(tot_nb + 1);
         dhist = C.take<int32_t>((size_t)np * (ORBX_HISTO_LENGTH + 2));
         dent = C.take<int32_t>(n_ent);
     }));
+    std::vector<BowRigRows> rigs(rig ? (size_t)np : 0);
     {
         size_t op = 0, ot = 0, oe = 0;
         for (int k = 0; k < np; k++) {
             BowProblem &P = probs[k];
             const BowSide &a = A[k], &b = B[k];
             P.mode = mode;
-            if (gate) { P.gate = *gate; P.gate.sigma2_2 = dsig; }
+            if (mode == 3) P.nb_left = b.roff;   // a row >= roff is the right camera's
+            if (gate) { P.gate = *gate; P.gate.sigma2_2 = dsig; P.gate.kb8 = dK; }
             P.fa.node_id = a.fv_node; P.fa.node_ptr = a.fv_ptr; P.fa.index = a.fv_index; P.fa.n_nodes = 0;   // (both node counts: k_bow_pair_resident)
             P.fb.node_id = b.fv_node; P.fb.node_ptr = b.fv_ptr; P.fb.index = b.fv_index; P.fb.n_nodes = 0;
             P.desc_a = a.desc; P.angle_a = a.angle; P.na = a.rows();
@@ -3087,45 +3124,176 @@ int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const 
             BowPairSrc &S = srcs[k];
             memset(&S, 0, sizeof(S));
             S.node_a = a.fv_node; S.node_b = b.fv_node; S.meta_a = a.fv_meta; S.meta_b = b.fv_meta; S.count_a = a.count; S.count_b = b.count;
-            S.pair = dpair + op; S.counts_out = dcnt + 2 * (size_t)k; S.bound_a = a.bound; S.cap_a = a.cap; S.cap_b = b.cap;
-            op += (size_t)a.bound; ot += (size_t)b.rows(); oe += std::max<size_t>(std::max((size_t)a.rows(), (size_t)b.rows()), 1);
+            S.pair = dpair + op; S.counts_out = (rig ? dpc : dcnt) + 2 * (size_t)k; S.bound_a = a.bound; S.cap_a = a.cap; S.cap_b = b.cap;
+            op += (size_t)a.bound; ot += (size_t)b.rows(); oe += entries_of(k);
+            if (rig) {
+                BowRigRows &R = rigs[k];
+                memset(&R, 0, sizeof(R));
+                R.in = P.match; R.out = dout + (size_t)k * nfeat; R.counts_out = dcnt + 4 * (size_t)k; R.out_n = nfeat; R.index_side = to_b ? 1 : 0;
+                const BowSide *sd[2] = {&a, &b};
+                for (int s = 0; s < 2; s++) { R.count[s] = sd[s]->count; R.nl[s] = sd[s]->nl; R.nr[s] = sd[s]->nr; R.cap[s] = sd[s]->cap; R.roff[s] = sd[s]->roff; }
+            }
         }
+    }
+    if (kb8) {
+        Kb8Gate K = *kb8;
+        K.sigma2_1 = dsig1;
+        ORBX_TRY(m->h2d(dK, &K, sizeof(K)));
     }
     ORBX_TRY(m->h2d(dP, probs.data(), sizeof(BowProblem) * (size_t)np));
     ORBX_TRY(m->h2d(dS, srcs.data(), sizeof(BowPairSrc) * (size_t)np));
+    if (rig) ORBX_TRY(m->h2d(dR, rigs.data(), sizeof(BowRigRows) * (size_t)np));
     ORBX_HIP(m->fill(dmatch, 0xff, 4 * (size_t)np * nrows));
     ORBX_HIP(m->fill(dtaken, 0, (size_t)((const uint8_t *)(dhist + (size_t)np * (ORBX_HISTO_LENGTH + 2)) - dtaken)));   // vbMatched2, (padding,) histograms + counters
     hipLaunchKernelGGL(k_bow_pair_resident, dim3((unsigned)((max_bound + 255) / 256), (unsigned)np), dim3(256), 0, m->exec(), dP, (const BowPairSrc *)dS);
-    hipLaunchKernelGGL(k_replay_bow_batch, dim3((unsigned)((max_bound + 3) / 4), (unsigned)np), dim3(256), 0, m->exec(), (const BowProblem *)dP);
+    if (kb8) hipLaunchKernelGGL(k_tri_kb8_resident, dim3((unsigned)((max_bound + 3) / 4), (unsigned)np), dim3(256), 0, m->exec(), (const BowProblem *)dP);
+    else hipLaunchKernelGGL(k_replay_bow_batch, dim3((unsigned)((max_bound + 3) / 4), (unsigned)np), dim3(256), 0, m->exec(), (const BowProblem *)dP);
     hipLaunchKernelGGL(k_replay_bow_finish_batch, dim3((unsigned)np), dim3(64), 0, m->exec(), (const BowProblem *)dP);
+    if (rig) hipLaunchKernelGGL(k_bow_rig_rows, dim3((unsigned)((std::max(nfeat, 1) + 255) / 256), (unsigned)np), dim3(256), 0, m->exec(), (const BowRigRows *)dR);
     ORBX_HIP(hipGetLastError());
+    const int out_n = rig ? nfeat : nrows;   // entries of a row of dout
     std::vector<int32_t> rows;
     if (O.n >= 0) {
-        for (int k = 0; k < np; k++) ORBX_TRY(m->d2h(match + (size_t)k * match_stride, dmatch + (size_t)k * nrows, 4 * (size_t)O.n));
-    } else if (nrows > 0) {   // N comes back with the results
-        rows.resize((size_t)np * nrows);
-        ORBX_TRY(m->d2h(rows.data(), dmatch, 4 * (size_t)np * nrows));
+        for (int k = 0; k < np; k++) ORBX_TRY(m->d2h(match + (size_t)k * match_stride, dout + (size_t)k * out_n, 4 * (size_t)O.n));
+    } else if (out_n > 0) {   // N comes back with the results
+        rows.resize((size_t)np * out_n);
+        ORBX_TRY(m->d2h(rows.data(), dout, 4 * (size_t)np * out_n));
     }
-    counts.assign(2 * (size_t)np, 0);
+    std::vector<int32_t> got(cnt_per * (size_t)np, 0);
     ORBX_TRY(m->d2h(nmatches, dnm, 4 * (size_t)np));
-    ORBX_TRY(m->d2h(counts.data(), dcnt, 8 * (size_t)np));
+    ORBX_TRY(m->d2h(got.data(), dcnt, 4 * got.size()));
     ORBX_TRY(m->sync_and_deliver());
+    counts.assign(4 * (size_t)np, 0);
+    for (size_t k = 0; k < (size_t)np; k++)
+        for (size_t s = 0; s < 2; s++) {
+            counts[4 * k + 2 * s] = got[cnt_per * k + (rig ? 2 : 1) * s];
+            if (rig) counts[4 * k + 2 * s + 1] = got[4 * k + 2 * s + 1];
+        }
     if (O.n < 0) {
-        const int n = std::min(std::max(counts[mode == 0 ? 1 : 0], 0), O.cap);
+        const int32_t *c = counts.data() + (to_b ? 2 : 0);
+        const int n = std::min(std::max(c[0] + c[1], 0), O.feats());
         for (int k = 0; k < np; k++)
-            if (n > 0) memcpy(match + (size_t)k * match_stride, rows.data() + (size_t)k * nrows, 4 * (size_t)n);
+            if (n > 0) memcpy(match + (size_t)k * match_stride, rows.data() + (size_t)k * out_n, 4 * (size_t)n);
     }
     return ORBX_OK;
 }
 
-// a key frame a BoW search may take: on this device, with BoW; the vocabulary and levelsup it was made with come back for the cross-check
-inline bool keyframe_bow_ok(const orbx_matcher *m, const orbx_keyframe *kf, const orbx_vocabulary **voc, int *levelsup) {
-    if (!kf || kf->fisheye || kf->device != m->device) return false;
+// a key frame a BoW search of its kind (rig: fisheye-stereo) may take: on this device, with BoW; the vocabulary and levelsup it was made with come back
+// for the cross-check
+inline bool keyframe_bow_ok(const orbx_matcher *m, bool rig, const orbx_keyframe *kf, const orbx_vocabulary **voc, int *levelsup) {
+    if (!kf || kf->fisheye != rig || kf->device != m->device) return false;
     const KeyFrameBow *b = kf->bow.load(std::memory_order_acquire);
     if (!b) return false;
     if (*voc && (*voc != b->voc || *levelsup != b->levelsup)) return false;
     *voc = b->voc; *levelsup = b->levelsup;
     return true;
+}
+// the rows a key frame's BoW state may have to index: N, of a rig the row extent (capacity while the counts are pending)
+inline int keyframe_bow_rows(const orbx_keyframe *kf) {
+    return !kf->fisheye || kf->host_n() < 0 ? kf->rows_n() : kf->roff + kf->host_right();
+}
+// what a call learnt of a key frame's pending counts (run_bow_resident's counts of that side)
+inline void keyframe_adopt(orbx_keyframe *kf, const int32_t *c) {
+    if (kf->host_n() < 0) kf->adopt(c[0], c[1]);
+}
+
+// ---- The five calls below are one path per protocol for both kinds of key frame (rig: fisheye-stereo); the public entry points name the kind.
+
+// KeyFrame::ComputeBoW on the key frame's own descriptors through launch_compute_bow.  A rig key frame is a fisheye BowTarget in row space; its ids come
+// down renumbered into features [0, N) by k_frame_rows_to_features, so pending counts cost no wait.
+int keyframe_compute_bow(orbx_matcher *m, bool rig, orbx_keyframe *kf, const orbx_vocabulary *v, int levelsup, int32_t *word_id, int32_t *node_id) {
+    if (!m || !kf || !v || kf->fisheye != rig || kf->device != m->device || v->device != m->device) return ORBX_E_BAD_ARG;
+    KeyFrameBow *b = kf->bow.load(std::memory_order_acquire);
+    const bool down = word_id || node_id;
+    if (b) {   // `if (mBowVec.empty() || mFeatVec.empty())`: not computed again
+        if (b->voc != v || b->levelsup != levelsup) return ORBX_E_BAD_ARG;
+        if (!down) return ORBX_OK;
+    }
+    const int n_host = kf->host_n(), nc = kf->rows_n();   // nc: features the kernels may see
+    if (keyframe_bow_rows(kf) > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;
+    ORBX_HIP(hipSetDevice(m->device));
+    int32_t *dids = nullptr;   // rig: word ids, then node ids, in features [0, N)
+    ORBX_TRY(m->carve([&](Carve &A) { dids = A.take<int32_t>(2 * (size_t)nc); }));   // (monocular: the room the ids take in the staging)
+    if (!b) {
+        ORBX_TRY(keyframe_bow_alloc(kf->cap, &b));
+        b->voc = v; b->levelsup = levelsup;
+        hipError_t e = hipSuccess;
+        if (!kf->done.load(std::memory_order_acquire)) e = hipStreamWaitEvent(m->stream, kf->ready, 0);
+        if (e == hipSuccess) {
+            m->dirty = true;
+            e = launch_compute_bow(m, v, levelsup, BowTarget{kf->desc, kf->kps, kf->count, n_host, kf->cap, b->word, b->node, b->angle, b->fv_node, b->fv_ptr,
+                                                             b->fv_index, b->fv_meta, rig, kf->roff, {kf->host_left(), kf->host_right()}});
+        }
+        if (e == hipSuccess) e = hipEventRecord(b->ready, m->stream);
+        if (e != hipSuccess) { set_error(hipGetErrorString(e)); (void)hipStreamSynchronize(m->stream); m->dirty = false; keyframe_bow_free(b); return ORBX_E_HIP; }
+        kf->bow.store(b, std::memory_order_release);
+    } else {
+        ORBX_TRY(keyframe_bow_acquire(m, kf));
+    }
+    if (!down || nc == 0) return ORBX_OK;
+    const int32_t *src_w = b->word, *src_n = b->node;
+    if (rig) {
+        const int32_t *src[2] = {b->word, b->node};
+        for (int k = 0; k < 2; k++)
+            hipLaunchKernelGGL(k_frame_rows_to_features, dim3((unsigned)((nc + 255) / 256), 1), dim3(256), 0, m->exec(), src[k], 0, dids + (size_t)k * nc, nc,
+                               kf->count, kf->host_left(), kf->host_right(), kf->cap, kf->roff);
+        ORBX_HIP(hipGetLastError());
+        src_w = dids; src_n = dids + nc;
+    }
+    std::vector<int32_t> h;
+    int32_t cnt[2] = {n_host, 0};
+    if (n_host >= 0) {
+        if (word_id) ORBX_TRY(m->d2h(word_id, src_w, 4 * (size_t)nc));
+        if (node_id) ORBX_TRY(m->d2h(node_id, src_n, 4 * (size_t)nc));
+    } else {   // N comes back with the ids
+        h.resize(2 * (size_t)nc);
+        ORBX_TRY(m->d2h(h.data(), src_w, 4 * (size_t)nc));
+        ORBX_TRY(m->d2h(h.data() + nc, src_n, 4 * (size_t)nc));
+        ORBX_TRY(m->d2h(cnt, kf->count, rig ? 8 : 4));
+    }
+    ORBX_TRY(m->sync_and_deliver());
+    keyframe_bow_release(kf);
+    if (n_host < 0) {
+        kf->adopt(cnt[0], cnt[1]);
+        const int n = kf->host_n();
+        if (word_id) memcpy(word_id, h.data(), 4 * (size_t)n);
+        if (node_id) memcpy(node_id, h.data() + nc, 4 * (size_t)n);
+    }
+    return ORBX_OK;
+}
+
+// mBowVec(F.mBowVec), mFeatVec(F.mFeatVec) of KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-82): k_keyframe_bow_copy[_fisheye] on the owner's stream,
+// behind the frame's ComputeBoW and ahead of its next load; no host synchronisation.
+int keyframe_bow_from_frame(orbx_matcher *m, bool rig, orbx_keyframe *kf, orbx_frame *f) {
+    if (!m || !kf || !f || f->owner != m || f->fisheye != rig || kf->fisheye != rig || kf->device != m->device || kf->src_frame != f) return ORBX_E_BAD_ARG;
+    if (kf->bow.load(std::memory_order_acquire)) return ORBX_E_BAD_ARG;   // set once
+    if (f->load_seq != kf->src_seq) return ORBX_E_STALE;                  // the handle holds another frame by now
+    if (!f->bow_valid) return ORBX_E_BAD_ARG;
+    if ((rig ? keyframe_bow_rows(kf) : f->rows_n()) > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;
+    ORBX_HIP(hipSetDevice(m->device));
+    KeyFrameBow *b = nullptr;
+    int r = keyframe_bow_alloc(kf->cap, &b);
+    if (r != ORBX_OK) return r;
+    b->voc = f->bow_voc; b->levelsup = f->bow_levelsup;
+    KeyFrameBowCopyFisheye Cf;
+    memset(&Cf, 0, sizeof(Cf));
+    KeyFrameBowCopy &Cp = Cf.c;
+    Cp.src_count = f->count; Cp.n_host = f->host_n(); Cp.cap = kf->cap;
+    Cp.src_word = f->bow_word; Cp.src_node = f->bow_node; Cp.src_ptr = f->fv_ptr; Cp.src_index = f->fv_index; Cp.src_meta = f->fv_meta;
+    Cp.src_fv_node = f->fv_node; Cp.src_angle = f->angle;
+    Cp.word = b->word; Cp.node = b->node; Cp.ptr = b->fv_ptr; Cp.index = b->fv_index; Cp.meta = b->fv_meta; Cp.fv_node = b->fv_node; Cp.angle = b->angle;
+    m->dirty = true;
+    if (rig) {
+        Cf.nl_host = f->host_left(); Cf.nr_host = f->host_right(); Cf.src_roff = f->roff; Cf.src_cap = f->cap; Cf.roff = kf->roff;
+        hipLaunchKernelGGL(k_keyframe_bow_copy_fisheye, dim3((unsigned)((kf->cap + 256) / 256)), dim3(256), 0, m->stream, Cf);
+    } else {
+        hipLaunchKernelGGL(k_keyframe_bow_copy, dim3((unsigned)((kf->cap + 256) / 256)), dim3(256), 0, m->stream, Cp);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipEventRecord(b->ready, m->stream);
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); (void)hipStreamSynchronize(m->stream); m->dirty = false; keyframe_bow_free(b); return ORBX_E_HIP; }
+    kf->bow.store(b, std::memory_order_release);
+    return ORBX_OK;
 }
 
 }  // namespace
@@ -3136,100 +3304,44 @@ extern "C" {
 // (k_frame_bow_transform, k_frame_featvec): they take every array as an argument, so they run on the key frame's rows as they are -- no new code object,
 // no existing kernel's ISA touched.
 int orbx_keyframe_compute_bow(orbx_matcher *m, orbx_keyframe *kf, const orbx_vocabulary *v, int levelsup, int32_t *word_id, int32_t *node_id) {
-    if (!m || !kf || !v || kf->fisheye || kf->device != m->device || v->device != m->device) return ORBX_E_BAD_ARG;
-    KeyFrameBow *b = kf->bow.load(std::memory_order_acquire);
-    const bool down = word_id || node_id;
-    if (b) {   // `if (mBowVec.empty() || mFeatVec.empty())`: not computed again
-        if (b->voc != v || b->levelsup != levelsup) return ORBX_E_BAD_ARG;
-        if (!down) return ORBX_OK;
-    }
-    const int n_host = kf->host_n(), nc = kf->rows_n();   // nc: features the kernels may see
-    if (nc > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;
-    ORBX_HIP(hipSetDevice(m->device));
-    ORBX_TRY(m->reserve_staging(8 * (size_t)nc));   // the ids come down through it
-    if (!b) {
-        ORBX_TRY(keyframe_bow_alloc(kf->cap, &b));
-        b->voc = v; b->levelsup = levelsup;
-        hipError_t e = hipSuccess;
-        if (!kf->done.load(std::memory_order_acquire)) e = hipStreamWaitEvent(m->stream, kf->ready, 0);
-        if (e == hipSuccess) {
-            m->dirty = true;
-            e = launch_compute_bow(m, v, levelsup, BowTarget{kf->desc, kf->kps, kf->count, n_host, kf->cap, b->word, b->node, b->angle, b->fv_node, b->fv_ptr,
-                                                             b->fv_index, b->fv_meta, false, 0, {-1, -1}});
-        }
-        if (e == hipSuccess) e = hipEventRecord(b->ready, m->stream);
-        if (e != hipSuccess) { set_error(hipGetErrorString(e)); (void)hipStreamSynchronize(m->stream); m->dirty = false; keyframe_bow_free(b); return ORBX_E_HIP; }
-        kf->bow.store(b, std::memory_order_release);
-    } else {
-        ORBX_TRY(keyframe_bow_acquire(m, kf));
-    }
-    if (!down || nc == 0) return ORBX_OK;
-    std::vector<int32_t> h;
-    int32_t cnt = n_host;
-    if (n_host >= 0) {
-        if (word_id) ORBX_TRY(m->d2h(word_id, b->word, 4 * (size_t)nc));
-        if (node_id) ORBX_TRY(m->d2h(node_id, b->node, 4 * (size_t)nc));
-    } else {   // N comes back with the ids
-        h.resize(2 * (size_t)nc);
-        ORBX_TRY(m->d2h(h.data(), b->word, 4 * (size_t)nc));
-        ORBX_TRY(m->d2h(h.data() + nc, b->node, 4 * (size_t)nc));
-        ORBX_TRY(m->d2h(&cnt, kf->count, 4));
-    }
-    ORBX_TRY(m->sync_and_deliver());
-    keyframe_bow_release(kf);
-    if (n_host < 0) {
-        kf->adopt(cnt);
-        cnt = kf->host_n();
-        if (word_id) memcpy(word_id, h.data(), 4 * (size_t)cnt);
-        if (node_id) memcpy(node_id, h.data() + nc, 4 * (size_t)cnt);
-    }
-    return ORBX_OK;
+    return keyframe_compute_bow(m, false, kf, v, levelsup, word_id, node_id);
+}
+// The same over all N = N_left + N_right descriptor rows of a fisheye-stereo key frame: k_frame_bow_transform_fisheye / k_frame_featvec_fisheye in row
+// space; the ids come back in the reference's numbering, left then right.
+int orbx_keyframe_compute_bow_fisheye(orbx_matcher *m, orbx_keyframe *kf, const orbx_vocabulary *v, int levelsup, int32_t *word_id, int32_t *node_id) {
+    return keyframe_compute_bow(m, true, kf, v, levelsup, word_id, node_id);
 }
 
-// mBowVec(F.mBowVec), mFeatVec(F.mFeatVec) of KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-82): k_keyframe_bow_copy on the owner's stream, behind the
-// frame's orbx_frame_compute_bow and ahead of its next load; no host synchronisation.
-int orbx_keyframe_bow_from_frame(orbx_matcher *m, orbx_keyframe *kf, orbx_frame *f) {
-    if (!m || !kf || !f || f->owner != m || f->fisheye || kf->fisheye || kf->device != m->device || kf->src_frame != f) return ORBX_E_BAD_ARG;
-    if (kf->bow.load(std::memory_order_acquire)) return ORBX_E_BAD_ARG;   // set once
-    if (f->load_seq != kf->src_seq) return ORBX_E_STALE;                  // the handle holds another frame by now
-    if (!f->bow_valid) return ORBX_E_BAD_ARG;
-    if (f->rows_n() > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;
-    ORBX_HIP(hipSetDevice(m->device));
-    KeyFrameBow *b = nullptr;
-    int r = keyframe_bow_alloc(kf->cap, &b);
-    if (r != ORBX_OK) return r;
-    b->voc = f->bow_voc; b->levelsup = f->bow_levelsup;
-    KeyFrameBowCopy Cp;
-    memset(&Cp, 0, sizeof(Cp));
-    Cp.src_count = f->count; Cp.n_host = f->host_n(); Cp.cap = kf->cap;
-    Cp.src_word = f->bow_word; Cp.src_node = f->bow_node; Cp.src_ptr = f->fv_ptr; Cp.src_index = f->fv_index; Cp.src_meta = f->fv_meta;
-    Cp.src_fv_node = f->fv_node; Cp.src_angle = f->angle;
-    Cp.word = b->word; Cp.node = b->node; Cp.ptr = b->fv_ptr; Cp.index = b->fv_index; Cp.meta = b->fv_meta; Cp.fv_node = b->fv_node; Cp.angle = b->angle;
-    m->dirty = true;
-    hipLaunchKernelGGL(k_keyframe_bow_copy, dim3((unsigned)((kf->cap + 256) / 256)), dim3(256), 0, m->stream, Cp);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(b->ready, m->stream);
-    if (e != hipSuccess) { set_error(hipGetErrorString(e)); (void)hipStreamSynchronize(m->stream); m->dirty = false; keyframe_bow_free(b); return ORBX_E_HIP; }
-    kf->bow.store(b, std::memory_order_release);
-    return ORBX_OK;
+// mBowVec(F.mBowVec), mFeatVec(F.mFeatVec) of KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-82) from the handle the key frame was made from
+int orbx_keyframe_bow_from_frame(orbx_matcher *m, orbx_keyframe *kf, orbx_frame *f) { return keyframe_bow_from_frame(m, false, kf, f); }
+int orbx_keyframe_bow_from_frame_fisheye(orbx_matcher *m, orbx_keyframe *kf, orbx_frame *f) { return keyframe_bow_from_frame(m, true, kf, f); }
+
+}  // extern "C"
+
+namespace {
+
+// a key frame's N where a call needs it on the host (flags are given per feature; a row of the caller's is sized by it): one orbx_keyframe_count
+inline int keyframe_need_count(orbx_keyframe *kf) {
+    int n = 0;
+    return kf->host_n() < 0 ? orbx_keyframe_count(kf, &n) : ORBX_OK;
 }
 
-// SearchByBoW(kfs[k], F, ...) (ORBmatcher.cc:223-425) with both sides resident: mode 0, A = key frame k, B = the frame handle
-int orbx_frame_search_by_bow_resident(orbx_matcher *m, orbx_frame *f, int n_kf, orbx_keyframe *const *kfs, const uint8_t *const *valid, float nnratio,
-                                      int check_orientation, int32_t *match, int match_stride, int32_t *nmatches) {
-    if (!m || !f || f->owner != m || f->fisheye || !f->bow_valid || n_kf < 0) return ORBX_E_BAD_ARG;
+// SearchByBoW(kfs[k], F, ...) with both sides resident: A = key frame k, B = the frame handle; mode 0, of a rig mode 3 in row space (ORBmatcher.cc:283-392)
+int frame_search_by_bow_resident(orbx_matcher *m, bool rig, orbx_frame *f, int n_kf, orbx_keyframe *const *kfs, const uint8_t *const *valid, float nnratio,
+                                 int check_orientation, int32_t *match, int match_stride, int32_t *nmatches) {
+    if (!m || !f || f->owner != m || f->fisheye != rig || !f->bow_valid || n_kf < 0) return ORBX_E_BAD_ARG;
     if (n_kf > ORBX_MAX_BOW_KEYFRAMES) return ORBX_E_TOO_LARGE;
     if (n_kf == 0) return ORBX_OK;
     if (!kfs || !match || !nmatches || match_stride < 0) return ORBX_E_BAD_ARG;
     const orbx_vocabulary *voc = f->bow_voc;
     int levelsup = f->bow_levelsup;
     for (int k = 0; k < n_kf; k++)   // every key frame is checked before anything is enqueued
-        if (!keyframe_bow_ok(m, kfs[k], &voc, &levelsup)) return ORBX_E_BAD_ARG;
+        if (!keyframe_bow_ok(m, rig, kfs[k], &voc, &levelsup)) return ORBX_E_BAD_ARG;
     int n = f->host_n();
     if (n < 0 && match_stride < f->cap) { const int rc = frame_count(f, &n); if (rc != ORBX_OK) return rc; }   // the rows must fit the stride
     if (n >= 0 && match_stride < n) return ORBX_E_BAD_ARG;
     for (int k = 0; k < n_kf; k++) {
-        if (valid && valid[k] && kfs[k]->host_n() < 0) { int nk; const int rc = orbx_keyframe_count(kfs[k], &nk); if (rc != ORBX_OK) return rc; }   // flags: N entries
+        if (valid && valid[k]) { const int rc = keyframe_need_count(kfs[k]); if (rc != ORBX_OK) return rc; }   // flags: N entries
         nmatches[k] = 0;
         for (int i = 0; i < std::max(n, 0); i++) match[(size_t)k * match_stride + i] = -1;
     }
@@ -3239,34 +3351,36 @@ int orbx_frame_search_by_bow_resident(orbx_matcher *m, orbx_frame *f, int n_kf, 
     for (int k = 0; k < n_kf; k++) A[k] = bow_side(kfs[k]);
     for (int k = 0; k < n_kf; k++) { const int rc = keyframe_bow_acquire(m, kfs[k]); if (rc != ORBX_OK) return rc; }
     std::vector<int32_t> counts;
-    const int r = run_bow_resident(m, 0, n_kf, A.data(), B.data(), valid, nullptr, true, nnratio, check_orientation, nullptr, nullptr, 0, match, match_stride,
-                                   nmatches, counts);
+    const int r = run_bow_resident(m, rig ? 3 : 0, n_kf, A.data(), B.data(), valid, nullptr, true, nnratio, check_orientation, nullptr, nullptr, 0, match,
+                                   match_stride, nmatches, counts, rig);
     if (r != ORBX_OK) return r;
     for (int k = 0; k < n_kf; k++) {
         keyframe_bow_release(kfs[k]);
-        if (kfs[k]->host_n() < 0) kfs[k]->adopt(counts[2 * (size_t)k]);
+        keyframe_adopt(kfs[k], &counts[4 * (size_t)k]);
     }
-    if (!f->n_known) f->adopt(counts[1]);
+    if (!f->n_known) f->adopt(counts[2], counts[3]);
     return ORBX_OK;
 }
 
-// SearchByBoW(pKF1, kfs2[k], ...) (ORBmatcher.cc:765-905) with both sides resident: mode 1, A = kf1 for every problem, B = kfs2[k]
-int orbx_keyframe_search_by_bow(orbx_matcher *m, orbx_keyframe *kf1, const uint8_t *valid1, int n_kf, orbx_keyframe *const *kfs2,
-                                const uint8_t *const *valid2, float nnratio, int check_orientation, int32_t *match12, int match_stride, int32_t *nmatches) {
+// SearchByBoW(pKF1, kfs2[k], ...) (ORBmatcher.cc:765-905) with both sides resident: mode 1, A = kf1 for every problem, B = kfs2[k].  Between rig key
+// frames the reference skips the right camera's features as queries and as candidates (:800-802, :820-822): the same mode on the same kernels with
+// those rows switched off (run_bow_resident).
+int keyframe_search_by_bow(orbx_matcher *m, bool rig, orbx_keyframe *kf1, const uint8_t *valid1, int n_kf, orbx_keyframe *const *kfs2,
+                           const uint8_t *const *valid2, float nnratio, int check_orientation, int32_t *match12, int match_stride, int32_t *nmatches) {
     if (!m || n_kf < 0) return ORBX_E_BAD_ARG;
     const orbx_vocabulary *voc = nullptr;
     int levelsup = 0;
-    if (!keyframe_bow_ok(m, kf1, &voc, &levelsup)) return ORBX_E_BAD_ARG;
+    if (!keyframe_bow_ok(m, rig, kf1, &voc, &levelsup)) return ORBX_E_BAD_ARG;
     if (n_kf > ORBX_MAX_BOW_KEYFRAMES) return ORBX_E_TOO_LARGE;
     if (n_kf == 0) return ORBX_OK;
     if (!kfs2 || !match12 || !nmatches || match_stride < 0) return ORBX_E_BAD_ARG;
     for (int k = 0; k < n_kf; k++)
-        if (!keyframe_bow_ok(m, kfs2[k], &voc, &levelsup)) return ORBX_E_BAD_ARG;
+        if (!keyframe_bow_ok(m, rig, kfs2[k], &voc, &levelsup)) return ORBX_E_BAD_ARG;
     int n1 = kf1->host_n();
     if (n1 < 0 && (match_stride < kf1->cap || valid1)) { const int rc = orbx_keyframe_count(kf1, &n1); if (rc != ORBX_OK) return rc; }
     if (n1 >= 0 && match_stride < n1) return ORBX_E_BAD_ARG;
     for (int k = 0; k < n_kf; k++) {
-        if (valid2 && valid2[k] && kfs2[k]->host_n() < 0) { int nk; const int rc = orbx_keyframe_count(kfs2[k], &nk); if (rc != ORBX_OK) return rc; }
+        if (valid2 && valid2[k]) { const int rc = keyframe_need_count(kfs2[k]); if (rc != ORBX_OK) return rc; }
         nmatches[k] = 0;
         for (int i = 0; i < std::max(n1, 0); i++) match12[(size_t)k * match_stride + i] = -1;
     }
@@ -3280,26 +3394,27 @@ int orbx_keyframe_search_by_bow(orbx_matcher *m, orbx_keyframe *kf1, const uint8
     if (rc != ORBX_OK) return rc;
     std::vector<int32_t> counts;
     const int r = run_bow_resident(m, 1, n_kf, A.data(), B.data(), fa.data(), valid2, true, nnratio, check_orientation, nullptr, nullptr, 0, match12,
-                                   match_stride, nmatches, counts);
+                                   match_stride, nmatches, counts, rig);
     if (r != ORBX_OK) return r;
     keyframe_bow_release(kf1);
-    if (kf1->host_n() < 0) kf1->adopt(counts[0]);
+    keyframe_adopt(kf1, &counts[0]);
     for (int k = 0; k < n_kf; k++) {
         keyframe_bow_release(kfs2[k]);
-        if (kfs2[k]->host_n() < 0) kfs2[k]->adopt(counts[2 * (size_t)k + 1]);
+        keyframe_adopt(kfs2[k], &counts[4 * (size_t)k + 2]);
     }
     return ORBX_OK;
 }
 
-// SearchForTriangulation (ORBmatcher.cc:907-1146) between two resident pinhole key frames: mode 2 with the gates of orbx_search_for_triangulation_pinhole;
-// keypoints, mvuRight and pKF2->mvScaleFactors are the key frames' own rows, pKF2->mvLevelSigma2 rides up beside the record
-int orbx_keyframe_search_for_triangulation(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
-                                           int check_orientation, const orbx_keyframe_gate *gate, int32_t *matches12) {
-    if (!m || !gate || !gate->level_sigma2_2) return ORBX_E_BAD_ARG;
+// SearchForTriangulation (ORBmatcher.cc:907-1146) between two resident key frames of one kind, mode 2.  Pinhole: the gates of
+// orbx_search_for_triangulation_pinhole (G with the key frames' rows filled in here).  A rig: KannalaBrandt8::epipolarConstrain in k_tri_kb8_resident
+// (K; NULL = bCoarse: no gate at all, :1026, :1036).  Keypoints and scale factors are the key frames' own rows; the level tables ride up beside the record.
+int keyframe_search_for_triangulation(orbx_matcher *m, bool rig, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                      int check_orientation, TriGate *G, Kb8Gate *K, const float *sigma2_1, const float *sigma2_2, int nlevels,
+                                      int32_t *matches12) {
     const orbx_vocabulary *voc = nullptr;
     int levelsup = 0;
-    if (!keyframe_bow_ok(m, kf1, &voc, &levelsup) || !keyframe_bow_ok(m, kf2, &voc, &levelsup)) return ORBX_E_BAD_ARG;
-    if (gate->nlevels != kf2->nlevels) return ORBX_E_BAD_ARG;
+    if (!keyframe_bow_ok(m, rig, kf1, &voc, &levelsup) || !keyframe_bow_ok(m, rig, kf2, &voc, &levelsup)) return ORBX_E_BAD_ARG;
+    if (nlevels != kf2->nlevels || (K && nlevels != kf1->nlevels)) return ORBX_E_BAD_ARG;
     int n1 = 0, n2 = kf2->host_n();
     int rc = orbx_keyframe_count(kf1, &n1);   // matches12 holds N1 entries: N1 has to be known here
     if (rc == ORBX_OK && skip2 && n2 < 0) rc = orbx_keyframe_count(kf2, &n2);
@@ -3308,22 +3423,72 @@ int orbx_keyframe_search_for_triangulation(orbx_matcher *m, orbx_keyframe *kf1, 
     for (int i = 0; i < n1; i++) matches12[i] = -1;
     if (n1 == 0 || n2 == 0) return 0;
     ORBX_HIP(hipSetDevice(m->device));
-    TriGate G;
-    memset(&G, 0, sizeof(G));
-    G.enabled = 1; G.coarse = gate->coarse ? 1 : 0; G.strict = gate->strict_fp ? 1 : 0;
-    G.k1 = kf1->kps; G.k2 = kf2->kps; G.ur1 = kf1->u_right; G.ur2 = kf2->u_right; G.scale2 = kf2->scale;
-    for (int i = 0; i < 9; i++) G.F[i] = gate->F12[i];
-    G.ex = gate->ep_x; G.ey = gate->ep_y;
+    if (G) { G->k1 = kf1->kps; G->k2 = kf2->kps; G->ur1 = kf1->u_right; G->ur2 = kf2->u_right; G->scale2 = kf2->scale; }
+    if (K) { K->n_left1 = kf1->roff; K->n_left2 = kf2->roff; }   // row space: a row >= roff is the right camera's
     const BowSide A = bow_side(kf1), B = bow_side(kf2);
     if ((rc = keyframe_bow_acquire(m, kf1)) != ORBX_OK || (rc = keyframe_bow_acquire(m, kf2)) != ORBX_OK) return rc;
     std::vector<int32_t> counts;
     int32_t nm = 0;
-    const int r = run_bow_resident(m, 2, 1, &A, &B, &skip1, &skip2, false, 0.f, check_orientation, &G, gate->level_sigma2_2, gate->nlevels, matches12, n1, &nm,
-                                   counts);
+    const int r = run_bow_resident(m, 2, 1, &A, &B, &skip1, &skip2, false, 0.f, check_orientation, G, sigma2_2, nlevels, matches12, n1, &nm, counts, rig, K,
+                                   sigma2_1);
     if (r != ORBX_OK) return r;
     keyframe_bow_release(kf1); keyframe_bow_release(kf2);
-    if (kf2->host_n() < 0) kf2->adopt(counts[1]);
+    keyframe_adopt(kf2, &counts[2]);
     return nm;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbx_frame_search_by_bow_resident(orbx_matcher *m, orbx_frame *f, int n_kf, orbx_keyframe *const *kfs, const uint8_t *const *valid, float nnratio,
+                                      int check_orientation, int32_t *match, int match_stride, int32_t *nmatches) {
+    return frame_search_by_bow_resident(m, false, f, n_kf, kfs, valid, nnratio, check_orientation, match, match_stride, nmatches);
+}
+int orbx_frame_search_by_bow_resident_fisheye(orbx_matcher *m, orbx_frame *f, int n_kf, orbx_keyframe *const *kfs, const uint8_t *const *valid,
+                                              float nnratio, int check_orientation, int32_t *match, int match_stride, int32_t *nmatches) {
+    return frame_search_by_bow_resident(m, true, f, n_kf, kfs, valid, nnratio, check_orientation, match, match_stride, nmatches);
+}
+
+int orbx_keyframe_search_by_bow(orbx_matcher *m, orbx_keyframe *kf1, const uint8_t *valid1, int n_kf, orbx_keyframe *const *kfs2,
+                                const uint8_t *const *valid2, float nnratio, int check_orientation, int32_t *match12, int match_stride, int32_t *nmatches) {
+    return keyframe_search_by_bow(m, false, kf1, valid1, n_kf, kfs2, valid2, nnratio, check_orientation, match12, match_stride, nmatches);
+}
+int orbx_keyframe_search_by_bow_fisheye(orbx_matcher *m, orbx_keyframe *kf1, const uint8_t *valid1, int n_kf, orbx_keyframe *const *kfs2,
+                                        const uint8_t *const *valid2, float nnratio, int check_orientation, int32_t *match12, int match_stride,
+                                        int32_t *nmatches) {
+    return keyframe_search_by_bow(m, true, kf1, valid1, n_kf, kfs2, valid2, nnratio, check_orientation, match12, match_stride, nmatches);
+}
+
+int orbx_keyframe_search_for_triangulation(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                           int check_orientation, const orbx_keyframe_gate *gate, int32_t *matches12) {
+    if (!m || !gate || !gate->level_sigma2_2) return ORBX_E_BAD_ARG;
+    TriGate G;
+    memset(&G, 0, sizeof(G));
+    G.enabled = 1; G.coarse = gate->coarse ? 1 : 0; G.strict = gate->strict_fp ? 1 : 0;
+    for (int i = 0; i < 9; i++) G.F[i] = gate->F12[i];
+    G.ex = gate->ep_x; G.ey = gate->ep_y;
+    return keyframe_search_for_triangulation(m, false, kf1, kf2, skip1, skip2, check_orientation, &G, nullptr, nullptr, gate->level_sigma2_2, gate->nlevels,
+                                             matches12);
+}
+int orbx_keyframe_search_for_triangulation_fisheye(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                                   int check_orientation, const orbx_keyframe_kb8_gate *gate, int32_t *matches12) {
+    if (!m || !gate) return ORBX_E_BAD_ARG;
+    if (gate->coarse)   // bCoarse: no gate at all for such key frames, plain mode 2
+        return keyframe_search_for_triangulation(m, true, kf1, kf2, skip1, skip2, check_orientation, nullptr, nullptr, nullptr, nullptr,
+                                                 kf2 ? kf2->nlevels : 0, matches12);
+    if (!gate->level_sigma2_1 || !gate->level_sigma2_2) return ORBX_E_BAD_ARG;
+    TriGate G;
+    memset(&G, 0, sizeof(G));
+    G.enabled = 1; G.strict = 1;
+    Kb8Gate K;
+    memset(&K, 0, sizeof(K));
+    memcpy(K.cam[0], gate->cam1, sizeof(float) * 16);
+    memcpy(K.cam[2], gate->cam2, sizeof(float) * 16);
+    memcpy(K.R12, gate->R12, sizeof(K.R12));
+    memcpy(K.t12, gate->t12, sizeof(K.t12));
+    return keyframe_search_for_triangulation(m, true, kf1, kf2, skip1, skip2, check_orientation, &G, &K, gate->level_sigma2_1, gate->level_sigma2_2,
+                                             gate->nlevels, matches12);
 }
 
 }  // extern "C"

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import KP_DTYPE, BowKeyFrame, FeatVec, FrameDesc, FuseQueries, KeyFrameGate, PAIR_PREDICATE, PinholeGate, check, ptr
+from ._lib import KP_DTYPE, BowKeyFrame, FeatVec, FrameDesc, FuseQueries, KeyFrameGate, KeyFrameKb8Gate, PAIR_PREDICATE, PinholeGate, check, ptr
 
 
 @dataclass
@@ -159,7 +159,9 @@ class DeviceKeyFrame:
     ORBmatcher of the same device may search it (FuseSearchKeyFrames / FuseMapPoints), from any thread.  close() (or garbage collection) frees it;
     no call that was handed the key frame may be running then.
     A fisheye-stereo key frame (from_frame_fisheye / from_host_fisheye) holds mvKeys, mvKeysRight, all N descriptor rows, both counts and a grid per
-    camera; FuseSearchKeyFramesFisheye / FuseMapPointsFisheye search it, the other key-frame calls refuse it."""
+    camera; FuseSearchKeyFramesFisheye / FuseMapPointsFisheye search it, compute_bow_fisheye / bow_from_frame_fisheye attach its BoW for
+    ORBmatcher.SearchByBoWResidentFisheye / SearchByBoWKeyFramesResidentFisheye / SearchForTriangulationResidentKB8; the calls of the
+    monocular kind refuse it."""
 
     def __init__(self, handle):
         self._L = _lib.lib()
@@ -215,7 +217,8 @@ class DeviceKeyFrame:
         check(self._L.orbx_keyframe_counts(self._h, C.byref(nl), C.byref(nr)), "orbx_keyframe_counts")
         return nl.value, nr.value
 
-    def compute_bow(self, matcher: "ORBmatcher", voc: "ORBVocabulary", levelsup: int = 4, download: bool = True, cap: int | None = None):
+    def compute_bow(self, matcher: "ORBmatcher", voc: "ORBVocabulary", levelsup: int = 4, download: bool = True, cap: int | None = None,
+                    fn: str = "orbx_keyframe_compute_bow"):
         """KeyFrame::ComputeBoW on the resident descriptors (orbx_keyframe_compute_bow): the key frame keeps its FeatureVector for
         ORBmatcher.SearchByBoWResident / SearchByBoWKeyFramesResident / SearchForTriangulationResident.  Set once: a second call with the same
         vocabulary and levelsup only returns the ids.  download=True returns (word_id[N], node_id[N]); download=False returns None and does not
@@ -223,18 +226,29 @@ class DeviceKeyFrame:
         None = count first."""
         self._voc = voc   # (the vocabulary outlives the key frame's BoW state)
         if not download:
-            check(self._L.orbx_keyframe_compute_bow(matcher._h, self._h, voc._h, int(levelsup), None, None), "orbx_keyframe_compute_bow")
+            check(getattr(self._L, fn)(matcher._h, self._h, voc._h, int(levelsup), None, None), fn)
             return None
         size = self.count() if cap is None else int(cap)
         w, nd = np.zeros(max(size, 1), np.int32), np.zeros(max(size, 1), np.int32)
-        check(self._L.orbx_keyframe_compute_bow(matcher._h, self._h, voc._h, int(levelsup), ptr(w), ptr(nd)), "orbx_keyframe_compute_bow")
+        check(getattr(self._L, fn)(matcher._h, self._h, voc._h, int(levelsup), ptr(w), ptr(nd)), fn)
         n = self.count()   # (known after the call: no further synchronisation)
         return w[:n], nd[:n]
+
+    def compute_bow_fisheye(self, matcher: "ORBmatcher", voc: "ORBVocabulary", levelsup: int = 4, download: bool = True, cap: int | None = None):
+        """compute_bow for a fisheye-stereo key frame (orbx_keyframe_compute_bow_fisheye): all N = N_left + N_right descriptor rows; the ids come
+        back in the rig's numbering (features >= N_left are the right camera's).  cap: the capacity of the handle the key frame was made from."""
+        return self.compute_bow(matcher, voc, levelsup, download, cap, "orbx_keyframe_compute_bow_fisheye")
 
     def bow_from_frame(self, matcher: "ORBmatcher", frame: "DeviceFrame"):
         """The mBowVec / mFeatVec part of KeyFrame::KeyFrame(Frame&) (orbx_keyframe_bow_from_frame): a device-to-device copy of the BoW state of the
         DeviceFrame this key frame was made from (after its compute_bow, before its next load); asynchronous."""
         check(self._L.orbx_keyframe_bow_from_frame(matcher._h, self._h, frame._h), "orbx_keyframe_bow_from_frame")
+        return self
+
+    def bow_from_frame_fisheye(self, matcher: "ORBmatcher", frame: "DeviceFrame"):
+        """bow_from_frame for a fisheye-stereo key frame and the fisheye handle it was made from (orbx_keyframe_bow_from_frame_fisheye; after the
+        handle's compute_bow_fisheye, before its next load); asynchronous."""
+        check(self._L.orbx_keyframe_bow_from_frame_fisheye(matcher._h, self._h, frame._h), "orbx_keyframe_bow_from_frame_fisheye")
         return self
 
     def close(self):
@@ -702,7 +716,7 @@ class ORBmatcher:
         assert len(keep) == K
         return keep, (C.c_void_p * max(K, 1))(*[None if v is None else v.ctypes.data for v in keep])
 
-    def SearchByBoWResident(self, F: DeviceFrame, kfs, valid=None):
+    def SearchByBoWResident(self, F: DeviceFrame, kfs, valid=None, fn: str = "orbx_frame_search_by_bow_resident"):
         """SearchByBoW(KeyFrame*, Frame&) of the resident frame against DeviceKeyFrames that carry BoW, in one call (orbx_frame_search_by_bow_resident).
         valid: per key frame a uint8[N_k] mask or None (all), or None for all key frames.  Returns (nmatches[K], match[K, N]): row k =
         SearchByBoWFrame for key frame k's host arrays.  Only the masks and one record per key frame are uploaded."""
@@ -711,12 +725,18 @@ class ORBmatcher:
         stride = F.cap
         match = np.full((max(K, 1), stride), -1, np.int32)
         nm = np.zeros(max(K, 1), np.int32)
-        check(self._L.orbx_frame_search_by_bow_resident(self._h, F._h, K, self._kf_handles(kfs), rows, self.mfNNratio, int(self.mbCheckOrientation),
-                                                        ptr(match), stride, ptr(nm)), "orbx_frame_search_by_bow_resident")
+        check(getattr(self._L, fn)(self._h, F._h, K, self._kf_handles(kfs), rows, self.mfNNratio, int(self.mbCheckOrientation), ptr(match), stride,
+                                   ptr(nm)), fn)
         del keep
         return nm[:K], match[:K, :F.count()]
 
-    def SearchByBoWKeyFramesResident(self, kf1: DeviceKeyFrame, kfs2, valid1=None, valid2=None):
+    def SearchByBoWResidentFisheye(self, F: DeviceFrame, kfs, valid=None):
+        """SearchByBoWResident of a fisheye-stereo handle against fisheye-stereo DeviceKeyFrames that carry BoW
+        (orbx_frame_search_by_bow_resident_fisheye): row k = SearchByBoWFrameFisheye for key frame k's host arrays, features in the rig's numbering
+        on both sides."""
+        return self.SearchByBoWResident(F, kfs, valid, "orbx_frame_search_by_bow_resident_fisheye")
+
+    def SearchByBoWKeyFramesResident(self, kf1: DeviceKeyFrame, kfs2, valid1=None, valid2=None, fn: str = "orbx_keyframe_search_by_bow"):
         """SearchByBoW(pKF1, pKF2) for kf1 against every key frame of kfs2 in one call (orbx_keyframe_search_by_bow).  Returns (nmatches[K],
         match12[K, N1]): row k = SearchByBoWKeyFrames(kf1, kfs2[k]) on host arrays."""
         K = len(kfs2)
@@ -725,10 +745,28 @@ class ORBmatcher:
         n1 = kf1.count()
         match = np.full((max(K, 1), max(n1, 1)), -1, np.int32)
         nm = np.zeros(max(K, 1), np.int32)
-        check(self._L.orbx_keyframe_search_by_bow(self._h, kf1._h, ptr(v1), K, self._kf_handles(kfs2), rows, self.mfNNratio, int(self.mbCheckOrientation),
-                                                  ptr(match), max(n1, 1), ptr(nm)), "orbx_keyframe_search_by_bow")
+        check(getattr(self._L, fn)(self._h, kf1._h, ptr(v1), K, self._kf_handles(kfs2), rows, self.mfNNratio, int(self.mbCheckOrientation), ptr(match),
+                                   max(n1, 1), ptr(nm)), fn)
         del keep
         return nm[:K], match[:K, :n1]
+
+    def SearchByBoWKeyFramesResidentFisheye(self, kf1: DeviceKeyFrame, kfs2, valid1=None, valid2=None):
+        """SearchByBoW(pKF1, pKF2) between fisheye-stereo key frames (orbx_keyframe_search_by_bow_fisheye): the right camera's features are neither
+        queries nor candidates (ORBmatcher.cc:800-802, :820-822), so rows >= N_left1 are -1 and values are below N_left2."""
+        return self.SearchByBoWKeyFramesResident(kf1, kfs2, valid1, valid2, "orbx_keyframe_search_by_bow_fisheye")
+
+    def SearchForTriangulationResidentKB8(self, kf1: DeviceKeyFrame, kf2: DeviceKeyFrame, skip1, skip2, level_sigma2_1, level_sigma2_2, cam1, cam2, R12,
+                                          t12, coarse=False):
+        """SearchForTriangulationKB8 between two resident fisheye-stereo key frames (orbx_keyframe_search_for_triangulation_fisheye): keypoints,
+        descriptors and FeatureVectors are the key frames' own.  Returns (nmatches, matches12[N1]), values in kf2's features [0, N2)."""
+        s1, s2, sg1, sg2 = _u8(skip1), _u8(skip2), _f32(level_sigma2_1), _f32(level_sigma2_2)
+        flat = lambda x, n: (C.c_float * n)(*[float(v) for v in np.asarray(x, np.float32).ravel()])
+        g = KeyFrameKb8Gate(sg1.ctypes.data, sg2.ctypes.data, len(sg1), flat(cam1, 16), flat(cam2, 16), flat(R12, 36), flat(t12, 12), int(coarse))
+        n1 = kf1.count()
+        m12 = np.full(max(n1, 1), -1, np.int32)
+        n = check(self._L.orbx_keyframe_search_for_triangulation_fisheye(self._h, kf1._h, kf2._h, ptr(s1), ptr(s2), int(self.mbCheckOrientation),
+                                                                         C.byref(g), ptr(m12)), "orbx_keyframe_search_for_triangulation_fisheye")
+        return n, m12[:n1]
 
     def SearchForTriangulationResident(self, kf1: DeviceKeyFrame, kf2: DeviceKeyFrame, skip1, skip2, level_sigma2_2, F12, epipole, coarse=False,
                                        strict_fp=False):
