@@ -947,6 +947,55 @@ int orbx_keyframe_search_by_bow_fisheye(orbx_matcher *m, orbx_keyframe *kf1, con
 int orbx_keyframe_search_for_triangulation_fisheye(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
                                                    int check_orientation, const orbx_keyframe_kb8_gate *gate, int32_t *matches12);
 
+/* ---- LoopClosing's Sim3 projection searches on resident key frames (monocular / rectified key frames, Pinhole; a fisheye key frame is refused) ----
+ * The three matcher calls LoopClosing makes with a Sim3 share their projection gates (ORBmatcher.cc:452-487, :569-604, :1369-1399); the two calls below
+ * evaluate them on the device for n_kf key frames and ONE shared set of n_mp map points, and feed the search kernels from them: no key frame is uploaded,
+ * the map points go up once, the query records never visit the host.  poses[k] = Tcw = SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale())
+ * (Rcw row-major, tcw) with Ow = Tcw.inverse().translation(), evaluated by the caller exactly as the reference does (:436-437, :543-544, :1349-1350);
+ * cams[k]: the key frame's Pinhole intrinsics (bf is not read).  Map points flat as orbx_keyframe_fuse_map_points takes them (mfMinDistance /
+ * mfMaxDistance UNSCALED).  Per pair, in the reference's order, every float operation rounded on its own:
+ *   skip; p3Dc = Rcw p + tcw, p3Dc.z < 0 rejects; the projection (below); KeyFrame::IsInImage, strict on the max side; dist = |p - Ow| outside
+ *   [0.8f mfMinDistance, 1.2f mfMaxDistance] rejects; PO.dot(Pn) < 0.5 * dist rejects (compared in double, no division); PredictScale(dist, pKF)
+ *   (MapPoint.cc:531-546) with the key frame's levels and log_scale_factor; radius = th * mvScaleFactors[level]; candidate octaves [level - 1, level].
+ * No mvuRight is read and no ur is produced. */
+#define ORBX_SIM3_PROJECT_CAMERA 0   /* pKF->mpCamera->project(p3Dc), Pinhole: u = fx * X / Z + cx  (ORBmatcher.cc:463, :1378) */
+#define ORBX_SIM3_PROJECT_INVZ 1     /* invz = 1 / Z; x = X * invz; y = Y * invz; u = fx * x + cx, as written at ORBmatcher.cc:573-578 */
+/* orbx_keyframe_search_by_projection_sim3: SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (ORBmatcher.cc:427-532;
+ * projection_form = ORBX_SIM3_PROJECT_CAMERA) and its vpPointsKFs / vpMatchedKF overload (:534-646; ORBX_SIM3_PROJECT_INVZ) for n_kf key frames in one
+ * call -- the targets of LoopClosing::FindMatchesByProjection / DetectCommonRegionsFromLastKF (LoopClosing.cc:755,777,964), or n_kf = 1 per candidate
+ * of DetectCommonRegionsFromBoW.  The search is the window form of orbx_search_by_projection_window: accept iff (float)bestDist <= ORBX_TH_LOW *
+ * ratio_hamming, no rotation check, a matched feature becomes occupied -- so the queries of one key frame interact in map-point order as the
+ * reference's loop does (:489-528), and the key frames are independent problems.  Query index = map-point index (rejected pairs are switched off, not
+ * compacted): match[k][i] names vpPoints directly.
+ *   skip [n_kf][n_mp] or NULL: isBad() || spAlreadyFound.count(pMP) for key frame k (:445-449);
+ *   occupied: NULL, or n_kf rows, each NULL or N_k entries: vpMatched[i] != NULL on entry (:499);
+ *   match: n_kf rows of N_k entries: the map point assigned to feature i, or -1; nmatches [n_kf]: the member's return value per key frame;
+ *   projected [n_kf][n_mp] or NULL: 1 = the pair passed every gate; proj_u / proj_v [n_kf][n_mp], both or neither: the projection, meaningful where
+ *   projected == 1.
+ * N_k is orbx_keyframe_count (the caller sizes the rows by it; a count still pending costs that one download here).
+ * LIMITS.  The search kernels take ONE set of grid parameters per launch: the key frames of one call must have bit-equal image bounds (mnMinX, mnMaxX,
+ * mnMinY, mnMaxY) -- ORBX_E_BAD_ARG otherwise, callers split the list (key frames of one camera always qualify).  N_k > ORBX_MAX_FRAME_FEATURES or
+ * n_kf > ORBX_MAX_FUSE_KEYFRAMES: ORBX_E_TOO_LARGE.  A fisheye key frame, a key frame of another device, a NULL key frame or match row, projection_form
+ * not 0 / 1, proj_u without proj_v: ORBX_E_BAD_ARG.  Every check runs before anything is enqueued.  n_kf = 0 or n_mp = 0: ORBX_OK, match rows -1,
+ * nmatches 0.  One upload run, one download run, one synchronisation and a launch chain that do not grow with n_kf. */
+int orbx_keyframe_search_by_projection_sim3(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
+                                            const orbx_frame_pose *poses, float th, float ratio_hamming, float log_scale_factor, int projection_form,
+                                            int n_mp, const float *pos, const float *normal, const float *min_dist, const float *max_dist,
+                                            const uint8_t *mp_desc, const uint8_t *skip, const uint8_t *const *occupied, int32_t *const *match,
+                                            int32_t *nmatches, uint8_t *projected, float *proj_u, float *proj_v);
+/* orbx_keyframe_fuse_map_points_sim3: the loop of LoopClosing::SearchAndFuse -- Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (ORBmatcher.cc:1339-1455)
+ * per key frame of CorrectedPosesMap -- up to and including the candidate loop, in one call: the gates above with ORBX_SIM3_PROJECT_CAMERA, then the
+ * gate-less candidate search of orbx_keyframe_fuse_search(use_chi2 = 0) (:1405-1433: no chi2 test, no mvuRight).  skip [n_kf][n_mp] or NULL = isBad() ||
+ * spAlreadyFound.count(pMP) with spAlreadyFound = pKF_k->GetMapPoints() (:1352, :1363).  Outputs [n_kf][n_mp] as orbx_keyframe_fuse_map_points: best_idx /
+ * best_dist (-1 / 256 for no result), projected (may be NULL).  Key frames without inv_level_sigma2 are accepted, and the key frames of one call may
+ * have different image bounds; n_kf <= ORBX_MAX_FUSE_KEYFRAMES.  The caller accepts best_dist <= ORBX_TH_LOW and runs the tail :1436-1449 per key frame
+ * in the reference's order, re-checking isBad() / IsInKeyFrame on the live graph as for orbx_keyframe_fuse_map_points.  Four launches whatever n_kf is.
+ * Refusals as above (ORBX_E_BAD_ARG before anything is enqueued); n_kf = 0 or n_mp = 0: ORBX_OK. */
+int orbx_keyframe_fuse_map_points_sim3(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams, const orbx_frame_pose *poses,
+                                       float th, float log_scale_factor, int n_mp, const float *pos, const float *normal, const float *min_dist,
+                                       const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
+                                       uint8_t *projected);
+
 /* Frame::ComputeStereoMatches (Frame.cc:811-981) for every frame of two resident batches: `left` and `right` must have
  * extracted batches of the same size and image shape (rectified stereo, lapping {0,0}).  Row-band Hamming match, 11x11
  * SAD sub-pixel refinement on the device-resident pyramids and the median outlier rejection all run on the device, on

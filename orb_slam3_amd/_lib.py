@@ -126,6 +126,7 @@ class FuseQueries(C.Structure):
 
 
 MAX_FUSE_KEYFRAMES = 256   # ORBX_MAX_FUSE_KEYFRAMES
+SIM3_PROJECT_CAMERA, SIM3_PROJECT_INVZ = 0, 1   # ORBX_SIM3_PROJECT_CAMERA (Pinhole::project), ORBX_SIM3_PROJECT_INVZ (ORBmatcher.cc:573-578)
 
 
 class KeyFrameGate(C.Structure):
@@ -175,6 +176,7 @@ SYMBOLS = [
     "orbx_keyframe_fuse_map_points_fisheye",
     "orbx_keyframe_compute_bow_fisheye", "orbx_keyframe_bow_from_frame_fisheye", "orbx_frame_search_by_bow_resident_fisheye",
     "orbx_keyframe_search_by_bow_fisheye", "orbx_keyframe_search_for_triangulation_fisheye",
+    "orbx_keyframe_search_by_projection_sim3", "orbx_keyframe_fuse_map_points_sim3",
 ]
 
 
@@ -306,6 +308,10 @@ def lib() -> C.CDLL:
     L.orbx_frame_search_by_bow_resident_fisheye.argtypes = L.orbx_frame_search_by_bow_resident.argtypes
     L.orbx_keyframe_search_by_bow_fisheye.argtypes = [vp, vp, vp, i32, C.POINTER(vp), C.POINTER(vp), f32, i32, vp, i32, vp]
     L.orbx_keyframe_search_for_triangulation_fisheye.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(KeyFrameKb8Gate), vp]
+    L.orbx_keyframe_search_by_projection_sim3.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(Camera), C.POINTER(FramePose), f32, f32, f32, i32, i32, vp, vp, vp,
+                                                          vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp]
+    L.orbx_keyframe_fuse_map_points_sim3.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(Camera), C.POINTER(FramePose), f32, f32, i32, vp, vp, vp, vp, vp, vp,
+                                                     vp, vp, vp]
     L.orbx_keyframe_from_frame_fisheye.argtypes = [vp, vp, vp, C.POINTER(vp)]
     L.orbx_keyframe_create_host_fisheye.argtypes = [vp, C.POINTER(FrameDesc), vp, i32, vp, C.POINTER(vp)]
     L.orbx_keyframe_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

@@ -9,6 +9,7 @@
 #define ORBX_ADAPTER_ORBMATCHER_H
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 #include <set>
@@ -615,6 +616,68 @@ public:
                                                     mps.descriptors.data(), skip.empty() ? nullptr : skip.data(), bestIdx.data(), bestDist.data(),
                                                     projected ? projected->data() : nullptr);
         if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_fuse_map_points: ") + orbx_status_string(r));
+    }
+
+    // LoopClosing's Sim3 searches on resident key frames (monocular / rectified, Pinhole).  poses[k] = Tcw = SE3f(Scw.rotationMatrix(),
+    // Scw.translation() / Scw.scale()) and Ow = Tcw.inverse().translation(), as the reference evaluates them; the gates run on the device.
+    //
+    // SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (ORBmatcher.cc:427-532; projectionForm ORBX_SIM3_PROJECT_CAMERA) or its
+    // vpPointsKFs overload (:534-646; ORBX_SIM3_PROJECT_INVZ) for K key frames with ONE shared point set in one call
+    // (orbx_keyframe_search_by_projection_sim3).  skip [K][n] (empty = none) = isBad() || spAlreadyFound.count(pMP) for key frame k; occupied: empty, or
+    // K rows, each empty or N_k flags vpMatched[i] != NULL.  vpMatch[k][i] = the index into the point set assigned to feature i of key frame k, or -1;
+    // vnMatches[k] = the member's return value.  The key frames of one call must have equal image bounds (std::runtime_error otherwise: split the list).
+    void SearchByProjectionSim3KeyFrames(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<orbx_camera> &cams,
+                                         const std::vector<orbx_frame_pose> &poses, const FuseMapPointSet &mps, const std::vector<uint8_t> &skip,
+                                         const std::vector<std::vector<uint8_t>> &occupied, float th, float ratioHamming, float logScaleFactor,
+                                         int projectionForm, std::vector<std::vector<int32_t>> &vpMatch, std::vector<int> &vnMatches,
+                                         std::vector<uint8_t> *projected = nullptr) {
+        const size_t K = vpKFs.size(), n = (size_t)mps.size();
+        if (cams.size() != K || poses.size() != K || (!skip.empty() && skip.size() != K * n) || (!occupied.empty() && occupied.size() != K))
+            throw std::invalid_argument("SearchByProjectionSim3KeyFrames: one camera and pose per key frame, K x n skip flags, K occupancy rows");
+        std::vector<orbx_keyframe *> h(K);
+        std::vector<const uint8_t *> occ(K, nullptr);
+        std::vector<int32_t *> rows(K);
+        std::vector<int32_t> nm(K, 0);
+        vpMatch.assign(K, {});
+        for (size_t k = 0; k < K; k++) {
+            h[k] = vpKFs[k]->handle();
+            const size_t N = (size_t)vpKFs[k]->count();
+            if (!occupied.empty() && !occupied[k].empty()) {
+                if (occupied[k].size() != N) throw std::invalid_argument("SearchByProjectionSim3KeyFrames: an occupancy row holds N_k flags");
+                occ[k] = occupied[k].data();
+            }
+            vpMatch[k].assign(N + 1, -1);   // (+ 1: data() of an empty row may be NULL, which the call refuses)
+            rows[k] = vpMatch[k].data();
+        }
+        if (projected) projected->assign(K * n, 0);
+        const int r = orbx_keyframe_search_by_projection_sim3(m_, (int)K, h.data(), cams.data(), poses.data(), th, ratioHamming, logScaleFactor,
+                                                              projectionForm, (int)n, mps.pos.data(), mps.normal.data(), mps.minDistance.data(),
+                                                              mps.maxDistance.data(), mps.descriptors.data(), skip.empty() ? nullptr : skip.data(),
+                                                              occupied.empty() ? nullptr : occ.data(), rows.data(), nm.data(),
+                                                              projected ? projected->data() : nullptr, nullptr, nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_search_by_projection_sim3: ") + orbx_status_string(r));
+        for (size_t k = 0; k < K; k++) vpMatch[k].pop_back();
+        vnMatches.assign(nm.begin(), nm.end());
+    }
+
+    // The loop of LoopClosing::SearchAndFuse -- Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (ORBmatcher.cc:1339-1455) per key frame of
+    // CorrectedPosesMap -- in ONE call, projection included (orbx_keyframe_fuse_map_points_sim3): the gate-less candidate search, no mvuRight.
+    // skip [K][n] (empty = none) = isBad() || pKF_k->GetMapPoints().count(pMP).  bestIdx / bestDist / projected: [K][n], row-major.
+    void FuseMapPointsSim3(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<orbx_camera> &cams, const std::vector<orbx_frame_pose> &poses,
+                           const FuseMapPointSet &mps, const std::vector<uint8_t> &skip, float th, float logScaleFactor, std::vector<int32_t> &bestIdx,
+                           std::vector<int32_t> &bestDist, std::vector<uint8_t> *projected = nullptr) {
+        const size_t K = vpKFs.size(), n = (size_t)mps.size();
+        if (cams.size() != K || poses.size() != K || (!skip.empty() && skip.size() != K * n))
+            throw std::invalid_argument("FuseMapPointsSim3: one camera and pose per key frame, K x n skip flags");
+        std::vector<orbx_keyframe *> h(K);
+        for (size_t k = 0; k < K; k++) h[k] = vpKFs[k]->handle();
+        bestIdx.assign(K * n, -1); bestDist.assign(K * n, 256);
+        if (projected) projected->assign(K * n, 0);
+        const int r = orbx_keyframe_fuse_map_points_sim3(m_, (int)K, h.data(), cams.data(), poses.data(), th, logScaleFactor, (int)n, mps.pos.data(),
+                                                         mps.normal.data(), mps.minDistance.data(), mps.maxDistance.data(), mps.descriptors.data(),
+                                                         skip.empty() ? nullptr : skip.data(), bestIdx.data(), bestDist.data(),
+                                                         projected ? projected->data() : nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_fuse_map_points_sim3: ") + orbx_status_string(r));
     }
 
     // FuseSearchKeyFrames for K fisheye-stereo key frames (orbx_keyframe_fuse_search_fisheye): q / bestIdx / bestDist hold 2 K entries, 2 k = key frame

@@ -612,6 +612,90 @@ public:
         return nmatches;
     }
 
+private:
+    // ---- LoopClosing's Sim3 calls on RESIDENT key frames (orbx_keyframe_search_by_projection_sim3 / orbx_keyframe_fuse_map_points_sim3): no key frame
+    // is uploaded, the gates (:452-487, :569-604, :1369-1399) run on the device.  The device applies 0.8f / 1.2f to mfMinDistance / mfMaxDistance and
+    // divides mfMaxDistance in PredictScale itself, so it takes them UNSCALED -- the reference's MapPoint publishes only the scaled values.  A tree that
+    // uses these overloads adds
+    //     float MapPoint::GetMinDistance() { unique_lock<mutex> lock(mMutexPos); return mfMinDistance; }   // and GetMaxDistance()
+    // Without the two getters the overloads throw: dividing the scaled values back does not give the reference's floats.
+    template <class MP> static auto raw_distances(MP *p, float &mn, float &mx, int) -> decltype((void)p->GetMinDistance(), void()) {
+        mn = p->GetMinDistance(); mx = p->GetMaxDistance();
+    }
+    template <class MP> static void raw_distances(MP *, float &, float &, long) {
+        throw std::logic_error("the resident Sim3 overloads need MapPoint::GetMinDistance() / GetMaxDistance() (mfMinDistance / mfMaxDistance unscaled)");
+    }
+    // KeyFrame::mfLogScaleFactor (stand-in types without the member: the logarithm of mvScaleFactors[1] = mfScaleFactor)
+    template <class KF> static auto log_scale_factor_of(KF *p, int) -> decltype((float)p->mfLogScaleFactor) { return p->mfLogScaleFactor; }
+    template <class KF> static float log_scale_factor_of(KF *p, long) { return p->mvScaleFactors.size() > 1 ? (float)std::log((double)p->mvScaleFactors[1]) : 1.f; }
+
+    // Tcw = SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()), Ow = Tcw.inverse().translation() (:436-437, :543-544, :1349-1350) and the intrinsics
+    template <class Sim3> static void sim3_view(KeyFrame *pKF, Sim3 &Scw, orbx_camera &cam, orbx_frame_pose &pose) {
+        Sophus::SE3f Tcw = Sophus::SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale());
+        Eigen::Vector3f Ow = Tcw.inverse().translation();
+        const Eigen::Matrix3f R = Tcw.rotationMatrix();
+        const Eigen::Vector3f t = Tcw.translation();
+        for (int r = 0; r < 3; r++) {
+            for (int c = 0; c < 3; c++) pose.Rcw[3 * r + c] = R(r, c);
+            pose.tcw[r] = t(r); pose.Ow[r] = Ow(r);
+        }
+        cam = orbx_camera{pKF->fx, pKF->fy, pKF->cx, pKF->cy, 0.f, 0.f, 0.f, 0.f, 0.f, pKF->mbf};
+    }
+    // vpPoints flat, with the reference's accessors (GetWorldPos, GetNormal, the two distances, GetDescriptor)
+    static FuseMapPointSet sim3_point_set(const std::vector<MapPoint *> &vpPoints) {
+        FuseMapPointSet s;
+        for (MapPoint *pMP : vpPoints) {
+            const Eigen::Vector3f p = pMP->GetWorldPos(), nv = pMP->GetNormal();
+            float mn = 0.f, mx = 0.f;
+            raw_distances(pMP, mn, mx, 0);
+            for (int r = 0; r < 3; r++) { s.pos.push_back(p(r)); s.normal.push_back(nv(r)); }
+            s.minDistance.push_back(mn); s.maxDistance.push_back(mx);
+            push_desc(s.descriptors, pMP->GetDescriptor());
+        }
+        return s;
+    }
+    template <class Sim3>
+    int sim3_projection_resident(KeyFrame *pKF, DeviceKeyFrame *pDeviceKF, Sim3 &Scw, const std::vector<MapPoint *> &vpPoints,
+                                 std::vector<MapPoint *> &vpMatched, int th, float ratioHamming, int form, std::vector<int32_t> &match) {
+        std::vector<orbx_camera> cams(1);
+        std::vector<orbx_frame_pose> poses(1);
+        sim3_view(pKF, Scw, cams[0], poses[0]);
+        std::set<MapPoint *> spAlreadyFound(vpMatched.begin(), vpMatched.end());
+        spAlreadyFound.erase(static_cast<MapPoint *>(NULL));
+        std::vector<uint8_t> skip(vpPoints.size());
+        for (size_t i = 0; i < vpPoints.size(); i++) skip[i] = (vpPoints[i]->isBad() || spAlreadyFound.count(vpPoints[i])) ? 1 : 0;   // :445-449
+        std::vector<std::vector<uint8_t>> occupied(1, std::vector<uint8_t>(pKF->mvKeysUn.size()));
+        for (size_t i = 0; i < occupied[0].size(); i++) occupied[0][i] = vpMatched[i] ? 1 : 0;                                       // :499
+        std::vector<std::vector<int32_t>> rows;
+        std::vector<int> nm;
+        SearchByProjectionSim3KeyFrames({pDeviceKF}, cams, poses, sim3_point_set(vpPoints), skip, occupied, (float)th, ratioHamming,
+                                        log_scale_factor_of(pKF, 0), form, rows, nm);
+        match.swap(rows[0]);
+        return nm[0];
+    }
+
+public:
+    // ORBmatcher.cc:427-538 with pKF's resident copy (KeyFrame::mpDevice in an integrated tree): match[i] names vpPoints directly
+    int SearchByProjection(KeyFrame *pKF, DeviceKeyFrame *pDeviceKF, Sophus::Sim3f &Scw, const std::vector<MapPoint *> &vpPoints,
+                           std::vector<MapPoint *> &vpMatched, int th, float ratioHamming = 1.0) {
+        std::vector<int32_t> match;
+        const int nmatches = sim3_projection_resident(pKF, pDeviceKF, Scw, vpPoints, vpMatched, th, ratioHamming, ORBX_SIM3_PROJECT_CAMERA, match);
+        for (size_t i = 0; i < match.size(); i++)
+            if (match[i] >= 0) vpMatched[i] = vpPoints[match[i]];   // :527
+        return nmatches;
+    }
+
+    // ORBmatcher.cc:540-646 with pKF's resident copy: the projection written out with invz (:573-578)
+    int SearchByProjection(KeyFrame *pKF, DeviceKeyFrame *pDeviceKF, Sophus::Sim3<float> &Scw, const std::vector<MapPoint *> &vpPoints,
+                           const std::vector<KeyFrame *> &vpPointsKFs, std::vector<MapPoint *> &vpMatched, std::vector<KeyFrame *> &vpMatchedKF, int th,
+                           float ratioHamming = 1.0) {
+        std::vector<int32_t> match;
+        const int nmatches = sim3_projection_resident(pKF, pDeviceKF, Scw, vpPoints, vpMatched, th, ratioHamming, ORBX_SIM3_PROJECT_INVZ, match);
+        for (size_t i = 0; i < match.size(); i++)
+            if (match[i] >= 0) { vpMatched[i] = vpPoints[match[i]]; vpMatchedKF[i] = vpPointsKFs[match[i]]; }   // :638-639
+        return nmatches;
+    }
+
     // ORBmatcher.cc:907-1146 (LocalMapping::CreateNewMapPoints, LocalMapping.cc:466: 10-30 calls per key frame).
     // PINHOLE key frames (both cameras CAM_PINHOLE -- every monocular / stereo / RGB-D configuration of the reference): both geometric gates run
     // on the device (orbx_search_for_triangulation_pinhole: one upload, one launch chain, one download of the matches; no candidate distance
@@ -934,6 +1018,46 @@ public:
                 pKF->AddMapPoint(pMP, bestIdx[k]);
             }
             nFused++;
+        }
+        return nFused;
+    }
+
+    // The loop of LoopClosing::SearchAndFuse (`matcher.Fuse(pKFi, Scw, vpMapPoints, 4, vpReplacePoints)` per key frame of CorrectedPosesMap) as ONE
+    // device call on the resident key frames: projection and candidate search of all K targets in orbx_keyframe_fuse_map_points_sim3, then the
+    // reference's tail (:1436-1449) per key frame in the reference's order.  skip = isBad() || pKF_k->GetMapPoints().count(pMP) as the call is made
+    // (:1352, :1363); the tail re-checks isBad() / IsInKeyFrame(pKF) per query on the live graph, the rule of Fuse(vpTargetKFs, vpDeviceKFs, ...).
+    // vvpReplacePoint[k] must hold vpPoints.size() entries, as vpReplacePoint does.  Returns the fused points per key frame.
+    std::vector<int> Fuse(const std::vector<KeyFrame *> &vpKFs, const std::vector<DeviceKeyFrame *> &vpDeviceKFs, std::vector<Sophus::Sim3f> &vScw,
+                          const std::vector<MapPoint *> &vpPoints, float th, std::vector<std::vector<MapPoint *>> &vvpReplacePoint) {
+        const size_t K = vpKFs.size(), n = vpPoints.size();
+        if (vpDeviceKFs.size() != K || vScw.size() != K || vvpReplacePoint.size() != K)
+            throw std::invalid_argument("Fuse: one DeviceKeyFrame, one Sim3 and one vpReplacePoint per key frame");
+        std::vector<orbx_camera> cams(K);
+        std::vector<orbx_frame_pose> poses(K);
+        std::vector<uint8_t> skip(K * n);
+        for (size_t k = 0; k < K; k++) {
+            sim3_view(vpKFs[k], vScw[k], cams[k], poses[k]);
+            const std::set<MapPoint *> spAlreadyFound = vpKFs[k]->GetMapPoints();
+            for (size_t i = 0; i < n; i++) skip[k * n + i] = (vpPoints[i]->isBad() || spAlreadyFound.count(vpPoints[i])) ? 1 : 0;
+        }
+        std::vector<int32_t> bestIdx, bestDist;
+        FuseMapPointsSim3(vpDeviceKFs, cams, poses, sim3_point_set(vpPoints), skip, th, K ? log_scale_factor_of(vpKFs[0], 0) : 0.f, bestIdx, bestDist);
+        std::vector<int> nFused(K, 0);
+        for (size_t k = 0; k < K; k++) {
+            KeyFrame *pKF = vpKFs[k];
+            for (size_t i = 0; i < n; i++) {   // :1436-1449
+                if (bestIdx[k * n + i] < 0 || bestDist[k * n + i] > TH_LOW) continue;
+                MapPoint *pMP = vpPoints[i];
+                if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;   // an earlier key frame's AddObservation / the caller's Replace retired the query
+                MapPoint *pMPinKF = pKF->GetMapPoint(bestIdx[k * n + i]);
+                if (pMPinKF) {
+                    if (!pMPinKF->isBad()) vvpReplacePoint[k][i] = pMPinKF;
+                } else {
+                    pMP->AddObservation(pKF, bestIdx[k * n + i]);
+                    pKF->AddMapPoint(pMP, bestIdx[k * n + i]);
+                }
+                nFused[k]++;
+            }
         }
         return nFused;
     }

@@ -1391,6 +1391,72 @@ __global__ __launch_bounds__(256) void k_fuse_project(const KfProblem *__restric
     qvalid[o] = ok ? 1 : 0;
 }
 
+// k_sim3_project: the projection half shared by LoopClosing's three Sim3 matcher calls -- SearchByProjection(pKF, Scw, vpPoints, vpMatched, th,
+// ratioHamming) (ORBmatcher.cc:452-487), its vpPointsKFs overload (:569-604) and Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:1369-1399) -- for every
+// (key frame, map point) of one call: a lane per pair writes the query record of problem k where the search kernels read it (qvalid switches a rejected
+// pair off: query index = map-point index).  poses[k] = SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()) and its camera centre, evaluated by
+// the caller.  The gates in the reference's order, every float operation rounded separately, sums in k_fuse_project's order:
+//   reject skip (isBad() || spAlreadyFound.count(pMP)); p3Dc = Rcw p + tcw; reject p3Dc.z < 0
+//   ORBX_SIM3_PROJECT_CAMERA: Pinhole::project, u = fx X / Z + cx;  ORBX_SIM3_PROJECT_INVZ: invz = 1 / Z, x = X invz, y = Y invz, u = fx x + cx (:573-578)
+//   KeyFrame::IsInImage (strict on the max side)
+//   dist = |p - Ow|; reject outside [0.8f mfMinDistance, 1.2f mfMaxDistance]
+//   reject PO . Pn < 0.5 * dist, compared in double and without a division
+//   PredictScale(dist, pKF) as k_fuse_project evaluates it; radius = th * mvScaleFactors[level]; levels [level - 1, level]
+// No ur (no bf is read): these searches never look at mvuRight.  Streaming work: no LDS, no scratch.  grid (ceil(n_mp / 256), n_kf), block 256
+__global__ __launch_bounds__(256) void k_sim3_project(const KfProblem *__restrict__ recs, const orbx_camera *__restrict__ cams,
+                                                      const orbx_frame_pose *__restrict__ poses, float th, float log_scale_factor, int projection_form,
+                                                      int n_mp, const float *__restrict__ pos, const float *__restrict__ normal,
+                                                      const float *__restrict__ min_dist, const float *__restrict__ max_dist,
+                                                      const uint8_t *__restrict__ skip, float *__restrict__ qx, float *__restrict__ qy,
+                                                      float *__restrict__ qr, int32_t *__restrict__ qmin, int32_t *__restrict__ qmax,
+                                                      uint8_t *__restrict__ qvalid) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_mp) return;
+    const int k = blockIdx.y;
+    const size_t o = (size_t)k * n_mp + i;
+    const orbx_frame_pose T = poses[k];
+    const float fx = cams[k].fx, fy = cams[k].fy, cx = cams[k].cx, cy = cams[k].cy;
+    const float minx = recs[k].g.minx, miny = recs[k].g.miny, maxx = recs[k].maxx, maxy = recs[k].maxy;
+    const int nlevels = recs[k].nlevels;
+    const float *scale = recs[k].P.scale;
+    // every input of the pair requested at once (the gates read them conditionally: each would be a dependent round trip)
+    const uint8_t sk = skip ? skip[o] : (uint8_t)0;
+    const float P0 = pos[3 * i], P1 = pos[3 * i + 1], P2 = pos[3 * i + 2];
+    const float mn_in = min_dist[i], mx = max_dist[i], N0 = normal[3 * i], N1 = normal[3 * i + 1], N2 = normal[3 * i + 2];
+    float Pc[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+        Pc[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T.Rcw[3 * r], P0), __fmul_rn(T.Rcw[3 * r + 1], P1)), __fmul_rn(T.Rcw[3 * r + 2], P2)), T.tcw[r]);
+    bool ok = !sk && !(Pc[2] < 0.0f);
+    float u, v;
+    if (projection_form == ORBX_SIM3_PROJECT_INVZ) {   // the vpPointsKFs overload writes the pinhole projection out (:573-578)
+        const float invz = __fdiv_rn(1.0f, Pc[2]);
+        const float x = __fmul_rn(Pc[0], invz), y = __fmul_rn(Pc[1], invz);
+        u = __fadd_rn(__fmul_rn(fx, x), cx); v = __fadd_rn(__fmul_rn(fy, y), cy);
+    } else {                                           // pKF->mpCamera->project(p3Dc): Pinhole::project
+        u = __fadd_rn(__fdiv_rn(__fmul_rn(fx, Pc[0]), Pc[2]), cx); v = __fadd_rn(__fdiv_rn(__fmul_rn(fy, Pc[1]), Pc[2]), cy);
+    }
+    ok = ok && (u >= minx && u < maxx && v >= miny && v < maxy);
+    const float PO0 = __fsub_rn(P0, T.Ow[0]), PO1 = __fsub_rn(P1, T.Ow[1]), PO2 = __fsub_rn(P2, T.Ow[2]);
+    const float dist = sqrtf(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, PO0)), __fmul_rn(PO1, PO1)), __fmul_rn(PO2, PO2)));
+    const float maxDistance = __fmul_rn(1.2f, mx), minDistance = __fmul_rn(0.8f, mn_in);
+    ok = ok && !(dist < minDistance || dist > maxDistance);
+    const float dot = __fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, N0)), __fmul_rn(PO1, N1)), __fmul_rn(PO2, N2));
+    ok = ok && !((double)dot < 0.5 * (double)dist);
+    int lvl = 0;
+    float radius = 0.f;
+    if (ok) {   // MapPoint::PredictScale(dist, pKF) (MapPoint.cc:531-546), as k_fuse_project evaluates it
+        const float ratio = __fdiv_rn(mx, dist);
+        lvl = (int)ceilf(__fdiv_rn((float)log((double)ratio), log_scale_factor));
+        if (lvl < 0) lvl = 0;
+        else if (lvl >= nlevels) lvl = nlevels - 1;
+        radius = __fmul_rn(th, gld(scale + lvl));
+    }
+    qx[o] = u; qy[o] = v; qr[o] = radius;
+    qmin[o] = lvl - 1; qmax[o] = lvl;   // kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel (:504-507, :1411-1414)
+    qvalid[o] = ok ? 1 : 0;
+}
+
 // A loaded monocular / rectified orbx_frame copied into a key frame's own allocation -- what KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-82) does with
 // mvKeysUn, mDescriptors, mvuRight, mvScaleFactors, mvInvLevelSigma2 and mGrid: rows, count, scale factors and the grid AS BUILT (no rebuild).  The count is
 // read on the device (a batch-loaded frame's N may not have reached the host yet).

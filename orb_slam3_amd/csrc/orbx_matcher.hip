@@ -2458,6 +2458,7 @@ extern "C" int orbx_fuse_search(orbx_matcher *m, const orbx_frame_desc *kf, cons
 //   pending counts orbx_keyframe::host_n / rows_n / adopt -- orbx_keyframe_count, both Fuse drivers and the BoW calls learn N through adopt()
 //   Fuse           keyframe_fuse_search_impl (projected queries) and keyframe_fuse_map_points_impl (projection on the device: SearchInNeighbors'
 //                  loop, on a rig both Fuse calls per target), with one decode of the keys: keyframe_fuse_results
+//                  (sim3: LoopClosing::SearchAndFuse's Fuse through the same driver; LoopClosing's Sim3 SearchByProjection further down)
 // ---------------------------------------------------------------------------------------------------------
 // The BoW state of a key frame (orbx_keyframe_compute_bow / orbx_keyframe_bow_from_frame): a SECOND allocation, made when BoW is first attached -- key
 // frames without it keep their size.  Set once, immutable afterwards; guarded as the rows are (an event behind its creation, a done flag).
@@ -2852,7 +2853,9 @@ int orbx_keyframe_fuse_search_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *
 // [camera,] map point) into the arena, k_window_best1_kf searches the sides * n_kf problems -- the records never visit the host, the map points go up
 // once.  Monocular: cams / poses [n_kf], one problem per key frame, Fuse(pKFi, vpMapPointMatches).  fisheye: views [n_kf][2] instead, two problems per
 // key frame -- Fuse(pKFi, vpMapPointMatches) and Fuse(pKFi, vpMapPointMatches, true) -- and counts that are still on the device come home with the results.
-static int keyframe_fuse_map_points_impl(orbx_matcher *m, bool fisheye, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
+// sim3 (monocular key frames): LoopClosing::SearchAndFuse's loop instead, Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (ORBmatcher.cc:1339-1455) -- the
+// records come from k_sim3_project (no ur) and the search is the gate-less one: no inv_sigma2 wanted of the key frames, no mvuRight read.
+static int keyframe_fuse_map_points_impl(orbx_matcher *m, bool fisheye, bool sim3, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
                                          const orbx_frame_pose *poses, const orbx_fisheye_view *views, float th, float log_scale_factor, int strict_fp,
                                          int n_mp, const float *pos, const float *normal, const float *min_dist, const float *max_dist,
                                          const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist, uint8_t *projected) {
@@ -2862,7 +2865,7 @@ static int keyframe_fuse_map_points_impl(orbx_matcher *m, bool fisheye, int n_kf
     const size_t np = (size_t)n_mp, total = (size_t)nprob * np;
     if (total > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !best_idx || !best_dist)) return ORBX_E_BAD_ARG;
     for (int k = 0; k < n_kf; k++)
-        if (!kfs[k] || kfs[k]->fisheye != fisheye || kfs[k]->device != m->device || !kfs[k]->inv_sigma2) return ORBX_E_BAD_ARG;
+        if (!kfs[k] || kfs[k]->fisheye != fisheye || kfs[k]->device != m->device || (!sim3 && !kfs[k]->inv_sigma2)) return ORBX_E_BAD_ARG;
     if (total == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
     const int32_t cnt4[4] = {n_mp, 0, 0, 0};
@@ -2886,18 +2889,18 @@ static int keyframe_fuse_map_points_impl(orbx_matcher *m, bool fisheye, int n_kf
         dR = A.take<KfProblem>(nprob);
         dskip = A.up_opt(skip, (size_t)n_kf * np);
         // written by the projection kernel, read by k_window_best1_kf (no mvuRight on a rig: no qxr)
-        qx = A.take<float>(total); qy = A.take<float>(total); qxr = fisheye ? nullptr : A.take<float>(total); qr = A.take<float>(total);
+        qx = A.take<float>(total); qy = A.take<float>(total); qxr = fisheye || sim3 ? nullptr : A.take<float>(total); qr = A.take<float>(total);
         qmin = A.take<int32_t>(total); qmax = A.take<int32_t>(total);
         qvalid = A.take<uint8_t>(total);
         dkeys = A.take<u64>(total);
     }));
     std::vector<KfProblem> R((size_t)nprob);
     for (int p = 0; p < nprob; p++) {
-        keyframe_problem(kfs[p / sides], true, strict_fp, &R[p], p % sides == 1);
+        keyframe_problem(kfs[p / sides], !sim3, strict_fp, &R[p], p % sides == 1);
         WindowProblem &P = R[p].P;
         const size_t o = (size_t)p * np;
         P.qx = qx + o; P.qy = qy + o; P.qr = qr + o; P.qmin = qmin + o; P.qmax = qmax + o; P.qvalid = qvalid + o;
-        if (!fisheye) P.qxr = qxr + o;
+        if (qxr) P.qxr = qxr + o;
         P.qdesc = dd; P.nq_ptr = dcnt; P.keys = dkeys + o;
     }
     ORBX_TRY(m->h2d(dR, R.data(), sizeof(KfProblem) * (size_t)nprob));
@@ -2906,6 +2909,10 @@ static int keyframe_fuse_map_points_impl(orbx_matcher *m, bool fisheye, int n_kf
     if (fisheye)
         hipLaunchKernelGGL(k_fuse_project_kb8, grid, dim3(256), 0, m->exec(), (const KfProblem *)dR, (const FisheyeView *)dview, th, log_scale_factor, n_mp,
                            (const float *)dp, (const float *)dn, (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx, qy, qr, qmin, qmax, qvalid);
+    else if (sim3)
+        hipLaunchKernelGGL(k_sim3_project, grid, dim3(256), 0, m->exec(), (const KfProblem *)dR, (const orbx_camera *)dcam, (const orbx_frame_pose *)dpose, th,
+                           log_scale_factor, (int)ORBX_SIM3_PROJECT_CAMERA, n_mp, (const float *)dp, (const float *)dn, (const float *)dmn, (const float *)dmx,
+                           (const uint8_t *)dskip, qx, qy, qr, qmin, qmax, qvalid);
     else
         hipLaunchKernelGGL(k_fuse_project, grid, dim3(256), 0, m->exec(), (const KfProblem *)dR, (const orbx_camera *)dcam, (const orbx_frame_pose *)dpose, th,
                            log_scale_factor, n_mp, (const float *)dp, (const float *)dn, (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx, qy,
@@ -2927,7 +2934,7 @@ int orbx_keyframe_fuse_map_points(orbx_matcher *m, int n_kf, orbx_keyframe *cons
                                   float log_scale_factor, int strict_fp, int n_mp, const float *pos, const float *normal, const float *min_dist,
                                   const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
                                   uint8_t *projected) {
-    return keyframe_fuse_map_points_impl(m, false, n_kf, kfs, cams, poses, nullptr, th, log_scale_factor, strict_fp, n_mp, pos, normal, min_dist, max_dist,
+    return keyframe_fuse_map_points_impl(m, false, false, n_kf, kfs, cams, poses, nullptr, th, log_scale_factor, strict_fp, n_mp, pos, normal, min_dist, max_dist,
                                          mp_desc, skip, best_idx, best_dist, projected);
 }
 
@@ -2935,7 +2942,7 @@ int orbx_keyframe_fuse_map_points_fisheye(orbx_matcher *m, int n_kf, orbx_keyfra
                                           float log_scale_factor, int strict_fp, int n_mp, const float *pos, const float *normal, const float *min_dist,
                                           const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
                                           uint8_t *projected) {
-    return keyframe_fuse_map_points_impl(m, true, n_kf, kfs, nullptr, nullptr, views, th, log_scale_factor, strict_fp, n_mp, pos, normal, min_dist,
+    return keyframe_fuse_map_points_impl(m, true, false, n_kf, kfs, nullptr, nullptr, views, th, log_scale_factor, strict_fp, n_mp, pos, normal, min_dist,
                                          max_dist, mp_desc, skip, best_idx, best_dist, projected);
 }
 
@@ -3492,6 +3499,117 @@ int orbx_keyframe_search_for_triangulation_fisheye(orbx_matcher *m, orbx_keyfram
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------
+// LoopClosing's Sim3 projection searches on resident key frames: both SearchByProjection(KeyFrame*, Sim3f&, ...) overloads (ORBmatcher.cc:427-532,
+// :534-646) for K key frames with one shared point set, and SearchAndFuse's loop of Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:1339-1455).  The
+// gates run on the device (k_sim3_project); the searches are the existing kernels: k_window_best2_t + the replay of the query loop over n_kf problems
+// for the first, k_window_best1_kf through keyframe_fuse_map_points_impl for the second.  Monocular / rectified key frames only.
+// ---------------------------------------------------------------------------------------------------------
+extern "C" int orbx_keyframe_search_by_projection_sim3(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
+                                                       const orbx_frame_pose *poses, float th, float ratio_hamming, float log_scale_factor,
+                                                       int projection_form, int n_mp, const float *pos, const float *normal, const float *min_dist,
+                                                       const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip,
+                                                       const uint8_t *const *occupied, int32_t *const *match, int32_t *nmatches, uint8_t *projected,
+                                                       float *proj_u, float *proj_v) {
+    if (!m || n_kf < 0 || n_mp < 0 || (n_kf > 0 && (!kfs || !cams || !poses || !match || !nmatches))) return ORBX_E_BAD_ARG;
+    if ((projection_form != ORBX_SIM3_PROJECT_CAMERA && projection_form != ORBX_SIM3_PROJECT_INVZ) || (proj_u == nullptr) != (proj_v == nullptr))
+        return ORBX_E_BAD_ARG;
+    if (n_kf > ORBX_MAX_FUSE_KEYFRAMES) return ORBX_E_TOO_LARGE;
+    const size_t np = (size_t)n_mp, total = (size_t)n_kf * np;
+    if (total > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc)) return ORBX_E_BAD_ARG;
+    for (int k = 0; k < n_kf; k++) {
+        if (!kfs[k] || kfs[k]->fisheye || kfs[k]->device != m->device || !match[k]) return ORBX_E_BAD_ARG;
+        // k_window_best2_t and the replay take ONE GridParams per launch: the key frames of a call share their image bounds, bit for bit
+        if (memcmp(kfs[k]->bounds, kfs[0]->bounds, sizeof(kfs[0]->bounds)) != 0) return ORBX_E_BAD_ARG;
+    }
+    int nc = 0;   // the rows of match / occupied hold N_k entries: the counts are needed here (cached since the caller sized the rows)
+    for (int k = 0; k < n_kf; k++) {
+        const int rc = keyframe_need_count(kfs[k]);
+        if (rc != ORBX_OK) return rc;
+        nc = std::max(nc, kfs[k]->host_n());
+    }
+    if (nc > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;   // before anything is enqueued: the replay keeps 10 B per feature in LDS
+    for (int k = 0; k < n_kf; k++) {
+        for (int i = 0; i < kfs[k]->host_n(); i++) match[k][i] = -1;
+        nmatches[k] = 0;
+    }
+    if (total == 0) return ORBX_OK;
+    ORBX_HIP(hipSetDevice(m->device));
+    const int32_t cnt4[4] = {n_mp, 0, 0, 0};
+    float *dp, *dn, *dmn, *dmx, *qx, *qy, *qr;
+    uint8_t *dd, *dskip, *qvalid;
+    int32_t *dcnt, *qmin, *qmax, *dmeta, *dentries, *dnm;
+    orbx_camera *dcam;
+    orbx_frame_pose *dpose;
+    KfProblem *dK;
+    WindowProblem *dP;
+    ResolveProblem *dR;
+    u64 *dkeys;
+    std::vector<const uint8_t *> docc((size_t)n_kf, nullptr);
+    std::vector<int32_t *> dmatch((size_t)n_kf, nullptr);
+    ORBX_TRY(m->carve([&](Carve &A) {
+        // uploads, adjacent in the arena (one run): the map points ONCE, then what grows with n_kf -- cameras, poses, skip and occupancy rows, records
+        dp = A.up(pos, 3 * np); dn = A.up(normal, 3 * np); dmn = A.up(min_dist, np); dmx = A.up(max_dist, np);
+        dd = A.up(mp_desc, 32 * np);
+        dcnt = A.up(cnt4, 4);
+        dcam = A.up(cams, (size_t)n_kf); dpose = A.up(poses, (size_t)n_kf);
+        dskip = A.up_opt(skip, total);
+        for (int k = 0; k < n_kf; k++)
+            if (occupied && occupied[k] && kfs[k]->host_n() > 0) docc[(size_t)k] = A.up(occupied[k], (size_t)kfs[k]->host_n());
+        dK = A.take<KfProblem>(n_kf); dP = A.take<WindowProblem>(n_kf); dR = A.take<ResolveProblem>(n_kf);
+        // written by k_sim3_project and the window scan, read by the scan and the replay: device only
+        qr = A.take<float>(total); qmin = A.take<int32_t>(total); qmax = A.take<int32_t>(total);
+        dkeys = A.take<u64>(total * kTopK); dmeta = A.take<int32_t>(total); dentries = A.take<int32_t>(total);
+        // the downloads side by side (one run): the projections, the gates' verdicts, the match rows, nmatches
+        qx = A.take<float>(total); qy = A.take<float>(total); qvalid = A.take<uint8_t>(total);
+        for (int k = 0; k < n_kf; k++) dmatch[(size_t)k] = A.take<int32_t>((size_t)std::max(kfs[k]->host_n(), 1));
+        dnm = A.take<int32_t>(n_kf);
+    }));
+    std::vector<KfProblem> K((size_t)n_kf);
+    std::vector<WindowProblem> P((size_t)n_kf);
+    std::vector<ResolveProblem> R((size_t)n_kf);
+    for (int k = 0; k < n_kf; k++) {
+        const size_t o = (size_t)k * np;
+        keyframe_problem(kfs[k], false, 0, &K[(size_t)k]);   // bounds, levels and scale factors for the projection; the window problem of key frame k:
+        WindowProblem &W = K[(size_t)k].P;
+        W.occupied0 = docc[(size_t)k];
+        W.qx = qx + o; W.qy = qy + o; W.qr = qr + o; W.qmin = qmin + o; W.qmax = qmax + o; W.qvalid = qvalid + o;
+        W.qdesc = dd; W.nq_ptr = dcnt;
+        W.keys = dkeys + o * kTopK; W.meta = dmeta + o;
+        P[(size_t)k] = W;
+        ResolveProblem &Q = R[(size_t)k];
+        memset(&Q, 0, sizeof(Q));
+        Q.mode = 2; Q.max_dist = (float)ORBX_TH_LOW * ratio_hamming; Q.cleared_value = -2;   // the window form: no ratio test, no rotation check
+        Q.match = dmatch[(size_t)k]; Q.nmatches = dnm + k; Q.entries = dentries + o;
+    }
+    ORBX_TRY(m->h2d(dK, K.data(), sizeof(KfProblem) * (size_t)n_kf));
+    ORBX_TRY(m->h2d(dP, P.data(), sizeof(WindowProblem) * (size_t)n_kf));
+    ORBX_TRY(m->h2d(dR, R.data(), sizeof(ResolveProblem) * (size_t)n_kf));
+    ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
+    hipLaunchKernelGGL(k_sim3_project, dim3((unsigned)((n_mp + 255) / 256), (unsigned)n_kf), dim3(256), 0, m->exec(), (const KfProblem *)dK,
+                       (const orbx_camera *)dcam, (const orbx_frame_pose *)dpose, th, log_scale_factor, projection_form, n_mp, (const float *)dp,
+                       (const float *)dn, (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx, qy, qr, qmin, qmax, qvalid);
+    const GridParams g = grid_of(kfs[0]->bounds);
+    ORBX_LAUNCH_WINDOW_BEST2(n_mp, n_kf, m->exec(), (const WindowProblem *)dP, g);
+    { const int rr = launch_resolve<false>(n_kf, m->exec(), dP, dR, g, nc, n_mp, 4); if (rr != ORBX_OK) return rr; }
+    ORBX_HIP(hipGetLastError());
+    if (proj_u) { ORBX_TRY(m->d2h(proj_u, qx, 4 * total)); ORBX_TRY(m->d2h(proj_v, qy, 4 * total)); }
+    if (projected) ORBX_TRY(m->d2h(projected, qvalid, total));
+    for (int k = 0; k < n_kf; k++) ORBX_TRY(m->d2h(match[k], dmatch[(size_t)k], 4 * (size_t)kfs[k]->host_n()));
+    ORBX_TRY(m->d2h(nmatches, dnm, 4 * (size_t)n_kf));
+    ORBX_TRY(m->sync_and_deliver());
+    keyframe_release(kfs, n_kf);
+    return ORBX_OK;
+}
+
+extern "C" int orbx_keyframe_fuse_map_points_sim3(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
+                                                  const orbx_frame_pose *poses, float th, float log_scale_factor, int n_mp, const float *pos,
+                                                  const float *normal, const float *min_dist, const float *max_dist, const uint8_t *mp_desc,
+                                                  const uint8_t *skip, int32_t *best_idx, int32_t *best_dist, uint8_t *projected) {
+    return keyframe_fuse_map_points_impl(m, false, true, n_kf, kfs, cams, poses, nullptr, th, log_scale_factor, 0, n_mp, pos, normal, min_dist, max_dist,
+                                         mp_desc, skip, best_idx, best_dist, projected);
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // Tracking::SearchLocalPoints on a resident frame (Tracking.cc:3339-3413): Frame::isInFrustum (Frame.cc:512-575) of every local map point, the

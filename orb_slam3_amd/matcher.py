@@ -963,6 +963,56 @@ class ORBmatcher:
               "orbx_keyframe_fuse_map_points")
         return bi, bd, pr
 
+    # ---- LoopClosing's Sim3 searches on resident key frames (ORBmatcher.cc:427-646, 1339-1455) ----
+    def _sim3_args(self, kfs, cams, poses, map_points: dict, skip):
+        from ._lib import Camera, FramePose
+        K = len(kfs)
+        assert len(cams) == K and len(poses) == K
+        P, Nn = _f32(np.asarray(map_points["pos"]).reshape(-1, 3)), _f32(np.asarray(map_points["normal"]).reshape(-1, 3))
+        mn, mx, d = _f32(map_points["min_dist"]), _f32(map_points["max_dist"]), _u8(map_points["desc"])
+        n = len(P)
+        sk = None if skip is None else _u8(np.asarray(skip).reshape(K, n))
+        cs = (Camera * max(K, 1))(*[Camera(*[float(x) for x in c]) for c in cams])
+        ps = (FramePose * max(K, 1))(*[FramePose.make(*p) for p in poses])
+        return K, n, (P, Nn, mn, mx, d, sk), (self._kf_handles(kfs), cs, ps)
+
+    def SearchByProjectionSim3KeyFrames(self, kfs, cams, poses, map_points: dict, th: float, ratio_hamming: float = 1.0, log_scale_factor: float = 0.0,
+                                        projection_form: int = _lib.SIM3_PROJECT_CAMERA, skip=None, occupied=None, want_projected: bool = True,
+                                        want_uv: bool = False):
+        """SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (ORBmatcher.cc:427-532; projection_form SIM3_PROJECT_CAMERA) or its
+        vpPointsKFs overload (:534-646; SIM3_PROJECT_INVZ) for K DeviceKeyFrames with one shared point set in one call
+        (orbx_keyframe_search_by_projection_sim3).  cams[k] = orbx_camera fields, poses[k] = (Rcw, tcw, Ow) of Tcw = SE3f(Scw.rotationMatrix(),
+        Scw.translation() / Scw.scale()); map_points as FuseMapPoints; skip [K, n] = isBad() || in spAlreadyFound of key frame k, or None; occupied:
+        None, or per key frame a uint8[N_k] mask (vpMatched[i] != NULL) or None.  The key frames must share their image bounds.
+        Returns (nmatches [K], match: K arrays of N_k map-point indices or -1, projected [K, n] or None, (proj_u, proj_v) [K, n] or None)."""
+        K, n, (P, Nn, mn, mx, d, sk), (hs, cs, ps) = self._sim3_args(kfs, cams, poses, map_points, skip)
+        keep, occ = self._flag_rows(occupied, K)
+        match = [np.full(kf.count(), -1, np.int32) for kf in kfs]
+        rows = (C.c_void_p * max(K, 1))(*[ptr(x) for x in match])
+        nm = np.zeros(max(K, 1), np.int32)
+        pr = np.zeros((K, n), np.uint8) if want_projected else None
+        pu, pv = (np.zeros((K, n), np.float32), np.zeros((K, n), np.float32)) if want_uv else (None, None)
+        check(self._L.orbx_keyframe_search_by_projection_sim3(self._h, K, hs, cs, ps, float(th), float(ratio_hamming), float(log_scale_factor),
+                                                              int(projection_form), n, ptr(P), ptr(Nn), ptr(mn), ptr(mx), ptr(d), ptr(sk),
+                                                              occ if occupied is not None else None, rows, ptr(nm), ptr(pr), ptr(pu), ptr(pv)),
+              "orbx_keyframe_search_by_projection_sim3")
+        del keep
+        return nm[:K], match, pr, ((pu, pv) if want_uv else None)
+
+    def FuseMapPointsSim3(self, kfs, cams, poses, map_points: dict, th: float = 3.0, log_scale_factor: float = 0.0, skip=None,
+                          want_projected: bool = True):
+        """The loop of LoopClosing::SearchAndFuse -- Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (ORBmatcher.cc:1339-1455) per key frame -- in one
+        call, projection included (orbx_keyframe_fuse_map_points_sim3): the gate-less candidate search, no mvuRight.  Arguments as FuseMapPoints with
+        poses[k] of Tcw = SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()); skip [K, n] = isBad() || in pKF_k->GetMapPoints(), or None.
+        Returns (best_idx [K, n], best_dist [K, n], projected [K, n] or None)."""
+        K, n, (P, Nn, mn, mx, d, sk), (hs, cs, ps) = self._sim3_args(kfs, cams, poses, map_points, skip)
+        bi, bd = np.full((K, n), -1, np.int32), np.full((K, n), 256, np.int32)
+        pr = np.zeros((K, n), np.uint8) if want_projected else None
+        check(self._L.orbx_keyframe_fuse_map_points_sim3(self._h, K, hs, cs, ps, float(th), float(log_scale_factor), n, ptr(P), ptr(Nn), ptr(mn),
+                                                         ptr(mx), ptr(d), ptr(sk), ptr(bi), ptr(bd), ptr(pr)),
+              "orbx_keyframe_fuse_map_points_sim3")
+        return bi, bd, pr
+
     # ---- SearchBySim3 (ORBmatcher.cc:1457-1674): two gate-less fuse searches + mutual agreement ----
     def SearchBySim3(self, KF1: FrameView, KF2: FrameView, side1: dict, side2: dict, th: float, already_matched1=None,
                      already_matched2=None, scale_factors1=None, scale_factors2=None):
