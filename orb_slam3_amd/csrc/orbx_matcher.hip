@@ -286,6 +286,62 @@ int orbx_compute_stereo_matches(orbx_matcher *m, const orbx_keypoint *kl, const 
 
 }  // extern "C"
 
+namespace {
+
+// Result rows on their way to the caller of a call on a resident handle (a frame handle, a key frame) whose N may still be on the device only.
+// A block: row k = nc int32 at src + k * nc on the device, bound for dst + k * stride (dst NULL: not wanted).  N known (nc = the entries the caller
+// gets): each row goes straight to the caller.  N pending (nc = the capacity the rows are sized by): each block comes down whole into `land`, one block
+// behind the other, and take() hands the first `count` entries of every row out once the call knows N.  A call names all its blocks at once: `land`
+// must not move while a download into it is on its way.
+struct Rows { const int32_t *src; int k_rows, nc; int32_t *dst; size_t stride; };
+struct PendingRows {
+    orbx_matcher *m;
+    std::vector<int32_t> &land;
+    bool pending;
+    int fetch(const Rows *blocks, int n_blocks = 1) {
+        size_t total = 0, at = 0;
+        for (int b = 0; b < n_blocks; b++) total += (size_t)blocks[b].k_rows * blocks[b].nc;
+        if (pending && land.size() < total) land.resize(total);
+        for (int b = 0; b < n_blocks; b++) {
+            const Rows &r = blocks[b];
+            if (pending) ORBX_TRY(m->d2h(land.data() + at, r.src, 4 * (size_t)r.k_rows * r.nc));
+            for (int k = 0; !pending && r.dst && k < r.k_rows; k++) ORBX_TRY(m->d2h(r.dst + k * r.stride, r.src + (size_t)k * r.nc, 4 * (size_t)r.nc));
+            at += (size_t)r.k_rows * r.nc;
+        }
+        return ORBX_OK;
+    }
+    void take(const Rows *blocks, int n_blocks, int count) const {
+        size_t at = 0;
+        for (int b = 0; b < n_blocks; b++) {
+            const Rows &r = blocks[b];
+            for (int k = 0; count > 0 && r.dst && k < r.k_rows; k++) memcpy(r.dst + k * r.stride, land.data() + at + (size_t)k * r.nc, 4 * (size_t)count);
+            at += (size_t)r.k_rows * r.nc;
+        }
+    }
+};
+
+// What ComputeBoW leaves on a handle, of either kind: word / node id per feature, mvKeysUn[i].angle, the FeatureVector as k_frame_featvec writes it
+// (ascending node ids, the CSR and the indices in std::map / addFeature order, stopped words dropped; fv_meta = {node count, features kept}), and
+// what it was computed with.
+struct BowArrays {
+    int32_t *word = nullptr, *node = nullptr; float *angle = nullptr;
+    uint32_t *fv_node = nullptr; int32_t *fv_ptr = nullptr, *fv_index = nullptr, *fv_meta = nullptr;
+    const orbx_vocabulary *voc = nullptr; int levelsup = 0;
+};
+
+// The rows of a handle as one call sees them (orbx_frame::view, orbx_keyframe::view): n / nl / nr = the counts, -1 while they are on the device only;
+// a fisheye-stereo handle keeps the right camera's rows from roff on.
+struct HandleRows {
+    const uint8_t *desc; const orbx_keypoint *kps; const int32_t *count;
+    int cap, n; bool fisheye; int roff, nl, nr;
+    int feats() const { return n >= 0 ? n : cap; }                                   // features, or their bound
+    // Rows the kernels index.  A fisheye-stereo handle is in ROW space; one made from a batch load keeps the gap behind its left rows after its counts
+    // are adopted: what a call sizes per row goes by the row EXTENT, roff + N_right, not by N.
+    int rows() const { return !fisheye || n < 0 ? feats() : roff + nr; }
+};
+
+}  // namespace
+
 // A frame resident on the device across matcher calls (include/orbx.h, orbx_frame): keypoints, descriptors, optional mvuRight, the count, the
 // scale factors and the 64x48 grid in buffers of its own -- not in the matcher's per-call arena, which begin() hands out again on every call.
 // Every load and every use is enqueued on the owner's stream, so a load is ordered behind the calls that read the previous contents.
@@ -308,23 +364,17 @@ struct orbx_frame {
     int n = 0, nlevels = 0;
     std::vector<float> scale_h;       // mvScaleFactors on the host (the projection matchers' host-side window setup)
     float bounds[4] = {0, 0, 0, 0};
-    std::vector<int32_t> h_match;     // result rows of a call made while N was still on the device (fetch_rows / take_rows)
+    std::vector<int32_t> h_match;     // result rows of a call made while N was still on the device (PendingRows: frame_fetch / frame_take)
     size_t off_kps = 0, off_desc = 0, off_ur = 0, off_count = 0, off_scale = 0, off_gstart = 0, off_gorder = 0;
-    // Frame::ComputeBoW (orbx_frame_compute_bow): word / node id per feature, the FeatureVector (ascending node ids, CSR, feature indices) with its
-    // node count on the device, and mvKeysUn[i].angle.  Valid until the next load.
-    int32_t *bow_word = nullptr, *bow_node = nullptr, *fv_ptr = nullptr, *fv_index = nullptr, *fv_meta = nullptr;
-    uint32_t *fv_node = nullptr;
-    float *angle = nullptr;
+    BowArrays bow;                    // Frame::ComputeBoW (orbx_frame_compute_bow[_fisheye]); valid until the next load
     bool bow_valid = false;
     uint64_t load_seq = 0;            // loads so far: orbx_keyframe_from_frame remembers (handle, load_seq) for orbx_keyframe_bow_from_frame
-    const orbx_vocabulary *bow_voc = nullptr;
-    int bow_levelsup = 0;
     // A fisheye-stereo frame (Frame::Nleft != -1, orbx_frame_load_host_fisheye / orbx_frame_load_stereo_fisheye_batch): features [0, N_left) are the
     // left camera's (rows [0, N_left)), [N_left, N) the right camera's, stored at rows [roff, roff + N_right) -- roff is known on the host before
     // the counts are (a batch load puts them at the left extractor's capacity).  count[0] / count[1] = N_left / N_right on the device; the right
     // camera has a grid of its own; l2r [N_left] / r2l [N_right] = mvLeftToRightMatch / mvRightToLeftMatch.
     bool fisheye = false;
-    int roff = 0, n_left = 0, n_right = -1;   // (cached with n_known)
+    int roff = 0, n_left = 0, n_right = -1;   // (cached with n_known; a monocular frame: roff = 0, n_left = n, n_right = -1)
     int32_t *l2r = nullptr, *r2l = nullptr;
     uint16_t *gstart_r = nullptr, *gorder_r = nullptr;
     size_t off_l2r = 0, off_r2l = 0;
@@ -337,40 +387,17 @@ struct orbx_frame {
     int rows_n() const { return n_known ? n : cap; }
     int rows_left() const { return n_known ? n_left : roff; }
     int rows_right() const { return n_known ? n_right : cap - roff; }
+    HandleRows view() const { return HandleRows{desc, kps, count, cap, host_n(), fisheye, roff, host_left(), host_right()}; }
     // A call that meets the handle with N pending brings N home with its results: fetch_count() among its downloads, adopt_count() behind its
-    // synchronisation.  Apart from the loaders, adopt() is the one place that learns N.
+    // synchronisation (frame_fetch / frame_take).  adopt() is the one place that learns N -- from a loader (frame_loaded) or from the device.
     int fetch_count() { return owner->d2h(h_count, count, fisheye ? 8 : 4); }
     void adopt(int c0, int c1 = 0) {
-        if (fisheye) { n_left = std::min(std::max(c0, 0), roff); n_right = std::min(std::max(c1, 0), cap - roff); }
-        n = fisheye ? n_left + n_right : std::min(std::max(c0, 0), cap);
+        n_left = std::min(std::max(c0, 0), fisheye ? roff : cap);
+        n_right = fisheye ? std::min(std::max(c1, 0), cap - roff) : -1;
+        n = n_left + std::max(n_right, 0);
         n_known = true;
     }
     void adopt_count() { adopt(h_count[0], fisheye ? h_count[1] : 0); }
-    // Result rows on their way to the caller.  A block: row k = nc int32 at src + k * nc on the device, bound for dst + k * stride (dst NULL: not
-    // wanted).  N known (nc = the entries the caller gets): each row goes straight to the caller.  N pending (nc = the capacity the rows are
-    // sized by): each block comes down whole into h_match, one block behind the other, and take_rows() hands the first `count` entries of every
-    // row out once N is adopted.  A call names all its blocks at once: h_match must not move while a download into it is on its way.
-    struct Rows { const int32_t *src; int k_rows, nc; int32_t *dst; size_t stride; };
-    int fetch_rows(const Rows *blocks, int n_blocks = 1) {
-        size_t total = 0, at = 0;
-        for (int b = 0; b < n_blocks; b++) total += (size_t)blocks[b].k_rows * blocks[b].nc;
-        if (!n_known && h_match.size() < total) h_match.resize(total);
-        for (int b = 0; b < n_blocks; b++) {
-            const Rows &r = blocks[b];
-            if (!n_known) ORBX_TRY(owner->d2h(h_match.data() + at, r.src, 4 * (size_t)r.k_rows * r.nc));
-            for (int k = 0; n_known && r.dst && k < r.k_rows; k++) ORBX_TRY(owner->d2h(r.dst + k * r.stride, r.src + (size_t)k * r.nc, 4 * (size_t)r.nc));
-            at += (size_t)r.k_rows * r.nc;
-        }
-        return ORBX_OK;
-    }
-    void take_rows(const Rows *blocks, int n_blocks, int count) const {
-        size_t at = 0;
-        for (int b = 0; b < n_blocks; b++) {
-            const Rows &r = blocks[b];
-            for (int k = 0; r.dst && k < r.k_rows; k++) memcpy(r.dst + k * r.stride, h_match.data() + at + (size_t)k * r.nc, 4 * (size_t)count);
-            at += (size_t)r.k_rows * r.nc;
-        }
-    }
 };
 
 namespace {
@@ -381,6 +408,16 @@ inline GridParams grid_of(const float *b) {
     g.inv_w = 64.0f / (b[1] - b[0]);  // Frame.cc:342-343
     g.inv_h = 48.0f / (b[3] - b[2]);
     return g;
+}
+
+// the frame side of k_in_frustum's record
+inline FrustumFrame frustum_frame(const orbx_camera *cam, const orbx_frame_pose *pose, const float *b, float log_sf, int nlevels, float cos_limit) {
+    FrustumFrame F;
+    memcpy(F.Rcw, pose->Rcw, sizeof(F.Rcw)); memcpy(F.tcw, pose->tcw, sizeof(F.tcw)); memcpy(F.Ow, pose->Ow, sizeof(F.Ow));
+    F.fx = cam->fx; F.fy = cam->fy; F.cx = cam->cx; F.cy = cam->cy; F.mbf = cam->bf;
+    F.minx = b[0]; F.maxx = b[1]; F.miny = b[2]; F.maxy = b[3];
+    F.log_scale_factor = log_sf; F.nlevels = nlevels; F.cos_limit = cos_limit;
+    return F;
 }
 
 // The destination half of a prepare record (FramePrepare / FisheyePrepare), everything else zeroed: the resident buffers of a frame handle or a key frame
@@ -419,9 +456,84 @@ int frame_count(orbx_frame *f, int *n) {
     return ORBX_OK;
 }
 
-}  // namespace
+// The result tail of every call on a frame handle: frame_fetch() among the call's downloads -- the rows, then the count(s) if N is pending -- and
+// frame_take() behind its synchronisation: the count(s) adopted, the first N (left_only: N_left) entries of every row handed out.  Every site calls
+// frame_take() unconditionally: it does nothing for a host-pointer call (f NULL) or when N was known, and says whether it adopted the count(s).
+int frame_fetch(orbx_frame *f, const Rows *blocks, int n_blocks) {
+    ORBX_TRY((PendingRows{f->owner, f->h_match, !f->n_known}.fetch(blocks, n_blocks)));
+    return f->n_known ? ORBX_OK : f->fetch_count();   // N comes back with the results (one small copy of the handle's count(s))
+}
+bool frame_take(orbx_frame *f, const Rows *blocks, int n_blocks, bool left_only = false) {
+    if (!f || f->n_known) return false;
+    f->adopt_count();
+    PendingRows{f->owner, f->h_match, true}.take(blocks, n_blocks, left_only ? f->n_left : f->n);
+    return true;
+}
 
-namespace {
+// the resident side of a window problem; right: the right camera of a fisheye-stereo frame (rows from roff on, count[1], its own grid)
+inline void frame_side(const orbx_frame *f, bool right, WindowProblem &P) {
+    const size_t ro = right ? (size_t)f->roff : 0;
+    P.kps = f->kps + ro; P.desc = f->desc + 32 * ro; P.n_ptr = f->count + (right ? 1 : 0);
+    P.gstart = right ? f->gstart_r : f->gstart; P.gorder = right ? f->gorder_r : f->gorder;
+}
+
+// The head of a load from host arrays: the previous load may still read the staging; the transfer statistics of this load start here
+// (orbx_matcher_debug_transfers).
+int frame_begin_host_load(orbx_frame *f) {
+    ORBX_HIP(hipSetDevice(f->owner->device));
+    if (f->stage_busy) { ORBX_HIP(hipEventSynchronize(f->ev_done)); f->stage_busy = false; }
+    f->owner->begin();
+    return ORBX_OK;
+}
+
+// The tail of every load, behind its kernel launch: the launch's error, ev_done (a batch load: the copy has run; staged: the staging is free again),
+// and ALL of the handle's bookkeeping -- nothing else writes it.  roff: the right camera's first row (monocular: 0); c0, c1: N (, 0) or N_left,
+// N_right where the host knows them, c0 < 0 while they are on the device only.
+int frame_loaded(orbx_frame *f, bool fisheye, int roff, int c0, int c1, bool has_ur, bool staged) {
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipEventRecord(f->ev_done, f->owner->stream));
+    if (staged) f->stage_busy = true;
+    f->fisheye = fisheye; f->roff = roff; f->has_ur = has_ur;
+    f->loaded = true; f->bow_valid = false; f->load_seq++;
+    f->n_known = false; f->n = f->n_left = 0; f->n_right = -1;
+    if (c0 >= 0) f->adopt(c0, c1);
+    return ORBX_OK;
+}
+
+// The host-side window setup of the projection matchers, per query.
+struct Windows {
+    std::vector<float> qr;
+    std::vector<int32_t> qmin, qmax;
+    std::vector<uint8_t> valid;
+    explicit Windows(int n) : qr(n), qmin(n), qmax(n), valid(n) {}
+};
+// map points: r = RadiusByViewingCos(viewCos) [* th] * scale[level], levels [lvl-1, lvl]  (ORBmatcher.cc:63-72; in_view NULL: every point)
+Windows mappoint_windows(const orbx_frame_desc *F, int n, const uint8_t *in_view, const int32_t *level, const float *view_cos, float th) {
+    Windows w(n);
+    const bool bFactor = th != 1.0;
+    for (int i = 0; i < n; i++) {
+        const int lvl = level[i];
+        w.valid[i] = (!in_view || in_view[i]) && lvl >= 0 && lvl < F->nlevels;
+        float r = (view_cos[i] > 0.998) ? 2.5f : 4.0f;
+        if (bFactor) r *= th;
+        w.qr[i] = w.valid[i] ? r * F->scale_factors[lvl] : 0.f;
+        w.qmin[i] = lvl - 1; w.qmax[i] = lvl;
+    }
+    return w;
+}
+// the last frame's features: r = th * scale[octave], levels by level_mode  (ORBmatcher.cc:1726-1735)
+Windows octave_windows(const orbx_frame_desc *F, int n, const int32_t *octave, float th, int level_mode) {
+    Windows w(n);
+    for (int i = 0; i < n; i++) {
+        const int o = octave[i];
+        w.valid[i] = o >= 0 && o < F->nlevels;
+        w.qr[i] = w.valid[i] ? th * F->scale_factors[o] : 0.f;  // :1726
+        if (level_mode == 1) { w.qmin[i] = o; w.qmax[i] = -1; }          // bForward  :1731
+        else if (level_mode == 2) { w.qmin[i] = 0; w.qmax[i] = o; }      // bBackward :1733
+        else { w.qmin[i] = o - 1; w.qmax[i] = o + 1; }                   // :1735
+    }
+    return w;
+}
 
 // shared driver of the two projection matchers (host-pointer form)
 struct ProjArgs {
@@ -473,11 +585,7 @@ int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr,
     WindowProblem *dP;
     ResolveProblem *dR;
     ORBX_TRY(m->carve([&](Carve &A) {
-        if (fh) {   // resident rows: nothing of the frame travels
-            P.kps = fh->kps; P.desc = fh->desc;
-        } else {
-            P.kps = A.up(F->keypoints_un, (size_t)n); P.desc = A.up(F->descriptors, 32 * (size_t)n);
-        }
+        if (!fh) { P.kps = A.up(F->keypoints_un, (size_t)n); P.desc = A.up(F->descriptors, 32 * (size_t)n); }   // (resident rows: nothing of the frame travels)
         dcnt = A.up(cnts, 2, 2);
         if (fh && has_ur) P.u_right = fh->u_right;
         else if (has_ur) P.u_right = A.up(F->u_right, (size_t)n);
@@ -494,13 +602,14 @@ int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr,
         dP = A.take<WindowProblem>(1);
         dR = A.take<ResolveProblem>(1);
         P.keys = A.take<u64>((size_t)nq * kTopK); P.meta = A.take<int32_t>(nq);
-        if (fh) { P.gstart = fh->gstart; P.gorder = fh->gorder; }
-        else { P.gstart = A.take<uint16_t>(kGridCells + 1); P.gorder = A.take<uint16_t>(n); }
+        if (!fh) { P.gstart = A.take<uint16_t>(kGridCells + 1); P.gorder = A.take<uint16_t>(n); }
         R.entries = A.take<int32_t>(nq);
         R.match = A.take<int32_t>(nc);
         R.nmatches = A.take<int32_t>(1);
     }));
-    P.n_ptr = fh ? fh->count : dcnt; P.nq_ptr = dcnt + 1;
+    if (fh) frame_side(fh, false, P);
+    else P.n_ptr = dcnt;
+    P.nq_ptr = dcnt + 1;
     if (brute) { P.gstart = nullptr; P.gorder = nullptr; }
     ORBX_TRY(m->h2d(dP, &P, sizeof(P))); ORBX_TRY(m->h2d(dR, &R, sizeof(R)));
     const float fb[4] = {fh ? fh->bounds[0] : F->min_x, fh ? fh->bounds[1] : F->max_x, fh ? fh->bounds[2] : F->min_y, fh ? fh->bounds[3] : F->max_y};
@@ -513,17 +622,13 @@ int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr,
     }
     { const int rr = brute ? launch_resolve<true>(1, m->exec(), dP, dR, g, nc, nq, 4) : launch_resolve<false>(1, m->exec(), dP, dR, g, nc, nq, 4); if (rr != ORBX_OK) return rr; }
     int32_t nm = 0;
-    const orbx_frame::Rows rows = {R.match, 1, nc, a.match_out, 0};
+    const Rows rows = {R.match, 1, nc, a.match_out, 0};
     if (!fh) ORBX_TRY(m->d2h(a.match_out, R.match, 4 * (size_t)n));
-    else ORBX_TRY(fh->fetch_rows(&rows));
-    if (n < 0) ORBX_TRY(fh->fetch_count());   // N comes back with the results (one small copy of the handle's count)
+    else ORBX_TRY(frame_fetch(fh, &rows, 1));
     ORBX_TRY(m->d2h(&nm, R.nmatches, 4));
     ORBX_TRY(m->sync_and_deliver());
-    if (n < 0) {
-        fh->adopt_count();
-        fh->take_rows(&rows, 1, left_only ? fh->n_left : fh->n);
-        if (left_only) for (int i = fh->n_left; i < fh->n; i++) a.match_out[i] = -1;
-    }
+    if (frame_take(fh, &rows, 1, left_only) && left_only)
+        for (int i = fh->n_left; i < fh->n; i++) a.match_out[i] = -1;
     return nm;
 }
 
@@ -537,20 +642,8 @@ static int search_mappoints_impl(orbx_matcher *m, const orbx_frame_desc *frame, 
                                  int32_t *frame_match) {
     if (!m || !frame || frame->n < 0 || (!frame_match && frame->n > 0) || n_mp < 0) return ORBX_E_BAD_ARG;   // empty frames / query sets are legal
     if (n_mp > 0 && (!proj_x || !proj_y || !pred_level || !view_cos || !mp_desc)) return ORBX_E_BAD_ARG;
-    // per-query window: r = RadiusByViewingCos(viewCos) [* th] * scale[level], levels [lvl-1, lvl]  (ORBmatcher.cc:63-72)
-    std::vector<float> qr(n_mp);
-    std::vector<int32_t> qmin(n_mp), qmax(n_mp);
-    std::vector<uint8_t> valid(n_mp);
-    const bool bFactor = th != 1.0;
-    for (int i = 0; i < n_mp; i++) {
-        const int lvl = pred_level[i];
-        valid[i] = (!mp_in_view || mp_in_view[i]) && lvl >= 0 && lvl < frame->nlevels;
-        float r = (view_cos[i] > 0.998) ? 2.5f : 4.0f;
-        if (bFactor) r *= th;
-        qr[i] = valid[i] ? r * frame->scale_factors[lvl] : 0.f;
-        qmin[i] = lvl - 1; qmax[i] = lvl;
-    }
-    ProjArgs a = {frame, frame_occupied, n_mp, proj_x, proj_y, qr.data(), proj_xr, qmin.data(), qmax.data(), mp_desc, valid.data(),
+    const Windows w = mappoint_windows(frame, n_mp, mp_in_view, pred_level, view_cos, th);
+    ProjArgs a = {frame, frame_occupied, n_mp, proj_x, proj_y, w.qr.data(), proj_xr, w.qmin.data(), w.qmax.data(), mp_desc, w.valid.data(),
                   mp_has_obs, nullptr, 1, nnratio, 0, frame_match, (float)ORBX_TH_HIGH};
     return run_projection(m, a, fh);
 }
@@ -569,18 +662,8 @@ static int search_frame_impl(orbx_matcher *m, const orbx_frame_desc *cur, orbx_f
                              const uint8_t *q_has_obs, float th, int level_mode, int check_orientation, int32_t *cur_match) {
     if (!m || !cur || cur->n < 0 || (!cur_match && cur->n > 0) || n_q < 0) return ORBX_E_BAD_ARG;
     if (n_q > 0 && (!q_u || !q_v || !q_octave || !q_desc || (check_orientation && !q_angle))) return ORBX_E_BAD_ARG;
-    std::vector<float> qr(n_q);
-    std::vector<int32_t> qmin(n_q), qmax(n_q);
-    std::vector<uint8_t> valid(n_q);
-    for (int i = 0; i < n_q; i++) {
-        const int o = q_octave[i];
-        valid[i] = o >= 0 && o < cur->nlevels;
-        qr[i] = valid[i] ? th * cur->scale_factors[o] : 0.f;  // :1726
-        if (level_mode == 1) { qmin[i] = o; qmax[i] = -1; }          // bForward  :1731
-        else if (level_mode == 2) { qmin[i] = 0; qmax[i] = o; }      // bBackward :1733
-        else { qmin[i] = o - 1; qmax[i] = o + 1; }                   // :1735
-    }
-    ProjArgs a = {cur, cur_occupied, n_q, q_u, q_v, qr.data(), q_ur, qmin.data(), qmax.data(), q_desc, valid.data(), q_has_obs,
+    const Windows w = octave_windows(cur, n_q, q_octave, th, level_mode);
+    ProjArgs a = {cur, cur_occupied, n_q, q_u, q_v, w.qr.data(), q_ur, w.qmin.data(), w.qmax.data(), q_desc, w.valid.data(), q_has_obs,
                   q_angle, 2, 0.f, check_orientation, cur_match, (float)ORBX_TH_HIGH};
     return run_projection(m, a, fh);
 }
@@ -591,152 +674,6 @@ int orbx_search_by_projection_frame(orbx_matcher *m, const orbx_frame_desc *cur,
                                     int check_orientation, int32_t *cur_match) {
     return search_frame_impl(m, cur, nullptr, cur_occupied, n_q, q_u, q_v, q_ur, q_octave, q_angle, q_desc, q_has_obs, th, level_mode,
                              check_orientation, cur_match);
-}
-// ---------------------------------------------------------------------------------------------------------
-// Device-resident frame handle (orbx_frame): ExtractORB -> UndistortKeyPoints -> AssignFeaturesToGrid once per frame, then every projection
-// matcher of that frame reads the resident rows and grid.
-// ---------------------------------------------------------------------------------------------------------
-void orbx_frame_destroy(orbx_frame *f) {
-    if (!f) return;
-    (void)hipSetDevice(f->owner->device);
-    (void)hipStreamSynchronize(f->owner->stream);   // nothing of the owner's may still read or write the buffers
-    if (f->dev) (void)hipFree(f->dev);
-    if (f->stage) (void)hipHostFree(f->stage);
-    if (f->h_count) (void)hipHostFree(f->h_count);
-    if (f->ev_src) (void)hipEventDestroy(f->ev_src);
-    if (f->ev_done) (void)hipEventDestroy(f->ev_done);
-    delete f;
-}
-
-int orbx_frame_create(orbx_matcher *m, int cap, orbx_frame **out) {
-    if (!m || !out || cap < 1) return ORBX_E_BAD_ARG;
-    *out = nullptr;
-    if (cap > ORBX_MAX_FRAME_FEATURES) return ORBX_E_TOO_LARGE;
-    ORBX_HIP(hipSetDevice(m->device));
-    orbx_frame *f = new orbx_frame();
-    f->owner = m;
-    f->cap = cap;
-    Layout L;
-    f->off_kps = L.add(28 * (size_t)cap); f->off_desc = L.add(32 * (size_t)cap); f->off_ur = L.add(4 * (size_t)cap);
-    f->off_count = L.add(8); f->off_scale = L.add(4 * (size_t)kFrameMaxLevels);
-    f->off_gstart = L.add(2 * ((size_t)kGridCells + 1)); f->off_gorder = L.add(2 * (size_t)cap);
-    const size_t off_gsr = L.add(2 * ((size_t)kGridCells + 1)), off_gor = L.add(2 * (size_t)cap);
-    f->off_l2r = L.add(4 * (size_t)cap); f->off_r2l = L.add(4 * (size_t)cap);
-    const size_t off_bw = L.add(4 * (size_t)cap), off_bn = L.add(4 * (size_t)cap), off_fn = L.add(4 * (size_t)cap), off_fp = L.add(4 * ((size_t)cap + 1)),
-                 off_fi = L.add(4 * (size_t)cap), off_fm = L.add(16), off_an = L.add(4 * (size_t)cap);
-    f->stage_bytes = L.used;   // the rows (keypoints, descriptors, mvuRight; a fisheye frame's partners) at the device layout's offsets
-    hipError_t e = hipMalloc((void **)&f->dev, L.used);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&f->stage, f->stage_bytes, hipHostMallocCoherent);   // read by k_xfer's lanes
-    if (e == hipSuccess) e = hipHostMalloc((void **)&f->h_count, 64, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_src, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_done, hipEventDisableTiming);
-    if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_frame_destroy(f); return ORBX_E_HIP; }
-    f->kps = (orbx_keypoint *)(f->dev + f->off_kps); f->desc = f->dev + f->off_desc; f->u_right = (float *)(f->dev + f->off_ur);
-    f->count = (int32_t *)(f->dev + f->off_count); f->scale = (float *)(f->dev + f->off_scale);
-    f->gstart = (uint16_t *)(f->dev + f->off_gstart); f->gorder = (uint16_t *)(f->dev + f->off_gorder);
-    f->bow_word = (int32_t *)(f->dev + off_bw); f->bow_node = (int32_t *)(f->dev + off_bn); f->fv_node = (uint32_t *)(f->dev + off_fn);
-    f->fv_ptr = (int32_t *)(f->dev + off_fp); f->fv_index = (int32_t *)(f->dev + off_fi); f->fv_meta = (int32_t *)(f->dev + off_fm);
-    f->angle = (float *)(f->dev + off_an);
-    f->gstart_r = (uint16_t *)(f->dev + off_gsr); f->gorder_r = (uint16_t *)(f->dev + off_gor);
-    f->l2r = (int32_t *)(f->dev + f->off_l2r); f->r2l = (int32_t *)(f->dev + f->off_r2l);
-    f->n_known = true;   // an empty frame until the first load
-    *out = f;
-    return ORBX_OK;
-}
-
-
-int orbx_frame_load_host(orbx_frame *f, const orbx_frame_desc *d) {
-    if (!f || !d || d->n < 0 || (d->n > 0 && (!d->keypoints_un || !d->descriptors)) || !d->scale_factors || d->nlevels < 1 ||
-        d->nlevels > kFrameMaxLevels)
-        return ORBX_E_BAD_ARG;
-    if (d->n > f->cap) return ORBX_E_TOO_LARGE;
-    orbx_matcher *m = f->owner;
-    ORBX_HIP(hipSetDevice(m->device));
-    if (f->stage_busy) { ORBX_HIP(hipEventSynchronize(f->ev_done)); f->stage_busy = false; }   // the previous load still reads the staging
-    m->begin();   // (transfer statistics of this load: orbx_matcher_debug_transfers)
-    const int n = d->n;
-    const size_t b_kps = 28 * (size_t)n, b_desc = 32 * (size_t)n, b_ur = d->u_right ? 4 * (size_t)n : 0;
-    memcpy(f->stage + f->off_kps, d->keypoints_un, b_kps);
-    memcpy(f->stage + f->off_desc, d->descriptors, b_desc);
-    if (b_ur) memcpy(f->stage + f->off_ur, d->u_right, b_ur);
-    // the rows in ONE k_xfer launch in the owner's queue (ORBX_MATCHER_DMA=1: by the DMA engine); count and scale factors travel as k_frame_prepare's arguments
-    const orbx_matcher::Span rows[3] = {{f->off_kps, b_kps}, {f->off_desc, b_desc}, {f->off_ur, b_ur}};
-    ORBX_TRY(m->upload_ranges(f->dev, f->stage, rows, 3));
-    FramePrepare P;
-    const float b[4] = {d->min_x, d->max_x, d->min_y, d->max_y};
-    frame_prepare_common(f, P, 0, d->scale_factors, d->nlevels, b);
-    P.n_host = n; P.cap = f->cap;
-    hipLaunchKernelGGL(k_frame_prepare, dim3(1), dim3(64), 0, m->stream, P, grid_of(f->bounds));
-    ORBX_HIP(hipGetLastError());
-    ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
-    f->stage_busy = true;
-    f->n = n; f->n_known = true; f->has_ur = d->u_right != nullptr; f->loaded = true; f->bow_valid = false; f->load_seq++;
-    f->fisheye = false; f->n_right = -1;
-    return ORBX_OK;
-}
-
-int orbx_frame_load_batch(orbx_frame *f, orbx_extractor *ex, int frame, const float *bounds4, const float *scale_factors, int nlevels) {
-    if (!f || !ex) return ORBX_E_BAD_ARG;
-    orbx_matcher *m = f->owner;
-    if (frame < 0 || frame >= ex->last_batch || ex->device != m->device || ex->cap > f->cap) return ORBX_E_BAD_ARG;
-    const float *sf = scale_factors ? scale_factors : ex->scale.data();
-    const int nl = scale_factors ? nlevels : ex->prm.nlevels;
-    if (nl < 1 || nl > kFrameMaxLevels || (!bounds4 && ex->width <= 0)) return ORBX_E_BAD_ARG;
-    const float *b = bounds4 ? bounds4 : ex->bounds;   // mnMinX.. of the extractor's camera (orbx_set_camera) or the image rectangle
-    ORBX_HIP(hipSetDevice(m->device));
-    FramePrepare P;
-    frame_prepare_common(f, P, 0, sf, nl, b);
-    P.cap = f->cap;
-    const size_t cap = (size_t)ex->cap;
-    P.src_kps = (const orbx_keypoint *)ex->match_kps() + (size_t)frame * cap;   // mvKeysUn
-    P.src_desc = (const uint8_t *)ex->d_desc.p + (size_t)frame * cap * 32;
-    P.src_count = (const int32_t *)ex->d_count.p + frame;
-    // the owner's stream waits for the extraction, the extractor's stream for the copy: no host synchronisation, and the next batch on `ex`
-    // overwrites its outputs only after this frame holds its own copy
-    ORBX_HIP(hipEventRecord(f->ev_src, ex->stream));
-    ORBX_HIP(hipStreamWaitEvent(m->stream, f->ev_src, 0));
-    hipLaunchKernelGGL(k_frame_prepare, dim3(1 + (unsigned)((cap + 255) / 256)), dim3(64), 0, m->stream, P, grid_of(f->bounds));
-    ORBX_HIP(hipGetLastError());
-    ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
-    ORBX_HIP(hipStreamWaitEvent(ex->stream, f->ev_done, 0));
-    f->n_known = false; f->has_ur = false; f->loaded = true; f->bow_valid = false; f->load_seq++;
-    f->fisheye = false; f->n_right = -1;
-    return ORBX_OK;
-}
-
-int orbx_frame_count(orbx_frame *f, int *n) {
-    if (!f || !n) return ORBX_E_BAD_ARG;
-    return frame_count(f, n);
-}
-
-// the orbx_frame_desc the host-side window setup reads (scale factors, levels, bounds); rows are never read from it
-static orbx_frame_desc frame_desc_of(const orbx_frame *f) {
-    orbx_frame_desc d;
-    memset(&d, 0, sizeof(d));
-    d.n = f->rows_n();
-    d.min_x = f->bounds[0]; d.max_x = f->bounds[1]; d.min_y = f->bounds[2]; d.max_y = f->bounds[3];
-    d.scale_factors = f->scale_h.data(); d.nlevels = f->nlevels;
-    d.u_right = f->has_ur ? f->u_right : nullptr;
-    return d;
-}
-
-int orbx_frame_search_by_projection_mappoints(orbx_matcher *m, orbx_frame *frame, const uint8_t *frame_occupied, int n_mp, const float *proj_x,
-                                              const float *proj_y, const float *proj_xr, const int32_t *pred_level, const float *view_cos,
-                                              const uint8_t *mp_desc, const uint8_t *mp_in_view, const uint8_t *mp_has_obs, float th, float nnratio,
-                                              int32_t *frame_match) {
-    if (!m || !frame || frame->owner != m || frame->fisheye || !frame_match) return ORBX_E_BAD_ARG;   // (a fisheye frame: the _fisheye forms)
-    const orbx_frame_desc d = frame_desc_of(frame);
-    return search_mappoints_impl(m, &d, frame, frame_occupied, n_mp, proj_x, proj_y, proj_xr, pred_level, view_cos, mp_desc, mp_in_view, mp_has_obs,
-                                 th, nnratio, frame_match);
-}
-
-int orbx_frame_search_by_projection_frame(orbx_matcher *m, orbx_frame *cur, const uint8_t *cur_occupied, int n_q, const float *q_u, const float *q_v,
-                                          const float *q_ur, const int32_t *q_octave, const float *q_angle, const uint8_t *q_desc,
-                                          const uint8_t *q_has_obs, float th, int level_mode, int check_orientation, int32_t *cur_match) {
-    if (!m || !cur || cur->owner != m || cur->fisheye || !cur_match) return ORBX_E_BAD_ARG;
-    const orbx_frame_desc d = frame_desc_of(cur);
-    return search_frame_impl(m, &d, cur, cur_occupied, n_q, q_u, q_v, q_ur, q_octave, q_angle, q_desc, q_has_obs, th, level_mode, check_orientation,
-                             cur_match);
 }
 
 }  // extern "C"
@@ -824,9 +761,7 @@ int run_projection_twin(orbx_matcher *m, const TwinArgs &a, orbx_frame *fh = nul
         dP = A.take<WindowProblem>(2);
     }));
     if (fh) {
-        P[0].kps = fh->kps; P[0].desc = fh->desc; P[0].n_ptr = fh->count; P[0].gstart = fh->gstart; P[0].gorder = fh->gorder;
-        P[1].kps = fh->kps + fh->roff; P[1].desc = fh->desc + (size_t)fh->roff * 32; P[1].n_ptr = fh->count + 1;
-        P[1].gstart = fh->gstart_r; P[1].gorder = fh->gorder_r;
+        for (int s = 0; s < 2; s++) frame_side(fh, s == 1, P[s]);
     } else {
         if (nl) ORBX_TRY(m->h2d(dk, F->keypoints_un, 28 * (size_t)nl));
         if (nr) ORBX_TRY(m->h2d(dk + nl, a.kps_right, 28 * (size_t)nr));
@@ -839,13 +774,12 @@ int run_projection_twin(orbx_matcher *m, const TwinArgs &a, orbx_frame *fh = nul
     if (!fh) ORBX_LAUNCH_GRID_BUILD( dim3(2), dim3(64), 0, m->exec(), dP, g);
     ORBX_TRY(launch_twin(m, dP, T, g, nc, nq));
     int32_t nm = 0;
-    const orbx_frame::Rows rows = {T.match, 1, nc, a.match_out, 0};
+    const Rows rows = {T.match, 1, nc, a.match_out, 0};
     if (!fh) ORBX_TRY(m->d2h(a.match_out, T.match, 4 * (size_t)N));
-    else ORBX_TRY(fh->fetch_rows(&rows));
-    if (N < 0) ORBX_TRY(fh->fetch_count());   // the counts come back with the results
+    else ORBX_TRY(frame_fetch(fh, &rows, 1));
     ORBX_TRY(m->d2h(&nm, T.nmatches, 4));
     ORBX_TRY(m->sync_and_deliver());
-    if (N < 0) { fh->adopt_count(); fh->take_rows(&rows, 1, fh->n); }
+    frame_take(fh, &rows, 1);
     return nm;
 }
 
@@ -864,29 +798,11 @@ static int search_mappoints_fisheye_impl(orbx_matcher *m, const orbx_frame_desc 
     if (!fh && ((left->n > 0 && !left_to_right) || (n_right > 0 && (!right_to_left || !kps_right)))) return ORBX_E_BAD_ARG;
     if (n_mp > 0 && (!in_view || !proj_x || !proj_y || !pred_level || !view_cos || !in_view_r || !proj_xr || !proj_yr || !pred_level_r || !view_cos_r || !mp_desc))
         return ORBX_E_BAD_ARG;
-    std::vector<float> qr[2];
-    std::vector<int32_t> qmin[2], qmax[2];
-    std::vector<uint8_t> valid[2];
-    const bool bFactor = th != 1.0;
-    for (int s = 0; s < 2; s++) { qr[s].resize(n_mp); qmin[s].resize(n_mp); qmax[s].resize(n_mp); valid[s].resize(n_mp); }
-    for (int i = 0; i < n_mp; i++) {
-        // left search :60-76
-        const int lvl = pred_level[i];
-        valid[0][i] = in_view[i] && lvl >= 0 && lvl < left->nlevels;
-        float r = (view_cos[i] > 0.998) ? 2.5f : 4.0f;
-        if (bFactor) r *= th;
-        qr[0][i] = valid[0][i] ? r * left->scale_factors[lvl] : 0.f;
-        qmin[0][i] = lvl - 1; qmax[0][i] = lvl;
-        // right twin :144-152: needs mbTrackInViewR and mnTrackScaleLevelR != -1; RadiusByViewingCos(mTrackViewCosR) WITHOUT the th factor
-        const int lr = pred_level_r[i];
-        valid[1][i] = in_view_r[i] && lr >= 0 && lr < left->nlevels;
-        const float rr = (view_cos_r[i] > 0.998) ? 2.5f : 4.0f;
-        qr[1][i] = valid[1][i] ? rr * left->scale_factors[lr] : 0.f;
-        qmin[1][i] = lr - 1; qmax[1][i] = lr;
-    }
+    // left search :60-76; right twin :144-152: needs mbTrackInViewR and mnTrackScaleLevelR != -1, RadiusByViewingCos(mTrackViewCosR) WITHOUT the th factor
+    const Windows w[2] = {mappoint_windows(left, n_mp, in_view, pred_level, view_cos, th), mappoint_windows(left, n_mp, in_view_r, pred_level_r, view_cos_r, 1.f)};
     TwinArgs a = {left, kps_right, n_right, left_to_right, right_to_left, frame_occupied, n_mp, {proj_x, proj_xr}, {proj_y, proj_yr},
-                  {qr[0].data(), qr[1].data()}, {qmin[0].data(), qmin[1].data()}, {qmax[0].data(), qmax[1].data()}, {valid[0].data(), valid[1].data()},
-                  mp_desc, mp_has_obs, nullptr, 1, nnratio, 0, frame_match};
+                  {w[0].qr.data(), w[1].qr.data()}, {w[0].qmin.data(), w[1].qmin.data()}, {w[0].qmax.data(), w[1].qmax.data()},
+                  {w[0].valid.data(), w[1].valid.data()}, mp_desc, mp_has_obs, nullptr, 1, nnratio, 0, frame_match};
     return run_projection_twin(m, a, fh);
 }
 
@@ -909,19 +825,9 @@ static int search_frame_fisheye_impl(orbx_matcher *m, const orbx_frame_desc *lef
                                      const uint8_t *q_has_obs, float th, int level_mode, int check_orientation, int32_t *cur_match) {
     if (!m || !left || left->n < 0 || n_right < 0 || n_q < 0 || (!cur_match && left->n + n_right > 0) || (!fh && n_right > 0 && !kps_right)) return ORBX_E_BAD_ARG;
     if (n_q > 0 && (!q_u || !q_v || !q_ur || !q_vr || !q_octave || !q_desc || (check_orientation && !q_angle))) return ORBX_E_BAD_ARG;
-    std::vector<float> qr(n_q);
-    std::vector<int32_t> qmin(n_q), qmax(n_q);
-    std::vector<uint8_t> valid(n_q);
-    for (int i = 0; i < n_q; i++) {
-        const int o = q_octave[i];
-        valid[i] = o >= 0 && o < left->nlevels;
-        qr[i] = valid[i] ? th * left->scale_factors[o] : 0.f;   // :1726, the twin uses the same radius (:1800)
-        if (level_mode == 1) { qmin[i] = o; qmax[i] = -1; }
-        else if (level_mode == 2) { qmin[i] = 0; qmax[i] = o; }
-        else { qmin[i] = o - 1; qmax[i] = o + 1; }
-    }
-    TwinArgs a = {left, kps_right, n_right, nullptr, nullptr, cur_occupied, n_q, {q_u, q_ur}, {q_v, q_vr}, {qr.data(), qr.data()},
-                  {qmin.data(), qmin.data()}, {qmax.data(), qmax.data()}, {valid.data(), valid.data()}, q_desc, q_has_obs, q_angle, 2, 0.f,
+    const Windows w = octave_windows(left, n_q, q_octave, th, level_mode);   // the twin uses the same radius (:1800)
+    TwinArgs a = {left, kps_right, n_right, nullptr, nullptr, cur_occupied, n_q, {q_u, q_ur}, {q_v, q_vr}, {w.qr.data(), w.qr.data()},
+                  {w.qmin.data(), w.qmin.data()}, {w.qmax.data(), w.qmax.data()}, {w.valid.data(), w.valid.data()}, q_desc, q_has_obs, q_angle, 2, 0.f,
                   check_orientation, cur_match};
     return run_projection_twin(m, a, fh);
 }
@@ -944,6 +850,256 @@ extern "C" int orbx_search_by_projection_window(orbx_matcher *m, const orbx_fram
                   q_angle, 2, 0.f, check_orientation, match, max_dist};
     return run_projection(m, a);
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// Device-resident frame handle (include/orbx.h, orbx_frame): ExtractORB -> UndistortKeyPoints -> AssignFeaturesToGrid once per frame, then every
+// matcher of that frame reads the resident rows and grids.  Two kinds, monocular / rectified and fisheye-stereo (Frame::Nleft != -1: features
+// [0, N_left) are the left camera's, [N_left, N) the right camera's, and every occupancy mask and match array uses that numbering), with ONE path each
+// for what they share:
+//   loads           the four public loaders describe their source (staged host arrays, an extractor's batch) and launch k_frame_prepare[_fisheye];
+//                   one head for the host loads (frame_begin_host_load), one tail that writes ALL the bookkeeping (frame_loaded)
+//   pending counts  orbx_frame::host_* / rows_* / adopt -- orbx_frame_count[s] (frame_count) and every call below learn N through adopt()
+//   result tail     frame_fetch among a call's downloads, frame_take behind its synchronisation (PendingRows on h_match)
+//   projection      the wrappers below hand the handle to run_projection / run_projection_twin, which read its side through frame_side
+//   SearchLocalPoints  local_points_head / local_points_up / local_points_tail around each kind's records and kernels
+//   BoW             further down (it needs the vocabulary): BowArrays on the handle, frame_compute_bow / frame_bow_ids_down,
+//                   frame_search_by_bow_impl (host key frames) and frame_search_by_bow_resident (resident ones, run_bow_resident)
+// ---------------------------------------------------------------------------------------------------------
+extern "C" {
+
+void orbx_frame_destroy(orbx_frame *f) {
+    if (!f) return;
+    (void)hipSetDevice(f->owner->device);
+    (void)hipStreamSynchronize(f->owner->stream);   // nothing of the owner's may still read or write the buffers
+    if (f->dev) (void)hipFree(f->dev);
+    if (f->stage) (void)hipHostFree(f->stage);
+    if (f->h_count) (void)hipHostFree(f->h_count);
+    if (f->ev_src) (void)hipEventDestroy(f->ev_src);
+    if (f->ev_done) (void)hipEventDestroy(f->ev_done);
+    delete f;
+}
+
+int orbx_frame_create(orbx_matcher *m, int cap, orbx_frame **out) {
+    if (!m || !out || cap < 1) return ORBX_E_BAD_ARG;
+    *out = nullptr;
+    if (cap > ORBX_MAX_FRAME_FEATURES) return ORBX_E_TOO_LARGE;
+    ORBX_HIP(hipSetDevice(m->device));
+    orbx_frame *f = new orbx_frame();
+    f->owner = m;
+    f->cap = cap;
+    Layout L;
+    f->off_kps = L.add(28 * (size_t)cap); f->off_desc = L.add(32 * (size_t)cap); f->off_ur = L.add(4 * (size_t)cap);
+    f->off_count = L.add(8); f->off_scale = L.add(4 * (size_t)kFrameMaxLevels);
+    f->off_gstart = L.add(2 * ((size_t)kGridCells + 1)); f->off_gorder = L.add(2 * (size_t)cap);
+    const size_t off_gsr = L.add(2 * ((size_t)kGridCells + 1)), off_gor = L.add(2 * (size_t)cap);
+    f->off_l2r = L.add(4 * (size_t)cap); f->off_r2l = L.add(4 * (size_t)cap);
+    const size_t off_bw = L.add(4 * (size_t)cap), off_bn = L.add(4 * (size_t)cap), off_fn = L.add(4 * (size_t)cap), off_fp = L.add(4 * ((size_t)cap + 1)),
+                 off_fi = L.add(4 * (size_t)cap), off_fm = L.add(16), off_an = L.add(4 * (size_t)cap);
+    f->stage_bytes = L.used;   // the rows (keypoints, descriptors, mvuRight; a fisheye frame's partners) at the device layout's offsets
+    hipError_t e = hipMalloc((void **)&f->dev, L.used);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&f->stage, f->stage_bytes, hipHostMallocCoherent);   // read by k_xfer's lanes
+    if (e == hipSuccess) e = hipHostMalloc((void **)&f->h_count, 64, hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_src, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&f->ev_done, hipEventDisableTiming);
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); orbx_frame_destroy(f); return ORBX_E_HIP; }
+    f->kps = (orbx_keypoint *)(f->dev + f->off_kps); f->desc = f->dev + f->off_desc; f->u_right = (float *)(f->dev + f->off_ur);
+    f->count = (int32_t *)(f->dev + f->off_count); f->scale = (float *)(f->dev + f->off_scale);
+    f->gstart = (uint16_t *)(f->dev + f->off_gstart); f->gorder = (uint16_t *)(f->dev + f->off_gorder);
+    f->bow.word = (int32_t *)(f->dev + off_bw); f->bow.node = (int32_t *)(f->dev + off_bn); f->bow.fv_node = (uint32_t *)(f->dev + off_fn);
+    f->bow.fv_ptr = (int32_t *)(f->dev + off_fp); f->bow.fv_index = (int32_t *)(f->dev + off_fi); f->bow.fv_meta = (int32_t *)(f->dev + off_fm);
+    f->bow.angle = (float *)(f->dev + off_an);
+    f->gstart_r = (uint16_t *)(f->dev + off_gsr); f->gorder_r = (uint16_t *)(f->dev + off_gor);
+    f->l2r = (int32_t *)(f->dev + f->off_l2r); f->r2l = (int32_t *)(f->dev + f->off_r2l);
+    f->n_known = true;   // an empty frame until the first load
+    *out = f;
+    return ORBX_OK;
+}
+
+
+int orbx_frame_load_host(orbx_frame *f, const orbx_frame_desc *d) {
+    if (!f || !d || d->n < 0 || (d->n > 0 && (!d->keypoints_un || !d->descriptors)) || !d->scale_factors || d->nlevels < 1 ||
+        d->nlevels > kFrameMaxLevels)
+        return ORBX_E_BAD_ARG;
+    if (d->n > f->cap) return ORBX_E_TOO_LARGE;
+    orbx_matcher *m = f->owner;
+    ORBX_TRY(frame_begin_host_load(f));
+    const int n = d->n;
+    const size_t b_kps = 28 * (size_t)n, b_desc = 32 * (size_t)n, b_ur = d->u_right ? 4 * (size_t)n : 0;
+    memcpy(f->stage + f->off_kps, d->keypoints_un, b_kps);
+    memcpy(f->stage + f->off_desc, d->descriptors, b_desc);
+    if (b_ur) memcpy(f->stage + f->off_ur, d->u_right, b_ur);
+    // the rows in ONE k_xfer launch in the owner's queue (ORBX_MATCHER_DMA=1: by the DMA engine); count and scale factors travel as k_frame_prepare's arguments
+    const orbx_matcher::Span rows[3] = {{f->off_kps, b_kps}, {f->off_desc, b_desc}, {f->off_ur, b_ur}};
+    ORBX_TRY(m->upload_ranges(f->dev, f->stage, rows, 3));
+    FramePrepare P;
+    const float b[4] = {d->min_x, d->max_x, d->min_y, d->max_y};
+    frame_prepare_common(f, P, 0, d->scale_factors, d->nlevels, b);
+    P.n_host = n; P.cap = f->cap;
+    hipLaunchKernelGGL(k_frame_prepare, dim3(1), dim3(64), 0, m->stream, P, grid_of(f->bounds));
+    return frame_loaded(f, false, 0, n, 0, d->u_right != nullptr, true);
+}
+
+int orbx_frame_load_batch(orbx_frame *f, orbx_extractor *ex, int frame, const float *bounds4, const float *scale_factors, int nlevels) {
+    if (!f || !ex) return ORBX_E_BAD_ARG;
+    orbx_matcher *m = f->owner;
+    if (frame < 0 || frame >= ex->last_batch || ex->device != m->device || ex->cap > f->cap) return ORBX_E_BAD_ARG;
+    const float *sf = scale_factors ? scale_factors : ex->scale.data();
+    const int nl = scale_factors ? nlevels : ex->prm.nlevels;
+    if (nl < 1 || nl > kFrameMaxLevels || (!bounds4 && ex->width <= 0)) return ORBX_E_BAD_ARG;
+    const float *b = bounds4 ? bounds4 : ex->bounds;   // mnMinX.. of the extractor's camera (orbx_set_camera) or the image rectangle
+    ORBX_HIP(hipSetDevice(m->device));
+    FramePrepare P;
+    frame_prepare_common(f, P, 0, sf, nl, b);
+    P.cap = f->cap;
+    const size_t cap = (size_t)ex->cap;
+    P.src_kps = (const orbx_keypoint *)ex->match_kps() + (size_t)frame * cap;   // mvKeysUn
+    P.src_desc = (const uint8_t *)ex->d_desc.p + (size_t)frame * cap * 32;
+    P.src_count = (const int32_t *)ex->d_count.p + frame;
+    // the owner's stream waits for the extraction, the extractor's stream for the copy: no host synchronisation, and the next batch on `ex`
+    // overwrites its outputs only after this frame holds its own copy
+    ORBX_HIP(hipEventRecord(f->ev_src, ex->stream));
+    ORBX_HIP(hipStreamWaitEvent(m->stream, f->ev_src, 0));
+    hipLaunchKernelGGL(k_frame_prepare, dim3(1 + (unsigned)((cap + 255) / 256)), dim3(64), 0, m->stream, P, grid_of(f->bounds));
+    ORBX_TRY(frame_loaded(f, false, 0, -1, -1, false, false));
+    ORBX_HIP(hipStreamWaitEvent(ex->stream, f->ev_done, 0));
+    return ORBX_OK;
+}
+
+int orbx_frame_load_host_fisheye(orbx_frame *f, const orbx_frame_desc *left, const orbx_keypoint *kps_right, int n_right, const int32_t *l2r,
+                                 const int32_t *r2l) {
+    if (!f || !left || left->n < 0 || n_right < 0 || (left->n > 0 && (!left->keypoints_un || !l2r)) || (n_right > 0 && (!kps_right || !r2l)) ||
+        (left->n + n_right > 0 && !left->descriptors) || !left->scale_factors || left->nlevels < 1 || left->nlevels > kFrameMaxLevels)
+        return ORBX_E_BAD_ARG;
+    const int nl = left->n, nr = n_right, N = nl + nr;
+    // the partners index device memory: checked before anything is enqueued
+    for (int i = 0; i < nl; i++) if (l2r[i] < -1 || l2r[i] >= nr) return ORBX_E_BAD_ARG;
+    for (int j = 0; j < nr; j++) if (r2l[j] < -1 || r2l[j] >= nl) return ORBX_E_BAD_ARG;
+    if (N > f->cap) return ORBX_E_TOO_LARGE;
+    orbx_matcher *m = f->owner;
+    ORBX_TRY(frame_begin_host_load(f));
+    // rows in place: left at 0, right at roff = N_left, so the descriptors of all N features are one run
+    const size_t b_kl = 28 * (size_t)nl, b_kr = 28 * (size_t)nr, b_desc = 32 * (size_t)N, b_l2r = 4 * (size_t)nl, b_r2l = 4 * (size_t)nr;
+    memcpy(f->stage + f->off_kps, left->keypoints_un, b_kl);
+    memcpy(f->stage + f->off_kps + b_kl, kps_right, b_kr);
+    memcpy(f->stage + f->off_desc, left->descriptors, b_desc);
+    memcpy(f->stage + f->off_l2r, l2r, b_l2r);
+    memcpy(f->stage + f->off_r2l, r2l, b_r2l);
+    const orbx_matcher::Span rows[4] = {{f->off_kps, b_kl + b_kr}, {f->off_desc, b_desc}, {f->off_l2r, b_l2r}, {f->off_r2l, b_r2l}};
+    ORBX_TRY(m->upload_ranges(f->dev, f->stage, rows, 4));
+    const float b[4] = {left->min_x, left->max_x, left->min_y, left->max_y};
+    FisheyePrepare P;
+    frame_prepare_common(f, P, nl, left->scale_factors, left->nlevels, b);
+    P.n_host[0] = nl; P.n_host[1] = nr; P.cap_side[0] = nl; P.cap_side[1] = nr;
+    P.l2r = f->l2r; P.r2l = f->r2l;
+    hipLaunchKernelGGL(k_frame_prepare_fisheye, dim3(2), dim3(64), 0, m->stream, P, grid_of(f->bounds));
+    return frame_loaded(f, true, nl, nl, nr, false, true);
+}
+
+int orbx_frame_load_stereo_fisheye_batch(orbx_frame *f, orbx_extractor *L, orbx_extractor *R, int frame, const float *bounds4,
+                                         const float *scale_factors, int nlevels) {
+    if (!f || !L || !R) return ORBX_E_BAD_ARG;
+    orbx_matcher *m = f->owner;
+    // the stage's results must be those of the extractors' current batches
+    if (L->sf_batch <= 0 || !L->ev_sf || L->sf_right != R || L->sf_seq_l != L->batch_seq || L->sf_seq_r != R->batch_seq) return ORBX_E_BAD_ARG;
+    if (frame < 0 || frame >= L->sf_batch || frame >= L->last_batch || L->device != m->device || R->device != m->device) return ORBX_E_BAD_ARG;
+    const int capL = L->sf_capL, capR = L->sf_capR;
+    if (capL != L->cap || capR != R->cap || (size_t)capL + (size_t)capR > (size_t)f->cap) return ORBX_E_BAD_ARG;
+    const float *sf = scale_factors ? scale_factors : L->scale.data();
+    const int nl = scale_factors ? nlevels : L->prm.nlevels;
+    if (nl < 1 || nl > kFrameMaxLevels || (!bounds4 && L->width <= 0)) return ORBX_E_BAD_ARG;
+    const float *b = bounds4 ? bounds4 : L->bounds;
+    ORBX_HIP(hipSetDevice(m->device));
+    FisheyePrepare P;
+    frame_prepare_common(f, P, capL, sf, nl, b);
+    const size_t fr = (size_t)frame;
+    P.src_kps[0] = (const orbx_keypoint *)L->d_kps.p + fr * capL;   // mvKeys: the raw keypoints k_tri_kb8_stereo read
+    P.src_kps[1] = (const orbx_keypoint *)R->d_kps.p + fr * capR;
+    P.src_desc[0] = (const uint8_t *)L->d_desc.p + fr * capL * 32;
+    P.src_desc[1] = (const uint8_t *)R->d_desc.p + fr * capR * 32;
+    P.src_count[0] = (const int32_t *)L->d_count.p + fr;
+    P.src_count[1] = (const int32_t *)R->d_count.p + fr;
+    P.src_l2r = (const int32_t *)L->d_sf_l2r.p + fr * capL;
+    P.src_r2l = (const int32_t *)L->d_sf_r2l.p + fr * capR;
+    P.cap_side[0] = capL; P.cap_side[1] = capR;
+    P.l2r = f->l2r; P.r2l = f->r2l;
+    // the owner's stream waits for the stage (which waited for both extractions); both extractors' next batches and the left extractor's next
+    // stage wait for the copy: no host synchronisation
+    ORBX_HIP(hipStreamWaitEvent(m->stream, L->ev_sf, 0));
+    hipLaunchKernelGGL(k_frame_prepare_fisheye, dim3(2 + (unsigned)((std::max(capL, capR) + 255) / 256)), dim3(64), 0, m->stream, P, grid_of(f->bounds));
+    ORBX_TRY(frame_loaded(f, true, capL, -1, -1, false, false));
+    ORBX_HIP(hipStreamWaitEvent(L->stream, f->ev_done, 0));
+    ORBX_HIP(hipStreamWaitEvent(R->stream, f->ev_done, 0));
+    if (L->match_stream) ORBX_HIP(hipStreamWaitEvent(L->match_stream, f->ev_done, 0));
+    return ORBX_OK;
+}
+
+int orbx_frame_count(orbx_frame *f, int *n) {
+    if (!f || !n) return ORBX_E_BAD_ARG;
+    return frame_count(f, n);
+}
+
+int orbx_frame_counts(orbx_frame *f, int *n_left, int *n_right) {
+    if (!f) return ORBX_E_BAD_ARG;
+    int n = 0;
+    const int rc = frame_count(f, &n);
+    if (rc != ORBX_OK) return rc;
+    if (n_left) *n_left = f->n_left;     // (a monocular frame: N, -1)
+    if (n_right) *n_right = f->n_right;
+    return ORBX_OK;
+}
+
+// the orbx_frame_desc the host-side window setup reads (scale factors, levels, bounds); rows are never read from it
+static orbx_frame_desc frame_desc_of(const orbx_frame *f) {
+    orbx_frame_desc d;
+    memset(&d, 0, sizeof(d));
+    d.n = f->rows_n();
+    d.min_x = f->bounds[0]; d.max_x = f->bounds[1]; d.min_y = f->bounds[2]; d.max_y = f->bounds[3];
+    d.scale_factors = f->scale_h.data(); d.nlevels = f->nlevels;
+    d.u_right = f->has_ur ? f->u_right : nullptr;
+    return d;
+}
+
+int orbx_frame_search_by_projection_mappoints(orbx_matcher *m, orbx_frame *frame, const uint8_t *frame_occupied, int n_mp, const float *proj_x,
+                                              const float *proj_y, const float *proj_xr, const int32_t *pred_level, const float *view_cos,
+                                              const uint8_t *mp_desc, const uint8_t *mp_in_view, const uint8_t *mp_has_obs, float th, float nnratio,
+                                              int32_t *frame_match) {
+    if (!m || !frame || frame->owner != m || frame->fisheye || !frame_match) return ORBX_E_BAD_ARG;   // (a fisheye frame: the _fisheye forms)
+    const orbx_frame_desc d = frame_desc_of(frame);
+    return search_mappoints_impl(m, &d, frame, frame_occupied, n_mp, proj_x, proj_y, proj_xr, pred_level, view_cos, mp_desc, mp_in_view, mp_has_obs,
+                                 th, nnratio, frame_match);
+}
+
+int orbx_frame_search_by_projection_frame(orbx_matcher *m, orbx_frame *cur, const uint8_t *cur_occupied, int n_q, const float *q_u, const float *q_v,
+                                          const float *q_ur, const int32_t *q_octave, const float *q_angle, const uint8_t *q_desc,
+                                          const uint8_t *q_has_obs, float th, int level_mode, int check_orientation, int32_t *cur_match) {
+    if (!m || !cur || cur->owner != m || cur->fisheye || !cur_match) return ORBX_E_BAD_ARG;
+    const orbx_frame_desc d = frame_desc_of(cur);
+    return search_frame_impl(m, &d, cur, cur_occupied, n_q, q_u, q_v, q_ur, q_octave, q_angle, q_desc, q_has_obs, th, level_mode, check_orientation,
+                             cur_match);
+}
+
+int orbx_frame_search_by_projection_mappoints_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, int n_mp,
+                                                      const uint8_t *in_view, const float *proj_x, const float *proj_y, const int32_t *pred_level,
+                                                      const float *view_cos, const uint8_t *in_view_r, const float *proj_xr, const float *proj_yr,
+                                                      const int32_t *pred_level_r, const float *view_cos_r, const uint8_t *mp_desc,
+                                                      const uint8_t *mp_has_obs, float th, float nnratio, int32_t *frame_match) {
+    if (!m || !f || f->owner != m || !f->fisheye || !frame_match) return ORBX_E_BAD_ARG;
+    const orbx_frame_desc d = frame_desc_of(f);
+    return search_mappoints_fisheye_impl(m, &d, f, nullptr, 0, nullptr, nullptr, frame_occupied, n_mp, in_view, proj_x, proj_y, pred_level, view_cos,
+                                         in_view_r, proj_xr, proj_yr, pred_level_r, view_cos_r, mp_desc, mp_has_obs, th, nnratio, frame_match);
+}
+
+int orbx_frame_search_by_projection_frame_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *cur_occupied, int n_q, const float *q_u,
+                                                  const float *q_v, const float *q_ur, const float *q_vr, const int32_t *q_octave,
+                                                  const float *q_angle, const uint8_t *q_desc, const uint8_t *q_has_obs, float th, int level_mode,
+                                                  int check_orientation, int32_t *cur_match) {
+    if (!m || !f || f->owner != m || !f->fisheye || !cur_match) return ORBX_E_BAD_ARG;
+    const orbx_frame_desc d = frame_desc_of(f);
+    return search_frame_fisheye_impl(m, &d, f, nullptr, 0, cur_occupied, n_q, q_u, q_v, q_ur, q_vr, q_octave, q_angle, q_desc, q_has_obs, th, level_mode,
+                                     check_orientation, cur_match);
+}
+
+}  // extern "C"
 
 // the same on a resident frame (Tracking::Relocalization's second stage, Tracking.cc:3726,3740): the frame's rows and grid are the handle's
 extern "C" int orbx_frame_search_by_projection_window(orbx_matcher *m, orbx_frame *f, const uint8_t *occupied, int n_q, const float *q_x,
@@ -971,6 +1127,191 @@ extern "C" int orbx_frame_search_by_projection_window_fisheye(orbx_matcher *m, o
     ProjArgs a = {&d, occupied, n_q, q_x, q_y, q_r, nullptr, q_min_level, q_max_level, q_desc, nullptr, q_has_obs,
                   q_angle, 2, 0.f, check_orientation, match, max_dist};
     return run_projection(m, a, f, true);
+}
+
+namespace {
+
+// ---- Tracking::SearchLocalPoints on a resident frame of either kind.  The two forms share their head, the upload of the map points and their tail;
+// the projection records, the frustum and window kernels and resolve-versus-twin are each kind's own, and each carves its arena in its own order.
+struct LocalPoints { int n; const float *pos, *normal, *min_dist, *max_dist; const uint8_t *desc, *eligible, *has_obs; const float *track_depth; };   // (track_depth: a rig's only)
+struct LocalPointsDev { float *pos, *normal, *min_dist, *max_dist, *track_depth; uint8_t *desc, *eligible, *has_obs, *occupied; };
+
+// The head: the argument checks both forms share (have_view: the form's camera arguments are there), N where the call needs it on the host -- *n = -1
+// while it stays on the device -- and frame_match's -1 fill.  The caller returns 0 behind it when there are no map points.
+int local_points_head(orbx_matcher *m, orbx_frame *f, bool fisheye, bool have_view, const LocalPoints &mp, const uint8_t *occupied, const uint8_t *in_view,
+                      int32_t *frame_match, int *n) {
+    if (!m || !f || f->owner != m || f->fisheye != fisheye || !have_view || mp.n < 0 || !frame_match) return ORBX_E_BAD_ARG;
+    if (mp.n > 0 && (!mp.pos || !mp.normal || !mp.min_dist || !mp.max_dist || !mp.desc || !in_view)) return ORBX_E_BAD_ARG;
+    *n = -1;
+    if (f->n_known || occupied || mp.n == 0) ORBX_TRY(frame_count(f, n));   // the mask holds N entries
+    for (int i = 0; i < *n; i++) frame_match[i] = -1;
+    return ORBX_OK;
+}
+// the first buffers of both arenas: the map points and the occupancy mask, one run of uploads
+LocalPointsDev local_points_up(Carve &A, const LocalPoints &mp, const uint8_t *occupied, int n) {
+    const size_t q = (size_t)mp.n;
+    LocalPointsDev d;
+    d.pos = A.up(mp.pos, 3 * q); d.normal = A.up(mp.normal, 3 * q); d.min_dist = A.up(mp.min_dist, q); d.max_dist = A.up(mp.max_dist, q);
+    d.desc = A.up(mp.desc, 32 * q); d.eligible = A.up_opt(mp.eligible, q); d.has_obs = A.up_opt(mp.has_obs, q); d.track_depth = A.up_opt(mp.track_depth, q);
+    d.occupied = n > 0 ? A.up_opt(occupied, (size_t)n) : nullptr;
+    return d;
+}
+// The tail: mbTrackInView [n_view], then -- unless the frame is empty (match == false: the frustum test only) -- the matches, the count(s) while
+// pending and nmatches; one synchronisation.  Returns nmatches.
+int local_points_tail(orbx_matcher *m, orbx_frame *f, bool match, uint8_t *in_view, const uint8_t *d_in_view, size_t n_view, const int32_t *d_match, int nc,
+                      const int32_t *d_nmatches, int32_t *frame_match) {
+    ORBX_HIP(hipGetLastError());
+    int32_t nm = 0;
+    ORBX_TRY(m->d2h(in_view, d_in_view, n_view));
+    const Rows rows = {d_match, 1, nc, frame_match, 0};
+    if (match) { ORBX_TRY(frame_fetch(f, &rows, 1)); ORBX_TRY(m->d2h(&nm, d_nmatches, 4)); }
+    ORBX_TRY(m->sync_and_deliver());
+    frame_take(f, &rows, 1);
+    return nm;
+}
+
+}  // namespace
+
+// Tracking::SearchLocalPoints on a resident frame (Tracking.cc:3339-3413): Frame::isInFrustum (Frame.cc:512-575) of every local map point, the
+// window setup and SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) (ORBmatcher.cc:43-213, Nleft == -1) in one call: the projection
+// records stay in the call's arena, one transfer up, one down, one synchronisation.
+extern "C" int orbx_frame_search_local_points(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_camera *cam,
+                                              const orbx_frame_pose *pose, float log_scale_factor, float viewing_cos_limit, int n_mp, const float *pos,
+                                              const float *normal, const float *min_dist, const float *max_dist, const uint8_t *mp_desc,
+                                              const uint8_t *eligible, const uint8_t *has_obs, float th, float nnratio, int far_points,
+                                              float th_far_points, uint8_t *in_view, int32_t *frame_match) {
+    const LocalPoints mp = {n_mp, pos, normal, min_dist, max_dist, mp_desc, eligible, has_obs, nullptr};
+    int n = -1;
+    const int rc = local_points_head(m, f, false, cam && pose, mp, frame_occupied, in_view, frame_match, &n);
+    if (rc != ORBX_OK || n_mp == 0) return rc;
+    const int nc = f->rows_n();
+    if (nc > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;
+    ORBX_HIP(hipSetDevice(m->device));
+    const size_t q = (size_t)n_mp;
+    const FrustumFrame FF = frustum_frame(cam, pose, f->bounds, log_scale_factor, f->nlevels, viewing_cos_limit);
+    const int32_t cnts[2] = {n, n_mp};
+    WindowProblem P;
+    memset(&P, 0, sizeof(P));
+    ResolveProblem R;
+    memset(&R, 0, sizeof(R));
+    LocalPointsDev D;
+    float *dx, *dy, *dxr, *dd, *dvc, *dqr;
+    uint8_t *div, *dvalid, *div_out;
+    int32_t *dcnt, *dl, *dqmin, *dqmax;
+    FrustumFrame *dF;
+    WindowProblem *dP;
+    ResolveProblem *dR;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        // inputs (one run of the arena)
+        D = local_points_up(A, mp, frame_occupied, n);
+        dF = A.up(&FF, 1);
+        dcnt = A.up(cnts, 2, 2);
+        dP = A.take<WindowProblem>(1);
+        dR = A.take<ResolveProblem>(1);
+        // the projection records and the windows: device only
+        div = A.take<uint8_t>(q);
+        dx = A.take<float>(q); dy = A.take<float>(q); dxr = A.take<float>(q); dd = A.take<float>(q); dvc = A.take<float>(q);
+        dl = A.take<int32_t>(q);
+        dqr = A.take<float>(q);
+        dqmin = A.take<int32_t>(q); dqmax = A.take<int32_t>(q);
+        dvalid = A.take<uint8_t>(q);
+        P.keys = A.take<u64>(q * kTopK); P.meta = A.take<int32_t>(q);
+        R.entries = A.take<int32_t>(q);
+        // the downloads side by side: mbTrackInView, the matches, nmatches
+        div_out = A.take<uint8_t>(q);
+        R.match = A.take<int32_t>(nc);
+        R.nmatches = A.take<int32_t>(1);
+    }));
+    frame_side(f, false, P);
+    P.nq_ptr = dcnt + 1; P.occupied0 = D.occupied;
+    if (f->has_ur) { P.u_right = f->u_right; P.qxr = dxr; }   // mTrackProjXR against mvuRight (ORBmatcher.cc:92-97)
+    P.qx = dx; P.qy = dy; P.qr = dqr; P.qmin = dqmin; P.qmax = dqmax; P.qdesc = D.desc; P.qvalid = dvalid;
+    R.q_has_obs = D.has_obs;
+    R.mode = 1; R.nnratio = nnratio; R.max_dist = (float)ORBX_TH_HIGH; R.cleared_value = -2;
+    ORBX_TRY(m->h2d(dP, &P, sizeof(P))); ORBX_TRY(m->h2d(dR, &R, sizeof(R)));
+    hipLaunchKernelGGL(k_in_frustum, dim3((n_mp + 255) / 256, 1), dim3(256), 0, m->exec(), (const FrustumFrame *)dF, n_mp, (const float *)D.pos,
+                       (const float *)D.normal, (const float *)D.min_dist, (const float *)D.max_dist, div, dx, dy, dxr, dd, dl, dvc);
+    hipLaunchKernelGGL(k_local_windows, dim3((n_mp + 255) / 256), dim3(256), 0, m->exec(), n_mp, (const uint8_t *)div, (const uint8_t *)D.eligible,
+                       (const int32_t *)dl, (const float *)dvc, (const float *)dd, (const float *)f->scale, f->nlevels, th, far_points ? 1 : 0,
+                       th_far_points, dqr, dqmin, dqmax, dvalid, div_out);
+    const bool match = n != 0;   // (an empty frame: isInFrustum only)
+    if (match) {
+        const GridParams g = grid_of(f->bounds);
+        ORBX_LAUNCH_WINDOW_BEST2(n_mp, 1, m->exec(), dP, g);
+        const int rr = launch_resolve<false>(1, m->exec(), dP, dR, g, nc, n_mp, 4);
+        if (rr != ORBX_OK) return rr;
+    }
+    return local_points_tail(m, f, match, in_view, div_out, q, R.match, nc, R.nmatches, frame_match);
+}
+
+// Tracking::SearchLocalPoints on a resident fisheye-stereo frame: isInFrustumChecks of both cameras (k_in_frustum_checks), the windows
+// (k_local_windows_fisheye), the twin window search and the replay (k_replay_twin) -- the projection records never leave the device.
+extern "C" int orbx_frame_search_local_points_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_fisheye_view *views,
+                                                      float log_scale_factor, float viewing_cos_limit, int n_mp, const float *pos, const float *normal,
+                                                      const float *min_dist, const float *max_dist, const uint8_t *mp_desc, const uint8_t *eligible,
+                                                      const uint8_t *has_obs, const float *track_depth, float th, float nnratio, int far_points,
+                                                      float th_far_points, uint8_t *in_view, int32_t *frame_match) {
+    const LocalPoints mp = {n_mp, pos, normal, min_dist, max_dist, mp_desc, eligible, has_obs, track_depth};
+    int N = -1;
+    const int rc = local_points_head(m, f, true, views != nullptr, mp, frame_occupied, in_view, frame_match, &N);
+    if (rc != ORBX_OK || n_mp == 0) return rc;
+    const int nc = f->rows_n();
+    ORBX_HIP(hipSetDevice(m->device));
+    const size_t q = (size_t)n_mp, q2 = 2 * q;
+    FrustumChecks FC;
+    memset(&FC, 0, sizeof(FC));
+    memcpy(FC.view, views, sizeof(FisheyeView) * 2);
+    FC.minx = f->bounds[0]; FC.maxx = f->bounds[1]; FC.miny = f->bounds[2]; FC.maxy = f->bounds[3];
+    FC.log_scale_factor = log_scale_factor; FC.nlevels = f->nlevels; FC.cos_limit = viewing_cos_limit;
+    const int32_t cnts[4] = {n_mp, 0, 0, 0};
+    WindowProblem P[2];
+    memset(P, 0, sizeof(P));
+    TwinProblem T;
+    memset(&T, 0, sizeof(T));
+    LocalPointsDev D;
+    float *dx, *dy, *dd, *dvc, *dqr;
+    uint8_t *div, *dvalid, *div_out;
+    int32_t *dcnt, *dl, *dqmin, *dqmax;
+    FrustumChecks *dF;
+    WindowProblem *dP;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        // inputs (one run of the arena)
+        D = local_points_up(A, mp, frame_occupied, N);
+        dF = A.up(&FC, 1);
+        dcnt = A.up(cnts, 4);
+        dP = A.take<WindowProblem>(2);
+        // the projection records and the windows: device only, [2][n_mp] (left, right)
+        div = A.take<uint8_t>(q2);
+        dx = A.take<float>(q2); dy = A.take<float>(q2); dd = A.take<float>(q2); dvc = A.take<float>(q2);
+        dl = A.take<int32_t>(q2);
+        dqr = A.take<float>(q2);
+        dqmin = A.take<int32_t>(q2); dqmax = A.take<int32_t>(q2);
+        dvalid = A.take<uint8_t>(q2);
+        for (int s = 0; s < 2; s++) { P[s].keys = A.take<u64>(q * kTopK); P[s].meta = A.take<int32_t>(q); }
+        T.entries = A.take<int32_t>(q2);
+        // the downloads side by side: mbTrackInView / mbTrackInViewR, the matches, nmatches
+        div_out = A.take<uint8_t>(q2);
+        T.match = A.take<int32_t>(nc);
+        T.nmatches = A.take<int32_t>(1);
+    }));
+    for (int s = 0; s < 2; s++) {
+        const size_t o = (size_t)s * q;
+        frame_side(f, s == 1, P[s]);
+        P[s].nq_ptr = dcnt;
+        P[s].qx = dx + o; P[s].qy = dy + o; P[s].qr = dqr + o; P[s].qmin = dqmin + o; P[s].qmax = dqmax + o; P[s].qvalid = dvalid + o; P[s].qdesc = D.desc;
+    }
+    T.q_has_obs = D.has_obs; T.occupied0 = D.occupied;
+    T.mode = 1; T.nq = n_mp; T.nnratio = nnratio; T.max_dist = (float)ORBX_TH_HIGH; T.cleared_value = -2;
+    T.l2r = f->l2r; T.r2l = f->r2l;
+    ORBX_TRY(m->h2d(dP, P, sizeof(P)));
+    hipLaunchKernelGGL(k_in_frustum_checks, dim3((n_mp + 255) / 256, 2), dim3(256), 0, m->exec(), (const FrustumChecks *)dF, n_mp, (const float *)D.pos,
+                       (const float *)D.normal, (const float *)D.min_dist, (const float *)D.max_dist, div, dx, dy, dd, dl, dvc);
+    hipLaunchKernelGGL(k_local_windows_fisheye, dim3((n_mp + 255) / 256), dim3(256), 0, m->exec(), n_mp, (const uint8_t *)div, (const uint8_t *)D.eligible,
+                       (const int32_t *)dl, (const float *)dvc, (const float *)dd, (const float *)D.track_depth, (const float *)f->scale, f->nlevels, th,
+                       far_points ? 1 : 0, th_far_points, dqr, dqmin, dqmax, dvalid, div_out);
+    const bool match = N != 0;   // (an empty frame: isInFrustumChecks only)
+    if (match) ORBX_TRY(launch_twin(m, dP, T, grid_of(f->bounds), nc, n_mp));
+    return local_points_tail(m, f, match, in_view, div_out, q2, T.match, nc, T.nmatches, frame_match);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1632,14 +1973,6 @@ extern "C" int orbx_search_mappoints_batch_device(orbx_extractor *ex, int n_mp, 
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 inline CameraModel model_of(const orbx_camera *c) { return CameraModel{c->fx, c->fy, c->cx, c->cy, c->k1, c->k2, c->p1, c->p2, c->k3}; }
-inline FrustumFrame frustum_frame(const orbx_camera *cam, const orbx_frame_pose *pose, const float *b, float log_sf, int nlevels, float cos_limit) {
-    FrustumFrame F;
-    memcpy(F.Rcw, pose->Rcw, sizeof(F.Rcw)); memcpy(F.tcw, pose->tcw, sizeof(F.tcw)); memcpy(F.Ow, pose->Ow, sizeof(F.Ow));
-    F.fx = cam->fx; F.fy = cam->fy; F.cx = cam->cx; F.cy = cam->cy; F.mbf = cam->bf;
-    F.minx = b[0]; F.maxx = b[1]; F.miny = b[2]; F.maxy = b[3];
-    F.log_scale_factor = log_sf; F.nlevels = nlevels; F.cos_limit = cos_limit;
-    return F;
-}
 }  // namespace
 
 extern "C" int orbx_image_bounds(const orbx_camera *cam, int width, int height, float *bounds4) {
@@ -2138,24 +2471,23 @@ extern "C" int orbx_bow_transform(orbx_matcher *m, const orbx_vocabulary *v, con
 
 namespace {
 
-// What ComputeBoW reads and writes: the rows of a frame handle or of a key frame, and the seven arrays that take the result.
-struct BowTarget {
-    const uint8_t *desc; const orbx_keypoint *kps; const int32_t *count;
-    int n_host, cap;                  // N, or -1 while it is on the device only; the rows the arrays hold
-    int32_t *word, *node; float *angle; uint32_t *fv_node; int32_t *fv_ptr, *fv_index, *fv_meta;
-    bool fisheye;                     // a fisheye-stereo handle: the row-space kernel pair; the right camera's rows from roff on, N per camera (or -1)
-    int roff, n_host_side[2];
-    int rows() const { return n_host >= 0 ? n_host : cap; }   // features the kernels may see
-};
-inline BowTarget bow_target(const orbx_frame *f) {
-    return BowTarget{f->desc, f->kps, f->count, f->host_n(), f->cap, f->bow_word, f->bow_node, f->angle, f->fv_node, f->fv_ptr, f->fv_index, f->fv_meta,
-                     f->fisheye, f->roff, {f->host_left(), f->host_right()}};
+// What ComputeBoW reads and writes: the rows of a frame handle or of a key frame (a fisheye-stereo one: the row-space kernel pair), and the seven
+// arrays that take the result.
+struct BowTarget : HandleRows, BowArrays {};   // (rows() is HandleRows': the row EXTENT; the features the kernels may see are feats())
+inline BowTarget bow_target(const HandleRows &r, const BowArrays &b) { return BowTarget{r, b}; }
+// The ids of a fisheye-stereo handle as they go down: word ids, then node ids, renumbered from rows into features [0, N) at dids [2 nc]
+// (k_frame_rows_to_features on `st`: with N_left still on the device nothing waits for it).
+inline void launch_bow_ids_to_features(hipStream_t st, const HandleRows &r, const BowArrays &b, int nc, int32_t *dids) {
+    const int32_t *src[2] = {b.word, b.node};
+    for (int k = 0; k < 2; k++)
+        hipLaunchKernelGGL(k_frame_rows_to_features, dim3((unsigned)((nc + 255) / 256), 1), dim3(256), 0, st, src[k], 0, dids + (size_t)k * nc, nc, r.count, r.nl,
+                           r.nr, r.cap, r.roff);
 }
 
 // The driver of every ComputeBoW: the transform of the target's descriptors (k_frame_bow_transform[_fisheye]) and the FeatureVector
 // (k_frame_featvec[_fisheye]) on m->stream.  Returns the first HIP error; nothing is synchronised.
 hipError_t launch_compute_bow(orbx_matcher *m, const orbx_vocabulary *v, int levelsup, const BowTarget &t) {
-    const int nc = t.rows();
+    const int nc = t.feats();   // features the kernels may see
     int sort_cap = 1;
     while (sort_cap < nc) sort_cap <<= 1;
     const size_t lds = 8 * (size_t)sort_cap;
@@ -2166,12 +2498,12 @@ hipError_t launch_compute_bow(orbx_matcher *m, const orbx_vocabulary *v, int lev
     }
     FrameBow B;
     memset(&B, 0, sizeof(B));
-    B.count = t.count; B.n_host = t.n_host; B.cap = t.cap; B.kps = t.kps; B.word = t.word; B.node = t.node;
+    B.count = t.count; B.n_host = t.n; B.cap = t.cap; B.kps = t.kps; B.word = t.word; B.node = t.node;
     B.word_pos = v->word_pos; B.n_words = v->n_words;
     B.angle = t.angle; B.fv_node = t.fv_node; B.fv_ptr = t.fv_ptr; B.fv_index = t.fv_index; B.fv_meta = t.fv_meta;
     if (t.fisheye) {
-        const int nl = t.n_host_side[0], nr = t.n_host_side[1], cap_l = t.roff, cap_r = t.cap - t.roff;   // the rows each camera may occupy
-        const int side = t.n_host >= 0 ? std::max(nl, nr) : std::max(cap_l, cap_r);
+        const int nl = t.nl, nr = t.nr, cap_l = t.roff, cap_r = t.cap - t.roff;   // the rows each camera may occupy
+        const int side = t.n >= 0 ? std::max(nl, nr) : std::max(cap_l, cap_r);
         if (side > 0)
             hipLaunchKernelGGL(k_frame_bow_transform_fisheye, dim3((unsigned)((side + 15) / 16), 2), dim3(256), 0, m->stream, v->child_ptr, v->child_idx,
                                v->node_desc, v->word_id, v->L, levelsup, t.desc, t.count, nl, nr, cap_l, cap_r, t.roff, t.word, t.node);
@@ -2179,7 +2511,7 @@ hipError_t launch_compute_bow(orbx_matcher *m, const orbx_vocabulary *v, int lev
     } else {
         if (nc > 0)
             hipLaunchKernelGGL(k_frame_bow_transform, dim3((nc + 15) / 16), dim3(256), 0, m->stream, v->child_ptr, v->child_idx, v->node_desc, v->word_id,
-                               v->L, levelsup, t.desc, t.count, t.n_host, t.cap, t.word, t.node);
+                               v->L, levelsup, t.desc, t.count, t.n, t.cap, t.word, t.node);
         hipLaunchKernelGGL(k_frame_featvec, dim3(1), dim3(1024), lds, m->stream, B, sort_cap);
     }
     return hipGetLastError();
@@ -2189,17 +2521,15 @@ hipError_t launch_compute_bow(orbx_matcher *m, const orbx_vocabulary *v, int lev
 // src_node, with N while it is pending.
 int frame_compute_bow(orbx_matcher *m, orbx_frame *f, const orbx_vocabulary *v, int levelsup) {
     f->bow_valid = false;
-    ORBX_HIP(launch_compute_bow(m, v, levelsup, bow_target(f)));
-    f->bow_valid = true; f->bow_voc = v; f->bow_levelsup = levelsup;
+    ORBX_HIP(launch_compute_bow(m, v, levelsup, bow_target(f->view(), f->bow)));
+    f->bow_valid = true; f->bow.voc = v; f->bow.levelsup = levelsup;
     return ORBX_OK;
 }
 int frame_bow_ids_down(orbx_frame *f, const int32_t *src_word, const int32_t *src_node, int32_t *word_id, int32_t *node_id) {
-    const bool pending = !f->n_known;
-    const orbx_frame::Rows ids[2] = {{src_word, 1, f->rows_n(), word_id, 0}, {src_node, 1, f->rows_n(), node_id, 0}};
-    ORBX_TRY(f->fetch_rows(ids, 2));
-    if (pending) ORBX_TRY(f->fetch_count());   // N comes back with the ids
+    const Rows ids[2] = {{src_word, 1, f->rows_n(), word_id, 0}, {src_node, 1, f->rows_n(), node_id, 0}};
+    ORBX_TRY(frame_fetch(f, ids, 2));
     ORBX_TRY(f->owner->sync_and_deliver());
-    if (pending) { f->adopt_count(); f->take_rows(ids, 2, f->n); }
+    frame_take(f, ids, 2);
     return ORBX_OK;
 }
 
@@ -2214,7 +2544,7 @@ extern "C" int orbx_frame_compute_bow(orbx_matcher *m, orbx_frame *f, const orbx
     ORBX_TRY(m->reserve_staging(8 * (size_t)nc));   // the ids come down through it
     ORBX_TRY(frame_compute_bow(m, f, v, levelsup));
     if ((!word_id && !node_id) || nc == 0) return ORBX_OK;
-    return frame_bow_ids_down(f, f->bow_word, f->bow_node, word_id, node_id);
+    return frame_bow_ids_down(f, f->bow.word, f->bow.node, word_id, node_id);
 }
 
 // Frame::ComputeBoW of a resident fisheye-stereo frame (Frame.cc:738-745 over all N = N_left + N_right rows of mDescriptors): the handle's rows
@@ -2230,10 +2560,7 @@ extern "C" int orbx_frame_compute_bow_fisheye(orbx_matcher *m, orbx_frame *f, co
     ORBX_TRY(m->carve([&](Carve &A) { dids = A.take<int32_t>(2 * (size_t)nc); }));
     ORBX_TRY(frame_compute_bow(m, f, v, levelsup));
     if ((!word_id && !node_id) || nc == 0) return ORBX_OK;
-    const int32_t *src[2] = {f->bow_word, f->bow_node};
-    for (int k = 0; k < 2; k++)
-        hipLaunchKernelGGL(k_frame_rows_to_features, dim3((unsigned)((nc + 255) / 256), 1), dim3(256), 0, m->stream, src[k], 0, dids + (size_t)k * nc, nc,
-                           f->count, f->host_left(), f->host_right(), f->cap, f->roff);
+    launch_bow_ids_to_features(m->stream, f->view(), f->bow, nc, dids);
     ORBX_HIP(hipGetLastError());
     return frame_bow_ids_down(f, dids, dids + nc, word_id, node_id);
 }
@@ -2332,8 +2659,8 @@ static int frame_search_by_bow_impl(orbx_matcher *m, orbx_frame *f, int n_kf, co
         for (int k = 0; k < n_kf; k++) {
             BowProblem &P = probs[k];
             P.mode = fisheye ? 3 : 0; P.nb_left = fisheye ? f->roff : 0;
-            P.fb.node_id = f->fv_node; P.fb.node_ptr = f->fv_ptr; P.fb.index = f->fv_index; P.fb.n_nodes = 0;   // (the frame's node count stays on the device)
-            P.desc_b = f->desc; P.angle_b = f->angle; P.nb = nrows;
+            P.fb.node_id = f->bow.fv_node; P.fb.node_ptr = f->bow.fv_ptr; P.fb.index = f->bow.fv_index; P.fb.n_nodes = 0;   // (the frame's node count stays on the device)
+            P.desc_b = f->desc; P.angle_b = f->bow.angle; P.nb = nrows;
             P.nnratio = nnratio; P.check_orientation = check_orientation ? 1 : 0;
             P.match = dmatch + (size_t)k * nrows; P.nmatches = dnm + k;
             P.hist = dhist + (size_t)k * (ORBX_HISTO_LENGTH + 2); P.counters = P.hist + ORBX_HISTO_LENGTH;
@@ -2347,8 +2674,8 @@ static int frame_search_by_bow_impl(orbx_matcher *m, orbx_frame *f, int n_kf, co
     ORBX_HIP(m->fill(dmatch, 0xff, 4 * (size_t)n_kf * nrows));
     ORBX_HIP(m->fill(dhist, 0, 4 * (size_t)n_kf * (ORBX_HISTO_LENGTH + 2)));
     if (tot_nodes > 0) {
-        hipLaunchKernelGGL(k_bow_pair_nodes, dim3((unsigned)((tot_nodes + 255) / 256)), dim3(256), 0, m->exec(), dkn, (int)tot_nodes, f->fv_node,
-                           f->fv_meta, dpair);
+        hipLaunchKernelGGL(k_bow_pair_nodes, dim3((unsigned)((tot_nodes + 255) / 256)), dim3(256), 0, m->exec(), dkn, (int)tot_nodes, f->bow.fv_node,
+                           f->bow.fv_meta, dpair);
         hipLaunchKernelGGL(k_replay_bow_batch, dim3((unsigned)((max_nodes + 3) / 4), (unsigned)n_kf), dim3(256), 0, m->exec(), (const BowProblem *)dP);
     }
     hipLaunchKernelGGL(k_replay_bow_finish_batch, dim3((unsigned)n_kf), dim3(64), 0, m->exec(), (const BowProblem *)dP);
@@ -2356,12 +2683,11 @@ static int frame_search_by_bow_impl(orbx_matcher *m, orbx_frame *f, int n_kf, co
         hipLaunchKernelGGL(k_frame_rows_to_features, dim3((unsigned)((nc + 255) / 256), (unsigned)n_kf), dim3(256), 0, m->exec(), dmatch, nrows, dout, nc,
                            f->count, f->host_left(), f->host_right(), f->cap, f->roff);
     ORBX_HIP(hipGetLastError());
-    const orbx_frame::Rows rows = {dout, n_kf, nc, match, (size_t)match_stride};
-    ORBX_TRY(f->fetch_rows(&rows));
-    if (n < 0) ORBX_TRY(f->fetch_count());   // N comes back with the results
+    const Rows rows = {dout, n_kf, nc, match, (size_t)match_stride};
+    ORBX_TRY(frame_fetch(f, &rows, 1));
     ORBX_TRY(m->d2h(nmatches, dnm, 4 * (size_t)n_kf));
     ORBX_TRY(m->sync_and_deliver());
-    if (n < 0) { f->adopt_count(); f->take_rows(&rows, 1, f->n); }
+    frame_take(f, &rows, 1);
     return ORBX_OK;
 }
 
@@ -2462,15 +2788,8 @@ extern "C" int orbx_fuse_search(orbx_matcher *m, const orbx_frame_desc *kf, cons
 // ---------------------------------------------------------------------------------------------------------
 // The BoW state of a key frame (orbx_keyframe_compute_bow / orbx_keyframe_bow_from_frame): a SECOND allocation, made when BoW is first attached -- key
 // frames without it keep their size.  Set once, immutable afterwards; guarded as the rows are (an event behind its creation, a done flag).
-struct KeyFrameBow {
-    uint8_t *dev = nullptr;            // one allocation, carved below
-    int32_t *word = nullptr, *node = nullptr;          // per-feature WordId / NodeId
-    float *angle = nullptr;                            // mvKeysUn[i].angle
-    uint32_t *fv_node = nullptr;                       // the FeatureVector as k_frame_featvec writes it: ascending node ids,
-    int32_t *fv_ptr = nullptr, *fv_index = nullptr;    //   the CSR and the indices in std::map / addFeature order (stopped words dropped),
-    int32_t *fv_meta = nullptr;                        //   {node count, features kept}
-    const orbx_vocabulary *voc = nullptr;
-    int levelsup = 0;
+struct KeyFrameBow : BowArrays {
+    uint8_t *dev = nullptr;            // one allocation, the arrays carved from it
     hipEvent_t ready = nullptr;
     std::atomic<bool> done{false};
 };
@@ -2509,6 +2828,7 @@ struct orbx_keyframe {
     int host_left() const { return n_left.load(); }
     int host_right() const { return n_right.load(); }
     int rows_n() const { const int v = n.load(); return v >= 0 ? v : cap; }
+    HandleRows view() const { return HandleRows{desc, kps, count, cap, n.load(), fisheye, roff, n_left.load(), n_right.load()}; }
     // The one place that learns the counts: a constructor with what the host knows, or a call that met the key frame with its counts pending and
     // brought count[0] (, count[1]) home with its results.  Clamped as k_keyframe_copy / k_keyframe_copy_fisheye clamp what they write, so a device
     // count comes through unchanged.
@@ -2989,37 +3309,13 @@ inline void keyframe_bow_release(orbx_keyframe *kf) {   // after the call's sync
 }
 
 // One side of a resident BoW problem: a key frame with BoW, or the frame handle.
-struct BowSide {
-    const uint8_t *desc; const float *angle;
-    const uint32_t *fv_node; const int32_t *fv_ptr, *fv_index, *fv_meta, *count;
-    int n;       // N, or -1 while it is on the device only
-    int cap;     // rows the side's arrays hold
+// its rows (a fisheye-stereo side in ROW space: the flags, the match row, vbMatched2 and the entries go by HandleRows::rows()) and its BoW arrays.
+struct BowSide : BowTarget {
     int bound;   // the host's bound on the FeatureVector's node count
-    // A fisheye-stereo side (roff >= 0) is in ROW space: the right camera's rows from roff on, its counts nl / nr (-1 with n).  A key frame made from a
-    // batch-loaded handle keeps the gap behind its left rows after its counts are adopted: what a call sizes per row (the flags, the match row, vbMatched2,
-    // the entries) goes by the row EXTENT, roff + N_right, not by N.
-    int roff = -1, nl = -1, nr = -1;
-    int feats() const { return n >= 0 ? n : cap; }                                   // features, or their bound
-    int rows() const { return roff < 0 || n < 0 ? feats() : roff + nr; }             // rows the kernels index
-    int flag_n() const { return roff < 0 ? n : rows(); }                             // entries of the side's flags as they go up
+    int flag_n() const { return fisheye ? rows() : n; }                              // entries of the side's flags as they go up
 };
-inline BowSide bow_side(const orbx_keyframe *kf) {
-    const KeyFrameBow *b = kf->bow.load(std::memory_order_acquire);
-    BowSide S;
-    S.desc = kf->desc; S.angle = b->angle; S.fv_node = b->fv_node; S.fv_ptr = b->fv_ptr; S.fv_index = b->fv_index; S.fv_meta = b->fv_meta;
-    S.count = kf->count; S.n = kf->host_n(); S.cap = kf->cap;
-    if (kf->fisheye) { S.roff = kf->roff; S.nl = kf->host_left(); S.nr = kf->host_right(); }
-    S.bound = std::min(S.feats(), b->voc->node_bound(b->levelsup));
-    return S;
-}
-inline BowSide bow_side(const orbx_frame *f) {
-    BowSide S;
-    S.desc = f->desc; S.angle = f->angle; S.fv_node = f->fv_node; S.fv_ptr = f->fv_ptr; S.fv_index = f->fv_index; S.fv_meta = f->fv_meta;
-    S.count = f->count; S.n = f->host_n(); S.cap = f->cap;
-    if (f->fisheye) { S.roff = f->roff; S.nl = f->host_left(); S.nr = f->host_right(); }
-    S.bound = std::min(S.feats(), f->bow_voc->node_bound(f->bow_levelsup));
-    return S;
-}
+inline BowSide bow_side(const HandleRows &r, const BowArrays &b) { return BowSide{bow_target(r, b), std::min(r.feats(), b.voc->node_bound(b.levelsup))}; }
+inline BowSide bow_side(const orbx_keyframe *kf) { return bow_side(kf->view(), *kf->bow.load(std::memory_order_acquire)); }
 
 // The driver of the resident BoW searches of both kinds of side.  Problem k: A[k] against B[k] in `mode` (BowProblem::mode: 0 / 3 rows indexed by B's
 // features, 1 / 2 by A's); flags_a[k] / flags_b[k] (arrays may be NULL, entries may be NULL = no feature is switched off) are `valid` flags when invert, else `skip`
@@ -3158,14 +3454,10 @@ int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const 
     hipLaunchKernelGGL(k_replay_bow_finish_batch, dim3((unsigned)np), dim3(64), 0, m->exec(), (const BowProblem *)dP);
     if (rig) hipLaunchKernelGGL(k_bow_rig_rows, dim3((unsigned)((std::max(nfeat, 1) + 255) / 256), (unsigned)np), dim3(256), 0, m->exec(), (const BowRigRows *)dR);
     ORBX_HIP(hipGetLastError());
-    const int out_n = rig ? nfeat : nrows;   // entries of a row of dout
-    std::vector<int32_t> rows;
-    if (O.n >= 0) {
-        for (int k = 0; k < np; k++) ORBX_TRY(m->d2h(match + (size_t)k * match_stride, dout + (size_t)k * out_n, 4 * (size_t)O.n));
-    } else if (out_n > 0) {   // N comes back with the results
-        rows.resize((size_t)np * out_n);
-        ORBX_TRY(m->d2h(rows.data(), dout, 4 * (size_t)np * out_n));
-    }
+    std::vector<int32_t> land;
+    PendingRows down{m, land, O.n < 0};   // N comes back with the results (the sides' counts, below)
+    const Rows rows = {dout, np, rig ? nfeat : nrows, match, (size_t)match_stride};   // (N known: nfeat = nrows = N)
+    ORBX_TRY(down.fetch(&rows));
     std::vector<int32_t> got(cnt_per * (size_t)np, 0);
     ORBX_TRY(m->d2h(nmatches, dnm, 4 * (size_t)np));
     ORBX_TRY(m->d2h(got.data(), dcnt, 4 * got.size()));
@@ -3178,9 +3470,7 @@ int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const 
         }
     if (O.n < 0) {
         const int32_t *c = counts.data() + (to_b ? 2 : 0);
-        const int n = std::min(std::max(c[0] + c[1], 0), O.feats());
-        for (int k = 0; k < np; k++)
-            if (n > 0) memcpy(match + (size_t)k * match_stride, rows.data() + (size_t)k * out_n, 4 * (size_t)n);
+        down.take(&rows, 1, std::min(std::max(c[0] + c[1], 0), O.feats()));
     }
     return ORBX_OK;
 }
@@ -3194,10 +3484,6 @@ inline bool keyframe_bow_ok(const orbx_matcher *m, bool rig, const orbx_keyframe
     if (*voc && (*voc != b->voc || *levelsup != b->levelsup)) return false;
     *voc = b->voc; *levelsup = b->levelsup;
     return true;
-}
-// the rows a key frame's BoW state may have to index: N, of a rig the row extent (capacity while the counts are pending)
-inline int keyframe_bow_rows(const orbx_keyframe *kf) {
-    return !kf->fisheye || kf->host_n() < 0 ? kf->rows_n() : kf->roff + kf->host_right();
 }
 // what a call learnt of a key frame's pending counts (run_bow_resident's counts of that side)
 inline void keyframe_adopt(orbx_keyframe *kf, const int32_t *c) {
@@ -3216,8 +3502,9 @@ int keyframe_compute_bow(orbx_matcher *m, bool rig, orbx_keyframe *kf, const orb
         if (b->voc != v || b->levelsup != levelsup) return ORBX_E_BAD_ARG;
         if (!down) return ORBX_OK;
     }
-    const int n_host = kf->host_n(), nc = kf->rows_n();   // nc: features the kernels may see
-    if (keyframe_bow_rows(kf) > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;
+    const HandleRows rows = kf->view();
+    const int n_host = rows.n, nc = rows.feats();   // nc: features the kernels may see
+    if (rows.rows() > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;   // (the rows the BoW state may have to index)
     ORBX_HIP(hipSetDevice(m->device));
     int32_t *dids = nullptr;   // rig: word ids, then node ids, in features [0, N)
     ORBX_TRY(m->carve([&](Carve &A) { dids = A.take<int32_t>(2 * (size_t)nc); }));   // (monocular: the room the ids take in the staging)
@@ -3228,8 +3515,7 @@ int keyframe_compute_bow(orbx_matcher *m, bool rig, orbx_keyframe *kf, const orb
         if (!kf->done.load(std::memory_order_acquire)) e = hipStreamWaitEvent(m->stream, kf->ready, 0);
         if (e == hipSuccess) {
             m->dirty = true;
-            e = launch_compute_bow(m, v, levelsup, BowTarget{kf->desc, kf->kps, kf->count, n_host, kf->cap, b->word, b->node, b->angle, b->fv_node, b->fv_ptr,
-                                                             b->fv_index, b->fv_meta, rig, kf->roff, {kf->host_left(), kf->host_right()}});
+            e = launch_compute_bow(m, v, levelsup, bow_target(rows, *b));
         }
         if (e == hipSuccess) e = hipEventRecord(b->ready, m->stream);
         if (e != hipSuccess) { set_error(hipGetErrorString(e)); (void)hipStreamSynchronize(m->stream); m->dirty = false; keyframe_bow_free(b); return ORBX_E_HIP; }
@@ -3240,31 +3526,21 @@ int keyframe_compute_bow(orbx_matcher *m, bool rig, orbx_keyframe *kf, const orb
     if (!down || nc == 0) return ORBX_OK;
     const int32_t *src_w = b->word, *src_n = b->node;
     if (rig) {
-        const int32_t *src[2] = {b->word, b->node};
-        for (int k = 0; k < 2; k++)
-            hipLaunchKernelGGL(k_frame_rows_to_features, dim3((unsigned)((nc + 255) / 256), 1), dim3(256), 0, m->exec(), src[k], 0, dids + (size_t)k * nc, nc,
-                               kf->count, kf->host_left(), kf->host_right(), kf->cap, kf->roff);
+        launch_bow_ids_to_features(m->exec(), rows, *b, nc, dids);
         ORBX_HIP(hipGetLastError());
         src_w = dids; src_n = dids + nc;
     }
-    std::vector<int32_t> h;
+    std::vector<int32_t> land;
+    PendingRows got{m, land, n_host < 0};
+    const Rows ids[2] = {{src_w, 1, nc, word_id, 0}, {src_n, 1, nc, node_id, 0}};
     int32_t cnt[2] = {n_host, 0};
-    if (n_host >= 0) {
-        if (word_id) ORBX_TRY(m->d2h(word_id, src_w, 4 * (size_t)nc));
-        if (node_id) ORBX_TRY(m->d2h(node_id, src_n, 4 * (size_t)nc));
-    } else {   // N comes back with the ids
-        h.resize(2 * (size_t)nc);
-        ORBX_TRY(m->d2h(h.data(), src_w, 4 * (size_t)nc));
-        ORBX_TRY(m->d2h(h.data() + nc, src_n, 4 * (size_t)nc));
-        ORBX_TRY(m->d2h(cnt, kf->count, rig ? 8 : 4));
-    }
+    ORBX_TRY(got.fetch(ids, 2));
+    if (n_host < 0) ORBX_TRY(m->d2h(cnt, kf->count, rig ? 8 : 4));   // N comes back with the ids
     ORBX_TRY(m->sync_and_deliver());
     keyframe_bow_release(kf);
     if (n_host < 0) {
         kf->adopt(cnt[0], cnt[1]);
-        const int n = kf->host_n();
-        if (word_id) memcpy(word_id, h.data(), 4 * (size_t)n);
-        if (node_id) memcpy(node_id, h.data() + nc, 4 * (size_t)n);
+        got.take(ids, 2, kf->host_n());
     }
     return ORBX_OK;
 }
@@ -3276,19 +3552,19 @@ int keyframe_bow_from_frame(orbx_matcher *m, bool rig, orbx_keyframe *kf, orbx_f
     if (kf->bow.load(std::memory_order_acquire)) return ORBX_E_BAD_ARG;   // set once
     if (f->load_seq != kf->src_seq) return ORBX_E_STALE;                  // the handle holds another frame by now
     if (!f->bow_valid) return ORBX_E_BAD_ARG;
-    if ((rig ? keyframe_bow_rows(kf) : f->rows_n()) > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;
+    if ((rig ? kf->view().rows() : f->rows_n()) > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;
     ORBX_HIP(hipSetDevice(m->device));
     KeyFrameBow *b = nullptr;
     int r = keyframe_bow_alloc(kf->cap, &b);
     if (r != ORBX_OK) return r;
-    b->voc = f->bow_voc; b->levelsup = f->bow_levelsup;
+    const BowArrays &S = f->bow, &D = *b;
+    b->voc = S.voc; b->levelsup = S.levelsup;
     KeyFrameBowCopyFisheye Cf;
     memset(&Cf, 0, sizeof(Cf));
     KeyFrameBowCopy &Cp = Cf.c;
     Cp.src_count = f->count; Cp.n_host = f->host_n(); Cp.cap = kf->cap;
-    Cp.src_word = f->bow_word; Cp.src_node = f->bow_node; Cp.src_ptr = f->fv_ptr; Cp.src_index = f->fv_index; Cp.src_meta = f->fv_meta;
-    Cp.src_fv_node = f->fv_node; Cp.src_angle = f->angle;
-    Cp.word = b->word; Cp.node = b->node; Cp.ptr = b->fv_ptr; Cp.index = b->fv_index; Cp.meta = b->fv_meta; Cp.fv_node = b->fv_node; Cp.angle = b->angle;
+    Cp.src_word = S.word; Cp.src_node = S.node; Cp.src_ptr = S.fv_ptr; Cp.src_index = S.fv_index; Cp.src_meta = S.fv_meta; Cp.src_fv_node = S.fv_node; Cp.src_angle = S.angle;
+    Cp.word = D.word; Cp.node = D.node; Cp.ptr = D.fv_ptr; Cp.index = D.fv_index; Cp.meta = D.fv_meta; Cp.fv_node = D.fv_node; Cp.angle = D.angle;
     m->dirty = true;
     if (rig) {
         Cf.nl_host = f->host_left(); Cf.nr_host = f->host_right(); Cf.src_roff = f->roff; Cf.src_cap = f->cap; Cf.roff = kf->roff;
@@ -3340,8 +3616,8 @@ int frame_search_by_bow_resident(orbx_matcher *m, bool rig, orbx_frame *f, int n
     if (n_kf > ORBX_MAX_BOW_KEYFRAMES) return ORBX_E_TOO_LARGE;
     if (n_kf == 0) return ORBX_OK;
     if (!kfs || !match || !nmatches || match_stride < 0) return ORBX_E_BAD_ARG;
-    const orbx_vocabulary *voc = f->bow_voc;
-    int levelsup = f->bow_levelsup;
+    const orbx_vocabulary *voc = f->bow.voc;
+    int levelsup = f->bow.levelsup;
     for (int k = 0; k < n_kf; k++)   // every key frame is checked before anything is enqueued
         if (!keyframe_bow_ok(m, rig, kfs[k], &voc, &levelsup)) return ORBX_E_BAD_ARG;
     int n = f->host_n();
@@ -3354,7 +3630,7 @@ int frame_search_by_bow_resident(orbx_matcher *m, bool rig, orbx_frame *f, int n
     }
     if (n == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
-    std::vector<BowSide> A((size_t)n_kf), B((size_t)n_kf, bow_side(f));
+    std::vector<BowSide> A((size_t)n_kf), B((size_t)n_kf, bow_side(f->view(), f->bow));
     for (int k = 0; k < n_kf; k++) A[k] = bow_side(kfs[k]);
     for (int k = 0; k < n_kf; k++) { const int rc = keyframe_bow_acquire(m, kfs[k]); if (rc != ORBX_OK) return rc; }
     std::vector<int32_t> counts;
@@ -3609,294 +3885,4 @@ extern "C" int orbx_keyframe_fuse_map_points_sim3(orbx_matcher *m, int n_kf, orb
                                                   const uint8_t *skip, int32_t *best_idx, int32_t *best_dist, uint8_t *projected) {
     return keyframe_fuse_map_points_impl(m, false, true, n_kf, kfs, cams, poses, nullptr, th, log_scale_factor, 0, n_mp, pos, normal, min_dist, max_dist,
                                          mp_desc, skip, best_idx, best_dist, projected);
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Tracking::SearchLocalPoints on a resident frame (Tracking.cc:3339-3413): Frame::isInFrustum (Frame.cc:512-575) of every local map point, the
-// window setup and SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) (ORBmatcher.cc:43-213, Nleft == -1) in one call: the projection
-// records stay in the call's arena, one transfer up, one down, one synchronisation.
-// ---------------------------------------------------------------------------------------------------------
-extern "C" int orbx_frame_search_local_points(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_camera *cam,
-                                              const orbx_frame_pose *pose, float log_scale_factor, float viewing_cos_limit, int n_mp, const float *pos,
-                                              const float *normal, const float *min_dist, const float *max_dist, const uint8_t *mp_desc,
-                                              const uint8_t *eligible, const uint8_t *has_obs, float th, float nnratio, int far_points,
-                                              float th_far_points, uint8_t *in_view, int32_t *frame_match) {
-    if (!m || !f || f->owner != m || f->fisheye || !cam || !pose || n_mp < 0 || !frame_match) return ORBX_E_BAD_ARG;
-    if (n_mp > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !in_view)) return ORBX_E_BAD_ARG;
-    int n = -1;
-    if (f->n_known || frame_occupied || n_mp == 0) { const int rc = frame_count(f, &n); if (rc != ORBX_OK) return rc; }   // the mask holds N entries
-    for (int i = 0; i < n; i++) frame_match[i] = -1;
-    if (n_mp == 0) return 0;
-    const int nc = f->rows_n();
-    if (nc > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;
-    ORBX_HIP(hipSetDevice(m->device));
-    const size_t q = (size_t)n_mp;
-    const FrustumFrame FF = frustum_frame(cam, pose, f->bounds, log_scale_factor, f->nlevels, viewing_cos_limit);
-    const int32_t cnts[2] = {n, n_mp};
-    WindowProblem P;
-    memset(&P, 0, sizeof(P));
-    ResolveProblem R;
-    memset(&R, 0, sizeof(R));
-    float *dp, *dn, *dmn, *dmx, *dx, *dy, *dxr, *dd, *dvc, *dqr;
-    uint8_t *ddesc, *delig, *div, *dvalid, *div_out;
-    int32_t *dcnt, *dl, *dqmin, *dqmax;
-    FrustumFrame *dF;
-    WindowProblem *dP;
-    ResolveProblem *dR;
-    ORBX_TRY(m->carve([&](Carve &A) {
-        // inputs (one run of the arena)
-        dp = A.up(pos, 3 * q); dn = A.up(normal, 3 * q); dmn = A.up(min_dist, q); dmx = A.up(max_dist, q);
-        ddesc = A.up(mp_desc, 32 * q);
-        delig = A.up_opt(eligible, q);
-        R.q_has_obs = A.up_opt(has_obs, q);
-        if (n > 0) P.occupied0 = A.up_opt(frame_occupied, (size_t)n);
-        dF = A.up(&FF, 1);
-        dcnt = A.up(cnts, 2, 2);
-        dP = A.take<WindowProblem>(1);
-        dR = A.take<ResolveProblem>(1);
-        // the projection records and the windows: device only
-        div = A.take<uint8_t>(q);
-        dx = A.take<float>(q); dy = A.take<float>(q); dxr = A.take<float>(q); dd = A.take<float>(q); dvc = A.take<float>(q);
-        dl = A.take<int32_t>(q);
-        dqr = A.take<float>(q);
-        dqmin = A.take<int32_t>(q); dqmax = A.take<int32_t>(q);
-        dvalid = A.take<uint8_t>(q);
-        P.keys = A.take<u64>(q * kTopK); P.meta = A.take<int32_t>(q);
-        R.entries = A.take<int32_t>(q);
-        // the downloads side by side: mbTrackInView, the matches, nmatches
-        div_out = A.take<uint8_t>(q);
-        R.match = A.take<int32_t>(nc);
-        R.nmatches = A.take<int32_t>(1);
-    }));
-    P.kps = f->kps; P.desc = f->desc; P.n_ptr = f->count; P.nq_ptr = dcnt + 1;
-    if (f->has_ur) { P.u_right = f->u_right; P.qxr = dxr; }   // mTrackProjXR against mvuRight (ORBmatcher.cc:92-97)
-    P.qx = dx; P.qy = dy; P.qr = dqr; P.qmin = dqmin; P.qmax = dqmax; P.qdesc = ddesc; P.qvalid = dvalid;
-    P.gstart = f->gstart; P.gorder = f->gorder;
-    R.mode = 1; R.nnratio = nnratio; R.max_dist = (float)ORBX_TH_HIGH; R.cleared_value = -2;
-    ORBX_TRY(m->h2d(dP, &P, sizeof(P))); ORBX_TRY(m->h2d(dR, &R, sizeof(R)));
-    hipLaunchKernelGGL(k_in_frustum, dim3((n_mp + 255) / 256, 1), dim3(256), 0, m->exec(), (const FrustumFrame *)dF, n_mp, (const float *)dp,
-                       (const float *)dn, (const float *)dmn, (const float *)dmx, div, dx, dy, dxr, dd, dl, dvc);
-    hipLaunchKernelGGL(k_local_windows, dim3((n_mp + 255) / 256), dim3(256), 0, m->exec(), n_mp, (const uint8_t *)div, (const uint8_t *)delig,
-                       (const int32_t *)dl, (const float *)dvc, (const float *)dd, (const float *)f->scale, f->nlevels, th, far_points ? 1 : 0,
-                       th_far_points, dqr, dqmin, dqmax, dvalid, div_out);
-    const bool match = n != 0;   // (an empty frame: isInFrustum only)
-    if (match) {
-        const GridParams g = grid_of(f->bounds);
-        ORBX_LAUNCH_WINDOW_BEST2(n_mp, 1, m->exec(), dP, g);
-        const int rr = launch_resolve<false>(1, m->exec(), dP, dR, g, nc, n_mp, 4);
-        if (rr != ORBX_OK) return rr;
-    }
-    ORBX_HIP(hipGetLastError());
-    int32_t nm = 0;
-    ORBX_TRY(m->d2h(in_view, div_out, q));
-    const orbx_frame::Rows rows = {R.match, 1, nc, frame_match, 0};
-    if (match) {
-        ORBX_TRY(f->fetch_rows(&rows));
-        if (n < 0) ORBX_TRY(f->fetch_count());   // N comes back with the results
-        ORBX_TRY(m->d2h(&nm, R.nmatches, 4));
-    }
-    ORBX_TRY(m->sync_and_deliver());
-    if (n < 0) { f->adopt_count(); f->take_rows(&rows, 1, f->n); }
-    return nm;
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// Fisheye-stereo frames on the handle (Frame::Nleft != -1: KannalaBrandt8 rigs).  Features [0, N_left) are the left camera's, [N_left, N) the right
-// camera's; the occupancy masks and match arrays of every entry point use that numbering.
-// ---------------------------------------------------------------------------------------------------------
-extern "C" int orbx_frame_load_host_fisheye(orbx_frame *f, const orbx_frame_desc *left, const orbx_keypoint *kps_right, int n_right, const int32_t *l2r,
-                                            const int32_t *r2l) {
-    if (!f || !left || left->n < 0 || n_right < 0 || (left->n > 0 && (!left->keypoints_un || !l2r)) || (n_right > 0 && (!kps_right || !r2l)) ||
-        (left->n + n_right > 0 && !left->descriptors) || !left->scale_factors || left->nlevels < 1 || left->nlevels > kFrameMaxLevels)
-        return ORBX_E_BAD_ARG;
-    const int nl = left->n, nr = n_right, N = nl + nr;
-    // the partners index device memory: checked before anything is enqueued
-    for (int i = 0; i < nl; i++) if (l2r[i] < -1 || l2r[i] >= nr) return ORBX_E_BAD_ARG;
-    for (int j = 0; j < nr; j++) if (r2l[j] < -1 || r2l[j] >= nl) return ORBX_E_BAD_ARG;
-    if (N > f->cap) return ORBX_E_TOO_LARGE;
-    orbx_matcher *m = f->owner;
-    ORBX_HIP(hipSetDevice(m->device));
-    if (f->stage_busy) { ORBX_HIP(hipEventSynchronize(f->ev_done)); f->stage_busy = false; }   // the previous load still reads the staging
-    m->begin();
-    // rows in place: left at 0, right at roff = N_left, so the descriptors of all N features are one run
-    const size_t b_kl = 28 * (size_t)nl, b_kr = 28 * (size_t)nr, b_desc = 32 * (size_t)N, b_l2r = 4 * (size_t)nl, b_r2l = 4 * (size_t)nr;
-    memcpy(f->stage + f->off_kps, left->keypoints_un, b_kl);
-    memcpy(f->stage + f->off_kps + b_kl, kps_right, b_kr);
-    memcpy(f->stage + f->off_desc, left->descriptors, b_desc);
-    memcpy(f->stage + f->off_l2r, l2r, b_l2r);
-    memcpy(f->stage + f->off_r2l, r2l, b_r2l);
-    const orbx_matcher::Span rows[4] = {{f->off_kps, b_kl + b_kr}, {f->off_desc, b_desc}, {f->off_l2r, b_l2r}, {f->off_r2l, b_r2l}};
-    ORBX_TRY(m->upload_ranges(f->dev, f->stage, rows, 4));
-    const float b[4] = {left->min_x, left->max_x, left->min_y, left->max_y};
-    FisheyePrepare P;
-    frame_prepare_common(f, P, nl, left->scale_factors, left->nlevels, b);
-    P.n_host[0] = nl; P.n_host[1] = nr; P.cap_side[0] = nl; P.cap_side[1] = nr;
-    P.l2r = f->l2r; P.r2l = f->r2l;
-    hipLaunchKernelGGL(k_frame_prepare_fisheye, dim3(2), dim3(64), 0, m->stream, P, grid_of(f->bounds));
-    ORBX_HIP(hipGetLastError());
-    ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
-    f->stage_busy = true;
-    f->fisheye = true; f->roff = nl; f->n_left = nl; f->n_right = nr; f->n = N; f->n_known = true;
-    f->has_ur = false; f->loaded = true; f->bow_valid = false; f->load_seq++;
-    return ORBX_OK;
-}
-
-extern "C" int orbx_frame_load_stereo_fisheye_batch(orbx_frame *f, orbx_extractor *L, orbx_extractor *R, int frame, const float *bounds4,
-                                                    const float *scale_factors, int nlevels) {
-    if (!f || !L || !R) return ORBX_E_BAD_ARG;
-    orbx_matcher *m = f->owner;
-    // the stage's results must be those of the extractors' current batches
-    if (L->sf_batch <= 0 || !L->ev_sf || L->sf_right != R || L->sf_seq_l != L->batch_seq || L->sf_seq_r != R->batch_seq) return ORBX_E_BAD_ARG;
-    if (frame < 0 || frame >= L->sf_batch || frame >= L->last_batch || L->device != m->device || R->device != m->device) return ORBX_E_BAD_ARG;
-    const int capL = L->sf_capL, capR = L->sf_capR;
-    if (capL != L->cap || capR != R->cap || (size_t)capL + (size_t)capR > (size_t)f->cap) return ORBX_E_BAD_ARG;
-    const float *sf = scale_factors ? scale_factors : L->scale.data();
-    const int nl = scale_factors ? nlevels : L->prm.nlevels;
-    if (nl < 1 || nl > kFrameMaxLevels || (!bounds4 && L->width <= 0)) return ORBX_E_BAD_ARG;
-    const float *b = bounds4 ? bounds4 : L->bounds;
-    ORBX_HIP(hipSetDevice(m->device));
-    FisheyePrepare P;
-    frame_prepare_common(f, P, capL, sf, nl, b);
-    const size_t fr = (size_t)frame;
-    P.src_kps[0] = (const orbx_keypoint *)L->d_kps.p + fr * capL;   // mvKeys: the raw keypoints k_tri_kb8_stereo read
-    P.src_kps[1] = (const orbx_keypoint *)R->d_kps.p + fr * capR;
-    P.src_desc[0] = (const uint8_t *)L->d_desc.p + fr * capL * 32;
-    P.src_desc[1] = (const uint8_t *)R->d_desc.p + fr * capR * 32;
-    P.src_count[0] = (const int32_t *)L->d_count.p + fr;
-    P.src_count[1] = (const int32_t *)R->d_count.p + fr;
-    P.src_l2r = (const int32_t *)L->d_sf_l2r.p + fr * capL;
-    P.src_r2l = (const int32_t *)L->d_sf_r2l.p + fr * capR;
-    P.cap_side[0] = capL; P.cap_side[1] = capR;
-    P.l2r = f->l2r; P.r2l = f->r2l;
-    // the owner's stream waits for the stage (which waited for both extractions); both extractors' next batches and the left extractor's next
-    // stage wait for the copy: no host synchronisation
-    ORBX_HIP(hipStreamWaitEvent(m->stream, L->ev_sf, 0));
-    hipLaunchKernelGGL(k_frame_prepare_fisheye, dim3(2 + (unsigned)((std::max(capL, capR) + 255) / 256)), dim3(64), 0, m->stream, P, grid_of(f->bounds));
-    ORBX_HIP(hipGetLastError());
-    ORBX_HIP(hipEventRecord(f->ev_done, m->stream));
-    ORBX_HIP(hipStreamWaitEvent(L->stream, f->ev_done, 0));
-    ORBX_HIP(hipStreamWaitEvent(R->stream, f->ev_done, 0));
-    if (L->match_stream) ORBX_HIP(hipStreamWaitEvent(L->match_stream, f->ev_done, 0));
-    f->fisheye = true; f->roff = capL; f->n_known = false; f->has_ur = false; f->loaded = true; f->bow_valid = false; f->load_seq++;
-    return ORBX_OK;
-}
-
-extern "C" int orbx_frame_counts(orbx_frame *f, int *n_left, int *n_right) {
-    if (!f) return ORBX_E_BAD_ARG;
-    int n = 0;
-    const int rc = frame_count(f, &n);
-    if (rc != ORBX_OK) return rc;
-    if (n_left) *n_left = f->fisheye ? f->n_left : n;
-    if (n_right) *n_right = f->fisheye ? f->n_right : -1;
-    return ORBX_OK;
-}
-
-extern "C" int orbx_frame_search_by_projection_mappoints_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, int n_mp,
-                                                                 const uint8_t *in_view, const float *proj_x, const float *proj_y, const int32_t *pred_level,
-                                                                 const float *view_cos, const uint8_t *in_view_r, const float *proj_xr, const float *proj_yr,
-                                                                 const int32_t *pred_level_r, const float *view_cos_r, const uint8_t *mp_desc,
-                                                                 const uint8_t *mp_has_obs, float th, float nnratio, int32_t *frame_match) {
-    if (!m || !f || f->owner != m || !f->fisheye || !frame_match) return ORBX_E_BAD_ARG;
-    const orbx_frame_desc d = frame_desc_of(f);
-    return search_mappoints_fisheye_impl(m, &d, f, nullptr, 0, nullptr, nullptr, frame_occupied, n_mp, in_view, proj_x, proj_y, pred_level, view_cos,
-                                         in_view_r, proj_xr, proj_yr, pred_level_r, view_cos_r, mp_desc, mp_has_obs, th, nnratio, frame_match);
-}
-
-extern "C" int orbx_frame_search_by_projection_frame_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *cur_occupied, int n_q, const float *q_u,
-                                                             const float *q_v, const float *q_ur, const float *q_vr, const int32_t *q_octave,
-                                                             const float *q_angle, const uint8_t *q_desc, const uint8_t *q_has_obs, float th, int level_mode,
-                                                             int check_orientation, int32_t *cur_match) {
-    if (!m || !f || f->owner != m || !f->fisheye || !cur_match) return ORBX_E_BAD_ARG;
-    const orbx_frame_desc d = frame_desc_of(f);
-    return search_frame_fisheye_impl(m, &d, f, nullptr, 0, cur_occupied, n_q, q_u, q_v, q_ur, q_vr, q_octave, q_angle, q_desc, q_has_obs, th, level_mode,
-                                     check_orientation, cur_match);
-}
-
-// Tracking::SearchLocalPoints on a resident fisheye-stereo frame: isInFrustumChecks of both cameras (k_in_frustum_checks), the windows
-// (k_local_windows_fisheye), the twin window search and the replay (k_replay_twin) -- the projection records never leave the device.
-extern "C" int orbx_frame_search_local_points_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_fisheye_view *views,
-                                                      float log_scale_factor, float viewing_cos_limit, int n_mp, const float *pos, const float *normal,
-                                                      const float *min_dist, const float *max_dist, const uint8_t *mp_desc, const uint8_t *eligible,
-                                                      const uint8_t *has_obs, const float *track_depth, float th, float nnratio, int far_points,
-                                                      float th_far_points, uint8_t *in_view, int32_t *frame_match) {
-    if (!m || !f || f->owner != m || !f->fisheye || !views || n_mp < 0 || !frame_match) return ORBX_E_BAD_ARG;
-    if (n_mp > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !in_view)) return ORBX_E_BAD_ARG;
-    int N = -1;
-    if (f->n_known || frame_occupied || n_mp == 0) { const int rc = frame_count(f, &N); if (rc != ORBX_OK) return rc; }   // the mask holds N entries
-    for (int i = 0; i < N; i++) frame_match[i] = -1;
-    if (n_mp == 0) return 0;
-    const int nc = f->rows_n();
-    ORBX_HIP(hipSetDevice(m->device));
-    const size_t q = (size_t)n_mp, q2 = 2 * q;
-    FrustumChecks FC;
-    memset(&FC, 0, sizeof(FC));
-    memcpy(FC.view, views, sizeof(FisheyeView) * 2);
-    FC.minx = f->bounds[0]; FC.maxx = f->bounds[1]; FC.miny = f->bounds[2]; FC.maxy = f->bounds[3];
-    FC.log_scale_factor = log_scale_factor; FC.nlevels = f->nlevels; FC.cos_limit = viewing_cos_limit;
-    const int32_t cnts[4] = {n_mp, 0, 0, 0};
-    WindowProblem P[2];
-    memset(P, 0, sizeof(P));
-    TwinProblem T;
-    memset(&T, 0, sizeof(T));
-    float *dp, *dn, *dmn, *dmx, *dtd, *dx, *dy, *dd, *dvc, *dqr;
-    uint8_t *ddesc, *delig, *div, *dvalid, *div_out;
-    int32_t *dcnt, *dl, *dqmin, *dqmax;
-    FrustumChecks *dF;
-    WindowProblem *dP;
-    ORBX_TRY(m->carve([&](Carve &A) {
-        // inputs (one run of the arena)
-        dp = A.up(pos, 3 * q); dn = A.up(normal, 3 * q); dmn = A.up(min_dist, q); dmx = A.up(max_dist, q);
-        ddesc = A.up(mp_desc, 32 * q);
-        delig = A.up_opt(eligible, q);
-        T.q_has_obs = A.up_opt(has_obs, q);
-        dtd = A.up_opt(track_depth, q);
-        if (N > 0) T.occupied0 = A.up_opt(frame_occupied, (size_t)N);
-        dF = A.up(&FC, 1);
-        dcnt = A.up(cnts, 4);
-        dP = A.take<WindowProblem>(2);
-        // the projection records and the windows: device only, [2][n_mp] (left, right)
-        div = A.take<uint8_t>(q2);
-        dx = A.take<float>(q2); dy = A.take<float>(q2); dd = A.take<float>(q2); dvc = A.take<float>(q2);
-        dl = A.take<int32_t>(q2);
-        dqr = A.take<float>(q2);
-        dqmin = A.take<int32_t>(q2); dqmax = A.take<int32_t>(q2);
-        dvalid = A.take<uint8_t>(q2);
-        for (int s = 0; s < 2; s++) { P[s].keys = A.take<u64>(q * kTopK); P[s].meta = A.take<int32_t>(q); }
-        T.entries = A.take<int32_t>(q2);
-        // the downloads side by side: mbTrackInView / mbTrackInViewR, the matches, nmatches
-        div_out = A.take<uint8_t>(q2);
-        T.match = A.take<int32_t>(nc);
-        T.nmatches = A.take<int32_t>(1);
-    }));
-    P[0].kps = f->kps; P[0].desc = f->desc; P[0].n_ptr = f->count; P[0].gstart = f->gstart; P[0].gorder = f->gorder;
-    P[1].kps = f->kps + f->roff; P[1].desc = f->desc + (size_t)f->roff * 32; P[1].n_ptr = f->count + 1; P[1].gstart = f->gstart_r; P[1].gorder = f->gorder_r;
-    for (int s = 0; s < 2; s++) {
-        const size_t o = (size_t)s * q;
-        P[s].nq_ptr = dcnt;
-        P[s].qx = dx + o; P[s].qy = dy + o; P[s].qr = dqr + o; P[s].qmin = dqmin + o; P[s].qmax = dqmax + o; P[s].qvalid = dvalid + o; P[s].qdesc = ddesc;
-    }
-    T.mode = 1; T.nq = n_mp; T.nnratio = nnratio; T.max_dist = (float)ORBX_TH_HIGH; T.cleared_value = -2;
-    T.l2r = f->l2r; T.r2l = f->r2l;
-    ORBX_TRY(m->h2d(dP, P, sizeof(P)));
-    hipLaunchKernelGGL(k_in_frustum_checks, dim3((n_mp + 255) / 256, 2), dim3(256), 0, m->exec(), (const FrustumChecks *)dF, n_mp, (const float *)dp,
-                       (const float *)dn, (const float *)dmn, (const float *)dmx, div, dx, dy, dd, dl, dvc);
-    hipLaunchKernelGGL(k_local_windows_fisheye, dim3((n_mp + 255) / 256), dim3(256), 0, m->exec(), n_mp, (const uint8_t *)div, (const uint8_t *)delig,
-                       (const int32_t *)dl, (const float *)dvc, (const float *)dd, (const float *)dtd, (const float *)f->scale, f->nlevels, th,
-                       far_points ? 1 : 0, th_far_points, dqr, dqmin, dqmax, dvalid, div_out);
-    const bool match = N != 0;   // (an empty frame: isInFrustumChecks only)
-    if (match) {
-        ORBX_TRY(launch_twin(m, dP, T, grid_of(f->bounds), nc, n_mp));
-    }
-    ORBX_HIP(hipGetLastError());
-    int32_t nm = 0;
-    ORBX_TRY(m->d2h(in_view, div_out, q2));
-    const orbx_frame::Rows rows = {T.match, 1, nc, frame_match, 0};
-    if (match) {
-        ORBX_TRY(f->fetch_rows(&rows));
-        if (N < 0) ORBX_TRY(f->fetch_count());   // the counts come back with the results
-        ORBX_TRY(m->d2h(&nm, T.nmatches, 4));
-    }
-    ORBX_TRY(m->sync_and_deliver());
-    if (N < 0) { f->adopt_count(); f->take_rows(&rows, 1, f->n); }
-    return nm;
 }
