@@ -947,7 +947,8 @@ int orbx_keyframe_search_by_bow_fisheye(orbx_matcher *m, orbx_keyframe *kf1, con
 int orbx_keyframe_search_for_triangulation_fisheye(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
                                                    int check_orientation, const orbx_keyframe_kb8_gate *gate, int32_t *matches12);
 
-/* ---- LoopClosing's Sim3 projection searches on resident key frames (monocular / rectified key frames, Pinhole; a fisheye key frame is refused) ----
+/* ---- LoopClosing's Sim3 projection searches on resident key frames (monocular / rectified key frames, Pinhole; a fisheye key frame is refused by
+ * this pair and served by the _fisheye pair below it) ----
  * The three matcher calls LoopClosing makes with a Sim3 share their projection gates (ORBmatcher.cc:452-487, :569-604, :1369-1399); the two calls below
  * evaluate them on the device for n_kf key frames and ONE shared set of n_mp map points, and feed the search kernels from them: no key frame is uploaded,
  * the map points go up once, the query records never visit the host.  poses[k] = Tcw = SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale())
@@ -995,6 +996,34 @@ int orbx_keyframe_fuse_map_points_sim3(orbx_matcher *m, int n_kf, orbx_keyframe 
                                        float th, float log_scale_factor, int n_mp, const float *pos, const float *normal, const float *min_dist,
                                        const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
                                        uint8_t *projected);
+/* The same two calls for FISHEYE-STEREO key frames (KeyFrame::NLeft != -1, KannalaBrandt8; a monocular key frame is refused).  The three members never
+ * look at the right camera: GetFeaturesInArea(u, v, radius) with bRight = false, mvKeysUn[idx].octave, pKF->mpCamera -- so a key frame is ONE problem,
+ * its left rows, left grid and N_left, and views holds n_kf entries (one per key frame, not two as orbx_keyframe_fuse_map_points_fisheye takes):
+ * R, t = SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()), twc = Tcw.inverse().translation(), params = the LEFT camera's eight parameters.
+ * The gates are the ones above, in that order and rounding; the projection is
+ *   ORBX_SIM3_PROJECT_CAMERA: pKF->mpCamera->project(p3Dc) = KannalaBrandt8::project, the restatement orbx_is_in_frustum_checks uses (same bit contract,
+ *     same one-ulp caveat), evaluated for pairs that are not skipped and lie in front of the camera;
+ *   ORBX_SIM3_PROJECT_INVZ: the pinhole form as written at ORBmatcher.cc:573-578 with fx, fy, cx, cy = params[0..3] -- the reference writes it whatever
+ *     the camera model is, with pKF->fx, fy, cx, cy: the caller puts those there (params[4..7] are not read).
+ * orbx_keyframe_search_by_projection_sim3_fisheye: semantics, arguments and limits as orbx_keyframe_search_by_projection_sim3, except that match[k] and
+ * occupied[k] hold N_k = N_left + N_right entries (orbx_keyframe_counts), the shape of vpMatched on a rig: occupied[k] is read for [0, N_left) only and
+ * match[k][i] is always -1 for i >= N_left.  N_left <= ORBX_MAX_FRAME_FEATURES; bit-equal image bounds within one call; counts still on the device
+ * cost that one download (orbx_keyframe_counts' path).
+ * orbx_keyframe_fuse_map_points_sim3_fisheye: as orbx_keyframe_fuse_map_points_sim3; outputs [n_kf][n_mp], best_idx always below N_left (no N_left offset
+ * is ever added).  Different bounds in one call and key frames without inv_level_sigma2 are accepted; counts still on the device come home with the
+ * results and are known afterwards.  Four launches whatever n_kf is.
+ * Refusals (ORBX_E_BAD_ARG / ORBX_E_TOO_LARGE before anything is enqueued): a monocular key frame, a key frame of another device, NULL rows,
+ * projection_form not 0 / 1, proj_u without proj_v, unequal bounds in the search form, too many key frames or features.  n_kf = 0 or n_mp = 0: ORBX_OK,
+ * match rows -1, nmatches 0. */
+int orbx_keyframe_search_by_projection_sim3_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views, float th,
+                                                    float ratio_hamming, float log_scale_factor, int projection_form, int n_mp, const float *pos,
+                                                    const float *normal, const float *min_dist, const float *max_dist, const uint8_t *mp_desc,
+                                                    const uint8_t *skip, const uint8_t *const *occupied, int32_t *const *match, int32_t *nmatches,
+                                                    uint8_t *projected, float *proj_u, float *proj_v);
+int orbx_keyframe_fuse_map_points_sim3_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views, float th,
+                                               float log_scale_factor, int n_mp, const float *pos, const float *normal, const float *min_dist,
+                                               const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
+                                               uint8_t *projected);
 
 /* Frame::ComputeStereoMatches (Frame.cc:811-981) for every frame of two resident batches: `left` and `right` must have
  * extracted batches of the same size and image shape (rectified stereo, lapping {0,0}).  Row-band Hamming match, 11x11

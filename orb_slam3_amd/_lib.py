@@ -177,6 +177,7 @@ SYMBOLS = [
     "orbx_keyframe_compute_bow_fisheye", "orbx_keyframe_bow_from_frame_fisheye", "orbx_frame_search_by_bow_resident_fisheye",
     "orbx_keyframe_search_by_bow_fisheye", "orbx_keyframe_search_for_triangulation_fisheye",
     "orbx_keyframe_search_by_projection_sim3", "orbx_keyframe_fuse_map_points_sim3",
+    "orbx_keyframe_search_by_projection_sim3_fisheye", "orbx_keyframe_fuse_map_points_sim3_fisheye",
 ]
 
 
@@ -312,6 +313,9 @@ def lib() -> C.CDLL:
                                                           vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp]
     L.orbx_keyframe_fuse_map_points_sim3.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(Camera), C.POINTER(FramePose), f32, f32, i32, vp, vp, vp, vp, vp, vp,
                                                      vp, vp, vp]
+    L.orbx_keyframe_search_by_projection_sim3_fisheye.argtypes = [vp, i32, C.POINTER(vp), vp, f32, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp,
+                                                                  C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp]
+    L.orbx_keyframe_fuse_map_points_sim3_fisheye.argtypes = [vp, i32, C.POINTER(vp), vp, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbx_keyframe_from_frame_fisheye.argtypes = [vp, vp, vp, C.POINTER(vp)]
     L.orbx_keyframe_create_host_fisheye.argtypes = [vp, C.POINTER(FrameDesc), vp, i32, vp, C.POINTER(vp)]
     L.orbx_keyframe_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

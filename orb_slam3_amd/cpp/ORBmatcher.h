@@ -680,6 +680,61 @@ public:
         if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_fuse_map_points_sim3: ") + orbx_status_string(r));
     }
 
+    // The two calls above for K FISHEYE-STEREO key frames (orbx_keyframe_search_by_projection_sim3_fisheye / orbx_keyframe_fuse_map_points_sim3_fisheye):
+    // the members read the LEFT camera only, so views holds K entries, one per key frame -- R, t = Tcw = SE3f(Scw.rotationMatrix(), Scw.translation() /
+    // Scw.scale()), twc = Tcw.inverse().translation(), params = mpCamera's eight (KannalaBrandt8; ORBX_SIM3_PROJECT_INVZ: params[0..3] = pKF->fx, fy,
+    // cx, cy).  occupied rows and vpMatch[k] hold N_k = N_left + N_right entries as vpMatched does on a rig; only indices below N_left are read or set.
+    void SearchByProjectionSim3KeyFramesFisheye(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<orbx_fisheye_view> &views,
+                                                const FuseMapPointSet &mps, const std::vector<uint8_t> &skip,
+                                                const std::vector<std::vector<uint8_t>> &occupied, float th, float ratioHamming, float logScaleFactor,
+                                                int projectionForm, std::vector<std::vector<int32_t>> &vpMatch, std::vector<int> &vnMatches,
+                                                std::vector<uint8_t> *projected = nullptr) {
+        const size_t K = vpKFs.size(), n = (size_t)mps.size();
+        if (views.size() != K || (!skip.empty() && skip.size() != K * n) || (!occupied.empty() && occupied.size() != K))
+            throw std::invalid_argument("SearchByProjectionSim3KeyFramesFisheye: one view per key frame, K x n skip flags, K occupancy rows");
+        std::vector<orbx_keyframe *> h(K);
+        std::vector<const uint8_t *> occ(K, nullptr);
+        std::vector<int32_t *> rows(K);
+        std::vector<int32_t> nm(K, 0);
+        vpMatch.assign(K, {});
+        for (size_t k = 0; k < K; k++) {
+            h[k] = vpKFs[k]->handle();
+            const size_t N = (size_t)vpKFs[k]->count();
+            if (!occupied.empty() && !occupied[k].empty()) {
+                if (occupied[k].size() != N) throw std::invalid_argument("SearchByProjectionSim3KeyFramesFisheye: an occupancy row holds N_k flags");
+                occ[k] = occupied[k].data();
+            }
+            vpMatch[k].assign(N + 1, -1);   // (+ 1: data() of an empty row may be NULL, which the call refuses)
+            rows[k] = vpMatch[k].data();
+        }
+        if (projected) projected->assign(K * n, 0);
+        const int r = orbx_keyframe_search_by_projection_sim3_fisheye(m_, (int)K, h.data(), views.data(), th, ratioHamming, logScaleFactor, projectionForm,
+                                                                      (int)n, mps.pos.data(), mps.normal.data(), mps.minDistance.data(),
+                                                                      mps.maxDistance.data(), mps.descriptors.data(), skip.empty() ? nullptr : skip.data(),
+                                                                      occupied.empty() ? nullptr : occ.data(), rows.data(), nm.data(),
+                                                                      projected ? projected->data() : nullptr, nullptr, nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_search_by_projection_sim3_fisheye: ") + orbx_status_string(r));
+        for (size_t k = 0; k < K; k++) vpMatch[k].pop_back();
+        vnMatches.assign(nm.begin(), nm.end());
+    }
+    // bestIdx (always below N_left) / bestDist / projected: [K][n], row-major.
+    void FuseMapPointsSim3Fisheye(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<orbx_fisheye_view> &views, const FuseMapPointSet &mps,
+                                  const std::vector<uint8_t> &skip, float th, float logScaleFactor, std::vector<int32_t> &bestIdx,
+                                  std::vector<int32_t> &bestDist, std::vector<uint8_t> *projected = nullptr) {
+        const size_t K = vpKFs.size(), n = (size_t)mps.size();
+        if (views.size() != K || (!skip.empty() && skip.size() != K * n))
+            throw std::invalid_argument("FuseMapPointsSim3Fisheye: one view per key frame, K x n skip flags");
+        std::vector<orbx_keyframe *> h(K);
+        for (size_t k = 0; k < K; k++) h[k] = vpKFs[k]->handle();
+        bestIdx.assign(K * n, -1); bestDist.assign(K * n, 256);
+        if (projected) projected->assign(K * n, 0);
+        const int r = orbx_keyframe_fuse_map_points_sim3_fisheye(m_, (int)K, h.data(), views.data(), th, logScaleFactor, (int)n, mps.pos.data(),
+                                                                 mps.normal.data(), mps.minDistance.data(), mps.maxDistance.data(),
+                                                                 mps.descriptors.data(), skip.empty() ? nullptr : skip.data(), bestIdx.data(),
+                                                                 bestDist.data(), projected ? projected->data() : nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_fuse_map_points_sim3_fisheye: ") + orbx_status_string(r));
+    }
+
     // FuseSearchKeyFrames for K fisheye-stereo key frames (orbx_keyframe_fuse_search_fisheye): q / bestIdx / bestDist hold 2 K entries, 2 k = key frame
     // k's left-camera set, 2 k + 1 its right-camera set (ur is not read).  A right-camera index is NLeft + j (ORBmatcher.cc:1296).
     void FuseSearchKeyFramesFisheye(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<FuseQueries> &q, bool useChi2,

@@ -613,10 +613,11 @@ public:
     }
 
 private:
-    // ---- LoopClosing's Sim3 calls on RESIDENT key frames (orbx_keyframe_search_by_projection_sim3 / orbx_keyframe_fuse_map_points_sim3): no key frame
-    // is uploaded, the gates (:452-487, :569-604, :1369-1399) run on the device.  The device applies 0.8f / 1.2f to mfMinDistance / mfMaxDistance and
-    // divides mfMaxDistance in PredictScale itself, so it takes them UNSCALED -- the reference's MapPoint publishes only the scaled values.  A tree that
-    // uses these overloads adds
+    // ---- LoopClosing's Sim3 calls on RESIDENT key frames (orbx_keyframe_search_by_projection_sim3 / orbx_keyframe_fuse_map_points_sim3, for
+    // fisheye-stereo key frames -- pKF->NLeft != -1 -- their _fisheye twins on the left camera): no key frame is uploaded, the gates (:452-487,
+    // :569-604, :1369-1399) run on the device.  The device applies 0.8f / 1.2f to mfMinDistance / mfMaxDistance and divides mfMaxDistance in
+    // PredictScale itself, so it takes them UNSCALED -- the reference's MapPoint publishes only the scaled values.  A tree that uses these overloads
+    // adds
     //     float MapPoint::GetMinDistance() { unique_lock<mutex> lock(mMutexPos); return mfMinDistance; }   // and GetMaxDistance()
     // Without the two getters the overloads throw: dividing the scaled values back does not give the reference's floats.
     template <class MP> static auto raw_distances(MP *p, float &mn, float &mx, int) -> decltype((void)p->GetMinDistance(), void()) {
@@ -641,6 +642,36 @@ private:
         }
         cam = orbx_camera{pKF->fx, pKF->fy, pKF->cx, pKF->cy, 0.f, 0.f, 0.f, 0.f, 0.f, pKF->mbf};
     }
+    // The same for a fisheye-stereo key frame (NLeft != -1): the members project with pKF->mpCamera -- the LEFT camera, KannalaBrandt8 -- and never
+    // look at the right one.  invz: the vpPointsKFs overload writes the pinhole form out with pKF->fx, fy, cx, cy whatever the camera model is (:573-578).
+    template <class Sim3> static void sim3_view_fisheye(KeyFrame *pKF, Sim3 &Scw, bool invz, orbx_fisheye_view &view) {
+        GeometricCamera *c = pKF->mpCamera;
+        if (!c || c->GetType() != GeometricCamera::CAM_FISHEYE || c->size() != 8)
+            throw std::invalid_argument("the resident Sim3 overloads on a fisheye-stereo key frame need a KannalaBrandt8 mpCamera (CAM_FISHEYE, 8 parameters)");
+        Sophus::SE3f Tcw = Sophus::SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale());
+        Eigen::Vector3f Ow = Tcw.inverse().translation();
+        const Eigen::Matrix3f R = Tcw.rotationMatrix();
+        const Eigen::Vector3f t = Tcw.translation();
+        for (int r = 0; r < 3; r++) {
+            for (int col = 0; col < 3; col++) view.R[3 * r + col] = R(r, col);
+            view.t[r] = t(r); view.twc[r] = Ow(r);
+        }
+        for (int k = 0; k < 8; k++) view.params[k] = c->getParameter(k);
+        if (invz) { view.params[0] = pKF->fx; view.params[1] = pKF->fy; view.params[2] = pKF->cx; view.params[3] = pKF->cy; }
+    }
+
+public:
+    // true: every key frame of the list is fisheye-stereo (NLeft != -1), false: every one is monocular / rectified (an empty list too); a mixed list
+    // throws -- a device call takes key frames of one kind.  (Public only so that tests/test_keyframe_sim3_fisheye_abi.py can run the rule on stand-in
+    // key frames without a device; a SLAM tree has no reason to call it.)
+    static bool sim3_rig_list(const std::vector<KeyFrame *> &vpKFs) {
+        const bool rig = !vpKFs.empty() && vpKFs[0]->NLeft != -1;
+        for (KeyFrame *pKF : vpKFs)
+            if ((pKF->NLeft != -1) != rig) throw std::invalid_argument("Fuse: monocular / rectified and fisheye-stereo key frames in one list");
+        return rig;
+    }
+
+private:
     // vpPoints flat, with the reference's accessors (GetWorldPos, GetNormal, the two distances, GetDescriptor)
     static FuseMapPointSet sim3_point_set(const std::vector<MapPoint *> &vpPoints) {
         FuseMapPointSet s;
@@ -657,19 +688,28 @@ private:
     template <class Sim3>
     int sim3_projection_resident(KeyFrame *pKF, DeviceKeyFrame *pDeviceKF, Sim3 &Scw, const std::vector<MapPoint *> &vpPoints,
                                  std::vector<MapPoint *> &vpMatched, int th, float ratioHamming, int form, std::vector<int32_t> &match) {
-        std::vector<orbx_camera> cams(1);
-        std::vector<orbx_frame_pose> poses(1);
-        sim3_view(pKF, Scw, cams[0], poses[0]);
+        const bool rig = pKF->NLeft != -1;   // a fisheye-stereo key frame: its left camera, vpMatched spans N = NLeft + NRight
+        if (pDeviceKF->fisheye() != rig) throw std::invalid_argument("SearchByProjection: the resident copy is of another kind than pKF");
         std::set<MapPoint *> spAlreadyFound(vpMatched.begin(), vpMatched.end());
         spAlreadyFound.erase(static_cast<MapPoint *>(NULL));
         std::vector<uint8_t> skip(vpPoints.size());
         for (size_t i = 0; i < vpPoints.size(); i++) skip[i] = (vpPoints[i]->isBad() || spAlreadyFound.count(vpPoints[i])) ? 1 : 0;   // :445-449
-        std::vector<std::vector<uint8_t>> occupied(1, std::vector<uint8_t>(pKF->mvKeysUn.size()));
+        std::vector<std::vector<uint8_t>> occupied(1, std::vector<uint8_t>(rig ? vpMatched.size() : pKF->mvKeysUn.size()));
         for (size_t i = 0; i < occupied[0].size(); i++) occupied[0][i] = vpMatched[i] ? 1 : 0;                                       // :499
         std::vector<std::vector<int32_t>> rows;
         std::vector<int> nm;
-        SearchByProjectionSim3KeyFrames({pDeviceKF}, cams, poses, sim3_point_set(vpPoints), skip, occupied, (float)th, ratioHamming,
-                                        log_scale_factor_of(pKF, 0), form, rows, nm);
+        if (rig) {
+            std::vector<orbx_fisheye_view> views(1);
+            sim3_view_fisheye(pKF, Scw, form == ORBX_SIM3_PROJECT_INVZ, views[0]);
+            SearchByProjectionSim3KeyFramesFisheye({pDeviceKF}, views, sim3_point_set(vpPoints), skip, occupied, (float)th, ratioHamming,
+                                                   log_scale_factor_of(pKF, 0), form, rows, nm);
+        } else {
+            std::vector<orbx_camera> cams(1);
+            std::vector<orbx_frame_pose> poses(1);
+            sim3_view(pKF, Scw, cams[0], poses[0]);
+            SearchByProjectionSim3KeyFrames({pDeviceKF}, cams, poses, sim3_point_set(vpPoints), skip, occupied, (float)th, ratioHamming,
+                                            log_scale_factor_of(pKF, 0), form, rows, nm);
+        }
         match.swap(rows[0]);
         return nm[0];
     }
@@ -1032,16 +1072,21 @@ public:
         const size_t K = vpKFs.size(), n = vpPoints.size();
         if (vpDeviceKFs.size() != K || vScw.size() != K || vvpReplacePoint.size() != K)
             throw std::invalid_argument("Fuse: one DeviceKeyFrame, one Sim3 and one vpReplacePoint per key frame");
-        std::vector<orbx_camera> cams(K);
-        std::vector<orbx_frame_pose> poses(K);
+        const bool rig = sim3_rig_list(vpKFs);   // all fisheye-stereo: the left cameras through orbx_keyframe_fuse_map_points_sim3_fisheye (a mixed list throws)
+        std::vector<orbx_camera> cams(rig ? 0 : K);
+        std::vector<orbx_frame_pose> poses(rig ? 0 : K);
+        std::vector<orbx_fisheye_view> views(rig ? K : 0);
         std::vector<uint8_t> skip(K * n);
         for (size_t k = 0; k < K; k++) {
-            sim3_view(vpKFs[k], vScw[k], cams[k], poses[k]);
+            if (rig) sim3_view_fisheye(vpKFs[k], vScw[k], false, views[k]);
+            else sim3_view(vpKFs[k], vScw[k], cams[k], poses[k]);
             const std::set<MapPoint *> spAlreadyFound = vpKFs[k]->GetMapPoints();
             for (size_t i = 0; i < n; i++) skip[k * n + i] = (vpPoints[i]->isBad() || spAlreadyFound.count(vpPoints[i])) ? 1 : 0;
         }
         std::vector<int32_t> bestIdx, bestDist;
-        FuseMapPointsSim3(vpDeviceKFs, cams, poses, sim3_point_set(vpPoints), skip, th, K ? log_scale_factor_of(vpKFs[0], 0) : 0.f, bestIdx, bestDist);
+        const float lsf = K ? log_scale_factor_of(vpKFs[0], 0) : 0.f;
+        if (rig) FuseMapPointsSim3Fisheye(vpDeviceKFs, views, sim3_point_set(vpPoints), skip, th, lsf, bestIdx, bestDist);   // (bestIdx < NLeft: mvKeys' numbering)
+        else FuseMapPointsSim3(vpDeviceKFs, cams, poses, sim3_point_set(vpPoints), skip, th, lsf, bestIdx, bestDist);
         std::vector<int> nFused(K, 0);
         for (size_t k = 0; k < K; k++) {
             KeyFrame *pKF = vpKFs[k];

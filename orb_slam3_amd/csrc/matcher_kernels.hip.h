@@ -1567,6 +1567,73 @@ __global__ __launch_bounds__(256) void k_fuse_project_kb8(const KfProblem *__res
     qvalid[o] = ok ? 1 : 0;
 }
 
+// k_sim3_project_kb8: k_sim3_project with the rig's camera -- the projection half of LoopClosing's three Sim3 matcher calls (ORBmatcher.cc:452-487,
+// :569-604, :1369-1399) on a fisheye-stereo key frame.  Those members never look at the right camera (GetFeaturesInArea with bRight = false,
+// mvKeysUn[idx], mpCamera): ONE problem per key frame -- its left rows, left grid, count[0] -- and one view per key frame: R, t =
+// SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()), twc = its camera centre, p = the LEFT camera's parameters.  The gates are k_sim3_project's,
+// statement for statement (every input requested first, sums in k_fuse_project's order, every float operation rounded separately):
+//   reject skip; p3Dc = R p + t; reject p3Dc.z < 0.0f
+//   ORBX_SIM3_PROJECT_CAMERA: pKF->mpCamera->project(p3Dc) = KannalaBrandt8::project -- kb8_project as k_fuse_project_kb8 calls it (the bit contract and
+//     the one-ulp caveat of orbx_is_in_frustum_checks), evaluated only for pairs that are not skipped and lie in front of the camera;
+//   ORBX_SIM3_PROJECT_INVZ: the vpPointsKFs overload's written-out pinhole form (:573-578) with fx, fy, cx, cy = p[0..3] -- the caller puts pKF->fx,
+//     fy, cx, cy there: the reference writes it whatever the camera model is
+//   KeyFrame::IsInImage (strict on the max side)
+//   dist = |p - twc|; reject outside [0.8f mfMinDistance, 1.2f mfMaxDistance]
+//   reject PO . Pn < 0.5 * dist, compared in double and without a division
+//   PredictScale(dist, pKF); radius = th * mvScaleFactors[level]; levels [level - 1, level]
+// No ur.  skip / outputs [n_kf][n_mp].  Streaming work: no LDS.  grid (ceil(n_mp / 256), n_kf), block 256
+__global__ __launch_bounds__(256) void k_sim3_project_kb8(const KfProblem *__restrict__ recs, const FisheyeView *__restrict__ views, float th,
+                                                          float log_scale_factor, int projection_form, int n_mp, const float *__restrict__ pos,
+                                                          const float *__restrict__ normal, const float *__restrict__ min_dist,
+                                                          const float *__restrict__ max_dist, const uint8_t *__restrict__ skip, float *__restrict__ qx,
+                                                          float *__restrict__ qy, float *__restrict__ qr, int32_t *__restrict__ qmin,
+                                                          int32_t *__restrict__ qmax, uint8_t *__restrict__ qvalid) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_mp) return;
+    const int k = blockIdx.y;
+    const size_t o = (size_t)k * n_mp + i;
+    const FisheyeView &V = views[k];
+    const float minx = recs[k].g.minx, miny = recs[k].g.miny, maxx = recs[k].maxx, maxy = recs[k].maxy;
+    const int nlevels = recs[k].nlevels;
+    const float *scale = recs[k].P.scale;
+    // every input of the pair requested at once (the gates read them conditionally: each would be a dependent round trip)
+    const uint8_t sk = skip ? skip[o] : (uint8_t)0;
+    const float P0 = pos[3 * i], P1 = pos[3 * i + 1], P2 = pos[3 * i + 2];
+    const float mn_in = min_dist[i], mx = max_dist[i], N0 = normal[3 * i], N1 = normal[3 * i + 1], N2 = normal[3 * i + 2];
+    float Pc[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+        Pc[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(V.R[3 * r], P0), __fmul_rn(V.R[3 * r + 1], P1)), __fmul_rn(V.R[3 * r + 2], P2)), V.t[r]);
+    bool ok = !sk && !(Pc[2] < 0.0f);
+    float u = 0.f, v = 0.f;
+    if (projection_form == ORBX_SIM3_PROJECT_INVZ) {   // the vpPointsKFs overload writes the pinhole projection out (:573-578)
+        const float invz = __fdiv_rn(1.0f, Pc[2]);
+        const float x = __fmul_rn(Pc[0], invz), y = __fmul_rn(Pc[1], invz);
+        u = __fadd_rn(__fmul_rn(V.p[0], x), V.p[2]); v = __fadd_rn(__fmul_rn(V.p[1], y), V.p[3]);
+    } else if (ok) {                                   // pKF->mpCamera->project(p3Dc): KannalaBrandt8::project
+        kb8_project(V.p, Pc[0], Pc[1], Pc[2], &u, &v);
+    }
+    ok = ok && (u >= minx && u < maxx && v >= miny && v < maxy);
+    const float PO0 = __fsub_rn(P0, V.twc[0]), PO1 = __fsub_rn(P1, V.twc[1]), PO2 = __fsub_rn(P2, V.twc[2]);
+    const float dist = sqrtf(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, PO0)), __fmul_rn(PO1, PO1)), __fmul_rn(PO2, PO2)));
+    const float maxDistance = __fmul_rn(1.2f, mx), minDistance = __fmul_rn(0.8f, mn_in);
+    ok = ok && !(dist < minDistance || dist > maxDistance);
+    const float dot = __fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, N0)), __fmul_rn(PO1, N1)), __fmul_rn(PO2, N2));
+    ok = ok && !((double)dot < 0.5 * (double)dist);
+    int lvl = 0;
+    float radius = 0.f;
+    if (ok) {   // MapPoint::PredictScale(dist, pKF) (MapPoint.cc:531-546), as k_fuse_project evaluates it
+        const float ratio = __fdiv_rn(mx, dist);
+        lvl = (int)ceilf(__fdiv_rn((float)log((double)ratio), log_scale_factor));
+        if (lvl < 0) lvl = 0;
+        else if (lvl >= nlevels) lvl = nlevels - 1;
+        radius = __fmul_rn(th, gld(scale + lvl));
+    }
+    qx[o] = u; qy[o] = v; qr[o] = radius;
+    qmin[o] = lvl - 1; qmax[o] = lvl;   // kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel (:504-507, :1411-1414)
+    qvalid[o] = ok ? 1 : 0;
+}
+
 // A loaded fisheye-stereo orbx_frame copied into a key frame's own allocation -- what KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-82) does with mvKeys,
 // mvKeysRight, mDescriptors, mvScaleFactors, mvInvLevelSigma2, mGrid and mGridRight: both cameras' rows, both counts, the scale factors and both grids AS
 // BUILT.  The counts are read on the device.  The right rows move from the frame's row offset src_roff to the key frame's roff (the frame keeps them at

@@ -3173,15 +3173,16 @@ int orbx_keyframe_fuse_search_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *
 // [camera,] map point) into the arena, k_window_best1_kf searches the sides * n_kf problems -- the records never visit the host, the map points go up
 // once.  Monocular: cams / poses [n_kf], one problem per key frame, Fuse(pKFi, vpMapPointMatches).  fisheye: views [n_kf][2] instead, two problems per
 // key frame -- Fuse(pKFi, vpMapPointMatches) and Fuse(pKFi, vpMapPointMatches, true) -- and counts that are still on the device come home with the results.
-// sim3 (monocular key frames): LoopClosing::SearchAndFuse's loop instead, Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (ORBmatcher.cc:1339-1455) -- the
-// records come from k_sim3_project (no ur) and the search is the gate-less one: no inv_sigma2 wanted of the key frames, no mvuRight read.
+// sim3: LoopClosing::SearchAndFuse's loop instead, Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (ORBmatcher.cc:1339-1455) -- the records come from
+// k_sim3_project (no ur) and the search is the gate-less one: no inv_sigma2 wanted of the key frames, no mvuRight read.  fisheye && sim3: that member
+// reads the left camera only -- views [n_kf], ONE problem per key frame (its left side), records from k_sim3_project_kb8, best_idx below N_left.
 static int keyframe_fuse_map_points_impl(orbx_matcher *m, bool fisheye, bool sim3, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
                                          const orbx_frame_pose *poses, const orbx_fisheye_view *views, float th, float log_scale_factor, int strict_fp,
                                          int n_mp, const float *pos, const float *normal, const float *min_dist, const float *max_dist,
                                          const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist, uint8_t *projected) {
     if (!m || n_kf < 0 || n_mp < 0 || (n_kf > 0 && (!kfs || (fisheye ? !views : !cams || !poses)))) return ORBX_E_BAD_ARG;
     if (n_kf > ORBX_MAX_FUSE_KEYFRAMES) return ORBX_E_TOO_LARGE;
-    const int sides = fisheye ? 2 : 1, nprob = n_kf * sides;   // problem p: key frame p / sides, camera p % sides
+    const int sides = fisheye && !sim3 ? 2 : 1, nprob = n_kf * sides;   // problem p: key frame p / sides, camera p % sides (a Sim3 Fuse: the left one only)
     const size_t np = (size_t)n_mp, total = (size_t)nprob * np;
     if (total > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !best_idx || !best_dist)) return ORBX_E_BAD_ARG;
     for (int k = 0; k < n_kf; k++)
@@ -3226,7 +3227,11 @@ static int keyframe_fuse_map_points_impl(orbx_matcher *m, bool fisheye, bool sim
     ORBX_TRY(m->h2d(dR, R.data(), sizeof(KfProblem) * (size_t)nprob));
     ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
     const dim3 grid((unsigned)((n_mp + 255) / 256), (unsigned)nprob);
-    if (fisheye)
+    if (fisheye && sim3)
+        hipLaunchKernelGGL(k_sim3_project_kb8, grid, dim3(256), 0, m->exec(), (const KfProblem *)dR, (const FisheyeView *)dview, th, log_scale_factor,
+                           (int)ORBX_SIM3_PROJECT_CAMERA, n_mp, (const float *)dp, (const float *)dn, (const float *)dmn, (const float *)dmx,
+                           (const uint8_t *)dskip, qx, qy, qr, qmin, qmax, qvalid);
+    else if (fisheye)
         hipLaunchKernelGGL(k_fuse_project_kb8, grid, dim3(256), 0, m->exec(), (const KfProblem *)dR, (const FisheyeView *)dview, th, log_scale_factor, n_mp,
                            (const float *)dp, (const float *)dn, (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx, qy, qr, qmin, qmax, qvalid);
     else if (sim3)
@@ -3780,30 +3785,38 @@ int orbx_keyframe_search_for_triangulation_fisheye(orbx_matcher *m, orbx_keyfram
 // LoopClosing's Sim3 projection searches on resident key frames: both SearchByProjection(KeyFrame*, Sim3f&, ...) overloads (ORBmatcher.cc:427-532,
 // :534-646) for K key frames with one shared point set, and SearchAndFuse's loop of Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:1339-1455).  The
 // gates run on the device (k_sim3_project); the searches are the existing kernels: k_window_best2_t + the replay of the query loop over n_kf problems
-// for the first, k_window_best1_kf through keyframe_fuse_map_points_impl for the second.  Monocular / rectified key frames only.
+// for the first, k_window_best1_kf through keyframe_fuse_map_points_impl for the second.  The _fisheye twins run the same on the LEFT side of rig key
+// frames (k_sim3_project_kb8: KannalaBrandt8::project, or the written-out pinhole form of the second overload).
 // ---------------------------------------------------------------------------------------------------------
-extern "C" int orbx_keyframe_search_by_projection_sim3(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
-                                                       const orbx_frame_pose *poses, float th, float ratio_hamming, float log_scale_factor,
-                                                       int projection_form, int n_mp, const float *pos, const float *normal, const float *min_dist,
-                                                       const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip,
-                                                       const uint8_t *const *occupied, int32_t *const *match, int32_t *nmatches, uint8_t *projected,
-                                                       float *proj_u, float *proj_v) {
-    if (!m || n_kf < 0 || n_mp < 0 || (n_kf > 0 && (!kfs || !cams || !poses || !match || !nmatches))) return ORBX_E_BAD_ARG;
+namespace {
+
+// Both kinds of key frame through one body, the kind being `fisheye`: cams + poses [n_kf] and k_sim3_project, or views [n_kf] and k_sim3_project_kb8 on
+// the LEFT side of a rig key frame (the members read nothing else: GetFeaturesInArea with bRight = false, mvKeysUn[idx], mpCamera) -- the left
+// keyframe_problem, N_left features for the replay, while the caller's match / occupied rows span N = N_left + N_right as vpMatched does.
+int keyframe_search_by_projection_sim3_impl(orbx_matcher *m, bool fisheye, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
+                                            const orbx_frame_pose *poses, const orbx_fisheye_view *views, float th, float ratio_hamming,
+                                            float log_scale_factor, int projection_form, int n_mp, const float *pos, const float *normal,
+                                            const float *min_dist, const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip,
+                                            const uint8_t *const *occupied, int32_t *const *match, int32_t *nmatches, uint8_t *projected, float *proj_u,
+                                            float *proj_v) {
+    if (!m || n_kf < 0 || n_mp < 0 || (n_kf > 0 && (!kfs || (fisheye ? !views : !cams || !poses) || !match || !nmatches))) return ORBX_E_BAD_ARG;
     if ((projection_form != ORBX_SIM3_PROJECT_CAMERA && projection_form != ORBX_SIM3_PROJECT_INVZ) || (proj_u == nullptr) != (proj_v == nullptr))
         return ORBX_E_BAD_ARG;
     if (n_kf > ORBX_MAX_FUSE_KEYFRAMES) return ORBX_E_TOO_LARGE;
     const size_t np = (size_t)n_mp, total = (size_t)n_kf * np;
     if (total > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc)) return ORBX_E_BAD_ARG;
     for (int k = 0; k < n_kf; k++) {
-        if (!kfs[k] || kfs[k]->fisheye || kfs[k]->device != m->device || !match[k]) return ORBX_E_BAD_ARG;
+        if (!kfs[k] || kfs[k]->fisheye != fisheye || kfs[k]->device != m->device || !match[k]) return ORBX_E_BAD_ARG;
         // k_window_best2_t and the replay take ONE GridParams per launch: the key frames of a call share their image bounds, bit for bit
         if (memcmp(kfs[k]->bounds, kfs[0]->bounds, sizeof(kfs[0]->bounds)) != 0) return ORBX_E_BAD_ARG;
     }
     int nc = 0;   // the rows of match / occupied hold N_k entries: the counts are needed here (cached since the caller sized the rows)
+    std::vector<int> ns((size_t)n_kf, 0);   // the features the search sees: N, of a rig N_left (a match row's entries [N_left, N) stay -1)
     for (int k = 0; k < n_kf; k++) {
         const int rc = keyframe_need_count(kfs[k]);
         if (rc != ORBX_OK) return rc;
-        nc = std::max(nc, kfs[k]->host_n());
+        ns[(size_t)k] = fisheye ? kfs[k]->host_left() : kfs[k]->host_n();
+        nc = std::max(nc, ns[(size_t)k]);
     }
     if (nc > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;   // before anything is enqueued: the replay keeps 10 B per feature in LDS
     for (int k = 0; k < n_kf; k++) {
@@ -3818,6 +3831,7 @@ extern "C" int orbx_keyframe_search_by_projection_sim3(orbx_matcher *m, int n_kf
     int32_t *dcnt, *qmin, *qmax, *dmeta, *dentries, *dnm;
     orbx_camera *dcam;
     orbx_frame_pose *dpose;
+    FisheyeView *dview;
     KfProblem *dK;
     WindowProblem *dP;
     ResolveProblem *dR;
@@ -3829,17 +3843,18 @@ extern "C" int orbx_keyframe_search_by_projection_sim3(orbx_matcher *m, int n_kf
         dp = A.up(pos, 3 * np); dn = A.up(normal, 3 * np); dmn = A.up(min_dist, np); dmx = A.up(max_dist, np);
         dd = A.up(mp_desc, 32 * np);
         dcnt = A.up(cnt4, 4);
-        dcam = A.up(cams, (size_t)n_kf); dpose = A.up(poses, (size_t)n_kf);
+        dcam = fisheye ? nullptr : A.up(cams, (size_t)n_kf); dpose = fisheye ? nullptr : A.up(poses, (size_t)n_kf);
+        dview = fisheye ? A.up(reinterpret_cast<const FisheyeView *>(views), (size_t)n_kf) : nullptr;
         dskip = A.up_opt(skip, total);
         for (int k = 0; k < n_kf; k++)
-            if (occupied && occupied[k] && kfs[k]->host_n() > 0) docc[(size_t)k] = A.up(occupied[k], (size_t)kfs[k]->host_n());
+            if (occupied && occupied[k] && ns[(size_t)k] > 0) docc[(size_t)k] = A.up(occupied[k], (size_t)ns[(size_t)k]);
         dK = A.take<KfProblem>(n_kf); dP = A.take<WindowProblem>(n_kf); dR = A.take<ResolveProblem>(n_kf);
         // written by k_sim3_project and the window scan, read by the scan and the replay: device only
         qr = A.take<float>(total); qmin = A.take<int32_t>(total); qmax = A.take<int32_t>(total);
         dkeys = A.take<u64>(total * kTopK); dmeta = A.take<int32_t>(total); dentries = A.take<int32_t>(total);
         // the downloads side by side (one run): the projections, the gates' verdicts, the match rows, nmatches
         qx = A.take<float>(total); qy = A.take<float>(total); qvalid = A.take<uint8_t>(total);
-        for (int k = 0; k < n_kf; k++) dmatch[(size_t)k] = A.take<int32_t>((size_t)std::max(kfs[k]->host_n(), 1));
+        for (int k = 0; k < n_kf; k++) dmatch[(size_t)k] = A.take<int32_t>((size_t)std::max(ns[(size_t)k], 1));
         dnm = A.take<int32_t>(n_kf);
     }));
     std::vector<KfProblem> K((size_t)n_kf);
@@ -3863,20 +3878,56 @@ extern "C" int orbx_keyframe_search_by_projection_sim3(orbx_matcher *m, int n_kf
     ORBX_TRY(m->h2d(dP, P.data(), sizeof(WindowProblem) * (size_t)n_kf));
     ORBX_TRY(m->h2d(dR, R.data(), sizeof(ResolveProblem) * (size_t)n_kf));
     ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
-    hipLaunchKernelGGL(k_sim3_project, dim3((unsigned)((n_mp + 255) / 256), (unsigned)n_kf), dim3(256), 0, m->exec(), (const KfProblem *)dK,
-                       (const orbx_camera *)dcam, (const orbx_frame_pose *)dpose, th, log_scale_factor, projection_form, n_mp, (const float *)dp,
-                       (const float *)dn, (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx, qy, qr, qmin, qmax, qvalid);
+    const dim3 pgrid((unsigned)((n_mp + 255) / 256), (unsigned)n_kf);
+    if (fisheye)
+        hipLaunchKernelGGL(k_sim3_project_kb8, pgrid, dim3(256), 0, m->exec(), (const KfProblem *)dK, (const FisheyeView *)dview, th, log_scale_factor,
+                           projection_form, n_mp, (const float *)dp, (const float *)dn, (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx,
+                           qy, qr, qmin, qmax, qvalid);
+    else
+        hipLaunchKernelGGL(k_sim3_project, pgrid, dim3(256), 0, m->exec(), (const KfProblem *)dK, (const orbx_camera *)dcam,
+                           (const orbx_frame_pose *)dpose, th, log_scale_factor, projection_form, n_mp, (const float *)dp, (const float *)dn,
+                           (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx, qy, qr, qmin, qmax, qvalid);
     const GridParams g = grid_of(kfs[0]->bounds);
     ORBX_LAUNCH_WINDOW_BEST2(n_mp, n_kf, m->exec(), (const WindowProblem *)dP, g);
     { const int rr = launch_resolve<false>(n_kf, m->exec(), dP, dR, g, nc, n_mp, 4); if (rr != ORBX_OK) return rr; }
     ORBX_HIP(hipGetLastError());
     if (proj_u) { ORBX_TRY(m->d2h(proj_u, qx, 4 * total)); ORBX_TRY(m->d2h(proj_v, qy, 4 * total)); }
     if (projected) ORBX_TRY(m->d2h(projected, qvalid, total));
-    for (int k = 0; k < n_kf; k++) ORBX_TRY(m->d2h(match[k], dmatch[(size_t)k], 4 * (size_t)kfs[k]->host_n()));
+    for (int k = 0; k < n_kf; k++) ORBX_TRY(m->d2h(match[k], dmatch[(size_t)k], 4 * (size_t)ns[(size_t)k]));
     ORBX_TRY(m->d2h(nmatches, dnm, 4 * (size_t)n_kf));
     ORBX_TRY(m->sync_and_deliver());
     keyframe_release(kfs, n_kf);
     return ORBX_OK;
+}
+
+}  // namespace
+
+extern "C" int orbx_keyframe_search_by_projection_sim3(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
+                                                       const orbx_frame_pose *poses, float th, float ratio_hamming, float log_scale_factor,
+                                                       int projection_form, int n_mp, const float *pos, const float *normal, const float *min_dist,
+                                                       const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip,
+                                                       const uint8_t *const *occupied, int32_t *const *match, int32_t *nmatches, uint8_t *projected,
+                                                       float *proj_u, float *proj_v) {
+    return keyframe_search_by_projection_sim3_impl(m, false, n_kf, kfs, cams, poses, nullptr, th, ratio_hamming, log_scale_factor, projection_form, n_mp, pos,
+                                                   normal, min_dist, max_dist, mp_desc, skip, occupied, match, nmatches, projected, proj_u, proj_v);
+}
+
+extern "C" int orbx_keyframe_search_by_projection_sim3_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views,
+                                                               float th, float ratio_hamming, float log_scale_factor, int projection_form, int n_mp,
+                                                               const float *pos, const float *normal, const float *min_dist, const float *max_dist,
+                                                               const uint8_t *mp_desc, const uint8_t *skip, const uint8_t *const *occupied,
+                                                               int32_t *const *match, int32_t *nmatches, uint8_t *projected, float *proj_u,
+                                                               float *proj_v) {
+    return keyframe_search_by_projection_sim3_impl(m, true, n_kf, kfs, nullptr, nullptr, views, th, ratio_hamming, log_scale_factor, projection_form, n_mp, pos,
+                                                   normal, min_dist, max_dist, mp_desc, skip, occupied, match, nmatches, projected, proj_u, proj_v);
+}
+
+extern "C" int orbx_keyframe_fuse_map_points_sim3_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views, float th,
+                                                          float log_scale_factor, int n_mp, const float *pos, const float *normal,
+                                                          const float *min_dist, const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip,
+                                                          int32_t *best_idx, int32_t *best_dist, uint8_t *projected) {
+    return keyframe_fuse_map_points_impl(m, true, true, n_kf, kfs, nullptr, nullptr, views, th, log_scale_factor, 0, n_mp, pos, normal, min_dist, max_dist,
+                                         mp_desc, skip, best_idx, best_dist, projected);
 }
 
 extern "C" int orbx_keyframe_fuse_map_points_sim3(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,

@@ -1013,6 +1013,55 @@ class ORBmatcher:
               "orbx_keyframe_fuse_map_points_sim3")
         return bi, bd, pr
 
+    def _sim3_fisheye_args(self, kfs, views, map_points: dict, skip):
+        K = len(kfs)
+        assert len(views) == K
+        P, Nn = _f32(np.asarray(map_points["pos"]).reshape(-1, 3)), _f32(np.asarray(map_points["normal"]).reshape(-1, 3))
+        mn, mx, d = _f32(map_points["min_dist"]), _f32(map_points["max_dist"]), _u8(map_points["desc"])
+        n = len(P)
+        sk = None if skip is None else _u8(np.asarray(skip).reshape(K, n))
+        V = np.zeros(23 * max(K, 1), np.float32)   # ONE orbx_fisheye_view per key frame: the left camera's
+        for k, cam in enumerate(views):
+            V[23 * k:23 * (k + 1)] = np.concatenate([np.asarray(x, np.float32).ravel() for x in cam])
+        return K, n, (P, Nn, mn, mx, d, sk), (self._kf_handles(kfs), V)
+
+    def SearchByProjectionSim3KeyFramesFisheye(self, kfs, views, map_points: dict, th: float, ratio_hamming: float = 1.0,
+                                               log_scale_factor: float = 0.0, projection_form: int = _lib.SIM3_PROJECT_CAMERA, skip=None, occupied=None,
+                                               want_projected: bool = True, want_uv: bool = False):
+        """SearchByProjectionSim3KeyFrames for K fisheye-stereo DeviceKeyFrames (orbx_keyframe_search_by_projection_sim3_fisheye): the members read the
+        LEFT camera only.  views[k] = (R, t, twc, params8) of Tcw = SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()) with the left camera's
+        parameters (SIM3_PROJECT_INVZ: params8[0..3] = pKF->fx, fy, cx, cy).  occupied: None, or per key frame a uint8[N_k] mask or None, N_k =
+        N_left + N_right as vpMatched on a rig (entries from N_left on are not read).
+        Returns (nmatches [K], match: K arrays of N_k map-point indices or -1 (always -1 from N_left on), projected [K, n] or None, (proj_u, proj_v)
+        [K, n] or None)."""
+        K, n, (P, Nn, mn, mx, d, sk), (hs, V) = self._sim3_fisheye_args(kfs, views, map_points, skip)
+        keep, occ = self._flag_rows(occupied, K)
+        match = [np.full(kf.count(), -1, np.int32) for kf in kfs]
+        rows = (C.c_void_p * max(K, 1))(*[ptr(x) for x in match])
+        nm = np.zeros(max(K, 1), np.int32)
+        pr = np.zeros((K, n), np.uint8) if want_projected else None
+        pu, pv = (np.zeros((K, n), np.float32), np.zeros((K, n), np.float32)) if want_uv else (None, None)
+        check(self._L.orbx_keyframe_search_by_projection_sim3_fisheye(self._h, K, hs, ptr(V), float(th), float(ratio_hamming), float(log_scale_factor),
+                                                                      int(projection_form), n, ptr(P), ptr(Nn), ptr(mn), ptr(mx), ptr(d), ptr(sk),
+                                                                      occ if occupied is not None else None, rows, ptr(nm), ptr(pr), ptr(pu),
+                                                                      ptr(pv)),
+              "orbx_keyframe_search_by_projection_sim3_fisheye")
+        del keep
+        return nm[:K], match, pr, ((pu, pv) if want_uv else None)
+
+    def FuseMapPointsSim3Fisheye(self, kfs, views, map_points: dict, th: float = 3.0, log_scale_factor: float = 0.0, skip=None,
+                                 want_projected: bool = True):
+        """FuseMapPointsSim3 for K fisheye-stereo DeviceKeyFrames (orbx_keyframe_fuse_map_points_sim3_fisheye): KannalaBrandt8::project of the left
+        camera, the gate-less search of the left features.  views as SearchByProjectionSim3KeyFramesFisheye takes them.
+        Returns (best_idx [K, n], always below N_left, best_dist [K, n], projected [K, n] or None)."""
+        K, n, (P, Nn, mn, mx, d, sk), (hs, V) = self._sim3_fisheye_args(kfs, views, map_points, skip)
+        bi, bd = np.full((K, n), -1, np.int32), np.full((K, n), 256, np.int32)
+        pr = np.zeros((K, n), np.uint8) if want_projected else None
+        check(self._L.orbx_keyframe_fuse_map_points_sim3_fisheye(self._h, K, hs, ptr(V), float(th), float(log_scale_factor), n, ptr(P), ptr(Nn), ptr(mn),
+                                                                 ptr(mx), ptr(d), ptr(sk), ptr(bi), ptr(bd), ptr(pr)),
+              "orbx_keyframe_fuse_map_points_sim3_fisheye")
+        return bi, bd, pr
+
     # ---- SearchBySim3 (ORBmatcher.cc:1457-1674): two gate-less fuse searches + mutual agreement ----
     def SearchBySim3(self, KF1: FrameView, KF2: FrameView, side1: dict, side2: dict, th: float, already_matched1=None,
                      already_matched2=None, scale_factors1=None, scale_factors2=None):
