@@ -1025,6 +1025,30 @@ int orbx_keyframe_fuse_map_points_sim3_fisheye(orbx_matcher *m, int n_kf, orbx_k
                                                const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
                                                uint8_t *projected);
 
+/* MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403) for a batch of map points whose observations are rows of RESIDENT key frames: what
+ * LocalMapping::ProcessNewKeyFrame, the "Update points" loop of LocalMapping::SearchInNeighbors, Tracking::CreateNewKeyFrame and the loop-correction
+ * and merge code call per map point.  orbx_distinctive_descriptors takes the rows gathered on the host (32 bytes per observation go up); this call
+ * takes where they are: set s is the observations [set_ptr[s], set_ptr[s+1]); observation o is row obs_idx[o] of mDescriptors of key frame
+ * kfs[obs_kf[o]], in the reference's feature numbering.  The caller lists a map point's observations in std::map order, skips isBad() key frames, and
+ * for a rig observation lists leftIndex, then rightIndex, each where it is not -1 (MapPoint.cc:345-356).
+ * best_obs[s] = the position inside set s of the row with the least median Hamming distance to the set's rows -- the median is sorted element
+ * (int)(0.5 * (N - 1)) of the N distances, the row's distance to itself included; the first minimum wins -- or -1 for an empty set.
+ * best_desc: NULL, or [n_sets][32]: the winning row itself (zeros for an empty set) -- mDescriptor, assigned without touching a key frame.
+ * Key frames of both kinds may be mixed; only descriptor rows are read.  Of a fisheye-stereo key frame an index i >= N_left names the right
+ * camera's row i - N_left; the device translates it with the key frame's own counts, also while these are still on the device (a key frame made from
+ * a batch-loaded frame) -- such a call brings the counts home with its results, and they are known afterwards.
+ * Refusals, ORBX_E_BAD_ARG before anything is enqueued: an index outside [0, N) of a key frame whose count the host knows (outside [0, capacity) of
+ * one whose counts are pending), obs_kf outside [0, n_kf), a decreasing set_ptr or set_ptr[0] < 0, a NULL array that would be read or written, a NULL
+ * key frame or one of another device.  An index outside [0, N) of a key frame with pending counts is found by the kernel: no address is formed from
+ * it, a flag comes home with the results and the call returns ORBX_E_BAD_ARG (the outputs are unspecified then).  n_kf above
+ * ORBX_MAX_DISTINCTIVE_KEYFRAMES: ORBX_E_TOO_LARGE.  The size of a set has no limit (sets of up to 64 rows are held in registers, larger ones are
+ * gathered into the call's scratch once).  n_sets = 0: ORBX_OK, nothing enqueued; n_kf = 0 and empty sets are fine.
+ * Cost shape: one upload run (set_ptr, obs_kf, obs_idx, one 32-byte record per key frame), one kernel (a second one if a set holds more than 64 rows), one download run, one
+ * synchronisation, whatever n_kf and n_sets are.  Sharing as every key-frame call: waits for each key frame's creation unless a call has done so before. */
+#define ORBX_MAX_DISTINCTIVE_KEYFRAMES 4096
+int orbx_keyframe_distinctive_descriptors(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, int n_sets, const int32_t *set_ptr,
+                                          const int32_t *obs_kf, const int32_t *obs_idx, int32_t *best_obs, uint8_t *best_desc);
+
 /* Frame::ComputeStereoMatches (Frame.cc:811-981) for every frame of two resident batches: `left` and `right` must have
  * extracted batches of the same size and image shape (rectified stereo, lapping {0,0}).  Row-band Hamming match, 11x11
  * SAD sub-pixel refinement on the device-resident pyramids and the median outlier rejection all run on the device, on

@@ -127,6 +127,7 @@ class FuseQueries(C.Structure):
 
 MAX_FUSE_KEYFRAMES = 256   # ORBX_MAX_FUSE_KEYFRAMES
 SIM3_PROJECT_CAMERA, SIM3_PROJECT_INVZ = 0, 1   # ORBX_SIM3_PROJECT_CAMERA (Pinhole::project), ORBX_SIM3_PROJECT_INVZ (ORBmatcher.cc:573-578)
+MAX_DISTINCTIVE_KEYFRAMES = 4096   # ORBX_MAX_DISTINCTIVE_KEYFRAMES
 
 
 class KeyFrameGate(C.Structure):
@@ -178,6 +179,7 @@ SYMBOLS = [
     "orbx_keyframe_search_by_bow_fisheye", "orbx_keyframe_search_for_triangulation_fisheye",
     "orbx_keyframe_search_by_projection_sim3", "orbx_keyframe_fuse_map_points_sim3",
     "orbx_keyframe_search_by_projection_sim3_fisheye", "orbx_keyframe_fuse_map_points_sim3_fisheye",
+    "orbx_keyframe_distinctive_descriptors",
 ]
 
 
@@ -316,6 +318,7 @@ def lib() -> C.CDLL:
     L.orbx_keyframe_search_by_projection_sim3_fisheye.argtypes = [vp, i32, C.POINTER(vp), vp, f32, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp,
                                                                   C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp]
     L.orbx_keyframe_fuse_map_points_sim3_fisheye.argtypes = [vp, i32, C.POINTER(vp), vp, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbx_keyframe_distinctive_descriptors.argtypes = [vp, i32, C.POINTER(vp), i32, vp, vp, vp, vp, vp]
     L.orbx_keyframe_from_frame_fisheye.argtypes = [vp, vp, vp, C.POINTER(vp)]
     L.orbx_keyframe_create_host_fisheye.argtypes = [vp, C.POINTER(FrameDesc), vp, i32, vp, C.POINTER(vp)]
     L.orbx_keyframe_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

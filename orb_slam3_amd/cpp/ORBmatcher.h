@@ -808,6 +808,24 @@ public:
         const int r = orbx_distinctive_descriptors(m_, descriptors.data(), setPtr.data(), n_sets, bestIdx.data());
         if (r < 0) throw std::runtime_error(std::string("orbx_distinctive_descriptors: ") + orbx_status_string(r));
     }
+    // The same with the observations named where they are (orbx_keyframe_distinctive_descriptors): observation o of map point p, o in
+    // [setPtr[p], setPtr[p+1]), is row obsIdx[o] of mDescriptors of vpKFs[obsKf[o]] (key frames of both kinds may be mixed; a rig's leftIndex, then
+    // rightIndex, in its own numbering).  bestObs[p] is the position inside the set the reference keeps, -1 for an empty set; bestDesc, where given,
+    // receives the winning rows, [n_sets][32] (zeros for an empty set): mDescriptor without touching a key frame.  No row is uploaded.
+    void ComputeDistinctiveDescriptors(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<int32_t> &setPtr, const std::vector<int32_t> &obsKf,
+                                       const std::vector<int32_t> &obsIdx, std::vector<int32_t> &bestObs, std::vector<uint8_t> *bestDesc = nullptr) {
+        const int n_sets = (int)setPtr.size() - 1;
+        bestObs.assign(n_sets > 0 ? n_sets : 0, -1);
+        if (bestDesc) bestDesc->assign(n_sets > 0 ? 32 * (size_t)n_sets : 0, 0);
+        if (n_sets <= 0) return;
+        if (obsKf.size() != obsIdx.size() || setPtr[n_sets] < 0 || (size_t)setPtr[n_sets] > obsKf.size())
+            throw std::invalid_argument("ComputeDistinctiveDescriptors: a key frame number and an index per observation, setPtr inside them");
+        std::vector<orbx_keyframe *> h(vpKFs.size());
+        for (size_t k = 0; k < vpKFs.size(); k++) h[k] = vpKFs[k]->handle();
+        const int r = orbx_keyframe_distinctive_descriptors(m_, (int)h.size(), h.data(), n_sets, setPtr.data(), obsKf.data(), obsIdx.data(), bestObs.data(),
+                                                            bestDesc ? bestDesc->data() : nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_distinctive_descriptors: ") + orbx_status_string(r));
+    }
 
     // Frame::ComputeStereoFishEyeMatches (Frame.cc:1126-1166) on host vectors: the brute-force kNN-2 of the two lapping-area descriptor
     // tails (BFmatcher.knnMatch, :1144) on the device, Lowe's ratio (:1151) and the bookkeeping (:1157-1162) here.  `triangulate(iLeft,

@@ -305,6 +305,167 @@ __global__ __launch_bounds__(256) void k_distinctive(const uint8_t *__restrict__
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// MapPoint::ComputeDistinctiveDescriptors on RESIDENT key frames (orbx_keyframe_distinctive_descriptors): observation o of a set is row obs_idx[o] of
+// mDescriptors of key frame obs_kf[o], read where the key frame keeps it -- nothing of a row is uploaded.  Every row is gathered once per set.
+//   record table   DistinctKf per key frame: descriptor base, count pointer, roff, capacity, kind.  Index i of a rig key frame (reference numbering,
+//                  left then right) is row i for i < N_left = count[0] and row roff + (i - N_left) from there on; the counts are read on the device, so
+//                  a key frame whose counts the host has not seen yet works the same.  An index outside [0, N) (or a key frame number outside the
+//                  table) forms no address: the row reads as zeros and *flag is raised.
+//   N <= 64        k_distinctive_kf, one wave per set: the set lives in registers, one row per lane.  Row i is broadcast (v_readlane: i is wave-uniform), lane j forms d(i, j), and the
+//                  kth smallest of the N lane values is selected bit by bit from bit 8 down (a distance is 0 .. 256): a ballot of the lanes still
+//                  in the running whose bit is 0, a population count, keep one half.  No LDS, no atomics; the running (median, first index) minimum is
+//                  wave-uniform.  9 ballots per row of the matrix against a 320-bin histogram (zeroed, filled, scanned) in k_distinctive.
+//   N > 64         k_distinctive_kf_large (below), one workgroup per set: the rows are gathered into the call's scratch (row o of it is observation o)
+//                  and k_distinctive's histogram runs on that copy, the rows of the matrix dealt to 16 waves.
+// k_distinctive_kf's first blocks also copy the key frames' counts into counts_out (where given): the host adopts them behind the call's synchronisation.
+// grid (max(ceil(n_sets / 4), ceil(n_kf / 256))), block 256
+// ---------------------------------------------------------------------------------------------------------
+constexpr int kDistinctRegisterRows = 64;
+struct DistinctKf { const uint8_t *desc; const int32_t *count; int32_t roff, cap, fisheye, pad; };
+struct DistinctSets {
+    const DistinctKf *kf; const int32_t *set_ptr, *obs_kf, *obs_idx;
+    int32_t *best_obs, *flag, *counts_out;   // counts_out: [n_kf][2] or NULL
+    uint8_t *best_desc, *scratch;            // best_desc: [n_sets][32] or NULL; scratch: [set_ptr[n_sets]][32], NULL if no set has more than 64 rows
+    int n_kf, n_sets;
+};
+
+// the four words of observation o's row; false (zeros): the observation names no row of a key frame of the table
+__device__ __forceinline__ bool distinct_gather(const DistinctSets &A, int o, u64 *w) {
+    w[0] = w[1] = w[2] = w[3] = 0;
+    const int k = gld(A.obs_kf + o), i = gld(A.obs_idx + o);
+    if ((unsigned)k >= (unsigned)A.n_kf) return false;
+    const DistinctKf *R = A.kf + k;
+    const int32_t *cnt = gld(&R->count);
+    const int roff = gld(&R->roff), cap = gld(&R->cap);
+    int n, row = i;
+    if (gld(&R->fisheye)) {   // clamped as orbx_keyframe::adopt clamps them
+        const int nl = min(max(gld(cnt), 0), roff), nr = min(max(gld(cnt + 1), 0), cap - roff);
+        n = nl + nr;
+        if (i >= nl) row = roff + (i - nl);
+    } else {
+        n = min(max(gld(cnt), 0), cap);
+    }
+    if ((unsigned)i >= (unsigned)n) return false;
+    const u64 *q = reinterpret_cast<const u64 *>(gld(&R->desc) + (size_t)row * 32);   // rows are 32-byte aligned
+    w[0] = gld(q); w[1] = gld(q + 1); w[2] = gld(q + 2); w[3] = gld(q + 3);
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_distinctive_kf(const DistinctSets A) {
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;   // (the set, its bounds and the medians: scalar registers)
+    const int gt = blockIdx.x * 256 + threadIdx.x;
+    if (A.counts_out && gt < A.n_kf) {
+        const int32_t *cnt = gld(&A.kf[gt].count);
+        gst(A.counts_out + 2 * gt, gld(cnt));
+        gst(A.counts_out + 2 * gt + 1, gld(&A.kf[gt].fisheye) ? gld(cnt + 1) : 0);
+    }
+    const int s = blockIdx.x * 4 + wv;
+    if (s >= A.n_sets) return;  // wave-uniform; no block barrier below
+    const int b = gld(A.set_ptr + s), N = gld(A.set_ptr + s + 1) - b;
+    if (N > kDistinctRegisterRows) return;   // k_distinctive_kf_large's
+    uint8_t *out = A.best_desc ? A.best_desc + (size_t)s * 32 : nullptr;
+    if (N <= 0) {
+        if (lane == 0) gst(A.best_obs + s, -1);
+        if (out && lane < 4) gst(reinterpret_cast<u64 *>(out) + lane, (u64)0);
+        return;
+    }
+    const int kth = (int)(0.5 * (N - 1));
+    int bestMedian = 0x7fffffff, bestIdx = 0;
+    u64 w[4] = {0, 0, 0, 0};
+    bool bad = false;
+    if (lane < N) bad = !distinct_gather(A, b + lane, w);
+    if (__ballot(bad) != 0ull && lane == 0) gst(A.flag, 1);
+    uint32_t r[8];
+#pragma unroll
+    for (int q = 0; q < 4; q++) { r[2 * q] = (uint32_t)w[q]; r[2 * q + 1] = (uint32_t)(w[q] >> 32); }
+    const u64 members = N == 64 ? ~0ull : (1ull << N) - 1ull;
+    for (int i = 0; i < N; i++) {
+        int d = 0;
+#pragma unroll
+        for (int q = 0; q < 8; q++) d += __popc(r[q] ^ (uint32_t)__builtin_amdgcn_readlane((int)r[q], i));
+        // the kth smallest of the members' d: from the top bit down, the members whose bit is 0 are the smaller half
+        u64 act = members;
+        int k = kth, med = 0;
+#pragma unroll
+        for (int bit = 8; bit >= 0; bit--) {
+            const u64 zeros = __ballot(((d >> bit) & 1) == 0) & act;
+            const int c = __popcll(zeros);
+            if (k < c) { act = zeros; } else { k -= c; act &= ~zeros; med |= 1 << bit; }
+        }
+        if (med < bestMedian) { bestMedian = med; bestIdx = i; }
+    }
+    if (lane == 0) gst(A.best_obs + s, bestIdx);
+    if (out && lane == bestIdx) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) gst(reinterpret_cast<u64 *>(out) + q, w[q]);
+    }
+}
+
+// the median of row i of the N x N matrix over the gathered rows D, by one wave: k_distinctive's 257-bin LDS histogram and prefix scan
+__device__ __forceinline__ int distinct_hist_median(int *hist, const uint8_t *D, int N, int i, int kth, int lane) {
+#pragma unroll
+    for (int q = 0; q < 5; q++) hist[lane * 5 + q] = 0;
+    __builtin_amdgcn_wave_barrier();
+    const Desc di = gld_desc(D + (size_t)i * 32);
+    for (int j = lane; j < N; j += 64) atomicAdd(&hist[hamming(di, gld_desc(D + (size_t)j * 32))], 1);
+    __builtin_amdgcn_wave_barrier();
+    int c[5], tot = 0;
+#pragma unroll
+    for (int q = 0; q < 5; q++) { c[q] = hist[lane * 5 + q]; tot += c[q]; }
+    int incl = tot;
+#pragma unroll
+    for (int sft = 1; sft < 64; sft <<= 1) {
+        const int t = __shfl_up(incl, sft);
+        if (lane >= sft) incl += t;
+    }
+    int excl = incl - tot, med = -1;
+    if (excl <= kth && kth < incl) {  // exactly one lane
+        int acc = excl;
+#pragma unroll
+        for (int q = 0; q < 5; q++) { if (med < 0 && kth < acc + c[q]) med = lane * 5 + q; acc += c[q]; }
+    }
+    const unsigned long long owner = __ballot(med >= 0);
+    med = __shfl(med, __ffsll((long long)owner) - 1);
+    __builtin_amdgcn_wave_barrier();
+    return med;
+}
+
+// The sets of more than kDistinctRegisterRows rows, one WORKGROUP of 16 waves per set (large_sets lists them): the rows are gathered into the scratch
+// once by all lanes, wave w takes rows w, w + 16, ... of the matrix, and the packed (median, row) minimum over the waves is the first minimum.
+// grid (number of large sets), block 1024
+constexpr int kDistinctLargeWaves = 16;
+__global__ __launch_bounds__(1024) void k_distinctive_kf_large(const DistinctSets A, const int32_t *__restrict__ large_sets) {
+    __shared__ int hist_all[kDistinctLargeWaves][320];
+    __shared__ u64 wave_best[kDistinctLargeWaves];
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int s = large_sets[blockIdx.x];
+    const int b = gld(A.set_ptr + s), N = gld(A.set_ptr + s + 1) - b;
+    uint8_t *D = A.scratch + (size_t)b * 32;
+    bool bad = false;
+    for (int j = threadIdx.x; j < N; j += 64 * kDistinctLargeWaves) {
+        u64 w[4];
+        bad |= !distinct_gather(A, b + j, w);
+#pragma unroll
+        for (int q = 0; q < 4; q++) gst(reinterpret_cast<u64 *>(D + (size_t)j * 32) + q, w[q]);
+    }
+    if (__ballot(bad) != 0ull && lane == 0) gst(A.flag, 1);
+    __syncthreads();   // (also the fence that makes the gathered rows visible to the workgroup)
+    const int kth = (int)(0.5 * (N - 1));
+    u64 best = kNoKey;
+    for (int i = wv; i < N; i += kDistinctLargeWaves) {
+        const u64 key = ((u64)(uint32_t)distinct_hist_median(hist_all[wv], D, N, i, kth, lane) << 32) | (u64)(uint32_t)i;
+        best = key < best ? key : best;
+    }
+    if (lane == 0) wave_best[wv] = best;
+    __syncthreads();
+    if (wv != 0) return;
+    const int bestIdx = (int)(wave_min1(lane < kDistinctLargeWaves ? wave_best[lane] : kNoKey) & 0xffffffffu);
+    if (lane == 0) gst(A.best_obs + s, bestIdx);
+    if (A.best_desc && lane < 4)
+        gst(reinterpret_cast<u64 *>(A.best_desc + (size_t)s * 32) + lane, gld(reinterpret_cast<const u64 *>(D + (size_t)bestIdx * 32) + lane));
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // DBoW2 TemplatedVocabulary::transform(feature, word_id, weight, nid, levelsup) (TemplatedVocabulary.h:1206-1250):
 // descend the k-ary vocabulary tree, at every level to the child with the smallest Hamming distance (strict '<': the
 // first minimum in m_nodes[i].children order wins).  16 lanes per feature; lanes stride the children of the current

@@ -3604,6 +3604,74 @@ int orbx_keyframe_compute_bow_fisheye(orbx_matcher *m, orbx_keyframe *kf, const 
 int orbx_keyframe_bow_from_frame(orbx_matcher *m, orbx_keyframe *kf, orbx_frame *f) { return keyframe_bow_from_frame(m, false, kf, f); }
 int orbx_keyframe_bow_from_frame_fisheye(orbx_matcher *m, orbx_keyframe *kf, orbx_frame *f) { return keyframe_bow_from_frame(m, true, kf, f); }
 
+// MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403) for a batch of map points whose observations are rows of resident key frames of either
+// kind: k_distinctive_kf (sets of up to 64 rows) and k_distinctive_kf_large gather the rows through a record per key frame.  One upload run (set_ptr, the
+// two index arrays, the records, the list of large sets), one launch per kernel, one download run (best_obs, the flag, best_desc, the counts of key
+// frames that still had them on the device), one synchronisation.
+int orbx_keyframe_distinctive_descriptors(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, int n_sets, const int32_t *set_ptr, const int32_t *obs_kf,
+                                          const int32_t *obs_idx, int32_t *best_obs, uint8_t *best_desc) {
+    if (!m || n_kf < 0 || n_sets < 0 || (n_kf > 0 && !kfs) || (n_sets > 0 && (!set_ptr || !best_obs))) return ORBX_E_BAD_ARG;
+    if (n_kf > ORBX_MAX_DISTINCTIVE_KEYFRAMES) return ORBX_E_TOO_LARGE;
+    if (n_sets == 0) return ORBX_OK;
+    // everything is checked before anything is enqueued
+    if (set_ptr[0] < 0) return ORBX_E_BAD_ARG;
+    std::vector<int32_t> large;   // the sets k_distinctive_kf_large takes
+    for (int s = 0; s < n_sets; s++) {
+        if (set_ptr[s + 1] < set_ptr[s]) return ORBX_E_BAD_ARG;
+        if (set_ptr[s + 1] - set_ptr[s] > kDistinctRegisterRows) large.push_back(s);
+    }
+    const size_t total = (size_t)set_ptr[n_sets];
+    if (total > 0 && (!obs_kf || !obs_idx)) return ORBX_E_BAD_ARG;
+    bool pending = false;
+    for (int k = 0; k < n_kf; k++) {
+        if (!kfs[k] || kfs[k]->device != m->device) return ORBX_E_BAD_ARG;
+        pending |= kfs[k]->host_n() < 0;
+    }
+    for (size_t o = (size_t)set_ptr[0]; o < total; o++) {
+        if (obs_kf[o] < 0 || obs_kf[o] >= n_kf) return ORBX_E_BAD_ARG;
+        if (obs_idx[o] < 0 || obs_idx[o] >= kfs[obs_kf[o]]->rows_n()) return ORBX_E_BAD_ARG;   // (counts pending: the capacity; the kernel checks against N)
+    }
+    if (total == (size_t)set_ptr[0]) {   // empty sets only
+        for (int s = 0; s < n_sets; s++) best_obs[s] = -1;
+        if (best_desc) memset(best_desc, 0, 32 * (size_t)n_sets);
+        return ORBX_OK;
+    }
+    ORBX_HIP(hipSetDevice(m->device));
+    std::vector<DistinctKf> recs((size_t)n_kf);
+    for (int k = 0; k < n_kf; k++) recs[k] = DistinctKf{kfs[k]->desc, kfs[k]->count, kfs[k]->roff, kfs[k]->cap, kfs[k]->fisheye ? 1 : 0, 0};
+    DistinctSets A;
+    memset(&A, 0, sizeof(A));
+    A.n_kf = n_kf; A.n_sets = n_sets;
+    const int32_t *dlarge = nullptr;
+    ORBX_TRY(m->carve([&](Carve &C) {
+        A.set_ptr = C.up(set_ptr, (size_t)n_sets + 1); A.obs_kf = C.up(obs_kf, total); A.obs_idx = C.up(obs_idx, total);
+        A.kf = C.up(recs.data(), (size_t)n_kf);
+        if (!large.empty()) dlarge = C.up(large.data(), large.size());
+        A.best_obs = C.take<int32_t>(n_sets); A.flag = C.take<int32_t>(4);   // (best_obs between the uploads and the flag's fill: one k_xfer launch for both)
+        if (best_desc) A.best_desc = C.take<uint8_t>(32 * (size_t)n_sets);
+        if (pending) A.counts_out = C.take<int32_t>(2 * (size_t)n_kf);
+        if (!large.empty()) A.scratch = C.take<uint8_t>(32 * total);
+    }));
+    ORBX_HIP(m->fill(A.flag, 0, 16));
+    ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
+    const unsigned grid = (unsigned)std::max((n_sets + 3) / 4, (n_kf + 255) / 256);
+    hipLaunchKernelGGL(k_distinctive_kf, dim3(grid), dim3(256), 0, m->exec(), A);
+    if (!large.empty()) hipLaunchKernelGGL(k_distinctive_kf_large, dim3((unsigned)large.size()), dim3(64 * kDistinctLargeWaves), 0, m->exec(), A, dlarge);
+    ORBX_HIP(hipGetLastError());
+    int32_t flag = 0;
+    std::vector<int32_t> counts(pending ? 2 * (size_t)n_kf : 0);
+    ORBX_TRY(m->d2h(best_obs, A.best_obs, 4 * (size_t)n_sets));
+    ORBX_TRY(m->d2h(&flag, A.flag, 4));
+    if (best_desc) ORBX_TRY(m->d2h(best_desc, A.best_desc, 32 * (size_t)n_sets));
+    if (pending) ORBX_TRY(m->d2h(counts.data(), A.counts_out, 8 * (size_t)n_kf));
+    ORBX_TRY(m->sync_and_deliver());
+    keyframe_release(kfs, n_kf);
+    for (int k = 0; pending && k < n_kf; k++)
+        if (kfs[k]->host_n() < 0) kfs[k]->adopt(counts[2 * (size_t)k], counts[2 * (size_t)k + 1]);
+    if (flag) { set_error("an observation index outside [0, N) of its key frame"); return ORBX_E_BAD_ARG; }
+    return ORBX_OK;
+}
+
 }  // extern "C"
 
 namespace {

@@ -856,6 +856,20 @@ class ORBmatcher:
         check(self._L.orbx_distinctive_descriptors(self._h, ptr(d), ptr(sp), len(sp) - 1, ptr(out)), "orbx_distinctive_descriptors")
         return out
 
+    def DistinctiveDescriptorsKeyFrames(self, kfs, set_ptr, obs_kf, obs_idx, want_desc: bool = True):
+        """ComputeDistinctiveDescriptors with the observations named where they are (orbx_keyframe_distinctive_descriptors): observation o of set s,
+        o in [set_ptr[s], set_ptr[s+1]), is row obs_idx[o] of mDescriptors of the DeviceKeyFrame kfs[obs_kf[o]] (both kinds may be mixed; a rig key
+        frame in its own numbering, left then right).  No row is uploaded.  Returns (best_obs[n_sets]: the winner's position inside its set, -1 for
+        an empty set; best_desc[n_sets, 32]: the winning rows, zeros for an empty set, or None)."""
+        sp, ok, oi = _i32(set_ptr), _i32(obs_kf), _i32(obs_idx)
+        n_sets = len(sp) - 1
+        assert n_sets >= 0 and len(ok) == len(oi) and (n_sets == 0 or sp[-1] <= len(ok))
+        best = np.full(n_sets, -1, np.int32)
+        desc = np.zeros((n_sets, 32), np.uint8) if want_desc else None
+        check(self._L.orbx_keyframe_distinctive_descriptors(self._h, len(kfs), self._kf_handles(kfs), n_sets, ptr(sp), ptr(ok), ptr(oi), ptr(best),
+                                                            ptr(desc)), "orbx_keyframe_distinctive_descriptors")
+        return best, desc
+
     # ---- matching core of Fuse x2 (ORBmatcher.cc:1148-1455) ----
     def FuseSearch(self, KF: FrameView, q: dict, inv_level_sigma2=None, strict_fp: bool = False):
         """q: u, v, ur, r, level, desc.  Returns (best_idx[nq], best_dist[nq])."""
