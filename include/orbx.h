@@ -1049,6 +1049,87 @@ int orbx_keyframe_fuse_map_points_sim3_fisheye(orbx_matcher *m, int n_kf, orbx_k
 int orbx_keyframe_distinctive_descriptors(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, int n_sets, const int32_t *set_ptr,
                                           const int32_t *obs_kf, const int32_t *obs_idx, int32_t *best_obs, uint8_t *best_desc);
 
+/* ---- Device-resident map points.  An orbx_map is a table of `capacity` slots on one device, one 64-byte record per slot: what the one-call searches
+ * read of a MapPoint -- mWorldPos (pos), mNormalVector (normal), mfMinDistance / mfMaxDistance as GetMinDistanceInvariance() /
+ * GetMaxDistanceInvariance() return them (min_dist, max_dist) and mDescriptor (desc, 32 bytes).  The caller addresses a slot by an id in
+ * [0, capacity) that it assigns itself (one int in MapPoint).  A table is device-wide like a key frame: every matcher context of its device may write
+ * and read it (a context of another device: ORBX_E_BAD_ARG).  The `_map` forms of the eight one-call searches below take (map, ids) where the flat
+ * forms take pos, normal, min_dist, max_dist, mp_desc: 4 bytes per point go up instead of 64.
+ *   orbx_map_create: capacity in [1, ORBX_MAX_MAP_POINTS] (ORBX_E_TOO_LARGE beyond, ORBX_E_BAD_ARG below 1); ORBX_E_HIP if the allocation fails.  No
+ *     slot is live.
+ *   orbx_map_update: writes row j of the given arrays into slot ids[j], j < n.  Any of the five field pointers may be NULL: that field of the
+ *     slots keeps its value.  The first update of a slot (and the first after orbx_map_erase) must give all five: ORBX_E_BAD_ARG otherwise.  An id may
+ *     be named once per call: a duplicate is refused with ORBX_E_BAD_ARG (a parallel scatter has no "last wins").  One upload run in m's arena, one
+ *     launch (k_map_scatter); returns WITHOUT waiting.  n = 0: ORBX_OK.
+ *   orbx_map_erase: MapPoint::SetBadFlag -- host bookkeeping only: the slots stop being live, and every call that names one is refused until an
+ *     update has written it whole again.  All ids are checked first (each in [0, capacity) and live); n = 0: ORBX_OK.
+ *   orbx_map_read: slot ids[j] -> row j of the outputs that are not NULL; one gather, one download run, one synchronisation.  For tests,
+ *     serialization and debugging.  The same id may appear more than once.
+ * Every call that takes ids checks them BEFORE anything is enqueued and before a transfer counter moves: ids not NULL when n > 0, each in
+ * [0, capacity), its slot live, the map on m's device; a refused call changes neither the table nor the context (ORBX_E_BAD_ARG).
+ * Ordering.  The table holds one event, `written`.  An update (orbx_map_update, orbx_keyframe_distinctive_descriptors_to_map) makes its context's
+ * stream wait for the previous `written`, launches and records the next one; every call that reads the table makes its stream wait for `written`
+ * ahead of its gather, until a reading call that did so has synchronised.  So updates and reads issued one after the other, from any contexts and
+ * threads, take effect in the order of the calls, and no host synchronisation is needed between an update and the search that follows it.
+ * What the library does NOT order is a write against reads that are still RUNNING: as under the reference's Map::mMutexMapUpdate, the caller does not
+ * run orbx_map_update / orbx_map_erase / ..._to_map on a table concurrently with a call that reads that table.  Every reading call ends in a
+ * synchronisation, so once it has returned its reads are done.  Destroy a table before the matchers that used it and after every call that names it
+ * has returned; orbx_map_destroy waits for `written`. */
+typedef struct orbx_map orbx_map;
+#define ORBX_MAX_MAP_POINTS (1 << 24)   /* 1 GiB of records */
+int orbx_map_create(int device, int capacity, orbx_map **out);
+void orbx_map_destroy(orbx_map *map);
+int orbx_map_update(orbx_matcher *m, orbx_map *map, int n, const int32_t *ids, const float *pos, const float *normal, const float *min_dist,
+                    const float *max_dist, const uint8_t *desc);
+int orbx_map_erase(orbx_map *map, int n, const int32_t *ids);
+int orbx_map_read(orbx_matcher *m, orbx_map *map, int n, const int32_t *ids, float *pos, float *normal, float *min_dist, float *max_dist,
+                  uint8_t *desc);
+
+/* The one-call searches with their map points named by id.  Each takes its flat form's arguments with (pos, normal, min_dist, max_dist, mp_desc)
+ * replaced by (map, ids [n_mp]) and returns what the flat form returns for the rows of those slots, bit for bit.  The per-point arrays that are not
+ * part of the table stay positional -- eligible, has_obs, skip, track_depth in, in_view, projected, proj_u / proj_v out: entry j belongs to ids[j] --
+ * and every output indexes POSITIONS in ids, never ids.  The same id may appear twice: two queries with equal data, as the flat form given one row
+ * twice.  Cost shape as the flat form -- one upload run (the ids lead it), one download run, one synchronisation, a launch chain independent of n_kf --
+ * plus ONE launch, k_map_gather, which fills the flat form's five device arrays behind the wait for `written`. */
+int orbx_frame_search_local_points_map(orbx_matcher *m, orbx_frame *frame, const uint8_t *frame_occupied, const orbx_camera *cam,
+                                       const orbx_frame_pose *pose, float log_scale_factor, float viewing_cos_limit, int n_mp, orbx_map *map,
+                                       const int32_t *ids, const uint8_t *eligible, const uint8_t *has_obs, float th, float nnratio, int far_points,
+                                       float th_far_points, uint8_t *in_view, int32_t *frame_match);
+int orbx_frame_search_local_points_fisheye_map(orbx_matcher *m, orbx_frame *frame, const uint8_t *frame_occupied, const orbx_fisheye_view *views,
+                                               float log_scale_factor, float viewing_cos_limit, int n_mp, orbx_map *map, const int32_t *ids,
+                                               const uint8_t *eligible, const uint8_t *has_obs, const float *track_depth, float th, float nnratio,
+                                               int far_points, float th_far_points, uint8_t *in_view, int32_t *frame_match);
+int orbx_keyframe_fuse_map_points_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams, const orbx_frame_pose *poses,
+                                      float th, float log_scale_factor, int strict_fp, int n_mp, orbx_map *map, const int32_t *ids,
+                                      const uint8_t *skip, int32_t *best_idx, int32_t *best_dist, uint8_t *projected);
+int orbx_keyframe_fuse_map_points_fisheye_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views, float th,
+                                              float log_scale_factor, int strict_fp, int n_mp, orbx_map *map, const int32_t *ids, const uint8_t *skip,
+                                              int32_t *best_idx, int32_t *best_dist, uint8_t *projected);
+int orbx_keyframe_fuse_map_points_sim3_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams, const orbx_frame_pose *poses,
+                                           float th, float log_scale_factor, int n_mp, orbx_map *map, const int32_t *ids, const uint8_t *skip,
+                                           int32_t *best_idx, int32_t *best_dist, uint8_t *projected);
+int orbx_keyframe_fuse_map_points_sim3_fisheye_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views, float th,
+                                                   float log_scale_factor, int n_mp, orbx_map *map, const int32_t *ids, const uint8_t *skip,
+                                                   int32_t *best_idx, int32_t *best_dist, uint8_t *projected);
+int orbx_keyframe_search_by_projection_sim3_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
+                                                const orbx_frame_pose *poses, float th, float ratio_hamming, float log_scale_factor,
+                                                int projection_form, int n_mp, orbx_map *map, const int32_t *ids, const uint8_t *skip,
+                                                const uint8_t *const *occupied, int32_t *const *match, int32_t *nmatches, uint8_t *projected,
+                                                float *proj_u, float *proj_v);
+int orbx_keyframe_search_by_projection_sim3_fisheye_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views, float th,
+                                                        float ratio_hamming, float log_scale_factor, int projection_form, int n_mp, orbx_map *map,
+                                                        const int32_t *ids, const uint8_t *skip, const uint8_t *const *occupied,
+                                                        int32_t *const *match, int32_t *nmatches, uint8_t *projected, float *proj_u, float *proj_v);
+
+/* orbx_keyframe_distinctive_descriptors with the winning rows written straight into the table: the same sets, the same two kernels and the same
+ * result run (best_obs -- mDescriptor's provenance -- still comes home), then k_map_scatter_desc writes set s's winning row into the descriptor of
+ * slot set_id[s], ordered as an update.  An empty set (best_obs = -1) leaves its slot untouched.  set_id [n_sets] must name live slots without
+ * duplicates (ORBX_E_BAD_ARG before anything is enqueued).  If the kernel finds an index outside [0, N) of a key frame with pending counts, NOTHING
+ * is written to the table and the call returns ORBX_E_BAD_ARG as orbx_keyframe_distinctive_descriptors does. */
+int orbx_keyframe_distinctive_descriptors_to_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, int n_sets, const int32_t *set_ptr,
+                                                 const int32_t *obs_kf, const int32_t *obs_idx, orbx_map *map, const int32_t *set_id,
+                                                 int32_t *best_obs);
+
 /* Frame::ComputeStereoMatches (Frame.cc:811-981) for every frame of two resident batches: `left` and `right` must have
  * extracted batches of the same size and image shape (rectified stereo, lapping {0,0}).  Row-band Hamming match, 11x11
  * SAD sub-pixel refinement on the device-resident pyramids and the median outlier rejection all run on the device, on

@@ -128,6 +128,7 @@ class FuseQueries(C.Structure):
 MAX_FUSE_KEYFRAMES = 256   # ORBX_MAX_FUSE_KEYFRAMES
 SIM3_PROJECT_CAMERA, SIM3_PROJECT_INVZ = 0, 1   # ORBX_SIM3_PROJECT_CAMERA (Pinhole::project), ORBX_SIM3_PROJECT_INVZ (ORBmatcher.cc:573-578)
 MAX_DISTINCTIVE_KEYFRAMES = 4096   # ORBX_MAX_DISTINCTIVE_KEYFRAMES
+MAX_MAP_POINTS = 1 << 24   # ORBX_MAX_MAP_POINTS
 
 
 class KeyFrameGate(C.Structure):
@@ -180,6 +181,12 @@ SYMBOLS = [
     "orbx_keyframe_search_by_projection_sim3", "orbx_keyframe_fuse_map_points_sim3",
     "orbx_keyframe_search_by_projection_sim3_fisheye", "orbx_keyframe_fuse_map_points_sim3_fisheye",
     "orbx_keyframe_distinctive_descriptors",
+    "orbx_map_create", "orbx_map_destroy", "orbx_map_update", "orbx_map_erase", "orbx_map_read",
+    "orbx_frame_search_local_points_map", "orbx_frame_search_local_points_fisheye_map",
+    "orbx_keyframe_fuse_map_points_map", "orbx_keyframe_fuse_map_points_fisheye_map",
+    "orbx_keyframe_fuse_map_points_sim3_map", "orbx_keyframe_fuse_map_points_sim3_fisheye_map",
+    "orbx_keyframe_search_by_projection_sim3_map", "orbx_keyframe_search_by_projection_sim3_fisheye_map",
+    "orbx_keyframe_distinctive_descriptors_to_map",
 ]
 
 
@@ -319,6 +326,26 @@ def lib() -> C.CDLL:
                                                                   C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp]
     L.orbx_keyframe_fuse_map_points_sim3_fisheye.argtypes = [vp, i32, C.POINTER(vp), vp, f32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbx_keyframe_distinctive_descriptors.argtypes = [vp, i32, C.POINTER(vp), i32, vp, vp, vp, vp, vp]
+    L.orbx_map_create.argtypes = [i32, i32, C.POINTER(vp)]
+    L.orbx_map_destroy.argtypes = [vp]
+    L.orbx_map_destroy.restype = None
+    L.orbx_map_update.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.orbx_map_erase.argtypes = [vp, i32, vp]
+    L.orbx_map_read.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    L.orbx_frame_search_local_points_map.argtypes = [vp, vp, vp, C.POINTER(Camera), C.POINTER(FramePose), f32, f32, i32, vp, vp, vp, vp,
+                                                     f32, f32, i32, f32, vp, vp]
+    L.orbx_frame_search_local_points_fisheye_map.argtypes = [vp, vp, vp, vp, f32, f32, i32] + [vp] * 5 + [f32, f32, i32, f32, vp, vp]
+    L.orbx_keyframe_fuse_map_points_map.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(Camera), C.POINTER(FramePose), f32, f32, i32, i32, vp, vp, vp, vp,
+                                                    vp, vp]
+    L.orbx_keyframe_fuse_map_points_fisheye_map.argtypes = [vp, i32, C.POINTER(vp), vp, f32, f32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.orbx_keyframe_fuse_map_points_sim3_map.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(Camera), C.POINTER(FramePose), f32, f32, i32, vp, vp, vp, vp,
+                                                         vp, vp]
+    L.orbx_keyframe_fuse_map_points_sim3_fisheye_map.argtypes = [vp, i32, C.POINTER(vp), vp, f32, f32, i32, vp, vp, vp, vp, vp, vp]
+    L.orbx_keyframe_search_by_projection_sim3_map.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(Camera), C.POINTER(FramePose), f32, f32, f32, i32, i32,
+                                                              vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp]
+    L.orbx_keyframe_search_by_projection_sim3_fisheye_map.argtypes = [vp, i32, C.POINTER(vp), vp, f32, f32, f32, i32, i32, vp, vp, vp,
+                                                                      C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp]
+    L.orbx_keyframe_distinctive_descriptors_to_map.argtypes = [vp, i32, C.POINTER(vp), i32, vp, vp, vp, vp, vp, vp]
     L.orbx_keyframe_from_frame_fisheye.argtypes = [vp, vp, vp, C.POINTER(vp)]
     L.orbx_keyframe_create_host_fisheye.argtypes = [vp, C.POINTER(FrameDesc), vp, i32, vp, C.POINTER(vp)]
     L.orbx_keyframe_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

@@ -152,6 +152,36 @@ private:
     bool fisheye_ = false;
 };
 
+// A device-resident table of map points (orbx_map): what the one-call searches read of a MapPoint -- GetWorldPos(), GetNormal(), mfMinDistance,
+// mfMaxDistance, mDescriptor -- in `capacity` slots addressed by ids the caller assigns (one int in MapPoint).  It belongs to no matcher: every
+// ORBmatcher of its device may update and read it, and the ...Map overloads of ORBmatcher take (map, ids) where the others take the five arrays.
+// update() after SetWorldPos / UpdateNormalAndDepth / a bundle adjustment's write-back, erase() at SetBadFlag; the caller does not run either
+// concurrently with a call that reads the table (Map::mMutexMapUpdate).  Destroy it only when no call that was handed it is running.
+class DeviceMap {
+public:
+    explicit DeviceMap(int capacity, int device = 0) {
+        const int st = orbx_map_create(device, capacity, &map_);
+        if (st < 0) throw std::runtime_error(std::string("orbx_map_create: ") + orbx_status_string(st) + " " + orbx_last_error());
+    }
+    ~DeviceMap() { orbx_map_destroy(map_); }
+    DeviceMap(const DeviceMap &) = delete;
+    DeviceMap &operator=(const DeviceMap &) = delete;
+    // row j of the arrays that are given (NULL: that field keeps its value) -> slot ids[j]; a slot's first update gives all five.  Does not wait.
+    inline void update(ORBmatcher &matcher, const std::vector<int32_t> &ids, const float *pos, const float *normal, const float *minDistance,
+                       const float *maxDistance, const uint8_t *descriptors);
+    void erase(const std::vector<int32_t> &ids) {
+        const int st = orbx_map_erase(map_, (int)ids.size(), ids.data());
+        if (st < 0) throw std::runtime_error(std::string("orbx_map_erase: ") + orbx_status_string(st));
+    }
+    // slot ids[j] -> row j of the outputs that are given; one synchronisation (tests, serialization, debugging)
+    inline void read(ORBmatcher &matcher, const std::vector<int32_t> &ids, float *pos, float *normal, float *minDistance, float *maxDistance,
+                     uint8_t *descriptors);
+    orbx_map *handle() const { return map_; }
+
+private:
+    orbx_map *map_ = nullptr;
+};
+
 class ORBmatcher {
 public:
     static const int TH_LOW = ORBX_TH_LOW;
@@ -799,6 +829,136 @@ public:
         return nFound;
     }
 
+    // ---- The one-call searches with their map points resident (DeviceMap): ids[j] names the slot of map point j; eligible / hasObservations / skip /
+    // trackDepth, inView and projected stay positional (entry j belongs to ids[j]) and every output indexes POSITIONS in ids.  Results as the
+    // overloads that take the arrays, given the slots' rows.
+    int SearchLocalPoints(DeviceFrame &F, const std::vector<uint8_t> &occupied, const orbx_camera &cam, const orbx_frame_pose &pose, float logScaleFactor,
+                          float viewingCosLimit, const DeviceMap &map, const std::vector<int32_t> &ids, const std::vector<uint8_t> &eligible,
+                          const std::vector<uint8_t> &hasObservations, float th, bool bFarPoints, float thFarPoints, std::vector<uint8_t> &inView,
+                          std::vector<int32_t> &vpMatch) {
+        inView.assign(ids.size(), 0);
+        vpMatch.assign(F.count(), -1);
+        const int r = orbx_frame_search_local_points_map(m_, F.handle(), occupied.empty() ? nullptr : occupied.data(), &cam, &pose, logScaleFactor,
+                                                         viewingCosLimit, (int)ids.size(), map.handle(), ids.data(),
+                                                         eligible.empty() ? nullptr : eligible.data(), hasObservations.empty() ? nullptr : hasObservations.data(),
+                                                         th, mfNNratio, bFarPoints ? 1 : 0, thFarPoints, inView.data(), vpMatch.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_local_points_map: ") + orbx_status_string(r));
+        return r;
+    }
+    int SearchLocalPointsFisheye(DeviceFrame &F, const std::vector<uint8_t> &occupied, const orbx_fisheye_view views[2], float logScaleFactor,
+                                 float viewingCosLimit, const DeviceMap &map, const std::vector<int32_t> &ids, const std::vector<uint8_t> &eligible,
+                                 const std::vector<uint8_t> &hasObservations, const std::vector<float> &trackDepth, float th, bool bFarPoints,
+                                 float thFarPoints, std::vector<uint8_t> &inView, std::vector<int32_t> &vpMatch) {
+        inView.assign(2 * ids.size(), 0);
+        vpMatch.assign(F.count(), -1);
+        const int r = orbx_frame_search_local_points_fisheye_map(
+            m_, F.handle(), occupied.empty() ? nullptr : occupied.data(), views, logScaleFactor, viewingCosLimit, (int)ids.size(), map.handle(), ids.data(),
+            eligible.empty() ? nullptr : eligible.data(), hasObservations.empty() ? nullptr : hasObservations.data(),
+            trackDepth.empty() ? nullptr : trackDepth.data(), th, mfNNratio, bFarPoints ? 1 : 0, thFarPoints, inView.data(), vpMatch.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_local_points_fisheye_map: ") + orbx_status_string(r));
+        return r;
+    }
+    void FuseMapPoints(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<orbx_camera> &cams, const std::vector<orbx_frame_pose> &poses,
+                       const DeviceMap &map, const std::vector<int32_t> &ids, const std::vector<uint8_t> &skip, float th, float logScaleFactor,
+                       std::vector<int32_t> &bestIdx, std::vector<int32_t> &bestDist, std::vector<uint8_t> *projected = nullptr, bool strictFloat = false) {
+        const size_t K = vpKFs.size(), n = ids.size();
+        if (cams.size() != K || poses.size() != K) throw std::invalid_argument("FuseMapPoints: one camera and pose per key frame");
+        const std::vector<orbx_keyframe *> h = mapCallHandles(vpKFs, K, n, skip, bestIdx, bestDist, projected);
+        const int r = orbx_keyframe_fuse_map_points_map(m_, (int)K, h.data(), cams.data(), poses.data(), th, logScaleFactor, strictFloat ? 1 : 0, (int)n,
+                                                        map.handle(), ids.data(), skip.empty() ? nullptr : skip.data(), bestIdx.data(), bestDist.data(),
+                                                        projected ? projected->data() : nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_fuse_map_points_map: ") + orbx_status_string(r));
+    }
+    // views: 2 K entries (left, right per key frame); bestIdx / bestDist / projected [K][2][n]
+    void FuseMapPointsFisheye(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<orbx_fisheye_view> &views, const DeviceMap &map,
+                              const std::vector<int32_t> &ids, const std::vector<uint8_t> &skip, float th, float logScaleFactor,
+                              std::vector<int32_t> &bestIdx, std::vector<int32_t> &bestDist, std::vector<uint8_t> *projected = nullptr,
+                              bool strictFloat = false) {
+        const size_t K = vpKFs.size(), n = ids.size();
+        if (views.size() != 2 * K) throw std::invalid_argument("FuseMapPointsFisheye: a left and a right view per key frame");
+        const std::vector<orbx_keyframe *> h = mapCallHandles(vpKFs, K, n, skip, bestIdx, bestDist, projected, 2);
+        const int r = orbx_keyframe_fuse_map_points_fisheye_map(m_, (int)K, h.data(), views.data(), th, logScaleFactor, strictFloat ? 1 : 0, (int)n,
+                                                                map.handle(), ids.data(), skip.empty() ? nullptr : skip.data(), bestIdx.data(),
+                                                                bestDist.data(), projected ? projected->data() : nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_fuse_map_points_fisheye_map: ") + orbx_status_string(r));
+    }
+    void FuseMapPointsSim3(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<orbx_camera> &cams, const std::vector<orbx_frame_pose> &poses,
+                           const DeviceMap &map, const std::vector<int32_t> &ids, const std::vector<uint8_t> &skip, float th, float logScaleFactor,
+                           std::vector<int32_t> &bestIdx, std::vector<int32_t> &bestDist, std::vector<uint8_t> *projected = nullptr) {
+        const size_t K = vpKFs.size(), n = ids.size();
+        if (cams.size() != K || poses.size() != K) throw std::invalid_argument("FuseMapPointsSim3: one camera and pose per key frame");
+        const std::vector<orbx_keyframe *> h = mapCallHandles(vpKFs, K, n, skip, bestIdx, bestDist, projected);
+        const int r = orbx_keyframe_fuse_map_points_sim3_map(m_, (int)K, h.data(), cams.data(), poses.data(), th, logScaleFactor, (int)n, map.handle(),
+                                                             ids.data(), skip.empty() ? nullptr : skip.data(), bestIdx.data(), bestDist.data(),
+                                                             projected ? projected->data() : nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_fuse_map_points_sim3_map: ") + orbx_status_string(r));
+    }
+    void FuseMapPointsSim3Fisheye(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<orbx_fisheye_view> &views, const DeviceMap &map,
+                                  const std::vector<int32_t> &ids, const std::vector<uint8_t> &skip, float th, float logScaleFactor,
+                                  std::vector<int32_t> &bestIdx, std::vector<int32_t> &bestDist, std::vector<uint8_t> *projected = nullptr) {
+        const size_t K = vpKFs.size(), n = ids.size();
+        if (views.size() != K) throw std::invalid_argument("FuseMapPointsSim3Fisheye: one (left) view per key frame");
+        const std::vector<orbx_keyframe *> h = mapCallHandles(vpKFs, K, n, skip, bestIdx, bestDist, projected);
+        const int r = orbx_keyframe_fuse_map_points_sim3_fisheye_map(m_, (int)K, h.data(), views.data(), th, logScaleFactor, (int)n, map.handle(), ids.data(),
+                                                                     skip.empty() ? nullptr : skip.data(), bestIdx.data(), bestDist.data(),
+                                                                     projected ? projected->data() : nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_fuse_map_points_sim3_fisheye_map: ") + orbx_status_string(r));
+    }
+    // cams / poses [K] of monocular key frames, or (cams empty) views [K] of rig key frames: orbx_keyframe_search_by_projection_sim3[_fisheye]_map
+    void SearchByProjectionSim3KeyFrames(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<orbx_camera> &cams,
+                                         const std::vector<orbx_frame_pose> &poses, const std::vector<orbx_fisheye_view> &views, const DeviceMap &map,
+                                         const std::vector<int32_t> &ids, const std::vector<uint8_t> &skip, const std::vector<std::vector<uint8_t>> &occupied,
+                                         float th, float ratioHamming, float logScaleFactor, int projectionForm, std::vector<std::vector<int32_t>> &vpMatch,
+                                         std::vector<int> &vnMatches, std::vector<uint8_t> *projected = nullptr) {
+        const size_t K = vpKFs.size(), n = ids.size();
+        const bool rig = cams.empty() && K > 0;
+        if ((rig ? views.size() != K : cams.size() != K || poses.size() != K) || (!skip.empty() && skip.size() != K * n) ||
+            (!occupied.empty() && occupied.size() != K))
+            throw std::invalid_argument("SearchByProjectionSim3KeyFrames: one camera and pose (or one view) per key frame, K x n skip flags, K occupancy rows");
+        std::vector<orbx_keyframe *> h(K);
+        std::vector<const uint8_t *> occ(K, nullptr);
+        std::vector<int32_t *> rows(K);
+        std::vector<int32_t> nm(K, 0);
+        vpMatch.assign(K, {});
+        for (size_t k = 0; k < K; k++) {
+            h[k] = vpKFs[k]->handle();
+            const size_t N = (size_t)vpKFs[k]->count();
+            if (!occupied.empty() && !occupied[k].empty()) {
+                if (occupied[k].size() != N) throw std::invalid_argument("SearchByProjectionSim3KeyFrames: an occupancy row holds N_k flags");
+                occ[k] = occupied[k].data();
+            }
+            vpMatch[k].assign(N + 1, -1);   // (+ 1: data() of an empty row may be NULL, which the call refuses)
+            rows[k] = vpMatch[k].data();
+        }
+        if (projected) projected->assign(K * n, 0);
+        const int r = rig ? orbx_keyframe_search_by_projection_sim3_fisheye_map(m_, (int)K, h.data(), views.data(), th, ratioHamming, logScaleFactor,
+                                                                                projectionForm, (int)n, map.handle(), ids.data(),
+                                                                                skip.empty() ? nullptr : skip.data(), occupied.empty() ? nullptr : occ.data(),
+                                                                                rows.data(), nm.data(), projected ? projected->data() : nullptr, nullptr, nullptr)
+                          : orbx_keyframe_search_by_projection_sim3_map(m_, (int)K, h.data(), cams.data(), poses.data(), th, ratioHamming, logScaleFactor,
+                                                                        projectionForm, (int)n, map.handle(), ids.data(),
+                                                                        skip.empty() ? nullptr : skip.data(), occupied.empty() ? nullptr : occ.data(),
+                                                                        rows.data(), nm.data(), projected ? projected->data() : nullptr, nullptr, nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_search_by_projection_sim3_map: ") + orbx_status_string(r));
+        for (size_t k = 0; k < K; k++) vpMatch[k].pop_back();
+        vnMatches.assign(nm.begin(), nm.end());
+    }
+    // ComputeDistinctiveDescriptors with map point s's winning row written into the descriptor of slot setId[s]
+    // (orbx_keyframe_distinctive_descriptors_to_map); a map point without observations keeps its descriptor.  bestObs as the overload above.
+    void ComputeDistinctiveDescriptors(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<int32_t> &setPtr, const std::vector<int32_t> &obsKf,
+                                       const std::vector<int32_t> &obsIdx, const DeviceMap &map, const std::vector<int32_t> &setId,
+                                       std::vector<int32_t> &bestObs) {
+        const size_t n = setPtr.empty() ? 0 : setPtr.size() - 1;
+        if (obsKf.size() != obsIdx.size() || setId.size() != n || (n > 0 && (setPtr[n] < 0 || (size_t)setPtr[n] > obsKf.size())))
+            throw std::invalid_argument("ComputeDistinctiveDescriptors: a key frame number and an index per observation, setPtr inside them, an id per set");
+        std::vector<orbx_keyframe *> h(vpKFs.size());
+        for (size_t k = 0; k < vpKFs.size(); k++) h[k] = vpKFs[k]->handle();
+        bestObs.assign(n, -1);
+        const int r = orbx_keyframe_distinctive_descriptors_to_map(m_, (int)h.size(), h.data(), (int)n, setPtr.data(), obsKf.data(), obsIdx.data(), map.handle(),
+                                                                   setId.data(), bestObs.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_distinctive_descriptors_to_map: ") + orbx_status_string(r) + " " + orbx_last_error());
+    }
+
     // MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403) for a batch of map points: the observations' descriptors of map
     // point p are rows [setPtr[p], setPtr[p+1]) of `descriptors`; bestIdx[p] is the row offset (within the set) the reference keeps.
     void ComputeDistinctiveDescriptors(const std::vector<uint8_t> &descriptors, const std::vector<int32_t> &setPtr, std::vector<int32_t> &bestIdx) {
@@ -918,6 +1078,19 @@ public:
 
     orbx_matcher *handle() { return m_; }
 
+private:
+    // what the key-frame ...Map overloads share: the handles, the skip row count and the output rows (sides per key frame)
+    static std::vector<orbx_keyframe *> mapCallHandles(const std::vector<DeviceKeyFrame *> &vpKFs, size_t K, size_t n, const std::vector<uint8_t> &skip,
+                                                       std::vector<int32_t> &bestIdx, std::vector<int32_t> &bestDist, std::vector<uint8_t> *projected,
+                                                       size_t sides = 1) {
+        if (!skip.empty() && skip.size() != K * n) throw std::invalid_argument("a ...Map call takes K x n skip flags");
+        std::vector<orbx_keyframe *> h(K);
+        for (size_t k = 0; k < K; k++) h[k] = vpKFs[k]->handle();
+        bestIdx.assign(K * sides * n, -1); bestDist.assign(K * sides * n, 256);
+        if (projected) projected->assign(K * sides * n, 0);
+        return h;
+    }
+
 protected:
     float mfNNratio;
     bool mbCheckOrientation;
@@ -931,6 +1104,17 @@ protected:
 // levels above the leaf; the caller folds them into BowVector (addWeight) and FeatureVector (addFeature) in feature order.
 inline DeviceFrame::DeviceFrame(ORBmatcher &matcher, int cap) : cap_(cap) {
     check(orbx_frame_create(matcher.handle(), cap, &f_), "orbx_frame_create");
+}
+
+inline void DeviceMap::update(ORBmatcher &matcher, const std::vector<int32_t> &ids, const float *pos, const float *normal, const float *minDistance,
+                              const float *maxDistance, const uint8_t *descriptors) {
+    const int st = orbx_map_update(matcher.handle(), map_, (int)ids.size(), ids.data(), pos, normal, minDistance, maxDistance, descriptors);
+    if (st < 0) throw std::runtime_error(std::string("orbx_map_update: ") + orbx_status_string(st) + " " + orbx_last_error());
+}
+inline void DeviceMap::read(ORBmatcher &matcher, const std::vector<int32_t> &ids, float *pos, float *normal, float *minDistance, float *maxDistance,
+                            uint8_t *descriptors) {
+    const int st = orbx_map_read(matcher.handle(), map_, (int)ids.size(), ids.data(), pos, normal, minDistance, maxDistance, descriptors);
+    if (st < 0) throw std::runtime_error(std::string("orbx_map_read: ") + orbx_status_string(st) + " " + orbx_last_error());
 }
 
 inline DeviceKeyFrame::DeviceKeyFrame(ORBmatcher &matcher, DeviceFrame &frame, const float *mvInvLevelSigma2) {

@@ -466,6 +466,70 @@ __global__ __launch_bounds__(1024) void k_distinctive_kf_large(const DistinctSet
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// The device-resident map-point table (orbx_map): one 64-byte record per slot, four 16-byte quarters
+//   quarter 0   pos.x pos.y pos.z normal.x        quarter 1   normal.y normal.z min_dist max_dist        quarters 2, 3   the descriptor (32-byte aligned)
+// Four lanes per point, one quarter each: a wave moves 16 records, a block 64.  Streaming work: no LDS, nothing kept between points.  Every id comes
+// from the host, which has checked it against the capacity and the liveness of its slot before the launch; a lane whose id is not below `cap` forms
+// no address all the same.
+//   k_map_scatter       row j of the given field arrays -> slot ids[j]; a NULL array keeps that field (quarters 0 and 1 are read, patched, written)
+//   k_map_gather        slot ids[j] -> row j of the five arrays every projection kernel reads (the flat call's arena buffers)
+//   k_map_scatter_desc  the winning row of set s (orbx_keyframe_distinctive_descriptors_to_map) -> the descriptor of slot set_id[s]; nothing for an
+//                       empty set (best_obs < 0), nothing at all once the distinctive kernels raised *flag
+// grid (ceil(n / 64)), block 256
+// ---------------------------------------------------------------------------------------------------------
+struct MapRows {
+    uint4 *rec; const int32_t *ids; int n, cap;
+    float *pos, *normal, *min_dist, *max_dist; uint8_t *desc;   // [n] rows: read by k_map_scatter (NULL: keep), written by k_map_gather
+};
+__global__ __launch_bounds__(256) void k_map_scatter(const MapRows M) {
+    const int t = blockIdx.x * 256 + threadIdx.x, j = t >> 2, q = t & 3;
+    if (j >= M.n) return;
+    const int id = gld(M.ids + j);
+    if ((unsigned)id >= (unsigned)M.cap) return;
+    uint4 *dst = M.rec + (size_t)id * 4 + q;
+    if (q >= 2) {
+        if (M.desc) *dst = reinterpret_cast<const uint4 *>(M.desc)[(size_t)j * 2 + (q - 2)];
+        return;
+    }
+    uint4 v = *dst;
+    if (q == 0) {
+        if (M.pos) { v.x = __float_as_uint(gld(M.pos + 3 * (size_t)j)); v.y = __float_as_uint(gld(M.pos + 3 * (size_t)j + 1)); v.z = __float_as_uint(gld(M.pos + 3 * (size_t)j + 2)); }
+        if (M.normal) v.w = __float_as_uint(gld(M.normal + 3 * (size_t)j));
+    } else {
+        if (M.normal) { v.x = __float_as_uint(gld(M.normal + 3 * (size_t)j + 1)); v.y = __float_as_uint(gld(M.normal + 3 * (size_t)j + 2)); }
+        if (M.min_dist) v.z = __float_as_uint(gld(M.min_dist + j));
+        if (M.max_dist) v.w = __float_as_uint(gld(M.max_dist + j));
+    }
+    *dst = v;
+}
+__global__ __launch_bounds__(256) void k_map_gather(const MapRows M) {
+    const int t = blockIdx.x * 256 + threadIdx.x, j = t >> 2, q = t & 3;
+    if (j >= M.n) return;
+    const int id = gld(M.ids + j);
+    if ((unsigned)id >= (unsigned)M.cap) return;
+    const uint4 v = M.rec[(size_t)id * 4 + q];
+    if (q >= 2) {
+        reinterpret_cast<uint4 *>(M.desc)[(size_t)j * 2 + (q - 2)] = v;
+    } else if (q == 0) {
+        gst(M.pos + 3 * (size_t)j, __uint_as_float(v.x)); gst(M.pos + 3 * (size_t)j + 1, __uint_as_float(v.y)); gst(M.pos + 3 * (size_t)j + 2, __uint_as_float(v.z));
+        gst(M.normal + 3 * (size_t)j, __uint_as_float(v.w));
+    } else {
+        gst(M.normal + 3 * (size_t)j + 1, __uint_as_float(v.x)); gst(M.normal + 3 * (size_t)j + 2, __uint_as_float(v.y));
+        gst(M.min_dist + j, __uint_as_float(v.z)); gst(M.max_dist + j, __uint_as_float(v.w));
+    }
+}
+// grid (ceil(n_sets / 128)), block 256: two lanes per set, a 16-byte half of the row each
+__global__ __launch_bounds__(256) void k_map_scatter_desc(uint4 *rec, int cap, int n_sets, const int32_t *__restrict__ set_id,
+                                                          const int32_t *__restrict__ best_obs, const int32_t *__restrict__ flag,
+                                                          const uint8_t *__restrict__ best_desc) {
+    const int t = blockIdx.x * 256 + threadIdx.x, s = t >> 1, h = t & 1;
+    if (s >= n_sets || gld(flag) != 0) return;
+    const int id = gld(set_id + s);
+    if (gld(best_obs + s) < 0 || (unsigned)id >= (unsigned)cap) return;
+    rec[(size_t)id * 4 + 2 + h] = reinterpret_cast<const uint4 *>(best_desc)[(size_t)s * 2 + h];
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // DBoW2 TemplatedVocabulary::transform(feature, word_id, weight, nid, levelsup) (TemplatedVocabulary.h:1206-1250):
 // descend the k-ary vocabulary tree, at every level to the child with the smallest Hamming distance (strict '<': the
 // first minimum in m_nodes[i].children order wins).  16 lanes per feature; lanes stride the children of the current

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -1129,30 +1130,216 @@ extern "C" int orbx_frame_search_by_projection_window_fisheye(orbx_matcher *m, o
     return run_projection(m, a, f, true);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The device-resident map-point table (include/orbx.h, orbx_map) and the ONE map-point source of the eight one-call searches (MapPoints): host
+// arrays, uploaded as ever, or (map, ids), gathered into the same five arena buffers by k_map_gather.  Everything behind those buffers is shared.
+// ---------------------------------------------------------------------------------------------------------
+struct orbx_map {
+    int device = 0, capacity = 0;
+    uint4 *rec = nullptr;              // [capacity] 64-byte records (matcher_kernels.hip.h, MapRows)
+    hipEvent_t written = nullptr;      // recorded behind the newest update, on the updating context's stream
+    std::mutex mu;                     // guards everything below and the re-recording of `written`
+    uint64_t write_seq = 0;            // updates recorded so far
+    uint64_t seen_seq = 0;             // the newest update a reading call has waited for AND synchronised behind: nobody needs to wait for it again
+    uint8_t *live = nullptr;           // [capacity] the slot has been written whole since its creation / its erase
+    uint32_t *stamp = nullptr;         // [capacity] the last checking pass that named the slot (duplicate detection)
+    uint32_t stamp_now = 0;
+};
+
+namespace {
+
+// every id in [0, capacity) and live; unique: named once (the stamp array).  Under map->mu.
+bool map_ids_ok(orbx_map *map, int n, const int32_t *ids, bool unique) {
+    if (unique && ++map->stamp_now == 0) { memset(map->stamp, 0, sizeof(uint32_t) * (size_t)map->capacity); map->stamp_now = 1; }
+    for (int j = 0; j < n; j++) {
+        const int32_t id = ids[j];
+        if (id < 0 || id >= map->capacity || !map->live[id]) return false;
+        if (unique) {
+            if (map->stamp[id] == map->stamp_now) return false;
+            map->stamp[id] = map->stamp_now;
+        }
+    }
+    return true;
+}
+
+// The map points of a call: n rows of host arrays, or n slots of a table (map != NULL; the five pointers are NULL then).
+struct MapPoints { int n; const float *pos, *normal, *min_dist, *max_dist; const uint8_t *desc; orbx_map *map; const int32_t *ids; };
+struct MapPointsDev { float *pos, *normal, *min_dist, *max_dist; uint8_t *desc; int32_t *ids; };
+
+inline MapPoints map_points_of(int n, orbx_map *map, const int32_t *ids) { return MapPoints{n, nullptr, nullptr, nullptr, nullptr, nullptr, map, ids}; }
+// a table source needs its table: a `_map` entry point given map = NULL is refused, not read as "flat arrays, all NULL"
+inline bool map_form_ok(const orbx_map *map, int n) { return map != nullptr || n <= 0; }
+
+// what a call checks of its n > 0 map points before it enqueues anything: the five arrays, or the table's device and every id
+bool map_points_ok(const orbx_matcher *m, const MapPoints &S) {
+    if (!S.map) return S.pos && S.normal && S.min_dist && S.max_dist && S.desc;
+    if (S.map->device != m->device || !S.ids) return false;
+    std::lock_guard<std::mutex> lock(S.map->mu);
+    return map_ids_ok(S.map, S.n, S.ids, false);
+}
+// the five device arrays every projection kernel reads, first in the call's arena: uploaded from the host arrays, or only carved, with the ids behind
+// them -- at the head of the call's one upload run
+MapPointsDev map_points_up(Carve &A, const MapPoints &S) {
+    const size_t q = (size_t)S.n;
+    MapPointsDev d;
+    d.pos = A.up(S.pos, 3 * q); d.normal = A.up(S.normal, 3 * q); d.min_dist = A.up(S.min_dist, q); d.max_dist = A.up(S.max_dist, q);
+    d.desc = A.up(S.desc, 32 * q);
+    d.ids = S.map ? A.up(S.ids, q) : nullptr;
+    return d;
+}
+// a table source: the context's stream waits for `written` (unless a reader has synchronised behind it), then k_map_gather fills the five arrays.
+// *seq: what map_points_done() reports once the call has synchronised.  Host arrays: nothing.
+int map_points_gather(orbx_matcher *m, const MapPoints &S, const MapPointsDev &D, uint64_t *seq) {
+    *seq = 0;
+    if (!S.map || S.n <= 0) return ORBX_OK;
+    {
+        std::lock_guard<std::mutex> lock(S.map->mu);
+        if (S.map->seen_seq < S.map->write_seq) ORBX_HIP(hipStreamWaitEvent(m->stream, S.map->written, 0));
+        *seq = S.map->write_seq;
+    }
+    const MapRows G = {S.map->rec, D.ids, S.n, S.map->capacity, D.pos, D.normal, D.min_dist, D.max_dist, D.desc};
+    hipLaunchKernelGGL(k_map_gather, dim3((unsigned)((S.n + 63) / 64)), dim3(256), 0, m->exec(), G);
+    return ORBX_OK;
+}
+inline void map_points_done(const MapPoints &S, uint64_t seq) {   // after the call's synchronisation
+    if (!S.map || seq == 0) return;
+    std::lock_guard<std::mutex> lock(S.map->mu);
+    S.map->seen_seq = std::max(S.map->seen_seq, seq);
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbx_map_create(int device, int capacity, orbx_map **out) {
+    if (!out) return ORBX_E_BAD_ARG;
+    *out = nullptr;
+    if (capacity < 1) return ORBX_E_BAD_ARG;
+    if (capacity > ORBX_MAX_MAP_POINTS) return ORBX_E_TOO_LARGE;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+        set_error("no usable HIP device (liborbx has no CPU fallback)");
+        return ORBX_E_NO_DEVICE;
+    }
+    ORBX_HIP(hipSetDevice(device));
+    std::unique_ptr<orbx_map> map(new orbx_map());
+    map->device = device; map->capacity = capacity;
+    map->live = static_cast<uint8_t *>(calloc((size_t)capacity, 1));
+    map->stamp = static_cast<uint32_t *>(calloc((size_t)capacity, sizeof(uint32_t)));
+    hipError_t e = hipMalloc((void **)&map->rec, 64 * (size_t)capacity);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&map->written, hipEventDisableTiming);
+    if (e != hipSuccess || !map->live || !map->stamp) {
+        set_error(e != hipSuccess ? hipGetErrorString(e) : "out of host memory");
+        orbx_map_destroy(map.release());
+        return ORBX_E_HIP;
+    }
+    *out = map.release();
+    return ORBX_OK;
+}
+
+void orbx_map_destroy(orbx_map *map) {
+    if (!map) return;
+    (void)hipSetDevice(map->device);
+    if (map->written) { (void)hipEventSynchronize(map->written); (void)hipEventDestroy(map->written); }   // the last update has run; no search is running (the caller's contract)
+    if (map->rec) (void)hipFree(map->rec);
+    free(map->live);
+    free(map->stamp);
+    delete map;
+}
+
+int orbx_map_update(orbx_matcher *m, orbx_map *map, int n, const int32_t *ids, const float *pos, const float *normal, const float *min_dist,
+                    const float *max_dist, const uint8_t *desc) {
+    if (!m || !map || n < 0 || map->device != m->device) return ORBX_E_BAD_ARG;
+    if (n == 0) return ORBX_OK;
+    if (!ids) return ORBX_E_BAD_ARG;
+    std::lock_guard<std::mutex> lock(map->mu);
+    // everything is checked before anything is enqueued: range, one mention per id, and all five fields for a slot that is not live
+    const bool whole = pos && normal && min_dist && max_dist && desc;
+    if (++map->stamp_now == 0) { memset(map->stamp, 0, sizeof(uint32_t) * (size_t)map->capacity); map->stamp_now = 1; }
+    for (int j = 0; j < n; j++) {
+        const int32_t id = ids[j];
+        if (id < 0 || id >= map->capacity || map->stamp[id] == map->stamp_now || (!whole && !map->live[id])) return ORBX_E_BAD_ARG;
+        map->stamp[id] = map->stamp_now;
+    }
+    if (!pos && !normal && !min_dist && !max_dist && !desc) return ORBX_OK;   // every field kept
+    ORBX_HIP(hipSetDevice(m->device));
+    const size_t q = (size_t)n;
+    MapRows S;
+    memset(&S, 0, sizeof(S));
+    S.rec = map->rec; S.n = n; S.cap = map->capacity;
+    ORBX_TRY(m->carve([&](Carve &A) {   // one run
+        S.ids = A.up(ids, q);
+        S.pos = A.up_opt(pos, 3 * q); S.normal = A.up_opt(normal, 3 * q); S.min_dist = A.up_opt(min_dist, q); S.max_dist = A.up_opt(max_dist, q);
+        S.desc = A.up_opt(desc, 32 * q);
+    }));
+    if (map->write_seq > 0) ORBX_HIP(hipStreamWaitEvent(m->stream, map->written, 0));
+    hipLaunchKernelGGL(k_map_scatter, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, m->exec(), S);
+    ORBX_HIP(hipGetLastError());
+    ORBX_HIP(hipEventRecord(map->written, m->stream));
+    map->write_seq++;
+    for (int j = 0; j < n; j++) map->live[ids[j]] = 1;
+    return ORBX_OK;
+}
+
+int orbx_map_erase(orbx_map *map, int n, const int32_t *ids) {
+    if (!map || n < 0) return ORBX_E_BAD_ARG;
+    if (n == 0) return ORBX_OK;
+    if (!ids) return ORBX_E_BAD_ARG;
+    std::lock_guard<std::mutex> lock(map->mu);
+    if (!map_ids_ok(map, n, ids, false)) return ORBX_E_BAD_ARG;
+    for (int j = 0; j < n; j++) map->live[ids[j]] = 0;
+    return ORBX_OK;
+}
+
+int orbx_map_read(orbx_matcher *m, orbx_map *map, int n, const int32_t *ids, float *pos, float *normal, float *min_dist, float *max_dist,
+                  uint8_t *desc) {
+    if (!m || !map || n < 0) return ORBX_E_BAD_ARG;
+    if (n == 0) return map->device == m->device ? ORBX_OK : ORBX_E_BAD_ARG;
+    const MapPoints S = map_points_of(n, map, ids);
+    if (!map_points_ok(m, S)) return ORBX_E_BAD_ARG;
+    ORBX_HIP(hipSetDevice(m->device));
+    MapPointsDev D;
+    ORBX_TRY(m->carve([&](Carve &A) { D = map_points_up(A, S); }));
+    uint64_t seq = 0;
+    ORBX_TRY(map_points_gather(m, S, D, &seq));
+    ORBX_HIP(hipGetLastError());
+    const size_t q = (size_t)n;
+    if (pos) ORBX_TRY(m->d2h(pos, D.pos, 12 * q));
+    if (normal) ORBX_TRY(m->d2h(normal, D.normal, 12 * q));
+    if (min_dist) ORBX_TRY(m->d2h(min_dist, D.min_dist, 4 * q));
+    if (max_dist) ORBX_TRY(m->d2h(max_dist, D.max_dist, 4 * q));
+    if (desc) ORBX_TRY(m->d2h(desc, D.desc, 32 * q));
+    ORBX_TRY(m->sync_and_deliver());
+    map_points_done(S, seq);
+    return ORBX_OK;
+}
+
+}  // extern "C"
+
 namespace {
 
 // ---- Tracking::SearchLocalPoints on a resident frame of either kind.  The two forms share their head, the upload of the map points and their tail;
 // the projection records, the frustum and window kernels and resolve-versus-twin are each kind's own, and each carves its arena in its own order.
-struct LocalPoints { int n; const float *pos, *normal, *min_dist, *max_dist; const uint8_t *desc, *eligible, *has_obs; const float *track_depth; };   // (track_depth: a rig's only)
-struct LocalPointsDev { float *pos, *normal, *min_dist, *max_dist, *track_depth; uint8_t *desc, *eligible, *has_obs, *occupied; };
+struct LocalPoints { MapPoints src; const uint8_t *eligible, *has_obs; const float *track_depth; };   // (track_depth: a rig's only)
+struct LocalPointsDev : MapPointsDev { float *track_depth; uint8_t *eligible, *has_obs, *occupied; };
 
 // The head: the argument checks both forms share (have_view: the form's camera arguments are there), N where the call needs it on the host -- *n = -1
 // while it stays on the device -- and frame_match's -1 fill.  The caller returns 0 behind it when there are no map points.
 int local_points_head(orbx_matcher *m, orbx_frame *f, bool fisheye, bool have_view, const LocalPoints &mp, const uint8_t *occupied, const uint8_t *in_view,
                       int32_t *frame_match, int *n) {
-    if (!m || !f || f->owner != m || f->fisheye != fisheye || !have_view || mp.n < 0 || !frame_match) return ORBX_E_BAD_ARG;
-    if (mp.n > 0 && (!mp.pos || !mp.normal || !mp.min_dist || !mp.max_dist || !mp.desc || !in_view)) return ORBX_E_BAD_ARG;
+    if (!m || !f || f->owner != m || f->fisheye != fisheye || !have_view || mp.src.n < 0 || !frame_match) return ORBX_E_BAD_ARG;
+    if (mp.src.n > 0 && (!in_view || !map_points_ok(m, mp.src))) return ORBX_E_BAD_ARG;
     *n = -1;
-    if (f->n_known || occupied || mp.n == 0) ORBX_TRY(frame_count(f, n));   // the mask holds N entries
+    if (f->n_known || occupied || mp.src.n == 0) ORBX_TRY(frame_count(f, n));   // the mask holds N entries
     for (int i = 0; i < *n; i++) frame_match[i] = -1;
     return ORBX_OK;
 }
 // the first buffers of both arenas: the map points and the occupancy mask, one run of uploads
 LocalPointsDev local_points_up(Carve &A, const LocalPoints &mp, const uint8_t *occupied, int n) {
-    const size_t q = (size_t)mp.n;
+    const size_t q = (size_t)mp.src.n;
     LocalPointsDev d;
-    d.pos = A.up(mp.pos, 3 * q); d.normal = A.up(mp.normal, 3 * q); d.min_dist = A.up(mp.min_dist, q); d.max_dist = A.up(mp.max_dist, q);
-    d.desc = A.up(mp.desc, 32 * q); d.eligible = A.up_opt(mp.eligible, q); d.has_obs = A.up_opt(mp.has_obs, q); d.track_depth = A.up_opt(mp.track_depth, q);
+    static_cast<MapPointsDev &>(d) = map_points_up(A, mp.src);
+    d.eligible = A.up_opt(mp.eligible, q); d.has_obs = A.up_opt(mp.has_obs, q); d.track_depth = A.up_opt(mp.track_depth, q);
     d.occupied = n > 0 ? A.up_opt(occupied, (size_t)n) : nullptr;
     return d;
 }
@@ -1175,12 +1362,12 @@ int local_points_tail(orbx_matcher *m, orbx_frame *f, bool match, uint8_t *in_vi
 // Tracking::SearchLocalPoints on a resident frame (Tracking.cc:3339-3413): Frame::isInFrustum (Frame.cc:512-575) of every local map point, the
 // window setup and SearchByProjection(F, vpMapPoints, th, bFarPoints, thFarPoints) (ORBmatcher.cc:43-213, Nleft == -1) in one call: the projection
 // records stay in the call's arena, one transfer up, one down, one synchronisation.
-extern "C" int orbx_frame_search_local_points(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_camera *cam,
-                                              const orbx_frame_pose *pose, float log_scale_factor, float viewing_cos_limit, int n_mp, const float *pos,
-                                              const float *normal, const float *min_dist, const float *max_dist, const uint8_t *mp_desc,
-                                              const uint8_t *eligible, const uint8_t *has_obs, float th, float nnratio, int far_points,
-                                              float th_far_points, uint8_t *in_view, int32_t *frame_match) {
-    const LocalPoints mp = {n_mp, pos, normal, min_dist, max_dist, mp_desc, eligible, has_obs, nullptr};
+static int frame_search_local_points_impl(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_camera *cam,
+                                          const orbx_frame_pose *pose, float log_scale_factor, float viewing_cos_limit, const MapPoints &src,
+                                          const uint8_t *eligible, const uint8_t *has_obs, float th, float nnratio, int far_points,
+                                          float th_far_points, uint8_t *in_view, int32_t *frame_match) {
+    const LocalPoints mp = {src, eligible, has_obs, nullptr};
+    const int n_mp = src.n;
     int n = -1;
     const int rc = local_points_head(m, f, false, cam && pose, mp, frame_occupied, in_view, frame_match, &n);
     if (rc != ORBX_OK || n_mp == 0) return rc;
@@ -1229,6 +1416,8 @@ extern "C" int orbx_frame_search_local_points(orbx_matcher *m, orbx_frame *f, co
     R.q_has_obs = D.has_obs;
     R.mode = 1; R.nnratio = nnratio; R.max_dist = (float)ORBX_TH_HIGH; R.cleared_value = -2;
     ORBX_TRY(m->h2d(dP, &P, sizeof(P))); ORBX_TRY(m->h2d(dR, &R, sizeof(R)));
+    uint64_t seq = 0;
+    ORBX_TRY(map_points_gather(m, src, D, &seq));
     hipLaunchKernelGGL(k_in_frustum, dim3((n_mp + 255) / 256, 1), dim3(256), 0, m->exec(), (const FrustumFrame *)dF, n_mp, (const float *)D.pos,
                        (const float *)D.normal, (const float *)D.min_dist, (const float *)D.max_dist, div, dx, dy, dxr, dd, dl, dvc);
     hipLaunchKernelGGL(k_local_windows, dim3((n_mp + 255) / 256), dim3(256), 0, m->exec(), n_mp, (const uint8_t *)div, (const uint8_t *)D.eligible,
@@ -1241,17 +1430,37 @@ extern "C" int orbx_frame_search_local_points(orbx_matcher *m, orbx_frame *f, co
         const int rr = launch_resolve<false>(1, m->exec(), dP, dR, g, nc, n_mp, 4);
         if (rr != ORBX_OK) return rr;
     }
-    return local_points_tail(m, f, match, in_view, div_out, q, R.match, nc, R.nmatches, frame_match);
+    const int nm = local_points_tail(m, f, match, in_view, div_out, q, R.match, nc, R.nmatches, frame_match);
+    if (nm >= 0) map_points_done(src, seq);
+    return nm;
+}
+
+extern "C" int orbx_frame_search_local_points(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_camera *cam,
+                                              const orbx_frame_pose *pose, float log_scale_factor, float viewing_cos_limit, int n_mp, const float *pos,
+                                              const float *normal, const float *min_dist, const float *max_dist, const uint8_t *mp_desc,
+                                              const uint8_t *eligible, const uint8_t *has_obs, float th, float nnratio, int far_points,
+                                              float th_far_points, uint8_t *in_view, int32_t *frame_match) {
+    return frame_search_local_points_impl(m, f, frame_occupied, cam, pose, log_scale_factor, viewing_cos_limit,
+                                          MapPoints{n_mp, pos, normal, min_dist, max_dist, mp_desc, nullptr, nullptr}, eligible, has_obs, th, nnratio,
+                                          far_points, th_far_points, in_view, frame_match);
+}
+extern "C" int orbx_frame_search_local_points_map(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_camera *cam,
+                                                  const orbx_frame_pose *pose, float log_scale_factor, float viewing_cos_limit, int n_mp, orbx_map *map,
+                                                  const int32_t *ids, const uint8_t *eligible, const uint8_t *has_obs, float th, float nnratio,
+                                                  int far_points, float th_far_points, uint8_t *in_view, int32_t *frame_match) {
+    if (!map_form_ok(map, n_mp)) return ORBX_E_BAD_ARG;
+    return frame_search_local_points_impl(m, f, frame_occupied, cam, pose, log_scale_factor, viewing_cos_limit, map_points_of(n_mp, map, ids), eligible,
+                                          has_obs, th, nnratio, far_points, th_far_points, in_view, frame_match);
 }
 
 // Tracking::SearchLocalPoints on a resident fisheye-stereo frame: isInFrustumChecks of both cameras (k_in_frustum_checks), the windows
 // (k_local_windows_fisheye), the twin window search and the replay (k_replay_twin) -- the projection records never leave the device.
-extern "C" int orbx_frame_search_local_points_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_fisheye_view *views,
-                                                      float log_scale_factor, float viewing_cos_limit, int n_mp, const float *pos, const float *normal,
-                                                      const float *min_dist, const float *max_dist, const uint8_t *mp_desc, const uint8_t *eligible,
-                                                      const uint8_t *has_obs, const float *track_depth, float th, float nnratio, int far_points,
-                                                      float th_far_points, uint8_t *in_view, int32_t *frame_match) {
-    const LocalPoints mp = {n_mp, pos, normal, min_dist, max_dist, mp_desc, eligible, has_obs, track_depth};
+static int frame_search_local_points_fisheye_impl(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_fisheye_view *views,
+                                                  float log_scale_factor, float viewing_cos_limit, const MapPoints &src, const uint8_t *eligible,
+                                                  const uint8_t *has_obs, const float *track_depth, float th, float nnratio, int far_points,
+                                                  float th_far_points, uint8_t *in_view, int32_t *frame_match) {
+    const LocalPoints mp = {src, eligible, has_obs, track_depth};
+    const int n_mp = src.n;
     int N = -1;
     const int rc = local_points_head(m, f, true, views != nullptr, mp, frame_occupied, in_view, frame_match, &N);
     if (rc != ORBX_OK || n_mp == 0) return rc;
@@ -1304,6 +1513,8 @@ extern "C" int orbx_frame_search_local_points_fisheye(orbx_matcher *m, orbx_fram
     T.mode = 1; T.nq = n_mp; T.nnratio = nnratio; T.max_dist = (float)ORBX_TH_HIGH; T.cleared_value = -2;
     T.l2r = f->l2r; T.r2l = f->r2l;
     ORBX_TRY(m->h2d(dP, P, sizeof(P)));
+    uint64_t seq = 0;
+    ORBX_TRY(map_points_gather(m, src, D, &seq));
     hipLaunchKernelGGL(k_in_frustum_checks, dim3((n_mp + 255) / 256, 2), dim3(256), 0, m->exec(), (const FrustumChecks *)dF, n_mp, (const float *)D.pos,
                        (const float *)D.normal, (const float *)D.min_dist, (const float *)D.max_dist, div, dx, dy, dd, dl, dvc);
     hipLaunchKernelGGL(k_local_windows_fisheye, dim3((n_mp + 255) / 256), dim3(256), 0, m->exec(), n_mp, (const uint8_t *)div, (const uint8_t *)D.eligible,
@@ -1311,7 +1522,27 @@ extern "C" int orbx_frame_search_local_points_fisheye(orbx_matcher *m, orbx_fram
                        far_points ? 1 : 0, th_far_points, dqr, dqmin, dqmax, dvalid, div_out);
     const bool match = N != 0;   // (an empty frame: isInFrustumChecks only)
     if (match) ORBX_TRY(launch_twin(m, dP, T, grid_of(f->bounds), nc, n_mp));
-    return local_points_tail(m, f, match, in_view, div_out, q2, T.match, nc, T.nmatches, frame_match);
+    const int nm = local_points_tail(m, f, match, in_view, div_out, q2, T.match, nc, T.nmatches, frame_match);
+    if (nm >= 0) map_points_done(src, seq);
+    return nm;
+}
+
+extern "C" int orbx_frame_search_local_points_fisheye(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_fisheye_view *views,
+                                                      float log_scale_factor, float viewing_cos_limit, int n_mp, const float *pos, const float *normal,
+                                                      const float *min_dist, const float *max_dist, const uint8_t *mp_desc, const uint8_t *eligible,
+                                                      const uint8_t *has_obs, const float *track_depth, float th, float nnratio, int far_points,
+                                                      float th_far_points, uint8_t *in_view, int32_t *frame_match) {
+    return frame_search_local_points_fisheye_impl(m, f, frame_occupied, views, log_scale_factor, viewing_cos_limit,
+                                                  MapPoints{n_mp, pos, normal, min_dist, max_dist, mp_desc, nullptr, nullptr}, eligible, has_obs, track_depth,
+                                                  th, nnratio, far_points, th_far_points, in_view, frame_match);
+}
+extern "C" int orbx_frame_search_local_points_fisheye_map(orbx_matcher *m, orbx_frame *f, const uint8_t *frame_occupied, const orbx_fisheye_view *views,
+                                                          float log_scale_factor, float viewing_cos_limit, int n_mp, orbx_map *map, const int32_t *ids,
+                                                          const uint8_t *eligible, const uint8_t *has_obs, const float *track_depth, float th,
+                                                          float nnratio, int far_points, float th_far_points, uint8_t *in_view, int32_t *frame_match) {
+    if (!map_form_ok(map, n_mp)) return ORBX_E_BAD_ARG;
+    return frame_search_local_points_fisheye_impl(m, f, frame_occupied, views, log_scale_factor, viewing_cos_limit, map_points_of(n_mp, map, ids), eligible,
+                                                  has_obs, track_depth, th, nnratio, far_points, th_far_points, in_view, frame_match);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -3178,31 +3409,31 @@ int orbx_keyframe_fuse_search_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *
 // reads the left camera only -- views [n_kf], ONE problem per key frame (its left side), records from k_sim3_project_kb8, best_idx below N_left.
 static int keyframe_fuse_map_points_impl(orbx_matcher *m, bool fisheye, bool sim3, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
                                          const orbx_frame_pose *poses, const orbx_fisheye_view *views, float th, float log_scale_factor, int strict_fp,
-                                         int n_mp, const float *pos, const float *normal, const float *min_dist, const float *max_dist,
-                                         const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist, uint8_t *projected) {
+                                         const MapPoints &src, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist, uint8_t *projected) {
+    const int n_mp = src.n;
     if (!m || n_kf < 0 || n_mp < 0 || (n_kf > 0 && (!kfs || (fisheye ? !views : !cams || !poses)))) return ORBX_E_BAD_ARG;
     if (n_kf > ORBX_MAX_FUSE_KEYFRAMES) return ORBX_E_TOO_LARGE;
     const int sides = fisheye && !sim3 ? 2 : 1, nprob = n_kf * sides;   // problem p: key frame p / sides, camera p % sides (a Sim3 Fuse: the left one only)
     const size_t np = (size_t)n_mp, total = (size_t)nprob * np;
-    if (total > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc || !best_idx || !best_dist)) return ORBX_E_BAD_ARG;
+    if (total > 0 && (!best_idx || !best_dist || !map_points_ok(m, src))) return ORBX_E_BAD_ARG;
     for (int k = 0; k < n_kf; k++)
         if (!kfs[k] || kfs[k]->fisheye != fisheye || kfs[k]->device != m->device || (!sim3 && !kfs[k]->inv_sigma2)) return ORBX_E_BAD_ARG;
     if (total == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
     const int32_t cnt4[4] = {n_mp, 0, 0, 0};
-    float *dp, *dn, *dmn, *dmx, *qx, *qy, *qxr, *qr;
-    uint8_t *dd, *dskip, *qvalid;
+    float *qx, *qy, *qxr, *qr;
+    uint8_t *dskip, *qvalid;
     int32_t *dcnt, *qmin, *qmax;
     orbx_camera *dcam;
     orbx_frame_pose *dpose;
     FisheyeView *dview;
     KfProblem *dR;
     u64 *dkeys;
+    MapPointsDev D;
     ORBX_TRY(m->carve([&](Carve &A) {
         // uploads, adjacent in the arena (one run): the map points ONCE, then what grows with n_kf -- cameras and poses (a rig: two views), problem
         // records, one skip row per key frame
-        dp = A.up(pos, 3 * np); dn = A.up(normal, 3 * np); dmn = A.up(min_dist, np); dmx = A.up(max_dist, np);
-        dd = A.up(mp_desc, 32 * np);
+        D = map_points_up(A, src);
         dcnt = A.up(cnt4, 4);
         dcam = fisheye ? nullptr : A.up(cams, (size_t)n_kf);
         dpose = fisheye ? nullptr : A.up(poses, (size_t)n_kf);
@@ -3222,10 +3453,13 @@ static int keyframe_fuse_map_points_impl(orbx_matcher *m, bool fisheye, bool sim
         const size_t o = (size_t)p * np;
         P.qx = qx + o; P.qy = qy + o; P.qr = qr + o; P.qmin = qmin + o; P.qmax = qmax + o; P.qvalid = qvalid + o;
         if (qxr) P.qxr = qxr + o;
-        P.qdesc = dd; P.nq_ptr = dcnt; P.keys = dkeys + o;
+        P.qdesc = D.desc; P.nq_ptr = dcnt; P.keys = dkeys + o;
     }
     ORBX_TRY(m->h2d(dR, R.data(), sizeof(KfProblem) * (size_t)nprob));
     ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
+    uint64_t seq = 0;
+    ORBX_TRY(map_points_gather(m, src, D, &seq));
+    const float *dp = D.pos, *dn = D.normal, *dmn = D.min_dist, *dmx = D.max_dist;
     const dim3 grid((unsigned)((n_mp + 255) / 256), (unsigned)nprob);
     if (fisheye && sim3)
         hipLaunchKernelGGL(k_sim3_project_kb8, grid, dim3(256), 0, m->exec(), (const KfProblem *)dR, (const FisheyeView *)dview, th, log_scale_factor,
@@ -3250,6 +3484,7 @@ static int keyframe_fuse_map_points_impl(orbx_matcher *m, bool fisheye, bool sim
     ORBX_TRY(keyframe_fetch_counts(m, fisheye, n_kf, kfs, &pend));
     ORBX_TRY(m->sync_and_deliver());
     keyframe_release(kfs, n_kf);
+    map_points_done(src, seq);
     keyframe_take_counts(fisheye, n_kf, kfs, pend);
     for (int p = 0; p < nprob; p++) keyframe_fuse_results(kfs, sides, p, keys.data() + (size_t)p * np, np, best_idx + (size_t)p * np, best_dist + (size_t)p * np);
     return ORBX_OK;
@@ -3259,16 +3494,30 @@ int orbx_keyframe_fuse_map_points(orbx_matcher *m, int n_kf, orbx_keyframe *cons
                                   float log_scale_factor, int strict_fp, int n_mp, const float *pos, const float *normal, const float *min_dist,
                                   const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
                                   uint8_t *projected) {
-    return keyframe_fuse_map_points_impl(m, false, false, n_kf, kfs, cams, poses, nullptr, th, log_scale_factor, strict_fp, n_mp, pos, normal, min_dist, max_dist,
-                                         mp_desc, skip, best_idx, best_dist, projected);
+    return keyframe_fuse_map_points_impl(m, false, false, n_kf, kfs, cams, poses, nullptr, th, log_scale_factor, strict_fp,
+                                         MapPoints{n_mp, pos, normal, min_dist, max_dist, mp_desc, nullptr, nullptr}, skip, best_idx, best_dist, projected);
+}
+int orbx_keyframe_fuse_map_points_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams, const orbx_frame_pose *poses,
+                                      float th, float log_scale_factor, int strict_fp, int n_mp, orbx_map *map, const int32_t *ids,
+                                      const uint8_t *skip, int32_t *best_idx, int32_t *best_dist, uint8_t *projected) {
+    if (!map_form_ok(map, n_mp)) return ORBX_E_BAD_ARG;
+    return keyframe_fuse_map_points_impl(m, false, false, n_kf, kfs, cams, poses, nullptr, th, log_scale_factor, strict_fp, map_points_of(n_mp, map, ids), skip,
+                                         best_idx, best_dist, projected);
 }
 
 int orbx_keyframe_fuse_map_points_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views, float th,
                                           float log_scale_factor, int strict_fp, int n_mp, const float *pos, const float *normal, const float *min_dist,
                                           const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
                                           uint8_t *projected) {
-    return keyframe_fuse_map_points_impl(m, true, false, n_kf, kfs, nullptr, nullptr, views, th, log_scale_factor, strict_fp, n_mp, pos, normal, min_dist,
-                                         max_dist, mp_desc, skip, best_idx, best_dist, projected);
+    return keyframe_fuse_map_points_impl(m, true, false, n_kf, kfs, nullptr, nullptr, views, th, log_scale_factor, strict_fp,
+                                         MapPoints{n_mp, pos, normal, min_dist, max_dist, mp_desc, nullptr, nullptr}, skip, best_idx, best_dist, projected);
+}
+int orbx_keyframe_fuse_map_points_fisheye_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views, float th,
+                                              float log_scale_factor, int strict_fp, int n_mp, orbx_map *map, const int32_t *ids, const uint8_t *skip,
+                                              int32_t *best_idx, int32_t *best_dist, uint8_t *projected) {
+    if (!map_form_ok(map, n_mp)) return ORBX_E_BAD_ARG;
+    return keyframe_fuse_map_points_impl(m, true, false, n_kf, kfs, nullptr, nullptr, views, th, log_scale_factor, strict_fp, map_points_of(n_mp, map, ids),
+                                         skip, best_idx, best_dist, projected);
 }
 
 }  // extern "C"
@@ -3608,8 +3857,10 @@ int orbx_keyframe_bow_from_frame_fisheye(orbx_matcher *m, orbx_keyframe *kf, orb
 // kind: k_distinctive_kf (sets of up to 64 rows) and k_distinctive_kf_large gather the rows through a record per key frame.  One upload run (set_ptr, the
 // two index arrays, the records, the list of large sets), one launch per kernel, one download run (best_obs, the flag, best_desc, the counts of key
 // frames that still had them on the device), one synchronisation.
-int orbx_keyframe_distinctive_descriptors(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, int n_sets, const int32_t *set_ptr, const int32_t *obs_kf,
-                                          const int32_t *obs_idx, int32_t *best_obs, uint8_t *best_desc) {
+// map != NULL (orbx_keyframe_distinctive_descriptors_to_map): best_desc stays in the arena and k_map_scatter_desc writes its rows into the slots set_id
+// names, ordered as an update of the table.
+static int keyframe_distinctive_impl(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, int n_sets, const int32_t *set_ptr, const int32_t *obs_kf,
+                                     const int32_t *obs_idx, int32_t *best_obs, uint8_t *best_desc, orbx_map *map, const int32_t *set_id) {
     if (!m || n_kf < 0 || n_sets < 0 || (n_kf > 0 && !kfs) || (n_sets > 0 && (!set_ptr || !best_obs))) return ORBX_E_BAD_ARG;
     if (n_kf > ORBX_MAX_DISTINCTIVE_KEYFRAMES) return ORBX_E_TOO_LARGE;
     if (n_sets == 0) return ORBX_OK;
@@ -3622,6 +3873,12 @@ int orbx_keyframe_distinctive_descriptors(orbx_matcher *m, int n_kf, orbx_keyfra
     }
     const size_t total = (size_t)set_ptr[n_sets];
     if (total > 0 && (!obs_kf || !obs_idx)) return ORBX_E_BAD_ARG;
+    std::unique_lock<std::mutex> map_lock;   // held to the end of an update of the table
+    if (map) {
+        if (map->device != m->device || !set_id) return ORBX_E_BAD_ARG;
+        map_lock = std::unique_lock<std::mutex>(map->mu);
+        if (!map_ids_ok(map, n_sets, set_id, true)) return ORBX_E_BAD_ARG;
+    }
     bool pending = false;
     for (int k = 0; k < n_kf; k++) {
         if (!kfs[k] || kfs[k]->device != m->device) return ORBX_E_BAD_ARG;
@@ -3642,14 +3899,16 @@ int orbx_keyframe_distinctive_descriptors(orbx_matcher *m, int n_kf, orbx_keyfra
     DistinctSets A;
     memset(&A, 0, sizeof(A));
     A.n_kf = n_kf; A.n_sets = n_sets;
-    const int32_t *dlarge = nullptr;
+    const int32_t *dlarge = nullptr, *dset_id = nullptr;
     ORBX_TRY(m->carve([&](Carve &C) {
         A.set_ptr = C.up(set_ptr, (size_t)n_sets + 1); A.obs_kf = C.up(obs_kf, total); A.obs_idx = C.up(obs_idx, total);
         A.kf = C.up(recs.data(), (size_t)n_kf);
         if (!large.empty()) dlarge = C.up(large.data(), large.size());
+        if (map) dset_id = C.up(set_id, (size_t)n_sets);
         A.best_obs = C.take<int32_t>(n_sets); A.flag = C.take<int32_t>(4);   // (best_obs between the uploads and the flag's fill: one k_xfer launch for both)
         if (best_desc) A.best_desc = C.take<uint8_t>(32 * (size_t)n_sets);
         if (pending) A.counts_out = C.take<int32_t>(2 * (size_t)n_kf);
+        if (map) A.best_desc = C.take<uint8_t>(32 * (size_t)n_sets);   // (not downloaded: behind the result run)
         if (!large.empty()) A.scratch = C.take<uint8_t>(32 * total);
     }));
     ORBX_HIP(m->fill(A.flag, 0, 16));
@@ -3657,6 +3916,13 @@ int orbx_keyframe_distinctive_descriptors(orbx_matcher *m, int n_kf, orbx_keyfra
     const unsigned grid = (unsigned)std::max((n_sets + 3) / 4, (n_kf + 255) / 256);
     hipLaunchKernelGGL(k_distinctive_kf, dim3(grid), dim3(256), 0, m->exec(), A);
     if (!large.empty()) hipLaunchKernelGGL(k_distinctive_kf_large, dim3((unsigned)large.size()), dim3(64 * kDistinctLargeWaves), 0, m->exec(), A, dlarge);
+    if (map) {
+        if (map->write_seq > 0) ORBX_HIP(hipStreamWaitEvent(m->stream, map->written, 0));
+        hipLaunchKernelGGL(k_map_scatter_desc, dim3((unsigned)((n_sets + 127) / 128)), dim3(256), 0, m->exec(), map->rec, map->capacity, n_sets, dset_id,
+                           (const int32_t *)A.best_obs, (const int32_t *)A.flag, (const uint8_t *)A.best_desc);
+        ORBX_HIP(hipEventRecord(map->written, m->stream));
+        map->write_seq++;
+    }
     ORBX_HIP(hipGetLastError());
     int32_t flag = 0;
     std::vector<int32_t> counts(pending ? 2 * (size_t)n_kf : 0);
@@ -3670,6 +3936,16 @@ int orbx_keyframe_distinctive_descriptors(orbx_matcher *m, int n_kf, orbx_keyfra
         if (kfs[k]->host_n() < 0) kfs[k]->adopt(counts[2 * (size_t)k], counts[2 * (size_t)k + 1]);
     if (flag) { set_error("an observation index outside [0, N) of its key frame"); return ORBX_E_BAD_ARG; }
     return ORBX_OK;
+}
+
+int orbx_keyframe_distinctive_descriptors(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, int n_sets, const int32_t *set_ptr, const int32_t *obs_kf,
+                                          const int32_t *obs_idx, int32_t *best_obs, uint8_t *best_desc) {
+    return keyframe_distinctive_impl(m, n_kf, kfs, n_sets, set_ptr, obs_kf, obs_idx, best_obs, best_desc, nullptr, nullptr);
+}
+int orbx_keyframe_distinctive_descriptors_to_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, int n_sets, const int32_t *set_ptr,
+                                                 const int32_t *obs_kf, const int32_t *obs_idx, orbx_map *map, const int32_t *set_id, int32_t *best_obs) {
+    if (!map) return ORBX_E_BAD_ARG;
+    return keyframe_distinctive_impl(m, n_kf, kfs, n_sets, set_ptr, obs_kf, obs_idx, best_obs, nullptr, map, set_id);
 }
 
 }  // extern "C"
@@ -3863,16 +4139,16 @@ namespace {
 // keyframe_problem, N_left features for the replay, while the caller's match / occupied rows span N = N_left + N_right as vpMatched does.
 int keyframe_search_by_projection_sim3_impl(orbx_matcher *m, bool fisheye, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
                                             const orbx_frame_pose *poses, const orbx_fisheye_view *views, float th, float ratio_hamming,
-                                            float log_scale_factor, int projection_form, int n_mp, const float *pos, const float *normal,
-                                            const float *min_dist, const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip,
+                                            float log_scale_factor, int projection_form, const MapPoints &src, const uint8_t *skip,
                                             const uint8_t *const *occupied, int32_t *const *match, int32_t *nmatches, uint8_t *projected, float *proj_u,
                                             float *proj_v) {
+    const int n_mp = src.n;
     if (!m || n_kf < 0 || n_mp < 0 || (n_kf > 0 && (!kfs || (fisheye ? !views : !cams || !poses) || !match || !nmatches))) return ORBX_E_BAD_ARG;
     if ((projection_form != ORBX_SIM3_PROJECT_CAMERA && projection_form != ORBX_SIM3_PROJECT_INVZ) || (proj_u == nullptr) != (proj_v == nullptr))
         return ORBX_E_BAD_ARG;
     if (n_kf > ORBX_MAX_FUSE_KEYFRAMES) return ORBX_E_TOO_LARGE;
     const size_t np = (size_t)n_mp, total = (size_t)n_kf * np;
-    if (total > 0 && (!pos || !normal || !min_dist || !max_dist || !mp_desc)) return ORBX_E_BAD_ARG;
+    if (total > 0 && !map_points_ok(m, src)) return ORBX_E_BAD_ARG;
     for (int k = 0; k < n_kf; k++) {
         if (!kfs[k] || kfs[k]->fisheye != fisheye || kfs[k]->device != m->device || !match[k]) return ORBX_E_BAD_ARG;
         // k_window_best2_t and the replay take ONE GridParams per launch: the key frames of a call share their image bounds, bit for bit
@@ -3894,8 +4170,9 @@ int keyframe_search_by_projection_sim3_impl(orbx_matcher *m, bool fisheye, int n
     if (total == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(m->device));
     const int32_t cnt4[4] = {n_mp, 0, 0, 0};
-    float *dp, *dn, *dmn, *dmx, *qx, *qy, *qr;
-    uint8_t *dd, *dskip, *qvalid;
+    float *qx, *qy, *qr;
+    uint8_t *dskip, *qvalid;
+    MapPointsDev D;
     int32_t *dcnt, *qmin, *qmax, *dmeta, *dentries, *dnm;
     orbx_camera *dcam;
     orbx_frame_pose *dpose;
@@ -3908,8 +4185,7 @@ int keyframe_search_by_projection_sim3_impl(orbx_matcher *m, bool fisheye, int n
     std::vector<int32_t *> dmatch((size_t)n_kf, nullptr);
     ORBX_TRY(m->carve([&](Carve &A) {
         // uploads, adjacent in the arena (one run): the map points ONCE, then what grows with n_kf -- cameras, poses, skip and occupancy rows, records
-        dp = A.up(pos, 3 * np); dn = A.up(normal, 3 * np); dmn = A.up(min_dist, np); dmx = A.up(max_dist, np);
-        dd = A.up(mp_desc, 32 * np);
+        D = map_points_up(A, src);
         dcnt = A.up(cnt4, 4);
         dcam = fisheye ? nullptr : A.up(cams, (size_t)n_kf); dpose = fisheye ? nullptr : A.up(poses, (size_t)n_kf);
         dview = fisheye ? A.up(reinterpret_cast<const FisheyeView *>(views), (size_t)n_kf) : nullptr;
@@ -3934,7 +4210,7 @@ int keyframe_search_by_projection_sim3_impl(orbx_matcher *m, bool fisheye, int n
         WindowProblem &W = K[(size_t)k].P;
         W.occupied0 = docc[(size_t)k];
         W.qx = qx + o; W.qy = qy + o; W.qr = qr + o; W.qmin = qmin + o; W.qmax = qmax + o; W.qvalid = qvalid + o;
-        W.qdesc = dd; W.nq_ptr = dcnt;
+        W.qdesc = D.desc; W.nq_ptr = dcnt;
         W.keys = dkeys + o * kTopK; W.meta = dmeta + o;
         P[(size_t)k] = W;
         ResolveProblem &Q = R[(size_t)k];
@@ -3946,6 +4222,9 @@ int keyframe_search_by_projection_sim3_impl(orbx_matcher *m, bool fisheye, int n
     ORBX_TRY(m->h2d(dP, P.data(), sizeof(WindowProblem) * (size_t)n_kf));
     ORBX_TRY(m->h2d(dR, R.data(), sizeof(ResolveProblem) * (size_t)n_kf));
     ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
+    uint64_t seq = 0;
+    ORBX_TRY(map_points_gather(m, src, D, &seq));
+    const float *dp = D.pos, *dn = D.normal, *dmn = D.min_dist, *dmx = D.max_dist;
     const dim3 pgrid((unsigned)((n_mp + 255) / 256), (unsigned)n_kf);
     if (fisheye)
         hipLaunchKernelGGL(k_sim3_project_kb8, pgrid, dim3(256), 0, m->exec(), (const KfProblem *)dK, (const FisheyeView *)dview, th, log_scale_factor,
@@ -3965,6 +4244,7 @@ int keyframe_search_by_projection_sim3_impl(orbx_matcher *m, bool fisheye, int n
     ORBX_TRY(m->d2h(nmatches, dnm, 4 * (size_t)n_kf));
     ORBX_TRY(m->sync_and_deliver());
     keyframe_release(kfs, n_kf);
+    map_points_done(src, seq);
     return ORBX_OK;
 }
 
@@ -3976,8 +4256,18 @@ extern "C" int orbx_keyframe_search_by_projection_sim3(orbx_matcher *m, int n_kf
                                                        const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip,
                                                        const uint8_t *const *occupied, int32_t *const *match, int32_t *nmatches, uint8_t *projected,
                                                        float *proj_u, float *proj_v) {
-    return keyframe_search_by_projection_sim3_impl(m, false, n_kf, kfs, cams, poses, nullptr, th, ratio_hamming, log_scale_factor, projection_form, n_mp, pos,
-                                                   normal, min_dist, max_dist, mp_desc, skip, occupied, match, nmatches, projected, proj_u, proj_v);
+    return keyframe_search_by_projection_sim3_impl(m, false, n_kf, kfs, cams, poses, nullptr, th, ratio_hamming, log_scale_factor, projection_form,
+                                                   MapPoints{n_mp, pos, normal, min_dist, max_dist, mp_desc, nullptr, nullptr}, skip, occupied, match, nmatches,
+                                                   projected, proj_u, proj_v);
+}
+extern "C" int orbx_keyframe_search_by_projection_sim3_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
+                                                           const orbx_frame_pose *poses, float th, float ratio_hamming, float log_scale_factor,
+                                                           int projection_form, int n_mp, orbx_map *map, const int32_t *ids, const uint8_t *skip,
+                                                           const uint8_t *const *occupied, int32_t *const *match, int32_t *nmatches, uint8_t *projected,
+                                                           float *proj_u, float *proj_v) {
+    if (!map_form_ok(map, n_mp)) return ORBX_E_BAD_ARG;
+    return keyframe_search_by_projection_sim3_impl(m, false, n_kf, kfs, cams, poses, nullptr, th, ratio_hamming, log_scale_factor, projection_form,
+                                                   map_points_of(n_mp, map, ids), skip, occupied, match, nmatches, projected, proj_u, proj_v);
 }
 
 extern "C" int orbx_keyframe_search_by_projection_sim3_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views,
@@ -3986,22 +4276,47 @@ extern "C" int orbx_keyframe_search_by_projection_sim3_fisheye(orbx_matcher *m, 
                                                                const uint8_t *mp_desc, const uint8_t *skip, const uint8_t *const *occupied,
                                                                int32_t *const *match, int32_t *nmatches, uint8_t *projected, float *proj_u,
                                                                float *proj_v) {
-    return keyframe_search_by_projection_sim3_impl(m, true, n_kf, kfs, nullptr, nullptr, views, th, ratio_hamming, log_scale_factor, projection_form, n_mp, pos,
-                                                   normal, min_dist, max_dist, mp_desc, skip, occupied, match, nmatches, projected, proj_u, proj_v);
+    return keyframe_search_by_projection_sim3_impl(m, true, n_kf, kfs, nullptr, nullptr, views, th, ratio_hamming, log_scale_factor, projection_form,
+                                                   MapPoints{n_mp, pos, normal, min_dist, max_dist, mp_desc, nullptr, nullptr}, skip, occupied, match, nmatches,
+                                                   projected, proj_u, proj_v);
+}
+extern "C" int orbx_keyframe_search_by_projection_sim3_fisheye_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views,
+                                                                   float th, float ratio_hamming, float log_scale_factor, int projection_form, int n_mp,
+                                                                   orbx_map *map, const int32_t *ids, const uint8_t *skip,
+                                                                   const uint8_t *const *occupied, int32_t *const *match, int32_t *nmatches,
+                                                                   uint8_t *projected, float *proj_u, float *proj_v) {
+    if (!map_form_ok(map, n_mp)) return ORBX_E_BAD_ARG;
+    return keyframe_search_by_projection_sim3_impl(m, true, n_kf, kfs, nullptr, nullptr, views, th, ratio_hamming, log_scale_factor, projection_form,
+                                                   map_points_of(n_mp, map, ids), skip, occupied, match, nmatches, projected, proj_u, proj_v);
 }
 
 extern "C" int orbx_keyframe_fuse_map_points_sim3_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views, float th,
                                                           float log_scale_factor, int n_mp, const float *pos, const float *normal,
                                                           const float *min_dist, const float *max_dist, const uint8_t *mp_desc, const uint8_t *skip,
                                                           int32_t *best_idx, int32_t *best_dist, uint8_t *projected) {
-    return keyframe_fuse_map_points_impl(m, true, true, n_kf, kfs, nullptr, nullptr, views, th, log_scale_factor, 0, n_mp, pos, normal, min_dist, max_dist,
-                                         mp_desc, skip, best_idx, best_dist, projected);
+    return keyframe_fuse_map_points_impl(m, true, true, n_kf, kfs, nullptr, nullptr, views, th, log_scale_factor, 0,
+                                         MapPoints{n_mp, pos, normal, min_dist, max_dist, mp_desc, nullptr, nullptr}, skip, best_idx, best_dist, projected);
+}
+extern "C" int orbx_keyframe_fuse_map_points_sim3_fisheye_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_fisheye_view *views,
+                                                              float th, float log_scale_factor, int n_mp, orbx_map *map, const int32_t *ids,
+                                                              const uint8_t *skip, int32_t *best_idx, int32_t *best_dist, uint8_t *projected) {
+    if (!map_form_ok(map, n_mp)) return ORBX_E_BAD_ARG;
+    return keyframe_fuse_map_points_impl(m, true, true, n_kf, kfs, nullptr, nullptr, views, th, log_scale_factor, 0, map_points_of(n_mp, map, ids), skip,
+                                         best_idx, best_dist, projected);
 }
 
 extern "C" int orbx_keyframe_fuse_map_points_sim3(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
                                                   const orbx_frame_pose *poses, float th, float log_scale_factor, int n_mp, const float *pos,
                                                   const float *normal, const float *min_dist, const float *max_dist, const uint8_t *mp_desc,
                                                   const uint8_t *skip, int32_t *best_idx, int32_t *best_dist, uint8_t *projected) {
-    return keyframe_fuse_map_points_impl(m, false, true, n_kf, kfs, cams, poses, nullptr, th, log_scale_factor, 0, n_mp, pos, normal, min_dist, max_dist,
-                                         mp_desc, skip, best_idx, best_dist, projected);
+    return keyframe_fuse_map_points_impl(m, false, true, n_kf, kfs, cams, poses, nullptr, th, log_scale_factor, 0,
+                                         MapPoints{n_mp, pos, normal, min_dist, max_dist, mp_desc, nullptr, nullptr}, skip, best_idx, best_dist, projected);
+}
+extern "C" int orbx_keyframe_fuse_map_points_sim3_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
+                                                      const orbx_frame_pose *poses, float th, float log_scale_factor, int n_mp, orbx_map *map,
+                                                      const int32_t *ids, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist,
+                                                      uint8_t *projected) {
+    if (!map_form_ok(map, n_mp)) return ORBX_E_BAD_ARG;
+    return keyframe_fuse_map_points_impl(m, false, true, n_kf, kfs, cams, poses, nullptr, th, log_scale_factor, 0, map_points_of(n_mp, map, ids), skip,
+                                         best_idx, best_dist, projected);
 }

@@ -259,6 +259,55 @@ class DeviceKeyFrame:
     __del__ = close
 
 
+class DeviceMap:
+    """A device-resident table of map points (orbx_map, include/orbx.h): `capacity` slots of pos, normal, min_dist, max_dist and the 32-byte
+    descriptor, addressed by ids in [0, capacity) that the caller assigns.  It belongs to no matcher: every ORBmatcher of its device may update and
+    read it, and the ...Map forms of the one-call searches take (map, ids) where the flat forms take the five arrays.  update() after SetWorldPos /
+    UpdateNormalAndDepth / a bundle adjustment's write-back / ComputeDistinctiveDescriptors, erase() at SetBadFlag.  The caller does not run
+    update / erase concurrently with a call that reads the table (the reference's Map::mMutexMapUpdate).  close() (or garbage collection) frees it;
+    no call that was handed the table may be running then."""
+
+    def __init__(self, capacity: int, device: int = 0):
+        self._L = _lib.lib()
+        h = C.c_void_p()
+        check(self._L.orbx_map_create(int(device), int(capacity), C.byref(h)), "orbx_map_create")
+        self._h = h
+        self.capacity = int(capacity)
+
+    def update(self, matcher: "ORBmatcher", ids, pos=None, normal=None, min_dist=None, max_dist=None, desc=None):
+        """Row j of the given arrays -> slot ids[j]; None keeps that field (a slot's first update gives all five).  Returns without waiting."""
+        i = _i32(ids)
+        P = None if pos is None else _f32(np.asarray(pos).reshape(-1, 3))
+        Nn = None if normal is None else _f32(np.asarray(normal).reshape(-1, 3))
+        mn, mx, d = _f32(min_dist), _f32(max_dist), _u8(desc)
+        for a, w in ((P, 3), (Nn, 3), (mn, 1), (mx, 1), (d, 32)):
+            assert a is None or a.size == len(i) * w, "one row per id"
+        check(self._L.orbx_map_update(matcher._h, self._h, len(i), ptr(i), ptr(P), ptr(Nn), ptr(mn), ptr(mx), ptr(d)), "orbx_map_update")
+        return self
+
+    def erase(self, ids):
+        i = _i32(ids)
+        check(self._L.orbx_map_erase(self._h, len(i), ptr(i)), "orbx_map_erase")
+        return self
+
+    def read(self, matcher: "ORBmatcher", ids) -> dict:
+        """dict(pos [n, 3], normal [n, 3], min_dist, max_dist, desc [n, 32]) of the slots ids names; one synchronisation."""
+        i = _i32(ids)
+        n = len(i)
+        out = dict(pos=np.zeros((n, 3), np.float32), normal=np.zeros((n, 3), np.float32), min_dist=np.zeros(n, np.float32),
+                   max_dist=np.zeros(n, np.float32), desc=np.zeros((n, 32), np.uint8))
+        check(self._L.orbx_map_read(matcher._h, self._h, n, ptr(i), ptr(out["pos"]), ptr(out["normal"]), ptr(out["min_dist"]), ptr(out["max_dist"]),
+                                    ptr(out["desc"])), "orbx_map_read")
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_map_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
 def _f32(a):
     return None if a is None else np.ascontiguousarray(a, np.float32)
 
@@ -1075,6 +1124,149 @@ class ORBmatcher:
                                                                  ptr(mx), ptr(d), ptr(sk), ptr(bi), ptr(bd), ptr(pr)),
               "orbx_keyframe_fuse_map_points_sim3_fisheye")
         return bi, bd, pr
+
+    # ---- the one-call searches with their map points resident (orbx_map): (map, ids) where the flat forms take the five arrays ----
+    def SearchLocalPointsMap(self, F: DeviceFrame, cam, pose, log_scale_factor, cos_limit, map: DeviceMap, ids, eligible=None, has_obs=None,
+                             th: float = 1.0, far_points: bool = False, th_far_points: float = 0.0, frame_occupied=None):
+        """SearchLocalPoints with the map points named by id (orbx_frame_search_local_points_map): eligible / has_obs / in_view entry j belongs to
+        ids[j] and frame_match holds POSITIONS in ids.  Returns (nmatches, frame_match[N], in_view[n_mp]) as SearchLocalPoints on the slots' rows."""
+        from ._lib import Camera, FramePose
+        i, el, ho, occ = _i32(ids), _u8(eligible), _u8(has_obs), _u8(frame_occupied)
+        iv = np.zeros(len(i), np.uint8)
+        fm = np.full(self._frame_rows(F, occ), -1, np.int32)
+        c, p = Camera(*[float(x) for x in cam]), FramePose.make(*pose)
+        n = check(self._L.orbx_frame_search_local_points_map(self._h, F._h, ptr(occ), C.byref(c), C.byref(p), float(log_scale_factor), float(cos_limit),
+                                                             len(i), map._h, ptr(i), ptr(el), ptr(ho), float(th), self.mfNNratio,
+                                                             int(bool(far_points)), float(th_far_points), ptr(iv), ptr(fm)),
+                  "orbx_frame_search_local_points_map")
+        return n, fm[:F.count()], iv
+
+    def SearchLocalPointsFisheyeMap(self, F: DeviceFrame, views, log_scale_factor, cos_limit, map: DeviceMap, ids, eligible=None, has_obs=None,
+                                    track_depth=None, th: float = 1.0, far_points: bool = False, th_far_points: float = 0.0, frame_occupied=None):
+        """SearchLocalPointsFisheye with the map points named by id (orbx_frame_search_local_points_fisheye_map).
+        Returns (nmatches, frame_match[N], in_view[2, n_mp])."""
+        i, el, ho, td, occ = _i32(ids), _u8(eligible), _u8(has_obs), _f32(track_depth), _u8(frame_occupied)
+        V = np.ascontiguousarray(np.concatenate([np.concatenate([np.asarray(x, np.float32).ravel() for x in v]) for v in views]), np.float32)
+        assert V.size == 46, "views: left and right camera"
+        iv = np.zeros((2, len(i)), np.uint8)
+        fm = np.full(self._frame_rows(F, occ), -1, np.int32)
+        n = check(self._L.orbx_frame_search_local_points_fisheye_map(self._h, F._h, ptr(occ), ptr(V), float(log_scale_factor), float(cos_limit), len(i),
+                                                                     map._h, ptr(i), ptr(el), ptr(ho), ptr(td), float(th), self.mfNNratio,
+                                                                     int(bool(far_points)), float(th_far_points), ptr(iv), ptr(fm)),
+                  "orbx_frame_search_local_points_fisheye_map")
+        return n, fm[:F.count()], iv
+
+    def _pinhole_map_args(self, kfs, cams, poses, ids, skip):
+        from ._lib import Camera, FramePose
+        K, i = len(kfs), _i32(ids)
+        assert len(cams) == K and len(poses) == K
+        sk = None if skip is None else _u8(np.asarray(skip).reshape(K, len(i)))
+        cs = (Camera * max(K, 1))(*[Camera(*[float(x) for x in c]) for c in cams])
+        ps = (FramePose * max(K, 1))(*[FramePose.make(*p) for p in poses])
+        return K, i, sk, self._kf_handles(kfs), cs, ps
+
+    def _fisheye_map_args(self, kfs, views, ids, skip, per_kf: int):
+        K, i = len(kfs), _i32(ids)
+        assert len(views) == K
+        sk = None if skip is None else _u8(np.asarray(skip).reshape(K, len(i)))
+        V = np.zeros(23 * per_kf * max(K, 1), np.float32)   # per_kf orbx_fisheye_view records per key frame
+        for k, v in enumerate(views):
+            cams = v if per_kf == 2 else (v,)
+            V[23 * per_kf * k:23 * per_kf * (k + 1)] = np.concatenate([np.asarray(x, np.float32).ravel() for cam in cams for x in cam])
+        return K, i, sk, self._kf_handles(kfs), V
+
+    def FuseMapPointsMap(self, kfs, cams, poses, map: DeviceMap, ids, th: float = 3.0, log_scale_factor: float = 0.0, skip=None,
+                         strict_fp: bool = False, want_projected: bool = True):
+        """FuseMapPoints with the map points named by id (orbx_keyframe_fuse_map_points_map).  Returns (best_idx [K, n], best_dist, projected)."""
+        K, i, sk, hs, cs, ps = self._pinhole_map_args(kfs, cams, poses, ids, skip)
+        n = len(i)
+        bi, bd = np.full((K, n), -1, np.int32), np.full((K, n), 256, np.int32)
+        pr = np.zeros((K, n), np.uint8) if want_projected else None
+        check(self._L.orbx_keyframe_fuse_map_points_map(self._h, K, hs, cs, ps, float(th), float(log_scale_factor), int(bool(strict_fp)), n, map._h,
+                                                        ptr(i), ptr(sk), ptr(bi), ptr(bd), ptr(pr)), "orbx_keyframe_fuse_map_points_map")
+        return bi, bd, pr
+
+    def FuseMapPointsFisheyeMap(self, kfs, views, map: DeviceMap, ids, th: float = 3.0, log_scale_factor: float = 0.0, skip=None,
+                                strict_fp: bool = False, want_projected: bool = True):
+        """FuseMapPointsFisheye with the map points named by id (orbx_keyframe_fuse_map_points_fisheye_map).
+        Returns (best_idx [K, 2, n], best_dist [K, 2, n], projected [K, 2, n] or None)."""
+        K, i, sk, hs, V = self._fisheye_map_args(kfs, views, ids, skip, 2)
+        n = len(i)
+        bi, bd = np.full((K, 2, n), -1, np.int32), np.full((K, 2, n), 256, np.int32)
+        pr = np.zeros((K, 2, n), np.uint8) if want_projected else None
+        check(self._L.orbx_keyframe_fuse_map_points_fisheye_map(self._h, K, hs, ptr(V), float(th), float(log_scale_factor), int(bool(strict_fp)), n,
+                                                                map._h, ptr(i), ptr(sk), ptr(bi), ptr(bd), ptr(pr)),
+              "orbx_keyframe_fuse_map_points_fisheye_map")
+        return bi, bd, pr
+
+    def FuseMapPointsSim3Map(self, kfs, cams, poses, map: DeviceMap, ids, th: float = 3.0, log_scale_factor: float = 0.0, skip=None,
+                             want_projected: bool = True):
+        """FuseMapPointsSim3 with the map points named by id (orbx_keyframe_fuse_map_points_sim3_map)."""
+        K, i, sk, hs, cs, ps = self._pinhole_map_args(kfs, cams, poses, ids, skip)
+        n = len(i)
+        bi, bd = np.full((K, n), -1, np.int32), np.full((K, n), 256, np.int32)
+        pr = np.zeros((K, n), np.uint8) if want_projected else None
+        check(self._L.orbx_keyframe_fuse_map_points_sim3_map(self._h, K, hs, cs, ps, float(th), float(log_scale_factor), n, map._h, ptr(i), ptr(sk),
+                                                             ptr(bi), ptr(bd), ptr(pr)), "orbx_keyframe_fuse_map_points_sim3_map")
+        return bi, bd, pr
+
+    def FuseMapPointsSim3FisheyeMap(self, kfs, views, map: DeviceMap, ids, th: float = 3.0, log_scale_factor: float = 0.0, skip=None,
+                                    want_projected: bool = True):
+        """FuseMapPointsSim3Fisheye with the map points named by id (orbx_keyframe_fuse_map_points_sim3_fisheye_map)."""
+        K, i, sk, hs, V = self._fisheye_map_args(kfs, views, ids, skip, 1)
+        n = len(i)
+        bi, bd = np.full((K, n), -1, np.int32), np.full((K, n), 256, np.int32)
+        pr = np.zeros((K, n), np.uint8) if want_projected else None
+        check(self._L.orbx_keyframe_fuse_map_points_sim3_fisheye_map(self._h, K, hs, ptr(V), float(th), float(log_scale_factor), n, map._h, ptr(i),
+                                                                     ptr(sk), ptr(bi), ptr(bd), ptr(pr)),
+              "orbx_keyframe_fuse_map_points_sim3_fisheye_map")
+        return bi, bd, pr
+
+    def _sim3_search_outputs(self, kfs, K, n, occupied, want_projected, want_uv):
+        keep, occ = self._flag_rows(occupied, K)
+        match = [np.full(kf.count(), -1, np.int32) for kf in kfs]
+        rows = (C.c_void_p * max(K, 1))(*[ptr(x) for x in match])
+        nm = np.zeros(max(K, 1), np.int32)
+        pr = np.zeros((K, n), np.uint8) if want_projected else None
+        pu, pv = (np.zeros((K, n), np.float32), np.zeros((K, n), np.float32)) if want_uv else (None, None)
+        return keep, (occ if occupied is not None else None), match, rows, nm, pr, pu, pv
+
+    def SearchByProjectionSim3KeyFramesMap(self, kfs, cams, poses, map: DeviceMap, ids, th: float, ratio_hamming: float = 1.0,
+                                           log_scale_factor: float = 0.0, projection_form: int = _lib.SIM3_PROJECT_CAMERA, skip=None, occupied=None,
+                                           want_projected: bool = True, want_uv: bool = False):
+        """SearchByProjectionSim3KeyFrames with the map points named by id (orbx_keyframe_search_by_projection_sim3_map): a match row holds
+        POSITIONS in ids.  Returns (nmatches [K], match, projected [K, n] or None, (proj_u, proj_v) or None)."""
+        K, i, sk, hs, cs, ps = self._pinhole_map_args(kfs, cams, poses, ids, skip)
+        keep, occ, match, rows, nm, pr, pu, pv = self._sim3_search_outputs(kfs, K, len(i), occupied, want_projected, want_uv)
+        check(self._L.orbx_keyframe_search_by_projection_sim3_map(self._h, K, hs, cs, ps, float(th), float(ratio_hamming), float(log_scale_factor),
+                                                                  int(projection_form), len(i), map._h, ptr(i), ptr(sk), occ, rows, ptr(nm), ptr(pr),
+                                                                  ptr(pu), ptr(pv)), "orbx_keyframe_search_by_projection_sim3_map")
+        del keep
+        return nm[:K], match, pr, ((pu, pv) if want_uv else None)
+
+    def SearchByProjectionSim3KeyFramesFisheyeMap(self, kfs, views, map: DeviceMap, ids, th: float, ratio_hamming: float = 1.0,
+                                                  log_scale_factor: float = 0.0, projection_form: int = _lib.SIM3_PROJECT_CAMERA, skip=None,
+                                                  occupied=None, want_projected: bool = True, want_uv: bool = False):
+        """SearchByProjectionSim3KeyFramesFisheye with the map points named by id (orbx_keyframe_search_by_projection_sim3_fisheye_map)."""
+        K, i, sk, hs, V = self._fisheye_map_args(kfs, views, ids, skip, 1)
+        keep, occ, match, rows, nm, pr, pu, pv = self._sim3_search_outputs(kfs, K, len(i), occupied, want_projected, want_uv)
+        check(self._L.orbx_keyframe_search_by_projection_sim3_fisheye_map(self._h, K, hs, ptr(V), float(th), float(ratio_hamming),
+                                                                          float(log_scale_factor), int(projection_form), len(i), map._h, ptr(i),
+                                                                          ptr(sk), occ, rows, ptr(nm), ptr(pr), ptr(pu), ptr(pv)),
+              "orbx_keyframe_search_by_projection_sim3_fisheye_map")
+        del keep
+        return nm[:K], match, pr, ((pu, pv) if want_uv else None)
+
+    def DistinctiveDescriptorsKeyFramesToMap(self, kfs, set_ptr, obs_kf, obs_idx, map: DeviceMap, set_id):
+        """DistinctiveDescriptorsKeyFrames with set s's winning row written into the descriptor of slot set_id[s] of the table
+        (orbx_keyframe_distinctive_descriptors_to_map); an empty set leaves its slot as it is.  Returns best_obs[n_sets]."""
+        sp, ok, oi, si = _i32(set_ptr), _i32(obs_kf), _i32(obs_idx), _i32(set_id)
+        n_sets = len(sp) - 1
+        assert n_sets >= 0 and len(ok) == len(oi) and len(si) == n_sets and (n_sets == 0 or sp[-1] <= len(ok))
+        best = np.full(n_sets, -1, np.int32)
+        check(self._L.orbx_keyframe_distinctive_descriptors_to_map(self._h, len(kfs), self._kf_handles(kfs), n_sets, ptr(sp), ptr(ok), ptr(oi),
+                                                                   map._h, ptr(si), ptr(best)), "orbx_keyframe_distinctive_descriptors_to_map")
+        return best
 
     # ---- SearchBySim3 (ORBmatcher.cc:1457-1674): two gate-less fuse searches + mutual agreement ----
     def SearchBySim3(self, KF1: FrameView, KF2: FrameView, side1: dict, side2: dict, th: float, already_matched1=None,
