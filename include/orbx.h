@@ -1121,6 +1121,59 @@ int orbx_keyframe_search_by_projection_sim3_fisheye_map(orbx_matcher *m, int n_k
                                                         const int32_t *ids, const uint8_t *skip, const uint8_t *const *occupied,
                                                         int32_t *const *match, int32_t *nmatches, uint8_t *projected, float *proj_u, float *proj_v);
 
+/* The Tracking thread's two searches whose queries are ANOTHER frame's map points, from map ids, on a monocular / rectified resident frame:
+ *   orbx_frame_track_last_frame_map               SearchByProjection(CurrentFrame, LastFrame, th, bMono)  (ORBmatcher.cc:1676-1887,
+ *                                                 Tracking::TrackWithMotionModel); the source is `last`, a handle of the same matcher and kind
+ *   orbx_frame_search_by_projection_keyframe_map  SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist)  (:1889-2010,
+ *                                                 Tracking::Relocalization); the source is `kf`, read for mvKeysUn[i].angle only
+ * Their flat forms (orbx_frame_search_by_projection_frame / _window) take queries the caller projected on the host, about 70 bytes each.  Here
+ * ids [n_ids] has one entry per feature of the source, n_ids = its N: the map slot of mvpMapPoints[i], or -1 (track_last_frame: no point or
+ * mvbOutlier[i]; keyframe: no point, isBad(), or in sAlreadyFound).  The projection, the gates and the windows are evaluated on the device
+ * (k_track_project reads the source's row and the slot's record directly: no k_map_gather, no flat arrays) in the order and rounding of the host
+ * loops they replace:
+ *   x3Dc = Rcw p + tcw (pose: the CURRENT frame's); track_last_frame: invzc = 1 / z, reject invzc < 0 -- keyframe: NO depth gate
+ *   Pinhole::project; reject u < mnMinX || u > mnMaxX, likewise v (both sides inclusive)
+ *   track_last_frame: ur = u - bf invzc; r = th * scale[octave of the source's row i], searched iff 0 <= octave < nlevels; levels by level_mode
+ *                     (0: [o-1, o+1], 1: bForward, 2: bBackward -- the caller's, from the two poses and mb)
+ *   keyframe:         dist3D = |p - Ow| within [0.8f mfMinDistance, 1.2f mfMaxDistance]; PredictScale(dist3D, &CurrentFrame) with
+ *                     log_scale_factor; r = th * scale[l]; levels [l-1, l+1]; accepted iff (float)bestDist <= max_dist
+ * cur_match / match [N of cur]: as the flat forms write them (-1 never assigned, -2 cleared by the rotation check), but a value >= 0 is the SOURCE
+ * FEATURE INDEX i -- the caller writes Cur.mvpMapPoints[j] = Source.mvpMapPoints[match[j]].  has_obs [n_ids] (may be NULL: all true) as q_has_obs.
+ * Optional outputs [n_ids]: projected[i] = 1 where entry i passed every gate above, proj_u / proj_v (both or neither) its (u, v).
+ * The same id may appear twice.  The calls work while the counts of cur and of the source are still on the device: entries at or beyond the source's
+ * count are switched off there.  One upload run (4 bytes per id, a flag byte, the occupancy mask), one download run, one synchronisation; the launches
+ * of the flat handle form plus one.  Ordered against orbx_map_update as every reading call.
+ * ORBX_E_BAD_ARG before anything is enqueued or a transfer counter moves: a NULL argument, cur or last of another matcher, a fisheye-stereo frame or
+ * key frame, cur == last, a map on another device, an id outside {-1} and [0, capacity), an id whose slot is not live, n_ids different from the source's
+ * count where the host knows it (above its capacity while it is pending), level_mode outside 0 .. 2; ORBX_E_TOO_LARGE as the flat forms. */
+int orbx_frame_track_last_frame_map(orbx_matcher *m, orbx_frame *cur, orbx_frame *last, const uint8_t *cur_occupied, const orbx_camera *cam,
+                                    const orbx_frame_pose *pose, orbx_map *map, int n_ids, const int32_t *ids, const uint8_t *has_obs, float th,
+                                    int level_mode, int check_orientation, int32_t *cur_match, uint8_t *projected, float *proj_u, float *proj_v);
+int orbx_frame_search_by_projection_keyframe_map(orbx_matcher *m, orbx_frame *cur, const uint8_t *occupied, const orbx_camera *cam,
+                                                 const orbx_frame_pose *pose, float log_scale_factor, orbx_keyframe *kf, orbx_map *map, int n_ids,
+                                                 const int32_t *ids, float th, float max_dist, int check_orientation, int32_t *match,
+                                                 uint8_t *projected, float *proj_u, float *proj_v);
+
+/* The same two searches for a fisheye-stereo rig (Frame::Nleft != -1): cur is a fisheye-stereo handle, `view` the LEFT camera's view of the CURRENT
+ * frame (R = Rcw, t = tcw, twc = Ow, params = mpCamera's), and the projection is KannalaBrandt8::project (kb8_project) on the device.
+ *   track_last_frame_fisheye  ORBmatcher.cc:1676-1887 with the twin :1794-1863.  `last` is a rig handle as well: ids has N = N_left + N_right entries,
+ *                             octave / angle of entry i come from mvKeys[i] below N_left and from mvKeysRight[i - N_left] beyond.  Instead of ur the
+ *                             point is carried into the right camera, x3Dr = Trl_R x3Dc + Trl_t (GetRelativePoseTrl()), and projected with the LEFT
+ *                             parameters as the reference does (:1795-1796); both cameras are searched (k_replay_twin) and cur_match holds N entries.
+ *   keyframe_fisheye          ORBmatcher.cc:1889-2010: the LEFT camera only is searched, as orbx_frame_search_by_projection_window_fisheye; kf is a rig
+ *                             key frame, angle = mvKeysUn[i].angle below N_left and 0.f beyond; occupied / match hold N entries, the right camera's
+ *                             entries of match stay -1.
+ * Everything else -- ids, -1, match values, the optional outputs, the checks, the cost shape -- as the two calls above; a monocular / rectified frame or
+ * key frame is refused here as a rig is there. */
+int orbx_frame_track_last_frame_fisheye_map(orbx_matcher *m, orbx_frame *cur, orbx_frame *last, const uint8_t *cur_occupied,
+                                            const orbx_fisheye_view *view, const float *Trl_R9, const float *Trl_t3, orbx_map *map, int n_ids,
+                                            const int32_t *ids, const uint8_t *has_obs, float th, int level_mode, int check_orientation,
+                                            int32_t *cur_match, uint8_t *projected, float *proj_u, float *proj_v);
+int orbx_frame_search_by_projection_keyframe_fisheye_map(orbx_matcher *m, orbx_frame *cur, const uint8_t *occupied, const orbx_fisheye_view *view,
+                                                         float log_scale_factor, orbx_keyframe *kf, orbx_map *map, int n_ids, const int32_t *ids,
+                                                         float th, float max_dist, int check_orientation, int32_t *match, uint8_t *projected,
+                                                         float *proj_u, float *proj_v);
+
 /* orbx_keyframe_distinctive_descriptors with the winning rows written straight into the table: the same sets, the same two kernels and the same
  * result run (best_obs -- mDescriptor's provenance -- still comes home), then k_map_scatter_desc writes set s's winning row into the descriptor of
  * slot set_id[s], ordered as an update.  An empty set (best_obs = -1) leaves its slot untouched.  set_id [n_sets] must name live slots without

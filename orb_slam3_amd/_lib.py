@@ -187,6 +187,8 @@ SYMBOLS = [
     "orbx_keyframe_fuse_map_points_sim3_map", "orbx_keyframe_fuse_map_points_sim3_fisheye_map",
     "orbx_keyframe_search_by_projection_sim3_map", "orbx_keyframe_search_by_projection_sim3_fisheye_map",
     "orbx_keyframe_distinctive_descriptors_to_map",
+    "orbx_frame_track_last_frame_map", "orbx_frame_search_by_projection_keyframe_map",
+    "orbx_frame_track_last_frame_fisheye_map", "orbx_frame_search_by_projection_keyframe_fisheye_map",
 ]
 
 
@@ -346,6 +348,11 @@ def lib() -> C.CDLL:
     L.orbx_keyframe_search_by_projection_sim3_fisheye_map.argtypes = [vp, i32, C.POINTER(vp), vp, f32, f32, f32, i32, i32, vp, vp, vp,
                                                                       C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp]
     L.orbx_keyframe_distinctive_descriptors_to_map.argtypes = [vp, i32, C.POINTER(vp), i32, vp, vp, vp, vp, vp, vp]
+    L.orbx_frame_track_last_frame_map.argtypes = [vp, vp, vp, vp, C.POINTER(Camera), C.POINTER(FramePose), vp, i32, vp, vp, f32, i32, i32, vp, vp, vp, vp]
+    L.orbx_frame_search_by_projection_keyframe_map.argtypes = [vp, vp, vp, C.POINTER(Camera), C.POINTER(FramePose), f32, vp, vp, i32, vp, f32, f32, i32,
+                                                               vp, vp, vp, vp]
+    L.orbx_frame_track_last_frame_fisheye_map.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, f32, i32, i32, vp, vp, vp, vp]
+    L.orbx_frame_search_by_projection_keyframe_fisheye_map.argtypes = [vp, vp, vp, vp, f32, vp, vp, i32, vp, f32, f32, i32, vp, vp, vp, vp]
     L.orbx_keyframe_from_frame_fisheye.argtypes = [vp, vp, vp, C.POINTER(vp)]
     L.orbx_keyframe_create_host_fisheye.argtypes = [vp, C.POINTER(FrameDesc), vp, i32, vp, C.POINTER(vp)]
     L.orbx_keyframe_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

@@ -959,6 +959,82 @@ public:
         if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_distinctive_descriptors_to_map: ") + orbx_status_string(r) + " " + orbx_last_error());
     }
 
+    // ---- The Tracking thread's searches whose queries are another frame's map points, from map ids (monocular / rectified frames): ids[i] = the
+    // slot of the source's mvpMapPoints[i] or -1; the projection, the gates and the windows run on the device (k_track_project).  vpMatch[j] >= 0 is
+    // the SOURCE feature index: CurrentFrame.mvpMapPoints[j] = Source.mvpMapPoints[vpMatch[j]]; -2 = cleared by the rotation check (set it NULL).
+    // projected / projU / projV (optional, [ids.size()]): the entries that passed every gate and their projections.
+    // SearchByProjection(CurrentFrame, LastFrame, th, bMono) (ORBmatcher.cc:1676-1887): cam / pose are the CURRENT frame's, ids[i] = -1 also for
+    // mvbOutlier[i], hasObservations[i] = Observations() > 0 (empty: all), levelMode 0 / 1 (bForward) / 2 (bBackward).
+    int TrackLastFrame(DeviceFrame &Cur, DeviceFrame &Last, const std::vector<uint8_t> &occupied, const orbx_camera &cam, const orbx_frame_pose &pose,
+                       const DeviceMap &map, const std::vector<int32_t> &ids, const std::vector<uint8_t> &hasObservations, float th, int levelMode,
+                       std::vector<int32_t> &vpMatch, std::vector<uint8_t> *projected = nullptr, std::vector<float> *projU = nullptr,
+                       std::vector<float> *projV = nullptr) {
+        if (!hasObservations.empty() && hasObservations.size() != ids.size()) throw std::invalid_argument("TrackLastFrame: one flag per id");
+        if ((projU == nullptr) != (projV == nullptr)) throw std::invalid_argument("TrackLastFrame: projU and projV together");
+        vpMatch.assign(Cur.count(), -1);
+        if (projected) projected->assign(ids.size(), 0);
+        if (projU) { projU->assign(ids.size(), 0.f); projV->assign(ids.size(), 0.f); }
+        const int r = orbx_frame_track_last_frame_map(m_, Cur.handle(), Last.handle(), occupied.empty() ? nullptr : occupied.data(), &cam, &pose, map.handle(),
+                                                      (int)ids.size(), ids.data(), hasObservations.empty() ? nullptr : hasObservations.data(), th, levelMode,
+                                                      mbCheckOrientation ? 1 : 0, vpMatch.data(), projected ? projected->data() : nullptr,
+                                                      projU ? projU->data() : nullptr, projV ? projV->data() : nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_track_last_frame_map: ") + orbx_status_string(r));
+        return r;
+    }
+    // SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORBmatcher.cc:1889-2010): ids[i] = -1 for no point, isBad() or a point in
+    // sAlreadyFound; occupied[j] = CurrentFrame.mvpMapPoints[j] != NULL.
+    int SearchByProjection(DeviceFrame &Cur, DeviceKeyFrame &KF, const std::vector<uint8_t> &occupied, const orbx_camera &cam, const orbx_frame_pose &pose,
+                           float logScaleFactor, const DeviceMap &map, const std::vector<int32_t> &ids, float th, int ORBdist,
+                           std::vector<int32_t> &vpMatch, std::vector<uint8_t> *projected = nullptr, std::vector<float> *projU = nullptr,
+                           std::vector<float> *projV = nullptr) {
+        if ((projU == nullptr) != (projV == nullptr)) throw std::invalid_argument("SearchByProjection: projU and projV together");
+        vpMatch.assign(Cur.count(), -1);
+        if (projected) projected->assign(ids.size(), 0);
+        if (projU) { projU->assign(ids.size(), 0.f); projV->assign(ids.size(), 0.f); }
+        const int r = orbx_frame_search_by_projection_keyframe_map(m_, Cur.handle(), occupied.empty() ? nullptr : occupied.data(), &cam, &pose,
+                                                                   logScaleFactor, KF.handle(), map.handle(), (int)ids.size(), ids.data(), th, (float)ORBdist,
+                                                                   mbCheckOrientation ? 1 : 0, vpMatch.data(), projected ? projected->data() : nullptr,
+                                                                   projU ? projU->data() : nullptr, projV ? projV->data() : nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_by_projection_keyframe_map: ") + orbx_status_string(r));
+        return r;
+    }
+    // The same two for a fisheye-stereo rig: view = the CURRENT frame's left camera (Rcw, tcw, Ow, mpCamera's parameters), TrlR / Trlt =
+    // GetRelativePoseTrl(); Last / KF are rig handles, ids has N_left + N_right entries, vpMatch N entries (Relocalization's form searches the left
+    // camera only: the right camera's entries stay -1).
+    int TrackLastFrameFisheye(DeviceFrame &Cur, DeviceFrame &Last, const std::vector<uint8_t> &occupied, const orbx_fisheye_view &view, const float TrlR[9],
+                              const float Trlt[3], const DeviceMap &map, const std::vector<int32_t> &ids, const std::vector<uint8_t> &hasObservations,
+                              float th, int levelMode, std::vector<int32_t> &vpMatch, std::vector<uint8_t> *projected = nullptr,
+                              std::vector<float> *projU = nullptr, std::vector<float> *projV = nullptr) {
+        if (!hasObservations.empty() && hasObservations.size() != ids.size()) throw std::invalid_argument("TrackLastFrameFisheye: one flag per id");
+        if ((projU == nullptr) != (projV == nullptr)) throw std::invalid_argument("TrackLastFrameFisheye: projU and projV together");
+        vpMatch.assign(Cur.count(), -1);
+        if (projected) projected->assign(ids.size(), 0);
+        if (projU) { projU->assign(ids.size(), 0.f); projV->assign(ids.size(), 0.f); }
+        const int r = orbx_frame_track_last_frame_fisheye_map(m_, Cur.handle(), Last.handle(), occupied.empty() ? nullptr : occupied.data(), &view, TrlR, Trlt,
+                                                              map.handle(), (int)ids.size(), ids.data(),
+                                                              hasObservations.empty() ? nullptr : hasObservations.data(), th, levelMode,
+                                                              mbCheckOrientation ? 1 : 0, vpMatch.data(), projected ? projected->data() : nullptr,
+                                                              projU ? projU->data() : nullptr, projV ? projV->data() : nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_track_last_frame_fisheye_map: ") + orbx_status_string(r));
+        return r;
+    }
+    int SearchByProjectionFisheye(DeviceFrame &Cur, DeviceKeyFrame &KF, const std::vector<uint8_t> &occupied, const orbx_fisheye_view &view,
+                                  float logScaleFactor, const DeviceMap &map, const std::vector<int32_t> &ids, float th, int ORBdist,
+                                  std::vector<int32_t> &vpMatch, std::vector<uint8_t> *projected = nullptr, std::vector<float> *projU = nullptr,
+                                  std::vector<float> *projV = nullptr) {
+        if ((projU == nullptr) != (projV == nullptr)) throw std::invalid_argument("SearchByProjectionFisheye: projU and projV together");
+        vpMatch.assign(Cur.count(), -1);
+        if (projected) projected->assign(ids.size(), 0);
+        if (projU) { projU->assign(ids.size(), 0.f); projV->assign(ids.size(), 0.f); }
+        const int r = orbx_frame_search_by_projection_keyframe_fisheye_map(m_, Cur.handle(), occupied.empty() ? nullptr : occupied.data(), &view,
+                                                                           logScaleFactor, KF.handle(), map.handle(), (int)ids.size(), ids.data(), th,
+                                                                           (float)ORBdist, mbCheckOrientation ? 1 : 0, vpMatch.data(),
+                                                                           projected ? projected->data() : nullptr, projU ? projU->data() : nullptr,
+                                                                           projV ? projV->data() : nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_frame_search_by_projection_keyframe_fisheye_map: ") + orbx_status_string(r));
+        return r;
+    }
+
     // MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:329-403) for a batch of map points: the observations' descriptors of map
     // point p are rows [setPtr[p], setPtr[p+1]) of `descriptors`; bestIdx[p] is the row offset (within the set) the reference keeps.
     void ComputeDistinctiveDescriptors(const std::vector<uint8_t> &descriptors, const std::vector<int32_t> &setPtr, std::vector<int32_t> &bestIdx) {

@@ -1682,6 +1682,125 @@ __global__ __launch_bounds__(256) void k_sim3_project(const KfProblem *__restric
     qvalid[o] = ok ? 1 : 0;
 }
 
+// k_track_project: the projection half of the Tracking thread's two searches that take their queries from another frame's map points --
+// SearchByProjection(CurrentFrame, LastFrame, th, bMono) (ORBmatcher.cc:1676-1887, RELOC = false) and SearchByProjection(CurrentFrame, pKF,
+// sAlreadyFound, th, ORBdist) (:1889-2010, RELOC = true) -- on a monocular / rectified current frame (KB8 = false) or a fisheye-stereo rig (KB8 = true:
+// KannalaBrandt8::project through kb8_project, no ur but the projection into the right camera), straight from the map table: a lane per SOURCE
+// feature i reads ids[i] (the slot of mvpMapPoints[i], -1: none), the source row's octave and angle and the 64-byte record of the slot, and writes
+// the query record where k_window_best2_t and the replay read it (qvalid switches a rejected entry off: query index = source feature index).  No
+// k_map_gather launch, no flat map-point arrays.  Entries at or beyond the source's count (read on the device) are off.  The gates in the host
+// adapters' order, every float operation rounded separately, sums in k_fuse_project's order:
+//   x3Dc = Rcw p + tcw
+//   RELOC = false: invzc = 1 / z; reject invzc < 0
+//   Pinhole::project; reject u < mnMinX || u > mnMaxX, likewise v  (BOTH sides inclusive, unlike KeyFrame::IsInImage)
+//   RELOC = false: ur = u - bf invzc; r = th * scale[octave], on iff 0 <= octave < nlevels; levels by level_mode (ORBmatcher.cc:1726-1735)
+//   RELOC = true:  dist3D = |p - Ow|; reject outside [0.8f mfMinDistance, 1.2f mfMaxDistance]; PredictScale(dist3D, &CurrentFrame) as
+//                  k_fuse_project evaluates it; r = th * scale[level]; levels [level - 1, level + 1]
+// projected[i] = the entry passed the geometric gates (qvalid also needs the octave of RELOC = false in range); qx / qy hold (u, v) of every entry with
+// a point.  Streaming work: no LDS, no scratch.  No address is formed from an id that is not below `cap`.  grid (ceil(n_ids / 256)), block 256
+struct TrackProject {
+    const uint4 *rec; int cap;                        // the map table
+    const int32_t *ids; int n_ids;
+    const orbx_keypoint *src_kps; const int32_t *src_count;   // the source's rows (last frame / key frame) and its count on the device
+    orbx_frame_pose pose;                             // the CURRENT frame's
+    float fx, fy, cx, cy, bf;
+    float minx, maxx, miny, maxy;
+    float th, log_scale_factor;
+    int level_mode, nlevels;
+    const float *scale;                               // the current frame's mvScaleFactors
+    float *qx, *qy, *qxr, *qr;                        // qxr NULL: not wanted (no mvuRight on the current frame)
+    int32_t *qmin, *qmax;
+    uint8_t *qvalid, *qdesc;
+    float *q_angle;
+    uint8_t *projected;
+    // KB8 (a fisheye-stereo rig; pose = the LEFT camera's R, t, twc): KannalaBrandt8::mvParameters of the left camera, Trl = GetRelativePoseTrl() and
+    // the right-camera prediction (qxr, qyr) = project(Trl x3Dc) with the LEFT parameters, as the reference does (ORBmatcher.cc:1795-1796; RELOC: unused).
+    // The source is a rig as well: feature i < N_left is row i, the others rows src_roff + (i - N_left); src_count[0..1] = N_left, N_right.
+    float kb8[8], Trl_R[9], Trl_t[3];
+    float *qyr;
+    int src_roff;
+};
+template <bool RELOC, bool KB8>
+__global__ __launch_bounds__(256) void k_track_project(const TrackProject T) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= T.n_ids) return;
+    // the inputs of the entry are requested ahead of the first gate: the id, the count(s) and the source row (a rig's row number waits for N_left), then
+    // the four quarters of the record, which wait for the id; the one read behind the gates is the scale factor of the entry's level
+    const int id = gld(T.ids + i);
+    int n_src = gld(T.src_count), row = i;
+    bool left_row = true;
+    if (KB8) {
+        const int nl = n_src;
+        n_src = nl + gld(T.src_count + 1);
+        left_row = i < nl;
+        row = left_row ? i : (i < n_src ? T.src_roff + (i - nl) : 0);
+    }
+    const int octave = gld(&T.src_kps[row].octave);
+    const float angle = (RELOC && !left_row) ? 0.f : gld(&T.src_kps[row].angle);   // :1973 reads mvKeysUn, which holds the left camera only
+    const bool have = (unsigned)id < (unsigned)T.cap && i < n_src;
+    const uint4 *slot = T.rec + (size_t)(have ? id : 0) * 4;
+    const uint4 q0 = slot[0], q1 = slot[1], d0 = slot[2], d1 = slot[3];
+    const float P0 = __uint_as_float(q0.x), P1 = __uint_as_float(q0.y), P2 = __uint_as_float(q0.z);
+    const float mn_in = __uint_as_float(q1.z), mx = __uint_as_float(q1.w);
+    const orbx_frame_pose &S = T.pose;
+    float Pc[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+        Pc[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(S.Rcw[3 * r], P0), __fmul_rn(S.Rcw[3 * r + 1], P1)), __fmul_rn(S.Rcw[3 * r + 2], P2)), S.tcw[r]);
+    const float invz = __fdiv_rn(1.0f, Pc[2]);
+    bool ok = have && (RELOC || !(invz < 0.f));
+    float u, v, xr = 0.f, yr = 0.f;
+    if (KB8) {
+        kb8_project(T.kb8, Pc[0], Pc[1], Pc[2], &u, &v);
+        if (!RELOC) {
+            float Pr[3];
+#pragma unroll
+            for (int r = 0; r < 3; r++)
+                Pr[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T.Trl_R[3 * r], Pc[0]), __fmul_rn(T.Trl_R[3 * r + 1], Pc[1])), __fmul_rn(T.Trl_R[3 * r + 2], Pc[2])), T.Trl_t[r]);
+            kb8_project(T.kb8, Pr[0], Pr[1], Pr[2], &xr, &yr);
+        }
+    } else {
+        u = __fadd_rn(__fdiv_rn(__fmul_rn(T.fx, Pc[0]), Pc[2]), T.cx); v = __fadd_rn(__fdiv_rn(__fmul_rn(T.fy, Pc[1]), Pc[2]), T.cy);
+        xr = __fsub_rn(u, __fmul_rn(T.bf, invz));
+    }
+    ok = ok && !(u < T.minx || u > T.maxx) && !(v < T.miny || v > T.maxy);
+    int lo, hi, lvl;
+    bool on = ok;
+    if (RELOC) {
+        const float PO0 = __fsub_rn(P0, S.Ow[0]), PO1 = __fsub_rn(P1, S.Ow[1]), PO2 = __fsub_rn(P2, S.Ow[2]);
+        const float dist = sqrtf(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, PO0)), __fmul_rn(PO1, PO1)), __fmul_rn(PO2, PO2)));
+        const float maxDistance = __fmul_rn(1.2f, mx), minDistance = __fmul_rn(0.8f, mn_in);
+        ok = ok && !(dist < minDistance || dist > maxDistance);
+        on = ok;
+        lvl = 0;
+        if (ok) {   // MapPoint::PredictScale(dist3D, &CurrentFrame) (MapPoint.cc:548-563), as k_fuse_project evaluates it
+            const float ratio = __fdiv_rn(mx, dist);
+            lvl = (int)ceilf(__fdiv_rn((float)log((double)ratio), T.log_scale_factor));
+            if (lvl < 0) lvl = 0;
+            else if (lvl >= T.nlevels) lvl = T.nlevels - 1;
+        }
+        lo = lvl - 1; hi = lvl + 1;   // :1942
+    } else {
+        lvl = octave;
+        on = ok && octave >= 0 && octave < T.nlevels;
+        if (T.level_mode == 1) { lo = octave; hi = -1; }          // bForward  :1731
+        else if (T.level_mode == 2) { lo = 0; hi = octave; }      // bBackward :1733
+        else { lo = octave - 1; hi = octave + 1; }                // :1735
+    }
+    const float radius = on ? __fmul_rn(T.th, gld(T.scale + lvl)) : 0.f;
+    gst(T.qx + i, have ? u : 0.f); gst(T.qy + i, have ? v : 0.f);
+    if (!RELOC && T.qxr) gst(T.qxr + i, have ? xr : 0.f);
+    if (!RELOC && KB8) gst(T.qyr + i, have ? yr : 0.f);
+    gst(T.qr + i, radius); gst(T.qmin + i, lo); gst(T.qmax + i, hi);
+    gst(T.qvalid + i, (uint8_t)(on ? 1 : 0));
+    gst(T.q_angle + i, angle);
+    if (T.projected) gst(T.projected + i, (uint8_t)(ok ? 1 : 0));
+    if (on) {
+        uint4 *qd = reinterpret_cast<uint4 *>(T.qdesc) + (size_t)i * 2;
+        qd[0] = d0; qd[1] = d1;
+    }
+}
+
 // A loaded monocular / rectified orbx_frame copied into a key frame's own allocation -- what KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-82) does with
 // mvKeysUn, mDescriptors, mvuRight, mvScaleFactors, mvInvLevelSigma2 and mGrid: rows, count, scale factors and the grid AS BUILT (no rebuild).  The count is
 // read on the device (a batch-loaded frame's N may not have reached the host yet).

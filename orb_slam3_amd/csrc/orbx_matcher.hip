@@ -550,7 +550,61 @@ struct ProjArgs {
     int check_orientation;
     int32_t *match_out;
     float max_dist;
+    const struct TrackArgs *track = nullptr;
 };
+
+// The queries of a handle call that projects on the device (k_track_project) instead of uploading query records: entry i of ids = the map slot of the
+// source's feature i or -1, nq = n_ids, q_has_obs [n_ids] the only per-query host array (qx .. q_angle of ProjArgs are NULL).  The source's rows are
+// resident (the last frame's handle, a key frame).  orbx_map and orbx_keyframe are defined further down: run_projection reaches the table's records
+// and the two waits that order the table and a key-frame source in front of the kernel through the three functions declared here.
+struct TrackArgs {
+    bool reloc;                                   // k_track_project<RELOC>
+    orbx_map *map; const int32_t *ids;
+    orbx_keyframe *kf;                            // the source when it is a key frame (waited for through keyframe_wait_ready), else NULL
+    const orbx_keypoint *src_kps; const int32_t *src_count;
+    const orbx_camera *cam; const orbx_frame_pose *pose;   // a monocular / rectified current frame
+    float th, log_scale_factor; int level_mode;
+    uint8_t *projected; float *proj_u, *proj_v;   // optional outputs [n_ids]
+    // a fisheye-stereo rig (view != NULL; cam and pose are NULL then): the LEFT camera's view, GetRelativePoseTrl() (k_track_project<false, true> only)
+    // and the right camera's first row of the source
+    const orbx_fisheye_view *view; const float *Trl_R, *Trl_t; int src_roff;
+    struct Out { uint64_t seq; bool waited; } *out;   // what map_points_done() is told behind the call; the call got as far as its waits
+};
+const uint4 *map_records(const orbx_map *map, int *cap);
+int map_wait_written(orbx_matcher *m, orbx_map *map, uint64_t *seq);
+int keyframe_wait_ready(orbx_matcher *m, orbx_keyframe *kf);
+
+// Everything of k_track_project's record but the arena buffers (the caller's layout has carved those), the two waits, and the launch: between a
+// call's uploads and its window scan.
+int track_launch(orbx_matcher *m, const TrackArgs &tr, const orbx_frame *fh, int nq, TrackProject &T) {
+    T.rec = map_records(tr.map, &T.cap); T.n_ids = nq;
+    T.src_kps = tr.src_kps; T.src_count = tr.src_count; T.src_roff = tr.src_roff;
+    if (tr.view) {
+        memcpy(T.pose.Rcw, tr.view->R, sizeof(T.pose.Rcw)); memcpy(T.pose.tcw, tr.view->t, sizeof(T.pose.tcw)); memcpy(T.pose.Ow, tr.view->twc, sizeof(T.pose.Ow));
+        memcpy(T.kb8, tr.view->params, sizeof(T.kb8));
+        if (tr.Trl_R) { memcpy(T.Trl_R, tr.Trl_R, sizeof(T.Trl_R)); memcpy(T.Trl_t, tr.Trl_t, sizeof(T.Trl_t)); }
+    } else {
+        T.pose = *tr.pose;
+        T.fx = tr.cam->fx; T.fy = tr.cam->fy; T.cx = tr.cam->cx; T.cy = tr.cam->cy; T.bf = tr.cam->bf;
+    }
+    T.minx = fh->bounds[0]; T.maxx = fh->bounds[1]; T.miny = fh->bounds[2]; T.maxy = fh->bounds[3];
+    T.th = tr.th; T.log_scale_factor = tr.log_scale_factor; T.level_mode = tr.level_mode; T.nlevels = fh->nlevels; T.scale = fh->scale;
+    if (tr.kf) ORBX_TRY(keyframe_wait_ready(m, tr.kf));
+    ORBX_TRY(map_wait_written(m, tr.map, &tr.out->seq));
+    tr.out->waited = true;
+    const dim3 grid((unsigned)((nq + 255) / 256));
+    if (tr.view && tr.reloc) hipLaunchKernelGGL((k_track_project<true, true>), grid, dim3(256), 0, m->exec(), T);
+    else if (tr.view) hipLaunchKernelGGL((k_track_project<false, true>), grid, dim3(256), 0, m->exec(), T);
+    else if (tr.reloc) hipLaunchKernelGGL((k_track_project<true, false>), grid, dim3(256), 0, m->exec(), T);
+    else hipLaunchKernelGGL((k_track_project<false, false>), grid, dim3(256), 0, m->exec(), T);
+    return ORBX_OK;
+}
+// the optional outputs among a call's downloads
+int track_fetch(orbx_matcher *m, const TrackArgs &tr, const TrackProject &T, int nq) {
+    if (tr.proj_u) { ORBX_TRY(m->d2h(tr.proj_u, T.qx, 4 * (size_t)nq)); ORBX_TRY(m->d2h(tr.proj_v, T.qy, 4 * (size_t)nq)); }
+    if (tr.projected) ORBX_TRY(m->d2h(tr.projected, T.projected, (size_t)nq));
+    return ORBX_OK;
+}
 
 // fh != NULL: the handle form -- the frame's rows and grid are resident (a.frame is not read); while its N is still on the device (a load_batch
 // nobody has counted yet) every per-feature buffer is sized by the handle's capacity and the count comes back with the results.
@@ -583,6 +637,9 @@ int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr,
     const bool brute = !fh && m->brute_windows && (size_t)nq * (size_t)n <= kBruteMaxPairs;
     const int32_t cnts[2] = {n, nq};
     int32_t *dcnt;
+    const TrackArgs *tr = a.track;
+    TrackProject T;
+    memset(&T, 0, sizeof(T));
     WindowProblem *dP;
     ResolveProblem *dR;
     ORBX_TRY(m->carve([&](Carve &A) {
@@ -591,20 +648,33 @@ int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr,
         if (fh && has_ur) P.u_right = fh->u_right;
         else if (has_ur) P.u_right = A.up(F->u_right, (size_t)n);
         P.occupied0 = A.up_opt(a.occupied, (size_t)n);
-        P.qx = A.up(a.qx, (size_t)nq); P.qy = A.up(a.qy, (size_t)nq); P.qr = A.up(a.qr, (size_t)nq);
-        P.qmin = A.up(a.qmin, (size_t)nq); P.qmax = A.up(a.qmax, (size_t)nq);
-        if (has_ur) P.qxr = A.up_opt(a.qxr, (size_t)nq);
-        P.qdesc = A.up(a.qdesc, 32 * (size_t)nq);
-        P.qvalid = A.up_opt(a.qvalid, (size_t)nq);
-        R.q_angle = A.up_opt(a.q_angle, (size_t)nq);
+        if (tr) {   // the ids and the flags are all that travels per query; the records are k_track_project's, behind the uploads
+            T.ids = A.up(tr->ids, (size_t)nq);
+        } else {
+            P.qx = A.up(a.qx, (size_t)nq); P.qy = A.up(a.qy, (size_t)nq); P.qr = A.up(a.qr, (size_t)nq);
+            P.qmin = A.up(a.qmin, (size_t)nq); P.qmax = A.up(a.qmax, (size_t)nq);
+            if (has_ur) P.qxr = A.up_opt(a.qxr, (size_t)nq);
+            P.qdesc = A.up(a.qdesc, 32 * (size_t)nq);
+            P.qvalid = A.up_opt(a.qvalid, (size_t)nq);
+            R.q_angle = A.up_opt(a.q_angle, (size_t)nq);
+        }
         R.q_has_obs = A.up_opt(a.q_has_obs, (size_t)nq);
         // everything the call uploads lies in ONE run of the arena (one DMA, orbx_matcher::exec): the two problem records directly behind the inputs,
         // the buffers only the device writes behind them; the downloads (match, nmatches) side by side as well
         dP = A.take<WindowProblem>(1);
         dR = A.take<ResolveProblem>(1);
+        if (tr) {
+            T.qr = A.take<float>(nq); T.qmin = A.take<int32_t>(nq); T.qmax = A.take<int32_t>(nq);
+            if (has_ur && !tr->reloc) T.qxr = A.take<float>(nq);
+            T.qdesc = A.take<uint8_t>(32 * (size_t)nq); T.qvalid = A.take<uint8_t>(nq); T.q_angle = A.take<float>(nq);
+        }
         P.keys = A.take<u64>((size_t)nq * kTopK); P.meta = A.take<int32_t>(nq);
         if (!fh) { P.gstart = A.take<uint16_t>(kGridCells + 1); P.gorder = A.take<uint16_t>(n); }
         R.entries = A.take<int32_t>(nq);
+        if (tr) {   // (u, v) and the gates' verdicts go down with the matches
+            T.qx = A.take<float>(nq); T.qy = A.take<float>(nq);
+            if (tr->projected) T.projected = A.take<uint8_t>(nq);
+        }
         R.match = A.take<int32_t>(nc);
         R.nmatches = A.take<int32_t>(1);
     }));
@@ -612,7 +682,13 @@ int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr,
     else P.n_ptr = dcnt;
     P.nq_ptr = dcnt + 1;
     if (brute) { P.gstart = nullptr; P.gorder = nullptr; }
+    if (tr) {
+        P.qx = T.qx; P.qy = T.qy; P.qr = T.qr; P.qmin = T.qmin; P.qmax = T.qmax; P.qxr = T.qxr; P.qdesc = T.qdesc; P.qvalid = T.qvalid;
+        R.q_angle = T.q_angle;
+        if (tr->reloc) P.u_right = nullptr;   // Relocalization's search never reads mvuRight (ORBmatcher.cc:1955-1966): no right-coordinate gate
+    }
     ORBX_TRY(m->h2d(dP, &P, sizeof(P))); ORBX_TRY(m->h2d(dR, &R, sizeof(R)));
+    if (tr) ORBX_TRY(track_launch(m, *tr, fh, nq, T));
     const float fb[4] = {fh ? fh->bounds[0] : F->min_x, fh ? fh->bounds[1] : F->max_x, fh ? fh->bounds[2] : F->min_y, fh ? fh->bounds[3] : F->max_y};
     const GridParams g = grid_of(fb);
     if (brute) {
@@ -627,6 +703,7 @@ int run_projection(orbx_matcher *m, const ProjArgs &a, orbx_frame *fh = nullptr,
     if (!fh) ORBX_TRY(m->d2h(a.match_out, R.match, 4 * (size_t)n));
     else ORBX_TRY(frame_fetch(fh, &rows, 1));
     ORBX_TRY(m->d2h(&nm, R.nmatches, 4));
+    if (tr) ORBX_TRY(track_fetch(m, *tr, T, nq));
     ORBX_TRY(m->sync_and_deliver());
     if (frame_take(fh, &rows, 1, left_only) && left_only)
         for (int i = fh->n_left; i < fh->n; i++) a.match_out[i] = -1;
@@ -695,6 +772,7 @@ struct TwinArgs {
     const float *q_angle;
     int mode; float nnratio; int check_orientation;
     int32_t *match_out;
+    const TrackArgs *track = nullptr;     // a handle call whose queries k_track_project writes (qx .. q_angle are NULL then)
 };
 
 // the twin window search of both cameras and the replay; dP = the two problems (uploaded or to be uploaded by the caller), n_alloc >= N
@@ -734,7 +812,24 @@ int run_projection_twin(orbx_matcher *m, const TwinArgs &a, orbx_frame *fh = nul
     orbx_keypoint *dk = nullptr;
     uint8_t *dd = nullptr;
     WindowProblem *dP;
-    ORBX_TRY(m->carve([&](Carve &A) {
+    const TrackArgs *tr = a.track;
+    TrackProject K;
+    memset(&K, 0, sizeof(K));
+    if (tr) ORBX_TRY(m->carve([&](Carve &A) {   // the track form's own layout: ids and flags up in one run, the records k_track_project's
+        dcnt = A.up(cnts, 3, 1);
+        K.ids = A.up(tr->ids, (size_t)nq);
+        T.occupied0 = A.up_opt(a.occupied, (size_t)N);
+        T.q_has_obs = A.up_opt(a.q_has_obs, (size_t)nq);
+        dP = A.take<WindowProblem>(2);
+        K.qr = A.take<float>(nq); K.qmin = A.take<int32_t>(nq); K.qmax = A.take<int32_t>(nq); K.qxr = A.take<float>(nq); K.qyr = A.take<float>(nq);
+        K.qdesc = A.take<uint8_t>(32 * (size_t)nq); K.qvalid = A.take<uint8_t>(nq); K.q_angle = A.take<float>(nq);
+        for (int s = 0; s < 2; s++) { P[s].keys = A.take<u64>((size_t)nq * kTopK); P[s].meta = A.take<int32_t>(nq); }
+        T.entries = A.take<int32_t>(2 * (size_t)nq);
+        K.qx = A.take<float>(nq); K.qy = A.take<float>(nq);   // (u, v) and the verdicts go down with the matches
+        if (tr->projected) K.projected = A.take<uint8_t>(nq);
+        T.match = A.take<int32_t>(nc); T.nmatches = A.take<int32_t>(1);
+    }));
+    else ORBX_TRY(m->carve([&](Carve &A) {
         dcnt = A.up(cnts, 3, 1);
         if (!fh) {   // (resident rows and grids: nothing of the frame travels)
             dk = A.take<orbx_keypoint>(N);
@@ -761,6 +856,13 @@ int run_projection_twin(orbx_matcher *m, const TwinArgs &a, orbx_frame *fh = nul
         T.match = A.take<int32_t>(nc); T.nmatches = A.take<int32_t>(1); T.entries = A.take<int32_t>(2 * (size_t)nq);
         dP = A.take<WindowProblem>(2);
     }));
+    if (tr) {   // left: (u, v); right: the projection into the right camera; one radius, level window and validity for both (:1800)
+        for (int s = 0; s < 2; s++) {
+            WindowProblem &w = P[s];
+            w.qx = s ? K.qxr : K.qx; w.qy = s ? K.qyr : K.qy; w.qr = K.qr; w.qmin = K.qmin; w.qmax = K.qmax; w.qvalid = K.qvalid; w.qdesc = K.qdesc;
+        }
+        T.q_angle = K.q_angle; T.l2r = fh->l2r; T.r2l = fh->r2l;
+    }
     if (fh) {
         for (int s = 0; s < 2; s++) frame_side(fh, s == 1, P[s]);
     } else {
@@ -773,12 +875,14 @@ int run_projection_twin(orbx_matcher *m, const TwinArgs &a, orbx_frame *fh = nul
     const float fb[4] = {F->min_x, F->max_x, F->min_y, F->max_y};
     const GridParams g = grid_of(fb);
     if (!fh) ORBX_LAUNCH_GRID_BUILD( dim3(2), dim3(64), 0, m->exec(), dP, g);
+    if (tr) ORBX_TRY(track_launch(m, *tr, fh, nq, K));
     ORBX_TRY(launch_twin(m, dP, T, g, nc, nq));
     int32_t nm = 0;
     const Rows rows = {T.match, 1, nc, a.match_out, 0};
     if (!fh) ORBX_TRY(m->d2h(a.match_out, T.match, 4 * (size_t)N));
     else ORBX_TRY(frame_fetch(fh, &rows, 1));
     ORBX_TRY(m->d2h(&nm, T.nmatches, 4));
+    if (tr) ORBX_TRY(track_fetch(m, *tr, K, nq));
     ORBX_TRY(m->sync_and_deliver());
     frame_take(fh, &rows, 1);
     return nm;
@@ -1149,10 +1253,11 @@ struct orbx_map {
 namespace {
 
 // every id in [0, capacity) and live; unique: named once (the stamp array).  Under map->mu.
-bool map_ids_ok(orbx_map *map, int n, const int32_t *ids, bool unique) {
+bool map_ids_ok(orbx_map *map, int n, const int32_t *ids, bool unique, bool none_ok = false) {
     if (unique && ++map->stamp_now == 0) { memset(map->stamp, 0, sizeof(uint32_t) * (size_t)map->capacity); map->stamp_now = 1; }
     for (int j = 0; j < n; j++) {
         const int32_t id = ids[j];
+        if (none_ok && id == -1) continue;   // (the per-feature id rows of the track forms: no map point here)
         if (id < 0 || id >= map->capacity || !map->live[id]) return false;
         if (unique) {
             if (map->stamp[id] == map->stamp_now) return false;
@@ -1187,16 +1292,21 @@ MapPointsDev map_points_up(Carve &A, const MapPoints &S) {
     d.ids = S.map ? A.up(S.ids, q) : nullptr;
     return d;
 }
+// the order every reader of a table keeps against its updates: the context's stream waits for `written` unless a reader has synchronised behind the
+// newest update.  *seq: what map_points_done() reports once the call has synchronised.
+int map_wait_written(orbx_matcher *m, orbx_map *map, uint64_t *seq) {
+    std::lock_guard<std::mutex> lock(map->mu);
+    if (map->seen_seq < map->write_seq) ORBX_HIP(hipStreamWaitEvent(m->stream, map->written, 0));
+    *seq = map->write_seq;
+    return ORBX_OK;
+}
+const uint4 *map_records(const orbx_map *map, int *cap) { *cap = map->capacity; return map->rec; }
 // a table source: the context's stream waits for `written` (unless a reader has synchronised behind it), then k_map_gather fills the five arrays.
 // *seq: what map_points_done() reports once the call has synchronised.  Host arrays: nothing.
 int map_points_gather(orbx_matcher *m, const MapPoints &S, const MapPointsDev &D, uint64_t *seq) {
     *seq = 0;
     if (!S.map || S.n <= 0) return ORBX_OK;
-    {
-        std::lock_guard<std::mutex> lock(S.map->mu);
-        if (S.map->seen_seq < S.map->write_seq) ORBX_HIP(hipStreamWaitEvent(m->stream, S.map->written, 0));
-        *seq = S.map->write_seq;
-    }
+    ORBX_TRY(map_wait_written(m, S.map, seq));
     const MapRows G = {S.map->rec, D.ids, S.n, S.map->capacity, D.pos, D.normal, D.min_dist, D.max_dist, D.desc};
     hipLaunchKernelGGL(k_map_gather, dim3((unsigned)((S.n + 63) / 64)), dim3(256), 0, m->exec(), G);
     return ORBX_OK;
@@ -3118,6 +3228,7 @@ inline int keyframe_acquire(orbx_matcher *m, orbx_keyframe *const *kfs, int n_kf
         if (!kfs[k]->done.load(std::memory_order_acquire)) ORBX_HIP(hipStreamWaitEvent(m->stream, kfs[k]->ready, 0));
     return ORBX_OK;
 }
+int keyframe_wait_ready(orbx_matcher *m, orbx_keyframe *kf) { return keyframe_acquire(m, &kf, 1); }
 inline void keyframe_release(orbx_keyframe *const *kfs, int n_kf) {   // after the call's synchronisation
     for (int k = 0; k < n_kf; k++) kfs[k]->done.store(true, std::memory_order_release);
 }
@@ -4319,4 +4430,107 @@ extern "C" int orbx_keyframe_fuse_map_points_sim3_map(orbx_matcher *m, int n_kf,
     if (!map_form_ok(map, n_mp)) return ORBX_E_BAD_ARG;
     return keyframe_fuse_map_points_impl(m, false, true, n_kf, kfs, cams, poses, nullptr, th, log_scale_factor, 0, map_points_of(n_mp, map, ids), skip,
                                          best_idx, best_dist, projected);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The Tracking thread's two searches whose queries are another frame's map points, from map ids: TrackWithMotionModel's SearchByProjection(Cur, Last,
+// th, bMono) and Relocalization's SearchByProjection(Cur, pKF, sAlreadyFound, th, ORBdist) on a monocular / rectified resident frame.  ids [n_ids] =
+// the map slot of the source's mvpMapPoints[i] or -1; k_track_project evaluates the adapters' host loops on the device and writes the query records
+// into the arena of run_projection's handle form, which runs unchanged behind it: the same window scan, the same replay, one launch more.  A match
+// value >= 0 is the SOURCE feature index.  Everything is checked before anything is enqueued.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+
+// the checks all four forms share; fisheye: the kind of the form (cur must be of it); have_view: the form's camera arguments are there; n_src: the
+// source's count where the host knows it (-1: pending), cap_src: its capacity
+int track_check(orbx_matcher *m, orbx_frame *cur, bool fisheye, bool have_view, orbx_map *map, int n_ids, const int32_t *ids, int n_src, int cap_src,
+                const int32_t *match, const float *proj_u, const float *proj_v) {
+    if (!m || !cur || !have_view || !map || !match || n_ids < 0 || (n_ids > 0 && !ids)) return ORBX_E_BAD_ARG;
+    if (cur->owner != m || cur->fisheye != fisheye || !cur->loaded || map->device != m->device || (proj_u == nullptr) != (proj_v == nullptr))
+        return ORBX_E_BAD_ARG;
+    if (n_src >= 0 ? n_ids != n_src : n_ids > cap_src) return ORBX_E_BAD_ARG;   // one entry per feature of the source
+    if (cur->rows_n() > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;
+    std::lock_guard<std::mutex> lock(map->mu);
+    return map_ids_ok(map, n_ids, ids, false, true) ? ORBX_OK : ORBX_E_BAD_ARG;
+}
+
+// twin: the rig form of TrackWithMotionModel's search (both cameras, k_replay_twin); left_only: the rig form of Relocalization's (the left camera)
+int track_run(orbx_matcher *m, orbx_frame *cur, const uint8_t *occupied, TrackArgs &tr, int n_ids, const uint8_t *has_obs, float max_dist,
+              int check_orientation, int32_t *match, bool twin = false, bool left_only = false) {
+    if (tr.projected) memset(tr.projected, 0, (size_t)n_ids);
+    if (tr.proj_u) { memset(tr.proj_u, 0, 4 * (size_t)n_ids); memset(tr.proj_v, 0, 4 * (size_t)n_ids); }
+    TrackArgs::Out out = {0, false};
+    tr.out = &out;
+    const orbx_frame_desc d = frame_desc_of(cur);
+    int nm;
+    if (twin) {
+        TwinArgs a = {&d, nullptr, 0, nullptr, nullptr, occupied, n_ids, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr},
+                      {nullptr, nullptr}, {nullptr, nullptr}, nullptr, has_obs, nullptr, 2, 0.f, check_orientation, match, &tr};
+        nm = run_projection_twin(m, a, cur);
+    } else {
+        ProjArgs a = {&d, occupied, n_ids, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, has_obs, nullptr, 2, 0.f,
+                      check_orientation, match, max_dist, &tr};
+        nm = run_projection(m, a, cur, left_only);
+    }
+    if (nm >= 0 && out.waited) {   // the call made its waits and has synchronised behind them
+        map_points_done(map_points_of(n_ids, tr.map, tr.ids), out.seq);
+        if (tr.kf) keyframe_release(&tr.kf, 1);
+    }
+    return nm;
+}
+
+}  // namespace
+
+extern "C" int orbx_frame_track_last_frame_map(orbx_matcher *m, orbx_frame *cur, orbx_frame *last, const uint8_t *cur_occupied, const orbx_camera *cam,
+                                               const orbx_frame_pose *pose, orbx_map *map, int n_ids, const int32_t *ids, const uint8_t *has_obs,
+                                               float th, int level_mode, int check_orientation, int32_t *cur_match, uint8_t *projected, float *proj_u,
+                                               float *proj_v) {
+    if (!last || last == cur || last->owner != m || last->fisheye || !last->loaded || level_mode < 0 || level_mode > 2) return ORBX_E_BAD_ARG;
+    const int rc = track_check(m, cur, false, cam && pose, map, n_ids, ids, last->host_n(), last->cap, cur_match, proj_u, proj_v);
+    if (rc != ORBX_OK) return rc;
+    TrackArgs tr = {false, map, ids, nullptr, last->kps, last->count, cam, pose, th, 0.f, level_mode, projected, proj_u, proj_v, nullptr, nullptr, nullptr,
+                    0, nullptr};
+    return track_run(m, cur, cur_occupied, tr, n_ids, has_obs, (float)ORBX_TH_HIGH, check_orientation, cur_match);
+}
+
+// the same for a fisheye-stereo rig (ORBmatcher.cc:1676-1887 with the twin :1794-1863): view = the LEFT camera's, Trl = GetRelativePoseTrl(); `last` is a
+// rig handle as well -- rows [0, N_left) are mvKeys, the others mvKeysRight; cur_match holds N = N_left + N_right entries
+extern "C" int orbx_frame_track_last_frame_fisheye_map(orbx_matcher *m, orbx_frame *cur, orbx_frame *last, const uint8_t *cur_occupied,
+                                                       const orbx_fisheye_view *view, const float *Trl_R9, const float *Trl_t3, orbx_map *map, int n_ids,
+                                                       const int32_t *ids, const uint8_t *has_obs, float th, int level_mode, int check_orientation,
+                                                       int32_t *cur_match, uint8_t *projected, float *proj_u, float *proj_v) {
+    if (!last || last == cur || last->owner != m || !last->fisheye || !last->loaded || level_mode < 0 || level_mode > 2) return ORBX_E_BAD_ARG;
+    const int rc = track_check(m, cur, true, view && Trl_R9 && Trl_t3, map, n_ids, ids, last->host_n(), last->cap, cur_match, proj_u, proj_v);
+    if (rc != ORBX_OK) return rc;
+    TrackArgs tr = {false, map, ids, nullptr, last->kps, last->count, nullptr, nullptr, th, 0.f, level_mode, projected, proj_u, proj_v, view, Trl_R9, Trl_t3,
+                    last->roff, nullptr};
+    return track_run(m, cur, cur_occupied, tr, n_ids, has_obs, (float)ORBX_TH_HIGH, check_orientation, cur_match, true);
+}
+
+extern "C" int orbx_frame_search_by_projection_keyframe_map(orbx_matcher *m, orbx_frame *cur, const uint8_t *occupied, const orbx_camera *cam,
+                                                            const orbx_frame_pose *pose, float log_scale_factor, orbx_keyframe *kf, orbx_map *map,
+                                                            int n_ids, const int32_t *ids, float th, float max_dist, int check_orientation,
+                                                            int32_t *match, uint8_t *projected, float *proj_u, float *proj_v) {
+    if (!m || !kf || kf->fisheye || kf->device != m->device) return ORBX_E_BAD_ARG;
+    const int rc = track_check(m, cur, false, cam && pose, map, n_ids, ids, kf->host_n(), kf->cap, match, proj_u, proj_v);
+    if (rc != ORBX_OK) return rc;
+    TrackArgs tr = {true, map, ids, kf, kf->kps, kf->count, cam, pose, th, log_scale_factor, 0, projected, proj_u, proj_v, nullptr, nullptr, nullptr, 0,
+                    nullptr};
+    return track_run(m, cur, occupied, tr, n_ids, nullptr, max_dist, check_orientation, match);
+}
+
+// the same for a fisheye-stereo rig: the LEFT camera only is searched (GetFeaturesInArea's default bRight = false, as
+// orbx_frame_search_by_projection_window_fisheye); kf is a rig key frame, read for mvKeysUn[i].angle below N_left (0.f beyond, :1973); occupied / match
+// hold N entries and the right camera's entries of match stay -1
+extern "C" int orbx_frame_search_by_projection_keyframe_fisheye_map(orbx_matcher *m, orbx_frame *cur, const uint8_t *occupied,
+                                                                    const orbx_fisheye_view *view, float log_scale_factor, orbx_keyframe *kf,
+                                                                    orbx_map *map, int n_ids, const int32_t *ids, float th, float max_dist,
+                                                                    int check_orientation, int32_t *match, uint8_t *projected, float *proj_u,
+                                                                    float *proj_v) {
+    if (!m || !kf || !kf->fisheye || kf->device != m->device) return ORBX_E_BAD_ARG;
+    const int rc = track_check(m, cur, true, view != nullptr, map, n_ids, ids, kf->host_n(), kf->cap, match, proj_u, proj_v);
+    if (rc != ORBX_OK) return rc;
+    TrackArgs tr = {true, map, ids, kf, kf->kps, kf->count, nullptr, nullptr, th, log_scale_factor, 0, projected, proj_u, proj_v, view, nullptr, nullptr,
+                    kf->roff, nullptr};
+    return track_run(m, cur, occupied, tr, n_ids, nullptr, max_dist, check_orientation, match, false, true);
 }

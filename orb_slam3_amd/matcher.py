@@ -1257,6 +1257,77 @@ class ORBmatcher:
         del keep
         return nm[:K], match, pr, ((pu, pv) if want_uv else None)
 
+    # ---- the Tracking thread's searches whose queries are another frame's map points, from map ids (k_track_project) ----
+    def _track_outputs(self, Cur: DeviceFrame, n, occ, want_projected, want_uv):
+        cm = np.full(self._frame_rows(Cur, occ), -1, np.int32)
+        pr = np.zeros(n, np.uint8) if want_projected else None
+        pu, pv = (np.zeros(n, np.float32), np.zeros(n, np.float32)) if want_uv else (None, None)
+        return cm, pr, pu, pv
+
+    def TrackLastFrame(self, Cur: DeviceFrame, Last: DeviceFrame, cam, pose, map: DeviceMap, ids, th: float, level_mode: int = 0, has_obs=None,
+                       cur_occupied=None, want_projected: bool = True, want_uv: bool = False):
+        """SearchByProjection(CurrentFrame, LastFrame, th, bMono) (ORBmatcher.cc:1676-1887) from map ids (orbx_frame_track_last_frame_map): ids[i] =
+        the slot of LastFrame.mvpMapPoints[i] or -1 (none / outlier), has_obs[i] = Observations() > 0; cam / pose are the CURRENT frame's; the
+        projection, the gates and the windows run on the device.  Returns (nmatches, cur_match [N], projected [n_ids] or None, (proj_u, proj_v) or
+        None); cur_match[j] >= 0 is the LAST frame's feature index, -2 a slot the rotation check cleared."""
+        from ._lib import Camera, FramePose
+        i, ho, occ = _i32(ids), _u8(has_obs), _u8(cur_occupied)
+        cm, pr, pu, pv = self._track_outputs(Cur, len(i), occ, want_projected, want_uv)
+        c, p = Camera(*[float(x) for x in cam]), FramePose.make(*pose)
+        n = check(self._L.orbx_frame_track_last_frame_map(self._h, Cur._h, Last._h, ptr(occ), C.byref(c), C.byref(p), map._h, len(i), ptr(i), ptr(ho),
+                                                          float(th), int(level_mode), int(self.mbCheckOrientation), ptr(cm), ptr(pr), ptr(pu), ptr(pv)),
+                  "orbx_frame_track_last_frame_map")
+        return n, cm[:Cur.count()], pr, ((pu, pv) if want_uv else None)
+
+    def SearchByProjectionKeyFrame(self, Cur: DeviceFrame, KF: DeviceKeyFrame, cam, pose, log_scale_factor: float, map: DeviceMap, ids, th: float,
+                                   max_dist: float, check_orientation: bool = True, occupied=None, want_projected: bool = True,
+                                   want_uv: bool = False):
+        """SearchByProjection(CurrentFrame, pKF, sAlreadyFound, th, ORBdist) (ORBmatcher.cc:1889-2010) from map ids
+        (orbx_frame_search_by_projection_keyframe_map): ids[i] = the slot of pKF's map point i or -1 (none / bad / already found).
+        Returns (nmatches, match [N], projected or None, (proj_u, proj_v) or None); match[j] >= 0 is the KEY FRAME's feature index."""
+        from ._lib import Camera, FramePose
+        i, occ = _i32(ids), _u8(occupied)
+        cm, pr, pu, pv = self._track_outputs(Cur, len(i), occ, want_projected, want_uv)
+        c, p = Camera(*[float(x) for x in cam]), FramePose.make(*pose)
+        n = check(self._L.orbx_frame_search_by_projection_keyframe_map(self._h, Cur._h, ptr(occ), C.byref(c), C.byref(p), float(log_scale_factor),
+                                                                       KF._h, map._h, len(i), ptr(i), float(th), float(max_dist),
+                                                                       int(bool(check_orientation)), ptr(cm), ptr(pr), ptr(pu), ptr(pv)),
+                  "orbx_frame_search_by_projection_keyframe_map")
+        return n, cm[:Cur.count()], pr, ((pu, pv) if want_uv else None)
+
+    @staticmethod
+    def _left_view(view):
+        V = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).ravel() for x in view]), np.float32)
+        assert V.size == 23, "view: (R, t, twc, params8) of the left camera"
+        return V
+
+    def TrackLastFrameFisheye(self, Cur: DeviceFrame, Last: DeviceFrame, view, Trl, map: DeviceMap, ids, th: float, level_mode: int = 0, has_obs=None,
+                              cur_occupied=None, want_projected: bool = True, want_uv: bool = False):
+        """TrackLastFrame for a fisheye-stereo rig (orbx_frame_track_last_frame_fisheye_map): view = (R, t, twc, params8) of the CURRENT frame's left
+        camera, Trl = (R [3, 3], t [3]) of GetRelativePoseTrl(); Last is a rig handle too and ids has N_left + N_right entries.  Returns as
+        TrackLastFrame; cur_match holds N entries of both cameras."""
+        i, ho, occ = _i32(ids), _u8(has_obs), _u8(cur_occupied)
+        cm, pr, pu, pv = self._track_outputs(Cur, len(i), occ, want_projected, want_uv)
+        V, R, t = self._left_view(view), _f32(np.asarray(Trl[0]).reshape(9)), _f32(np.asarray(Trl[1]).reshape(3))
+        n = check(self._L.orbx_frame_track_last_frame_fisheye_map(self._h, Cur._h, Last._h, ptr(occ), ptr(V), ptr(R), ptr(t), map._h, len(i), ptr(i),
+                                                                  ptr(ho), float(th), int(level_mode), int(self.mbCheckOrientation), ptr(cm), ptr(pr),
+                                                                  ptr(pu), ptr(pv)), "orbx_frame_track_last_frame_fisheye_map")
+        return n, cm[:Cur.count()], pr, ((pu, pv) if want_uv else None)
+
+    def SearchByProjectionKeyFrameFisheye(self, Cur: DeviceFrame, KF: DeviceKeyFrame, view, log_scale_factor: float, map: DeviceMap, ids, th: float,
+                                          max_dist: float, check_orientation: bool = True, occupied=None, want_projected: bool = True,
+                                          want_uv: bool = False):
+        """SearchByProjectionKeyFrame for a fisheye-stereo rig (orbx_frame_search_by_projection_keyframe_fisheye_map): the left camera only is
+        searched; match holds N entries, the right camera's stay -1."""
+        i, occ = _i32(ids), _u8(occupied)
+        cm, pr, pu, pv = self._track_outputs(Cur, len(i), occ, want_projected, want_uv)
+        V = self._left_view(view)
+        n = check(self._L.orbx_frame_search_by_projection_keyframe_fisheye_map(self._h, Cur._h, ptr(occ), ptr(V), float(log_scale_factor), KF._h, map._h,
+                                                                               len(i), ptr(i), float(th), float(max_dist), int(bool(check_orientation)),
+                                                                               ptr(cm), ptr(pr), ptr(pu), ptr(pv)),
+                  "orbx_frame_search_by_projection_keyframe_fisheye_map")
+        return n, cm[:Cur.count()], pr, ((pu, pv) if want_uv else None)
+
     def DistinctiveDescriptorsKeyFramesToMap(self, kfs, set_ptr, obs_kf, obs_idx, map: DeviceMap, set_id):
         """DistinctiveDescriptorsKeyFrames with set s's winning row written into the descriptor of slot set_id[s] of the table
         (orbx_keyframe_distinctive_descriptors_to_map); an empty set leaves its slot as it is.  Returns best_obs[n_sets]."""

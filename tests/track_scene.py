@@ -1,0 +1,542 @@
+"""The scene and the COMPOSED reference of the Tracking searches that run from map ids (tests/test_gpu_track_map.py, tests/test_track_map_abi.py,
+tools/track_map_latency.py): TrackWithMotionModel's SearchByProjection(Cur, Last, th, bMono) ("M2") and Relocalization's SearchByProjection(Cur, pKF,
+sAlreadyFound, th, ORBdist) ("M3") on a monocular / rectified frame.  Nothing here calls the code under test: the gates and the queries are float32
+numpy with one rounding per operation in the order of the host loops the calls replace (orb_slam3_amd/cpp/ORBmatcher_slam.inl), the searches are the
+oracle's search_by_projection_frame / search_by_projection_window on the surviving entries in source order, indices mapped back through the
+survivor list.  The second half of the file is the same for a fisheye-stereo rig."""
+import numpy as np
+
+f32 = np.float32
+BOUNDS = (0.0, 320.0, 0.0, 240.0)
+CAM = (200.0, 200.0, 160.0, 120.0, 0.0, 0.0, 0.0, 0.0, 0.0, 40.0)   # orbx_camera: fx, fy, cx, cy, k1, k2, p1, p2, k3, bf
+NLEVELS, SCALE = 8, 1.2
+N_SRC, N_CUR, CAPACITY, N_DUP = 600, 600, 2000, 60
+TH_HIGH = 100
+SEEDS = (11, 12)
+# what a source feature's map point is: 0 ordinary, 1 behind the camera, 2 outside the image, 3 beyond 1.2 mfMaxDistance, 4 below 0.8 mfMinDistance,
+# 5 ordinary with a source octave outside [0, nlevels), 6 u == mnMaxX in float32 bits
+KINDS = ("ordinary", "behind", "image", "above", "below", "octave", "edge")
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, f32).view(np.uint32)
+
+
+def camera_points(pose, pos):
+    """x3Dc = Rcw p + tcw, one rounding per operation, summed as k_fuse_project sums."""
+    Rcw, tcw, _ = pose
+    R, P = Rcw.astype(f32), pos.astype(f32)
+    return [((R[r, 0] * P[:, 0] + R[r, 1] * P[:, 1]) + R[r, 2] * P[:, 2]) + tcw[r] for r in range(3)]
+
+
+def project(pose, pos):
+    """(u, v, invz, inside): Pinhole::project and the image test with BOTH sides inclusive (u < mnMinX || u > mnMaxX rejects)."""
+    fx, fy, cx, cy = [f32(x) for x in CAM[:4]]
+    Pc = camera_points(pose, pos)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        invz = f32(1) / Pc[2]
+        u, v = (fx * Pc[0]) / Pc[2] + cx, (fy * Pc[1]) / Pc[2] + cy
+    assert u.dtype == f32 and invz.dtype == f32
+    b = [f32(x) for x in BOUNDS]
+    inside = ~((u < b[0]) | (u > b[1])) & ~((v < b[2]) | (v > b[3]))
+    return u, v, invz, inside
+
+
+def make_scene(seed, n_src=N_SRC, n_cur=N_CUR, cur=None, src_kps=None, p_none=0.15):
+    """A current frame of n_cur features (320 x 240, 8 levels, scale 1.2), a source (last frame / key frame) of n_src features, a table of 2000 slots
+    and ids [n_src] with about 15 % (p_none) -1.  The current frame's features sit at 70 % of the ordinary points' projections (0.8 px noise, 2 - 20 % of
+    the descriptor's bits flipped, the source's octave, the source's angle turned by a common 10 degrees -- a tenth of them by anything) plus clutter;
+    half of them have mvuRight.  60 source features hold near-duplicates of other features' points (1 cm, 3 % of the bits): they compete for one
+    feature.  cur = dict(kps, desc) / src_kps: frames that exist already (an extractor's batch: the tests of pending counts) -- the first points then
+    sit at cur's features and the source's rows are src_kps (no octave is bent out of range).  Returns a dict; `kind` [n_src] says what each
+    entry is (-1: no point)."""
+    from orb_slam3_amd._lib import KP_DTYPE
+    rng = np.random.default_rng(seed)
+    fx, fy, cx, cy, bf = CAM[0], CAM[1], CAM[2], CAM[3], CAM[9]
+    sf = (f32(SCALE) ** np.arange(NLEVELS)).astype(f32)
+    lsf = float(np.log(f32(SCALE)))
+    w = np.array([0.01, -0.02, 0.015])
+    a = np.linalg.norm(w)
+    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]]) / a
+    Rcw = (np.eye(3) + np.sin(a) * K + (1 - np.cos(a)) * K @ K).astype(f32)
+    tcw = np.array([0.05, -0.03, 0.08], f32)
+    Ow = (-Rcw.astype(np.float64).T @ tcw.astype(np.float64)).astype(f32)
+    pose = (Rcw, tcw, Ow)
+    R64, t64 = Rcw.astype(np.float64), tcw.astype(np.float64)
+
+    if src_kps is not None:
+        n_src = len(src_kps)
+    kind = rng.choice(6, n_src, p=[0.74, 0.08, 0.06, 0.04, 0.04, 0.04]).astype(np.int32)
+    if src_kps is not None:
+        kind[kind == 5] = 0
+    kind[rng.random(n_src) < p_none] = -1
+    # the points in the CURRENT camera's frame, then in the world
+    z = rng.uniform(2.0, 12.0, n_src)
+    u0, v0 = rng.uniform(12, 308, n_src), rng.uniform(12, 228, n_src)
+    at = 0 if cur is None else min(n_src, len(cur["kps"]))
+    if cur is not None:
+        u0[:at], v0[:at] = cur["kps"]["x"][:at], cur["kps"]["y"][:at]
+    pc = np.stack([(u0 - cx) / fx * z, (v0 - cy) / fy * z, z], axis=1)
+    pc[kind == 1] *= -1.0                       # mirrored through the camera centre: the same (u, v), z < 0
+    pc[kind == 2, 0] *= 2.5
+    pc[kind == 2, 0] += np.where(pc[kind == 2, 0] >= 0, 1.0, -1.0) * pc[kind == 2, 2]   # well outside in x
+    octave = rng.integers(0, NLEVELS - 1, n_src).astype(np.int32)
+    if src_kps is not None:
+        octave = np.clip(src_kps["octave"], 0, NLEVELS - 1).astype(np.int32)
+    # near-duplicates: entry j takes the point (and the octave) of an ordinary entry s
+    ordinary = np.flatnonzero(kind == 0)
+    dup = rng.choice(ordinary, N_DUP if n_src >= 300 else 0, replace=False)
+    dup_of = rng.choice(np.setdiff1d(ordinary, dup), len(dup))
+    pc[dup] = pc[dup_of] + rng.normal(0, 0.01, (len(dup), 3))
+    octave[dup] = octave[dup_of]
+    pos = ((pc - t64) @ R64).astype(f32)        # Rcw^T (pc - tcw)
+    dist = np.linalg.norm(pos.astype(np.float64) - Ow.astype(np.float64), axis=1)
+    max_d = dist * sf[octave].astype(np.float64) * rng.uniform(0.96, 0.999, n_src)   # PredictScale gives the source's octave
+    min_d = max_d / float(sf[-1])
+    max_d[kind == 3] = 0.5 * dist[kind == 3]   # 1.2 mfMaxDistance < dist3D at every octave
+    min_d[kind == 3] = max_d[kind == 3] / float(sf[-1])
+    min_d[kind == 4] = 2.0 * max_d[kind == 4]
+    normal = rng.normal(0, 1, (n_src, 3))
+    normal /= np.linalg.norm(normal, axis=1, keepdims=True)
+    desc = rng.integers(0, 256, (n_src, 32), dtype=np.uint8)
+    if cur is not None:
+        desc[:at] = cur["desc"][:at] ^ np.packbits(rng.random((at, 256)) < 0.05, axis=1, bitorder="little")
+    desc[dup] = desc[dup_of] ^ np.packbits(rng.random((len(dup), 256)) < 0.03, axis=1, bitorder="little")
+    pos, normal, min_d, max_d = pos, normal.astype(f32), min_d.astype(f32), max_d.astype(f32)
+
+    # two points whose u equals mnMaxX in float32 bits (the inclusive side of the image test): found by trial, the exact arithmetic decides
+    edge = []
+    free = np.flatnonzero(kind == 0)
+    free = free[~np.isin(free, np.concatenate([dup, dup_of]))][:2] if n_src >= 300 else np.zeros(0, np.int64)
+    for j in free:
+        for _ in range(20000):
+            zz, vv = rng.uniform(2.0, 12.0), rng.uniform(12, 228)
+            p = ((np.array([(BOUNDS[1] - cx) / fx * zz, (vv - cy) / fy * zz, zz]) - t64) @ R64).astype(f32)
+            uu = project(pose, p[None, :])[0]
+            if _bits(uu)[0] == _bits(f32(BOUNDS[1])):
+                pos[j] = p
+                d = float(np.linalg.norm(p.astype(np.float64) - Ow.astype(np.float64)))
+                max_d[j] = f32(d * float(sf[octave[j]]) * 0.98)
+                min_d[j] = f32(float(max_d[j]) / float(sf[-1]))
+                kind[j] = 6
+                edge.append(int(j))
+                break
+    # the source's rows: mvKeysUn of the last frame / the key frame (only octave and angle are read)
+    if src_kps is None:
+        src_kps = np.zeros(n_src, KP_DTYPE)
+        src_kps["x"], src_kps["y"] = rng.uniform(1, 319, n_src), rng.uniform(1, 239, n_src)
+        src_octave = octave.copy()
+        bad = np.flatnonzero(kind == 5)
+        src_octave[bad] = np.resize(np.array([-1, NLEVELS, NLEVELS + 3, -2], np.int32), len(bad))
+        src_kps["octave"] = src_octave
+        src_kps["size"] = 31.0 * sf[octave]
+        src_kps["angle"] = rng.uniform(0, 360, n_src)
+        src_kps["response"] = rng.integers(7, 200, n_src)
+        src_kps["class_id"] = -1
+    src_kps = np.ascontiguousarray(src_kps, KP_DTYPE)
+
+    # the current frame: features at the projections of the visible points, plus clutter
+    pc_now = pos.astype(np.float64) @ R64.T + t64
+    with np.errstate(divide="ignore", invalid="ignore"):
+        uu, vv = fx * pc_now[:, 0] / pc_now[:, 2] + cx, fy * pc_now[:, 1] / pc_now[:, 2] + cy
+    vis = (kind >= 0) & (pc_now[:, 2] > 0) & (uu > 2) & (uu < 318) & (vv > 2) & (vv < 238) & ~np.isin(np.arange(n_src), dup)
+    sel = np.flatnonzero(vis & (rng.random(n_src) < 0.7))
+    n_clutter = max(n_cur - len(sel), 0)
+    n = len(sel) + n_clutter
+    kp = np.zeros(n, KP_DTYPE)
+    kp["x"][:len(sel)] = np.clip(uu[sel] + rng.normal(0, 0.8, len(sel)), 0.5, 319.5)
+    kp["y"][:len(sel)] = np.clip(vv[sel] + rng.normal(0, 0.8, len(sel)), 0.5, 239.5)
+    kp["octave"][:len(sel)] = octave[sel]
+    turn = np.where(rng.random(len(sel)) < 0.9, 10.0 + rng.normal(0, 2.0, len(sel)), rng.uniform(0, 360, len(sel)))
+    kp["angle"][:len(sel)] = np.mod(src_kps["angle"][sel] - turn, 360.0)
+    kp["x"][len(sel):], kp["y"][len(sel):] = rng.uniform(1, 319, n_clutter), rng.uniform(1, 239, n_clutter)
+    kp["octave"][len(sel):] = rng.integers(0, NLEVELS, n_clutter)
+    kp["angle"][len(sel):] = rng.uniform(0, 360, n_clutter)
+    kp["size"] = 31.0 * sf[kp["octave"]]
+    kp["response"] = rng.integers(7, 200, n)
+    kp["class_id"] = -1
+    flip = rng.uniform(0.02, 0.20, len(sel))[:, None]
+    d = np.concatenate([desc[sel] ^ np.packbits(rng.random((len(sel), 256)) < flip, axis=1, bitorder="little"),
+                        rng.integers(0, 256, (n_clutter, 32), dtype=np.uint8)])
+    ur = np.full(n, -1.0, f32)
+    ur[:len(sel)] = (kp["x"][:len(sel)] - bf / pc_now[sel, 2] + rng.normal(0, 0.4, len(sel))).astype(f32)
+    ur[len(sel):] = kp["x"][len(sel):] - rng.uniform(2, 30, n_clutter).astype(f32)
+    ur[rng.random(n) < 0.5] = -1.0
+    perm = rng.permutation(n)
+    if cur is None:
+        cur = dict(kps=np.ascontiguousarray(kp[perm]), desc=np.ascontiguousarray(d[perm]), u_right=np.ascontiguousarray(ur[perm]))
+    else:
+        cur = dict(kps=np.ascontiguousarray(cur["kps"], KP_DTYPE), desc=np.ascontiguousarray(cur["desc"], np.uint8), u_right=None)
+        n = len(cur["kps"])
+
+    # the table: the points at random slots among 2000, every other field of a -1 entry unused
+    slots = rng.permutation(CAPACITY)[:n_src].astype(np.int32)
+    ids = np.where(kind >= 0, slots, -1).astype(np.int32)
+    return dict(pose=pose, cam=CAM, bounds=np.array(BOUNDS, f32), scale_factors=sf, log_scale_factor=lsf, nlevels=NLEVELS,
+                map_points=dict(pos=pos, normal=normal, min_dist=min_d, max_dist=max_d, desc=desc), slots=slots, ids=ids, kind=kind,
+                src_kps=src_kps, cur=cur, edge=edge, dup=dup, has_obs=(rng.random(n_src) < 0.9).astype(np.uint8),
+                occupied=(rng.random(n) < 0.04).astype(np.uint8))
+
+
+def gates_m2(sc, ids=None):
+    """(projected, searched, u, v, ur) per source entry for TrackWithMotionModel's loop: x3Dc, invzc = 1 / z with invzc < 0 rejected, the inclusive
+    image test, ur = u - bf invzc; searched = projected and the source's octave within [0, nlevels)."""
+    ids = sc["ids"] if ids is None else ids
+    n = len(ids)
+    mp = sc["map_points"]
+    u, v, invz, inside = project(sc["pose"], mp["pos"][:n])
+    have = ids >= 0
+    projected = have & ~(invz < 0) & inside
+    ur = u - f32(sc["cam"][9]) * invz
+    o = sc["src_kps"]["octave"][:n]
+    searched = projected & (o >= 0) & (o < sc["nlevels"])
+    z = f32(0)
+    return projected, searched, np.where(have, u, z), np.where(have, v, z), np.where(have, ur, z)
+
+
+def gates_m3(sc, ids=None):
+    """(projected, u, v, level, stats) per source entry for Relocalization's loop: NO depth gate, the inclusive image test, dist3D = |p - Ow| within
+    [0.8f mfMinDistance, 1.2f mfMaxDistance], PredictScale(dist3D, &CurrentFrame)."""
+    ids = sc["ids"] if ids is None else ids
+    n = len(ids)
+    mp = sc["map_points"]
+    P = mp["pos"][:n]
+    u, v, invz, inside = project(sc["pose"], P)
+    have = ids >= 0
+    Ow = sc["pose"][2]
+    PO = [P[:, r] - Ow[r] for r in range(3)]
+    dist = np.sqrt(((f32(0) + PO[0] * PO[0]) + PO[1] * PO[1]) + PO[2] * PO[2])
+    mx, mn = mp["max_dist"][:n], mp["min_dist"][:n]
+    below, above = dist < f32(0.8) * mn, dist > f32(1.2) * mx
+    ok = have & inside & ~(below | above)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lvl = np.ceil(np.log((mx / dist).astype(np.float64)).astype(f32) / f32(sc["log_scale_factor"]))
+    lvl = np.clip(np.nan_to_num(lvl, nan=0.0, posinf=1e6, neginf=-1e6), 0, sc["nlevels"] - 1).astype(np.int32)
+    assert dist.dtype == f32
+    stats = dict(behind_kept=int((ok & (invz < 0)).sum()), below=int((have & inside & below).sum()), above=int((have & inside & above).sum()),
+                 image=int((have & ~inside).sum()))
+    z = f32(0)
+    return ok, np.where(have, u, z), np.where(have, v, z), lvl, stats
+
+
+def grid_of(oracle, sc):
+    b = sc["bounds"]
+    return oracle.OracleGrid(sc["cur"]["kps"], float(b[0]), float(b[1]), float(b[2]), float(b[3]))
+
+
+def _back(cm, sel):
+    if len(sel) == 0:
+        return np.full(len(cm), -1, np.int32)
+    return np.where(cm >= 0, sel[np.maximum(cm, 0)], -1).astype(np.int32)
+
+
+def queries_m2(sc, ids=None, has_obs=None):
+    """(sel, q): the flat form's queries of the searched entries, in source order."""
+    ids = sc["ids"] if ids is None else ids
+    n = len(ids)
+    projected, searched, u, v, ur = gates_m2(sc, ids)
+    sel = np.flatnonzero(searched)
+    k = sc["src_kps"][:n]
+    ho = np.ones(n, np.uint8) if has_obs is None else np.asarray(has_obs, np.uint8)
+    q = dict(u=u[sel], v=v[sel], ur=ur[sel], octave=k["octave"][sel].astype(np.int32), angle=k["angle"][sel].astype(f32),
+             desc=np.ascontiguousarray(sc["map_points"]["desc"][:n][sel]), has_obs=np.ascontiguousarray(ho[sel]))
+    return sel, q
+
+
+def reference_m2(oracle, sc, th, level_mode=0, check_orientation=True, with_ur=True, ids=None, has_obs=None, occupied=None):
+    """dict(nm, match [N of cur] -- the SOURCE feature index or -1, projected, u, v, sel, q) of orbx_frame_track_last_frame_map."""
+    ids = sc["ids"] if ids is None else ids
+    projected, _, u, v, _ = gates_m2(sc, ids)
+    sel, q = queries_m2(sc, ids, has_obs)
+    cur = sc["cur"]
+    nm, cm = oracle.search_by_projection_frame(grid_of(oracle, sc), cur["desc"], sc["scale_factors"], q, th, level_mode, check_orientation,
+                                               cur["u_right"] if with_ur else None, occupied)
+    return dict(nm=nm, match=_back(cm, sel), projected=projected.astype(np.uint8), u=u, v=v, sel=sel, q=q)
+
+
+def queries_m3(sc, th, ids=None):
+    ids = sc["ids"] if ids is None else ids
+    n = len(ids)
+    ok, u, v, lvl, _ = gates_m3(sc, ids)
+    sel = np.flatnonzero(ok)
+    q = dict(x=u[sel], y=v[sel], r=(f32(th) * sc["scale_factors"][lvl[sel]]).astype(f32), min_level=(lvl[sel] - 1).astype(np.int32),
+             max_level=(lvl[sel] + 1).astype(np.int32), angle=sc["src_kps"]["angle"][:n][sel].astype(f32),
+             desc=np.ascontiguousarray(sc["map_points"]["desc"][:n][sel]))
+    return sel, q
+
+
+def reference_m3(oracle, sc, th, max_dist, check_orientation=True, ids=None, occupied=None):
+    """The same of orbx_frame_search_by_projection_keyframe_map (accept iff (float)bestDist <= max_dist; mvuRight is never read)."""
+    ids = sc["ids"] if ids is None else ids
+    ok, u, v, _, stats = gates_m3(sc, ids)
+    sel, q = queries_m3(sc, th, ids)
+    nm, cm = oracle.search_by_projection_window(grid_of(oracle, sc), sc["cur"]["desc"], q, float(max_dist), check_orientation, occupied=occupied)
+    return dict(nm=nm, match=_back(cm, sel), projected=ok.astype(np.uint8), u=u, v=v, sel=sel, q=q, stats=stats)
+
+
+def stolen_m2(oracle, sc, ref, th):
+    """Searched entries whose independent best feature is acceptable but went to an EARLIER entry in the replay (the order matters for them)."""
+    sel, q = ref["sel"], ref["q"]
+    lvl = q["octave"]
+    fq = dict(u=q["u"], v=q["v"], ur=np.zeros(len(sel), f32), r=(f32(th) * sc["scale_factors"][lvl]).astype(f32), level=(lvl + 1).astype(np.int32),
+              desc=q["desc"])
+    # fuse_search looks at levels [level - 1, level]: two passes cover [o - 1, o + 1]
+    bi, bd = oracle.fuse_search(grid_of(oracle, sc), sc["cur"]["desc"], None, None, fq)
+    fq2 = dict(fq, level=lvl.astype(np.int32))
+    bi2, bd2 = oracle.fuse_search(grid_of(oracle, sc), sc["cur"]["desc"], None, None, fq2)
+    take2 = (bd2 < bd) | ((bd2 == bd) & (bi2 >= 0) & ((bi < 0) | (bi2 < bi)))
+    bi, bd = np.where(take2, bi2, bi), np.where(take2, bd2, bd)
+    owner = ref["match"]
+    return int(sum(1 for j in range(len(sel)) if bi[j] >= 0 and bd[j] <= TH_HIGH and 0 <= owner[bi[j]] < sel[j]))
+
+
+def check_conditions(oracle, sc):
+    """What the issue demands of the inputs, asserted on the oracle's output alone (M2: th = 7, level_mode 0, no mvuRight, nothing occupied; M3:
+    th = 10, ORBdist = 100).  Returns the figures."""
+    ids, kind = sc["ids"], sc["kind"]
+    have = int((ids >= 0).sum())
+    assert len(ids) == N_SRC and 0.10 * N_SRC <= N_SRC - have <= 0.20 * N_SRC and len(sc["dup"]) == N_DUP and 550 <= len(sc["cur"]["kps"]) <= 650
+    r2 = reference_m2(oracle, sc, 7.0, 0, True, False)
+    r2_free = reference_m2(oracle, sc, 7.0, 0, False, False)
+    r3 = reference_m3(oracle, sc, 10.0, 100.0, True)
+    r3_free = reference_m3(oracle, sc, 10.0, 100.0, False)
+    fig = dict(m2_projected=r2["projected"].sum() / have, m2_matched=r2["nm"] / have, m3_projected=r3["projected"].sum() / have,
+               m3_matched=r3["nm"] / have, stolen=stolen_m2(oracle, sc, r2_free, 7.0), m2_cleared=r2_free["nm"] - r2["nm"],
+               m3_cleared=r3_free["nm"] - r3["nm"], **r3["stats"])
+    for key in ("m2_projected", "m3_projected"):
+        assert fig[key] >= 0.5, fig
+    for key in ("m2_matched", "m3_matched"):
+        assert fig[key] >= 0.2, fig
+    assert fig["stolen"] >= 8, fig
+    assert fig["m2_cleared"] >= 1 and fig["m3_cleared"] >= 1, fig
+    # every gate removes or keeps at least one entry as stated
+    p2, s2 = gates_m2(sc)[:2]
+    edge = sc["edge"]
+    assert len(edge) == 2 and all(p2[j] and r3["projected"][j] for j in edge), (edge, fig)          # u == mnMaxX is INSIDE here
+    assert all(_bits(r2["u"][j:j + 1])[0] == _bits(f32(BOUNDS[1])) for j in edge)
+    behind = kind == 1
+    assert behind.sum() >= 5 and not p2[behind].any(), fig                                           # M2 rejects them all
+    assert fig["behind_kept"] >= 1 and r3["projected"][behind].sum() >= 1, fig                        # M3 keeps those inside the bounds
+    assert fig["below"] >= 1 and fig["above"] >= 1 and fig["image"] >= 1, fig
+    assert not r3["projected"][(kind == 3) | (kind == 4)].any() and p2[(kind == 3) | (kind == 4)].all()
+    assert not p2[kind == 2].any()
+    octv = kind == 5
+    assert octv.sum() >= 4 and p2[octv].all() and not s2[octv].any(), fig                             # projected, never searched
+    assert (sc["src_kps"]["octave"][octv] < 0).any() and (sc["src_kps"]["octave"][octv] >= NLEVELS).any()
+    return fig
+
+
+# ---------------------------------------------------------------------------------------------------------
+# The fisheye-stereo rig (Frame::Nleft != -1): KannalaBrandt8::project is the ORACLE's (orbo_kb8_project), the searches are the oracle's
+# search_by_projection_frame_fisheye (both cameras, the twin) and search_by_projection_window on the LEFT features (Relocalization's form).
+# ---------------------------------------------------------------------------------------------------------
+RIG_BOUNDS = (0.0, 512.0, 0.0, 512.0)
+KB8_LEFT = (190.97847715128717, 190.9733070521226, 254.93170605935475, 256.8974428996504, 0.0034823894022493434, 0.0007150348452162257,
+            -0.0020532361418706202, 0.00020293673591811182)   # TUM-VI cam0: fx, fy, cx, cy, k0 .. k3
+RIG_SEEDS = (13,)
+
+
+def kb8_project(oracle, params8, Pc):
+    """(u, v) of the camera-frame points Pc = [X, Y, Z] (float32 arrays) through the oracle's KannalaBrandt8::project."""
+    import ctypes as C
+    L = oracle.lib()
+    L.orbo_kb8_project.restype = None
+    L.orbo_kb8_project.argtypes = [C.c_void_p, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    prm = np.ascontiguousarray(params8, f32)
+    n = len(Pc[0])
+    u, v = np.zeros(n, f32), np.zeros(n, f32)
+    a, b = C.c_float(0), C.c_float(0)
+    for i in range(n):
+        L.orbo_kb8_project(prm.ctypes.data, float(Pc[0][i]), float(Pc[1][i]), float(Pc[2][i]), C.byref(a), C.byref(b))
+        u[i], v[i] = a.value, b.value
+    return u, v
+
+
+def right_points(Trl, Pc):
+    """x3Dr = Trl_R x3Dc + Trl_t, one rounding per operation, summed as k_fuse_project sums."""
+    R, t = Trl[0].astype(f32), Trl[1].astype(f32)
+    return [((R[r, 0] * Pc[0] + R[r, 1] * Pc[1]) + R[r, 2] * Pc[2]) + t[r] for r in range(3)]
+
+
+def _inside(u, v, bounds):
+    b = [f32(x) for x in bounds]
+    return ~((u < b[0]) | (u > b[1])) & ~((v < b[2]) | (v > b[3]))
+
+
+def make_rig_scene(oracle, seed, n_src=N_SRC, n_left_src=330, n_side=300, p_none=0.15):
+    """The rig twin of make_scene: a source rig of n_left_src + (n_src - n_left_src) features, a current rig frame whose left / right features sit at
+    the projections of the ordinary points into the left camera / into the right camera as the reference predicts it (Trl x3Dc through the LEFT
+    parameters), plus clutter; a 2000-slot table, 15 % of the ids -1, near-duplicates, points behind the cameras, outside the image, outside their
+    distance bounds, source octaves out of range."""
+    from orb_slam3_amd._lib import KP_DTYPE
+    rng = np.random.default_rng(seed)
+    sf = (f32(SCALE) ** np.arange(NLEVELS)).astype(f32)
+    lsf = float(np.log(f32(SCALE)))
+    base = make_scene(seed, n_src=8)            # (the pose)
+    pose = base["pose"]
+    Rcw, tcw, Ow = pose
+    R64, t64 = Rcw.astype(np.float64), tcw.astype(np.float64)
+    a = np.array([0.011, -0.007, 0.004])
+    Trl = ((np.array([[1, -a[2], a[1]], [a[2], 1, -a[0]], [-a[1], a[0], 1]])).astype(f32), np.array([-0.101, 0.002, 0.001], f32))
+    kind = rng.choice(6, n_src, p=[0.74, 0.08, 0.06, 0.04, 0.04, 0.04]).astype(np.int32)
+    kind[rng.random(n_src) < p_none] = -1
+    z = rng.uniform(2.0, 12.0, n_src)
+    pc = np.stack([rng.uniform(-1, 1, n_src) * z, rng.uniform(-1, 1, n_src) * z, z], axis=1)
+    nb = int((kind == 1).sum())                 # slightly behind the camera on a diagonal: theta about 96 degrees still lands inside the image's corners
+    ab = rng.uniform(2.0, 8.0, nb)
+    pc[kind == 1] = np.stack([ab * rng.choice([-1.0, 1.0], nb), ab * rng.choice([-1.0, 1.0], nb), -0.1 * ab], axis=1)
+    pc[kind == 2, 0] = np.where(rng.random((kind == 2).sum()) < 0.5, 5.0, -5.0) * pc[kind == 2, 2]
+    octave = rng.integers(0, NLEVELS - 1, n_src).astype(np.int32)
+    ordinary = np.flatnonzero(kind == 0)
+    dup = rng.choice(ordinary, N_DUP, replace=False)
+    dup_of = rng.choice(np.setdiff1d(ordinary, dup), len(dup))
+    pc[dup] = pc[dup_of] + rng.normal(0, 0.01, (len(dup), 3))
+    octave[dup] = octave[dup_of]
+    pos = ((pc - t64) @ R64).astype(f32)
+    dist = np.linalg.norm(pos.astype(np.float64) - Ow.astype(np.float64), axis=1)
+    max_d = dist * sf[octave].astype(np.float64) * rng.uniform(0.96, 0.999, n_src)
+    min_d = max_d / float(sf[-1])
+    max_d[kind == 3] = 0.5 * dist[kind == 3]
+    min_d[kind == 3] = max_d[kind == 3] / float(sf[-1])
+    min_d[kind == 4] = 2.0 * max_d[kind == 4]
+    normal = rng.normal(0, 1, (n_src, 3))
+    normal /= np.linalg.norm(normal, axis=1, keepdims=True)
+    desc = rng.integers(0, 256, (n_src, 32), dtype=np.uint8)
+    desc[dup] = desc[dup_of] ^ np.packbits(rng.random((len(dup), 256)) < 0.03, axis=1, bitorder="little")
+    src_kps = np.zeros(n_src, KP_DTYPE)       # feature i < n_left_src: mvKeys[i]; beyond: mvKeysRight[i - n_left_src]
+    src_kps["x"], src_kps["y"] = rng.uniform(1, 511, n_src), rng.uniform(1, 511, n_src)
+    src_octave = octave.copy()
+    bad = np.flatnonzero(kind == 5)
+    src_octave[bad] = np.resize(np.array([-1, NLEVELS, NLEVELS + 3, -2], np.int32), len(bad))
+    src_kps["octave"], src_kps["size"], src_kps["angle"] = src_octave, 31.0 * sf[octave], rng.uniform(0, 360, n_src)
+    src_kps["response"], src_kps["class_id"] = 50.0, -1
+    mp = dict(pos=pos, normal=normal.astype(f32), min_dist=min_d.astype(f32), max_dist=max_d.astype(f32), desc=desc)
+    # the current rig frame
+    Pc = camera_points(pose, pos)
+    ul, vl = kb8_project(oracle, KB8_LEFT, Pc)
+    ur, vr = kb8_project(oracle, KB8_LEFT, right_points(Trl, Pc))
+    front = (kind >= 0) & ~(Pc[2] < 0) & ~np.isin(np.arange(n_src), dup)
+    sides = []
+    for (uu, vv) in ((ul, vl), (ur, vr)):
+        vis = np.flatnonzero(front & (uu > 2) & (uu < 510) & (vv > 2) & (vv < 510))
+        sel = rng.choice(vis, min(n_side - 60, len(vis)), replace=False)
+        n = len(sel) + 60
+        kp = np.zeros(n, KP_DTYPE)
+        kp["x"][:len(sel)] = np.clip(uu[sel] + rng.normal(0, 0.8, len(sel)), 0.5, 511.5)
+        kp["y"][:len(sel)] = np.clip(vv[sel] + rng.normal(0, 0.8, len(sel)), 0.5, 511.5)
+        kp["octave"][:len(sel)] = octave[sel]
+        turn = np.where(rng.random(len(sel)) < 0.9, 10.0 + rng.normal(0, 2.0, len(sel)), rng.uniform(0, 360, len(sel)))
+        kp["angle"][:len(sel)] = np.mod(src_kps["angle"][sel] - turn, 360.0)
+        kp["x"][len(sel):], kp["y"][len(sel):] = rng.uniform(1, 511, 60), rng.uniform(1, 511, 60)
+        kp["octave"][len(sel):], kp["angle"][len(sel):] = rng.integers(0, NLEVELS, 60), rng.uniform(0, 360, 60)
+        kp["size"], kp["response"], kp["class_id"] = 31.0 * sf[kp["octave"]], 50.0, -1
+        flip = rng.uniform(0.02, 0.20, len(sel))[:, None]
+        d = np.concatenate([desc[sel] ^ np.packbits(rng.random((len(sel), 256)) < flip, axis=1, bitorder="little"),
+                            rng.integers(0, 256, (60, 32), dtype=np.uint8)])
+        perm = rng.permutation(n)
+        sides.append((np.ascontiguousarray(kp[perm]), np.ascontiguousarray(d[perm])))
+    (kl, dl), (kr, dr) = sides
+    cur = dict(kps_left=kl, kps_right=kr, desc=np.ascontiguousarray(np.concatenate([dl, dr])), l2r=np.full(len(kl), -1, np.int32),
+               r2l=np.full(len(kr), -1, np.int32))
+    slots = rng.permutation(CAPACITY)[:n_src].astype(np.int32)
+    ids = np.where(kind >= 0, slots, -1).astype(np.int32)
+    N = len(kl) + len(kr)
+    return dict(pose=pose, view=(Rcw.reshape(9), tcw, Ow, np.array(KB8_LEFT, f32)), Trl=Trl, bounds=np.array(RIG_BOUNDS, f32), scale_factors=sf,
+                log_scale_factor=lsf, nlevels=NLEVELS, map_points=mp, slots=slots, ids=ids, kind=kind, src_kps=src_kps, n_left_src=n_left_src, cur=cur,
+                dup=dup, has_obs=(rng.random(n_src) < 0.9).astype(np.uint8), occupied=(rng.random(N) < 0.04).astype(np.uint8))
+
+
+def rig_gates_m2(oracle, sc, ids=None):
+    """(projected, searched, u, v, xr, yr): invzc < 0 rejected, KannalaBrandt8::project, the inclusive image test, the projection of Trl x3Dc through
+    the LEFT parameters (ORBmatcher.cc:1795-1796); searched = projected and the source's octave within [0, nlevels)."""
+    ids = sc["ids"] if ids is None else ids
+    n = len(ids)
+    Pc = camera_points(sc["pose"], sc["map_points"]["pos"][:n])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        invz = f32(1) / Pc[2]
+    u, v = kb8_project(oracle, KB8_LEFT, Pc)
+    xr, yr = kb8_project(oracle, KB8_LEFT, right_points(sc["Trl"], Pc))
+    have = ids >= 0
+    projected = have & ~(invz < 0) & _inside(u, v, sc["bounds"])
+    o = sc["src_kps"]["octave"][:n]
+    z = f32(0)
+    return projected, projected & (o >= 0) & (o < sc["nlevels"]), np.where(have, u, z), np.where(have, v, z), np.where(have, xr, z), np.where(have, yr, z)
+
+
+def rig_grids(oracle, sc):
+    b = [float(x) for x in sc["bounds"]]
+    return oracle.OracleGrid(sc["cur"]["kps_left"], *b), oracle.OracleGrid(sc["cur"]["kps_right"], *b)
+
+
+def rig_reference_m2(oracle, sc, th, level_mode=0, check_orientation=True, ids=None, has_obs=None, occupied=None):
+    """dict(nm, match [N = N_left + N_right] -- the SOURCE feature index or -1, projected, u, v, sel, q) of orbx_frame_track_last_frame_fisheye_map."""
+    ids = sc["ids"] if ids is None else ids
+    n = len(ids)
+    projected, searched, u, v, xr, yr = rig_gates_m2(oracle, sc, ids)
+    sel = np.flatnonzero(searched)
+    k = sc["src_kps"][:n]
+    ho = np.ones(n, np.uint8) if has_obs is None else np.asarray(has_obs, np.uint8)
+    q = dict(u=u[sel], v=v[sel], xr=xr[sel], yr=yr[sel], octave=k["octave"][sel].astype(np.int32), angle=k["angle"][sel].astype(f32),
+             desc=np.ascontiguousarray(sc["map_points"]["desc"][:n][sel]), has_obs=np.ascontiguousarray(ho[sel]))
+    gl, gr = rig_grids(oracle, sc)
+    nm, cm = oracle.search_by_projection_frame_fisheye(gl, gr, sc["cur"]["desc"], sc["scale_factors"], q, th, level_mode, check_orientation, occupied)
+    return dict(nm=nm, match=_back(cm, sel), projected=projected.astype(np.uint8), u=u, v=v, sel=sel, q=q)
+
+
+def rig_reference_m3(oracle, sc, th, max_dist, check_orientation=True, ids=None, occupied=None):
+    """The same of orbx_frame_search_by_projection_keyframe_fisheye_map: no depth gate, the LEFT camera only, angle = mvKeysUn[i].angle below the key
+    frame's N_left and 0.f beyond; match rows of N entries, -1 from N_left on; occupied [N], read below N_left."""
+    ids = sc["ids"] if ids is None else ids
+    n = len(ids)
+    mp = sc["map_points"]
+    P = mp["pos"][:n]
+    Pc = camera_points(sc["pose"], P)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        invz = f32(1) / Pc[2]
+    u, v = kb8_project(oracle, KB8_LEFT, Pc)
+    have = ids >= 0
+    Ow = sc["pose"][2]
+    PO = [P[:, r] - Ow[r] for r in range(3)]
+    dist = np.sqrt(((f32(0) + PO[0] * PO[0]) + PO[1] * PO[1]) + PO[2] * PO[2])
+    mx, mn = mp["max_dist"][:n], mp["min_dist"][:n]
+    inside = _inside(u, v, sc["bounds"])
+    below, above = dist < f32(0.8) * mn, dist > f32(1.2) * mx
+    ok = have & inside & ~(below | above)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lvl = np.ceil(np.log((mx / dist).astype(np.float64)).astype(f32) / f32(sc["log_scale_factor"]))
+    lvl = np.clip(np.nan_to_num(lvl, nan=0.0, posinf=1e6, neginf=-1e6), 0, sc["nlevels"] - 1).astype(np.int32)
+    sel = np.flatnonzero(ok)
+    angle = np.where(np.arange(n) < sc["n_left_src"], sc["src_kps"]["angle"][:n], f32(0)).astype(f32)
+    q = dict(x=u[sel], y=v[sel], r=(f32(th) * sc["scale_factors"][lvl[sel]]).astype(f32), min_level=(lvl[sel] - 1).astype(np.int32),
+             max_level=(lvl[sel] + 1).astype(np.int32), angle=angle[sel], desc=np.ascontiguousarray(mp["desc"][:n][sel]))
+    kl = sc["cur"]["kps_left"]
+    nl, N = len(kl), len(sc["cur"]["desc"])
+    occ = None if occupied is None else np.ascontiguousarray(occupied[:nl], np.uint8)
+    nm, cm = oracle.search_by_projection_window(rig_grids(oracle, sc)[0], sc["cur"]["desc"][:nl], q, float(max_dist), check_orientation, occupied=occ)
+    full = np.full(N, -1, np.int32)
+    full[:nl] = _back(cm, sel)
+    z = f32(0)
+    stats = dict(behind_kept=int((ok & (invz < 0)).sum()), below=int((have & inside & below).sum()), above=int((have & inside & above).sum()),
+                 image=int((have & ~inside).sum()))
+    return dict(nm=nm, match=full, projected=ok.astype(np.uint8), u=np.where(have, u, z), v=np.where(have, v, z), sel=sel, q=q, stats=stats)
+
+
+def check_rig_conditions(oracle, sc):
+    """check_conditions for the rig scene, on the oracle's output alone (M2: th = 7, level_mode 0; M3: th = 10, ORBdist = 100)."""
+    ids, kind = sc["ids"], sc["kind"]
+    have = int((ids >= 0).sum())
+    nl = len(sc["cur"]["kps_left"])
+    r2, r2_free = rig_reference_m2(oracle, sc, 7.0, 0, True), rig_reference_m2(oracle, sc, 7.0, 0, False)
+    r3, r3_free = rig_reference_m3(oracle, sc, 10.0, 100.0, True), rig_reference_m3(oracle, sc, 10.0, 100.0, False)
+    fig = dict(m2_projected=r2["projected"].sum() / have, m2_matched=r2["nm"] / have, m3_projected=r3["projected"].sum() / have,
+               m3_matched=r3["nm"] / have, m2_cleared=r2_free["nm"] - r2["nm"], m3_cleared=r3_free["nm"] - r3["nm"],
+               m2_right=int((r2["match"][nl:] >= 0).sum()), m2_from_right_rows=int((r2["match"] >= sc["n_left_src"]).sum()), **r3["stats"])
+    assert fig["m2_projected"] >= 0.5 and fig["m3_projected"] >= 0.5 and fig["m2_matched"] >= 0.2 and fig["m3_matched"] >= 0.2, fig
+    assert fig["m2_cleared"] >= 1 and fig["m3_cleared"] >= 1 and fig["m2_right"] >= 20 and fig["m2_from_right_rows"] >= 20, fig
+    p2, s2 = rig_gates_m2(oracle, sc)[:2]
+    assert (kind == 1).sum() >= 5 and not p2[kind == 1].any() and fig["behind_kept"] >= 1, fig
+    assert fig["below"] >= 1 and fig["above"] >= 1 and fig["image"] >= 1 and not p2[kind == 2].any(), fig
+    assert not r3["projected"][(kind == 3) | (kind == 4)].any() and p2[(kind == 3) | (kind == 4)].all()
+    assert (kind == 5).sum() >= 4 and p2[kind == 5].all() and not s2[kind == 5].any(), fig
+    assert (r3["match"][nl:] == -1).all()
+    return fig
