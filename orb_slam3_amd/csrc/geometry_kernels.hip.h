@@ -5,6 +5,7 @@
 //                  (CameraModels/KannalaBrandt8.cpp:67-85), with glibc's atan2f restated for the device
 //   k_undistort    cv::undistortPoints as Frame::UndistortKeyPoints (Frame.cc:747-780) calls it [OCV-recalled]: 5 fixed-point
 //                  iterations of the radial-tangential model in double, P = K
+//   rigid_transform .. pinhole_project_invz: the gates every map-point projection kernel shares (here and in matcher_kernels.hip.h), one body each
 // Built with -ffp-contract=off: every operation rounds as the reference text writes it (a reference built against the real Eigen may
 // evaluate mRcw * P with packet FMAs and differ in the last ulp; tolerance stated in DESIGN.md section 5).
 #pragma once
@@ -25,6 +26,55 @@ struct FrustumFrame {   // what Frame::isInFrustum reads of the frame
     float cos_limit;
 };
 
+// ---------------------------------------------------------------------------------------------------------
+// The shared gates of the map-point projection kernels -- k_in_frustum, k_in_frustum_checks, k_kf_project, k_track_project.  Their bit contract
+// ("The projection gates"): every float operation rounds on its own, sums associate left to right as Eigen's unrolled 3-vector
+// products do, logf goes through the double logarithm.  A kernel of the family writes none of these expressions out: it calls them here, so two
+// kernels given the same view and point hold the same bits.  Always inlined, operands by value or through pointers the caller's code already holds.
+// ---------------------------------------------------------------------------------------------------------
+// Pc = R p + t (row-major R): ((R_r0 p0 + R_r1 p1) + R_r2 p2) + t_r
+__device__ __forceinline__ void rigid_transform(const float *R, const float *t, float P0, float P1, float P2, float *Pc) {
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+        Pc[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(R[3 * r], P0), __fmul_rn(R[3 * r + 1], P1)), __fmul_rn(R[3 * r + 2], P2)), t[r]);
+}
+// a . b as Eigen's dot() / squaredNorm() sum it, starting from 0: |Pc|^2, |PO|^2 and PO . Pn
+__device__ __forceinline__ float dot3(float a0, float a1, float a2, float b0, float b1, float b2) {
+    return __fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(a0, b0)), __fmul_rn(a1, b1)), __fmul_rn(a2, b2));
+}
+// dist inside [0.8f mfMinDistance, 1.2f mfMaxDistance], both ends inclusive
+__device__ __forceinline__ bool distance_gate(float dist, float min_dist, float max_dist) {
+    const float maxDistance = __fmul_rn(1.2f, max_dist), minDistance = __fmul_rn(0.8f, min_dist);
+    return !(dist < minDistance || dist > maxDistance);
+}
+// MapPoint::PredictScale (MapPoint.cc:531-546 for a key frame, :548-563 for a frame)
+__device__ __forceinline__ int predict_scale(float max_dist, float dist, float log_scale_factor, int nlevels) {
+    const float ratio = __fdiv_rn(max_dist, dist);
+    // logf through the double logarithm: correctly rounded to float but for double-rounding cases (libm's logf is
+    // within 1 ulp as well); the level changes only if log(ratio)/logScale sits within an ulp of an integer
+    int nScale = (int)ceilf(__fdiv_rn((float)log((double)ratio), log_scale_factor));
+    if (nScale < 0) nScale = 0;
+    else if (nScale >= nlevels) nScale = nlevels - 1;
+    return nScale;
+}
+// Pinhole::project (CameraModels/Pinhole.cpp:43-49): u = fx X / Z + cx
+__device__ __forceinline__ void pinhole_project(float fx, float fy, float cx, float cy, const float *Pc, float *u, float *v) {
+    *u = __fadd_rn(__fdiv_rn(__fmul_rn(fx, Pc[0]), Pc[2]), cx); *v = __fadd_rn(__fdiv_rn(__fmul_rn(fy, Pc[1]), Pc[2]), cy);
+}
+// the pinhole projection as SearchByProjection's vpPointsKFs overload writes it out (ORBmatcher.cc:573-578): invz = 1 / Z, x = X invz, u = fx x + cx
+__device__ __forceinline__ void pinhole_project_invz(float fx, float fy, float cx, float cy, const float *Pc, float *u, float *v) {
+    const float invz = __fdiv_rn(1.0f, Pc[2]);
+    const float x = __fmul_rn(Pc[0], invz), y = __fmul_rn(Pc[1], invz);
+    *u = __fadd_rn(__fmul_rn(fx, x), cx); *v = __fadd_rn(__fmul_rn(fy, y), cy);
+}
+
+// Frame::isInFrustum (Frame.cc:512-575), the gates in the reference's order through the helpers above:
+//   Pc = Rcw p + tcw; Pc_dist = |Pc|; invz = 1 / z; reject z < 0.0f
+//   Pinhole::project; reject u < mnMinX || u > mnMaxX, likewise v  (both sides inclusive); mTrackProjX/Y = (u, v) from here on
+//   dist = |p - Ow|; reject outside [0.8f mfMinDistance, 1.2f mfMaxDistance]
+//   viewCos = PO . Pn / dist; reject viewCos < viewingCosLimit
+//   PredictScale(dist, this); ur = u - mbf invz
+// A rejected point keeps the projection -1 (once the bounds test has passed: (u, v)) and level 0.
 // grid (ceil(n_mp / 256), n_frames), block 256.  Map-point data are shared by all frames; outputs are [n_frames][n_mp].
 static __global__ __launch_bounds__(256) void k_in_frustum(const FrustumFrame *__restrict__ frames, int n_mp, const float *__restrict__ pos,
                                                     const float *__restrict__ normal, const float *__restrict__ min_dist,
@@ -43,30 +93,22 @@ static __global__ __launch_bounds__(256) void k_in_frustum(const FrustumFrame *_
     // link when the call runs in the matcher context's direct mode)
     const float mn_in = min_dist[i], mx = max_dist[i], N0 = normal[3 * i], N1 = normal[3 * i + 1], N2 = normal[3 * i + 2];
     float Pc[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-        Pc[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(F.Rcw[3 * r], P0), __fmul_rn(F.Rcw[3 * r + 1], P1)), __fmul_rn(F.Rcw[3 * r + 2], P2)), F.tcw[r]);
-    const float Pc_dist = sqrtf(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(Pc[0], Pc[0])), __fmul_rn(Pc[1], Pc[1])), __fmul_rn(Pc[2], Pc[2])));
+    rigid_transform(F.Rcw, F.tcw, P0, P1, P2, Pc);
+    const float Pc_dist = sqrtf(dot3(Pc[0], Pc[1], Pc[2], Pc[0], Pc[1], Pc[2]));
     const float invz = __fdiv_rn(1.0f, Pc[2]);
     if (!(Pc[2] < 0.0f)) {
-        const float u = __fadd_rn(__fdiv_rn(__fmul_rn(F.fx, Pc[0]), Pc[2]), F.cx), v = __fadd_rn(__fdiv_rn(__fmul_rn(F.fy, Pc[1]), Pc[2]), F.cy);
+        float u, v;
+        pinhole_project(F.fx, F.fy, F.cx, F.cy, Pc, &u, &v);
         if (!(u < F.minx || u > F.maxx) && !(v < F.miny || v > F.maxy)) {
             px = u; py = v;
             const float PO0 = __fsub_rn(P0, F.Ow[0]), PO1 = __fsub_rn(P1, F.Ow[1]), PO2 = __fsub_rn(P2, F.Ow[2]);
-            const float dist = sqrtf(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, PO0)), __fmul_rn(PO1, PO1)), __fmul_rn(PO2, PO2)));
-            const float maxDistance = __fmul_rn(1.2f, mx), minDistance = __fmul_rn(0.8f, mn_in);
-            if (!(dist < minDistance || dist > maxDistance)) {
-                const float viewCos = __fdiv_rn(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, N0)), __fmul_rn(PO1, N1)), __fmul_rn(PO2, N2)), dist);
+            const float dist = sqrtf(dot3(PO0, PO1, PO2, PO0, PO1, PO2));
+            if (distance_gate(dist, mn_in, mx)) {
+                const float viewCos = __fdiv_rn(dot3(PO0, PO1, PO2, N0, N1, N2), dist);
                 if (!(viewCos < F.cos_limit)) {
-                    const float ratio = __fdiv_rn(mx, dist);
-                    // logf through the double logarithm: correctly rounded to float but for double-rounding cases (libm's logf is
-                    // within 1 ulp as well); the level changes only if log(ratio)/logScale sits within an ulp of an integer
-                    int nScale = (int)ceilf(__fdiv_rn((float)log((double)ratio), F.log_scale_factor));
-                    if (nScale < 0) nScale = 0;
-                    else if (nScale >= F.nlevels) nScale = F.nlevels - 1;
                     iv = 1;
                     pxr = __fsub_rn(u, __fmul_rn(F.mbf, invz));
-                    dep = Pc_dist; lvl = nScale; vc = viewCos;
+                    dep = Pc_dist; lvl = predict_scale(mx, dist, F.log_scale_factor, F.nlevels); vc = viewCos;
                 }
             }
         }
@@ -375,6 +417,13 @@ __host__ __device__ inline bool kb8_epipolar_constrain(const float *cam1, const 
     return kb8_triangulate_matches(cam1, cam2, x1, y1, x2, y2, R12, t12, sigmaLevel, unc).value > 0.0001f;
 }
 
+// Frame::isInFrustumChecks (Frame.cc:1168-1240), the gates in the reference's order through the shared helpers:
+//   Pc = R p + t; Pc_dist = |Pc|; reject z < 0.0f
+//   KannalaBrandt8::project; reject u < mnMinX || u > mnMaxX, likewise v  (both sides inclusive)
+//   dist = |p - twc|; reject outside [0.8f mfMinDistance, 1.2f mfMaxDistance]
+//   viewCos = PO . Pn / dist; reject viewCos < viewingCosLimit
+//   PredictScale(dist, this)
+// A rejected point has projection 0 and level -1: k_in_frustum's defaults the other way round, which is why the two stay two kernels.
 // grid (ceil(n_mp / 256), n_views), block 256.  Outputs [n_views][n_mp]: the MapPoint fields the function writes when every test passes
 // (mTrackProjX/Y[R], mnTrackScaleLevel[R], mTrackViewCos[R], mTrackDepth[R]); otherwise in_view = 0, level = -1 (Frame.cc:579-580) and zeros.
 static __global__ __launch_bounds__(256) void k_in_frustum_checks(const FrustumChecks *__restrict__ fc, int n_mp, const float *__restrict__ pos,
@@ -393,25 +442,18 @@ static __global__ __launch_bounds__(256) void k_in_frustum_checks(const FrustumC
     float px = 0.f, py = 0.f, dep = 0.f, vc = 0.f;
     int lvl = -1;
     float Pc[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-        Pc[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(V.R[3 * r], P0), __fmul_rn(V.R[3 * r + 1], P1)), __fmul_rn(V.R[3 * r + 2], P2)), V.t[r]);
-    const float Pc_dist = sqrtf(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(Pc[0], Pc[0])), __fmul_rn(Pc[1], Pc[1])), __fmul_rn(Pc[2], Pc[2])));
+    rigid_transform(V.R, V.t, P0, P1, P2, Pc);
+    const float Pc_dist = sqrtf(dot3(Pc[0], Pc[1], Pc[2], Pc[0], Pc[1], Pc[2]));
     if (!(Pc[2] < 0.0f)) {
         float u, v;
         kb8_project(V.p, Pc[0], Pc[1], Pc[2], &u, &v);
         if (!(u < F.minx || u > F.maxx) && !(v < F.miny || v > F.maxy)) {
             const float PO0 = __fsub_rn(P0, V.twc[0]), PO1 = __fsub_rn(P1, V.twc[1]), PO2 = __fsub_rn(P2, V.twc[2]);
-            const float dist = sqrtf(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, PO0)), __fmul_rn(PO1, PO1)), __fmul_rn(PO2, PO2)));
-            const float maxDistance = __fmul_rn(1.2f, mx), minDistance = __fmul_rn(0.8f, mn_in);
-            if (!(dist < minDistance || dist > maxDistance)) {
-                const float viewCos = __fdiv_rn(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, N0)), __fmul_rn(PO1, N1)), __fmul_rn(PO2, N2)), dist);
+            const float dist = sqrtf(dot3(PO0, PO1, PO2, PO0, PO1, PO2));
+            if (distance_gate(dist, mn_in, mx)) {
+                const float viewCos = __fdiv_rn(dot3(PO0, PO1, PO2, N0, N1, N2), dist);
                 if (!(viewCos < F.cos_limit)) {
-                    const float ratio = __fdiv_rn(mx, dist);
-                    int nScale = (int)ceilf(__fdiv_rn((float)log((double)ratio), F.log_scale_factor));   // as k_in_frustum
-                    if (nScale < 0) nScale = 0;
-                    else if (nScale >= F.nlevels) nScale = F.nlevels - 1;
-                    iv = 1; px = u; py = v; dep = Pc_dist; lvl = nScale; vc = viewCos;
+                    iv = 1; px = u; py = v; dep = Pc_dist; lvl = predict_scale(mx, dist, F.log_scale_factor, F.nlevels); vc = viewCos;
                 }
             }
         }

@@ -1556,130 +1556,90 @@ __global__ __launch_bounds__(256) void k_window_best1_kf(const KfProblem *__rest
     if (qvalid && sl == 0) gst(P.keys + qi, m);
 }
 
-// k_fuse_project: the projection half of ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint*> &vpMapPoints, th) (ORBmatcher.cc:1186-1244) for every
-// (key frame, map point) of LocalMapping::SearchInNeighbors' Fuse loop -- a lane per pair writes the query record of problem k straight into the arrays
-// k_window_best1_kf reads (qvalid switches a rejected pair off; the descriptors are the one shared array).  The gates in the reference's order, every float
-// operation rounded separately and summed in the order k_in_frustum fixes for the same expressions:
-//   p3Dc = Rcw p + tcw; reject p3Dc.z < 0.0f; invz = 1 / z
-//   Pinhole::project; KeyFrame::IsInImage: x >= mnMinX && x < mnMaxX && y >= mnMinY && y < mnMaxY  (strict on the max side)
-//   ur = u - bf invz
+// k_kf_project: the projection half of the matcher members that project map points into KEY FRAMES -- a lane per (problem, map point) writes the
+// query record of problem p straight into the arrays the search kernels read (qvalid switches a rejected pair off; query index = map-point index; the
+// descriptors are the one shared array).  The records never visit the host.
+//   SIM3 = false: ORBmatcher::Fuse(pKF, vpMapPoints, th, bRight) (ORBmatcher.cc:1186-1244) for LocalMapping::SearchInNeighbors' Fuse loop.
+//   SIM3 = true:  LoopClosing's three Sim3 calls -- SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (:452-487), its vpPointsKFs
+//                 overload (:569-604) and Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:1369-1399).  The view is SE3f(Scw.rotationMatrix(),
+//                 Scw.translation() / Scw.scale()) and its camera centre, evaluated by the caller.
+//   KB8 = false:  a monocular / rectified key frame: cams[k], poses[k], one problem per key frame.
+//   KB8 = true:   a fisheye-stereo rig key frame (KeyFrame::NLeft != -1): views[p] = R, t, twc and the KannalaBrandt8 parameters of problem p's camera.
+//                 Fuse has two problems per key frame, p = 2 k + camera (GetPose() / GetRightPose(), mpCamera / mpCamera2); the Sim3 members never
+//                 look at the right camera (GetFeaturesInArea with bRight = false, mvKeysUn[idx], mpCamera): one problem per key frame, its left side.
+// The gates in the reference's order, through the shared helpers of geometry_kernels.hip.h (their bit contract: DESIGN.md section 5):
+//   reject skip (Fuse: !pMP || isBad() || IsInKeyFrame(pKF); Sim3: isBad() || spAlreadyFound.count(pMP)); p3Dc = R p + t; reject p3Dc.z < 0.0f
+//   the projection: Pinhole::project, or KannalaBrandt8::project (kb8_project: the bit contract and the one-ulp caveat of orbx_is_in_frustum_checks),
+//     evaluated only for pairs that are neither skipped nor behind the camera ((0, 0) is written for the others); SIM3 with ORBX_SIM3_PROJECT_INVZ:
+//     the vpPointsKFs overload's written-out pinhole form (:573-578) with fx, fy, cx, cy -- of a rig views[p].p[0..3], where the caller puts
+//     pKF->fx, fy, cx, cy: the reference writes that form whatever the camera model is
+//   KeyFrame::IsInImage: x >= mnMinX && x < mnMaxX && y >= mnMinY && y < mnMaxY  (strict on the max side)
+//   !KB8 && !SIM3: ur = u - bf invz, invz = 1 / z (no other member reads mvuRight; a rig key frame has none)
 //   dist3D = |p - Ow|; reject outside [0.8f mfMinDistance, 1.2f mfMaxDistance]
 //   reject PO . Pn < 0.5 * dist3D, compared in double and WITHOUT isInFrustum's division
-//   PredictScale(dist3D, pKF); radius = th * mvScaleFactors[level]; levels [level - 1, level]
-// skip [n_kf][n_mp] (may be NULL) = !pMP || isBad() || IsInKeyFrame(pKF_k).  Streaming work: no LDS, no scratch.
-// grid (ceil(n_mp / 256), n_kf), block 256
-__global__ __launch_bounds__(256) void k_fuse_project(const KfProblem *__restrict__ recs, const orbx_camera *__restrict__ cams,
-                                                      const orbx_frame_pose *__restrict__ poses, float th, float log_scale_factor, int n_mp,
-                                                      const float *__restrict__ pos, const float *__restrict__ normal, const float *__restrict__ min_dist,
-                                                      const float *__restrict__ max_dist, const uint8_t *__restrict__ skip, float *__restrict__ qx,
-                                                      float *__restrict__ qy, float *__restrict__ qxr, float *__restrict__ qr, int32_t *__restrict__ qmin,
-                                                      int32_t *__restrict__ qmax, uint8_t *__restrict__ qvalid) {
+//   PredictScale(dist3D, pKF) (MapPoint.cc:531-546); radius = th * mvScaleFactors[level]; levels [level - 1, level]
+//     (kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel; the Sim3 members: :504-507, :1411-1414)
+// Every output of every pair is written, rejected pairs included: (u, v) as far as it was evaluated, radius 0, level 0.  Streaming work: no LDS, no
+// scratch.  grid (ceil(n_mp / 256), n_kf * sides), block 256
+struct KfProject {
+    const KfProblem *recs;                                     // [n_kf * sides]: bounds, levels and scale factors of problem p
+    const orbx_camera *cams; const orbx_frame_pose *poses;     // !KB8: [n_kf]
+    const FisheyeView *views;                                  // KB8: [n_kf * sides]
+    float th, log_scale_factor;
+    int projection_form;                                       // SIM3: ORBX_SIM3_PROJECT_CAMERA / _INVZ
+    int n_mp, sides;                                           // problems per key frame: the skip row of problem p is p / sides
+    const float *pos, *normal, *min_dist, *max_dist;           // [n_mp]
+    const uint8_t *skip;                                       // [n_kf][n_mp], may be NULL
+    float *qx, *qy, *qxr, *qr;                                 // [n_kf * sides][n_mp]; qxr: !KB8 && !SIM3 only
+    int32_t *qmin, *qmax;
+    uint8_t *qvalid;
+};
+template <bool KB8, bool SIM3>
+__global__ __launch_bounds__(256) void k_kf_project(const KfProject K) {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_mp) return;
-    const int k = blockIdx.y;
-    const size_t o = (size_t)k * n_mp + i;
-    const orbx_frame_pose T = poses[k];
-    const float fx = cams[k].fx, fy = cams[k].fy, cx = cams[k].cx, cy = cams[k].cy, bf = cams[k].bf;
-    const float minx = recs[k].g.minx, miny = recs[k].g.miny, maxx = recs[k].maxx, maxy = recs[k].maxy;
-    const int nlevels = recs[k].nlevels;
-    const float *scale = recs[k].P.scale;
+    if (i >= K.n_mp) return;
+    const int p = blockIdx.y;
+    const size_t o = (size_t)p * K.n_mp + i;
+    const float *R, *t, *C, *kb8 = nullptr;
+    float fx, fy, cx, cy, bf = 0.f;
+    if (KB8) {
+        const FisheyeView &V = K.views[p];
+        R = V.R; t = V.t; C = V.twc; kb8 = V.p;
+        fx = V.p[0]; fy = V.p[1]; cx = V.p[2]; cy = V.p[3];
+    } else {
+        const orbx_frame_pose &T = K.poses[p];
+        R = T.Rcw; t = T.tcw; C = T.Ow;
+        fx = K.cams[p].fx; fy = K.cams[p].fy; cx = K.cams[p].cx; cy = K.cams[p].cy; bf = K.cams[p].bf;
+    }
+    const float minx = K.recs[p].g.minx, miny = K.recs[p].g.miny, maxx = K.recs[p].maxx, maxy = K.recs[p].maxy;
+    const int nlevels = K.recs[p].nlevels;
+    const float *scale = K.recs[p].P.scale;
     // every input of the pair requested at once (the gates read them conditionally: each would be a dependent round trip)
-    const uint8_t sk = skip ? skip[o] : (uint8_t)0;
-    const float P0 = pos[3 * i], P1 = pos[3 * i + 1], P2 = pos[3 * i + 2];
-    const float mn_in = min_dist[i], mx = max_dist[i], N0 = normal[3 * i], N1 = normal[3 * i + 1], N2 = normal[3 * i + 2];
+    const uint8_t sk = K.skip ? K.skip[(size_t)(p / K.sides) * K.n_mp + i] : (uint8_t)0;
+    const float P0 = K.pos[3 * i], P1 = K.pos[3 * i + 1], P2 = K.pos[3 * i + 2];
+    const float mn_in = K.min_dist[i], mx = K.max_dist[i], N0 = K.normal[3 * i], N1 = K.normal[3 * i + 1], N2 = K.normal[3 * i + 2];
     float Pc[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-        Pc[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T.Rcw[3 * r], P0), __fmul_rn(T.Rcw[3 * r + 1], P1)), __fmul_rn(T.Rcw[3 * r + 2], P2)), T.tcw[r]);
+    rigid_transform(R, t, P0, P1, P2, Pc);
     bool ok = !sk && !(Pc[2] < 0.0f);
-    const float invz = __fdiv_rn(1.0f, Pc[2]);
-    const float u = __fadd_rn(__fdiv_rn(__fmul_rn(fx, Pc[0]), Pc[2]), cx), v = __fadd_rn(__fdiv_rn(__fmul_rn(fy, Pc[1]), Pc[2]), cy);
+    float u = 0.f, v = 0.f;
+    if (SIM3 && K.projection_form == ORBX_SIM3_PROJECT_INVZ) pinhole_project_invz(fx, fy, cx, cy, Pc, &u, &v);
+    else if (!KB8) pinhole_project(fx, fy, cx, cy, Pc, &u, &v);
+    else if (ok) kb8_project(kb8, Pc[0], Pc[1], Pc[2], &u, &v);
     ok = ok && (u >= minx && u < maxx && v >= miny && v < maxy);
-    const float ur = __fsub_rn(u, __fmul_rn(bf, invz));
-    const float PO0 = __fsub_rn(P0, T.Ow[0]), PO1 = __fsub_rn(P1, T.Ow[1]), PO2 = __fsub_rn(P2, T.Ow[2]);
-    const float dist = sqrtf(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, PO0)), __fmul_rn(PO1, PO1)), __fmul_rn(PO2, PO2)));
-    const float maxDistance = __fmul_rn(1.2f, mx), minDistance = __fmul_rn(0.8f, mn_in);
-    ok = ok && !(dist < minDistance || dist > maxDistance);
-    const float dot = __fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, N0)), __fmul_rn(PO1, N1)), __fmul_rn(PO2, N2));
-    ok = ok && !((double)dot < 0.5 * (double)dist);
+    const float PO0 = __fsub_rn(P0, C[0]), PO1 = __fsub_rn(P1, C[1]), PO2 = __fsub_rn(P2, C[2]);
+    const float dist = sqrtf(dot3(PO0, PO1, PO2, PO0, PO1, PO2));
+    ok = ok && distance_gate(dist, mn_in, mx);
+    ok = ok && !((double)dot3(PO0, PO1, PO2, N0, N1, N2) < 0.5 * (double)dist);
     int lvl = 0;
     float radius = 0.f;
-    if (ok) {   // MapPoint::PredictScale(dist3D, pKF) (MapPoint.cc:531-546), as k_in_frustum evaluates the same expressions
-        const float ratio = __fdiv_rn(mx, dist);
-        lvl = (int)ceilf(__fdiv_rn((float)log((double)ratio), log_scale_factor));
-        if (lvl < 0) lvl = 0;
-        else if (lvl >= nlevels) lvl = nlevels - 1;
-        radius = __fmul_rn(th, gld(scale + lvl));
+    if (ok) {
+        lvl = predict_scale(mx, dist, K.log_scale_factor, nlevels);
+        radius = __fmul_rn(K.th, gld(scale + lvl));
     }
-    qx[o] = u; qy[o] = v; qxr[o] = ur; qr[o] = radius;
-    qmin[o] = lvl - 1; qmax[o] = lvl;   // kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel
-    qvalid[o] = ok ? 1 : 0;
-}
-
-// k_sim3_project: the projection half shared by LoopClosing's three Sim3 matcher calls -- SearchByProjection(pKF, Scw, vpPoints, vpMatched, th,
-// ratioHamming) (ORBmatcher.cc:452-487), its vpPointsKFs overload (:569-604) and Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:1369-1399) -- for every
-// (key frame, map point) of one call: a lane per pair writes the query record of problem k where the search kernels read it (qvalid switches a rejected
-// pair off: query index = map-point index).  poses[k] = SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()) and its camera centre, evaluated by
-// the caller.  The gates in the reference's order, every float operation rounded separately, sums in k_fuse_project's order:
-//   reject skip (isBad() || spAlreadyFound.count(pMP)); p3Dc = Rcw p + tcw; reject p3Dc.z < 0
-//   ORBX_SIM3_PROJECT_CAMERA: Pinhole::project, u = fx X / Z + cx;  ORBX_SIM3_PROJECT_INVZ: invz = 1 / Z, x = X invz, y = Y invz, u = fx x + cx (:573-578)
-//   KeyFrame::IsInImage (strict on the max side)
-//   dist = |p - Ow|; reject outside [0.8f mfMinDistance, 1.2f mfMaxDistance]
-//   reject PO . Pn < 0.5 * dist, compared in double and without a division
-//   PredictScale(dist, pKF) as k_fuse_project evaluates it; radius = th * mvScaleFactors[level]; levels [level - 1, level]
-// No ur (no bf is read): these searches never look at mvuRight.  Streaming work: no LDS, no scratch.  grid (ceil(n_mp / 256), n_kf), block 256
-__global__ __launch_bounds__(256) void k_sim3_project(const KfProblem *__restrict__ recs, const orbx_camera *__restrict__ cams,
-                                                      const orbx_frame_pose *__restrict__ poses, float th, float log_scale_factor, int projection_form,
-                                                      int n_mp, const float *__restrict__ pos, const float *__restrict__ normal,
-                                                      const float *__restrict__ min_dist, const float *__restrict__ max_dist,
-                                                      const uint8_t *__restrict__ skip, float *__restrict__ qx, float *__restrict__ qy,
-                                                      float *__restrict__ qr, int32_t *__restrict__ qmin, int32_t *__restrict__ qmax,
-                                                      uint8_t *__restrict__ qvalid) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_mp) return;
-    const int k = blockIdx.y;
-    const size_t o = (size_t)k * n_mp + i;
-    const orbx_frame_pose T = poses[k];
-    const float fx = cams[k].fx, fy = cams[k].fy, cx = cams[k].cx, cy = cams[k].cy;
-    const float minx = recs[k].g.minx, miny = recs[k].g.miny, maxx = recs[k].maxx, maxy = recs[k].maxy;
-    const int nlevels = recs[k].nlevels;
-    const float *scale = recs[k].P.scale;
-    // every input of the pair requested at once (the gates read them conditionally: each would be a dependent round trip)
-    const uint8_t sk = skip ? skip[o] : (uint8_t)0;
-    const float P0 = pos[3 * i], P1 = pos[3 * i + 1], P2 = pos[3 * i + 2];
-    const float mn_in = min_dist[i], mx = max_dist[i], N0 = normal[3 * i], N1 = normal[3 * i + 1], N2 = normal[3 * i + 2];
-    float Pc[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-        Pc[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T.Rcw[3 * r], P0), __fmul_rn(T.Rcw[3 * r + 1], P1)), __fmul_rn(T.Rcw[3 * r + 2], P2)), T.tcw[r]);
-    bool ok = !sk && !(Pc[2] < 0.0f);
-    float u, v;
-    if (projection_form == ORBX_SIM3_PROJECT_INVZ) {   // the vpPointsKFs overload writes the pinhole projection out (:573-578)
-        const float invz = __fdiv_rn(1.0f, Pc[2]);
-        const float x = __fmul_rn(Pc[0], invz), y = __fmul_rn(Pc[1], invz);
-        u = __fadd_rn(__fmul_rn(fx, x), cx); v = __fadd_rn(__fmul_rn(fy, y), cy);
-    } else {                                           // pKF->mpCamera->project(p3Dc): Pinhole::project
-        u = __fadd_rn(__fdiv_rn(__fmul_rn(fx, Pc[0]), Pc[2]), cx); v = __fadd_rn(__fdiv_rn(__fmul_rn(fy, Pc[1]), Pc[2]), cy);
-    }
-    ok = ok && (u >= minx && u < maxx && v >= miny && v < maxy);
-    const float PO0 = __fsub_rn(P0, T.Ow[0]), PO1 = __fsub_rn(P1, T.Ow[1]), PO2 = __fsub_rn(P2, T.Ow[2]);
-    const float dist = sqrtf(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, PO0)), __fmul_rn(PO1, PO1)), __fmul_rn(PO2, PO2)));
-    const float maxDistance = __fmul_rn(1.2f, mx), minDistance = __fmul_rn(0.8f, mn_in);
-    ok = ok && !(dist < minDistance || dist > maxDistance);
-    const float dot = __fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, N0)), __fmul_rn(PO1, N1)), __fmul_rn(PO2, N2));
-    ok = ok && !((double)dot < 0.5 * (double)dist);
-    int lvl = 0;
-    float radius = 0.f;
-    if (ok) {   // MapPoint::PredictScale(dist, pKF) (MapPoint.cc:531-546), as k_fuse_project evaluates it
-        const float ratio = __fdiv_rn(mx, dist);
-        lvl = (int)ceilf(__fdiv_rn((float)log((double)ratio), log_scale_factor));
-        if (lvl < 0) lvl = 0;
-        else if (lvl >= nlevels) lvl = nlevels - 1;
-        radius = __fmul_rn(th, gld(scale + lvl));
-    }
-    qx[o] = u; qy[o] = v; qr[o] = radius;
-    qmin[o] = lvl - 1; qmax[o] = lvl;   // kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel (:504-507, :1411-1414)
-    qvalid[o] = ok ? 1 : 0;
+    K.qx[o] = u; K.qy[o] = v; K.qr[o] = radius;
+    if (!KB8 && !SIM3) K.qxr[o] = __fsub_rn(u, __fmul_rn(bf, __fdiv_rn(1.0f, Pc[2])));
+    K.qmin[o] = lvl - 1; K.qmax[o] = lvl;
+    K.qvalid[o] = ok ? 1 : 0;
 }
 
 // k_track_project: the projection half of the Tracking thread's two searches that take their queries from another frame's map points --
@@ -1689,13 +1649,13 @@ __global__ __launch_bounds__(256) void k_sim3_project(const KfProblem *__restric
 // feature i reads ids[i] (the slot of mvpMapPoints[i], -1: none), the source row's octave and angle and the 64-byte record of the slot, and writes
 // the query record where k_window_best2_t and the replay read it (qvalid switches a rejected entry off: query index = source feature index).  No
 // k_map_gather launch, no flat map-point arrays.  Entries at or beyond the source's count (read on the device) are off.  The gates in the host
-// adapters' order, every float operation rounded separately, sums in k_fuse_project's order:
+// adapters' order, through the shared helpers of geometry_kernels.hip.h (their bit contract: DESIGN.md section 5):
 //   x3Dc = Rcw p + tcw
 //   RELOC = false: invzc = 1 / z; reject invzc < 0
 //   Pinhole::project; reject u < mnMinX || u > mnMaxX, likewise v  (BOTH sides inclusive, unlike KeyFrame::IsInImage)
 //   RELOC = false: ur = u - bf invzc; r = th * scale[octave], on iff 0 <= octave < nlevels; levels by level_mode (ORBmatcher.cc:1726-1735)
-//   RELOC = true:  dist3D = |p - Ow|; reject outside [0.8f mfMinDistance, 1.2f mfMaxDistance]; PredictScale(dist3D, &CurrentFrame) as
-//                  k_fuse_project evaluates it; r = th * scale[level]; levels [level - 1, level + 1]
+//   RELOC = true:  dist3D = |p - Ow|; reject outside [0.8f mfMinDistance, 1.2f mfMaxDistance]; PredictScale(dist3D, &CurrentFrame);
+//                  r = th * scale[level]; levels [level - 1, level + 1]
 // projected[i] = the entry passed the geometric gates (qvalid also needs the octave of RELOC = false in range); qx / qy hold (u, v) of every entry with
 // a point.  Streaming work: no LDS, no scratch.  No address is formed from an id that is not below `cap`.  grid (ceil(n_ids / 256)), block 256
 struct TrackProject {
@@ -1744,9 +1704,7 @@ __global__ __launch_bounds__(256) void k_track_project(const TrackProject T) {
     const float mn_in = __uint_as_float(q1.z), mx = __uint_as_float(q1.w);
     const orbx_frame_pose &S = T.pose;
     float Pc[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-        Pc[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(S.Rcw[3 * r], P0), __fmul_rn(S.Rcw[3 * r + 1], P1)), __fmul_rn(S.Rcw[3 * r + 2], P2)), S.tcw[r]);
+    rigid_transform(S.Rcw, S.tcw, P0, P1, P2, Pc);
     const float invz = __fdiv_rn(1.0f, Pc[2]);
     bool ok = have && (RELOC || !(invz < 0.f));
     float u, v, xr = 0.f, yr = 0.f;
@@ -1754,13 +1712,11 @@ __global__ __launch_bounds__(256) void k_track_project(const TrackProject T) {
         kb8_project(T.kb8, Pc[0], Pc[1], Pc[2], &u, &v);
         if (!RELOC) {
             float Pr[3];
-#pragma unroll
-            for (int r = 0; r < 3; r++)
-                Pr[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(T.Trl_R[3 * r], Pc[0]), __fmul_rn(T.Trl_R[3 * r + 1], Pc[1])), __fmul_rn(T.Trl_R[3 * r + 2], Pc[2])), T.Trl_t[r]);
+            rigid_transform(T.Trl_R, T.Trl_t, Pc[0], Pc[1], Pc[2], Pr);
             kb8_project(T.kb8, Pr[0], Pr[1], Pr[2], &xr, &yr);
         }
     } else {
-        u = __fadd_rn(__fdiv_rn(__fmul_rn(T.fx, Pc[0]), Pc[2]), T.cx); v = __fadd_rn(__fdiv_rn(__fmul_rn(T.fy, Pc[1]), Pc[2]), T.cy);
+        pinhole_project(T.fx, T.fy, T.cx, T.cy, Pc, &u, &v);
         xr = __fsub_rn(u, __fmul_rn(T.bf, invz));
     }
     ok = ok && !(u < T.minx || u > T.maxx) && !(v < T.miny || v > T.maxy);
@@ -1768,17 +1724,11 @@ __global__ __launch_bounds__(256) void k_track_project(const TrackProject T) {
     bool on = ok;
     if (RELOC) {
         const float PO0 = __fsub_rn(P0, S.Ow[0]), PO1 = __fsub_rn(P1, S.Ow[1]), PO2 = __fsub_rn(P2, S.Ow[2]);
-        const float dist = sqrtf(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, PO0)), __fmul_rn(PO1, PO1)), __fmul_rn(PO2, PO2)));
-        const float maxDistance = __fmul_rn(1.2f, mx), minDistance = __fmul_rn(0.8f, mn_in);
-        ok = ok && !(dist < minDistance || dist > maxDistance);
+        const float dist = sqrtf(dot3(PO0, PO1, PO2, PO0, PO1, PO2));
+        ok = ok && distance_gate(dist, mn_in, mx);
         on = ok;
         lvl = 0;
-        if (ok) {   // MapPoint::PredictScale(dist3D, &CurrentFrame) (MapPoint.cc:548-563), as k_fuse_project evaluates it
-            const float ratio = __fdiv_rn(mx, dist);
-            lvl = (int)ceilf(__fdiv_rn((float)log((double)ratio), T.log_scale_factor));
-            if (lvl < 0) lvl = 0;
-            else if (lvl >= T.nlevels) lvl = T.nlevels - 1;
-        }
+        if (ok) lvl = predict_scale(mx, dist, T.log_scale_factor, T.nlevels);   // MapPoint::PredictScale(dist3D, &CurrentFrame) (MapPoint.cc:548-563)
         lo = lvl - 1; hi = lvl + 1;   // :1942
     } else {
         lvl = octave;
@@ -1852,131 +1802,7 @@ __global__ __launch_bounds__(64) void k_keyframe_copy(const KeyFrameCopy F) {
 // roff the host knows, a grid per camera with side-local indices (as the fisheye frame handle).  A key frame is TWO problems of k_window_best1_kf:
 // (mvKeys, left grid, rows [0, N_left)) and (mvKeysRight, right grid, rows [N_left, N)).
 // ---------------------------------------------------------------------------------------------------------
-// k_fuse_project_kb8: k_fuse_project with the rig's camera -- the projection half of Fuse(pKF, vpMapPoints, th, bRight) (ORBmatcher.cc:1186-1244) for
-// every (key frame, camera, map point); problem p = 2 k + camera has its own view (GetPose() / GetRightPose(), the camera centre, mpCamera / mpCamera2's
-// parameters).  The gates in the reference's order, sums in k_fuse_project's order:
-//   p3Dc = R p + t; reject p3Dc.z < 0.0f
-//   KannalaBrandt8::project (kb8_project, as k_in_frustum_checks calls it); KeyFrame::IsInImage, strict on the max side
-//   dist3D = |p - twc|; reject outside [0.8f mfMinDistance, 1.2f mfMaxDistance]
-//   reject PO . Pn < 0.5 * dist3D, compared in double and without a division
-//   PredictScale(dist3D, pKF); radius = th * mvScaleFactors[level]; levels [level - 1, level]
-// There is no mvuRight on a rig key frame: no right-coordinate prediction is written.  skip [n_kf][n_mp] (may be NULL): one row per key frame, read by
-// both cameras.  Outputs [n_kf][2][n_mp].  Streaming work: no LDS.
-// grid (ceil(n_mp / 256), 2 n_kf), block 256
-__global__ __launch_bounds__(256) void k_fuse_project_kb8(const KfProblem *__restrict__ recs, const FisheyeView *__restrict__ views, float th,
-                                                          float log_scale_factor, int n_mp, const float *__restrict__ pos,
-                                                          const float *__restrict__ normal, const float *__restrict__ min_dist,
-                                                          const float *__restrict__ max_dist, const uint8_t *__restrict__ skip, float *__restrict__ qx,
-                                                          float *__restrict__ qy, float *__restrict__ qr, int32_t *__restrict__ qmin,
-                                                          int32_t *__restrict__ qmax, uint8_t *__restrict__ qvalid) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_mp) return;
-    const int p = blockIdx.y;
-    const size_t o = (size_t)p * n_mp + i;
-    const FisheyeView &V = views[p];
-    const float minx = recs[p].g.minx, miny = recs[p].g.miny, maxx = recs[p].maxx, maxy = recs[p].maxy;
-    const int nlevels = recs[p].nlevels;
-    const float *scale = recs[p].P.scale;
-    // every input of the pair requested at once (the gates read them conditionally: each would be a dependent round trip)
-    const uint8_t sk = skip ? skip[(size_t)(p >> 1) * n_mp + i] : (uint8_t)0;
-    const float P0 = pos[3 * i], P1 = pos[3 * i + 1], P2 = pos[3 * i + 2];
-    const float mn_in = min_dist[i], mx = max_dist[i], N0 = normal[3 * i], N1 = normal[3 * i + 1], N2 = normal[3 * i + 2];
-    float Pc[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-        Pc[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(V.R[3 * r], P0), __fmul_rn(V.R[3 * r + 1], P1)), __fmul_rn(V.R[3 * r + 2], P2)), V.t[r]);
-    float u = 0.f, v = 0.f, radius = 0.f;
-    int lvl = 0;
-    bool ok = false;
-    if (!sk && !(Pc[2] < 0.0f)) {
-        kb8_project(V.p, Pc[0], Pc[1], Pc[2], &u, &v);
-        if (u >= minx && u < maxx && v >= miny && v < maxy) {
-            const float PO0 = __fsub_rn(P0, V.twc[0]), PO1 = __fsub_rn(P1, V.twc[1]), PO2 = __fsub_rn(P2, V.twc[2]);
-            const float dist = sqrtf(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, PO0)), __fmul_rn(PO1, PO1)), __fmul_rn(PO2, PO2)));
-            const float maxDistance = __fmul_rn(1.2f, mx), minDistance = __fmul_rn(0.8f, mn_in);
-            const float dot = __fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, N0)), __fmul_rn(PO1, N1)), __fmul_rn(PO2, N2));
-            if (!(dist < minDistance || dist > maxDistance) && !((double)dot < 0.5 * (double)dist)) {
-                // MapPoint::PredictScale(dist3D, pKF) (MapPoint.cc:531-546), as k_fuse_project evaluates it
-                const float ratio = __fdiv_rn(mx, dist);
-                lvl = (int)ceilf(__fdiv_rn((float)log((double)ratio), log_scale_factor));
-                if (lvl < 0) lvl = 0;
-                else if (lvl >= nlevels) lvl = nlevels - 1;
-                radius = __fmul_rn(th, gld(scale + lvl));
-                ok = true;
-            }
-        }
-    }
-    qx[o] = u; qy[o] = v; qr[o] = radius;
-    qmin[o] = lvl - 1; qmax[o] = lvl;   // kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel
-    qvalid[o] = ok ? 1 : 0;
-}
-
-// k_sim3_project_kb8: k_sim3_project with the rig's camera -- the projection half of LoopClosing's three Sim3 matcher calls (ORBmatcher.cc:452-487,
-// :569-604, :1369-1399) on a fisheye-stereo key frame.  Those members never look at the right camera (GetFeaturesInArea with bRight = false,
-// mvKeysUn[idx], mpCamera): ONE problem per key frame -- its left rows, left grid, count[0] -- and one view per key frame: R, t =
-// SE3f(Scw.rotationMatrix(), Scw.translation() / Scw.scale()), twc = its camera centre, p = the LEFT camera's parameters.  The gates are k_sim3_project's,
-// statement for statement (every input requested first, sums in k_fuse_project's order, every float operation rounded separately):
-//   reject skip; p3Dc = R p + t; reject p3Dc.z < 0.0f
-//   ORBX_SIM3_PROJECT_CAMERA: pKF->mpCamera->project(p3Dc) = KannalaBrandt8::project -- kb8_project as k_fuse_project_kb8 calls it (the bit contract and
-//     the one-ulp caveat of orbx_is_in_frustum_checks), evaluated only for pairs that are not skipped and lie in front of the camera;
-//   ORBX_SIM3_PROJECT_INVZ: the vpPointsKFs overload's written-out pinhole form (:573-578) with fx, fy, cx, cy = p[0..3] -- the caller puts pKF->fx,
-//     fy, cx, cy there: the reference writes it whatever the camera model is
-//   KeyFrame::IsInImage (strict on the max side)
-//   dist = |p - twc|; reject outside [0.8f mfMinDistance, 1.2f mfMaxDistance]
-//   reject PO . Pn < 0.5 * dist, compared in double and without a division
-//   PredictScale(dist, pKF); radius = th * mvScaleFactors[level]; levels [level - 1, level]
-// No ur.  skip / outputs [n_kf][n_mp].  Streaming work: no LDS.  grid (ceil(n_mp / 256), n_kf), block 256
-__global__ __launch_bounds__(256) void k_sim3_project_kb8(const KfProblem *__restrict__ recs, const FisheyeView *__restrict__ views, float th,
-                                                          float log_scale_factor, int projection_form, int n_mp, const float *__restrict__ pos,
-                                                          const float *__restrict__ normal, const float *__restrict__ min_dist,
-                                                          const float *__restrict__ max_dist, const uint8_t *__restrict__ skip, float *__restrict__ qx,
-                                                          float *__restrict__ qy, float *__restrict__ qr, int32_t *__restrict__ qmin,
-                                                          int32_t *__restrict__ qmax, uint8_t *__restrict__ qvalid) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n_mp) return;
-    const int k = blockIdx.y;
-    const size_t o = (size_t)k * n_mp + i;
-    const FisheyeView &V = views[k];
-    const float minx = recs[k].g.minx, miny = recs[k].g.miny, maxx = recs[k].maxx, maxy = recs[k].maxy;
-    const int nlevels = recs[k].nlevels;
-    const float *scale = recs[k].P.scale;
-    // every input of the pair requested at once (the gates read them conditionally: each would be a dependent round trip)
-    const uint8_t sk = skip ? skip[o] : (uint8_t)0;
-    const float P0 = pos[3 * i], P1 = pos[3 * i + 1], P2 = pos[3 * i + 2];
-    const float mn_in = min_dist[i], mx = max_dist[i], N0 = normal[3 * i], N1 = normal[3 * i + 1], N2 = normal[3 * i + 2];
-    float Pc[3];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-        Pc[r] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(V.R[3 * r], P0), __fmul_rn(V.R[3 * r + 1], P1)), __fmul_rn(V.R[3 * r + 2], P2)), V.t[r]);
-    bool ok = !sk && !(Pc[2] < 0.0f);
-    float u = 0.f, v = 0.f;
-    if (projection_form == ORBX_SIM3_PROJECT_INVZ) {   // the vpPointsKFs overload writes the pinhole projection out (:573-578)
-        const float invz = __fdiv_rn(1.0f, Pc[2]);
-        const float x = __fmul_rn(Pc[0], invz), y = __fmul_rn(Pc[1], invz);
-        u = __fadd_rn(__fmul_rn(V.p[0], x), V.p[2]); v = __fadd_rn(__fmul_rn(V.p[1], y), V.p[3]);
-    } else if (ok) {                                   // pKF->mpCamera->project(p3Dc): KannalaBrandt8::project
-        kb8_project(V.p, Pc[0], Pc[1], Pc[2], &u, &v);
-    }
-    ok = ok && (u >= minx && u < maxx && v >= miny && v < maxy);
-    const float PO0 = __fsub_rn(P0, V.twc[0]), PO1 = __fsub_rn(P1, V.twc[1]), PO2 = __fsub_rn(P2, V.twc[2]);
-    const float dist = sqrtf(__fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, PO0)), __fmul_rn(PO1, PO1)), __fmul_rn(PO2, PO2)));
-    const float maxDistance = __fmul_rn(1.2f, mx), minDistance = __fmul_rn(0.8f, mn_in);
-    ok = ok && !(dist < minDistance || dist > maxDistance);
-    const float dot = __fadd_rn(__fadd_rn(__fadd_rn(0.f, __fmul_rn(PO0, N0)), __fmul_rn(PO1, N1)), __fmul_rn(PO2, N2));
-    ok = ok && !((double)dot < 0.5 * (double)dist);
-    int lvl = 0;
-    float radius = 0.f;
-    if (ok) {   // MapPoint::PredictScale(dist, pKF) (MapPoint.cc:531-546), as k_fuse_project evaluates it
-        const float ratio = __fdiv_rn(mx, dist);
-        lvl = (int)ceilf(__fdiv_rn((float)log((double)ratio), log_scale_factor));
-        if (lvl < 0) lvl = 0;
-        else if (lvl >= nlevels) lvl = nlevels - 1;
-        radius = __fmul_rn(th, gld(scale + lvl));
-    }
-    qx[o] = u; qy[o] = v; qr[o] = radius;
-    qmin[o] = lvl - 1; qmax[o] = lvl;   // kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel (:504-507, :1411-1414)
-    qvalid[o] = ok ? 1 : 0;
-}
+// The projection half of Fuse and of the Sim3 members on such key frames is k_kf_project<true, SIM3> above.
 
 // A loaded fisheye-stereo orbx_frame copied into a key frame's own allocation -- what KeyFrame::KeyFrame(Frame&) (KeyFrame.cc:36-82) does with mvKeys,
 // mvKeysRight, mDescriptors, mvScaleFactors, mvInvLevelSigma2, mGrid and mGridRight: both cameras' rows, both counts, the scale factors and both grids AS

@@ -3511,13 +3511,22 @@ int orbx_keyframe_fuse_search_fisheye(orbx_matcher *m, int n_kf, orbx_keyframe *
     return keyframe_fuse_search_impl(m, true, n_kf, kfs, queries, use_chi2, strict_fp, best_idx, best_dist);
 }
 
-// LocalMapping::SearchInNeighbors' Fuse loop in one call: k_fuse_project (a rig: k_fuse_project_kb8) writes the query records of every (key frame,
+// k_kf_project over nprob = n_kf * K.sides problems: the one launch of the key-frame projection kernel, the instantiation by the kind of key frame and member
+static void launch_kf_project(hipStream_t stream, bool fisheye, bool sim3, int nprob, const KfProject &K) {
+    const dim3 grid((unsigned)((K.n_mp + 255) / 256), (unsigned)nprob);
+    if (fisheye && sim3) hipLaunchKernelGGL((k_kf_project<true, true>), grid, dim3(256), 0, stream, K);
+    else if (fisheye) hipLaunchKernelGGL((k_kf_project<true, false>), grid, dim3(256), 0, stream, K);
+    else if (sim3) hipLaunchKernelGGL((k_kf_project<false, true>), grid, dim3(256), 0, stream, K);
+    else hipLaunchKernelGGL((k_kf_project<false, false>), grid, dim3(256), 0, stream, K);
+}
+
+// LocalMapping::SearchInNeighbors' Fuse loop in one call: k_kf_project writes the query records of every (key frame,
 // [camera,] map point) into the arena, k_window_best1_kf searches the sides * n_kf problems -- the records never visit the host, the map points go up
 // once.  Monocular: cams / poses [n_kf], one problem per key frame, Fuse(pKFi, vpMapPointMatches).  fisheye: views [n_kf][2] instead, two problems per
 // key frame -- Fuse(pKFi, vpMapPointMatches) and Fuse(pKFi, vpMapPointMatches, true) -- and counts that are still on the device come home with the results.
 // sim3: LoopClosing::SearchAndFuse's loop instead, Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (ORBmatcher.cc:1339-1455) -- the records come from
-// k_sim3_project (no ur) and the search is the gate-less one: no inv_sigma2 wanted of the key frames, no mvuRight read.  fisheye && sim3: that member
-// reads the left camera only -- views [n_kf], ONE problem per key frame (its left side), records from k_sim3_project_kb8, best_idx below N_left.
+// k_kf_project<., true> (no ur) and the search is the gate-less one: no inv_sigma2 wanted of the key frames, no mvuRight read.  fisheye && sim3: that member
+// reads the left camera only -- views [n_kf], ONE problem per key frame (its left side), best_idx below N_left.
 static int keyframe_fuse_map_points_impl(orbx_matcher *m, bool fisheye, bool sim3, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
                                          const orbx_frame_pose *poses, const orbx_fisheye_view *views, float th, float log_scale_factor, int strict_fp,
                                          const MapPoints &src, const uint8_t *skip, int32_t *best_idx, int32_t *best_dist, uint8_t *projected) {
@@ -3570,23 +3579,9 @@ static int keyframe_fuse_map_points_impl(orbx_matcher *m, bool fisheye, bool sim
     ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
     uint64_t seq = 0;
     ORBX_TRY(map_points_gather(m, src, D, &seq));
-    const float *dp = D.pos, *dn = D.normal, *dmn = D.min_dist, *dmx = D.max_dist;
-    const dim3 grid((unsigned)((n_mp + 255) / 256), (unsigned)nprob);
-    if (fisheye && sim3)
-        hipLaunchKernelGGL(k_sim3_project_kb8, grid, dim3(256), 0, m->exec(), (const KfProblem *)dR, (const FisheyeView *)dview, th, log_scale_factor,
-                           (int)ORBX_SIM3_PROJECT_CAMERA, n_mp, (const float *)dp, (const float *)dn, (const float *)dmn, (const float *)dmx,
-                           (const uint8_t *)dskip, qx, qy, qr, qmin, qmax, qvalid);
-    else if (fisheye)
-        hipLaunchKernelGGL(k_fuse_project_kb8, grid, dim3(256), 0, m->exec(), (const KfProblem *)dR, (const FisheyeView *)dview, th, log_scale_factor, n_mp,
-                           (const float *)dp, (const float *)dn, (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx, qy, qr, qmin, qmax, qvalid);
-    else if (sim3)
-        hipLaunchKernelGGL(k_sim3_project, grid, dim3(256), 0, m->exec(), (const KfProblem *)dR, (const orbx_camera *)dcam, (const orbx_frame_pose *)dpose, th,
-                           log_scale_factor, (int)ORBX_SIM3_PROJECT_CAMERA, n_mp, (const float *)dp, (const float *)dn, (const float *)dmn, (const float *)dmx,
-                           (const uint8_t *)dskip, qx, qy, qr, qmin, qmax, qvalid);
-    else
-        hipLaunchKernelGGL(k_fuse_project, grid, dim3(256), 0, m->exec(), (const KfProblem *)dR, (const orbx_camera *)dcam, (const orbx_frame_pose *)dpose, th,
-                           log_scale_factor, n_mp, (const float *)dp, (const float *)dn, (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx, qy,
-                           qxr, qr, qmin, qmax, qvalid);
+    launch_kf_project(m->exec(), fisheye, sim3, nprob,
+                      KfProject{dR, dcam, dpose, dview, th, log_scale_factor, ORBX_SIM3_PROJECT_CAMERA, n_mp, sides, D.pos, D.normal, D.min_dist, D.max_dist, dskip,
+                                qx, qy, qxr, qr, qmin, qmax, qvalid});
     launch_window_best1_kf(m->exec(), dR, n_mp, nprob);
     std::vector<u64> keys(total);
     if (projected) ORBX_TRY(m->d2h(projected, qvalid, total));   // (adjacent to the keys: one download run)
@@ -4239,13 +4234,13 @@ int orbx_keyframe_search_for_triangulation_fisheye(orbx_matcher *m, orbx_keyfram
 // ---------------------------------------------------------------------------------------------------------
 // LoopClosing's Sim3 projection searches on resident key frames: both SearchByProjection(KeyFrame*, Sim3f&, ...) overloads (ORBmatcher.cc:427-532,
 // :534-646) for K key frames with one shared point set, and SearchAndFuse's loop of Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (:1339-1455).  The
-// gates run on the device (k_sim3_project); the searches are the existing kernels: k_window_best2_t + the replay of the query loop over n_kf problems
+// gates run on the device (k_kf_project<., true>); the searches are the existing kernels: k_window_best2_t + the replay of the query loop over n_kf problems
 // for the first, k_window_best1_kf through keyframe_fuse_map_points_impl for the second.  The _fisheye twins run the same on the LEFT side of rig key
-// frames (k_sim3_project_kb8: KannalaBrandt8::project, or the written-out pinhole form of the second overload).
+// frames (KannalaBrandt8::project, or the written-out pinhole form of the second overload).
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 
-// Both kinds of key frame through one body, the kind being `fisheye`: cams + poses [n_kf] and k_sim3_project, or views [n_kf] and k_sim3_project_kb8 on
+// Both kinds of key frame through one body, the kind being `fisheye`: cams + poses [n_kf], or views [n_kf] on
 // the LEFT side of a rig key frame (the members read nothing else: GetFeaturesInArea with bRight = false, mvKeysUn[idx], mpCamera) -- the left
 // keyframe_problem, N_left features for the replay, while the caller's match / occupied rows span N = N_left + N_right as vpMatched does.
 int keyframe_search_by_projection_sim3_impl(orbx_matcher *m, bool fisheye, int n_kf, orbx_keyframe *const *kfs, const orbx_camera *cams,
@@ -4304,7 +4299,7 @@ int keyframe_search_by_projection_sim3_impl(orbx_matcher *m, bool fisheye, int n
         for (int k = 0; k < n_kf; k++)
             if (occupied && occupied[k] && ns[(size_t)k] > 0) docc[(size_t)k] = A.up(occupied[k], (size_t)ns[(size_t)k]);
         dK = A.take<KfProblem>(n_kf); dP = A.take<WindowProblem>(n_kf); dR = A.take<ResolveProblem>(n_kf);
-        // written by k_sim3_project and the window scan, read by the scan and the replay: device only
+        // written by k_kf_project and the window scan, read by the scan and the replay: device only
         qr = A.take<float>(total); qmin = A.take<int32_t>(total); qmax = A.take<int32_t>(total);
         dkeys = A.take<u64>(total * kTopK); dmeta = A.take<int32_t>(total); dentries = A.take<int32_t>(total);
         // the downloads side by side (one run): the projections, the gates' verdicts, the match rows, nmatches
@@ -4335,16 +4330,9 @@ int keyframe_search_by_projection_sim3_impl(orbx_matcher *m, bool fisheye, int n
     ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
     uint64_t seq = 0;
     ORBX_TRY(map_points_gather(m, src, D, &seq));
-    const float *dp = D.pos, *dn = D.normal, *dmn = D.min_dist, *dmx = D.max_dist;
-    const dim3 pgrid((unsigned)((n_mp + 255) / 256), (unsigned)n_kf);
-    if (fisheye)
-        hipLaunchKernelGGL(k_sim3_project_kb8, pgrid, dim3(256), 0, m->exec(), (const KfProblem *)dK, (const FisheyeView *)dview, th, log_scale_factor,
-                           projection_form, n_mp, (const float *)dp, (const float *)dn, (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx,
-                           qy, qr, qmin, qmax, qvalid);
-    else
-        hipLaunchKernelGGL(k_sim3_project, pgrid, dim3(256), 0, m->exec(), (const KfProblem *)dK, (const orbx_camera *)dcam,
-                           (const orbx_frame_pose *)dpose, th, log_scale_factor, projection_form, n_mp, (const float *)dp, (const float *)dn,
-                           (const float *)dmn, (const float *)dmx, (const uint8_t *)dskip, qx, qy, qr, qmin, qmax, qvalid);
+    launch_kf_project(m->exec(), fisheye, true, n_kf,
+                      KfProject{dK, dcam, dpose, dview, th, log_scale_factor, projection_form, n_mp, 1, D.pos, D.normal, D.min_dist, D.max_dist, dskip, qx, qy,
+                                nullptr, qr, qmin, qmax, qvalid});
     const GridParams g = grid_of(kfs[0]->bounds);
     ORBX_LAUNCH_WINDOW_BEST2(n_mp, n_kf, m->exec(), (const WindowProblem *)dP, g);
     { const int rr = launch_resolve<false>(n_kf, m->exec(), dP, dR, g, nc, n_mp, 4); if (rr != ORBX_OK) return rr; }

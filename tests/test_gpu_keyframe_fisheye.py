@@ -7,7 +7,7 @@ search) is compared with a reference COMPOSED here from the oracle and float32 n
 is_in_frustum_checks(view, bounds, cos_limit = -2) per camera gives u, v, the distance gate and the level; the test removes the pairs on the strict
 image edge (KeyFrame::IsInImage: x < mnMaxX, y < mnMaxY) and those with float64(PO . Pn) < 0.5 * float64(dist3D) (float32 sums in the oracle's order),
 and feeds the survivors to the oracle's fuse_search WITHOUT u_right, with r = float32(th) * mvScaleFactors[level].  Every comparison is equality of
-integers, no pair is excluded.  Shapes: about 300 left / 200 right features per key frame, 300 map points (two blocks of k_fuse_project_kb8, the second
+integers, no pair is excluded.  Shapes: about 300 left / 200 right features per key frame, 300 map points (two blocks of k_kf_project<true, false>, the second
 partial), K in {1, 3}; key frame 1 has bounds of its own."""
 import ctypes as C
 import threading

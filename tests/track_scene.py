@@ -23,7 +23,7 @@ def _bits(a):
 
 
 def camera_points(pose, pos):
-    """x3Dc = Rcw p + tcw, one rounding per operation, summed as k_fuse_project sums."""
+    """x3Dc = Rcw p + tcw, one rounding per operation, summed as rigid_transform (geometry_kernels.hip.h) sums."""
     Rcw, tcw, _ = pose
     R, P = Rcw.astype(f32), pos.astype(f32)
     return [((R[r, 0] * P[:, 0] + R[r, 1] * P[:, 1]) + R[r, 2] * P[:, 2]) + tcw[r] for r in range(3)]
@@ -353,7 +353,7 @@ def kb8_project(oracle, params8, Pc):
 
 
 def right_points(Trl, Pc):
-    """x3Dr = Trl_R x3Dc + Trl_t, one rounding per operation, summed as k_fuse_project sums."""
+    """x3Dr = Trl_R x3Dc + Trl_t, one rounding per operation, summed as rigid_transform (geometry_kernels.hip.h) sums."""
     R, t = Trl[0].astype(f32), Trl[1].astype(f32)
     return [((R[r, 0] * Pc[0] + R[r, 1] * Pc[1]) + R[r, 2] * Pc[2]) + t[r] for r in range(3)]
 
