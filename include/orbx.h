@@ -1067,7 +1067,8 @@ int orbx_keyframe_distinctive_descriptors(orbx_matcher *m, int n_kf, orbx_keyfra
  *     serialization and debugging.  The same id may appear more than once.
  * Every call that takes ids checks them BEFORE anything is enqueued and before a transfer counter moves: ids not NULL when n > 0, each in
  * [0, capacity), its slot live, the map on m's device; a refused call changes neither the table nor the context (ORBX_E_BAD_ARG).
- * Ordering.  The table holds one event, `written`.  An update (orbx_map_update, orbx_keyframe_distinctive_descriptors_to_map) makes its context's
+ * Ordering.  The table holds one event, `written`.  An update (orbx_map_update, orbx_keyframe_distinctive_descriptors_to_map,
+ * orbx_keyframe_update_normal_and_depth_to_map, orbx_keyframe_refresh_map_points_to_map) makes its context's
  * stream wait for the previous `written`, launches and records the next one; every call that reads the table makes its stream wait for `written`
  * ahead of its gather, until a reading call that did so has synchronised.  So updates and reads issued one after the other, from any contexts and
  * threads, take effect in the order of the calls, and no host synchronisation is needed between an update and the search that follows it.
@@ -1182,6 +1183,60 @@ int orbx_frame_search_by_projection_keyframe_fisheye_map(orbx_matcher *m, orbx_f
 int orbx_keyframe_distinctive_descriptors_to_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, int n_sets, const int32_t *set_ptr,
                                                  const int32_t *obs_kf, const int32_t *obs_idx, orbx_map *map, const int32_t *set_id,
                                                  int32_t *best_obs);
+
+/* MapPoint::UpdateNormalAndDepth (MapPoint.cc, the member the reference calls right behind ComputeDistinctiveDescriptors in
+ * LocalMapping::ProcessNewKeyFrame, the "Update points" loop of SearchInNeighbors, Tracking::CreateNewKeyFrame and the loop-correction and merge
+ * code) for a batch of map points whose observations are features of RESIDENT key frames.  The observation list is
+ * orbx_keyframe_distinctive_descriptors' (set_ptr, obs_kf, obs_idx: std::map order, leftIndex then rightIndex of a rig observation), and so are the
+ * key frames.  In addition:
+ *   centers [n_kf][3]        GetCameraCenter() of each key frame
+ *   centers_right [n_kf][3]  GetRightCameraCenter(); may be NULL if no key frame of kfs is a fisheye-stereo one (rows of monocular ones are not read)
+ *   ref_obs [n_sets]         the position inside set s of the observation in mpRefKF -- on a rig the left one where both exist; ignored for an empty set
+ *   pos [n_sets][3]          mWorldPos (flat form); the `_to_map` forms read it from the slots
+ * The member as the device evaluates it, every float operation rounded on its own:
+ *   for observation o of the set, in the order of the list:
+ *       Owi = centers[obs_kf[o]] if obs_idx[o] < N_left or the key frame is monocular, centers_right[obs_kf[o]] otherwise
+ *       normali = Pos - Owi                          three subtractions
+ *       norm = sqrt(dot3(normali, normali))          ((0 + x x) + y y) + z z, correctly rounded square root     [Eigen-internal, unpinned]
+ *       normal = normal + normali / norm             three true divisions, three additions                      [Eigen-internal, unpinned]
+ *   mNormalVector = normal / (float)n                three divisions, n = the size of the set
+ *   PC = Pos - centers[key frame of ref_obs]         ALWAYS the left centre
+ *   dist = sqrt(dot3(PC, PC)); level = the octave of the reference observation's key point (mvKeysUn / mvKeys / mvKeysRight by its index)
+ *   mfMaxDistance = dist * mvScaleFactors[level];  mfMinDistance = mfMaxDistance / mvScaleFactors[mnScaleLevels - 1]
+ * The two distances are UNSCALED, as the member leaves them and as the table stores them (the device's gates apply 0.8f / 1.2f themselves).  A term
+ * with Pos == Owi is 0 / 0 = NaN here as in the reference.  An empty set is the member's early return: its entries of normal, min_dist, max_dist keep
+ * the caller's values and its slot is not written.
+ *   orbx_keyframe_update_normal_and_depth          flat: pos in; normal [n_sets][3], min_dist, max_dist [n_sets] out (all three required)
+ *   orbx_keyframe_update_normal_and_depth_to_map   pos is read from slot set_id[s], and normal, min_dist, max_dist are written into it (pos and the
+ *                                                  descriptor keep their bits).  normal / min_dist / max_dist: each NULL or an output as above; with
+ *                                                  all three NULL only the flag and any pending counts come home.  The host's mNormalVector /
+ *                                                  mfMinDistance / mfMaxDistance go stale unless they are requested.
+ *   orbx_keyframe_refresh_map_points_to_map        both members in one call: orbx_keyframe_distinctive_descriptors_to_map followed by
+ *                                                  orbx_keyframe_update_normal_and_depth_to_map (normal = min_dist = max_dist = NULL), bit for bit,
+ *                                                  with one upload run, one launch chain, one download run (best_obs), one synchronisation.
+ * The `_to_map` forms are updates of the table that also read it: they wait for `written`, launch, record `written` anew under the map's mutex -- and,
+ * unlike orbx_map_update, end in the call's one synchronisation.  After them only SetWorldPos (a bundle adjustment's write-back) is left to
+ * orbx_map_update.
+ * Refusals, ORBX_E_BAD_ARG before anything is enqueued or a transfer counter moves: everything orbx_keyframe_distinctive_descriptors[_to_map]
+ * refuses; centers NULL; centers_right NULL while a fisheye-stereo key frame is in kfs; ref_obs NULL; ref_obs[s] outside [0, size of set s) for a
+ * non-empty set; pos NULL (flat form); an output NULL (flat form); set_id NULL, not live, out of range or named twice; a map on another device.  An
+ * index outside [0, N) behind pending counts, or a reference key point whose octave is outside [0, nlevels), is found by the kernel: no address is formed
+ * from it, NOTHING is written to the table and the call returns ORBX_E_BAD_ARG (the flat outputs are unspecified then).  n_sets = 0: ORBX_OK, nothing
+ * enqueued.
+ * Cost shape: one upload run (the distinctive call's, plus ref_obs, one 64-byte record per key frame that holds the two centres, and pos in the flat
+ * form), one download run, one synchronisation, and a launch chain independent of n_kf and n_sets: k_normal_depth_kf (one wave per set; a set of
+ * more than 64 observations is walked in chunks by the same wave) and, `_to_map`, one k_map_scatter_refresh; the refresh call runs k_distinctive_kf
+ * (+ k_distinctive_kf_large) in front of them. */
+int orbx_keyframe_update_normal_and_depth(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const float *centers, const float *centers_right,
+                                          int n_sets, const int32_t *set_ptr, const int32_t *obs_kf, const int32_t *obs_idx, const int32_t *ref_obs,
+                                          const float *pos, float *normal, float *min_dist, float *max_dist);
+int orbx_keyframe_update_normal_and_depth_to_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const float *centers,
+                                                 const float *centers_right, int n_sets, const int32_t *set_ptr, const int32_t *obs_kf,
+                                                 const int32_t *obs_idx, const int32_t *ref_obs, orbx_map *map, const int32_t *set_id, float *normal,
+                                                 float *min_dist, float *max_dist);
+int orbx_keyframe_refresh_map_points_to_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const float *centers, const float *centers_right,
+                                            int n_sets, const int32_t *set_ptr, const int32_t *obs_kf, const int32_t *obs_idx,
+                                            const int32_t *ref_obs, orbx_map *map, const int32_t *set_id, int32_t *best_obs);
 
 /* Frame::ComputeStereoMatches (Frame.cc:811-981) for every frame of two resident batches: `left` and `right` must have
  * extracted batches of the same size and image shape (rectified stereo, lapping {0,0}).  Row-band Hamming match, 11x11

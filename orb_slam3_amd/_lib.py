@@ -189,6 +189,7 @@ SYMBOLS = [
     "orbx_keyframe_distinctive_descriptors_to_map",
     "orbx_frame_track_last_frame_map", "orbx_frame_search_by_projection_keyframe_map",
     "orbx_frame_track_last_frame_fisheye_map", "orbx_frame_search_by_projection_keyframe_fisheye_map",
+    "orbx_keyframe_update_normal_and_depth", "orbx_keyframe_update_normal_and_depth_to_map", "orbx_keyframe_refresh_map_points_to_map",
 ]
 
 
@@ -348,6 +349,9 @@ def lib() -> C.CDLL:
     L.orbx_keyframe_search_by_projection_sim3_fisheye_map.argtypes = [vp, i32, C.POINTER(vp), vp, f32, f32, f32, i32, i32, vp, vp, vp,
                                                                       C.POINTER(vp), C.POINTER(vp), vp, vp, vp, vp]
     L.orbx_keyframe_distinctive_descriptors_to_map.argtypes = [vp, i32, C.POINTER(vp), i32, vp, vp, vp, vp, vp, vp]
+    L.orbx_keyframe_update_normal_and_depth.argtypes = [vp, i32, C.POINTER(vp), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbx_keyframe_update_normal_and_depth_to_map.argtypes = [vp, i32, C.POINTER(vp), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbx_keyframe_refresh_map_points_to_map.argtypes = [vp, i32, C.POINTER(vp), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
     L.orbx_frame_track_last_frame_map.argtypes = [vp, vp, vp, vp, C.POINTER(Camera), C.POINTER(FramePose), vp, i32, vp, vp, f32, i32, i32, vp, vp, vp, vp]
     L.orbx_frame_search_by_projection_keyframe_map.argtypes = [vp, vp, vp, C.POINTER(Camera), C.POINTER(FramePose), f32, vp, vp, i32, vp, f32, f32, i32,
                                                                vp, vp, vp, vp]

@@ -155,8 +155,10 @@ private:
 // A device-resident table of map points (orbx_map): what the one-call searches read of a MapPoint -- GetWorldPos(), GetNormal(), mfMinDistance,
 // mfMaxDistance, mDescriptor -- in `capacity` slots addressed by ids the caller assigns (one int in MapPoint).  It belongs to no matcher: every
 // ORBmatcher of its device may update and read it, and the ...Map overloads of ORBmatcher take (map, ids) where the others take the five arrays.
-// update() after SetWorldPos / UpdateNormalAndDepth / a bundle adjustment's write-back, erase() at SetBadFlag; the caller does not run either
-// concurrently with a call that reads the table (Map::mMutexMapUpdate).  Destroy it only when no call that was handed it is running.
+// What keeps it current: ORBmatcher::RefreshMapPoints writes the descriptor, the normal and both distances of the map points a LocalMapping step
+// changed (ComputeDistinctiveDescriptors + UpdateNormalAndDepth, computed on the device; the table overloads of those two names are its halves);
+// update() is left for SetWorldPos / a bundle adjustment's write-back and for a slot's first, whole write; erase() at SetBadFlag.  The caller runs
+// none of them concurrently with a call that reads the table (Map::mMutexMapUpdate).  Destroy it only when no call that was handed it is running.
 class DeviceMap {
 public:
     explicit DeviceMap(int capacity, int device = 0) {
@@ -958,6 +960,78 @@ public:
                                                                    setId.data(), bestObs.data());
         if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_distinctive_descriptors_to_map: ") + orbx_status_string(r) + " " + orbx_last_error());
     }
+
+    // ---- MapPoint::UpdateNormalAndDepth on resident key frames, over ComputeDistinctiveDescriptors' observation lists.  centers / centersRight:
+    // 3 floats per key frame of vpKFs, GetCameraCenter() / GetRightCameraCenter() (centersRight may be empty without rig key frames); refObs[s] = the
+    // position inside map point s's observations of the one in mpRefKF (the left one of a rig observation that has both).  The distances come back /
+    // are stored UNSCALED, as the member leaves mfMinDistance / mfMaxDistance; a map point without observations keeps what it had.
+    // flat (orbx_keyframe_update_normal_and_depth): pos = 3 floats per map point (mWorldPos) in, normal (3 per point), minDistance, maxDistance out
+    void UpdateNormalAndDepth(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<float> &centers, const std::vector<float> &centersRight,
+                              const std::vector<int32_t> &setPtr, const std::vector<int32_t> &obsKf, const std::vector<int32_t> &obsIdx,
+                              const std::vector<int32_t> &refObs, const std::vector<float> &pos, std::vector<float> &normal,
+                              std::vector<float> &minDistance, std::vector<float> &maxDistance) {
+        const size_t n = NormalDepthSets("UpdateNormalAndDepth", vpKFs, centers, centersRight, setPtr, obsKf, obsIdx, refObs);
+        if (pos.size() != 3 * n) throw std::invalid_argument("UpdateNormalAndDepth: three floats of pos per map point");
+        normal.resize(3 * n); minDistance.resize(n); maxDistance.resize(n);
+        std::vector<orbx_keyframe *> h = KeyFrameHandles(vpKFs);
+        const int r = orbx_keyframe_update_normal_and_depth(m_, (int)h.size(), h.data(), centers.data(), centersRight.empty() ? nullptr : centersRight.data(),
+                                                            (int)n, setPtr.data(), obsKf.data(), obsIdx.data(), refObs.data(), pos.data(), normal.data(),
+                                                            minDistance.data(), maxDistance.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_update_normal_and_depth: ") + orbx_status_string(r) + " " + orbx_last_error());
+    }
+    // into the table (orbx_keyframe_update_normal_and_depth_to_map): pos is read from slot setId[s], the results are written into it.  normal /
+    // minDistance / maxDistance: NULL, or vectors that receive what was written -- without them the host's members go stale.
+    void UpdateNormalAndDepth(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<float> &centers, const std::vector<float> &centersRight,
+                              const std::vector<int32_t> &setPtr, const std::vector<int32_t> &obsKf, const std::vector<int32_t> &obsIdx,
+                              const std::vector<int32_t> &refObs, const DeviceMap &map, const std::vector<int32_t> &setId,
+                              std::vector<float> *normal = nullptr, std::vector<float> *minDistance = nullptr, std::vector<float> *maxDistance = nullptr) {
+        const size_t n = NormalDepthSets("UpdateNormalAndDepth", vpKFs, centers, centersRight, setPtr, obsKf, obsIdx, refObs);
+        if (setId.size() != n) throw std::invalid_argument("UpdateNormalAndDepth: an id per map point");
+        if (normal) normal->resize(3 * n);
+        if (minDistance) minDistance->resize(n);
+        if (maxDistance) maxDistance->resize(n);
+        std::vector<orbx_keyframe *> h = KeyFrameHandles(vpKFs);
+        const int r = orbx_keyframe_update_normal_and_depth_to_map(m_, (int)h.size(), h.data(), centers.data(),
+                                                                   centersRight.empty() ? nullptr : centersRight.data(), (int)n, setPtr.data(), obsKf.data(),
+                                                                   obsIdx.data(), refObs.data(), map.handle(), setId.data(), normal ? normal->data() : nullptr,
+                                                                   minDistance ? minDistance->data() : nullptr, maxDistance ? maxDistance->data() : nullptr);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_update_normal_and_depth_to_map: ") + orbx_status_string(r) + " " + orbx_last_error());
+    }
+    // pMP->ComputeDistinctiveDescriptors(); pMP->UpdateNormalAndDepth(); for a batch of map points in ONE call
+    // (orbx_keyframe_refresh_map_points_to_map): the descriptor, the normal and both distances of slot setId[s] are refreshed on the device; bestObs as
+    // ComputeDistinctiveDescriptors returns it.  After it only SetWorldPos is left to DeviceMap::update.
+    void RefreshMapPoints(const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<float> &centers, const std::vector<float> &centersRight,
+                          const std::vector<int32_t> &setPtr, const std::vector<int32_t> &obsKf, const std::vector<int32_t> &obsIdx,
+                          const std::vector<int32_t> &refObs, const DeviceMap &map, const std::vector<int32_t> &setId, std::vector<int32_t> &bestObs) {
+        const size_t n = NormalDepthSets("RefreshMapPoints", vpKFs, centers, centersRight, setPtr, obsKf, obsIdx, refObs);
+        if (setId.size() != n) throw std::invalid_argument("RefreshMapPoints: an id per map point");
+        bestObs.assign(n, -1);
+        std::vector<orbx_keyframe *> h = KeyFrameHandles(vpKFs);
+        const int r = orbx_keyframe_refresh_map_points_to_map(m_, (int)h.size(), h.data(), centers.data(), centersRight.empty() ? nullptr : centersRight.data(),
+                                                              (int)n, setPtr.data(), obsKf.data(), obsIdx.data(), refObs.data(), map.handle(), setId.data(),
+                                                              bestObs.data());
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_refresh_map_points_to_map: ") + orbx_status_string(r) + " " + orbx_last_error());
+    }
+
+private:
+    static std::vector<orbx_keyframe *> KeyFrameHandles(const std::vector<DeviceKeyFrame *> &vpKFs) {
+        std::vector<orbx_keyframe *> h(vpKFs.size());
+        for (size_t k = 0; k < vpKFs.size(); k++) h[k] = vpKFs[k]->handle();
+        return h;
+    }
+    // the sizes the three calls above share; returns the number of map points
+    static size_t NormalDepthSets(const char *who, const std::vector<DeviceKeyFrame *> &vpKFs, const std::vector<float> &centers,
+                                  const std::vector<float> &centersRight, const std::vector<int32_t> &setPtr, const std::vector<int32_t> &obsKf,
+                                  const std::vector<int32_t> &obsIdx, const std::vector<int32_t> &refObs) {
+        const size_t n = setPtr.empty() ? 0 : setPtr.size() - 1;
+        if (obsKf.size() != obsIdx.size() || refObs.size() != n || (n > 0 && (setPtr[n] < 0 || (size_t)setPtr[n] > obsKf.size())) ||
+            centers.size() != 3 * vpKFs.size() || (!centersRight.empty() && centersRight.size() != 3 * vpKFs.size()))
+            throw std::invalid_argument(std::string(who) + ": a key frame number and an index per observation, setPtr inside them, a reference position "
+                                                           "per map point, three floats per key frame and centre");
+        return n;
+    }
+
+public:
 
     // ---- The Tracking thread's searches whose queries are another frame's map points, from map ids (monocular / rectified frames): ids[i] = the
     // slot of the source's mvpMapPoints[i] or -1; the projection, the gates and the windows run on the device (k_track_project).  vpMatch[j] >= 0 is

@@ -329,12 +329,15 @@ struct DistinctSets {
     int n_kf, n_sets;
 };
 
-// the four words of observation o's row; false (zeros): the observation names no row of a key frame of the table
-__device__ __forceinline__ bool distinct_gather(const DistinctSets &A, int o, u64 *w) {
-    w[0] = w[1] = w[2] = w[3] = 0;
-    const int k = gld(A.obs_kf + o), i = gld(A.obs_idx + o);
-    if ((unsigned)k >= (unsigned)A.n_kf) return false;
-    const DistinctKf *R = A.kf + k;
+// Observation o of a call's lists = feature obs_idx[o] of key frame obs_kf[o]: use(R, i, row) with the key frame's record, the index (reference
+// numbering, left then right) and the row that holds it.  Index i of a rig key frame is row i below N_left and row roff + (i - N_left) from there on
+// (so its rows from roff on are the right camera's: N_left <= roff); the counts are read here, on the device.  false, and use() not called: the
+// observation names no row of a key frame of the table.  Rec: DistinctKf or NormalKf (count, roff, cap, fisheye).
+template <class Rec, class Use>
+__device__ __forceinline__ bool kf_observation_row(const Rec *kf, int n_kf, const int32_t *obs_kf, const int32_t *obs_idx, int o, Use use) {
+    const int k = gld(obs_kf + o), i = gld(obs_idx + o);
+    if ((unsigned)k >= (unsigned)n_kf) return false;
+    const Rec *R = kf + k;
     const int32_t *cnt = gld(&R->count);
     const int roff = gld(&R->roff), cap = gld(&R->cap);
     int n, row = i;
@@ -346,9 +349,17 @@ __device__ __forceinline__ bool distinct_gather(const DistinctSets &A, int o, u6
         n = min(max(gld(cnt), 0), cap);
     }
     if ((unsigned)i >= (unsigned)n) return false;
-    const u64 *q = reinterpret_cast<const u64 *>(gld(&R->desc) + (size_t)row * 32);   // rows are 32-byte aligned
-    w[0] = gld(q); w[1] = gld(q + 1); w[2] = gld(q + 2); w[3] = gld(q + 3);
+    use(R, i, row);
     return true;
+}
+
+// the four words of observation o's row; false (zeros): the observation names no row of a key frame of the table
+__device__ __forceinline__ bool distinct_gather(const DistinctSets &A, int o, u64 *w) {
+    w[0] = w[1] = w[2] = w[3] = 0;
+    return kf_observation_row(A.kf, A.n_kf, A.obs_kf, A.obs_idx, o, [&](const DistinctKf *R, int, int row) {
+        const u64 *q = reinterpret_cast<const u64 *>(gld(&R->desc) + (size_t)row * 32);   // rows are 32-byte aligned
+        w[0] = gld(q); w[1] = gld(q + 1); w[2] = gld(q + 2); w[3] = gld(q + 3);
+    });
 }
 
 __global__ __launch_bounds__(256) void k_distinctive_kf(const DistinctSets A) {
@@ -466,6 +477,97 @@ __global__ __launch_bounds__(1024) void k_distinctive_kf_large(const DistinctSet
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// MapPoint::UpdateNormalAndDepth (MapPoint.cc) on RESIDENT key frames (orbx_keyframe_update_normal_and_depth): the same observation list as
+// k_distinctive_kf's, one wave per set, four sets per block, lane j takes observation j of the set.
+//   record table   NormalKf per key frame: key points, scale factors, count pointer, roff, capacity, kind, nlevels and the two camera centres.  An index
+//                  below N_left (any index of a monocular key frame) uses `center`, one from N_left on `center_right`; index -> row is
+//                  kf_observation_row, the rule distinct_gather goes through.
+//   per lane       normali = Pos - Owi (three subtractions), its norm (sqrt of dot3), normali / norm (three divisions): every operation rounds on its own
+//   ordered sum    the set is wave-uniform, so is the loop: term i is broadcast (v_readlane) and added to an accumulator every lane holds, three adds per
+//                  observation IN THE ORDER OF THE LIST.  A set of more than 64 observations is walked in chunks of 64 with the accumulator carried.
+//   reference      the lane at ref_obs[s] reads its row's octave and forms dist = |Pos - Ow(left)|, max = dist * scale[level], min = max / scale[nlevels - 1].
+//                  An octave outside [0, nlevels), an index outside [0, N) or a key frame number outside the table forms no address and raises *flag.
+//   Pos            row s of `pos`, or (pos == NULL) quarter 0 of slot set_id[s] of the table
+// An empty set writes nothing.  A term with Pos == Owi is 0 / 0 = NaN, as in the reference.  No LDS, no scratch.  counts_out as k_distinctive_kf.
+// grid (max(ceil(n_sets / 4), ceil(n_kf / 256))), block 256
+// ---------------------------------------------------------------------------------------------------------
+struct NormalKf {
+    const orbx_keypoint *kps; const float *scale; const int32_t *count;
+    int32_t roff, cap, fisheye, nlevels;
+    float center[3], center_right[3];
+};
+struct NormalSets {
+    const NormalKf *kf; const int32_t *set_ptr, *obs_kf, *obs_idx, *ref_obs;
+    const float *pos;                          // [n_sets][3], or NULL: the table's
+    const uint4 *rec; const int32_t *set_id;   // the table and the sets' slots (pos == NULL)
+    float *normal, *min_dist, *max_dist;       // [n_sets][3], [n_sets], [n_sets]
+    int32_t *flag, *counts_out;                // counts_out: [n_kf][2] or NULL
+    int n_kf, n_sets, map_cap;
+};
+
+__global__ __launch_bounds__(256) void k_normal_depth_kf(const NormalSets A) {
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+    const int gt = blockIdx.x * 256 + threadIdx.x;
+    if (A.counts_out && gt < A.n_kf) {
+        const int32_t *cnt = gld(&A.kf[gt].count);
+        gst(A.counts_out + 2 * gt, gld(cnt));
+        gst(A.counts_out + 2 * gt + 1, gld(&A.kf[gt].fisheye) ? gld(cnt + 1) : 0);
+    }
+    const int s = blockIdx.x * 4 + wv;
+    if (s >= A.n_sets) return;  // wave-uniform; no block barrier below
+    const int b = gld(A.set_ptr + s), N = gld(A.set_ptr + s + 1) - b;
+    if (N <= 0) return;
+    float P0, P1, P2;
+    if (A.pos) {
+        P0 = gld(A.pos + 3 * (size_t)s); P1 = gld(A.pos + 3 * (size_t)s + 1); P2 = gld(A.pos + 3 * (size_t)s + 2);
+    } else {
+        const int id = gld(A.set_id + s);
+        if ((unsigned)id >= (unsigned)A.map_cap) { if (lane == 0) gst(A.flag, 1); return; }   // (the host has checked every id)
+        const uint4 q0 = A.rec[(size_t)id * 4];
+        P0 = __uint_as_float(q0.x); P1 = __uint_as_float(q0.y); P2 = __uint_as_float(q0.z);
+    }
+    const int ref = gld(A.ref_obs + s);
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    bool bad = false;
+    for (int c = 0; c < N; c += 64) {
+        const int j = c + lane;
+        float t0 = 0.f, t1 = 0.f, t2 = 0.f;
+        if (j < N) {
+            bool level_ok = true;
+            const bool ok = kf_observation_row(A.kf, A.n_kf, A.obs_kf, A.obs_idx, b + j, [&](const NormalKf *R, int, int row) {
+                const float *O = gld(&R->fisheye) && row >= gld(&R->roff) ? R->center_right : R->center;
+                const float d0 = __fsub_rn(P0, gld(O)), d1 = __fsub_rn(P1, gld(O + 1)), d2 = __fsub_rn(P2, gld(O + 2));
+                const float nrm = sqrtf(dot3(d0, d1, d2, d0, d1, d2));
+                t0 = __fdiv_rn(d0, nrm); t1 = __fdiv_rn(d1, nrm); t2 = __fdiv_rn(d2, nrm);
+                if (j != ref) return;
+                const int level = gld(&R->kps[row].octave), nlevels = gld(&R->nlevels);
+                level_ok = (unsigned)level < (unsigned)nlevels;
+                if (!level_ok) return;
+                // PC = Pos - pRefKF->GetCameraCenter(): always the left centre
+                const float *sc = gld(&R->scale);
+                const float c0 = __fsub_rn(P0, gld(R->center)), c1 = __fsub_rn(P1, gld(R->center + 1)), c2 = __fsub_rn(P2, gld(R->center + 2));
+                const float dist = sqrtf(dot3(c0, c1, c2, c0, c1, c2));
+                const float mx = __fmul_rn(dist, gld(sc + level));
+                gst(A.max_dist + s, mx);
+                gst(A.min_dist + s, __fdiv_rn(mx, gld(sc + nlevels - 1)));
+            });
+            bad = !ok || !level_ok;
+        }
+        if (__ballot(bad) != 0ull && lane == 0) gst(A.flag, 1);
+        const int m = min(N - c, 64);
+        for (int i = 0; i < m; i++) {   // (i is wave-uniform: v_readlane)
+            a0 = __fadd_rn(a0, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t0), i)));
+            a1 = __fadd_rn(a1, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t1), i)));
+            a2 = __fadd_rn(a2, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(t2), i)));
+        }
+    }
+    if (lane < 3) {
+        const float n = (float)N;
+        gst(A.normal + 3 * (size_t)s + lane, __fdiv_rn(lane == 0 ? a0 : lane == 1 ? a1 : a2, n));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // The device-resident map-point table (orbx_map): one 64-byte record per slot, four 16-byte quarters
 //   quarter 0   pos.x pos.y pos.z normal.x        quarter 1   normal.y normal.z min_dist max_dist        quarters 2, 3   the descriptor (32-byte aligned)
 // Four lanes per point, one quarter each: a wave moves 16 records, a block 64.  Streaming work: no LDS, nothing kept between points.  Every id comes
@@ -475,6 +577,7 @@ __global__ __launch_bounds__(1024) void k_distinctive_kf_large(const DistinctSet
 //   k_map_gather        slot ids[j] -> row j of the five arrays every projection kernel reads (the flat call's arena buffers)
 //   k_map_scatter_desc  the winning row of set s (orbx_keyframe_distinctive_descriptors_to_map) -> the descriptor of slot set_id[s]; nothing for an
 //                       empty set (best_obs < 0), nothing at all once the distinctive kernels raised *flag
+//   k_map_scatter_refresh  k_normal_depth_kf's normal and distance bounds of set s (and the winning row) -> slot set_id[s], pos kept; the same two rules
 // grid (ceil(n / 64)), block 256
 // ---------------------------------------------------------------------------------------------------------
 struct MapRows {
@@ -527,6 +630,30 @@ __global__ __launch_bounds__(256) void k_map_scatter_desc(uint4 *rec, int cap, i
     const int id = gld(set_id + s);
     if (gld(best_obs + s) < 0 || (unsigned)id >= (unsigned)cap) return;
     rec[(size_t)id * 4 + 2 + h] = reinterpret_cast<const uint4 *>(best_desc)[(size_t)s * 2 + h];
+}
+// k_map_scatter_refresh: what k_normal_depth_kf (and, best_desc != NULL, the distinctive kernels) left in the arena for set s -> slot set_id[s].  Four
+// lanes per set, one quarter each: quarter 0 keeps pos and takes normal.x, quarter 1 is written whole, quarters 2 and 3 are the winning row.  Nothing
+// for an empty set, nothing at all once a compute kernel raised *flag.
+// grid (ceil(n_sets / 64)), block 256
+__global__ __launch_bounds__(256) void k_map_scatter_refresh(uint4 *rec, int cap, int n_sets, const int32_t *__restrict__ set_id,
+                                                             const int32_t *__restrict__ set_ptr, const int32_t *__restrict__ flag,
+                                                             const float *__restrict__ normal, const float *__restrict__ min_dist,
+                                                             const float *__restrict__ max_dist, const uint8_t *__restrict__ best_desc) {
+    const int t = blockIdx.x * 256 + threadIdx.x, s = t >> 2, q = t & 3;
+    if (s >= n_sets || gld(flag) != 0) return;
+    const int id = gld(set_id + s);
+    if (gld(set_ptr + s + 1) - gld(set_ptr + s) <= 0 || (unsigned)id >= (unsigned)cap) return;
+    uint4 *dst = rec + (size_t)id * 4 + q;
+    if (q >= 2) {
+        if (best_desc) *dst = reinterpret_cast<const uint4 *>(best_desc)[(size_t)s * 2 + (q - 2)];
+    } else if (q == 0) {
+        uint4 v = *dst;
+        v.w = __float_as_uint(gld(normal + 3 * (size_t)s));
+        *dst = v;
+    } else {
+        *dst = make_uint4(__float_as_uint(gld(normal + 3 * (size_t)s + 1)), __float_as_uint(gld(normal + 3 * (size_t)s + 2)),
+                          __float_as_uint(gld(min_dist + s)), __float_as_uint(gld(max_dist + s)));
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <climits>
 #include <cmath>
@@ -3965,17 +3966,29 @@ int orbx_keyframe_bow_from_frame_fisheye(orbx_matcher *m, orbx_keyframe *kf, orb
 // frames that still had them on the device), one synchronisation.
 // map != NULL (orbx_keyframe_distinctive_descriptors_to_map): best_desc stays in the arena and k_map_scatter_desc writes its rows into the slots set_id
 // names, ordered as an update of the table.
+// nd != NULL: MapPoint::UpdateNormalAndDepth over the same observation lists (k_normal_depth_kf), alone (distinct = false:
+// orbx_keyframe_update_normal_and_depth[_to_map]) or behind the distinctive kernels (orbx_keyframe_refresh_map_points_to_map); with a table its results
+// (and the winning rows) go into the slots through ONE k_map_scatter_refresh.  Same checks, same upload run, same download run, same synchronisation.
+struct NormalDepth {
+    const float *centers, *centers_right; const int32_t *ref_obs;
+    const float *pos;                       // flat form; NULL with a table
+    float *normal, *min_dist, *max_dist;    // outputs; each may be NULL with a table
+};
 static int keyframe_distinctive_impl(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, int n_sets, const int32_t *set_ptr, const int32_t *obs_kf,
-                                     const int32_t *obs_idx, int32_t *best_obs, uint8_t *best_desc, orbx_map *map, const int32_t *set_id) {
-    if (!m || n_kf < 0 || n_sets < 0 || (n_kf > 0 && !kfs) || (n_sets > 0 && (!set_ptr || !best_obs))) return ORBX_E_BAD_ARG;
+                                     const int32_t *obs_idx, int32_t *best_obs, uint8_t *best_desc, orbx_map *map, const int32_t *set_id,
+                                     const NormalDepth *nd = nullptr, bool distinct = true) {
+    if (!m || n_kf < 0 || n_sets < 0 || (n_kf > 0 && !kfs) || (n_sets > 0 && (!set_ptr || (distinct && !best_obs)))) return ORBX_E_BAD_ARG;
     if (n_kf > ORBX_MAX_DISTINCTIVE_KEYFRAMES) return ORBX_E_TOO_LARGE;
     if (n_sets == 0) return ORBX_OK;
     // everything is checked before anything is enqueued
     if (set_ptr[0] < 0) return ORBX_E_BAD_ARG;
+    if (nd && ((n_kf > 0 && !nd->centers) || !nd->ref_obs || (!map && (!nd->pos || !nd->normal || !nd->min_dist || !nd->max_dist)))) return ORBX_E_BAD_ARG;
     std::vector<int32_t> large;   // the sets k_distinctive_kf_large takes
     for (int s = 0; s < n_sets; s++) {
-        if (set_ptr[s + 1] < set_ptr[s]) return ORBX_E_BAD_ARG;
-        if (set_ptr[s + 1] - set_ptr[s] > kDistinctRegisterRows) large.push_back(s);
+        const int32_t size = set_ptr[s + 1] - set_ptr[s];
+        if (size < 0) return ORBX_E_BAD_ARG;
+        if (distinct && size > kDistinctRegisterRows) large.push_back(s);
+        if (nd && size > 0 && (nd->ref_obs[s] < 0 || nd->ref_obs[s] >= size)) return ORBX_E_BAD_ARG;
     }
     const size_t total = (size_t)set_ptr[n_sets];
     if (total > 0 && (!obs_kf || !obs_idx)) return ORBX_E_BAD_ARG;
@@ -3988,59 +4001,107 @@ static int keyframe_distinctive_impl(orbx_matcher *m, int n_kf, orbx_keyframe *c
     bool pending = false;
     for (int k = 0; k < n_kf; k++) {
         if (!kfs[k] || kfs[k]->device != m->device) return ORBX_E_BAD_ARG;
+        if (nd && kfs[k]->fisheye && !nd->centers_right) return ORBX_E_BAD_ARG;
         pending |= kfs[k]->host_n() < 0;
     }
     for (size_t o = (size_t)set_ptr[0]; o < total; o++) {
         if (obs_kf[o] < 0 || obs_kf[o] >= n_kf) return ORBX_E_BAD_ARG;
         if (obs_idx[o] < 0 || obs_idx[o] >= kfs[obs_kf[o]]->rows_n()) return ORBX_E_BAD_ARG;   // (counts pending: the capacity; the kernel checks against N)
     }
-    if (total == (size_t)set_ptr[0]) {   // empty sets only
-        for (int s = 0; s < n_sets; s++) best_obs[s] = -1;
+    if (total == (size_t)set_ptr[0]) {   // empty sets only: nothing to compute, nothing to write
+        for (int s = 0; distinct && s < n_sets; s++) best_obs[s] = -1;
         if (best_desc) memset(best_desc, 0, 32 * (size_t)n_sets);
         return ORBX_OK;
     }
     ORBX_HIP(hipSetDevice(m->device));
-    std::vector<DistinctKf> recs((size_t)n_kf);
-    for (int k = 0; k < n_kf; k++) recs[k] = DistinctKf{kfs[k]->desc, kfs[k]->count, kfs[k]->roff, kfs[k]->cap, kfs[k]->fisheye ? 1 : 0, 0};
+    std::vector<DistinctKf> recs(distinct ? (size_t)n_kf : 0);
+    for (int k = 0; distinct && k < n_kf; k++) recs[k] = DistinctKf{kfs[k]->desc, kfs[k]->count, kfs[k]->roff, kfs[k]->cap, kfs[k]->fisheye ? 1 : 0, 0};
+    std::vector<NormalKf> nrecs(nd ? (size_t)n_kf : 0);
+    for (int k = 0; nd && k < n_kf; k++) {
+        NormalKf &R = nrecs[k];
+        memset(&R, 0, sizeof(R));
+        R.kps = kfs[k]->kps; R.scale = kfs[k]->scale; R.count = kfs[k]->count;
+        R.roff = kfs[k]->roff; R.cap = kfs[k]->cap; R.fisheye = kfs[k]->fisheye ? 1 : 0; R.nlevels = kfs[k]->nlevels;
+        memcpy(R.center, nd->centers + 3 * (size_t)k, sizeof(R.center));
+        if (kfs[k]->fisheye) memcpy(R.center_right, nd->centers_right + 3 * (size_t)k, sizeof(R.center_right));
+    }
     DistinctSets A;
     memset(&A, 0, sizeof(A));
     A.n_kf = n_kf; A.n_sets = n_sets;
+    NormalSets B;
+    memset(&B, 0, sizeof(B));
+    B.n_kf = n_kf; B.n_sets = n_sets;
     const int32_t *dlarge = nullptr, *dset_id = nullptr;
+    int32_t *flag = nullptr, *counts_out = nullptr;
     ORBX_TRY(m->carve([&](Carve &C) {
         A.set_ptr = C.up(set_ptr, (size_t)n_sets + 1); A.obs_kf = C.up(obs_kf, total); A.obs_idx = C.up(obs_idx, total);
-        A.kf = C.up(recs.data(), (size_t)n_kf);
+        if (distinct) A.kf = C.up(recs.data(), (size_t)n_kf);
         if (!large.empty()) dlarge = C.up(large.data(), large.size());
         if (map) dset_id = C.up(set_id, (size_t)n_sets);
-        A.best_obs = C.take<int32_t>(n_sets); A.flag = C.take<int32_t>(4);   // (best_obs between the uploads and the flag's fill: one k_xfer launch for both)
+        if (nd) {
+            B.kf = C.up(nrecs.data(), (size_t)n_kf); B.ref_obs = C.up(nd->ref_obs, (size_t)n_sets);
+            if (!map) B.pos = C.up(nd->pos, 3 * (size_t)n_sets);
+        }
+        if (distinct) A.best_obs = C.take<int32_t>(n_sets);   // (best_obs between the uploads and the flag's fill: one k_xfer launch for both)
+        flag = C.take<int32_t>(4);
         if (best_desc) A.best_desc = C.take<uint8_t>(32 * (size_t)n_sets);
-        if (pending) A.counts_out = C.take<int32_t>(2 * (size_t)n_kf);
-        if (map) A.best_desc = C.take<uint8_t>(32 * (size_t)n_sets);   // (not downloaded: behind the result run)
+        if (pending) counts_out = C.take<int32_t>(2 * (size_t)n_kf);
+        if (nd) { B.normal = C.take<float>(3 * (size_t)n_sets); B.min_dist = C.take<float>(n_sets); B.max_dist = C.take<float>(n_sets); }
+        if (map && distinct) A.best_desc = C.take<uint8_t>(32 * (size_t)n_sets);   // (not downloaded: behind the result run)
         if (!large.empty()) A.scratch = C.take<uint8_t>(32 * total);
     }));
-    ORBX_HIP(m->fill(A.flag, 0, 16));
+    A.flag = B.flag = flag;
+    (distinct ? A.counts_out : B.counts_out) = counts_out;   // the first compute kernel of the chain brings the pending counts
+    B.set_ptr = A.set_ptr; B.obs_kf = A.obs_kf; B.obs_idx = A.obs_idx;
+    if (map) { B.rec = map->rec; B.set_id = dset_id; B.map_cap = map->capacity; }
+    ORBX_HIP(m->fill(flag, 0, 16));
     ORBX_TRY(keyframe_acquire(m, kfs, n_kf));
     const unsigned grid = (unsigned)std::max((n_sets + 3) / 4, (n_kf + 255) / 256);
-    hipLaunchKernelGGL(k_distinctive_kf, dim3(grid), dim3(256), 0, m->exec(), A);
+    if (distinct) hipLaunchKernelGGL(k_distinctive_kf, dim3(grid), dim3(256), 0, m->exec(), A);
     if (!large.empty()) hipLaunchKernelGGL(k_distinctive_kf_large, dim3((unsigned)large.size()), dim3(64 * kDistinctLargeWaves), 0, m->exec(), A, dlarge);
+    if (map && map->write_seq > 0) ORBX_HIP(hipStreamWaitEvent(m->exec(), map->written, 0));   // (k_normal_depth_kf reads pos from the slots)
+    if (nd) hipLaunchKernelGGL(k_normal_depth_kf, dim3(grid), dim3(256), 0, m->exec(), B);
     if (map) {
-        if (map->write_seq > 0) ORBX_HIP(hipStreamWaitEvent(m->stream, map->written, 0));
-        hipLaunchKernelGGL(k_map_scatter_desc, dim3((unsigned)((n_sets + 127) / 128)), dim3(256), 0, m->exec(), map->rec, map->capacity, n_sets, dset_id,
-                           (const int32_t *)A.best_obs, (const int32_t *)A.flag, (const uint8_t *)A.best_desc);
+        if (nd)
+            hipLaunchKernelGGL(k_map_scatter_refresh, dim3((unsigned)((n_sets + 63) / 64)), dim3(256), 0, m->exec(), map->rec, map->capacity, n_sets, dset_id,
+                               A.set_ptr, (const int32_t *)flag, (const float *)B.normal, (const float *)B.min_dist, (const float *)B.max_dist,
+                               (const uint8_t *)A.best_desc);
+        else
+            hipLaunchKernelGGL(k_map_scatter_desc, dim3((unsigned)((n_sets + 127) / 128)), dim3(256), 0, m->exec(), map->rec, map->capacity, n_sets, dset_id,
+                               (const int32_t *)A.best_obs, (const int32_t *)flag, (const uint8_t *)A.best_desc);
         ORBX_HIP(hipEventRecord(map->written, m->stream));
         map->write_seq++;
     }
     ORBX_HIP(hipGetLastError());
-    int32_t flag = 0;
+    int32_t raised = 0;
     std::vector<int32_t> counts(pending ? 2 * (size_t)n_kf : 0);
-    ORBX_TRY(m->d2h(best_obs, A.best_obs, 4 * (size_t)n_sets));
-    ORBX_TRY(m->d2h(&flag, A.flag, 4));
+    // an empty set is the member's early return: its entries of the caller's arrays keep their values (the arena's rows of such a set are never written)
+    std::vector<std::pair<int, std::array<float, 5>>> kept;
+    for (int s = 0; nd && s < n_sets; s++) {
+        if (set_ptr[s + 1] > set_ptr[s]) continue;
+        std::array<float, 5> v = {0, 0, 0, 0, 0};
+        if (nd->normal) memcpy(v.data(), nd->normal + 3 * (size_t)s, 12);
+        if (nd->min_dist) v[3] = nd->min_dist[s];
+        if (nd->max_dist) v[4] = nd->max_dist[s];
+        kept.emplace_back(s, v);
+    }
+    if (distinct) ORBX_TRY(m->d2h(best_obs, A.best_obs, 4 * (size_t)n_sets));
+    ORBX_TRY(m->d2h(&raised, flag, 4));
     if (best_desc) ORBX_TRY(m->d2h(best_desc, A.best_desc, 32 * (size_t)n_sets));
-    if (pending) ORBX_TRY(m->d2h(counts.data(), A.counts_out, 8 * (size_t)n_kf));
+    if (pending) ORBX_TRY(m->d2h(counts.data(), counts_out, 8 * (size_t)n_kf));
+    if (nd && nd->normal) ORBX_TRY(m->d2h(nd->normal, B.normal, 12 * (size_t)n_sets));
+    if (nd && nd->min_dist) ORBX_TRY(m->d2h(nd->min_dist, B.min_dist, 4 * (size_t)n_sets));
+    if (nd && nd->max_dist) ORBX_TRY(m->d2h(nd->max_dist, B.max_dist, 4 * (size_t)n_sets));
     ORBX_TRY(m->sync_and_deliver());
+    for (const auto &kv : kept) {
+        if (nd->normal) memcpy(nd->normal + 3 * (size_t)kv.first, kv.second.data(), 12);
+        if (nd->min_dist) nd->min_dist[kv.first] = kv.second[3];
+        if (nd->max_dist) nd->max_dist[kv.first] = kv.second[4];
+    }
     keyframe_release(kfs, n_kf);
     for (int k = 0; pending && k < n_kf; k++)
         if (kfs[k]->host_n() < 0) kfs[k]->adopt(counts[2 * (size_t)k], counts[2 * (size_t)k + 1]);
-    if (flag) { set_error("an observation index outside [0, N) of its key frame"); return ORBX_E_BAD_ARG; }
+    if (raised) { set_error("an observation index outside [0, N) of its key frame, or a reference octave outside its pyramid"); return ORBX_E_BAD_ARG; }
     return ORBX_OK;
 }
 
@@ -4052,6 +4113,29 @@ int orbx_keyframe_distinctive_descriptors_to_map(orbx_matcher *m, int n_kf, orbx
                                                  const int32_t *obs_kf, const int32_t *obs_idx, orbx_map *map, const int32_t *set_id, int32_t *best_obs) {
     if (!map) return ORBX_E_BAD_ARG;
     return keyframe_distinctive_impl(m, n_kf, kfs, n_sets, set_ptr, obs_kf, obs_idx, best_obs, nullptr, map, set_id);
+}
+
+// MapPoint::UpdateNormalAndDepth on resident key frames, flat / into the table / together with ComputeDistinctiveDescriptors (include/orbx.h)
+int orbx_keyframe_update_normal_and_depth(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const float *centers, const float *centers_right,
+                                          int n_sets, const int32_t *set_ptr, const int32_t *obs_kf, const int32_t *obs_idx, const int32_t *ref_obs,
+                                          const float *pos, float *normal, float *min_dist, float *max_dist) {
+    const NormalDepth nd = {centers, centers_right, ref_obs, pos, normal, min_dist, max_dist};
+    return keyframe_distinctive_impl(m, n_kf, kfs, n_sets, set_ptr, obs_kf, obs_idx, nullptr, nullptr, nullptr, nullptr, &nd, false);
+}
+int orbx_keyframe_update_normal_and_depth_to_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const float *centers,
+                                                 const float *centers_right, int n_sets, const int32_t *set_ptr, const int32_t *obs_kf,
+                                                 const int32_t *obs_idx, const int32_t *ref_obs, orbx_map *map, const int32_t *set_id, float *normal,
+                                                 float *min_dist, float *max_dist) {
+    if (!map) return ORBX_E_BAD_ARG;
+    const NormalDepth nd = {centers, centers_right, ref_obs, nullptr, normal, min_dist, max_dist};
+    return keyframe_distinctive_impl(m, n_kf, kfs, n_sets, set_ptr, obs_kf, obs_idx, nullptr, nullptr, map, set_id, &nd, false);
+}
+int orbx_keyframe_refresh_map_points_to_map(orbx_matcher *m, int n_kf, orbx_keyframe *const *kfs, const float *centers, const float *centers_right,
+                                            int n_sets, const int32_t *set_ptr, const int32_t *obs_kf, const int32_t *obs_idx,
+                                            const int32_t *ref_obs, orbx_map *map, const int32_t *set_id, int32_t *best_obs) {
+    if (!map) return ORBX_E_BAD_ARG;
+    const NormalDepth nd = {centers, centers_right, ref_obs, nullptr, nullptr, nullptr, nullptr};
+    return keyframe_distinctive_impl(m, n_kf, kfs, n_sets, set_ptr, obs_kf, obs_idx, best_obs, nullptr, map, set_id, &nd, true);
 }
 
 }  // extern "C"

@@ -262,8 +262,11 @@ class DeviceKeyFrame:
 class DeviceMap:
     """A device-resident table of map points (orbx_map, include/orbx.h): `capacity` slots of pos, normal, min_dist, max_dist and the 32-byte
     descriptor, addressed by ids in [0, capacity) that the caller assigns.  It belongs to no matcher: every ORBmatcher of its device may update and
-    read it, and the ...Map forms of the one-call searches take (map, ids) where the flat forms take the five arrays.  update() after SetWorldPos /
-    UpdateNormalAndDepth / a bundle adjustment's write-back / ComputeDistinctiveDescriptors, erase() at SetBadFlag.  The caller does not run
+    read it, and the ...Map forms of the one-call searches take (map, ids) where the flat forms take the five arrays.  What keeps it current:
+    ORBmatcher.RefreshMapPointsToMap writes the descriptor, the normal and both distance bounds of the points a LocalMapping step changed
+    (ComputeDistinctiveDescriptors + UpdateNormalAndDepth, computed on the device; DistinctiveDescriptorsKeyFramesToMap /
+    UpdateNormalAndDepthKeyFramesToMap are its halves); update() is left for SetWorldPos / a bundle adjustment's write-back and for a slot's first,
+    whole write; erase() at SetBadFlag.  The caller does not run
     update / erase concurrently with a call that reads the table (the reference's Map::mMutexMapUpdate).  close() (or garbage collection) frees it;
     no call that was handed the table may be running then."""
 
@@ -1337,6 +1340,54 @@ class ORBmatcher:
         best = np.full(n_sets, -1, np.int32)
         check(self._L.orbx_keyframe_distinctive_descriptors_to_map(self._h, len(kfs), self._kf_handles(kfs), n_sets, ptr(sp), ptr(ok), ptr(oi),
                                                                    map._h, ptr(si), ptr(best)), "orbx_keyframe_distinctive_descriptors_to_map")
+        return best
+
+    # ---- MapPoint::UpdateNormalAndDepth on resident key frames (orbx_keyframe_update_normal_and_depth*) ----
+    def _normal_depth_args(self, kfs, centers, centers_right, set_ptr, obs_kf, obs_idx, ref_obs):
+        sp, ok, oi, ro = _i32(set_ptr), _i32(obs_kf), _i32(obs_idx), _i32(ref_obs)
+        n_sets = len(sp) - 1
+        ce = _f32(np.asarray(centers).reshape(-1, 3))
+        cr = None if centers_right is None else _f32(np.asarray(centers_right).reshape(-1, 3))
+        assert n_sets >= 0 and len(ok) == len(oi) and len(ro) == n_sets and (n_sets == 0 or sp[-1] <= len(ok))
+        assert len(ce) == len(kfs) and (cr is None or len(cr) == len(kfs)), "one centre (and one right centre) per key frame"
+        return n_sets, sp, ok, oi, ro, ce, cr
+
+    def UpdateNormalAndDepthKeyFrames(self, kfs, centers, centers_right, set_ptr, obs_kf, obs_idx, ref_obs, pos):
+        """MapPoint::UpdateNormalAndDepth for a batch of map points over DistinctiveDescriptorsKeyFrames' observation lists
+        (orbx_keyframe_update_normal_and_depth): centers / centers_right [K, 3] = GetCameraCenter() / GetRightCameraCenter() (None without rigs),
+        ref_obs[s] = the position inside set s of the reference key frame's observation, pos [n_sets, 3] = mWorldPos.  Returns
+        (normal [n_sets, 3], min_dist, max_dist), the distances unscaled as the member leaves them; the rows of empty sets are zeros."""
+        n_sets, sp, ok, oi, ro, ce, cr = self._normal_depth_args(kfs, centers, centers_right, set_ptr, obs_kf, obs_idx, ref_obs)
+        P = _f32(np.asarray(pos).reshape(-1, 3))
+        assert len(P) == n_sets
+        normal, mn, mx = np.zeros((n_sets, 3), np.float32), np.zeros(n_sets, np.float32), np.zeros(n_sets, np.float32)
+        check(self._L.orbx_keyframe_update_normal_and_depth(self._h, len(kfs), self._kf_handles(kfs), ptr(ce), ptr(cr), n_sets, ptr(sp), ptr(ok), ptr(oi),
+                                                            ptr(ro), ptr(P), ptr(normal), ptr(mn), ptr(mx)), "orbx_keyframe_update_normal_and_depth")
+        return normal, mn, mx
+
+    def UpdateNormalAndDepthKeyFramesToMap(self, kfs, centers, centers_right, set_ptr, obs_kf, obs_idx, ref_obs, map: DeviceMap, set_id,
+                                           want_outputs: bool = False):
+        """The same with pos read from slot set_id[s] of the table and the results written into it (orbx_keyframe_update_normal_and_depth_to_map); an
+        empty set leaves its slot as it is.  Returns (normal, min_dist, max_dist) with want_outputs, None otherwise -- the host's copies go stale then."""
+        n_sets, sp, ok, oi, ro, ce, cr = self._normal_depth_args(kfs, centers, centers_right, set_ptr, obs_kf, obs_idx, ref_obs)
+        si = _i32(set_id)
+        assert len(si) == n_sets
+        out = (np.zeros((n_sets, 3), np.float32), np.zeros(n_sets, np.float32), np.zeros(n_sets, np.float32)) if want_outputs else (None, None, None)
+        check(self._L.orbx_keyframe_update_normal_and_depth_to_map(self._h, len(kfs), self._kf_handles(kfs), ptr(ce), ptr(cr), n_sets, ptr(sp), ptr(ok),
+                                                                   ptr(oi), ptr(ro), map._h, ptr(si), ptr(out[0]), ptr(out[1]), ptr(out[2])),
+              "orbx_keyframe_update_normal_and_depth_to_map")
+        return out if want_outputs else None
+
+    def RefreshMapPointsToMap(self, kfs, centers, centers_right, set_ptr, obs_kf, obs_idx, ref_obs, map: DeviceMap, set_id):
+        """ComputeDistinctiveDescriptors and UpdateNormalAndDepth of a batch of map points in one call, straight into the table
+        (orbx_keyframe_refresh_map_points_to_map): DistinctiveDescriptorsKeyFramesToMap followed by UpdateNormalAndDepthKeyFramesToMap, bit for bit,
+        with one upload, one launch chain and one synchronisation.  Returns best_obs[n_sets]."""
+        n_sets, sp, ok, oi, ro, ce, cr = self._normal_depth_args(kfs, centers, centers_right, set_ptr, obs_kf, obs_idx, ref_obs)
+        si = _i32(set_id)
+        assert len(si) == n_sets
+        best = np.full(n_sets, -1, np.int32)
+        check(self._L.orbx_keyframe_refresh_map_points_to_map(self._h, len(kfs), self._kf_handles(kfs), ptr(ce), ptr(cr), n_sets, ptr(sp), ptr(ok), ptr(oi),
+                                                              ptr(ro), map._h, ptr(si), ptr(best)), "orbx_keyframe_refresh_map_points_to_map")
         return best
 
     # ---- SearchBySim3 (ORBmatcher.cc:1457-1674): two gate-less fuse searches + mutual agreement ----
