@@ -947,6 +947,100 @@ int orbx_keyframe_search_by_bow_fisheye(orbx_matcher *m, orbx_keyframe *kf1, con
 int orbx_keyframe_search_for_triangulation_fisheye(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
                                                    int check_orientation, const orbx_keyframe_kb8_gate *gate, int32_t *matches12);
 
+/* ---- LocalMapping::CreateNewMapPoints: triangulating a neighbour's matches on the two resident key frames (PARITY UNPINNED) ----
+ * What the member does with one matched pair (idx1, idx2) of the current key frame KF1 and a neighbour KF2 -- unproject, parallax test,
+ * GeometricTools::Triangulate, depth, reprojection, distance and scale-ratio tests -- runs on the device over the key frames' own rows: key points,
+ * octaves, mvuRight and mvScaleFactors never leave it.  PARITY UNPINNED: neither LocalMapping.cc nor GeometricTools.cc is among the units the oracle
+ * compiles and the SVD is Eigen-internal; the text below is ORB-SLAM3 v1.0's as restated for this project, and where a reference tree is at hand its
+ * text wins (DESIGN section 7p records the differences).  The member, per pair, as the device evaluates it:
+ *   kp1 = NLeft == -1 ? mvKeysUn[idx1] : idx1 < NLeft ? mvKeys[idx1] : mvKeysRight[idx1 - NLeft];  bRight1 = NLeft != -1 && idx1 >= NLeft   (kp2, bRight2 alike)
+ *   bStereo1 = !KF1.mpCamera2 && mvuRight[idx1] >= 0                                                                           (bStereo2 alike)
+ *   rig: (Tcw1, Ow1, camera1) = bRight1 ? (GetRightPose(), GetRightCameraCenter(), mpCamera2) : (GetPose(), GetCameraCenter(), mpCamera); same for 2
+ *   Rcw = Tcw.block<3,3>; Rwc = Rcw.transpose(); tcw = translation
+ *   xn1 = camera1->unprojectEig(kp1.pt); xn2 alike        Pinhole: ((x - cx) / fx, (y - cy) / fy, 1.f), true divisions; KannalaBrandt8: unproject, 1e-6
+ *   ray1 = Rwc1 * xn1; ray2 = Rwc2 * xn2
+ *   cosParallaxRays = ray1.dot(ray2) / (ray1.norm() * ray2.norm());  cosParallaxStereo = cosParallaxRays + 1       (no stereo observation)
+ *   if (cosParallaxRays < cosParallaxStereo && cosParallaxRays > 0 && cosParallaxRays < (mbInertial ? 0.9996 : 0.9998))        compared in double
+ *        A.row(0) = xn1(0) * Tcw1.row(2) - Tcw1.row(0);  A.row(1) = xn1(1) * Tcw1.row(2) - Tcw1.row(1);  rows 2, 3 with xn2, Tcw2   (Tcw: 3 x 4)
+ *        x3Dh = JacobiSVD<Matrix4f>(A, ComputeFullV).matrixV().col(3);  if (x3Dh(3) == 0) continue;  x3D = x3Dh.head(3) / x3Dh(3)
+ *   else continue                                                                                          "no stereo and very low parallax"
+ *   z1 = Rcw1.row(2).dot(x3D) + tcw1(2);  if (z1 <= 0) continue;   z2 alike;  if (z2 <= 0) continue
+ *   x1 = Rcw1.row(0).dot(x3D) + tcw1(0);  y1 alike;  uv1 = camera1->project((x1, y1, z1));  errX1 = uv1.x - kp1.pt.x;  errY1 alike
+ *   if ((errX1 * errX1 + errY1 * errY1) > 5.991 * mvLevelSigma2_1[kp1.octave]) continue           float sum, compared in double; then camera 2
+ *   dist1 = (x3D - Ow1).norm();  dist2 = (x3D - Ow2).norm();  if (dist1 == 0 || dist2 == 0) continue
+ *   if (mbFarPoints && (dist1 >= mThFarPoints || dist2 >= mThFarPoints)) continue
+ *   ratioDist = dist2 / dist1;  ratioOctave = KF1.mvScaleFactors[kp1.octave] / KF2.mvScaleFactors[kp2.octave];  ratioFactor = 1.5f * KF1.mfScaleFactor
+ *   if (ratioDist * ratioFactor < ratioOctave || ratioDist > ratioOctave * ratioFactor) continue
+ *   new MapPoint(x3D, ...)
+ * Every float operation is rounded on its own; matrix-vector products and dot() sum as ((0.f + a0 b0) + a1 b1) + a2 b2, norm() is the correctly
+ * rounded square root of that sum; a NaN takes whatever branch the comparisons, as written, give it.
+ * status: the first `continue` the member takes, numbered in the member's order.  A pair with bStereo1 || bStereo2 (rectified stereo / RGB-D: the
+ * member reads mvDepth, which a resident key frame does not hold) is reported as ORBX_NEWPT_STEREO_LEFT_TO_HOST and nothing is decided for it: the
+ * caller runs the member's text for that pair. */
+enum {
+    ORBX_NEWPT_OK = 0,
+    ORBX_NEWPT_NO_MATCH = 1,              /* the match entry is -1 */
+    ORBX_NEWPT_LOW_PARALLAX = 2,
+    ORBX_NEWPT_TRIANGULATE_FAILED = 3,    /* x3Dh(3) == 0 */
+    ORBX_NEWPT_BEHIND_1 = 4,
+    ORBX_NEWPT_BEHIND_2 = 5,
+    ORBX_NEWPT_REPROJ_1 = 6,
+    ORBX_NEWPT_REPROJ_2 = 7,
+    ORBX_NEWPT_ZERO_DIST = 8,
+    ORBX_NEWPT_FAR = 9,
+    ORBX_NEWPT_SCALE_RATIO = 10,
+    ORBX_NEWPT_STEREO_LEFT_TO_HOST = 11
+};
+/* One Pinhole camera of the pair: Rcw / tcw of GetPose(), Ow = GetCameraCenter(), fx, fy, cx, cy.  A rig gives two orbx_fisheye_view per key frame
+ * instead, left then right: R / t of GetPose() / GetRightPose(), twc = GetCameraCenter() / GetRightCameraCenter(), params of mpCamera / mpCamera2. */
+typedef struct orbx_new_points_view {
+    float Rcw[9], tcw[3], Ow[3];
+    float fx, fy, cx, cy;
+} orbx_new_points_view;
+/* What is left of the member's state: ratio_factor = 1.5f * mpCurrentKeyFrame->mfScaleFactor (the caller's product), mbInertial, mbFarPoints,
+ * mThFarPoints and the two key frames' mvLevelSigma2 [nlevels_k = key frame k's] -- sent, not derived from the mvInvLevelSigma2 the key frames keep,
+ * for the reason given at orbx_keyframe_gate. */
+typedef struct orbx_new_points_params {
+    float ratio_factor;
+    int inertial;
+    int far_points;
+    float th_far_points;
+    int nlevels_1, nlevels_2;
+    const float *level_sigma2_1, *level_sigma2_2;
+} orbx_new_points_params;
+/* orbx_keyframe_triangulate_pairs[_fisheye]: the member's loop body for n_pairs pairs the host knows, idx1[p] in [0, N1) and idx2[p] in [-1, N2) in
+ *   the reference's feature numbering (-1: ORBX_NEWPT_NO_MATCH).  status [n_pairs] (uint8, ORBX_NEWPT_*) and pos [n_pairs][3]: row p of pos is written
+ *   where status[p] == ORBX_NEWPT_OK and keeps the caller's values otherwise; *n_accepted (may be NULL) = the number of such rows.  One upload run (the
+ *   two index arrays, the two level tables, one record), one k_new_points launch, one download run, one synchronisation.  Counts that are still on the
+ *   device stay there: an index is checked against the capacity meanwhile and against N by the kernel, and the counts come home with the results.
+ * orbx_keyframe_search_and_triangulate[_fisheye]: orbx_keyframe_search_for_triangulation[_fisheye] with the same arguments, and k_new_points launched
+ *   behind it on the match row where it lies on the device: matches12 [N1] and the return value are that call's, pos [N1][3] / status [N1] /
+ *   *n_accepted as above with pair p = (p, matches12[p]).  One launch more than the search, no synchronisation more; the three results lie side by
+ *   side in the arena and come home in the search's download run; the upload run grows by the record and by each level table the search does not
+ *   send itself (Pinhole: level_sigma2_1; a rig with coarse: both).
+ * Left to the caller per neighbour, as scalar work: the baseline / median-depth test, bCoarse, the skip flags, building MapPoints from the accepted
+ * rows -- whose positions then go into the table through orbx_map_update, 12 bytes per new point.
+ * Refusals, ORBX_E_BAD_ARG before anything is enqueued or a transfer counter moves: a NULL argument (n_accepted and, with n_pairs = 0, the arrays
+ * excepted), the other kind of key frame, a key frame of another device, nlevels_k other than key frame k's, a NULL level table, n_pairs < 0, an
+ * index outside its range, and whatever the search refuses.  Found by the kernel -- an index outside [0, N) behind pending counts, a key point whose
+ * octave is outside its pyramid: no address is formed from it, a flag comes home, the call returns ORBX_E_BAD_ARG and NONE of the caller's arrays
+ * is written.  n_pairs = 0: ORBX_OK, nothing enqueued.  Not covered: stereo pairs (above), a `_to_map` form (it would reserve slots before the
+ * outcome is known). */
+int orbx_keyframe_triangulate_pairs(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const orbx_new_points_view *view1,
+                                    const orbx_new_points_view *view2, const orbx_new_points_params *par, int n_pairs, const int32_t *idx1,
+                                    const int32_t *idx2, float *pos, uint8_t *status, int *n_accepted);
+int orbx_keyframe_triangulate_pairs_fisheye(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const orbx_fisheye_view *views1,
+                                            const orbx_fisheye_view *views2, const orbx_new_points_params *par, int n_pairs, const int32_t *idx1,
+                                            const int32_t *idx2, float *pos, uint8_t *status, int *n_accepted);
+int orbx_keyframe_search_and_triangulate(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                         int check_orientation, const orbx_keyframe_gate *gate, const orbx_new_points_view *view1,
+                                         const orbx_new_points_view *view2, const orbx_new_points_params *par, int32_t *matches12, float *pos,
+                                         uint8_t *status, int *n_accepted);
+int orbx_keyframe_search_and_triangulate_fisheye(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                                 int check_orientation, const orbx_keyframe_kb8_gate *gate, const orbx_fisheye_view *views1,
+                                                 const orbx_fisheye_view *views2, const orbx_new_points_params *par, int32_t *matches12, float *pos,
+                                                 uint8_t *status, int *n_accepted);
+
 /* ---- LoopClosing's Sim3 projection searches on resident key frames (monocular / rectified key frames, Pinhole; a fisheye key frame is refused by
  * this pair and served by the _fisheye pair below it) ----
  * The three matcher calls LoopClosing makes with a Sim3 share their projection gates (ORBmatcher.cc:452-487, :569-604, :1369-1399); the two calls below

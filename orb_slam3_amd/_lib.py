@@ -143,6 +143,24 @@ class KeyFrameKb8Gate(C.Structure):
                 ("R12", C.c_float * 36), ("t12", C.c_float * 12), ("coarse", C.c_int)]
 
 
+class NewPointsView(C.Structure):
+    """orbx_new_points_view: one Pinhole camera of a CreateNewMapPoints pair -- GetPose() as Rcw (row-major) and tcw, GetCameraCenter(), fx, fy, cx, cy."""
+    _fields_ = [("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float)]
+
+
+class NewPointsParams(C.Structure):
+    """orbx_new_points_params: ratio_factor = 1.5f * mfScaleFactor, mbInertial, mbFarPoints, mThFarPoints and both key frames' mvLevelSigma2."""
+    _fields_ = [("ratio_factor", C.c_float), ("inertial", C.c_int), ("far_points", C.c_int), ("th_far_points", C.c_float), ("nlevels_1", C.c_int),
+                ("nlevels_2", C.c_int), ("level_sigma2_1", C.c_void_p), ("level_sigma2_2", C.c_void_p)]
+
+
+# orbx.h's ORBX_NEWPT_* enum: the first `continue` LocalMapping::CreateNewMapPoints takes for a pair
+NEWPT_STATUS = ("OK", "NO_MATCH", "LOW_PARALLAX", "TRIANGULATE_FAILED", "BEHIND_1", "BEHIND_2", "REPROJ_1", "REPROJ_2", "ZERO_DIST", "FAR", "SCALE_RATIO",
+                "STEREO_LEFT_TO_HOST")
+(NEWPT_OK, NEWPT_NO_MATCH, NEWPT_LOW_PARALLAX, NEWPT_TRIANGULATE_FAILED, NEWPT_BEHIND_1, NEWPT_BEHIND_2, NEWPT_REPROJ_1, NEWPT_REPROJ_2, NEWPT_ZERO_DIST,
+ NEWPT_FAR, NEWPT_SCALE_RATIO, NEWPT_STEREO_LEFT_TO_HOST) = range(12)
+
 PAIR_PREDICATE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
 _lib = None
@@ -190,6 +208,8 @@ SYMBOLS = [
     "orbx_frame_track_last_frame_map", "orbx_frame_search_by_projection_keyframe_map",
     "orbx_frame_track_last_frame_fisheye_map", "orbx_frame_search_by_projection_keyframe_fisheye_map",
     "orbx_keyframe_update_normal_and_depth", "orbx_keyframe_update_normal_and_depth_to_map", "orbx_keyframe_refresh_map_points_to_map",
+    "orbx_keyframe_triangulate_pairs", "orbx_keyframe_triangulate_pairs_fisheye", "orbx_keyframe_search_and_triangulate",
+    "orbx_keyframe_search_and_triangulate_fisheye",
 ]
 
 
@@ -352,6 +372,13 @@ def lib() -> C.CDLL:
     L.orbx_keyframe_update_normal_and_depth.argtypes = [vp, i32, C.POINTER(vp), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbx_keyframe_update_normal_and_depth_to_map.argtypes = [vp, i32, C.POINTER(vp), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbx_keyframe_refresh_map_points_to_map.argtypes = [vp, i32, C.POINTER(vp), vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.orbx_keyframe_triangulate_pairs.argtypes = [vp, vp, vp, C.POINTER(NewPointsView), C.POINTER(NewPointsView), C.POINTER(NewPointsParams), i32, vp, vp,
+                                                  vp, vp, C.POINTER(i32)]
+    L.orbx_keyframe_triangulate_pairs_fisheye.argtypes = [vp, vp, vp, vp, vp, C.POINTER(NewPointsParams), i32, vp, vp, vp, vp, C.POINTER(i32)]
+    L.orbx_keyframe_search_and_triangulate.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(KeyFrameGate), C.POINTER(NewPointsView), C.POINTER(NewPointsView),
+                                                       C.POINTER(NewPointsParams), vp, vp, vp, C.POINTER(i32)]
+    L.orbx_keyframe_search_and_triangulate_fisheye.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(KeyFrameKb8Gate), vp, vp, C.POINTER(NewPointsParams), vp,
+                                                               vp, vp, C.POINTER(i32)]
     L.orbx_frame_track_last_frame_map.argtypes = [vp, vp, vp, vp, C.POINTER(Camera), C.POINTER(FramePose), vp, i32, vp, vp, f32, i32, i32, vp, vp, vp, vp]
     L.orbx_frame_search_by_projection_keyframe_map.argtypes = [vp, vp, vp, C.POINTER(Camera), C.POINTER(FramePose), f32, vp, vp, i32, vp, f32, f32, i32,
                                                                vp, vp, vp, vp]

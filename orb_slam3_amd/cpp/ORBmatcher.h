@@ -519,6 +519,67 @@ public:
         for (int i = 0; i < n1; i++) if (m12[i] >= 0) vMatchedPairs.emplace_back((size_t)i, (size_t)m12[i]);  // :1138-1143
         return r;
     }
+    // ---- LocalMapping::CreateNewMapPoints' triangulation on the two resident key frames (include/orbx.h restates the member; PARITY UNPINNED).
+    // TriangulatePairs: the loop body for the pairs the caller names (orbx_keyframe_triangulate_pairs[_fisheye]; the kind is the view type's).  pos
+    // ([n][3]) is resized and only the rows of accepted pairs are written; status [n] = ORBX_NEWPT_*.  Returns the number of accepted pairs.
+    int TriangulatePairs(DeviceKeyFrame &KF1, DeviceKeyFrame &KF2, const orbx_new_points_view &view1, const orbx_new_points_view &view2,
+                         const orbx_new_points_params &par, const std::vector<int32_t> &idx1, const std::vector<int32_t> &idx2, std::vector<float> &pos,
+                         std::vector<uint8_t> &status) {
+        const size_t n = NewPointsPairs(idx1, idx2, pos, status);
+        int accepted = 0;
+        const int r = orbx_keyframe_triangulate_pairs(m_, KF1.handle(), KF2.handle(), &view1, &view2, &par, (int)n, idx1.data(), idx2.data(), pos.data(),
+                                                      status.data(), &accepted);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_triangulate_pairs: ") + orbx_status_string(r) + " " + orbx_last_error());
+        return accepted;
+    }
+    int TriangulatePairs(DeviceKeyFrame &KF1, DeviceKeyFrame &KF2, const orbx_fisheye_view views1[2], const orbx_fisheye_view views2[2],
+                         const orbx_new_points_params &par, const std::vector<int32_t> &idx1, const std::vector<int32_t> &idx2, std::vector<float> &pos,
+                         std::vector<uint8_t> &status) {
+        const size_t n = NewPointsPairs(idx1, idx2, pos, status);
+        int accepted = 0;
+        const int r = orbx_keyframe_triangulate_pairs_fisheye(m_, KF1.handle(), KF2.handle(), views1, views2, &par, (int)n, idx1.data(), idx2.data(),
+                                                              pos.data(), status.data(), &accepted);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_triangulate_pairs_fisheye: ") + orbx_status_string(r) + " " + orbx_last_error());
+        return accepted;
+    }
+    // SearchAndTriangulate: SearchForTriangulation(KF1, KF2, ...) above and TriangulatePairs on its matches in ONE call
+    // (orbx_keyframe_search_and_triangulate[_fisheye]): one launch more than the search, one synchronisation.  vMatchedPairs as the search fills it;
+    // pos [N1][3] / status [N1] are indexed by KF1's feature.  Returns the number of matches; nAccepted the number of ORBX_NEWPT_OK rows.
+    int SearchAndTriangulate(DeviceKeyFrame &KF1, DeviceKeyFrame &KF2, const std::vector<uint8_t> &skip1, const std::vector<uint8_t> &skip2,
+                             const orbx_keyframe_gate &gate, const orbx_new_points_view &view1, const orbx_new_points_view &view2,
+                             const orbx_new_points_params &par, std::vector<std::pair<size_t, size_t>> &vMatchedPairs, std::vector<float> &pos,
+                             std::vector<uint8_t> &status, int &nAccepted) {
+        const int n1 = KF1.count();
+        std::vector<int32_t> m12((size_t)std::max(n1, 1), -1);
+        pos.resize(3 * (size_t)std::max(n1, 1)); status.assign((size_t)std::max(n1, 1), (uint8_t)ORBX_NEWPT_NO_MATCH);
+        const int r = orbx_keyframe_search_and_triangulate(m_, KF1.handle(), KF2.handle(), skip1.empty() ? nullptr : skip1.data(),
+                                                           skip2.empty() ? nullptr : skip2.data(), mbCheckOrientation ? 1 : 0, &gate, &view1, &view2, &par,
+                                                           m12.data(), pos.data(), status.data(), &nAccepted);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_search_and_triangulate: ") + orbx_status_string(r) + " " + orbx_last_error());
+        vMatchedPairs.clear();
+        for (int i = 0; i < n1; i++) if (m12[i] >= 0) vMatchedPairs.emplace_back((size_t)i, (size_t)m12[i]);  // :1138-1143
+        return r;
+    }
+    int SearchAndTriangulate(DeviceKeyFrame &KF1, DeviceKeyFrame &KF2, const std::vector<uint8_t> &skip1, const std::vector<uint8_t> &skip2,
+                             const orbx_keyframe_kb8_gate &gate, const orbx_fisheye_view views1[2], const orbx_fisheye_view views2[2],
+                             const orbx_new_points_params &par, std::vector<std::pair<size_t, size_t>> &vMatchedPairs, std::vector<float> &pos,
+                             std::vector<uint8_t> &status, int &nAccepted) {
+        const int n1 = KF1.count();
+        std::vector<int32_t> m12((size_t)std::max(n1, 1), -1);
+        pos.resize(3 * (size_t)std::max(n1, 1)); status.assign((size_t)std::max(n1, 1), (uint8_t)ORBX_NEWPT_NO_MATCH);
+        const int r = orbx_keyframe_search_and_triangulate_fisheye(m_, KF1.handle(), KF2.handle(), skip1.empty() ? nullptr : skip1.data(),
+                                                                   skip2.empty() ? nullptr : skip2.data(), mbCheckOrientation ? 1 : 0, &gate, views1, views2,
+                                                                   &par, m12.data(), pos.data(), status.data(), &nAccepted);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_search_and_triangulate_fisheye: ") + orbx_status_string(r) + " " + orbx_last_error());
+        vMatchedPairs.clear();
+        for (int i = 0; i < n1; i++) if (m12[i] >= 0) vMatchedPairs.emplace_back((size_t)i, (size_t)m12[i]);  // :1138-1143
+        return r;
+    }
+    static size_t NewPointsPairs(const std::vector<int32_t> &idx1, const std::vector<int32_t> &idx2, std::vector<float> &pos, std::vector<uint8_t> &status) {
+        if (idx1.size() != idx2.size()) throw std::invalid_argument("TriangulatePairs: one index of each key frame per pair");
+        pos.resize(3 * idx1.size()); status.assign(idx1.size(), (uint8_t)ORBX_NEWPT_NO_MATCH);
+        return idx1.size();
+    }
     // the kind of a list of resident key frames: all fisheye-stereo or none (a mixed list throws, as Fuse does)
     static bool allFisheye(const std::vector<DeviceKeyFrame *> &kfs, const char *who) {
         size_t n = 0;

@@ -287,6 +287,9 @@ __host__ __device__ inline void kb8_unproject(const float *p, float px, float py
 // Eigen/src/Jacobi/Jacobi.h) restated from the published source: scaling by the largest coefficient, sweeps over (p, q), real_2x2_jacobi_svd, rotations
 // applied in Eigen's operation order, singular values sorted with column swaps.  PARITY UNPINNED: Eigen is not vendored by the reference and absent from
 // this image; what the gate does with the result are threshold tests, which a last-bit difference moves only at a boundary.
+// SWAP_V: the sort swaps V's columns with it, as Eigen does, and out = V.col(3) -- the same bits; the default picks the column by its number at the
+// end, which in a kernel that holds V in registers the compiler turns into an indexed read of a copy of V in LDS (k_new_points asks for SWAP_V).
+template <bool SWAP_V = false>
 __host__ __device__ inline void eigen_jacobi_svd4_v3(const float (*A)[4], float *out) {
     const float fmin_ = 1.17549435e-38f, eps2 = 2.f * 1.1920929e-07f;
     float W[4][4], V[4][4];
@@ -352,7 +355,17 @@ __host__ __device__ inline void eigen_jacobi_svd4_v3(const float (*A)[4], float 
         stop = stop || best == 0.f;
 #pragma unroll
         for (int j = i + 1; j < 4; j++)
-            if (!stop && pos == j) { const float ts = sv[i]; sv[i] = sv[j]; sv[j] = ts; const int tc = col[i]; col[i] = col[j]; col[j] = tc; }
+            if (!stop && pos == j) {
+                const float ts = sv[i]; sv[i] = sv[j]; sv[j] = ts; const int tc = col[i]; col[i] = col[j]; col[j] = tc;
+                if (SWAP_V) {
+#pragma unroll
+                    for (int r = 0; r < 4; r++) { const float tv = V[r][i]; V[r][i] = V[r][j]; V[r][j] = tv; }
+                }
+            }
+    }
+    if (SWAP_V) {
+        out[0] = V[0][3]; out[1] = V[1][3]; out[2] = V[2][3]; out[3] = V[3][3];
+        return;
     }
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -415,6 +428,31 @@ __host__ __device__ inline Kb8Triangulation kb8_triangulate_matches(const float 
 __host__ __device__ inline bool kb8_epipolar_constrain(const float *cam1, const float *cam2, float x1, float y1, float x2, float y2, const float *R12,
                                                        const float *t12, float sigmaLevel, float unc) {
     return kb8_triangulate_matches(cam1, cam2, x1, y1, x2, y2, R12, t12, sigmaLevel, unc).value > 0.0001f;
+}
+
+// Pinhole::unprojectEig (CameraModels/Pinhole.cpp): the ray ((x - cx) / fx, (y - cy) / fy, 1.f), true divisions
+__host__ __device__ inline void pinhole_unproject(float fx, float fy, float cx, float cy, float px, float py, float *rx, float *ry) {
+    *rx = (px - cx) / fx; *ry = (py - cy) / fy;
+}
+
+// GeometricTools::Triangulate (GeometricTools.cc): A.row(0) = x_c1(0) * Tc1w.row(2) - Tc1w.row(0), A.row(1) = x_c1(1) * Tc1w.row(2) - Tc1w.row(1), rows 2 and
+// 3 with x_c2 and Tc2w (T = [R | t], 3 x 4, R row-major); x3Dh = JacobiSVD<Matrix4f>(A, ComputeFullV).matrixV().col(3); false when x3Dh(3) == 0, else
+// x3D = x3Dh.head(3) / x3Dh(3), three divisions.  PARITY UNPINNED with the SVD (eigen_jacobi_svd4_v3).
+__host__ __device__ inline bool geometric_triangulate(float x1, float y1, const float *R1, const float *t1, float x2, float y2, const float *R2, const float *t2,
+                                                      float *x3D) {
+    float A[4][4];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const float a0 = j < 3 ? R1[j] : t1[0], a1 = j < 3 ? R1[3 + j] : t1[1], a2 = j < 3 ? R1[6 + j] : t1[2];
+        const float b0 = j < 3 ? R2[j] : t2[0], b1 = j < 3 ? R2[3 + j] : t2[1], b2 = j < 3 ? R2[6 + j] : t2[2];
+        A[0][j] = x1 * a2 - a0; A[1][j] = y1 * a2 - a1;
+        A[2][j] = x2 * b2 - b0; A[3][j] = y2 * b2 - b1;
+    }
+    float xh[4];
+    eigen_jacobi_svd4_v3<true>(A, xh);
+    if (xh[3] == 0.f) return false;
+    x3D[0] = xh[0] / xh[3]; x3D[1] = xh[1] / xh[3]; x3D[2] = xh[2] / xh[3];
+    return true;
 }
 
 // Frame::isInFrustumChecks (Frame.cc:1168-1240), the gates in the reference's order through the shared helpers:

@@ -4068,4 +4068,132 @@ __global__ __launch_bounds__(256) void k_tri_kb8_stereo_init(const FisheyeStereo
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// k_new_points: what LocalMapping::CreateNewMapPoints does with one matched pair (LocalMapping.cc, the loop over vMatchedIndices, with
+// GeometricTools::Triangulate), for every pair of a call, on two RESIDENT key frames of one kind (KB8 = false: monocular / rectified, Pinhole; KB8 = true:
+// a fisheye-stereo rig, KannalaBrandt8, the camera of each side chosen by the feature's index).  PARITY UNPINNED: nothing compiles LocalMapping.cc, the
+// SVD is Eigen-internal.  include/orbx.h restates the member; the bit contract is DESIGN.md section 5's (every float operation rounded on its own, dot3's
+// order for every product and norm, comparisons with a double literal in double).
+//   query q        feature idx1[q] of key frame 1 (idx1 == NULL: feature q) against feature match[q] of key frame 2, both in the reference's numbering
+//                  (left then right); match[q] == -1: ORBX_NEWPT_NO_MATCH, before any address is formed from it
+//   index -> row   kf_observation_row's rule: row i below N_left (any index of a monocular key frame), row roff + (i - N_left) from there on, the
+//                  counts read here, on the device, clamped as orbx_keyframe::adopt clamps them
+//   flag           an index outside [0, N) of its key frame, a match entry below -1, an octave outside [0, nlevels) of its key frame: no address is
+//                  formed from it, nothing is written for the query and flag[0] is raised
+//   status[q]      the first `continue` the member takes, ORBX_NEWPT_*; pos[q] is written on ORBX_NEWPT_OK only
+//   stereo         a pair with mvuRight >= 0 on either side (Pinhole key frames that hold mvuRight): ORBX_NEWPT_STEREO_LEFT_TO_HOST, nothing decided
+// counts_out (flag + 4, where given): the counts of key frame 1, then 2, as read here.  A lane per query, streaming: no LDS, no scratch.
+// grid (ceil(n / 64)), block 64: a matched lane is a long dependent chain (two unprojections, the SVD, two projections) and the matches are scattered
+// over the features, so the queries are spread over as many waves as there are -- they fit the device many times over.
+// ---------------------------------------------------------------------------------------------------------
+struct NewPointsKf {
+    const orbx_keypoint *kps; const float *scale, *sigma2, *u_right;   // sigma2: mvLevelSigma2 (the call's arena); u_right NULL: no mvuRight
+    const int32_t *count;
+    int32_t roff, cap, nlevels, pad;
+};
+struct NewPoints {
+    FisheyeView view[4];     // [2 * key frame + right]: R = Rcw, t = tcw, twc = Ow; p = mvParameters (Pinhole: fx, fy, cx, cy; view[0] and view[2])
+    NewPointsKf kf[2];
+    const int32_t *idx1, *match;
+    float *pos; uint8_t *status; int32_t *flag;
+    int32_t n, inertial, far_points, counts_out;
+    float ratio_factor, th_far_points;
+};
+constexpr int kNewPointsBlock = 64;
+
+// feature i of key frame R (reference numbering) -> its row and camera; false: i is outside [0, N)
+template <bool KB8> __device__ __forceinline__ bool new_points_row(const NewPointsKf *R, int i, int *row, bool *right) {
+    const int32_t *cnt = gld(&R->count);
+    const int roff = gld(&R->roff), cap = gld(&R->cap);
+    int n;
+    *row = i; *right = false;
+    if (KB8) {
+        const int nl = min(max(gld(cnt), 0), roff), nr = min(max(gld(cnt + 1), 0), cap - roff);
+        n = nl + nr;
+        if (i >= nl) { *row = roff + (i - nl); *right = true; }
+    } else {
+        n = min(max(gld(cnt), 0), cap);
+    }
+    return (unsigned)i < (unsigned)n;
+}
+
+template <bool KB8>
+__global__ __launch_bounds__(kNewPointsBlock) void k_new_points(const NewPoints *__restrict__ Tp) {
+    const NewPoints &T = *Tp;
+    const int q = blockIdx.x * kNewPointsBlock + threadIdx.x;
+    if (q < 2 && gld(&T.counts_out)) {
+        const int32_t *cnt = gld(&T.kf[q].count);
+        int32_t *flag = gld(&T.flag);
+        gst(flag + 4 + 2 * q, gld(cnt));
+        gst(flag + 5 + 2 * q, KB8 ? gld(cnt + 1) : 0);
+    }
+    if (q >= gld(&T.n)) return;
+    const int32_t *idx1 = gld(&T.idx1);
+    const int i2 = gld(gld(&T.match) + q), i1 = idx1 ? gld(idx1 + q) : q;
+    uint8_t *status = gld(&T.status) + q;
+    if (i2 == -1) { gst(status, (uint8_t)ORBX_NEWPT_NO_MATCH); return; }
+    int row1, row2;
+    bool right1, right2;
+    const bool in1 = new_points_row<KB8>(&T.kf[0], i1, &row1, &right1), in2 = new_points_row<KB8>(&T.kf[1], i2, &row2, &right2);
+    if (!in1 || !in2) { gst(gld(&T.flag), 1); return; }
+    const orbx_keypoint *k1 = gld(&T.kf[0].kps) + row1, *k2 = gld(&T.kf[1].kps) + row2;
+    const float px1 = gld(&k1->x), py1 = gld(&k1->y), px2 = gld(&k2->x), py2 = gld(&k2->y);
+    const int oct1 = gld(&k1->octave), oct2 = gld(&k2->octave);
+    if ((unsigned)oct1 >= (unsigned)gld(&T.kf[0].nlevels) || (unsigned)oct2 >= (unsigned)gld(&T.kf[1].nlevels)) { gst(gld(&T.flag), 1); return; }
+    if (!KB8) {   // bStereo1 || bStereo2: the member's mvDepth branch, left to the caller
+        const float *ur1 = gld(&T.kf[0].u_right), *ur2 = gld(&T.kf[1].u_right);
+        const bool stereo1 = ur1 && gld(ur1 + row1) >= 0.f, stereo2 = ur2 && gld(ur2 + row2) >= 0.f;
+        if (stereo1 || stereo2) { gst(status, (uint8_t)ORBX_NEWPT_STEREO_LEFT_TO_HOST); return; }
+    }
+    // the level-indexed values of both sides, requested ahead of the arithmetic
+    const float sigma1 = gld(gld(&T.kf[0].sigma2) + oct1), sigma2 = gld(gld(&T.kf[1].sigma2) + oct2);
+    const float scale1 = gld(gld(&T.kf[0].scale) + oct1), scale2 = gld(gld(&T.kf[1].scale) + oct2);
+    const FisheyeView &V1 = T.view[right1 ? 1 : 0], &V2 = T.view[right2 ? 3 : 2];
+    float xn1x, xn1y, xn2x, xn2y;
+    if (KB8) {
+        kb8_unproject(V1.p, px1, py1, 1e-6f, &xn1x, &xn1y);
+        kb8_unproject(V2.p, px2, py2, 1e-6f, &xn2x, &xn2y);
+    } else {
+        pinhole_unproject(V1.p[0], V1.p[1], V1.p[2], V1.p[3], px1, py1, &xn1x, &xn1y);
+        pinhole_unproject(V2.p[0], V2.p[1], V2.p[2], V2.p[3], px2, py2, &xn2x, &xn2y);
+    }
+    // ray = Rwc xn, Rwc = Rcw.transpose()
+    const float *R1 = V1.R, *R2 = V2.R;
+    const float r10 = dot3(R1[0], R1[3], R1[6], xn1x, xn1y, 1.f), r11 = dot3(R1[1], R1[4], R1[7], xn1x, xn1y, 1.f), r12 = dot3(R1[2], R1[5], R1[8], xn1x, xn1y, 1.f);
+    const float r20 = dot3(R2[0], R2[3], R2[6], xn2x, xn2y, 1.f), r21 = dot3(R2[1], R2[4], R2[7], xn2x, xn2y, 1.f), r22 = dot3(R2[2], R2[5], R2[8], xn2x, xn2y, 1.f);
+    const float n1 = sqrtf(dot3(r10, r11, r12, r10, r11, r12)), n2 = sqrtf(dot3(r20, r21, r22, r20, r21, r22));
+    const float cosParallaxRays = __fdiv_rn(dot3(r10, r11, r12, r20, r21, r22), __fmul_rn(n1, n2));
+    const float cosParallaxStereo = __fadd_rn(cosParallaxRays, 1.f);   // no stereo observation on either side
+    const double lim = gld(&T.inertial) ? 0.9996 : 0.9998;
+    if (!(cosParallaxRays < cosParallaxStereo && cosParallaxRays > 0.f && (double)cosParallaxRays < lim)) { gst(status, (uint8_t)ORBX_NEWPT_LOW_PARALLAX); return; }
+    float X[3];
+    if (!geometric_triangulate(xn1x, xn1y, R1, V1.t, xn2x, xn2y, R2, V2.t, X)) { gst(status, (uint8_t)ORBX_NEWPT_TRIANGULATE_FAILED); return; }
+    const float z1 = __fadd_rn(dot3(R1[6], R1[7], R1[8], X[0], X[1], X[2]), V1.t[2]);
+    if (z1 <= 0.f) { gst(status, (uint8_t)ORBX_NEWPT_BEHIND_1); return; }
+    const float z2 = __fadd_rn(dot3(R2[6], R2[7], R2[8], X[0], X[1], X[2]), V2.t[2]);
+    if (z2 <= 0.f) { gst(status, (uint8_t)ORBX_NEWPT_BEHIND_2); return; }
+    float Pc[3], u, v;
+    Pc[0] = __fadd_rn(dot3(R1[0], R1[1], R1[2], X[0], X[1], X[2]), V1.t[0]); Pc[1] = __fadd_rn(dot3(R1[3], R1[4], R1[5], X[0], X[1], X[2]), V1.t[1]); Pc[2] = z1;
+    if (KB8) kb8_project(V1.p, Pc[0], Pc[1], Pc[2], &u, &v);
+    else pinhole_project(V1.p[0], V1.p[1], V1.p[2], V1.p[3], Pc, &u, &v);
+    const float errX1 = __fsub_rn(u, px1), errY1 = __fsub_rn(v, py1);
+    if ((double)__fadd_rn(__fmul_rn(errX1, errX1), __fmul_rn(errY1, errY1)) > 5.991 * (double)sigma1) { gst(status, (uint8_t)ORBX_NEWPT_REPROJ_1); return; }
+    Pc[0] = __fadd_rn(dot3(R2[0], R2[1], R2[2], X[0], X[1], X[2]), V2.t[0]); Pc[1] = __fadd_rn(dot3(R2[3], R2[4], R2[5], X[0], X[1], X[2]), V2.t[1]); Pc[2] = z2;
+    if (KB8) kb8_project(V2.p, Pc[0], Pc[1], Pc[2], &u, &v);
+    else pinhole_project(V2.p[0], V2.p[1], V2.p[2], V2.p[3], Pc, &u, &v);
+    const float errX2 = __fsub_rn(u, px2), errY2 = __fsub_rn(v, py2);
+    if ((double)__fadd_rn(__fmul_rn(errX2, errX2), __fmul_rn(errY2, errY2)) > 5.991 * (double)sigma2) { gst(status, (uint8_t)ORBX_NEWPT_REPROJ_2); return; }
+    const float a0 = __fsub_rn(X[0], V1.twc[0]), a1 = __fsub_rn(X[1], V1.twc[1]), a2 = __fsub_rn(X[2], V1.twc[2]);
+    const float b0 = __fsub_rn(X[0], V2.twc[0]), b1 = __fsub_rn(X[1], V2.twc[1]), b2 = __fsub_rn(X[2], V2.twc[2]);
+    const float dist1 = sqrtf(dot3(a0, a1, a2, a0, a1, a2)), dist2 = sqrtf(dot3(b0, b1, b2, b0, b1, b2));
+    if (dist1 == 0.f || dist2 == 0.f) { gst(status, (uint8_t)ORBX_NEWPT_ZERO_DIST); return; }
+    const float th_far = gld(&T.th_far_points);
+    if (gld(&T.far_points) && (dist1 >= th_far || dist2 >= th_far)) { gst(status, (uint8_t)ORBX_NEWPT_FAR); return; }
+    const float ratioDist = __fdiv_rn(dist2, dist1), ratioOctave = __fdiv_rn(scale1, scale2), ratioFactor = gld(&T.ratio_factor);
+    if (__fmul_rn(ratioDist, ratioFactor) < ratioOctave || ratioDist > __fmul_rn(ratioOctave, ratioFactor)) { gst(status, (uint8_t)ORBX_NEWPT_SCALE_RATIO); return; }
+    float *pos = gld(&T.pos) + 3 * (size_t)q;
+    gst(pos, X[0]); gst(pos + 1, X[1]); gst(pos + 2, X[2]);
+    gst(status, (uint8_t)ORBX_NEWPT_OK);
+}
+
 }  // namespace orbx

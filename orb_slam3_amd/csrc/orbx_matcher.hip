@@ -3678,6 +3678,89 @@ struct BowSide : BowTarget {
 inline BowSide bow_side(const HandleRows &r, const BowArrays &b) { return BowSide{bow_target(r, b), std::min(r.feats(), b.voc->node_bound(b.levelsup))}; }
 inline BowSide bow_side(const orbx_keyframe *kf) { return bow_side(kf->view(), *kf->bow.load(std::memory_order_acquire)); }
 
+// LocalMapping::CreateNewMapPoints' triangulation (k_new_points, include/orbx.h) as one call sees it: alone over pairs the host names
+// (keyframe_triangulate_pairs) or behind SearchForTriangulation on the row it left on the device (run_bow_resident's optional argument).  Both carve the
+// same buffers through it: the level tables and the record among the call's uploads, pos / status / the flag (+ the counts as the kernel read them) side
+// by side among its downloads.  The results land here and reach the caller's arrays behind the synchronisation, and only if the flag stayed down.
+static_assert(sizeof(NewPoints) == 544, "the record a triangulating call uploads (tests/test_gpu_new_points.py states its size)");
+struct NewPointsCall {
+    NewPoints rec;                      // views, key-frame rows and parameters (new_points_prepare); the arena's addresses are filled in by stage()
+    const float *sigma2[2];             // the caller's mvLevelSigma2 tables
+    const float *dsig[2];
+    NewPoints *drec; float *dpos; uint8_t *dstatus; int32_t *dflag;
+    bool ran = false;
+    std::vector<int32_t> matches;       // the fused form's row
+    std::vector<float> pos; std::vector<uint8_t> status; int32_t flag[8];
+    // have1 / have2: the search sends that table itself (at d1 / d2)
+    void carve_up(Carve &C, bool have1, bool have2, const float *d1, const float *d2) {
+        dsig[0] = have1 ? d1 : C.up(sigma2[0], (size_t)rec.kf[0].nlevels);
+        dsig[1] = have2 ? d2 : C.up(sigma2[1], (size_t)rec.kf[1].nlevels);
+        drec = C.take<NewPoints>(1);
+    }
+    void carve_out(Carve &C, int n) { dpos = C.take<float>(3 * (size_t)n); dstatus = C.take<uint8_t>((size_t)n); dflag = C.take<int32_t>(8); }
+    int stage(orbx_matcher *m, const int32_t *didx1, const int32_t *dmatch, int n, bool counts) {
+        rec.kf[0].sigma2 = dsig[0]; rec.kf[1].sigma2 = dsig[1];
+        rec.idx1 = didx1; rec.match = dmatch; rec.pos = dpos; rec.status = dstatus; rec.flag = dflag; rec.n = n; rec.counts_out = counts ? 1 : 0;
+        ORBX_TRY(m->h2d(drec, &rec, sizeof(rec)));
+        ORBX_HIP(m->fill(dflag, 0, sizeof(flag)));
+        return ORBX_OK;
+    }
+    void launch(orbx_matcher *m, bool rig, int n) {
+        const dim3 grid((unsigned)((n + kNewPointsBlock - 1) / kNewPointsBlock)), block(kNewPointsBlock);
+        if (rig) hipLaunchKernelGGL(k_new_points<true>, grid, block, 0, m->exec(), (const NewPoints *)drec);
+        else hipLaunchKernelGGL(k_new_points<false>, grid, block, 0, m->exec(), (const NewPoints *)drec);
+        ran = true;
+    }
+    int fetch(orbx_matcher *m, int n) {
+        pos.resize(3 * (size_t)n); status.resize((size_t)n);
+        ORBX_TRY(m->d2h(pos.data(), dpos, 12 * (size_t)n));
+        ORBX_TRY(m->d2h(status.data(), dstatus, (size_t)n));
+        return m->d2h(flag, dflag, sizeof(flag));
+    }
+    // behind the synchronisation: status of every pair, pos of the accepted ones; a raised flag leaves the caller's arrays alone
+    int deliver(int n, float *out_pos, uint8_t *out_status, int *n_accepted) const {
+        if (ran && flag[0]) { set_error("an index outside [0, N) of its key frame, or a key point whose octave is outside its pyramid"); return ORBX_E_BAD_ARG; }
+        int accepted = 0;
+        for (int p = 0; p < n; p++) {
+            out_status[p] = ran ? status[p] : (uint8_t)ORBX_NEWPT_NO_MATCH;   // (a search that found a side empty launched nothing)
+            if (out_status[p] != ORBX_NEWPT_OK) continue;
+            memcpy(out_pos + 3 * (size_t)p, pos.data() + 3 * (size_t)p, 12);
+            accepted++;
+        }
+        if (n_accepted) *n_accepted = accepted;
+        return ORBX_OK;
+    }
+};
+
+// the checks both forms share and the host's part of the record; views: orbx_new_points_view (one per key frame) or, rig, orbx_fisheye_view [2] each
+int new_points_prepare(const orbx_matcher *m, bool rig, const orbx_keyframe *kf1, const orbx_keyframe *kf2, const void *views1, const void *views2,
+                       const orbx_new_points_params *par, NewPointsCall &T) {
+    if (!m || !kf1 || !kf2 || !views1 || !views2 || !par || !par->level_sigma2_1 || !par->level_sigma2_2) return ORBX_E_BAD_ARG;
+    const orbx_keyframe *kfs[2] = {kf1, kf2};
+    const void *views[2] = {views1, views2};
+    const int nlevels[2] = {par->nlevels_1, par->nlevels_2};
+    memset(&T.rec, 0, sizeof(T.rec));
+    for (int k = 0; k < 2; k++) {
+        if (kfs[k]->fisheye != rig || kfs[k]->device != m->device || nlevels[k] != kfs[k]->nlevels) return ORBX_E_BAD_ARG;
+        static_assert(sizeof(orbx_fisheye_view) == sizeof(FisheyeView), "orbx_fisheye_view is FisheyeView");
+        if (rig) {
+            memcpy(&T.rec.view[2 * k], views[k], 2 * sizeof(FisheyeView));
+        } else {
+            const orbx_new_points_view *v = static_cast<const orbx_new_points_view *>(views[k]);
+            FisheyeView &V = T.rec.view[2 * k];
+            memcpy(V.R, v->Rcw, sizeof(V.R)); memcpy(V.t, v->tcw, sizeof(V.t)); memcpy(V.twc, v->Ow, sizeof(V.twc));
+            V.p[0] = v->fx; V.p[1] = v->fy; V.p[2] = v->cx; V.p[3] = v->cy;
+        }
+        NewPointsKf &R = T.rec.kf[k];
+        R.kps = kfs[k]->kps; R.scale = kfs[k]->scale; R.u_right = kfs[k]->u_right; R.count = kfs[k]->count;
+        R.roff = kfs[k]->roff; R.cap = kfs[k]->cap; R.nlevels = kfs[k]->nlevels;
+    }
+    T.sigma2[0] = par->level_sigma2_1; T.sigma2[1] = par->level_sigma2_2;
+    T.rec.ratio_factor = par->ratio_factor; T.rec.inertial = par->inertial ? 1 : 0;
+    T.rec.far_points = par->far_points ? 1 : 0; T.rec.th_far_points = par->th_far_points;
+    return ORBX_OK;
+}
+
 // The driver of the resident BoW searches of both kinds of side.  Problem k: A[k] against B[k] in `mode` (BowProblem::mode: 0 / 3 rows indexed by B's
 // features, 1 / 2 by A's); flags_a[k] / flags_b[k] (arrays may be NULL, entries may be NULL = no feature is switched off) are `valid` flags when invert, else `skip`
 // flags, of A[k].n / B[k].n entries (the callers resolve N before they hand over flags).  The side the rows are indexed by is the same object in
@@ -3688,10 +3771,13 @@ inline BowSide bow_side(const orbx_keyframe *kf) { return bow_side(kf->view(), *
 // also switches every right-camera row off on both sides, ORBmatcher.cc:800-802, :820-822 -- roff is on the host, so this needs no count), and
 // k_bow_rig_rows hands rows and values back in feature numbering, with both counts of both sides.  kb8 (mode 2, rig): the KannalaBrandt8 gate of
 // k_tri_kb8_resident, which then takes k_replay_bow_batch's place; its level table sigma2_1 and the record ride up beside sigma2_2.
+// tri (mode 2, np = 1, A's N known): CreateNewMapPoints' triangulation of the row behind the chain (NewPointsCall) -- its record and the level tables the
+// gate does not send ride up beside the gate's, k_new_points reads the row where it lies, pos / status / the flag lie between the row and the counts and come home
+// in the same download run.  One launch more, nothing else changes; without it every statement here is the one it was.
 int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const BowSide *B, const uint8_t *const *flags_a, const uint8_t *const *flags_b,
                      bool invert, float nnratio, int check_orientation, const TriGate *gate, const float *sigma2_2, int nlevels, int32_t *match,
                      int match_stride, int32_t *nmatches, std::vector<int32_t> &counts, bool rig = false, const Kb8Gate *kb8 = nullptr,
-                     const float *sigma2_1 = nullptr) {
+                     const float *sigma2_1 = nullptr, NewPointsCall *tri = nullptr) {
     const bool to_b = mode == 0 || mode == 3;
     const BowSide &O = to_b ? B[0] : A[0];
     const int nrows = O.rows(), nfeat = O.feats();
@@ -3751,6 +3837,7 @@ int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const 
         }
         if (gate) dsig = C.up(sigma2_2, (size_t)nlevels);
         if (kb8) { dsig1 = C.up(sigma2_1, (size_t)nlevels); dK = C.take<Kb8Gate>(1); }
+        if (tri) tri->carve_up(C, kb8 != nullptr, gate != nullptr, dsig1, dsig);
         dP = C.take<BowProblem>(np);
         dS = C.take<BowPairSrc>(np);
         if (rig) dR = C.take<BowRigRows>(np);
@@ -3760,6 +3847,7 @@ int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const 
         dmatch = C.take<int32_t>((size_t)np * nrows);
         if (rig) dpc = C.take<int32_t>(2 * (size_t)np);
         dout = rig ? C.take<int32_t>((size_t)np * nfeat) : dmatch;
+        if (tri) tri->carve_out(C, nfeat);   // (between the row and the counts: one download run)
         dnm = C.take<int32_t>(np);
         dcnt = C.take<int32_t>(cnt_per * (size_t)np);
         dtaken = C.take<uint8_t>(tot_nb + 1);
@@ -3807,6 +3895,7 @@ int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const 
     ORBX_TRY(m->h2d(dP, probs.data(), sizeof(BowProblem) * (size_t)np));
     ORBX_TRY(m->h2d(dS, srcs.data(), sizeof(BowPairSrc) * (size_t)np));
     if (rig) ORBX_TRY(m->h2d(dR, rigs.data(), sizeof(BowRigRows) * (size_t)np));
+    if (tri) ORBX_TRY(tri->stage(m, nullptr, dout, nfeat, false));   // (the row in feature numbering: a rig's is k_bow_rig_rows')
     ORBX_HIP(m->fill(dmatch, 0xff, 4 * (size_t)np * nrows));
     ORBX_HIP(m->fill(dtaken, 0, (size_t)((const uint8_t *)(dhist + (size_t)np * (ORBX_HISTO_LENGTH + 2)) - dtaken)));   // vbMatched2, (padding,) histograms + counters
     hipLaunchKernelGGL(k_bow_pair_resident, dim3((unsigned)((max_bound + 255) / 256), (unsigned)np), dim3(256), 0, m->exec(), dP, (const BowPairSrc *)dS);
@@ -3814,6 +3903,7 @@ int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const 
     else hipLaunchKernelGGL(k_replay_bow_batch, dim3((unsigned)((max_bound + 3) / 4), (unsigned)np), dim3(256), 0, m->exec(), (const BowProblem *)dP);
     hipLaunchKernelGGL(k_replay_bow_finish_batch, dim3((unsigned)np), dim3(64), 0, m->exec(), (const BowProblem *)dP);
     if (rig) hipLaunchKernelGGL(k_bow_rig_rows, dim3((unsigned)((std::max(nfeat, 1) + 255) / 256), (unsigned)np), dim3(256), 0, m->exec(), (const BowRigRows *)dR);
+    if (tri) tri->launch(m, rig, nfeat);
     ORBX_HIP(hipGetLastError());
     std::vector<int32_t> land;
     PendingRows down{m, land, O.n < 0};   // N comes back with the results (the sides' counts, below)
@@ -3822,6 +3912,7 @@ int run_bow_resident(orbx_matcher *m, int mode, int np, const BowSide *A, const 
     std::vector<int32_t> got(cnt_per * (size_t)np, 0);
     ORBX_TRY(m->d2h(nmatches, dnm, 4 * (size_t)np));
     ORBX_TRY(m->d2h(got.data(), dcnt, 4 * got.size()));
+    if (tri) ORBX_TRY(tri->fetch(m, nfeat));
     ORBX_TRY(m->sync_and_deliver());
     counts.assign(4 * (size_t)np, 0);
     for (size_t k = 0; k < (size_t)np; k++)
@@ -4232,7 +4323,7 @@ int keyframe_search_by_bow(orbx_matcher *m, bool rig, orbx_keyframe *kf1, const 
 // (K; NULL = bCoarse: no gate at all, :1026, :1036).  Keypoints and scale factors are the key frames' own rows; the level tables ride up beside the record.
 int keyframe_search_for_triangulation(orbx_matcher *m, bool rig, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
                                       int check_orientation, TriGate *G, Kb8Gate *K, const float *sigma2_1, const float *sigma2_2, int nlevels,
-                                      int32_t *matches12) {
+                                      int32_t *matches12, NewPointsCall *tri = nullptr) {
     const orbx_vocabulary *voc = nullptr;
     int levelsup = 0;
     if (!keyframe_bow_ok(m, rig, kf1, &voc, &levelsup) || !keyframe_bow_ok(m, rig, kf2, &voc, &levelsup)) return ORBX_E_BAD_ARG;
@@ -4242,6 +4333,7 @@ int keyframe_search_for_triangulation(orbx_matcher *m, bool rig, orbx_keyframe *
     if (rc == ORBX_OK && skip2 && n2 < 0) rc = orbx_keyframe_count(kf2, &n2);
     if (rc != ORBX_OK) return rc;
     if (n1 > 0 && !matches12) return ORBX_E_BAD_ARG;
+    if (tri) { tri->matches.resize((size_t)n1); matches12 = tri->matches.data(); }   // (the caller's row is written with pos and status, or not at all)
     for (int i = 0; i < n1; i++) matches12[i] = -1;
     if (n1 == 0 || n2 == 0) return 0;
     ORBX_HIP(hipSetDevice(m->device));
@@ -4252,11 +4344,92 @@ int keyframe_search_for_triangulation(orbx_matcher *m, bool rig, orbx_keyframe *
     std::vector<int32_t> counts;
     int32_t nm = 0;
     const int r = run_bow_resident(m, 2, 1, &A, &B, &skip1, &skip2, false, 0.f, check_orientation, G, sigma2_2, nlevels, matches12, n1, &nm, counts, rig, K,
-                                   sigma2_1);
+                                   sigma2_1, tri);
     if (r != ORBX_OK) return r;
     keyframe_bow_release(kf1); keyframe_bow_release(kf2);
     keyframe_adopt(kf2, &counts[2]);
     return nm;
+}
+
+// The two public searches' gates, each built once for the plain call and the one that triangulates behind it (tri).
+int search_for_triangulation_pinhole(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                     int check_orientation, const orbx_keyframe_gate *gate, int32_t *matches12, NewPointsCall *tri) {
+    if (!m || !gate || !gate->level_sigma2_2) return ORBX_E_BAD_ARG;
+    TriGate G;
+    memset(&G, 0, sizeof(G));
+    G.enabled = 1; G.coarse = gate->coarse ? 1 : 0; G.strict = gate->strict_fp ? 1 : 0;
+    for (int i = 0; i < 9; i++) G.F[i] = gate->F12[i];
+    G.ex = gate->ep_x; G.ey = gate->ep_y;
+    return keyframe_search_for_triangulation(m, false, kf1, kf2, skip1, skip2, check_orientation, &G, nullptr, nullptr, gate->level_sigma2_2, gate->nlevels,
+                                             matches12, tri);
+}
+int search_for_triangulation_rig(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                 int check_orientation, const orbx_keyframe_kb8_gate *gate, int32_t *matches12, NewPointsCall *tri) {
+    if (!m || !gate) return ORBX_E_BAD_ARG;
+    if (gate->coarse)   // bCoarse: no gate at all for such key frames, plain mode 2
+        return keyframe_search_for_triangulation(m, true, kf1, kf2, skip1, skip2, check_orientation, nullptr, nullptr, nullptr, nullptr,
+                                                 kf2 ? kf2->nlevels : 0, matches12, tri);
+    if (!gate->level_sigma2_1 || !gate->level_sigma2_2) return ORBX_E_BAD_ARG;
+    TriGate G;
+    memset(&G, 0, sizeof(G));
+    G.enabled = 1; G.strict = 1;
+    Kb8Gate K;
+    memset(&K, 0, sizeof(K));
+    memcpy(K.cam[0], gate->cam1, sizeof(float) * 16);
+    memcpy(K.cam[2], gate->cam2, sizeof(float) * 16);
+    memcpy(K.R12, gate->R12, sizeof(K.R12));
+    memcpy(K.t12, gate->t12, sizeof(K.t12));
+    return keyframe_search_for_triangulation(m, true, kf1, kf2, skip1, skip2, check_orientation, &G, &K, gate->level_sigma2_1, gate->level_sigma2_2,
+                                             gate->nlevels, matches12, tri);
+}
+
+// orbx_keyframe_search_and_triangulate[_fisheye]: the search with k_new_points behind it (run_bow_resident's tri); gate: the kind's gate struct
+int keyframe_search_and_triangulate(orbx_matcher *m, bool rig, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                    int check_orientation, const void *gate, const void *views1, const void *views2, const orbx_new_points_params *par,
+                                    int32_t *matches12, float *pos, uint8_t *status, int *n_accepted) {
+    if (!matches12 || !pos || !status) return ORBX_E_BAD_ARG;
+    NewPointsCall T;
+    ORBX_TRY(new_points_prepare(m, rig, kf1, kf2, views1, views2, par, T));
+    const int nm = rig ? search_for_triangulation_rig(m, kf1, kf2, skip1, skip2, check_orientation, static_cast<const orbx_keyframe_kb8_gate *>(gate), matches12, &T)
+                       : search_for_triangulation_pinhole(m, kf1, kf2, skip1, skip2, check_orientation, static_cast<const orbx_keyframe_gate *>(gate), matches12, &T);
+    if (nm < 0) return nm;
+    const int n1 = (int)T.matches.size();
+    ORBX_TRY(T.deliver(n1, pos, status, n_accepted));
+    if (n1 > 0) memcpy(matches12, T.matches.data(), 4 * (size_t)n1);
+    return nm;
+}
+
+// orbx_keyframe_triangulate_pairs[_fisheye]: k_new_points over pairs the host names.  One upload run (idx1, idx2, the two level tables, the record), one
+// launch, one download run (pos, status, the flag and the counts as the kernel read them), one synchronisation.
+int keyframe_triangulate_pairs(orbx_matcher *m, bool rig, orbx_keyframe *kf1, orbx_keyframe *kf2, const void *views1, const void *views2,
+                               const orbx_new_points_params *par, int n_pairs, const int32_t *idx1, const int32_t *idx2, float *pos, uint8_t *status,
+                               int *n_accepted) {
+    NewPointsCall T;
+    ORBX_TRY(new_points_prepare(m, rig, kf1, kf2, views1, views2, par, T));
+    if (n_pairs < 0 || (n_pairs > 0 && (!idx1 || !idx2 || !pos || !status))) return ORBX_E_BAD_ARG;
+    const int b1 = kf1->rows_n(), b2 = kf2->rows_n();   // (counts pending: the capacity; the kernel checks against N)
+    for (int p = 0; p < n_pairs; p++)
+        if (idx1[p] < 0 || idx1[p] >= b1 || idx2[p] < -1 || idx2[p] >= b2) return ORBX_E_BAD_ARG;
+    if (n_pairs == 0) { if (n_accepted) *n_accepted = 0; return ORBX_OK; }
+    ORBX_HIP(hipSetDevice(m->device));
+    const int32_t *d1 = nullptr, *d2 = nullptr;
+    ORBX_TRY(m->carve([&](Carve &C) {
+        d1 = C.up(idx1, (size_t)n_pairs); d2 = C.up(idx2, (size_t)n_pairs);
+        T.carve_up(C, false, false, nullptr, nullptr);
+        T.carve_out(C, n_pairs);
+    }));
+    orbx_keyframe *kfs[2] = {kf1, kf2};
+    const bool pending = kf1->host_n() < 0 || kf2->host_n() < 0;
+    ORBX_TRY(T.stage(m, d1, d2, n_pairs, pending));
+    ORBX_TRY(keyframe_acquire(m, kfs, 2));
+    T.launch(m, rig, n_pairs);
+    ORBX_HIP(hipGetLastError());
+    ORBX_TRY(T.fetch(m, n_pairs));
+    ORBX_TRY(m->sync_and_deliver());
+    keyframe_release(kfs, 2);
+    for (int k = 0; pending && k < 2; k++)
+        if (kfs[k]->host_n() < 0) kfs[k]->adopt(T.flag[4 + 2 * k], T.flag[5 + 2 * k]);
+    return T.deliver(n_pairs, pos, status, n_accepted);
 }
 
 }  // namespace
@@ -4284,33 +4457,35 @@ int orbx_keyframe_search_by_bow_fisheye(orbx_matcher *m, orbx_keyframe *kf1, con
 
 int orbx_keyframe_search_for_triangulation(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
                                            int check_orientation, const orbx_keyframe_gate *gate, int32_t *matches12) {
-    if (!m || !gate || !gate->level_sigma2_2) return ORBX_E_BAD_ARG;
-    TriGate G;
-    memset(&G, 0, sizeof(G));
-    G.enabled = 1; G.coarse = gate->coarse ? 1 : 0; G.strict = gate->strict_fp ? 1 : 0;
-    for (int i = 0; i < 9; i++) G.F[i] = gate->F12[i];
-    G.ex = gate->ep_x; G.ey = gate->ep_y;
-    return keyframe_search_for_triangulation(m, false, kf1, kf2, skip1, skip2, check_orientation, &G, nullptr, nullptr, gate->level_sigma2_2, gate->nlevels,
-                                             matches12);
+    return search_for_triangulation_pinhole(m, kf1, kf2, skip1, skip2, check_orientation, gate, matches12, nullptr);
 }
 int orbx_keyframe_search_for_triangulation_fisheye(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
                                                    int check_orientation, const orbx_keyframe_kb8_gate *gate, int32_t *matches12) {
-    if (!m || !gate) return ORBX_E_BAD_ARG;
-    if (gate->coarse)   // bCoarse: no gate at all for such key frames, plain mode 2
-        return keyframe_search_for_triangulation(m, true, kf1, kf2, skip1, skip2, check_orientation, nullptr, nullptr, nullptr, nullptr,
-                                                 kf2 ? kf2->nlevels : 0, matches12);
-    if (!gate->level_sigma2_1 || !gate->level_sigma2_2) return ORBX_E_BAD_ARG;
-    TriGate G;
-    memset(&G, 0, sizeof(G));
-    G.enabled = 1; G.strict = 1;
-    Kb8Gate K;
-    memset(&K, 0, sizeof(K));
-    memcpy(K.cam[0], gate->cam1, sizeof(float) * 16);
-    memcpy(K.cam[2], gate->cam2, sizeof(float) * 16);
-    memcpy(K.R12, gate->R12, sizeof(K.R12));
-    memcpy(K.t12, gate->t12, sizeof(K.t12));
-    return keyframe_search_for_triangulation(m, true, kf1, kf2, skip1, skip2, check_orientation, &G, &K, gate->level_sigma2_1, gate->level_sigma2_2,
-                                             gate->nlevels, matches12);
+    return search_for_triangulation_rig(m, kf1, kf2, skip1, skip2, check_orientation, gate, matches12, nullptr);
+}
+
+// LocalMapping::CreateNewMapPoints' triangulation on resident key frames (include/orbx.h), over named pairs or behind the search
+int orbx_keyframe_triangulate_pairs(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const orbx_new_points_view *view1,
+                                    const orbx_new_points_view *view2, const orbx_new_points_params *par, int n_pairs, const int32_t *idx1,
+                                    const int32_t *idx2, float *pos, uint8_t *status, int *n_accepted) {
+    return keyframe_triangulate_pairs(m, false, kf1, kf2, view1, view2, par, n_pairs, idx1, idx2, pos, status, n_accepted);
+}
+int orbx_keyframe_triangulate_pairs_fisheye(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const orbx_fisheye_view *views1,
+                                            const orbx_fisheye_view *views2, const orbx_new_points_params *par, int n_pairs, const int32_t *idx1,
+                                            const int32_t *idx2, float *pos, uint8_t *status, int *n_accepted) {
+    return keyframe_triangulate_pairs(m, true, kf1, kf2, views1, views2, par, n_pairs, idx1, idx2, pos, status, n_accepted);
+}
+int orbx_keyframe_search_and_triangulate(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                         int check_orientation, const orbx_keyframe_gate *gate, const orbx_new_points_view *view1,
+                                         const orbx_new_points_view *view2, const orbx_new_points_params *par, int32_t *matches12, float *pos,
+                                         uint8_t *status, int *n_accepted) {
+    return keyframe_search_and_triangulate(m, false, kf1, kf2, skip1, skip2, check_orientation, gate, view1, view2, par, matches12, pos, status, n_accepted);
+}
+int orbx_keyframe_search_and_triangulate_fisheye(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                                 int check_orientation, const orbx_keyframe_kb8_gate *gate, const orbx_fisheye_view *views1,
+                                                 const orbx_fisheye_view *views2, const orbx_new_points_params *par, int32_t *matches12, float *pos,
+                                                 uint8_t *status, int *n_accepted) {
+    return keyframe_search_and_triangulate(m, true, kf1, kf2, skip1, skip2, check_orientation, gate, views1, views2, par, matches12, pos, status, n_accepted);
 }
 
 }  // extern "C"

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import KP_DTYPE, BowKeyFrame, FeatVec, FrameDesc, FuseQueries, KeyFrameGate, KeyFrameKb8Gate, PAIR_PREDICATE, PinholeGate, check, ptr
+from ._lib import KP_DTYPE, BowKeyFrame, FeatVec, FrameDesc, FuseQueries, KeyFrameGate, KeyFrameKb8Gate, NewPointsParams, NewPointsView, PAIR_PREDICATE, PinholeGate, check, ptr
 
 
 @dataclass
@@ -831,6 +831,96 @@ class ORBmatcher:
         n = check(self._L.orbx_keyframe_search_for_triangulation(self._h, kf1._h, kf2._h, ptr(s1), ptr(s2), int(self.mbCheckOrientation), C.byref(g),
                                                                  ptr(m12)), "orbx_keyframe_search_for_triangulation")
         return n, m12[:kf1.count()]
+
+    # ---- LocalMapping::CreateNewMapPoints' triangulation on resident key frames (include/orbx.h; PARITY UNPINNED) ----
+    @staticmethod
+    def _new_points_params(kf1, kf2, level_sigma2_1, level_sigma2_2, ratio_factor, inertial, far_points, th_far_points):
+        sg1, sg2 = _f32(level_sigma2_1), _f32(level_sigma2_2)
+        return (sg1, sg2), NewPointsParams(float(ratio_factor), int(bool(inertial)), int(bool(far_points)), float(th_far_points), len(sg1), len(sg2),
+                                           sg1.ctypes.data, sg2.ctypes.data)
+
+    @staticmethod
+    def _new_points_views(views1, views2, rig: bool):
+        """Pinhole: a view is (Rcw, tcw, Ow, fx, fy, cx, cy); a rig: (left, right) per key frame, each (R, t, twc, params8) as orbx_fisheye_view.
+        A caller that triangulates against the same poses again may pass what NewPointsViews returned: nothing is converted then."""
+        if isinstance(views1, NewPointsView) or (isinstance(views1, np.ndarray) and views1.dtype == np.float32 and views1.shape == (46,)):
+            return (views1, views2), ((ptr(views1), ptr(views2)) if rig else (C.byref(views1), C.byref(views2)))
+        if rig:
+            flat = [np.ascontiguousarray(np.concatenate([np.asarray(x, np.float32).ravel() for cam in v for x in cam])) for v in (views1, views2)]
+            assert all(len(f) == 46 for f in flat), "two orbx_fisheye_view per key frame"
+            return flat, (ptr(flat[0]), ptr(flat[1]))
+        vs = [NewPointsView((C.c_float * 9)(*[float(x) for x in np.asarray(v[0], np.float32).ravel()]), (C.c_float * 3)(*[float(x) for x in v[1]]),
+                            (C.c_float * 3)(*[float(x) for x in v[2]]), float(v[3]), float(v[4]), float(v[5]), float(v[6])) for v in (views1, views2)]
+        return vs, (C.byref(vs[0]), C.byref(vs[1]))
+
+    @classmethod
+    def NewPointsViews(cls, views1, views2, rig: bool = False):
+        """The two key frames' views in the form the four calls below hand to the library, for reuse over several calls."""
+        return cls._new_points_views(views1, views2, rig)[0]
+
+    def TriangulatePairsKeyFrames(self, kf1: DeviceKeyFrame, kf2: DeviceKeyFrame, view1, view2, level_sigma2_1, level_sigma2_2, ratio_factor, idx1, idx2,
+                                  inertial=False, far_points=False, th_far_points=0.0, pos=None, rig: bool = False):
+        """The loop body of LocalMapping::CreateNewMapPoints for the pairs (idx1[p], idx2[p]) of two resident key frames
+        (orbx_keyframe_triangulate_pairs): unprojection, parallax test, GeometricTools::Triangulate, depth, reprojection, distance and scale-ratio
+        tests on the device.  ratio_factor = 1.5f * mfScaleFactor of kf1; idx2[p] = -1: no match.  pos (optional, [n, 3] float32): rows of accepted pairs
+        are written, the others keep their values.  Returns (n_accepted, pos [n, 3], status [n] of _lib.NEWPT_*)."""
+        i1, i2 = _i32(idx1), _i32(idx2)
+        n = len(i1)
+        assert len(i2) == n
+        keep, par = self._new_points_params(kf1, kf2, level_sigma2_1, level_sigma2_2, ratio_factor, inertial, far_points, th_far_points)
+        vkeep, (v1, v2) = self._new_points_views(view1, view2, rig)
+        out = np.zeros((n, 3), np.float32) if pos is None else pos
+        assert out.dtype == np.float32 and out.shape == (n, 3) and out.flags.c_contiguous
+        status = np.zeros(n, np.uint8)
+        acc = C.c_int32(0)
+        fn = "orbx_keyframe_triangulate_pairs_fisheye" if rig else "orbx_keyframe_triangulate_pairs"
+        check(getattr(self._L, fn)(self._h, kf1._h, kf2._h, v1, v2, C.byref(par), n, ptr(i1), ptr(i2), ptr(out), ptr(status), C.byref(acc)), fn)
+        del keep, vkeep
+        return acc.value, out, status
+
+    def TriangulatePairsKeyFramesKB8(self, kf1: DeviceKeyFrame, kf2: DeviceKeyFrame, views1, views2, level_sigma2_1, level_sigma2_2, ratio_factor, idx1,
+                                     idx2, inertial=False, far_points=False, th_far_points=0.0, pos=None):
+        """The same between two fisheye-stereo key frames (orbx_keyframe_triangulate_pairs_fisheye): views1 / views2 = (left, right) of each key frame,
+        each (R, t, twc, params8) -- GetPose() / GetRightPose(), GetCameraCenter() / GetRightCameraCenter(), mpCamera / mpCamera2; an index from
+        N_left on is the right camera's."""
+        return self.TriangulatePairsKeyFrames(kf1, kf2, views1, views2, level_sigma2_1, level_sigma2_2, ratio_factor, idx1, idx2, inertial, far_points,
+                                              th_far_points, pos, rig=True)
+
+    def _search_and_triangulate(self, fn, kf1, kf2, skip1, skip2, gate, views, par, pos):
+        s1, s2 = _u8(skip1), _u8(skip2)
+        n1 = kf1.count()
+        m12 = np.full(max(n1, 1), -1, np.int32)
+        out = np.zeros((max(n1, 1), 3), np.float32) if pos is None else pos
+        assert out.dtype == np.float32 and out.shape == (max(n1, 1), 3) and out.flags.c_contiguous
+        status = np.zeros(max(n1, 1), np.uint8)
+        acc = C.c_int32(0)
+        n = check(getattr(self._L, fn)(self._h, kf1._h, kf2._h, ptr(s1), ptr(s2), int(self.mbCheckOrientation), C.byref(gate), views[0], views[1],
+                                       C.byref(par), ptr(m12), ptr(out), ptr(status), C.byref(acc)), fn)
+        return n, m12[:n1], acc.value, out[:n1], status[:n1]
+
+    def SearchAndTriangulateResident(self, kf1: DeviceKeyFrame, kf2: DeviceKeyFrame, skip1, skip2, level_sigma2_1, level_sigma2_2, F12, epipole, view1,
+                                     view2, ratio_factor, coarse=False, strict_fp=False, inertial=False, far_points=False, th_far_points=0.0, pos=None):
+        """SearchForTriangulationResident and TriangulatePairsKeyFrames on its match row in one call (orbx_keyframe_search_and_triangulate): one
+        launch more than the search, one synchronisation.  Returns (nmatches, matches12 [N1], n_accepted, pos [N1, 3], status [N1])."""
+        keep, par = self._new_points_params(kf1, kf2, level_sigma2_1, level_sigma2_2, ratio_factor, inertial, far_points, th_far_points)
+        g = KeyFrameGate((C.c_float * 9)(*[float(x) for x in np.asarray(F12, np.float32).ravel()]), float(epipole[0]), float(epipole[1]), int(coarse),
+                         int(strict_fp), len(keep[1]), keep[1].ctypes.data)
+        vkeep, views = self._new_points_views(view1, view2, False)
+        r = self._search_and_triangulate("orbx_keyframe_search_and_triangulate", kf1, kf2, skip1, skip2, g, views, par, pos)
+        del keep, vkeep
+        return r
+
+    def SearchAndTriangulateResidentKB8(self, kf1: DeviceKeyFrame, kf2: DeviceKeyFrame, skip1, skip2, level_sigma2_1, level_sigma2_2, cam1, cam2, R12, t12,
+                                        views1, views2, ratio_factor, coarse=False, inertial=False, far_points=False, th_far_points=0.0, pos=None):
+        """SearchForTriangulationResidentKB8 and TriangulatePairsKeyFramesKB8 on its match row in one call
+        (orbx_keyframe_search_and_triangulate_fisheye).  Returns (nmatches, matches12 [N1], n_accepted, pos [N1, 3], status [N1])."""
+        keep, par = self._new_points_params(kf1, kf2, level_sigma2_1, level_sigma2_2, ratio_factor, inertial, far_points, th_far_points)
+        flat = lambda x, n: (C.c_float * n)(*[float(v) for v in np.asarray(x, np.float32).ravel()])
+        g = KeyFrameKb8Gate(keep[0].ctypes.data, keep[1].ctypes.data, len(keep[0]), flat(cam1, 16), flat(cam2, 16), flat(R12, 36), flat(t12, 12), int(coarse))
+        vkeep, views = self._new_points_views(views1, views2, True)
+        r = self._search_and_triangulate("orbx_keyframe_search_and_triangulate_fisheye", kf1, kf2, skip1, skip2, g, views, par, pos)
+        del keep, vkeep
+        return r
 
     # ---- SearchForTriangulation (ORBmatcher.cc:907-1146) ----
     def SearchForTriangulation(self, desc1, angle1, skip1, fv1: FeatureVector, desc2, angle2, skip2, fv2: FeatureVector,
