@@ -1347,6 +1347,83 @@ int orbx_stereo_batch_download_all(orbx_extractor *left, float *u_right, float *
 int orbx_stereo_batch_download_async(orbx_extractor *left, float *u_right, float *depth, int32_t *n_matches);
 int orbx_stereo_download_wait(orbx_extractor *left);
 
+/* ---- rectified-stereo / RGB-D depth on the extractor's batch and on frame handles ----
+ * Frame::ComputeStereoFromRGBD for every frame of `ex`'s last batch (k_stereo_from_rgbd).  d_depth: DEVICE memory, one float32 depth image of the
+ * extractor's width x height per frame, pitch_bytes per row, frame_stride_bytes per image, already scaled (what GrabImageRGBD hands to Frame
+ * after convertTo).  Per feature i:  u = mvKeys[i].pt.x, v = mvKeys[i].pt.y (the RAW key point);  d = imDepth.at<float>(v, u), both coordinates
+ * converted to int by truncation;  d > 0: mvDepth[i] = d, mvuRight[i] = mvKeysUn[i].pt.x - bf / d (one true division, one subtraction;
+ * mvKeysUn = the rows orbx_set_camera undistorts);  else mvDepth[i] = mvuRight[i] = -1 (a NaN depth therefore gives -1).  A coordinate outside
+ * the image forms no address and gives -1.  The results lie where orbx_stereo_batch_device leaves its own -- with n_matches = the features with
+ * d > 0 -- so orbx_stereo_batch_download[_all | _async] serve both sources.  Enqueued behind the extraction on the MATCH stream, no host
+ * synchronisation: the depth images must stay valid until orbx_sync or a download has returned.  ORBX_E_BAD_ARG, before anything is enqueued:
+ * a NULL argument, no batch, pitch_bytes < 4 * width, !(bf > 0), and d_depth, pitch_bytes or frame_stride_bytes not a multiple of 4 (every row is a
+ * row of aligned floats).  frame_stride_bytes is otherwise the caller's: images may overlap or repeat.
+ * Both stages stamp the (left) extractor with the batch their results belong to; orbx_frame_load_stereo_batch checks the stamp. */
+int orbx_rgbd_batch_device(orbx_extractor *ex, const float *d_depth, size_t pitch_bytes, size_t frame_stride_bytes, float bf);
+/* A frame WITH depth on the handle: besides orbx_frame_load_batch's / orbx_frame_load_host's rows the handle then holds mvuRight, mvDepth and the raw
+ * mvKeys[i].pt, and every handle call treats it as the monocular / rectified frame it is (those that read mvuRight read the resident row).
+ *   orbx_frame_load_stereo_batch: orbx_frame_load_batch plus frame `frame`'s mvuRight / mvDepth of `left`'s last orbx_stereo_batch_device or
+ *     orbx_rgbd_batch_device and its raw key points, copied on the device in the same launch, behind the stage.  ORBX_E_BAD_ARG when no stage has
+ *     run or its results are not those of the extractor's current batch (an extraction since); otherwise orbx_frame_load_batch's refusals.
+ *   orbx_frame_load_host_stereo: orbx_frame_load_host with desc->u_right and depth [n] required; keys_xy [n][2] = mvKeys[i].pt (NULL: keypoints_un's).
+ * The other loads leave a handle without depth.
+ *   orbx_frame_unproject_stereo: Frame::UnprojectStereo for every feature (k_unproject_stereo; view: Rcw, Ow, fx, fy, cx, cy are read):
+ *       z = mvDepth[i];  nothing unless z > 0;  u, v = mvKeysUn[i].pt;  x = (u - cx) * z * invfx;  y = (v - cy) * z * invfy   (invfx = 1.0f / fx)
+ *       x3D = mRwc * (x, y, z) + mOw                                     (Rwc = Rcw.transpose(); each row a dot() plus one addition)
+ *     under the float contract stated at orbx_keyframe_triangulate_pairs.  u_right / depth [N] (the frame's rows), pos [N][3] (written where
+ *     depth > 0, the caller's values elsewhere), n_with_depth: each may be NULL.  One launch, one download run, one synchronisation; a pending
+ *     count comes home with the results.  ORBX_E_BAD_ARG for a handle without depth, a fisheye handle, another matcher's handle. */
+int orbx_frame_load_stereo_batch(orbx_frame *f, orbx_extractor *left, int frame, const float *bounds4, const float *scale_factors, int nlevels);
+int orbx_frame_load_host_stereo(orbx_frame *f, const orbx_frame_desc *desc, const float *depth, const float *keys_xy);
+int orbx_frame_unproject_stereo(orbx_matcher *m, orbx_frame *f, const orbx_new_points_view *view, float *u_right, float *depth, float *pos,
+                                int *n_with_depth);
+/* Depth on key frames.  orbx_keyframe_from_frame copies mvDepth and the raw key points when, and only when, the handle holds them (a key frame made
+ * from a handle without depth has the size and the contents it always had); orbx_keyframe_create_host_stereo is orbx_keyframe_create_host with
+ * desc->u_right and depth [n] required and keys_xy [n][2] = mvKeys[i].pt (NULL: keypoints_un's).  Fisheye key frames hold no depth.
+ *
+ * The stereo branches of LocalMapping::CreateNewMapPoints: the `_stereo` forms take every argument of orbx_keyframe_triangulate_pairs /
+ * orbx_keyframe_search_and_triangulate plus `st` behind `par`, share their implementation (k_new_points_stereo is k_new_points' body with the
+ * branches below switched on) and their cost shape; the record they send is 48 bytes longer.  ORBX_NEWPT_STEREO_LEFT_TO_HOST remains for a stereo
+ * observation (mvuRight >= 0) on a key frame that holds mvuRight but no mvDepth; ORBX_NEWPT_UNPROJECT_FAILED is UnprojectStereo returning false.
+ * A pair without a stereo observation takes the existing forms' path with their bits.  The member's stereo text, ORB-SLAM3 v1.0, restated (PARITY
+ * UNPINNED as the text above: no reference tree compiles LocalMapping.cc here, and where one is at hand its text wins):
+ *   bStereo1 = !KF1.mpCamera2 && mvuRight1[idx1] >= 0          (bStereo2 alike)
+ *   cosParallaxStereo = cosParallaxRays + 1;  cosParallaxStereo1 = cosParallaxStereo2 = cosParallaxStereo
+ *   if (bStereo1)      cosParallaxStereo1 = cos(2 * atan2(KF1.mb / 2, KF1.mvDepth[idx1]));
+ *   else if (bStereo2) cosParallaxStereo2 = cos(2 * atan2(KF2.mb / 2, KF2.mvDepth[idx2]));     "else if": with bStereo1 the second stays cosParallaxRays + 1
+ *   cosParallaxStereo = min(cosParallaxStereo1, cosParallaxStereo2);
+ *   if (cosParallaxRays < cosParallaxStereo && cosParallaxRays > 0 && (bStereo1 || bStereo2 || cosParallaxRays < (mbInertial ? 0.9996 : 0.9998)))
+ *         Triangulate as above (ORBX_NEWPT_TRIANGULATE_FAILED on false)
+ *   else if (bStereo1 && cosParallaxStereo1 < cosParallaxStereo2)  ok = KF1.UnprojectStereo(idx1, x3D)
+ *   else if (bStereo2 && cosParallaxStereo2 < cosParallaxStereo1)  ok = KF2.UnprojectStereo(idx2, x3D)
+ *   else continue                                                                              ORBX_NEWPT_LOW_PARALLAX
+ *   if (!ok) continue                                                                          ORBX_NEWPT_UNPROJECT_FAILED
+ *   KeyFrame::UnprojectStereo(i): z = mvDepth[i]; false unless z > 0; u, v = mvKeys[i].pt (the RAW key point, unlike Frame's member);
+ *         x3D = mRwc * ((u - cx) * z * invfx, (v - cy) * z * invfy, z) + Ow
+ *   z1, z2 tests as above.  Reprojection in key frame 1 when bStereo1 (key frame 2 alike with its own values):
+ *         invz1 = 1.0 / z1;  u1 = fx1 * x1 * invz1 + cx1;  u1_r = u1 - KF1.mbf * invz1;  v1 = fy1 * y1 * invz1 + cy1
+ *         errX1 = u1 - kp1.pt.x;  errY1 = v1 - kp1.pt.y;  errX1_r = u1_r - mvuRight1[idx1]
+ *         if ((errX1*errX1 + errY1*errY1 + errX1_r*errX1_r) > 7.8 * mvLevelSigma2_1[kp1.octave]) continue          ORBX_NEWPT_REPROJ_1
+ *      when !bStereo1: camera->project and 5.991, as above.  The rest of the member as above.
+ * As the device evaluates it: LocalMapping.cc is compiled under `using namespace std`, so the float overloads are taken -- mb / 2 a float halving,
+ * atan2 glibc's atan2f, the product with 2 exact, cos glibc's cosf (the "fma" variant the oracle's orbo_cosf restates), min(a, b) = b < a ? b : a;
+ * invz the correctly rounded float quotient; u1 = ((fx x1) invz1) + cx1, two products, each rounded, and a sum (u1_r, v1 alike); the three squares
+ * summed left to right in float and compared in double with 7.8 * (double)sigma2; UnprojectStereo is orbx_frame_unproject_stereo's arithmetic on
+ * the key frame's raw (x, y) and mvDepth rows with the view's Rcw and Ow. */
+typedef struct orbx_new_points_stereo { float mb1, mbf1, mb2, mbf2; } orbx_new_points_stereo;   /* KeyFrame::mb, mbf of KF1 / KF2 */
+/* status 12, behind the enum above: only the `_stereo` forms report it (KeyFrame::UnprojectStereo returned false: mvDepth <= 0), so the enum of the
+ * forms that never do stays as it is */
+#define ORBX_NEWPT_UNPROJECT_FAILED 12
+int orbx_keyframe_create_host_stereo(orbx_matcher *m, const orbx_frame_desc *desc, const float *depth, const float *keys_xy,
+                                     const float *inv_level_sigma2, orbx_keyframe **out);
+int orbx_keyframe_triangulate_pairs_stereo(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const orbx_new_points_view *view1,
+                                           const orbx_new_points_view *view2, const orbx_new_points_params *par, const orbx_new_points_stereo *st,
+                                           int n_pairs, const int32_t *idx1, const int32_t *idx2, float *pos, uint8_t *status, int *n_accepted);
+int orbx_keyframe_search_and_triangulate_stereo(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                                int check_orientation, const orbx_keyframe_gate *gate, const orbx_new_points_view *view1,
+                                                const orbx_new_points_view *view2, const orbx_new_points_params *par,
+                                                const orbx_new_points_stereo *st, int32_t *matches12, float *pos, uint8_t *status, int *n_accepted);
+
 const char *orbx_last_error(void);
 const char *orbx_status_string(int status);
 

@@ -155,11 +155,19 @@ class NewPointsParams(C.Structure):
                 ("nlevels_2", C.c_int), ("level_sigma2_1", C.c_void_p), ("level_sigma2_2", C.c_void_p)]
 
 
+class NewPointsStereo(C.Structure):
+    """orbx_new_points_stereo: KeyFrame::mb, mbf of key frame 1 / 2 for the `_stereo` forms of CreateNewMapPoints' triangulation."""
+    _fields_ = [("mb1", C.c_float), ("mbf1", C.c_float), ("mb2", C.c_float), ("mbf2", C.c_float)]
+
+
 # orbx.h's ORBX_NEWPT_* enum: the first `continue` LocalMapping::CreateNewMapPoints takes for a pair
 NEWPT_STATUS = ("OK", "NO_MATCH", "LOW_PARALLAX", "TRIANGULATE_FAILED", "BEHIND_1", "BEHIND_2", "REPROJ_1", "REPROJ_2", "ZERO_DIST", "FAR", "SCALE_RATIO",
                 "STEREO_LEFT_TO_HOST")
 (NEWPT_OK, NEWPT_NO_MATCH, NEWPT_LOW_PARALLAX, NEWPT_TRIANGULATE_FAILED, NEWPT_BEHIND_1, NEWPT_BEHIND_2, NEWPT_REPROJ_1, NEWPT_REPROJ_2, NEWPT_ZERO_DIST,
  NEWPT_FAR, NEWPT_SCALE_RATIO, NEWPT_STEREO_LEFT_TO_HOST) = range(12)
+# status 12 (orbx.h's ORBX_NEWPT_UNPROJECT_FAILED): reported by the `_stereo` forms alone -- their status names are NEWPT_STATUS_STEREO
+NEWPT_UNPROJECT_FAILED = 12
+NEWPT_STATUS_STEREO = NEWPT_STATUS + ("UNPROJECT_FAILED",)
 
 PAIR_PREDICATE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int)
 
@@ -210,6 +218,8 @@ SYMBOLS = [
     "orbx_keyframe_update_normal_and_depth", "orbx_keyframe_update_normal_and_depth_to_map", "orbx_keyframe_refresh_map_points_to_map",
     "orbx_keyframe_triangulate_pairs", "orbx_keyframe_triangulate_pairs_fisheye", "orbx_keyframe_search_and_triangulate",
     "orbx_keyframe_search_and_triangulate_fisheye",
+    "orbx_rgbd_batch_device", "orbx_frame_load_stereo_batch", "orbx_frame_load_host_stereo", "orbx_frame_unproject_stereo",
+    "orbx_keyframe_create_host_stereo", "orbx_keyframe_triangulate_pairs_stereo", "orbx_keyframe_search_and_triangulate_stereo",
 ]
 
 
@@ -308,6 +318,10 @@ def lib() -> C.CDLL:
     L.orbx_frame_load_host.argtypes = [vp, C.POINTER(FrameDesc)]
     L.orbx_frame_load_batch.argtypes = [vp, vp, i32, vp, vp, i32]
     L.orbx_frame_count.argtypes = [vp, C.POINTER(i32)]
+    L.orbx_rgbd_batch_device.argtypes = [vp, vp, sz, sz, f32]
+    L.orbx_frame_load_stereo_batch.argtypes = [vp, vp, i32, vp, vp, i32]
+    L.orbx_frame_load_host_stereo.argtypes = [vp, C.POINTER(FrameDesc), vp, vp]
+    L.orbx_frame_unproject_stereo.argtypes = [vp, vp, C.POINTER(NewPointsView), vp, vp, vp, C.POINTER(i32)]
     L.orbx_frame_search_by_projection_mappoints.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp]
     L.orbx_frame_search_by_projection_frame.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, f32, i32, i32, vp]
     L.orbx_frame_search_local_points.argtypes = [vp, vp, vp, C.POINTER(Camera), C.POINTER(FramePose), f32, f32, i32, vp, vp, vp, vp, vp, vp, vp,
@@ -375,6 +389,12 @@ def lib() -> C.CDLL:
     L.orbx_keyframe_triangulate_pairs.argtypes = [vp, vp, vp, C.POINTER(NewPointsView), C.POINTER(NewPointsView), C.POINTER(NewPointsParams), i32, vp, vp,
                                                   vp, vp, C.POINTER(i32)]
     L.orbx_keyframe_triangulate_pairs_fisheye.argtypes = [vp, vp, vp, vp, vp, C.POINTER(NewPointsParams), i32, vp, vp, vp, vp, C.POINTER(i32)]
+    L.orbx_keyframe_create_host_stereo.argtypes = [vp, C.POINTER(FrameDesc), vp, vp, vp, C.POINTER(vp)]
+    L.orbx_keyframe_triangulate_pairs_stereo.argtypes = [vp, vp, vp, C.POINTER(NewPointsView), C.POINTER(NewPointsView), C.POINTER(NewPointsParams),
+                                                         C.POINTER(NewPointsStereo), i32, vp, vp, vp, vp, C.POINTER(i32)]
+    L.orbx_keyframe_search_and_triangulate_stereo.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(KeyFrameGate), C.POINTER(NewPointsView),
+                                                              C.POINTER(NewPointsView), C.POINTER(NewPointsParams), C.POINTER(NewPointsStereo), vp, vp, vp,
+                                                              C.POINTER(i32)]
     L.orbx_keyframe_search_and_triangulate.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(KeyFrameGate), C.POINTER(NewPointsView), C.POINTER(NewPointsView),
                                                        C.POINTER(NewPointsParams), vp, vp, vp, C.POINTER(i32)]
     L.orbx_keyframe_search_and_triangulate_fisheye.argtypes = [vp, vp, vp, vp, vp, i32, C.POINTER(KeyFrameKb8Gate), vp, vp, C.POINTER(NewPointsParams), vp,

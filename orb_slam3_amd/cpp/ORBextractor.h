@@ -134,6 +134,13 @@ public:
     std::vector<float> inline GetScaleSigmaSquares() { return mvLevelSigma2; }
     std::vector<float> inline GetInverseScaleSigmaSquares() { return mvInvLevelSigma2; }
 
+    // Frame::ComputeStereoFromRGBD for every frame of the last batch (orbx_rgbd_batch_device): dDepth = DEVICE memory, one scaled float32 depth image
+    // per frame; enqueued behind the extraction.  The results are read with orbx_stereo_batch_download* or copied by DeviceFrame::loadStereoBatch.
+    void RGBDBatch(const float *dDepth, size_t pitchBytes, size_t frameStrideBytes, float mbf) {
+        const int st = orbx_rgbd_batch_device(ex_, dDepth, pitchBytes, frameStrideBytes, mbf);
+        if (st != ORBX_OK) throw std::runtime_error(std::string("orbx_rgbd_batch_device: ") + orbx_status_string(st) + " " + orbx_last_error());
+    }
+
     orbx_extractor *handle() { return ex_; }
 
 protected:

@@ -66,6 +66,17 @@ public:
     void loadBatch(orbx_extractor *ex, int frame, const float *bounds4 = nullptr, const float *scaleFactors = nullptr, int nlevels = 0) {
         check(orbx_frame_load_batch(f_, ex, frame, bounds4, scaleFactors, nlevels), "orbx_frame_load_batch");
     }
+    // loadBatch plus the frame's mvuRight, mvDepth and raw key points of the (left) extractor's last orbx_stereo_batch_device / orbx_rgbd_batch_device
+    // stage, copied on the device in the same launch; refused when no stage has run on the extractor's current batch
+    void loadStereoBatch(orbx_extractor *left, int frame, const float *bounds4 = nullptr, const float *scaleFactors = nullptr, int nlevels = 0) {
+        check(orbx_frame_load_stereo_batch(f_, left, frame, bounds4, scaleFactors, nlevels), "orbx_frame_load_stereo_batch");
+    }
+    // load() with F.mvuRight required, mvDepth [N] and the raw mvKeys[i].pt as (x, y) pairs (empty: the undistorted points) in the same upload
+    void loadHostStereo(const FrameView &F, const std::vector<float> &mvDepth, const std::vector<float> &keysXY = {}) {
+        orbx_frame_desc fd = F.c();
+        if ((int)mvDepth.size() != fd.n || (!keysXY.empty() && (int)keysXY.size() != 2 * fd.n)) throw std::runtime_error("loadHostStereo: array sizes");
+        check(orbx_frame_load_host_stereo(f_, &fd, mvDepth.data(), keysXY.empty() ? nullptr : keysXY.data()), "orbx_frame_load_host_stereo");
+    }
     int count() {
         int n = 0;
         check(orbx_frame_count(f_, &n), "orbx_frame_count");
@@ -93,6 +104,7 @@ public:
     inline void ComputeBoWFisheye(ORBmatcher &matcher, const ORBVocabularyDevice &voc, int levelsup = 4, std::vector<int32_t> *wordId = nullptr,
                                   std::vector<int32_t> *nodeId = nullptr);
     orbx_frame *handle() const { return f_; }
+    int capacity() const { return cap_; }
 
 private:
     static void check(int st, const char *what) {
@@ -111,6 +123,10 @@ public:
     inline DeviceKeyFrame(ORBmatcher &matcher, DeviceFrame &frame, const float *mvInvLevelSigma2);
     // the same object from host arrays (a loaded atlas): one upload
     inline DeviceKeyFrame(ORBmatcher &matcher, const FrameView &KF, const float *mvInvLevelSigma2);
+    // a rectified-stereo / RGB-D key frame from host arrays (orbx_keyframe_create_host_stereo): KF.mvuRight required, mvDepth [N], keysXY = the raw
+    // mvKeys[i].pt as (x, y) pairs (empty: the undistorted points) -- what ORBmatcher::TriangulatePairsStereo / SearchAndTriangulateStereo decide stereo pairs on
+    inline DeviceKeyFrame(ORBmatcher &matcher, const FrameView &KF, const std::vector<float> &mvDepth, const std::vector<float> &keysXY,
+                          const float *mvInvLevelSigma2);
     // a fisheye-stereo key frame (KeyFrame::NLeft != -1) -- mvKeys, mvKeysRight, all N descriptor rows, both counts and both grids: a device-to-device
     // copy of a loaded fisheye-stereo DeviceFrame of `matcher` (orbx_keyframe_from_frame_fisheye; asynchronous, also while the counts are still on the
     // device) ...
@@ -571,6 +587,34 @@ public:
                                                                    skip2.empty() ? nullptr : skip2.data(), mbCheckOrientation ? 1 : 0, &gate, views1, views2,
                                                                    &par, m12.data(), pos.data(), status.data(), &nAccepted);
         if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_search_and_triangulate_fisheye: ") + orbx_status_string(r) + " " + orbx_last_error());
+        vMatchedPairs.clear();
+        for (int i = 0; i < n1; i++) if (m12[i] >= 0) vMatchedPairs.emplace_back((size_t)i, (size_t)m12[i]);  // :1138-1143
+        return r;
+    }
+    // The same two with the member's stereo branches (orbx_keyframe_triangulate_pairs_stereo / orbx_keyframe_search_and_triangulate_stereo; st = mb, mbf of
+    // each key frame): a pair with mvuRight >= 0 on a key frame that holds mvDepth (made with DeviceKeyFrame's stereo constructor or from a DeviceFrame
+    // with depth) is triangulated or unprojected from its depth on the device; status may be ORBX_NEWPT_UNPROJECT_FAILED.
+    int TriangulatePairsStereo(DeviceKeyFrame &KF1, DeviceKeyFrame &KF2, const orbx_new_points_view &view1, const orbx_new_points_view &view2,
+                               const orbx_new_points_params &par, const orbx_new_points_stereo &st, const std::vector<int32_t> &idx1,
+                               const std::vector<int32_t> &idx2, std::vector<float> &pos, std::vector<uint8_t> &status) {
+        const size_t n = NewPointsPairs(idx1, idx2, pos, status);
+        int accepted = 0;
+        const int r = orbx_keyframe_triangulate_pairs_stereo(m_, KF1.handle(), KF2.handle(), &view1, &view2, &par, &st, (int)n, idx1.data(), idx2.data(),
+                                                             pos.data(), status.data(), &accepted);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_triangulate_pairs_stereo: ") + orbx_status_string(r) + " " + orbx_last_error());
+        return accepted;
+    }
+    int SearchAndTriangulateStereo(DeviceKeyFrame &KF1, DeviceKeyFrame &KF2, const std::vector<uint8_t> &skip1, const std::vector<uint8_t> &skip2,
+                                   const orbx_keyframe_gate &gate, const orbx_new_points_view &view1, const orbx_new_points_view &view2,
+                                   const orbx_new_points_params &par, const orbx_new_points_stereo &st,
+                                   std::vector<std::pair<size_t, size_t>> &vMatchedPairs, std::vector<float> &pos, std::vector<uint8_t> &status, int &nAccepted) {
+        const int n1 = KF1.count();
+        std::vector<int32_t> m12((size_t)std::max(n1, 1), -1);
+        pos.resize(3 * (size_t)std::max(n1, 1)); status.assign((size_t)std::max(n1, 1), (uint8_t)ORBX_NEWPT_NO_MATCH);
+        const int r = orbx_keyframe_search_and_triangulate_stereo(m_, KF1.handle(), KF2.handle(), skip1.empty() ? nullptr : skip1.data(),
+                                                                  skip2.empty() ? nullptr : skip2.data(), mbCheckOrientation ? 1 : 0, &gate, &view1, &view2,
+                                                                  &par, &st, m12.data(), pos.data(), status.data(), &nAccepted);
+        if (r < 0) throw std::runtime_error(std::string("orbx_keyframe_search_and_triangulate_stereo: ") + orbx_status_string(r) + " " + orbx_last_error());
         vMatchedPairs.clear();
         for (int i = 0; i < n1; i++) if (m12[i] >= 0) vMatchedPairs.emplace_back((size_t)i, (size_t)m12[i]);  // :1138-1143
         return r;
@@ -1282,6 +1326,21 @@ public:
         return r;
     }
 
+    // Frame::UnprojectStereo for every feature of a resident frame that holds mvDepth (DeviceFrame::loadStereoBatch / loadHostStereo;
+    // orbx_frame_unproject_stereo): mvuRight / mvDepth get N entries; x3D gets N rows of 3, the point where mvDepth > 0 and zeros elsewhere.
+    // Returns the number of features with depth.
+    int UnprojectStereo(DeviceFrame &F, const orbx_new_points_view &view, std::vector<float> &mvuRight, std::vector<float> &mvDepth, std::vector<float> &x3D) {
+        // (the count may still be on the device: sized by the handle's capacity, trimmed once the call has brought N home)
+        const size_t cap = (size_t)F.capacity();
+        mvuRight.assign(cap, 0.f); mvDepth.assign(cap, 0.f); x3D.assign(3 * cap, 0.f);
+        int with = 0;
+        const int st = orbx_frame_unproject_stereo(m_, F.handle(), &view, mvuRight.data(), mvDepth.data(), x3D.data(), &with);
+        if (st < 0) throw std::runtime_error(std::string("orbx_frame_unproject_stereo: ") + orbx_status_string(st) + " " + orbx_last_error());
+        const size_t n = (size_t)F.count();   // known after the call
+        mvuRight.resize(n); mvDepth.resize(n); x3D.resize(3 * n);
+        return with;
+    }
+
 #ifdef ORBX_WITH_SLAM_TYPES
     // the reference's own signatures (Frame / KeyFrame / MapPoint graphs): see ORBmatcher_slam.inl
 #include "ORBmatcher_slam.inl"
@@ -1336,6 +1395,14 @@ inline DeviceKeyFrame::DeviceKeyFrame(ORBmatcher &matcher, const FrameView &KF, 
     orbx_frame_desc fd = KF.c();
     const int st = orbx_keyframe_create_host(matcher.handle(), &fd, mvInvLevelSigma2, &kf_);
     if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_create_host: ") + orbx_status_string(st) + " " + orbx_last_error());
+}
+
+inline DeviceKeyFrame::DeviceKeyFrame(ORBmatcher &matcher, const FrameView &KF, const std::vector<float> &mvDepth, const std::vector<float> &keysXY,
+                                      const float *mvInvLevelSigma2) {
+    orbx_frame_desc fd = KF.c();
+    if ((int)mvDepth.size() != fd.n || (!keysXY.empty() && (int)keysXY.size() != 2 * fd.n)) throw std::invalid_argument("DeviceKeyFrame: array sizes");
+    const int st = orbx_keyframe_create_host_stereo(matcher.handle(), &fd, mvDepth.data(), keysXY.empty() ? nullptr : keysXY.data(), mvInvLevelSigma2, &kf_);
+    if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_create_host_stereo: ") + orbx_status_string(st) + " " + orbx_last_error());
 }
 
 inline DeviceKeyFrame::DeviceKeyFrame(Fisheye, ORBmatcher &matcher, DeviceFrame &frame, const float *mvInvLevelSigma2) : fisheye_(true) {

@@ -205,6 +205,9 @@ struct orbx_extractor {
     bool copy_pending = false;                         // a download was issued since the last (re)configuration
     int32_t *h_err = nullptr;  // pinned, 2 slots
     DevBuf d_st_bidx, d_st_bdist, d_st_ur, d_st_depth, d_st_sad, d_st_nm, d_st_scales, d_st_rowptr, d_st_rowidx;  // device stereo matcher (left extractor)
+    // the batch (batch_seq) whose mvuRight / mvDepth lie in d_st_ur / d_st_depth, written by orbx_stereo_batch_device or orbx_rgbd_batch_device
+    // (0: no stage has run): orbx_frame_load_stereo_batch copies from them
+    uint64_t st_seq = 0;
     // fisheye stereo stage (orbx_stereo_fisheye_batch_device, left extractor): its own result buffers -- kNN-2 rows [B][capL][2], l2r / depth [B][capL],
     // p3d [B][capL][3], r2l [B][capR], counts [B][4] (nMatches, descMatches, n_left, n_right) -- and the shape they were written with (a later extraction
     // may change last_batch / the counts before the download)

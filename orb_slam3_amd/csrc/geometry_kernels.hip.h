@@ -182,6 +182,37 @@ __host__ __device__ inline float glibc_atan2f(float y, float x) {
     if (m == 2) return pi - (z - pi_lo);
     return (z - pi_lo) - pi;
 }
+// glibc 2.35 cosf (sysdeps/ieee754/flt-32/s_cosf.c, the "fma" variant: every multiply-add of the double polynomial fused; tables __sincosf_table),
+// restated for |x| < 120 with the branches it has -- the cosine of extractor_kernels.hip.h's branch-free glibc_sincosf; the oracle's twin is orbo_cosf.
+// Its one caller passes 2 * atan2f(..), so nothing finite lies outside the range; a NaN (and whatever else is outside) gives NaN.
+__host__ __device__ inline float glibc_cosf(float y) {
+    uint32_t u;
+    memcpy(&u, &y, 4);
+    const uint32_t top = (u >> 20) & 0x7ff;
+    if (top >= 0x42f) return (y - y) / (y - y);
+    if (top < 0x398) return 1.0f;   // |y| < 2^-12
+    double x = (double)y, sg = 1.0;
+    bool sine = false;
+    if (top >= 0x3f4) {             // |y| >= pi / 4: reduce_fast
+        const double r = x * 0x1.45F306DC9C883p+23;
+        const int n = ((int32_t)r + 0x800000) >> 24;
+        x = __builtin_fma(-(double)n, 0x1.921FB54442D18p0, x);
+        if (n & 2) sg = -1.0;       // table 1: c0 .. c4 negated, s1 .. s3 unchanged
+        sine = (n & 1) != 0;
+        if (sine && ((n & 3) == 1 || (n & 3) == 2)) x = x * -1.0;
+        else if (sine) x = x * 1.0;
+    }
+    const double x2 = x * x;
+    if (sine) {
+        const double x3 = x * x2, s1 = __builtin_fma(x2, -0x1.994eb3774cf24p-13, 0x1.1107605230bc4p-7), x7 = x3 * x2;
+        const double s = __builtin_fma(x3, -0x1.555545995a603p-3, x);
+        return (float)__builtin_fma(x7, s1, s);
+    }
+    const double x4 = x2 * x2, c2 = __builtin_fma(x2, sg * 0x1.99343027bf8c3p-16, sg * -0x1.6c087e89a359dp-10);
+    const double c1 = __builtin_fma(x2, sg * -0x1.ffffffd0c621cp-2, sg * 0x1p0), x6 = x4 * x2;
+    const double c = __builtin_fma(x4, sg * 0x1.55553e1068f19p-5, c1);
+    return (float)__builtin_fma(x6, c2, c);
+}
 
 // One camera of a fisheye rig as Frame::isInFrustumChecks sees it (Frame.cc:1172-1186): the caller evaluates the reference's Eigen expressions
 // (bRight: mR = Rrl * mRcw, mt = Rrl * mtcw + trl, twc = mRwc * mTlr.translation() + mOw; left: mRcw, mtcw, mOw)

@@ -1311,6 +1311,13 @@ struct FramePrepare {
     int cap, nlevels;
     float scale_host[kFrameMaxLevels];
 };
+// The depth rows of a rectified-stereo / RGB-D frame (orbx_frame_load_stereo_batch): mvuRight and mvDepth of the extractor's stage and the RAW key
+// point's (x, y) -- mvKeys[i].pt, which KeyFrame::UnprojectStereo reads -- copied beside the rows FramePrepare names.
+struct FrameDepthRows {
+    const float *src_ur, *src_depth;
+    const orbx_keypoint *src_raw;
+    float *ur, *depth, *keys_xy;    // the handle's buffers [cap], [cap], [cap][2]
+};
 // grid (1 + ceil(copied rows / 256)), block 64: block 0 writes the count and the scale factors and builds the grid from the SOURCE rows (it does not
 // wait for the copy), block b >= 1 copies rows [256 (b-1), 256 b)
 __global__ __launch_bounds__(64) void k_frame_prepare(const FramePrepare F, GridParams g) {
@@ -1332,6 +1339,34 @@ __global__ __launch_bounds__(64) void k_frame_prepare(const FramePrepare F, Grid
     const uint4 *sd = reinterpret_cast<const uint4 *>(F.src_desc);       // 32-byte rows: 2 x 16 bytes
     uint4 *dd = reinterpret_cast<uint4 *>(F.desc);
     for (int w = i0 * 2 + (int)threadIdx.x; w < i1 * 2; w += 64) dd[w] = sd[w];
+}
+// The sibling for a frame with depth (orbx_frame_load_stereo_batch; src_kps is never NULL): block b >= 1 also copies the depth rows D of its features.
+// A kernel of its own and not a template switch on the one above: routed through a shared body, k_frame_prepare's code object came out different
+// from the one the frame handle's tests and measurements were made with.
+__global__ __launch_bounds__(64) void k_frame_prepare_stereo(const FramePrepare F, const FrameDepthRows D, GridParams g) {
+    __shared__ uint16_t cnt[kGridCells];
+    __shared__ uint16_t start[kGridCells];
+    __shared__ uint32_t claim[kGridCells];
+    const int n = max(0, min(gld(F.src_count), F.cap));
+    if (blockIdx.x == 0) {
+        if (threadIdx.x == 0) gst(F.count, (int32_t)n);
+        if (threadIdx.x < F.nlevels) gst(F.scale + threadIdx.x, F.scale_host[threadIdx.x]);
+        grid_build_wave(F.src_kps, n, F.gstart, F.gorder, g, cnt, start, claim);
+        return;
+    }
+    const int i0 = (blockIdx.x - 1) * 256, i1 = min(i0 + 256, n);
+    if (i0 >= i1) return;
+    const uint32_t *sk = reinterpret_cast<const uint32_t *>(F.src_kps);
+    uint32_t *dk = reinterpret_cast<uint32_t *>(F.kps);
+    for (int w = i0 * 7 + (int)threadIdx.x; w < i1 * 7; w += 64) dk[w] = sk[w];
+    const uint4 *sd = reinterpret_cast<const uint4 *>(F.src_desc);
+    uint4 *dd = reinterpret_cast<uint4 *>(F.desc);
+    for (int w = i0 * 2 + (int)threadIdx.x; w < i1 * 2; w += 64) dd[w] = sd[w];
+    for (int i = i0 + (int)threadIdx.x; i < i1; i += 64) {
+        D.ur[i] = D.src_ur[i];
+        D.depth[i] = D.src_depth[i];
+        D.keys_xy[2 * i] = D.src_raw[i].x; D.keys_xy[2 * i + 1] = D.src_raw[i].y;
+    }
 }
 
 // The same for a fisheye-stereo frame: both cameras' rows (right rows at the fixed row offset roff), both counts, mvLeftToRightMatch /
@@ -4069,6 +4104,91 @@ __global__ __launch_bounds__(256) void k_tri_kb8_stereo_init(const FisheyeStereo
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Frame::ComputeStereoFromRGBD (Frame.cc) for every frame of a resident batch: per feature i, d = imDepth.at<float>(v, u) at the RAW key point
+// (mvKeys[i].pt, both coordinates converted to int by truncation); d > 0: mvDepth[i] = d, mvuRight[i] = mvKeysUn[i].pt.x - mbf / d (one true division,
+// one subtraction); else both -1 (a NaN depth fails d > 0).  A coordinate outside the image forms no address and gives -1 (an extractor's key point is
+// never outside).  nmatches[f] = features of frame f with d > 0.  The results lie where the rectified stage (k_stereo_reject) leaves its own.
+// grid (n_frames), block 256
+// ---------------------------------------------------------------------------------------------------------
+struct RgbdStage {
+    const orbx_keypoint *kps, *kps_un;   // [B][cap] mvKeys, mvKeysUn
+    const int32_t *count;                // [B]
+    const uint8_t *depth;                // B float32 images, `pitch` bytes per row, `frame_stride` bytes per image
+    size_t pitch, frame_stride;
+    int cap, width, height;
+    float bf;
+    float *u_right, *out_depth;          // [B][cap]
+    int32_t *nmatches;                   // [B]
+};
+__global__ __launch_bounds__(256) void k_stereo_from_rgbd(const RgbdStage S) {
+    __shared__ int32_t total;
+    const int f = blockIdx.x;
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    const int n = max(0, min(S.count[f], S.cap));
+    const uint8_t *img = S.depth + (size_t)f * S.frame_stride;
+    int mine = 0;
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const size_t o = (size_t)f * S.cap + i;
+        const float u = S.kps[o].x, v = S.kps[o].y;
+        float d = -1.f;
+        // (int)u lies in [0, width) exactly when -1 < u < width; a NaN coordinate fails the comparison and is never converted
+        if (u > -1.f && u < (float)S.width && v > -1.f && v < (float)S.height)
+            d = *reinterpret_cast<const float *>(img + (size_t)(int)v * S.pitch + 4 * (size_t)(int)u);
+        const bool has = d > 0.f;
+        S.out_depth[o] = has ? d : -1.f;
+        S.u_right[o] = has ? __fsub_rn(S.kps_un[o].x, __fdiv_rn(S.bf, d)) : -1.f;
+        mine += has ? 1 : 0;
+    }
+    if (mine) atomicAdd(&total, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) S.nmatches[f] = total;
+}
+
+// orbx_keyframe_from_frame of a handle with depth: mvDepth and the raw (x, y) of the first N rows (N read here, clamped as k_keyframe_copy clamps it)
+// grid (ceil(cap / 256)), block 256
+__global__ __launch_bounds__(256) void k_keyframe_copy_depth(const int32_t *__restrict__ src_count, int cap, const float *__restrict__ src_depth,
+                                                             const float *__restrict__ src_xy, float *__restrict__ depth, float *__restrict__ xy) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= max(0, min(gld(src_count), cap))) return;
+    depth[i] = src_depth[i];
+    xy[2 * i] = src_xy[2 * i]; xy[2 * i + 1] = src_xy[2 * i + 1];
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Frame::UnprojectStereo (Frame.cc) for every feature of a resident frame that holds mvDepth: z = mvDepth[i], nothing unless z > 0;
+// x = (u - cx) * z * invfx, y = (v - cy) * z * invfy with (u, v) = mvKeysUn[i].pt and invfx = 1.0f / fx (a subtraction and two products, each rounded on
+// its own); x3D = mRwc * (x, y, z) + mOw, Rwc = Rcw.transpose(), every row a dot3 and one addition.  out_ur / out_depth: the
+// frame's mvuRight / mvDepth beside the points, so that one download run brings everything home.  pos[i] is written where z > 0 only.
+// grid (ceil(cap / 256)), block 256
+// ---------------------------------------------------------------------------------------------------------
+struct UnprojectStereo {
+    const orbx_keypoint *kps; const float *u_right, *depth; const int32_t *count;
+    int cap;
+    float Rcw[9], Ow[3], fx, fy, cx, cy;
+    float *out_ur, *out_depth, *out_pos;   // [cap], [cap], [cap][3]
+};
+__device__ __forceinline__ void unproject_stereo_point(const float *Rcw, const float *Ow, float fx, float fy, float cx, float cy, float u, float v, float z,
+                                                       float *X) {
+    const float invfx = __fdiv_rn(1.f, fx), invfy = __fdiv_rn(1.f, fy);
+    const float x = __fmul_rn(__fmul_rn(__fsub_rn(u, cx), z), invfx), y = __fmul_rn(__fmul_rn(__fsub_rn(v, cy), z), invfy);
+    X[0] = __fadd_rn(dot3(Rcw[0], Rcw[3], Rcw[6], x, y, z), Ow[0]);
+    X[1] = __fadd_rn(dot3(Rcw[1], Rcw[4], Rcw[7], x, y, z), Ow[1]);
+    X[2] = __fadd_rn(dot3(Rcw[2], Rcw[5], Rcw[8], x, y, z), Ow[2]);
+}
+__global__ __launch_bounds__(256) void k_unproject_stereo(const UnprojectStereo U) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= max(0, min(gld(U.count), U.cap))) return;
+    const float z = gld(U.depth + i);
+    gst(U.out_ur + i, gld(U.u_right + i));
+    gst(U.out_depth + i, z);
+    if (!(z > 0.f)) return;
+    float X[3];
+    unproject_stereo_point(U.Rcw, U.Ow, U.fx, U.fy, U.cx, U.cy, gld(&U.kps[i].x), gld(&U.kps[i].y), z, X);
+    gst(U.out_pos + 3 * (size_t)i, X[0]); gst(U.out_pos + 3 * (size_t)i + 1, X[1]); gst(U.out_pos + 3 * (size_t)i + 2, X[2]);
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // k_new_points: what LocalMapping::CreateNewMapPoints does with one matched pair (LocalMapping.cc, the loop over vMatchedIndices, with
 // GeometricTools::Triangulate), for every pair of a call, on two RESIDENT key frames of one kind (KB8 = false: monocular / rectified, Pinhole; KB8 = true:
 // a fisheye-stereo rig, KannalaBrandt8, the camera of each side chosen by the feature's index).  PARITY UNPINNED: nothing compiles LocalMapping.cc, the
@@ -4101,6 +4221,18 @@ struct NewPoints {
 };
 constexpr int kNewPointsBlock = 64;
 
+// The member's reprojection test in a key frame with a stereo observation: invz = 1.0 / z;  u = fx * x * invz + cx;  u_r = u - mbf * invz;
+// v = fy * y * invz + cy (two products, each rounded, and a sum);  the three squared errors summed left to right in float and compared in double with
+// 7.8 * mvLevelSigma2.  true: the pair is rejected.
+__device__ __forceinline__ bool new_points_stereo_reproj(const float *p, const float *Pc, float mbf, float kx, float ky, float ur, float sigma2) {
+    const float invz = __fdiv_rn(1.f, Pc[2]);
+    const float u = __fadd_rn(__fmul_rn(__fmul_rn(p[0], Pc[0]), invz), p[2]);
+    const float u_r = __fsub_rn(u, __fmul_rn(mbf, invz));
+    const float v = __fadd_rn(__fmul_rn(__fmul_rn(p[1], Pc[1]), invz), p[3]);
+    const float ex = __fsub_rn(u, kx), ey = __fsub_rn(v, ky), er = __fsub_rn(u_r, ur);
+    return (double)__fadd_rn(__fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), __fmul_rn(er, er)) > 7.8 * (double)sigma2;
+}
+
 // feature i of key frame R (reference numbering) -> its row and camera; false: i is outside [0, N)
 template <bool KB8> __device__ __forceinline__ bool new_points_row(const NewPointsKf *R, int i, int *row, bool *right) {
     const int32_t *cnt = gld(&R->count);
@@ -4117,8 +4249,13 @@ template <bool KB8> __device__ __forceinline__ bool new_points_row(const NewPoin
     return (unsigned)i < (unsigned)n;
 }
 
-template <bool KB8>
-__global__ __launch_bounds__(kNewPointsBlock) void k_new_points(const NewPoints *__restrict__ Tp) {
+// STEREO (the `_stereo` forms, Pinhole key frames): the record is a NewPointsStereoRec and the member's stereo branches run where a key frame holds mvDepth.
+struct NewPointsStereoRec {
+    NewPoints base;
+    const float *depth[2], *keys_xy[2];   // mvDepth [cap], mvKeys[i].pt [cap][2] of key frame 1 / 2; NULL: the key frame holds none
+    float mb[2], mbf[2];                  // KeyFrame::mb, mbf
+};
+template <bool KB8, bool STEREO> __device__ __forceinline__ void new_points_body(const NewPoints *__restrict__ Tp) {
     const NewPoints &T = *Tp;
     const int q = blockIdx.x * kNewPointsBlock + threadIdx.x;
     if (q < 2 && gld(&T.counts_out)) {
@@ -4140,10 +4277,20 @@ __global__ __launch_bounds__(kNewPointsBlock) void k_new_points(const NewPoints 
     const float px1 = gld(&k1->x), py1 = gld(&k1->y), px2 = gld(&k2->x), py2 = gld(&k2->y);
     const int oct1 = gld(&k1->octave), oct2 = gld(&k2->octave);
     if ((unsigned)oct1 >= (unsigned)gld(&T.kf[0].nlevels) || (unsigned)oct2 >= (unsigned)gld(&T.kf[1].nlevels)) { gst(gld(&T.flag), 1); return; }
-    if (!KB8) {   // bStereo1 || bStereo2: the member's mvDepth branch, left to the caller
+    // (every STEREO statement is an `if constexpr` block or a constant factor of a condition: without STEREO the statements are the ones they were)
+    bool st1 = false, st2 = false;
+    float ur1v = -1.f, ur2v = -1.f, dep1 = -1.f, dep2 = -1.f;
+    if (!KB8) {   // bStereo1 || bStereo2: the member's mvDepth branch -- left to the caller unless STEREO and the key frame holds mvDepth
         const float *ur1 = gld(&T.kf[0].u_right), *ur2 = gld(&T.kf[1].u_right);
         const bool stereo1 = ur1 && gld(ur1 + row1) >= 0.f, stereo2 = ur2 && gld(ur2 + row2) >= 0.f;
-        if (stereo1 || stereo2) { gst(status, (uint8_t)ORBX_NEWPT_STEREO_LEFT_TO_HOST); return; }
+        if constexpr (STEREO) {
+            const NewPointsStereoRec &E = *reinterpret_cast<const NewPointsStereoRec *>(Tp);
+            const float *d1 = gld(&E.depth[0]), *d2 = gld(&E.depth[1]);
+            if ((stereo1 && !d1) || (stereo2 && !d2)) { gst(status, (uint8_t)ORBX_NEWPT_STEREO_LEFT_TO_HOST); return; }
+            st1 = stereo1; st2 = stereo2;
+            if (st1) { ur1v = gld(ur1 + row1); dep1 = gld(d1 + row1); }
+            if (st2) { ur2v = gld(ur2 + row2); dep2 = gld(d2 + row2); }
+        } else if (stereo1 || stereo2) { gst(status, (uint8_t)ORBX_NEWPT_STEREO_LEFT_TO_HOST); return; }
     }
     // the level-indexed values of both sides, requested ahead of the arithmetic
     const float sigma1 = gld(gld(&T.kf[0].sigma2) + oct1), sigma2 = gld(gld(&T.kf[1].sigma2) + oct2);
@@ -4165,9 +4312,38 @@ __global__ __launch_bounds__(kNewPointsBlock) void k_new_points(const NewPoints 
     const float cosParallaxRays = __fdiv_rn(dot3(r10, r11, r12, r20, r21, r22), __fmul_rn(n1, n2));
     const float cosParallaxStereo = __fadd_rn(cosParallaxRays, 1.f);   // no stereo observation on either side
     const double lim = gld(&T.inertial) ? 0.9996 : 0.9998;
-    if (!(cosParallaxRays < cosParallaxStereo && cosParallaxRays > 0.f && (double)cosParallaxRays < lim)) { gst(status, (uint8_t)ORBX_NEWPT_LOW_PARALLAX); return; }
     float X[3];
-    if (!geometric_triangulate(xn1x, xn1y, R1, V1.t, xn2x, xn2y, R2, V2.t, X)) { gst(status, (uint8_t)ORBX_NEWPT_TRIANGULATE_FAILED); return; }
+    bool tested = false, unprojected = false;   // STEREO: the pair passed the member's stereo parallax test / X is an unprojected point
+    if constexpr (STEREO) {
+        if (st1 || st2) {
+            const NewPointsStereoRec &E = *reinterpret_cast<const NewPointsStereoRec *>(Tp);
+            // cosParallaxStereo1 / 2 = cos(2 * atan2(mb / 2, mvDepth)): the float overloads (LocalMapping.cc is compiled under `using namespace std`);
+            // with bStereo1 the second stays cosParallaxRays + 1 (the member's `else if`)
+            float cs1 = cosParallaxStereo, cs2 = cosParallaxStereo;
+            // (one call site, inlined: glibc_atan2f is an out-of-line function of the code object for the KB8 kernels, and a call here would cost this
+            // kernel the callee's register and stack conventions)
+            float angle;
+            [[clang::always_inline]] angle = glibc_atan2f(__fdiv_rn(gld(&E.mb[st1 ? 0 : 1]), 2.f), st1 ? dep1 : dep2);
+            const float cs_k = glibc_cosf(__fmul_rn(2.f, angle));
+            if (st1) cs1 = cs_k;
+            else cs2 = cs_k;
+            const float cs = cs2 < cs1 ? cs2 : cs1;   // std::min(a, b) = b < a ? b : a
+            tested = true;
+            if (!(cosParallaxRays < cs && cosParallaxRays > 0.f)) {   // (bStereo1 || bStereo2 holds: the 0.9998 test is not reached)
+                // KeyFrame::UnprojectStereo of the side with the smaller cosine: z = mvDepth, false unless z > 0; (u, v) = mvKeys[i].pt, the RAW key point
+                const int side = (st1 && cs1 < cs2) ? 0 : (st2 && cs2 < cs1) ? 1 : -1;
+                if (side < 0) { gst(status, (uint8_t)ORBX_NEWPT_LOW_PARALLAX); return; }
+                const float z = side ? dep2 : dep1;
+                if (!(z > 0.f)) { gst(status, (uint8_t)ORBX_NEWPT_UNPROJECT_FAILED); return; }
+                const float *xy = gld(&E.keys_xy[side]) + 2 * (size_t)(side ? row2 : row1);
+                const FisheyeView &V = side ? V2 : V1;
+                unproject_stereo_point(V.R, V.twc, V.p[0], V.p[1], V.p[2], V.p[3], gld(xy), gld(xy + 1), z, X);
+                unprojected = true;
+            }
+        }
+    }
+    if ((!STEREO || !tested) && !(cosParallaxRays < cosParallaxStereo && cosParallaxRays > 0.f && (double)cosParallaxRays < lim)) { gst(status, (uint8_t)ORBX_NEWPT_LOW_PARALLAX); return; }
+    if ((!STEREO || !unprojected) && !geometric_triangulate(xn1x, xn1y, R1, V1.t, xn2x, xn2y, R2, V2.t, X)) { gst(status, (uint8_t)ORBX_NEWPT_TRIANGULATE_FAILED); return; }
     const float z1 = __fadd_rn(dot3(R1[6], R1[7], R1[8], X[0], X[1], X[2]), V1.t[2]);
     if (z1 <= 0.f) { gst(status, (uint8_t)ORBX_NEWPT_BEHIND_1); return; }
     const float z2 = __fadd_rn(dot3(R2[6], R2[7], R2[8], X[0], X[1], X[2]), V2.t[2]);
@@ -4176,13 +4352,19 @@ __global__ __launch_bounds__(kNewPointsBlock) void k_new_points(const NewPoints 
     Pc[0] = __fadd_rn(dot3(R1[0], R1[1], R1[2], X[0], X[1], X[2]), V1.t[0]); Pc[1] = __fadd_rn(dot3(R1[3], R1[4], R1[5], X[0], X[1], X[2]), V1.t[1]); Pc[2] = z1;
     if (KB8) kb8_project(V1.p, Pc[0], Pc[1], Pc[2], &u, &v);
     else pinhole_project(V1.p[0], V1.p[1], V1.p[2], V1.p[3], Pc, &u, &v);
+    if constexpr (STEREO) {
+        if (st1 && new_points_stereo_reproj(V1.p, Pc, gld(&reinterpret_cast<const NewPointsStereoRec *>(Tp)->mbf[0]), px1, py1, ur1v, sigma1)) { gst(status, (uint8_t)ORBX_NEWPT_REPROJ_1); return; }
+    }
     const float errX1 = __fsub_rn(u, px1), errY1 = __fsub_rn(v, py1);
-    if ((double)__fadd_rn(__fmul_rn(errX1, errX1), __fmul_rn(errY1, errY1)) > 5.991 * (double)sigma1) { gst(status, (uint8_t)ORBX_NEWPT_REPROJ_1); return; }
+    if ((!STEREO || !st1) && (double)__fadd_rn(__fmul_rn(errX1, errX1), __fmul_rn(errY1, errY1)) > 5.991 * (double)sigma1) { gst(status, (uint8_t)ORBX_NEWPT_REPROJ_1); return; }
     Pc[0] = __fadd_rn(dot3(R2[0], R2[1], R2[2], X[0], X[1], X[2]), V2.t[0]); Pc[1] = __fadd_rn(dot3(R2[3], R2[4], R2[5], X[0], X[1], X[2]), V2.t[1]); Pc[2] = z2;
     if (KB8) kb8_project(V2.p, Pc[0], Pc[1], Pc[2], &u, &v);
     else pinhole_project(V2.p[0], V2.p[1], V2.p[2], V2.p[3], Pc, &u, &v);
+    if constexpr (STEREO) {
+        if (st2 && new_points_stereo_reproj(V2.p, Pc, gld(&reinterpret_cast<const NewPointsStereoRec *>(Tp)->mbf[1]), px2, py2, ur2v, sigma2)) { gst(status, (uint8_t)ORBX_NEWPT_REPROJ_2); return; }
+    }
     const float errX2 = __fsub_rn(u, px2), errY2 = __fsub_rn(v, py2);
-    if ((double)__fadd_rn(__fmul_rn(errX2, errX2), __fmul_rn(errY2, errY2)) > 5.991 * (double)sigma2) { gst(status, (uint8_t)ORBX_NEWPT_REPROJ_2); return; }
+    if ((!STEREO || !st2) && (double)__fadd_rn(__fmul_rn(errX2, errX2), __fmul_rn(errY2, errY2)) > 5.991 * (double)sigma2) { gst(status, (uint8_t)ORBX_NEWPT_REPROJ_2); return; }
     const float a0 = __fsub_rn(X[0], V1.twc[0]), a1 = __fsub_rn(X[1], V1.twc[1]), a2 = __fsub_rn(X[2], V1.twc[2]);
     const float b0 = __fsub_rn(X[0], V2.twc[0]), b1 = __fsub_rn(X[1], V2.twc[1]), b2 = __fsub_rn(X[2], V2.twc[2]);
     const float dist1 = sqrtf(dot3(a0, a1, a2, a0, a1, a2)), dist2 = sqrtf(dot3(b0, b1, b2, b0, b1, b2));
@@ -4195,5 +4377,7 @@ __global__ __launch_bounds__(kNewPointsBlock) void k_new_points(const NewPoints 
     gst(pos, X[0]); gst(pos + 1, X[1]); gst(pos + 2, X[2]);
     gst(status, (uint8_t)ORBX_NEWPT_OK);
 }
+template <bool KB8> __global__ __launch_bounds__(kNewPointsBlock) void k_new_points(const NewPoints *__restrict__ Tp) { new_points_body<KB8, false>(Tp); }
+__global__ __launch_bounds__(kNewPointsBlock) void k_new_points_stereo(const NewPoints *__restrict__ Tp) { new_points_body<false, true>(Tp); }
 
 }  // namespace orbx

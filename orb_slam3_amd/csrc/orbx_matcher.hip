@@ -354,6 +354,7 @@ struct orbx_frame {
     orbx_keypoint *kps = nullptr;
     uint8_t *desc = nullptr;
     float *u_right = nullptr, *scale = nullptr;
+    float *depth = nullptr, *keys_xy = nullptr;   // mvDepth [cap], mvKeys[i].pt [cap][2]: valid while has_depth (the `_stereo` loads)
     int32_t *count = nullptr;
     uint16_t *gstart = nullptr, *gorder = nullptr;
     uint8_t *stage = nullptr;         // pinned (device-visible) staging of orbx_frame_load_host: the rows at the device layout's offsets
@@ -362,12 +363,12 @@ struct orbx_frame {
     hipEvent_t ev_src = nullptr;      // load_batch: the extractor's stream up to the batch
     hipEvent_t ev_done = nullptr;     // load_batch: the copy has run (the extractor's next batch waits for it); load_host: the staging is free again
     bool stage_busy = false;
-    bool loaded = false, has_ur = false, n_known = false;
+    bool loaded = false, has_ur = false, has_depth = false, n_known = false;
     int n = 0, nlevels = 0;
     std::vector<float> scale_h;       // mvScaleFactors on the host (the projection matchers' host-side window setup)
     float bounds[4] = {0, 0, 0, 0};
     std::vector<int32_t> h_match;     // result rows of a call made while N was still on the device (PendingRows: frame_fetch / frame_take)
-    size_t off_kps = 0, off_desc = 0, off_ur = 0, off_count = 0, off_scale = 0, off_gstart = 0, off_gorder = 0;
+    size_t off_kps = 0, off_desc = 0, off_ur = 0, off_count = 0, off_scale = 0, off_gstart = 0, off_gorder = 0, off_depth = 0, off_xy = 0;
     BowArrays bow;                    // Frame::ComputeBoW (orbx_frame_compute_bow[_fisheye]); valid until the next load
     bool bow_valid = false;
     uint64_t load_seq = 0;            // loads so far: orbx_keyframe_from_frame remembers (handle, load_seq) for orbx_keyframe_bow_from_frame
@@ -490,12 +491,12 @@ int frame_begin_host_load(orbx_frame *f) {
 
 // The tail of every load, behind its kernel launch: the launch's error, ev_done (a batch load: the copy has run; staged: the staging is free again),
 // and ALL of the handle's bookkeeping -- nothing else writes it.  roff: the right camera's first row (monocular: 0); c0, c1: N (, 0) or N_left,
-// N_right where the host knows them, c0 < 0 while they are on the device only.
-int frame_loaded(orbx_frame *f, bool fisheye, int roff, int c0, int c1, bool has_ur, bool staged) {
+// N_right where the host knows them, c0 < 0 while they are on the device only.  has_depth: the load filled mvDepth and the raw (x, y) rows too.
+int frame_loaded(orbx_frame *f, bool fisheye, int roff, int c0, int c1, bool has_ur, bool has_depth, bool staged) {
     ORBX_HIP(hipGetLastError());
     ORBX_HIP(hipEventRecord(f->ev_done, f->owner->stream));
     if (staged) f->stage_busy = true;
-    f->fisheye = fisheye; f->roff = roff; f->has_ur = has_ur;
+    f->fisheye = fisheye; f->roff = roff; f->has_ur = has_ur; f->has_depth = has_depth;
     f->loaded = true; f->bow_valid = false; f->load_seq++;
     f->n_known = false; f->n = f->n_left = 0; f->n_right = -1;
     if (c0 >= 0) f->adopt(c0, c1);
@@ -1001,7 +1002,8 @@ int orbx_frame_create(orbx_matcher *m, int cap, orbx_frame **out) {
     f->off_l2r = L.add(4 * (size_t)cap); f->off_r2l = L.add(4 * (size_t)cap);
     const size_t off_bw = L.add(4 * (size_t)cap), off_bn = L.add(4 * (size_t)cap), off_fn = L.add(4 * (size_t)cap), off_fp = L.add(4 * ((size_t)cap + 1)),
                  off_fi = L.add(4 * (size_t)cap), off_fm = L.add(16), off_an = L.add(4 * (size_t)cap);
-    f->stage_bytes = L.used;   // the rows (keypoints, descriptors, mvuRight; a fisheye frame's partners) at the device layout's offsets
+    f->off_depth = L.add(4 * (size_t)cap); f->off_xy = L.add(8 * (size_t)cap);   // behind everything else: the other rows lie where they lay
+    f->stage_bytes = L.used;   // the rows (keypoints, descriptors, mvuRight, mvDepth, raw (x, y); a fisheye frame's partners) at the device layout's offsets
     hipError_t e = hipMalloc((void **)&f->dev, L.used);
     if (e == hipSuccess) e = hipHostMalloc((void **)&f->stage, f->stage_bytes, hipHostMallocCoherent);   // read by k_xfer's lanes
     if (e == hipSuccess) e = hipHostMalloc((void **)&f->h_count, 64, hipHostMallocDefault);
@@ -1016,39 +1018,64 @@ int orbx_frame_create(orbx_matcher *m, int cap, orbx_frame **out) {
     f->bow.angle = (float *)(f->dev + off_an);
     f->gstart_r = (uint16_t *)(f->dev + off_gsr); f->gorder_r = (uint16_t *)(f->dev + off_gor);
     f->l2r = (int32_t *)(f->dev + f->off_l2r); f->r2l = (int32_t *)(f->dev + f->off_r2l);
+    f->depth = (float *)(f->dev + f->off_depth); f->keys_xy = (float *)(f->dev + f->off_xy);
     f->n_known = true;   // an empty frame until the first load
     *out = f;
     return ORBX_OK;
 }
 
 
-int orbx_frame_load_host(orbx_frame *f, const orbx_frame_desc *d) {
-    if (!f || !d || d->n < 0 || (d->n > 0 && (!d->keypoints_un || !d->descriptors)) || !d->scale_factors || d->nlevels < 1 ||
-        d->nlevels > kFrameMaxLevels)
-        return ORBX_E_BAD_ARG;
-    if (d->n > f->cap) return ORBX_E_TOO_LARGE;
+// orbx_frame_load_host and, depth given, orbx_frame_load_host_stereo: the same load, the second with mvuRight required and mvDepth / the raw
+// (x, y) rows in the same upload run (keys_xy NULL: the undistorted key points')
+static int frame_load_host(orbx_frame *f, const orbx_frame_desc *d, const float *depth, const float *keys_xy) {
     orbx_matcher *m = f->owner;
     ORBX_TRY(frame_begin_host_load(f));
     const int n = d->n;
-    const size_t b_kps = 28 * (size_t)n, b_desc = 32 * (size_t)n, b_ur = d->u_right ? 4 * (size_t)n : 0;
+    const size_t b_kps = 28 * (size_t)n, b_desc = 32 * (size_t)n, b_ur = d->u_right ? 4 * (size_t)n : 0, b_dep = depth ? 4 * (size_t)n : 0;
     memcpy(f->stage + f->off_kps, d->keypoints_un, b_kps);
     memcpy(f->stage + f->off_desc, d->descriptors, b_desc);
     if (b_ur) memcpy(f->stage + f->off_ur, d->u_right, b_ur);
+    if (b_dep) {
+        memcpy(f->stage + f->off_depth, depth, b_dep);
+        float *xy = reinterpret_cast<float *>(f->stage + f->off_xy);
+        if (keys_xy) memcpy(xy, keys_xy, 2 * b_dep);
+        else for (int i = 0; i < n; i++) { xy[2 * i] = d->keypoints_un[i].x; xy[2 * i + 1] = d->keypoints_un[i].y; }
+    }
     // the rows in ONE k_xfer launch in the owner's queue (ORBX_MATCHER_DMA=1: by the DMA engine); count and scale factors travel as k_frame_prepare's arguments
-    const orbx_matcher::Span rows[3] = {{f->off_kps, b_kps}, {f->off_desc, b_desc}, {f->off_ur, b_ur}};
-    ORBX_TRY(m->upload_ranges(f->dev, f->stage, rows, 3));
+    const orbx_matcher::Span rows[5] = {{f->off_kps, b_kps}, {f->off_desc, b_desc}, {f->off_ur, b_ur}, {f->off_depth, b_dep}, {f->off_xy, 2 * b_dep}};
+    ORBX_TRY(m->upload_ranges(f->dev, f->stage, rows, depth ? 5 : 3));
     FramePrepare P;
     const float b[4] = {d->min_x, d->max_x, d->min_y, d->max_y};
     frame_prepare_common(f, P, 0, d->scale_factors, d->nlevels, b);
     P.n_host = n; P.cap = f->cap;
     hipLaunchKernelGGL(k_frame_prepare, dim3(1), dim3(64), 0, m->stream, P, grid_of(f->bounds));
-    return frame_loaded(f, false, 0, n, 0, d->u_right != nullptr, true);
+    return frame_loaded(f, false, 0, n, 0, d->u_right != nullptr, depth != nullptr, true);
 }
 
-int orbx_frame_load_batch(orbx_frame *f, orbx_extractor *ex, int frame, const float *bounds4, const float *scale_factors, int nlevels) {
+int orbx_frame_load_host(orbx_frame *f, const orbx_frame_desc *d) {
+    if (!f || !d || d->n < 0 || (d->n > 0 && (!d->keypoints_un || !d->descriptors)) || !d->scale_factors || d->nlevels < 1 ||
+        d->nlevels > kFrameMaxLevels)
+        return ORBX_E_BAD_ARG;
+    if (d->n > f->cap) return ORBX_E_TOO_LARGE;
+    return frame_load_host(f, d, nullptr, nullptr);
+}
+
+int orbx_frame_load_host_stereo(orbx_frame *f, const orbx_frame_desc *d, const float *depth, const float *keys_xy) {
+    if (!f || !d || d->n < 0 || (d->n > 0 && (!d->keypoints_un || !d->descriptors)) || !d->scale_factors || d->nlevels < 1 ||
+        d->nlevels > kFrameMaxLevels || !d->u_right || !depth)
+        return ORBX_E_BAD_ARG;
+    if (d->n > f->cap) return ORBX_E_TOO_LARGE;
+    return frame_load_host(f, d, depth, keys_xy);
+}
+
+// orbx_frame_load_batch and, stereo, orbx_frame_load_stereo_batch: the second copies mvuRight / mvDepth of the extractor's stereo / RGB-D stage and the raw
+// (x, y) in the same launch, behind the stage
+static int frame_load_batch(orbx_frame *f, orbx_extractor *ex, int frame, const float *bounds4, const float *scale_factors, int nlevels, bool stereo) {
     if (!f || !ex) return ORBX_E_BAD_ARG;
     orbx_matcher *m = f->owner;
     if (frame < 0 || frame >= ex->last_batch || ex->device != m->device || ex->cap > f->cap) return ORBX_E_BAD_ARG;
+    // the stage's results must be those of the extractor's current batch
+    if (stereo && (!ex->d_st_ur.p || !ex->d_st_depth.p || ex->st_seq == 0 || ex->st_seq != ex->batch_seq)) return ORBX_E_BAD_ARG;
     const float *sf = scale_factors ? scale_factors : ex->scale.data();
     const int nl = scale_factors ? nlevels : ex->prm.nlevels;
     if (nl < 1 || nl > kFrameMaxLevels || (!bounds4 && ex->width <= 0)) return ORBX_E_BAD_ARG;
@@ -1065,10 +1092,29 @@ int orbx_frame_load_batch(orbx_frame *f, orbx_extractor *ex, int frame, const fl
     // overwrites its outputs only after this frame holds its own copy
     ORBX_HIP(hipEventRecord(f->ev_src, ex->stream));
     ORBX_HIP(hipStreamWaitEvent(m->stream, f->ev_src, 0));
-    hipLaunchKernelGGL(k_frame_prepare, dim3(1 + (unsigned)((cap + 255) / 256)), dim3(64), 0, m->stream, P, grid_of(f->bounds));
-    ORBX_TRY(frame_loaded(f, false, 0, -1, -1, false, false));
+    const dim3 grid(1 + (unsigned)((cap + 255) / 256));
+    if (stereo) {
+        ORBX_HIP(hipStreamWaitEvent(m->stream, ex->ev_match, 0));   // the stage runs on the match stream
+        FrameDepthRows D;
+        D.src_ur = (const float *)ex->d_st_ur.p + (size_t)frame * cap; D.src_depth = (const float *)ex->d_st_depth.p + (size_t)frame * cap;
+        D.src_raw = (const orbx_keypoint *)ex->d_kps.p + (size_t)frame * cap;   // mvKeys
+        D.ur = f->u_right; D.depth = f->depth; D.keys_xy = f->keys_xy;
+        hipLaunchKernelGGL(k_frame_prepare_stereo, grid, dim3(64), 0, m->stream, P, D, grid_of(f->bounds));
+    } else {
+        hipLaunchKernelGGL(k_frame_prepare, grid, dim3(64), 0, m->stream, P, grid_of(f->bounds));
+    }
+    ORBX_TRY(frame_loaded(f, false, 0, -1, -1, stereo, stereo, false));
     ORBX_HIP(hipStreamWaitEvent(ex->stream, f->ev_done, 0));
+    if (stereo && ex->match_stream) ORBX_HIP(hipStreamWaitEvent(ex->match_stream, f->ev_done, 0));   // the next stage overwrites what the copy reads
     return ORBX_OK;
+}
+
+int orbx_frame_load_batch(orbx_frame *f, orbx_extractor *ex, int frame, const float *bounds4, const float *scale_factors, int nlevels) {
+    return frame_load_batch(f, ex, frame, bounds4, scale_factors, nlevels, false);
+}
+
+int orbx_frame_load_stereo_batch(orbx_frame *f, orbx_extractor *left, int frame, const float *bounds4, const float *scale_factors, int nlevels) {
+    return frame_load_batch(f, left, frame, bounds4, scale_factors, nlevels, true);
 }
 
 int orbx_frame_load_host_fisheye(orbx_frame *f, const orbx_frame_desc *left, const orbx_keypoint *kps_right, int n_right, const int32_t *l2r,
@@ -1098,7 +1144,7 @@ int orbx_frame_load_host_fisheye(orbx_frame *f, const orbx_frame_desc *left, con
     P.n_host[0] = nl; P.n_host[1] = nr; P.cap_side[0] = nl; P.cap_side[1] = nr;
     P.l2r = f->l2r; P.r2l = f->r2l;
     hipLaunchKernelGGL(k_frame_prepare_fisheye, dim3(2), dim3(64), 0, m->stream, P, grid_of(f->bounds));
-    return frame_loaded(f, true, nl, nl, nr, false, true);
+    return frame_loaded(f, true, nl, nl, nr, false, false, true);
 }
 
 int orbx_frame_load_stereo_fisheye_batch(orbx_frame *f, orbx_extractor *L, orbx_extractor *R, int frame, const float *bounds4,
@@ -1132,7 +1178,7 @@ int orbx_frame_load_stereo_fisheye_batch(orbx_frame *f, orbx_extractor *L, orbx_
     // stage wait for the copy: no host synchronisation
     ORBX_HIP(hipStreamWaitEvent(m->stream, L->ev_sf, 0));
     hipLaunchKernelGGL(k_frame_prepare_fisheye, dim3(2 + (unsigned)((std::max(capL, capR) + 255) / 256)), dim3(64), 0, m->stream, P, grid_of(f->bounds));
-    ORBX_TRY(frame_loaded(f, true, capL, -1, -1, false, false));
+    ORBX_TRY(frame_loaded(f, true, capL, -1, -1, false, false, false));
     ORBX_HIP(hipStreamWaitEvent(L->stream, f->ev_done, 0));
     ORBX_HIP(hipStreamWaitEvent(R->stream, f->ev_done, 0));
     if (L->match_stream) ORBX_HIP(hipStreamWaitEvent(L->match_stream, f->ev_done, 0));
@@ -1151,6 +1197,49 @@ int orbx_frame_counts(orbx_frame *f, int *n_left, int *n_right) {
     if (rc != ORBX_OK) return rc;
     if (n_left) *n_left = f->n_left;     // (a monocular frame: N, -1)
     if (n_right) *n_right = f->n_right;
+    return ORBX_OK;
+}
+
+// Frame::UnprojectStereo for every feature of a frame that holds mvDepth (k_unproject_stereo): one launch, one download run (mvuRight, mvDepth and the
+// points side by side in the arena, with N while it is pending), one synchronisation.  pos rows are written where depth > 0 only.
+int orbx_frame_unproject_stereo(orbx_matcher *m, orbx_frame *f, const orbx_new_points_view *view, float *u_right, float *depth, float *pos,
+                                int *n_with_depth) {
+    if (!m || !f || !view || f->owner != m || f->fisheye || !f->loaded || !f->has_depth) return ORBX_E_BAD_ARG;
+    ORBX_HIP(hipSetDevice(m->device));
+    const int nr = f->rows_n();
+    if (nr == 0) { if (n_with_depth) *n_with_depth = 0; return ORBX_OK; }
+    UnprojectStereo U;
+    ORBX_TRY(m->carve([&](Carve &A) {
+        U.out_ur = A.take<float>((size_t)nr); U.out_depth = A.take<float>((size_t)nr); U.out_pos = A.take<float>(3 * (size_t)nr);
+    }));
+    U.kps = f->kps; U.u_right = f->u_right; U.depth = f->depth; U.count = f->count; U.cap = nr;
+    memcpy(U.Rcw, view->Rcw, sizeof(U.Rcw)); memcpy(U.Ow, view->Ow, sizeof(U.Ow));
+    U.fx = view->fx; U.fy = view->fy; U.cx = view->cx; U.cy = view->cy;
+    hipLaunchKernelGGL(k_unproject_stereo, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, m->exec(), U);
+    ORBX_HIP(hipGetLastError());
+    // N known: mvuRight and mvDepth go straight to the caller's arrays where they are given; the points always land here first (only rows with depth
+    // are handed out), and so does whatever has no destination yet.  Rows beyond N are never written by the kernel and never read here.
+    const bool known = f->n_known;
+    const bool ur_direct = known && u_right, dep_direct = known && depth;
+    const size_t n_land = (ur_direct ? 0 : (size_t)nr) + (dep_direct ? 0 : (size_t)nr) + 3 * (size_t)nr;
+    std::unique_ptr<float[]> land(new float[n_land]);
+    float *l_pos = land.get(), *l_ur = ur_direct ? u_right : l_pos + 3 * (size_t)nr, *l_dep = dep_direct ? depth : l_pos + 3 * (size_t)nr + (ur_direct ? 0 : (size_t)nr);
+    ORBX_TRY(m->d2h(l_ur, U.out_ur, 4 * (size_t)nr));
+    ORBX_TRY(m->d2h(l_dep, U.out_depth, 4 * (size_t)nr));
+    ORBX_TRY(m->d2h(l_pos, U.out_pos, 12 * (size_t)nr));
+    if (!known) ORBX_TRY(f->fetch_count());
+    ORBX_TRY(m->sync_and_deliver());
+    if (!known) f->adopt_count();
+    const int n = f->n;
+    if (u_right && !ur_direct) memcpy(u_right, l_ur, 4 * (size_t)n);
+    if (depth && !dep_direct) memcpy(depth, l_dep, 4 * (size_t)n);
+    int with = 0;
+    for (int i = 0; i < n; i++) {
+        if (!(l_dep[i] > 0.f)) continue;
+        with++;
+        if (pos) memcpy(pos + 3 * (size_t)i, l_pos + 3 * (size_t)i, 12);
+    }
+    if (n_with_depth) *n_with_depth = with;
     return ORBX_OK;
 }
 
@@ -2515,11 +2604,45 @@ extern "C" int orbx_stereo_batch_device(orbx_extractor *L, orbx_extractor *R, fl
     hipLaunchKernelGGL(k_stereo_sad, dim3((capL + 15) / 16, n), dim3(256), 0, st, S);
     hipLaunchKernelGGL(k_stereo_reject, dim3(n), dim3(256), 0, st, S);
     ORBX_HIP(hipGetLastError());
+    L->st_seq = L->batch_seq;   // (orbx_frame_load_stereo_batch: the results are this batch's)
     // the extractors must not overwrite their outputs / pyramids before these kernels are done
     ORBX_HIP(hipEventRecord(L->ev_match, st));
     L->match_pending = true; L->copy_covers_match = false;
     ORBX_HIP(hipEventRecord(R->ev_match, st));   // the right extractor's next k_finalize waits for it as for a matcher of its own
     R->match_pending = true; R->copy_covers_match = false;
+    return ORBX_OK;
+}
+
+// Frame::ComputeStereoFromRGBD for every frame of a resident batch (k_stereo_from_rgbd): one launch on the extractor's MATCH stream behind the
+// extraction, no host synchronisation.  mvuRight / mvDepth / the count of features with depth land in the rectified stage's result buffers, so the
+// orbx_stereo_batch_download* calls serve both sources.  No pyramid level is read: level 0 is not materialised and the extractor keeps its single slab.
+extern "C" int orbx_rgbd_batch_device(orbx_extractor *ex, const float *d_depth, size_t pitch_bytes, size_t frame_stride_bytes, float bf) {
+    RoctxRange rr("orbx:rgbd");
+    if (!ex || !d_depth || ex->last_batch <= 0 || ex->width <= 0 || pitch_bytes < 4 * (size_t)ex->width || !(bf > 0.f)) return ORBX_E_BAD_ARG;
+    // every row of every image must be a row of aligned floats
+    if (((uintptr_t)d_depth | pitch_bytes | frame_stride_bytes) & 3u) return ORBX_E_BAD_ARG;
+    ORBX_HIP(hipSetDevice(ex->device));
+    const int n = ex->last_batch;
+    int r;
+    for (DevBuf *b : {&ex->d_st_ur, &ex->d_st_depth})
+        if ((r = b->ensure(4 * (size_t)ex->cap * ex->batch_cap)) != ORBX_OK) return r;
+    if ((r = ex->d_st_nm.ensure(4 * (size_t)ex->batch_cap)) != ORBX_OK) return r;
+    const bool side = !ex->profile && ex->side_streams;
+    hipStream_t st = side ? ex->match_stream : ex->stream;
+    ORBX_HIP(hipStreamWaitEvent(st, ex->ev_describe, 0));   // the extraction of this batch (its k_undistort included)
+    if (ex->stereo_copy_issued) ORBX_HIP(hipStreamWaitEvent(st, ex->ev_stereo_copy[(ex->stereo_copy_issued - 1) & 1], 0));  // the previous results may still be on their way to the host
+    RgbdStage S;
+    S.kps = (const orbx_keypoint *)ex->d_kps.p; S.kps_un = (const orbx_keypoint *)ex->match_kps();
+    S.count = (const int32_t *)ex->d_count.p;
+    S.depth = (const uint8_t *)d_depth; S.pitch = pitch_bytes; S.frame_stride = frame_stride_bytes;
+    S.cap = ex->cap; S.width = ex->width; S.height = ex->height; S.bf = bf;
+    S.u_right = (float *)ex->d_st_ur.p; S.out_depth = (float *)ex->d_st_depth.p; S.nmatches = (int32_t *)ex->d_st_nm.p;
+    hipLaunchKernelGGL(k_stereo_from_rgbd, dim3((unsigned)n), dim3(256), 0, st, S);
+    ORBX_HIP(hipGetLastError());
+    ex->st_seq = ex->batch_seq;
+    // the extractor must not overwrite its key points / counts before the kernel is done
+    ORBX_HIP(hipEventRecord(ex->ev_match, st));
+    ex->match_pending = true; ex->copy_covers_match = false;
     return ORBX_OK;
 }
 
@@ -3142,6 +3265,7 @@ struct orbx_keyframe {
     orbx_keypoint *kps = nullptr;
     uint8_t *desc = nullptr;
     float *u_right = nullptr;          // NULL: no mvuRight
+    float *depth = nullptr, *keys_xy = nullptr;   // mvDepth [cap], mvKeys[i].pt [cap][2]; NULL: none (made without depth)
     float *inv_sigma2 = nullptr;       // NULL: no mvInvLevelSigma2 given
     float *scale = nullptr;
     int32_t *count = nullptr;
@@ -3199,7 +3323,7 @@ void keyframe_bow_free(KeyFrameBow *b) {
 
 // one allocation per key frame: rows for `cap` features (28 + 32 [+ 4] + 2 bytes each), the per-level arrays, the count and the grid's 3073 cell offsets
 // (roff >= 0: a fisheye-stereo key frame -- cap = roff + the right camera's rows, a second set of cell offsets; roff < 0: a monocular one)
-int keyframe_alloc(int device, int cap, int roff, bool has_ur, bool has_sigma, int nlevels, const float *bounds4, KeyFramePtr &out) {
+int keyframe_alloc(int device, int cap, int roff, bool has_ur, bool has_sigma, int nlevels, const float *bounds4, KeyFramePtr &out, bool has_depth = false) {
     out.reset(new orbx_keyframe());
     orbx_keyframe *kf = out.get();
     kf->device = device; kf->cap = cap; kf->nlevels = nlevels;
@@ -3211,6 +3335,8 @@ int keyframe_alloc(int device, int cap, int roff, bool has_ur, bool has_sigma, i
     const size_t off_kps = L.add(28 * c), off_desc = L.add(32 * c), off_ur = has_ur ? L.add(4 * c) : 0, off_sg = has_sigma ? L.add(4 * (size_t)kFrameMaxLevels) : 0;
     const size_t off_scale = L.add(4 * (size_t)kFrameMaxLevels), off_count = L.add(8), off_gs = L.add(2 * ((size_t)kGridCells + 1)), off_go = L.add(2 * c);
     const size_t off_gsr = kf->fisheye ? L.add(2 * ((size_t)kGridCells + 1)) : 0;
+    // (behind everything else: a key frame without depth has the size and the layout it had)
+    const size_t off_dep = has_depth ? L.add(4 * c) : 0, off_xy = has_depth ? L.add(8 * c) : 0;
     hipError_t e = hipMalloc((void **)&kf->dev, L.used);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&kf->ready, hipEventDisableTiming);
     if (e != hipSuccess) { set_error(hipGetErrorString(e)); return ORBX_E_HIP; }
@@ -3220,6 +3346,7 @@ int keyframe_alloc(int device, int cap, int roff, bool has_ur, bool has_sigma, i
     kf->scale = (float *)(kf->dev + off_scale); kf->count = (int32_t *)(kf->dev + off_count);
     kf->gstart = (uint16_t *)(kf->dev + off_gs); kf->gorder = (uint16_t *)(kf->dev + off_go);
     if (kf->fisheye) { kf->gstart_r = (uint16_t *)(kf->dev + off_gsr); kf->gorder_r = kf->gorder + kf->roff; }
+    if (has_depth) { kf->depth = (float *)(kf->dev + off_dep); kf->keys_xy = (float *)(kf->dev + off_xy); }
     return ORBX_OK;
 }
 
@@ -3295,30 +3422,39 @@ int keyframe_publish(orbx_matcher *m, KeyFramePtr &kf, int c0, int c1, orbx_keyf
 // From host arrays (arguments checked by the caller).  d: mvKeysUn / mDescriptors [d->n] and the optional mvuRight of a monocular key frame; of a rig
 // mvKeys [d->n = N_left] and ALL N descriptor rows, with kps_right [n_right] = mvKeysRight (monocular: NULL, 0).
 int keyframe_create_host(orbx_matcher *m, bool fisheye, const orbx_frame_desc *d, const orbx_keypoint *kps_right, int n_right,
-                         const float *inv_level_sigma2, orbx_keyframe **out) {
+                         const float *inv_level_sigma2, orbx_keyframe **out, const float *depth = nullptr, const float *keys_xy = nullptr) {
     ORBX_HIP(hipSetDevice(m->device));
     const int nl = d->n, nr = n_right, N = nl + nr, nlv = d->nlevels;
     const float *ur = fisheye ? nullptr : d->u_right;
     const float b[4] = {d->min_x, d->max_x, d->min_y, d->max_y};
     KeyFramePtr kf;
-    ORBX_TRY(keyframe_alloc(m->device, N, fisheye ? nl : -1, ur != nullptr, inv_level_sigma2 != nullptr, nlv, b, kf));
+    ORBX_TRY(keyframe_alloc(m->device, N, fisheye ? nl : -1, ur != nullptr, inv_level_sigma2 != nullptr, nlv, b, kf, depth != nullptr));
     // ONE upload: the rows -- a rig's mvKeysRight right behind its mvKeys (roff = N_left) -- mvuRight and inv_sigma2, staged at the allocation's own
     // offsets (pinned; the context's next call waits before it stages over them)
     const size_t up_end = (size_t)((inv_level_sigma2 ? (uint8_t *)(kf->inv_sigma2 + nlv) : ur ? (uint8_t *)(kf->u_right + N) : kf->desc + 32 * (size_t)N) - kf->dev);
-    ORBX_TRY(m->reserve_staging(up_end));   // the rows go up through it
+    // (with depth: a second range of the same upload, mvDepth and the raw (x, y) rows side by side at the allocation's end)
+    const size_t o_dep = depth ? (size_t)((uint8_t *)kf->depth - kf->dev) : 0, dep_end = depth ? (size_t)((uint8_t *)(kf->keys_xy + 2 * (size_t)N) - kf->dev) : 0;
+    const size_t st_bytes = std::max(up_end, dep_end);
+    ORBX_TRY(m->reserve_staging(st_bytes));   // the rows go up through it
     if (N > 0 || inv_level_sigma2) {
-        uint8_t *st = static_cast<uint8_t *>(m->stage.take(up_end + 16));
+        uint8_t *st = static_cast<uint8_t *>(m->stage.take(st_bytes + 16));
         if (!st) { set_error("staging arena exhausted"); return ORBX_E_INTERNAL; }
-        memset(st, 0, up_end + 16);
+        memset(st, 0, st_bytes + 16);
         const size_t o_kps = (size_t)((uint8_t *)kf->kps - kf->dev);
         if (nl) memcpy(st + o_kps, d->keypoints_un, 28 * (size_t)nl);
         if (nr) memcpy(st + o_kps + 28 * (size_t)nl, kps_right, 28 * (size_t)nr);
         if (N) memcpy(st + (kf->desc - kf->dev), d->descriptors, 32 * (size_t)N);
         if (ur) memcpy(st + ((uint8_t *)kf->u_right - kf->dev), ur, 4 * (size_t)N);
         if (inv_level_sigma2) memcpy(st + ((uint8_t *)kf->inv_sigma2 - kf->dev), inv_level_sigma2, 4 * (size_t)nlv);
+        if (depth && N) {
+            memcpy(st + o_dep, depth, 4 * (size_t)N);
+            float *xy = reinterpret_cast<float *>(st + ((uint8_t *)kf->keys_xy - kf->dev));
+            if (keys_xy) memcpy(xy, keys_xy, 8 * (size_t)N);
+            else for (int i = 0; i < N; i++) { xy[2 * i] = d->keypoints_un[i].x; xy[2 * i + 1] = d->keypoints_un[i].y; }
+        }
         m->dirty = true;
-        const orbx_matcher::Span run = {0, up_end};
-        ORBX_TRY(m->upload_ranges(kf->dev, st, &run, 1));
+        const orbx_matcher::Span run[2] = {{0, up_end}, {o_dep, depth && N ? dep_end - o_dep : 0}};
+        ORBX_TRY(m->upload_ranges(kf->dev, st, run, 2));
     }
     // the in-place form of the frame loaders' kernels: count(s), scale factors, grid_build_wave over the uploaded rows (a grid per camera)
     m->dirty = true;
@@ -3342,7 +3478,8 @@ int keyframe_from_frame(orbx_matcher *m, bool fisheye, orbx_frame *f, const floa
     ORBX_HIP(hipSetDevice(m->device));
     const int cap_l = fisheye ? f->rows_left() : f->rows_n(), cap_r = fisheye ? f->rows_right() : 0;
     KeyFramePtr kf;
-    ORBX_TRY(keyframe_alloc(m->device, cap_l + cap_r, fisheye ? cap_l : -1, f->has_ur, inv_level_sigma2 != nullptr, f->nlevels, f->bounds, kf));
+    const bool with_depth = !fisheye && f->has_depth;
+    ORBX_TRY(keyframe_alloc(m->device, cap_l + cap_r, fisheye ? cap_l : -1, f->has_ur, inv_level_sigma2 != nullptr, f->nlevels, f->bounds, kf, with_depth));
     m->dirty = true;
     if (fisheye) {
         KeyFrameCopyFisheye C;
@@ -3363,6 +3500,10 @@ int keyframe_from_frame(orbx_matcher *m, bool fisheye, orbx_frame *f, const floa
         C.gstart = kf->gstart; C.gorder = kf->gorder; C.cap = cap_l; C.nlevels = f->nlevels;
         if (inv_level_sigma2) memcpy(C.inv_sigma2_host, inv_level_sigma2, sizeof(float) * (size_t)f->nlevels);
         hipLaunchKernelGGL(k_keyframe_copy, dim3(1 + (unsigned)((cap_l + 255) / 256)), dim3(64), 0, m->stream, C);
+        // a handle with depth: mvDepth and the raw (x, y) rows follow in a launch of their own (k_keyframe_copy and its record stay what they were)
+        if (with_depth && cap_l > 0)   // (an empty frame: nothing to copy, and a grid of no blocks is no launch)
+            hipLaunchKernelGGL(k_keyframe_copy_depth, dim3((unsigned)((cap_l + 255) / 256)), dim3(256), 0, m->stream, (const int32_t *)f->count, cap_l,
+                               (const float *)f->depth, (const float *)f->keys_xy, kf->depth, kf->keys_xy);
     }
     kf->src_frame = f; kf->src_seq = f->load_seq;
     return keyframe_publish(m, kf, fisheye ? f->host_left() : f->host_n(), f->host_right(), out);
@@ -3388,6 +3529,16 @@ int orbx_keyframe_create_host(orbx_matcher *m, const orbx_frame_desc *d, const f
         return ORBX_E_BAD_ARG;
     if (d->n > 65535) return ORBX_E_TOO_LARGE;   // 16-bit grid entries, as orbx_fuse_search
     return keyframe_create_host(m, false, d, nullptr, 0, inv_level_sigma2, out);
+}
+
+int orbx_keyframe_create_host_stereo(orbx_matcher *m, const orbx_frame_desc *d, const float *depth, const float *keys_xy, const float *inv_level_sigma2,
+                                     orbx_keyframe **out) {
+    if (out) *out = nullptr;
+    if (!m || !out || !d || d->n < 0 || (d->n > 0 && (!d->keypoints_un || !d->descriptors)) || !d->scale_factors || d->nlevels < 1 ||
+        d->nlevels > kFrameMaxLevels || !d->u_right || !depth)
+        return ORBX_E_BAD_ARG;
+    if (d->n > 65535) return ORBX_E_TOO_LARGE;   // 16-bit grid entries, as orbx_fuse_search
+    return keyframe_create_host(m, false, d, nullptr, 0, inv_level_sigma2, out, depth, keys_xy);
 }
 
 int orbx_keyframe_create_host_fisheye(orbx_matcher *m, const orbx_frame_desc *left, const orbx_keypoint *kps_right, int n_right,
@@ -3683,8 +3834,12 @@ inline BowSide bow_side(const orbx_keyframe *kf) { return bow_side(kf->view(), *
 // same buffers through it: the level tables and the record among the call's uploads, pos / status / the flag (+ the counts as the kernel read them) side
 // by side among its downloads.  The results land here and reach the caller's arrays behind the synchronisation, and only if the flag stayed down.
 static_assert(sizeof(NewPoints) == 544, "the record a triangulating call uploads (tests/test_gpu_new_points.py states its size)");
+static_assert(sizeof(NewPointsStereoRec) == 592, "the record of the `_stereo` forms (tests/test_gpu_stereo_resident.py states its size)");
 struct NewPointsCall {
     NewPoints rec;                      // views, key-frame rows and parameters (new_points_prepare); the arena's addresses are filled in by stage()
+    bool stereo = false;                // the `_stereo` forms: the record that goes up is a NewPointsStereoRec, rec with what follows
+    const float *depth[2] = {nullptr, nullptr}, *keys_xy[2] = {nullptr, nullptr};   // the key frames' mvDepth / raw (x, y) rows (NULL: none)
+    float mb[2] = {0, 0}, mbf[2] = {0, 0};
     const float *sigma2[2];             // the caller's mvLevelSigma2 tables
     const float *dsig[2];
     NewPoints *drec; float *dpos; uint8_t *dstatus; int32_t *dflag;
@@ -3695,19 +3850,27 @@ struct NewPointsCall {
     void carve_up(Carve &C, bool have1, bool have2, const float *d1, const float *d2) {
         dsig[0] = have1 ? d1 : C.up(sigma2[0], (size_t)rec.kf[0].nlevels);
         dsig[1] = have2 ? d2 : C.up(sigma2[1], (size_t)rec.kf[1].nlevels);
-        drec = C.take<NewPoints>(1);
+        drec = stereo ? &C.take<NewPointsStereoRec>(1)->base : C.take<NewPoints>(1);
     }
     void carve_out(Carve &C, int n) { dpos = C.take<float>(3 * (size_t)n); dstatus = C.take<uint8_t>((size_t)n); dflag = C.take<int32_t>(8); }
     int stage(orbx_matcher *m, const int32_t *didx1, const int32_t *dmatch, int n, bool counts) {
         rec.kf[0].sigma2 = dsig[0]; rec.kf[1].sigma2 = dsig[1];
         rec.idx1 = didx1; rec.match = dmatch; rec.pos = dpos; rec.status = dstatus; rec.flag = dflag; rec.n = n; rec.counts_out = counts ? 1 : 0;
-        ORBX_TRY(m->h2d(drec, &rec, sizeof(rec)));
+        if (stereo) {
+            NewPointsStereoRec E;
+            E.base = rec;
+            for (int k = 0; k < 2; k++) { E.depth[k] = depth[k]; E.keys_xy[k] = keys_xy[k]; E.mb[k] = mb[k]; E.mbf[k] = mbf[k]; }
+            ORBX_TRY(m->h2d(drec, &E, sizeof(E)));
+        } else {
+            ORBX_TRY(m->h2d(drec, &rec, sizeof(rec)));
+        }
         ORBX_HIP(m->fill(dflag, 0, sizeof(flag)));
         return ORBX_OK;
     }
     void launch(orbx_matcher *m, bool rig, int n) {
         const dim3 grid((unsigned)((n + kNewPointsBlock - 1) / kNewPointsBlock)), block(kNewPointsBlock);
-        if (rig) hipLaunchKernelGGL(k_new_points<true>, grid, block, 0, m->exec(), (const NewPoints *)drec);
+        if (stereo) hipLaunchKernelGGL(k_new_points_stereo, grid, block, 0, m->exec(), (const NewPoints *)drec);
+        else if (rig) hipLaunchKernelGGL(k_new_points<true>, grid, block, 0, m->exec(), (const NewPoints *)drec);
         else hipLaunchKernelGGL(k_new_points<false>, grid, block, 0, m->exec(), (const NewPoints *)drec);
         ran = true;
     }
@@ -3734,8 +3897,8 @@ struct NewPointsCall {
 
 // the checks both forms share and the host's part of the record; views: orbx_new_points_view (one per key frame) or, rig, orbx_fisheye_view [2] each
 int new_points_prepare(const orbx_matcher *m, bool rig, const orbx_keyframe *kf1, const orbx_keyframe *kf2, const void *views1, const void *views2,
-                       const orbx_new_points_params *par, NewPointsCall &T) {
-    if (!m || !kf1 || !kf2 || !views1 || !views2 || !par || !par->level_sigma2_1 || !par->level_sigma2_2) return ORBX_E_BAD_ARG;
+                       const orbx_new_points_params *par, const orbx_new_points_stereo *st, bool stereo, NewPointsCall &T) {
+    if (!m || !kf1 || !kf2 || !views1 || !views2 || !par || !par->level_sigma2_1 || !par->level_sigma2_2 || (stereo && (!st || rig))) return ORBX_E_BAD_ARG;
     const orbx_keyframe *kfs[2] = {kf1, kf2};
     const void *views[2] = {views1, views2};
     const int nlevels[2] = {par->nlevels_1, par->nlevels_2};
@@ -3754,7 +3917,9 @@ int new_points_prepare(const orbx_matcher *m, bool rig, const orbx_keyframe *kf1
         NewPointsKf &R = T.rec.kf[k];
         R.kps = kfs[k]->kps; R.scale = kfs[k]->scale; R.u_right = kfs[k]->u_right; R.count = kfs[k]->count;
         R.roff = kfs[k]->roff; R.cap = kfs[k]->cap; R.nlevels = kfs[k]->nlevels;
+        if (stereo) { T.depth[k] = kfs[k]->depth; T.keys_xy[k] = kfs[k]->keys_xy; T.mb[k] = k ? st->mb2 : st->mb1; T.mbf[k] = k ? st->mbf2 : st->mbf1; }
     }
+    T.stereo = stereo;
     T.sigma2[0] = par->level_sigma2_1; T.sigma2[1] = par->level_sigma2_2;
     T.rec.ratio_factor = par->ratio_factor; T.rec.inertial = par->inertial ? 1 : 0;
     T.rec.far_points = par->far_points ? 1 : 0; T.rec.th_far_points = par->th_far_points;
@@ -4386,10 +4551,10 @@ int search_for_triangulation_rig(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyfr
 // orbx_keyframe_search_and_triangulate[_fisheye]: the search with k_new_points behind it (run_bow_resident's tri); gate: the kind's gate struct
 int keyframe_search_and_triangulate(orbx_matcher *m, bool rig, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
                                     int check_orientation, const void *gate, const void *views1, const void *views2, const orbx_new_points_params *par,
-                                    int32_t *matches12, float *pos, uint8_t *status, int *n_accepted) {
+                                    const orbx_new_points_stereo *st, bool stereo, int32_t *matches12, float *pos, uint8_t *status, int *n_accepted) {
     if (!matches12 || !pos || !status) return ORBX_E_BAD_ARG;
     NewPointsCall T;
-    ORBX_TRY(new_points_prepare(m, rig, kf1, kf2, views1, views2, par, T));
+    ORBX_TRY(new_points_prepare(m, rig, kf1, kf2, views1, views2, par, st, stereo, T));
     const int nm = rig ? search_for_triangulation_rig(m, kf1, kf2, skip1, skip2, check_orientation, static_cast<const orbx_keyframe_kb8_gate *>(gate), matches12, &T)
                        : search_for_triangulation_pinhole(m, kf1, kf2, skip1, skip2, check_orientation, static_cast<const orbx_keyframe_gate *>(gate), matches12, &T);
     if (nm < 0) return nm;
@@ -4402,10 +4567,10 @@ int keyframe_search_and_triangulate(orbx_matcher *m, bool rig, orbx_keyframe *kf
 // orbx_keyframe_triangulate_pairs[_fisheye]: k_new_points over pairs the host names.  One upload run (idx1, idx2, the two level tables, the record), one
 // launch, one download run (pos, status, the flag and the counts as the kernel read them), one synchronisation.
 int keyframe_triangulate_pairs(orbx_matcher *m, bool rig, orbx_keyframe *kf1, orbx_keyframe *kf2, const void *views1, const void *views2,
-                               const orbx_new_points_params *par, int n_pairs, const int32_t *idx1, const int32_t *idx2, float *pos, uint8_t *status,
-                               int *n_accepted) {
+                               const orbx_new_points_params *par, const orbx_new_points_stereo *st, bool stereo, int n_pairs, const int32_t *idx1,
+                               const int32_t *idx2, float *pos, uint8_t *status, int *n_accepted) {
     NewPointsCall T;
-    ORBX_TRY(new_points_prepare(m, rig, kf1, kf2, views1, views2, par, T));
+    ORBX_TRY(new_points_prepare(m, rig, kf1, kf2, views1, views2, par, st, stereo, T));
     if (n_pairs < 0 || (n_pairs > 0 && (!idx1 || !idx2 || !pos || !status))) return ORBX_E_BAD_ARG;
     const int b1 = kf1->rows_n(), b2 = kf2->rows_n();   // (counts pending: the capacity; the kernel checks against N)
     for (int p = 0; p < n_pairs; p++)
@@ -4468,24 +4633,38 @@ int orbx_keyframe_search_for_triangulation_fisheye(orbx_matcher *m, orbx_keyfram
 int orbx_keyframe_triangulate_pairs(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const orbx_new_points_view *view1,
                                     const orbx_new_points_view *view2, const orbx_new_points_params *par, int n_pairs, const int32_t *idx1,
                                     const int32_t *idx2, float *pos, uint8_t *status, int *n_accepted) {
-    return keyframe_triangulate_pairs(m, false, kf1, kf2, view1, view2, par, n_pairs, idx1, idx2, pos, status, n_accepted);
+    return keyframe_triangulate_pairs(m, false, kf1, kf2, view1, view2, par, nullptr, false, n_pairs, idx1, idx2, pos, status, n_accepted);
+}
+int orbx_keyframe_triangulate_pairs_stereo(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const orbx_new_points_view *view1,
+                                           const orbx_new_points_view *view2, const orbx_new_points_params *par, const orbx_new_points_stereo *st,
+                                           int n_pairs, const int32_t *idx1, const int32_t *idx2, float *pos, uint8_t *status, int *n_accepted) {
+    return keyframe_triangulate_pairs(m, false, kf1, kf2, view1, view2, par, st, true, n_pairs, idx1, idx2, pos, status, n_accepted);
 }
 int orbx_keyframe_triangulate_pairs_fisheye(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const orbx_fisheye_view *views1,
                                             const orbx_fisheye_view *views2, const orbx_new_points_params *par, int n_pairs, const int32_t *idx1,
                                             const int32_t *idx2, float *pos, uint8_t *status, int *n_accepted) {
-    return keyframe_triangulate_pairs(m, true, kf1, kf2, views1, views2, par, n_pairs, idx1, idx2, pos, status, n_accepted);
+    return keyframe_triangulate_pairs(m, true, kf1, kf2, views1, views2, par, nullptr, false, n_pairs, idx1, idx2, pos, status, n_accepted);
 }
 int orbx_keyframe_search_and_triangulate(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
                                          int check_orientation, const orbx_keyframe_gate *gate, const orbx_new_points_view *view1,
                                          const orbx_new_points_view *view2, const orbx_new_points_params *par, int32_t *matches12, float *pos,
                                          uint8_t *status, int *n_accepted) {
-    return keyframe_search_and_triangulate(m, false, kf1, kf2, skip1, skip2, check_orientation, gate, view1, view2, par, matches12, pos, status, n_accepted);
+    return keyframe_search_and_triangulate(m, false, kf1, kf2, skip1, skip2, check_orientation, gate, view1, view2, par, nullptr, false, matches12, pos, status,
+                                           n_accepted);
+}
+int orbx_keyframe_search_and_triangulate_stereo(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
+                                                int check_orientation, const orbx_keyframe_gate *gate, const orbx_new_points_view *view1,
+                                                const orbx_new_points_view *view2, const orbx_new_points_params *par, const orbx_new_points_stereo *st,
+                                                int32_t *matches12, float *pos, uint8_t *status, int *n_accepted) {
+    return keyframe_search_and_triangulate(m, false, kf1, kf2, skip1, skip2, check_orientation, gate, view1, view2, par, st, true, matches12, pos, status,
+                                           n_accepted);
 }
 int orbx_keyframe_search_and_triangulate_fisheye(orbx_matcher *m, orbx_keyframe *kf1, orbx_keyframe *kf2, const uint8_t *skip1, const uint8_t *skip2,
                                                  int check_orientation, const orbx_keyframe_kb8_gate *gate, const orbx_fisheye_view *views1,
                                                  const orbx_fisheye_view *views2, const orbx_new_points_params *par, int32_t *matches12, float *pos,
                                                  uint8_t *status, int *n_accepted) {
-    return keyframe_search_and_triangulate(m, true, kf1, kf2, skip1, skip2, check_orientation, gate, views1, views2, par, matches12, pos, status, n_accepted);
+    return keyframe_search_and_triangulate(m, true, kf1, kf2, skip1, skip2, check_orientation, gate, views1, views2, par, nullptr, false, matches12, pos, status,
+                                           n_accepted);
 }
 
 }  // extern "C"

@@ -175,6 +175,14 @@ class ORBextractor:
     def stereo_batch_device(self, right: "ORBextractor", bf: float, b: float):
         check(self._L.orbx_stereo_batch_device(self._h, right._h, bf, b), "orbx_stereo_batch_device")
 
+    def RGBDBatch(self, d_depth: int, pitch_bytes: int, frame_stride_bytes: int, bf: float):
+        """Frame::ComputeStereoFromRGBD for every frame of the last batch (orbx_rgbd_batch_device): d_depth = DEVICE address of one scaled float32
+        depth image per frame (width x height of the batch, pitch_bytes per row, frame_stride_bytes per image).  Enqueued behind the extraction;
+        stereo_download / stereo_download_all return mvuRight / mvDepth and the count of features with depth, and DeviceFrame.load_stereo_batch
+        copies them on the device.  The images must stay valid until sync() or a download has returned."""
+        check(self._L.orbx_rgbd_batch_device(self._h, C.c_void_p(d_depth) if d_depth else None, pitch_bytes, frame_stride_bytes, bf),
+              "orbx_rgbd_batch_device")
+
     def stereo_download(self, frame: int):
         """Returns (n_matches, mvuRight[N], mvDepth[N]) of `frame` (-1 where unmatched)."""
         cap = self.batch_view().cap

@@ -12,7 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from ._lib import KP_DTYPE, BowKeyFrame, FeatVec, FrameDesc, FuseQueries, KeyFrameGate, KeyFrameKb8Gate, NewPointsParams, NewPointsView, PAIR_PREDICATE, PinholeGate, check, ptr
+from ._lib import KP_DTYPE, BowKeyFrame, FeatVec, FrameDesc, FuseQueries, KeyFrameGate, KeyFrameKb8Gate, NewPointsParams, NewPointsStereo, NewPointsView, PAIR_PREDICATE, PinholeGate, check, ptr
 
 
 @dataclass
@@ -79,11 +79,13 @@ class DeviceFrame:
         self.cap = int(cap)
         self._h = C.c_void_p()
         check(self._L.orbx_frame_create(matcher._h, self.cap, C.byref(self._h)), "orbx_frame_create")
+        matcher._frames[self._h.value] = self._h   # (the owner destroys what is left of its handles before itself: ORBmatcher.__del__)
 
     def __del__(self):
-        if getattr(self, "_h", None):
-            self._L.orbx_frame_destroy(self._h)
-            self._h = None
+        h = getattr(self, "_h", None)
+        if h and self.matcher._frames.pop(h.value, None) is not None:
+            self._L.orbx_frame_destroy(h)
+        self._h = None
 
     def load(self, F: "FrameView"):
         """Upload a host frame once and build its grid (orbx_frame_load_host)."""
@@ -96,6 +98,23 @@ class DeviceFrame:
         bounds = (minX, maxX, minY, maxY) or None (the extractor's camera / image rectangle); scale_factors None = the extractor's."""
         b, sf = _f32(bounds), _f32(scale_factors)
         check(self._L.orbx_frame_load_batch(self._h, extractor._h, int(f), ptr(b), ptr(sf), 0 if sf is None else len(sf)), "orbx_frame_load_batch")
+        return self
+
+    def load_stereo_batch(self, extractor, f: int, bounds=None, scale_factors=None):
+        """load_batch plus the frame's mvuRight, mvDepth and raw key points from the (left) extractor's last stereo_device / rgbd_device stage, copied
+        on the device in the same launch (orbx_frame_load_stereo_batch).  Refused when no stage has run on the extractor's current batch."""
+        b, sf = _f32(bounds), _f32(scale_factors)
+        check(self._L.orbx_frame_load_stereo_batch(self._h, extractor._h, int(f), ptr(b), ptr(sf), 0 if sf is None else len(sf)),
+              "orbx_frame_load_stereo_batch")
+        return self
+
+    def load_host_stereo(self, F: "FrameView", depth, keys_xy=None):
+        """load with mvuRight (F.u_right) required, and mvDepth [n] / the raw mvKeys[i].pt [n, 2] (None: the undistorted points) in the same upload
+        (orbx_frame_load_host_stereo)."""
+        fd = F.c_struct()
+        d, xy = _f32(depth), _f32(keys_xy)
+        assert len(d) == fd.n and (xy is None or xy.shape == (fd.n, 2))
+        check(self._L.orbx_frame_load_host_stereo(self._h, C.byref(fd), ptr(d), ptr(xy)), "orbx_frame_load_host_stereo")   # (staged before it returns)
         return self
 
     def count(self) -> int:
@@ -183,6 +202,19 @@ class DeviceKeyFrame:
         fd = F.c_struct()
         h = C.c_void_p()
         check(_lib.lib().orbx_keyframe_create_host(matcher._h, C.byref(fd), ptr(isg), C.byref(h)), "orbx_keyframe_create_host")   # (staged before it returns)
+        return cls(h)
+
+    @classmethod
+    def create_host_stereo(cls, matcher: "ORBmatcher", F: "FrameView", depth, keys_xy=None, inv_level_sigma2=None) -> "DeviceKeyFrame":
+        """from_host with mvuRight (F.u_right) required, mvDepth [n] and the raw mvKeys[i].pt [n, 2] (None: the undistorted points) in the same
+        upload (orbx_keyframe_create_host_stereo): the key frame the `_stereo` forms of CreateNewMapPoints' triangulation decide stereo pairs on.
+        from_frame of a DeviceFrame loaded with load_stereo_batch / load_host_stereo gives the same object."""
+        isg, d, xy = _f32(inv_level_sigma2), _f32(depth), _f32(keys_xy)
+        fd = F.c_struct()
+        assert len(d) == fd.n and (xy is None or xy.shape == (fd.n, 2))
+        h = C.c_void_p()
+        check(_lib.lib().orbx_keyframe_create_host_stereo(matcher._h, C.byref(fd), ptr(d), ptr(xy), ptr(isg), C.byref(h)),
+              "orbx_keyframe_create_host_stereo")   # (staged before it returns)
         return cls(h)
 
     @classmethod
@@ -359,9 +391,16 @@ class ORBmatcher:
         check(self._L.orbx_matcher_create(device, C.byref(self._h)), "orbx_matcher_create")
         self.mfNNratio = nnratio
         self.mbCheckOrientation = checkOri
+        self._frames = {}   # the live DeviceFrame handles of this matcher
 
     def __del__(self):
         if getattr(self, "_h", None):
+            # A DeviceFrame keeps its owner alive, so it normally goes first.  The collector of reference cycles (a traceback that holds both as
+            # locals) finalizes in any order: the handles that are left are destroyed here, ahead of the context their destruction synchronises.
+            frames = getattr(self, "_frames", {})
+            for h in list(frames.values()):
+                self._L.orbx_frame_destroy(h)
+            frames.clear()
             self._L.orbx_matcher_destroy(self._h)
             self._h = None
 
@@ -858,8 +897,22 @@ class ORBmatcher:
         """The two key frames' views in the form the four calls below hand to the library, for reuse over several calls."""
         return cls._new_points_views(views1, views2, rig)[0]
 
+    def UnprojectStereo(self, frame: DeviceFrame, view, pos=None):
+        """Frame::UnprojectStereo for every feature of a resident frame that holds mvDepth (orbx_frame_unproject_stereo): view = (Rcw, tcw, Ow, fx, fy,
+        cx, cy) or a NewPointsView.  pos (optional, [cap, 3] float32): rows of features with depth > 0 are written, the others keep their values.
+        Returns (n_with_depth, mvuRight [N], mvDepth [N], pos [N, 3])."""
+        v = view if isinstance(view, NewPointsView) else self._new_points_views(view, view, False)[0][0]
+        out = np.zeros((frame.cap, 3), np.float32) if pos is None else pos
+        assert out.dtype == np.float32 and out.shape == (frame.cap, 3) and out.flags.c_contiguous
+        ur, depth = np.zeros(frame.cap, np.float32), np.zeros(frame.cap, np.float32)
+        with_depth = C.c_int(0)
+        check(self._L.orbx_frame_unproject_stereo(self._h, frame._h, C.byref(v), ptr(ur), ptr(depth), ptr(out), C.byref(with_depth)),
+              "orbx_frame_unproject_stereo")
+        n = frame.count()   # (known after the call: no further synchronisation)
+        return with_depth.value, ur[:n], depth[:n], out[:n]
+
     def TriangulatePairsKeyFrames(self, kf1: DeviceKeyFrame, kf2: DeviceKeyFrame, view1, view2, level_sigma2_1, level_sigma2_2, ratio_factor, idx1, idx2,
-                                  inertial=False, far_points=False, th_far_points=0.0, pos=None, rig: bool = False):
+                                  inertial=False, far_points=False, th_far_points=0.0, pos=None, rig: bool = False, stereo=None):
         """The loop body of LocalMapping::CreateNewMapPoints for the pairs (idx1[p], idx2[p]) of two resident key frames
         (orbx_keyframe_triangulate_pairs): unprojection, parallax test, GeometricTools::Triangulate, depth, reprojection, distance and scale-ratio
         tests on the device.  ratio_factor = 1.5f * mfScaleFactor of kf1; idx2[p] = -1: no match.  pos (optional, [n, 3] float32): rows of accepted pairs
@@ -873,8 +926,9 @@ class ORBmatcher:
         assert out.dtype == np.float32 and out.shape == (n, 3) and out.flags.c_contiguous
         status = np.zeros(n, np.uint8)
         acc = C.c_int32(0)
-        fn = "orbx_keyframe_triangulate_pairs_fisheye" if rig else "orbx_keyframe_triangulate_pairs"
-        check(getattr(self._L, fn)(self._h, kf1._h, kf2._h, v1, v2, C.byref(par), n, ptr(i1), ptr(i2), ptr(out), ptr(status), C.byref(acc)), fn)
+        fn = "orbx_keyframe_triangulate_pairs_fisheye" if rig else "orbx_keyframe_triangulate_pairs_stereo" if stereo is not None else "orbx_keyframe_triangulate_pairs"
+        extra = () if stereo is None else (C.byref(stereo),)   # (`st` follows `par`)
+        check(getattr(self._L, fn)(self._h, kf1._h, kf2._h, v1, v2, C.byref(par), *extra, n, ptr(i1), ptr(i2), ptr(out), ptr(status), C.byref(acc)), fn)
         del keep, vkeep
         return acc.value, out, status
 
@@ -886,7 +940,16 @@ class ORBmatcher:
         return self.TriangulatePairsKeyFrames(kf1, kf2, views1, views2, level_sigma2_1, level_sigma2_2, ratio_factor, idx1, idx2, inertial, far_points,
                                               th_far_points, pos, rig=True)
 
-    def _search_and_triangulate(self, fn, kf1, kf2, skip1, skip2, gate, views, par, pos):
+    def TriangulatePairsKeyFramesStereo(self, kf1: DeviceKeyFrame, kf2: DeviceKeyFrame, view1, view2, level_sigma2_1, level_sigma2_2, ratio_factor, mb1, mbf1,
+                                        mb2, mbf2, idx1, idx2, inertial=False, far_points=False, th_far_points=0.0, pos=None):
+        """TriangulatePairsKeyFrames with the member's stereo branches (orbx_keyframe_triangulate_pairs_stereo): mb / mbf = KeyFrame::mb, mbf of each key
+        frame.  A pair with mvuRight >= 0 on a key frame that holds mvDepth (create_host_stereo, from_frame of a depth handle) is decided on the
+        device -- triangulated, or unprojected from its depth (NEWPT_UNPROJECT_FAILED where mvDepth <= 0)."""
+        st = NewPointsStereo(float(mb1), float(mbf1), float(mb2), float(mbf2))
+        return self.TriangulatePairsKeyFrames(kf1, kf2, view1, view2, level_sigma2_1, level_sigma2_2, ratio_factor, idx1, idx2, inertial, far_points,
+                                              th_far_points, pos, stereo=st)
+
+    def _search_and_triangulate(self, fn, kf1, kf2, skip1, skip2, gate, views, par, pos, stereo=None):
         s1, s2 = _u8(skip1), _u8(skip2)
         n1 = kf1.count()
         m12 = np.full(max(n1, 1), -1, np.int32)
@@ -894,21 +957,33 @@ class ORBmatcher:
         assert out.dtype == np.float32 and out.shape == (max(n1, 1), 3) and out.flags.c_contiguous
         status = np.zeros(max(n1, 1), np.uint8)
         acc = C.c_int32(0)
+        extra = () if stereo is None else (C.byref(stereo),)   # (`st` follows `par`)
         n = check(getattr(self._L, fn)(self._h, kf1._h, kf2._h, ptr(s1), ptr(s2), int(self.mbCheckOrientation), C.byref(gate), views[0], views[1],
-                                       C.byref(par), ptr(m12), ptr(out), ptr(status), C.byref(acc)), fn)
+                                       C.byref(par), *extra, ptr(m12), ptr(out), ptr(status), C.byref(acc)), fn)
         return n, m12[:n1], acc.value, out[:n1], status[:n1]
 
     def SearchAndTriangulateResident(self, kf1: DeviceKeyFrame, kf2: DeviceKeyFrame, skip1, skip2, level_sigma2_1, level_sigma2_2, F12, epipole, view1,
-                                     view2, ratio_factor, coarse=False, strict_fp=False, inertial=False, far_points=False, th_far_points=0.0, pos=None):
+                                     view2, ratio_factor, coarse=False, strict_fp=False, inertial=False, far_points=False, th_far_points=0.0, pos=None,
+                                     stereo=None):
         """SearchForTriangulationResident and TriangulatePairsKeyFrames on its match row in one call (orbx_keyframe_search_and_triangulate): one
         launch more than the search, one synchronisation.  Returns (nmatches, matches12 [N1], n_accepted, pos [N1, 3], status [N1])."""
         keep, par = self._new_points_params(kf1, kf2, level_sigma2_1, level_sigma2_2, ratio_factor, inertial, far_points, th_far_points)
         g = KeyFrameGate((C.c_float * 9)(*[float(x) for x in np.asarray(F12, np.float32).ravel()]), float(epipole[0]), float(epipole[1]), int(coarse),
                          int(strict_fp), len(keep[1]), keep[1].ctypes.data)
         vkeep, views = self._new_points_views(view1, view2, False)
-        r = self._search_and_triangulate("orbx_keyframe_search_and_triangulate", kf1, kf2, skip1, skip2, g, views, par, pos)
+        fn = "orbx_keyframe_search_and_triangulate" if stereo is None else "orbx_keyframe_search_and_triangulate_stereo"
+        r = self._search_and_triangulate(fn, kf1, kf2, skip1, skip2, g, views, par, pos, stereo)
         del keep, vkeep
         return r
+
+    def SearchAndTriangulateResidentStereo(self, kf1: DeviceKeyFrame, kf2: DeviceKeyFrame, skip1, skip2, level_sigma2_1, level_sigma2_2, F12, epipole, view1,
+                                           view2, ratio_factor, mb1, mbf1, mb2, mbf2, coarse=False, strict_fp=False, inertial=False, far_points=False,
+                                           th_far_points=0.0, pos=None):
+        """SearchAndTriangulateResident with the member's stereo branches (orbx_keyframe_search_and_triangulate_stereo): the row and the return value are
+        the plain search's, pos / status those of TriangulatePairsKeyFramesStereo on that row."""
+        st = NewPointsStereo(float(mb1), float(mbf1), float(mb2), float(mbf2))
+        return self.SearchAndTriangulateResident(kf1, kf2, skip1, skip2, level_sigma2_1, level_sigma2_2, F12, epipole, view1, view2, ratio_factor, coarse,
+                                                 strict_fp, inertial, far_points, th_far_points, pos, stereo=st)
 
     def SearchAndTriangulateResidentKB8(self, kf1: DeviceKeyFrame, kf2: DeviceKeyFrame, skip1, skip2, level_sigma2_1, level_sigma2_2, cam1, cam2, R12, t12,
                                         views1, views2, ratio_factor, coarse=False, inertial=False, far_points=False, th_far_points=0.0, pos=None):
