@@ -786,8 +786,9 @@ int orbx_bow_transform(orbx_matcher *m, const orbx_vocabulary *voc, const uint8_
                        int32_t *word_id, int32_t *node_id);
 /* The stop words of TemplatedVocabulary::transform(features, BowVector&, FeatureVector&, levelsup) (TemplatedVocabulary.h:1151-1193): a
  * feature enters the FeatureVector only `if (w > 0)`.  weight[id] = m_words[id]->weight for every word id 0 .. n_words - 1 (n_words above the
- * largest word id of the tree, ORBX_E_BAD_ARG otherwise); only the sign is kept on the device.  A vocabulary without weights stops no word.
- * Takes effect at the next orbx_frame_compute_bow. */
+ * largest word id of the tree, ORBX_E_BAD_ARG otherwise).  The device keeps the sign of every weight for the stop-word test and, beside it, the
+ * weights themselves as doubles: the tf-idf values of orbx_frame_bow_vector / orbx_keyframe_bow_vector and the key-frame database (below).  A
+ * vocabulary without weights stops no word and has no BowVector.  Takes effect at the next orbx_frame_compute_bow. */
 int orbx_vocabulary_set_word_weights(orbx_vocabulary *voc, const double *weight, int n_words);
 
 /* ---- BoW on the device-resident frame: Tracking::TrackReferenceKeyFrame and Tracking::Relocalization ----
@@ -795,8 +796,8 @@ int orbx_vocabulary_set_word_weights(orbx_vocabulary *voc, const double *weight,
  * on the handle's descriptors: nothing of the frame is uploaded.  The frame's FeatureVector (ascending node ids, each with its feature indices in
  * ascending order, stopped features left out: the std::map order of FeatureVector::addFeature) stays in the handle.  Node ids are
  * orbx_bow_transform's (node 0 for a leaf above level L - levelsup).  word_id / node_id (optional, N entries each; N may be unknown to the caller
- * after orbx_frame_load_batch: buffers of the handle's capacity always suffice) return the per-feature ids -- the adapter still folds the word ids
- * into mBowVec (tf-idf, L1) for the KeyFrameDatabase.  Both NULL: asynchronous, nothing waits.  The handle keeps the result, the vocabulary and
+ * after orbx_frame_load_batch: buffers of the handle's capacity always suffice) return the per-feature ids; mBowVec itself (tf-idf, L1) is built
+ * on the device from the kept ids: orbx_frame_bow_vector and the orbx_keyframe_database, below.  Both NULL: asynchronous, nothing waits.  The handle keeps the result, the vocabulary and
  * levelsup until its next load.  ORBX_E_BAD_ARG for a handle of another matcher or a vocabulary on another device, before anything is enqueued. */
 int orbx_frame_compute_bow(orbx_matcher *m, orbx_frame *f, const orbx_vocabulary *voc, int levelsup, int32_t *word_id, int32_t *node_id);
 /* One key frame of a SearchByBoW batch: mDescriptors (n x 32), mvKeysUn[i].angle, valid[i] = GetMapPointMatches()[i] present and !isBad()
@@ -1423,6 +1424,77 @@ int orbx_keyframe_search_and_triangulate_stereo(orbx_matcher *m, orbx_keyframe *
                                                 int check_orientation, const orbx_keyframe_gate *gate, const orbx_new_points_view *view1,
                                                 const orbx_new_points_view *view2, const orbx_new_points_params *par,
                                                 const orbx_new_points_stereo *st, int32_t *matches12, float *pos, uint8_t *status, int *n_accepted);
+
+/* ---- The BowVector on the device and the key-frame database: KeyFrameDatabase::add / erase / clear and the first halves of
+ * DetectRelocalizationCandidates / DetectNBestCandidates (PARITY UNPINNED: DBoW2 and KeyFrameDatabase.cc are not compiled against this library by
+ * any test; what follows restates them and the tests compare with that restatement, bit for bit) ----
+ * TemplatedVocabulary::transform(features, v, fv, levelsup) with TF_IDF weighting and L1_NORM scoring (TemplatedVocabulary.h:1151-1193), the BowVector
+ * half:
+ *   for every feature, in feature order:  transform(*fit, id, w, &nid, levelsup);  if (w > 0) v.addWeight(id, w);
+ *   BowVector::addWeight(id, w):  a new word is inserted with the value w; a word that is there gets `vit->second += w` -- ONE double addition per
+ *         occurrence.  All occurrences of a word add the same w, so the feature order does not matter, but the NUMBER of sequential additions does:
+ *         w added five times to w differs from 6.0 * w for about half of all doubles (two to five occurrences are exact).
+ *   v.normalize(L1):  norm = 0.0;  for every entry of the std::map, in ascending word id:  norm += fabs(value);  if (norm > 0.0) every value /= norm.
+ * L1Scoring::score(v1, v2) (ScoringObject.cc), v1 the query's vector, v2 the key frame's:
+ *   score = 0;  over the words both hold, in ascending id:  score += fabs(vi - wi) - fabs(vi) - fabs(wi);   (left to right)
+ *   return -score / 2.0;                                    (a pair without a common word scores -0.0)
+ * No expression holds a multiply-add, so contraction cannot fork it; the ORDER of the additions is the whole parity question -- a tree or a
+ * per-lane partial sum differs from the sequential one in the last bit for most inputs -- and every sum here runs in word order on one accumulator.
+ * KeyFrameDatabase::DetectRelocalizationCandidates(F) / DetectNBestCandidates(pKF, ...) (KeyFrameDatabase.cc), first halves:
+ *   mnRelocWords / mnPlaceRecognitionWords of a key frame = the words its mBowVec shares with the query's (the inverted-file walk counts them);
+ *   DetectNBestCandidates skips the key frames of spConnectedKF before it counts, so they do not enter the maximum;
+ *   maxCommonWords = the largest count;  int minCommonWords = maxCommonWords * 0.8f;   (int -> float, a float product, truncation)
+ *   every key frame with more than minCommonWords common words gets si = score(query, key frame);  no key frame sharing a word: an empty result.
+ * Here the inverted file is replaced by brute force over all slots (sparse-vector arithmetic on resident data).  Left to the host: everything
+ * behind these lines -- GetBestCovisibilityKeyFrames, the accumulated scores, 0.75f * bestAccScore, the map filter.
+ *
+ * orbx_frame_bow_vector / orbx_keyframe_bow_vector: mBowVec of a handle that has BoW (orbx_frame_compute_bow[_fisheye], orbx_keyframe_compute_bow
+ *   [_fisheye] / orbx_keyframe_bow_from_frame[_fisheye]): word_id ascending, value normalised, *n_words entries each, built on the device from the
+ *   kept per-feature word ids (k_bow_vector).  Handles of both kinds: for a fisheye-stereo handle the rows of both cameras form ONE vector over all
+ *   N rows, as Frame::ComputeBoW makes it.  The count may still be on the device only: buffers of the handle's capacity (a key frame's: N, or the
+ *   capacity of the handle it was made from) always suffice.  ORBX_E_BAD_ARG: no BoW, a vocabulary without orbx_vocabulary_set_word_weights, a
+ *   handle of another matcher / device.  One launch, one download run, one synchronisation.
+ * orbx_keyframe_database: n_slots rows of words_cap entries (word id, double value) and each row's word count, owned by the database, on one
+ *   device; any matcher context of that device may write and query it (another device: ORBX_E_BAD_ARG).  The caller numbers the slots, as it
+ *   numbers an orbx_map's.  n_slots in [1, ORBX_MAX_DATABASE_SLOTS], words_cap in [1, 16384] (ORBX_E_TOO_LARGE beyond, ORBX_E_BAD_ARG below).
+ *   _add: the key frame's BowVector is built straight into the row of `slot` (k_bow_vector), replacing what the slot held; stream order, no host
+ *     wait.  The row is a COPY: the key frame may be destroyed afterwards.  Refused before anything is enqueued: a key frame without BoW or whose
+ *     vocabulary has no weights, a vocabulary or levelsup other than that of the first key frame added (since the last _clear), a key frame or a
+ *     database of another device, a slot outside [0, n_slots) (all ORBX_E_BAD_ARG); a key frame whose row bound exceeds words_cap
+ *     (ORBX_E_TOO_LARGE; the bound is N where the host knows it, the key frame's capacity otherwise).
+ *   _erase: the slot is empty from here on, in stream order (an empty slot: no effect).  _clear: every slot.
+ *   _query_frame / _query_keyframe: the query's BowVector is built in the call's arena (the query key frame need not be in the database; it counts
+ *     against its own slot if it is), every slot is compared with it (k_bow_score) and the candidates are chosen (k_bow_select).
+ *     exclude [n_exclude]: slots that are not counted (spConnectedKF), each in [0, n_slots).  min_ratio in [0, 1]: the reference's 0.8f.
+ *     n_common / score (optional, n_slots entries each): the common words of every slot, -1 for an empty or excluded one, and
+ *     L1Scoring::score(query, slot) of every counted slot, -0.0 included (0.0 where n_common is -1).
+ *     The candidates: the slots with n_common > (int)((float)max_common * min_ratio) and at least one common word, in ascending slot order, with
+ *     their counts and scores (cand_common / cand_score optional).  *n_cand is the true count also when it exceeds cand_cap: the list is then cut
+ *     and the status stays ORBX_OK.  *max_common = maxCommonWords; 0 gives *n_cand = 0.
+ *     Refused before anything is enqueued (ORBX_E_BAD_ARG): a source without BoW or weights, a vocabulary / levelsup other than the database's, an
+ *     exclude id out of range, min_ratio outside [0, 1], another device.
+ *     Cost shape: one upload run (the exclude list), three launches whatever n_slots is, one download run, one synchronisation.
+ * Ordering, as an orbx_map's: the database holds one event, `written`.  _add, _erase and _clear make their context's stream wait for the previous
+ * `written`, enqueue and record the next; a query makes its stream wait for `written` ahead of its kernels until a query that did so has
+ * synchronised.  So writes and queries issued one after the other, from any contexts and threads, take effect in the order of the calls, with no
+ * host synchronisation between an add and the query behind it.  NOT ordered: a write against a query that is still RUNNING -- as under
+ * KeyFrameDatabase::mMutex, the caller does not write while another thread's query has not returned.  Destroy a database after every call that names
+ * it has returned and before the matchers that used it; orbx_keyframe_database_destroy waits for `written`. */
+typedef struct orbx_keyframe_database orbx_keyframe_database;
+#define ORBX_MAX_DATABASE_SLOTS (1 << 20)
+int orbx_frame_bow_vector(orbx_matcher *m, orbx_frame *f, int32_t *word_id, double *value, int *n_words);
+int orbx_keyframe_bow_vector(orbx_matcher *m, orbx_keyframe *kf, int32_t *word_id, double *value, int *n_words);
+int orbx_keyframe_database_create(int device, int n_slots, int words_cap, orbx_keyframe_database **out);
+void orbx_keyframe_database_destroy(orbx_keyframe_database *db);
+int orbx_keyframe_database_add(orbx_matcher *m, orbx_keyframe_database *db, int slot, orbx_keyframe *kf);
+int orbx_keyframe_database_erase(orbx_matcher *m, orbx_keyframe_database *db, int slot);
+int orbx_keyframe_database_clear(orbx_matcher *m, orbx_keyframe_database *db);
+int orbx_keyframe_database_query_frame(orbx_matcher *m, orbx_keyframe_database *db, orbx_frame *f, const int32_t *exclude, int n_exclude,
+                                       float min_ratio, int32_t *n_common, double *score, int32_t *cand_slot, int32_t *cand_common,
+                                       double *cand_score, int cand_cap, int *n_cand, int *max_common);
+int orbx_keyframe_database_query_keyframe(orbx_matcher *m, orbx_keyframe_database *db, orbx_keyframe *kf, const int32_t *exclude, int n_exclude,
+                                          float min_ratio, int32_t *n_common, double *score, int32_t *cand_slot, int32_t *cand_common,
+                                          double *cand_score, int cand_cap, int *n_cand, int *max_common);
 
 const char *orbx_last_error(void);
 const char *orbx_status_string(int status);

@@ -220,6 +220,9 @@ SYMBOLS = [
     "orbx_keyframe_search_and_triangulate_fisheye",
     "orbx_rgbd_batch_device", "orbx_frame_load_stereo_batch", "orbx_frame_load_host_stereo", "orbx_frame_unproject_stereo",
     "orbx_keyframe_create_host_stereo", "orbx_keyframe_triangulate_pairs_stereo", "orbx_keyframe_search_and_triangulate_stereo",
+    "orbx_frame_bow_vector", "orbx_keyframe_bow_vector", "orbx_keyframe_database_create", "orbx_keyframe_database_destroy",
+    "orbx_keyframe_database_add", "orbx_keyframe_database_erase", "orbx_keyframe_database_clear", "orbx_keyframe_database_query_frame",
+    "orbx_keyframe_database_query_keyframe",
 ]
 
 
@@ -404,6 +407,16 @@ def lib() -> C.CDLL:
                                                                vp, vp, vp, vp]
     L.orbx_frame_track_last_frame_fisheye_map.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp, f32, i32, i32, vp, vp, vp, vp]
     L.orbx_frame_search_by_projection_keyframe_fisheye_map.argtypes = [vp, vp, vp, vp, f32, vp, vp, i32, vp, f32, f32, i32, vp, vp, vp, vp]
+    L.orbx_frame_bow_vector.argtypes = [vp, vp, vp, vp, C.POINTER(i32)]
+    L.orbx_keyframe_bow_vector.argtypes = [vp, vp, vp, vp, C.POINTER(i32)]
+    L.orbx_keyframe_database_create.argtypes = [i32, i32, i32, C.POINTER(vp)]
+    L.orbx_keyframe_database_destroy.argtypes = [vp]
+    L.orbx_keyframe_database_destroy.restype = None
+    L.orbx_keyframe_database_add.argtypes = [vp, vp, i32, vp]
+    L.orbx_keyframe_database_erase.argtypes = [vp, vp, i32]
+    L.orbx_keyframe_database_clear.argtypes = [vp, vp]
+    L.orbx_keyframe_database_query_frame.argtypes = [vp, vp, vp, vp, i32, f32, vp, vp, vp, vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]
+    L.orbx_keyframe_database_query_keyframe.argtypes = [vp, vp, vp, vp, i32, f32, vp, vp, vp, vp, vp, i32, C.POINTER(i32), C.POINTER(i32)]
     L.orbx_keyframe_from_frame_fisheye.argtypes = [vp, vp, vp, C.POINTER(vp)]
     L.orbx_keyframe_create_host_fisheye.argtypes = [vp, C.POINTER(FrameDesc), vp, i32, vp, C.POINTER(vp)]
     L.orbx_keyframe_counts.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]

@@ -103,6 +103,9 @@ public:
     // >= Nleft are the right camera's); the FeatureVector stays here for ORBmatcher::SearchByBoWFisheye
     inline void ComputeBoWFisheye(ORBmatcher &matcher, const ORBVocabularyDevice &voc, int levelsup = 4, std::vector<int32_t> *wordId = nullptr,
                                   std::vector<int32_t> *nodeId = nullptr);
+    // Frame::mBowVec after ComputeBoW / ComputeBoWFisheye (orbx_frame_bow_vector): ascending word ids and their normalised tf-idf values, built on the
+    // device from the kept word ids.  One synchronisation.
+    inline void BowVector(ORBmatcher &matcher, std::vector<int32_t> &wordId, std::vector<double> &value);
     orbx_frame *handle() const { return f_; }
     int capacity() const { return cap_; }
 
@@ -161,6 +164,8 @@ public:
     // the mBowVec(F.mBowVec), mFeatVec(F.mFeatVec) part of KeyFrame::KeyFrame(Frame&) (orbx_keyframe_bow_from_frame): a device-to-device copy from the
     // DeviceFrame this key frame was made from, after its ComputeBoW and before its next load; asynchronous
     inline void BowFromFrame(ORBmatcher &matcher, DeviceFrame &frame);
+    // KeyFrame::mBowVec of a key frame that has BoW (orbx_keyframe_bow_vector): ascending word ids and their normalised values
+    inline void BowVector(ORBmatcher &matcher, std::vector<int32_t> &wordId, std::vector<double> &value);
     orbx_keyframe *handle() const { return kf_; }
 
 private:
@@ -198,6 +203,48 @@ public:
 
 private:
     orbx_map *map_ = nullptr;
+};
+
+// The BowVectors of a KeyFrameDatabase's key frames, resident on the device (orbx_keyframe_database): nSlots rows of at most wordsCap words, in slots
+// the caller numbers (one int in KeyFrame).  It belongs to no matcher: every ORBmatcher of its device may write and query it.  add() at
+// KeyFrameDatabase::add, erase() / clear() at the members of those names; queryFrame() / queryKeyFrame() are the first halves of
+// DetectRelocalizationCandidates / DetectNBestCandidates -- the common words and L1 scores of every slot and the slots above minCommonWords -- and the
+// covisibility accumulation behind them stays on the host.  The caller does not write while another thread's query is running
+// (KeyFrameDatabase::mMutex).  Destroy it only when no call that was handed it is running.
+class DeviceKeyFrameDatabase {
+public:
+    struct Candidates {
+        int nCandidates = 0, maxCommonWords = 0;        // nCandidates is the true count; the lists hold at most the capacity asked for
+        std::vector<int32_t> slot, commonWords;         // ascending slots with more than int(maxCommonWords * minRatio) common words
+        std::vector<double> score;                      // L1Scoring::score(query, slot)
+        std::vector<int32_t> nCommon;                   // full arrays (on request): per slot, -1 for an empty or excluded one
+        std::vector<double> allScores;
+    };
+    DeviceKeyFrameDatabase(int nSlots, int wordsCap, int device = 0) : nSlots_(nSlots) {
+        check(orbx_keyframe_database_create(device, nSlots, wordsCap, &db_), "orbx_keyframe_database_create");
+    }
+    ~DeviceKeyFrameDatabase() { orbx_keyframe_database_destroy(db_); }
+    DeviceKeyFrameDatabase(const DeviceKeyFrameDatabase &) = delete;
+    DeviceKeyFrameDatabase &operator=(const DeviceKeyFrameDatabase &) = delete;
+    // the key frame's BowVector into `slot`; does not wait.  The row is a copy: the key frame may be destroyed afterwards
+    inline void add(ORBmatcher &matcher, int slot, DeviceKeyFrame &kf);
+    inline void erase(ORBmatcher &matcher, int slot);
+    inline void clear(ORBmatcher &matcher);
+    // exclude: slots left out of the count (spConnectedKF); candCap < 0: nSlots; full: also nCommon / allScores of every slot
+    inline Candidates queryFrame(ORBmatcher &matcher, DeviceFrame &frame, const std::vector<int32_t> &exclude = {}, float minRatio = 0.8f, int candCap = -1,
+                                 bool full = false);
+    inline Candidates queryKeyFrame(ORBmatcher &matcher, DeviceKeyFrame &kf, const std::vector<int32_t> &exclude = {}, float minRatio = 0.8f,
+                                    int candCap = -1, bool full = false);
+    orbx_keyframe_database *handle() const { return db_; }
+
+private:
+    static void check(int st, const char *what) {
+        if (st < 0) throw std::runtime_error(std::string(what) + ": " + orbx_status_string(st) + " " + orbx_last_error());
+    }
+    template <class Fn, class H> Candidates query(Fn fn, const char *what, ORBmatcher &matcher, H *src, const std::vector<int32_t> &exclude, float minRatio,
+                                                  int candCap, bool full);
+    orbx_keyframe_database *db_ = nullptr;
+    int nSlots_ = 0;
 };
 
 class ORBmatcher {
@@ -1482,6 +1529,51 @@ inline void DeviceKeyFrame::ComputeBoW(ORBmatcher &matcher, const ORBVocabularyD
     check(compute(matcher.handle(), kf_, voc.handle(), levelsup, w.data(), nd.data()));
     if (wordId) wordId->assign(w.begin(), w.begin() + n);
     if (nodeId) nodeId->assign(nd.begin(), nd.begin() + n);
+}
+
+inline void DeviceFrame::BowVector(ORBmatcher &matcher, std::vector<int32_t> &wordId, std::vector<double> &value) {
+    wordId.assign((size_t)std::max(cap_, 1), 0); value.assign((size_t)std::max(cap_, 1), 0.0);
+    int n = 0;
+    check(orbx_frame_bow_vector(matcher.handle(), f_, wordId.data(), value.data(), &n), "orbx_frame_bow_vector");
+    wordId.resize((size_t)n); value.resize((size_t)n);
+}
+
+inline void DeviceKeyFrame::BowVector(ORBmatcher &matcher, std::vector<int32_t> &wordId, std::vector<double> &value) {
+    const size_t cap = (size_t)std::max(count(), 1);   // (the buffers hold N entries)
+    wordId.assign(cap, 0); value.assign(cap, 0.0);
+    int n = 0;
+    const int st = orbx_keyframe_bow_vector(matcher.handle(), kf_, wordId.data(), value.data(), &n);
+    if (st < 0) throw std::runtime_error(std::string("orbx_keyframe_bow_vector: ") + orbx_status_string(st) + " " + orbx_last_error());
+    wordId.resize((size_t)n); value.resize((size_t)n);
+}
+
+inline void DeviceKeyFrameDatabase::add(ORBmatcher &matcher, int slot, DeviceKeyFrame &kf) {
+    check(orbx_keyframe_database_add(matcher.handle(), db_, slot, kf.handle()), "orbx_keyframe_database_add");
+}
+inline void DeviceKeyFrameDatabase::erase(ORBmatcher &matcher, int slot) {
+    check(orbx_keyframe_database_erase(matcher.handle(), db_, slot), "orbx_keyframe_database_erase");
+}
+inline void DeviceKeyFrameDatabase::clear(ORBmatcher &matcher) { check(orbx_keyframe_database_clear(matcher.handle(), db_), "orbx_keyframe_database_clear"); }
+template <class Fn, class H>
+DeviceKeyFrameDatabase::Candidates DeviceKeyFrameDatabase::query(Fn fn, const char *what, ORBmatcher &matcher, H *src, const std::vector<int32_t> &exclude,
+                                                                 float minRatio, int candCap, bool full) {
+    Candidates c;
+    const int cap = candCap < 0 ? nSlots_ : candCap;
+    c.slot.assign((size_t)std::max(cap, 1), 0); c.commonWords.assign((size_t)std::max(cap, 1), 0); c.score.assign((size_t)std::max(cap, 1), 0.0);
+    if (full) { c.nCommon.assign((size_t)nSlots_, -1); c.allScores.assign((size_t)nSlots_, 0.0); }
+    check(fn(matcher.handle(), db_, src, exclude.empty() ? nullptr : exclude.data(), (int)exclude.size(), minRatio, full ? c.nCommon.data() : nullptr,
+             full ? c.allScores.data() : nullptr, c.slot.data(), c.commonWords.data(), c.score.data(), cap, &c.nCandidates, &c.maxCommonWords), what);
+    const size_t k = (size_t)std::min(c.nCandidates, cap);
+    c.slot.resize(k); c.commonWords.resize(k); c.score.resize(k);
+    return c;
+}
+inline DeviceKeyFrameDatabase::Candidates DeviceKeyFrameDatabase::queryFrame(ORBmatcher &matcher, DeviceFrame &frame, const std::vector<int32_t> &exclude,
+                                                                             float minRatio, int candCap, bool full) {
+    return query(orbx_keyframe_database_query_frame, "orbx_keyframe_database_query_frame", matcher, frame.handle(), exclude, minRatio, candCap, full);
+}
+inline DeviceKeyFrameDatabase::Candidates DeviceKeyFrameDatabase::queryKeyFrame(ORBmatcher &matcher, DeviceKeyFrame &kf, const std::vector<int32_t> &exclude,
+                                                                                float minRatio, int candCap, bool full) {
+    return query(orbx_keyframe_database_query_keyframe, "orbx_keyframe_database_query_keyframe", matcher, kf.handle(), exclude, minRatio, candCap, full);
 }
 
 inline void DeviceKeyFrame::BowFromFrame(ORBmatcher &matcher, DeviceFrame &frame) {

@@ -19,6 +19,7 @@
 
 #include "matcher_kernels.hip.h"
 #include "geometry_kernels.hip.h"
+#include "bow_database_kernels.hip.h"
 #include "extractor_state.h"
 #include "matcher_context.h"
 
@@ -75,6 +76,7 @@ struct orbx_vocabulary {
     uint8_t *node_desc = nullptr;
     int max_word = -1;                 // the largest word id of the tree
     uint8_t *word_pos = nullptr;       // [n_words] m_words[id]->weight > 0 (orbx_vocabulary_set_word_weights); NULL: no word is stopped
+    double *weight = nullptr;          // [n_words] m_words[id]->weight as given (k_bow_vector's tf-idf); NULL with word_pos
     int n_words = 0;
     std::vector<int> depth_nodes;      // nodes at depth d of the tree (root: depth 0), counted once at creation: the host's bound on a FeatureVector's node count
     int node_bound(int levelsup) const {   // node ids of TemplatedVocabulary::transform at level L - levelsup: the nodes of that depth, or node 0 (a leaf above it / a level <= 0)
@@ -2901,21 +2903,27 @@ extern "C" void orbx_vocabulary_destroy(orbx_vocabulary *v) {
     (void)hipSetDevice(v->device);
     (void)hipFree(v->child_ptr); (void)hipFree(v->child_idx); (void)hipFree(v->word_id); (void)hipFree(v->node_desc);
     if (v->word_pos) (void)hipFree(v->word_pos);
+    if (v->weight) (void)hipFree(v->weight);
     delete v;
 }
 
-// the stop-word test of TemplatedVocabulary::transform (`if (w > 0)`, TemplatedVocabulary.h:1170): only the sign of each word's weight is kept
+// the stop-word test of TemplatedVocabulary::transform (`if (w > 0)`, TemplatedVocabulary.h:1170) reads the sign of each word's weight (word_pos);
+// the weights themselves stay beside it for the BowVector (k_bow_vector)
 extern "C" int orbx_vocabulary_set_word_weights(orbx_vocabulary *v, const double *weight, int n_words) {
     if (!v || !weight || n_words <= v->max_word || n_words <= 0) return ORBX_E_BAD_ARG;   // every word id of the tree needs a weight
     std::vector<uint8_t> pos((size_t)n_words);
     for (int i = 0; i < n_words; i++) pos[i] = weight[i] > 0 ? 1 : 0;
     ORBX_HIP(hipSetDevice(v->device));
     uint8_t *d = nullptr;
+    double *dw = nullptr;
     ORBX_HIP(hipMalloc((void **)&d, (size_t)n_words));
     hipError_t e = hipMemcpy(d, pos.data(), (size_t)n_words, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); set_error(hipGetErrorString(e)); return ORBX_E_HIP; }
+    if (e == hipSuccess) e = hipMalloc((void **)&dw, 8 * (size_t)n_words);
+    if (e == hipSuccess) e = hipMemcpy(dw, weight, 8 * (size_t)n_words, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); if (dw) (void)hipFree(dw); set_error(hipGetErrorString(e)); return ORBX_E_HIP; }
     if (v->word_pos) (void)hipFree(v->word_pos);
-    v->word_pos = d; v->n_words = n_words;
+    if (v->weight) (void)hipFree(v->weight);
+    v->word_pos = d; v->weight = dw; v->n_words = n_words;
     return ORBX_OK;
 }
 
@@ -4960,3 +4968,289 @@ extern "C" int orbx_frame_search_by_projection_keyframe_fisheye_map(orbx_matcher
                     kf->roff, nullptr};
     return track_run(m, cur, occupied, tr, n_ids, nullptr, max_dist, check_orientation, match, false, true);
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// The BowVector of a resident handle and the key-frame database (include/orbx.h, orbx_keyframe_database; PARITY UNPINNED).  A BowVector is
+// (ascending word ids, normalised double values, their count) wherever it lies: a row of the database, or arena space for a query and for
+// orbx_frame_bow_vector / orbx_keyframe_bow_vector.  One kernel builds it from the word ids a handle keeps (k_bow_vector); a query is that kernel,
+// k_bow_score over all slots and k_bow_select -- three launches whatever n_slots is.
+// ---------------------------------------------------------------------------------------------------------
+struct orbx_keyframe_database {
+    int device = 0, n_slots = 0, words_cap = 0;
+    uint8_t *dev = nullptr;            // one allocation, carved below
+    int32_t *row_n = nullptr;          // [n_slots] words of the slot's vector, -1: empty
+    int32_t *row_word = nullptr;       // [n_slots][words_cap]
+    double *row_val = nullptr;         // [n_slots][words_cap]
+    hipEvent_t written = nullptr;      // recorded behind the newest add / erase / clear, on the writing context's stream
+    std::mutex mu;                     // guards everything below and the re-recording of `written`
+    uint64_t write_seq = 0;            // writes recorded so far
+    uint64_t seen_seq = 0;             // the newest write a query has waited for AND synchronised behind
+    const orbx_vocabulary *voc = nullptr;   // of the first key frame added (since the last clear); every other must match, and so must a query
+    int levelsup = 0;
+};
+
+namespace {
+
+// what a BowVector is built from: the rows and the BoW arrays of a frame handle or of a key frame (kf != NULL: its events are waited for)
+struct BowSource { HandleRows rows; const BowArrays *bow; orbx_keyframe *kf; };
+struct BowVecDst { int32_t *word; double *val; int32_t *n; int cap; };
+
+// the checks every entry point makes of its source before anything is enqueued
+int bow_source_of_frame(const orbx_matcher *m, const orbx_frame *f, BowSource *out) {
+    if (!m || !f || f->owner != m || !f->bow_valid) return ORBX_E_BAD_ARG;
+    *out = BowSource{f->view(), &f->bow, nullptr};
+    return ORBX_OK;
+}
+int bow_source_of_keyframe(const orbx_matcher *m, orbx_keyframe *kf, BowSource *out) {
+    if (!m || !kf || kf->device != m->device) return ORBX_E_BAD_ARG;
+    const KeyFrameBow *b = kf->bow.load(std::memory_order_acquire);
+    if (!b) return ORBX_E_BAD_ARG;
+    *out = BowSource{kf->view(), b, kf};
+    return ORBX_OK;
+}
+int bow_source_ok(const BowSource &s) {
+    if (!s.bow->voc || !s.bow->voc->weight) return ORBX_E_BAD_ARG;   // tf-idf needs the weights (orbx_vocabulary_set_word_weights)
+    if (s.rows.feats() > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;   // (the word ids are sorted in LDS)
+    return ORBX_OK;
+}
+inline int bow_sort_cap(const BowSource &s) {
+    int sort_cap = 1;
+    while (sort_cap < s.rows.feats()) sort_cap <<= 1;
+    return sort_cap;
+}
+hipError_t launch_bow_vector(hipStream_t st, const BowSource &s, const BowVecDst &d) {
+    const int sort_cap = bow_sort_cap(s);
+    const size_t lds = (size_t)kBowVecLdsHead + 4 * (size_t)sort_cap;
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void *)k_bow_vector, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    const HandleRows &r = s.rows;
+    const orbx_vocabulary *v = s.bow->voc;
+    BowVecSrc S;
+    memset(&S, 0, sizeof(S));
+    S.count = r.count; S.cap = r.cap;
+    S.nl_host = r.fisheye ? r.nl : r.n; S.nr_host = r.fisheye ? r.nr : 0; S.roff = r.fisheye ? r.roff : r.cap;
+    S.word = s.bow->word; S.word_pos = v->word_pos; S.weight = v->weight; S.n_words = v->n_words;
+    S.out_word = d.word; S.out_val = d.val; S.out_n = d.n; S.out_cap = d.cap;
+    hipLaunchKernelGGL(k_bow_vector, dim3(1), dim3(1024), lds, st, S, sort_cap);
+    return hipGetLastError();
+}
+
+// mBowVec of a handle that has BoW, home: built in the call's arena, one download run (the handle's bound on its words), one synchronisation
+int bow_vector_home(orbx_matcher *m, const BowSource &s, int32_t *word_id, double *value, int *n_words) {
+    if (!word_id || !value || !n_words) return ORBX_E_BAD_ARG;
+    ORBX_TRY(bow_source_ok(s));
+    ORBX_HIP(hipSetDevice(m->device));
+    const size_t cap = (size_t)std::max(s.rows.feats(), 1);
+    BowVecDst d;
+    ORBX_TRY(m->carve([&](Carve &A) { d.word = A.take<int32_t>(cap); d.val = A.take<double>(cap); d.n = A.take<int32_t>(1); }));
+    d.cap = (int)cap;
+    if (s.kf) ORBX_TRY(keyframe_bow_acquire(m, s.kf));
+    ORBX_HIP(launch_bow_vector(m->exec(), s, d));
+    std::vector<int32_t> w(cap);
+    std::vector<double> v(cap);
+    int32_t n = 0;
+    ORBX_TRY(m->d2h(w.data(), d.word, 4 * cap)); ORBX_TRY(m->d2h(v.data(), d.val, 8 * cap)); ORBX_TRY(m->d2h(&n, d.n, 4));
+    ORBX_TRY(m->sync_and_deliver());
+    if (s.kf) keyframe_bow_release(s.kf);
+    n = std::min(std::max(n, 0), (int32_t)cap);
+    memcpy(word_id, w.data(), 4 * (size_t)n); memcpy(value, v.data(), 8 * (size_t)n);
+    *n_words = n;
+    return ORBX_OK;
+}
+
+// a write to the database on m's stream, under db->mu: behind the previous write, the next `written` recorded behind it
+template <class F> int database_write(orbx_matcher *m, orbx_keyframe_database *db, F &&enqueue) {
+    hipError_t e = db->write_seq > 0 ? hipStreamWaitEvent(m->stream, db->written, 0) : hipSuccess;
+    m->dirty = true;
+    if (e == hipSuccess) e = enqueue();
+    if (e == hipSuccess) e = hipEventRecord(db->written, m->stream);
+    if (e != hipSuccess) { set_error(hipGetErrorString(e)); return ORBX_E_HIP; }
+    db->write_seq++;
+    return ORBX_OK;
+}
+
+struct DatabaseQueryOut {
+    int32_t *n_common; double *score; int32_t *cand_slot, *cand_common; double *cand_score; int cand_cap; int *n_cand, *max_common;
+};
+
+// The query: the source's BowVector into the arena, every slot scored against it, the candidates selected.  One upload run (the exclude list), three
+// launches, one download run, one synchronisation.
+int database_query(orbx_matcher *m, orbx_keyframe_database *db, const BowSource &s, const int32_t *exclude, int n_exclude, float min_ratio,
+                   const DatabaseQueryOut &o) {
+    if (!db || db->device != m->device || n_exclude < 0 || (n_exclude > 0 && !exclude) || !(min_ratio >= 0.f && min_ratio <= 1.f) || o.cand_cap < 0 ||
+        (o.cand_cap > 0 && !o.cand_slot) || !o.n_cand || !o.max_common)
+        return ORBX_E_BAD_ARG;
+    ORBX_TRY(bow_source_ok(s));
+    for (int e = 0; e < n_exclude; e++)
+        if (exclude[e] < 0 || exclude[e] >= db->n_slots) return ORBX_E_BAD_ARG;
+    uint64_t seq = 0;
+    bool wait = false;
+    {
+        std::lock_guard<std::mutex> lock(db->mu);
+        if (db->voc && (db->voc != s.bow->voc || db->levelsup != s.bow->levelsup)) return ORBX_E_BAD_ARG;
+        wait = db->seen_seq < db->write_seq;
+        seq = db->write_seq;
+    }
+    ORBX_HIP(hipSetDevice(m->device));
+    const size_t qcap = (size_t)std::max(s.rows.feats(), 1), ns = (size_t)db->n_slots, cc = (size_t)std::max(o.cand_cap, 1);
+    BowVecDst q;
+    BowQuery Q;
+    BowSelect S;
+    memset(&Q, 0, sizeof(Q)); memset(&S, 0, sizeof(S));
+    ORBX_TRY(m->carve([&](Carve &A) {
+        Q.exclude = A.up_opt(exclude, (size_t)n_exclude);
+        q.word = A.take<int32_t>(qcap); q.val = A.take<double>(qcap); q.n = A.take<int32_t>(1);
+        S.meta = A.take<int32_t>(2);   // the downloads side by side: one run
+        S.cand_slot = A.take<int32_t>(cc); S.cand_common = A.take<int32_t>(cc); S.cand_score = A.take<double>(cc);
+        Q.common = A.take<int32_t>(ns); Q.score = A.take<double>(ns);
+    }));
+    q.cap = (int)qcap;
+    if (s.kf) ORBX_TRY(keyframe_bow_acquire(m, s.kf));
+    if (wait) {
+        std::lock_guard<std::mutex> lock(db->mu);   // (`written` is re-recorded under the lock)
+        ORBX_HIP(hipStreamWaitEvent(m->stream, db->written, 0));
+        seq = db->write_seq;
+    }
+    ORBX_HIP(launch_bow_vector(m->exec(), s, q));
+    Q.q_word = q.word; Q.q_val = q.val; Q.q_n = q.n; Q.q_cap = q.cap;
+    Q.row_n = db->row_n; Q.row_word = db->row_word; Q.row_val = db->row_val; Q.n_slots = db->n_slots; Q.words_cap = db->words_cap;
+    Q.n_exclude = n_exclude;
+    hipLaunchKernelGGL(k_bow_score, dim3((unsigned)((db->n_slots + 3) / 4)), dim3(256), 0, m->exec(), Q);
+    S.common = Q.common; S.score = Q.score; S.n_slots = db->n_slots; S.min_ratio = min_ratio; S.cand_cap = o.cand_cap;
+    hipLaunchKernelGGL(k_bow_select, dim3(1), dim3(1024), 0, m->exec(), S);
+    ORBX_HIP(hipGetLastError());
+    int32_t meta[2] = {0, 0};
+    std::vector<int32_t> c_slot(cc), c_common(cc);
+    std::vector<double> c_score(cc);
+    ORBX_TRY(m->d2h(meta, S.meta, 8));
+    if (o.cand_cap > 0) {
+        ORBX_TRY(m->d2h(c_slot.data(), S.cand_slot, 4 * cc)); ORBX_TRY(m->d2h(c_common.data(), S.cand_common, 4 * cc));
+        ORBX_TRY(m->d2h(c_score.data(), S.cand_score, 8 * cc));
+    }
+    if (o.n_common) ORBX_TRY(m->d2h(o.n_common, Q.common, 4 * ns));
+    if (o.score) ORBX_TRY(m->d2h(o.score, Q.score, 8 * ns));
+    ORBX_TRY(m->sync_and_deliver());
+    if (s.kf) keyframe_bow_release(s.kf);
+    {
+        std::lock_guard<std::mutex> lock(db->mu);
+        db->seen_seq = std::max(db->seen_seq, seq);
+    }
+    const size_t got = (size_t)std::min(std::max(meta[0], 0), o.cand_cap);   // the list is cut at cand_cap; n_cand is the true count
+    if (got) {
+        memcpy(o.cand_slot, c_slot.data(), 4 * got);
+        if (o.cand_common) memcpy(o.cand_common, c_common.data(), 4 * got);
+        if (o.cand_score) memcpy(o.cand_score, c_score.data(), 8 * got);
+    }
+    *o.n_cand = meta[0]; *o.max_common = meta[1];
+    return ORBX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int orbx_frame_bow_vector(orbx_matcher *m, orbx_frame *f, int32_t *word_id, double *value, int *n_words) {
+    BowSource s;
+    ORBX_TRY(bow_source_of_frame(m, f, &s));
+    return bow_vector_home(m, s, word_id, value, n_words);
+}
+
+int orbx_keyframe_bow_vector(orbx_matcher *m, orbx_keyframe *kf, int32_t *word_id, double *value, int *n_words) {
+    BowSource s;
+    ORBX_TRY(bow_source_of_keyframe(m, kf, &s));
+    return bow_vector_home(m, s, word_id, value, n_words);
+}
+
+int orbx_keyframe_database_create(int device, int n_slots, int words_cap, orbx_keyframe_database **out) {
+    if (!out) return ORBX_E_BAD_ARG;
+    *out = nullptr;
+    if (n_slots < 1 || words_cap < 1) return ORBX_E_BAD_ARG;
+    if (n_slots > ORBX_MAX_DATABASE_SLOTS || words_cap > kKeyFrameBowMax) return ORBX_E_TOO_LARGE;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+        set_error("no usable HIP device (liborbx has no CPU fallback)");
+        return ORBX_E_NO_DEVICE;
+    }
+    ORBX_HIP(hipSetDevice(device));
+    std::unique_ptr<orbx_keyframe_database> db(new orbx_keyframe_database());
+    db->device = device; db->n_slots = n_slots; db->words_cap = words_cap;
+    const size_t rows = (size_t)n_slots * (size_t)words_cap;
+    Layout L;
+    const size_t off_n = L.add(4 * (size_t)n_slots), off_w = L.add(4 * rows), off_v = L.add(8 * rows);
+    hipError_t e = hipMalloc((void **)&db->dev, L.used);
+    if (e == hipSuccess) e = hipMemset(db->dev + off_n, 0xff, 4 * (size_t)n_slots);   // every slot empty
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&db->written, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        set_error(hipGetErrorString(e));
+        orbx_keyframe_database_destroy(db.release());
+        return ORBX_E_HIP;
+    }
+    db->row_n = (int32_t *)(db->dev + off_n); db->row_word = (int32_t *)(db->dev + off_w); db->row_val = (double *)(db->dev + off_v);
+    *out = db.release();
+    return ORBX_OK;
+}
+
+void orbx_keyframe_database_destroy(orbx_keyframe_database *db) {
+    if (!db) return;
+    (void)hipSetDevice(db->device);
+    if (db->written) { (void)hipEventSynchronize(db->written); (void)hipEventDestroy(db->written); }   // the last write has run; no query is running (the caller's contract)
+    if (db->dev) (void)hipFree(db->dev);
+    delete db;
+}
+
+// KeyFrameDatabase::add: the key frame's BowVector straight into the row of `slot`.  Stream order, no host wait; the row is a copy.
+int orbx_keyframe_database_add(orbx_matcher *m, orbx_keyframe_database *db, int slot, orbx_keyframe *kf) {
+    BowSource s;
+    ORBX_TRY(bow_source_of_keyframe(m, kf, &s));
+    if (!db || db->device != m->device || slot < 0 || slot >= db->n_slots) return ORBX_E_BAD_ARG;
+    ORBX_TRY(bow_source_ok(s));
+    std::lock_guard<std::mutex> lock(db->mu);
+    if (db->voc && (db->voc != s.bow->voc || db->levelsup != s.bow->levelsup)) return ORBX_E_BAD_ARG;
+    if (s.rows.feats() > db->words_cap) return ORBX_E_TOO_LARGE;   // the row's bound: N where the host knows it, the capacity otherwise
+    ORBX_HIP(hipSetDevice(m->device));
+    ORBX_TRY(keyframe_bow_acquire(m, kf));
+    const size_t at = (size_t)slot * (size_t)db->words_cap;
+    const BowVecDst d = {db->row_word + at, db->row_val + at, db->row_n + slot, db->words_cap};
+    ORBX_TRY(database_write(m, db, [&] { return launch_bow_vector(m->stream, s, d); }));
+    db->voc = s.bow->voc; db->levelsup = s.bow->levelsup;
+    return ORBX_OK;
+}
+
+// KeyFrameDatabase::erase: the slot's count becomes -1 in stream order
+int orbx_keyframe_database_erase(orbx_matcher *m, orbx_keyframe_database *db, int slot) {
+    if (!m || !db || db->device != m->device || slot < 0 || slot >= db->n_slots) return ORBX_E_BAD_ARG;
+    std::lock_guard<std::mutex> lock(db->mu);
+    ORBX_HIP(hipSetDevice(m->device));
+    return database_write(m, db, [&] { return hipMemsetAsync(db->row_n + slot, 0xff, 4, m->stream); });
+}
+
+// KeyFrameDatabase::clear: every slot empty; the next add names the vocabulary anew
+int orbx_keyframe_database_clear(orbx_matcher *m, orbx_keyframe_database *db) {
+    if (!m || !db || db->device != m->device) return ORBX_E_BAD_ARG;
+    std::lock_guard<std::mutex> lock(db->mu);
+    ORBX_HIP(hipSetDevice(m->device));
+    ORBX_TRY(database_write(m, db, [&] { return hipMemsetAsync(db->row_n, 0xff, 4 * (size_t)db->n_slots, m->stream); }));
+    db->voc = nullptr; db->levelsup = 0;
+    return ORBX_OK;
+}
+
+int orbx_keyframe_database_query_frame(orbx_matcher *m, orbx_keyframe_database *db, orbx_frame *f, const int32_t *exclude, int n_exclude,
+                                       float min_ratio, int32_t *n_common, double *score, int32_t *cand_slot, int32_t *cand_common,
+                                       double *cand_score, int cand_cap, int *n_cand, int *max_common) {
+    BowSource s;
+    ORBX_TRY(bow_source_of_frame(m, f, &s));
+    return database_query(m, db, s, exclude, n_exclude, min_ratio, {n_common, score, cand_slot, cand_common, cand_score, cand_cap, n_cand, max_common});
+}
+
+int orbx_keyframe_database_query_keyframe(orbx_matcher *m, orbx_keyframe_database *db, orbx_keyframe *kf, const int32_t *exclude, int n_exclude,
+                                          float min_ratio, int32_t *n_common, double *score, int32_t *cand_slot, int32_t *cand_common,
+                                          double *cand_score, int cand_cap, int *n_cand, int *max_common) {
+    BowSource s;
+    ORBX_TRY(bow_source_of_keyframe(m, kf, &s));
+    return database_query(m, db, s, exclude, n_exclude, min_ratio, {n_common, score, cand_slot, cand_common, cand_score, cand_cap, n_cand, max_common});
+}
+
+}  // extern "C"

@@ -171,6 +171,13 @@ class DeviceFrame:
         n = self.count()   # (known after the call: no further synchronisation)
         return w[:n], nd[:n]
 
+    def bow_vector(self):
+        """Frame::mBowVec after compute_bow / compute_bow_fisheye (orbx_frame_bow_vector): (word_id ascending, value normalised), tf-idf and L1 as
+        TemplatedVocabulary::transform makes it, built on the device from the kept word ids.  One synchronisation."""
+        w, v, n = np.zeros(max(self.cap, 1), np.int32), np.zeros(max(self.cap, 1), np.float64), C.c_int(0)
+        check(self._L.orbx_frame_bow_vector(self.matcher._h, self._h, ptr(w), ptr(v), C.byref(n)), "orbx_frame_bow_vector")
+        return w[:n.value], v[:n.value]
+
 
 class DeviceKeyFrame:
     """An immutable key frame resident on the device (orbx_keyframe, include/orbx.h): what KeyFrame::KeyFrame(Frame&) copies of the frame --
@@ -283,9 +290,77 @@ class DeviceKeyFrame:
         check(self._L.orbx_keyframe_bow_from_frame_fisheye(matcher._h, self._h, frame._h), "orbx_keyframe_bow_from_frame_fisheye")
         return self
 
+    def bow_vector(self, matcher: "ORBmatcher", cap: int | None = None):
+        """KeyFrame::mBowVec of a key frame that has BoW (orbx_keyframe_bow_vector): (word_id ascending, value normalised).  cap: the size of the
+        buffers while N is on the device only (the capacity of the frame handle the key frame was made from); None = count first."""
+        size = max(self.count() if cap is None else int(cap), 1)
+        w, v, n = np.zeros(size, np.int32), np.zeros(size, np.float64), C.c_int(0)
+        check(self._L.orbx_keyframe_bow_vector(matcher._h, self._h, ptr(w), ptr(v), C.byref(n)), "orbx_keyframe_bow_vector")
+        return w[:n.value], v[:n.value]
+
     def close(self):
         if getattr(self, "_h", None):
             self._L.orbx_keyframe_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+class DeviceKeyFrameDatabase:
+    """The BowVectors of the key frames of a KeyFrameDatabase, resident on the device (orbx_keyframe_database, include/orbx.h): `n_slots` rows of at
+    most `words_cap` words, addressed by slot numbers the caller assigns (one int in KeyFrame).  It belongs to no matcher: every ORBmatcher of its
+    device may add to it and query it.  add() copies the key frame's BowVector into a slot without waiting; query_frame() / query_keyframe() are the
+    first halves of DetectRelocalizationCandidates / DetectNBestCandidates: common words and L1 scores of every slot and the candidates above
+    minCommonWords, in one call.  The covisibility accumulation behind them stays on the host.  The caller does not write while a query of another
+    thread is running (KeyFrameDatabase::mMutex).  close() (or garbage collection) frees it; no call that was handed it may be running then."""
+
+    def __init__(self, n_slots: int, words_cap: int, device: int = 0):
+        self._L = _lib.lib()
+        h = C.c_void_p()
+        check(self._L.orbx_keyframe_database_create(int(device), int(n_slots), int(words_cap), C.byref(h)), "orbx_keyframe_database_create")
+        self._h = h
+        self.n_slots, self.words_cap = int(n_slots), int(words_cap)
+
+    def add(self, matcher: "ORBmatcher", slot: int, kf: DeviceKeyFrame):
+        """KeyFrameDatabase::add: the key frame's BowVector into `slot` (orbx_keyframe_database_add); returns without waiting."""
+        check(self._L.orbx_keyframe_database_add(matcher._h, self._h, int(slot), kf._h), "orbx_keyframe_database_add")
+        return self
+
+    def erase(self, matcher: "ORBmatcher", slot: int):
+        check(self._L.orbx_keyframe_database_erase(matcher._h, self._h, int(slot)), "orbx_keyframe_database_erase")
+        return self
+
+    def clear(self, matcher: "ORBmatcher"):
+        check(self._L.orbx_keyframe_database_clear(matcher._h, self._h), "orbx_keyframe_database_clear")
+        return self
+
+    def _query(self, fn, matcher, src, exclude, min_ratio, cand_cap, full):
+        ex = _i32([] if exclude is None else exclude)
+        cap = self.n_slots if cand_cap is None else int(cand_cap)
+        common = np.zeros(self.n_slots, np.int32) if full else None
+        score = np.zeros(self.n_slots, np.float64) if full else None
+        cs, cc, csc = np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.int32), np.zeros(max(cap, 1), np.float64)
+        n_cand, max_common = C.c_int(0), C.c_int(0)
+        check(getattr(self._L, fn)(matcher._h, self._h, src._h, ptr(ex) if len(ex) else None, len(ex), float(min_ratio), ptr(common), ptr(score), ptr(cs),
+                                   ptr(cc), ptr(csc), cap, C.byref(n_cand), C.byref(max_common)), fn)
+        k = min(n_cand.value, cap)
+        return dict(n_cand=n_cand.value, max_common=max_common.value, cand_slot=cs[:k], cand_common=cc[:k], cand_score=csc[:k], n_common=common,
+                    score=score)
+
+    def query_frame(self, matcher: "ORBmatcher", frame: DeviceFrame, exclude=None, min_ratio: float = 0.8, cand_cap: int | None = None, full: bool = True):
+        """KeyFrameDatabase::DetectRelocalizationCandidates' first half for a DeviceFrame after compute_bow (orbx_keyframe_database_query_frame).
+        Returns dict(n_cand, max_common, cand_slot, cand_common, cand_score, n_common [n_slots] or None, score [n_slots] or None): the candidates are
+        the slots with more than int(float32(max_common) * min_ratio) common words, ascending; n_cand is the true count, the lists hold at most
+        cand_cap (None: n_slots) entries.  exclude: slots left out of the count (spConnectedKF)."""
+        return self._query("orbx_keyframe_database_query_frame", matcher, frame, exclude, min_ratio, cand_cap, full)
+
+    def query_keyframe(self, matcher: "ORBmatcher", kf: DeviceKeyFrame, exclude=None, min_ratio: float = 0.8, cand_cap: int | None = None, full: bool = True):
+        """DetectNBestCandidates' first half for a key frame with BoW, in the database or not (orbx_keyframe_database_query_keyframe)."""
+        return self._query("orbx_keyframe_database_query_keyframe", matcher, kf, exclude, min_ratio, cand_cap, full)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_keyframe_database_destroy(self._h)
             self._h = None
 
     __del__ = close
