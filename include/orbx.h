@@ -116,6 +116,43 @@ int orbx_extract_batch_device(orbx_extractor *ex, const uint8_t *d_images, int n
 int orbx_extract_batch_host(orbx_extractor *ex, const uint8_t *h_images, int n_frames, int width, int height,
                             size_t row_stride, size_t frame_stride, int lap0, int lap1);
 
+/* ---- raw stereo frames: the rectification in front of the extractor (PARITY UNPINNED) ----
+ * System::TrackStereo (System.cc:259-260) runs cv::remap(imLeft, imLeftToFeed, M1l, M2l, cv::INTER_LINEAR) on both images of every frame when
+ * settings_->needToRectify() holds; M1 / M2 are the CV_32FC1 maps Settings.cc builds once with initUndistortRectifyMap(..., CV_32F, M1, M2).
+ * orbx_rectify_batch_device is that call for 8-bit one-channel images on the device (k_rectify): border mode BORDER_CONSTANT, value 0, the defaults
+ * the call in System.cc gets.  Building the maps stays with the caller.  PARITY UNPINNED, as cv::resize and cv::GaussianBlur are: no OpenCV is in
+ * the tree, the text below restates OpenCV's imgwarp.cpp (remap, remapBilinear, the float -> fixed-point map conversion), and where an OpenCV at
+ * hand disagrees its code wins.  Per destination pixel (x, y):
+ *     sx = cvRound(map_x[y][x] * 32),  sy = cvRound(map_y[y][x] * 32)
+ *         the product is a float product and exact (the exponent moves); cvRound rounds to nearest, ties to even, and gives INT_MIN when the
+ *         product is NaN, infinite or outside int (what the x86 conversion returns; the range is tested here, no conversion is relied on)
+ *     a = sx & 31,  b = sy & 31                                            (INTER_BITS = 5)
+ *     ix = saturate_cast<short>(sx >> 5),  iy = saturate_cast<short>(sy >> 5)   (arithmetic shifts)
+ *     four taps (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1): the source pixel where the tap lies inside [0, src_width) x [0, src_height),
+ *         0 otherwise
+ *     weights (32 - a)(32 - b) * 32,  a (32 - b) * 32,  (32 - a) b * 32,  a b * 32     (they sum to 32768 = 1 << INTER_REMAP_COEF_BITS)
+ *     dst = (sum of tap * weight + 16384) >> 15
+ *   - OpenCV's table of `short` weights stores 32767 for a = b = 0 (32768 does not fit) and puts the missing unit elsewhere;
+ *     ((32767 p + q + 16384) >> 15) == p for all bytes p, q (checked exhaustively), so the formula above gives the same bytes.
+ *   - OpenCV's three border branches (all taps inside, all outside, some outside) all reduce to "a tap outside is 0".
+ * orbx_rectifier_create converts the maps to that fixed-point form once (ix, iy, a, b: 6 bytes per destination pixel) and keeps it on `device`.
+ * map_x / map_y: HOST float32, dst_height rows of dst_width entries, map_stride floats per row.  Synchronous; the maps are copied and may be freed
+ * afterwards.  ORBX_E_BAD_ARG: a NULL pointer, dst_width or dst_height outside [1, 32766], map_stride < dst_width.
+ * orbx_rectify_batch_device: n_frames raw images (src_width x src_height, any size; frame f row y at d_src + f*src_frame_stride + y*src_row_stride)
+ * -> n_frames rectified images of the maps' size at d_dst, both in DEVICE memory, at any alignment.  One launch on `ex`'s stream, no host wait:
+ * orbx_extract_batch_device(ex, d_dst, ...) issued right after it needs no synchronisation in between, whichever route the extraction takes, and
+ * neither does anything that batch reads from level 0 later (orbx_stereo_batch_device, orbx_get_level).  d_dst is an input buffer of the extractor in
+ * every respect: the rule for d_images above applies to it, and rectifying into it counts as touching it.  d_src must be complete when the call is
+ * made and stay untouched until the same wait.  One rectifier may serve several extractors of its device.  ORBX_E_BAD_ARG, before anything is
+ * enqueued: a NULL pointer; n_frames < 1; src_width or src_height outside [1, 32766] (above that a saturated `short` would land inside the image);
+ * a row stride below its width; for n_frames > 1 a dst_frame_stride below one destination image; a d_dst range that overlaps d_src's; an `ex` on
+ * another device than the rectifier's. */
+typedef struct orbx_rectifier orbx_rectifier;
+int orbx_rectifier_create(int device, const float *map_x, const float *map_y, int dst_width, int dst_height, size_t map_stride, orbx_rectifier **out);
+void orbx_rectifier_destroy(orbx_rectifier *r);
+int orbx_rectify_batch_device(orbx_rectifier *r, orbx_extractor *ex, const uint8_t *d_src, int n_frames, int src_width, int src_height,
+                              size_t src_row_stride, size_t src_frame_stride, uint8_t *d_dst, size_t dst_row_stride, size_t dst_frame_stride);
+
 /* Device-side view of the last batch (valid until the next extract call on this extractor). */
 typedef struct orbx_batch_view {
     int32_t n_frames;
@@ -1361,6 +1398,13 @@ int orbx_stereo_download_wait(orbx_extractor *left);
  * row of aligned floats).  frame_stride_bytes is otherwise the caller's: images may overlap or repeat.
  * Both stages stamp the (left) extractor with the batch their results belong to; orbx_frame_load_stereo_batch checks the stamp. */
 int orbx_rgbd_batch_device(orbx_extractor *ex, const float *d_depth, size_t pitch_bytes, size_t frame_stride_bytes, float bf);
+/* The same on the depth image as the sensor delivers it (k_stereo_from_rgbd_u16): d_depth = DEVICE memory, one uint16 image per frame, and
+ * depth_factor = the float mDepthMapFactor (1.0f / DepthMapFactor, as Tracking stores it).  Tracking::GrabImageRGBD's
+ * imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor) happens at the one pixel a feature reads:  d = (float)raw * depth_factor, one rounded float
+ * product (what convertTo's float scale path gives with a zero shift; the conversion of 16 bits is exact) -- and from there exactly as above.
+ * ORBX_E_BAD_ARG as above with pitch_bytes < 2 * width, d_depth / pitch_bytes / frame_stride_bytes odd, and a depth_factor that is not finite
+ * and above 0. */
+int orbx_rgbd_batch_device_u16(orbx_extractor *ex, const uint16_t *d_depth, size_t pitch_bytes, size_t frame_stride_bytes, float depth_factor, float bf);
 /* A frame WITH depth on the handle: besides orbx_frame_load_batch's / orbx_frame_load_host's rows the handle then holds mvuRight, mvDepth and the raw
  * mvKeys[i].pt, and every handle call treats it as the monocular / rectified frame it is (those that read mvuRight read the resident row).
  *   orbx_frame_load_stereo_batch: orbx_frame_load_batch plus frame `frame`'s mvuRight / mvDepth of `left`'s last orbx_stereo_batch_device or

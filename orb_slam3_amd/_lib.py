@@ -223,6 +223,7 @@ SYMBOLS = [
     "orbx_frame_bow_vector", "orbx_keyframe_bow_vector", "orbx_keyframe_database_create", "orbx_keyframe_database_destroy",
     "orbx_keyframe_database_add", "orbx_keyframe_database_erase", "orbx_keyframe_database_clear", "orbx_keyframe_database_query_frame",
     "orbx_keyframe_database_query_keyframe",
+    "orbx_rectifier_create", "orbx_rectifier_destroy", "orbx_rectify_batch_device", "orbx_rgbd_batch_device_u16",
 ]
 
 
@@ -322,6 +323,11 @@ def lib() -> C.CDLL:
     L.orbx_frame_load_batch.argtypes = [vp, vp, i32, vp, vp, i32]
     L.orbx_frame_count.argtypes = [vp, C.POINTER(i32)]
     L.orbx_rgbd_batch_device.argtypes = [vp, vp, sz, sz, f32]
+    L.orbx_rgbd_batch_device_u16.argtypes = [vp, vp, sz, sz, f32, f32]
+    L.orbx_rectifier_create.argtypes = [i32, vp, vp, i32, i32, sz, C.POINTER(vp)]
+    L.orbx_rectifier_destroy.argtypes = [vp]
+    L.orbx_rectifier_destroy.restype = None
+    L.orbx_rectify_batch_device.argtypes = [vp, vp, vp, i32, i32, i32, sz, sz, vp, sz, sz]
     L.orbx_frame_load_stereo_batch.argtypes = [vp, vp, i32, vp, vp, i32]
     L.orbx_frame_load_host_stereo.argtypes = [vp, C.POINTER(FrameDesc), vp, vp]
     L.orbx_frame_unproject_stereo.argtypes = [vp, vp, C.POINTER(NewPointsView), vp, vp, vp, C.POINTER(i32)]

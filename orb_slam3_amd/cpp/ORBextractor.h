@@ -141,6 +141,13 @@ public:
         if (st != ORBX_OK) throw std::runtime_error(std::string("orbx_rgbd_batch_device: ") + orbx_status_string(st) + " " + orbx_last_error());
     }
 
+    // The same on the depth images as the sensor delivers them (orbx_rgbd_batch_device_u16): dDepth = DEVICE memory, one uint16 image per frame;
+    // depthMapFactor = Tracking's mDepthMapFactor, so that GrabImageRGBD's convertTo happens on the device, at the pixels the features read.
+    void RGBDBatchU16(const uint16_t *dDepth, size_t pitchBytes, size_t frameStrideBytes, float depthMapFactor, float mbf) {
+        const int st = orbx_rgbd_batch_device_u16(ex_, dDepth, pitchBytes, frameStrideBytes, depthMapFactor, mbf);
+        if (st != ORBX_OK) throw std::runtime_error(std::string("orbx_rgbd_batch_device_u16: ") + orbx_status_string(st) + " " + orbx_last_error());
+    }
+
     orbx_extractor *handle() { return ex_; }
 
 protected:
@@ -149,6 +156,34 @@ protected:
     double scaleFactor_;
     int width_ = 0, height_ = 0;
     std::vector<float> mvScaleFactor, mvInvScaleFactor, mvLevelSigma2, mvInvLevelSigma2;
+};
+
+// System::TrackStereo's cv::remap(im, imToFeed, M1, M2, cv::INTER_LINEAR) for batches of raw 8-bit frames on the device (orbx_rectifier_create /
+// orbx_rectify_batch_device).  M1 / M2: the CV_32FC1 maps of initUndistortRectifyMap, host memory, copied once.  One Rectifier per camera; it may
+// serve several extractors of its device.
+class Rectifier {
+public:
+    Rectifier(const float *M1, const float *M2, int width, int height, size_t mapStride, int device = 0) : width_(width), height_(height) {
+        const int st = orbx_rectifier_create(device, M1, M2, width, height, mapStride, &r_);
+        if (st != ORBX_OK) throw std::runtime_error(std::string("orbx_rectifier_create: ") + orbx_status_string(st) + " " + orbx_last_error());
+    }
+    ~Rectifier() { orbx_rectifier_destroy(r_); }
+    Rectifier(const Rectifier &) = delete;
+    Rectifier &operator=(const Rectifier &) = delete;
+
+    // n raw frames at dSrc -> n rectified frames (the maps' size) at dDst, both DEVICE memory, on ex's stream: ex's extract call on dDst may follow at once
+    void RectifyBatch(ORBextractor &ex, const uint8_t *dSrc, int n, int srcWidth, int srcHeight, size_t srcRowStride, size_t srcFrameStride,
+                      uint8_t *dDst, size_t dstRowStride, size_t dstFrameStride) {
+        const int st = orbx_rectify_batch_device(r_, ex.handle(), dSrc, n, srcWidth, srcHeight, srcRowStride, srcFrameStride, dDst, dstRowStride, dstFrameStride);
+        if (st != ORBX_OK) throw std::runtime_error(std::string("orbx_rectify_batch_device: ") + orbx_status_string(st) + " " + orbx_last_error());
+    }
+    int width() const { return width_; }
+    int height() const { return height_; }
+    orbx_rectifier *handle() { return r_; }
+
+private:
+    orbx_rectifier *r_ = nullptr;
+    int width_, height_;
 };
 
 }  // namespace ORB_SLAM3

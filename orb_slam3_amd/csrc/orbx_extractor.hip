@@ -22,6 +22,7 @@
 
 #include "extractor_kernels.hip.h"
 #include "geometry_kernels.hip.h"
+#include "image_prep_kernels.hip.h"
 #include "extractor_state.h"
 
 namespace orbx {
@@ -1657,6 +1658,121 @@ int orbx_profile_read(orbx_extractor *ex, const char **names, double *avg_ms, in
         if (launches) launches[k] = ex->prof_n[k];
     }
     return K_COUNT;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Raw sensor images on the device (image_prep_kernels.hip.h): the stereo rectification in front of the extractor, the 16-bit depth image behind it
+// ---------------------------------------------------------------------------------------------------------
+}  // extern "C"
+
+// the maps of one camera in the kernel's fixed-point form; read-only after creation, so one rectifier serves any extractor of its device
+struct orbx_rectifier {
+    int device = 0, dst_w = 0, dst_h = 0, groups = 0;
+    orbx::DevBuf d_xy, d_frac;
+};
+
+extern "C" {
+
+int orbx_rectifier_create(int device, const float *map_x, const float *map_y, int dst_width, int dst_height, size_t map_stride, orbx_rectifier **out) {
+    if (out) *out = nullptr;
+    if (!map_x || !map_y || !out || dst_width < 1 || dst_width > 32766 || dst_height < 1 || dst_height > 32766 || map_stride < (size_t)dst_width)
+        return ORBX_E_BAD_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+        set_error("no usable HIP device (liborbx has no CPU fallback)");
+        return ORBX_E_NO_DEVICE;
+    }
+    ORBX_HIP(hipSetDevice(device));
+    const int groups = (dst_width + 3) / 4;
+    const size_t n = (size_t)groups * 4 * dst_height;
+    std::vector<uint32_t> xy(n, 0x80008000u);   // padding: ix = iy = -32768, every tap outside
+    std::vector<uint16_t> frac(n, 0);
+    for (int y = 0; y < dst_height; y++)
+        for (int x = 0; x < dst_width; x++) {
+            const size_t o = (size_t)y * groups * 4 + x;
+            remap_entry(map_x[y * map_stride + x], map_y[y * map_stride + x], &xy[o], &frac[o]);
+        }
+    orbx_rectifier *r = new orbx_rectifier;
+    r->device = device; r->dst_w = dst_width; r->dst_h = dst_height; r->groups = groups;
+    int st = r->d_xy.ensure(4 * n);
+    if (st == ORBX_OK) st = r->d_frac.ensure(2 * n);
+    if (st == ORBX_OK && (hipMemcpy(r->d_xy.p, xy.data(), 4 * n, hipMemcpyHostToDevice) != hipSuccess ||
+                          hipMemcpy(r->d_frac.p, frac.data(), 2 * n, hipMemcpyHostToDevice) != hipSuccess)) {
+        set_error("orbx_rectifier_create: the upload of the converted maps failed");
+        st = ORBX_E_HIP;
+    }
+    if (st != ORBX_OK) { orbx_rectifier_destroy(r); return st; }
+    *out = r;
+    return ORBX_OK;
+}
+
+void orbx_rectifier_destroy(orbx_rectifier *r) {
+    if (!r) return;
+    (void)hipSetDevice(r->device);
+    r->d_xy.release(); r->d_frac.release();   // (hipFree waits for the kernels that still read them)
+    delete r;
+}
+
+int orbx_rectify_batch_device(orbx_rectifier *r, orbx_extractor *ex, const uint8_t *d_src, int n_frames, int src_width, int src_height,
+                              size_t src_row_stride, size_t src_frame_stride, uint8_t *d_dst, size_t dst_row_stride, size_t dst_frame_stride) {
+    RoctxRange rr("orbx:rectify");
+    if (!r || !ex || !d_src || !d_dst || n_frames < 1 || src_width < 1 || src_width > 32766 || src_height < 1 || src_height > 32766 ||
+        src_row_stride < (size_t)src_width || dst_row_stride < (size_t)r->dst_w || ex->device != r->device)
+        return ORBX_E_BAD_ARG;
+    // the bytes the call reads and the bytes it writes: first byte of frame 0 .. last byte of the last row of the last frame
+    const size_t dst_frame_bytes = (size_t)(r->dst_h - 1) * dst_row_stride + (size_t)r->dst_w;
+    const size_t src_span = (size_t)(n_frames - 1) * src_frame_stride + (size_t)(src_height - 1) * src_row_stride + (size_t)src_width;
+    const size_t dst_span = (size_t)(n_frames - 1) * dst_frame_stride + dst_frame_bytes;
+    if (n_frames > 1 && dst_frame_stride < dst_frame_bytes) return ORBX_E_BAD_ARG;   // two frames would be written into the same bytes
+    const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
+    if (s0 < d0 + dst_span && d0 < s0 + src_span) return ORBX_E_BAD_ARG;
+    ORBX_HIP(hipSetDevice(ex->device));
+    RectifyArgs A;
+    A.xy = (const uint4 *)r->d_xy.p; A.frac = (const uint2 *)r->d_frac.p; A.groups = r->groups;
+    A.dst_w = r->dst_w; A.dst_h = r->dst_h; A.src_w = src_width; A.src_h = src_height; A.n_frames = n_frames;
+    A.src = d_src; A.src_row = src_row_stride; A.src_frame = src_frame_stride;
+    A.dst = d_dst; A.dst_row = dst_row_stride; A.dst_frame = dst_frame_stride;
+    const int chunks = (n_frames + kRectifyFrames - 1) / kRectifyFrames;
+    // The extractor's main stream: every reader of an extractor's frames -- k_pyr_base, k_pyr_stream, and for a batch that reads level 0 in place
+    // k_fast_strip, k_describe_fused and the later orbx_materialize_level0 (orbx_get_level, the stereo rig's SAD stage) -- is enqueued on it, and so
+    // is the last reader of whatever d_dst held for the batch before; stream order is all the ordering there is to add.
+    hipLaunchKernelGGL(k_rectify, dim3((unsigned)((r->groups + 63) / 64), (unsigned)((r->dst_h + 3) / 4), (unsigned)std::min(chunks, 65535)), dim3(256), 0,
+                       ex->stream, A);
+    ORBX_HIP(hipGetLastError());
+    return ORBX_OK;
+}
+
+// orbx_rgbd_batch_device (orbx_matcher.hip) on the sensor's 16-bit depth images: the same stream, events, result buffers and stamps
+int orbx_rgbd_batch_device_u16(orbx_extractor *ex, const uint16_t *d_depth, size_t pitch_bytes, size_t frame_stride_bytes, float depth_factor, float bf) {
+    RoctxRange rr("orbx:rgbd");
+    if (!ex || !d_depth || ex->last_batch <= 0 || ex->width <= 0 || pitch_bytes < 2 * (size_t)ex->width || !(bf > 0.f) ||
+        !(depth_factor > 0.f) || !std::isfinite(depth_factor))
+        return ORBX_E_BAD_ARG;
+    // every row of every image must be a row of aligned 16-bit values
+    if (((uintptr_t)d_depth | pitch_bytes | frame_stride_bytes) & 1u) return ORBX_E_BAD_ARG;
+    ORBX_HIP(hipSetDevice(ex->device));
+    const int n = ex->last_batch;
+    int r;
+    for (DevBuf *b : {&ex->d_st_ur, &ex->d_st_depth})
+        if ((r = b->ensure(4 * (size_t)ex->cap * ex->batch_cap)) != ORBX_OK) return r;
+    if ((r = ex->d_st_nm.ensure(4 * (size_t)ex->batch_cap)) != ORBX_OK) return r;
+    const bool side = !ex->profile && ex->side_streams;
+    hipStream_t st = side ? ex->match_stream : ex->stream;
+    ORBX_HIP(hipStreamWaitEvent(st, ex->ev_describe, 0));   // the extraction of this batch (its k_undistort included)
+    if (ex->stereo_copy_issued) ORBX_HIP(hipStreamWaitEvent(st, ex->ev_stereo_copy[(ex->stereo_copy_issued - 1) & 1], 0));  // the previous results may still be on their way to the host
+    RgbdU16Stage S;
+    S.kps = (const orbx_keypoint *)ex->d_kps.p; S.kps_un = (const orbx_keypoint *)ex->match_kps();
+    S.count = (const int32_t *)ex->d_count.p;
+    S.depth = (const uint8_t *)d_depth; S.pitch = pitch_bytes; S.frame_stride = frame_stride_bytes;
+    S.cap = ex->cap; S.width = ex->width; S.height = ex->height; S.bf = bf; S.depth_factor = depth_factor;
+    S.u_right = (float *)ex->d_st_ur.p; S.out_depth = (float *)ex->d_st_depth.p; S.nmatches = (int32_t *)ex->d_st_nm.p;
+    hipLaunchKernelGGL(k_stereo_from_rgbd_u16, dim3((unsigned)n), dim3(256), 0, st, S);
+    ORBX_HIP(hipGetLastError());
+    ex->st_seq = ex->batch_seq;
+    // the extractor must not overwrite its key points / counts before the kernel is done
+    ORBX_HIP(hipEventRecord(ex->ev_match, st));
+    ex->match_pending = true; ex->copy_covers_match = false;
+    return ORBX_OK;
 }
 
 }  // extern "C"

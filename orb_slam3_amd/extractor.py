@@ -183,6 +183,12 @@ class ORBextractor:
         check(self._L.orbx_rgbd_batch_device(self._h, C.c_void_p(d_depth) if d_depth else None, pitch_bytes, frame_stride_bytes, bf),
               "orbx_rgbd_batch_device")
 
+    def rgbd_batch_u16(self, d_depth: int, pitch_bytes: int, frame_stride_bytes: int, depth_factor: float, bf: float):
+        """RGBDBatch on the depth images as the sensor delivers them (orbx_rgbd_batch_device_u16): d_depth = DEVICE address of one uint16 image per
+        frame, depth_factor = Tracking's mDepthMapFactor (1.0f / DepthMapFactor); d = float(raw) * depth_factor is formed per feature, on the device."""
+        check(self._L.orbx_rgbd_batch_device_u16(self._h, C.c_void_p(d_depth) if d_depth else None, pitch_bytes, frame_stride_bytes, depth_factor, bf),
+              "orbx_rgbd_batch_device_u16")
+
     def stereo_download(self, frame: int):
         """Returns (n_matches, mvuRight[N], mvDepth[N]) of `frame` (-1 where unmatched)."""
         cap = self.batch_view().cap
@@ -342,3 +348,33 @@ class ORBextractor:
         cnt = (C.c_int64 * 16)()
         k = self._L.orbx_profile_read(self._h, names, ms, cnt, 16)
         return {names[i].decode(): (ms[i], cnt[i]) for i in range(k)}
+
+
+class DeviceRectifier:
+    """cv::remap(src, dst, map_x, map_y, INTER_LINEAR) of System::TrackStereo for batches of raw 8-bit frames on the device (orbx_rectifier_create /
+    orbx_rectify_batch_device).  map_x / map_y: the two float32 maps of initUndistortRectifyMap(..., CV_32F, ...), shape (dst_height, dst_width);
+    they are converted to fixed point and copied once.  One rectifier serves every extractor of its device."""
+
+    def __init__(self, map_x: np.ndarray, map_y: np.ndarray, device: int = 0):
+        self._L = _lib.lib()
+        self._h = C.c_void_p()
+        map_x, map_y = np.ascontiguousarray(map_x, np.float32), np.ascontiguousarray(map_y, np.float32)
+        if map_x.ndim != 2 or map_x.shape != map_y.shape:
+            raise ValueError(f"two 2-D maps of one shape expected, got {map_x.shape} and {map_y.shape}")
+        self.height, self.width = map_x.shape
+        self.device = device
+        check(self._L.orbx_rectifier_create(device, ptr(map_x), ptr(map_y), self.width, self.height, self.width, C.byref(self._h)), "orbx_rectifier_create")
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_rectifier_destroy(self._h)
+            self._h = None
+
+    def rectify_batch(self, extractor: ORBextractor, d_src: int, n: int, src_w: int, src_h: int, src_row_stride: int, src_frame_stride: int,
+                      d_dst: int, dst_row_stride: int, dst_frame_stride: int):
+        """n raw frames at the DEVICE address d_src -> n rectified frames (width x height of the maps) at d_dst, enqueued on the extractor's stream:
+        extractor.extract_batch_device(d_dst, n, self.width, self.height, dst_row_stride, dst_frame_stride) may follow at once.  Both buffers stay
+        untouched until sync() / download_wait()."""
+        check(self._L.orbx_rectify_batch_device(self._h, extractor._h, C.c_void_p(d_src) if d_src else None, n, src_w, src_h, src_row_stride,
+                                                src_frame_stride, C.c_void_p(d_dst) if d_dst else None, dst_row_stride, dst_frame_stride),
+              "orbx_rectify_batch_device")
