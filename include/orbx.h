@@ -153,6 +153,71 @@ void orbx_rectifier_destroy(orbx_rectifier *r);
 int orbx_rectify_batch_device(orbx_rectifier *r, orbx_extractor *ex, const uint8_t *d_src, int n_frames, int src_width, int src_height,
                               size_t src_row_stride, size_t src_frame_stride, uint8_t *d_dst, size_t dst_row_stride, size_t dst_frame_stride);
 
+/* ---- raw frames: colour, size and contrast in front of the extractor (PARITY UNPINNED) ----
+ * The other image-sized host steps between the sensor's bytes and ORBextractor::operator():
+ *   Tracking::GrabImageMonocular / Stereo / RGBD (Tracking.cc:1569-1582): cvtColor(im, im, COLOR_{RGB,BGR,RGBA,BGRA}2GRAY) for 3 or 4 channels
+ *   System::TrackMonocular / Stereo / RGBD: cv::resize(im, im, settings_->newImSize()) when settings_->needToResize() (Camera.newWidth)
+ *   the TUM-VI examples: cv::createCLAHE(3.0, cv::Size(8, 8))->apply(im, im) on every frame before System::Track*
+ * An integrator chains them in that code's order -- the example's CLAHE, System's resize / remap, Tracking's cvtColor -- or uses any one alone.
+ * Each call enqueues its kernels on `ex`'s stream exactly as orbx_rectify_batch_device does: `ex` is passed for the stream and the device only, there is
+ * no host wait, orbx_extract_batch_device(ex, d_dst, ...) (or the next of these calls) issued right after needs no synchronisation in between, d_dst is
+ * an input buffer of the extractor in every respect (the rule for d_images above), and d_src must be complete when the call is made and stay
+ * untouched until the same wait.  Frame f row y lies at d_src + f*src_frame_stride + y*src_row_stride (bytes); source and destination may sit at
+ * any alignment.  PARITY UNPINNED, as cv::remap is: no OpenCV is in the tree, the text below restates OpenCV 4.x (color_rgb.simd.hpp, resize.cpp,
+ * clahe.cpp), and where an OpenCV at hand disagrees its code wins.
+ * ORBX_E_BAD_ARG, before anything is enqueued (d_dst keeps its bytes): a NULL pointer; n_frames < 1; a width or height outside [1, 65535]; a row
+ * stride below the row's bytes; for n_frames > 1 a dst_frame_stride below one destination image; a d_dst range that overlaps d_src's (CLAHE's exact
+ * in-place form excepted); and what each call adds below.
+ *
+ * orbx_gray_batch_device (k_gray): channels = 3 or 4 interleaved bytes per pixel (anything else: ORBX_E_BAD_ARG); rgb != 0: the first byte of a pixel
+ * is R (Tracking's mbRGB), else B.
+ *     gray = (R * 9798 + G * 19235 + B * 3735 + 16384) >> 15
+ *   the coefficients sum to 32768; the shift of 15 is OpenCV 4's (ORB-SLAM3 requires OpenCV >= 4.4); a fourth channel is skipped.
+ *
+ * orbx_resize_batch_device (k_resize, k_resize_half): cv::resize(src, dst, Size(dst_width, dst_height)) with the default INTER_LINEAR, 8-bit one channel.
+ *   - exactly src_width == 2 * dst_width && src_height == 2 * dst_height: OpenCV turns INTER_LINEAR into its fast area path,
+ *         dst = (a + b + c + d + 2) >> 2 over the 2 x 2 block;
+ *   - every other size pair, enlargement and a half in one dimension only included: the generic path.  Per dimension, for destination index d:
+ *         f = (float)((d + 0.5) * scale - 0.5), scale = 1. / ((double)dsize / ssize);  s = floor(f);  f -= s
+ *         horizontally: s < 0 -> f = 0, s = 0;  s >= ssize - 1 -> f = 0, s = ssize - 1.  Vertically the rows s, s + 1 are clamped to the image, f is kept.
+ *         c0 = saturate_cast<short>((1.f - f) * 2048), c1 = saturate_cast<short>(f * 2048)        (cvRound: nearest, ties to even)
+ *         row(sy)[x] = S[sy][sx] * c0x + S[sy][sx + 1] * c1x, or S[sy][sx] * 2048 where sx + 1 >= src_width
+ *         dst = clamp((((c0y * (row(sy0)[x] >> 4)) >> 16) + ((c1y * (row(sy1)[x] >> 4)) >> 16) + 2) >> 2, 0, 255)
+ *     The tables are built on the host and kept on the device per size pair (the last four of an extractor; a new size pair uploads its tables
+ *     synchronously, a fifth one waits for the stream first); the kernel does the integer part only.
+ *
+ * orbx_clahe_batch_device (k_clahe_lut, k_clahe_apply): cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y)) and clahe->apply(src, dst), 8-bit one
+ * channel, histSize = 256.  d_dst == d_src with equal strides is allowed (apply(im, im)); any other overlap is refused.
+ *   1. If width % tiles_x == 0 && height % tiles_y == 0 the tables are made from the source.  Otherwise from the source extended at the right by
+ *      tiles_x - width % tiles_x columns AND at the bottom by tiles_y - height % tiles_y rows with BORDER_REFLECT_101 -- a full extra tiles_y rows when only
+ *      the width fails to divide, and the reverse.  (The extension is never materialised: a tile's histogram reads reflected coordinates.)
+ *      tile_w, tile_h = the extended size / the tile counts; area = tile_w * tile_h.
+ *   2. clip = clip_limit > 0 ? max((int)(clip_limit * area / 256), 1) : 0   (double arithmetic, truncated);  lutScale = 255.0f / area (float).
+ *   3. Per tile: the histogram of its `area` pixels.  If clip > 0: clipped = sum of max(hist[i] - clip, 0), those bins set to clip;
+ *      batch = clipped / 256, residual = clipped - batch * 256; every bin += batch; if residual != 0: step = max(256 / residual, 1) and
+ *      for (i = 0; i < 256 && residual > 0; i += step, residual--) hist[i]++.
+ *      lut[i] = saturate_cast<uchar>(cvRound((float)(sum of hist[0..i]) * lutScale))   (one rounded float product; nearest, ties to even)
+ *   4. Per source pixel (x, y) of value v: txf = (float)x * (1.0f / tile_w) - 0.5f;  tx1 = floor(txf), tx2 = tx1 + 1;  xa = txf - tx1, xa1 = 1.0f - xa;
+ *      THEN tx1 = max(tx1, 0), tx2 = min(tx2, tiles_x - 1); the same in y.
+ *      res = (lut[ty1][tx1][v] * xa1 + lut[ty1][tx2][v] * xa) * ya1 + (lut[ty2][tx1][v] * xa1 + lut[ty2][tx2][v] * xa) * ya
+ *      in float, every operation rounded as written;  dst = saturate_cast<uchar>(cvRound(res)).
+ * orbx_clahe_create: ORBX_E_BAD_ARG for out == NULL, tiles_x or tiles_y outside [1, 64], a NaN clip_limit; clip_limit <= 0 means no clipping.
+ * The object owns the tables of the batch in flight (n_frames * tiles_x * tiles_y * 256 bytes), allocated at the first batch and grown when a batch
+ * needs more (that call waits for the device).  One object may serve several extractors of its device, PROVIDED TWO BATCHES ARE NEVER IN FLIGHT ON THE
+ * SAME OBJECT AT ONCE: batches through one extractor are ordered by its stream; before the object is used with another extractor, wait for the first
+ * (orbx_sync / orbx_download_wait).  orbx_clahe_batch_device adds to the refusals: an image in which the padding of step 1 would be at least as wide
+ * as the dimension it reflects (pad_x >= width or pad_y >= height); an `ex` on another device than the object's. */
+int orbx_gray_batch_device(orbx_extractor *ex, const uint8_t *d_src, int n_frames, int width, int height, int channels, int rgb,
+                           size_t src_row_stride, size_t src_frame_stride, uint8_t *d_dst, size_t dst_row_stride, size_t dst_frame_stride);
+int orbx_resize_batch_device(orbx_extractor *ex, const uint8_t *d_src, int n_frames, int src_width, int src_height,
+                             size_t src_row_stride, size_t src_frame_stride,
+                             uint8_t *d_dst, int dst_width, int dst_height, size_t dst_row_stride, size_t dst_frame_stride);
+typedef struct orbx_clahe orbx_clahe;
+int orbx_clahe_create(int device, double clip_limit, int tiles_x, int tiles_y, orbx_clahe **out);
+void orbx_clahe_destroy(orbx_clahe *c);
+int orbx_clahe_batch_device(orbx_clahe *c, orbx_extractor *ex, const uint8_t *d_src, int n_frames, int width, int height,
+                            size_t src_row_stride, size_t src_frame_stride, uint8_t *d_dst, size_t dst_row_stride, size_t dst_frame_stride);
+
 /* Device-side view of the last batch (valid until the next extract call on this extractor). */
 typedef struct orbx_batch_view {
     int32_t n_frames;

@@ -6,7 +6,7 @@ frame generator used by tests and bench.  Importing the package does not load th
 ORBextractor / ORBmatcher does, and fails loudly when liborbx.so or a HIP device is missing (no CPU fallback).
 """
 from ._lib import KP_DTYPE, OrbxError, LIB_PATH  # noqa: F401
-from .extractor import ORBextractor, DeviceRectifier  # noqa: F401
+from .extractor import ORBextractor, DeviceRectifier, DeviceClahe  # noqa: F401
 from .matcher import ORBmatcher, ORBVocabulary, FrameView, FeatureVector, DeviceFrame, DeviceKeyFrame, DeviceKeyFrameDatabase, DeviceMap, FisheyeRig  # noqa: F401
 
-__all__ = ["ORBextractor", "DeviceRectifier", "ORBmatcher", "ORBVocabulary", "FrameView", "FeatureVector", "DeviceFrame", "DeviceKeyFrame", "DeviceKeyFrameDatabase", "DeviceMap", "FisheyeRig", "KP_DTYPE", "OrbxError", "LIB_PATH"]
+__all__ = ["ORBextractor", "DeviceRectifier", "DeviceClahe", "ORBmatcher", "ORBVocabulary", "FrameView", "FeatureVector", "DeviceFrame", "DeviceKeyFrame", "DeviceKeyFrameDatabase", "DeviceMap", "FisheyeRig", "KP_DTYPE", "OrbxError", "LIB_PATH"]

@@ -224,6 +224,7 @@ SYMBOLS = [
     "orbx_keyframe_database_add", "orbx_keyframe_database_erase", "orbx_keyframe_database_clear", "orbx_keyframe_database_query_frame",
     "orbx_keyframe_database_query_keyframe",
     "orbx_rectifier_create", "orbx_rectifier_destroy", "orbx_rectify_batch_device", "orbx_rgbd_batch_device_u16",
+    "orbx_gray_batch_device", "orbx_resize_batch_device", "orbx_clahe_create", "orbx_clahe_destroy", "orbx_clahe_batch_device",
 ]
 
 
@@ -328,6 +329,12 @@ def lib() -> C.CDLL:
     L.orbx_rectifier_destroy.argtypes = [vp]
     L.orbx_rectifier_destroy.restype = None
     L.orbx_rectify_batch_device.argtypes = [vp, vp, vp, i32, i32, i32, sz, sz, vp, sz, sz]
+    L.orbx_gray_batch_device.argtypes = [vp, vp, i32, i32, i32, i32, i32, sz, sz, vp, sz, sz]
+    L.orbx_resize_batch_device.argtypes = [vp, vp, i32, i32, i32, sz, sz, vp, i32, i32, sz, sz]
+    L.orbx_clahe_create.argtypes = [i32, C.c_double, i32, i32, C.POINTER(vp)]
+    L.orbx_clahe_destroy.argtypes = [vp]
+    L.orbx_clahe_destroy.restype = None
+    L.orbx_clahe_batch_device.argtypes = [vp, vp, vp, i32, i32, i32, sz, sz, vp, sz, sz]
     L.orbx_frame_load_stereo_batch.argtypes = [vp, vp, i32, vp, vp, i32]
     L.orbx_frame_load_host_stereo.argtypes = [vp, C.POINTER(FrameDesc), vp, vp]
     L.orbx_frame_unproject_stereo.argtypes = [vp, vp, C.POINTER(NewPointsView), vp, vp, vp, C.POINTER(i32)]

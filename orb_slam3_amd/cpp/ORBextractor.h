@@ -148,6 +148,21 @@ public:
         if (st != ORBX_OK) throw std::runtime_error(std::string("orbx_rgbd_batch_device_u16: ") + orbx_status_string(st) + " " + orbx_last_error());
     }
 
+    // Tracking::GrabImage*'s cvtColor(im, im, COLOR_{RGB,BGR,RGBA,BGRA}2GRAY) for n interleaved 8-bit frames of 3 or 4 channels (orbx_gray_batch_device):
+    // dSrc -> dDst, both DEVICE memory, on this extractor's stream; its extract call on dDst may follow at once.  rgb = Tracking's mbRGB.
+    void GrayBatch(const uint8_t *dSrc, int n, int width, int height, int channels, bool rgb, size_t srcRowStride, size_t srcFrameStride,
+                   uint8_t *dDst, size_t dstRowStride, size_t dstFrameStride) {
+        const int st = orbx_gray_batch_device(ex_, dSrc, n, width, height, channels, rgb ? 1 : 0, srcRowStride, srcFrameStride, dDst, dstRowStride, dstFrameStride);
+        if (st != ORBX_OK) throw std::runtime_error(std::string("orbx_gray_batch_device: ") + orbx_status_string(st) + " " + orbx_last_error());
+    }
+
+    // System::Track*'s cv::resize(im, im, settings_->newImSize()) (INTER_LINEAR) for n 8-bit one-channel frames (orbx_resize_batch_device), as GrayBatch
+    void ResizeBatch(const uint8_t *dSrc, int n, int srcWidth, int srcHeight, size_t srcRowStride, size_t srcFrameStride,
+                     uint8_t *dDst, int dstWidth, int dstHeight, size_t dstRowStride, size_t dstFrameStride) {
+        const int st = orbx_resize_batch_device(ex_, dSrc, n, srcWidth, srcHeight, srcRowStride, srcFrameStride, dDst, dstWidth, dstHeight, dstRowStride, dstFrameStride);
+        if (st != ORBX_OK) throw std::runtime_error(std::string("orbx_resize_batch_device: ") + orbx_status_string(st) + " " + orbx_last_error());
+    }
+
     orbx_extractor *handle() { return ex_; }
 
 protected:
@@ -184,6 +199,32 @@ public:
 private:
     orbx_rectifier *r_ = nullptr;
     int width_, height_;
+};
+
+// The TUM-VI examples' cv::createCLAHE(clipLimit, cv::Size(tilesX, tilesY)) for batches of 8-bit frames on the device (orbx_clahe_create /
+// orbx_clahe_batch_device).  The object owns the look-up tables of the batch in flight: it may serve several extractors of its device, but two batches
+// must never be in flight on it at once (batches through one extractor are ordered by its stream; wait before using it with another).
+class Clahe {
+public:
+    explicit Clahe(double clipLimit = 3.0, int tilesX = 8, int tilesY = 8, int device = 0) {
+        const int st = orbx_clahe_create(device, clipLimit, tilesX, tilesY, &c_);
+        if (st != ORBX_OK) throw std::runtime_error(std::string("orbx_clahe_create: ") + orbx_status_string(st) + " " + orbx_last_error());
+    }
+    ~Clahe() { orbx_clahe_destroy(c_); }
+    Clahe(const Clahe &) = delete;
+    Clahe &operator=(const Clahe &) = delete;
+
+    // clahe->apply(src, dst) for n frames, both DEVICE memory, on ex's stream: ex's extract call on dDst may follow at once.  dDst == dSrc with equal
+    // strides is apply(im, im).
+    void ApplyBatch(ORBextractor &ex, const uint8_t *dSrc, int n, int width, int height, size_t srcRowStride, size_t srcFrameStride,
+                    uint8_t *dDst, size_t dstRowStride, size_t dstFrameStride) {
+        const int st = orbx_clahe_batch_device(c_, ex.handle(), dSrc, n, width, height, srcRowStride, srcFrameStride, dDst, dstRowStride, dstFrameStride);
+        if (st != ORBX_OK) throw std::runtime_error(std::string("orbx_clahe_batch_device: ") + orbx_status_string(st) + " " + orbx_last_error());
+    }
+    orbx_clahe *handle() { return c_; }
+
+private:
+    orbx_clahe *c_ = nullptr;
 };
 
 }  // namespace ORB_SLAM3

@@ -238,6 +238,11 @@ struct orbx_extractor {
     hipEvent_t ev_frustum[3] = {nullptr, nullptr, nullptr};
     bool frustum_used[3] = {false, false, false};
     unsigned frustum_issued = 0;
+    // orbx_resize_batch_device: cv::resize's coefficient tables of the last size pairs (k_resize).  A table is written once, before the first kernel
+    // that reads it is enqueued; a fifth size pair waits for the stream before it takes the oldest slot.
+    struct ResizeTabDev { int sw = 0, sh = 0, dw = 0, dh = 0; DevBuf x, y; };
+    ResizeTabDev rs_tab[4];
+    unsigned rs_next = 0;
     const void *match_kps() const { return has_camera ? d_kps_un.p : d_kps.p; }
 
     // Synchronous device -> caller copy through the pinned staging buffer (no caller pointer is ever handed to the HIP runtime: see

@@ -23,6 +23,7 @@
 #include "extractor_kernels.hip.h"
 #include "geometry_kernels.hip.h"
 #include "image_prep_kernels.hip.h"
+#include "image_enhance_kernels.hip.h"
 #include "extractor_state.h"
 
 namespace orbx {
@@ -1123,6 +1124,7 @@ void orbx_destroy(orbx_extractor *ex) {
                       &ex->ps_plan[1].tasks, &ex->ps_plan[1].lists, &ex->ps_plan[2].cols, &ex->ps_plan[2].steps, &ex->ps_plan[2].tasks, &ex->ps_plan[2].lists,
                       &ex->ps_plan[3].cols, &ex->ps_plan[3].steps, &ex->ps_plan[3].tasks, &ex->ps_plan[3].lists};
     for (DevBuf *b : bufs) b->release();
+    for (auto &t : ex->rs_tab) { t.x.release(); t.y.release(); }
     if (ex->h_stage) (void)hipHostFree(ex->h_stage);
     if (ex->ev0) (void)hipEventDestroy(ex->ev0);
     if (ex->ev1) (void)hipEventDestroy(ex->ev1);
@@ -1772,6 +1774,192 @@ int orbx_rgbd_batch_device_u16(orbx_extractor *ex, const uint16_t *d_depth, size
     // the extractor must not overwrite its key points / counts before the kernel is done
     ORBX_HIP(hipEventRecord(ex->ev_match, st));
     ex->match_pending = true; ex->copy_covers_match = false;
+    return ORBX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Colour, size and contrast of raw frames on the device (image_enhance_kernels.hip.h): cvtColor, cv::resize and cv::CLAHE::apply in front of the
+// extractor, each enqueued on the extractor's main stream as orbx_rectify_batch_device is (the same readers, the same ordering argument)
+// ---------------------------------------------------------------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+constexpr int kMaxImageSide = 65535;   // four rows per workgroup row: the grid's y stays far below its limit, and every pixel index fits an int
+
+// What the three calls share: n frames of `src_bytes` x src_h bytes are read, n frames of dst_w x dst_h bytes are written.  False for a row stride below its
+// row, destination frames that would share bytes, and a destination range that overlaps the source's (in_place_ok: except the exact in-place form).
+bool image_ranges_ok(const uint8_t *d_src, int n, size_t src_bytes, int src_h, size_t src_row, size_t src_frame, const uint8_t *d_dst, int dst_w, int dst_h,
+                     size_t dst_row, size_t dst_frame, bool in_place_ok) {
+    if (src_row < src_bytes || dst_row < (size_t)dst_w) return false;
+    const size_t dst_frame_bytes = (size_t)(dst_h - 1) * dst_row + (size_t)dst_w;
+    if (n > 1 && dst_frame < dst_frame_bytes) return false;   // two frames would be written into the same bytes
+    if (in_place_ok && d_src == d_dst && src_row == dst_row && src_frame == dst_frame) return true;
+    const size_t src_span = (size_t)(n - 1) * src_frame + (size_t)(src_h - 1) * src_row + src_bytes;
+    const size_t dst_span = (size_t)(n - 1) * dst_frame + dst_frame_bytes;
+    const uintptr_t s0 = (uintptr_t)d_src, d0 = (uintptr_t)d_dst;
+    return !(s0 < d0 + dst_span && d0 < s0 + src_span);
+}
+
+constexpr int kFramesPerLaunch = 65535;   // the grid's z
+
+}  // namespace
+
+// the look-up tables of the batch in flight: [n_frames][tiles_y][tiles_x][256], grown when a batch needs more
+struct orbx_clahe {
+    int device = 0, tiles_x = 0, tiles_y = 0;
+    double clip_limit = 0;
+    orbx::DevBuf d_lut;
+};
+
+extern "C" {
+
+int orbx_gray_batch_device(orbx_extractor *ex, const uint8_t *d_src, int n_frames, int width, int height, int channels, int rgb,
+                           size_t src_row_stride, size_t src_frame_stride, uint8_t *d_dst, size_t dst_row_stride, size_t dst_frame_stride) {
+    RoctxRange rr("orbx:gray");
+    if (!ex || !d_src || !d_dst || n_frames < 1 || width < 1 || width > kMaxImageSide || height < 1 || height > kMaxImageSide ||
+        (channels != 3 && channels != 4) ||
+        !image_ranges_ok(d_src, n_frames, (size_t)width * channels, height, src_row_stride, src_frame_stride, d_dst, width, height, dst_row_stride,
+                         dst_frame_stride, false))
+        return ORBX_E_BAD_ARG;
+    ORBX_HIP(hipSetDevice(ex->device));
+    GrayArgs A;
+    A.src_row = src_row_stride; A.src_frame = src_frame_stride; A.dst_row = dst_row_stride; A.dst_frame = dst_frame_stride;
+    A.width = width; A.height = height; A.channels = channels;
+    A.c0 = rgb ? 9798u : 3735u; A.c2 = rgb ? 3735u : 9798u;
+    const int groups = (width + 3) / 4;
+    for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
+        A.src = d_src + (size_t)f0 * src_frame_stride; A.dst = d_dst + (size_t)f0 * dst_frame_stride;
+        hipLaunchKernelGGL(k_gray, dim3((unsigned)((groups + 63) / 64), (unsigned)((height + 3) / 4), (unsigned)std::min(n_frames - f0, kFramesPerLaunch)),
+                           dim3(256), 0, ex->stream, A);
+    }
+    ORBX_HIP(hipGetLastError());
+    return ORBX_OK;
+}
+
+int orbx_resize_batch_device(orbx_extractor *ex, const uint8_t *d_src, int n_frames, int src_width, int src_height, size_t src_row_stride,
+                             size_t src_frame_stride, uint8_t *d_dst, int dst_width, int dst_height, size_t dst_row_stride, size_t dst_frame_stride) {
+    RoctxRange rr("orbx:resize");
+    if (!ex || !d_src || !d_dst || n_frames < 1 || src_width < 1 || src_width > kMaxImageSide || src_height < 1 || src_height > kMaxImageSide ||
+        dst_width < 1 || dst_width > kMaxImageSide || dst_height < 1 || dst_height > kMaxImageSide ||
+        !image_ranges_ok(d_src, n_frames, (size_t)src_width, src_height, src_row_stride, src_frame_stride, d_dst, dst_width, dst_height, dst_row_stride,
+                         dst_frame_stride, false))
+        return ORBX_E_BAD_ARG;
+    ORBX_HIP(hipSetDevice(ex->device));
+    ResizeArgs A;
+    A.xtab = nullptr; A.ytab = nullptr;
+    A.src_row = src_row_stride; A.src_frame = src_frame_stride; A.dst_row = dst_row_stride; A.dst_frame = dst_frame_stride;
+    A.src_w = src_width; A.src_h = src_height; A.dst_w = dst_width; A.dst_h = dst_height;
+    const int groups = (dst_width + 3) / 4;
+    const bool half = src_width == 2 * dst_width && src_height == 2 * dst_height;
+    if (!half) {
+        orbx_extractor::ResizeTabDev *t = nullptr;
+        for (auto &c : ex->rs_tab)
+            if (c.sw == src_width && c.sh == src_height && c.dw == dst_width && c.dh == dst_height) t = &c;
+        if (!t) {
+            t = &ex->rs_tab[ex->rs_next++ % 4];
+            if (t->sw) ORBX_HIP(hipStreamSynchronize(ex->stream));   // a kernel that reads the slot's old tables may still run
+            t->sw = 0;
+            std::vector<int32_t> xt(2 * (size_t)groups * 4, 0), yt(4 * (size_t)dst_height);
+            for (int x = 0; x < dst_width; x++) {
+                int ofs, c0, c1;
+                resize_tab(src_width, dst_width, true, x, &ofs, &c0, &c1);
+                xt[2 * (size_t)x] = ofs;
+                xt[2 * (size_t)x + 1] = (int32_t)((uint32_t)(uint16_t)(int16_t)c0 | (uint32_t)(uint16_t)(int16_t)c1 << 16);
+            }
+            for (int y = 0; y < dst_height; y++) {
+                int ofs, b0, b1;
+                resize_tab(src_height, dst_height, false, y, &ofs, &b0, &b1);
+                yt[4 * (size_t)y] = std::min(std::max(ofs, 0), src_height - 1);
+                yt[4 * (size_t)y + 1] = std::min(std::max(ofs + 1, 0), src_height - 1);
+                yt[4 * (size_t)y + 2] = b0; yt[4 * (size_t)y + 3] = b1;
+            }
+            int st = t->x.ensure(4 * xt.size());
+            if (st == ORBX_OK) st = t->y.ensure(4 * yt.size());
+            if (st != ORBX_OK) return st;
+            ORBX_HIP(hipMemcpy(t->x.p, xt.data(), 4 * xt.size(), hipMemcpyHostToDevice));
+            ORBX_HIP(hipMemcpy(t->y.p, yt.data(), 4 * yt.size(), hipMemcpyHostToDevice));
+            t->sw = src_width; t->sh = src_height; t->dw = dst_width; t->dh = dst_height;
+        }
+        A.xtab = (const uint2 *)t->x.p; A.ytab = (const uint4 *)t->y.p;
+    }
+    for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
+        A.src = d_src + (size_t)f0 * src_frame_stride; A.dst = d_dst + (size_t)f0 * dst_frame_stride;
+        const dim3 grid((unsigned)((groups + 63) / 64), (unsigned)((dst_height + 3) / 4), (unsigned)std::min(n_frames - f0, kFramesPerLaunch));
+        if (half) hipLaunchKernelGGL(k_resize_half, grid, dim3(256), 0, ex->stream, A);
+        else hipLaunchKernelGGL(k_resize, grid, dim3(256), 0, ex->stream, A);
+    }
+    ORBX_HIP(hipGetLastError());
+    return ORBX_OK;
+}
+
+int orbx_clahe_create(int device, double clip_limit, int tiles_x, int tiles_y, orbx_clahe **out) {
+    if (out) *out = nullptr;
+    if (!out || tiles_x < 1 || tiles_x > kClaheMaxTiles || tiles_y < 1 || tiles_y > kClaheMaxTiles || std::isnan(clip_limit)) return ORBX_E_BAD_ARG;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) {
+        set_error("no usable HIP device (liborbx has no CPU fallback)");
+        return ORBX_E_NO_DEVICE;
+    }
+    orbx_clahe *c = new orbx_clahe;
+    c->device = device; c->tiles_x = tiles_x; c->tiles_y = tiles_y; c->clip_limit = clip_limit;
+    *out = c;
+    return ORBX_OK;
+}
+
+void orbx_clahe_destroy(orbx_clahe *c) {
+    if (!c) return;
+    (void)hipSetDevice(c->device);
+    c->d_lut.release();   // (hipFree waits for the kernels that still use it)
+    delete c;
+}
+
+int orbx_clahe_batch_device(orbx_clahe *c, orbx_extractor *ex, const uint8_t *d_src, int n_frames, int width, int height, size_t src_row_stride,
+                            size_t src_frame_stride, uint8_t *d_dst, size_t dst_row_stride, size_t dst_frame_stride) {
+    RoctxRange rr("orbx:clahe");
+    if (!c || !ex || !d_src || !d_dst || n_frames < 1 || width < 1 || width > kMaxImageSide || height < 1 || height > kMaxImageSide ||
+        ex->device != c->device ||
+        !image_ranges_ok(d_src, n_frames, (size_t)width, height, src_row_stride, src_frame_stride, d_dst, width, height, dst_row_stride, dst_frame_stride,
+                         true))
+        return ORBX_E_BAD_ARG;
+    // clahe.cpp: the image the tables are made from is the source, or the source extended at the right AND at the bottom when either side does not divide
+    int pad_x = 0, pad_y = 0;
+    if (width % c->tiles_x != 0 || height % c->tiles_y != 0) {
+        pad_x = c->tiles_x - width % c->tiles_x;
+        pad_y = c->tiles_y - height % c->tiles_y;
+        if (pad_x >= width || pad_y >= height) return ORBX_E_BAD_ARG;   // BORDER_REFLECT_101 would reflect more than once
+    }
+    ClaheArgs A;
+    A.src = d_src; A.src_row = src_row_stride; A.src_frame = src_frame_stride;
+    A.dst = d_dst; A.dst_row = dst_row_stride; A.dst_frame = dst_frame_stride;
+    A.width = width; A.height = height; A.tiles_x = c->tiles_x; A.tiles_y = c->tiles_y;
+    A.tile_w = (width + pad_x) / c->tiles_x; A.tile_h = (height + pad_y) / c->tiles_y;
+    const int area = A.tile_w * A.tile_h;
+    A.clip = c->clip_limit > 0 ? std::max((int)(c->clip_limit * area / 256), 1) : 0;
+    A.lut_scale = 255.0f / (float)area;
+    A.inv_tw = 1.0f / (float)A.tile_w; A.inv_th = 1.0f / (float)A.tile_h;
+    // the bands of rows between two tile-centre rows, by the kernel's own float expression
+    int b = 0, longest = 0;
+    A.band[0] = 0;
+    for (int y = 0; y < height; y++) {
+        const int ty1 = (int)std::floor((float)y * A.inv_th - 0.5f);
+        while (b < std::min(ty1 + 1, c->tiles_y)) A.band[++b] = y;
+    }
+    while (b < c->tiles_y + 1) A.band[++b] = height;
+    for (int k = 0; k <= c->tiles_y; k++) longest = std::max(longest, A.band[k + 1] - A.band[k]);
+    ORBX_HIP(hipSetDevice(ex->device));
+    const int chunk = std::min(n_frames, kFramesPerLaunch);
+    int st = c->d_lut.ensure((size_t)chunk * c->tiles_x * c->tiles_y * 256);   // (growing it waits for the device: the first batch, or a larger one)
+    if (st != ORBX_OK) return st;
+    A.lut = (uint8_t *)c->d_lut.p;
+    for (int f0 = 0; f0 < n_frames; f0 += kFramesPerLaunch) {
+        const unsigned nf = (unsigned)std::min(n_frames - f0, kFramesPerLaunch);
+        A.src = d_src + (size_t)f0 * src_frame_stride; A.dst = d_dst + (size_t)f0 * dst_frame_stride;
+        hipLaunchKernelGGL(k_clahe_lut, dim3((unsigned)c->tiles_x, (unsigned)c->tiles_y, nf), dim3(256), 0, ex->stream, A);
+        hipLaunchKernelGGL(k_clahe_apply, dim3((unsigned)((longest + kClaheBandRows - 1) / kClaheBandRows), (unsigned)(c->tiles_y + 1), nf), dim3(256),
+                           2 * (size_t)c->tiles_x * 256, ex->stream, A);
+    }
+    ORBX_HIP(hipGetLastError());
     return ORBX_OK;
 }
 

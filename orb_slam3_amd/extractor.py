@@ -189,6 +189,23 @@ class ORBextractor:
         check(self._L.orbx_rgbd_batch_device_u16(self._h, C.c_void_p(d_depth) if d_depth else None, pitch_bytes, frame_stride_bytes, depth_factor, bf),
               "orbx_rgbd_batch_device_u16")
 
+    def gray_batch(self, d_src: int, n: int, width: int, height: int, channels: int, rgb: bool, src_row_stride: int, src_frame_stride: int,
+                   d_dst: int, dst_row_stride: int, dst_frame_stride: int):
+        """Tracking::GrabImage*'s cvtColor(..., COLOR_{RGB,BGR,RGBA,BGRA}2GRAY) for n interleaved 8-bit frames of 3 or 4 channels at the DEVICE address
+        d_src -> n gray frames at d_dst (orbx_gray_batch_device); rgb: the first byte of a pixel is R (mbRGB).  Enqueued on this extractor's stream:
+        extract_batch_device(d_dst, ...) may follow at once.  Both buffers stay untouched until sync() / download_wait()."""
+        check(self._L.orbx_gray_batch_device(self._h, C.c_void_p(d_src) if d_src else None, n, width, height, channels, int(bool(rgb)), src_row_stride,
+                                             src_frame_stride, C.c_void_p(d_dst) if d_dst else None, dst_row_stride, dst_frame_stride),
+              "orbx_gray_batch_device")
+
+    def resize_batch(self, d_src: int, n: int, src_w: int, src_h: int, src_row_stride: int, src_frame_stride: int,
+                     d_dst: int, dst_w: int, dst_h: int, dst_row_stride: int, dst_frame_stride: int):
+        """System::Track*'s cv::resize(im, im, newImSize()) (INTER_LINEAR, 8-bit one channel) for n frames at the DEVICE address d_src -> n frames of
+        dst_w x dst_h at d_dst (orbx_resize_batch_device), enqueued on this extractor's stream like gray_batch."""
+        check(self._L.orbx_resize_batch_device(self._h, C.c_void_p(d_src) if d_src else None, n, src_w, src_h, src_row_stride, src_frame_stride,
+                                               C.c_void_p(d_dst) if d_dst else None, dst_w, dst_h, dst_row_stride, dst_frame_stride),
+              "orbx_resize_batch_device")
+
     def stereo_download(self, frame: int):
         """Returns (n_matches, mvuRight[N], mvDepth[N]) of `frame` (-1 where unmatched)."""
         cap = self.batch_view().cap
@@ -378,3 +395,28 @@ class DeviceRectifier:
         check(self._L.orbx_rectify_batch_device(self._h, extractor._h, C.c_void_p(d_src) if d_src else None, n, src_w, src_h, src_row_stride,
                                                 src_frame_stride, C.c_void_p(d_dst) if d_dst else None, dst_row_stride, dst_frame_stride),
               "orbx_rectify_batch_device")
+
+
+class DeviceClahe:
+    """cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y)) of the TUM-VI examples for batches of 8-bit frames on the device (orbx_clahe_create /
+    orbx_clahe_batch_device).  The object owns the look-up tables of the batch in flight: it serves every extractor of its device, but two batches
+    must never be in flight on it at once (batches through one extractor are ordered by its stream; wait before using it with another)."""
+
+    def __init__(self, clip_limit: float = 3.0, tiles=(8, 8), device: int = 0):
+        self._L = _lib.lib()
+        self._h = C.c_void_p()
+        self.clip_limit, self.tiles, self.device = float(clip_limit), (int(tiles[0]), int(tiles[1])), device
+        check(self._L.orbx_clahe_create(device, self.clip_limit, self.tiles[0], self.tiles[1], C.byref(self._h)), "orbx_clahe_create")
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.orbx_clahe_destroy(self._h)
+            self._h = None
+
+    def apply_batch(self, extractor: ORBextractor, d_src: int, n: int, width: int, height: int, src_row_stride: int, src_frame_stride: int,
+                    d_dst: int, dst_row_stride: int, dst_frame_stride: int):
+        """clahe->apply(src, dst) for n frames at the DEVICE address d_src -> d_dst, enqueued on the extractor's stream: its extract_batch_device on
+        d_dst may follow at once.  d_dst == d_src with equal strides is apply(im, im); any other overlap is refused."""
+        check(self._L.orbx_clahe_batch_device(self._h, extractor._h, C.c_void_p(d_src) if d_src else None, n, width, height, src_row_stride,
+                                              src_frame_stride, C.c_void_p(d_dst) if d_dst else None, dst_row_stride, dst_frame_stride),
+              "orbx_clahe_batch_device")
