@@ -5,6 +5,8 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -101,6 +103,25 @@ struct DevBuf {
         p = nullptr; bytes = 0;
     }
 };
+
+// The layout primitive: buffers of one allocation in the order they are declared, each on a multiple of 256 bytes and owning its size rounded up to 256
+// (k_xfer rounds a run up to 16 bytes).  Used for a matcher call's arena (Carve), for the allocations that stay resident (frame handles, key frames)
+// and for the extractor's pinned staging block (Staged).
+struct Layout {
+    size_t used = 0;
+    static size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+    size_t add(size_t bytes) { const size_t o = used; used += pad(bytes); return o; }
+};
+
+// The asynchronous entry points hand the caller's host pointers straight to the copy engine, so they insist on pinned memory
+// (hipHostMalloc / hipHostRegister, e.g. torch's pin_memory()): pageable memory would be pinned page by page by the runtime behind
+// the caller's back and the copy would not be asynchronous at all.
+inline bool is_pinned_host(const void *p) {
+    if (!p) return true;
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return a.type == hipMemoryTypeHost;
+}
 
 enum { K_PYR_BASE, K_PYR_RESIZE, K_FAST, K_OCTREE, K_FINALIZE, K_BLUR, K_DESCRIBE, K_MATCH_SCAN, K_MATCH_RESOLVE, K_COUNT };
 
@@ -220,12 +241,22 @@ struct orbx_extractor {
     DevBuf d_match, d_nmatch;  // internal match outputs [B][cap], [B] (one matcher per batch: orbx.h)
     int internal_match_owner = 0;   // which batched matcher wrote them for the current batch: 0 none, 1 frame-to-frame, 2 map points
     // cached problem descriptors of orbx_match_consecutive_device
-    struct MatchKey { int n = 0, cap = 0; const void *match = nullptr, *nm = nullptr; float th = 0, du = 0, dv = 0; int ori = 0; const void *kps = nullptr; } mkey;
+    struct MatchKey {
+        int n = 0, cap = 0; const void *match = nullptr, *nm = nullptr; float th = 0, du = 0, dv = 0; int ori = 0; const void *kps = nullptr;
+        bool operator==(const MatchKey &o) const {
+            return n == o.n && cap == o.cap && match == o.match && nm == o.nm && th == o.th && du == o.du && dv == o.dv && ori == o.ori && kps == o.kps;
+        }
+    } mkey;
 
     // batched SearchByProjection(Frame, MapPoints) on the resident batch (orbx_search_mappoints_batch_device)
     DevBuf d_mp_qr, d_mp_qmin, d_mp_qmax, d_mp_valid, d_mp_keys, d_mp_meta, d_mp_grid, d_mp_probs, d_mp_res, d_mp_misc, d_mp_entries;
     struct MpKey { int n = 0, cap = 0, n_mp = 0; const void *px = nullptr, *py = nullptr, *lvl = nullptr, *vc = nullptr, *iv = nullptr, *desc = nullptr,
-                   *match = nullptr, *nm = nullptr, *kps = nullptr; size_t dstride = 0; float th = 0, ratio = 0; } mpkey;
+                   *match = nullptr, *nm = nullptr, *kps = nullptr; size_t dstride = 0; float th = 0, ratio = 0;
+        bool operator==(const MpKey &o) const {
+            return n == o.n && cap == o.cap && n_mp == o.n_mp && px == o.px && py == o.py && lvl == o.lvl && vc == o.vc && iv == o.iv && desc == o.desc &&
+                   match == o.match && nm == o.nm && kps == o.kps && dstride == o.dstride && th == o.th && ratio == o.ratio;
+        }
+    } mpkey;
 
     // camera of the batch path (orbx_set_camera): undistorted keypoints + undistorted image bounds for the batched matchers
     bool has_camera = false;
@@ -245,15 +276,12 @@ struct orbx_extractor {
     unsigned rs_next = 0;
     const void *match_kps() const { return has_camera ? d_kps_un.p : d_kps.p; }
 
-    // Synchronous device -> caller copy through the pinned staging buffer (no caller pointer is ever handed to the HIP runtime: see
-    // PinnedArena in orbx_matcher.hip).  `off` = byte offset inside the staging buffer, so that several copies share one sync.
-    int d2h_staged_begin(size_t total_bytes) { return ensure_stage(total_bytes); }
-    int d2h_staged(size_t off, const void *d_src, size_t bytes) {
-        if (bytes == 0) return ORBX_OK;
-        ORBX_HIP(hipMemcpyAsync((uint8_t *)h_stage + off, d_src, bytes, hipMemcpyDeviceToHost, stream));
-        return ORBX_OK;
-    }
-    const uint8_t *staged(size_t off) const { return (const uint8_t *)h_stage + off; }
+    // One synchronous download through the pinned staging block (no caller pointer is ever handed to the HIP runtime: see PinnedArena in
+    // matcher_context.h).  `copies(S)` names every copy of the call once -- S.view / S.out / S.room (Staged, below) -- and the block's layout, its
+    // size and the transfers are those statements, nothing else.  As orbx_matcher::carve it runs twice: a sizing pass (it only adds up; every pointer
+    // it hands out is NULL), then the block is sized -- before the first copy is issued: growing it frees the old one -- and the pass that issues the
+    // copies on the main stream.  ONE stream synchronisation; then the views may be read and the outputs are in the caller's buffers.
+    template <class F> int download(F &&copies);
 
     int ensure_stage(size_t bytes) {
         if (bytes <= h_stage_bytes) return ORBX_OK;
@@ -266,4 +294,115 @@ struct orbx_extractor {
         return ORBX_OK;
     }
 };
+
+// The copies of one orbx_extractor::download, declared in the order they lie in the staging block.
+struct Staged {
+    orbx_extractor *ex;
+    bool sizing;
+    orbx::Layout L;
+    int err = ORBX_OK;
+    struct Out { void *dst; const uint8_t *src; size_t bytes; } outs[8];
+    int n_outs = 0;
+    // `bytes` from d_src, read by the caller in the block after the synchronisation (headers, counts, rows it unpacks or clamps itself);
+    // the pointer holds until the extractor's next download
+    template <class T> const T *view(const void *d_src, size_t bytes) {
+        const size_t o = L.add(bytes);
+        if (sizing) return nullptr;
+        uint8_t *h = (uint8_t *)ex->h_stage + o;
+        if (bytes && err == ORBX_OK) err = issue(h, d_src, bytes);
+        return reinterpret_cast<const T *>(h);
+    }
+    // `bytes` from d_src delivered to the caller's `dst` after the synchronisation; dst NULL: no copy is issued and nothing is written
+    void out(void *dst, const void *d_src, size_t bytes) {
+        if (!dst) return;
+        const uint8_t *h = view<uint8_t>(d_src, bytes);
+        if (sizing) return;
+        if (n_outs == (int)(sizeof(outs) / sizeof(outs[0]))) { orbx::set_error("a download declared more outputs than Staged holds"); err = ORBX_E_INTERNAL; return; }
+        outs[n_outs++] = Out{dst, h, bytes};
+    }
+    // room that a later download of the same call will take (a two-phase call sizes the block once, in its first phase)
+    void room(size_t bytes) { L.add(bytes); }
+    int issue(void *h, const void *d_src, size_t bytes) {
+        ORBX_HIP(hipMemcpyAsync(h, d_src, bytes, hipMemcpyDeviceToHost, ex->stream));
+        return ORBX_OK;
+    }
+};
+
+template <class F> int orbx_extractor::download(F &&copies) {
+    Staged S{this, true};
+    copies(S);
+    ORBX_TRY(ensure_stage(S.L.used));
+    Staged D{this, false};
+    copies(D);
+    ORBX_TRY(D.err);
+    ORBX_HIP(hipStreamSynchronize(stream));
+    for (int i = 0; i < D.n_outs; i++) memcpy(D.outs[i].dst, D.outs[i].src, D.outs[i].bytes);
+    return ORBX_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// A stage behind an extraction (a batched matcher, a stereo or RGB-D stage): kernels that read the resident batch of one extractor, or of the left /
+// right pair of a rig, while the next batch's pyramid / FAST / quad-tree run on the main stream.  Every such entry point is
+//     st = stage_stream(first);  stage_begin(st, {participants}, ..);  its launches on st;  stage_end(st, {participants});
+// The extractor's side of the protocol: the next k_finalize (enqueue_extract) waits for ev_match while match_pending is set, unless a download issued
+// since then has waited for it on the copy stream already (copy_covers_match: stage_results_on).
+// ---------------------------------------------------------------------------------------------------------
+namespace orbx {
+
+// the stage's stream: the match stream of the first participant; profile mode and side_streams off keep every kernel on the main stream
+inline hipStream_t stage_stream(const orbx_extractor *ex) { return !ex->profile && ex->side_streams ? ex->match_stream : ex->stream; }
+
+// Behind every participant's extraction (ev_describe: its k_undistort and a later materialisation of level 0 included) -- except an extraction
+// enqueued on `st` itself, where stream order says the same -- and, for a stage that overwrites the first participant's d_st_* results, behind the
+// last orbx_stereo_batch_download_async, whose copy may still read them.
+inline int stage_begin(hipStream_t st, std::initializer_list<orbx_extractor *> parts, bool overwrites_stereo_results = false) {
+    for (orbx_extractor *e : parts)
+        if (e->stream != st) ORBX_HIP(hipStreamWaitEvent(st, e->ev_describe, 0));
+    orbx_extractor *first = *parts.begin();
+    if (overwrites_stereo_results && first->stereo_copy_issued)
+        ORBX_HIP(hipStreamWaitEvent(st, first->ev_stereo_copy[(first->stereo_copy_issued - 1) & 1], 0));
+    return ORBX_OK;
+}
+
+// The stage is enqueued: no participant may overwrite its key points / descriptors / counts / pyramid before the stage is done.  ev_match and the two
+// flags change together: the next extraction and the next download read all three.
+inline int stage_end(hipStream_t st, std::initializer_list<orbx_extractor *> parts) {
+    ORBX_HIP(hipGetLastError());
+    for (orbx_extractor *e : parts) {
+        ORBX_HIP(hipEventRecord(e->ev_match, st));
+        e->match_pending = true; e->copy_covers_match = false;
+    }
+    return ORBX_OK;
+}
+
+// A download on copy stream `cs` that reads a pending stage's results waits for the stage; the download's end then implies the stage's.
+inline int stage_results_on(orbx_extractor *ex, hipStream_t cs) {
+    if (ex->match_pending) ORBX_HIP(hipStreamWaitEvent(cs, ex->ev_match, 0));
+    ex->copy_covers_match = ex->match_pending;
+    return ORBX_OK;
+}
+
+// Frame::ComputeStereoFromRGBD for every frame of a resident batch, for either form of the depth images: one launch behind the extraction, no host
+// synchronisation.  `S` arrives with the form's own fields set and is given the ones both forms share.  mvuRight / mvDepth / the count of features
+// with depth land in the rectified stage's result buffers, so the orbx_stereo_batch_download* calls serve both sources.  No pyramid level is read:
+// level 0 is not materialised and the extractor keeps its single slab.
+template <class Stage> int rgbd_stage(orbx_extractor *ex, Stage S, void (*kernel)(const Stage), const void *d_depth, size_t pitch_bytes,
+                                      size_t frame_stride_bytes, float bf) {
+    ORBX_HIP(hipSetDevice(ex->device));
+    for (DevBuf *b : {&ex->d_st_ur, &ex->d_st_depth}) ORBX_TRY(b->ensure(4 * (size_t)ex->cap * ex->batch_cap));
+    ORBX_TRY(ex->d_st_nm.ensure(4 * (size_t)ex->batch_cap));
+    const hipStream_t st = stage_stream(ex);
+    ORBX_TRY(stage_begin(st, {ex}, true));
+    S.kps = (const orbx_keypoint *)ex->d_kps.p; S.kps_un = (const orbx_keypoint *)ex->match_kps();
+    S.count = (const int32_t *)ex->d_count.p;
+    S.depth = (const uint8_t *)d_depth; S.pitch = pitch_bytes; S.frame_stride = frame_stride_bytes;
+    S.cap = ex->cap; S.width = ex->width; S.height = ex->height; S.bf = bf;
+    S.u_right = (float *)ex->d_st_ur.p; S.out_depth = (float *)ex->d_st_depth.p; S.nmatches = (int32_t *)ex->d_st_nm.p;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)ex->last_batch), dim3(256), 0, st, S);
+    ORBX_TRY(stage_end(st, {ex}));
+    ex->st_seq = ex->batch_seq;   // (orbx_frame_load_stereo_batch: the results are this batch's)
+    return ORBX_OK;
+}
+
+}  // namespace orbx
 

@@ -8,17 +8,9 @@
 #include <vector>
 
 #include "matcher_kernels.hip.h"
-#include "extractor_state.h"
+#include "extractor_state.h"   // orbx::Layout, the layout primitive of the arena (Carve) and of the resident allocations, comes from there
 
-// The layout primitive: buffers of one allocation in the order they are declared, each on a multiple of 256 bytes and owning its size rounded up to 256
-// (k_xfer rounds a run up to 16 bytes).  Used for a call's arena (Carve) and for the allocations that stay resident (frame handles, key frames).
 namespace orbx {
-
-struct Layout {
-    size_t used = 0;
-    static size_t pad(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-    size_t add(size_t bytes) { const size_t o = used; used += pad(bytes); return o; }
-};
 
 struct Arena {  // one device buffer, handed out anew on every call (Carve)
     uint8_t *base = nullptr;

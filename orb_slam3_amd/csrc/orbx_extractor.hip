@@ -485,23 +485,21 @@ static int configure(orbx_extractor *ex, int width, int height, int batch) {
     // from here on device tables and buffers change: a failure below must not leave the extractor claiming its old geometry (the early return at
     // the top would then launch on half-updated tables) -- the geometry is committed again at the end
     ex->width = 0; ex->height = 0;
-    int r;
-#define ENS(buf, bytes) if ((r = (buf).ensure(bytes)) != ORBX_OK) return r
-    ENS(ex->d_lv, sizeof(LevelInfo) * nl);
-    ENS(ex->d_xtab, sizeof(ResizeTap) * std::max<size_t>(xtab.size(), 1));
-    ENS(ex->d_ytab, sizeof(ResizeTap) * std::max<size_t>(ytab.size(), 1));
-    ENS(ex->d_xgtab, sizeof(ResizeGroup) * std::max<size_t>(xgtab.size(), 1));
-    ENS(ex->d_fast_tiles, sizeof(TileRef) * fast_tiles.size());
-    ENS(ex->d_blur_items, sizeof(BlurItem) * blur_items.size());
+    ORBX_TRY(ex->d_lv.ensure(sizeof(LevelInfo) * nl));
+    ORBX_TRY(ex->d_xtab.ensure(sizeof(ResizeTap) * std::max<size_t>(xtab.size(), 1)));
+    ORBX_TRY(ex->d_ytab.ensure(sizeof(ResizeTap) * std::max<size_t>(ytab.size(), 1)));
+    ORBX_TRY(ex->d_xgtab.ensure(sizeof(ResizeGroup) * std::max<size_t>(xgtab.size(), 1)));
+    ORBX_TRY(ex->d_fast_tiles.ensure(sizeof(TileRef) * fast_tiles.size()));
+    ORBX_TRY(ex->d_blur_items.ensure(sizeof(BlurItem) * blur_items.size()));
     for (int k = 0; k < 4; k++)
         if (plan_ok[k]) {
-            ENS(ex->ps_plan[k].cols, plans[k].cols.size() * sizeof(PyrColumn));
-            ENS(ex->ps_plan[k].steps, plans[k].steps.size() * sizeof(PyrStep));
-            ENS(ex->ps_plan[k].tasks, plans[k].tasks.size() * sizeof(PyrTask));
-            ENS(ex->ps_plan[k].lists, plans[k].lists.size() * sizeof(PyrWaveList));
+            ORBX_TRY(ex->ps_plan[k].cols.ensure(plans[k].cols.size() * sizeof(PyrColumn)));
+            ORBX_TRY(ex->ps_plan[k].steps.ensure(plans[k].steps.size() * sizeof(PyrStep)));
+            ORBX_TRY(ex->ps_plan[k].tasks.ensure(plans[k].tasks.size() * sizeof(PyrTask)));
+            ORBX_TRY(ex->ps_plan[k].lists.ensure(plans[k].lists.size() * sizeof(PyrWaveList)));
         }
-    ENS(ex->d_pyr, pyr_off * B);
-    if (ex->pyr_double) ENS(ex->d_pyr2, pyr_off * B);
+    ORBX_TRY(ex->d_pyr.ensure(pyr_off * B));
+    if (ex->pyr_double) ORBX_TRY(ex->d_pyr2.ensure(pyr_off * B));
     // The blur on demand (k_describe_fused) filters 43 x 43 pixels per keypoint (VALU bound: +39 us per 256 k keypoints over k_describe), the blur pass
     // (k_blur_stream) every pixel of the pyramid once (HBM bound, 200 us per 285 M pixels, about half of it hidden beside the FAST strips).  Measured
     // (profiles/r04_s_ab_*, r04_t_ab_*): EuRoC 752x480 / 1000 (the keypoints' windows = 1.2 x the pyramid) step 1.053 -> 0.972 ms, TUM-VI 1024x1024 / 1500
@@ -513,25 +511,24 @@ static int configure(orbx_extractor *ex, int width, int height, int batch) {
         const char *v = getenv("ORBX_FUSED_BLUR");
         fused_blur = v && (v[0] == '0' || v[0] == '1') ? v[0] == '1' : (size_t)std::max(ex->prm.nfeatures, 0) * 1369 <= 4 * pyr_px;
     }
-    if (!fused_blur) ENS(ex->d_blur, blur_off * B);   // (orbx_debug_level_blurred allocates it when it is the only user)
-    ENS(ex->d_cellcnt, sizeof(int32_t) * (size_t)cell_base * B);
-    ENS(ex->d_cellent, sizeof(uint32_t) * (size_t)cand_off * B);
-    ENS(ex->d_keys0, sizeof(uint32_t) * (size_t)cand_off * B);
-    ENS(ex->d_keys1, sizeof(uint32_t) * (size_t)cand_off * B);
-    ENS(ex->d_fast_ovf, 4 * (16 + fast_tiles.size() * (size_t)B) + 64);
-    ENS(ex->d_nof0, sizeof(uint16_t) * (size_t)cand_off * B);
-    ENS(ex->d_nof1, sizeof(uint16_t) * (size_t)cand_off * B);
-    ENS(ex->d_lvlkp, sizeof(uint32_t) * (size_t)lvl_off * B);
-    ENS(ex->d_lvlcnt, sizeof(int32_t) * (size_t)nl * B);
-    ENS(ex->d_candtot, sizeof(int32_t) * (size_t)nl * B);
-    ENS(ex->d_work, sizeof(WorkItem) * (size_t)cap * B);
-    ENS(ex->d_kps, sizeof(orbx_keypoint) * (size_t)cap * B);
-    ENS(ex->d_desc, (size_t)32 * cap * B);
-    if (ex->has_camera) { ENS(ex->d_kps_un, sizeof(orbx_keypoint) * (size_t)cap * B); }
-    ENS(ex->d_count, sizeof(int32_t) * (size_t)B);
-    ENS(ex->d_mono, sizeof(int32_t) * (size_t)B);
-    ENS(ex->d_err, sizeof(int32_t));
-#undef ENS
+    if (!fused_blur) ORBX_TRY(ex->d_blur.ensure(blur_off * B));   // (orbx_debug_level_blurred allocates it when it is the only user)
+    ORBX_TRY(ex->d_cellcnt.ensure(sizeof(int32_t) * (size_t)cell_base * B));
+    ORBX_TRY(ex->d_cellent.ensure(sizeof(uint32_t) * (size_t)cand_off * B));
+    ORBX_TRY(ex->d_keys0.ensure(sizeof(uint32_t) * (size_t)cand_off * B));
+    ORBX_TRY(ex->d_keys1.ensure(sizeof(uint32_t) * (size_t)cand_off * B));
+    ORBX_TRY(ex->d_fast_ovf.ensure(4 * (16 + fast_tiles.size() * (size_t)B) + 64));
+    ORBX_TRY(ex->d_nof0.ensure(sizeof(uint16_t) * (size_t)cand_off * B));
+    ORBX_TRY(ex->d_nof1.ensure(sizeof(uint16_t) * (size_t)cand_off * B));
+    ORBX_TRY(ex->d_lvlkp.ensure(sizeof(uint32_t) * (size_t)lvl_off * B));
+    ORBX_TRY(ex->d_lvlcnt.ensure(sizeof(int32_t) * (size_t)nl * B));
+    ORBX_TRY(ex->d_candtot.ensure(sizeof(int32_t) * (size_t)nl * B));
+    ORBX_TRY(ex->d_work.ensure(sizeof(WorkItem) * (size_t)cap * B));
+    ORBX_TRY(ex->d_kps.ensure(sizeof(orbx_keypoint) * (size_t)cap * B));
+    ORBX_TRY(ex->d_desc.ensure((size_t)32 * cap * B));
+    if (ex->has_camera) { ORBX_TRY(ex->d_kps_un.ensure(sizeof(orbx_keypoint) * (size_t)cap * B)); }
+    ORBX_TRY(ex->d_count.ensure(sizeof(int32_t) * (size_t)B));
+    ORBX_TRY(ex->d_mono.ensure(sizeof(int32_t) * (size_t)B));
+    ORBX_TRY(ex->d_err.ensure(sizeof(int32_t)));
     ORBX_HIP(hipMemcpy(ex->d_lv.p, lv.data(), sizeof(LevelInfo) * nl, hipMemcpyHostToDevice));
     if (!xtab.empty()) ORBX_HIP(hipMemcpy(ex->d_xtab.p, xtab.data(), sizeof(ResizeTap) * xtab.size(), hipMemcpyHostToDevice));
     if (!ytab.empty()) ORBX_HIP(hipMemcpy(ex->d_ytab.p, ytab.data(), sizeof(ResizeTap) * ytab.size(), hipMemcpyHostToDevice));
@@ -945,25 +942,11 @@ static int enqueue_extract(orbx_extractor *ex, const uint8_t *d_images, int n, s
     return ORBX_OK;
 }
 
-// The asynchronous entry points hand the caller's host pointers straight to the copy engine, so they insist on pinned memory
-// (hipHostMalloc / hipHostRegister, e.g. torch's pin_memory()): pageable memory would be pinned page by page by the runtime behind
-// the caller's back and the copy would not be asynchronous at all.
-static bool is_pinned_host(const void *p) {
-    if (!p) return true;
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return a.type == hipMemoryTypeHost;
-}
-
 static int check_device_error(orbx_extractor *ex) {
-    int r0 = ex->ensure_stage(64);
-    if (r0 != ORBX_OK) return r0;
-    ORBX_HIP(hipMemcpyAsync(ex->h_stage, ex->d_err.p, sizeof(int32_t), hipMemcpyDeviceToHost, ex->stream));
-    ORBX_HIP(hipStreamSynchronize(ex->stream));
-    int32_t e = 0;
-    memcpy(&e, ex->h_stage, sizeof(e));
-    if (e != 0) {
-        set_error("device-side consistency check failed, code " + std::to_string(e));
+    const int32_t *e = nullptr;
+    ORBX_TRY(ex->download([&](Staged &S) { e = S.view<int32_t>(ex->d_err.p, sizeof(int32_t)); }));
+    if (*e != 0) {
+        set_error("device-side consistency check failed, code " + std::to_string(*e));
         (void)hipMemsetAsync(ex->d_err.p, 0, sizeof(int32_t), ex->stream);
         return ORBX_E_INTERNAL;
     }
@@ -1203,16 +1186,16 @@ int orbx_set_camera(orbx_extractor *ex, const orbx_camera *cam) {
 int orbx_batch_download_keypoints_un(orbx_extractor *ex, int frame, orbx_keypoint *kps_un, int cap, int *n_out) {
     if (!ex || frame < 0 || frame >= ex->last_batch) return ORBX_E_BAD_ARG;
     ORBX_HIP(hipSetDevice(ex->device));
-    int r = ex->d2h_staged_begin(64 + sizeof(orbx_keypoint) * (size_t)ex->cap);
-    if (r != ORBX_OK) return r;
-    if ((r = ex->d2h_staged(0, (int32_t *)ex->d_count.p + frame, 4)) != ORBX_OK) return r;
-    if ((r = ex->d2h_staged(64, (const orbx_keypoint *)ex->match_kps() + (size_t)frame * ex->cap, sizeof(orbx_keypoint) * (size_t)ex->cap)) != ORBX_OK) return r;
-    ORBX_HIP(hipStreamSynchronize(ex->stream));
-    int32_t n = 0;
-    memcpy(&n, ex->staged(0), 4);
+    const int32_t *count = nullptr;
+    const orbx_keypoint *k = nullptr;
+    ORBX_TRY(ex->download([&](Staged &S) {
+        count = S.view<int32_t>((int32_t *)ex->d_count.p + frame, 4);
+        k = S.view<orbx_keypoint>((const orbx_keypoint *)ex->match_kps() + (size_t)frame * ex->cap, sizeof(orbx_keypoint) * (size_t)ex->cap);
+    }));
+    const int32_t n = *count;
     if (n_out) *n_out = n;
     if (n > cap) return ORBX_E_CAPACITY;
-    if (n > 0 && kps_un) memcpy(kps_un, ex->staged(64), sizeof(orbx_keypoint) * (size_t)n);
+    if (n > 0 && kps_un) memcpy(kps_un, k, sizeof(orbx_keypoint) * (size_t)n);
     return ORBX_OK;
 }
 
@@ -1250,47 +1233,37 @@ int orbx_batch_view_get(orbx_extractor *ex, orbx_batch_view *v) {
 int orbx_batch_download(orbx_extractor *ex, int frame, orbx_keypoint *kps, uint8_t *desc, int cap, int *n_out, int *mono) {
     if (!ex || frame < 0 || frame >= ex->last_batch) return ORBX_E_BAD_ARG;
     ORBX_HIP(hipSetDevice(ex->device));
-    int r = check_device_error(ex);
-    if (r != ORBX_OK) return r;
-    if ((r = ex->d2h_staged_begin(64 + (size_t)ex->cap * (sizeof(orbx_keypoint) + 32))) != ORBX_OK) return r;
-    if ((r = ex->d2h_staged(0, (int32_t *)ex->d_count.p + frame, 4)) != ORBX_OK) return r;
-    if ((r = ex->d2h_staged(4, (int32_t *)ex->d_mono.p + frame, 4)) != ORBX_OK) return r;
-    ORBX_HIP(hipStreamSynchronize(ex->stream));
-    int32_t cm[2];
-    memcpy(cm, ex->staged(0), 8);
-    if (n_out) *n_out = cm[0];
-    if (mono) *mono = cm[1];
-    if (cm[0] > cap) return ORBX_E_CAPACITY;
-    if (cm[0] > 0) {
-        const size_t kb = sizeof(orbx_keypoint) * (size_t)cm[0], db = (size_t)32 * cm[0], off_d = 64 + (size_t)ex->cap * sizeof(orbx_keypoint);
-        if (kps && (r = ex->d2h_staged(64, (orbx_keypoint *)ex->d_kps.p + (size_t)frame * ex->cap, kb)) != ORBX_OK) return r;
-        if (desc && (r = ex->d2h_staged(off_d, (uint8_t *)ex->d_desc.p + (size_t)frame * ex->cap * 32, db)) != ORBX_OK) return r;
-        ORBX_HIP(hipStreamSynchronize(ex->stream));
-        if (kps) memcpy(kps, ex->staged(64), kb);
-        if (desc) memcpy(desc, ex->staged(off_d), db);
-    }
-    return ORBX_OK;
+    ORBX_TRY(check_device_error(ex));
+    // two phases: the counts first, then exactly n key points and descriptors (the block is sized once, for the most the second phase can take)
+    const int32_t *count = nullptr, *mono_index = nullptr;
+    ORBX_TRY(ex->download([&](Staged &S) {
+        count = S.view<int32_t>((int32_t *)ex->d_count.p + frame, 4);
+        mono_index = S.view<int32_t>((int32_t *)ex->d_mono.p + frame, 4);
+        S.room(sizeof(orbx_keypoint) * (size_t)ex->cap);
+        S.room((size_t)32 * ex->cap);
+    }));
+    const int32_t n = *count;
+    if (n_out) *n_out = n;
+    if (mono) *mono = *mono_index;
+    if (n > cap) return ORBX_E_CAPACITY;
+    if (n <= 0) return ORBX_OK;
+    return ex->download([&](Staged &S) {
+        S.out(kps, (orbx_keypoint *)ex->d_kps.p + (size_t)frame * ex->cap, sizeof(orbx_keypoint) * (size_t)n);
+        S.out(desc, (uint8_t *)ex->d_desc.p + (size_t)frame * ex->cap * 32, (size_t)32 * n);
+    });
 }
 
 int orbx_batch_download_all(orbx_extractor *ex, orbx_keypoint *kps, uint8_t *desc, int32_t *counts, int32_t *mono) {
     if (!ex || ex->last_batch <= 0) return ORBX_E_BAD_ARG;
     ORBX_HIP(hipSetDevice(ex->device));
     const size_t n = (size_t)ex->last_batch;
-    const size_t cb = 4 * n, kb = sizeof(orbx_keypoint) * (size_t)ex->cap * n, db = (size_t)32 * ex->cap * n;
-    const size_t o_m = (cb + 63) & ~(size_t)63, o_k = 2 * o_m, o_d = o_k + ((kb + 63) & ~(size_t)63);
-    int r = check_device_error(ex);
-    if (r != ORBX_OK) return r;
-    if ((r = ex->d2h_staged_begin(o_d + db)) != ORBX_OK) return r;
-    if (counts && (r = ex->d2h_staged(0, ex->d_count.p, cb)) != ORBX_OK) return r;
-    if (mono && (r = ex->d2h_staged(o_m, ex->d_mono.p, cb)) != ORBX_OK) return r;
-    if (kps && (r = ex->d2h_staged(o_k, ex->d_kps.p, kb)) != ORBX_OK) return r;
-    if (desc && (r = ex->d2h_staged(o_d, ex->d_desc.p, db)) != ORBX_OK) return r;
-    ORBX_HIP(hipStreamSynchronize(ex->stream));
-    if (counts) memcpy(counts, ex->staged(0), cb);
-    if (mono) memcpy(mono, ex->staged(o_m), cb);
-    if (kps) memcpy(kps, ex->staged(o_k), kb);
-    if (desc) memcpy(desc, ex->staged(o_d), db);
-    return ORBX_OK;
+    ORBX_TRY(check_device_error(ex));
+    return ex->download([&](Staged &S) {
+        S.out(counts, ex->d_count.p, 4 * n);
+        S.out(mono, ex->d_mono.p, 4 * n);
+        S.out(kps, ex->d_kps.p, sizeof(orbx_keypoint) * (size_t)ex->cap * n);
+        S.out(desc, ex->d_desc.p, (size_t)32 * ex->cap * n);
+    });
 }
 
 int orbx_batch_download_async(orbx_extractor *ex, orbx_keypoint *kps, uint8_t *desc, int32_t *counts, int32_t *mono,
@@ -1317,8 +1290,7 @@ int orbx_batch_download_async(orbx_extractor *ex, orbx_keypoint *kps, uint8_t *d
     if (mono) ORBX_HIP(hipMemcpyAsync(mono, ex->d_mono.p, 4 * (size_t)n, hipMemcpyDeviceToHost, cs));
     if (kps) ORBX_HIP(hipMemcpyAsync(kps, ex->d_kps.p, sizeof(orbx_keypoint) * (size_t)ex->cap * n, hipMemcpyDeviceToHost, cs));
     if (desc) ORBX_HIP(hipMemcpyAsync(desc, ex->d_desc.p, (size_t)32 * ex->cap * n, hipMemcpyDeviceToHost, cs));
-    if (ex->match_pending) ORBX_HIP(hipStreamWaitEvent(cs, ex->ev_match, 0));
-    ex->copy_covers_match = ex->match_pending;
+    ORBX_TRY(stage_results_on(ex, cs));
     if (match && ex->d_match.p) ORBX_HIP(hipMemcpyAsync(match, ex->d_match.p, 4 * (size_t)ex->cap * n, hipMemcpyDeviceToHost, cs));
     if (nmatches && ex->d_nmatch.p) ORBX_HIP(hipMemcpyAsync(nmatches, ex->d_nmatch.p, 4 * (size_t)n, hipMemcpyDeviceToHost, cs));
     const unsigned slot = ex->copy_issued & 1;
@@ -1399,13 +1371,11 @@ int orbx_get_level(orbx_extractor *ex, int frame, int level, uint8_t *dst, size_
     if (dst_stride < (size_t)(L.w + 2 * kEdge)) return ORBX_E_BAD_ARG;
     ORBX_HIP(hipSetDevice(ex->device));
     if (level == 0) { int r0 = orbx_materialize_level0(ex); if (r0 != ORBX_OK) return r0; }
-    const uint8_t *src = (const uint8_t *)ex->pyr_cur() + (size_t)frame * ex->pyr_frame + L.off;
-    const size_t bytes = (size_t)L.pitch * (L.h + 2 * kEdge);
-    int r = ex->d2h_staged_begin(bytes);
-    if (r != ORBX_OK) return r;
-    if ((r = ex->d2h_staged(0, src, bytes)) != ORBX_OK) return r;
-    ORBX_HIP(hipStreamSynchronize(ex->stream));
-    for (int y = 0; y < L.h + 2 * kEdge; y++) memcpy(dst + (size_t)y * dst_stride, ex->staged((size_t)y * L.pitch + kRingX), (size_t)(L.w + 2 * kEdge));
+    const uint8_t *rows = nullptr;
+    ORBX_TRY(ex->download([&](Staged &S) {
+        rows = S.view<uint8_t>((const uint8_t *)ex->pyr_cur() + (size_t)frame * ex->pyr_frame + L.off, (size_t)L.pitch * (L.h + 2 * kEdge));
+    }));
+    for (int y = 0; y < L.h + 2 * kEdge; y++) memcpy(dst + (size_t)y * dst_stride, rows + (size_t)y * L.pitch + kRingX, (size_t)(L.w + 2 * kEdge));
     return ORBX_OK;
 }
 
@@ -1446,14 +1416,12 @@ int orbx_debug_level_candidates(orbx_extractor *ex, int frame, int level, orbx_k
     ORBX_HIP(hipStreamSynchronize(ex->stream));
     const LevelInfo &L = ex->lv[level];
     const int ncell = L.nCols * L.nRows;
-    const size_t cb = 4 * (size_t)ncell, eb = 4 * (size_t)L.cand_cap, eoff = (cb + 63) & ~(size_t)63;
-    int r = ex->d2h_staged_begin(eoff + eb);
-    if (r != ORBX_OK) return r;
-    if ((r = ex->d2h_staged(0, (int32_t *)ex->d_cellcnt.p + (size_t)frame * ex->total_cells + L.cell_base, cb)) != ORBX_OK) return r;
-    if ((r = ex->d2h_staged(eoff, (uint32_t *)ex->d_cellent.p + (size_t)frame * ex->cand_frame + L.cand_off, eb)) != ORBX_OK) return r;
-    ORBX_HIP(hipStreamSynchronize(ex->stream));
-    const int32_t *cnt = (const int32_t *)ex->staged(0);
-    const uint32_t *ent = (const uint32_t *)ex->staged(eoff);
+    const int32_t *cnt = nullptr;
+    const uint32_t *ent = nullptr;
+    ORBX_TRY(ex->download([&](Staged &S) {
+        cnt = S.view<int32_t>((int32_t *)ex->d_cellcnt.p + (size_t)frame * ex->total_cells + L.cell_base, 4 * (size_t)ncell);
+        ent = S.view<uint32_t>((uint32_t *)ex->d_cellent.p + (size_t)frame * ex->cand_frame + L.cand_off, 4 * (size_t)L.cand_cap);
+    }));
     int n = 0;
     for (int c = 0; c < ncell; c++)
         for (int k = 0; k < cnt[c]; k++) {
@@ -1469,15 +1437,13 @@ int orbx_debug_level_keypoints(orbx_extractor *ex, int frame, int level, orbx_ke
     ORBX_HIP(hipSetDevice(ex->device));
     ORBX_HIP(hipStreamSynchronize(ex->stream));
     const LevelInfo &L = ex->lv[level];
-    int r = ex->d2h_staged_begin(64 + 4 * (size_t)L.lvl_cap);
-    if (r != ORBX_OK) return r;
-    if ((r = ex->d2h_staged(0, (int32_t *)ex->d_lvlcnt.p + (size_t)frame * ex->prm.nlevels + level, 4)) != ORBX_OK) return r;
-    if ((r = ex->d2h_staged(64, (uint32_t *)ex->d_lvlkp.p + (size_t)frame * ex->lvl_frame + L.lvl_off, 4 * (size_t)L.lvl_cap)) != ORBX_OK) return r;
-    ORBX_HIP(hipStreamSynchronize(ex->stream));
-    int32_t n = 0;
-    memcpy(&n, ex->staged(0), 4);
-    n = std::min(std::max(n, 0), L.lvl_cap);
-    const uint32_t *keys = (const uint32_t *)ex->staged(64);
+    const int32_t *count = nullptr;
+    const uint32_t *keys = nullptr;
+    ORBX_TRY(ex->download([&](Staged &S) {
+        count = S.view<int32_t>((int32_t *)ex->d_lvlcnt.p + (size_t)frame * ex->prm.nlevels + level, 4);
+        keys = S.view<uint32_t>((uint32_t *)ex->d_lvlkp.p + (size_t)frame * ex->lvl_frame + L.lvl_off, 4 * (size_t)L.lvl_cap);
+    }));
+    const int n = std::min(std::max(*count, 0), L.lvl_cap);
     for (int i = 0; i < n && i < cap && out; i++)
         out[i] = orbx_keypoint{(float)key_x(keys[i]), (float)key_y(keys[i]), L.size, -1.f, (float)key_s(keys[i]), level, -1};
     return n;
@@ -1488,18 +1454,17 @@ int orbx_debug_level_blurred(orbx_extractor *ex, int frame, int level, uint8_t *
     const LevelInfo &L = ex->lv[level];
     if (dst_stride < (size_t)L.w) return ORBX_E_BAD_ARG;
     ORBX_HIP(hipSetDevice(ex->device));
-    const size_t bytes = (size_t)L.bpitch * L.h;
-    int r = ex->d2h_staged_begin(bytes);
-    if (r != ORBX_OK) return r;
     if (ex->fused_blur) {   // k_describe_fused blurs around the keypoints only: fill the blur slab of the last batch now
-        if ((r = ex->d_blur.ensure(ex->blur_frame * (size_t)ex->batch_cap)) != ORBX_OK) return r;
-        if ((r = orbx_materialize_level0(ex)) != ORBX_OK) return r;
+        ORBX_TRY(ex->d_blur.ensure(ex->blur_frame * (size_t)ex->batch_cap));
+        ORBX_TRY(orbx_materialize_level0(ex));
         launch_blur_stream(ex, ex->last_batch, ex->pyr_cur(), ex->stream);
         ORBX_HIP(hipGetLastError());
     }
-    if ((r = ex->d2h_staged(0, (const uint8_t *)ex->d_blur.p + (size_t)frame * ex->blur_frame + L.boff, bytes)) != ORBX_OK) return r;
-    ORBX_HIP(hipStreamSynchronize(ex->stream));
-    for (int y = 0; y < L.h; y++) memcpy(dst + (size_t)y * dst_stride, ex->staged((size_t)y * L.bpitch), (size_t)L.w);
+    const uint8_t *rows = nullptr;
+    ORBX_TRY(ex->download([&](Staged &S) {
+        rows = S.view<uint8_t>((const uint8_t *)ex->d_blur.p + (size_t)frame * ex->blur_frame + L.boff, (size_t)L.bpitch * L.h);
+    }));
+    for (int y = 0; y < L.h; y++) memcpy(dst + (size_t)y * dst_stride, rows + (size_t)y * L.bpitch, (size_t)L.w);
     return ORBX_OK;
 }
 
@@ -1550,15 +1515,12 @@ int orbx_debug_stage_stats(orbx_extractor *ex, int64_t *out, int cap) {
     ORBX_HIP(hipSetDevice(ex->device));
     ORBX_HIP(hipStreamSynchronize(ex->stream));
     const int nl = ex->prm.nlevels, B = ex->last_batch;
-    const size_t cb = sizeof(int32_t) * (size_t)nl * B;
-    int r = ex->d2h_staged_begin(64 + cb);
-    if (r != ORBX_OK) return r;
-    if ((r = ex->d2h_staged(0, ex->d_fast_ovf.p, 4)) != ORBX_OK) return r;
-    if ((r = ex->d2h_staged(64, ex->d_candtot.p, cb)) != ORBX_OK) return r;
-    ORBX_HIP(hipStreamSynchronize(ex->stream));
-    int32_t listed = 0;
-    memcpy(&listed, ex->staged(0), 4);
-    const int32_t *ct = (const int32_t *)ex->staged(64);
+    const int32_t *listed_cells = nullptr, *ct = nullptr;
+    ORBX_TRY(ex->download([&](Staged &S) {
+        listed_cells = S.view<int32_t>(ex->d_fast_ovf.p, 4);
+        ct = S.view<int32_t>(ex->d_candtot.p, sizeof(int32_t) * (size_t)nl * B);
+    }));
+    const int32_t listed = *listed_cells;
     int64_t t1 = 0, t2 = 0, t3 = 0, total = 0, most = 0;
     for (int i = 0; i < nl * B; i++) {
         const int64_t c = ct[i];
@@ -1576,11 +1538,9 @@ int orbx_tune_fast_queues(orbx_extractor *ex, int mode, int32_t info[4]) {
     const int64_t cells = (int64_t)ex->total_cells * std::max(ex->last_batch, 0);
     if (ex->last_batch > 0 && ex->fast_strip) {
         ORBX_HIP(hipStreamSynchronize(ex->stream));
-        int r = ex->d2h_staged_begin(64);
-        if (r != ORBX_OK) return r;
-        if ((r = ex->d2h_staged(0, ex->d_fast_ovf.p, 4)) != ORBX_OK) return r;
-        ORBX_HIP(hipStreamSynchronize(ex->stream));
-        memcpy(&listed, ex->staged(0), 4);
+        const int32_t *listed_cells = nullptr;
+        ORBX_TRY(ex->download([&](Staged &S) { listed_cells = S.view<int32_t>(ex->d_fast_ovf.p, 4); }));
+        listed = *listed_cells;
     }
     const int g0 = ex->strip_gcap, q0 = ex->strip_qcap;
     const int gdef = orbx_extractor::kStripGcap0, qdef = orbx_extractor::kStripQcap0;
@@ -1752,29 +1712,9 @@ int orbx_rgbd_batch_device_u16(orbx_extractor *ex, const uint16_t *d_depth, size
         return ORBX_E_BAD_ARG;
     // every row of every image must be a row of aligned 16-bit values
     if (((uintptr_t)d_depth | pitch_bytes | frame_stride_bytes) & 1u) return ORBX_E_BAD_ARG;
-    ORBX_HIP(hipSetDevice(ex->device));
-    const int n = ex->last_batch;
-    int r;
-    for (DevBuf *b : {&ex->d_st_ur, &ex->d_st_depth})
-        if ((r = b->ensure(4 * (size_t)ex->cap * ex->batch_cap)) != ORBX_OK) return r;
-    if ((r = ex->d_st_nm.ensure(4 * (size_t)ex->batch_cap)) != ORBX_OK) return r;
-    const bool side = !ex->profile && ex->side_streams;
-    hipStream_t st = side ? ex->match_stream : ex->stream;
-    ORBX_HIP(hipStreamWaitEvent(st, ex->ev_describe, 0));   // the extraction of this batch (its k_undistort included)
-    if (ex->stereo_copy_issued) ORBX_HIP(hipStreamWaitEvent(st, ex->ev_stereo_copy[(ex->stereo_copy_issued - 1) & 1], 0));  // the previous results may still be on their way to the host
-    RgbdU16Stage S;
-    S.kps = (const orbx_keypoint *)ex->d_kps.p; S.kps_un = (const orbx_keypoint *)ex->match_kps();
-    S.count = (const int32_t *)ex->d_count.p;
-    S.depth = (const uint8_t *)d_depth; S.pitch = pitch_bytes; S.frame_stride = frame_stride_bytes;
-    S.cap = ex->cap; S.width = ex->width; S.height = ex->height; S.bf = bf; S.depth_factor = depth_factor;
-    S.u_right = (float *)ex->d_st_ur.p; S.out_depth = (float *)ex->d_st_depth.p; S.nmatches = (int32_t *)ex->d_st_nm.p;
-    hipLaunchKernelGGL(k_stereo_from_rgbd_u16, dim3((unsigned)n), dim3(256), 0, st, S);
-    ORBX_HIP(hipGetLastError());
-    ex->st_seq = ex->batch_seq;
-    // the extractor must not overwrite its key points / counts before the kernel is done
-    ORBX_HIP(hipEventRecord(ex->ev_match, st));
-    ex->match_pending = true; ex->copy_covers_match = false;
-    return ORBX_OK;
+    RgbdU16Stage S{};
+    S.depth_factor = depth_factor;
+    return rgbd_stage(ex, S, k_stereo_from_rgbd_u16, d_depth, pitch_bytes, frame_stride_bytes, bf);
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -2203,6 +2203,27 @@ int orbx_debug_kb8_epipolar(orbx_matcher *m, const float *cam1_2x8, const float 
 
 }  // extern "C"
 
+// The internal result buffers (downloaded by orbx_batch_download_async) for one of the two batched matchers of the current batch: owner 1 the
+// frame-to-frame matcher, 2 the map-point search (one matcher per batch: orbx.h).
+static int claim_internal_match(orbx_extractor *ex, int owner, int32_t **d_match, int32_t **d_nmatches) {
+    if (ex->internal_match_owner == 3 - owner) {
+        set_error(owner == 1 ? "the internal match buffers hold the map-point search of this batch: download it first, or pass result buffers"
+                             : "the internal match buffers hold the frame-to-frame matches of this batch: download them first, or pass result buffers");
+        return ORBX_E_BAD_ARG;
+    }
+    ex->internal_match_owner = owner;
+    const size_t mb = 4 * (size_t)ex->cap * ex->batch_cap, nb = 4 * (size_t)ex->batch_cap;
+    if (ex->d_match.bytes < mb || ex->d_nmatch.bytes < nb) {
+        // growing frees the old buffers: an earlier matcher / download may still be using them
+        ORBX_HIP(hipStreamSynchronize(ex->match_stream)); ORBX_HIP(hipStreamSynchronize(ex->copy_stream));
+    }
+    ORBX_TRY(ex->d_match.ensure(mb));
+    ORBX_TRY(ex->d_nmatch.ensure(nb));
+    *d_match = (int32_t *)ex->d_match.p;
+    *d_nmatches = (int32_t *)ex->d_nmatch.p;
+    return ORBX_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Device-resident batched frame-to-frame matcher (throughput path): problem f-1 matches frame f-1 (queries)
 // into frame f of the extractor's last batch; everything stays in HBM on the extractor's stream.
@@ -2216,37 +2237,20 @@ extern "C" int orbx_match_consecutive_device(orbx_extractor *ex, float th, float
     if (ex->cap > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;
     ORBX_HIP(hipSetDevice(ex->device));
     const int np = n - 1, cap = ex->cap;
-    int r;
-    if (!d_match || !d_nmatches) {  // internal result buffers (downloaded by orbx_batch_download_async)
-        if (ex->internal_match_owner == 2) { set_error("the internal match buffers hold the map-point search of this batch: download it first, or pass result buffers"); return ORBX_E_BAD_ARG; }
-        ex->internal_match_owner = 1;
-        if (ex->d_match.bytes < 4 * (size_t)cap * ex->batch_cap || ex->d_nmatch.bytes < 4 * (size_t)ex->batch_cap) {
-            // growing frees the old buffers: an earlier matcher / download may still be using them
-            ORBX_HIP(hipStreamSynchronize(ex->match_stream)); ORBX_HIP(hipStreamSynchronize(ex->copy_stream));
-        }
-        if ((r = ex->d_match.ensure(4 * (size_t)cap * ex->batch_cap)) != ORBX_OK) return r;
-        if ((r = ex->d_nmatch.ensure(4 * (size_t)ex->batch_cap)) != ORBX_OK) return r;
-        d_match = (int32_t *)ex->d_match.p;
-        d_nmatches = (int32_t *)ex->d_nmatch.p;
-    }
+    if (!d_match || !d_nmatches) ORBX_TRY(claim_internal_match(ex, 1, &d_match, &d_nmatches));
     const orbx_keypoint *kps = (const orbx_keypoint *)ex->match_kps();   // mvKeysUn (== mvKeys without a distortion model)
     orbx_extractor::MatchKey key;
     key.n = n; key.cap = cap; key.match = d_match; key.nm = d_nmatches; key.th = th; key.du = du; key.dv = dv;
     key.ori = check_orientation; key.kps = kps;
-    const orbx_extractor::MatchKey &old = ex->mkey;
-    const bool cached = old.n == key.n && old.cap == key.cap && old.match == key.match && old.nm == key.nm && old.th == key.th &&
-                        old.du == key.du && old.dv == key.dv && old.ori == key.ori && old.kps == key.kps;
-    if (!cached) {  // (re)build the per-pair problem descriptors; steady-state batches reuse them without any host sync
+    if (!(key == ex->mkey)) {  // (re)build the per-pair problem descriptors; steady-state batches reuse them without any host sync
         ORBX_HIP(hipStreamSynchronize(ex->match_stream));   // the scratch below may be in use by the previous batch's matcher
-#define ENS(buf, bytes) if ((r = (buf).ensure(bytes)) != ORBX_OK) return r
-        ENS(ex->d_mkey1, 8 * (size_t)kTopK * cap * np);
-        ENS(ex->d_mkey2, 4 * (size_t)cap * np);
-        ENS(ex->d_mentries, 4 * (size_t)cap * np);
-        ENS(ex->d_mgrid, 2 * ((size_t)kGridCells + 1 + 63 + cap) * np);
-        ENS(ex->d_mprobs, sizeof(WindowProblem) * (size_t)np);
-        ENS(ex->d_mres, sizeof(ResolveProblem) * (size_t)np);
-        ENS(ex->d_mscale, sizeof(float) * ex->prm.nlevels);
-#undef ENS
+        ORBX_TRY(ex->d_mkey1.ensure(8 * (size_t)kTopK * cap * np));
+        ORBX_TRY(ex->d_mkey2.ensure(4 * (size_t)cap * np));
+        ORBX_TRY(ex->d_mentries.ensure(4 * (size_t)cap * np));
+        ORBX_TRY(ex->d_mgrid.ensure(2 * ((size_t)kGridCells + 1 + 63 + cap) * np));
+        ORBX_TRY(ex->d_mprobs.ensure(sizeof(WindowProblem) * (size_t)np));
+        ORBX_TRY(ex->d_mres.ensure(sizeof(ResolveProblem) * (size_t)np));
+        ORBX_TRY(ex->d_mscale.ensure(sizeof(float) * ex->prm.nlevels));
         std::vector<WindowProblem> P(np);
         std::vector<ResolveProblem> R(np);
         const uint8_t *desc = (const uint8_t *)ex->d_desc.p;
@@ -2276,9 +2280,8 @@ extern "C" int orbx_match_consecutive_device(orbx_extractor *ex, float th, float
     }
     const GridParams g = grid_of(ex->bounds);  // mnMinX.. of the extractor's camera (image rectangle without one, Frame.cc:804-807)
     // the matcher of batch i runs on its own stream beside the pyramid / FAST / quad-tree of batch i+1
-    const bool side = !ex->profile && ex->side_streams;
-    hipStream_t ms = side ? ex->match_stream : ex->stream;
-    if (side) ORBX_HIP(hipStreamWaitEvent(ms, ex->ev_describe, 0));
+    const hipStream_t ms = stage_stream(ex);
+    ORBX_TRY(stage_begin(ms, {ex}));
     hipEvent_t e0 = ex->ev0, e1 = ex->ev1;
     if (ex->profile) (void)hipEventRecord(e0, ms);
     ORBX_LAUNCH_GRID_BUILD( dim3(np), dim3(64), 0, ms, (const WindowProblem *)ex->d_mprobs.p, g);
@@ -2295,10 +2298,7 @@ extern "C" int orbx_match_consecutive_device(orbx_extractor *ex, float th, float
         float t = 0; (void)hipEventElapsedTime(&t, e0, e1);
         ex->prof_ms[K_MATCH_RESOLVE] += t; ex->prof_n[K_MATCH_RESOLVE]++;
     }
-    ORBX_HIP(hipEventRecord(ex->ev_match, ms));
-    ex->match_pending = true; ex->copy_covers_match = false;
-    ORBX_HIP(hipGetLastError());
-    return ORBX_OK;
+    return stage_end(ms, {ex});
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2318,38 +2318,21 @@ extern "C" int orbx_search_mappoints_batch_device(orbx_extractor *ex, int n_mp, 
     if (ex->cap > kMaxResolveFeatures) return ORBX_E_TOO_LARGE;
     ORBX_HIP(hipSetDevice(ex->device));
     const int cap = ex->cap;
-    int r;
-    if (!d_match || !d_nmatches) {  // internal result buffers (downloaded by orbx_batch_download_async)
-        if (ex->internal_match_owner == 1) { set_error("the internal match buffers hold the frame-to-frame matches of this batch: download them first, or pass result buffers"); return ORBX_E_BAD_ARG; }
-        ex->internal_match_owner = 2;
-        if (ex->d_match.bytes < 4 * (size_t)cap * ex->batch_cap || ex->d_nmatch.bytes < 4 * (size_t)ex->batch_cap) {
-            ORBX_HIP(hipStreamSynchronize(ex->match_stream)); ORBX_HIP(hipStreamSynchronize(ex->copy_stream));
-        }
-        if ((r = ex->d_match.ensure(4 * (size_t)cap * ex->batch_cap)) != ORBX_OK) return r;
-        if ((r = ex->d_nmatch.ensure(4 * (size_t)ex->batch_cap)) != ORBX_OK) return r;
-        d_match = (int32_t *)ex->d_match.p;
-        d_nmatches = (int32_t *)ex->d_nmatch.p;
-    }
+    if (!d_match || !d_nmatches) ORBX_TRY(claim_internal_match(ex, 2, &d_match, &d_nmatches));
     const orbx_keypoint *kps = (const orbx_keypoint *)ex->match_kps();
     orbx_extractor::MpKey key;
     key.n = n; key.cap = cap; key.n_mp = n_mp; key.px = d_proj_x; key.py = d_proj_y; key.lvl = d_level; key.vc = d_view_cos; key.iv = d_in_view;
     key.desc = d_mp_desc; key.match = d_match; key.nm = d_nmatches; key.kps = kps; key.dstride = desc_frame_stride; key.th = th; key.ratio = nnratio;
-    const orbx_extractor::MpKey &o = ex->mpkey;
-    const bool cached = o.n == key.n && o.cap == key.cap && o.n_mp == key.n_mp && o.px == key.px && o.py == key.py && o.lvl == key.lvl &&
-                        o.vc == key.vc && o.iv == key.iv && o.desc == key.desc && o.match == key.match && o.nm == key.nm && o.kps == key.kps &&
-                        o.dstride == key.dstride && o.th == key.th && o.ratio == key.ratio;
     const size_t nq_all = (size_t)std::max(n_mp, 1) * n;
-    if (!cached) {  // (re)build the per-frame problem descriptors; steady-state batches reuse them without a host sync
+    if (!(key == ex->mpkey)) {  // (re)build the per-frame problem descriptors; steady-state batches reuse them without a host sync
         ORBX_HIP(hipStreamSynchronize(ex->match_stream));   // the scratch below may be in use by the previous batch's matcher
-#define ENS(buf, bytes) if ((r = (buf).ensure(bytes)) != ORBX_OK) return r
-        ENS(ex->d_mp_qr, 4 * nq_all); ENS(ex->d_mp_qmin, 4 * nq_all); ENS(ex->d_mp_qmax, 4 * nq_all); ENS(ex->d_mp_valid, nq_all);
-        ENS(ex->d_mp_keys, 8 * (size_t)kTopK * nq_all); ENS(ex->d_mp_meta, 4 * nq_all);
-        ENS(ex->d_mp_grid, 2 * ((size_t)kGridCells + 1 + 63 + cap) * n);
-        ENS(ex->d_mp_entries, 4 * nq_all);
-        ENS(ex->d_mp_probs, sizeof(WindowProblem) * (size_t)n);
-        ENS(ex->d_mp_res, sizeof(ResolveProblem) * (size_t)n);
-        ENS(ex->d_mp_misc, 256 + sizeof(float) * ex->prm.nlevels);
-#undef ENS
+        ORBX_TRY(ex->d_mp_qr.ensure(4 * nq_all)); ORBX_TRY(ex->d_mp_qmin.ensure(4 * nq_all)); ORBX_TRY(ex->d_mp_qmax.ensure(4 * nq_all)); ORBX_TRY(ex->d_mp_valid.ensure(nq_all));
+        ORBX_TRY(ex->d_mp_keys.ensure(8 * (size_t)kTopK * nq_all)); ORBX_TRY(ex->d_mp_meta.ensure(4 * nq_all));
+        ORBX_TRY(ex->d_mp_grid.ensure(2 * ((size_t)kGridCells + 1 + 63 + cap) * n));
+        ORBX_TRY(ex->d_mp_entries.ensure(4 * nq_all));
+        ORBX_TRY(ex->d_mp_probs.ensure(sizeof(WindowProblem) * (size_t)n));
+        ORBX_TRY(ex->d_mp_res.ensure(sizeof(ResolveProblem) * (size_t)n));
+        ORBX_TRY(ex->d_mp_misc.ensure(256 + sizeof(float) * ex->prm.nlevels));
         std::vector<WindowProblem> P(n);
         std::vector<ResolveProblem> R(n);
         const uint8_t *desc = (const uint8_t *)ex->d_desc.p;
@@ -2384,9 +2367,8 @@ extern "C" int orbx_search_mappoints_batch_device(orbx_extractor *ex, int n_mp, 
         ex->mpkey = key;
     }
     const GridParams g = grid_of(ex->bounds);  // mnMinX.. of the extractor's camera (image rectangle without one, Frame.cc:804-807)
-    const bool side = !ex->profile && ex->side_streams;
-    hipStream_t ms = side ? ex->match_stream : ex->stream;
-    if (side) ORBX_HIP(hipStreamWaitEvent(ms, ex->ev_describe, 0));
+    const hipStream_t ms = stage_stream(ex);
+    ORBX_TRY(stage_begin(ms, {ex}));
     if (n_mp > 0)
         hipLaunchKernelGGL(k_mappoint_windows, dim3((n_mp + 255) / 256, n), dim3(256), 0, ms, n_mp, d_level, d_view_cos, d_in_view,
                            (const float *)((const uint8_t *)ex->d_mp_misc.p + 256), ex->prm.nlevels, th, (float *)ex->d_mp_qr.p,
@@ -2395,10 +2377,7 @@ extern "C" int orbx_search_mappoints_batch_device(orbx_extractor *ex, int n_mp, 
     if (n_mp > 0)
         ORBX_LAUNCH_WINDOW_BEST2(n_mp, n, ms, (const WindowProblem *)ex->d_mp_probs.p, g);
     { const int rr = launch_resolve<false>(n, ms, (const WindowProblem *)ex->d_mp_probs.p, (const ResolveProblem *)ex->d_mp_res.p, g, cap, 0, 4); if (rr != ORBX_OK) return rr; }
-    ORBX_HIP(hipEventRecord(ex->ev_match, ms));
-    ex->match_pending = true; ex->copy_covers_match = false;
-    ORBX_HIP(hipGetLastError());
-    return ORBX_OK;
+    return stage_end(ms, {ex});
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2509,11 +2488,11 @@ extern "C" int orbx_frustum_batch_device(orbx_extractor *ex, const orbx_camera *
         return ORBX_E_BAD_ARG;
     if (n_mp == 0) return ORBX_OK;
     ORBX_HIP(hipSetDevice(ex->device));
-    const bool side = !ex->profile && ex->side_streams;
-    hipStream_t ms = side ? ex->match_stream : ex->stream;
+    // On the stage stream, in front of the map-point search it feeds, but no stage of the protocol: k_in_frustum reads the caller's map points and the
+    // poses uploaded here (ev_frustum guards their pinned ring), nothing of the extraction -- so it neither waits for ev_describe nor records ev_match.
+    const hipStream_t ms = stage_stream(ex);
     if (ex->d_frustum_frames.bytes < sizeof(FrustumFrame) * (size_t)n_frames) ORBX_HIP(hipStreamSynchronize(ms));
-    int r = ex->d_frustum_frames.ensure(sizeof(FrustumFrame) * (size_t)n_frames);
-    if (r != ORBX_OK) return r;
+    ORBX_TRY(ex->d_frustum_frames.ensure(sizeof(FrustumFrame) * (size_t)n_frames));
     const float *b = bounds4 ? bounds4 : ex->bounds;
     if (!bounds4 && ex->width <= 0) return ORBX_E_BAD_ARG;
     const float log_sf = logf((float)(double)ex->prm.scale_factor);   // Frame::mfLogScaleFactor = log(mfScaleFactor) (Frame.cc:120)
@@ -2554,39 +2533,33 @@ extern "C" int orbx_stereo_batch_device(orbx_extractor *L, orbx_extractor *R, fl
         return ORBX_E_BAD_ARG;
     ORBX_HIP(hipSetDevice(L->device));
     const int n = L->last_batch, capL = L->cap, nl = L->prm.nlevels;
-    int r;
-#define ENS(buf, bytes) if ((r = (buf).ensure(bytes)) != ORBX_OK) return r
-    ENS(L->d_st_bidx, 4 * (size_t)capL * L->batch_cap);
-    ENS(L->d_st_bdist, 4 * (size_t)capL * L->batch_cap);
-    ENS(L->d_st_ur, 4 * (size_t)capL * L->batch_cap);
-    ENS(L->d_st_depth, 4 * (size_t)capL * L->batch_cap);
-    ENS(L->d_st_sad, 4 * (size_t)capL * L->batch_cap);
-    ENS(L->d_st_nm, 4 * (size_t)L->batch_cap);
-    ENS(L->d_st_scales, sizeof(float) * 2 * nl);
+    ORBX_TRY(L->d_st_bidx.ensure(4 * (size_t)capL * L->batch_cap));
+    ORBX_TRY(L->d_st_bdist.ensure(4 * (size_t)capL * L->batch_cap));
+    ORBX_TRY(L->d_st_ur.ensure(4 * (size_t)capL * L->batch_cap));
+    ORBX_TRY(L->d_st_depth.ensure(4 * (size_t)capL * L->batch_cap));
+    ORBX_TRY(L->d_st_sad.ensure(4 * (size_t)capL * L->batch_cap));
+    ORBX_TRY(L->d_st_nm.ensure(4 * (size_t)L->batch_cap));
+    ORBX_TRY(L->d_st_scales.ensure(sizeof(float) * 2 * nl));
     StereoBatch S;
     stereo_index_params(S, L->height, L->scale.data(), nl);
-    ENS(L->d_st_rowptr, 4 * ((size_t)S.n_buckets + 1) * L->batch_cap);
-    ENS(L->d_st_rowidx, 16 * (size_t)R->cap * L->batch_cap);
-#undef ENS
+    ORBX_TRY(L->d_st_rowptr.ensure(4 * ((size_t)S.n_buckets + 1) * L->batch_cap));
+    ORBX_TRY(L->d_st_rowidx.ensure(16 * (size_t)R->cap * L->batch_cap));
     // From now on both extractors alternate between two pyramid slabs: these kernels run on the left extractor's MATCH stream beside the next
     // pair of extractions, and k_stereo_sad reads the pyramids of THIS pair.  (The slab written next is the one the stereo stage before this
     // one read: every extraction waits for the rig's previous stereo stage before its k_finalize -- match_pending -- and the one after it
     // follows on the same stream.)
     for (orbx_extractor *e : {L, R}) {
         // a pair extracted before the rig existed may have read its level 0 in place: the SAD stage needs the padded level in the slab
-        if ((r = orbx_materialize_level0(e)) != ORBX_OK) return r;
+        ORBX_TRY(orbx_materialize_level0(e));
         if (!e->pyr_double) {
-            if ((r = e->d_pyr2.ensure(e->d_pyr.bytes)) != ORBX_OK) return r;
+            ORBX_TRY(e->d_pyr2.ensure(e->d_pyr.bytes));
             e->pyr_double = true;   // pyr_slot stays: the current batch lies in the slab it was extracted into
         }
     }
-    const bool side = !L->profile && L->side_streams;
-    hipStream_t st = side ? L->match_stream : L->stream;
+    const hipStream_t st = stage_stream(L);
     ORBX_HIP(hipMemcpyAsync(L->d_st_scales.p, L->scale.data(), sizeof(float) * nl, hipMemcpyHostToDevice, st));
     ORBX_HIP(hipMemcpyAsync((float *)L->d_st_scales.p + nl, L->inv_scale.data(), sizeof(float) * nl, hipMemcpyHostToDevice, st));
-    ORBX_HIP(hipStreamWaitEvent(st, L->ev_describe, 0));  // the two extractions of this batch
-    ORBX_HIP(hipStreamWaitEvent(st, R->ev_describe, 0));
-    if (L->stereo_copy_issued) ORBX_HIP(hipStreamWaitEvent(st, L->ev_stereo_copy[(L->stereo_copy_issued - 1) & 1], 0));  // the previous results may still be on their way to the host
+    ORBX_TRY(stage_begin(st, {L, R}, true));
     S.kl = (const orbx_keypoint *)L->d_kps.p; S.kr = (const orbx_keypoint *)R->d_kps.p;
     S.dl = (const uint8_t *)L->d_desc.p; S.dr = (const uint8_t *)R->d_desc.p;
     S.nl = (const int32_t *)L->d_count.p; S.nr = (const int32_t *)R->d_count.p;
@@ -2605,68 +2578,38 @@ extern "C" int orbx_stereo_batch_device(orbx_extractor *L, orbx_extractor *R, fl
     hipLaunchKernelGGL(k_stereo_rowband_batch, dim3((capL + 15) / 16, n), dim3(256), 0, st, S);
     hipLaunchKernelGGL(k_stereo_sad, dim3((capL + 15) / 16, n), dim3(256), 0, st, S);
     hipLaunchKernelGGL(k_stereo_reject, dim3(n), dim3(256), 0, st, S);
-    ORBX_HIP(hipGetLastError());
+    ORBX_TRY(stage_end(st, {L, R}));   // the right extractor's next k_finalize waits for it as for a matcher of its own
     L->st_seq = L->batch_seq;   // (orbx_frame_load_stereo_batch: the results are this batch's)
-    // the extractors must not overwrite their outputs / pyramids before these kernels are done
-    ORBX_HIP(hipEventRecord(L->ev_match, st));
-    L->match_pending = true; L->copy_covers_match = false;
-    ORBX_HIP(hipEventRecord(R->ev_match, st));   // the right extractor's next k_finalize waits for it as for a matcher of its own
-    R->match_pending = true; R->copy_covers_match = false;
     return ORBX_OK;
 }
 
-// Frame::ComputeStereoFromRGBD for every frame of a resident batch (k_stereo_from_rgbd): one launch on the extractor's MATCH stream behind the
-// extraction, no host synchronisation.  mvuRight / mvDepth / the count of features with depth land in the rectified stage's result buffers, so the
-// orbx_stereo_batch_download* calls serve both sources.  No pyramid level is read: level 0 is not materialised and the extractor keeps its single slab.
+// Frame::ComputeStereoFromRGBD for every frame of a resident batch, float depth images (k_stereo_from_rgbd): rgbd_stage, extractor_state.h
 extern "C" int orbx_rgbd_batch_device(orbx_extractor *ex, const float *d_depth, size_t pitch_bytes, size_t frame_stride_bytes, float bf) {
     RoctxRange rr("orbx:rgbd");
     if (!ex || !d_depth || ex->last_batch <= 0 || ex->width <= 0 || pitch_bytes < 4 * (size_t)ex->width || !(bf > 0.f)) return ORBX_E_BAD_ARG;
     // every row of every image must be a row of aligned floats
     if (((uintptr_t)d_depth | pitch_bytes | frame_stride_bytes) & 3u) return ORBX_E_BAD_ARG;
-    ORBX_HIP(hipSetDevice(ex->device));
-    const int n = ex->last_batch;
-    int r;
-    for (DevBuf *b : {&ex->d_st_ur, &ex->d_st_depth})
-        if ((r = b->ensure(4 * (size_t)ex->cap * ex->batch_cap)) != ORBX_OK) return r;
-    if ((r = ex->d_st_nm.ensure(4 * (size_t)ex->batch_cap)) != ORBX_OK) return r;
-    const bool side = !ex->profile && ex->side_streams;
-    hipStream_t st = side ? ex->match_stream : ex->stream;
-    ORBX_HIP(hipStreamWaitEvent(st, ex->ev_describe, 0));   // the extraction of this batch (its k_undistort included)
-    if (ex->stereo_copy_issued) ORBX_HIP(hipStreamWaitEvent(st, ex->ev_stereo_copy[(ex->stereo_copy_issued - 1) & 1], 0));  // the previous results may still be on their way to the host
-    RgbdStage S;
-    S.kps = (const orbx_keypoint *)ex->d_kps.p; S.kps_un = (const orbx_keypoint *)ex->match_kps();
-    S.count = (const int32_t *)ex->d_count.p;
-    S.depth = (const uint8_t *)d_depth; S.pitch = pitch_bytes; S.frame_stride = frame_stride_bytes;
-    S.cap = ex->cap; S.width = ex->width; S.height = ex->height; S.bf = bf;
-    S.u_right = (float *)ex->d_st_ur.p; S.out_depth = (float *)ex->d_st_depth.p; S.nmatches = (int32_t *)ex->d_st_nm.p;
-    hipLaunchKernelGGL(k_stereo_from_rgbd, dim3((unsigned)n), dim3(256), 0, st, S);
-    ORBX_HIP(hipGetLastError());
-    ex->st_seq = ex->batch_seq;
-    // the extractor must not overwrite its key points / counts before the kernel is done
-    ORBX_HIP(hipEventRecord(ex->ev_match, st));
-    ex->match_pending = true; ex->copy_covers_match = false;
-    return ORBX_OK;
+    return rgbd_stage(ex, RgbdStage{}, k_stereo_from_rgbd, d_depth, pitch_bytes, frame_stride_bytes, bf);
 }
 
 extern "C" int orbx_stereo_batch_download(orbx_extractor *L, int frame, float *u_right, float *depth, int *n_left, int *n_matches) {
     if (!L || frame < 0 || frame >= L->last_batch || !L->d_st_ur.p) return ORBX_E_BAD_ARG;
     ORBX_HIP(hipSetDevice(L->device));
     ORBX_HIP(hipStreamWaitEvent(L->stream, L->ev_match, 0));   // the stereo stage runs on the match stream
-    const size_t fb = 4 * (size_t)L->cap, o_u = 64, o_d = o_u + ((fb + 63) & ~(size_t)63);
-    int r = L->d2h_staged_begin(o_d + fb);
-    if (r != ORBX_OK) return r;
-    if ((r = L->d2h_staged(0, (int32_t *)L->d_count.p + frame, 4)) != ORBX_OK) return r;
-    if ((r = L->d2h_staged(4, (int32_t *)L->d_st_nm.p + frame, 4)) != ORBX_OK) return r;
-    if ((r = L->d2h_staged(o_u, (float *)L->d_st_ur.p + (size_t)frame * L->cap, fb)) != ORBX_OK) return r;
-    if ((r = L->d2h_staged(o_d, (float *)L->d_st_depth.p + (size_t)frame * L->cap, fb)) != ORBX_OK) return r;
-    ORBX_HIP(hipStreamSynchronize(L->stream));
-    int32_t h[2];
-    memcpy(h, L->staged(0), 8);
-    if (n_left) *n_left = h[0];
-    if (n_matches) *n_matches = h[1];
-    const int nlv = std::min(std::max(h[0], 0), L->cap);
-    if (u_right) memcpy(u_right, L->staged(o_u), 4 * (size_t)nlv);
-    if (depth) memcpy(depth, L->staged(o_d), 4 * (size_t)nlv);
+    const size_t fb = 4 * (size_t)L->cap;
+    const int32_t *count = nullptr, *nm = nullptr;
+    const float *ur = nullptr, *dp = nullptr;
+    ORBX_TRY(L->download([&](Staged &S) {
+        count = S.view<int32_t>((int32_t *)L->d_count.p + frame, 4);
+        nm = S.view<int32_t>((int32_t *)L->d_st_nm.p + frame, 4);
+        ur = S.view<float>((float *)L->d_st_ur.p + (size_t)frame * L->cap, fb);
+        dp = S.view<float>((float *)L->d_st_depth.p + (size_t)frame * L->cap, fb);
+    }));
+    if (n_left) *n_left = *count;
+    if (n_matches) *n_matches = *nm;
+    const int nlv = std::min(std::max(*count, 0), L->cap);   // the rows are the frame's capacity on the device, the caller's arrays its count
+    if (u_right) memcpy(u_right, ur, 4 * (size_t)nlv);
+    if (depth) memcpy(depth, dp, 4 * (size_t)nlv);
     return ORBX_OK;
 }
 
@@ -2677,17 +2620,12 @@ extern "C" int orbx_stereo_batch_download_all(orbx_extractor *L, float *u_right,
     if (!L || L->last_batch <= 0 || !L->d_st_ur.p) return ORBX_E_BAD_ARG;
     ORBX_HIP(hipSetDevice(L->device));
     ORBX_HIP(hipStreamWaitEvent(L->stream, L->ev_match, 0));   // the stereo stage runs on the match stream
-    const size_t n = (size_t)L->last_batch, fb = 4 * n * L->cap, o_d = (fb + 63) & ~(size_t)63, o_n = 2 * o_d;
-    int r = L->d2h_staged_begin(o_n + 4 * n);
-    if (r != ORBX_OK) return r;
-    if (u_right && (r = L->d2h_staged(0, L->d_st_ur.p, fb)) != ORBX_OK) return r;
-    if (depth && (r = L->d2h_staged(o_d, L->d_st_depth.p, fb)) != ORBX_OK) return r;
-    if (n_matches && (r = L->d2h_staged(o_n, L->d_st_nm.p, 4 * n)) != ORBX_OK) return r;
-    ORBX_HIP(hipStreamSynchronize(L->stream));
-    if (u_right) memcpy(u_right, L->staged(0), fb);
-    if (depth) memcpy(depth, L->staged(o_d), fb);
-    if (n_matches) memcpy(n_matches, L->staged(o_n), 4 * n);
-    return ORBX_OK;
+    const size_t n = (size_t)L->last_batch, fb = 4 * n * L->cap;
+    return L->download([&](Staged &S) {
+        S.out(u_right, L->d_st_ur.p, fb);
+        S.out(depth, L->d_st_depth.p, fb);
+        S.out(n_matches, L->d_st_nm.p, 4 * n);
+    });
 }
 
 // the same into PINNED host buffers, asynchronously on the left extractor's copy stream behind the stereo kernels: the pipelined form
@@ -2696,14 +2634,8 @@ extern "C" int orbx_stereo_batch_download_all(orbx_extractor *L, float *u_right,
 extern "C" int orbx_stereo_batch_download_async(orbx_extractor *L, float *u_right, float *depth, int32_t *n_matches) {
     if (!L || L->last_batch <= 0 || !L->d_st_ur.p) return ORBX_E_BAD_ARG;
     if (L->stereo_copy_issued - L->stereo_copy_waited >= 2) { set_error("two stereo downloads already in flight: call orbx_stereo_download_wait first"); return ORBX_E_BAD_ARG; }
-    for (const void *p : {(const void *)u_right, (const void *)depth, (const void *)n_matches}) {
-        hipPointerAttribute_t a;
-        if (p && (hipPointerGetAttributes(&a, p) != hipSuccess || a.type != hipMemoryTypeHost)) {
-            (void)hipGetLastError();
-            set_error("orbx_stereo_batch_download_async needs pinned host buffers (hipHostMalloc / hipHostRegister)");
-            return ORBX_E_BAD_ARG;
-        }
-    }
+    for (const void *p : {(const void *)u_right, (const void *)depth, (const void *)n_matches})
+        if (!is_pinned_host(p)) { set_error("orbx_stereo_batch_download_async needs pinned host buffers (hipHostMalloc / hipHostRegister)"); return ORBX_E_BAD_ARG; }
     ORBX_HIP(hipSetDevice(L->device));
     for (hipEvent_t &ev : L->ev_stereo_copy) if (!ev) ORBX_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
     const size_t n = (size_t)L->last_batch, fb = 4 * n * L->cap;
@@ -2740,22 +2672,17 @@ extern "C" int orbx_stereo_fisheye_batch_device(orbx_extractor *L, orbx_extracto
     const int n = L->last_batch, capL = L->cap, capR = R->cap, nl = L->prm.nlevels;
     const size_t NL = (size_t)n * capL, NR = (size_t)n * capR;
     if (NR + 4 * (size_t)n > (size_t)INT_MAX || nl > kMaxLevels || (int)L->sigma2.size() < nl) return ORBX_E_BAD_ARG;
-    int r;
-#define ENS(buf, bytes) if ((r = (buf).ensure(bytes)) != ORBX_OK) return r
-    ENS(L->d_sf_idx, 8 * NL);
-    ENS(L->d_sf_dist, 8 * NL);
-    ENS(L->d_sf_l2r, 4 * NL);
-    ENS(L->d_sf_depth, 4 * NL);
-    ENS(L->d_sf_p3d, 12 * NL);
-    ENS(L->d_sf_r2l, 4 * NR);
-    ENS(L->d_sf_cnt, 16 * (size_t)n);
-    ENS(L->d_sf_sigma, sizeof(float) * kMaxLevels);
-    ENS(L->d_sf_rig, sizeof(orbx_kb8_rig));
-#undef ENS
-    const bool side = !L->profile && L->side_streams;
-    hipStream_t st = side ? L->match_stream : L->stream;
-    ORBX_HIP(hipStreamWaitEvent(st, L->ev_describe, 0));  // the two extractions of this batch (the downloads of these results are synchronous: none in flight)
-    ORBX_HIP(hipStreamWaitEvent(st, R->ev_describe, 0));
+    ORBX_TRY(L->d_sf_idx.ensure(8 * NL));
+    ORBX_TRY(L->d_sf_dist.ensure(8 * NL));
+    ORBX_TRY(L->d_sf_l2r.ensure(4 * NL));
+    ORBX_TRY(L->d_sf_depth.ensure(4 * NL));
+    ORBX_TRY(L->d_sf_p3d.ensure(12 * NL));
+    ORBX_TRY(L->d_sf_r2l.ensure(4 * NR));
+    ORBX_TRY(L->d_sf_cnt.ensure(16 * (size_t)n));
+    ORBX_TRY(L->d_sf_sigma.ensure(sizeof(float) * kMaxLevels));
+    ORBX_TRY(L->d_sf_rig.ensure(sizeof(orbx_kb8_rig)));
+    const hipStream_t st = stage_stream(L);
+    ORBX_TRY(stage_begin(st, {L, R}));   // (the downloads of these results are synchronous: none in flight)
     FisheyeStereoInit I;
     memset(&I, 0, sizeof(I));
     I.rig = *rig;
@@ -2785,12 +2712,7 @@ extern "C" int orbx_stereo_fisheye_batch_device(orbx_extractor *L, orbx_extracto
     L->sf_seq_l = L->batch_seq; L->sf_seq_r = R->batch_seq; L->sf_right = R;
     if (!L->ev_sf) ORBX_HIP(hipEventCreateWithFlags(&L->ev_sf, hipEventDisableTiming));
     ORBX_HIP(hipEventRecord(L->ev_sf, st));   // (orbx_frame_load_stereo_fisheye_batch waits for it)
-    // the extractors must not overwrite their keypoints / descriptors / counts before these kernels are done
-    ORBX_HIP(hipEventRecord(L->ev_match, st));
-    L->match_pending = true; L->copy_covers_match = false;
-    ORBX_HIP(hipEventRecord(R->ev_match, st));   // the right extractor's next k_finalize waits for it as for a matcher of its own
-    R->match_pending = true; R->copy_covers_match = false;
-    return ORBX_OK;
+    return stage_end(st, {L, R});
 }
 
 // one frame of the last fisheye stereo stage: l2r / depth [n_left], p3d [n_left][3], r2l [n_right] (any output may be NULL); synchronous
@@ -2800,27 +2722,24 @@ extern "C" int orbx_stereo_fisheye_batch_download(orbx_extractor *L, int frame, 
     ORBX_HIP(hipSetDevice(L->device));
     ORBX_HIP(hipStreamWaitEvent(L->stream, L->ev_match, 0));   // the stage runs on the match stream
     const size_t cl = (size_t)L->sf_capL, cr = (size_t)L->sf_capR, f = (size_t)frame;
-    auto al = [](size_t b) { return (b + 63) & ~(size_t)63; };
-    const size_t o_l = 64, o_d = o_l + al(4 * cl), o_p = o_d + al(4 * cl), o_r = o_p + al(12 * cl);
-    int r = L->d2h_staged_begin(o_r + al(4 * cr));
-    if (r != ORBX_OK) return r;
-    if ((r = L->d2h_staged(0, (int32_t *)L->d_sf_cnt.p + 4 * f, 16)) != ORBX_OK) return r;
-    if (l2r && (r = L->d2h_staged(o_l, (int32_t *)L->d_sf_l2r.p + f * cl, 4 * cl)) != ORBX_OK) return r;
-    if (depth && (r = L->d2h_staged(o_d, (float *)L->d_sf_depth.p + f * cl, 4 * cl)) != ORBX_OK) return r;
-    if (p3d && (r = L->d2h_staged(o_p, (float *)L->d_sf_p3d.p + 3 * f * cl, 12 * cl)) != ORBX_OK) return r;
-    if (r2l && (r = L->d2h_staged(o_r, (int32_t *)L->d_sf_r2l.p + f * cr, 4 * cr)) != ORBX_OK) return r;
-    ORBX_HIP(hipStreamSynchronize(L->stream));
-    int32_t h[4];
-    memcpy(h, L->staged(0), 16);
+    const int32_t *h = nullptr, *h_l2r = nullptr, *h_r2l = nullptr;   // h: nMatches, descMatches, n_left, n_right
+    const float *h_depth = nullptr, *h_p3d = nullptr;
+    ORBX_TRY(L->download([&](Staged &S) {   // the rows are the frame's capacities on the device, the caller's arrays its counts: clamped below
+        h = S.view<int32_t>((int32_t *)L->d_sf_cnt.p + 4 * f, 16);
+        if (l2r) h_l2r = S.view<int32_t>((int32_t *)L->d_sf_l2r.p + f * cl, 4 * cl);
+        if (depth) h_depth = S.view<float>((float *)L->d_sf_depth.p + f * cl, 4 * cl);
+        if (p3d) h_p3d = S.view<float>((float *)L->d_sf_p3d.p + 3 * f * cl, 12 * cl);
+        if (r2l) h_r2l = S.view<int32_t>((int32_t *)L->d_sf_r2l.p + f * cr, 4 * cr);
+    }));
     const size_t nlv = (size_t)std::min(std::max(h[2], 0), L->sf_capL), nrv = (size_t)std::min(std::max(h[3], 0), L->sf_capR);
     if (n_matches) *n_matches = h[0];
     if (desc_matches) *desc_matches = h[1];
     if (n_left) *n_left = (int)nlv;
     if (n_right) *n_right = (int)nrv;
-    if (l2r) memcpy(l2r, L->staged(o_l), 4 * nlv);
-    if (depth) memcpy(depth, L->staged(o_d), 4 * nlv);
-    if (p3d) memcpy(p3d, L->staged(o_p), 12 * nlv);
-    if (r2l) memcpy(r2l, L->staged(o_r), 4 * nrv);
+    if (l2r) memcpy(l2r, h_l2r, 4 * nlv);
+    if (depth) memcpy(depth, h_depth, 4 * nlv);
+    if (p3d) memcpy(p3d, h_p3d, 12 * nlv);
+    if (r2l) memcpy(r2l, h_r2l, 4 * nrv);
     return ORBX_OK;
 }
 
@@ -2832,25 +2751,18 @@ extern "C" int orbx_stereo_fisheye_batch_download_all(orbx_extractor *L, int32_t
     ORBX_HIP(hipSetDevice(L->device));
     ORBX_HIP(hipStreamWaitEvent(L->stream, L->ev_match, 0));
     const size_t n = (size_t)L->sf_batch, bl = 4 * n * L->sf_capL, br = 4 * n * L->sf_capR;
-    auto al = [](size_t b) { return (b + 63) & ~(size_t)63; };
-    const size_t o_d = al(16 * n), o_l = o_d + al(bl), o_p = o_l + al(bl), o_r = o_p + al(3 * bl);
-    int r = L->d2h_staged_begin(o_r + al(br));
-    if (r != ORBX_OK) return r;
-    if ((n_matches || desc_matches) && (r = L->d2h_staged(0, L->d_sf_cnt.p, 16 * n)) != ORBX_OK) return r;
-    if (depth && (r = L->d2h_staged(o_d, L->d_sf_depth.p, bl)) != ORBX_OK) return r;
-    if (l2r && (r = L->d2h_staged(o_l, L->d_sf_l2r.p, bl)) != ORBX_OK) return r;
-    if (p3d && (r = L->d2h_staged(o_p, L->d_sf_p3d.p, 3 * bl)) != ORBX_OK) return r;
-    if (r2l && (r = L->d2h_staged(o_r, L->d_sf_r2l.p, br)) != ORBX_OK) return r;
-    ORBX_HIP(hipStreamSynchronize(L->stream));
-    const int32_t *c = (const int32_t *)L->staged(0);
+    const int32_t *c = nullptr;   // [n][4]: nMatches, descMatches, n_left, n_right
+    ORBX_TRY(L->download([&](Staged &S) {
+        if (n_matches || desc_matches) c = S.view<int32_t>(L->d_sf_cnt.p, 16 * n);
+        S.out(depth, L->d_sf_depth.p, bl);
+        S.out(l2r, L->d_sf_l2r.p, bl);
+        S.out(p3d, L->d_sf_p3d.p, 3 * bl);
+        S.out(r2l, L->d_sf_r2l.p, br);
+    }));
     for (size_t f = 0; f < n; f++) {
         if (n_matches) n_matches[f] = c[4 * f];
         if (desc_matches) desc_matches[f] = c[4 * f + 1];
     }
-    if (depth) memcpy(depth, L->staged(o_d), bl);
-    if (l2r) memcpy(l2r, L->staged(o_l), bl);
-    if (p3d) memcpy(p3d, L->staged(o_p), 3 * bl);
-    if (r2l) memcpy(r2l, L->staged(o_r), br);
     return ORBX_OK;
 }
 
